@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py -- the headline measurement of this repo (driver contract).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--full] [--dump-outputs DIR]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
 
 Headline (the fields the driver reads; BASELINE.json configs[1], the configuration the metric is quoted on):
@@ -14,12 +14,15 @@ Headline (the fields the driver reads; BASELINE.json configs[1], the configurati
     Infinity Cache -- the reference's own benchmark reuses a single buffer
     (tools/benchmarks/matmul/rocm/matmul_petit.cc:116-132), which on MI355X would measure the
     cache, not HBM.
-    The K steps are one HIP-graph replay, bracketed by barrier + synchronize on both sides as the
-    contract asks; that bracketed region is repeated `--repeats` times (default 11) and the MEDIAN is
-    reported, so a short run (--steps 20 = 0.17 ms) is not a single sample.
+    The K timed steps are replays of captured HIP graphs (one graph of K steps; above GRAPH_MAX_STEPS, graphs of a
+    whole number of weight rotations, so that capture does not grow with K), run once and bracketed by barrier +
+    synchronize on both sides as the contract asks; ms_per_step = that region's device time / K.  `--repeats R`
+    times R such regions and reports the median.
+    --dump-outputs DIR writes what the last timed step returned (C, as float32) to DIR/c.npy; the inputs depend
+    on the arguments only, so two builds can be compared output for output.
 
 The rest of the metric ("TFLOPS + achieved HBM GB/s, M in {1,8,16,512}, Llama-70B shapes") is in `cells`
-(rank 0, N = 1 only; the list is tools/benchlib.py bench_cell_plan(), shared with tests/test_gpu_parity.py::
+(--full only, as are `host_us_per_call` and `cpu_baseline`; rank 0, N = 1 only; the list is tools/benchlib.py bench_cell_plan(), shared with tests/test_gpu_parity.py::
 test_bench_cells_parity so that every timed cell is also checked against the oracle): for qkv / o / gate_up / down,
 bf16 x NVFP4 at M in {1, 4, 8, 16, 512}, fp16 x NVFP4 (the reference benchmark's default dtype, tools/benchmarks/matmul.py:92-127)
 at M in {16, 512}, fp16 x MXFP4 (BASELINE configs[3]) at M in {1, 16}, bf16 x MXFP4 at M = 512 -- all through solution_id = -1 --
@@ -53,6 +56,7 @@ import torch
 import torch.distributed as dist
 
 HBM_PEAK_GBS = 8000.0          # MI355X HBM3E spec (MI355X_MICROARCH.md); ~6300 achievable
+GRAPH_MAX_STEPS = 1000         # steps per captured graph: capture time and graph memory stay flat however long --steps is
 M, N, K = 1, 8192, 8192
 GROUP = 16
 
@@ -259,11 +263,16 @@ def main() -> None:
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=1000)
     ap.add_argument("--warmup", type=int, default=1000)
-    ap.add_argument("--repeats", type=int, default=11, help="timed K-step regions; the median is reported")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what the headline does not need: the eager host cost per call, the M x shape cell table "
+                         "(a child process, minutes) and the CPU baseline")
+    ap.add_argument("--dump-outputs", metavar="DIR", default="",
+                    help="after the timed steps, write what the last step returned to DIR/c.npy (float32)")
+    ap.add_argument("--repeats", type=int, default=1, help="timed K-step regions; the median is reported")
     ap.add_argument("--no-graph", action="store_true", help="launch eagerly instead of replaying a HIP graph")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-cells", action="store_true", help="headline only (skip the M x shape table)")
-    ap.add_argument("--no-host-overhead", action="store_true", help="skip the eager host-cost measurement (profiling runs)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
+    ap.add_argument("--no-cells", action="store_true", help="with --full: skip the M x shape table")
+    ap.add_argument("--no-host-overhead", action="store_true", help="with --full: skip the eager host-cost measurement")
     ap.add_argument("--cells-budget-s", type=float, default=420.0)
     ap.add_argument("--verbose", action="store_true", help="one stderr line per cell (the kernel each call resolved to)")
     ap.add_argument("--cells-child", default="", help=argparse.SUPPRESS)   # internal: run the cell table, append JSON lines to this file
@@ -329,30 +338,48 @@ def main() -> None:
     stream = torch.cuda.Stream(dev)
     warmup_done = 0
     region_ms, region_wall_ms = [], []
+    # the K steps as graphs of at most GRAPH_MAX_STEPS steps; a longer run replays graphs of a whole number of weight
+    # rotations (plus one for the rest), so that every step reads the copy it would in one graph of K steps
+    chunk = args.steps if args.steps <= GRAPH_MAX_STEPS else copies * max(1, GRAPH_MAX_STEPS // copies)
+    plan = [chunk] * (args.steps // chunk) + ([args.steps % chunk] if args.steps % chunk else [])
     with torch.cuda.stream(stream):
         out = step(0)                              # first call: module load, arch table
         stream.synchronize()
-        graph = None
+        graphs = {}                                # steps -> (graph, the output of its last step)
         if not args.no_graph:
             try:
-                graph = torch.cuda.CUDAGraph()
-                with torch.cuda.graph(graph, stream=stream):
-                    for i in range(args.steps):
-                        out = step(i)
+                for n_steps in sorted(set(plan), reverse=True):
+                    graph = torch.cuda.CUDAGraph()
+                    with torch.cuda.graph(graph, stream=stream):
+                        for i in range(n_steps):
+                            out = step(i)
+                    graphs[n_steps] = (graph, out)
             except Exception as exc:               # capture unsupported: time eager launches
                 print(f"[bench] graph capture failed ({exc}); timing eager launches", file=sys.stderr)
-                graph = None
+                graphs = {}
+
+        def timed_steps():
+            """exactly args.steps steps; returns the last one's output"""
+            if graphs:
+                for n_steps in plan:
+                    graphs[n_steps][0].replay()
+                return graphs[plan[-1]][1]
+            for i in range(args.steps):
+                o = step(i)
+            return o
+
         # untimed warm-up: the same steps, so clocks and caches are in steady state: --warmup steps, and at least
         # ~20 ms of them (measured on MI355X: a 400-step replay timed after only 400 warm-up steps reads 10.4 us/step,
         # after 2000 warm-up steps 9.2 -- DVFS ramp)
         t_w = time.perf_counter()
         while warmup_done < args.warmup or time.perf_counter() - t_w < 0.03:
-            if graph is not None:
-                graph.replay()
+            if graphs:
+                graphs[plan[0]][0].replay()
+                warmup_done += plan[0]
             else:
                 for i in range(args.steps):
                     out = step(i)
-            warmup_done += args.steps
+                warmup_done += args.steps
             stream.synchronize()
 
         # events are recorded on the stream the kernels run on; every timed region is exactly --steps steps,
@@ -364,11 +391,7 @@ def main() -> None:
             torch.cuda.synchronize()
             t0 = time.perf_counter()
             e0.record(stream)
-            if graph is not None:
-                graph.replay()                         # exactly args.steps steps
-            else:
-                for i in range(args.steps):
-                    out = step(i)
+            out = timed_steps()
             e1.record(stream)
             torch.cuda.synchronize()
             wall = time.perf_counter() - t0
@@ -386,6 +409,10 @@ def main() -> None:
 
     # sanity: the timed kernel really computes the GEMM (checked against the oracle in smoke()/tests)
     assert out.shape == (M, N) and torch.isfinite(out.float()).all()
+    if args.dump_outputs and rank == 0:
+        dump = Path(args.dump_outputs)
+        dump.mkdir(parents=True, exist_ok=True)
+        np.save(dump / "c.npy", out.float().cpu().numpy())      # bf16 -> f32 is exact
 
     if rank == 0:
         # HBM bytes per launch from the PMC passes of the same command (tools/collect_profiles.sh,
@@ -417,9 +444,9 @@ def main() -> None:
             "data": "synthetic",
             "config": {"workload": "M=1 N=8192 K=8192 bf16 x nvfp4 (e4m3 scales, g=16), one mul_nvfp4_a16 call per step",
                        "weights_rotated_over_copies": copies, "parallelism": f"replicas x{world} (no data-path collective)",
-                       "launch": "hip graph replay" if graph is not None else "eager",
+                       "launch": f"hip graph replay ({len(plan)} replays per region)" if graphs else "eager",
                        "solution": f"0x{sid:x} {_lib.describe_solution(sid)}",
-                       "timed_regions": len(region_ms), "statistic": "median region",
+                       "timed_regions": len(region_ms), "statistic": "median region" if len(region_ms) > 1 else "one region",
                        "warmup_steps_run": warmup_done},
             "tflops": 2.0 * M * N * K / (ms_per_step * 1e-3) / 1e12 * world,
             "wall_ms_per_step": wall_ms_max / args.steps,
@@ -439,7 +466,7 @@ def main() -> None:
             },
         }
         print(f"[bench] headline {ms_per_step * 1e3:.3f} us/step", file=sys.stderr, flush=True)
-        if world == 1 and not args.no_host_overhead:
+        if world == 1 and args.full and not args.no_host_overhead:
             # eager host cost per call of the two operator layers, on a TINY problem (M=1, N=256, K=1024: a ~2 us kernel), so
             # that the host -- not the GPU -- is what the loop waits for (under graph replay, above, the host is out of the loop)
             from petit_kernel import compiled, ops
@@ -460,7 +487,7 @@ def main() -> None:
         del packed
         torch.cuda.empty_cache()
         full_cells = None
-        if world == 1 and not args.no_cells:
+        if world == 1 and args.full and not args.no_cells:
             # the table runs in a CHILD process that reports every finished cell at once: a fault in any one kernel (or in
             # the vendor comparator) costs that cell, never the headline line or the cells already measured
             import subprocess
@@ -489,7 +516,7 @@ def main() -> None:
                     side.write_text(json.dumps({"steps": args.steps, "cells": cells}, indent=0))
                 except OSError:
                     pass
-        if world == 1 and not args.no_cpu_baseline:
+        if world == 1 and args.full and not args.no_cpu_baseline:
             line["cpu_baseline"] = cpu_baseline(a, gs, qs[0], ss[0])
         if full_cells is not None:
             line.update(compact_cells(full_cells))   # LAST: the metric's own cells end the line

@@ -61,7 +61,8 @@ def build(force: bool = False, jobs: int | None = None) -> Path:
     LIB.parent.mkdir(exist_ok=True)
     hdr = deps_mtime()
     srcs = sources()
-    jobs = jobs or min(len(srcs), os.cpu_count() or 4)
+    # $MAX_JOBS, else the CPUs this process may run on (os.cpu_count() counts the whole machine)
+    jobs = jobs or min(len(srcs), int(os.environ.get("MAX_JOBS") or len(os.sched_getaffinity(0))))
     for stale in OBJ.glob("*.o"):  # objects of translation units that no longer exist
         if not (CSRC / (stale.stem + ".hip")).exists():
             stale.unlink()

@@ -24,9 +24,16 @@ What is pinned
   * dequant_tables.npz -- 16 fp4 codes x 126 positive e4m3 scales and
     16 codes x e8m0 1..237 (quantization_utils_fp4_test.cc:246-278,344-365),
     values from the reference's LUT * torch's float8 decodes.
+  * reference_floats.npz -- the reference's software floats
+    (lib/tests/floating_points.h, through oracle/ref_shim.cc): every e4m3 / e5m2
+    byte -> f32, every positive finite e4m3 -> e5m3, and 50000 sampled f32 bit
+    patterns (numpy seed 11) -> bf16 / fp16 bits.
+  * reference_matmul_problems.npz -- the (m, n, k) list of the reference's
+    benchmark (tools/benchmarks/matmul.py:8-117), in its order.
 """
 import hashlib
 import importlib.util
+import re
 import sys
 import types
 from pathlib import Path
@@ -118,6 +125,29 @@ def tables():
                 mx=np.outer(lut, e8).astype(np.float32))    # [16, 237]
 
 
+def reference_floats():
+    sys.path.insert(0, str(OUT.parents[1]))
+    from oracle import oracle as O
+    O.build()
+    R = O.ref_lib()
+    assert R is not None, "oracle/_ref was not built"
+    e4m3 = np.array([R.ref_e4m3_to_f32(i) for i in range(256)], dtype=np.float32)
+    e5m2 = np.array([R.ref_e5m2_to_f32(i) for i in range(256)], dtype=np.float32)
+    e5m3 = np.array([R.ref_e4m3_to_e5m3(i) for i in range(1, 0x7F)], dtype=np.uint8)      # e4m3 bytes 1..126
+    rng = np.random.default_rng(11)
+    f32 = rng.integers(0, 2 ** 32, 50000, dtype=np.uint64).astype(np.uint32)
+    finite = f32.view(np.float32)[~np.isnan(f32.view(np.float32))]
+    bf16 = np.array([R.ref_f32_to_bf16(float(v)) for v in finite], dtype=np.uint16)
+    f16 = np.array([R.ref_f32_to_f16(float(v)) for v in finite], dtype=np.uint16)
+    return dict(e4m3_to_f32=e4m3, e5m2_to_f32=e5m2, e4m3_to_e5m3=e5m3, f32_bits=finite.view(np.uint32), f32_to_bf16=bf16, f32_to_f16=f16)
+
+
+def reference_matmul_problems():
+    text = (REF / "tools/benchmarks/matmul.py").read_text()
+    listed = [tuple(int(x) for x in t) for t in re.findall(r"\((\d+), (\d+), (\d+)\),", text)]
+    return dict(mnk=np.array(listed, dtype=np.int64))
+
+
 def main():
     ref = load_reference_oracle()
     for (m, n, k, seed) in ref.NVFP4_CASES:
@@ -128,6 +158,8 @@ def main():
         np.savez_compressed(OUT / f"mx_{m}_{n}_{k}_{seed}_f16.npz", **mx_case(ref, m, n, k, seed, torch.float16))
     np.savez_compressed(OUT / "config1_nv_1_4096_4096.npz", **config1(ref))
     np.savez_compressed(OUT / "dequant_tables.npz", **tables())
+    np.savez_compressed(OUT / "reference_floats.npz", **reference_floats())
+    np.savez_compressed(OUT / "reference_matmul_problems.npz", **reference_matmul_problems())
     for p in sorted(OUT.glob("*.npz")):
         print(p.name, p.stat().st_size)
 

@@ -144,26 +144,32 @@ def test_scalar_formats_vs_torch():
     assert np.array_equal(O.f32_to_bf16_bits(x), mb)
 
 
-def test_against_reference_floats():
-    """oracle/_ref: the reference's lib/tests/floating_points.h compiled from its tree."""
-    R = O.ref_lib()
-    if R is None:
-        pytest.skip("oracle/_ref not built (no /root/reference on this machine)")
-    L = O.lib()
-    for i in range(256):
-        for mine, ref in ((L.po_e4m3_to_f32(i), R.ref_e4m3_to_f32(i)), (L.po_e5m2_to_f32(i), R.ref_e5m2_to_f32(i))):
-            assert (np.isnan(mine) and np.isnan(ref)) or (mine == ref and np.signbit(mine) == np.signbit(ref))
-    for i in range(1, 0x7F):  # every positive, finite e4m3 (lib/tests/quantization.cc:117-130)
-        assert L.po_e4m3_to_e5m3(i) == R.ref_e4m3_to_e5m3(i)
-        assert L.po_e5m3_to_f32(L.po_e4m3_to_e5m3(i)) == L.po_e4m3_to_f32(i)
+def test_against_reference_floats(golden_dir):
+    """The reference's lib/tests/floating_points.h: its outputs stored in tests/golden/reference_floats.npz (make_golden.py),
+    and, where oracle/_ref was built from the reference's tree, the compiled functions themselves."""
+    g = np.load(golden_dir / "reference_floats.npz")
     rng = np.random.default_rng(11)
     raw = rng.integers(0, 2 ** 32, 50000, dtype=np.uint64).astype(np.uint32).view(np.float32)
-    for v in raw:
+    raw = raw[~np.isnan(raw)]
+    assert np.array_equal(raw.view(np.uint32), g["f32_bits"])
+    R = O.ref_lib()
+    if R is not None:                          # the stored vectors are still what the reference computes
+        assert np.array_equal(g["e4m3_to_f32"].view(np.uint32), np.array([R.ref_e4m3_to_f32(i) for i in range(256)], dtype=np.float32).view(np.uint32))
+        assert np.array_equal(g["e5m2_to_f32"].view(np.uint32), np.array([R.ref_e5m2_to_f32(i) for i in range(256)], dtype=np.float32).view(np.uint32))
+        assert g["e4m3_to_e5m3"].tolist() == [R.ref_e4m3_to_e5m3(i) for i in range(1, 0x7F)]
+        assert g["f32_to_bf16"].tolist() == [R.ref_f32_to_bf16(float(v)) for v in raw]
+        assert g["f32_to_f16"].tolist() == [R.ref_f32_to_f16(float(v)) for v in raw]
+    L = O.lib()
+    for i in range(256):
+        for mine, ref in ((L.po_e4m3_to_f32(i), float(g["e4m3_to_f32"][i])), (L.po_e5m2_to_f32(i), float(g["e5m2_to_f32"][i]))):
+            assert (np.isnan(mine) and np.isnan(ref)) or (mine == ref and np.signbit(mine) == np.signbit(ref))
+    for i in range(1, 0x7F):  # every positive, finite e4m3 (lib/tests/quantization.cc:117-130)
+        assert L.po_e4m3_to_e5m3(i) == g["e4m3_to_e5m3"][i - 1]
+        assert L.po_e5m3_to_f32(L.po_e4m3_to_e5m3(i)) == L.po_e4m3_to_f32(i)
+    for v, b, h in zip(raw, g["f32_to_bf16"], g["f32_to_f16"]):
         v = float(v)
-        if v != v:
-            continue
-        assert L.po_f32_to_bf16(v) == R.ref_f32_to_bf16(v)
-        assert L.po_f32_to_f16(v) == R.ref_f32_to_f16(v)
+        assert L.po_f32_to_bf16(v) == b
+        assert L.po_f32_to_f16(v) == h
 
 
 def test_petit_format_truth_table():

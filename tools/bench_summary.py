@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""tools/bench_summary.py <bench.json> [<bench_steps20.json>] -- the cell tables of profiles/rNN_summary.md from a bench.py line (stdout: markdown)."""
+"""tools/bench_summary.py <bench.json> [<bench_steps20.json>] -- the cell tables of profiles/rNN_summary.md from a `bench.py --full` line (stdout: markdown)."""
 import json
 import sys
 
