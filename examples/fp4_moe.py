@@ -1,0 +1,56 @@
+#!/usr/bin/env python3
+"""examples/fp4_moe.py -- an NVFP4 mixture-of-experts layer (E = 8 experts, top-2) the way a serving stack runs it: the experts' weights
+stacked and packed once at load time, then one `fp4_moe` call per forward (two MoE launches: gate_up with fused SiLU-mul, down).
+Checks against the same layer in torch on the dequantised weights.  Needs an MI355X.
+
+    python examples/fp4_moe.py
+"""
+import sys
+from pathlib import Path
+
+import torch
+
+sys.path.insert(0, str(Path(__file__).resolve().parent.parent / "petit-kernel_amd"))
+import petit_kernel  # noqa: E402
+
+
+def random_nvfp4(rows, cols, g):
+    q = torch.randint(0, 256, (rows, cols // 2), dtype=torch.uint8, generator=g)
+    s = (torch.rand(rows, cols // 16, generator=g) * 3.5 + 0.25).to(torch.float8_e4m3fn)
+    return q, s
+
+
+def main():
+    dev = "cuda"
+    E, topk, H, I, T = 8, 2, 1024, 512, 32
+    g = torch.Generator().manual_seed(0)
+    q13, s13 = random_nvfp4(E * 2 * I, H, g)          # [gate; up] of every expert, stacked along N
+    q2, s2 = random_nvfp4(E * H, I, g)
+    gs13, gs2 = torch.full((E,), 0.05), torch.full((E,), 0.05)
+    # load time: one repack of each stacked tensor
+    w13 = petit_kernel.repack_nvfp4(q13.to(dev).view(torch.int32), E * 2 * I, H)
+    p13 = petit_kernel.process_nvfp4_scales(s13.to(dev), E * 2 * I, H)
+    w2 = petit_kernel.repack_nvfp4(q2.to(dev).view(torch.int32), E * H, I)
+    p2 = petit_kernel.process_nvfp4_scales(s2.to(dev), E * H, I)
+    # forward
+    x = torch.randn(T, H, generator=g).to(torch.bfloat16)
+    topk_w, topk_ids = torch.topk(torch.softmax(torch.randn(T, E, generator=g), -1), topk, dim=-1)
+    out = petit_kernel.fp4_moe(x.to(dev), w13, p13, gs13.to(dev), w2, p2, gs2.to(dev), topk_w.to(dev), topk_ids.to(torch.int32).to(dev), "nvfp4")
+    # the same layer in torch on the dequantised weights
+    d13 = petit_kernel.ops.dequant_packed(w13, p13, E * 2 * I, H, "nvfp4").cpu().view(E, 2 * I, H) * 0.05
+    d2 = petit_kernel.ops.dequant_packed(w2, p2, E * H, I, "nvfp4").cpu().view(E, H, I) * 0.05
+    ref = torch.zeros(T, H, dtype=torch.float64)
+    xf = x.double()
+    for t in range(T):
+        for j in range(topk):
+            e = int(topk_ids[t, j])
+            y = d13[e].double() @ xf[t]
+            h = torch.nn.functional.silu(y[:I]) * y[I:]
+            ref[t] += topk_w[t, j].double() * (d2[e].double() @ h)
+    err = (out.double().cpu() - ref).pow(2).mean().sqrt() / ref.pow(2).mean().sqrt()
+    print(f"fp4_moe: T={T} E={E} top-{topk} H={H} I={I}: rms error / rms = {err:.2e}")
+    assert err < 1e-2
+
+
+if __name__ == "__main__":
+    main()

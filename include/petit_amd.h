@@ -440,6 +440,36 @@ int petit_gemm_fp4_fp16_grouped(const petit_group_member *members, unsigned coun
                                 const petit_solution_hints *hints, uint64_t solution_id, void *stream);
 
 /*
+ * Routed-expert (MoE) launch (no counterpart in the reference): the E experts of a mixture-of-experts layer in ONE kernel launch,
+ * each on its own subset of the token rows:  rows r in [expert_offsets[e], expert_offsets[e+1]) of a belong to expert e, and
+ *     c[r][:] = a[r][:] . dequant(b_e)[n][k]^T * global_scales[e] (+ bias[e][:])          (SiLU-mul: silu(gate) * up, c is [m][n/2])
+ *   a               [m][k], hints->a_type (16-bit), rows ALREADY GROUPED by expert; c has the same row order, hints->c_type == a_type.
+ *   b, scales       the E experts' packed tensors back to back: expert e's block is exactly what repack_nvfp4 / process_nvfp4_scales /
+ *                   process_mxfp4_scales make of its [n, k] weight.  The packed layout is n-tile-major, so packing the stacked [E*n, k]
+ *                   weight (and its [E*n, k/16] or [E*n, k/32] scales) in ONE call gives the same bytes: callers may repack the stacked tensor.
+ *   global_scales   float32 device array [E].
+ *   expert_offsets  int32 device array [E + 1]: offsets[0] = 0, non-decreasing, offsets[E] = m.  The host never reads it: the call makes no
+ *                   host sync and may be captured in a graph whose replays route differently.
+ *   epilogue        optional: bias is read as [E][n] in c's dtype; activation = PETIT_ACTIVATION_SILU_MUL takes each expert's weight as
+ *                   [gate; up] along N (vLLM / SGLang's w13) and writes c as [m][n/2].
+ *   solution_id     PETIT_SOLUTION_AUTO, or the id of a kernel that has a MoE form (a decode, staged streaming or tiled kernel of a curated
+ *                   subset; no K split): the dense ids, petit_describe_solution names them.  Within an expert the result equals, bit for bit,
+ *                   a dense call on that expert's rows with the same id.
+ * Shapes: n % 16 == 0 (MXFP4: n % 32 == 0), k % 256 == 0, 1 <= E <= PETIT_MOE_MAX_EXPERTS; PETIT_ERROR_PROBLEM_SHAPE for other shapes and
+ * for null pointers, PETIT_ERROR_KERNEL_SHAPE for an id without a MoE form (or when the routing bound ceil(m / rows per workgroup) +
+ * min(E, m) exceeds the grid).  No workspace, no K split across workgroups.
+ * Robustness: the kernel clamps every offset it reads into [offsets[e-1], m], so malformed offsets can only leave rows of c unwritten;
+ * they never make it read or write out of bounds.  An expert without rows is never touched: its weights are not read.
+ * petit_gemm_moe_resolve_solution() returns the id the call would run (0: refused) -- the launcher uses the same pick.
+ */
+#define PETIT_MOE_MAX_EXPERTS 1024
+int petit_gemm_fp4_fp16_moe(void *c, const void *a, const void *b, const void *scales, const float *global_scales,
+                            const int32_t *expert_offsets, unsigned num_experts, unsigned m, unsigned n, unsigned k,
+                            const petit_solution_hints *hints, uint64_t solution_id, const petit_epilogue *epilogue, void *stream);
+uint64_t petit_gemm_moe_resolve_solution(const petit_solution_hints *hints, unsigned num_experts, unsigned m, unsigned n, unsigned k,
+                                         uint64_t solution_id, const petit_epilogue *epilogue);
+
+/*
  * Tune-and-persist (replaces the reference's `bench_matmul -algo tune`, tools/benchmarks/matmul/main.cc:269-325, which
  * enumerates and times every solution on the user's device but leaves the winning id for the user to carry around).
  *

@@ -105,7 +105,9 @@ double tiled_cost_us(const SolutionEntry &e, unsigned m, unsigned n, unsigned k,
 
 // *splitk_out (when given): the heuristic may answer with a K split across workgroups for the tiled kernels (needs scratch:
 // callers without any pass nullptr and get the best kernel that needs none).
-const SolutionEntry *heuristic(const Family &fam, unsigned m, unsigned n, unsigned k, bool need_pairs, unsigned *splitk_out, bool need_grouped) {
+// need_moe: only kernels with a MoE form (petit_gemm_fp4_fp16_moe, moe.hip: m = rows per active expert, n = the columns of all of them)
+const SolutionEntry *heuristic(const Family &fam, unsigned m, unsigned n, unsigned k, bool need_pairs, unsigned *splitk_out, bool need_grouped,
+                               bool need_moe) {
     if (splitk_out)
         *splitk_out = 1;
     // Rules distilled from the MI355X sweeps (profiles/):
@@ -126,7 +128,7 @@ const SolutionEntry *heuristic(const Family &fam, unsigned m, unsigned n, unsign
         for (int i = 0; i < fam.count; ++i) {
             const SolutionEntry &e = fam.entries[i];
             const StreamShape &s = e.shape;
-            if (!entry_fits(e, m, k) || is_native_am(s.am) || s.am == kWideAm || (need_pairs && !act_ok(e)))
+            if (!entry_fits(e, m, k) || is_native_am(s.am) || s.am == kWideAm || (need_pairs && !act_ok(e)) || (need_moe && !e.launch_moe))
                 continue; // (never the native-FP4 kernels: different accuracy class; the 32x32 kernels come from the arch table: the
                           //  cost model is good to ~10 % per kernel, and an argmin over twice the candidates loses more to that noise than it gains)
             double us;
@@ -164,7 +166,7 @@ const SolutionEntry *heuristic(const Family &fam, unsigned m, unsigned n, unsign
         // kernel would pull the activations through L2 once per 32-64 columns (measured 52.9 vs 57.0 us at M = 16)
         for (int i = 0; i < fam.count; ++i) {
             const SolutionEntry &e = fam.entries[i];
-            if (e.shape.am == kTiledAm && e.shape.mt == 1 && e.shape.nt == 4 && entry_fits(e, m, k) && (!need_pairs || act_ok(e)))
+            if (e.shape.am == kTiledAm && e.shape.mt == 1 && e.shape.nt == 4 && entry_fits(e, m, k) && (!need_pairs || act_ok(e)) && (!need_moe || e.launch_moe))
                 return &e;
         }
     }
@@ -191,7 +193,7 @@ const SolutionEntry *heuristic(const Family &fam, unsigned m, unsigned n, unsign
     double best_score = -1e30;
     for (int i = 0; i < fam.count; ++i) {
         const SolutionEntry &e = fam.entries[i];
-        if (!entry_fits(e, m, k) || (need_pairs && !act_ok(e)) || (need_grouped && !e.launch_grouped))
+        if (!entry_fits(e, m, k) || (need_pairs && !act_ok(e)) || (need_grouped && !e.launch_grouped) || (need_moe && !e.launch_moe))
             continue;
         const StreamShape &s = e.shape;
         if (s.mt != want_mt || s.am == kTiledAm || is_native_am(s.am) || s.am == kWideAm || s.wm != 1)
@@ -222,7 +224,7 @@ const SolutionEntry *heuristic(const Family &fam, unsigned m, unsigned n, unsign
     }
     if (!best) { // relax the m-tile preference
         for (int i = 0; i < fam.count; ++i)
-            if (entry_fits(fam.entries[i], m, k) && (!need_grouped || fam.entries[i].launch_grouped) && fam.entries[i].shape.am != kTiledAm && !is_batch(fam.entries[i]) &&
+            if (entry_fits(fam.entries[i], m, k) && (!need_grouped || fam.entries[i].launch_grouped) && (!need_moe || fam.entries[i].launch_moe) && fam.entries[i].shape.am != kTiledAm && !is_batch(fam.entries[i]) &&
                 !is_native_am(fam.entries[i].shape.am) && fam.entries[i].shape.am != kWideAm && (!need_pairs || act_ok(fam.entries[i])) &&
                 (!best || fam.entries[i].shape.mt > best->shape.mt))
                 best = &fam.entries[i];

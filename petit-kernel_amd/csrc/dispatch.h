@@ -60,7 +60,7 @@ unsigned guarded_splitk(const SolutionEntry &e, unsigned splitk, unsigned m, uns
 double stream_cost_us(const SolutionEntry &e, unsigned m, unsigned n, unsigned k, int num_cus);
 double tiled_cost_us(const SolutionEntry &e, unsigned m, unsigned n, unsigned k, int num_cus, unsigned splitk = 1);
 const SolutionEntry *heuristic(const Family &fam, unsigned m, unsigned n, unsigned k, bool need_pairs = false, unsigned *splitk_out = nullptr,
-                               bool need_grouped = false);
+                               bool need_grouped = false, bool need_moe = false);
 
 // --- pick.hip
 const SolutionEntry *heuristic_native(const Family &fam, int klass, unsigned m, unsigned n, unsigned k, bool need_pairs, bool have_slabs,

@@ -81,7 +81,8 @@ struct StreamCfg {
 // command processor hands the leading ones to every wave in SGPRs at launch, so a wave computes its first W / scale / A
 // addresses without waiting for the s_load round trip of the kernarg segment -- the decode kernel is all prologue
 // (every wave issues its whole share of loads at once), and that round trip sits in front of all of them.
-// (block_x: the workgroup's index along N -- blockIdx.x for a plain launch, the index inside its member for a grouped one)
+// (block_x: the workgroup's index along N -- blockIdx.x for a plain launch, the index inside its member for a grouped one;
+//  block_y: its m-block -- blockIdx.y, or the block inside its expert for a MoE launch, gemm_moe.hpp)
 // kCombine (gemm_stream_combine_kernel below): a K split across workgroups (gridDim.z) whose partial sums meet INSIDE the launch -- every
 // slice publishes its fp32 partial tile in its slab, takes a ticket for the output tile, and the last arriver sums the slabs in slice
 // order (deterministic) and finishes the epilogue -- instead of in a second launch (splitk_reduce_kernel).
@@ -89,7 +90,7 @@ template <class Cfg, bool kCombine = false>
 __device__ __forceinline__ void gemm_stream_body(const void *arg_w, const void *arg_s, const void *arg_a, unsigned arg_k, unsigned arg_n,
                                                  unsigned arg_m, unsigned arg_spw, unsigned arg_act, void *arg_c, const float *arg_gs,
                                                  const void *arg_bias, float *arg_workspace, const unsigned block_x,
-                                                 unsigned *arg_tickets = nullptr) {
+                                                 const unsigned block_y, unsigned *arg_tickets = nullptr) {
     GemmArgs p;
     p.c = arg_c, p.a = arg_a, p.w = arg_w, p.s = arg_s, p.gs = arg_gs, p.bias = arg_bias, p.act = arg_act;
     p.workspace = arg_workspace, p.m = arg_m, p.n = arg_n, p.k = arg_k, p.spans_per_wave = arg_spw, p.flags = 0;
@@ -116,7 +117,7 @@ __device__ __forceinline__ void gemm_stream_body(const void *arg_w, const void *
     const unsigned nspans = ktiles / KS;
     const unsigned ntiles = p.n / kTileN;
     const unsigned nt0 = (block_x * WN + wn) * NT;
-    const unsigned m0 = blockIdx.y * (16 * MT);
+    const unsigned m0 = block_y * (16 * MT);
 
     // K range of this wave: contiguous spans.  gridDim.z splits K across
     // workgroups first, WK across the waves of a workgroup second.
@@ -713,7 +714,7 @@ __global__ __launch_bounds__(Cfg::kThreads) void gemm_stream_kernel(const void *
                                                                     unsigned arg_spw, unsigned arg_act, void *arg_c,
                                                                     const float *arg_gs, const void *arg_bias,
                                                                     float *arg_workspace) {
-    gemm_stream_body<Cfg>(arg_w, arg_s, arg_a, arg_k, arg_n, arg_m, arg_spw, arg_act, arg_c, arg_gs, arg_bias, arg_workspace, blockIdx.x);
+    gemm_stream_body<Cfg>(arg_w, arg_s, arg_a, arg_k, arg_n, arg_m, arg_spw, arg_act, arg_c, arg_gs, arg_bias, arg_workspace, blockIdx.x, blockIdx.y);
 }
 
 // The same kernel with the cross-workgroup K split combined in the launch (kCombine above); tickets: one zero-initialised counter per
@@ -725,7 +726,7 @@ __global__ __launch_bounds__(Cfg::kThreads) void gemm_stream_combine_kernel(cons
                                                                             const float *arg_gs, const void *arg_bias,
                                                                             float *arg_workspace, unsigned *arg_tickets) {
     gemm_stream_body<Cfg, true>(arg_w, arg_s, arg_a, arg_k, arg_n, arg_m, arg_spw, arg_act, arg_c, arg_gs, arg_bias, arg_workspace, blockIdx.x,
-                                arg_tickets);
+                                blockIdx.y, arg_tickets);
 }
 
 // Grouped form (see gemm_decode_grouped_kernel in gemm_decode.hpp): the members' grids concatenated along x; one m-block, no K
@@ -738,7 +739,7 @@ __global__ __launch_bounds__(Cfg::kThreads) void gemm_stream_grouped_kernel(cons
         if (blockIdx.x >= g.wg_end[i])
             idx = i + 1, base = g.wg_end[i];
     gemm_stream_body<Cfg>(g.w[idx], g.s[idx], arg_a, arg_k, g.n[idx], arg_m, arg_spw, 0u, g.c[idx], g.gs[idx], g.bias[idx], nullptr,
-                          blockIdx.x - base);
+                          blockIdx.x - base, 0u);
 }
 
 // Second pass of the cross-workgroup split-K: sum the fp32 slabs in a fixed

@@ -52,8 +52,10 @@ template <class AT_, int FMT_, int KS_, int MT_, int NTW_, int WAVES_, int D_> s
     static_assert(!AT::kAdaptive || FMT == kFmtMx, "Fp16Mx: fp16 activations x MXFP4 weights");
 };
 
+// One workgroup tile (bn, bm) of C: bn = block along N, bm = block along M (gemm_tiled_kernel below takes them from its raster order,
+// the MoE form from its expert's rows: gemm_moe.hpp).
 template <class Cfg>
-__global__ __launch_bounds__(Cfg::kThreads, Cfg::kMinWavesPerSimd) void gemm_tiled_kernel(const GemmArgs p) {
+__device__ __forceinline__ void gemm_tiled_body(const GemmArgs &p, const unsigned bn, const unsigned bm) {
     using AT = typename Cfg::AT;
     using Frag = typename AT::frag;
     constexpr int FMT = Cfg::FMT, KS = Cfg::KS, MT = Cfg::MT, NTW = Cfg::NTW, WAVES = Cfg::WAVES, D = Cfg::D;
@@ -70,8 +72,6 @@ __global__ __launch_bounds__(Cfg::kThreads, Cfg::kMinWavesPerSimd) void gemm_til
     const unsigned ktiles = p.k / kTileK;
     const unsigned nspans = ktiles / KS;
     const unsigned ntiles = p.n / kTileN;
-    unsigned bn, bm;
-    tile_of_block(p.flags, bn, bm);
     stagger_priority(p.flags);
     const unsigned nt0 = (bn * WAVES + wave) * NTW;
     const unsigned m0 = bm * Cfg::BM;
@@ -325,6 +325,13 @@ __global__ __launch_bounds__(Cfg::kThreads, Cfg::kMinWavesPerSimd) void gemm_til
                 *reinterpret_cast<uint2 *>((char *)p.c + ((size_t)m * p.n + n) * 2) = finish4<AT>(v, gs, p.bias, n);
             }
         }
+}
+
+template <class Cfg>
+__global__ __launch_bounds__(Cfg::kThreads, Cfg::kMinWavesPerSimd) void gemm_tiled_kernel(const GemmArgs p) {
+    unsigned bn, bm;
+    tile_of_block(p.flags, bn, bm);
+    gemm_tiled_body<Cfg>(p, bn, bm);
 }
 
 } // namespace petit_amd

@@ -79,6 +79,25 @@ struct GroupTable {
     const void *bias[kMaxGroup];
 };
 
+// A routed-expert (MoE) GEMM (petit_gemm_fp4_fp16_moe, gemm_moe.hpp): E experts' packed weights / scales / global scales / biases
+// stacked back to back, the activation rows grouped by expert (rows offsets[e] .. offsets[e+1]-1: expert e; a device array the host never reads).
+constexpr unsigned kMoeMaxExperts = 1024;
+struct MoeArgs {
+    void *c;              // [m][n] (SiLU-mul: [m][n/2]) 16-bit, rows in a's order
+    const void *a;        // [m][k] 16-bit
+    const void *w, *s;    // E packed weight / scale blocks of one [n, k] matrix each
+    const float *gs;      // [E]
+    const void *bias;     // [E][n] in c's dtype, or null
+    unsigned act;         // 0 none, 1 SiLU-mul (each expert's weight is [gate; up] along N)
+    const int32_t *offsets; // [E + 1]
+    unsigned num_experts, m, n, k;
+};
+// the grid rows a MoE launch needs for any routing (gemm_moe.hpp), 0 when that exceeds the grid's y limit
+inline unsigned moe_slots(unsigned m, unsigned bm, unsigned num_experts) {
+    const uint64_t slots = ((uint64_t)m + bm - 1) / bm + (num_experts < m ? num_experts : m);
+    return slots <= 65535u ? (unsigned)slots : 0u;
+}
+
 // dispatch.hip: the dispatcher behind every GEMM entry point (solution_id: explicit id or one of the AUTO sentinels)
 } // namespace petit_amd
 struct petit_solution_hints;

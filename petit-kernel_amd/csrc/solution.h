@@ -107,13 +107,31 @@ using LaunchFn = int (*)(const GemmArgs &, unsigned splitk, hipStream_t);
 // several GEMMs sharing the activation rows in one launch (GroupTable, petit_internal.h): the launcher fills wg_end
 using LaunchGroupedFn = int (*)(GroupTable, const void *a, unsigned m, unsigned k, hipStream_t);
 
+// all experts of a MoE layer in one launch (MoeArgs, petit_internal.h; gemm_moe.hpp); never a K split across workgroups, no scratch
+using LaunchMoeFn = int (*)(const MoeArgs &, hipStream_t);
+
 struct SolutionEntry {
     StreamShape shape;
     int a_type; // kDataTypeBf16 / kDataTypeFp16
     int fmt;    // kFmtNv / kFmtMx (gemm_stream.hpp)
     LaunchFn launch;
     LaunchGroupedFn launch_grouped = nullptr; // the decode and the staged streaming kernels have one (M <= 16)
+    LaunchMoeFn launch_moe = nullptr;         // the decode, staged streaming and tiled kernels of moe_tu.inc
 };
+
+// The MoE forms of a family: compiled in translation units of their own (gemm_moe_<family>.hip) and attached to the table entries of the
+// same shape when the family's table is assembled (solutions.hip) -- no table entries and no ids of their own.
+struct MoeForm {
+    StreamShape shape;
+    LaunchMoeFn launch;
+};
+constexpr bool same_shape(const StreamShape &a, const StreamShape &b) {
+    return a.ks == b.ks && a.mt == b.mt && a.nt == b.nt && a.wn == b.wn && a.wk == b.wk && a.d == b.d && a.am == b.am && a.pa == b.pa && a.wm == b.wm;
+}
+const MoeForm *moe_forms_nv_bf16(int *count);
+const MoeForm *moe_forms_nv_f16(int *count);
+const MoeForm *moe_forms_mx_bf16(int *count);
+const MoeForm *moe_forms_mx_f16(int *count);
 
 // one table per (activation type, weight format) family, concatenated once (solutions.hip) from the parts its translation units export
 // (stream_tu.inc: gemm_<family>_p<part>.hip)

@@ -19,21 +19,30 @@ namespace petit_amd {
 
 // The family tables: the parts exported by the family's translation units, concatenated once (streaming kernels first, as the
 // heuristic and the tuner's reference-kernel choice expect: the plain direct-path kernel is the first entry).
+// The family's MoE forms (gemm_moe_<family>.hip) are attached to the entries of the same shape.
 using PartFn = const SolutionEntry *(*)(int *);
-static const SolutionEntry *concat_parts(std::vector<SolutionEntry> &store, std::initializer_list<PartFn> parts, int *count) {
-    if (store.empty())
+using MoeFormsFn = const MoeForm *(*)(int *);
+static const SolutionEntry *concat_parts(std::vector<SolutionEntry> &store, std::initializer_list<PartFn> parts, MoeFormsFn moe, int *count) {
+    if (store.empty()) {
         for (PartFn fn : parts) {
             int n = 0;
             const SolutionEntry *e = fn(&n);
             store.insert(store.end(), e, e + n);
         }
+        int nf = 0;
+        const MoeForm *forms = moe(&nf);
+        for (int i = 0; i < nf; ++i)
+            for (SolutionEntry &e : store)
+                if (forms[i].launch && same_shape(e.shape, forms[i].shape))
+                    e.launch_moe = forms[i].launch;
+    }
     *count = (int)store.size();
     return store.data();
 }
 #define PETIT_FAMILY_TABLE(fam, ...)                                                                          \
     const SolutionEntry *solutions_##fam(int *count) {                                                        \
         static std::vector<SolutionEntry> store;                                                              \
-        static const SolutionEntry *const table = concat_parts(store, {__VA_ARGS__}, count);                  \
+        static const SolutionEntry *const table = concat_parts(store, {__VA_ARGS__}, moe_forms_##fam, count); \
         *count = (int)store.size();                                                                           \
         return table;                                                                                         \
     }

@@ -134,6 +134,53 @@ at::Tensor mul_mxfp4_a16(const at::Tensor &A, const at::Tensor &B, const at::Ten
     return mul_a16(true, A, B, s, gs, m, n, k, solution_id, bias, activation);
 }
 
+// routed-expert (MoE) launch: all experts in one call (include/petit_amd.h); the same checks and texts as petit_kernel/ops.py _mul_moe
+at::Tensor mul_a16_moe(bool mx, const at::Tensor &A, const at::Tensor &B, const at::Tensor &s, const at::Tensor &global_scales,
+                       const at::Tensor &expert_offsets, int64_t size_m, int64_t size_n, int64_t size_k, int64_t num_experts, int64_t solution_id,
+                       const std::optional<at::Tensor> &bias, int64_t activation) {
+    const int64_t group = mx ? 32 : 16, E = num_experts;
+    TORCH_CHECK(A.scalar_type() == at::kBFloat16 || A.scalar_type() == at::kHalf, "A must be bfloat16 or float16.");
+    TORCH_CHECK(E >= 1 && E <= PETIT_MOE_MAX_EXPERTS, "num_experts must be in 1..", PETIT_MOE_MAX_EXPERTS, ", got ", E);
+    TORCH_CHECK(A.is_cuda() && B.is_cuda() && s.is_cuda() && global_scales.is_cuda() && expert_offsets.is_cuda(), "all tensors must be on GPU");
+    TORCH_CHECK(A.is_contiguous() && A.numel() == size_m * size_k, "A must be a contiguous [size_m, size_k] tensor");
+    TORCH_CHECK(B.is_contiguous() && B.numel() * B.element_size() == E * size_n * size_k / 2,
+                "B does not hold num_experts * size_n * size_k packed 4-bit weights");
+    TORCH_CHECK(s.is_contiguous() && s.numel() * s.element_size() == E * size_n * size_k / group, "s does not hold num_experts * size_n * size_k / ",
+                group, " scales");
+    TORCH_CHECK(global_scales.scalar_type() == at::kFloat && global_scales.is_contiguous() && global_scales.numel() == E,
+                "global_scales must be a contiguous float32 [num_experts] tensor");
+    TORCH_CHECK(expert_offsets.scalar_type() == at::kInt && expert_offsets.is_contiguous() && expert_offsets.numel() == E + 1,
+                "expert_offsets must be a contiguous int32 [num_experts + 1] tensor");
+    TORCH_CHECK(activation == 0 || activation == 1, "activation must be 0 (none) or 1 (silu_mul)");
+    if (activation)
+        TORCH_CHECK(size_n % 32 == 0, "silu_mul needs size_n % 32 == 0 (gate / up halves of whole tiles), got ", size_n);
+    if (bias.has_value())
+        TORCH_CHECK(bias->is_cuda() && bias->device() == A.device() && bias->scalar_type() == A.scalar_type() && bias->is_contiguous() &&
+                        bias->numel() == E * size_n,
+                    "bias must be a contiguous [num_experts, size_n] tensor of A's dtype on A's device");
+    const c10::hip::HIPGuardMasqueradingAsCUDA guard(A.device());
+    at::Tensor c = at::empty({size_m, activation ? size_n / 2 : size_n}, A.options());
+    const int a_type = A.scalar_type() == at::kBFloat16 ? kCxxBf16 : kCxxFp16;
+    const petit_solution_hints hints{a_type, mx ? kCxxMxFp4 : kCxxFp4, a_type, 0};
+    const uint64_t sid = (solution_id < 0 && solution_id >= -4096) ? PETIT_SOLUTION_AUTO : (uint64_t)solution_id;
+    const petit_epilogue epi{bias.has_value() ? bias->data_ptr() : nullptr, (int32_t)activation, 0};
+    const int rc = petit_gemm_fp4_fp16_moe(c.data_ptr(), A.data_ptr(), B.data_ptr(), s.data_ptr(), (const float *)global_scales.data_ptr(),
+                                           (const int32_t *)expert_offsets.data_ptr(), (unsigned)E, (unsigned)size_m, (unsigned)size_n,
+                                           (unsigned)size_k, &hints, sid, (bias.has_value() || activation) ? &epi : nullptr, stream_of(A));
+    TORCH_CHECK(rc != PETIT_ERROR_PROBLEM_SHAPE, "Incompatible problem shape (m=", size_m, ", n=", size_n, ", k=", size_k, ", num_experts=", E, ")");
+    TORCH_CHECK(rc != PETIT_ERROR_KERNEL_SHAPE, "No kernel implementation for solution_id=", sid == PETIT_SOLUTION_AUTO ? "-1" : std::to_string((int64_t)sid), ".");
+    TORCH_CHECK(rc == PETIT_OK, mx ? "mul_mxfp4_a16_moe: " : "mul_nvfp4_a16_moe: ", petit_error_string(rc));
+    return c;
+}
+at::Tensor mul_nvfp4_a16_moe(const at::Tensor &A, const at::Tensor &B, const at::Tensor &s, const at::Tensor &gs, const at::Tensor &off, int64_t m,
+                             int64_t n, int64_t k, int64_t e, int64_t solution_id, const std::optional<at::Tensor> &bias, int64_t activation) {
+    return mul_a16_moe(false, A, B, s, gs, off, m, n, k, e, solution_id, bias, activation);
+}
+at::Tensor mul_mxfp4_a16_moe(const at::Tensor &A, const at::Tensor &B, const at::Tensor &s, const at::Tensor &gs, const at::Tensor &off, int64_t m,
+                             int64_t n, int64_t k, int64_t e, int64_t solution_id, const std::optional<at::Tensor> &bias, int64_t activation) {
+    return mul_a16_moe(true, A, B, s, gs, off, m, n, k, e, solution_id, bias, activation);
+}
+
 // Shape functions for the Meta key (FakeTensor / torch.compile tracing, torch.export): outputs of the right shape, dtype and
 // device, nothing launched -- the ops trace as opaque calls instead of breaking the graph.
 at::Tensor repack_nvfp4_meta(const at::Tensor &q, int64_t n, int64_t k) { return at::empty({n / kLayoutN, k * kLayoutN / kPack}, q.options()); }
@@ -141,6 +188,11 @@ at::Tensor process_nvfp4_scales_meta(const at::Tensor &s, int64_t n, int64_t k) 
 at::Tensor process_mxfp4_scales_meta(const at::Tensor &s, int64_t n, int64_t k) { return at::empty({n / 32, k}, s.options()); }
 at::Tensor mul_a16_meta(const at::Tensor &A, const at::Tensor &, const at::Tensor &, const at::Tensor &, int64_t m, int64_t n, int64_t, int64_t,
                         const std::optional<at::Tensor> &, int64_t activation) {
+    TORCH_CHECK(A.scalar_type() == at::kBFloat16 || A.scalar_type() == at::kHalf, "A must be bfloat16 or float16.");
+    return at::empty({m, activation ? n / 2 : n}, A.options());
+}
+at::Tensor mul_a16_moe_meta(const at::Tensor &A, const at::Tensor &, const at::Tensor &, const at::Tensor &, const at::Tensor &, int64_t m, int64_t n,
+                            int64_t, int64_t, int64_t, const std::optional<at::Tensor> &, int64_t activation) {
     TORCH_CHECK(A.scalar_type() == at::kBFloat16 || A.scalar_type() == at::kHalf, "A must be bfloat16 or float16.");
     return at::empty({m, activation ? n / 2 : n}, A.options());
 }
@@ -158,6 +210,10 @@ TORCH_LIBRARY(petit_kernel, m) {
           "Tensor? bias=None, int activation=0) -> Tensor");
     m.def("mul_mxfp4_a16(Tensor A, Tensor B, Tensor s, Tensor global_scale, int size_m, int size_n, int size_k, int solution_id, "
           "Tensor? bias=None, int activation=0) -> Tensor");
+    m.def("mul_nvfp4_a16_moe(Tensor A, Tensor B, Tensor s, Tensor global_scales, Tensor expert_offsets, int size_m, int size_n, int size_k, "
+          "int num_experts, int solution_id=-1, Tensor? bias=None, int activation=0) -> Tensor");
+    m.def("mul_mxfp4_a16_moe(Tensor A, Tensor B, Tensor s, Tensor global_scales, Tensor expert_offsets, int size_m, int size_n, int size_k, "
+          "int num_experts, int solution_id=-1, Tensor? bias=None, int activation=0) -> Tensor");
     // round 3's op name (scales promised inside fp16's range): an alias of mul_mxfp4_a16 for one more round -- the kernels test the range themselves
     m.def("mul_mxfp4_a16_f16range(Tensor A, Tensor B, Tensor s, Tensor global_scale, int size_m, int size_n, int size_k, int solution_id, "
           "Tensor? bias=None, int activation=0) -> Tensor");
@@ -168,7 +224,9 @@ TORCH_LIBRARY(petit_kernel, m) {
     m.impl("process_mxfp4_scales", &process_mxfp4_scales);      \
     m.impl("mul_nvfp4_a16", &mul_nvfp4_a16);                    \
     m.impl("mul_mxfp4_a16", &mul_mxfp4_a16);                    \
-    m.impl("mul_mxfp4_a16_f16range", &mul_mxfp4_a16);
+    m.impl("mul_mxfp4_a16_f16range", &mul_mxfp4_a16);          \
+    m.impl("mul_nvfp4_a16_moe", &mul_nvfp4_a16_moe);            \
+    m.impl("mul_mxfp4_a16_moe", &mul_mxfp4_a16_moe);
 TORCH_LIBRARY_IMPL(petit_kernel, CUDA, m) { PETIT_IMPL_REAL(m) }
 TORCH_LIBRARY_IMPL(petit_kernel, CPU, m) { PETIT_IMPL_REAL(m) }
 TORCH_LIBRARY_IMPL(petit_kernel, Meta, m) {
@@ -178,4 +236,6 @@ TORCH_LIBRARY_IMPL(petit_kernel, Meta, m) {
     m.impl("mul_nvfp4_a16", &mul_a16_meta);
     m.impl("mul_mxfp4_a16", &mul_a16_meta);
     m.impl("mul_mxfp4_a16_f16range", &mul_a16_meta);
+    m.impl("mul_nvfp4_a16_moe", &mul_a16_moe_meta);
+    m.impl("mul_mxfp4_a16_moe", &mul_a16_moe_meta);
 }

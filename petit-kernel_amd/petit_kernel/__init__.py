@@ -13,6 +13,7 @@ import enum
 import torch
 
 from . import compiled, offline, ops, tuning
+from .moe import fp4_moe, moe_align
 from .ops import QuantizedActivations, mul_fp4_a16_grouped, mul_mxfp4_native, quantize_activations
 from .ops import attach_nvfp4_native, mul_nvfp4_native, nvfp4_native_image
 from .tuning import tune, tune_tensors
@@ -90,6 +91,26 @@ def mul_mxfp4_a16(a: torch.Tensor, b: torch.Tensor, s: torch.Tensor, global_scal
     return _impl.mul_mxfp4_a16(a, b, s, global_scale, size_m, size_n, size_k, solution_id, bias, activation)
 
 
+def mul_nvfp4_a16_moe(a: torch.Tensor, b: torch.Tensor, s: torch.Tensor, global_scales: torch.Tensor, expert_offsets: torch.Tensor,
+                      size_m: int, size_n: int, size_k: int, num_experts: int, solution_id: int = -1, bias: torch.Tensor = None,
+                      activation: str = None) -> torch.Tensor:
+    # all experts of a MoE layer in one launch (include/petit_amd.h "Routed-expert (MoE) launch"): rows expert_offsets[e] .. expert_offsets[e+1]-1
+    # of `a` (grouped by expert, int32 [E + 1] on the GPU, never read by the host) times expert e's weights; b / s hold the experts' packed
+    # tensors back to back, global_scales is float32 [E], bias [E, size_n]; activation "silu_mul" takes each expert's weight as [gate; up]
+    return _impl.mul_nvfp4_a16_moe(a, b, s, global_scales, expert_offsets, size_m, size_n, size_k, num_experts, solution_id, bias, activation)
+
+
+def mul_mxfp4_a16_moe(a: torch.Tensor, b: torch.Tensor, s: torch.Tensor, global_scales: torch.Tensor, expert_offsets: torch.Tensor,
+                      size_m: int, size_n: int, size_k: int, num_experts: int, solution_id: int = -1, bias: torch.Tensor = None,
+                      activation: str = None) -> torch.Tensor:
+    return _impl.mul_mxfp4_a16_moe(a, b, s, global_scales, expert_offsets, size_m, size_n, size_k, num_experts, solution_id, bias, activation)
+
+
+def moe_resolve_solution(hints: PetitSolutionHints, num_experts: int, size_m: int, size_n: int, size_k: int, solution_id: int = -1,
+                         activation: str = None) -> int:
+    return ops.moe_resolve_solution(hints, num_experts, size_m, size_n, size_k, solution_id, activation)
+
+
 def get_fp4_solutions(size_m: int, size_n: int, size_k: int, a_type, c_type) -> list:
     return ops.get_fp4_solutions(size_m, size_n, size_k, a_type, c_type)
 
@@ -109,6 +130,11 @@ __all__ = [
     "tune_tensors",
     "quantize_activations",
     "mul_fp4_a16_grouped",
+    "mul_nvfp4_a16_moe",
+    "mul_mxfp4_a16_moe",
+    "moe_resolve_solution",
+    "moe_align",
+    "fp4_moe",
     "mul_mxfp4_native",
     "nvfp4_native_image",
     "attach_nvfp4_native",

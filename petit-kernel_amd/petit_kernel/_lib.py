@@ -29,6 +29,7 @@ CXX_DTYPE_BF16 = 5
 CXX_DTYPE_MXFP4_E2M1 = 7
 CXX_DTYPE_MXFP4_E2M1_F16RANGE = 8   # extension: MXFP4 with every e8m0 scale in 114..140 (include/petit_amd.h)
 MXFP4_F16RANGE_SCALE_MIN, MXFP4_F16RANGE_SCALE_MAX = 114, 140
+PETIT_MOE_MAX_EXPERTS = 1024
 PETIT_DTYPE_FP32 = 100   # petit_dequant_packed_weights only
 
 
@@ -103,6 +104,9 @@ _SIGNATURES = {
     "petit_native_workspace_bytes": (C.c_uint64, [C.c_uint, C.c_uint]),
     "petit_gemm_fp4_fp16_grouped": (C.c_int, [C.POINTER(GroupMember), C.c_uint, C.c_void_p, C.c_uint, C.c_uint, C.POINTER(SolutionHints), C.c_uint64,
                                               C.c_void_p]),
+    "petit_gemm_fp4_fp16_moe": (C.c_int, [C.c_void_p] * 6 + [C.c_uint] * 4 + [C.POINTER(SolutionHints), C.c_uint64, C.POINTER(Epilogue),
+                                          C.c_void_p]),
+    "petit_gemm_moe_resolve_solution": (C.c_uint64, [C.POINTER(SolutionHints)] + [C.c_uint] * 4 + [C.c_uint64, C.POINTER(Epilogue)]),
     "petit_gemm_mxfp4_native": (C.c_int, [C.c_void_p] * 5 + [C.c_uint] * 3 + [C.POINTER(SolutionHints), C.c_uint64, C.POINTER(Epilogue),
                                           C.POINTER(NativeArgs), C.c_void_p, C.c_uint64, C.c_void_p]),
     "petit_nvfp4_native_image_bytes": (C.c_uint64, [C.c_uint, C.c_uint]),

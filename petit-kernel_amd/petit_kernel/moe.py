@@ -1,0 +1,51 @@
+"""petit_kernel.moe -- a routed-expert (mixture-of-experts) FP4 layer on the MoE launch (include/petit_amd.h "Routed-expert (MoE) launch").
+
+`moe_align` sorts the (token, slot) pairs of a top-k routing by expert and counts them per expert -- torch ops only, no host sync, so the
+whole layer can be captured in a graph and replayed with a different routing.  `fp4_moe` runs gate_up (fused SiLU-mul) and down as one
+MoE launch each; the router weighting and the top-k combine are torch plumbing, in fp32, in a fixed order (deterministic).
+"""
+from __future__ import annotations
+
+import torch
+
+
+def moe_align(topk_ids: torch.Tensor, num_experts: int):
+    """topk_ids [T, topk] (any integer dtype) -> (sorted_idx, expert_offsets).
+
+    sorted_idx: int64 [T * topk], the flattened (token, slot) positions grouped by expert (stable: ascending position inside an expert);
+    position p is token p // topk.  expert_offsets: int32 [num_experts + 1], rows expert_offsets[e] .. expert_offsets[e+1]-1 of the grouped
+    order belong to expert e.  Works on CPU and GPU tensors alike and never synchronises with the device."""
+    flat = topk_ids.reshape(-1).to(torch.int64)
+    sorted_idx = torch.argsort(flat, stable=True)
+    counts = torch.zeros(num_experts, dtype=torch.int32, device=flat.device)
+    counts.scatter_add_(0, flat, torch.ones_like(flat, dtype=torch.int32))
+    offsets = torch.zeros(num_experts + 1, dtype=torch.int32, device=flat.device)
+    offsets[1:] = torch.cumsum(counts, 0, dtype=torch.int32)
+    return sorted_idx, offsets
+
+
+def fp4_moe(hidden: torch.Tensor, w13: torch.Tensor, s13: torch.Tensor, gs13: torch.Tensor, w2: torch.Tensor, s2: torch.Tensor,
+            gs2: torch.Tensor, topk_weights: torch.Tensor, topk_ids: torch.Tensor, kind: str = "nvfp4") -> torch.Tensor:
+    """A gated-MLP MoE layer: out[t] = sum_j topk_weights[t, j] * down_e(silu(gate_e(x_t)) * up_e(x_t)), e = topk_ids[t, j].
+
+    hidden [T, H] bf16 / fp16.  w13 / s13: the E experts' [gate; up] weights ([2 I, H] each, vLLM / SGLang's w13 layout) packed back to
+    back -- repack_* / process_*_scales of the stacked [E * 2 I, H] tensors; w2 / s2 the same for the [H, I] down weights; gs13 / gs2:
+    float32 [E] global scales.  kind: 'nvfp4' or 'mxfp4'.  Returns [T, H] in hidden's dtype."""
+    from . import mul_mxfp4_a16_moe, mul_nvfp4_a16_moe
+    if kind not in ("nvfp4", "mxfp4"):
+        raise RuntimeError("kind must be 'nvfp4' or 'mxfp4'")
+    mul = mul_nvfp4_a16_moe if kind == "nvfp4" else mul_mxfp4_a16_moe
+    T, H = hidden.shape
+    topk = topk_ids.shape[1]
+    E = gs13.numel()
+    n13 = w13.numel() * w13.element_size() * 2 // (E * H)   # 2 I
+    inter = n13 // 2
+    m = T * topk
+    sorted_idx, offsets = moe_align(topk_ids, E)
+    a = hidden.index_select(0, sorted_idx // topk)                                        # rows grouped by expert
+    h = mul(a, w13, s13, gs13, offsets, m, n13, H, E, activation="silu_mul")             # [m, I]
+    y = mul(h, w2, s2, gs2, offsets, m, H, inter, E)                                      # [m, H]
+    w = topk_weights.reshape(-1).to(torch.float32).index_select(0, sorted_idx)
+    buf = torch.empty((m, H), dtype=torch.float32, device=hidden.device)
+    buf.index_copy_(0, sorted_idx, y.float() * w[:, None])                                # every (token, slot) position exactly once
+    return buf.view(T, topk, H).sum(dim=1).to(hidden.dtype)

@@ -587,3 +587,72 @@ def mul_fp4_a16_grouped(kind: str, A: torch.Tensor, members, size_m: int, size_k
         raise RuntimeError(f"No kernel implementation for solution_id={solution_id}.")
     _raise_on(err, "mul_fp4_a16_grouped")
     return outs
+
+
+# --- routed-expert (MoE) launch (include/petit_amd.h "Routed-expert (MoE) launch"; no counterpart in the reference) ------------------------
+
+def _moe_hints(kind: str, A: torch.Tensor) -> _CHints:
+    a_type = _lib.CXX_DTYPE_BF16 if A.dtype == torch.bfloat16 else _lib.CXX_DTYPE_FP16
+    return _CHints(a_type, _lib.CXX_DTYPE_FP4_E2M1 if kind == "nv" else _lib.CXX_DTYPE_MXFP4_E2M1, a_type, 0)
+
+
+def _mul_moe(kind: str, A, B, s, global_scales, expert_offsets, size_m, size_n, size_k, num_experts, solution_id=-1, bias=None,
+             activation=None) -> torch.Tensor:
+    """All experts of a MoE layer in one launch: rows expert_offsets[e] .. expert_offsets[e+1]-1 of A (grouped by expert) times expert e's
+    weights.  B / s: the experts' packed tensors back to back (repack / process the stacked [E * size_n, size_k] tensors in one call);
+    global_scales: float32 [E]; expert_offsets: int32 [E + 1] on A's device, never read by the host (no sync: capturable)."""
+    if A.dtype != torch.bfloat16 and A.dtype != torch.float16:
+        raise RuntimeError("A must be bfloat16 or float16.")
+    group = 16 if kind == "nv" else 32
+    E = int(num_experts)
+    _check(1 <= E <= _lib.PETIT_MOE_MAX_EXPERTS, f"num_experts must be in 1..{_lib.PETIT_MOE_MAX_EXPERTS}, got {E}")
+    _check(A.is_cuda and B.is_cuda and s.is_cuda and global_scales.is_cuda and expert_offsets.is_cuda, "all tensors must be on GPU")
+    _check(A.is_contiguous() and A.numel() == size_m * size_k, "A must be a contiguous [size_m, size_k] tensor")
+    _check(B.is_contiguous() and B.numel() * B.element_size() == E * size_n * size_k // 2,
+           "B does not hold num_experts * size_n * size_k packed 4-bit weights")
+    _check(s.is_contiguous() and s.numel() * s.element_size() == E * size_n * size_k // group,
+           f"s does not hold num_experts * size_n * size_k / {group} scales")
+    _check(global_scales.dtype == torch.float32 and global_scales.is_contiguous() and global_scales.numel() == E,
+           "global_scales must be a contiguous float32 [num_experts] tensor")
+    _check(expert_offsets.dtype == torch.int32 and expert_offsets.is_contiguous() and expert_offsets.numel() == E + 1,
+           "expert_offsets must be a contiguous int32 [num_experts + 1] tensor")
+    _check(activation in _ACTIVATIONS, f"activation must be one of {sorted(k for k in _ACTIVATIONS if k)} or None")
+    act = _ACTIVATIONS[activation]
+    if act:
+        _check(size_n % 32 == 0, f"silu_mul needs size_n % 32 == 0 (gate / up halves of whole tiles), got {size_n}")
+    if bias is not None:
+        _check(bias.is_cuda and bias.device == A.device and bias.dtype == A.dtype and bias.is_contiguous() and bias.numel() == E * size_n,
+               "bias must be a contiguous [num_experts, size_n] tensor of A's dtype on A's device")
+    c = torch.empty((size_m, size_n // 2 if act else size_n), dtype=A.dtype, device=A.device)
+    hints = _moe_hints(kind, A)
+    epi = _lib.Epilogue(bias.data_ptr() if bias is not None else None, act, 0) if (bias is not None or act) else None
+    with torch.cuda.device(A.device):
+        err = _lib.lib.petit_gemm_fp4_fp16_moe(_ptr(c), _ptr(A), _ptr(B), _ptr(s), _ptr(global_scales), _ptr(expert_offsets), E, size_m, size_n,
+                                               size_k, C.byref(hints), C.c_uint64(_c_solution_id(solution_id)),
+                                               C.byref(epi) if epi is not None else None, _stream(A))
+    if err == _lib.PETIT_ERROR_PROBLEM_SHAPE:
+        raise RuntimeError(f"Incompatible problem shape (m={size_m}, n={size_n}, k={size_k}, num_experts={E})")
+    if err == _lib.PETIT_ERROR_KERNEL_SHAPE:
+        raise RuntimeError(f"No kernel implementation for solution_id={solution_id}.")
+    _raise_on(err, "mul_%sfp4_a16_moe" % kind)
+    return c
+
+
+def mul_nvfp4_a16_moe(A, B, s, global_scales, expert_offsets, size_m, size_n, size_k, num_experts, solution_id=-1, bias=None,
+                      activation=None) -> torch.Tensor:
+    return _mul_moe("nv", A, B, s, global_scales, expert_offsets, size_m, size_n, size_k, num_experts, solution_id, bias, activation)
+
+
+def mul_mxfp4_a16_moe(A, B, s, global_scales, expert_offsets, size_m, size_n, size_k, num_experts, solution_id=-1, bias=None,
+                      activation=None) -> torch.Tensor:
+    return _mul_moe("mx", A, B, s, global_scales, expert_offsets, size_m, size_n, size_k, num_experts, solution_id, bias, activation)
+
+
+def moe_resolve_solution(hints: PetitSolutionHints, num_experts: int, size_m: int, size_n: int, size_k: int, solution_id: int = -1,
+                         activation=None) -> int:
+    """The kernel id a MoE call with these arguments runs (petit_gemm_moe_resolve_solution, the launcher's own pick); 0 when it would be refused."""
+    ch = _c_hints(hints)
+    act = _ACTIVATIONS[activation]
+    epi = _lib.Epilogue(None, act, 0)
+    return int(_lib.lib.petit_gemm_moe_resolve_solution(C.byref(ch), int(num_experts), size_m, size_n, size_k,
+                                                        C.c_uint64(_c_solution_id(solution_id)), C.byref(epi) if act else None))

@@ -1,0 +1,188 @@
+#!/usr/bin/env python3
+"""tools/moe_bench.py -- the routed-expert (MoE) launch against a host loop of dense calls, on real expert shapes.
+
+    python tools/moe_bench.py [--cells decode|prefill|all] [--models deepseek,qwen3,mixtral] [--iters N] [--out FILE]
+                              [--only-moe | --only-loop] [--single-expert]
+
+Per cell (model, projection, T tokens): E experts' NVFP4 weights (bf16 activations) stacked back to back, copied until the pool is >= 1 GB so
+that rotating over copies and over routings (drawn from a seed, top-k of random router logits) keeps the 256 MB Infinity Cache from serving
+the weights.  Timed with HIP events over `--iters` iterations (eager launches):
+  moe_us   one petit_gemm_fp4_fp16_moe launch (solution_id = -1)
+  loop_us  the per-active-expert loop of dense mul_nvfp4_a16 calls (solution_id = -1 for each expert's row count); the benchmark knows its own
+           routing, so the loop needs no device -> host copy (a real caller's would)
+  active_bytes  weight + scale bytes of the experts that have rows (+ activations and outputs), the bytes the MoE launch has to move
+--single-expert: every row routed to one expert, the MoE launch against the dense call with the SAME id (the indirection cost), at M = 1, 16, 512.
+Kernel times without launch gaps: run under `rocprofv3 --kernel-trace --stats -- python tools/moe_bench.py ...`.
+Prints one JSON object (and writes it to --out).
+"""
+from __future__ import annotations
+
+import argparse
+import json
+import sys
+from pathlib import Path
+
+import torch
+
+ROOT = Path(__file__).resolve().parent.parent
+sys.path.insert(0, str(ROOT / "petit-kernel_amd"))
+
+MODELS = {  # (gate_up n x k, down n x k, E, top-k)
+    "deepseek": ((4096, 7168), (7168, 2048), 256, 8),
+    "qwen3": ((1536, 2048), (2048, 768), 128, 8),
+    "mixtral": ((32768, 6144), (6144, 16384), 8, 2),
+}
+DECODE_T, PREFILL_T = (1, 4, 16, 64), (1024, 4096)
+POOL_BYTES = 1 << 30
+
+
+class Pool:
+    """copies of E experts' packed [n, k] NVFP4 weights (random bytes: timing only)"""
+
+    def __init__(self, pk, E, n, k):
+        self.E, self.n, self.k = E, n, k
+        self.w_bytes, self.s_bytes = n * k // 2, n * k // 16
+        per_copy = E * (self.w_bytes + self.s_bytes)
+        self.copies = max(1, -(-POOL_BYTES // per_copy))
+        g = torch.Generator(device="cuda").manual_seed(n * 31 + k)
+        self.b = [torch.randint(-2 ** 31, 2 ** 31 - 1, (E * n // 16, 2 * k), dtype=torch.int32, device="cuda", generator=g) for _ in range(self.copies)]
+        # e4m3 scales in [0.25, 4): exponent field 5..8
+        self.s = [(torch.randint(0x28, 0x40, (E * n, k // 16), dtype=torch.uint8, device="cuda", generator=g)).view(torch.float8_e4m3fn)
+                  for _ in range(self.copies)]
+        self.gs = torch.rand(E, device="cuda") + 0.5
+
+    def expert(self, c, e):
+        n, k = self.n, self.k
+        b = self.b[c].view(-1)[e * n * k // 8:(e + 1) * n * k // 8].view(n // 16, 2 * k)
+        s = self.s[c].view(-1)[e * self.s_bytes:(e + 1) * self.s_bytes].view(n, k // 16)
+        return b, s, self.gs[e:e + 1]
+
+
+def routings(T, E, topk, count, seed):
+    out = []
+    g = torch.Generator().manual_seed(seed)
+    for _ in range(count):
+        ids = torch.topk(torch.randn(T, E, generator=g), topk, dim=-1).indices
+        counts = torch.bincount(ids.reshape(-1), minlength=E)
+        offs = torch.zeros(E + 1, dtype=torch.int32)
+        offs[1:] = torch.cumsum(counts, 0)
+        out.append((counts.tolist(), offs))
+    return out
+
+
+def time_us(fn, iters):
+    for i in range(3):
+        fn(i)
+    torch.cuda.synchronize()
+    t0, t1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    t0.record()
+    for i in range(iters):
+        fn(i)
+    t1.record()
+    torch.cuda.synchronize()
+    return t0.elapsed_time(t1) * 1e3 / iters
+
+
+def cell(pk, pool, T, topk, iters, do_moe=True, do_loop=True, seed=0):
+    E, n, k = pool.E, pool.n, pool.k
+    m = T * topk
+    routes = routings(T, E, topk, 16, seed)
+    a = torch.randn(m, k, device="cuda").to(torch.bfloat16)
+    offs_d = [o.to("cuda") for _, o in routes]
+    res = {"T": T, "E": E, "topk": topk, "n": n, "k": k, "m": m}
+    act = [sum(1 for c in cnt if c) for cnt, _ in routes]
+    res["active_experts_mean"] = sum(act) / len(act)
+    res["active_bytes_mean"] = sum(a_ * (pool.w_bytes + pool.s_bytes) for a_ in act) / len(act) + 2 * m * k + 2 * m * n
+    h = pk.PetitSolutionHints()
+    h.a_type = h.c_type = torch.bfloat16
+    h.b_type = pk.DataType.float4_e2m1
+    res["moe_solution"] = pk.ops._lib.describe_solution(pk.moe_resolve_solution(h, E, m, n, k, -1))
+
+    def moe(i):
+        c = i % pool.copies
+        pk.mul_nvfp4_a16_moe(a, pool.b[c], pool.s[c], pool.gs, offs_d[i % len(offs_d)], m, n, k, E)
+
+    def loop(i):
+        c = i % pool.copies
+        cnt, offs = routes[i % len(routes)]
+        for e in range(E):
+            if cnt[e]:
+                b, s, gs = pool.expert(c, e)
+                lo = int(offs[e])
+                pk.mul_nvfp4_a16(a[lo:lo + cnt[e]], b, s, gs, cnt[e], n, k, -1)
+
+    if do_moe:
+        res["moe_us"] = time_us(moe, iters)
+        res["moe_TBps_active"] = res["active_bytes_mean"] / res["moe_us"] / 1e6
+    if do_loop:
+        res["loop_us"] = time_us(loop, max(3, iters // 4))
+        res["loop_TBps_active"] = res["active_bytes_mean"] / res["loop_us"] / 1e6
+    if do_moe and do_loop:
+        res["speedup_vs_loop"] = res["loop_us"] / res["moe_us"]
+    return res
+
+
+def single_expert(pk, iters):
+    """every row on one expert: the MoE launch against the dense call with the same id (DeepSeek gate_up shape, E = 256)"""
+    out = []
+    pool = Pool(pk, 256, 4096, 7168)
+    h = pk.PetitSolutionHints()
+    h.a_type = h.c_type = torch.bfloat16
+    h.b_type = pk.DataType.float4_e2m1
+    for m in (1, 16, 512):
+        E, n, k = pool.E, pool.n, pool.k
+        a = torch.randn(m, k, device="cuda").to(torch.bfloat16)
+        offs = []
+        for e in range(16):
+            o = torch.zeros(E + 1, dtype=torch.int32)
+            o[e * 7 + 1:] = m
+            offs.append((e * 7, o.to("cuda")))
+        sid = pk.moe_resolve_solution(h, 1, m, n, k, -1)   # (the pick for m rows on one expert, which the dense call also runs)
+
+        def moe(i):
+            pk.mul_nvfp4_a16_moe(a, pool.b[0], pool.s[0], pool.gs, offs[i % 16][1], m, n, k, E, sid)
+
+        def dense(i):
+            b, s, gs = pool.expert(0, offs[i % 16][0])
+            pk.mul_nvfp4_a16(a, b, s, gs, m, n, k, sid)
+
+        mu, du = time_us(moe, iters), time_us(dense, iters)
+        out.append({"m": m, "solution": pk.ops._lib.describe_solution(sid), "moe_us": mu, "dense_us": du, "moe_over_dense": mu / du})
+    return out
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--cells", default="all", choices=["decode", "prefill", "all"])
+    ap.add_argument("--models", default="deepseek,qwen3,mixtral")
+    ap.add_argument("--iters", type=int, default=50)
+    ap.add_argument("--only-moe", action="store_true")
+    ap.add_argument("--only-loop", action="store_true")
+    ap.add_argument("--single-expert", action="store_true")
+    ap.add_argument("--out", default="")
+    args = ap.parse_args()
+    import petit_kernel as pk
+    report = {"device": torch.cuda.get_device_properties(0).gcnArchName, "cells": []}
+    if args.single_expert:
+        report["single_expert"] = single_expert(pk, args.iters)
+    else:
+        ts = (DECODE_T if args.cells != "prefill" else ()) + (PREFILL_T if args.cells != "decode" else ())
+        for name in args.models.split(","):
+            gate_up, down, E, topk = MODELS[name]
+            for proj, (n, k) in (("gate_up", gate_up), ("down", down)):
+                pool = Pool(pk, E, n, k)
+                for T in ts:
+                    r = cell(pk, pool, T, topk, args.iters if T < 1024 else max(5, args.iters // 10), not args.only_loop, not args.only_moe, seed=T)
+                    r.update(model=name, proj=proj)
+                    print(json.dumps(r), file=sys.stderr, flush=True)
+                    report["cells"].append(r)
+                del pool
+                torch.cuda.empty_cache()
+    text = json.dumps(report)
+    if args.out:
+        Path(args.out).write_text(json.dumps(report, indent=1))
+    print(text)
+
+
+if __name__ == "__main__":
+    main()
