@@ -50,6 +50,11 @@ def main():
     err = (out.double().cpu() - ref).pow(2).mean().sqrt() / ref.pow(2).mean().sqrt()
     print(f"fp4_moe: T={T} E={E} top-{topk} H={H} I={I}: rms error / rms = {err:.2e}")
     assert err < 1e-2
+    # the fused layer: device align, gate_up on gathered rows, down scattered into slot order, top-k combine (4 launches)
+    fused = petit_kernel.fp4_moe_fused(x.to(dev), w13, p13, gs13.to(dev), w2, p2, gs2.to(dev), topk_w.to(dev), topk_ids.to(dev), "nvfp4")
+    err_f = (fused.double().cpu() - ref).pow(2).mean().sqrt() / ref.pow(2).mean().sqrt()
+    print(f"fp4_moe_fused: rms error / rms = {err_f:.2e}")
+    assert err_f < 1e-2
 
 
 if __name__ == "__main__":

@@ -470,6 +470,45 @@ uint64_t petit_gemm_moe_resolve_solution(const petit_solution_hints *hints, unsi
                                          uint64_t solution_id, const petit_epilogue *epilogue);
 
 /*
+ * Indexed MoE launch: petit_gemm_fp4_fp16_moe with a row gather on A and a row scatter on C, so that a layer needs neither a copy of
+ * the activations in expert order nor an un-permute of the output.  Grouped row r (r in [expert_offsets[e], expert_offsets[e+1]): expert
+ * e, as above) reads row a_row_index[r] of a [a_rows][k] and writes row c_row_index[r] of c [c_rows][n] ([c_rows][n/2] with SiLU-mul).
+ *   a_row_index, c_row_index   int32 device arrays [m], or null for the identity (a_rows / c_rows must then be >= m).  Never read by the host.
+ *   An A index outside [0, a_rows) reads zeros; a C index outside [0, c_rows) stores nothing (rows of c no index names stay untouched).
+ *   expert_offsets[E] may be < m: grouped rows past it belong to no expert and are not computed (petit_moe_align's unrouted entries).
+ * Same pick, same ids and, within an expert, the same numbers bit for bit as petit_gemm_fp4_fp16_moe: every kernel with a MoE form has an
+ * indexed one.  With both indices null the call IS petit_gemm_fp4_fp16_moe.  PETIT_ERROR_PROBLEM_SHAPE also when an index is given and
+ * a_rows * k * 2 > 2^31 (the bytes one 32-bit buffer descriptor of A can bound-check with an out-of-range marker to spare).
+ */
+int petit_gemm_fp4_fp16_moe_ex(void *c, const void *a, const void *b, const void *scales, const float *global_scales,
+                               const int32_t *expert_offsets, unsigned num_experts, unsigned m, unsigned n, unsigned k,
+                               const int32_t *a_row_index, unsigned a_rows, const int32_t *c_row_index, unsigned c_rows,
+                               const petit_solution_hints *hints, uint64_t solution_id, const petit_epilogue *epilogue, void *stream);
+
+/*
+ * Routing on the device (no host sync, graph-capturable, deterministic: no result depends on the order of atomics).
+ * petit_moe_align: topk_ids [num_tokens][topk] (int32, or int64 when ids_are_int64) -> the grouped order of the MoE launches:
+ *   sorted_pos    int32 [num_tokens * topk]: the flat (token, slot) positions p = token * topk + slot grouped by expert, ascending inside an
+ *                 expert (a stable sort by expert id).
+ *   token_index   int32 [num_tokens * topk]: sorted_pos[r] / topk (the A row index of gate_up).
+ *   expert_offsets int32 [num_experts + 1], as petit_gemm_fp4_fp16_moe reads it.
+ *   Ids outside [0, num_experts) (-1: an expert that is not local under expert parallelism) are not routed: they get no row, and
+ *   expert_offsets[E] counts the routed entries.  Rows r >= expert_offsets[E] of sorted_pos / token_index are set to -1.
+ *   workspace     petit_moe_align_workspace_bytes() bytes of device scratch (0: may be null); one or three launches.
+ * petit_moe_combine: the top-k reduce of a layer, out[t][:] = to16(acc) with acc = 0 and, for j = 0 .. topk-1 in order, skipping ids
+ *   outside [0, num_experts):  acc = acc + float(slot_out[t * topk + j][:]) * topk_weights[t][j]   (fp32, no FMA contraction, one
+ *   round-to-nearest-even at the end).  slot_out [num_tokens * topk][n] and out [num_tokens][n] in dtype (PETIT_DTYPE-style: 4 fp16,
+ *   5 bf16), topk_weights float32 [num_tokens][topk], n % 8 == 0.  Slots of unrouted entries are never read.
+ * Errors: PETIT_ERROR_PROBLEM_SHAPE for null pointers, topk == 0, num_experts outside 1..PETIT_MOE_MAX_EXPERTS, num_tokens * topk >= 2^31,
+ * n % 8 != 0; PETIT_ERROR_BAD_ARGUMENT for another dtype.
+ */
+uint64_t petit_moe_align_workspace_bytes(unsigned num_tokens, unsigned topk, unsigned num_experts);
+int petit_moe_align(const void *topk_ids, int ids_are_int64, unsigned num_tokens, unsigned topk, unsigned num_experts, int32_t *expert_offsets,
+                    int32_t *sorted_pos, int32_t *token_index, void *workspace, void *stream);
+int petit_moe_combine(void *out, const void *slot_out, const float *topk_weights, const void *topk_ids, int ids_are_int64, unsigned num_tokens,
+                      unsigned topk, unsigned n, unsigned num_experts, int dtype, void *stream);
+
+/*
  * Tune-and-persist (replaces the reference's `bench_matmul -algo tune`, tools/benchmarks/matmul/main.cc:269-325, which
  * enumerates and times every solution on the user's device but leaves the winning id for the user to carry around).
  *

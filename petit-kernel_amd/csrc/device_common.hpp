@@ -456,4 +456,27 @@ template <int I, int N, class F> __device__ __forceinline__ void static_for(F &&
     }
 }
 
+// Row addressing of the indexed MoE forms (gemm_moe.hpp, petit_gemm_fp4_fp16_moe_ex): row m of a body's problem is grouped row
+// row0 + m; it reads A row a_idx[row0 + m] and writes C row c_idx[row0 + m] (a null index: the grouped row itself).  A and C are then
+// the caller's whole matrices, not the expert's slice.  The bodies take it behind a compile-time switch (kIdx, default off): with the
+// switch off they never touch it and compile to the code they had without it.
+struct RowIndex {
+    const int *a_idx, *c_idx;
+    unsigned row0, a_rows, c_rows;
+};
+// A descriptors of the indexed forms cover a_rows * k * 2 <= 2^31 bytes (the host refuses more), so this voffset is out of range
+constexpr unsigned kIdxOob = 0x80000000u;
+// byte offset of body row m's A row, or kIdxOob for rows past the body's m (no index is read for them) and indices outside [0, a_rows)
+__device__ __forceinline__ unsigned idx_a_off(const RowIndex &ix, unsigned m, unsigned body_m, unsigned k) {
+    if (m >= body_m)
+        return kIdxOob;
+    const unsigned a = ix.a_idx ? (unsigned)ix.a_idx[ix.row0 + m] : ix.row0 + m;
+    return a < ix.a_rows ? a * k * 2 : kIdxOob;
+}
+// C row of body row m (m < the body's m), or ~0u: an index outside [0, c_rows) -- the store is skipped
+__device__ __forceinline__ unsigned idx_c_row(const RowIndex &ix, unsigned m) {
+    const unsigned c = ix.c_idx ? (unsigned)ix.c_idx[ix.row0 + m] : ix.row0 + m;
+    return c < ix.c_rows ? c : ~0u;
+}
+
 } // namespace petit_amd

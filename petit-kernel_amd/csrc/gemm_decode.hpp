@@ -101,11 +101,12 @@ __device__ __forceinline__ float sum_rows(float v) {
     return __builtin_bit_cast(float, b0) + __builtin_bit_cast(float, b1);
 }
 
-// (block_x: the workgroup's index along N -- blockIdx.x for a plain launch, the index inside its member for a grouped one)
-template <class Cfg>
+// (block_x: the workgroup's index along N -- blockIdx.x for a plain launch, the index inside its member for a grouped one;
+//  kIdx / ix: the indexed MoE form's row gather and scatter, device_common.hpp RowIndex -- arg_a and arg_c are then whole matrices)
+template <class Cfg, bool kIdx = false>
 __device__ __forceinline__ void gemm_decode_body(const void *arg_w, const void *arg_s, const void *arg_a, unsigned arg_k, unsigned arg_n,
                                                  unsigned arg_m, unsigned arg_spw, unsigned arg_act, void *arg_c, const float *arg_gs,
-                                                 const void *arg_bias, const unsigned block_x) {
+                                                 const void *arg_bias, const unsigned block_x, const RowIndex ix = RowIndex{}) {
     using AT = typename Cfg::AT;
     using Frag = typename AT::frag;
     constexpr int KS = Cfg::KS, NT = Cfg::NT, WK = Cfg::WK, D = Cfg::D, R = Cfg::R, TG = Cfg::TG;
@@ -142,7 +143,7 @@ __device__ __forceinline__ void gemm_decode_body(const void *arg_w, const void *
         const unsigned span_tiles = arg_act ? (valid_nt >> 1) + (ntiles >> 1) : valid_nt;
         const __amdgpu_buffer_rsrc_t w_rsrc = make_rsrc((const char *)arg_w + (size_t)pt0 * w_row_bytes, span_tiles * w_row_bytes);
         const __amdgpu_buffer_rsrc_t s_rsrc = make_rsrc((const char *)arg_s + (size_t)pt0 * s_row_bytes, span_tiles * s_row_bytes);
-        const __amdgpu_buffer_rsrc_t a_rsrc = make_rsrc(arg_a, rows * arg_k * 2);
+        const __amdgpu_buffer_rsrc_t a_rsrc = make_rsrc(arg_a, (kIdx ? ix.a_rows : rows) * arg_k * 2);
 
         unsigned w_voff[NT], s_voff[NT];
 #pragma unroll
@@ -157,16 +158,23 @@ __device__ __forceinline__ void gemm_decode_body(const void *arg_w, const void *
         // KS == 2: a wave-load covers two rows of 512 B
         constexpr bool kRowLoads = (KS * 16) % 64 == 0;
         // (validity lives in the VGPR offset: it is bounds-checked against the descriptor on every generation)
+        // (indexed: the gathered row's offset, read once here; rows >= M and indices outside the descriptor read zeros)
         unsigned a_vrow[R];
 #pragma unroll
         for (int row = 0; row < R; ++row)
-            a_vrow[row] = lane * 16 + row * arg_k * 2;
+            a_vrow[row] = lane * 16 + (kIdx ? idx_a_off(ix, row, arg_m, arg_k) : row * arg_k * 2);
         unsigned a_voff2 = 0;
         int a_dst2 = 0;
+        [[maybe_unused]] unsigned a_vidx2[kIdx && !kRowLoads ? Cfg::kAStageLoads : 1];
         if constexpr (!kRowLoads) {
             static_assert(kRowLoads || KS == 2, "span of 2, 4 or 8 tiles");
             a_voff2 = (lane >> 5) * arg_k * 2 + (lane & 31u) * 16;
             a_dst2 = (int)((lane >> 5) * Cfg::kARowU4 + (lane & 31u));
+            if constexpr (kIdx) { // wave-load i covers rows 2 i, 2 i + 1: the row step moves from the SGPR into the VGPR offset
+#pragma unroll
+                for (int i = 0; i < Cfg::kAStageLoads; ++i)
+                    a_vidx2[i] = (2 * i + (lane >> 5) < (unsigned)R) ? idx_a_off(ix, 2 * i + (lane >> 5), arg_m, arg_k) + (lane & 31u) * 16 : kOob;
+            }
         }
         u32x4 astage[Cfg::kAStageLoads];
         auto issue_a_stage = [&](unsigned sp) {
@@ -175,6 +183,8 @@ __device__ __forceinline__ void gemm_decode_body(const void *arg_w, const void *
                 if constexpr (kRowLoads) { // rows >= M fall out of the descriptor: zeros
                     constexpr int kPerRow = KS * 16 / 64;
                     astage[i] = buf_load16(a_rsrc, a_vrow[i / kPerRow] + (i % kPerRow) * 1024, sp * (KS * 256), kAuxDefault);
+                } else if constexpr (kIdx) {
+                    astage[i] = buf_load16(a_rsrc, a_vidx2[i], sp * (KS * 256), kAuxDefault);
                 } else {
                     const unsigned vo = (2 * i + (lane >> 5) < (unsigned)R) ? a_voff2 : kOob;
                     astage[i] = buf_load16(a_rsrc, vo, sp * (KS * 256) + 2 * i * arg_k * 2, kAuxDefault);
@@ -404,18 +414,20 @@ __device__ __forceinline__ void gemm_decode_body(const void *arg_w, const void *
             return v;
         };
         const unsigned ntile = nt0 + nt;
-        if (m < arg_m && ntile < ntiles) {
+        // (indexed: the scattered row; an index outside [0, c_rows) stores nothing)
+        const unsigned cm = (kIdx && m < arg_m) ? idx_c_row(ix, m) : m;
+        if (m < arg_m && ntile < ntiles && (!kIdx || cm != ~0u)) {
             if (arg_act) {
                 if constexpr (NT % 2 == 0) {
                     if ((nt & 1u) == 0) { // logical tiles (nt, nt + 1) = gate / up halves of output tile ntile / 2
                         const unsigned n_half = arg_n >> 1, n = (ntile >> 1) * 16 + q * 4;
-                        *reinterpret_cast<uint2 *>((char *)arg_c + ((size_t)m * n_half + n) * 2) =
+                        *reinterpret_cast<uint2 *>((char *)arg_c + ((size_t)cm * n_half + n) * 2) =
                             finish4_silu_mul<AT>(gather(nt), gather(nt + 1), gs, arg_bias, n, n_half);
                     }
                 }
             } else {
                 const unsigned n = ntile * 16 + q * 4;
-                *reinterpret_cast<uint2 *>((char *)arg_c + ((size_t)m * arg_n + n) * 2) = finish4<AT>(gather(nt), gs, arg_bias, n);
+                *reinterpret_cast<uint2 *>((char *)arg_c + ((size_t)cm * arg_n + n) * 2) = finish4<AT>(gather(nt), gs, arg_bias, n);
             }
         }
     }

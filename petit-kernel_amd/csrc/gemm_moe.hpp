@@ -14,6 +14,13 @@
 //
 // Robustness: every offset is clamped into [offsets[e-1], m] (offsets[-1] := 0) before use -- a running maximum, then
 // min(., m) -- so malformed offsets can only leave rows unwritten, never read or write out of bounds.
+//
+// Indexed forms (petit_gemm_fp4_fp16_moe_ex; the *_idx_kernel templates below, instantiated by the gemm_moe_idx_<family> TUs): grouped
+// row r reads A row a_idx[r] and writes C row c_idx[r] (device_common.hpp RowIndex), so the layer needs no gathered copy of the
+// activations and no un-permute of the output.  Only addresses change: each workgroup reads its rows' indices once before the K loop
+// (A: into the VGPR / SGPR offsets of its loads, against one descriptor over the caller's a_rows x k matrix, so an index outside
+// [0, a_rows) reads zeros) and once more in the epilogue (C: an explicit check, an index outside [0, c_rows) stores nothing).  Within an
+// expert the numbers are the plain form's, bit for bit.
 #pragma once
 
 #include "gemm_decode.hpp"
@@ -149,6 +156,63 @@ __global__ __launch_bounds__(Cfg::kThreads, Cfg::kMinWavesPerSimd) void gemm_til
     q.bias = p.bias ? (const char *)p.bias + (size_t)t.expert * p.n * 2 : nullptr;
     q.m = t.rows;
     gemm_tiled_body<Cfg>(q, local / t.tiles, local % t.tiles);
+}
+
+// --- indexed forms: the same kernels on gathered A rows and scattered C rows (A and C are the caller's whole matrices) ----------------
+template <class Cfg>
+__global__ __launch_bounds__(Cfg::kThreads) void gemm_stream_moe_idx_kernel(const void *arg_w, const void *arg_s, const void *arg_a, unsigned arg_k,
+                                                                            unsigned arg_n, unsigned arg_m, unsigned arg_spw, unsigned arg_act,
+                                                                            void *arg_c, const float *arg_gs, const void *arg_bias,
+                                                                            const int *arg_offsets, unsigned arg_experts, RowIndex ix) {
+    constexpr unsigned BM = Cfg::AM;
+    static_assert(Cfg::AM > 0 && Cfg::MT == 1, "MoE form: the staged streaming kernels");
+    MoeTile t;
+    if (!moe_locate(arg_offsets, arg_experts, arg_m, BM, blockIdx.y, t))
+        return;
+    const unsigned r0 = t.row0 + (blockIdx.y - t.first) * BM;
+    ix.row0 = r0;
+    gemm_stream_body<Cfg, false, true>((const char *)arg_w + t.expert * moe_w_bytes<Cfg::FMT>(arg_n, arg_k),
+                                       (const char *)arg_s + t.expert * moe_s_bytes<Cfg::FMT>(arg_n, arg_k), arg_a, arg_k, arg_n,
+                                       min(t.row0 + t.rows - r0, BM), arg_spw, arg_act, arg_c, arg_gs + t.expert,
+                                       arg_bias ? (const char *)arg_bias + (size_t)t.expert * arg_n * 2 : nullptr, nullptr, blockIdx.x, 0u, nullptr, ix);
+}
+
+template <class Cfg>
+__global__ __launch_bounds__(Cfg::kThreads, Cfg::kWavesPerSimd) void gemm_decode_moe_idx_kernel(const void *arg_w, const void *arg_s,
+                                                                                                const void *arg_a, unsigned arg_k, unsigned arg_n,
+                                                                                                unsigned arg_m, unsigned arg_spw, unsigned arg_act,
+                                                                                                void *arg_c, const float *arg_gs,
+                                                                                                const void *arg_bias, const int *arg_offsets,
+                                                                                                unsigned arg_experts, RowIndex ix) {
+    constexpr unsigned BM = Cfg::R;
+    MoeTile t;
+    if (!moe_locate(arg_offsets, arg_experts, arg_m, BM, blockIdx.y, t))
+        return;
+    const unsigned r0 = t.row0 + (blockIdx.y - t.first) * BM;
+    ix.row0 = r0;
+    gemm_decode_body<Cfg, true>((const char *)arg_w + t.expert * moe_w_bytes<kFmtNv>(arg_n, arg_k),
+                                (const char *)arg_s + t.expert * moe_s_bytes<kFmtNv>(arg_n, arg_k), arg_a, arg_k, arg_n, min(t.row0 + t.rows - r0, BM),
+                                arg_spw, arg_act, arg_c, arg_gs + t.expert,
+                                arg_bias ? (const char *)arg_bias + (size_t)t.expert * arg_n * 2 : nullptr, blockIdx.x, ix);
+}
+
+template <class Cfg>
+__global__ __launch_bounds__(Cfg::kThreads, Cfg::kMinWavesPerSimd) void gemm_tiled_moe_idx_kernel(const GemmArgs p, const int *arg_offsets,
+                                                                                                    unsigned arg_experts, RowIndex ix) {
+    const unsigned nb = gridDim.x;
+    const unsigned lin = blockIdx.y * nb + blockIdx.x;
+    MoeTile t;
+    if (!moe_locate(arg_offsets, arg_experts, p.m, Cfg::BM, lin / nb, t))
+        return;
+    const unsigned local = lin - t.first * nb;
+    GemmArgs q = p;
+    q.w = (const char *)p.w + t.expert * moe_w_bytes<Cfg::FMT>(p.n, p.k);
+    q.s = (const char *)p.s + t.expert * moe_s_bytes<Cfg::FMT>(p.n, p.k);
+    q.gs = p.gs + t.expert;
+    q.bias = p.bias ? (const char *)p.bias + (size_t)t.expert * p.n * 2 : nullptr;
+    q.m = t.rows;
+    ix.row0 = t.row0;
+    gemm_tiled_body<Cfg, true>(q, local / t.tiles, local % t.tiles, ix);
 }
 
 } // namespace petit_amd

@@ -86,11 +86,12 @@ struct StreamCfg {
 // kCombine (gemm_stream_combine_kernel below): a K split across workgroups (gridDim.z) whose partial sums meet INSIDE the launch -- every
 // slice publishes its fp32 partial tile in its slab, takes a ticket for the output tile, and the last arriver sums the slabs in slice
 // order (deterministic) and finishes the epilogue -- instead of in a second launch (splitk_reduce_kernel).
-template <class Cfg, bool kCombine = false>
+// kIdx / ix: the indexed MoE form's row gather and scatter (device_common.hpp RowIndex; arg_a and arg_c are then whole matrices).
+template <class Cfg, bool kCombine = false, bool kIdx = false>
 __device__ __forceinline__ void gemm_stream_body(const void *arg_w, const void *arg_s, const void *arg_a, unsigned arg_k, unsigned arg_n,
                                                  unsigned arg_m, unsigned arg_spw, unsigned arg_act, void *arg_c, const float *arg_gs,
                                                  const void *arg_bias, float *arg_workspace, const unsigned block_x,
-                                                 const unsigned block_y, unsigned *arg_tickets = nullptr) {
+                                                 const unsigned block_y, unsigned *arg_tickets = nullptr, const RowIndex ix = RowIndex{}) {
     GemmArgs p;
     p.c = arg_c, p.a = arg_a, p.w = arg_w, p.s = arg_s, p.gs = arg_gs, p.bias = arg_bias, p.act = arg_act;
     p.workspace = arg_workspace, p.m = arg_m, p.n = arg_n, p.k = arg_k, p.spans_per_wave = arg_spw, p.flags = 0;
@@ -157,10 +158,10 @@ __device__ __forceinline__ void gemm_stream_body(const void *arg_w, const void *
             make_rsrc((const char *)p.w + (size_t)pt0 * w_row_bytes, span_tiles * w_row_bytes);
         const __amdgpu_buffer_rsrc_t s_rsrc =
             make_rsrc((const char *)p.s + (size_t)pt0 * s_row_bytes, span_tiles * s_row_bytes);
-        const char *a_base = (const char *)p.a + (size_t)m0 * p.k * 2;
+        const char *a_base = (const char *)p.a + (kIdx ? 0 : (size_t)m0 * p.k * 2);
         if constexpr (ABL & 32) // tools/ablate: every workgroup reads its own copy of A (is the shared A a hot spot in L2?)
             a_base += (size_t)(block_x & 63u) * p.m * p.k * 2;
-        const __amdgpu_buffer_rsrc_t a_rsrc = make_rsrc(a_base, rows * p.k * 2);
+        const __amdgpu_buffer_rsrc_t a_rsrc = make_rsrc(a_base, (kIdx ? ix.a_rows : rows) * p.k * 2);
 
         // Everything that decides validity lives in the VGPR offset (bounds
         // checked on every generation); the SGPR offset only walks along K.
@@ -172,8 +173,8 @@ __device__ __forceinline__ void gemm_stream_body(const void *arg_w, const void *
             s_voff[nt] = ((unsigned)nt < valid_nt) ? lane * kRecBytes + rel * s_row_bytes : kOob;
         }
 #pragma unroll
-        for (int mt = 0; mt < MT; ++mt)
-            a_voff[mt] = ((mt * 16 + r) * p.k + g * kLaneK) * 2; // rows >= M fall out of range
+        for (int mt = 0; mt < MT; ++mt) // rows >= M fall out of range (indexed: so do indices outside the descriptor)
+            a_voff[mt] = kIdx ? idx_a_off(ix, m0 + mt * 16 + r, p.m, p.k) + g * kLaneK * 2 : ((mt * 16 + r) * p.k + g * kLaneK) * 2;
 
         const unsigned kt_begin = sp_begin * KS;
 
@@ -184,6 +185,19 @@ __device__ __forceinline__ void gemm_stream_body(const void *arg_w, const void *
         constexpr int SL = Cfg::SL;                                    // tiles per stage
         constexpr int kAStageLoads = AM * SL / 4;                      // 1 KiB per wave-load
         u32x4 astage[kAStageLoads > 0 ? kAStageLoads : 1];             // next stage, in flight
+        // indexed: the staged rows' gathered offsets, read once -- wave-uniform per row (SL >= 4), per lane for SL == 2
+        [[maybe_unused]] unsigned a_irow[kIdx && AM > 0 ? (SL >= 4 ? AM : kAStageLoads) : 1];
+        if constexpr (kIdx && AM > 0) {
+            if constexpr (SL >= 4) {
+#pragma unroll
+                for (int rr = 0; rr < AM; ++rr)
+                    a_irow[rr] = __builtin_amdgcn_readfirstlane(idx_a_off(ix, m0 + rr, p.m, p.k));
+            } else {
+#pragma unroll
+                for (int i = 0; i < kAStageLoads; ++i)
+                    a_irow[i] = idx_a_off(ix, m0 + 2 * i + (lane >> 5), p.m, p.k) + (lane & 31u) * 16;
+            }
+        }
         // stage `st` = tiles [st*SL, st*SL + SL) of K (absolute index: span * (KS/SL) + stage in span)
         auto issue_a_stage = [&](unsigned st, bool ok) {
             (void)ok;
@@ -193,7 +207,9 @@ __device__ __forceinline__ void gemm_stream_body(const void *arg_w, const void *
                     unsigned vo;
                     if constexpr (SL >= 4) { // a row of the stage is SL/4 whole wave-loads
                         constexpr int kPerRow = SL / 4;
-                        vo = (i / kPerRow) * p.k * 2 + (i % kPerRow) * 1024 + lane * 16;
+                        vo = (kIdx ? a_irow[i / kPerRow] : (i / kPerRow) * p.k * 2) + (i % kPerRow) * 1024 + lane * 16;
+                    } else if constexpr (kIdx) {
+                        vo = a_irow[i];
                     } else { // SL == 2: one wave-load covers two rows of 512 B
                         vo = (2 * i + (lane >> 5)) * p.k * 2 + (lane & 31u) * 16;
                     }
@@ -572,7 +588,11 @@ __device__ __forceinline__ void gemm_stream_body(const void *arg_w, const void *
         const unsigned n = ntile * 16 + (il >> 4) * 4;
         if (m >= p.m || ntile >= ntiles)
             return;
-        if (gridDim.z == 1) {
+        if constexpr (kIdx) { // (MoE launches never split K) the scattered row; an index outside [0, c_rows) stores nothing
+            const unsigned cm = idx_c_row(ix, m);
+            if (cm != ~0u)
+                *reinterpret_cast<uint2 *>((char *)p.c + ((size_t)cm * p.n + n) * 2) = finish4<AT>(v, gs, p.bias, n);
+        } else if (gridDim.z == 1) {
             *reinterpret_cast<uint2 *>((char *)p.c + ((size_t)m * p.n + n) * 2) = finish4<AT>(v, gs, p.bias, n);
         } else {
             float *slab = p.workspace + ((size_t)blockIdx.z * p.m + m) * p.n + n;
@@ -595,7 +615,10 @@ __device__ __forceinline__ void gemm_stream_body(const void *arg_w, const void *
             return;
         const unsigned n_half = p.n >> 1;
         const unsigned n = (ntile >> 1) * 16 + (il >> 4) * 4;
-        *reinterpret_cast<uint2 *>((char *)p.c + ((size_t)m * n_half + n) * 2) =
+        const unsigned cm = kIdx ? idx_c_row(ix, m) : m;
+        if (kIdx && cm == ~0u)
+            return;
+        *reinterpret_cast<uint2 *>((char *)p.c + ((size_t)cm * n_half + n) * 2) =
             finish4_silu_mul<AT>(gate, up, gs, p.bias, n, n_half);
     };
 

@@ -53,9 +53,10 @@ template <class AT_, int FMT_, int KS_, int MT_, int NTW_, int WAVES_, int D_> s
 };
 
 // One workgroup tile (bn, bm) of C: bn = block along N, bm = block along M (gemm_tiled_kernel below takes them from its raster order,
-// the MoE form from its expert's rows: gemm_moe.hpp).
-template <class Cfg>
-__device__ __forceinline__ void gemm_tiled_body(const GemmArgs &p, const unsigned bn, const unsigned bm) {
+// the MoE form from its expert's rows: gemm_moe.hpp).  kIdx / ix: the indexed MoE form's row gather and scatter (device_common.hpp
+// RowIndex; p.a and p.c are then whole matrices).
+template <class Cfg, bool kIdx = false>
+__device__ __forceinline__ void gemm_tiled_body(const GemmArgs &p, const unsigned bn, const unsigned bm, const RowIndex ix = RowIndex{}) {
     using AT = typename Cfg::AT;
     using Frag = typename AT::frag;
     constexpr int FMT = Cfg::FMT, KS = Cfg::KS, MT = Cfg::MT, NTW = Cfg::NTW, WAVES = Cfg::WAVES, D = Cfg::D;
@@ -100,7 +101,8 @@ __device__ __forceinline__ void gemm_tiled_body(const GemmArgs &p, const unsigne
         make_rsrc((const char *)p.w + (size_t)pt0 * w_row_bytes, span_tiles * w_row_bytes);
     const __amdgpu_buffer_rsrc_t s_rsrc =
         make_rsrc((const char *)p.s + (size_t)pt0 * s_row_bytes, span_tiles * s_row_bytes);
-    const __amdgpu_buffer_rsrc_t a_rsrc = make_rsrc((const char *)p.a + (size_t)m0 * p.k * 2, rows * p.k * 2);
+    const __amdgpu_buffer_rsrc_t a_rsrc =
+        kIdx ? make_rsrc(p.a, ix.a_rows * p.k * 2) : make_rsrc((const char *)p.a + (size_t)m0 * p.k * 2, rows * p.k * 2);
 
     unsigned w_voff[NTW], s_voff[NTW];
 #pragma unroll
@@ -117,12 +119,20 @@ __device__ __forceinline__ void gemm_tiled_body(const GemmArgs &p, const unsigne
     static_assert((4 * WAVES) % 16 == 0, "direct-to-LDS staging: wave-loads must step by whole 16-row groups");
     const unsigned dma_row0 = wave * 4 + (lane >> 4);
     const unsigned dma_voff = dma_row0 * p.k * 2 + (((lane & 15u) ^ (dma_row0 & 15u)) * 16); // rows >= M: out of range -> zeros
+    // indexed: each wave-load's rows are gathered, so the row step moves from the SGPR into kDmaLoads VGPR offsets (read once here)
+    [[maybe_unused]] unsigned dma_vidx[kIdx ? kDmaLoads : 1];
+    if constexpr (kIdx) {
+#pragma unroll
+        for (int i = 0; i < kDmaLoads; ++i)
+            dma_vidx[i] = idx_a_off(ix, m0 + dma_row0 + i * (4 * WAVES), p.m, p.k) + (((lane & 15u) ^ (dma_row0 & 15u)) * 16);
+    }
     auto dma_a_tile = [&](u32x4 *dst, unsigned kt) {
 #pragma unroll
         for (int i = 0; i < kDmaLoads; ++i) {
 #if defined(__HIP_DEVICE_COMPILE__) // (the host pass knows neither the builtin nor the LDS address space)
             __builtin_amdgcn_raw_ptr_buffer_load_lds(a_rsrc, (__attribute__((address_space(3))) void *)(dst + (i * WAVES + wave) * 64),
-                                                     16, dma_voff, i * (4 * WAVES) * p.k * 2 + kt * 256, 0, 0);
+                                                     16, kIdx ? dma_vidx[i] : dma_voff, kIdx ? kt * 256 : i * (4 * WAVES) * p.k * 2 + kt * 256,
+                                                     0, 0);
 #else
             (void)dst, (void)kt;
 #endif
@@ -307,8 +317,9 @@ __device__ __forceinline__ void gemm_tiled_body(const GemmArgs &p, const unsigne
                 for (int nt = 0; nt < NTW; nt += 2) {
                     const unsigned m = m0 + mt * 16 + r;
                     const unsigned n = ((nt0 + nt) >> 1) * 16 + g * 4;
-                    if (m < p.m && (unsigned)nt < valid_nt)
-                        *reinterpret_cast<uint2 *>((char *)p.c + ((size_t)m * n_half + n) * 2) =
+                    const unsigned cm = (kIdx && m < p.m) ? idx_c_row(ix, m) : m;
+                    if (m < p.m && (unsigned)nt < valid_nt && (!kIdx || cm != ~0u))
+                        *reinterpret_cast<uint2 *>((char *)p.c + ((size_t)cm * n_half + n) * 2) =
                             finish4_silu_mul<AT>(acc[mt][nt], acc[mt][nt + 1], gs, p.bias, n, n_half);
                 }
         }
@@ -320,9 +331,10 @@ __device__ __forceinline__ void gemm_tiled_body(const GemmArgs &p, const unsigne
         for (int nt = 0; nt < NTW; ++nt) {
             const unsigned m = m0 + mt * 16 + r;
             const unsigned n = (nt0 + nt) * 16 + g * 4;
-            if (m < p.m && (unsigned)nt < valid_nt) {
+            const unsigned cm = (kIdx && m < p.m) ? idx_c_row(ix, m) : m;
+            if (m < p.m && (unsigned)nt < valid_nt && (!kIdx || cm != ~0u)) {
                 const f32x4 v = acc[mt][nt];
-                *reinterpret_cast<uint2 *>((char *)p.c + ((size_t)m * p.n + n) * 2) = finish4<AT>(v, gs, p.bias, n);
+                *reinterpret_cast<uint2 *>((char *)p.c + ((size_t)cm * p.n + n) * 2) = finish4<AT>(v, gs, p.bias, n);
             }
         }
 }

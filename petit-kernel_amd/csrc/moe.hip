@@ -1,5 +1,6 @@
 // moe.hip -- the routed-expert (MoE) entry points of include/petit_amd.h: argument checks, the pick, the launch (the kernels: gemm_moe.hpp,
-// instantiated by moe_tu.inc).  One pick (moe_choose) serves both the launcher and petit_gemm_moe_resolve_solution.
+// instantiated by moe_tu.inc).  One pick (moe_choose) serves the launcher, its indexed form (petit_gemm_fp4_fp16_moe_ex) and
+// petit_gemm_moe_resolve_solution.
 #include <hip/hip_runtime.h>
 
 #include "../../include/petit_amd.h"
@@ -90,6 +91,36 @@ int petit_gemm_fp4_fp16_moe(void *c, const void *a, const void *b, const void *s
     g.c = c, g.a = a, g.w = b, g.s = scales, g.gs = global_scales, g.bias = epilogue ? epilogue->bias : nullptr, g.act = act ? 1u : 0u;
     g.offsets = expert_offsets, g.num_experts = num_experts, g.m = m, g.n = n, g.k = k;
     return e->launch_moe(g, (hipStream_t)stream);
+}
+
+int petit_gemm_fp4_fp16_moe_ex(void *c, const void *a, const void *b, const void *scales, const float *global_scales,
+                               const int32_t *expert_offsets, unsigned num_experts, unsigned m, unsigned n, unsigned k,
+                               const int32_t *a_row_index, unsigned a_rows, const int32_t *c_row_index, unsigned c_rows,
+                               const petit_solution_hints *hints, uint64_t solution_id, const petit_epilogue *epilogue, void *stream) {
+    // a null index is the identity: the rows it would name must exist
+    if ((!a_row_index && a_rows < m) || (!c_row_index && c_rows < m))
+        return kErrProblemShape;
+    if (!a_row_index && !c_row_index)
+        return petit_gemm_fp4_fp16_moe(c, a, b, scales, global_scales, expert_offsets, num_experts, m, n, k, hints, solution_id, epilogue, stream);
+    Family fam;
+    bool act = false;
+    if (const int rc = moe_check(hints, num_experts, m, n, k, epilogue, &fam, &act))
+        return rc;
+    if (!c || !a || !b || !scales || !global_scales || !expert_offsets)
+        return kErrProblemShape;
+    // one descriptor bounds every A load, and the kernels' out-of-range voffset (2^31) must lie past its end (device_common.hpp RowIndex)
+    if ((uint64_t)a_rows * k * 2 > (1ull << 31))
+        return kErrProblemShape;
+    if (m == 0)
+        return kOk;
+    const SolutionEntry *e = moe_choose(fam, hints->a_type, canonical_b_type(hints->b_type), act, num_experts, m, n, k, solution_id);
+    if (!e || !e->launch_moe_idx)
+        return kErrKernelShape;
+    MoeArgs g{};
+    g.c = c, g.a = a, g.w = b, g.s = scales, g.gs = global_scales, g.bias = epilogue ? epilogue->bias : nullptr, g.act = act ? 1u : 0u;
+    g.offsets = expert_offsets, g.num_experts = num_experts, g.m = m, g.n = n, g.k = k;
+    g.a_idx = a_row_index, g.c_idx = c_row_index, g.a_rows = a_rows, g.c_rows = c_rows;
+    return e->launch_moe_idx(g, (hipStream_t)stream);
 }
 
 uint64_t petit_gemm_moe_resolve_solution(const petit_solution_hints *hints, unsigned num_experts, unsigned m, unsigned n, unsigned k,

@@ -1,6 +1,8 @@
 // Body of the MoE translation units (gemm_moe_<family>.hip): the MoE forms (gemm_moe.hpp) of the family's decode, staged streaming and
 // tiled kernels, for PETIT_TU_AT / PETIT_TU_FMT, exported as moe_forms_<family> (solutions.hip attaches them to the
-// table entries of the same shape).  Included exactly once per TU.
+// table entries of the same shape).  Included exactly once per TU.  With PETIT_TU_MOE_INDEXED (gemm_moe_idx_<family>.hip) the same
+// list of shapes gets the indexed forms instead (gathered A rows, scattered C rows: gemm_moe.hpp), exported as moe_idx_forms_<family>:
+// every kernel with a MoE form has an indexed one, and the pick is shared.
 #include "gemm_moe.hpp"
 #include "solution.h"
 #include "stream_instances.inc"
@@ -9,6 +11,13 @@ namespace petit_amd {
 namespace {
 
 // what the decode / tiled launches check besides the grid: SiLU-mul pairs the gate and the up tile inside one wave
+#ifdef PETIT_TU_MOE_INDEXED
+constexpr bool kIndexed = true;
+#else
+constexpr bool kIndexed = false;
+#endif
+RowIndex row_index(const MoeArgs &g) { return RowIndex{g.a_idx, g.c_idx, 0u, g.a_rows, g.c_rows}; }
+
 template <class Cfg> int launch_stream_moe(const MoeArgs &g, hipStream_t stream) {
     if (g.act && Cfg::NT % 2 != 0)
         return kErrKernelShape;
@@ -17,8 +26,12 @@ template <class Cfg> int launch_stream_moe(const MoeArgs &g, hipStream_t stream)
         return kErrKernelShape;
     const unsigned ntiles = g.n / kTileN, per_wg = Cfg::WN * Cfg::NT;
     const unsigned nspans = g.k / (kTileK * Cfg::KS);
-    hipLaunchKernelGGL(gemm_stream_moe_kernel<Cfg>, dim3((ntiles + per_wg - 1) / per_wg, slots), dim3(Cfg::kThreads), 0, stream, g.w, g.s, g.a, g.k,
-                       g.n, g.m, (nspans + Cfg::WK - 1) / Cfg::WK, g.act, g.c, g.gs, g.bias, g.offsets, g.num_experts);
+    if constexpr (kIndexed)
+        hipLaunchKernelGGL(gemm_stream_moe_idx_kernel<Cfg>, dim3((ntiles + per_wg - 1) / per_wg, slots), dim3(Cfg::kThreads), 0, stream, g.w, g.s, g.a,
+                           g.k, g.n, g.m, (nspans + Cfg::WK - 1) / Cfg::WK, g.act, g.c, g.gs, g.bias, g.offsets, g.num_experts, row_index(g));
+    else
+        hipLaunchKernelGGL(gemm_stream_moe_kernel<Cfg>, dim3((ntiles + per_wg - 1) / per_wg, slots), dim3(Cfg::kThreads), 0, stream, g.w, g.s, g.a,
+                           g.k, g.n, g.m, (nspans + Cfg::WK - 1) / Cfg::WK, g.act, g.c, g.gs, g.bias, g.offsets, g.num_experts);
     return hipGetLastError() == hipSuccess ? kOk : kErrLaunch;
 }
 
@@ -30,8 +43,12 @@ template <class Cfg> int launch_decode_moe(const MoeArgs &g, hipStream_t stream)
         return kErrKernelShape;
     const unsigned ntiles = g.n / kTileN;
     const unsigned nspans = g.k / (kTileK * Cfg::KS);
-    hipLaunchKernelGGL(gemm_decode_moe_kernel<Cfg>, dim3((ntiles + Cfg::NT - 1) / Cfg::NT, slots), dim3(Cfg::kThreads), 0, stream, g.w, g.s, g.a,
-                       g.k, g.n, g.m, (nspans + Cfg::WK - 1) / Cfg::WK, g.act, g.c, g.gs, g.bias, g.offsets, g.num_experts);
+    if constexpr (kIndexed)
+        hipLaunchKernelGGL(gemm_decode_moe_idx_kernel<Cfg>, dim3((ntiles + Cfg::NT - 1) / Cfg::NT, slots), dim3(Cfg::kThreads), 0, stream, g.w, g.s,
+                           g.a, g.k, g.n, g.m, (nspans + Cfg::WK - 1) / Cfg::WK, g.act, g.c, g.gs, g.bias, g.offsets, g.num_experts, row_index(g));
+    else
+        hipLaunchKernelGGL(gemm_decode_moe_kernel<Cfg>, dim3((ntiles + Cfg::NT - 1) / Cfg::NT, slots), dim3(Cfg::kThreads), 0, stream, g.w, g.s,
+                           g.a, g.k, g.n, g.m, (nspans + Cfg::WK - 1) / Cfg::WK, g.act, g.c, g.gs, g.bias, g.offsets, g.num_experts);
     return hipGetLastError() == hipSuccess ? kOk : kErrLaunch;
 }
 
@@ -47,8 +64,12 @@ template <class Cfg> int launch_tiled_moe(const MoeArgs &g, hipStream_t stream) 
     a.m = g.m, a.n = g.n, a.k = g.k;
     a.spans_per_wave = g.k / (kTileK * Cfg::KS); // (one K slice: the whole K range)
     a.flags = kFlagPrio;                         // (the raster order is the MoE kernel's own: no XCD raster bits)
-    hipLaunchKernelGGL(gemm_tiled_moe_kernel<Cfg>, dim3((ntiles + per_wg - 1) / per_wg, slots), dim3(Cfg::kThreads), 0, stream, a, g.offsets,
-                       g.num_experts);
+    if constexpr (kIndexed)
+        hipLaunchKernelGGL(gemm_tiled_moe_idx_kernel<Cfg>, dim3((ntiles + per_wg - 1) / per_wg, slots), dim3(Cfg::kThreads), 0, stream, a, g.offsets,
+                           g.num_experts, row_index(g));
+    else
+        hipLaunchKernelGGL(gemm_tiled_moe_kernel<Cfg>, dim3((ntiles + per_wg - 1) / per_wg, slots), dim3(Cfg::kThreads), 0, stream, a, g.offsets,
+                           g.num_experts);
     return hipGetLastError() == hipSuccess ? kOk : kErrLaunch;
 }
 

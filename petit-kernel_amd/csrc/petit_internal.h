@@ -91,6 +91,10 @@ struct MoeArgs {
     unsigned act;         // 0 none, 1 SiLU-mul (each expert's weight is [gate; up] along N)
     const int32_t *offsets; // [E + 1]
     unsigned num_experts, m, n, k;
+    // the indexed forms only (petit_gemm_fp4_fp16_moe_ex): grouped row r reads a row a_idx[r] of a [a_rows][k] and writes c row
+    // c_idx[r] of c [c_rows][.]; a null index is the identity
+    const int32_t *a_idx = nullptr, *c_idx = nullptr;
+    unsigned a_rows = 0, c_rows = 0;
 };
 // the grid rows a MoE launch needs for any routing (gemm_moe.hpp), 0 when that exceeds the grid's y limit
 inline unsigned moe_slots(unsigned m, unsigned bm, unsigned num_experts) {

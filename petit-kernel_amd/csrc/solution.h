@@ -117,6 +117,7 @@ struct SolutionEntry {
     LaunchFn launch;
     LaunchGroupedFn launch_grouped = nullptr; // the decode and the staged streaming kernels have one (M <= 16)
     LaunchMoeFn launch_moe = nullptr;         // the decode, staged streaming and tiled kernels of moe_tu.inc
+    LaunchMoeFn launch_moe_idx = nullptr;     // their indexed forms (gathered A, scattered C): set exactly where launch_moe is
 };
 
 // The MoE forms of a family: compiled in translation units of their own (gemm_moe_<family>.hip) and attached to the table entries of the
@@ -132,6 +133,10 @@ const MoeForm *moe_forms_nv_bf16(int *count);
 const MoeForm *moe_forms_nv_f16(int *count);
 const MoeForm *moe_forms_mx_bf16(int *count);
 const MoeForm *moe_forms_mx_f16(int *count);
+const MoeForm *moe_idx_forms_nv_bf16(int *count);
+const MoeForm *moe_idx_forms_nv_f16(int *count);
+const MoeForm *moe_idx_forms_mx_bf16(int *count);
+const MoeForm *moe_idx_forms_mx_f16(int *count);
 
 // one table per (activation type, weight format) family, concatenated once (solutions.hip) from the parts its translation units export
 // (stream_tu.inc: gemm_<family>_p<part>.hip)

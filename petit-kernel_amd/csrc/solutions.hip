@@ -22,7 +22,8 @@ namespace petit_amd {
 // The family's MoE forms (gemm_moe_<family>.hip) are attached to the entries of the same shape.
 using PartFn = const SolutionEntry *(*)(int *);
 using MoeFormsFn = const MoeForm *(*)(int *);
-static const SolutionEntry *concat_parts(std::vector<SolutionEntry> &store, std::initializer_list<PartFn> parts, MoeFormsFn moe, int *count) {
+static const SolutionEntry *concat_parts(std::vector<SolutionEntry> &store, std::initializer_list<PartFn> parts, MoeFormsFn moe, MoeFormsFn moe_idx,
+                                         int *count) {
     if (store.empty()) {
         for (PartFn fn : parts) {
             int n = 0;
@@ -35,16 +36,21 @@ static const SolutionEntry *concat_parts(std::vector<SolutionEntry> &store, std:
             for (SolutionEntry &e : store)
                 if (forms[i].launch && same_shape(e.shape, forms[i].shape))
                     e.launch_moe = forms[i].launch;
+        const MoeForm *idx_forms = moe_idx(&nf); // (the same shapes: moe_tu.inc)
+        for (int i = 0; i < nf; ++i)
+            for (SolutionEntry &e : store)
+                if (idx_forms[i].launch && same_shape(e.shape, idx_forms[i].shape))
+                    e.launch_moe_idx = idx_forms[i].launch;
     }
     *count = (int)store.size();
     return store.data();
 }
-#define PETIT_FAMILY_TABLE(fam, ...)                                                                          \
-    const SolutionEntry *solutions_##fam(int *count) {                                                        \
-        static std::vector<SolutionEntry> store;                                                              \
-        static const SolutionEntry *const table = concat_parts(store, {__VA_ARGS__}, moe_forms_##fam, count); \
-        *count = (int)store.size();                                                                           \
-        return table;                                                                                         \
+#define PETIT_FAMILY_TABLE(fam, ...)                                                                                               \
+    const SolutionEntry *solutions_##fam(int *count) {                                                                             \
+        static std::vector<SolutionEntry> store;                                                                                   \
+        static const SolutionEntry *const table = concat_parts(store, {__VA_ARGS__}, moe_forms_##fam, moe_idx_forms_##fam, count); \
+        *count = (int)store.size();                                                                                                \
+        return table;                                                                                                              \
     }
 PETIT_FAMILY_TABLE(nv_bf16, solutions_nv_bf16_p1, solutions_nv_bf16_p2, solutions_nv_bf16_p3, solutions_nv_bf16_p4, solutions_nv_bf16_p5, solutions_nv_bf16_p6)
 PETIT_FAMILY_TABLE(nv_f16, solutions_nv_f16_p1, solutions_nv_f16_p2, solutions_nv_f16_p3, solutions_nv_f16_p4, solutions_nv_f16_p5, solutions_nv_f16_p6)

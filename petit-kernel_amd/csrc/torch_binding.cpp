@@ -181,6 +181,127 @@ at::Tensor mul_mxfp4_a16_moe(const at::Tensor &A, const at::Tensor &B, const at:
     return mul_a16_moe(true, A, B, s, gs, off, m, n, k, e, solution_id, bias, activation);
 }
 
+// indexed MoE launch (row gather on A, row scatter on C: petit_gemm_fp4_fp16_moe_ex); the same checks and texts as petit_kernel/ops.py
+// _mul_moe_indexed.  out: the _out op's destination (rows no index names stay untouched), else a new [c_rows, n_out] tensor.
+at::Tensor mul_a16_moe_indexed_impl(bool mx, const at::Tensor &A, const at::Tensor &B, const at::Tensor &s, const at::Tensor &global_scales,
+                                    const at::Tensor &expert_offsets, int64_t size_m, int64_t size_n, int64_t size_k, int64_t num_experts,
+                                    const std::optional<at::Tensor> &a_row_index, const std::optional<at::Tensor> &c_row_index, int64_t c_rows,
+                                    int64_t solution_id, const std::optional<at::Tensor> &bias, int64_t activation, const at::Tensor *out) {
+    const int64_t group = mx ? 32 : 16, E = num_experts;
+    TORCH_CHECK(A.scalar_type() == at::kBFloat16 || A.scalar_type() == at::kHalf, "A must be bfloat16 or float16.");
+    TORCH_CHECK(E >= 1 && E <= PETIT_MOE_MAX_EXPERTS, "num_experts must be in 1..", PETIT_MOE_MAX_EXPERTS, ", got ", E);
+    TORCH_CHECK(A.is_cuda() && B.is_cuda() && s.is_cuda() && global_scales.is_cuda() && expert_offsets.is_cuda(), "all tensors must be on GPU");
+    TORCH_CHECK(A.is_contiguous() && size_k > 0 && A.numel() % size_k == 0, "A must be a contiguous [a_rows, size_k] tensor");
+    TORCH_CHECK(B.is_contiguous() && B.numel() * B.element_size() == E * size_n * size_k / 2,
+                "B does not hold num_experts * size_n * size_k packed 4-bit weights");
+    TORCH_CHECK(s.is_contiguous() && s.numel() * s.element_size() == E * size_n * size_k / group, "s does not hold num_experts * size_n * size_k / ",
+                group, " scales");
+    TORCH_CHECK(global_scales.scalar_type() == at::kFloat && global_scales.is_contiguous() && global_scales.numel() == E,
+                "global_scales must be a contiguous float32 [num_experts] tensor");
+    TORCH_CHECK(expert_offsets.scalar_type() == at::kInt && expert_offsets.is_contiguous() && expert_offsets.numel() == E + 1,
+                "expert_offsets must be a contiguous int32 [num_experts + 1] tensor");
+    for (const auto *idx : {&a_row_index, &c_row_index})
+        if (idx->has_value())
+            TORCH_CHECK((*idx)->is_cuda() && (*idx)->device() == A.device() && (*idx)->scalar_type() == at::kInt && (*idx)->is_contiguous() &&
+                            (*idx)->numel() == size_m,
+                        "row indices must be contiguous int32 [size_m] tensors on A's device");
+    TORCH_CHECK(activation == 0 || activation == 1, "activation must be 0 (none) or 1 (silu_mul)");
+    if (activation)
+        TORCH_CHECK(size_n % 32 == 0, "silu_mul needs size_n % 32 == 0 (gate / up halves of whole tiles), got ", size_n);
+    if (bias.has_value())
+        TORCH_CHECK(bias->is_cuda() && bias->device() == A.device() && bias->scalar_type() == A.scalar_type() && bias->is_contiguous() &&
+                        bias->numel() == E * size_n,
+                    "bias must be a contiguous [num_experts, size_n] tensor of A's dtype on A's device");
+    const int64_t a_rows = A.numel() / size_k, n_out = activation ? size_n / 2 : size_n;
+    const c10::hip::HIPGuardMasqueradingAsCUDA guard(A.device());
+    at::Tensor c;
+    if (out) {
+        TORCH_CHECK(out->is_cuda() && out->device() == A.device() && out->scalar_type() == A.scalar_type() && out->is_contiguous() && out->dim() == 2 &&
+                        out->size(1) == n_out,
+                    "out must be a contiguous [c_rows, n_out] tensor of A's dtype on A's device");
+        TORCH_CHECK(c_rows < 0 || c_rows == out->size(0), "c_rows does not match out.size(0)");
+        c = *out;
+        c_rows = out->size(0);
+    } else {
+        c_rows = c_rows < 0 ? size_m : c_rows;
+        c = at::empty({c_rows, n_out}, A.options());
+    }
+    const int a_type = A.scalar_type() == at::kBFloat16 ? kCxxBf16 : kCxxFp16;
+    const petit_solution_hints hints{a_type, mx ? kCxxMxFp4 : kCxxFp4, a_type, 0};
+    const uint64_t sid = (solution_id < 0 && solution_id >= -4096) ? PETIT_SOLUTION_AUTO : (uint64_t)solution_id;
+    const petit_epilogue epi{bias.has_value() ? bias->data_ptr() : nullptr, (int32_t)activation, 0};
+    const int rc = petit_gemm_fp4_fp16_moe_ex(c.data_ptr(), A.data_ptr(), B.data_ptr(), s.data_ptr(), (const float *)global_scales.data_ptr(),
+                                              (const int32_t *)expert_offsets.data_ptr(), (unsigned)E, (unsigned)size_m, (unsigned)size_n,
+                                              (unsigned)size_k, a_row_index.has_value() ? (const int32_t *)a_row_index->data_ptr() : nullptr,
+                                              (unsigned)a_rows, c_row_index.has_value() ? (const int32_t *)c_row_index->data_ptr() : nullptr,
+                                              (unsigned)c_rows, &hints, sid, (bias.has_value() || activation) ? &epi : nullptr, stream_of(A));
+    TORCH_CHECK(rc != PETIT_ERROR_PROBLEM_SHAPE, "Incompatible problem shape (m=", size_m, ", n=", size_n, ", k=", size_k, ", num_experts=", E,
+                ", a_rows=", a_rows, ", c_rows=", c_rows, ")");
+    TORCH_CHECK(rc != PETIT_ERROR_KERNEL_SHAPE, "No kernel implementation for solution_id=", sid == PETIT_SOLUTION_AUTO ? "-1" : std::to_string((int64_t)sid), ".");
+    TORCH_CHECK(rc == PETIT_OK, mx ? "mul_mxfp4_a16_moe_indexed: " : "mul_nvfp4_a16_moe_indexed: ", petit_error_string(rc));
+    return c;
+}
+#define PETIT_MOE_INDEXED_ARGS                                                                                                                   \
+    const at::Tensor &A, const at::Tensor &B, const at::Tensor &s, const at::Tensor &gs, const at::Tensor &off, int64_t m, int64_t n, int64_t k, \
+        int64_t e, const std::optional<at::Tensor> &a_idx, const std::optional<at::Tensor> &c_idx, int64_t c_rows, int64_t solution_id,         \
+        const std::optional<at::Tensor> &bias, int64_t activation
+at::Tensor mul_nvfp4_a16_moe_indexed(PETIT_MOE_INDEXED_ARGS) {
+    return mul_a16_moe_indexed_impl(false, A, B, s, gs, off, m, n, k, e, a_idx, c_idx, c_rows, solution_id, bias, activation, nullptr);
+}
+at::Tensor mul_mxfp4_a16_moe_indexed(PETIT_MOE_INDEXED_ARGS) {
+    return mul_a16_moe_indexed_impl(true, A, B, s, gs, off, m, n, k, e, a_idx, c_idx, c_rows, solution_id, bias, activation, nullptr);
+}
+void mul_nvfp4_a16_moe_indexed_out(const at::Tensor &out, PETIT_MOE_INDEXED_ARGS) {
+    mul_a16_moe_indexed_impl(false, A, B, s, gs, off, m, n, k, e, a_idx, c_idx, c_rows, solution_id, bias, activation, &out);
+}
+void mul_mxfp4_a16_moe_indexed_out(const at::Tensor &out, PETIT_MOE_INDEXED_ARGS) {
+    mul_a16_moe_indexed_impl(true, A, B, s, gs, off, m, n, k, e, a_idx, c_idx, c_rows, solution_id, bias, activation, &out);
+}
+
+// device routing (petit_moe_align / petit_moe_combine); the same checks and texts as petit_kernel/ops.py
+void check_topk_ids(const at::Tensor &ids, int64_t num_experts) {
+    TORCH_CHECK(num_experts >= 1 && num_experts <= PETIT_MOE_MAX_EXPERTS, "num_experts must be in 1..", PETIT_MOE_MAX_EXPERTS, ", got ", num_experts);
+    TORCH_CHECK(ids.is_cuda() && ids.dim() == 2 && ids.is_contiguous() && (ids.scalar_type() == at::kInt || ids.scalar_type() == at::kLong),
+                "topk_ids must be a contiguous int32 / int64 [num_tokens, topk] GPU tensor");
+    TORCH_CHECK(ids.size(1) >= 1, "topk must be >= 1");
+}
+std::tuple<at::Tensor, at::Tensor, at::Tensor> moe_align_device(const at::Tensor &topk_ids, int64_t num_experts) {
+    check_topk_ids(topk_ids, num_experts);
+    const int64_t T = topk_ids.size(0), topk = topk_ids.size(1);
+    const c10::hip::HIPGuardMasqueradingAsCUDA guard(topk_ids.device());
+    const auto i32 = topk_ids.options().dtype(at::kInt);
+    at::Tensor sorted_pos = at::empty({T * topk}, i32), token_index = at::empty({T * topk}, i32), offsets = at::empty({num_experts + 1}, i32);
+    const uint64_t ws_bytes = petit_moe_align_workspace_bytes((unsigned)T, (unsigned)topk, (unsigned)num_experts);
+    at::Tensor ws = at::empty({(int64_t)ws_bytes}, topk_ids.options().dtype(at::kByte));
+    const int rc = petit_moe_align(topk_ids.data_ptr(), topk_ids.scalar_type() == at::kLong, (unsigned)T, (unsigned)topk, (unsigned)num_experts,
+                                   (int32_t *)offsets.data_ptr(), (int32_t *)sorted_pos.data_ptr(), (int32_t *)token_index.data_ptr(),
+                                   ws_bytes ? ws.data_ptr() : nullptr, stream_of(topk_ids));
+    TORCH_CHECK(rc != PETIT_ERROR_PROBLEM_SHAPE, "Incompatible routing shape (num_tokens=", T, ", topk=", topk, ", num_experts=", num_experts, ")");
+    TORCH_CHECK(rc == PETIT_OK, "moe_align_device: ", petit_error_string(rc));
+    return {sorted_pos, offsets, token_index};
+}
+at::Tensor moe_combine(const at::Tensor &slot_out, const at::Tensor &topk_weights, const at::Tensor &topk_ids, int64_t num_experts) {
+    check_topk_ids(topk_ids, num_experts);
+    const int64_t T = topk_ids.size(0), topk = topk_ids.size(1);
+    TORCH_CHECK(slot_out.is_cuda() && slot_out.device() == topk_ids.device() &&
+                    (slot_out.scalar_type() == at::kBFloat16 || slot_out.scalar_type() == at::kHalf) && slot_out.is_contiguous() &&
+                    slot_out.dim() == 2 && slot_out.size(0) == T * topk,
+                "slot_out must be a contiguous bfloat16 / float16 [num_tokens * topk, n] tensor on topk_ids' device");
+    TORCH_CHECK(topk_weights.is_cuda() && topk_weights.device() == topk_ids.device() && topk_weights.scalar_type() == at::kFloat &&
+                    topk_weights.is_contiguous() && topk_weights.sizes() == topk_ids.sizes(),
+                "topk_weights must be a contiguous float32 [num_tokens, topk] tensor");
+    const int64_t n = slot_out.size(1);
+    TORCH_CHECK(n % 8 == 0, "n must be a multiple of 8, got ", n);
+    const c10::hip::HIPGuardMasqueradingAsCUDA guard(slot_out.device());
+    at::Tensor out = at::empty({T, n}, slot_out.options());
+    const int rc = petit_moe_combine(out.data_ptr(), slot_out.data_ptr(), (const float *)topk_weights.data_ptr(), topk_ids.data_ptr(),
+                                     topk_ids.scalar_type() == at::kLong, (unsigned)T, (unsigned)topk, (unsigned)n, (unsigned)num_experts,
+                                     slot_out.scalar_type() == at::kBFloat16 ? kCxxBf16 : kCxxFp16, stream_of(slot_out));
+    TORCH_CHECK(rc != PETIT_ERROR_PROBLEM_SHAPE, "Incompatible routing shape (num_tokens=", T, ", topk=", topk, ", n=", n, ", num_experts=", num_experts, ")");
+    TORCH_CHECK(rc == PETIT_OK, "moe_combine: ", petit_error_string(rc));
+    return out;
+}
+
 // Shape functions for the Meta key (FakeTensor / torch.compile tracing, torch.export): outputs of the right shape, dtype and
 // device, nothing launched -- the ops trace as opaque calls instead of breaking the graph.
 at::Tensor repack_nvfp4_meta(const at::Tensor &q, int64_t n, int64_t k) { return at::empty({n / kLayoutN, k * kLayoutN / kPack}, q.options()); }
@@ -195,6 +316,20 @@ at::Tensor mul_a16_moe_meta(const at::Tensor &A, const at::Tensor &, const at::T
                             int64_t, int64_t, int64_t, const std::optional<at::Tensor> &, int64_t activation) {
     TORCH_CHECK(A.scalar_type() == at::kBFloat16 || A.scalar_type() == at::kHalf, "A must be bfloat16 or float16.");
     return at::empty({m, activation ? n / 2 : n}, A.options());
+}
+
+at::Tensor mul_a16_moe_indexed_meta(PETIT_MOE_INDEXED_ARGS) {
+    TORCH_CHECK(A.scalar_type() == at::kBFloat16 || A.scalar_type() == at::kHalf, "A must be bfloat16 or float16.");
+    return at::empty({c_rows < 0 ? m : c_rows, activation ? n / 2 : n}, A.options());
+}
+void mul_a16_moe_indexed_out_meta(const at::Tensor &, PETIT_MOE_INDEXED_ARGS) {}
+std::tuple<at::Tensor, at::Tensor, at::Tensor> moe_align_device_meta(const at::Tensor &topk_ids, int64_t num_experts) {
+    const auto i32 = topk_ids.options().dtype(at::kInt);
+    const int64_t entries = topk_ids.size(0) * topk_ids.size(1);
+    return {at::empty({entries}, i32), at::empty({num_experts + 1}, i32), at::empty({entries}, i32)};
+}
+at::Tensor moe_combine_meta(const at::Tensor &slot_out, const at::Tensor &, const at::Tensor &topk_ids, int64_t) {
+    return at::empty({topk_ids.size(0), slot_out.size(1)}, slot_out.options());
 }
 
 } // namespace
@@ -214,6 +349,15 @@ TORCH_LIBRARY(petit_kernel, m) {
           "int num_experts, int solution_id=-1, Tensor? bias=None, int activation=0) -> Tensor");
     m.def("mul_mxfp4_a16_moe(Tensor A, Tensor B, Tensor s, Tensor global_scales, Tensor expert_offsets, int size_m, int size_n, int size_k, "
           "int num_experts, int solution_id=-1, Tensor? bias=None, int activation=0) -> Tensor");
+#define PETIT_MOE_INDEXED_SCHEMA                                                                                                          \
+    "Tensor A, Tensor B, Tensor s, Tensor global_scales, Tensor expert_offsets, int size_m, int size_n, int size_k, int num_experts, " \
+    "Tensor? a_row_index=None, Tensor? c_row_index=None, int c_rows=-1, int solution_id=-1, Tensor? bias=None, int activation=0"
+    m.def("mul_nvfp4_a16_moe_indexed(" PETIT_MOE_INDEXED_SCHEMA ") -> Tensor");
+    m.def("mul_mxfp4_a16_moe_indexed(" PETIT_MOE_INDEXED_SCHEMA ") -> Tensor");
+    m.def("mul_nvfp4_a16_moe_indexed_out(Tensor(a!) out, " PETIT_MOE_INDEXED_SCHEMA ") -> ()");
+    m.def("mul_mxfp4_a16_moe_indexed_out(Tensor(a!) out, " PETIT_MOE_INDEXED_SCHEMA ") -> ()");
+    m.def("moe_align_device(Tensor topk_ids, int num_experts) -> (Tensor, Tensor, Tensor)");
+    m.def("moe_combine(Tensor slot_out, Tensor topk_weights, Tensor topk_ids, int num_experts) -> Tensor");
     // round 3's op name (scales promised inside fp16's range): an alias of mul_mxfp4_a16 for one more round -- the kernels test the range themselves
     m.def("mul_mxfp4_a16_f16range(Tensor A, Tensor B, Tensor s, Tensor global_scale, int size_m, int size_n, int size_k, int solution_id, "
           "Tensor? bias=None, int activation=0) -> Tensor");
@@ -226,7 +370,13 @@ TORCH_LIBRARY(petit_kernel, m) {
     m.impl("mul_mxfp4_a16", &mul_mxfp4_a16);                    \
     m.impl("mul_mxfp4_a16_f16range", &mul_mxfp4_a16);          \
     m.impl("mul_nvfp4_a16_moe", &mul_nvfp4_a16_moe);            \
-    m.impl("mul_mxfp4_a16_moe", &mul_mxfp4_a16_moe);
+    m.impl("mul_mxfp4_a16_moe", &mul_mxfp4_a16_moe);            \
+    m.impl("mul_nvfp4_a16_moe_indexed", &mul_nvfp4_a16_moe_indexed); \
+    m.impl("mul_mxfp4_a16_moe_indexed", &mul_mxfp4_a16_moe_indexed); \
+    m.impl("mul_nvfp4_a16_moe_indexed_out", &mul_nvfp4_a16_moe_indexed_out); \
+    m.impl("mul_mxfp4_a16_moe_indexed_out", &mul_mxfp4_a16_moe_indexed_out); \
+    m.impl("moe_align_device", &moe_align_device);              \
+    m.impl("moe_combine", &moe_combine);
 TORCH_LIBRARY_IMPL(petit_kernel, CUDA, m) { PETIT_IMPL_REAL(m) }
 TORCH_LIBRARY_IMPL(petit_kernel, CPU, m) { PETIT_IMPL_REAL(m) }
 TORCH_LIBRARY_IMPL(petit_kernel, Meta, m) {
@@ -238,4 +388,10 @@ TORCH_LIBRARY_IMPL(petit_kernel, Meta, m) {
     m.impl("mul_mxfp4_a16_f16range", &mul_a16_meta);
     m.impl("mul_nvfp4_a16_moe", &mul_a16_moe_meta);
     m.impl("mul_mxfp4_a16_moe", &mul_a16_moe_meta);
+    m.impl("mul_nvfp4_a16_moe_indexed", &mul_a16_moe_indexed_meta);
+    m.impl("mul_mxfp4_a16_moe_indexed", &mul_a16_moe_indexed_meta);
+    m.impl("mul_nvfp4_a16_moe_indexed_out", &mul_a16_moe_indexed_out_meta);
+    m.impl("mul_mxfp4_a16_moe_indexed_out", &mul_a16_moe_indexed_out_meta);
+    m.impl("moe_align_device", &moe_align_device_meta);
+    m.impl("moe_combine", &moe_combine_meta);
 }

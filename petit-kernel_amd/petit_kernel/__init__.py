@@ -13,7 +13,7 @@ import enum
 import torch
 
 from . import compiled, offline, ops, tuning
-from .moe import fp4_moe, moe_align
+from .moe import fp4_moe, fp4_moe_fused, moe_align
 from .ops import QuantizedActivations, mul_fp4_a16_grouped, mul_mxfp4_native, quantize_activations
 from .ops import attach_nvfp4_native, mul_nvfp4_native, nvfp4_native_image
 from .tuning import tune, tune_tensors
@@ -106,6 +106,35 @@ def mul_mxfp4_a16_moe(a: torch.Tensor, b: torch.Tensor, s: torch.Tensor, global_
     return _impl.mul_mxfp4_a16_moe(a, b, s, global_scales, expert_offsets, size_m, size_n, size_k, num_experts, solution_id, bias, activation)
 
 
+def mul_nvfp4_a16_moe_indexed(a: torch.Tensor, b: torch.Tensor, s: torch.Tensor, global_scales: torch.Tensor, expert_offsets: torch.Tensor,
+                              size_m: int, size_n: int, size_k: int, num_experts: int, a_row_index: torch.Tensor = None,
+                              c_row_index: torch.Tensor = None, c_rows: int = None, solution_id: int = -1, bias: torch.Tensor = None,
+                              activation: str = None, out: torch.Tensor = None) -> torch.Tensor:
+    # the MoE launch on gathered rows of `a` ([a_rows, size_k]: grouped row r reads a[a_row_index[r]]) writing scattered rows of the output
+    # ([c_rows, n_out]: grouped row r writes row c_row_index[r]); None is the identity; int32 [size_m] device indices, never read by the host.
+    # An index outside the matrix reads zeros / stores nothing.  out: write into this tensor (rows no index names stay untouched).
+    return _impl.mul_nvfp4_a16_moe_indexed(a, b, s, global_scales, expert_offsets, size_m, size_n, size_k, num_experts, a_row_index, c_row_index,
+                                           c_rows, solution_id, bias, activation, out)
+
+
+def mul_mxfp4_a16_moe_indexed(a: torch.Tensor, b: torch.Tensor, s: torch.Tensor, global_scales: torch.Tensor, expert_offsets: torch.Tensor,
+                              size_m: int, size_n: int, size_k: int, num_experts: int, a_row_index: torch.Tensor = None,
+                              c_row_index: torch.Tensor = None, c_rows: int = None, solution_id: int = -1, bias: torch.Tensor = None,
+                              activation: str = None, out: torch.Tensor = None) -> torch.Tensor:
+    return _impl.mul_mxfp4_a16_moe_indexed(a, b, s, global_scales, expert_offsets, size_m, size_n, size_k, num_experts, a_row_index, c_row_index,
+                                           c_rows, solution_id, bias, activation, out)
+
+
+def moe_align_device(topk_ids: torch.Tensor, num_experts: int):
+    # moe_align on the device: (sorted_pos, expert_offsets, token_index), int32; ids outside [0, E) are not routed
+    return _impl.moe_align_device(topk_ids, num_experts)
+
+
+def moe_combine(slot_out: torch.Tensor, topk_weights: torch.Tensor, topk_ids: torch.Tensor, num_experts: int) -> torch.Tensor:
+    # the deterministic top-k reduce of a MoE layer (fp32, fixed order, no FMA contraction, one RNE rounding)
+    return _impl.moe_combine(slot_out, topk_weights, topk_ids, num_experts)
+
+
 def moe_resolve_solution(hints: PetitSolutionHints, num_experts: int, size_m: int, size_n: int, size_k: int, solution_id: int = -1,
                          activation: str = None) -> int:
     return ops.moe_resolve_solution(hints, num_experts, size_m, size_n, size_k, solution_id, activation)
@@ -135,6 +164,11 @@ __all__ = [
     "moe_resolve_solution",
     "moe_align",
     "fp4_moe",
+    "fp4_moe_fused",
+    "mul_nvfp4_a16_moe_indexed",
+    "mul_mxfp4_a16_moe_indexed",
+    "moe_align_device",
+    "moe_combine",
     "mul_mxfp4_native",
     "nvfp4_native_image",
     "attach_nvfp4_native",

@@ -107,6 +107,11 @@ _SIGNATURES = {
     "petit_gemm_fp4_fp16_moe": (C.c_int, [C.c_void_p] * 6 + [C.c_uint] * 4 + [C.POINTER(SolutionHints), C.c_uint64, C.POINTER(Epilogue),
                                           C.c_void_p]),
     "petit_gemm_moe_resolve_solution": (C.c_uint64, [C.POINTER(SolutionHints)] + [C.c_uint] * 4 + [C.c_uint64, C.POINTER(Epilogue)]),
+    "petit_gemm_fp4_fp16_moe_ex": (C.c_int, [C.c_void_p] * 6 + [C.c_uint] * 4 + [C.c_void_p, C.c_uint, C.c_void_p, C.c_uint] +
+                                   [C.POINTER(SolutionHints), C.c_uint64, C.POINTER(Epilogue), C.c_void_p]),
+    "petit_moe_align_workspace_bytes": (C.c_uint64, [C.c_uint] * 3),
+    "petit_moe_align": (C.c_int, [C.c_void_p, C.c_int] + [C.c_uint] * 3 + [C.c_void_p] * 5),
+    "petit_moe_combine": (C.c_int, [C.c_void_p] * 4 + [C.c_int] + [C.c_uint] * 4 + [C.c_int, C.c_void_p]),
     "petit_gemm_mxfp4_native": (C.c_int, [C.c_void_p] * 5 + [C.c_uint] * 3 + [C.POINTER(SolutionHints), C.c_uint64, C.POINTER(Epilogue),
                                           C.POINTER(NativeArgs), C.c_void_p, C.c_uint64, C.c_void_p]),
     "petit_nvfp4_native_image_bytes": (C.c_uint64, [C.c_uint, C.c_uint]),

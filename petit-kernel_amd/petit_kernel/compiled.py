@@ -93,3 +93,34 @@ def mul_nvfp4_a16_moe(A, B, s, global_scales, expert_offsets, size_m, size_n, si
 def mul_mxfp4_a16_moe(A, B, s, global_scales, expert_offsets, size_m, size_n, size_k, num_experts, solution_id=-1, bias=None, activation=None):
     return torch.ops.petit_kernel.mul_mxfp4_a16_moe(A, B, s, global_scales, expert_offsets, size_m, size_n, size_k, num_experts, _sid(solution_id),
                                                     bias, _act(activation))
+
+
+def _mul_moe_indexed(kind, A, B, s, global_scales, expert_offsets, size_m, size_n, size_k, num_experts, a_row_index, c_row_index, c_rows,
+                     solution_id, bias, activation, out):
+    c_rows = -1 if c_rows is None else int(c_rows)
+    args = (A, B, s, global_scales, expert_offsets, size_m, size_n, size_k, num_experts, a_row_index, c_row_index, c_rows, _sid(solution_id), bias,
+            _act(activation))
+    if out is None:
+        return getattr(torch.ops.petit_kernel, f"mul_{kind}fp4_a16_moe_indexed")(*args)
+    getattr(torch.ops.petit_kernel, f"mul_{kind}fp4_a16_moe_indexed_out")(out, *args)
+    return out
+
+
+def mul_nvfp4_a16_moe_indexed(A, B, s, global_scales, expert_offsets, size_m, size_n, size_k, num_experts, a_row_index=None, c_row_index=None,
+                              c_rows=None, solution_id=-1, bias=None, activation=None, out=None):
+    return _mul_moe_indexed("nv", A, B, s, global_scales, expert_offsets, size_m, size_n, size_k, num_experts, a_row_index, c_row_index, c_rows,
+                            solution_id, bias, activation, out)
+
+
+def mul_mxfp4_a16_moe_indexed(A, B, s, global_scales, expert_offsets, size_m, size_n, size_k, num_experts, a_row_index=None, c_row_index=None,
+                              c_rows=None, solution_id=-1, bias=None, activation=None, out=None):
+    return _mul_moe_indexed("mx", A, B, s, global_scales, expert_offsets, size_m, size_n, size_k, num_experts, a_row_index, c_row_index, c_rows,
+                            solution_id, bias, activation, out)
+
+
+def moe_align_device(topk_ids, num_experts):
+    return torch.ops.petit_kernel.moe_align_device(topk_ids, num_experts)
+
+
+def moe_combine(slot_out, topk_weights, topk_ids, num_experts):
+    return torch.ops.petit_kernel.moe_combine(slot_out, topk_weights, topk_ids, num_experts)

@@ -3,6 +3,11 @@
 `moe_align` sorts the (token, slot) pairs of a top-k routing by expert and counts them per expert -- torch ops only, no host sync, so the
 whole layer can be captured in a graph and replayed with a different routing.  `fp4_moe` runs gate_up (fused SiLU-mul) and down as one
 MoE launch each; the router weighting and the top-k combine are torch plumbing, in fp32, in a fixed order (deterministic).
+
+`fp4_moe_fused` is the same layer in four launches of the library's own (one to three for the align, then gate_up, down, combine): the
+align runs on the device, gate_up reads the token rows through the sorted index (no gathered copy of the activations), down writes each
+(token, slot) result straight to its slot, and a deterministic top-k reduce finishes the layer.  Ids of -1 (experts that are not local
+under expert parallelism) are skipped.
 """
 from __future__ import annotations
 
@@ -49,3 +54,27 @@ def fp4_moe(hidden: torch.Tensor, w13: torch.Tensor, s13: torch.Tensor, gs13: to
     buf = torch.empty((m, H), dtype=torch.float32, device=hidden.device)
     buf.index_copy_(0, sorted_idx, y.float() * w[:, None])                                # every (token, slot) position exactly once
     return buf.view(T, topk, H).sum(dim=1).to(hidden.dtype)
+
+
+def fp4_moe_fused(hidden: torch.Tensor, w13: torch.Tensor, s13: torch.Tensor, gs13: torch.Tensor, w2: torch.Tensor, s2: torch.Tensor,
+                  gs2: torch.Tensor, topk_weights: torch.Tensor, topk_ids: torch.Tensor, kind: str = "nvfp4") -> torch.Tensor:
+    """fp4_moe's layer (same arguments, same result up to the combine's rounding order) on the indexed MoE launches: align on the device,
+    gate_up on gathered rows, down scattered into slot order, the top-k combine.  topk_ids: int32 or int64 [T, topk]; entries outside
+    [0, E) (-1 under expert parallelism) contribute nothing.  topk_weights: float32 or bfloat16 [T, topk] (converted to float32 once).
+    No host sync: capturable in a graph and replayable with any routing of the same shape."""
+    from . import moe_align_device, moe_combine, mul_mxfp4_a16_moe_indexed, mul_nvfp4_a16_moe_indexed
+    if kind not in ("nvfp4", "mxfp4"):
+        raise RuntimeError("kind must be 'nvfp4' or 'mxfp4'")
+    mul = mul_nvfp4_a16_moe_indexed if kind == "nvfp4" else mul_mxfp4_a16_moe_indexed
+    T, H = hidden.shape
+    topk = topk_ids.shape[1]
+    E = gs13.numel()
+    n13 = w13.numel() * w13.element_size() * 2 // (E * H)   # 2 I
+    inter = n13 // 2
+    m = T * topk
+    ids = topk_ids if topk_ids.dtype in (torch.int32, torch.int64) and topk_ids.is_contiguous() else topk_ids.contiguous().to(torch.int64)
+    w = topk_weights if topk_weights.dtype == torch.float32 and topk_weights.is_contiguous() else topk_weights.float().contiguous()
+    sorted_pos, offsets, token_index = moe_align_device(ids, E)
+    h = mul(hidden, w13, s13, gs13, offsets, m, n13, H, E, a_row_index=token_index, activation="silu_mul")   # [m, I], grouped order
+    y = mul(h, w2, s2, gs2, offsets, m, H, inter, E, c_row_index=sorted_pos, c_rows=m)                       # [m, H], (token, slot) order
+    return moe_combine(y, w, ids, E)

@@ -648,6 +648,127 @@ def mul_mxfp4_a16_moe(A, B, s, global_scales, expert_offsets, size_m, size_n, si
     return _mul_moe("mx", A, B, s, global_scales, expert_offsets, size_m, size_n, size_k, num_experts, solution_id, bias, activation)
 
 
+def _mul_moe_indexed(kind: str, A, B, s, global_scales, expert_offsets, size_m, size_n, size_k, num_experts, a_row_index=None,
+                     c_row_index=None, c_rows=None, solution_id=-1, bias=None, activation=None, out=None) -> torch.Tensor:
+    """The MoE launch with a row gather on A and a row scatter on C (petit_gemm_fp4_fp16_moe_ex): grouped row r reads row a_row_index[r]
+    of A [a_rows, size_k] and writes row c_row_index[r] of the output [c_rows, n_out] (None: the identity).  An index outside the
+    matrix reads zeros / stores nothing.  out: write into this tensor (rows no index names stay untouched) instead of a new one."""
+    if A.dtype != torch.bfloat16 and A.dtype != torch.float16:
+        raise RuntimeError("A must be bfloat16 or float16.")
+    group = 16 if kind == "nv" else 32
+    E = int(num_experts)
+    _check(1 <= E <= _lib.PETIT_MOE_MAX_EXPERTS, f"num_experts must be in 1..{_lib.PETIT_MOE_MAX_EXPERTS}, got {E}")
+    _check(A.is_cuda and B.is_cuda and s.is_cuda and global_scales.is_cuda and expert_offsets.is_cuda, "all tensors must be on GPU")
+    _check(A.is_contiguous() and size_k > 0 and A.numel() % size_k == 0, "A must be a contiguous [a_rows, size_k] tensor")
+    _check(B.is_contiguous() and B.numel() * B.element_size() == E * size_n * size_k // 2,
+           "B does not hold num_experts * size_n * size_k packed 4-bit weights")
+    _check(s.is_contiguous() and s.numel() * s.element_size() == E * size_n * size_k // group,
+           f"s does not hold num_experts * size_n * size_k / {group} scales")
+    _check(global_scales.dtype == torch.float32 and global_scales.is_contiguous() and global_scales.numel() == E,
+           "global_scales must be a contiguous float32 [num_experts] tensor")
+    _check(expert_offsets.dtype == torch.int32 and expert_offsets.is_contiguous() and expert_offsets.numel() == E + 1,
+           "expert_offsets must be a contiguous int32 [num_experts + 1] tensor")
+    for idx in (a_row_index, c_row_index):
+        if idx is not None:
+            _check(idx.is_cuda and idx.device == A.device and idx.dtype == torch.int32 and idx.is_contiguous() and idx.numel() == size_m,
+                   "row indices must be contiguous int32 [size_m] tensors on A's device")
+    _check(activation in _ACTIVATIONS, f"activation must be one of {sorted(k for k in _ACTIVATIONS if k)} or None")
+    act = _ACTIVATIONS[activation]
+    if act:
+        _check(size_n % 32 == 0, f"silu_mul needs size_n % 32 == 0 (gate / up halves of whole tiles), got {size_n}")
+    if bias is not None:
+        _check(bias.is_cuda and bias.device == A.device and bias.dtype == A.dtype and bias.is_contiguous() and bias.numel() == E * size_n,
+               "bias must be a contiguous [num_experts, size_n] tensor of A's dtype on A's device")
+    a_rows = A.numel() // size_k
+    n_out = size_n // 2 if act else size_n
+    if out is not None:
+        _check(out.is_cuda and out.device == A.device and out.dtype == A.dtype and out.is_contiguous() and out.dim() == 2 and out.size(1) == n_out,
+               "out must be a contiguous [c_rows, n_out] tensor of A's dtype on A's device")
+        _check(c_rows is None or c_rows < 0 or c_rows == out.size(0), "c_rows does not match out.size(0)")
+        c_rows = out.size(0)
+    else:
+        c_rows = size_m if c_rows is None or c_rows < 0 else int(c_rows)
+        out = torch.empty((c_rows, n_out), dtype=A.dtype, device=A.device)
+    hints = _moe_hints(kind, A)
+    epi = _lib.Epilogue(bias.data_ptr() if bias is not None else None, act, 0) if (bias is not None or act) else None
+    with torch.cuda.device(A.device):
+        err = _lib.lib.petit_gemm_fp4_fp16_moe_ex(_ptr(out), _ptr(A), _ptr(B), _ptr(s), _ptr(global_scales), _ptr(expert_offsets), E, size_m,
+                                                  size_n, size_k, _ptr(a_row_index) if a_row_index is not None else None, a_rows,
+                                                  _ptr(c_row_index) if c_row_index is not None else None, c_rows, C.byref(hints),
+                                                  C.c_uint64(_c_solution_id(solution_id)), C.byref(epi) if epi is not None else None, _stream(A))
+    if err == _lib.PETIT_ERROR_PROBLEM_SHAPE:
+        raise RuntimeError(f"Incompatible problem shape (m={size_m}, n={size_n}, k={size_k}, num_experts={E}, a_rows={a_rows}, c_rows={c_rows})")
+    if err == _lib.PETIT_ERROR_KERNEL_SHAPE:
+        raise RuntimeError(f"No kernel implementation for solution_id={solution_id}.")
+    _raise_on(err, "mul_%sfp4_a16_moe_indexed" % kind)
+    return out
+
+
+def mul_nvfp4_a16_moe_indexed(A, B, s, global_scales, expert_offsets, size_m, size_n, size_k, num_experts, a_row_index=None, c_row_index=None,
+                              c_rows=None, solution_id=-1, bias=None, activation=None, out=None) -> torch.Tensor:
+    return _mul_moe_indexed("nv", A, B, s, global_scales, expert_offsets, size_m, size_n, size_k, num_experts, a_row_index, c_row_index, c_rows,
+                            solution_id, bias, activation, out)
+
+
+def mul_mxfp4_a16_moe_indexed(A, B, s, global_scales, expert_offsets, size_m, size_n, size_k, num_experts, a_row_index=None, c_row_index=None,
+                              c_rows=None, solution_id=-1, bias=None, activation=None, out=None) -> torch.Tensor:
+    return _mul_moe_indexed("mx", A, B, s, global_scales, expert_offsets, size_m, size_n, size_k, num_experts, a_row_index, c_row_index, c_rows,
+                            solution_id, bias, activation, out)
+
+
+def _check_topk_ids(topk_ids: torch.Tensor, num_experts: int) -> None:
+    _check(1 <= int(num_experts) <= _lib.PETIT_MOE_MAX_EXPERTS, f"num_experts must be in 1..{_lib.PETIT_MOE_MAX_EXPERTS}, got {num_experts}")
+    _check(topk_ids.is_cuda and topk_ids.dim() == 2 and topk_ids.is_contiguous() and topk_ids.dtype in (torch.int32, torch.int64),
+           "topk_ids must be a contiguous int32 / int64 [num_tokens, topk] GPU tensor")
+    _check(topk_ids.size(1) >= 1, "topk must be >= 1")
+
+
+def moe_align_device(topk_ids: torch.Tensor, num_experts: int):
+    """moe_align on the device (petit_moe_align): topk_ids [T, topk] int32 / int64 -> (sorted_pos, expert_offsets, token_index), all int32.
+    sorted_pos [T * topk]: the flat (token, slot) positions grouped by expert, stable; token_index = sorted_pos // topk; expert_offsets
+    [E + 1].  Ids outside [0, E) (-1 under expert parallelism) get no row: expert_offsets[E] counts the routed entries, and the rows past
+    it are -1.  No host sync; deterministic."""
+    _check_topk_ids(topk_ids, num_experts)
+    T, topk = topk_ids.shape
+    dev = topk_ids.device
+    sorted_pos = torch.empty(T * topk, dtype=torch.int32, device=dev)
+    token_index = torch.empty(T * topk, dtype=torch.int32, device=dev)
+    offsets = torch.empty(int(num_experts) + 1, dtype=torch.int32, device=dev)
+    ws_bytes = int(_lib.lib.petit_moe_align_workspace_bytes(T, topk, int(num_experts)))
+    ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev) if ws_bytes else None
+    with torch.cuda.device(dev):
+        rc = _lib.lib.petit_moe_align(_ptr(topk_ids), int(topk_ids.dtype == torch.int64), T, topk, int(num_experts), _ptr(offsets),
+                                      _ptr(sorted_pos), _ptr(token_index), _ptr(ws) if ws is not None else None, _stream(topk_ids))
+    if rc == _lib.PETIT_ERROR_PROBLEM_SHAPE:
+        raise RuntimeError(f"Incompatible routing shape (num_tokens={T}, topk={topk}, num_experts={num_experts})")
+    _raise_on(rc, "moe_align_device")
+    return sorted_pos, offsets, token_index
+
+
+def moe_combine(slot_out: torch.Tensor, topk_weights: torch.Tensor, topk_ids: torch.Tensor, num_experts: int) -> torch.Tensor:
+    """The top-k reduce (petit_moe_combine): out[t] = to16(sum over j in order, ids in [0, E) only, of float(slot_out[t * topk + j]) *
+    topk_weights[t, j]) in fp32 without FMA contraction, one RNE rounding.  slot_out [T * topk, n] bf16 / fp16, topk_weights float32
+    [T, topk].  Returns [T, n] in slot_out's dtype."""
+    _check_topk_ids(topk_ids, num_experts)
+    T, topk = topk_ids.shape
+    _check(slot_out.is_cuda and slot_out.device == topk_ids.device and slot_out.dtype in (torch.bfloat16, torch.float16) and
+           slot_out.is_contiguous() and slot_out.dim() == 2 and slot_out.size(0) == T * topk,
+           "slot_out must be a contiguous bfloat16 / float16 [num_tokens * topk, n] tensor on topk_ids' device")
+    _check(topk_weights.is_cuda and topk_weights.device == topk_ids.device and topk_weights.dtype == torch.float32 and
+           topk_weights.is_contiguous() and topk_weights.shape == topk_ids.shape, "topk_weights must be a contiguous float32 [num_tokens, topk] tensor")
+    n = slot_out.size(1)
+    _check(n % 8 == 0, f"n must be a multiple of 8, got {n}")
+    out = torch.empty((T, n), dtype=slot_out.dtype, device=slot_out.device)
+    dtype = _lib.CXX_DTYPE_BF16 if slot_out.dtype == torch.bfloat16 else _lib.CXX_DTYPE_FP16
+    with torch.cuda.device(slot_out.device):
+        rc = _lib.lib.petit_moe_combine(_ptr(out), _ptr(slot_out), _ptr(topk_weights), _ptr(topk_ids), int(topk_ids.dtype == torch.int64), T, topk,
+                                        n, int(num_experts), dtype, _stream(slot_out))
+    if rc == _lib.PETIT_ERROR_PROBLEM_SHAPE:
+        raise RuntimeError(f"Incompatible routing shape (num_tokens={T}, topk={topk}, n={n}, num_experts={num_experts})")
+    _raise_on(rc, "moe_combine")
+    return out
+
+
 def moe_resolve_solution(hints: PetitSolutionHints, num_experts: int, size_m: int, size_n: int, size_k: int, solution_id: int = -1,
                          activation=None) -> int:
     """The kernel id a MoE call with these arguments runs (petit_gemm_moe_resolve_solution, the launcher's own pick); 0 when it would be refused."""

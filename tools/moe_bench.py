@@ -2,7 +2,7 @@
 """tools/moe_bench.py -- the routed-expert (MoE) launch against a host loop of dense calls, on real expert shapes.
 
     python tools/moe_bench.py [--cells decode|prefill|all] [--models deepseek,qwen3,mixtral] [--iters N] [--out FILE]
-                              [--only-moe | --only-loop] [--single-expert]
+                              [--only-moe | --only-loop] [--single-expert] [--layer]
 
 Per cell (model, projection, T tokens): E experts' NVFP4 weights (bf16 activations) stacked back to back, copied until the pool is >= 1 GB so
 that rotating over copies and over routings (drawn from a seed, top-k of random router logits) keeps the 256 MB Infinity Cache from serving
@@ -12,6 +12,9 @@ the weights.  Timed with HIP events over `--iters` iterations (eager launches):
            routing, so the loop needs no device -> host copy (a real caller's would)
   active_bytes  weight + scale bytes of the experts that have rows (+ activations and outputs), the bytes the MoE launch has to move
 --single-expert: every row routed to one expert, the MoE launch against the dense call with the SAME id (the indirection cost), at M = 1, 16, 512.
+--layer: the whole routed-expert layer (gate_up with SiLU-mul, down, top-k combine; DeepSeek-V3 / Qwen3-30B-A3B / Mixtral shapes), fp4_moe
+against fp4_moe_fused, each captured once in a torch.cuda.graph (one capture stream, no parallel branches) and replayed; per cell also the
+plain MoE GEMMs on pre-gathered rows against the indexed ones (gate_up gathering A, down scattering C), ten launches per captured graph.
 Kernel times without launch gaps: run under `rocprofv3 --kernel-trace --stats -- python tools/moe_bench.py ...`.
 Prints one JSON object (and writes it to --out).
 """
@@ -151,6 +154,75 @@ def single_expert(pk, iters):
     return out
 
 
+LAYER_T = (1, 4, 16, 64, 1024, 4096)
+
+
+def graph_us(fn, iters, per_graph=1):
+    """fn captured `per_graph` times in one graph (one stream), replayed `iters` times: microseconds per fn"""
+    side = torch.cuda.Stream()
+    side.wait_stream(torch.cuda.current_stream())
+    with torch.cuda.stream(side):
+        fn()
+    torch.cuda.current_stream().wait_stream(side)
+    torch.cuda.synchronize()
+    g = torch.cuda.CUDAGraph()
+    with torch.cuda.graph(g):
+        for _ in range(per_graph):
+            fn()
+    for _ in range(3):
+        g.replay()
+    torch.cuda.synchronize()
+    t0, t1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    t0.record()
+    for _ in range(iters):
+        g.replay()
+    t1.record()
+    torch.cuda.synchronize()
+    del g
+    return t0.elapsed_time(t1) * 1e3 / (iters * per_graph)
+
+
+def layer_cells(pk, models, ts, iters):
+    from petit_kernel.moe import moe_align
+    cells = []
+    for name in models:
+        (n13, hid), (_, inter), E, topk = MODELS[name]
+        g = torch.Generator(device="cuda").manual_seed(7)
+        w13 = torch.randint(-2 ** 31, 2 ** 31 - 1, (E * n13 // 16, 2 * hid), dtype=torch.int32, device="cuda", generator=g)
+        s13 = torch.randint(0x28, 0x40, (E * n13, hid // 16), dtype=torch.uint8, device="cuda", generator=g).view(torch.float8_e4m3fn)
+        w2 = torch.randint(-2 ** 31, 2 ** 31 - 1, (E * hid // 16, 2 * inter), dtype=torch.int32, device="cuda", generator=g)
+        s2 = torch.randint(0x28, 0x40, (E * hid, inter // 16), dtype=torch.uint8, device="cuda", generator=g).view(torch.float8_e4m3fn)
+        gs13, gs2 = torch.rand(E, device="cuda") * 0.01 + 0.01, torch.rand(E, device="cuda") * 0.01 + 0.01
+        for T in ts:
+            m = T * topk
+            it = iters if T < 1024 else max(5, iters // 5)
+            x = torch.randn(T, hid, device="cuda").to(torch.bfloat16)
+            logits = torch.randn(T, E, device="cuda", generator=g)
+            tw, tid = torch.topk(torch.softmax(logits, -1), topk, dim=-1)
+            tw, tid = tw.float().contiguous(), tid.to(torch.int32).contiguous()
+            args = (x, w13, s13, gs13, w2, s2, gs2, tw, tid)
+            r = {"model": name, "T": T, "E": E, "topk": topk, "hidden": hid, "inter": inter}
+            r["fp4_moe_us"] = graph_us(lambda: pk.fp4_moe(*args), it)
+            r["fp4_moe_fused_us"] = graph_us(lambda: pk.fp4_moe_fused(*args), it)
+            # the GEMMs alone: plain on pre-gathered rows against indexed
+            sorted_idx, offs = moe_align(tid, E)
+            tok = (sorted_idx // topk).int()
+            xg = x.index_select(0, sorted_idx // topk)
+            h = pk.mul_nvfp4_a16_moe(xg, w13, s13, gs13, offs, m, n13, hid, E, activation="silu_mul")
+            out = torch.empty(m, hid, dtype=torch.bfloat16, device="cuda")
+            r["gate_up_plain_us"] = graph_us(lambda: pk.mul_nvfp4_a16_moe(xg, w13, s13, gs13, offs, m, n13, hid, E, activation="silu_mul"), it, 10)
+            r["gate_up_indexed_us"] = graph_us(lambda: pk.mul_nvfp4_a16_moe_indexed(x, w13, s13, gs13, offs, m, n13, hid, E, a_row_index=tok,
+                                                                                    activation="silu_mul"), it, 10)
+            r["down_plain_us"] = graph_us(lambda: pk.mul_nvfp4_a16_moe(h, w2, s2, gs2, offs, m, hid, inter, E), it, 10)
+            r["down_indexed_us"] = graph_us(lambda: pk.mul_nvfp4_a16_moe_indexed(h, w2, s2, gs2, offs, m, hid, inter, E, c_row_index=sorted_idx.int(),
+                                                                                 out=out), it, 10)
+            print(json.dumps(r), file=sys.stderr, flush=True)
+            cells.append(r)
+        del w13, s13, w2, s2
+        torch.cuda.empty_cache()
+    return cells
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--cells", default="all", choices=["decode", "prefill", "all"])
@@ -159,11 +231,16 @@ def main():
     ap.add_argument("--only-moe", action="store_true")
     ap.add_argument("--only-loop", action="store_true")
     ap.add_argument("--single-expert", action="store_true")
+    ap.add_argument("--layer", action="store_true")
+    ap.add_argument("--t", default="", help="--layer: comma-separated token counts (default 1,4,16,64,1024,4096)")
     ap.add_argument("--out", default="")
     args = ap.parse_args()
     import petit_kernel as pk
     report = {"device": torch.cuda.get_device_properties(0).gcnArchName, "cells": []}
-    if args.single_expert:
+    if args.layer:
+        ts = tuple(int(t) for t in args.t.split(",")) if args.t else LAYER_T
+        report["layer"] = layer_cells(pk, args.models.split(","), ts, args.iters)
+    elif args.single_expert:
         report["single_expert"] = single_expert(pk, args.iters)
     else:
         ts = (DECODE_T if args.cells != "prefill" else ()) + (PREFILL_T if args.cells != "decode" else ())
