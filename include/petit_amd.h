@@ -509,6 +509,43 @@ int petit_moe_combine(void *out, const void *slot_out, const float *topk_weights
                       unsigned topk, unsigned n, unsigned num_experts, int dtype, void *stream);
 
 /*
+ * Native-class MoE launch (no counterpart in the reference): the routed-expert launch on the block-scaled MFMA, the accuracy class of
+ * petit_gemm_mxfp4_native (activations quantised to MXFP8 / MXFP6 / MXFP4; the per-element bound is the native block's above).  Opt-in
+ * like every native call: solution_id is a PETIT_SOLUTION_AUTO_NATIVE_* sentinel or an explicit native id that has a MoE form (the 128 x 256
+ * kernels per activation format and span size); PETIT_SOLUTION_AUTO and exact-class ids return PETIT_ERROR_KERNEL_SHAPE -- never another class.
+ * A sentinel picks as petit_gemm_moe_resolve_solution does (rows per active expert), among the native kernels with a MoE form.
+ *   b, scales       hints->b_type MXFP4: the stacked packed tensors, exactly what petit_gemm_fp4_fp16_moe reads.  NVFP4 (PETIT_DTYPE_FP4_E2M1):
+ *                   b is E MFMA-native images back to back, expert e's = petit_nvfp4_native_image of its packed block, at byte
+ *                   e * petit_nvfp4_native_image_bytes(k, n) (an image of the stacked [E n, k] tensor is NOT that: its scale region follows
+ *                   all the elements); b 256-byte aligned; scales is ignored (NULL).
+ *   a               native->a_format 0 (or native null): 16-bit rows, gathered through a_row_index as petit_gemm_fp4_fp16_moe_ex does (an index
+ *                   outside [0, a_rows) quantises a zero row) and quantised into `workspace` first: two launches, workspace_bytes >=
+ *                   petit_gemm_native_moe_workspace_bytes().  a_format 8 / 6 / 4: a holds the m GROUPED rows already quantised
+ *                   (petit_quantize_activations_rows, or a producer's out_format), a_row_index must be null: one launch, no workspace.
+ *   c               16-bit [c_rows][n] ([c_rows][n/2] with SiLU-mul), row c_row_index[r] (null: r) for grouped row r; an index outside
+ *                   [0, c_rows) stores nothing.  native->out_format 8 / 6 / 4 (SiLU-mul only, n % 512 == 0, c_row_index null): c receives
+ *                   the m grouped rows of [m][n/2] quantised for the next launch (petit_quantized_activation_bytes(m, n / 2, format)).
+ *   Row limit: every epilogue stores rows of its own expert only; rows past expert_offsets[E] are not computed.  Within an expert the
+ *   result equals, bit for bit, petit_gemm_mxfp4_native / petit_gemm_nvfp4_native on that expert's rows with the same id.
+ * Shapes and errors as petit_gemm_fp4_fp16_moe_ex and petit_gemm_mxfp4_native; also PETIT_ERROR_BAD_ARGUMENT for a_format with an
+ * a_row_index, out_format with a c_row_index or without SiLU-mul, misaligned pointers; PETIT_ERROR_KERNEL_SHAPE for a workspace below the
+ * query; PETIT_ERROR_PROBLEM_SHAPE when the quantised rows reach 2^32 bytes (32-bit offsets).  m == 0 returns PETIT_OK.  No host sync:
+ * capturable.  The queries return 0 for a call that would be refused; the workspace query also 0 with a_format set.
+ * petit_quantize_activations_rows: petit_quantize_activations of the gathered rows (layout row r from row a_row_index[r] of a [a_rows][k];
+ * null: the identity, a_rows >= m), one launch; any m (no grid-row limit) below 2^32 bytes of output.
+ */
+uint64_t petit_gemm_native_moe_workspace_bytes(const petit_solution_hints *hints, unsigned num_experts, unsigned m, unsigned n, unsigned k,
+                                               uint64_t solution_id, const petit_epilogue *epilogue, const petit_native_args *native);
+uint64_t petit_gemm_native_moe_resolve_solution(const petit_solution_hints *hints, unsigned num_experts, unsigned m, unsigned n, unsigned k,
+                                                uint64_t solution_id, const petit_epilogue *epilogue, const petit_native_args *native);
+int petit_gemm_native_moe(void *c, const void *a, const void *b, const void *scales, const float *global_scales, const int32_t *expert_offsets,
+                          unsigned num_experts, unsigned m, unsigned n, unsigned k, const int32_t *a_row_index, unsigned a_rows,
+                          const int32_t *c_row_index, unsigned c_rows, const petit_solution_hints *hints, uint64_t solution_id,
+                          const petit_epilogue *epilogue, const petit_native_args *native, void *workspace, uint64_t workspace_bytes, void *stream);
+int petit_quantize_activations_rows(void *qa, const void *a, const int32_t *a_row_index, unsigned a_rows, unsigned m, unsigned k, int a_type,
+                                    int format, void *stream);
+
+/*
  * Tune-and-persist (replaces the reference's `bench_matmul -algo tune`, tools/benchmarks/matmul/main.cc:269-325, which
  * enumerates and times every solution on the user's device but leaves the winning id for the user to carry around).
  *

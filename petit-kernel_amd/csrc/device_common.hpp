@@ -478,5 +478,23 @@ __device__ __forceinline__ unsigned idx_c_row(const RowIndex &ix, unsigned m) {
     const unsigned c = ix.c_idx ? (unsigned)ix.c_idx[ix.row0 + m] : ix.row0 + m;
     return c < ix.c_rows ? c : ~0u;
 }
+// c_tile_store with the rows scattered: image row r (tile row m0 + r) goes to C row idx_c_row(ix, m0 + r); an index outside [0, c_rows)
+// stores nothing
+template <int BM, int BN, int THREADS>
+__device__ __forceinline__ void c_tile_store_idx(const u32x4 *img, void *c, unsigned ldc, unsigned m0, unsigned n0, unsigned rows_valid,
+                                                 unsigned cols_valid, unsigned tid, const RowIndex &ix) {
+    constexpr int kPerRow = BN / 8;
+#pragma unroll
+    for (int u = 0; u < BM * kPerRow; u += THREADS) {
+        const unsigned unit = u + tid, row = unit / kPerRow, cu = unit % kPerRow;
+        if ((BM * kPerRow) % THREADS != 0 && unit >= (unsigned)(BM * kPerRow))
+            break;
+        if (row < rows_valid && cu * 8 < cols_valid) {
+            const unsigned cm = idx_c_row(ix, m0 + row);
+            if (cm != ~0u)
+                *reinterpret_cast<u32x4 *>(reinterpret_cast<char *>(c) + ((size_t)cm * ldc + n0 + cu * 8) * 2) = img[row * CTile<BN>::kStrideU4 + cu];
+        }
+    }
+}
 
 } // namespace petit_amd

@@ -54,26 +54,44 @@ template <int ACT> __host__ __device__ inline size_t native32_ws_bytes(unsigned 
     return (size_t)m * (k / 8 * ACT) + (size_t)m * (k / 32);
 }
 
+// The gathering form of the quantisers (the routed-expert layer, gemm_moe_native.hpp): layout row r from row idx[r] of a [a_rows][k] (a null
+// index: row r); an index outside [0, a_rows) quantises a zero row (scale byte 127, zero elements).  Its grid is xb * M workgroups along x (xb per
+// row): no 65535-row limit.  Passed as the quantiser kernels' optional last argument (none: the dense kernels, unchanged).
+struct QuantGather {
+    const int *idx;
+    unsigned a_rows, xb;
+};
+__device__ __forceinline__ unsigned q_row() { return blockIdx.y; }
+__device__ __forceinline__ unsigned q_row(const QuantGather &g) { return blockIdx.x / g.xb; }
+__device__ __forceinline__ unsigned q_bx() { return blockIdx.x; }
+__device__ __forceinline__ unsigned q_bx(const QuantGather &g) { return blockIdx.x % g.xb; }
+__device__ __forceinline__ unsigned q_src(unsigned row) { return row; }
+__device__ __forceinline__ unsigned q_src(unsigned row, const QuantGather &g) { return g.idx ? (unsigned)g.idx[row] : row; }
+__device__ __forceinline__ bool q_valid(unsigned) { return true; }
+__device__ __forceinline__ bool q_valid(unsigned src, const QuantGather &g) { return src < g.a_rows; }
+
 // One thread = 8 consecutive k of one row; the 4 threads of a quad share one 32-k block.
-template <class AT, int ACT>
-__global__ __launch_bounds__(256) void quantize_act32_kernel(const void *a, unsigned char *ws, unsigned m, unsigned k) {
+template <class AT, int ACT, class... Gather>
+__global__ __launch_bounds__(256) void quantize_act32_kernel(const void *a, unsigned char *ws, unsigned m, unsigned k, const Gather... gather) {
     // grid = (ceil(K / 8 / (4 * 256)), M): blockIdx.y is the row -- no division in the address arithmetic -- and a thread owns
     // four 8-element columns 256 apart, all four loads requested before the first is used
     const unsigned row_bytes = k / 8 * ACT;
     unsigned char *qa = ws;
     unsigned char *qs = ws + (size_t)m * row_bytes;
     constexpr int kIlp = 4;
-    const unsigned row = blockIdx.y, cols = k / 8;
-    const u32x4 *const a_row = reinterpret_cast<const u32x4 *>(a) + (size_t)row * cols;
+    const unsigned row = q_row(gather...), cols = k / 8, bx = q_bx(gather...);
+    const unsigned src = q_src(row, gather...);
+    const bool valid = q_valid(src, gather...);
+    const u32x4 *const a_row = reinterpret_cast<const u32x4 *>(a) + (size_t)src * cols;
     u32x4 raws[kIlp];
 #pragma unroll
     for (int j = 0; j < kIlp; ++j) {
-        const unsigned c = (blockIdx.x * kIlp + j) * 256 + threadIdx.x;
-        raws[j] = c < cols ? a_row[c] : u32x4{0u, 0u, 0u, 0u};
+        const unsigned c = (bx * kIlp + j) * 256 + threadIdx.x;
+        raws[j] = (c < cols && valid) ? a_row[c] : u32x4{0u, 0u, 0u, 0u};
     }
 #pragma unroll
     for (int j = 0; j < kIlp; ++j) {
-        const unsigned c8 = (blockIdx.x * kIlp + j) * 256 + threadIdx.x; // 8-element column
+        const unsigned c8 = (bx * kIlp + j) * 256 + threadIdx.x; // 8-element column
         if (c8 >= cols) // (K / 8 is a multiple of 16: the 16 lanes of a k-tile leave together)
             break;
         const u32x4 raw = raws[j];
@@ -136,17 +154,19 @@ __global__ __launch_bounds__(256) void quantize_act32_kernel(const void *a, unsi
 
 // MXFP6 (e2m3): one thread = one 32-k block of one row (the hardware converts 32 values at once: v_cvt_scalef32_pk32_fp6_{bf16,f16}, RNE of
 // src / scale, saturating at 7.5).  grid = (ceil(K / 32 / 256), M); the four blocks of a k-tile are four consecutive lanes.
-template <class AT>
-__global__ __launch_bounds__(256) void quantize_act32_fp6_kernel(const void *a, unsigned char *ws, unsigned m, unsigned k) {
-    const unsigned row = blockIdx.y, blocks = k / 32, blk = blockIdx.x * 256 + threadIdx.x;
+template <class AT, class... Gather>
+__global__ __launch_bounds__(256) void quantize_act32_fp6_kernel(const void *a, unsigned char *ws, unsigned m, unsigned k, const Gather... gather) {
+    const unsigned row = q_row(gather...), blocks = k / 32, blk = q_bx(gather...) * 256 + threadIdx.x;
     if (blk >= blocks) // (K / 32 is a multiple of 4: the lanes of a k-tile leave together)
         return;
     unsigned char *const qa_lo = ws, *const qa_hi = ws + (size_t)m * (k / 2), *const qs = ws + (size_t)m * (k / 8 * 6);
-    const u32x4 *const src = reinterpret_cast<const u32x4 *>(a) + ((size_t)row * blocks + blk) * 4;
+    const unsigned src_row = q_src(row, gather...);
+    const bool valid = q_valid(src_row, gather...);
+    const u32x4 *const src = reinterpret_cast<const u32x4 *>(a) + ((size_t)src_row * blocks + blk) * 4;
     u32x4 raw[4];
 #pragma unroll
     for (int j = 0; j < 4; ++j)
-        raw[j] = src[j];
+        raw[j] = valid ? src[j] : u32x4{0u, 0u, 0u, 0u};
     // block maximum on the 16-bit patterns (sign cleared: bf16 and fp16 magnitudes order like their bit patterns), exponent from its f32 value
     unsigned mx = 0;
 #pragma unroll
@@ -192,6 +212,8 @@ __global__ __launch_bounds__(256) void quantize_act32_fp6_kernel(const void *a, 
 // layout described above -- a 256-column workgroup tile produces exactly ONE 128-column k-tile of the consumer for its 128 rows, a
 // contiguous 8 / 16 KiB run plus 512 scale bytes.  The values are quantised from the f32 SiLU-mul result (one rounding, where
 // "round to 16 bit, then quantise" has two).
+// m_total is the layout's row count (its stride), m_lim the row limit: rows at or past it are not stored (a routed-expert launch: the
+// next expert's rows, which another workgroup writes).
 //   lane (m, h) of wave wn holds, for each of the wave's two output tiles np, columns {0-3, 8-11} (h = 0) or {4-7, 12-15} (h = 1): a
 //   32-column block is the wave's two tiles of one row, i.e. this lane's 16 values and its partner's (lane ^ 32) 16.  The block
 //   maximum needs one cross-half swap; a second swap (of the packed codes) leaves lane h with ALL 16 columns of tile np = h, so each
@@ -200,7 +222,8 @@ template <class AT, int OUTF, int MB>
 __device__ __forceinline__ void n32_silu_quant_epilogue(const f32x16 (&acc)[MB][2], const float gs, const void *bias, unsigned char *out,
                                                         const unsigned m_total, const unsigned n_half, const unsigned m_first,
                                                         const unsigned col0, const unsigned kt, const unsigned wn, const unsigned m_l,
-                                                        const unsigned h, unsigned char *lds_scales, const unsigned m0, const unsigned tid) {
+                                                        const unsigned h, unsigned char *lds_scales, const unsigned m0, const unsigned tid,
+                                                        const unsigned m_lim) {
     constexpr unsigned kRowB = OUTF == 6 ? 64 : 16 * OUTF; // bytes per row and k-tile: 128 (FP8) / 64 (FP4; FP6: of the image of registers 0-3)
     unsigned char *const qs = out + (size_t)m_total * (n_half / 8 * OUTF);
     unsigned char *const out_hi = out + (size_t)m_total * (n_half / 2); // FP6: the image of registers 4-5 (native32_ws_bytes)
@@ -263,7 +286,7 @@ __device__ __forceinline__ void n32_silu_quant_epilogue(const f32x16 (&acc)[MB][
                 const unsigned p0 = sw[0], p1 = sw[1];
                 full[d] = p0 | p1;
             }
-            if (m < m_total) {
+            if (m < m_lim) {
                 if (h == 0) {
                     *reinterpret_cast<u32x4 *>(out + ((size_t)kt * m_total + m) * 64 + 16 * wn) = u32x4{full[0], full[1], full[2], full[3]};
                 } else {
@@ -290,7 +313,7 @@ __device__ __forceinline__ void n32_silu_quant_epilogue(const f32x16 (&acc)[MB][
             uint2 o;
             o.x = __builtin_amdgcn_perm(r1, r0, 0x05040100u); // columns 0-7
             o.y = __builtin_amdgcn_perm(r1, r0, 0x07060302u); // columns 8-15
-            if (m < m_total)
+            if (m < m_lim)
                 *reinterpret_cast<uint2 *>(out + ((size_t)kt * m_total + m) * kRowB + 16 * wn + 8 * h) = o;
         } else {
             const float inv = __builtin_bit_cast(float, (254u - sbyte) << 23); // 2^-(sbyte - 127)
@@ -309,12 +332,12 @@ __device__ __forceinline__ void n32_silu_quant_epilogue(const f32x16 (&acc)[MB][
             const unsigned a0 = s0[0], a1 = s0[1], b0 = s1[0], b1 = s1[1];
             // the 16-column unit u16 = 2 wn + h sits at position pos of the tile's 128 bytes (the operand order of the layout note)
             const unsigned u16 = 2 * wn + h, pos = (u16 & 4u) | ((u16 & 1u) << 1) | ((u16 >> 1) & 1u);
-            if (m < m_total)
+            if (m < m_lim)
                 *reinterpret_cast<u32x4 *>(out + ((size_t)kt * m_total + m) * kRowB + pos * 16) = u32x4{a0, a1, b0, b1};
         }
     }
     __syncthreads();
-    if (tid < (unsigned)(32 * MB) && m0 + tid < m_total)
+    if (tid < (unsigned)(32 * MB) && m0 + tid < m_lim)
         *reinterpret_cast<unsigned *>(qs + ((size_t)kt * m_total + m0 + tid) * 4) = reinterpret_cast<const unsigned *>(lds_scales)[tid];
 }
 
@@ -423,8 +446,18 @@ constexpr int n32_stage_refills(bool last_span, int t_first, int kt, int d, int 
     return n;
 }
 
-template <class Cfg>
-__global__ __launch_bounds__(Cfg::kThreads, Cfg::kMinWavesPerSimd) void gemm_native32_kernel(const GemmArgs p, const unsigned char *ws) {
+// Moe: empty for a dense launch (the grid's raster order names the tile: tile_of_block).  The routed-expert form (gemm_moe_native.hpp) passes
+// ONE locator: it maps the workgroup to (expert, m-block) -- or tells it to exit -- and hands over the expert's operands, its row limit and the
+// C scatter.  Two roles of M are kept apart: p.m is the row count of the k-tile-major activation layout (its stride: qa_tile, qs_tile, the
+// descriptor ranges, the FP6 tail image; the split-K slabs), m_lim the row limit -- rows >= m_lim are never stored, in any epilogue (a dense
+// launch: p.m; the MoE form: its expert's end).  With a locator the plain / bias and 16-bit SiLU-mul epilogues store layout row m at C row
+// idx_c_row(ix, m) and skip indices outside [0, c_rows); the quantising epilogue is identity-only.  (One kernel template, not a body function
+// under two kernels: that split changed the dense kernels' code.)
+template <class Cfg, class... Moe>
+__global__ __launch_bounds__(Cfg::kThreads, Cfg::kMinWavesPerSimd) void gemm_native32_kernel(const GemmArgs p, const unsigned char *ws,
+                                                                                             const Moe... moe) {
+    static_assert(sizeof...(Moe) <= 1, "at most one MoE locator");
+    constexpr bool kIdx = sizeof...(Moe) == 1;
     using AT = typename Cfg::AT;
     constexpr int KS = Cfg::KS, MB = Cfg::MB, NP = Cfg::NP, WAVES = Cfg::WAVES, D = Cfg::D, ACT = Cfg::ACT;
     constexpr int KT = Cfg::KT, PF = Cfg::PF, NBUF = Cfg::NBUF, WM = Cfg::WM, kWaves = Cfg::kWaves;
@@ -452,10 +485,19 @@ __global__ __launch_bounds__(Cfg::kThreads, Cfg::kMinWavesPerSimd) void gemm_nat
     const unsigned ktiles = p.k / kTileK;
     const unsigned nspans = ktiles / KS;
     const unsigned ntiles = p.n / kTileN;
-    unsigned bn, bm;
-    tile_of_block(p.flags, bn, bm);
+    unsigned bn, bm, m0, m_lim = p.m;
+    const void *w_e = p.w, *s_e = p.s, *bias_e = p.bias; // (the MoE form: its expert's)
+    const float *gs_e = p.gs;
+    RowIndex ix{};
+    if constexpr (kIdx) {
+        if (!(moe.locate(p, bn, m0, m_lim, w_e, s_e, gs_e, bias_e, ix) && ...))
+            return; // a slot past the last tile: before any load
+    } else {
+        tile_of_block(p.flags, bn, bm);
+    }
     const unsigned nt0 = (bn * WAVES + wn) * (2 * NP);
-    const unsigned m0 = bm * Cfg::BM;
+    if constexpr (!kIdx)
+        m0 = bm * Cfg::BM;
     // K slice of this wave group: part blockIdx.z * KG + kg of spans_per_wave spans each.  A part past the end (possible for the
     // LAST group of a KG = 2 workgroup only) walks the last span with every weight row masked off (valid_nt = 0: zeros in, zeros
     // accumulated) instead of branching around the MFMA stream, and then keeps the barrier count of its partner.
@@ -477,7 +519,7 @@ __global__ __launch_bounds__(Cfg::kThreads, Cfg::kMinWavesPerSimd) void gemm_nat
     const unsigned valid_nt = (nt0 < ntiles && !empty_part) ? min((unsigned)(2 * NP), ntiles - nt0) : 0u;
     const unsigned w_row_bytes = ktiles * kTileBytes;
     const unsigned s_row_bytes = p.k / 2;
-    const unsigned rows = min(p.m - m0, (unsigned)Cfg::BM);
+    const unsigned rows = min(m_lim - m0, (unsigned)Cfg::BM);
     const unsigned pt0 = valid_nt ? physical_tile(nt0, ntiles, p.act) : 0u;
     const unsigned span_tiles = !valid_nt ? 0u : p.act ? (valid_nt >> 1) + (ntiles >> 1) : valid_nt;
     // WF = 6 (layout.h, "petit-cdna4-nv6/1"): the image is addressed from its start -- elements [N/32][K/128][3 planes][64 lanes] x 16 B, scales
@@ -485,10 +527,10 @@ __global__ __launch_bounds__(Cfg::kThreads, Cfg::kMinWavesPerSimd) void gemm_nat
     // row row % 16 of the logical n-tile nt0 + 2 np + row / 16, whose physical tile (SiLU-mul: a gate tile for rows 0-15, the matching up tile for
     // 16-31) is one HALF of an image block.  The operand a wave ends up with is what merge_tiles builds for the raw layout, so both epilogues
     // and the quantising SiLU-mul epilogue are shared.
-    const __amdgpu_buffer_rsrc_t w_rsrc = WF == 6 ? make_rsrc(p.w, (unsigned)nv6_elem_bytes(p.n, p.k))
-                                                  : make_rsrc((const char *)p.w + (size_t)pt0 * w_row_bytes, span_tiles * w_row_bytes);
-    const __amdgpu_buffer_rsrc_t s_rsrc = WF == 6 ? make_rsrc(p.s, (unsigned)nv6_scale_bytes(p.n, p.k))
-                                                  : make_rsrc((const char *)p.s + (size_t)pt0 * s_row_bytes, span_tiles * s_row_bytes);
+    const __amdgpu_buffer_rsrc_t w_rsrc = WF == 6 ? make_rsrc(w_e, (unsigned)nv6_elem_bytes(p.n, p.k))
+                                                  : make_rsrc((const char *)w_e + (size_t)pt0 * w_row_bytes, span_tiles * w_row_bytes);
+    const __amdgpu_buffer_rsrc_t s_rsrc = WF == 6 ? make_rsrc(s_e, (unsigned)nv6_scale_bytes(p.n, p.k))
+                                                  : make_rsrc((const char *)s_e + (size_t)pt0 * s_row_bytes, span_tiles * s_row_bytes);
     unsigned w_voff[2 * NP], s_voff[2 * NP]; // (WF = 6: one entry per n32-block, [np])
     if constexpr (WF == 6) {
 #pragma unroll
@@ -665,13 +707,13 @@ __global__ __launch_bounds__(Cfg::kThreads, Cfg::kMinWavesPerSimd) void gemm_nat
                 const unsigned valid_wg = nt0_wg < ntiles ? min((unsigned)kPwTiles, ntiles - nt0_wg) : 0u;
                 const unsigned pt0_wg = valid_wg ? physical_tile(nt0_wg, ntiles, p.act) : 0u;
                 const unsigned span_wg = !valid_wg ? 0u : p.act ? (valid_wg >> 1) + (ntiles >> 1) : valid_wg;
-                const __amdgpu_buffer_rsrc_t pw_rsrc = make_rsrc((const char *)p.w + (size_t)pt0_wg * w_row_bytes, span_wg * w_row_bytes);
+                const __amdgpu_buffer_rsrc_t pw_rsrc = make_rsrc((const char *)w_e + (size_t)pt0_wg * w_row_bytes, span_wg * w_row_bytes);
                 u32x4 *const pw_dump = smem + (Cfg::kSmemU4 - 16);
                 unsigned pvoff[kPwLoads];
 #pragma unroll
                 for (int j = 0; j < kPwLoads; ++j) {
                     const unsigned idx = j * 64 + lane, t = idx / 8, line = idx % 8;
-                    const bool mine = PETIT_N32_PWSHARE == 1 || (idx % PETIT_N32_PWSHARE) == (bm % PETIT_N32_PWSHARE);
+                    const bool mine = PETIT_N32_PWSHARE == 1 || (idx % PETIT_N32_PWSHARE) == ((m0 / Cfg::BM) % PETIT_N32_PWSHARE);
                     pvoff[j] = (t < valid_wg && mine) ? (physical_tile(nt0_wg + t, ntiles, p.act) - pt0_wg) * w_row_bytes + line * 128 : kOob;
                 }
                 auto prefetch = [&](unsigned kt) {
@@ -974,13 +1016,13 @@ __global__ __launch_bounds__(Cfg::kThreads, Cfg::kMinWavesPerSimd) void gemm_nat
                     const unsigned m = m_base + mb * 32;
                     const unsigned nt = 2 * np + (u >> 1);
                     const unsigned n = (nt0 + nt) * 16 + (u & 1) * 8 + 4 * h;
-                    if (m < p.m && nt < valid_nt)
+                    if (m < m_lim && nt < valid_nt)
                         *reinterpret_cast<f32x4 *>(p.workspace + ((size_t)blockIdx.z * p.m + m) * p.n + n) =
                             f32x4{acc[mb][np][4 * u], acc[mb][np][4 * u + 1], acc[mb][np][4 * u + 2], acc[mb][np][4 * u + 3]};
                 }
         return;
     }
-    const float gs = *p.gs;
+    const float gs = *gs_e;
     if (p.act) {
         const unsigned n_half = p.n >> 1;
         if (KG == 2 && kg != 0)
@@ -991,11 +1033,14 @@ __global__ __launch_bounds__(Cfg::kThreads, Cfg::kMinWavesPerSimd) void gemm_nat
                 unsigned char *const lds_sc = reinterpret_cast<unsigned char *>(smem);
                 const unsigned col0 = (nt0 >> 1) * 16;
                 if (p.out_format == 4)
-                    n32_silu_quant_epilogue<AT, 4, MB>(acc, gs, p.bias, (unsigned char *)p.c, p.m, n_half, m_base, col0, bn, wn, m_l, h, lds_sc, m0, tid);
+                    n32_silu_quant_epilogue<AT, 4, MB>(acc, gs, bias_e, (unsigned char *)p.c, p.m, n_half, m_base, col0, bn, wn, m_l, h, lds_sc, m0, tid,
+                                                              m_lim);
                 else if (p.out_format == 6)
-                    n32_silu_quant_epilogue<AT, 6, MB>(acc, gs, p.bias, (unsigned char *)p.c, p.m, n_half, m_base, col0, bn, wn, m_l, h, lds_sc, m0, tid);
+                    n32_silu_quant_epilogue<AT, 6, MB>(acc, gs, bias_e, (unsigned char *)p.c, p.m, n_half, m_base, col0, bn, wn, m_l, h, lds_sc, m0, tid,
+                                                              m_lim);
                 else
-                    n32_silu_quant_epilogue<AT, 8, MB>(acc, gs, p.bias, (unsigned char *)p.c, p.m, n_half, m_base, col0, bn, wn, m_l, h, lds_sc, m0, tid);
+                    n32_silu_quant_epilogue<AT, 8, MB>(acc, gs, bias_e, (unsigned char *)p.c, p.m, n_half, m_base, col0, bn, wn, m_l, h, lds_sc, m0, tid,
+                                                              m_lim);
                 return;
             }
         }
@@ -1008,10 +1053,11 @@ __global__ __launch_bounds__(Cfg::kThreads, Cfg::kMinWavesPerSimd) void gemm_nat
                     const unsigned m = m_base + mb * 32;
                     const unsigned n = ((nt0 + 2 * np) >> 1) * 16 + u * 8 + 4 * h;
                     const f32x16 &a = acc[mb][np];
-                    if (m < p.m && (unsigned)(2 * np + 1) < valid_nt)
-                        *reinterpret_cast<uint2 *>((char *)p.c + ((size_t)m * n_half + n) * 2) = finish4_silu_mul<AT>(
+                    const unsigned cm = (kIdx && m < m_lim) ? idx_c_row(ix, m) : m;
+                    if (m < m_lim && (unsigned)(2 * np + 1) < valid_nt && (!kIdx || cm != ~0u))
+                        *reinterpret_cast<uint2 *>((char *)p.c + ((size_t)cm * n_half + n) * 2) = finish4_silu_mul<AT>(
                             f32x4{a[4 * u], a[4 * u + 1], a[4 * u + 2], a[4 * u + 3]},
-                            f32x4{a[8 + 4 * u], a[8 + 4 * u + 1], a[8 + 4 * u + 2], a[8 + 4 * u + 3]}, gs, p.bias, n, n_half);
+                            f32x4{a[8 + 4 * u], a[8 + 4 * u + 1], a[8 + 4 * u + 2], a[8 + 4 * u + 3]}, gs, bias_e, n, n_half);
                 }
         return;
     }
@@ -1029,11 +1075,14 @@ __global__ __launch_bounds__(Cfg::kThreads, Cfg::kMinWavesPerSimd) void gemm_nat
                 const f32x4 v = f32x4{acc[mb][np][4 * u], acc[mb][np][4 * u + 1], acc[mb][np][4 * u + 2], acc[mb][np][4 * u + 3]};
                 if (nt < valid_nt && (KG == 1 || kg == 0)) // (bias is read at n: only for columns that exist)
                     c_tile_put<Cfg::BN>(smem, (wm * MB + mb) * 32 + m_l, (wn * 2 * NP + nt) * 16 + (u & 1) * 8 + 4 * h,
-                                        finish4<AT>(v, gs, p.bias, n));
+                                        finish4<AT>(v, gs, bias_e, n));
             }
     __syncthreads();
     const unsigned n0 = bn * Cfg::BN;
-    c_tile_store<Cfg::BM, Cfg::BN, Cfg::kComputeThreads>(smem, p.c, p.n, m0, n0, rows, n0 < p.n ? min((unsigned)Cfg::BN, p.n - n0) : 0u, tid);
+    if constexpr (kIdx)
+        c_tile_store_idx<Cfg::BM, Cfg::BN, Cfg::kComputeThreads>(smem, p.c, p.n, m0, n0, rows, n0 < p.n ? min((unsigned)Cfg::BN, p.n - n0) : 0u, tid, ix);
+    else
+        c_tile_store<Cfg::BM, Cfg::BN, Cfg::kComputeThreads>(smem, p.c, p.n, m0, n0, rows, n0 < p.n ? min((unsigned)Cfg::BN, p.n - n0) : 0u, tid);
 }
 
 } // namespace petit_amd

@@ -1,5 +1,5 @@
 // moe.hip -- the routed-expert (MoE) entry points of include/petit_amd.h: argument checks, the pick, the launch (the kernels: gemm_moe.hpp,
-// instantiated by moe_tu.inc).  One pick (moe_choose) serves the launcher, its indexed form (petit_gemm_fp4_fp16_moe_ex) and
+// instantiated by moe_tu.inc; the native class's: gemm_moe_native.hpp, instantiated by moe_native_tu.inc).  One pick (moe_choose) serves the launcher, its indexed form (petit_gemm_fp4_fp16_moe_ex) and
 // petit_gemm_moe_resolve_solution.
 #include <hip/hip_runtime.h>
 
@@ -69,9 +69,166 @@ int moe_check(const petit_solution_hints *hints, unsigned num_experts, unsigned 
     return kOk;
 }
 
+// --- the native class (petit_gemm_native_moe): the routed-expert forms of the 32x32x64 native kernels (gemm_moe_native.hpp) ---------------
+
+// bytes of m quantised rows of k in format 8 / 6 / 4 (the k-tile-major layout, gemm_native32.hpp)
+uint64_t qact_bytes(int format, unsigned m, unsigned k) {
+    return format == 8 ? native32_ws_bytes<8>(m, k) : format == 6 ? native32_ws_bytes<6>(m, k) : format == 4 ? native32_ws_bytes<4>(m, k) : 0;
+}
+
+bool native_moe_runs(const SolutionEntry &e, bool act, unsigned num_experts, unsigned m, unsigned k) {
+    unsigned bm, bn;
+    entry_tile(e, &bm, &bn);
+    return e.launch_moe_native && e.shape.ks == span_tiles_for_k(k) && (!act || act_ok(e)) && moe_slots(m, bm, num_experts) != 0;
+}
+
+// A native sentinel: rows per active expert r = ceil(m / min(E, m)); the class's pick for (r, n, k) when it has a MoE form and no K split, else
+// the class's MoE form of the span size k needs (one per class and span size: moe_native_tu.inc).  An explicit id: its entry, when that is a
+// native kernel with a MoE form, split-K 1, of the class a_format names (if set).  PETIT_SOLUTION_AUTO and exact-class ids: nothing -- this
+// entry point never serves another accuracy class.
+const SolutionEntry *native_moe_choose(const Family &fam, int a_type, int b_type, bool act, unsigned num_experts, unsigned m, unsigned n, unsigned k,
+                                       uint64_t solution_id, unsigned a_format, unsigned out_format) {
+    if (solution_id == PETIT_SOLUTION_AUTO)
+        return nullptr;
+    const int klass = auto_class(solution_id);
+    if (klass == kClassExact) {
+        if (solution_splitk(solution_id) != 1)
+            return nullptr;
+        const SolutionEntry *e = find_explicit(fam, solution_id);
+        if (!e || entry_class(*e) == kClassExact || (a_format && (unsigned)entry_class(*e) != a_format))
+            return nullptr;
+        return native_moe_runs(*e, act, num_experts, m, k) ? e : nullptr;
+    }
+    if (a_format && (unsigned)klass != a_format)
+        return nullptr; // activations quantised to one format, class of another
+    const unsigned active = num_experts < m ? num_experts : m;
+    const unsigned r = (m + active - 1) / active;
+    const unsigned restrict_ = kNeedK32 | (out_format ? kNeedQuantOut : 0u);
+    const AutoChoice ch = choose_auto(fam, current_device(), a_type, b_type, act, r, n, k, klass, restrict_);
+    if (ch.entry && ch.splitk == 1 && entry_class(*ch.entry) == klass && native_moe_runs(*ch.entry, act, num_experts, m, k))
+        return ch.entry;
+    for (int i = 0; i < fam.count; ++i)
+        if (entry_class(fam.entries[i]) == klass && native_moe_runs(fam.entries[i], act, num_experts, m, k))
+            return &fam.entries[i];
+    return nullptr;
+}
+
+bool native_args_valid(const petit_native_args *na) {
+    return !na || (na->struct_bytes == sizeof(petit_native_args) && na->reserved == 0 &&
+                   (na->a_format == 0 || na->a_format == 8 || na->a_format == 6 || na->a_format == 4) &&
+                   (na->out_format == 0 || na->out_format == 8 || na->out_format == 6 || na->out_format == 4));
+}
+
+// the checks every native MoE entry point shares (and the pick): *e, *fam, *act, *a_format, *out_format set on success; m == 0 passes with *e null
+int native_moe_plan(const petit_solution_hints *hints, unsigned num_experts, unsigned m, unsigned n, unsigned k, const int32_t *a_row_index,
+                    const int32_t *c_row_index, uint64_t solution_id, const petit_epilogue *epilogue, const petit_native_args *native,
+                    const SolutionEntry **e, Family *fam, bool *act, unsigned *a_format, unsigned *out_format) {
+    *e = nullptr;
+    if (!native_args_valid(native))
+        return kErrBadArgument;
+    if (const int rc = moe_check(hints, num_experts, m, n, k, epilogue, fam, act))
+        return rc;
+    *a_format = native ? (unsigned)native->a_format : 0u, *out_format = native ? (unsigned)native->out_format : 0u;
+    if (*a_format && a_row_index)
+        return kErrBadArgument; // quantised activations are grouped rows already: nothing to gather
+    if (*out_format && (!*act || c_row_index))
+        return kErrBadArgument; // the quantised output is the SiLU-mul epilogue's, in the grouped order the next launch reads
+    if (*out_format && n % 512 != 0)
+        return kErrProblemShape; // the consumer's K = n / 2 must be a whole number of 256-column producer tiles
+    if (solution_id == PETIT_SOLUTION_AUTO)
+        return kErrKernelShape; // the native class's entry point: name a native sentinel or a native kernel id
+    if (m == 0)
+        return kOk;
+    *e = native_moe_choose(*fam, hints->a_type, canonical_b_type(hints->b_type), *act, num_experts, m, n, k, solution_id, *a_format, *out_format);
+    if (!*e)
+        return kErrKernelShape;
+    // the kernels read the quantised rows (and the quantising epilogue writes its output) through 32-bit buffer offsets; one descriptor per NV6 image
+    if (qact_bytes(entry_class(**e), m, k) >= (1ull << 32) || (*out_format && qact_bytes((int)*out_format, m, n / 2) >= (1ull << 32)) ||
+        (!is_mx_type(hints->b_type) && nv6_elem_bytes(n, k) >= (1ull << 32)))
+        return kErrProblemShape;
+    return kOk;
+}
+
 } // namespace
 
 extern "C" {
+
+uint64_t petit_gemm_native_moe_workspace_bytes(const petit_solution_hints *hints, unsigned num_experts, unsigned m, unsigned n, unsigned k,
+                                               uint64_t solution_id, const petit_epilogue *epilogue, const petit_native_args *native) {
+    const SolutionEntry *e;
+    Family fam;
+    bool act = false;
+    unsigned a_format = 0, out_format = 0;
+    if (native_moe_plan(hints, num_experts, m, n, k, nullptr, nullptr, solution_id, epilogue, native, &e, &fam, &act, &a_format, &out_format) != kOk || !e)
+        return 0;
+    return a_format ? 0 : qact_bytes(entry_class(*e), m, k);
+}
+
+uint64_t petit_gemm_native_moe_resolve_solution(const petit_solution_hints *hints, unsigned num_experts, unsigned m, unsigned n, unsigned k,
+                                                uint64_t solution_id, const petit_epilogue *epilogue, const petit_native_args *native) {
+    const SolutionEntry *e;
+    Family fam;
+    bool act = false;
+    unsigned a_format = 0, out_format = 0;
+    if (native_moe_plan(hints, num_experts, m, n, k, nullptr, nullptr, solution_id, epilogue, native, &e, &fam, &act, &a_format, &out_format) != kOk || !e)
+        return 0;
+    return entry_id(fam, *e);
+}
+
+int petit_gemm_native_moe(void *c, const void *a, const void *b, const void *scales, const float *global_scales, const int32_t *expert_offsets,
+                          unsigned num_experts, unsigned m, unsigned n, unsigned k, const int32_t *a_row_index, unsigned a_rows,
+                          const int32_t *c_row_index, unsigned c_rows, const petit_solution_hints *hints, uint64_t solution_id,
+                          const petit_epilogue *epilogue, const petit_native_args *native, void *workspace, uint64_t workspace_bytes, void *stream) {
+    const SolutionEntry *e;
+    Family fam;
+    bool act = false;
+    unsigned a_format = 0, out_format = 0;
+    const bool mx = hints && is_mx_type(hints->b_type);
+    if (!c || !a || !b || (mx && !scales) || !global_scales || !expert_offsets)
+        return kErrProblemShape;
+    if (const int rc = native_moe_plan(hints, num_experts, m, n, k, a_row_index, c_row_index, solution_id, epilogue, native, &e, &fam, &act, &a_format,
+                                       &out_format))
+        return rc;
+    // a null index is the identity: the rows it would name must exist
+    if ((!a_format && !a_row_index && a_rows < m) || (!out_format && !c_row_index && c_rows < m))
+        return kErrProblemShape;
+    // 16-byte loads and stores of A / C, 256-byte aligned scratch and NV6 images (as the dense native entry points)
+    if (((uintptr_t)a & 15) || ((uintptr_t)c & 15) || ((uintptr_t)workspace & 255) || (!workspace && workspace_bytes) || (!mx && ((uintptr_t)b & 255)))
+        return kErrBadArgument;
+    if (m == 0)
+        return kOk;
+    const int klass = entry_class(*e);
+    const void *qa = a;
+    if (!a_format) {
+        if (!workspace || workspace_bytes < qact_bytes(klass, m, k))
+            return kErrKernelShape; // (as the dense native entry points: scratch below the query)
+        const int rc = hints->a_type == kDataTypeBf16 ? quantize32_rows_bf16(a, a_row_index, a_rows, workspace, m, k, klass, (hipStream_t)stream)
+                                                      : quantize32_rows_f16(a, a_row_index, a_rows, workspace, m, k, klass, (hipStream_t)stream);
+        if (rc)
+            return rc;
+        qa = workspace;
+    }
+    MoeArgs g{};
+    g.c = c, g.a = qa, g.w = b, g.s = mx ? scales : nullptr, g.gs = global_scales, g.bias = epilogue ? epilogue->bias : nullptr, g.act = act ? 1u : 0u;
+    g.offsets = expert_offsets, g.num_experts = num_experts, g.m = m, g.n = n, g.k = k;
+    g.c_idx = c_row_index, g.c_rows = c_row_index ? c_rows : m, g.out_format = out_format;
+    return e->launch_moe_native(g, (hipStream_t)stream);
+}
+
+int petit_quantize_activations_rows(void *qa, const void *a, const int32_t *a_row_index, unsigned a_rows, unsigned m, unsigned k, int a_type,
+                                    int format, void *stream) {
+    if (m == 0 || k == 0)
+        return kOk;
+    if (!qa || !a || ((uintptr_t)qa & 15) || ((uintptr_t)a & 15))
+        return kErrBadArgument;
+    if (k % 256 != 0 || (!a_row_index && a_rows < m) || qact_bytes(format, m, k) >= (1ull << 32))
+        return kErrProblemShape;
+    if (a_type == kDataTypeBf16)
+        return quantize32_rows_bf16(a, a_row_index, a_rows, qa, m, k, format, (hipStream_t)stream);
+    if (a_type == kDataTypeFp16)
+        return quantize32_rows_f16(a, a_row_index, a_rows, qa, m, k, format, (hipStream_t)stream);
+    return kErrKernelShape;
+}
 
 int petit_gemm_fp4_fp16_moe(void *c, const void *a, const void *b, const void *scales, const float *global_scales, const int32_t *expert_offsets,
                             unsigned num_experts, unsigned m, unsigned n, unsigned k, const petit_solution_hints *hints, uint64_t solution_id,

@@ -95,6 +95,9 @@ struct MoeArgs {
     // c_idx[r] of c [c_rows][.]; a null index is the identity
     const int32_t *a_idx = nullptr, *c_idx = nullptr;
     unsigned a_rows = 0, c_rows = 0;
+    // the native forms only (petit_gemm_native_moe, gemm_moe_native.hpp): a holds the QUANTISED grouped rows (the kernel's own format), and
+    // out_format 8 / 6 / 4 makes the SiLU-mul epilogue write c as the next launch's quantised grouped rows
+    unsigned out_format = 0;
 };
 // the grid rows a MoE launch needs for any routing (gemm_moe.hpp), 0 when that exceeds the grid's y limit
 inline unsigned moe_slots(unsigned m, unsigned bm, unsigned num_experts) {

@@ -118,6 +118,7 @@ struct SolutionEntry {
     LaunchGroupedFn launch_grouped = nullptr; // the decode and the staged streaming kernels have one (M <= 16)
     LaunchMoeFn launch_moe = nullptr;         // the decode, staged streaming and tiled kernels of moe_tu.inc
     LaunchMoeFn launch_moe_idx = nullptr;     // their indexed forms (gathered A, scattered C): set exactly where launch_moe is
+    LaunchMoeFn launch_moe_native = nullptr;  // 32x32x64 native kernels of moe_native_tu.inc: quantised grouped rows in, scattered C out
 };
 
 // The MoE forms of a family: compiled in translation units of their own (gemm_moe_<family>.hip) and attached to the table entries of the
@@ -137,6 +138,10 @@ const MoeForm *moe_idx_forms_nv_bf16(int *count);
 const MoeForm *moe_idx_forms_nv_f16(int *count);
 const MoeForm *moe_idx_forms_mx_bf16(int *count);
 const MoeForm *moe_idx_forms_mx_f16(int *count);
+const MoeForm *moe_native_forms_nv_bf16(int *count); // (gemm_moe_native_<family>.hip)
+const MoeForm *moe_native_forms_nv_f16(int *count);
+const MoeForm *moe_native_forms_mx_bf16(int *count);
+const MoeForm *moe_native_forms_mx_f16(int *count);
 
 // one table per (activation type, weight format) family, concatenated once (solutions.hip) from the parts its translation units export
 // (stream_tu.inc: gemm_<family>_p<part>.hip)
@@ -165,5 +170,8 @@ const SolutionEntry *solutions_nv_f16_p5(int *);
 // the activation quantiser of the 32x32x64 native kernels, stand-alone (gemm_mx_{bf16,f16}.hip): format 8 = MXFP8, 4 = MXFP4
 int quantize32_bf16(const void *a, void *qa, unsigned m, unsigned k, int format, hipStream_t stream);
 int quantize32_f16(const void *a, void *qa, unsigned m, unsigned k, int format, hipStream_t stream);
+// ... its gathering form (gemm_moe_native_mx_{bf16,f16}.hip): layout row r from row a_idx[r] of a [a_rows][k] (null: row r; outside: a zero row)
+int quantize32_rows_bf16(const void *a, const int *a_idx, unsigned a_rows, void *qa, unsigned m, unsigned k, int format, hipStream_t stream);
+int quantize32_rows_f16(const void *a, const int *a_idx, unsigned a_rows, void *qa, unsigned m, unsigned k, int format, hipStream_t stream);
 
 } // namespace petit_amd

@@ -23,7 +23,7 @@ namespace petit_amd {
 using PartFn = const SolutionEntry *(*)(int *);
 using MoeFormsFn = const MoeForm *(*)(int *);
 static const SolutionEntry *concat_parts(std::vector<SolutionEntry> &store, std::initializer_list<PartFn> parts, MoeFormsFn moe, MoeFormsFn moe_idx,
-                                         int *count) {
+                                         MoeFormsFn moe_native, int *count) {
     if (store.empty()) {
         for (PartFn fn : parts) {
             int n = 0;
@@ -41,6 +41,11 @@ static const SolutionEntry *concat_parts(std::vector<SolutionEntry> &store, std:
             for (SolutionEntry &e : store)
                 if (idx_forms[i].launch && same_shape(e.shape, idx_forms[i].shape))
                     e.launch_moe_idx = idx_forms[i].launch;
+        const MoeForm *native_forms = moe_native(&nf); // (native 32x32x64 entries: gemm_moe_native_<family>.hip)
+        for (int i = 0; i < nf; ++i)
+            for (SolutionEntry &e : store)
+                if (native_forms[i].launch && same_shape(e.shape, native_forms[i].shape))
+                    e.launch_moe_native = native_forms[i].launch;
     }
     *count = (int)store.size();
     return store.data();
@@ -48,7 +53,8 @@ static const SolutionEntry *concat_parts(std::vector<SolutionEntry> &store, std:
 #define PETIT_FAMILY_TABLE(fam, ...)                                                                                               \
     const SolutionEntry *solutions_##fam(int *count) {                                                                             \
         static std::vector<SolutionEntry> store;                                                                                   \
-        static const SolutionEntry *const table = concat_parts(store, {__VA_ARGS__}, moe_forms_##fam, moe_idx_forms_##fam, count); \
+        static const SolutionEntry *const table =                                                                                  \
+            concat_parts(store, {__VA_ARGS__}, moe_forms_##fam, moe_idx_forms_##fam, moe_native_forms_##fam, count);                \
         *count = (int)store.size();                                                                                                \
         return table;                                                                                                              \
     }

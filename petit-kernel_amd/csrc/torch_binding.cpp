@@ -302,6 +302,96 @@ at::Tensor moe_combine(const at::Tensor &slot_out, const at::Tensor &topk_weight
     return out;
 }
 
+// native-class MoE launch (petit_gemm_native_moe); the same checks and texts as petit_kernel/ops.py _mul_native_moe.  A: 16-bit [a_rows,
+// size_k] (a_format 0), or the bytes of the size_m quantised grouped rows (a_format 8 / 6 / 4; a_type names their 16-bit dtype).  Returns
+// 16-bit [c_rows, n_out], or with out_format the bytes of the quantised grouped [size_m, size_n / 2] rows.
+#define PETIT_NATIVE_MOE_ARGS                                                                                                                    \
+    const at::Tensor &A, const at::Tensor &B, const std::optional<at::Tensor> &s, const at::Tensor &global_scales,                                \
+        const at::Tensor &expert_offsets, int64_t size_m, int64_t size_n, int64_t size_k, int64_t num_experts,                                    \
+        const std::optional<at::Tensor> &a_row_index, const std::optional<at::Tensor> &c_row_index, int64_t c_rows, int64_t solution_id,         \
+        const std::optional<at::Tensor> &bias, int64_t activation, int64_t a_format, int64_t a_type, int64_t out_format
+at::ScalarType native_moe_dtype(const at::Tensor &A, int64_t a_format, int64_t a_type) {
+    if (!a_format) {
+        TORCH_CHECK(A.scalar_type() == at::kBFloat16 || A.scalar_type() == at::kHalf, "A must be bfloat16 or float16.");
+        return A.scalar_type();
+    }
+    TORCH_CHECK(A.scalar_type() == at::kByte && (a_type == kCxxBf16 || a_type == kCxxFp16), "quantised activations are uint8 bytes of a bf16 / fp16 matrix");
+    return a_type == kCxxBf16 ? at::kBFloat16 : at::kHalf;
+}
+at::Tensor mul_native_moe_impl(bool mx, PETIT_NATIVE_MOE_ARGS) {
+    const int64_t E = num_experts;
+    const at::ScalarType dtype = native_moe_dtype(A, a_format, a_type);
+    TORCH_CHECK(E >= 1 && E <= PETIT_MOE_MAX_EXPERTS, "num_experts must be in 1..", PETIT_MOE_MAX_EXPERTS, ", got ", E);
+    TORCH_CHECK(A.is_cuda() && B.is_cuda() && global_scales.is_cuda() && expert_offsets.is_cuda() && A.is_contiguous() && B.is_contiguous(),
+                "all tensors must be on GPU");
+    TORCH_CHECK(size_k > 0 && (a_format || A.numel() % size_k == 0), "A must be a contiguous [a_rows, size_k] bfloat16 / float16 GPU tensor");
+    if (a_format)
+        TORCH_CHECK(A.numel() == (int64_t)petit_quantized_activation_bytes((unsigned)size_m, (unsigned)size_k, (int)a_format) && !a_row_index.has_value(),
+                    "quantised activations are grouped rows already: a_row_index must be None");
+    if (mx) {
+        TORCH_CHECK(B.numel() * B.element_size() == E * size_n * size_k / 2, "B does not hold num_experts * size_n * size_k packed 4-bit weights");
+        TORCH_CHECK(s.has_value() && s->is_cuda() && s->is_contiguous() && s->numel() * s->element_size() == E * size_n * size_k / 32,
+                    "s does not hold num_experts * size_n * size_k / 32 scales");
+    } else {
+        const int64_t per = (int64_t)petit_nvfp4_native_image_bytes((unsigned)size_k, (unsigned)size_n);
+        TORCH_CHECK(B.scalar_type() == at::kByte && per > 0 && B.numel() == E * per, "images do not hold num_experts native images (nvfp4_native_images)");
+    }
+    TORCH_CHECK(global_scales.scalar_type() == at::kFloat && global_scales.is_contiguous() && global_scales.numel() == E,
+                "global_scales must be a contiguous float32 [num_experts] tensor");
+    TORCH_CHECK(expert_offsets.scalar_type() == at::kInt && expert_offsets.is_contiguous() && expert_offsets.numel() == E + 1,
+                "expert_offsets must be a contiguous int32 [num_experts + 1] tensor");
+    for (const auto *idx : {&a_row_index, &c_row_index})
+        if (idx->has_value())
+            TORCH_CHECK((*idx)->is_cuda() && (*idx)->device() == A.device() && (*idx)->scalar_type() == at::kInt && (*idx)->is_contiguous() &&
+                            (*idx)->numel() == size_m,
+                        "row indices must be contiguous int32 [size_m] tensors on A's device");
+    TORCH_CHECK(activation == 0 || activation == 1, "activation must be 0 (none) or 1 (silu_mul)");
+    TORCH_CHECK(!out_format || (activation && !c_row_index.has_value()), "out_quantized needs activation='silu_mul' and no c_row_index");
+    if (bias.has_value())
+        TORCH_CHECK(bias->is_cuda() && bias->device() == A.device() && bias->scalar_type() == dtype && bias->is_contiguous() && bias->numel() == E * size_n,
+                    "bias must be a contiguous [num_experts, size_n] tensor of the activation dtype on the same device");
+    const int64_t a_rows = a_format ? size_m : A.numel() / size_k, n_out = activation ? size_n / 2 : size_n;
+    const c10::hip::HIPGuardMasqueradingAsCUDA guard(A.device());
+    at::Tensor c;
+    if (out_format) {
+        c_rows = size_m;
+        c = at::empty({(int64_t)petit_quantized_activation_bytes((unsigned)size_m, (unsigned)n_out, (int)out_format)}, A.options().dtype(at::kByte));
+    } else {
+        c_rows = c_rows < 0 ? size_m : c_rows;
+        c = at::empty({c_rows, n_out}, A.options().dtype(dtype));
+    }
+    const int at_code = dtype == at::kBFloat16 ? kCxxBf16 : kCxxFp16;
+    const petit_solution_hints hints{at_code, mx ? kCxxMxFp4 : kCxxFp4, at_code, 0};
+    const uint64_t sid = solution_id == -2   ? PETIT_SOLUTION_AUTO_NATIVE_MXFP8
+                         : solution_id == -3 ? PETIT_SOLUTION_AUTO_NATIVE_MXFP4
+                         : solution_id == -4 ? PETIT_SOLUTION_AUTO_NATIVE_MXFP6
+                         : solution_id < 0   ? PETIT_SOLUTION_AUTO
+                                             : (uint64_t)solution_id;
+    const petit_epilogue epi{bias.has_value() ? bias->data_ptr() : nullptr, (int32_t)activation, 0};
+    const petit_epilogue *epi_p = (bias.has_value() || activation) ? &epi : nullptr;
+    const petit_native_args na{sizeof(petit_native_args), (int32_t)a_format, (int32_t)out_format, 0};
+    const uint64_t ws_bytes = petit_gemm_native_moe_workspace_bytes(&hints, (unsigned)E, (unsigned)size_m, (unsigned)size_n, (unsigned)size_k, sid, epi_p, &na);
+    at::Tensor ws = at::empty({(int64_t)ws_bytes}, A.options().dtype(at::kByte));
+    const int rc = petit_gemm_native_moe(c.data_ptr(), A.data_ptr(), B.data_ptr(), mx ? s->data_ptr() : nullptr, (const float *)global_scales.data_ptr(),
+                                         (const int32_t *)expert_offsets.data_ptr(), (unsigned)E, (unsigned)size_m, (unsigned)size_n, (unsigned)size_k,
+                                         a_row_index.has_value() ? (const int32_t *)a_row_index->data_ptr() : nullptr, (unsigned)a_rows,
+                                         c_row_index.has_value() ? (const int32_t *)c_row_index->data_ptr() : nullptr, (unsigned)c_rows, &hints, sid,
+                                         epi_p, &na, ws_bytes ? ws.data_ptr() : nullptr, ws_bytes, stream_of(A));
+    TORCH_CHECK(rc != PETIT_ERROR_PROBLEM_SHAPE, "Incompatible problem shape (m=", size_m, ", n=", size_n, ", k=", size_k, ", num_experts=", E,
+                ", a_rows=", a_rows, ", c_rows=", c_rows, ")");
+    TORCH_CHECK(rc != PETIT_ERROR_KERNEL_SHAPE, "No kernel implementation for solution_id=", solution_id < 0 ? std::to_string(solution_id) : std::to_string((int64_t)sid), ".");
+    TORCH_CHECK(rc == PETIT_OK, mx ? "mul_mxfp4_native_moe: " : "mul_nvfp4_native_moe: ", petit_error_string(rc));
+    return c;
+}
+at::Tensor mul_mxfp4_native_moe(PETIT_NATIVE_MOE_ARGS) {
+    return mul_native_moe_impl(true, A, B, s, global_scales, expert_offsets, size_m, size_n, size_k, num_experts, a_row_index, c_row_index, c_rows,
+                               solution_id, bias, activation, a_format, a_type, out_format);
+}
+at::Tensor mul_nvfp4_native_moe(PETIT_NATIVE_MOE_ARGS) {
+    return mul_native_moe_impl(false, A, B, s, global_scales, expert_offsets, size_m, size_n, size_k, num_experts, a_row_index, c_row_index, c_rows,
+                               solution_id, bias, activation, a_format, a_type, out_format);
+}
+
 // Shape functions for the Meta key (FakeTensor / torch.compile tracing, torch.export): outputs of the right shape, dtype and
 // device, nothing launched -- the ops trace as opaque calls instead of breaking the graph.
 at::Tensor repack_nvfp4_meta(const at::Tensor &q, int64_t n, int64_t k) { return at::empty({n / kLayoutN, k * kLayoutN / kPack}, q.options()); }
@@ -323,6 +413,13 @@ at::Tensor mul_a16_moe_indexed_meta(PETIT_MOE_INDEXED_ARGS) {
     return at::empty({c_rows < 0 ? m : c_rows, activation ? n / 2 : n}, A.options());
 }
 void mul_a16_moe_indexed_out_meta(const at::Tensor &, PETIT_MOE_INDEXED_ARGS) {}
+at::Tensor mul_native_moe_meta(PETIT_NATIVE_MOE_ARGS) {
+    const at::ScalarType dtype = native_moe_dtype(A, a_format, a_type);
+    const int64_t n_out = activation ? size_n / 2 : size_n;
+    if (out_format)
+        return at::empty({(int64_t)petit_quantized_activation_bytes((unsigned)size_m, (unsigned)n_out, (int)out_format)}, A.options().dtype(at::kByte));
+    return at::empty({c_rows < 0 ? size_m : c_rows, n_out}, A.options().dtype(dtype));
+}
 std::tuple<at::Tensor, at::Tensor, at::Tensor> moe_align_device_meta(const at::Tensor &topk_ids, int64_t num_experts) {
     const auto i32 = topk_ids.options().dtype(at::kInt);
     const int64_t entries = topk_ids.size(0) * topk_ids.size(1);
@@ -356,6 +453,12 @@ TORCH_LIBRARY(petit_kernel, m) {
     m.def("mul_mxfp4_a16_moe_indexed(" PETIT_MOE_INDEXED_SCHEMA ") -> Tensor");
     m.def("mul_nvfp4_a16_moe_indexed_out(Tensor(a!) out, " PETIT_MOE_INDEXED_SCHEMA ") -> ()");
     m.def("mul_mxfp4_a16_moe_indexed_out(Tensor(a!) out, " PETIT_MOE_INDEXED_SCHEMA ") -> ()");
+#define PETIT_NATIVE_MOE_SCHEMA                                                                                                           \
+    "Tensor A, Tensor B, Tensor? s, Tensor global_scales, Tensor expert_offsets, int size_m, int size_n, int size_k, int num_experts, "    \
+    "Tensor? a_row_index=None, Tensor? c_row_index=None, int c_rows=-1, int solution_id=-2, Tensor? bias=None, int activation=0, "        \
+    "int a_format=0, int a_type=5, int out_format=0"
+    m.def("mul_mxfp4_native_moe(" PETIT_NATIVE_MOE_SCHEMA ") -> Tensor");
+    m.def("mul_nvfp4_native_moe(" PETIT_NATIVE_MOE_SCHEMA ") -> Tensor");
     m.def("moe_align_device(Tensor topk_ids, int num_experts) -> (Tensor, Tensor, Tensor)");
     m.def("moe_combine(Tensor slot_out, Tensor topk_weights, Tensor topk_ids, int num_experts) -> Tensor");
     // round 3's op name (scales promised inside fp16's range): an alias of mul_mxfp4_a16 for one more round -- the kernels test the range themselves
@@ -375,6 +478,8 @@ TORCH_LIBRARY(petit_kernel, m) {
     m.impl("mul_mxfp4_a16_moe_indexed", &mul_mxfp4_a16_moe_indexed); \
     m.impl("mul_nvfp4_a16_moe_indexed_out", &mul_nvfp4_a16_moe_indexed_out); \
     m.impl("mul_mxfp4_a16_moe_indexed_out", &mul_mxfp4_a16_moe_indexed_out); \
+    m.impl("mul_mxfp4_native_moe", &mul_mxfp4_native_moe);      \
+    m.impl("mul_nvfp4_native_moe", &mul_nvfp4_native_moe);      \
     m.impl("moe_align_device", &moe_align_device);              \
     m.impl("moe_combine", &moe_combine);
 TORCH_LIBRARY_IMPL(petit_kernel, CUDA, m) { PETIT_IMPL_REAL(m) }
@@ -392,6 +497,8 @@ TORCH_LIBRARY_IMPL(petit_kernel, Meta, m) {
     m.impl("mul_mxfp4_a16_moe_indexed", &mul_a16_moe_indexed_meta);
     m.impl("mul_nvfp4_a16_moe_indexed_out", &mul_a16_moe_indexed_out_meta);
     m.impl("mul_mxfp4_a16_moe_indexed_out", &mul_a16_moe_indexed_out_meta);
+    m.impl("mul_mxfp4_native_moe", &mul_native_moe_meta);
+    m.impl("mul_nvfp4_native_moe", &mul_native_moe_meta);
     m.impl("moe_align_device", &moe_align_device_meta);
     m.impl("moe_combine", &moe_combine_meta);
 }

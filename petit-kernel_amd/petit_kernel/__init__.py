@@ -13,9 +13,9 @@ import enum
 import torch
 
 from . import compiled, offline, ops, tuning
-from .moe import fp4_moe, fp4_moe_fused, moe_align
+from .moe import fp4_moe, fp4_moe_fused, fp4_moe_native, moe_align
 from .ops import QuantizedActivations, mul_fp4_a16_grouped, mul_mxfp4_native, quantize_activations
-from .ops import attach_nvfp4_native, mul_nvfp4_native, nvfp4_native_image
+from .ops import attach_nvfp4_native, mul_nvfp4_native, nvfp4_native_image, nvfp4_native_images
 from .tuning import tune, tune_tensors
 from .ops import SOLUTION_AUTO, SOLUTION_AUTO_NATIVE_MXFP4, SOLUTION_AUTO_NATIVE_MXFP6, SOLUTION_AUTO_NATIVE_MXFP8, PetitSolutionHints
 from ._lib import MXFP4_F16RANGE_SCALE_MAX, MXFP4_F16RANGE_SCALE_MIN
@@ -135,6 +135,35 @@ def moe_combine(slot_out: torch.Tensor, topk_weights: torch.Tensor, topk_ids: to
     return _impl.moe_combine(slot_out, topk_weights, topk_ids, num_experts)
 
 
+def mul_mxfp4_native_moe(a, b: torch.Tensor, s: torch.Tensor, global_scales: torch.Tensor, expert_offsets: torch.Tensor, size_m: int, size_n: int,
+                         size_k: int, num_experts: int, a_row_index: torch.Tensor = None, c_row_index: torch.Tensor = None, c_rows: int = None,
+                         solution_id: int = SOLUTION_AUTO_NATIVE_MXFP8, bias: torch.Tensor = None, activation: str = None, out_quantized: str = None):
+    # the MoE launch on the native class (include/petit_amd.h "Native-class MoE launch"): `a` 16-bit [a_rows, size_k] (gathered through
+    # a_row_index, quantised by the call) or QuantizedActivations of the size_m grouped rows; solution_id a native sentinel or a native id with
+    # a MoE form; out_quantized (activation "silu_mul") returns the grouped rows quantised for the next launch
+    return _impl.mul_mxfp4_native_moe(a, b, s, global_scales, expert_offsets, size_m, size_n, size_k, num_experts, a_row_index, c_row_index, c_rows,
+                                      solution_id, bias, activation, out_quantized)
+
+
+def mul_nvfp4_native_moe(a, images: torch.Tensor, global_scales: torch.Tensor, expert_offsets: torch.Tensor, size_m: int, size_n: int, size_k: int,
+                         num_experts: int, a_row_index: torch.Tensor = None, c_row_index: torch.Tensor = None, c_rows: int = None,
+                         solution_id: int = SOLUTION_AUTO_NATIVE_MXFP8, bias: torch.Tensor = None, activation: str = None, out_quantized: str = None):
+    # NVFP4 experts on the native class: `images` = nvfp4_native_images of the stacked packed tensors (E images back to back)
+    return _impl.mul_nvfp4_native_moe(a, images, global_scales, expert_offsets, size_m, size_n, size_k, num_experts, a_row_index, c_row_index, c_rows,
+                                      solution_id, bias, activation, out_quantized)
+
+
+def quantize_activation_rows(a: torch.Tensor, fmt: str = "mxfp8", row_index: torch.Tensor = None, rows: int = None) -> QuantizedActivations:
+    # quantize_activations of the rows row_index names (None: all rows); an index outside the matrix gives a zero row
+    return ops.quantize_activation_rows(a, fmt, row_index, rows)
+
+
+def native_moe_resolve_solution(hints: PetitSolutionHints, num_experts: int, size_m: int, size_n: int, size_k: int,
+                                solution_id: int = SOLUTION_AUTO_NATIVE_MXFP8, activation: str = None, a_format: str = None,
+                                out_quantized: str = None) -> int:
+    return ops.native_moe_resolve_solution(hints, num_experts, size_m, size_n, size_k, solution_id, activation, a_format, out_quantized)
+
+
 def moe_resolve_solution(hints: PetitSolutionHints, num_experts: int, size_m: int, size_n: int, size_k: int, solution_id: int = -1,
                          activation: str = None) -> int:
     return ops.moe_resolve_solution(hints, num_experts, size_m, size_n, size_k, solution_id, activation)
@@ -169,6 +198,12 @@ __all__ = [
     "mul_mxfp4_a16_moe_indexed",
     "moe_align_device",
     "moe_combine",
+    "fp4_moe_native",
+    "mul_mxfp4_native_moe",
+    "mul_nvfp4_native_moe",
+    "quantize_activation_rows",
+    "nvfp4_native_images",
+    "native_moe_resolve_solution",
     "mul_mxfp4_native",
     "nvfp4_native_image",
     "attach_nvfp4_native",

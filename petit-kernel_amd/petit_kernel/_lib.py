@@ -126,6 +126,13 @@ _SIGNATURES = {
                                                        C.POINTER(NativeArgs)]),
     "petit_quantized_activation_bytes": (C.c_uint64, [C.c_uint, C.c_uint, C.c_int]),
     "petit_quantize_activations": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint, C.c_uint, C.c_int, C.c_int, C.c_void_p]),
+    "petit_quantize_activations_rows": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p] + [C.c_uint] * 3 + [C.c_int, C.c_int, C.c_void_p]),
+    "petit_gemm_native_moe_workspace_bytes": (C.c_uint64, [C.POINTER(SolutionHints)] + [C.c_uint] * 4 + [C.c_uint64, C.POINTER(Epilogue),
+                                                                                                        C.POINTER(NativeArgs)]),
+    "petit_gemm_native_moe_resolve_solution": (C.c_uint64, [C.POINTER(SolutionHints)] + [C.c_uint] * 4 + [C.c_uint64, C.POINTER(Epilogue),
+                                                                                                         C.POINTER(NativeArgs)]),
+    "petit_gemm_native_moe": (C.c_int, [C.c_void_p] * 6 + [C.c_uint] * 4 + [C.c_void_p, C.c_uint, C.c_void_p, C.c_uint] +
+                              [C.POINTER(SolutionHints), C.c_uint64, C.POINTER(Epilogue), C.POINTER(NativeArgs), C.c_void_p, C.c_uint64, C.c_void_p]),
     "petit_gemm_tune": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint, C.c_uint, C.c_uint, C.POINTER(SolutionHints),
                                   C.POINTER(TuneParams), C.c_void_p, C.c_uint64, C.c_void_p, C.POINTER(C.c_uint64), C.POINTER(C.c_float)]),
     "petit_tune_reserve": (C.c_int, [C.c_void_p, C.c_uint64]),

@@ -78,3 +78,44 @@ def fp4_moe_fused(hidden: torch.Tensor, w13: torch.Tensor, s13: torch.Tensor, gs
     h = mul(hidden, w13, s13, gs13, offsets, m, n13, H, E, a_row_index=token_index, activation="silu_mul")   # [m, I], grouped order
     y = mul(h, w2, s2, gs2, offsets, m, H, inter, E, c_row_index=sorted_pos, c_rows=m)                       # [m, H], (token, slot) order
     return moe_combine(y, w, ids, E)
+
+
+_NATIVE_SENTINELS = {"mxfp8": -2, "mxfp4": -3, "mxfp6": -4}   # SOLUTION_AUTO_NATIVE_MXFP8 / _MXFP4 / _MXFP6
+
+
+def fp4_moe_native(hidden: torch.Tensor, w13: torch.Tensor, s13, gs13: torch.Tensor, w2: torch.Tensor, s2, gs2: torch.Tensor,
+                   topk_weights: torch.Tensor, topk_ids: torch.Tensor, kind: str = "mxfp4", activations: str = "mxfp8") -> torch.Tensor:
+    """fp4_moe_fused's layer on the NATIVE class (the block-scaled MFMA, activations quantised to `activations`: 'mxfp8', 'mxfp6' or 'mxfp4';
+    petit_gemm_native_moe -- a different accuracy class than the exact layers).  kind 'mxfp4': w13 / s13 / w2 / s2 as fp4_moe_fused; kind
+    'nvfp4': w13 / w2 are the experts' MFMA-native images back to back (nvfp4_native_images) and s13 / s2 are None.  Five launches (seven
+    when the align needs its three-launch form): the device align, the gathering quantiser, gate_up with SiLU-mul writing the quantised
+    grouped rows down reads, down scattered into slot order, the top-k combine.  No host sync: capturable."""
+    from . import moe_align_device, moe_combine, mul_mxfp4_native_moe, mul_nvfp4_native_moe, quantize_activation_rows
+    if kind not in ("nvfp4", "mxfp4"):
+        raise RuntimeError("kind must be 'nvfp4' or 'mxfp4'")
+    if activations not in _NATIVE_SENTINELS:
+        raise RuntimeError("activations must be 'mxfp8', 'mxfp6' or 'mxfp4'")
+    sid = _NATIVE_SENTINELS[activations]
+    T, H = hidden.shape
+    topk = topk_ids.shape[1]
+    E = gs13.numel()
+    if kind == "mxfp4":
+        n13 = w13.numel() * w13.element_size() * 2 // (E * H)   # 2 I
+        mul13 = lambda a, **kw: mul_mxfp4_native_moe(a, w13, s13, gs13, offsets, m, n13, H, E, solution_id=sid, **kw)  # noqa: E731
+        mul2 = lambda a, **kw: mul_mxfp4_native_moe(a, w2, s2, gs2, offsets, m, H, inter, E, solution_id=sid, **kw)  # noqa: E731
+    else:
+        n13 = w13.numel() * 32 // (E * H * 25)                  # an image holds 25 / 32 bytes per weight (6.25 bits)
+        mul13 = lambda a, **kw: mul_nvfp4_native_moe(a, w13, gs13, offsets, m, n13, H, E, solution_id=sid, **kw)  # noqa: E731
+        mul2 = lambda a, **kw: mul_nvfp4_native_moe(a, w2, gs2, offsets, m, H, inter, E, solution_id=sid, **kw)  # noqa: E731
+    inter = n13 // 2
+    m = T * topk
+    ids = topk_ids if topk_ids.dtype in (torch.int32, torch.int64) and topk_ids.is_contiguous() else topk_ids.contiguous().to(torch.int64)
+    w = topk_weights if topk_weights.dtype == torch.float32 and topk_weights.is_contiguous() else topk_weights.float().contiguous()
+    sorted_pos, offsets, token_index = moe_align_device(ids, E)
+    qa = quantize_activation_rows(hidden, activations, token_index)                  # grouped rows; unrouted (-1) rows are zeros
+    if n13 % 512 == 0:
+        h = mul13(qa, activation="silu_mul", out_quantized=activations)              # down's quantised input, grouped
+    else:
+        h = mul13(qa, activation="silu_mul")                                         # 16-bit; down quantises it (one more launch)
+    y = mul2(h, c_row_index=sorted_pos, c_rows=m)                                    # [m, H], (token, slot) order
+    return moe_combine(y, w, ids, E)

@@ -777,3 +777,147 @@ def moe_resolve_solution(hints: PetitSolutionHints, num_experts: int, size_m: in
     epi = _lib.Epilogue(None, act, 0)
     return int(_lib.lib.petit_gemm_moe_resolve_solution(C.byref(ch), int(num_experts), size_m, size_n, size_k,
                                                         C.c_uint64(_c_solution_id(solution_id)), C.byref(epi) if act else None))
+
+
+# --- native-class MoE (include/petit_amd.h "Native-class MoE launch"; no counterpart in the reference) ------------------------------------
+
+def quantize_activation_rows(A: torch.Tensor, fmt: str = "mxfp8", row_index: torch.Tensor = None, rows: int = None) -> QuantizedActivations:
+    """quantize_activations of gathered rows (petit_quantize_activations_rows): row r of the result is row row_index[r] of A [a_rows, k]
+    (None: row r; rows = row_index.numel(), or A's row count).  An index outside [0, a_rows) gives a zero row.  One launch, any row count."""
+    _check(fmt in _QFORMATS, "fmt must be 'mxfp8', 'mxfp6' or 'mxfp4'")
+    _check(A.is_cuda and A.is_contiguous() and A.dim() == 2 and A.dtype in (torch.bfloat16, torch.float16),
+           "A must be a contiguous 2-D bfloat16 / float16 GPU tensor")
+    a_rows, k = A.shape
+    if row_index is not None:
+        _check(row_index.is_cuda and row_index.device == A.device and row_index.dtype == torch.int32 and row_index.is_contiguous() and
+               row_index.dim() == 1, "row_index must be a contiguous int32 1-D tensor on A's device")
+        _check(rows is None or rows == row_index.numel(), "rows does not match row_index.numel()")
+        m = row_index.numel()
+    else:
+        m = a_rows if rows is None else int(rows)
+    nbytes = int(_lib.lib.petit_quantized_activation_bytes(m, k, _QFORMATS[fmt]))
+    qa = torch.empty(nbytes, dtype=torch.uint8, device=A.device)
+    with torch.cuda.device(A.device):
+        rc = _lib.lib.petit_quantize_activations_rows(_ptr(qa), _ptr(A), _ptr(row_index) if row_index is not None else None, a_rows, m, k,
+                                                      _lib.CXX_DTYPE_BF16 if A.dtype == torch.bfloat16 else _lib.CXX_DTYPE_FP16, _QFORMATS[fmt],
+                                                      _stream(A))
+    if rc == _lib.PETIT_ERROR_PROBLEM_SHAPE:
+        raise RuntimeError(f"Incompatible problem shape (m={m}, k={k}, a_rows={a_rows})")
+    _raise_on(rc, "quantize_activation_rows")
+    return QuantizedActivations(qa, m, k, fmt, A.dtype)
+
+
+def nvfp4_native_images(B: torch.Tensor, s: torch.Tensor, num_experts: int, size_n: int, size_k: int) -> torch.Tensor:
+    """The MFMA-native images of E stacked NVFP4 experts, back to back (what mul_nvfp4_native_moe reads): expert e's image is
+    nvfp4_native_image of its slice of the stacked packed tensors B / s (repack_nvfp4 / process_nvfp4_scales of [E * size_n, size_k])."""
+    E = int(num_experts)
+    _check(1 <= E <= _lib.PETIT_MOE_MAX_EXPERTS, f"num_experts must be in 1..{_lib.PETIT_MOE_MAX_EXPERTS}, got {E}")
+    wb = size_n * size_k // 2
+    sb = size_n * size_k // 16
+    _check(B.is_cuda and s.is_cuda and B.is_contiguous() and s.is_contiguous(), "B and s must be contiguous GPU tensors")
+    _check(B.numel() * B.element_size() == E * wb, "B does not hold num_experts * size_n * size_k packed 4-bit weights")
+    _check(s.numel() * s.element_size() == E * sb, "s does not hold num_experts * size_n * size_k / 16 scales")
+    per = int(_lib.lib.petit_nvfp4_native_image_bytes(size_k, size_n))
+    _check(per > 0, f"no native image for size_n={size_n}, size_k={size_k}")
+    out = torch.empty(E * per, dtype=torch.uint8, device=B.device)
+    bb, ss = B.view(torch.uint8).reshape(-1), s.view(torch.uint8).reshape(-1)
+    with torch.cuda.device(B.device):
+        for e in range(E):
+            rc = _lib.lib.petit_nvfp4_native_image(_ptr(out[e * per:]), _ptr(bb[e * wb:]), _ptr(ss[e * sb:]), size_k, size_n, _stream(B))
+            _raise_on(rc, "nvfp4_native_images")
+    return out
+
+
+def _mul_native_moe(kind: str, A, B, s, global_scales, expert_offsets, size_m, size_n, size_k, num_experts, a_row_index=None, c_row_index=None,
+                    c_rows=None, solution_id=SOLUTION_AUTO_NATIVE_MXFP8, bias=None, activation=None, out_quantized=None):
+    """The routed-expert launch on the native class (petit_gemm_native_moe).  A: 16-bit [a_rows, size_k] (gathered through a_row_index and
+    quantised by the call: two launches) or QuantizedActivations of the size_m grouped rows (one launch).  Output: 16-bit [c_rows, n_out], row
+    c_row_index[r] for grouped row r (None: the identity), or with out_quantized (activation='silu_mul') QuantizedActivations of the grouped
+    [size_m, size_n / 2] rows for the next launch."""
+    pre = isinstance(A, QuantizedActivations)
+    E = int(num_experts)
+    _check(1 <= E <= _lib.PETIT_MOE_MAX_EXPERTS, f"num_experts must be in 1..{_lib.PETIT_MOE_MAX_EXPERTS}, got {E}")
+    if pre:
+        _check(A.m == size_m and A.k == size_k, f"quantised activations are [{A.m}, {A.k}], the call says [{size_m}, {size_k}]")
+        _check(a_row_index is None, "quantised activations are grouped rows already: a_row_index must be None")
+        a_t, dtype, a_fmt, dev, a_rows = A.data, A.dtype, _QFORMATS[A.fmt], A.data.device, size_m
+    else:
+        _check(A.is_cuda and A.is_contiguous() and A.dtype in (torch.bfloat16, torch.float16) and size_k > 0 and A.numel() % size_k == 0,
+               "A must be a contiguous [a_rows, size_k] bfloat16 / float16 GPU tensor")
+        a_t, dtype, a_fmt, dev, a_rows = A, A.dtype, 0, A.device, A.numel() // size_k
+    _check(B.is_cuda and global_scales.is_cuda and expert_offsets.is_cuda and B.is_contiguous(), "all tensors must be on GPU")
+    if kind == "mx":
+        _check(B.numel() * B.element_size() == E * size_n * size_k // 2, "B does not hold num_experts * size_n * size_k packed 4-bit weights")
+        _check(s is not None and s.is_cuda and s.is_contiguous() and s.numel() * s.element_size() == E * size_n * size_k // 32,
+               "s does not hold num_experts * size_n * size_k / 32 scales")
+    else:
+        per = int(_lib.lib.petit_nvfp4_native_image_bytes(size_k, size_n))
+        _check(B.dtype == torch.uint8 and per > 0 and B.numel() == E * per, "images do not hold num_experts native images (nvfp4_native_images)")
+    _check(global_scales.dtype == torch.float32 and global_scales.is_contiguous() and global_scales.numel() == E,
+           "global_scales must be a contiguous float32 [num_experts] tensor")
+    _check(expert_offsets.dtype == torch.int32 and expert_offsets.is_contiguous() and expert_offsets.numel() == E + 1,
+           "expert_offsets must be a contiguous int32 [num_experts + 1] tensor")
+    for idx in (a_row_index, c_row_index):
+        if idx is not None:
+            _check(idx.is_cuda and idx.device == dev and idx.dtype == torch.int32 and idx.is_contiguous() and idx.numel() == size_m,
+                   "row indices must be contiguous int32 [size_m] tensors on A's device")
+    _check(activation in _ACTIVATIONS, f"activation must be one of {sorted(k for k in _ACTIVATIONS if k)} or None")
+    _check(out_quantized is None or out_quantized in _QFORMATS, "out_quantized must be None, 'mxfp8', 'mxfp6' or 'mxfp4'")
+    act = _ACTIVATIONS[activation]
+    out_fmt = _QFORMATS[out_quantized] if out_quantized else 0
+    _check(not out_fmt or (act and c_row_index is None), "out_quantized needs activation='silu_mul' and no c_row_index")
+    if bias is not None:
+        _check(bias.is_cuda and bias.device == dev and bias.dtype == dtype and bias.is_contiguous() and bias.numel() == E * size_n,
+               "bias must be a contiguous [num_experts, size_n] tensor of the activation dtype on the same device")
+    a_type = _lib.CXX_DTYPE_BF16 if dtype == torch.bfloat16 else _lib.CXX_DTYPE_FP16
+    hints = _CHints(a_type, _lib.CXX_DTYPE_FP4_E2M1 if kind == "nv" else _lib.CXX_DTYPE_MXFP4_E2M1, a_type, 0)
+    sid = _c_solution_id(solution_id, native_ok=True)
+    epi = _lib.Epilogue(bias.data_ptr() if bias is not None else None, act, 0) if (bias is not None or act) else None
+    epi_p = C.byref(epi) if epi is not None else None
+    na = _lib.NativeArgs(C.sizeof(_lib.NativeArgs), a_fmt, out_fmt, 0)
+    n_out = size_n // 2 if act else size_n
+    if out_fmt:
+        c_rows = size_m
+        c = torch.empty(int(_lib.lib.petit_quantized_activation_bytes(size_m, n_out, out_fmt)), dtype=torch.uint8, device=dev)
+    else:
+        c_rows = size_m if c_rows is None or c_rows < 0 else int(c_rows)
+        c = torch.empty((c_rows, n_out), dtype=dtype, device=dev)
+    ws_bytes = int(_lib.lib.petit_gemm_native_moe_workspace_bytes(C.byref(hints), E, size_m, size_n, size_k, C.c_uint64(sid), epi_p, C.byref(na)))
+    ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev) if ws_bytes else None
+    with torch.cuda.device(dev):
+        err = _lib.lib.petit_gemm_native_moe(_ptr(c), _ptr(a_t), _ptr(B), _ptr(s) if s is not None else None, _ptr(global_scales),
+                                             _ptr(expert_offsets), E, size_m, size_n, size_k,
+                                             _ptr(a_row_index) if a_row_index is not None else None, a_rows,
+                                             _ptr(c_row_index) if c_row_index is not None else None, c_rows, C.byref(hints), C.c_uint64(sid),
+                                             epi_p, C.byref(na), _ptr(ws) if ws is not None else None, C.c_uint64(ws_bytes),
+                                             C.c_void_p(torch.cuda.current_stream(dev).cuda_stream))
+    if err == _lib.PETIT_ERROR_PROBLEM_SHAPE:
+        raise RuntimeError(f"Incompatible problem shape (m={size_m}, n={size_n}, k={size_k}, num_experts={E}, a_rows={a_rows}, c_rows={c_rows})")
+    if err == _lib.PETIT_ERROR_KERNEL_SHAPE:
+        raise RuntimeError(f"No kernel implementation for solution_id={solution_id}.")
+    _raise_on(err, "mul_%sfp4_native_moe" % kind)
+    return QuantizedActivations(c, size_m, n_out, out_quantized, dtype) if out_fmt else c
+
+
+def mul_mxfp4_native_moe(A, B, s, global_scales, expert_offsets, size_m, size_n, size_k, num_experts, a_row_index=None, c_row_index=None,
+                         c_rows=None, solution_id=SOLUTION_AUTO_NATIVE_MXFP8, bias=None, activation=None, out_quantized=None):
+    return _mul_native_moe("mx", A, B, s, global_scales, expert_offsets, size_m, size_n, size_k, num_experts, a_row_index, c_row_index, c_rows,
+                           solution_id, bias, activation, out_quantized)
+
+
+def mul_nvfp4_native_moe(A, images, global_scales, expert_offsets, size_m, size_n, size_k, num_experts, a_row_index=None, c_row_index=None,
+                         c_rows=None, solution_id=SOLUTION_AUTO_NATIVE_MXFP8, bias=None, activation=None, out_quantized=None):
+    return _mul_native_moe("nv", A, images, None, global_scales, expert_offsets, size_m, size_n, size_k, num_experts, a_row_index, c_row_index,
+                           c_rows, solution_id, bias, activation, out_quantized)
+
+
+def native_moe_resolve_solution(hints: PetitSolutionHints, num_experts: int, size_m: int, size_n: int, size_k: int,
+                                solution_id: int = SOLUTION_AUTO_NATIVE_MXFP8, activation=None, a_format: str = None, out_quantized: str = None) -> int:
+    """The kernel id petit_gemm_native_moe runs for these arguments (the launcher's own pick); 0 when the call would be refused."""
+    ch = _c_hints(hints)
+    act = _ACTIVATIONS[activation]
+    epi = _lib.Epilogue(None, act, 0)
+    na = _lib.NativeArgs(C.sizeof(_lib.NativeArgs), _QFORMATS[a_format] if a_format else 0, _QFORMATS[out_quantized] if out_quantized else 0, 0)
+    return int(_lib.lib.petit_gemm_native_moe_resolve_solution(C.byref(ch), int(num_experts), size_m, size_n, size_k,
+                                                               C.c_uint64(_c_solution_id(solution_id, native_ok=True)), C.byref(epi) if act else None,
+                                                               C.byref(na)))

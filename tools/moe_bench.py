@@ -2,7 +2,7 @@
 """tools/moe_bench.py -- the routed-expert (MoE) launch against a host loop of dense calls, on real expert shapes.
 
     python tools/moe_bench.py [--cells decode|prefill|all] [--models deepseek,qwen3,mixtral] [--iters N] [--out FILE]
-                              [--only-moe | --only-loop] [--single-expert] [--layer]
+                              [--only-moe | --only-loop] [--single-expert] [--layer [--native mxfp8|mxfp6|mxfp4]]
 
 Per cell (model, projection, T tokens): E experts' NVFP4 weights (bf16 activations) stacked back to back, copied until the pool is >= 1 GB so
 that rotating over copies and over routings (drawn from a seed, top-k of random router logits) keeps the 256 MB Infinity Cache from serving
@@ -15,6 +15,9 @@ the weights.  Timed with HIP events over `--iters` iterations (eager launches):
 --layer: the whole routed-expert layer (gate_up with SiLU-mul, down, top-k combine; DeepSeek-V3 / Qwen3-30B-A3B / Mixtral shapes), fp4_moe
 against fp4_moe_fused, each captured once in a torch.cuda.graph (one capture stream, no parallel branches) and replayed; per cell also the
 plain MoE GEMMs on pre-gathered rows against the indexed ones (gate_up gathering A, down scattering C), ten launches per captured graph.
+--layer --native mxfp8|mxfp6|mxfp4: fp4_moe_native against fp4_moe_fused on the same weights (MXFP4 raw; NVFP4 through nvfp4_native_images), graph
+replays, T = 1, 16, 64, 1024, 4096; plus one single-expert cell (M = 4096, every row on one expert, activations pre-quantised: the native MoE launch
+against the dense native call with the same id).
 Kernel times without launch gaps: run under `rocprofv3 --kernel-trace --stats -- python tools/moe_bench.py ...`.
 Prints one JSON object (and writes it to --out).
 """
@@ -155,6 +158,7 @@ def single_expert(pk, iters):
 
 
 LAYER_T = (1, 4, 16, 64, 1024, 4096)
+NATIVE_LAYER_T = (1, 16, 64, 1024, 4096)
 
 
 def graph_us(fn, iters, per_graph=1):
@@ -223,6 +227,79 @@ def layer_cells(pk, models, ts, iters):
     return cells
 
 
+def native_layer_cells(pk, models, ts, iters, fmt):
+    """--layer --native FMT: fp4_moe_native (activations quantised to FMT) against fp4_moe_fused on the same weights: MXFP4 weights raw, NVFP4
+    weights through their native images (nvfp4_native_images) -- graph replays, as layer_cells"""
+    cells = []
+    for name in models:
+        (n13, hid), (_, inter), E, topk = MODELS[name]
+        g = torch.Generator(device="cuda").manual_seed(11)
+        rnd = lambda rows, cols: torch.randint(-2 ** 31, 2 ** 31 - 1, (rows, cols), dtype=torch.int32, device="cuda", generator=g)  # noqa: E731
+        mx = {"w13": rnd(E * n13 // 16, 2 * hid), "w2": rnd(E * hid // 16, 2 * inter),
+              "s13": torch.randint(118, 127, (E * n13 // 32, hid), dtype=torch.uint8, device="cuda", generator=g),
+              "s2": torch.randint(118, 127, (E * hid // 32, inter), dtype=torch.uint8, device="cuda", generator=g)}
+        nv = {"w13": rnd(E * n13 // 16, 2 * hid), "w2": rnd(E * hid // 16, 2 * inter),
+              "s13": torch.randint(0x28, 0x40, (E * n13, hid // 16), dtype=torch.uint8, device="cuda", generator=g).view(torch.float8_e4m3fn),
+              "s2": torch.randint(0x28, 0x40, (E * hid, inter // 16), dtype=torch.uint8, device="cuda", generator=g).view(torch.float8_e4m3fn)}
+        nv["i13"] = pk.nvfp4_native_images(nv["w13"], nv["s13"], E, n13, hid)
+        nv["i2"] = pk.nvfp4_native_images(nv["w2"], nv["s2"], E, hid, inter)
+        gs13, gs2 = torch.rand(E, device="cuda") * 0.01 + 0.01, torch.rand(E, device="cuda") * 0.01 + 0.01
+        for T in ts:
+            it = iters if T < 1024 else max(5, iters // 5)
+            x = torch.randn(T, hid, device="cuda").to(torch.bfloat16)
+            logits = torch.randn(T, E, device="cuda", generator=g)
+            tw, tid = torch.topk(torch.softmax(logits, -1), topk, dim=-1)
+            tw, tid = tw.float().contiguous(), tid.to(torch.int32).contiguous()
+            r = {"model": name, "T": T, "E": E, "topk": topk, "hidden": hid, "inter": inter, "activations": fmt}
+            fused = lambda w, kind: pk.fp4_moe_fused(x, w["w13"], w["s13"], gs13, w["w2"], w["s2"], gs2, tw, tid, kind=kind)  # noqa: E731
+            r["mx_fused_us"] = graph_us(lambda: fused(mx, "mxfp4"), it)
+            r["mx_native_us"] = graph_us(lambda: pk.fp4_moe_native(x, mx["w13"], mx["s13"], gs13, mx["w2"], mx["s2"], gs2, tw, tid, kind="mxfp4",
+                                                                    activations=fmt), it)
+            r["nv_fused_us"] = graph_us(lambda: fused(nv, "nvfp4"), it)
+            r["nv_native_us"] = graph_us(lambda: pk.fp4_moe_native(x, nv["i13"], None, gs13, nv["i2"], None, gs2, tw, tid, kind="nvfp4",
+                                                                    activations=fmt), it)
+            r["mx_speedup"] = r["mx_fused_us"] / r["mx_native_us"]
+            r["nv_speedup"] = r["nv_fused_us"] / r["nv_native_us"]
+            print(json.dumps(r), file=sys.stderr, flush=True)
+            cells.append(r)
+        del mx, nv
+        torch.cuda.empty_cache()
+    return cells
+
+
+def native_single_expert(pk, iters, fmt, m=4096):
+    """every row on one expert (DeepSeek-V3 gate_up, MXFP4, E = 256), activations pre-quantised: the native MoE launch against the dense native
+    call with the same id (the indirection cost)"""
+    E, n, k = 256, 4096, 7168
+    g = torch.Generator(device="cuda").manual_seed(5)
+    w = torch.randint(-2 ** 31, 2 ** 31 - 1, (E * n // 16, 2 * k), dtype=torch.int32, device="cuda", generator=g)
+    s = torch.randint(118, 127, (E * n // 32, k), dtype=torch.uint8, device="cuda", generator=g)
+    gs = torch.rand(E, device="cuda") + 0.5
+    qa = pk.quantize_activation_rows(torch.randn(m, k, device="cuda").to(torch.bfloat16), fmt)
+    h = pk.PetitSolutionHints()
+    h.a_type = h.c_type = torch.bfloat16
+    h.b_type = pk.DataType.mxfloat4_e2m1
+    sid = pk.native_moe_resolve_solution(h, E, m, n, k, {"mxfp8": -2, "mxfp4": -3, "mxfp6": -4}[fmt], a_format=fmt)
+    offs = []
+    for e in range(16):
+        o = torch.zeros(E + 1, dtype=torch.int32)
+        o[e * 7 + 1:] = m
+        offs.append((e * 7, o.to("cuda")))
+
+    def moe(i):
+        pk.mul_mxfp4_native_moe(qa, w, s, gs, offs[i % 16][1], m, n, k, E, solution_id=sid)
+
+    def dense(i):
+        e = offs[i % 16][0]
+        b = w.view(-1)[e * n * k // 8:(e + 1) * n * k // 8].view(n // 16, 2 * k)
+        se = s.view(-1)[e * n * k // 32:(e + 1) * n * k // 32].view(n // 32, k)
+        pk.mul_mxfp4_native(qa, b, se, gs[e:e + 1], m, n, k, sid)
+
+    mu, du = time_us(moe, iters), time_us(dense, iters)
+    return {"m": m, "n": n, "k": k, "E": E, "activations": fmt, "solution": pk.ops._lib.describe_solution(sid), "moe_us": mu, "dense_us": du,
+            "moe_over_dense": mu / du}
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--cells", default="all", choices=["decode", "prefill", "all"])
@@ -233,11 +310,17 @@ def main():
     ap.add_argument("--single-expert", action="store_true")
     ap.add_argument("--layer", action="store_true")
     ap.add_argument("--t", default="", help="--layer: comma-separated token counts (default 1,4,16,64,1024,4096)")
+    ap.add_argument("--native", default="", choices=["", "mxfp8", "mxfp6", "mxfp4"],
+                    help="--layer: fp4_moe_native with these activations against fp4_moe_fused (MXFP4 raw and NVFP4 images), plus the single-expert cell")
     ap.add_argument("--out", default="")
     args = ap.parse_args()
     import petit_kernel as pk
     report = {"device": torch.cuda.get_device_properties(0).gcnArchName, "cells": []}
-    if args.layer:
+    if args.layer and args.native:
+        ts = tuple(int(t) for t in args.t.split(",")) if args.t else NATIVE_LAYER_T
+        report["native_layer"] = native_layer_cells(pk, args.models.split(","), ts, args.iters, args.native)
+        report["native_single_expert"] = native_single_expert(pk, args.iters, args.native)
+    elif args.layer:
         ts = tuple(int(t) for t in args.t.split(",")) if args.t else LAYER_T
         report["layer"] = layer_cells(pk, args.models.split(","), ts, args.iters)
     elif args.single_expert:
