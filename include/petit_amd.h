@@ -162,27 +162,30 @@ int petit_gemm_get_solutions(const petit_solution_hints *hints, unsigned m,
  *   replaces fp4::ChooseDefaultFp4Fp16Solution  fp4/algo_chooser.cc:64-132 */
 uint64_t petit_gemm_default_solution(const petit_solution_hints *hints,
                                      unsigned m, unsigned n, unsigned k);
-/* The concrete id a call (hints, m, n, k, solution_id, epilogue) that hands over `workspace_bytes` of scratch would RUN:
- * solution_id may be PETIT_SOLUTION_AUTO, one of the PETIT_SOLUTION_AUTO_NATIVE_* sentinels, or an explicit id (returned
- * normalised, or 0 when that call would be refused).  petit_gemm_default_solution() answers for "as much scratch as the pick
- * wants" (what the Python layers provide): possibly an id with a K split (bits 60-63 > 1), which a caller WITHOUT scratch
- * cannot run -- such a caller (petit_gemm_fp4_fp16_grid / _ex with no registered workspace) gets the kernel this function
- * names for workspace_bytes = 0.  epilogue may be NULL. */
+/* The concrete id a call (hints, m, n, k, solution_id, epilogue) that hands over `workspace_bytes` of scratch would RUN, read
+ * from the launcher's own plan: solution_id may be PETIT_SOLUTION_AUTO, one of the PETIT_SOLUTION_AUTO_NATIVE_* sentinels, or an
+ * explicit id (returned normalised), and 0 means that call would be refused.  petit_gemm_default_solution() answers for "as much
+ * scratch as the pick wants" (what the Python layers provide): possibly an id with a K split (bits 60-63 > 1), which a caller
+ * WITHOUT scratch cannot run -- such a caller (petit_gemm_fp4_fp16_grid / _ex with no registered workspace) gets the kernel this
+ * function names for workspace_bytes = 0.  A call that runs as bulk + tail (petit_gemm_row_split): the kernel of the problem as a
+ * whole -- resolve (rows) and (m - rows) for the two launches.  epilogue may be NULL. */
 uint64_t petit_gemm_resolve_solution(const petit_solution_hints *hints, unsigned m, unsigned n, unsigned k, uint64_t solution_id,
                                      const petit_epilogue *epilogue, uint64_t workspace_bytes);
-/* Rows are independent, so a default-pick call (PETIT_SOLUTION_AUTO, exact class) at a prefill M whose tile grid ends a little past a
- * whole number of rounds of the chip runs as TWO launches on the caller's stream: the first `rows` rows with the kernel picked for them
- * (a grid of whole rounds), the remaining m - rows rows as a default-pick problem of their own (petit-kernel_amd/csrc/pick.hip
- * plan_row_split; petit_gemm_workspace_bytes covers both).  Returns `rows`, or 0 when the call runs as one launch (always for explicit
- * ids, the native class, m <= 512, $PETIT_AMD_NO_ROW_SPLIT=1).  petit_gemm_default_solution / _resolve_solution name the kernel of
- * the problem as a whole; resolve them at (rows) and (m - rows) for the two launches.  No reference counterpart: the reference's
- * 234-kernel chooser (fp4/algo_chooser.cc:64-132) takes the grid as it comes. */
+/* Rows are independent, so a default-pick call (PETIT_SOLUTION_AUTO) at a prefill M whose tile grid ends a little past a whole number
+ * of rounds of the chip runs as TWO launches on the caller's stream: the first `rows` rows with the kernel picked for them (a grid of
+ * whole rounds), the remaining m - rows rows as a default-pick problem of their own (petit-kernel_amd/csrc/pick.hip plan_row_split;
+ * petit_gemm_workspace_bytes covers both).  When the process-wide MXFP4 default class is taken (petit_set_mxfp4_default_class), the
+ * split is that class's (petit_gemm_row_split).  Returns `rows` for a call that hands over as much scratch as petit_gemm_workspace_bytes
+ * asks for, or 0 when the call runs as one launch (always for explicit ids, m <= 512, $PETIT_AMD_NO_ROW_SPLIT=1).
+ * petit_gemm_default_solution / _resolve_solution name the kernel of the problem as a whole; resolve them at (rows) and (m - rows) for
+ * the two launches.  No reference counterpart: the reference's 234-kernel chooser (fp4/algo_chooser.cc:64-132) takes the grid as it comes. */
 unsigned petit_gemm_auto_row_split(const petit_solution_hints *hints, unsigned m, unsigned n, unsigned k, const petit_epilogue *epilogue);
 /* The same for any solution_id (round 6).  PETIT_SOLUTION_AUTO: as above.  A native-class sentinel: the rows the call runs IN THE CLASS when its grid of 128-row tiles
- * ends a little past a whole number of rounds -- the remaining few dozen rows (<= 128) then go through the EXACT default pick (a batched-decode kernel: the class has no
- * small-M kernel), i.e. they are computed exactly, never less accurately than the class promises; both parts share the call's scratch.  Only for calls that hand over 16-bit
- * activations and take a 16-bit result (no petit_native_args formats) and, for NVFP4 weights, through the entry point that has the packed tensors (the attached image).
- * 0 = one launch (always for explicit ids). */
+ * ends a little past a whole number of rounds -- the remaining few dozen rows (<= 128) then go through the default pick PETIT_SOLUTION_AUTO (a batched-decode kernel: the
+ * class has no small-M kernel), which computes them exactly unless the process-wide MXFP4 default class is set and the tail has $PETIT_AMD_NATIVE_MIN_M (64) rows or more;
+ * both parts share the call's scratch (petit_gemm_workspace_bytes_ex / petit_gemm_native_workspace_bytes cover both).  Only for calls that hand over 16-bit activations and
+ * take a 16-bit result (no petit_native_args formats) and, for NVFP4 weights, through the entry point that has the packed tensors (the attached image).  0 = one launch
+ * (always for explicit ids). */
 unsigned petit_gemm_row_split(const petit_solution_hints *hints, unsigned m, unsigned n, unsigned k, uint64_t solution_id, const petit_epilogue *epilogue);
 /* A test aid: the C tile (n-tile column *bn, m-tile row *bm) that workgroup `block` (= blockIdx.y * gridDim.x + blockIdx.x) of an nx x ny grid of the
  * large-M kernels computes under the XCD-aware raster with bands of `band` m-tiles (0 = whole columns) -- the very function the kernels call
@@ -289,7 +292,9 @@ int petit_gemm_mxfp4_fp16_grid_ws(unsigned *c, const unsigned *a, const unsigned
                                   const petit_solution_hints *hints, uint64_t solution_id,
                                   const petit_epilogue *epilogue, void *workspace, uint64_t workspace_bytes, void *stream);
 /* Bytes of scratch the call (hints, m, n, k, solution_id) uses when it is given enough; solution_id may be
- * PETIT_SOLUTION_AUTO (the arch table may name a K-split kernel for the shape).  0: none needed. */
+ * PETIT_SOLUTION_AUTO (the arch table may name a K-split kernel for the shape).  A call that runs as bulk + tail
+ * (petit_gemm_row_split): the larger part's, and no less than the process-wide default class was taken for.  0: none
+ * needed, or the call would be refused (an NVFP4 native-class call is taken to have its image attached). */
 uint64_t petit_gemm_workspace_bytes(const petit_solution_hints *hints, unsigned m, unsigned n, unsigned k,
                                     uint64_t solution_id);
 /* The same with the epilogue of the call taken into account: PETIT_SOLUTION_AUTO resolves differently under
@@ -353,7 +358,8 @@ int petit_get_mxfp4_default_class(void);
  * solution_id: PETIT_SOLUTION_AUTO_NATIVE_MXFP8 / _MXFP6 / _MXFP4 (must match a_format when given) or an explicit native kernel id;
  * with a_format or out_format set only the 32x32x64 kernels qualify (PETIT_ERROR_KERNEL_SHAPE otherwise).  hints->a_type
  * names the 16-bit type of the matrix input / output and of the bias.  workspace: what petit_gemm_native_workspace_bytes()
- * says for the same arguments (with a_format set: only the slabs of a K split; often 0).
+ * says for the same arguments (with a_format set: only the slabs of a K split; often 0; a call that runs as bulk + tail,
+ * petit_gemm_row_split: the larger part's; 0 also when the call would be refused).
  */
 typedef struct petit_native_args {
     uint32_t struct_bytes; /* sizeof(petit_native_args) */

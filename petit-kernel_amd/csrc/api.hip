@@ -1,4 +1,4 @@
-// api.hip -- the C ABI of include/petit_amd.h: argument checks and forwarding; the work is in dispatch.hip (gemm_impl), pick.hip (default picks),
+// api.hip -- the C ABI of include/petit_amd.h: argument checks and forwarding; the work is in dispatch.hip (plan_gemm / gemm_impl), pick.hip (default picks),
 // solutions.hip (ids), repack.hip / nvnative.hip / tune.hip.
 //
 // Replaces (reference paths under lib/gemm/rocm/quantization/):
@@ -66,44 +66,19 @@ int petit_gemm_mxfp4_fp16_grid_ws(unsigned *c, const unsigned *a, const unsigned
                      workspace_bytes, stream);
 }
 
-// what a call with this epilogue would resolve PETIT_SOLUTION_AUTO to (the SiLU-mul epilogue restricts the candidates)
-static bool epilogue_act(const petit_epilogue *epilogue, bool *ok) {
-    *ok = !epilogue || ((epilogue->activation == PETIT_ACTIVATION_NONE || epilogue->activation == PETIT_ACTIVATION_SILU_MUL) &&
-                        epilogue->reserved == 0);
-    return epilogue && epilogue->activation == PETIT_ACTIVATION_SILU_MUL;
+// The queries read the launcher's plan (dispatch.hip plan_gemm) of a call that hands over `ws_bytes` of scratch.  They have no matrices: an NVFP4
+// native-class call is taken to have its image.
+static GemmPlan plan_query(const petit_solution_hints *hints, unsigned m, unsigned n, unsigned k, uint64_t solution_id, const petit_epilogue *epilogue,
+                           uint64_t ws_bytes, const NativeIo *io = nullptr) {
+    const GemmCall g{hints ? canonical_b_type(hints->b_type) : 0, nullptr, nullptr, nullptr, nullptr, nullptr, m, n, k, hints, solution_id, epilogue,
+                     nullptr, io};
+    return plan_gemm(g, Scratch{Scratch::kQuery, nullptr, ws_bytes});
 }
 
 uint64_t petit_gemm_workspace_bytes_ex(const petit_solution_hints *hints, unsigned m, unsigned n, unsigned k,
                                        uint64_t solution_id, const petit_epilogue *epilogue) {
-    Family fam;
-    bool ok;
-    const bool act = epilogue_act(epilogue, &ok);
-    if (!ok || !hints)
-        return 0;
-    const petit_solution_hints eff = effective_hints(hints);
-    hints = &eff;
-    if (hints->c_type != hints->a_type || !family_for(hints->a_type, hints->b_type, &fam) || !shape_ok(n, k) || !problem_in_range(m, n, k))
-        return 0;
-    if (is_auto_id(solution_id)) {
-        int klass = auto_class(solution_id);
-        if (const int dflt = auto_default_class(solution_id, hints->b_type, m)) // (the process-wide default class: size the scratch it needs)
-            klass = dflt;
-        const int dev = current_device();
-        const AutoChoice ch = choose_auto(fam, dev, hints->a_type, hints->b_type, act, m, n, k, klass);
-        if (!ch.entry)
-            return 0;
-        if (klass == kClassExact && !autotune_enabled()) {
-            if (const unsigned m1 = plan_row_split(*ch.entry, ch.splitk, m, n, k, arch_info(dev).num_cus)) { // bulk + tail share the scratch
-                const AutoChoice c1 = choose_auto(fam, dev, hints->a_type, hints->b_type, act, m1, n, k, klass);
-                const AutoChoice c2 = choose_auto(fam, dev, hints->a_type, hints->b_type, act, m - m1, n, k, klass);
-                return std::max(c1.entry ? workspace_need(*c1.entry, c1.splitk, m1, n, k) : 0, c2.entry ? workspace_need(*c2.entry, c2.splitk, m - m1, n, k) : 0);
-            }
-        }
-        return workspace_need(*ch.entry, ch.splitk, m, n, k);
-    }
-    const SolutionEntry *e = find_explicit(fam, solution_id);
-    const unsigned splitk = solution_splitk(solution_id);
-    return e && splitk ? workspace_need(*e, splitk, m, n, k) : 0;
+    const GemmPlan p = plan_query(hints, m, n, k, solution_id, epilogue, UINT64_MAX);
+    return p.rc == kOk ? p.need : 0;
 }
 
 static bool native_args_ok(const petit_native_args *na) {
@@ -111,13 +86,16 @@ static bool native_args_ok(const petit_native_args *na) {
                    (na->a_format == 0 || na->a_format == 8 || na->a_format == 6 || na->a_format == 4) &&
                    (na->out_format == 0 || na->out_format == 8 || na->out_format == 6 || na->out_format == 4));
 }
+static NativeIo native_io(const petit_native_args *na, const void *image = nullptr) {
+    return NativeIo{na ? (unsigned)na->a_format : 0u, na ? (unsigned)na->out_format : 0u, image};
+}
 
 int petit_gemm_mxfp4_native(void *c, const void *a, const unsigned *b, const unsigned *scales, const float *global_scale, unsigned m,
                             unsigned n, unsigned k, const petit_solution_hints *hints, uint64_t solution_id, const petit_epilogue *epilogue,
                             const petit_native_args *native, void *workspace, uint64_t workspace_bytes, void *stream) {
     if (!native_args_ok(native))
         return kErrBadArgument;
-    const NativeIo io{native ? (unsigned)native->a_format : 0u, native ? (unsigned)native->out_format : 0u};
+    const NativeIo io = native_io(native);
     if (solution_id == PETIT_SOLUTION_AUTO)
         return kErrKernelShape; // this entry point is the native class's: name a sentinel or a native kernel id
     return gemm_impl(kDataTypeMxFp4e2m1, (unsigned *)c, (const unsigned *)a, b, scales, global_scale, m, n, k, hints, solution_id, epilogue,
@@ -126,24 +104,12 @@ int petit_gemm_mxfp4_native(void *c, const void *a, const unsigned *b, const uns
 
 uint64_t petit_gemm_native_workspace_bytes(const petit_solution_hints *hints, unsigned m, unsigned n, unsigned k, uint64_t solution_id,
                                            const petit_epilogue *epilogue, const petit_native_args *native) {
-    Family fam;
-    bool ok;
-    const bool act = epilogue_act(epilogue, &ok);
-    if (!ok || !native_args_ok(native) || !hints || hints->c_type != hints->a_type || (hints->b_type != kDataTypeMxFp4e2m1 && hints->b_type != kDataTypeFp4e2m1) ||
-        !family_for(hints->a_type, hints->b_type, &fam) || !shape_ok(n, k) || m == 0 || solution_id == PETIT_SOLUTION_AUTO)
+    // (hints->b_type names the entry point: petit_gemm_mxfp4_native, or petit_gemm_nvfp4_native, whose image comes per call; both refuse PETIT_SOLUTION_AUTO)
+    if (!native_args_ok(native) || !hints || (hints->b_type != kDataTypeMxFp4e2m1 && hints->b_type != kDataTypeFp4e2m1) || solution_id == PETIT_SOLUTION_AUTO)
         return 0;
-    const unsigned a_format = native ? (unsigned)native->a_format : 0u, out_format = native ? (unsigned)native->out_format : 0u;
-    const unsigned restrict_ = (a_format ? kNeedK32 : 0u) | (out_format ? kNeedQuantOut : 0u);
-    const SolutionEntry *e = nullptr;
-    unsigned splitk = 1;
-    if (is_auto_id(solution_id)) {
-        const AutoChoice ch = choose_auto(fam, current_device(), hints->a_type, hints->b_type, act, m, n, k, auto_class(solution_id), restrict_);
-        e = ch.entry, splitk = ch.splitk;
-    } else {
-        e = find_explicit(fam, solution_id);
-        splitk = solution_splitk(solution_id);
-    }
-    return e && splitk ? workspace_need(*e, splitk, m, n, k, a_format != 0) : 0;
+    const NativeIo io = native_io(native, hints->b_type == kDataTypeFp4e2m1 ? query_image() : nullptr);
+    const GemmPlan p = plan_query(hints, m, n, k, solution_id, epilogue, UINT64_MAX, &io);
+    return p.rc == kOk ? p.need : 0;
 }
 
 uint64_t petit_nvfp4_native_image_bytes(unsigned in_chan, unsigned out_chan) {
@@ -176,7 +142,7 @@ int petit_gemm_nvfp4_native(void *c, const void *a, const void *image, const flo
                             const petit_native_args *native, void *workspace, uint64_t workspace_bytes, void *stream) {
     if (!native_args_ok(native) || ((uintptr_t)image & 255))
         return kErrBadArgument;
-    const NativeIo io{native ? (unsigned)native->a_format : 0u, native ? (unsigned)native->out_format : 0u, image};
+    const NativeIo io = native_io(native, image);
     if (solution_id == PETIT_SOLUTION_AUTO)
         return kErrKernelShape; // this entry point is the native class's: name a sentinel or a native kernel id
     // (b / scales: the image stands in for both -- gemm_impl reads neither once it has the image)
@@ -279,49 +245,11 @@ int petit_gemm_get_solutions(const petit_solution_hints *hints, unsigned m, unsi
 
 uint64_t petit_gemm_resolve_solution(const petit_solution_hints *hints, unsigned m, unsigned n, unsigned k, uint64_t solution_id,
                                      const petit_epilogue *epilogue, uint64_t workspace_bytes) {
+    const GemmPlan p = plan_query(hints, m, n, k, solution_id, epilogue, workspace_bytes);
     Family fam;
-    bool ok;
-    const bool act = epilogue_act(epilogue, &ok);
-    if (!ok || !hints)
+    if (p.rc != kOk || !p.entry || !family_for(hints->a_type, canonical_b_type(hints->b_type), &fam))
         return 0;
-    const petit_solution_hints eff = effective_hints(hints);
-    hints = &eff;
-    if (hints->c_type != hints->a_type || !family_for(hints->a_type, hints->b_type, &fam) || !shape_ok(n, k) || !problem_in_range(m, n, k))
-        return 0;
-    if (act && (n % 32 != 0 || (uint64_t)n * k / 2 >= (1ull << 32)))
-        return 0; // (gemm_impl: SiLU-mul needs gate / up halves of whole n-tiles inside one descriptor)
-    if (!is_auto_id(solution_id)) {
-        const SolutionEntry *e = find_explicit(fam, solution_id);
-        const unsigned sk = solution_splitk(solution_id);
-        if (!e || !sk || !entry_fits(*e, m, k) || (act && !act_runs(*e, sk)) || workspace_need(*e, sk, m, n, k) > workspace_bytes)
-            return 0;
-        return make_solution_id(e->shape, fam.elem_b, entry_mfma(fam, *e), sk);
-    }
-    int klass = auto_class(solution_id);
-    if (klass != kClassExact && ((uint64_t)m * k >= (1ull << 32) || m > 65535u))
-        return 0; // (the native class's descriptor range: gemm_impl refuses the same)
-    if (const int dflt = auto_default_class(solution_id, hints->b_type, m)) { // the process-wide default class, when `workspace_bytes` covers its pick (gemm_impl)
-        const AutoChoice chn = choose_auto(fam, current_device(), hints->a_type, hints->b_type, act, m, n, k, dflt);
-        if (chn.entry && workspace_need(*chn.entry, chn.splitk, m, n, k) <= workspace_bytes)
-            klass = dflt;
-    }
-    AutoChoice ch = choose_auto(fam, current_device(), hints->a_type, hints->b_type, act, m, n, k, klass);
-    if (ch.entry && workspace_need(*ch.entry, ch.splitk, m, n, k) > workspace_bytes) {
-        // exactly what gemm_impl does when the caller's scratch does not cover the pick
-        if (klass == kClassExact) {
-            ch.entry = heuristic(fam, m, n, k, act), ch.splitk = 1;
-        } else {
-            if (act && !act_ok(*ch.entry)) { // (unsplit, SiLU-mul is the kernel's own epilogue's: gemm_impl re-picks the same way)
-                unsigned sk1 = 1;
-                ch.entry = heuristic_native(fam, klass, m, n, k, true, /*have_slabs=*/false, &sk1);
-            }
-            if (ch.entry && workspace_need(*ch.entry, 1, m, n, k) <= workspace_bytes)
-                ch.splitk = 1;
-            else
-                ch.entry = nullptr;
-        }
-    }
-    return ch.entry ? make_solution_id(ch.entry->shape, fam.elem_b, entry_mfma(fam, *ch.entry), ch.splitk) : 0;
+    return make_solution_id(p.entry->shape, fam.elem_b, entry_mfma(fam, *p.entry), p.splitk);
 }
 
 uint64_t petit_gemm_default_solution(const petit_solution_hints *hints, unsigned m, unsigned n, unsigned k) {
@@ -339,36 +267,11 @@ void petit_raster_tile(unsigned nx, unsigned ny, unsigned band, unsigned block, 
 }
 
 unsigned petit_gemm_row_split(const petit_solution_hints *hints, unsigned m, unsigned n, unsigned k, uint64_t solution_id, const petit_epilogue *epilogue) {
-    if (solution_id == PETIT_SOLUTION_AUTO)
-        return petit_gemm_auto_row_split(hints, m, n, k, epilogue);
-    Family fam;
-    bool ok;
-    const bool act = epilogue_act(epilogue, &ok);
-    const int klass = auto_class(solution_id);
-    if (!ok || !hints || klass == kClassExact)
-        return 0; // (explicit ids run as named)
-    const petit_solution_hints eff = effective_hints(hints);
-    if (eff.c_type != eff.a_type || !family_for(eff.a_type, eff.b_type, &fam) || !shape_ok(n, k) || !problem_in_range(m, n, k) || autotune_enabled() ||
-        (uint64_t)m * k >= (1ull << 32) || m > 65535u)
-        return 0;
-    const int dev = current_device();
-    const AutoChoice ch = choose_auto(fam, dev, eff.a_type, eff.b_type, act, m, n, k, klass);
-    return ch.entry ? plan_row_split_native(*ch.entry, klass, ch.splitk, m, n, k, arch_info(dev).num_cus) : 0;
+    return plan_query(hints, m, n, k, solution_id, epilogue, UINT64_MAX).bulk_rows;
 }
 
 unsigned petit_gemm_auto_row_split(const petit_solution_hints *hints, unsigned m, unsigned n, unsigned k, const petit_epilogue *epilogue) {
-    Family fam;
-    bool ok;
-    const bool act = epilogue_act(epilogue, &ok);
-    if (!ok || !hints)
-        return 0;
-    const petit_solution_hints eff = effective_hints(hints);
-    if (eff.c_type != eff.a_type || !family_for(eff.a_type, eff.b_type, &fam) || !shape_ok(n, k) || m == 0 || m > kMaxM || autotune_enabled() ||
-        auto_default_class(PETIT_SOLUTION_AUTO, eff.b_type, m))
-        return 0;
-    const int dev = current_device();
-    const AutoChoice ch = choose_auto(fam, dev, eff.a_type, eff.b_type, act, m, n, k, kClassExact);
-    return ch.entry ? plan_row_split(*ch.entry, ch.splitk, m, n, k, arch_info(dev).num_cus) : 0;
+    return petit_gemm_row_split(hints, m, n, k, PETIT_SOLUTION_AUTO, epilogue);
 }
 
 int petit_repack_nvfp4_weights(unsigned *output, const unsigned *input, unsigned in_chan, unsigned out_chan,

@@ -2,7 +2,7 @@
 //   solutions.hip  the family tables, ids <-> table entries, what an entry can run
 //   cost.hip       the cost model and the formula heuristic behind the arch tables
 //   pick.hip       what PETIT_SOLUTION_AUTO (and the native-class sentinels) resolve to: arch table, neighbours, row split
-//   dispatch.hip   scratch memory, the tuner's candidate list, gemm_impl -- the dispatcher behind every GEMM entry point
+//   dispatch.hip   scratch memory, the tuner's candidate list, plan_gemm (what a dense call runs) and gemm_impl (which launches the plan)
 //   api.hip        the C ABI of include/petit_amd.h;  describe.hip: petit_describe_solution / error strings
 // Not installed; the public surface is include/petit_amd.h.
 #pragma once
@@ -97,5 +97,42 @@ void *registered_workspace(int dev, void *stream, uint64_t need, bool *busy);
 // the MFMA-native images attached to packed NVFP4 weight pointers (petit_nvfp4_native_attach)
 int attach_image(const void *b, const void *image);
 const void *attached_image(const void *b);
+
+// A dense call is planned, then launched (gemm_impl); the C-ABI queries read the same plan.
+struct GemmCall { // the arguments of gemm_impl but the scratch (a query has no matrices: null pointers)
+    int b_type;
+    unsigned *c;
+    const unsigned *a, *b, *scales;
+    const float *global_scale;
+    unsigned m, n, k;
+    const petit_solution_hints *hints;
+    uint64_t solution_id;
+    const petit_epilogue *epilogue;
+    void *stream;
+    const NativeIo *io;
+};
+struct Scratch { // the scratch a call can use
+    enum Kind { kCallBuffer, kRegistered, kQuery } kind;
+    void *ptr;      // kCallBuffer: the call's own buffer (kRegistered: the workspace registered for the device, looked up per need)
+    uint64_t bytes; // kCallBuffer, kQuery: its size (a query has no pointer)
+};
+struct LaunchPlan {
+    int rc = kOk;                         // a refusal, or kOk -- with entry == nullptr: nothing to launch (m, n or k = 0)
+    int klass = kClassExact;              // the accuracy class
+    const SolutionEntry *entry = nullptr; // kernel and K split, after the scratch fallbacks
+    unsigned splitk = 1;
+    const void *nv_image = nullptr;       // NVFP4 weights on a native kernel: the MFMA-native image it reads
+    uint64_t need = 0;                    // scratch bytes, and the scratch (nullptr for a query)
+    void *ws = nullptr;
+    bool act = false, reduce_act = false; // SiLU-mul in the kernel's epilogue / in the reduce pass of a K split
+};
+struct GemmPlan : LaunchPlan {
+    unsigned bulk_rows = 0; // 0: one launch.  Else bulk + tail: the row where the tail starts, and the plans of both parts (then entry / splitk name the whole
+    LaunchPlan bulk, tail;  // problem's kernel; need is the larger part's, and at least what the default class was taken for)
+    bool tune = false;      // $PETIT_AMD_AUTOTUNE=1 and a default pick no table knows: the launcher tunes it, then plans again
+};
+// `part`: one part of a bulk + tail call, never split again
+GemmPlan plan_gemm(const GemmCall &g, const Scratch &s, bool part = false);
+const void *query_image(); // what a query takes for the image of an NVFP4 native-class call (it has no `b`)
 
 } // namespace petit_amd

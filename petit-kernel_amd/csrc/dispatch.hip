@@ -1,4 +1,4 @@
-// dispatch.hip -- the dispatcher behind every GEMM entry point (gemm_impl), the scratch-memory rules and the tuner's candidate list.
+// dispatch.hip -- the dispatcher behind every GEMM entry point (plan_gemm decides, gemm_impl launches the plan), the scratch-memory rules and the tuner's candidate list.
 // Replaces fp4/gemm_fp4_fp16_grid.cc:11-77 (Dispatcher, GemmFp4Fp16GridImpl), which has no scratch, no launch-error check and no fused epilogue.
 #include <hip/hip_runtime.h>
 
@@ -157,257 +157,285 @@ int tune_candidates(int a_type, int b_type, int klass, unsigned m, unsigned n, u
     return count;
 }
 
-// bulk + tail planning (gemm_impl): a dry run walks a call down to its launch -- kernel, split and scratch resolved, every refusal reported -- and stops there
-static thread_local bool tl_in_row_split = false, tl_dry_run = false;
+const void *query_image() {
+    static const char marker = 0; // (never read)
+    return &marker;
+}
+
+// the native pipeline's restrictions of a call (pre-quantised activations / quantised SiLU-mul output: 32x32x64 kernels only)
+static unsigned native_restrictions(const NativeIo *io) {
+    return (io && io->a_format ? kNeedK32 : 0u) | (io && io->out_format ? kNeedQuantOut : 0u);
+}
+
+// rows [row0, row0 + rows) of a call as a call of their own; `auto_tail`: as PETIT_SOLUTION_AUTO with no NativeIo (the tail of the native class's bulk + tail)
+static GemmCall rows_of(const GemmCall &g, unsigned row0, unsigned rows, bool auto_tail) {
+    GemmCall r = g;
+    r.m = rows;
+    if (g.c) { // (a query has no matrices)
+        const bool act = g.epilogue && g.epilogue->activation == PETIT_ACTIVATION_SILU_MUL;
+        r.c = (unsigned *)((char *)g.c + (size_t)row0 * (act ? g.n / 2 : g.n) * sizeof(uint16_t));
+        r.a = (const unsigned *)((const char *)g.a + (size_t)row0 * g.k * sizeof(uint16_t));
+    }
+    if (auto_tail)
+        r.solution_id = PETIT_SOLUTION_AUTO, r.io = nullptr;
+    return r;
+}
+
+// Every check and decision of a dense call, in the order they are made, and no launch: argument and range checks, the accuracy class, the NVFP4 image, the
+// pick, the bulk + tail row split, the scratch fallbacks.  It keeps no state between calls; the registered workspace is looked up where the launcher needs
+// it, which binds it to the call's stream.
+GemmPlan plan_gemm(const GemmCall &g, const Scratch &s, bool part) {
+    GemmPlan p;
+    const auto refuse = [&p](int rc) { return p.rc = rc, p; };
+    const petit_epilogue *epilogue = g.epilogue;
+    const NativeIo *io = g.io;
+    const petit_solution_hints *hints = g.hints;
+    const unsigned m = g.m, n = g.n, k = g.k;
+    if (epilogue && ((epilogue->activation != PETIT_ACTIVATION_NONE && epilogue->activation != PETIT_ACTIVATION_SILU_MUL) ||
+                     epilogue->reserved != 0))
+        return refuse(kErrBadArgument); // reject what a newer caller might ask for
+    const bool act = epilogue && epilogue->activation == PETIT_ACTIVATION_SILU_MUL;
+    const unsigned a_format = io ? io->a_format : 0u, out_format = io ? io->out_format : 0u;
+    if ((a_format != 0 && a_format != 8 && a_format != 6 && a_format != 4) || (out_format != 0 && out_format != 8 && out_format != 6 && out_format != 4))
+        return refuse(kErrBadArgument);
+    if (m == 0 || n == 0 || k == 0)
+        return p; // gemm_fp4_fp16_grid.cc:42-44
+    if (!hints)
+        return refuse(kErrBadArgument);
+    if (hints->c_type != hints->a_type)
+        return refuse(kErrKernelShape);
+    Family fam;
+    if (!family_for(hints->a_type, g.b_type, &fam))
+        return refuse(kErrKernelShape);
+    if (!shape_ok(n, k))
+        return refuse(kErrProblemShape);
+    // SiLU-mul: gate / up halves made of whole n-tiles, and one descriptor spans half the matrix
+    if (act && (n % 32 != 0 || (uint64_t)n * k / 2 >= (1ull << 32)))
+        return refuse(kErrProblemShape);
+    // 32-bit buffer offsets inside one n-tile row / activation block
+    if ((uint64_t)k * 16 * 4 * 2 >= (1ull << 31) || (uint64_t)k * 64 * 4 >= (1ull << 31))
+        return refuse(kErrProblemShape);
+    // M: every kernel addresses A and C per workgroup (64-bit base + a 32-bit offset inside at most 256 rows), so the exact kernels take any M
+    // up to the tables' last bucket (prefill chunks of 16375 x 57344 included); beyond it, refuse rather than wrap a grid dimension
+    if (m > kMaxM)
+        return refuse(kErrProblemShape);
+    // the native pipeline: pre-quantised activations / quantised SiLU-mul output (MXFP4 weights, 32x32x64 kernels only)
+    const unsigned restrict_ = native_restrictions(io);
+    if (out_format && !act)
+        return refuse(kErrBadArgument); // (the quantised output is the SiLU-mul epilogue's)
+    if (out_format && (n % 512 != 0 || ((uintptr_t)g.c & 15)))
+        return refuse(kErrProblemShape); // the consumer's K = n / 2 must be a whole number of 256-column producer tiles
+    if (a_format && ((uintptr_t)g.a & 15))
+        return refuse(kErrBadArgument);
+
+    const int dev = current_device();
+    // scratch of `need` bytes: the call's own buffer (a query's byte count) when large enough, else the registered workspace when it is and serves this
+    // stream (busy: it is bound to another)
+    bool busy = false;
+    const auto take = [&](uint64_t need, void **ws) {
+        void *const ptr = s.kind == Scratch::kRegistered ? registered_workspace(dev, g.stream, need, &busy) : s.bytes >= need ? s.ptr : nullptr;
+        if (ws)
+            *ws = ptr;
+        return s.kind == Scratch::kRegistered ? ptr != nullptr : s.bytes >= need;
+    };
+    const auto attached = [&] { return s.kind == Scratch::kQuery ? query_image() : attached_image(g.b); };
+    const bool is_auto = is_auto_id(g.solution_id);
+    int klass = auto_class(g.solution_id);
+    uint64_t need_class = 0;
+    if (const int dflt = (restrict_ == 0) ? auto_default_class(g.solution_id, g.b_type, m) : kClassExact) {
+        // the process-wide default class: taken when the scratch of this call (its own, else the registered one) covers the class's pick
+        const AutoChoice chn = choose_auto(fam, dev, hints->a_type, g.b_type, act, m, n, k, dflt, 0);
+        const uint64_t need_n = chn.entry ? workspace_need(*chn.entry, chn.splitk, m, n, k) : 0;
+        if (chn.entry && take(need_n, nullptr))
+            klass = dflt, need_class = need_n;
+    }
+    p.klass = klass;
+    // NVFP4 weights: the native class runs on the weights' MFMA-native image (e4m3 group scales are not E8M0 block scales: nvnative.hip), handed
+    // over by petit_gemm_nvfp4_native or attached to `b` beforehand; without one the call is refused, never served by another accuracy class
+    const void *nv_image = g.b_type != kDataTypeFp4e2m1 ? nullptr : (io && io->image) ? io->image : klass != kClassExact ? attached() : nullptr;
+    if (klass != kClassExact && g.b_type == kDataTypeFp4e2m1 && !nv_image)
+        return refuse(kErrKernelShape);
+    // the native kernels read the quantised activations (k-tile major, up to m * k bytes) through ONE 32-bit buffer descriptor, and the
+    // quantiser's grid has one row per activation row
+    if ((klass != kClassExact || a_format) && ((uint64_t)m * k >= (1ull << 32) || m > 65535u))
+        return refuse(kErrProblemShape);
+    if (restrict_ && is_auto && klass == kClassExact)
+        return refuse(kErrKernelShape); // quantised I/O is the native class's: name it (a sentinel or an explicit native id)
+    if (a_format && klass != kClassExact && (unsigned)klass != a_format)
+        return refuse(kErrKernelShape); // activations quantised to one format, kernel class of the other
+    const SolutionEntry *entry = nullptr;
+    unsigned splitk = 1;
+    if (is_auto) {
+        p.tune = klass == kClassExact && !act && autotune_enabled() && tuned_solution(dev, hints->a_type, g.b_type, m, n, k, kClassExact) == 0;
+        const AutoChoice ch = choose_auto(fam, dev, hints->a_type, g.b_type, act, m, n, k, klass, restrict_);
+        entry = ch.entry, splitk = ch.splitk;
+        if (!entry)
+            return refuse(kErrKernelShape);
+        // bulk + tail: two default-pick launches on row ranges of A and C, same stream, same scratch (the launches are ordered) -- in the exact class
+        // (plan_row_split), or the native class at a ragged prefill M (plan_row_split_native): bulk in the class, the few dozen rows of the tail through the
+        // exact default.  (io == nullptr: the entry points that take petit_native_args refuse PETIT_SOLUTION_AUTO.)
+        unsigned m1 = 0;
+        if (!part && !autotune_enabled()) {
+            if (klass == kClassExact && !io)
+                m1 = plan_row_split(*entry, splitk, m, n, k, arch_info(dev).num_cus);
+            else if (klass != kClassExact && restrict_ == 0 && !(io && io->image))
+                m1 = plan_row_split_native(*entry, klass, splitk, m, n, k, arch_info(dev).num_cus);
+        }
+        if (m1) {
+            // BOTH parts are planned before either is launched: a tail that cannot run must not leave C half written or one launch in a stream capture
+            //  -- the call then runs as the single launch it would have been
+            p.bulk = plan_gemm(rows_of(g, 0, m1, false), s, true);
+            if (p.bulk.rc == kOk)
+                p.tail = plan_gemm(rows_of(g, m1, m - m1, klass != kClassExact), s, true);
+            if (p.bulk.rc == kOk && p.tail.rc == kOk) {
+                p.bulk_rows = m1;
+                p.entry = entry, p.splitk = splitk, p.need = std::max({need_class, p.bulk.need, p.tail.need});
+                return p;
+            }
+        }
+    } else {
+        entry = find_explicit(fam, g.solution_id);
+        if (!entry)
+            return refuse(kErrKernelShape);
+        if (!entry_fits(*entry, m, k))
+            return refuse(kErrProblemShape);
+        splitk = solution_splitk(g.solution_id);
+        if (splitk == 0)
+            return refuse(kErrKernelShape);
+        if (act && !act_runs(*entry, splitk, restrict_))
+            return refuse(kErrKernelShape); // unsplit: needs an even number of n-tiles per wave; split: a 16-bit output (the reduce pass applies SiLU-mul)
+        if (!entry_allows(*entry, restrict_) || (a_format && (unsigned)entry_class(*entry) != a_format))
+            return refuse(kErrKernelShape);
+    }
+
+    if (is_native_am(entry->shape.am) && ((uint64_t)m * k >= (1ull << 32) || m > 65535u))
+        return refuse(kErrProblemShape); // (an explicit native id: the same descriptor range as above)
+    if (is_native_am(entry->shape.am) && g.b_type == kDataTypeFp4e2m1) {
+        if (!nv_image)
+            nv_image = attached(); // (an explicit native id)
+        if (!nv_image)
+            return refuse(kErrKernelShape); // an explicit native id on NVFP4 weights that have no image attached
+        if (nv6_elem_bytes(n, k) >= (1ull << 32))
+            return refuse(kErrProblemShape); // (the image's element part is read through one 32-bit buffer descriptor)
+        p.nv_image = nv_image;
+    }
+
+    const bool have_qa = a_format != 0;
+    uint64_t need = workspace_need(*entry, splitk, m, n, k, have_qa);
+    void *ws = nullptr;
+    if (need) {
+        bool got = take(need, &ws);
+        if (!is_auto && (s.kind == Scratch::kRegistered ? busy : !got))
+            return refuse(kErrBadArgument); // too small for the kernel the caller named / the registered workspace is bound to another stream: pass one per call
+        if (!got && klass != kClassExact && is_auto && splitk > 1) {
+            // native default pick with a K split, scratch (per call or registered) covers the activations only, or they came quantised: the
+            // same kernel unsplit.  SiLU-mul rode on the reduce pass of the split (act_runs): unsplit it is the kernel's own epilogue's job, which
+            // needs gate and up tile in one wave (act_ok) -- a row like the 64 x 320 kernel (five n-tiles per wave) x split 4 cannot, and returned
+            // kOk with C unwritten: re-pick
+            if (act && !act_ok(*entry)) {
+                unsigned sk1 = 1;
+                const SolutionEntry *e1 = heuristic_native(fam, klass, m, n, k, true, /*have_slabs=*/false, &sk1, restrict_);
+                if (!e1)
+                    return refuse(kErrKernelShape);
+                entry = e1;
+            }
+            const uint64_t need1 = workspace_need(*entry, 1, m, n, k, have_qa);
+            if (!need1)
+                splitk = 1, need = 0;
+            else if (take(need1, &ws))
+                splitk = 1, need = need1, got = true;
+        }
+        if (!got && need) {
+            if (!is_auto || klass != kClassExact)
+                return refuse(kErrKernelShape); // explicit id (or the native class) that needs scratch nobody provided
+            // AUTO without scratch: the best kernel that needs none (not the K-split pick minus its split: a tiled kernel
+            // chosen FOR its split leaves most of the chip idle without it)
+            entry = heuristic(fam, m, n, k, act);
+            splitk = 1, need = 0;
+            if (!entry || workspace_need(*entry, 1, m, n, k))
+                return refuse(kErrKernelShape); // (unreachable: the heuristic never picks a native kernel)
+        }
+    }
+    p.entry = entry, p.splitk = splitk, p.need = need, p.ws = ws;
+    // SiLU-mul: in the kernel's epilogue unsplit; by the reduce pass over plain slabs with a cross-workgroup K split
+    p.act = act && splitk == 1;
+    p.reduce_act = act && splitk > 1;
+    return p;
+}
+
+// one planned launch
+static int launch(const GemmCall &g, const LaunchPlan &p) {
+    if (p.rc != kOk || !p.entry)
+        return p.rc;
+    const unsigned a_format = g.io ? g.io->a_format : 0u;
+    GemmArgs args{};
+    args.c = g.c, args.a = g.a, args.w = g.b, args.s = g.scales, args.gs = g.global_scale;
+    if (p.nv_image)
+        args.w = p.nv_image, args.s = (const char *)p.nv_image + nv6_elem_bytes(g.n, g.k);
+    args.m = g.m, args.n = g.n, args.k = g.k;
+    args.bias = g.epilogue ? g.epilogue->bias : nullptr;
+    args.qa = a_format ? (const void *)g.a : nullptr, args.qa_format = a_format, args.out_format = g.io ? g.io->out_format : 0u;
+    args.workspace = (float *)p.ws;
+    args.act = p.act ? 1u : 0u, args.reduce_act = p.reduce_act ? 1u : 0u;
+    const SolutionEntry *entry = p.entry;
+    int rc = entry->launch(args, p.splitk, (hipStream_t)g.stream);
+    if (rc == kErrSplitCollapsed) {
+        // K is too short for the split the id (or the table row) names: the kernel runs as one part, so SiLU-mul is its own epilogue's job
+        if (!act_ok(*entry)) {
+            if (!is_auto_id(g.solution_id))
+                return kErrKernelShape;
+            Family fam;
+            family_for(g.hints->a_type, g.b_type, &fam);
+            if (p.klass != kClassExact) { // native class: the class's best kernel whose own epilogue applies SiLU-mul, within the scratch at hand
+                unsigned sk1 = 1;
+                const SolutionEntry *e1 = heuristic_native(fam, p.klass, g.m, g.n, g.k, true, /*have_slabs=*/false, &sk1, native_restrictions(g.io));
+                if (!e1 || workspace_need(*e1, 1, g.m, g.n, g.k, a_format != 0) > workspace_need(*entry, p.splitk, g.m, g.n, g.k, a_format != 0))
+                    return kErrKernelShape;
+                entry = e1;
+            } else {
+                entry = heuristic(fam, g.m, g.n, g.k, true);
+                if (!entry || workspace_need(*entry, 1, g.m, g.n, g.k))
+                    return kErrKernelShape;
+            }
+        }
+        args.act = 1u, args.reduce_act = 0u;
+        rc = entry->launch(args, 1, (hipStream_t)g.stream);
+    }
+    return rc;
+}
 
 int gemm_impl(int b_type, unsigned *c, const unsigned *a, const unsigned *b, const unsigned *scales,
               const float *global_scale, unsigned m, unsigned n, unsigned k,
               const petit_solution_hints *hints, uint64_t solution_id, const petit_epilogue *epilogue,
               void *call_ws, uint64_t call_ws_bytes, void *stream, const NativeIo *io) {
-    if (epilogue && ((epilogue->activation != PETIT_ACTIVATION_NONE && epilogue->activation != PETIT_ACTIVATION_SILU_MUL) ||
-                     epilogue->reserved != 0))
-        return kErrBadArgument; // reject what a newer caller might ask for
-    const bool act = epilogue && epilogue->activation == PETIT_ACTIVATION_SILU_MUL;
-    const unsigned a_format = io ? io->a_format : 0u, out_format = io ? io->out_format : 0u;
-    if ((a_format != 0 && a_format != 8 && a_format != 6 && a_format != 4) || (out_format != 0 && out_format != 8 && out_format != 6 && out_format != 4))
+    // the matrices and the call's scratch, which queries have not (a call with m, n or k = 0 has nothing to do, whatever its pointers).  Scratch: f32x4
+    // slabs and 16-byte activation loads -- the contract is 256-byte alignment (petit_amd.h)
+    if (m && n && k && (!c || !a || !b || !scales || !global_scale || (!call_ws && call_ws_bytes) || ((uintptr_t)call_ws & (kWorkspaceAlign - 1))))
         return kErrBadArgument;
-    if (m == 0 || n == 0 || k == 0)
-        return kOk; // gemm_fp4_fp16_grid.cc:42-44
-    if (!hints || !c || !a || !b || !scales || !global_scale || (!call_ws && call_ws_bytes))
-        return kErrBadArgument;
-    if ((uintptr_t)call_ws & (kWorkspaceAlign - 1))
-        return kErrBadArgument; // f32x4 slabs and 16-byte activation loads: the scratch contract is 256-byte alignment (petit_amd.h)
-    if (hints->c_type != hints->a_type)
-        return kErrKernelShape;
-    Family fam;
-    if (!family_for(hints->a_type, b_type, &fam))
-        return kErrKernelShape;
-    if (!shape_ok(n, k))
-        return kErrProblemShape;
-    // SiLU-mul: gate / up halves made of whole n-tiles, and one descriptor spans half the matrix
-    if (act && (n % 32 != 0 || (uint64_t)n * k / 2 >= (1ull << 32)))
-        return kErrProblemShape;
-    // 32-bit buffer offsets inside one n-tile row / activation block
-    if ((uint64_t)k * 16 * 4 * 2 >= (1ull << 31) || (uint64_t)k * 64 * 4 >= (1ull << 31))
-        return kErrProblemShape;
-    // M: every kernel addresses A and C per workgroup (64-bit base + a 32-bit offset inside at most 256 rows), so the exact kernels take any M
-    // up to the tables' last bucket (prefill chunks of 16375 x 57344 included); beyond it, refuse rather than wrap a grid dimension
-    if (m > kMaxM)
-        return kErrProblemShape;
-    // the native pipeline: pre-quantised activations / quantised SiLU-mul output (MXFP4 weights, 32x32x64 kernels only)
-    const unsigned restrict_ = (a_format ? kNeedK32 : 0u) | (out_format ? kNeedQuantOut : 0u);
-    if (out_format && !act)
-        return kErrBadArgument; // (the quantised output is the SiLU-mul epilogue's)
-    if (out_format && (n % 512 != 0 || ((uintptr_t)c & 15)))
-        return kErrProblemShape; // the consumer's K = n / 2 must be a whole number of 256-column producer tiles
-    if (a_format && ((uintptr_t)a & 15))
-        return kErrBadArgument;
-
-    const int dev = current_device();
-    const bool is_auto = is_auto_id(solution_id);
-    int klass = auto_class(solution_id);
-    if (const int dflt = (restrict_ == 0) ? auto_default_class(solution_id, b_type, m) : kClassExact) {
-        // the process-wide default class: taken when the scratch of this call (its own, else the registered one) covers the class's pick
-        const AutoChoice chn = choose_auto(fam, dev, hints->a_type, b_type, act, m, n, k, dflt, 0);
-        if (chn.entry) {
-            const uint64_t need_n = workspace_need(*chn.entry, chn.splitk, m, n, k);
+    const GemmCall g{b_type, c, a, b, scales, global_scale, m, n, k, hints, solution_id, epilogue, stream, io};
+    const Scratch s = call_ws ? Scratch{Scratch::kCallBuffer, call_ws, call_ws_bytes} : Scratch{Scratch::kRegistered, nullptr, 0};
+    GemmPlan p = plan_gemm(g, s);
+    if (p.tune) {
+        // $PETIT_AMD_AUTOTUNE=1: a problem no table knows is tuned once, here, before its first real launch (tune.hip), and planned again.  The
+        // candidates are limited to the scratch THIS call can use: its own, else the registered workspace if it serves this stream
+        void *tws = call_ws;
+        uint64_t tws_bytes = call_ws ? call_ws_bytes : 0;
+        if (!tws) {
             bool busy = false;
-            if (call_ws ? call_ws_bytes >= need_n : registered_workspace(dev, stream, need_n, &busy) != nullptr)
-                klass = dflt;
+            const int dev = current_device();
+            const uint64_t reg = g_workspace[dev].bytes.load();
+            tws = reg ? registered_workspace(dev, stream, reg, &busy) : nullptr;
+            tws_bytes = tws ? reg : 0;
         }
+        autotune_on_first_sight(b_type, c, a, b, scales, global_scale, m, n, k, hints->a_type, tws, tws_bytes, stream);
+        p = plan_gemm(g, s);
     }
-    // NVFP4 weights: the native class runs on the weights' MFMA-native image (e4m3 group scales are not E8M0 block scales: nvnative.hip), handed
-    // over by petit_gemm_nvfp4_native or attached to `b` beforehand; without one the call is refused, never served by another accuracy class
-    const void *nv_image = b_type != kDataTypeFp4e2m1 ? nullptr : (io && io->image) ? io->image : klass != kClassExact ? attached_image(b) : nullptr;
-    if (klass != kClassExact && b_type == kDataTypeFp4e2m1 && !nv_image)
-        return kErrKernelShape;
-    // the native kernels read the quantised activations (k-tile major, up to m * k bytes) through ONE 32-bit buffer descriptor, and the
-    // quantiser's grid has one row per activation row
-    if ((klass != kClassExact || a_format) && ((uint64_t)m * k >= (1ull << 32) || m > 65535u))
-        return kErrProblemShape;
-    if (restrict_ && is_auto && klass == kClassExact)
-        return kErrKernelShape; // quantised I/O is the native class's: name it (a sentinel or an explicit native id)
-    if (a_format && klass != kClassExact && (unsigned)klass != a_format)
-        return kErrKernelShape; // activations quantised to one format, kernel class of the other
-    const SolutionEntry *entry = nullptr;
-    unsigned splitk = 1;
-    if (is_auto) {
-        // $PETIT_AMD_AUTOTUNE=1: a problem no table knows is tuned once, here, before its first real launch (tune.hip)
-        if (klass == kClassExact && !act && autotune_enabled() && tuned_solution(dev, hints->a_type, b_type, m, n, k, kClassExact) == 0) {
-            // candidates are limited to the scratch THIS call can use: its own, else the registered workspace if it serves this stream
-            void *tws = call_ws;
-            uint64_t tws_bytes = call_ws ? call_ws_bytes : 0;
-            if (!tws) {
-                bool busy = false;
-                const uint64_t reg = g_workspace[dev].bytes.load();
-                tws = reg ? registered_workspace(dev, stream, reg, &busy) : nullptr;
-                tws_bytes = tws ? reg : 0;
-            }
-            autotune_on_first_sight(b_type, c, a, b, scales, global_scale, m, n, k, hints->a_type, tws, tws_bytes, stream);
-        }
-        const AutoChoice ch = choose_auto(fam, dev, hints->a_type, b_type, act, m, n, k, klass, restrict_);
-        entry = ch.entry, splitk = ch.splitk;
-        if (!entry)
-            return kErrKernelShape;
-        // (io == nullptr: the entry points that take petit_native_args refuse PETIT_SOLUTION_AUTO, so petit_gemm_auto_row_split and
-        // petit_gemm_workspace_bytes_ex, which see hints only, describe exactly the calls that get here)
-        if (klass == kClassExact && !io && !tl_in_row_split && !autotune_enabled()) {
-            if (const unsigned m1 = plan_row_split(*entry, splitk, m, n, k, arch_info(dev).num_cus)) {
-                // bulk + tail (plan_row_split): two default-pick calls on row ranges of A and C, same stream, same scratch (the launches are ordered).
-                // BOTH are resolved (kernel, split, scratch) before either is launched: a tail that cannot run must not leave C half written or one launch
-                // in a stream capture -- the call then runs as the single launch it would have been.
-                const size_t c_row = (act ? n / 2 : n) * sizeof(uint16_t), a_row = (size_t)k * sizeof(uint16_t);
-                unsigned *const c2 = (unsigned *)((char *)c + m1 * c_row);
-                const unsigned *const a2 = (const unsigned *)((const char *)a + m1 * a_row);
-                tl_in_row_split = true;
-                tl_dry_run = true;
-                const bool both = gemm_impl(b_type, c, a, b, scales, global_scale, m1, n, k, hints, solution_id, epilogue, call_ws, call_ws_bytes, stream, io) == kOk &&
-                                  gemm_impl(b_type, c2, a2, b, scales, global_scale, m - m1, n, k, hints, solution_id, epilogue, call_ws, call_ws_bytes, stream, io) == kOk;
-                tl_dry_run = false;
-                int rc = kOk;
-                if (both) {
-                    rc = gemm_impl(b_type, c, a, b, scales, global_scale, m1, n, k, hints, solution_id, epilogue, call_ws, call_ws_bytes, stream, io);
-                    if (rc == kOk)
-                        rc = gemm_impl(b_type, c2, a2, b, scales, global_scale, m - m1, n, k, hints, solution_id, epilogue, call_ws, call_ws_bytes, stream, io);
-                }
-                tl_in_row_split = false;
-                if (both)
-                    return rc; // (a failure here is a launch error of the device: nothing a different plan would have avoided)
-            }
-        }
-        // the native class at a ragged prefill M (plan_row_split_native, pick.hip): bulk in the class, the few dozen rows of the tail through the exact default
-        if (klass != kClassExact && restrict_ == 0 && !(io && io->image) && !tl_in_row_split && !autotune_enabled()) {
-            if (const unsigned m1 = plan_row_split_native(*entry, klass, splitk, m, n, k, arch_info(dev).num_cus)) {
-                const size_t c_row = (act ? n / 2 : n) * sizeof(uint16_t), a_row = (size_t)k * sizeof(uint16_t);
-                unsigned *const c2 = (unsigned *)((char *)c + m1 * c_row);
-                const unsigned *const a2 = (const unsigned *)((const char *)a + m1 * a_row);
-                tl_in_row_split = true;
-                tl_dry_run = true;
-                const bool both = gemm_impl(b_type, c, a, b, scales, global_scale, m1, n, k, hints, solution_id, epilogue, call_ws, call_ws_bytes, stream, io) == kOk &&
-                                  gemm_impl(b_type, c2, a2, b, scales, global_scale, m - m1, n, k, hints, PETIT_SOLUTION_AUTO, epilogue, call_ws, call_ws_bytes, stream, nullptr) == kOk;
-                tl_dry_run = false;
-                int rc = kOk;
-                if (both) {
-                    rc = gemm_impl(b_type, c, a, b, scales, global_scale, m1, n, k, hints, solution_id, epilogue, call_ws, call_ws_bytes, stream, io);
-                    if (rc == kOk)
-                        rc = gemm_impl(b_type, c2, a2, b, scales, global_scale, m - m1, n, k, hints, PETIT_SOLUTION_AUTO, epilogue, call_ws, call_ws_bytes, stream, nullptr);
-                }
-                tl_in_row_split = false;
-                if (both)
-                    return rc;
-            }
-        }
-    } else {
-        entry = find_explicit(fam, solution_id);
-        if (!entry)
-            return kErrKernelShape;
-        if (!entry_fits(*entry, m, k))
-            return kErrProblemShape;
-        splitk = solution_splitk(solution_id);
-        if (splitk == 0)
-            return kErrKernelShape;
-        if (act && !act_runs(*entry, splitk, restrict_))
-            return kErrKernelShape; // unsplit: needs an even number of n-tiles per wave; split: a 16-bit output (the reduce pass applies SiLU-mul)
-        if (!entry_allows(*entry, restrict_) || (a_format && (unsigned)entry_class(*entry) != a_format))
-            return kErrKernelShape;
-    }
-
-    if (is_native_am(entry->shape.am) && ((uint64_t)m * k >= (1ull << 32) || m > 65535u))
-        return kErrProblemShape; // (an explicit native id: the same descriptor range as above)
-    if (is_native_am(entry->shape.am) && b_type == kDataTypeFp4e2m1) {
-        if (!nv_image)
-            nv_image = attached_image(b); // (an explicit native id)
-        if (!nv_image)
-            return kErrKernelShape; // an explicit native id on NVFP4 weights that have no image attached
-        if (nv6_elem_bytes(n, k) >= (1ull << 32))
-            return kErrProblemShape; // (the image's element part is read through one 32-bit buffer descriptor)
-    }
-
-    GemmArgs args{};
-    args.c = c, args.a = a, args.w = b, args.s = scales, args.gs = global_scale;
-    if (is_native_am(entry->shape.am) && b_type == kDataTypeFp4e2m1)
-        args.w = nv_image, args.s = (const char *)nv_image + nv6_elem_bytes(n, k);
-    args.m = m, args.n = n, args.k = k;
-    args.bias = epilogue ? epilogue->bias : nullptr;
-    args.qa = a_format ? (const void *)a : nullptr, args.qa_format = a_format, args.out_format = out_format;
-    const bool have_qa = a_format != 0;
-    uint64_t need = workspace_need(*entry, splitk, m, n, k, have_qa);
-    if (need) {
-        void *ws = nullptr;
-        if (call_ws) {
-            if (call_ws_bytes < need && !is_auto)
-                return kErrBadArgument; // too small for the kernel the caller named
-            ws = call_ws_bytes >= need ? call_ws : nullptr;
-        } else {
-            bool busy = false;
-            ws = registered_workspace(dev, stream, need, &busy);
-            if (busy && !is_auto)
-                return kErrBadArgument; // the registered workspace is bound to another stream: pass one per call
-        }
-        if (!ws && klass != kClassExact && is_auto && splitk > 1) {
-            // native default pick with a K split, scratch (per call or registered) covers the activations only, or they came quantised: the
-            // same kernel unsplit -- what petit_gemm_resolve_solution reports for the same arguments.  SiLU-mul rode on the reduce pass of
-            // the split (act_runs): unsplit it is the kernel's own epilogue's job, which needs gate and up tile in one wave (act_ok) -- a
-            // row like the 64 x 320 kernel (five n-tiles per wave) x split 4 cannot, and returned kOk with C unwritten: re-pick
-            if (act && !act_ok(*entry)) {
-                unsigned sk1 = 1;
-                const SolutionEntry *e1 = heuristic_native(fam, klass, m, n, k, true, /*have_slabs=*/false, &sk1, restrict_);
-                if (!e1)
-                    return kErrKernelShape;
-                entry = e1;
-            }
-            const uint64_t need1 = workspace_need(*entry, 1, m, n, k, have_qa);
-            void *ws1 = nullptr;
-            if (!need1) {
-                splitk = 1, need = 0;
-            } else if (call_ws) {
-                ws1 = call_ws_bytes >= need1 ? call_ws : nullptr;
-            } else {
-                bool busy = false;
-                ws1 = registered_workspace(dev, stream, need1, &busy);
-            }
-            if (ws1)
-                splitk = 1, need = need1, ws = ws1;
-        }
-        if (!ws && need) {
-            if (!is_auto || klass != kClassExact)
-                return kErrKernelShape; // explicit id (or the native class) that needs scratch nobody provided
-            // AUTO without scratch: the best kernel that needs none (not the K-split pick minus its split: a tiled kernel
-            // chosen FOR its split leaves most of the chip idle without it)
-            entry = heuristic(fam, m, n, k, act);
-            splitk = 1;
-            if (!entry || workspace_need(*entry, 1, m, n, k))
-                return kErrKernelShape; // (unreachable: the heuristic never picks a native kernel)
-        }
-        args.workspace = (float *)ws;
-    }
-    // SiLU-mul: in the kernel's epilogue unsplit; by the reduce pass over plain slabs with a cross-workgroup K split
-    args.act = (act && splitk == 1) ? 1u : 0u;
-    args.reduce_act = (act && splitk > 1) ? 1u : 0u;
-    if (tl_dry_run)
-        return kOk;
-    int rc = entry->launch(args, splitk, (hipStream_t)stream);
-    if (rc == kErrSplitCollapsed) {
-        // K is too short for the split the id (or the table row) names: the kernel runs as one part, so SiLU-mul is its own epilogue's job
-        if (!act_ok(*entry)) {
-            if (!is_auto)
-                return kErrKernelShape;
-            if (klass != kClassExact) { // native class: the class's best kernel whose own epilogue applies SiLU-mul, within the scratch at hand
-                unsigned sk1 = 1;
-                const SolutionEntry *e1 = heuristic_native(fam, klass, m, n, k, true, /*have_slabs=*/false, &sk1, restrict_);
-                if (!e1 || workspace_need(*e1, 1, m, n, k, have_qa) > workspace_need(*entry, splitk, m, n, k, have_qa))
-                    return kErrKernelShape;
-                entry = e1;
-            } else {
-                entry = heuristic(fam, m, n, k, true);
-                if (!entry || workspace_need(*entry, 1, m, n, k))
-                    return kErrKernelShape;
-            }
-        }
-        args.act = 1u, args.reduce_act = 0u;
-        rc = entry->launch(args, 1, (hipStream_t)stream);
-    }
-    return rc;
+    if (!p.bulk_rows)
+        return launch(g, p);
+    const int rc = launch(rows_of(g, 0, p.bulk_rows, false), p.bulk);
+    if (rc != kOk)
+        return rc; // (a launch error of the device: nothing a different plan would have avoided)
+    return launch(rows_of(g, p.bulk_rows, m - p.bulk_rows, p.klass != kClassExact), p.tail);
 }
 
 } // namespace petit_amd

@@ -17,7 +17,7 @@ enum : int {
     kErrLaunch = 3,       // hipGetLastError() != hipSuccess after a launch
     kErrBadArgument = 4,  // null pointer / unknown dtype
     // internal, never returned to a caller: a launcher asked for SiLU-mul in the reduce pass found that the K range does not split (fewer
-    // spans than parts -> one part, no reduce pass); gemm_impl then runs the kernel unsplit with SiLU-mul in its own epilogue
+    // spans than parts -> one part, no reduce pass); gemm_impl's launch step then runs the kernel unsplit with SiLU-mul in its own epilogue
     kErrSplitCollapsed = 100,
 };
 
@@ -105,7 +105,7 @@ inline unsigned moe_slots(unsigned m, unsigned bm, unsigned num_experts) {
     return slots <= 65535u ? (unsigned)slots : 0u;
 }
 
-// dispatch.hip: the dispatcher behind every GEMM entry point (solution_id: explicit id or one of the AUTO sentinels)
+// dispatch.hip: the dispatcher behind every GEMM entry point, which launches what plan_gemm (dispatch.h) decides (solution_id: explicit id or one of the AUTO sentinels)
 } // namespace petit_amd
 struct petit_solution_hints;
 struct petit_epilogue;

@@ -1657,6 +1657,22 @@ def test_native_row_split_is_its_two_parts_and_is_capturable(pk):
             assert torch.equal(out.view(torch.int16), c.view(torch.int16)) and torch.equal(warm.view(torch.int16), c.view(torch.int16)), (kind, sid)
             ran += 1
             del c, bulk, tail, out, warm, g
+        if kind == "mx":
+            # the process-wide default class: AUTO on MXFP4 weights plans the same bulk + tail, and the queries say so
+            prev = pk.ops.mxfp4_default_activations()
+            pk.ops.set_mxfp4_default_activations("mxfp8")
+            try:
+                m1 = pk.ops.auto_row_split(h, m, n, k)
+                assert m1, "default class: no row split"
+                a = P.activations(m, True, 9300)
+                c = P.run(a, True, -1)
+                bulk = P.run(a[:m1], True, -1)
+                tail = P.run(a[m1:], True, -1)
+                assert torch.equal(c[:m1].view(torch.int16), bulk.view(torch.int16))
+                assert torch.equal(c[m1:].view(torch.int16), tail.view(torch.int16))
+                del c, bulk, tail
+            finally:
+                pk.ops.set_mxfp4_default_activations(prev)
         del P
         torch.cuda.empty_cache()
     assert ran >= 2

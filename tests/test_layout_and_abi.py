@@ -903,6 +903,24 @@ def test_ragged_prefill_m_is_planned_as_bulk_plus_tail():
     h = _lib.SolutionHints(_lib.CXX_DTYPE_BF16, _lib.CXX_DTYPE_FP4_E2M1, _lib.CXX_DTYPE_BF16, 0)
     assert _lib.lib.petit_gemm_auto_row_split(C.byref(h), 2084, 8192, 28672, None) == 2048
     assert fired >= 8
+    # the process-wide MXFP4 default class: AUTO at a ragged M runs bulk + tail in the class, and the queries describe that call -- the row split,
+    # and scratch that covers both parts and the class's own pick (the class is taken only when the call's scratch covers it)
+    L = _lib.lib
+    prev = L.petit_get_mxfp4_default_class()
+    L.petit_set_mxfp4_default_class(8)
+    try:
+        hm = _lib.SolutionHints(_lib.CXX_DTYPE_BF16, _lib.CXX_DTYPE_MXFP4_E2M1, _lib.CXX_DTYPE_BF16, 0)
+        m, n, k = 2084, 8192, 8192
+        m1 = L.petit_gemm_auto_row_split(C.byref(hm), m, n, k, None)
+        assert 0 < m1 < m and m - m1 <= 128 and m1 % 16 == 0, m1
+        assert L.petit_gemm_row_split(C.byref(hm), m, n, k, C.c_uint64(_lib.PETIT_SOLUTION_AUTO), None) == m1
+        assert L.petit_gemm_auto_row_split(C.byref(hm), m1, n, k, None) == 0
+        ws = lambda mm: int(L.petit_gemm_workspace_bytes(C.byref(hm), mm, n, k, C.c_uint64(_lib.PETIT_SOLUTION_AUTO)))
+        assert ws(m) >= max(ws(m1), ws(m - m1)) > 0
+        sid = int(L.petit_gemm_resolve_solution(C.byref(hm), m, n, k, C.c_uint64(_lib.PETIT_SOLUTION_AUTO), None, C.c_uint64(ws(m))))
+        assert (sid >> 48) & 0xF == 13, hex(sid)   # (the whole problem's kernel, for that scratch: the class's)
+    finally:
+        L.petit_set_mxfp4_default_class(prev)
 
 
 def test_problem_ranges_are_refused_not_wrapped():
