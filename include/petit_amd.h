@@ -410,7 +410,22 @@ int petit_quantize_activations(void *qa, const void *a, unsigned m, unsigned k, 
  *       petit_gemm_fp4_fp16_grid_ws(c, a, b, scales, ..., PETIT_SOLUTION_AUTO_NATIVE_*, ...) -- mul_nvfp4_a16(..., solution_id = -2 / -3 / -4) --
  *       runs on the image attached to `b`.  The image stays the caller's memory and must outlive the attachment; image = NULL detaches.  A
  *       sentinel (or explicit native id) on weights without an image returns PETIT_ERROR_KERNEL_SHAPE -- never another accuracy class.
- * PETIT_SOLUTION_AUTO on NVFP4 weights is never affected: it stays the exact class.
+ * PETIT_SOLUTION_AUTO on NVFP4 weights is never affected: it stays the exact class.  Both entry points refuse an explicit id of the exact class on an
+ * image (PETIT_ERROR_KERNEL_SHAPE).
+ *
+ * Without a resident image -- petit_gemm_nvfp4_native_transient(c, a, b, scales, ...): b / scales are the PACKED tensors (what
+ * petit_gemm_fp4_fp16_grid_ws takes); the call builds the image into its workspace, then runs the native call on it, in stream order on `stream`.
+ * Nothing is registered or cached: two calls with different weights may share one workspace one after the other, and a captured call reads b / scales
+ * anew at every replay.  The weights then cost 4.5 bits each plus ONE workspace the size of the largest layer's image, shared by all layers.
+ *   workspace layout: [0, I) the image, I = petit_nvfp4_native_image_bytes(k, n) rounded up to 256; [I, I + S) exactly the scratch the planned native
+ *       call needs.  petit_gemm_nvfp4_native_transient_workspace_bytes returns I + S, read from the launcher's plan (0: the call would be refused).
+ *   solution_id: PETIT_SOLUTION_AUTO_NATIVE_MXFP8 / _MXFP6 / _MXFP4 or an explicit native id of the NVFP4 family; PETIT_SOLUTION_AUTO and exact-class
+ *       ids: PETIT_ERROR_KERNEL_SHAPE.  N % 16, K % 256 or an element part of 2^32 bytes or more: PETIT_ERROR_PROBLEM_SHAPE.  A workspace that is
+ *       missing (the registered one is never used), too small or not 256-byte aligned: the rules of petit_gemm_nvfp4_native.  Every refusal happens
+ *       before the first launch: C is untouched and nothing enters a stream capture.
+ *   results: bit for bit those of the attached-image call it stands for -- with native NULL or both formats 0, petit_gemm_fp4_fp16_grid_ws(..., the
+ *       sentinel) on b with the image attached, its bulk + tail row split at a ragged M included (the image is built once, before the bulk; the exact
+ *       tail reads b / scales); with pre-quantised activations or a quantised SiLU-mul output, petit_gemm_nvfp4_native on the same image.
  */
 uint64_t petit_nvfp4_native_image_bytes(unsigned in_chan, unsigned out_chan);
 int petit_nvfp4_native_image(void *image, const unsigned *b, const unsigned *scales, unsigned in_chan, unsigned out_chan, void *stream);
@@ -421,6 +436,11 @@ const void *petit_nvfp4_native_attached(const void *b);
 int petit_gemm_nvfp4_native(void *c, const void *a, const void *image, const float *global_scale, unsigned m, unsigned n, unsigned k,
                             const petit_solution_hints *hints, uint64_t solution_id, const petit_epilogue *epilogue,
                             const petit_native_args *native, void *workspace, uint64_t workspace_bytes, void *stream);
+int petit_gemm_nvfp4_native_transient(void *c, const void *a, const unsigned *b, const unsigned *scales, const float *global_scale, unsigned m, unsigned n,
+                                      unsigned k, const petit_solution_hints *hints, uint64_t solution_id, const petit_epilogue *epilogue,
+                                      const petit_native_args *native, void *workspace, uint64_t workspace_bytes, void *stream);
+uint64_t petit_gemm_nvfp4_native_transient_workspace_bytes(const petit_solution_hints *hints, unsigned m, unsigned n, unsigned k, uint64_t solution_id,
+                                                           const petit_epilogue *epilogue, const petit_native_args *native);
 
 /*
  * Grouped launch (no counterpart in the reference): up to PETIT_GROUP_MAX weight matrices that share the activation rows --

@@ -150,6 +150,30 @@ int petit_gemm_nvfp4_native(void *c, const void *a, const void *image, const flo
                      solution_id, epilogue, workspace, workspace_bytes, stream, &io);
 }
 
+int petit_gemm_nvfp4_native_transient(void *c, const void *a, const unsigned *b, const unsigned *scales, const float *global_scale, unsigned m, unsigned n,
+                                      unsigned k, const petit_solution_hints *hints, uint64_t solution_id, const petit_epilogue *epilogue,
+                                      const petit_native_args *native, void *workspace, uint64_t workspace_bytes, void *stream) {
+    if (!native_args_ok(native))
+        return kErrBadArgument;
+    NativeIo io = native_io(native);
+    io.transient = true; // (the plan builds the image into the front of the workspace: dispatch.hip plan_transient)
+    if (solution_id == PETIT_SOLUTION_AUTO)
+        return kErrKernelShape; // this entry point is the native class's: name a sentinel or a native kernel id
+    return gemm_impl(kDataTypeFp4e2m1, (unsigned *)c, (const unsigned *)a, b, scales, global_scale, m, n, k, hints, solution_id, epilogue, workspace,
+                     workspace_bytes, stream, &io);
+}
+
+uint64_t petit_gemm_nvfp4_native_transient_workspace_bytes(const petit_solution_hints *hints, unsigned m, unsigned n, unsigned k, uint64_t solution_id,
+                                                           const petit_epilogue *epilogue, const petit_native_args *native) {
+    if (!native_args_ok(native) || !hints || solution_id == PETIT_SOLUTION_AUTO)
+        return 0;
+    NativeIo io = native_io(native);
+    io.transient = true;
+    const GemmCall g{kDataTypeFp4e2m1, nullptr, nullptr, nullptr, nullptr, nullptr, m, n, k, hints, solution_id, epilogue, nullptr, &io};
+    const GemmPlan p = plan_gemm(g, Scratch{Scratch::kQuery, nullptr, UINT64_MAX});
+    return p.rc == kOk ? p.need : 0;
+}
+
 int petit_gemm_fp4_fp16_grouped(const petit_group_member *members, unsigned count, const unsigned *a, unsigned m, unsigned k,
                                 const petit_solution_hints *hints, uint64_t solution_id, void *stream) {
     if (count == 0 || m == 0 || k == 0)

@@ -110,6 +110,7 @@ struct GemmCall { // the arguments of gemm_impl but the scratch (a query has no 
     const petit_epilogue *epilogue;
     void *stream;
     const NativeIo *io;
+    const void *image = nullptr; // NVFP4 weights: the image the call brings (a transient call's, built into its scratch); else the attached one
 };
 struct Scratch { // the scratch a call can use
     enum Kind { kCallBuffer, kRegistered, kQuery } kind;
@@ -130,6 +131,7 @@ struct GemmPlan : LaunchPlan {
     unsigned bulk_rows = 0; // 0: one launch.  Else bulk + tail: the row where the tail starts, and the plans of both parts (then entry / splitk name the whole
     LaunchPlan bulk, tail;  // problem's kernel; need is the larger part's, and at least what the default class was taken for)
     bool tune = false;      // $PETIT_AMD_AUTOTUNE=1 and a default pick no table knows: the launcher tunes it, then plans again
+    void *build_image = nullptr; // a transient call: the launcher builds the NVFP4 image here (offset 0 of the call's scratch) before the first part
 };
 // `part`: one part of a bulk + tail call, never split again
 GemmPlan plan_gemm(const GemmCall &g, const Scratch &s, bool part = false);

@@ -181,10 +181,49 @@ static GemmCall rows_of(const GemmCall &g, unsigned row0, unsigned rows, bool au
     return r;
 }
 
+// petit_gemm_nvfp4_native_transient: the image is built per call into the front of the call's scratch -- [image, nv6_image_bytes rounded up to 256][the
+// native call's own scratch] -- and the call is planned as the call it stands for, on the scratch behind the image: with 16-bit activations and result the
+// attached-image call (petit_gemm_fp4_fp16_grid_ws with the sentinel: its bulk + tail row split included; the image is built once, before the bulk, and
+// the exact tail reads b / scales), with pre-quantised activations or a quantised output petit_gemm_nvfp4_native on that image.  Every refusal comes
+// from this plan, before the build.
+static GemmPlan plan_transient(const GemmCall &g, const Scratch &s) {
+    GemmPlan p;
+    const auto refuse = [&p](int rc) { return p.rc = rc, p; };
+    if (g.m == 0 || g.n == 0 || g.k == 0)
+        return p;
+    if (g.solution_id == PETIT_SOLUTION_AUTO)
+        return refuse(kErrKernelShape); // (the exact class reads the packed tensors: there is nothing to build; exact ids: plan_gemm)
+    if (g.n % kTileN || g.k % 256 || nv6_elem_bytes(g.n, g.k) >= (1ull << 32))
+        return refuse(kErrProblemShape); // shapes the image does not take
+    const uint64_t img = (nv6_image_bytes(g.n, g.k) + kWorkspaceAlign - 1) & ~(uint64_t)(kWorkspaceAlign - 1);
+    void *image;
+    Scratch rest;
+    if (s.kind == Scratch::kQuery) {
+        image = (void *)query_image();
+        rest = Scratch{Scratch::kQuery, nullptr, s.bytes > img ? s.bytes - img : 0};
+    } else if (s.kind == Scratch::kCallBuffer && s.bytes >= img) {
+        image = s.ptr;
+        rest = Scratch{Scratch::kCallBuffer, (char *)s.ptr + img, s.bytes - img};
+    } else { // (the rules of a native call whose scratch is missing / too small; the registered workspace is never used for the image)
+        return refuse(s.kind != Scratch::kCallBuffer || is_auto_id(g.solution_id) ? kErrKernelShape : kErrBadArgument);
+    }
+    NativeIo io = *g.io;
+    io.transient = false;
+    GemmCall gi = g;
+    gi.io = (io.a_format || io.out_format) ? &io : nullptr; // (16-bit in and out: planned exactly as the attached-image call, io == nullptr)
+    gi.image = image;
+    p = plan_gemm(gi, rest);
+    if (p.rc == kOk && p.entry)
+        p.build_image = image, p.need += img;
+    return p;
+}
+
 // Every check and decision of a dense call, in the order they are made, and no launch: argument and range checks, the accuracy class, the NVFP4 image, the
 // pick, the bulk + tail row split, the scratch fallbacks.  It keeps no state between calls; the registered workspace is looked up where the launcher needs
 // it, which binds it to the call's stream.
 GemmPlan plan_gemm(const GemmCall &g, const Scratch &s, bool part) {
+    if (g.io && g.io->transient && !part)
+        return plan_transient(g, s);
     GemmPlan p;
     const auto refuse = [&p](int rc) { return p.rc = rc, p; };
     const petit_epilogue *epilogue = g.epilogue;
@@ -238,7 +277,7 @@ GemmPlan plan_gemm(const GemmCall &g, const Scratch &s, bool part) {
             *ws = ptr;
         return s.kind == Scratch::kRegistered ? ptr != nullptr : s.bytes >= need;
     };
-    const auto attached = [&] { return s.kind == Scratch::kQuery ? query_image() : attached_image(g.b); };
+    const auto attached = [&] { return g.image ? g.image : s.kind == Scratch::kQuery ? query_image() : attached_image(g.b); };
     const bool is_auto = is_auto_id(g.solution_id);
     int klass = auto_class(g.solution_id);
     uint64_t need_class = 0;
@@ -306,6 +345,8 @@ GemmPlan plan_gemm(const GemmCall &g, const Scratch &s, bool part) {
             return refuse(kErrKernelShape); // unsplit: needs an even number of n-tiles per wave; split: a 16-bit output (the reduce pass applies SiLU-mul)
         if (!entry_allows(*entry, restrict_) || (a_format && (unsigned)entry_class(*entry) != a_format))
             return refuse(kErrKernelShape);
+        if (g.b_type == kDataTypeFp4e2m1 && ((io && io->image) || g.image) && entry_class(*entry) == kClassExact)
+            return refuse(kErrKernelShape); // an image names the native class: an exact kernel would read image bytes as packed weights
     }
 
     if (is_native_am(entry->shape.am) && ((uint64_t)m * k >= (1ull << 32) || m > 65535u))
@@ -429,6 +470,11 @@ int gemm_impl(int b_type, unsigned *c, const unsigned *a, const unsigned *b, con
         }
         autotune_on_first_sight(b_type, c, a, b, scales, global_scale, m, n, k, hints->a_type, tws, tws_bytes, stream);
         p = plan_gemm(g, s);
+    }
+    if (p.rc == kOk && p.build_image) { // a transient call: its image first, in stream order on the same stream
+        const int rc = nv6_image(p.build_image, b, scales, n, k, (hipStream_t)stream);
+        if (rc != kOk)
+            return rc;
     }
     if (!p.bulk_rows)
         return launch(g, p);

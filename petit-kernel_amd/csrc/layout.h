@@ -96,7 +96,7 @@ PETIT_HD size_t packed_mxscale_byte_index(unsigned k_total, unsigned n, unsigned
 }
 
 // ---------------------------------------------------------------------------------------------------------------------------------
-// "petit-cdna4-nv6/1": the MFMA-native image of NVFP4 weights (nvnative.hip builds it ONCE at load time; gemm_native32.hpp, WF = 6,
+// "petit-cdna4-nv6/1": the MFMA-native image of NVFP4 weights (nvnative.hip builds it at load time or per call; gemm_native32.hpp, WF = 6,
 // consumes it).  NVFP4's e4m3 group-16 scales do not fit the block-scaled MFMA (one E8M0 scale per 32 k), so every 32-k block of a
 // weight row is re-encoded:  E = floor(log2(max |fp4 x scale| of the block)) - 2,  element = RNE_e2m3(fp4 x scale / 2^E)  (FP6 e2m3:
 // the block maximum lands in [4, 7.5]; never saturates, see nvnative.hip), scale byte = E + 127.  A different ACCURACY CLASS

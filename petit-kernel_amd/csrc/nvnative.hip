@@ -1,5 +1,6 @@
-// nvnative.hip -- the MFMA-native image of NVFP4 weights ("petit-cdna4-nv6/1", layout.h), built ONCE at load time from the packed
-// tensors the exact kernels read (petit_repack_nvfp4_weights / _scales), consumed by the WF = 6 instances of gemm_native32.hpp.
+// nvnative.hip -- the MFMA-native image of NVFP4 weights ("petit-cdna4-nv6/1", layout.h), built from the packed tensors the exact kernels read
+// (petit_repack_nvfp4_weights / _scales) once at load time, or per call into the call's workspace (petit_gemm_nvfp4_native_transient: then the builder
+// is on the hot path), consumed by the WF = 6 instances of gemm_native32.hpp.
 //
 // Why an image and not a conversion inside the GEMM (VERDICT r05 item 1 asked for the in-kernel form first): NVFP4 is
 //   w[n][k] = fp4(q[n][k]) x e4m3(s[n][k / 16]) x global_scale
@@ -21,10 +22,12 @@
 //   to 9.79 % of its rms (profiles/r06_nv6_reencode.md; FP8 e4m3 elements: 9.73 %, at 8 bits and the FP8 rate for every activation format).
 #include <hip/hip_runtime.h>
 
+#include <algorithm>
 #include <cmath>
 #include <cstring>
 
 #include "device_common.hpp"
+#include "hal.h"
 #include "layout.h"
 #include "petit_internal.h"
 
@@ -116,44 +119,115 @@ inline unsigned e2m3_rne_host(float x) {
 
 } // namespace
 
-// One thread = one 32-k block of one weight row; consecutive threads = consecutive rows of an n32-block (16-byte stores side by side).
-__global__ __launch_bounds__(256) void nv6_image_kernel(unsigned char *__restrict__ img, const u32x4 *__restrict__ pw, const unsigned char *__restrict__ ps,
-                                                        unsigned n, unsigned k) {
-    const unsigned ktiles = k / kTileK;
-    const size_t total = (size_t)((n + 31) / 32) * ktiles * 4 * 32;
-    unsigned char *const sc = img + nv6_elem_bytes(n, k);
-    for (size_t o = (size_t)blockIdx.x * blockDim.x + threadIdx.x; o < total; o += (size_t)gridDim.x * blockDim.x) {
-        const unsigned r32 = (unsigned)(o % 32), b4 = (unsigned)((o / 32) % 4);
-        const size_t tile = o / 128;
-        const unsigned kt = (unsigned)(tile % ktiles), blk32 = (unsigned)(tile / ktiles);
-        const unsigned row = blk32 * 32 + r32, blk = 4 * kt + b4, q = b4 >> 1, h = b4 & 1u;
-        unsigned words[6] = {0u, 0u, 0u, 0u, 0u, 0u}, sbyte = 127u;
-        if (row < n) {
-            const u32x4 raw = pw[packed_weight_word_index(k, row, 4 * blk) / 4];
-            const unsigned w[4] = {raw[0], raw[1], raw[2], raw[3]};
-            const size_t si = packed_nvscale_byte_index(k, row, 2 * blk);
-            float v[32];
-            sbyte = block_values(w, ps[si], ps[si + 1], v);
 #if defined(__HIP_DEVICE_COMPILE__)
-            f32x16v ea, eb; // element 2 t = ea[t], 2 t + 1 = eb[t] (tools/probes/mfma32_fp6_probe.hip)
-#pragma unroll
-            for (int t = 0; t < 16; ++t)
-                ea[t] = v[2 * t], eb[t] = v[2 * t + 1];
-            const float scale = bits_f32((sbyte == 0xffu ? 127u : sbyte) << 23);
-            const u32x6 qv = cvt_2xpk16_fp6_f32(ea, eb, scale); // (early-clobber form: device_common.hpp)
-#pragma unroll
-            for (int d = 0; d < 6; ++d)
-                words[d] = qv[d];
-#endif
-        }
-        const unsigned lane_img = h * 32 + r32;
-        unsigned char *const tile_base = img + ((size_t)blk32 * ktiles + kt) * kNv6TileBytes;
-        *reinterpret_cast<u32x4 *>(tile_base + q * 1024 + lane_img * 16) = u32x4{words[0], words[1], words[2], words[3]};
-        uint2 tail;
-        tail.x = words[4], tail.y = words[5];
-        *reinterpret_cast<uint2 *>(tile_base + 2048 + lane_img * 16 + q * 8) = tail;
-        sc[nv6_scale_offset(k, row, blk)] = (unsigned char)sbyte;
+// 2 KS bytes (a scale record of one lane for one span) as KS / 2 dwords, one vector load / store
+template <int KS> __device__ __forceinline__ void load_rec(unsigned (&d)[KS / 2], const unsigned char *p) {
+    if constexpr (KS == 8) {
+        const u32x4 v = *reinterpret_cast<const u32x4 *>(p);
+        d[0] = v[0], d[1] = v[1], d[2] = v[2], d[3] = v[3];
+    } else if constexpr (KS == 4) {
+        const uint2 v = *reinterpret_cast<const uint2 *>(p);
+        d[0] = v.x, d[1] = v.y;
+    } else {
+        d[0] = *reinterpret_cast<const unsigned *>(p);
     }
+}
+template <int KS> __device__ __forceinline__ void store_rec(unsigned char *p, const unsigned (&d)[KS / 2]) {
+    if constexpr (KS == 8) {
+        *reinterpret_cast<u32x4 *>(p) = u32x4{d[0], d[1], d[2], d[3]};
+    } else if constexpr (KS == 4) {
+        uint2 v;
+        v.x = d[0], v.y = d[1];
+        *reinterpret_cast<uint2 *>(p) = v;
+    } else {
+        *reinterpret_cast<unsigned *>(p) = d[0];
+    }
+}
+
+// One 32-k block: its 6 FP6 words and its E8M0 byte from the lane's 16 bytes of nibbles and the two group scale bytes -- block_values + the
+// hardware convert, bit for bit.  The nibbles go through the hardware E2M1 convert (exact, sign of zero kept) and the exact products are the
+// values block_values forms; their maximum is taken with abs-modifier max3 (products are canonical floats: no canonicalising moves).
+__device__ __forceinline__ unsigned nv6_block(const u32x4 w, unsigned s_lo, unsigned s_hi, unsigned (&words)[6]) {
+    bool nan_lo, nan_hi;
+    const float sl = e4m3_value(s_lo, &nan_lo), sh = e4m3_value(s_hi, &nan_hi);
+    f32x16v ea, eb; // element 2 t = ea[t], 2 t + 1 = eb[t] (tools/probes/mfma32_fp6_probe.hip); word j, byte sel = elements 8 j + 2 sel, + 1
+    float amax = 0.f;
+    static_for<0, 16>([&](auto T) {
+        constexpr int t = decltype(T)::value;
+        const f32x2 p = cvt_fp4_f32<t % 4>(w[t / 4], 1.0f);
+        const float s = t < 8 ? sl : sh;
+        const float x = p[0] * s, y = p[1] * s;
+        ea[t] = x, eb[t] = y;
+        amax = fmaxf(amax, fmaxf(fabsf(x), fabsf(y)));
+    });
+    const unsigned sbyte = amax == 0.f ? 127u : ((f32_bits(amax) >> 23) & 0xffu) - 2u;
+    const u32x6 qv = cvt_2xpk16_fp6_f32(ea, eb, bits_f32(sbyte << 23)); // (early-clobber form: device_common.hpp)
+    const bool nan = nan_lo || nan_hi; // (block_values: NaN-scaled zeros, scale byte 0xff)
+#pragma unroll
+    for (int d = 0; d < 6; ++d)
+        words[d] = nan ? 0u : (unsigned)qv[d];
+    return nan ? 0xffu : sbyte;
+}
+#endif
+
+// The builder, organised around the packed layout (layout.h): one wave = one (32-row block b, span sp of KS k-tiles).  Lane l = 32 h + r owns row
+// 32 b + r and, of every k-tile of the span, the blocks g = h (image plane 0) and g = 2 + h (plane 1) -- exactly its lane of the image tile.  Its
+// weight reads are one dwordx4 per block, contiguous across lanes within the two 1 KiB packed tiles of the block; its NV scales for the span are
+// one 2 KS-byte record per block (the packed scale layout's own record); its E8M0 bytes for the span collect in registers and leave as one
+// 2 KS-byte store (the image's scale record); the planes leave as three 16-byte stores per k-tile.  Rows >= N (N % 32 == 16: the upper half of
+// the last block) read nothing and produce what the host twin writes (zero elements, scale byte 127).  Vector stores only.
+template <int KS>
+__global__ __launch_bounds__(256) void nv6_image_kernel(unsigned char *__restrict__ img, const u32x4 *__restrict__ pw, const unsigned char *__restrict__ ps,
+                                                        unsigned n, unsigned k, unsigned items) {
+#if defined(__HIP_DEVICE_COMPILE__)
+    const unsigned lane = threadIdx.x % 64, h = lane / 32, r = lane % 32;
+    const unsigned ktiles = k / kTileK, nspans = ktiles / KS;
+    unsigned char *const sc = img + nv6_elem_bytes(n, k);
+    for (unsigned item = blockIdx.x * 4 + threadIdx.x / 64; item < items; item += gridDim.x * 4) {
+        const unsigned b32 = item / nspans, sp = item % nspans;
+        const unsigned row = b32 * 32 + r, nt = row / 16, rr = row % 16;
+        const bool live = row < n;
+        // packed inputs: tile (nt, kt) lane 16 g + rr (weights), record (nt, sp) lane 16 g + rr (scales), for g = h (q = 0) and g = 2 + h (q = 1)
+        unsigned rec[2][KS / 2];
+        u32x4 w[KS][2];
+#pragma unroll
+        for (int q = 0; q < 2; ++q) {
+            const unsigned g = 2 * q + h;
+            if (live) {
+                load_rec<KS>(rec[q], ps + (((size_t)nt * nspans + sp) * 64 + g * 16 + rr) * (2 * KS));
+#pragma unroll
+                for (int t = 0; t < KS; ++t)
+                    w[t][q] = pw[((size_t)nt * ktiles + sp * KS + t) * 64 + g * 16 + rr];
+            } else {
+#pragma unroll
+                for (int d = 0; d < KS / 2; ++d)
+                    rec[q][d] = 0u;
+#pragma unroll
+                for (int t = 0; t < KS; ++t)
+                    w[t][q] = u32x4{0u, 0u, 0u, 0u};
+            }
+        }
+        unsigned out_rec[KS / 2];
+#pragma unroll
+        for (int d = 0; d < KS / 2; ++d)
+            out_rec[d] = 0u;
+#pragma unroll
+        for (int t = 0; t < KS; ++t) {
+            unsigned words[2][6];
+#pragma unroll
+            for (int q = 0; q < 2; ++q) {
+                const unsigned sw = rec[q][t / 2] >> (16 * (t % 2)); // bytes [t][0 .. 1] of the record: the block's two group scales
+                const unsigned sbyte = nv6_block(w[t][q], sw & 0xffu, (sw >> 8) & 0xffu, words[q]);
+                out_rec[(q * KS + t) / 4] |= sbyte << (8 * ((q * KS + t) % 4)); // image record byte [q][t]
+            }
+            unsigned char *const tile = img + ((size_t)b32 * ktiles + sp * KS + t) * kNv6TileBytes + lane * 16;
+            *reinterpret_cast<u32x4 *>(tile) = u32x4{words[0][0], words[0][1], words[0][2], words[0][3]};
+            *reinterpret_cast<u32x4 *>(tile + 1024) = u32x4{words[1][0], words[1][1], words[1][2], words[1][3]};
+            *reinterpret_cast<u32x4 *>(tile + 2048) = u32x4{words[0][4], words[0][5], words[1][4], words[1][5]};
+        }
+        store_rec<KS>(sc + (((size_t)b32 * nspans + sp) * 64 + lane) * (2 * KS), out_rec);
+    }
+#endif
 }
 
 int nv6_image(void *image, const void *pw, const void *ps, unsigned n, unsigned k, hipStream_t stream) {
@@ -163,12 +237,15 @@ int nv6_image(void *image, const void *pw, const void *ps, unsigned n, unsigned 
         return kErrProblemShape;
     if (nv6_elem_bytes(n, k) >= (1ull << 32))
         return kErrProblemShape; // (the kernels address the element part through one 32-bit buffer descriptor)
-    const size_t items = (size_t)((n + 31) / 32) * (k / kTileK) * 128;
-    size_t blocks = (items + 255) / 256;
-    if (blocks > 256 * 16)
-        blocks = 256 * 16;
-    hipLaunchKernelGGL(nv6_image_kernel, dim3((unsigned)blocks), dim3(256), 0, stream, (unsigned char *)image, (const u32x4 *)pw,
-                       (const unsigned char *)ps, n, k);
+    const int ks = span_tiles_for_k(k);
+    const unsigned items = (n + 31) / 32 * (k / (kTileK * ks)); // (< 2^32 / 3072: the element bytes above)
+    // a grid-stride loop over the waves' items: at most one full occupancy of the device's CUs (4 waves per workgroup, 32 waves per CU)
+    int dev = 0;
+    (void)hipGetDevice(&dev);
+    const unsigned cap = (unsigned)arch_info(dev).num_cus * 8u;
+    const unsigned blocks = std::min((items + 3) / 4, cap);
+    const auto kern = ks == 8 ? nv6_image_kernel<8> : ks == 4 ? nv6_image_kernel<4> : nv6_image_kernel<2>;
+    hipLaunchKernelGGL(kern, dim3(blocks), dim3(256), 0, stream, (unsigned char *)image, (const u32x4 *)pw, (const unsigned char *)ps, n, k, items);
     return hipGetLastError() == hipSuccess ? kOk : kErrLaunch;
 }
 

@@ -115,6 +115,7 @@ namespace petit_amd {
 struct NativeIo {
     unsigned a_format, out_format;
     const void *image = nullptr; // NVFP4 weights: their MFMA-native image (nvnative.hip), when the caller hands it over per call
+    bool transient = false;      // NVFP4 weights: the image is built per call at the front of the call's scratch (petit_gemm_nvfp4_native_transient)
 };
 int gemm_impl(int b_type, unsigned *c, const unsigned *a, const unsigned *b, const unsigned *scales, const float *global_scale, unsigned m,
               unsigned n, unsigned k, const petit_solution_hints *hints, uint64_t solution_id, const petit_epilogue *epilogue, void *call_ws,

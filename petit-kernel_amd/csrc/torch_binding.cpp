@@ -392,6 +392,51 @@ at::Tensor mul_nvfp4_native_moe(PETIT_NATIVE_MOE_ARGS) {
                                solution_id, bias, activation, a_format, a_type, out_format);
 }
 
+// NVFP4 weights on the native class without a resident image (petit_gemm_nvfp4_native_transient): the same checks and texts as petit_kernel/ops.py
+// mul_nvfp4_native_transient.  A: 16-bit [size_m, size_k] (a_format 0) or the bytes of quantised activations (a_format 8 / 6 / 4; a_type names their
+// 16-bit dtype).  The workspace (image + the native call's scratch) comes from torch's caching allocator per call.
+#define PETIT_NV_TRANSIENT_ARGS                                                                                                              \
+    const at::Tensor &A, const at::Tensor &B, const at::Tensor &s, const at::Tensor &global_scale, int64_t size_m, int64_t size_n,         \
+        int64_t size_k, int64_t solution_id, const std::optional<at::Tensor> &bias, int64_t activation, int64_t a_format, int64_t a_type,    \
+        int64_t out_format
+at::Tensor mul_nvfp4_native_transient(PETIT_NV_TRANSIENT_ARGS) {
+    const at::ScalarType dtype = native_moe_dtype(A, a_format, a_type);
+    TORCH_CHECK(A.is_cuda() && A.is_contiguous() && (a_format ? A.numel() == (int64_t)petit_quantized_activation_bytes((unsigned)size_m, (unsigned)size_k, (int)a_format)
+                                                               : A.numel() == size_m * size_k),
+                "A must be a contiguous [size_m, size_k] bfloat16 / float16 GPU tensor");
+    TORCH_CHECK(B.is_cuda() && s.is_cuda() && global_scale.is_cuda(), "all tensors must be on GPU");
+    TORCH_CHECK(B.is_contiguous() && B.numel() * B.element_size() == size_n * size_k / 2, "B does not hold size_n * size_k packed 4-bit weights");
+    TORCH_CHECK(s.is_contiguous() && s.numel() * s.element_size() == size_n * size_k / 16, "s does not hold size_n * size_k / 16 scales");
+    TORCH_CHECK(activation == 0 || activation == 1, "activation must be 0 (none) or 1 (silu_mul)");
+    TORCH_CHECK(!out_format || activation, "out_quantized needs activation='silu_mul'");
+    if (bias.has_value())
+        TORCH_CHECK(bias->is_cuda() && bias->device() == A.device() && bias->scalar_type() == dtype && bias->is_contiguous() && bias->numel() == size_n,
+                    "bias must be a contiguous [size_n] tensor of the activation dtype on the same device");
+    const c10::hip::HIPGuardMasqueradingAsCUDA guard(A.device());
+    const int64_t n_out = activation ? size_n / 2 : size_n;
+    at::Tensor c = out_format ? at::empty({(int64_t)petit_quantized_activation_bytes((unsigned)size_m, (unsigned)n_out, (int)out_format)}, A.options().dtype(at::kByte))
+                              : at::empty({size_m, n_out}, A.options().dtype(dtype));
+    const int at_code = dtype == at::kBFloat16 ? kCxxBf16 : kCxxFp16;
+    const petit_solution_hints hints{at_code, kCxxFp4, at_code, 0};
+    const uint64_t sid = solution_id == -2   ? PETIT_SOLUTION_AUTO_NATIVE_MXFP8
+                         : solution_id == -3 ? PETIT_SOLUTION_AUTO_NATIVE_MXFP4
+                         : solution_id == -4 ? PETIT_SOLUTION_AUTO_NATIVE_MXFP6
+                         : solution_id < 0   ? PETIT_SOLUTION_AUTO
+                                             : (uint64_t)solution_id;
+    const petit_epilogue epi{bias.has_value() ? bias->data_ptr() : nullptr, (int32_t)activation, 0};
+    const petit_epilogue *epi_p = (bias.has_value() || activation) ? &epi : nullptr;
+    const petit_native_args na{sizeof(petit_native_args), (int32_t)a_format, (int32_t)out_format, 0};
+    const uint64_t ws_bytes = petit_gemm_nvfp4_native_transient_workspace_bytes(&hints, (unsigned)size_m, (unsigned)size_n, (unsigned)size_k, sid, epi_p, &na);
+    at::Tensor ws = at::empty({(int64_t)ws_bytes}, A.options().dtype(at::kByte));
+    const int rc = petit_gemm_nvfp4_native_transient(c.data_ptr(), A.data_ptr(), (const unsigned *)B.data_ptr(), (const unsigned *)s.data_ptr(),
+                                                     (const float *)global_scale.data_ptr(), (unsigned)size_m, (unsigned)size_n, (unsigned)size_k, &hints,
+                                                     sid, epi_p, &na, ws_bytes ? ws.data_ptr() : nullptr, ws_bytes, stream_of(A));
+    TORCH_CHECK(rc != PETIT_ERROR_PROBLEM_SHAPE, "Incompatible problem shape (m=", size_m, ", n=", size_n, ", k=", size_k, ")");
+    TORCH_CHECK(rc != PETIT_ERROR_KERNEL_SHAPE, "No kernel implementation for solution_id=", solution_id < 0 ? std::to_string(solution_id) : std::to_string((int64_t)sid), ".");
+    TORCH_CHECK(rc == PETIT_OK, "mul_nvfp4_native_transient: ", petit_error_string(rc));
+    return c;
+}
+
 // Shape functions for the Meta key (FakeTensor / torch.compile tracing, torch.export): outputs of the right shape, dtype and
 // device, nothing launched -- the ops trace as opaque calls instead of breaking the graph.
 at::Tensor repack_nvfp4_meta(const at::Tensor &q, int64_t n, int64_t k) { return at::empty({n / kLayoutN, k * kLayoutN / kPack}, q.options()); }
@@ -413,6 +458,13 @@ at::Tensor mul_a16_moe_indexed_meta(PETIT_MOE_INDEXED_ARGS) {
     return at::empty({c_rows < 0 ? m : c_rows, activation ? n / 2 : n}, A.options());
 }
 void mul_a16_moe_indexed_out_meta(const at::Tensor &, PETIT_MOE_INDEXED_ARGS) {}
+at::Tensor mul_nvfp4_native_transient_meta(PETIT_NV_TRANSIENT_ARGS) {
+    const at::ScalarType dtype = native_moe_dtype(A, a_format, a_type);
+    const int64_t n_out = activation ? size_n / 2 : size_n;
+    if (out_format)
+        return at::empty({(int64_t)petit_quantized_activation_bytes((unsigned)size_m, (unsigned)n_out, (int)out_format)}, A.options().dtype(at::kByte));
+    return at::empty({size_m, n_out}, A.options().dtype(dtype));
+}
 at::Tensor mul_native_moe_meta(PETIT_NATIVE_MOE_ARGS) {
     const at::ScalarType dtype = native_moe_dtype(A, a_format, a_type);
     const int64_t n_out = activation ? size_n / 2 : size_n;
@@ -459,6 +511,8 @@ TORCH_LIBRARY(petit_kernel, m) {
     "int a_format=0, int a_type=5, int out_format=0"
     m.def("mul_mxfp4_native_moe(" PETIT_NATIVE_MOE_SCHEMA ") -> Tensor");
     m.def("mul_nvfp4_native_moe(" PETIT_NATIVE_MOE_SCHEMA ") -> Tensor");
+    m.def("mul_nvfp4_native_transient(Tensor A, Tensor B, Tensor s, Tensor global_scale, int size_m, int size_n, int size_k, int solution_id=-2, "
+          "Tensor? bias=None, int activation=0, int a_format=0, int a_type=5, int out_format=0) -> Tensor");
     m.def("moe_align_device(Tensor topk_ids, int num_experts) -> (Tensor, Tensor, Tensor)");
     m.def("moe_combine(Tensor slot_out, Tensor topk_weights, Tensor topk_ids, int num_experts) -> Tensor");
     // round 3's op name (scales promised inside fp16's range): an alias of mul_mxfp4_a16 for one more round -- the kernels test the range themselves
@@ -480,6 +534,7 @@ TORCH_LIBRARY(petit_kernel, m) {
     m.impl("mul_mxfp4_a16_moe_indexed_out", &mul_mxfp4_a16_moe_indexed_out); \
     m.impl("mul_mxfp4_native_moe", &mul_mxfp4_native_moe);      \
     m.impl("mul_nvfp4_native_moe", &mul_nvfp4_native_moe);      \
+    m.impl("mul_nvfp4_native_transient", &mul_nvfp4_native_transient); \
     m.impl("moe_align_device", &moe_align_device);              \
     m.impl("moe_combine", &moe_combine);
 TORCH_LIBRARY_IMPL(petit_kernel, CUDA, m) { PETIT_IMPL_REAL(m) }
@@ -499,6 +554,7 @@ TORCH_LIBRARY_IMPL(petit_kernel, Meta, m) {
     m.impl("mul_mxfp4_a16_moe_indexed_out", &mul_a16_moe_indexed_out_meta);
     m.impl("mul_mxfp4_native_moe", &mul_native_moe_meta);
     m.impl("mul_nvfp4_native_moe", &mul_native_moe_meta);
+    m.impl("mul_nvfp4_native_transient", &mul_nvfp4_native_transient_meta);
     m.impl("moe_align_device", &moe_align_device_meta);
     m.impl("moe_combine", &moe_combine_meta);
 }

@@ -153,6 +153,22 @@ def mul_nvfp4_native_moe(a, images: torch.Tensor, global_scales: torch.Tensor, e
                                       solution_id, bias, activation, out_quantized)
 
 
+def mul_nvfp4_native_transient(a, b: torch.Tensor, s: torch.Tensor, global_scale: torch.Tensor, size_m: int, size_n: int, size_k: int,
+                               solution_id: int = SOLUTION_AUTO_NATIVE_MXFP8, bias: torch.Tensor = None, activation: str = None,
+                               out_quantized: str = None):
+    # NVFP4 weights on the native class WITHOUT a resident image (include/petit_amd.h "Without a resident image"): b / s are the packed tensors of
+    # mul_nvfp4_a16; each call builds the image into a per-call workspace and runs on it -- bit for bit mul_nvfp4_a16(..., -2 / -3 / -4) with the image
+    # attached, or mul_nvfp4_native on the image; `a` a 16-bit tensor or QuantizedActivations
+    return _impl.mul_nvfp4_native_transient(a, b, s, global_scale, size_m, size_n, size_k, solution_id, bias, activation, out_quantized)
+
+
+def nvfp4_native_transient_workspace_bytes(size_m: int, size_n: int, size_k: int, solution_id: int = SOLUTION_AUTO_NATIVE_MXFP8,
+                                           dtype: torch.dtype = torch.bfloat16, activation: str = None, a_format: str = None,
+                                           out_quantized: str = None) -> int:
+    # the per-call workspace of mul_nvfp4_native_transient: the image (rounded up to 256 bytes), then the native call's own scratch
+    return ops.nvfp4_native_transient_workspace_bytes(size_m, size_n, size_k, solution_id, dtype, activation, a_format, out_quantized)
+
+
 def quantize_activation_rows(a: torch.Tensor, fmt: str = "mxfp8", row_index: torch.Tensor = None, rows: int = None) -> QuantizedActivations:
     # quantize_activations of the rows row_index names (None: all rows); an index outside the matrix gives a zero row
     return ops.quantize_activation_rows(a, fmt, row_index, rows)
@@ -208,6 +224,8 @@ __all__ = [
     "nvfp4_native_image",
     "attach_nvfp4_native",
     "mul_nvfp4_native",
+    "mul_nvfp4_native_transient",
+    "nvfp4_native_transient_workspace_bytes",
     "QuantizedActivations",
     "SOLUTION_AUTO",
     "SOLUTION_AUTO_NATIVE_MXFP8",

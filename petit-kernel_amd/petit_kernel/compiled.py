@@ -161,3 +161,20 @@ def mul_nvfp4_native_moe(A, images, global_scales, expert_offsets, size_m, size_
                          c_rows=None, solution_id=-2, bias=None, activation=None, out_quantized=None):
     return _mul_native_moe("nv", A, images, None, global_scales, expert_offsets, size_m, size_n, size_k, num_experts, a_row_index, c_row_index,
                            c_rows, solution_id, bias, activation, out_quantized)
+
+
+def mul_nvfp4_native_transient(A, B, s, global_scale, size_m, size_n, size_k, solution_id=-2, bias=None, activation=None, out_quantized=None):
+    from .ops import _QFORMATS, QuantizedActivations
+    if out_quantized is not None and out_quantized not in _QFORMATS:
+        raise RuntimeError("out_quantized must be None, 'mxfp8', 'mxfp6' or 'mxfp4'")
+    out_fmt = _QFORMATS[out_quantized] if out_quantized else 0
+    if isinstance(A, QuantizedActivations):
+        if A.m != size_m or A.k != size_k:
+            raise RuntimeError(f"quantised activations are [{A.m}, {A.k}], the call says [{size_m}, {size_k}]")
+        a_t, a_fmt, dtype = A.data, _QFORMATS[A.fmt], A.dtype
+    else:
+        a_t, a_fmt, dtype = A, 0, A.dtype
+    a_type = 5 if dtype == torch.bfloat16 else 4
+    c = torch.ops.petit_kernel.mul_nvfp4_native_transient(a_t, B, s, global_scale, size_m, size_n, size_k, _native_sid(solution_id), bias,
+                                                          _act(activation), a_fmt, a_type, out_fmt)
+    return QuantizedActivations(c, size_m, size_n // 2, out_quantized, dtype) if out_fmt else c

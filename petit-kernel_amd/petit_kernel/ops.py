@@ -550,6 +550,80 @@ def mul_nvfp4_native(A, image: torch.Tensor, global_scale, size_m, size_n, size_
     return QuantizedActivations(c, size_m, size_n // 2, out_quantized, dtype) if out_fmt else c
 
 
+def _nv_transient_args(A, size_m, size_k, activation, out_quantized):
+    """(activation tensor, dtype, a_format, device, act, out_format) of a transient call, with the checks mul_nvfp4_native makes."""
+    if isinstance(A, QuantizedActivations):
+        _check(A.m == size_m and A.k == size_k, f"quantised activations are [{A.m}, {A.k}], the call says [{size_m}, {size_k}]")
+        a_t, dtype, a_fmt, dev = A.data, A.dtype, _QFORMATS[A.fmt], A.data.device
+    else:
+        _check(A.is_cuda and A.is_contiguous() and A.numel() == size_m * size_k and A.dtype in (torch.bfloat16, torch.float16),
+               "A must be a contiguous [size_m, size_k] bfloat16 / float16 GPU tensor")
+        a_t, dtype, a_fmt, dev = A, A.dtype, 0, A.device
+    _check(activation in _ACTIVATIONS, f"activation must be one of {sorted(k for k in _ACTIVATIONS if k)} or None")
+    _check(out_quantized is None or out_quantized in _QFORMATS, "out_quantized must be None, 'mxfp8', 'mxfp6' or 'mxfp4'")
+    act = _ACTIVATIONS[activation]
+    out_fmt = _QFORMATS[out_quantized] if out_quantized else 0
+    _check(not out_fmt or act, "out_quantized needs activation='silu_mul'")
+    return a_t, dtype, a_fmt, dev, act, out_fmt
+
+
+def nvfp4_native_transient_workspace_bytes(size_m, size_n, size_k, solution_id=SOLUTION_AUTO_NATIVE_MXFP8, dtype=torch.bfloat16, activation=None,
+                                           a_format=None, out_quantized=None) -> int:
+    """Workspace bytes of mul_nvfp4_native_transient (petit_gemm_nvfp4_native_transient_workspace_bytes): the image rounded up to 256 bytes, then the
+    native call's own scratch; 0 when the call would be refused.  a_format: the format of pre-quantised activations (None: 16-bit)."""
+    _check(activation in _ACTIVATIONS, f"activation must be one of {sorted(k for k in _ACTIVATIONS if k)} or None")
+    _check(a_format is None or a_format in _QFORMATS, "a_format must be None, 'mxfp8', 'mxfp6' or 'mxfp4'")
+    _check(out_quantized is None or out_quantized in _QFORMATS, "out_quantized must be None, 'mxfp8', 'mxfp6' or 'mxfp4'")
+    a_type = _lib.CXX_DTYPE_BF16 if dtype == torch.bfloat16 else _lib.CXX_DTYPE_FP16
+    hints = _CHints(a_type, _lib.CXX_DTYPE_FP4_E2M1, a_type, 0)
+    act = _ACTIVATIONS[activation]
+    epi = _lib.Epilogue(None, act, 0)
+    na = _lib.NativeArgs(C.sizeof(_lib.NativeArgs), _QFORMATS[a_format] if a_format else 0, _QFORMATS[out_quantized] if out_quantized else 0, 0)
+    return int(_lib.lib.petit_gemm_nvfp4_native_transient_workspace_bytes(C.byref(hints), size_m, size_n, size_k,
+                                                                          C.c_uint64(_c_solution_id(solution_id, native_ok=True)),
+                                                                          C.byref(epi) if act else None, C.byref(na)))
+
+
+def mul_nvfp4_native_transient(A, B, s, global_scale, size_m, size_n, size_k, solution_id=SOLUTION_AUTO_NATIVE_MXFP8, bias=None, activation=None,
+                               out_quantized=None):
+    """NVFP4 weights on the block-scaled MFMA WITHOUT a resident image (petit_gemm_nvfp4_native_transient): B / s are the packed tensors
+    mul_nvfp4_a16 takes; the call builds the image into a workspace it takes from torch's caching allocator, then runs the native call on it.
+    Bit for bit mul_nvfp4_a16(..., solution_id) with the image attached (16-bit A and result) / mul_nvfp4_native on the image (QuantizedActivations
+    A, out_quantized).  Everything else as mul_nvfp4_native."""
+    a_t, dtype, a_fmt, dev, act, out_fmt = _nv_transient_args(A, size_m, size_k, activation, out_quantized)
+    _check(B.is_cuda and s.is_cuda and global_scale.is_cuda, "all tensors must be on GPU")
+    _check(B.is_contiguous() and B.numel() * B.element_size() == size_n * size_k // 2, "B does not hold size_n * size_k packed 4-bit weights")
+    _check(s.is_contiguous() and s.numel() * s.element_size() == size_n * size_k // 16, "s does not hold size_n * size_k / 16 scales")
+    a_type = _lib.CXX_DTYPE_BF16 if dtype == torch.bfloat16 else _lib.CXX_DTYPE_FP16
+    hints = _CHints(a_type, _lib.CXX_DTYPE_FP4_E2M1, a_type, 0)
+    sid = _c_solution_id(solution_id, native_ok=True)
+    epi = None
+    if bias is not None or act:
+        if bias is not None:
+            _check(bias.is_cuda and bias.device == dev and bias.dtype == dtype and bias.is_contiguous() and bias.numel() == size_n,
+                   "bias must be a contiguous [size_n] tensor of the activation dtype on the same device")
+        epi = _lib.Epilogue(bias.data_ptr() if bias is not None else None, act, 0)
+    na = _lib.NativeArgs(C.sizeof(_lib.NativeArgs), a_fmt, out_fmt, 0)
+    epi_p = C.byref(epi) if epi is not None else None
+    if out_fmt:
+        c = torch.empty(int(_lib.lib.petit_quantized_activation_bytes(size_m, size_n // 2, out_fmt)), dtype=torch.uint8, device=dev)
+    else:
+        c = torch.empty((size_m, size_n // 2 if act else size_n), dtype=dtype, device=dev)
+    ws_bytes = int(_lib.lib.petit_gemm_nvfp4_native_transient_workspace_bytes(C.byref(hints), size_m, size_n, size_k, C.c_uint64(sid), epi_p,
+                                                                              C.byref(na)))
+    ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev) if ws_bytes else None
+    with torch.cuda.device(dev):
+        err = _lib.lib.petit_gemm_nvfp4_native_transient(_ptr(c), _ptr(a_t), _ptr(B), _ptr(s), _ptr(global_scale), size_m, size_n, size_k,
+                                                         C.byref(hints), C.c_uint64(sid), epi_p, C.byref(na), _ptr(ws) if ws is not None else None,
+                                                         C.c_uint64(ws_bytes), C.c_void_p(torch.cuda.current_stream(dev).cuda_stream))
+    if err == _lib.PETIT_ERROR_PROBLEM_SHAPE:
+        raise RuntimeError(f"Incompatible problem shape (m={size_m}, n={size_n}, k={size_k})")
+    if err == _lib.PETIT_ERROR_KERNEL_SHAPE:
+        raise RuntimeError(f"No kernel implementation for solution_id={solution_id}.")
+    _raise_on(err, "mul_nvfp4_native_transient")
+    return QuantizedActivations(c, size_m, size_n // 2, out_quantized, dtype) if out_fmt else c
+
+
 # --- grouped launch (include/petit_amd.h "Grouped launch"; no counterpart in the reference) ---------------------------------
 
 def mul_fp4_a16_grouped(kind: str, A: torch.Tensor, members, size_m: int, size_k: int, solution_id: int = -1) -> list:
