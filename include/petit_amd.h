@@ -126,10 +126,18 @@ int petit_gemm_mxfp4_fp16_grid(unsigned *c, const unsigned *a, const unsigned *b
  *   c[m][j] = round16( silu(y[m][j]) * y[m][j + n/2] ),   silu(x) = x / (1 + exp(-x)).
  * Needs n % 32 == 0 and a kernel with an even number of n-tiles per wave: PETIT_SOLUTION_AUTO picks one;
  * an explicit id without that property (or with a cross-workgroup K split) returns PETIT_ERROR_KERNEL_SHAPE.
+ * activation = PETIT_ACTIVATION_SWIGLU_OAI (gpt-oss's gated MLP): the same contract -- c is [m][n/2], column j of the first
+ * half of N is gate and column j + n/2 is up, y as above in f32 -- with the clamped formula
+ *   g = min(y[m][j], 7.0f),  u = min(max(y[m][j + n/2], -7.0f), 7.0f),
+ *   c[m][j] = round16( g / (1 + exp(-1.702f * g)) * (u + 1) ),   rounded once.
+ * alpha = 1.702 and limit = 7.0 are gpt-oss's own and fixed by the activation value (`reserved` keeps its meaning: 0).
+ * Every shape rule, pick and refusal of SILU_MUL holds for it unchanged (n % 32 == 0, the tile pairing or a cross-workgroup
+ * K split, the quantised output's n % 512 == 0); a gate of -inf gives -0 / 0, NaN and +-inf propagate as in the SiLU form.
  * Any other activation value returns PETIT_ERROR_BAD_ARGUMENT.
  */
 #define PETIT_ACTIVATION_NONE 0
 #define PETIT_ACTIVATION_SILU_MUL 1
+#define PETIT_ACTIVATION_SWIGLU_OAI 2
 typedef struct petit_epilogue {
     const void *bias;
     int32_t activation;
@@ -299,7 +307,8 @@ uint64_t petit_gemm_workspace_bytes(const petit_solution_hints *hints, unsigned 
                                     uint64_t solution_id);
 /* The same with the epilogue of the call taken into account: PETIT_SOLUTION_AUTO resolves differently under
  * PETIT_ACTIVATION_SILU_MUL (unsplit, only kernels that hold a gate / up tile pair per wave qualify; with a cross-workgroup K
- * split any kernel does -- the slabs hold the plain [m][n] product and the reduce pass applies SiLU-mul). */
+ * split any kernel does -- the slabs hold the plain [m][n] product and the reduce pass applies SiLU-mul); PETIT_ACTIVATION_SWIGLU_OAI
+ * resolves exactly as SILU_MUL does. */
 uint64_t petit_gemm_workspace_bytes_ex(const petit_solution_hints *hints, unsigned m, unsigned n, unsigned k,
                                        uint64_t solution_id, const petit_epilogue *epilogue);
 int petit_set_workspace(void *device_ptr, uint64_t bytes);
@@ -350,7 +359,8 @@ int petit_get_mxfp4_default_class(void);
  *              petit_quantize_activations() (once, for any number of GEMMs that share the input: q / k / v, gate / up) or by
  *              a producer GEMM's epilogue (next item).  The bytes are opaque ("petit-qact/1": k-tile-major, the 32x32x64
  *              kernels' operand order); petit_quantized_activation_bytes() sizes them.  0: `a` is the 16-bit [m][k] matrix.
- *   out_format 8 / 6 / 4, with epilogue->activation = PETIT_ACTIVATION_SILU_MUL: `c` receives silu(y_gate) * y_up QUANTISED for the
+ *   out_format 8 / 6 / 4, with epilogue->activation = PETIT_ACTIVATION_SILU_MUL (or _SWIGLU_OAI: its value instead, quantised from f32 by
+ *              the same rule): `c` receives silu(y_gate) * y_up QUANTISED for the
  *              next GEMM (m, k' = n / 2) -- petit_quantized_activation_bytes(m, n / 2, out_format) bytes -- instead of the
  *              16-bit [m][n/2] matrix: gate_up -> SiLU-mul -> down of a gated MLP in two launches.  Needs n % 512 == 0 and a
  *              kernel with 128 x 256 workgroup tiles (the sentinels pick one).  Quantised from the f32 result with the
@@ -477,7 +487,8 @@ int petit_gemm_fp4_fp16_grouped(const petit_group_member *members, unsigned coun
  *   expert_offsets  int32 device array [E + 1]: offsets[0] = 0, non-decreasing, offsets[E] = m.  The host never reads it: the call makes no
  *                   host sync and may be captured in a graph whose replays route differently.
  *   epilogue        optional: bias is read as [E][n] in c's dtype; activation = PETIT_ACTIVATION_SILU_MUL takes each expert's weight as
- *                   [gate; up] along N (vLLM / SGLang's w13) and writes c as [m][n/2].
+ *                   [gate; up] along N (vLLM / SGLang's w13) and writes c as [m][n/2]; PETIT_ACTIVATION_SWIGLU_OAI the same with gpt-oss's clamped
+ *                   formula (a gpt-oss checkpoint stores gate / up rows interleaved: de-interleave them first, petit_kernel.gptoss does).
  *   solution_id     PETIT_SOLUTION_AUTO, or the id of a kernel that has a MoE form (a decode, staged streaming or tiled kernel of a curated
  *                   subset; no K split): the dense ids, petit_describe_solution names them.  Within an expert the result equals, bit for bit,
  *                   a dense call on that expert's rows with the same id.
@@ -549,12 +560,12 @@ int petit_moe_combine(void *out, const void *slot_out, const float *topk_weights
  *                   petit_gemm_native_moe_workspace_bytes().  a_format 8 / 6 / 4: a holds the m GROUPED rows already quantised
  *                   (petit_quantize_activations_rows, or a producer's out_format), a_row_index must be null: one launch, no workspace.
  *   c               16-bit [c_rows][n] ([c_rows][n/2] with SiLU-mul), row c_row_index[r] (null: r) for grouped row r; an index outside
- *                   [0, c_rows) stores nothing.  native->out_format 8 / 6 / 4 (SiLU-mul only, n % 512 == 0, c_row_index null): c receives
+ *                   [0, c_rows) stores nothing.  native->out_format 8 / 6 / 4 (SiLU-mul or SwiGLU-OAI only, n % 512 == 0, c_row_index null): c receives
  *                   the m grouped rows of [m][n/2] quantised for the next launch (petit_quantized_activation_bytes(m, n / 2, format)).
  *   Row limit: every epilogue stores rows of its own expert only; rows past expert_offsets[E] are not computed.  Within an expert the
  *   result equals, bit for bit, petit_gemm_mxfp4_native / petit_gemm_nvfp4_native on that expert's rows with the same id.
  * Shapes and errors as petit_gemm_fp4_fp16_moe_ex and petit_gemm_mxfp4_native; also PETIT_ERROR_BAD_ARGUMENT for a_format with an
- * a_row_index, out_format with a c_row_index or without SiLU-mul, misaligned pointers; PETIT_ERROR_KERNEL_SHAPE for a workspace below the
+ * a_row_index, out_format with a c_row_index or without a gated activation, misaligned pointers; PETIT_ERROR_KERNEL_SHAPE for a workspace below the
  * query; PETIT_ERROR_PROBLEM_SHAPE when the quantised rows reach 2^32 bytes (32-bit offsets).  m == 0 returns PETIT_OK.  No host sync:
  * capturable.  The queries return 0 for a call that would be refused; the workspace query also 0 with a_format set.
  * petit_quantize_activations_rows: petit_quantize_activations of the gathered rows (layout row r from row a_row_index[r] of a [a_rows][k];

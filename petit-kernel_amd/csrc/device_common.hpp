@@ -269,12 +269,16 @@ __device__ __forceinline__ void c_tile_store(const u32x4 *img, void *c, unsigned
     }
 }
 
-// SiLU-mul epilogue (petit_epilogue.activation = 1): `gate` holds 4 consecutive columns j of the first half of
-// the GEMM's N, `up` the same columns of the second half; out[j] = silu(y_gate[j]) * y_up[j], y = acc*gs + bias,
-// rounded once.  bias (if any) spans the full N: gate part at n, up part at n + n_half.
+// Gated epilogue (petit_epilogue.activation = 1 / 2, `act`, wave-uniform): `gate` holds 4 consecutive columns j of the
+// first half of the GEMM's N, `up` the same columns of the second half, y = acc*gs + bias; rounded once.
+//   1 (SiLU-mul):   out[j] = silu(y_gate[j]) * y_up[j]
+//   2 (SwiGLU-OAI): g = min(y_gate[j], 7), u = clamp(y_up[j], -7, 7), out[j] = g * sigmoid(1.702 g) * (u + 1)  (gpt-oss)
+// bias (if any) spans the full N: gate part at n, up part at n + n_half.  The clamps are compares and selects, not
+// v_min / v_max, so that a NaN goes through them as it goes through the SiLU form; g -> -inf gives g / inf = -0.
+constexpr float kSwigluOaiAlpha = 1.702f, kSwigluOaiLimit = 7.0f;
 template <class AT>
 __device__ __forceinline__ f32x4 silu_mul4(const f32x4 gate, const f32x4 up, const float gs, const void *bias, const unsigned n,
-                                           const unsigned n_half) {
+                                           const unsigned n_half, const unsigned act) {
     float bg[4] = {0.f, 0.f, 0.f, 0.f}, bu[4] = {0.f, 0.f, 0.f, 0.f};
     if (bias) {
         auto load4 = [&](unsigned col, float *b) {
@@ -293,25 +297,34 @@ __device__ __forceinline__ f32x4 silu_mul4(const f32x4 gate, const f32x4 up, con
         load4(n, bg);
         load4(n + n_half, bu);
     }
+    // One body for both kinds, steered by wave-uniform scalars: for SiLU-mul the limit is +inf (no compare is ever true, NaN included), alpha
+    // is 1 (x * 1 is exact) and u passes through a select, so its value path is the fma / exp / divide / multiply it always was, bit for bit.
+    // Two forms with a branch were built and measured first (profiles/moe_gptoss.md): the compiler duplicates the epilogue behind it, which
+    // grew the large kernels' code by 45-70 % and moved their register allocation (scratch accesses gained inside two native K loops).
+    const bool oai = act == 2u;
+    const float hi = oai ? kSwigluOaiLimit : __builtin_inff(), lo = -hi, alpha = oai ? kSwigluOaiAlpha : 1.0f;
     f32x4 o;
 #pragma unroll
     for (int i = 0; i < 4; ++i) {
-        const float g = __builtin_fmaf(gate[i], gs, bg[i]), u = __builtin_fmaf(up[i], gs, bu[i]);
-        o[i] = g / (1.0f + __expf(-g)) * u;
+        const float yg = __builtin_fmaf(gate[i], gs, bg[i]), yu = __builtin_fmaf(up[i], gs, bu[i]);
+        const float g = yg > hi ? hi : yg;
+        const float uc = yu > hi ? hi : (yu < lo ? lo : yu);
+        const float u = oai ? uc + 1.0f : uc;
+        o[i] = g / (1.0f + __expf(-(alpha * g))) * u;
     }
     return o;
 }
 template <class AT>
 __device__ __forceinline__ uint2 finish4_silu_mul(const f32x4 gate, const f32x4 up, const float gs, const void *bias,
-                                                  const unsigned n, const unsigned n_half) {
-    const f32x4 o = silu_mul4<AT>(gate, up, gs, bias, n, n_half);
+                                                  const unsigned n, const unsigned n_half, const unsigned act) {
+    const f32x4 o = silu_mul4<AT>(gate, up, gs, bias, n, n_half, act);
     uint2 r;
     r.x = pack2(AT{}, o[0], o[1]);
     r.y = pack2(AT{}, o[2], o[3]);
     return r;
 }
 
-// Logical n-tile L of a kernel's grid -> physical n-tile of W.  Plain GEMM: identity.  SiLU-mul: consecutive
+// Logical n-tile L of a kernel's grid -> physical n-tile of W.  Plain GEMM: identity.  Gated (act = 1 or 2): consecutive
 // logical tiles (2p, 2p+1) are the gate tile p and the up tile p + ntiles/2, so that one wave (even NT) holds both.
 __device__ __forceinline__ unsigned physical_tile(unsigned l, unsigned ntiles, unsigned act) {
     return act ? (l >> 1) + (l & 1u) * (ntiles >> 1) : l;

@@ -172,7 +172,7 @@ static GemmCall rows_of(const GemmCall &g, unsigned row0, unsigned rows, bool au
     GemmCall r = g;
     r.m = rows;
     if (g.c) { // (a query has no matrices)
-        const bool act = g.epilogue && g.epilogue->activation == PETIT_ACTIVATION_SILU_MUL;
+        const bool act = g.epilogue && activation_gated(g.epilogue->activation);
         r.c = (unsigned *)((char *)g.c + (size_t)row0 * (act ? g.n / 2 : g.n) * sizeof(uint16_t));
         r.a = (const unsigned *)((const char *)g.a + (size_t)row0 * g.k * sizeof(uint16_t));
     }
@@ -230,10 +230,9 @@ GemmPlan plan_gemm(const GemmCall &g, const Scratch &s, bool part) {
     const NativeIo *io = g.io;
     const petit_solution_hints *hints = g.hints;
     const unsigned m = g.m, n = g.n, k = g.k;
-    if (epilogue && ((epilogue->activation != PETIT_ACTIVATION_NONE && epilogue->activation != PETIT_ACTIVATION_SILU_MUL) ||
-                     epilogue->reserved != 0))
+    if (epilogue && (!activation_known(epilogue->activation) || epilogue->reserved != 0))
         return refuse(kErrBadArgument); // reject what a newer caller might ask for
-    const bool act = epilogue && epilogue->activation == PETIT_ACTIVATION_SILU_MUL;
+    const bool act = epilogue && activation_gated(epilogue->activation); // SiLU-mul or SwiGLU-OAI: one set of rules, the kind goes to the epilogue
     const unsigned a_format = io ? io->a_format : 0u, out_format = io ? io->out_format : 0u;
     if ((a_format != 0 && a_format != 8 && a_format != 6 && a_format != 4) || (out_format != 0 && out_format != 8 && out_format != 6 && out_format != 4))
         return refuse(kErrBadArgument);
@@ -417,7 +416,8 @@ static int launch(const GemmCall &g, const LaunchPlan &p) {
     args.bias = g.epilogue ? g.epilogue->bias : nullptr;
     args.qa = a_format ? (const void *)g.a : nullptr, args.qa_format = a_format, args.out_format = g.io ? g.io->out_format : 0u;
     args.workspace = (float *)p.ws;
-    args.act = p.act ? 1u : 0u, args.reduce_act = p.reduce_act ? 1u : 0u;
+    const unsigned kind = g.epilogue ? (unsigned)g.epilogue->activation : 0u; // 1 SiLU-mul / 2 SwiGLU-OAI where p.act or p.reduce_act
+    args.act = p.act ? kind : 0u, args.reduce_act = p.reduce_act ? kind : 0u;
     const SolutionEntry *entry = p.entry;
     int rc = entry->launch(args, p.splitk, (hipStream_t)g.stream);
     if (rc == kErrSplitCollapsed) {
@@ -439,7 +439,7 @@ static int launch(const GemmCall &g, const LaunchPlan &p) {
                     return kErrKernelShape;
             }
         }
-        args.act = 1u, args.reduce_act = 0u;
+        args.act = kind, args.reduce_act = 0u;
         rc = entry->launch(args, 1, (hipStream_t)g.stream);
     }
     return rc;

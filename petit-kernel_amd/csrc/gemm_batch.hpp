@@ -481,7 +481,7 @@ __global__ __launch_bounds__(Cfg::kThreads) void gemm_batch_kernel(const void *a
                     u = acc[mt][nt + 1 < NT ? nt + 1 : nt];
                 }
                 const unsigned n_half = arg_n >> 1, n = (ntile >> 1) * 16 + g * 4;
-                *reinterpret_cast<uint2 *>((char *)arg_c + ((size_t)m * n_half + n) * 2) = finish4_silu_mul<AT>(v, u, gs, arg_bias, n, n_half);
+                *reinterpret_cast<uint2 *>((char *)arg_c + ((size_t)m * n_half + n) * 2) = finish4_silu_mul<AT>(v, u, gs, arg_bias, n, n_half, arg_act);
             }
         } else {
             const unsigned n = ntile * 16 + g * 4;

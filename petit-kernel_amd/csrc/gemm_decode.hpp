@@ -422,7 +422,7 @@ __device__ __forceinline__ void gemm_decode_body(const void *arg_w, const void *
                     if ((nt & 1u) == 0) { // logical tiles (nt, nt + 1) = gate / up halves of output tile ntile / 2
                         const unsigned n_half = arg_n >> 1, n = (ntile >> 1) * 16 + q * 4;
                         *reinterpret_cast<uint2 *>((char *)arg_c + ((size_t)cm * n_half + n) * 2) =
-                            finish4_silu_mul<AT>(gather(nt), gather(nt + 1), gs, arg_bias, n, n_half);
+                            finish4_silu_mul<AT>(gather(nt), gather(nt + 1), gs, arg_bias, n, n_half, arg_act);
                     }
                 }
             } else {

@@ -327,7 +327,7 @@ __global__ __launch_bounds__(Cfg::kThreads) void gemm_mid_kernel(const void *arg
                     u += red[q * kItems + item + 64];
                 const unsigned n_half = arg_n >> 1, n = (ntile >> 1) * 16 + (il >> 4) * 4;
                 *reinterpret_cast<uint2 *>((char *)arg_c + ((size_t)m * n_half + n) * 2) =
-                    finish4_silu_mul<AT>(v, u, gs, arg_bias, n, n_half);
+                    finish4_silu_mul<AT>(v, u, gs, arg_bias, n, n_half, arg_act);
             }
         } else {
             const unsigned n = ntile * 16 + (il >> 4) * 4;

@@ -340,7 +340,7 @@ __global__ __launch_bounds__(Cfg::kThreads, Cfg::kMinWavesPerSimd) void gemm_nat
         return;
     }
     const float gs = *p.gs;
-    if (p.act) { // SiLU-mul: tiles (nt, nt + 1) are the gate / up halves of output tile (nt0 + nt) / 2
+    if (p.act) { // SiLU-mul / SwiGLU-OAI: tiles (nt, nt + 1) are the gate / up halves of output tile (nt0 + nt) / 2
         if constexpr (NTW % 2 == 0) {
             const unsigned n_half = p.n >> 1;
 #pragma unroll
@@ -351,7 +351,7 @@ __global__ __launch_bounds__(Cfg::kThreads, Cfg::kMinWavesPerSimd) void gemm_nat
                     const unsigned n = ((nt0 + nt) >> 1) * 16 + g * 4;
                     if (m < p.m && (unsigned)nt < valid_nt)
                         *reinterpret_cast<uint2 *>((char *)p.c + ((size_t)m * n_half + n) * 2) =
-                            finish4_silu_mul<AT>(acc[mt][nt], acc[mt][nt + 1], gs, p.bias, n, n_half);
+                            finish4_silu_mul<AT>(acc[mt][nt], acc[mt][nt + 1], gs, p.bias, n, n_half, p.act);
                 }
         }
         return;

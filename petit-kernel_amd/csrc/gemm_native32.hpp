@@ -205,12 +205,12 @@ __global__ __launch_bounds__(256) void quantize_act32_fp6_kernel(const void *a, 
         *reinterpret_cast<unsigned *>(qs + tile_row * 4) = sbyte | (s1 << 8) | (s2 << 16) | (s3 << 24);
 }
 
-// The SiLU-mul epilogue as a PRODUCER of quantised activations (out_format 8 / 4; 128 x 256 workgroup tiles only: NP = 2, four waves).
+// The gated epilogue (SiLU-mul, or SwiGLU-OAI: `act`) as a PRODUCER of quantised activations (out_format 8 / 4; 128 x 256 workgroup tiles only: NP = 2, four waves).
 // A gated MLP is gate_up -> SiLU-mul -> down; with 16-bit hand-over the native path pays a quantiser launch in front of each GEMM
 // (5-6 us each at M = 512, 15-19 % of `o`).  Here the gate_up kernel writes what `down`'s kernel reads: out[m][j], j < N/2, quantised
 // per 32 columns to MXFP8 / MXFP4 with the quantiser's own rule (E8M0 scale from the block maximum), in the k-tile-major scratch
 // layout described above -- a 256-column workgroup tile produces exactly ONE 128-column k-tile of the consumer for its 128 rows, a
-// contiguous 8 / 16 KiB run plus 512 scale bytes.  The values are quantised from the f32 SiLU-mul result (one rounding, where
+// contiguous 8 / 16 KiB run plus 512 scale bytes.  The values are quantised from the f32 activation result (one rounding, where
 // "round to 16 bit, then quantise" has two).
 // m_total is the layout's row count (its stride), m_lim the row limit: rows at or past it are not stored (a routed-expert launch: the
 // next expert's rows, which another workgroup writes).
@@ -223,7 +223,7 @@ __device__ __forceinline__ void n32_silu_quant_epilogue(const f32x16 (&acc)[MB][
                                                         const unsigned m_total, const unsigned n_half, const unsigned m_first,
                                                         const unsigned col0, const unsigned kt, const unsigned wn, const unsigned m_l,
                                                         const unsigned h, unsigned char *lds_scales, const unsigned m0, const unsigned tid,
-                                                        const unsigned m_lim) {
+                                                        const unsigned m_lim, const unsigned act) {
     constexpr unsigned kRowB = OUTF == 6 ? 64 : 16 * OUTF; // bytes per row and k-tile: 128 (FP8) / 64 (FP4; FP6: of the image of registers 0-3)
     unsigned char *const qs = out + (size_t)m_total * (n_half / 8 * OUTF);
     unsigned char *const out_hi = out + (size_t)m_total * (n_half / 2); // FP6: the image of registers 4-5 (native32_ws_bytes)
@@ -239,7 +239,7 @@ __device__ __forceinline__ void n32_silu_quant_epilogue(const f32x16 (&acc)[MB][
                 const f32x16 &a = acc[mb][np];
                 v[np][u] = silu_mul4<AT>(f32x4{a[4 * u], a[4 * u + 1], a[4 * u + 2], a[4 * u + 3]},
                                          f32x4{a[8 + 4 * u], a[8 + 4 * u + 1], a[8 + 4 * u + 2], a[8 + 4 * u + 3]}, gs, bias,
-                                         col0 + np * 16 + u * 8 + 4 * h, n_half);
+                                         col0 + np * 16 + u * 8 + 4 * h, n_half, act);
 #pragma unroll
                 for (int i = 0; i < 4; ++i)
                     amax = fmaxf(amax, fabsf(v[np][u][i]));
@@ -1034,13 +1034,13 @@ __global__ __launch_bounds__(Cfg::kThreads, Cfg::kMinWavesPerSimd) void gemm_nat
                 const unsigned col0 = (nt0 >> 1) * 16;
                 if (p.out_format == 4)
                     n32_silu_quant_epilogue<AT, 4, MB>(acc, gs, bias_e, (unsigned char *)p.c, p.m, n_half, m_base, col0, bn, wn, m_l, h, lds_sc, m0, tid,
-                                                              m_lim);
+                                                              m_lim, p.act);
                 else if (p.out_format == 6)
                     n32_silu_quant_epilogue<AT, 6, MB>(acc, gs, bias_e, (unsigned char *)p.c, p.m, n_half, m_base, col0, bn, wn, m_l, h, lds_sc, m0, tid,
-                                                              m_lim);
+                                                              m_lim, p.act);
                 else
                     n32_silu_quant_epilogue<AT, 8, MB>(acc, gs, bias_e, (unsigned char *)p.c, p.m, n_half, m_base, col0, bn, wn, m_l, h, lds_sc, m0, tid,
-                                                              m_lim);
+                                                              m_lim, p.act);
                 return;
             }
         }
@@ -1057,7 +1057,7 @@ __global__ __launch_bounds__(Cfg::kThreads, Cfg::kMinWavesPerSimd) void gemm_nat
                     if (m < m_lim && (unsigned)(2 * np + 1) < valid_nt && (!kIdx || cm != ~0u))
                         *reinterpret_cast<uint2 *>((char *)p.c + ((size_t)cm * n_half + n) * 2) = finish4_silu_mul<AT>(
                             f32x4{a[4 * u], a[4 * u + 1], a[4 * u + 2], a[4 * u + 3]},
-                            f32x4{a[8 + 4 * u], a[8 + 4 * u + 1], a[8 + 4 * u + 2], a[8 + 4 * u + 3]}, gs, bias_e, n, n_half);
+                            f32x4{a[8 + 4 * u], a[8 + 4 * u + 1], a[8 + 4 * u + 2], a[8 + 4 * u + 3]}, gs, bias_e, n, n_half, p.act);
                 }
         return;
     }

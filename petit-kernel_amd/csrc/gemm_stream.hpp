@@ -606,7 +606,7 @@ __device__ __forceinline__ void gemm_stream_body(const void *arg_w, const void *
             }
         }
     };
-    // SiLU-mul: logical tiles (inn, inn + 1) are the gate / up halves of output tile ntile / 2 (host guarantees
+    // SiLU-mul / SwiGLU-OAI: logical tiles (inn, inn + 1) are the gate / up halves of output tile ntile / 2 (host guarantees
     // an even NT, an even N/16 and gridDim.z == 1)
     auto emit_pair = [&](f32x4 gate, f32x4 up, unsigned iwn, unsigned imt, unsigned inn, unsigned il) {
         const unsigned m = m0 + imt * 16 + (il & 15u);
@@ -619,7 +619,7 @@ __device__ __forceinline__ void gemm_stream_body(const void *arg_w, const void *
         if (kIdx && cm == ~0u)
             return;
         *reinterpret_cast<uint2 *>((char *)p.c + ((size_t)cm * n_half + n) * 2) =
-            finish4_silu_mul<AT>(gate, up, gs, p.bias, n, n_half);
+            finish4_silu_mul<AT>(gate, up, gs, p.bias, n, n_half, p.act);
     };
 
     f32x4 accs[MT][NT];
@@ -790,11 +790,11 @@ __global__ __launch_bounds__(256) void splitk_reduce_kernel(void *c, const float
     }
 }
 
-// The same second pass with the SiLU-mul epilogue: the slabs hold the plain [m][n] product (the kernels ran with act = 0), the output is
-// [m][n / 2], c[r][j] = silu(y[r][j]) * y[r][j + n/2] with y = sum * gs + bias -- the arithmetic of finish4_silu_mul, one rounding.
+// The same second pass with a gated epilogue (act = 1 SiLU-mul, 2 SwiGLU-OAI): the slabs hold the plain [m][n] product (the kernels ran with
+// act = 0), the output is [m][n / 2], c[r][j] = f(y[r][j], y[r][j + n/2]) with y = sum * gs + bias -- the arithmetic of finish4_silu_mul, one rounding.
 template <class AT>
 __global__ __launch_bounds__(256) void splitk_reduce_silu_kernel(void *c, const float *ws, const float *gs_ptr, const void *bias,
-                                                                 unsigned m, unsigned n, unsigned parts) {
+                                                                 unsigned m, unsigned n, unsigned parts, unsigned act) {
     const unsigned n_half = n >> 1, q_per_row = n_half / 4;
     const size_t total4 = (size_t)m * q_per_row;
     const float gs = *gs_ptr;
@@ -814,7 +814,7 @@ __global__ __launch_bounds__(256) void splitk_reduce_silu_kernel(void *c, const 
             gate += *reinterpret_cast<const f32x4 *>(src + q * slab);
             up += *reinterpret_cast<const f32x4 *>(src + q * slab + n_half);
         }
-        reinterpret_cast<uint2 *>(c)[i] = finish4_silu_mul<AT>(gate, up, gs, bias, col, n_half);
+        reinterpret_cast<uint2 *>(c)[i] = finish4_silu_mul<AT>(gate, up, gs, bias, col, n_half, act);
     }
 }
 

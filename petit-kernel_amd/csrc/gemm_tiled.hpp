@@ -308,7 +308,7 @@ __device__ __forceinline__ void gemm_tiled_body(const GemmArgs &p, const unsigne
     }
     // --- epilogue: x global scale, one RNE rounding, 8-byte stores
     const float gs = *p.gs;
-    if (p.act) { // SiLU-mul: tiles (nt, nt + 1) are the gate / up halves of output tile (nt0 + nt) / 2
+    if (p.act) { // SiLU-mul / SwiGLU-OAI: tiles (nt, nt + 1) are the gate / up halves of output tile (nt0 + nt) / 2
         if constexpr (NTW % 2 == 0) {
             const unsigned n_half = p.n >> 1;
 #pragma unroll
@@ -320,7 +320,7 @@ __device__ __forceinline__ void gemm_tiled_body(const GemmArgs &p, const unsigne
                     const unsigned cm = (kIdx && m < p.m) ? idx_c_row(ix, m) : m;
                     if (m < p.m && (unsigned)nt < valid_nt && (!kIdx || cm != ~0u))
                         *reinterpret_cast<uint2 *>((char *)p.c + ((size_t)cm * n_half + n) * 2) =
-                            finish4_silu_mul<AT>(acc[mt][nt], acc[mt][nt + 1], gs, p.bias, n, n_half);
+                            finish4_silu_mul<AT>(acc[mt][nt], acc[mt][nt + 1], gs, p.bias, n, n_half, p.act);
                 }
         }
         return;

@@ -607,7 +607,7 @@ __global__ __launch_bounds__(Cfg::kThreads, Cfg::kMinWavesPerSimd) void gemm_wid
         return;
     }
     const float gs = *p.gs;
-    if (p.act) { // SiLU-mul: the pair (2 np, 2 np + 1) is the gate / up halves of output tile (nt0 + 2 np) / 2
+    if (p.act) { // SiLU-mul / SwiGLU-OAI: the pair (2 np, 2 np + 1) is the gate / up halves of output tile (nt0 + 2 np) / 2
         const unsigned n_half = p.n >> 1;
 #pragma unroll
         for (int mb = 0; mb < MB; ++mb)
@@ -621,7 +621,7 @@ __global__ __launch_bounds__(Cfg::kThreads, Cfg::kMinWavesPerSimd) void gemm_wid
                     if (m < p.m && (unsigned)(2 * np + 1) < valid_nt)
                         *reinterpret_cast<uint2 *>((char *)p.c + ((size_t)m * n_half + n) * 2) = finish4_silu_mul<AT>(
                             f32x4{a[4 * u], a[4 * u + 1], a[4 * u + 2], a[4 * u + 3]},
-                            f32x4{a[8 + 4 * u], a[8 + 4 * u + 1], a[8 + 4 * u + 2], a[8 + 4 * u + 3]}, gs, p.bias, n, n_half);
+                            f32x4{a[8 + 4 * u], a[8 + 4 * u + 1], a[8 + 4 * u + 2], a[8 + 4 * u + 3]}, gs, p.bias, n, n_half, p.act);
                 }
         return;
     }

@@ -54,9 +54,9 @@ int moe_check(const petit_solution_hints *hints, unsigned num_experts, unsigned 
               Family *fam, bool *act) {
     if (!hints)
         return kErrProblemShape;
-    if (epilogue && ((epilogue->activation != PETIT_ACTIVATION_NONE && epilogue->activation != PETIT_ACTIVATION_SILU_MUL) || epilogue->reserved != 0))
+    if (epilogue && (!activation_known(epilogue->activation) || epilogue->reserved != 0))
         return kErrBadArgument;
-    *act = epilogue && epilogue->activation == PETIT_ACTIVATION_SILU_MUL;
+    *act = epilogue && activation_gated(epilogue->activation);
     if (hints->c_type != hints->a_type || !family_for(hints->a_type, canonical_b_type(hints->b_type), fam))
         return kErrKernelShape;
     if (num_experts == 0 || num_experts > kMoeMaxExperts)
@@ -209,7 +209,7 @@ int petit_gemm_native_moe(void *c, const void *a, const void *b, const void *sca
         qa = workspace;
     }
     MoeArgs g{};
-    g.c = c, g.a = qa, g.w = b, g.s = mx ? scales : nullptr, g.gs = global_scales, g.bias = epilogue ? epilogue->bias : nullptr, g.act = act ? 1u : 0u;
+    g.c = c, g.a = qa, g.w = b, g.s = mx ? scales : nullptr, g.gs = global_scales, g.bias = epilogue ? epilogue->bias : nullptr, g.act = act ? (unsigned)epilogue->activation : 0u;
     g.offsets = expert_offsets, g.num_experts = num_experts, g.m = m, g.n = n, g.k = k;
     g.c_idx = c_row_index, g.c_rows = c_row_index ? c_rows : m, g.out_format = out_format;
     return e->launch_moe_native(g, (hipStream_t)stream);
@@ -245,7 +245,7 @@ int petit_gemm_fp4_fp16_moe(void *c, const void *a, const void *b, const void *s
     if (!e)
         return kErrKernelShape;
     MoeArgs g{};
-    g.c = c, g.a = a, g.w = b, g.s = scales, g.gs = global_scales, g.bias = epilogue ? epilogue->bias : nullptr, g.act = act ? 1u : 0u;
+    g.c = c, g.a = a, g.w = b, g.s = scales, g.gs = global_scales, g.bias = epilogue ? epilogue->bias : nullptr, g.act = act ? (unsigned)epilogue->activation : 0u;
     g.offsets = expert_offsets, g.num_experts = num_experts, g.m = m, g.n = n, g.k = k;
     return e->launch_moe(g, (hipStream_t)stream);
 }
@@ -274,7 +274,7 @@ int petit_gemm_fp4_fp16_moe_ex(void *c, const void *a, const void *b, const void
     if (!e || !e->launch_moe_idx)
         return kErrKernelShape;
     MoeArgs g{};
-    g.c = c, g.a = a, g.w = b, g.s = scales, g.gs = global_scales, g.bias = epilogue ? epilogue->bias : nullptr, g.act = act ? 1u : 0u;
+    g.c = c, g.a = a, g.w = b, g.s = scales, g.gs = global_scales, g.bias = epilogue ? epilogue->bias : nullptr, g.act = act ? (unsigned)epilogue->activation : 0u;
     g.offsets = expert_offsets, g.num_experts = num_experts, g.m = m, g.n = n, g.k = k;
     g.a_idx = a_row_index, g.c_idx = c_row_index, g.a_rows = a_rows, g.c_rows = c_rows;
     return e->launch_moe_idx(g, (hipStream_t)stream);

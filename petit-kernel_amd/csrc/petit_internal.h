@@ -44,6 +44,11 @@ constexpr int canonical_b_type(int b_type) { return b_type == kDataTypeMxFp4e2m1
 // 32-bit quantity the kernels form from M (grid rows, row * k * 2 inside one workgroup's activation block) stays in range below it
 constexpr unsigned kMaxM = 1u << 20;
 
+// petit_epilogue.activation (PETIT_ACTIVATION_*): the values this library knows, and the gated ones -- SiLU-mul (1) and SwiGLU-OAI (2) share every
+// shape rule, pick and refusal; the kind itself reaches only the epilogue arithmetic (GemmArgs::act / reduce_act, MoeArgs::act)
+constexpr bool activation_known(int activation) { return activation >= 0 && activation <= 2; }
+constexpr bool activation_gated(int activation) { return activation == 1 || activation == 2; }
+
 struct GemmArgs {
     void *c;            // [m][n] 16-bit, row-major
     const void *a;      // [m][k] 16-bit, row-major
@@ -51,8 +56,9 @@ struct GemmArgs {
     const void *s;      // packed scales  (layout.h)
     const float *gs;    // device pointer, one float
     const void *bias;   // optional fused epilogue: [n] in c's dtype, added before the single rounding; may be null
-    unsigned act;       // 0 none; 1 SiLU-mul: c is [m][n/2], c[m][j] = silu(y[m][j]) * y[m][j + n/2]  (y = acc*gs + bias)
-    unsigned reduce_act; // 1: SiLU-mul with a cross-workgroup K split -- the kernels see act = 0 (plain slabs), the reduce pass applies it
+    unsigned act;       // 0 none; 1 SiLU-mul: c is [m][n/2], c[m][j] = silu(y[m][j]) * y[m][j + n/2]  (y = acc*gs + bias); 2 SwiGLU-OAI: same
+                        // shape and tile pairing, the clamped gpt-oss formula (silu_mul4, device_common.hpp) -- the PETIT_ACTIVATION_* value
+    unsigned reduce_act; // 1 / 2: that activation with a cross-workgroup K split -- the kernels see act = 0 (plain slabs), the reduce pass applies it
     float *workspace;   // fp32 split-K slabs (may be null when splitk == 1)
     unsigned m, n, k;
     unsigned spans_per_wave; // set by the launcher: ceil(spans / (split_k * WK))
@@ -61,7 +67,7 @@ struct GemmArgs {
     // SiLU-mul epilogue that emits the NEXT GEMM's quantised activations instead of a 16-bit matrix
     const void *qa;          // pre-quantised activations in the k-tile-major scratch layout of format qa_format, or null
     unsigned qa_format;      // 8 (MXFP8) / 4 (MXFP4) when qa is set
-    unsigned out_format;     // 0: c is a 16-bit matrix; 8 / 4: c receives [m][n/2] activations quantised to MXFP8 / MXFP4 (act = 1 only)
+    unsigned out_format;     // 0: c is a 16-bit matrix; 8 / 4: c receives [m][n/2] activations quantised to MXFP8 / MXFP4 (act = 1 / 2 only)
 };
 enum : unsigned { kFlagPrio = 1u, kFlagXcdRaster = 2u, kFlagBandShift = 8 }; // bits 8..15: m-tiles per raster band (0 = whole columns)
 
@@ -88,7 +94,7 @@ struct MoeArgs {
     const void *w, *s;    // E packed weight / scale blocks of one [n, k] matrix each
     const float *gs;      // [E]
     const void *bias;     // [E][n] in c's dtype, or null
-    unsigned act;         // 0 none, 1 SiLU-mul (each expert's weight is [gate; up] along N)
+    unsigned act;         // 0 none, 1 SiLU-mul, 2 SwiGLU-OAI (each expert's weight is [gate; up] along N)
     const int32_t *offsets; // [E + 1]
     unsigned num_experts, m, n, k;
     // the indexed forms only (petit_gemm_fp4_fp16_moe_ex): grouped row r reads a row a_idx[r] of a [a_rows][k] and writes c row

@@ -143,7 +143,7 @@ template <class AT> int launch_splitk_reduce(const GemmArgs &args, unsigned part
         blocks = 2048;
     if (args.reduce_act) {
         hipLaunchKernelGGL(splitk_reduce_silu_kernel<AT>, dim3((unsigned)blocks), dim3(256), 0, stream, args.c, args.workspace,
-                           args.gs, args.bias, args.m, args.n, parts);
+                           args.gs, args.bias, args.m, args.n, parts, args.reduce_act);
         return hipGetLastError() == hipSuccess ? kOk : kErrLaunch;
     }
     hipLaunchKernelGGL(splitk_reduce_kernel<AT>, dim3((unsigned)blocks), dim3(256), 0, stream, args.c, args.workspace,

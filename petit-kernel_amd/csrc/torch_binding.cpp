@@ -71,7 +71,7 @@ at::Tensor process_scales(const at::Tensor &scales, int64_t size_n, int64_t size
 at::Tensor process_nvfp4_scales(const at::Tensor &s, int64_t n, int64_t k) { return process_scales(s, n, k, false); }
 at::Tensor process_mxfp4_scales(const at::Tensor &s, int64_t n, int64_t k) { return process_scales(s, n, k, true); }
 
-// activation: 0 none, 1 silu_mul (PETIT_ACTIVATION_*)
+// activation: 0 none, 1 silu_mul, 2 swiglu_oai (PETIT_ACTIVATION_*)
 at::Tensor mul_a16(bool mx, const at::Tensor &A, const at::Tensor &B, const at::Tensor &s, const at::Tensor &global_scale, int64_t size_m,
                    int64_t size_n, int64_t size_k, int64_t solution_id, const std::optional<at::Tensor> &bias, int64_t activation) {
     // (check order as in the reference's MulNvFp4A16 / MulMxFp4A16, fp4.cc:163-260: the scale / weight tensor contracts first)
@@ -90,9 +90,9 @@ at::Tensor mul_a16(bool mx, const at::Tensor &A, const at::Tensor &B, const at::
     TORCH_CHECK(A.is_contiguous() && A.numel() == size_m * size_k, "A must be a contiguous [size_m, size_k] tensor");
     TORCH_CHECK(B.is_contiguous() && B.numel() * B.element_size() == size_n * size_k / 2, "B does not hold size_n * size_k packed 4-bit weights");
     TORCH_CHECK(global_scale.scalar_type() == at::kFloat && global_scale.numel() >= 1, "global_scale must be float32");
-    TORCH_CHECK(activation == 0 || activation == 1, "activation must be 0 (none) or 1 (silu_mul)");
+    TORCH_CHECK(activation >= 0 && activation <= 2, "activation must be 0 (none), 1 (silu_mul) or 2 (swiglu_oai)");
     if (activation)
-        TORCH_CHECK(size_n % 32 == 0, "silu_mul needs size_n % 32 == 0 (gate / up halves of whole tiles), got ", size_n);
+        TORCH_CHECK(size_n % 32 == 0, "silu_mul / swiglu_oai need size_n % 32 == 0 (gate / up halves of whole tiles), got ", size_n);
     if (bias.has_value())
         TORCH_CHECK(bias->is_cuda() && bias->device() == A.device() && bias->scalar_type() == A.scalar_type() && bias->is_contiguous() &&
                         bias->numel() == size_n,
@@ -151,9 +151,9 @@ at::Tensor mul_a16_moe(bool mx, const at::Tensor &A, const at::Tensor &B, const 
                 "global_scales must be a contiguous float32 [num_experts] tensor");
     TORCH_CHECK(expert_offsets.scalar_type() == at::kInt && expert_offsets.is_contiguous() && expert_offsets.numel() == E + 1,
                 "expert_offsets must be a contiguous int32 [num_experts + 1] tensor");
-    TORCH_CHECK(activation == 0 || activation == 1, "activation must be 0 (none) or 1 (silu_mul)");
+    TORCH_CHECK(activation >= 0 && activation <= 2, "activation must be 0 (none), 1 (silu_mul) or 2 (swiglu_oai)");
     if (activation)
-        TORCH_CHECK(size_n % 32 == 0, "silu_mul needs size_n % 32 == 0 (gate / up halves of whole tiles), got ", size_n);
+        TORCH_CHECK(size_n % 32 == 0, "silu_mul / swiglu_oai need size_n % 32 == 0 (gate / up halves of whole tiles), got ", size_n);
     if (bias.has_value())
         TORCH_CHECK(bias->is_cuda() && bias->device() == A.device() && bias->scalar_type() == A.scalar_type() && bias->is_contiguous() &&
                         bias->numel() == E * size_n,
@@ -205,9 +205,9 @@ at::Tensor mul_a16_moe_indexed_impl(bool mx, const at::Tensor &A, const at::Tens
             TORCH_CHECK((*idx)->is_cuda() && (*idx)->device() == A.device() && (*idx)->scalar_type() == at::kInt && (*idx)->is_contiguous() &&
                             (*idx)->numel() == size_m,
                         "row indices must be contiguous int32 [size_m] tensors on A's device");
-    TORCH_CHECK(activation == 0 || activation == 1, "activation must be 0 (none) or 1 (silu_mul)");
+    TORCH_CHECK(activation >= 0 && activation <= 2, "activation must be 0 (none), 1 (silu_mul) or 2 (swiglu_oai)");
     if (activation)
-        TORCH_CHECK(size_n % 32 == 0, "silu_mul needs size_n % 32 == 0 (gate / up halves of whole tiles), got ", size_n);
+        TORCH_CHECK(size_n % 32 == 0, "silu_mul / swiglu_oai need size_n % 32 == 0 (gate / up halves of whole tiles), got ", size_n);
     if (bias.has_value())
         TORCH_CHECK(bias->is_cuda() && bias->device() == A.device() && bias->scalar_type() == A.scalar_type() && bias->is_contiguous() &&
                         bias->numel() == E * size_n,
@@ -345,8 +345,8 @@ at::Tensor mul_native_moe_impl(bool mx, PETIT_NATIVE_MOE_ARGS) {
             TORCH_CHECK((*idx)->is_cuda() && (*idx)->device() == A.device() && (*idx)->scalar_type() == at::kInt && (*idx)->is_contiguous() &&
                             (*idx)->numel() == size_m,
                         "row indices must be contiguous int32 [size_m] tensors on A's device");
-    TORCH_CHECK(activation == 0 || activation == 1, "activation must be 0 (none) or 1 (silu_mul)");
-    TORCH_CHECK(!out_format || (activation && !c_row_index.has_value()), "out_quantized needs activation='silu_mul' and no c_row_index");
+    TORCH_CHECK(activation >= 0 && activation <= 2, "activation must be 0 (none), 1 (silu_mul) or 2 (swiglu_oai)");
+    TORCH_CHECK(!out_format || (activation && !c_row_index.has_value()), "out_quantized needs activation='silu_mul' or 'swiglu_oai' and no c_row_index");
     if (bias.has_value())
         TORCH_CHECK(bias->is_cuda() && bias->device() == A.device() && bias->scalar_type() == dtype && bias->is_contiguous() && bias->numel() == E * size_n,
                     "bias must be a contiguous [num_experts, size_n] tensor of the activation dtype on the same device");
@@ -407,8 +407,8 @@ at::Tensor mul_nvfp4_native_transient(PETIT_NV_TRANSIENT_ARGS) {
     TORCH_CHECK(B.is_cuda() && s.is_cuda() && global_scale.is_cuda(), "all tensors must be on GPU");
     TORCH_CHECK(B.is_contiguous() && B.numel() * B.element_size() == size_n * size_k / 2, "B does not hold size_n * size_k packed 4-bit weights");
     TORCH_CHECK(s.is_contiguous() && s.numel() * s.element_size() == size_n * size_k / 16, "s does not hold size_n * size_k / 16 scales");
-    TORCH_CHECK(activation == 0 || activation == 1, "activation must be 0 (none) or 1 (silu_mul)");
-    TORCH_CHECK(!out_format || activation, "out_quantized needs activation='silu_mul'");
+    TORCH_CHECK(activation >= 0 && activation <= 2, "activation must be 0 (none), 1 (silu_mul) or 2 (swiglu_oai)");
+    TORCH_CHECK(!out_format || activation, "out_quantized needs activation='silu_mul' or 'swiglu_oai'");
     if (bias.has_value())
         TORCH_CHECK(bias->is_cuda() && bias->device() == A.device() && bias->scalar_type() == dtype && bias->is_contiguous() && bias->numel() == size_n,
                     "bias must be a contiguous [size_n] tensor of the activation dtype on the same device");

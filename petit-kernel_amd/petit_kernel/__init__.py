@@ -12,7 +12,8 @@ import enum
 
 import torch
 
-from . import compiled, offline, ops, tuning
+from . import compiled, gptoss, offline, ops, tuning
+from .gptoss import GptOssExperts, prepare_gptoss_experts
 from .moe import fp4_moe, fp4_moe_fused, fp4_moe_native, moe_align
 from .ops import QuantizedActivations, mul_fp4_a16_grouped, mul_mxfp4_native, quantize_activations
 from .ops import attach_nvfp4_native, mul_nvfp4_native, nvfp4_native_image, nvfp4_native_images
@@ -76,6 +77,7 @@ def mul_nvfp4_a16(a: torch.Tensor, b: torch.Tensor, s: torch.Tensor, global_scal
     # `bias` / `activation` are extensions (keyword-only, default None = the reference's behaviour):
     #   bias       [size_n] of a.dtype, added before the single rounding to 16 bit
     #   activation "silu_mul": returns [size_m, size_n/2] = silu(y[:, :n/2]) * y[:, n/2:]  (gate_up of a gated MLP)
+    #   activation "swiglu_oai": the same shape with gpt-oss's clamped form, g = min(gate, 7), u = clamp(up, -7, 7): g * sigmoid(1.702 g) * (u + 1)
     return _impl.mul_nvfp4_a16(a, b, s, global_scale, size_m, size_n, size_k, solution_id, bias, activation)
 
 
@@ -231,4 +233,6 @@ __all__ = [
     "SOLUTION_AUTO_NATIVE_MXFP8",
     "SOLUTION_AUTO_NATIVE_MXFP4",
     "SOLUTION_AUTO_NATIVE_MXFP6",
+    "prepare_gptoss_experts",
+    "GptOssExperts",
 ]

@@ -42,7 +42,7 @@ def why_unavailable() -> str:
     return _error or ""
 
 
-_ACT = {None: 0, "none": 0, "silu_mul": 1}
+_ACT = {None: 0, "none": 0, "silu_mul": 1, "swiglu_oai": 2}
 
 
 def _act(activation) -> int:

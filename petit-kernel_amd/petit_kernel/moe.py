@@ -29,16 +29,37 @@ def moe_align(topk_ids: torch.Tensor, num_experts: int):
     return sorted_idx, offsets
 
 
+def _check_activation(activation) -> None:
+    if activation not in ("silu_mul", "swiglu_oai"):
+        raise RuntimeError("activation must be 'silu_mul' or 'swiglu_oai'")
+
+
+def _down_n(w2: torch.Tensor, num_experts: int, inter: int, hidden: int) -> int:
+    """N of the down launch: the rows of one expert's packed [N, I] FP4 weight (half a byte per element).  It equals hidden's width unless the
+    caller padded hidden's K for gate_up alone (petit_kernel.gptoss: 2880 -> 3072 columns in, 2880 out)."""
+    n2 = w2.numel() * w2.element_size() * 2 // (num_experts * inter)
+    if n2 > hidden:
+        raise RuntimeError(f"w2 holds [{n2}, {inter}] per expert, more rows than hidden's width {hidden}")
+    return n2
+
+
 def fp4_moe(hidden: torch.Tensor, w13: torch.Tensor, s13: torch.Tensor, gs13: torch.Tensor, w2: torch.Tensor, s2: torch.Tensor,
-            gs2: torch.Tensor, topk_weights: torch.Tensor, topk_ids: torch.Tensor, kind: str = "nvfp4") -> torch.Tensor:
+            gs2: torch.Tensor, topk_weights: torch.Tensor, topk_ids: torch.Tensor, kind: str = "nvfp4", *, bias13: torch.Tensor = None,
+            bias2: torch.Tensor = None, activation: str = "silu_mul") -> torch.Tensor:
     """A gated-MLP MoE layer: out[t] = sum_j topk_weights[t, j] * down_e(silu(gate_e(x_t)) * up_e(x_t)), e = topk_ids[t, j].
 
     hidden [T, H] bf16 / fp16.  w13 / s13: the E experts' [gate; up] weights ([2 I, H] each, vLLM / SGLang's w13 layout) packed back to
     back -- repack_* / process_*_scales of the stacked [E * 2 I, H] tensors; w2 / s2 the same for the [H, I] down weights; gs13 / gs2:
-    float32 [E] global scales.  kind: 'nvfp4' or 'mxfp4'.  Returns [T, H] in hidden's dtype."""
+    float32 [E] global scales.  kind: 'nvfp4' or 'mxfp4'.  Returns [T, H] in hidden's dtype.
+
+    bias13 [E, 2 I] (in [gate; up] order) and bias2 [E, H], in hidden's dtype, are added by the gate_up and the down launch: the router
+    weight multiplies down + bias2.  activation: 'silu_mul', or 'swiglu_oai' (gpt-oss: min(gate, 7) * sigmoid(1.702 gate) * (clamp(up, -7, 7)
+    + 1) on gate_up + bias13).  down's K is I and its N the hidden size of `w2`, which may be smaller than hidden's (petit_kernel.gptoss
+    pads K only).  With the defaults the layer issues the launches it always issued."""
     from . import mul_mxfp4_a16_moe, mul_nvfp4_a16_moe
     if kind not in ("nvfp4", "mxfp4"):
         raise RuntimeError("kind must be 'nvfp4' or 'mxfp4'")
+    _check_activation(activation)
     mul = mul_nvfp4_a16_moe if kind == "nvfp4" else mul_mxfp4_a16_moe
     T, H = hidden.shape
     topk = topk_ids.shape[1]
@@ -48,23 +69,27 @@ def fp4_moe(hidden: torch.Tensor, w13: torch.Tensor, s13: torch.Tensor, gs13: to
     m = T * topk
     sorted_idx, offsets = moe_align(topk_ids, E)
     a = hidden.index_select(0, sorted_idx // topk)                                        # rows grouped by expert
-    h = mul(a, w13, s13, gs13, offsets, m, n13, H, E, activation="silu_mul")             # [m, I]
-    y = mul(h, w2, s2, gs2, offsets, m, H, inter, E)                                      # [m, H]
+    n2 = _down_n(w2, E, inter, H)
+    h = mul(a, w13, s13, gs13, offsets, m, n13, H, E, bias=bias13, activation=activation)  # [m, I]
+    y = mul(h, w2, s2, gs2, offsets, m, n2, inter, E, bias=bias2)                          # [m, n2]
     w = topk_weights.reshape(-1).to(torch.float32).index_select(0, sorted_idx)
-    buf = torch.empty((m, H), dtype=torch.float32, device=hidden.device)
+    buf = torch.empty((m, n2), dtype=torch.float32, device=hidden.device)
     buf.index_copy_(0, sorted_idx, y.float() * w[:, None])                                # every (token, slot) position exactly once
-    return buf.view(T, topk, H).sum(dim=1).to(hidden.dtype)
+    return buf.view(T, topk, n2).sum(dim=1).to(hidden.dtype)
 
 
 def fp4_moe_fused(hidden: torch.Tensor, w13: torch.Tensor, s13: torch.Tensor, gs13: torch.Tensor, w2: torch.Tensor, s2: torch.Tensor,
-                  gs2: torch.Tensor, topk_weights: torch.Tensor, topk_ids: torch.Tensor, kind: str = "nvfp4") -> torch.Tensor:
+                  gs2: torch.Tensor, topk_weights: torch.Tensor, topk_ids: torch.Tensor, kind: str = "nvfp4", *, bias13: torch.Tensor = None,
+                  bias2: torch.Tensor = None, activation: str = "silu_mul") -> torch.Tensor:
     """fp4_moe's layer (same arguments, same result up to the combine's rounding order) on the indexed MoE launches: align on the device,
     gate_up on gathered rows, down scattered into slot order, the top-k combine.  topk_ids: int32 or int64 [T, topk]; entries outside
     [0, E) (-1 under expert parallelism) contribute nothing.  topk_weights: float32 or bfloat16 [T, topk] (converted to float32 once).
+    bias13 / bias2 / activation: as fp4_moe (the biases ride in the gate_up and down launches: no launch more).
     No host sync: capturable in a graph and replayable with any routing of the same shape."""
     from . import moe_align_device, moe_combine, mul_mxfp4_a16_moe_indexed, mul_nvfp4_a16_moe_indexed
     if kind not in ("nvfp4", "mxfp4"):
         raise RuntimeError("kind must be 'nvfp4' or 'mxfp4'")
+    _check_activation(activation)
     mul = mul_nvfp4_a16_moe_indexed if kind == "nvfp4" else mul_mxfp4_a16_moe_indexed
     T, H = hidden.shape
     topk = topk_ids.shape[1]
@@ -75,8 +100,9 @@ def fp4_moe_fused(hidden: torch.Tensor, w13: torch.Tensor, s13: torch.Tensor, gs
     ids = topk_ids if topk_ids.dtype in (torch.int32, torch.int64) and topk_ids.is_contiguous() else topk_ids.contiguous().to(torch.int64)
     w = topk_weights if topk_weights.dtype == torch.float32 and topk_weights.is_contiguous() else topk_weights.float().contiguous()
     sorted_pos, offsets, token_index = moe_align_device(ids, E)
-    h = mul(hidden, w13, s13, gs13, offsets, m, n13, H, E, a_row_index=token_index, activation="silu_mul")   # [m, I], grouped order
-    y = mul(h, w2, s2, gs2, offsets, m, H, inter, E, c_row_index=sorted_pos, c_rows=m)                       # [m, H], (token, slot) order
+    n2 = _down_n(w2, E, inter, H)
+    h = mul(hidden, w13, s13, gs13, offsets, m, n13, H, E, a_row_index=token_index, bias=bias13, activation=activation)  # [m, I], grouped order
+    y = mul(h, w2, s2, gs2, offsets, m, n2, inter, E, c_row_index=sorted_pos, c_rows=m, bias=bias2)          # [m, n2], (token, slot) order
     return moe_combine(y, w, ids, E)
 
 
@@ -84,15 +110,18 @@ _NATIVE_SENTINELS = {"mxfp8": -2, "mxfp4": -3, "mxfp6": -4}   # SOLUTION_AUTO_NA
 
 
 def fp4_moe_native(hidden: torch.Tensor, w13: torch.Tensor, s13, gs13: torch.Tensor, w2: torch.Tensor, s2, gs2: torch.Tensor,
-                   topk_weights: torch.Tensor, topk_ids: torch.Tensor, kind: str = "mxfp4", activations: str = "mxfp8") -> torch.Tensor:
+                   topk_weights: torch.Tensor, topk_ids: torch.Tensor, kind: str = "mxfp4", activations: str = "mxfp8", *,
+                   bias13: torch.Tensor = None, bias2: torch.Tensor = None, activation: str = "silu_mul") -> torch.Tensor:
     """fp4_moe_fused's layer on the NATIVE class (the block-scaled MFMA, activations quantised to `activations`: 'mxfp8', 'mxfp6' or 'mxfp4';
     petit_gemm_native_moe -- a different accuracy class than the exact layers).  kind 'mxfp4': w13 / s13 / w2 / s2 as fp4_moe_fused; kind
     'nvfp4': w13 / w2 are the experts' MFMA-native images back to back (nvfp4_native_images) and s13 / s2 are None.  Five launches (seven
     when the align needs its three-launch form): the device align, the gathering quantiser, gate_up with SiLU-mul writing the quantised
-    grouped rows down reads, down scattered into slot order, the top-k combine.  No host sync: capturable."""
+    grouped rows down reads, down scattered into slot order, the top-k combine.  bias13 / bias2 / activation: as fp4_moe; 'swiglu_oai' is
+    quantised for down from its f32 value, as SiLU-mul is.  No host sync: capturable."""
     from . import moe_align_device, moe_combine, mul_mxfp4_native_moe, mul_nvfp4_native_moe, quantize_activation_rows
     if kind not in ("nvfp4", "mxfp4"):
         raise RuntimeError("kind must be 'nvfp4' or 'mxfp4'")
+    _check_activation(activation)
     if activations not in _NATIVE_SENTINELS:
         raise RuntimeError("activations must be 'mxfp8', 'mxfp6' or 'mxfp4'")
     sid = _NATIVE_SENTINELS[activations]
@@ -102,20 +131,21 @@ def fp4_moe_native(hidden: torch.Tensor, w13: torch.Tensor, s13, gs13: torch.Ten
     if kind == "mxfp4":
         n13 = w13.numel() * w13.element_size() * 2 // (E * H)   # 2 I
         mul13 = lambda a, **kw: mul_mxfp4_native_moe(a, w13, s13, gs13, offsets, m, n13, H, E, solution_id=sid, **kw)  # noqa: E731
-        mul2 = lambda a, **kw: mul_mxfp4_native_moe(a, w2, s2, gs2, offsets, m, H, inter, E, solution_id=sid, **kw)  # noqa: E731
+        mul2 = lambda a, **kw: mul_mxfp4_native_moe(a, w2, s2, gs2, offsets, m, n2, inter, E, solution_id=sid, **kw)  # noqa: E731
     else:
         n13 = w13.numel() * 32 // (E * H * 25)                  # an image holds 25 / 32 bytes per weight (6.25 bits)
         mul13 = lambda a, **kw: mul_nvfp4_native_moe(a, w13, gs13, offsets, m, n13, H, E, solution_id=sid, **kw)  # noqa: E731
-        mul2 = lambda a, **kw: mul_nvfp4_native_moe(a, w2, gs2, offsets, m, H, inter, E, solution_id=sid, **kw)  # noqa: E731
+        mul2 = lambda a, **kw: mul_nvfp4_native_moe(a, w2, gs2, offsets, m, n2, inter, E, solution_id=sid, **kw)  # noqa: E731
     inter = n13 // 2
+    n2 = _down_n(w2, E, inter, H) if kind == "mxfp4" else H
     m = T * topk
     ids = topk_ids if topk_ids.dtype in (torch.int32, torch.int64) and topk_ids.is_contiguous() else topk_ids.contiguous().to(torch.int64)
     w = topk_weights if topk_weights.dtype == torch.float32 and topk_weights.is_contiguous() else topk_weights.float().contiguous()
     sorted_pos, offsets, token_index = moe_align_device(ids, E)
     qa = quantize_activation_rows(hidden, activations, token_index)                  # grouped rows; unrouted (-1) rows are zeros
     if n13 % 512 == 0:
-        h = mul13(qa, activation="silu_mul", out_quantized=activations)              # down's quantised input, grouped
+        h = mul13(qa, bias=bias13, activation=activation, out_quantized=activations)  # down's quantised input, grouped
     else:
-        h = mul13(qa, activation="silu_mul")                                         # 16-bit; down quantises it (one more launch)
-    y = mul2(h, c_row_index=sorted_pos, c_rows=m)                                    # [m, H], (token, slot) order
+        h = mul13(qa, bias=bias13, activation=activation)                            # 16-bit; down quantises it (one more launch)
+    y = mul2(h, c_row_index=sorted_pos, c_rows=m, bias=bias2)                        # [m, n2], (token, slot) order
     return moe_combine(y, w, ids, E)

@@ -142,7 +142,7 @@ def process_mxfp4_scales(scales: torch.Tensor, size_n: int, size_k: int) -> torc
     return out
 
 
-_ACTIVATIONS = {None: 0, "none": 0, "silu_mul": 1}   # PETIT_ACTIVATION_* (include/petit_amd.h)
+_ACTIVATIONS = {None: 0, "none": 0, "silu_mul": 1, "swiglu_oai": 2}   # PETIT_ACTIVATION_* (include/petit_amd.h)
 
 # solution_id of the Python surface: any negative value = "library default" as in the reference (fp4.cc:189-191), with two
 # values reserved for the default pick INSIDE the opt-in native-FP4 class (MXFP4 weights only; petit_amd.h)
@@ -195,7 +195,7 @@ def _mul(kind: str, A, B, s, global_scale, size_m, size_n, size_k, solution_id, 
     _check(activation in _ACTIVATIONS, f"activation must be one of {sorted(k for k in _ACTIVATIONS if k)} or None")
     act = _ACTIVATIONS[activation]
     if act:
-        _check(size_n % 32 == 0, f"silu_mul needs size_n % 32 == 0 (gate / up halves of whole tiles), got {size_n}")
+        _check(size_n % 32 == 0, f"{activation} needs size_n % 32 == 0 (gate / up halves of whole tiles), got {size_n}")
     c = torch.empty((size_m, size_n // 2 if act else size_n), dtype=A.dtype, device=A.device)
     a_type = _lib.CXX_DTYPE_BF16 if A.dtype == torch.bfloat16 else _lib.CXX_DTYPE_FP16
     b_type = _lib.CXX_DTYPE_FP4_E2M1 if kind == "nv" else _lib.CXX_DTYPE_MXFP4_E2M1
@@ -433,7 +433,7 @@ def mul_mxfp4_native(A, B, s, global_scale, size_m, size_n, size_k, solution_id=
     _check(out_quantized is None or out_quantized in _QFORMATS, "out_quantized must be None, 'mxfp8', 'mxfp6' or 'mxfp4'")
     act = _ACTIVATIONS[activation]
     out_fmt = _QFORMATS[out_quantized] if out_quantized else 0
-    _check(not out_fmt or act, "out_quantized needs activation='silu_mul'")
+    _check(not out_fmt or act, "out_quantized needs activation='silu_mul' or 'swiglu_oai'")
     a_type = _lib.CXX_DTYPE_BF16 if dtype == torch.bfloat16 else _lib.CXX_DTYPE_FP16
     hints = _CHints(a_type, _lib.CXX_DTYPE_MXFP4_E2M1, a_type, 0)
     sid = _c_solution_id(solution_id, native_ok=True)
@@ -520,7 +520,7 @@ def mul_nvfp4_native(A, image: torch.Tensor, global_scale, size_m, size_n, size_
     _check(out_quantized is None or out_quantized in _QFORMATS, "out_quantized must be None, 'mxfp8', 'mxfp6' or 'mxfp4'")
     act = _ACTIVATIONS[activation]
     out_fmt = _QFORMATS[out_quantized] if out_quantized else 0
-    _check(not out_fmt or act, "out_quantized needs activation='silu_mul'")
+    _check(not out_fmt or act, "out_quantized needs activation='silu_mul' or 'swiglu_oai'")
     a_type = _lib.CXX_DTYPE_BF16 if dtype == torch.bfloat16 else _lib.CXX_DTYPE_FP16
     hints = _CHints(a_type, _lib.CXX_DTYPE_FP4_E2M1, a_type, 0)
     sid = _c_solution_id(solution_id, native_ok=True)
@@ -563,7 +563,7 @@ def _nv_transient_args(A, size_m, size_k, activation, out_quantized):
     _check(out_quantized is None or out_quantized in _QFORMATS, "out_quantized must be None, 'mxfp8', 'mxfp6' or 'mxfp4'")
     act = _ACTIVATIONS[activation]
     out_fmt = _QFORMATS[out_quantized] if out_quantized else 0
-    _check(not out_fmt or act, "out_quantized needs activation='silu_mul'")
+    _check(not out_fmt or act, "out_quantized needs activation='silu_mul' or 'swiglu_oai'")
     return a_t, dtype, a_fmt, dev, act, out_fmt
 
 
@@ -693,7 +693,7 @@ def _mul_moe(kind: str, A, B, s, global_scales, expert_offsets, size_m, size_n, 
     _check(activation in _ACTIVATIONS, f"activation must be one of {sorted(k for k in _ACTIVATIONS if k)} or None")
     act = _ACTIVATIONS[activation]
     if act:
-        _check(size_n % 32 == 0, f"silu_mul needs size_n % 32 == 0 (gate / up halves of whole tiles), got {size_n}")
+        _check(size_n % 32 == 0, f"{activation} needs size_n % 32 == 0 (gate / up halves of whole tiles), got {size_n}")
     if bias is not None:
         _check(bias.is_cuda and bias.device == A.device and bias.dtype == A.dtype and bias.is_contiguous() and bias.numel() == E * size_n,
                "bias must be a contiguous [num_experts, size_n] tensor of A's dtype on A's device")
@@ -749,7 +749,7 @@ def _mul_moe_indexed(kind: str, A, B, s, global_scales, expert_offsets, size_m, 
     _check(activation in _ACTIVATIONS, f"activation must be one of {sorted(k for k in _ACTIVATIONS if k)} or None")
     act = _ACTIVATIONS[activation]
     if act:
-        _check(size_n % 32 == 0, f"silu_mul needs size_n % 32 == 0 (gate / up halves of whole tiles), got {size_n}")
+        _check(size_n % 32 == 0, f"{activation} needs size_n % 32 == 0 (gate / up halves of whole tiles), got {size_n}")
     if bias is not None:
         _check(bias.is_cuda and bias.device == A.device and bias.dtype == A.dtype and bias.is_contiguous() and bias.numel() == E * size_n,
                "bias must be a contiguous [num_experts, size_n] tensor of A's dtype on A's device")
@@ -939,7 +939,7 @@ def _mul_native_moe(kind: str, A, B, s, global_scales, expert_offsets, size_m, s
     _check(out_quantized is None or out_quantized in _QFORMATS, "out_quantized must be None, 'mxfp8', 'mxfp6' or 'mxfp4'")
     act = _ACTIVATIONS[activation]
     out_fmt = _QFORMATS[out_quantized] if out_quantized else 0
-    _check(not out_fmt or (act and c_row_index is None), "out_quantized needs activation='silu_mul' and no c_row_index")
+    _check(not out_fmt or (act and c_row_index is None), "out_quantized needs activation='silu_mul' or 'swiglu_oai' and no c_row_index")
     if bias is not None:
         _check(bias.is_cuda and bias.device == dev and bias.dtype == dtype and bias.is_contiguous() and bias.numel() == E * size_n,
                "bias must be a contiguous [num_experts, size_n] tensor of the activation dtype on the same device")

@@ -2,7 +2,7 @@
 """tools/moe_bench.py -- the routed-expert (MoE) launch against a host loop of dense calls, on real expert shapes.
 
     python tools/moe_bench.py [--cells decode|prefill|all] [--models deepseek,qwen3,mixtral] [--iters N] [--out FILE]
-                              [--only-moe | --only-loop] [--single-expert] [--layer [--native mxfp8|mxfp6|mxfp4]]
+                              [--only-moe | --only-loop] [--single-expert] [--layer [--native mxfp8|mxfp6|mxfp4]] [--gptoss]
 
 Per cell (model, projection, T tokens): E experts' NVFP4 weights (bf16 activations) stacked back to back, copied until the pool is >= 1 GB so
 that rotating over copies and over routings (drawn from a seed, top-k of random router logits) keeps the 256 MB Infinity Cache from serving
@@ -18,6 +18,8 @@ plain MoE GEMMs on pre-gathered rows against the indexed ones (gate_up gathering
 --layer --native mxfp8|mxfp6|mxfp4: fp4_moe_native against fp4_moe_fused on the same weights (MXFP4 raw; NVFP4 through nvfp4_native_images), graph
 replays, T = 1, 16, 64, 1024, 4096; plus one single-expert cell (M = 4096, every row on one expert, activations pre-quantised: the native MoE launch
 against the dense native call with the same id).
+--gptoss: the gpt-oss-20b / -120b expert block (bf16 x MXFP4, 2880 -> 3072, biases, activation="swiglu_oai"): see gptoss_cells.  The two
+models are also in the model list of the default cells (--models gpt-oss-20b,gpt-oss-120b: MXFP4 pools).
 Kernel times without launch gaps: run under `rocprofv3 --kernel-trace --stats -- python tools/moe_bench.py ...`.
 Prints one JSON object (and writes it to --out).
 """
@@ -37,31 +39,38 @@ MODELS = {  # (gate_up n x k, down n x k, E, top-k)
     "deepseek": ((4096, 7168), (7168, 2048), 256, 8),
     "qwen3": ((1536, 2048), (2048, 768), 128, 8),
     "mixtral": ((32768, 6144), (6144, 16384), 8, 2),
+    # gpt-oss: H = I = 2880, padded to 3072 by petit_kernel.gptoss (gate_up [2 * 3072, 3072], down [2880, 3072]); bf16 x MXFP4
+    "gpt-oss-20b": ((6144, 3072), (2880, 3072), 32, 4),
+    "gpt-oss-120b": ((6144, 3072), (2880, 3072), 128, 4),
 }
+MODEL_KIND = {"gpt-oss-20b": "mx", "gpt-oss-120b": "mx"}   # weight format of a model's cells (default "nv": NVFP4)
 DECODE_T, PREFILL_T = (1, 4, 16, 64), (1024, 4096)
 POOL_BYTES = 1 << 30
 
 
 class Pool:
-    """copies of E experts' packed [n, k] NVFP4 weights (random bytes: timing only)"""
+    """copies of E experts' packed [n, k] NVFP4 (kind "nv") or MXFP4 ("mx") weights (random bytes: timing only)"""
 
-    def __init__(self, pk, E, n, k):
-        self.E, self.n, self.k = E, n, k
-        self.w_bytes, self.s_bytes = n * k // 2, n * k // 16
+    def __init__(self, pk, E, n, k, kind="nv"):
+        self.E, self.n, self.k, self.kind = E, n, k, kind
+        self.w_bytes, self.s_bytes = n * k // 2, n * k // (16 if kind == "nv" else 32)
         per_copy = E * (self.w_bytes + self.s_bytes)
         self.copies = max(1, -(-POOL_BYTES // per_copy))
         g = torch.Generator(device="cuda").manual_seed(n * 31 + k)
         self.b = [torch.randint(-2 ** 31, 2 ** 31 - 1, (E * n // 16, 2 * k), dtype=torch.int32, device="cuda", generator=g) for _ in range(self.copies)]
-        # e4m3 scales in [0.25, 4): exponent field 5..8
-        self.s = [(torch.randint(0x28, 0x40, (E * n, k // 16), dtype=torch.uint8, device="cuda", generator=g)).view(torch.float8_e4m3fn)
-                  for _ in range(self.copies)]
+        # e4m3 scales in [0.25, 4): exponent field 5..8; e8m0 scales 2^-9 .. 2^-1
+        if kind == "nv":
+            self.s = [(torch.randint(0x28, 0x40, (E * n, k // 16), dtype=torch.uint8, device="cuda", generator=g)).view(torch.float8_e4m3fn)
+                      for _ in range(self.copies)]
+        else:
+            self.s = [torch.randint(118, 127, (E * n // 32, k), dtype=torch.uint8, device="cuda", generator=g) for _ in range(self.copies)]
         self.gs = torch.rand(E, device="cuda") + 0.5
 
     def expert(self, c, e):
         n, k = self.n, self.k
         b = self.b[c].view(-1)[e * n * k // 8:(e + 1) * n * k // 8].view(n // 16, 2 * k)
-        s = self.s[c].view(-1)[e * self.s_bytes:(e + 1) * self.s_bytes].view(n, k // 16)
-        return b, s, self.gs[e:e + 1]
+        s = self.s[c].view(-1)[e * self.s_bytes:(e + 1) * self.s_bytes]
+        return b, (s.view(n, k // 16) if self.kind == "nv" else s.view(n // 32, k)), self.gs[e:e + 1]
 
 
 def routings(T, E, topk, count, seed):
@@ -101,12 +110,13 @@ def cell(pk, pool, T, topk, iters, do_moe=True, do_loop=True, seed=0):
     res["active_bytes_mean"] = sum(a_ * (pool.w_bytes + pool.s_bytes) for a_ in act) / len(act) + 2 * m * k + 2 * m * n
     h = pk.PetitSolutionHints()
     h.a_type = h.c_type = torch.bfloat16
-    h.b_type = pk.DataType.float4_e2m1
+    h.b_type = pk.DataType.float4_e2m1 if pool.kind == "nv" else pk.DataType.mxfloat4_e2m1
     res["moe_solution"] = pk.ops._lib.describe_solution(pk.moe_resolve_solution(h, E, m, n, k, -1))
+    mul_moe, mul_dense = (pk.mul_nvfp4_a16_moe, pk.mul_nvfp4_a16) if pool.kind == "nv" else (pk.mul_mxfp4_a16_moe, pk.mul_mxfp4_a16)
 
     def moe(i):
         c = i % pool.copies
-        pk.mul_nvfp4_a16_moe(a, pool.b[c], pool.s[c], pool.gs, offs_d[i % len(offs_d)], m, n, k, E)
+        mul_moe(a, pool.b[c], pool.s[c], pool.gs, offs_d[i % len(offs_d)], m, n, k, E)
 
     def loop(i):
         c = i % pool.copies
@@ -115,7 +125,7 @@ def cell(pk, pool, T, topk, iters, do_moe=True, do_loop=True, seed=0):
             if cnt[e]:
                 b, s, gs = pool.expert(c, e)
                 lo = int(offs[e])
-                pk.mul_nvfp4_a16(a[lo:lo + cnt[e]], b, s, gs, cnt[e], n, k, -1)
+                mul_dense(a[lo:lo + cnt[e]], b, s, gs, cnt[e], n, k, -1)
 
     if do_moe:
         res["moe_us"] = time_us(moe, iters)
@@ -300,6 +310,75 @@ def native_single_expert(pk, iters, fmt, m=4096):
             "moe_over_dense": mu / du}
 
 
+def gptoss_cells(pk, models, ts, iters):
+    """--gptoss: gpt-oss-20b / -120b expert blocks (bf16 x MXFP4, H = I = 2880 -> 3072, top-4, biases, activation="swiglu_oai"), graph replays:
+      fused_us / native_us   prepare_gptoss_experts(...).forward on the fused and the native (MXFP8 activations) path, x padding included
+      loop_us                the host loop a caller without the MoE launch runs: per active expert one dense gate_up (fused activation and
+                             bias) and one dense down (bias) on that expert's rows, eager launches, no gather and no combine (GEMMs only)
+      act_fused_us           the gate_up MoE launch with activation="swiglu_oai" and the bias
+      act_unfused_us         the same launch with activation=None ([m, 2 I] out) plus the torch expression of the activation on it"""
+    from petit_kernel.gptoss import GptOssExperts
+    from petit_kernel.moe import moe_align
+    cells = []
+    for name in models:
+        (n13, hp), (hid, ip), E, topk = MODELS[name]
+        g = torch.Generator(device="cuda").manual_seed(3)
+        rnd = lambda rows, cols: torch.randint(-2 ** 31, 2 ** 31 - 1, (rows, cols), dtype=torch.int32, device="cuda", generator=g)  # noqa: E731
+        ex = GptOssExperts(w13=rnd(E * n13 // 16, 2 * hp), s13=torch.randint(118, 124, (E * n13 // 32, hp), dtype=torch.uint8, device="cuda", generator=g),
+                           w2=rnd(E * hid // 16, 2 * ip), s2=torch.randint(118, 124, (E * hid // 32, ip), dtype=torch.uint8, device="cuda", generator=g),
+                           gs13=torch.ones(E, device="cuda"), gs2=torch.ones(E, device="cuda"),
+                           bias13=(torch.randn(E, n13, device="cuda") * 0.5).bfloat16(), bias2=(torch.randn(E, hid, device="cuda") * 0.5).bfloat16(),
+                           hidden=hid, inter=hid, hidden_padded=hp, inter_padded=ip)
+        for T in ts:
+            m = T * topk
+            it = iters if T < 1024 else max(5, iters // 5)
+            x = (torch.randn(T, hid, device="cuda") * 0.05).to(torch.bfloat16)
+            tw, tid = torch.topk(torch.softmax(torch.randn(T, E, device="cuda", generator=g), -1), topk, dim=-1)
+            tw, tid = (tw / tw.sum(-1, keepdim=True)).float().contiguous(), tid.to(torch.int32).contiguous()
+            r = {"model": name, "T": T, "E": E, "topk": topk, "hidden": hid, "padded": hp}
+            r["fused_us"] = graph_us(lambda: ex.forward(x, tw, tid, path="fused"), it)
+            r["native_us"] = graph_us(lambda: ex.forward(x, tw, tid, path="native", activations="mxfp8"), it)
+            sorted_idx, offs = moe_align(tid, E)
+            tok = (sorted_idx // topk).int()
+            xg = ex.pad_hidden(x).index_select(0, sorted_idx // topk)
+            cnt = (offs[1:] - offs[:-1]).tolist()
+            lo_of = offs.tolist()
+            hmid = torch.zeros(m, ip, dtype=torch.bfloat16, device="cuda")
+
+            def loop(_i):
+                for e in range(E):
+                    if cnt[e]:
+                        lo = lo_of[e]
+                        b13 = ex.w13.view(-1)[e * n13 * hp // 8:(e + 1) * n13 * hp // 8].view(n13 // 16, 2 * hp)
+                        s13 = ex.s13.view(-1)[e * n13 * hp // 32:(e + 1) * n13 * hp // 32].view(n13 // 32, hp)
+                        hh = pk.mul_mxfp4_a16(xg[lo:lo + cnt[e]], b13, s13, ex.gs13[e:e + 1], cnt[e], n13, hp, -1, bias=ex.bias13[e],
+                                              activation="swiglu_oai")
+                        b2 = ex.w2.view(-1)[e * hid * ip // 8:(e + 1) * hid * ip // 8].view(hid // 16, 2 * ip)
+                        s2 = ex.s2.view(-1)[e * hid * ip // 32:(e + 1) * hid * ip // 32].view(hid // 32, ip)
+                        pk.mul_mxfp4_a16(hh, b2, s2, ex.gs2[e:e + 1], cnt[e], hid, ip, -1, bias=ex.bias2[e])
+
+            r["loop_us"] = time_us(loop, max(3, it // 4))
+            xp = ex.pad_hidden(x)
+            gate_up = lambda act: pk.mul_mxfp4_a16_moe_indexed(xp, ex.w13, ex.s13, ex.gs13, offs, m, n13, hp, E, a_row_index=tok, bias=ex.bias13,  # noqa: E731
+                                                               activation=act)
+
+            def unfused():
+                y = gate_up(None)
+                gt = y[:, :ip].clamp(max=7.0)
+                return gt * torch.sigmoid(1.702 * gt) * (y[:, ip:].clamp(-7.0, 7.0) + 1)
+
+            r["act_fused_us"] = graph_us(lambda: gate_up("swiglu_oai"), it, 10)
+            r["act_unfused_us"] = graph_us(unfused, it, 10)
+            r["fused_over_loop"] = r["loop_us"] / r["fused_us"]
+            r["native_over_fused"] = r["fused_us"] / r["native_us"]
+            r["act_fused_speedup"] = r["act_unfused_us"] / r["act_fused_us"]
+            print(json.dumps(r), file=sys.stderr, flush=True)
+            cells.append(r)
+        del ex
+        torch.cuda.empty_cache()
+    return cells
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--cells", default="all", choices=["decode", "prefill", "all"])
@@ -312,11 +391,16 @@ def main():
     ap.add_argument("--t", default="", help="--layer: comma-separated token counts (default 1,4,16,64,1024,4096)")
     ap.add_argument("--native", default="", choices=["", "mxfp8", "mxfp6", "mxfp4"],
                     help="--layer: fp4_moe_native with these activations against fp4_moe_fused (MXFP4 raw and NVFP4 images), plus the single-expert cell")
+    ap.add_argument("--gptoss", action="store_true", help="the gpt-oss expert block (petit_kernel.gptoss): layer, host loop, native, fused activation")
     ap.add_argument("--out", default="")
     args = ap.parse_args()
     import petit_kernel as pk
     report = {"device": torch.cuda.get_device_properties(0).gcnArchName, "cells": []}
-    if args.layer and args.native:
+    if args.gptoss:
+        ts = tuple(int(t) for t in args.t.split(",")) if args.t else LAYER_T
+        models = [m for m in args.models.split(",") if m in MODEL_KIND] or list(MODEL_KIND)
+        report["gptoss"] = gptoss_cells(pk, models, ts, args.iters)
+    elif args.layer and args.native:
         ts = tuple(int(t) for t in args.t.split(",")) if args.t else NATIVE_LAYER_T
         report["native_layer"] = native_layer_cells(pk, args.models.split(","), ts, args.iters, args.native)
         report["native_single_expert"] = native_single_expert(pk, args.iters, args.native)
@@ -330,7 +414,7 @@ def main():
         for name in args.models.split(","):
             gate_up, down, E, topk = MODELS[name]
             for proj, (n, k) in (("gate_up", gate_up), ("down", down)):
-                pool = Pool(pk, E, n, k)
+                pool = Pool(pk, E, n, k, MODEL_KIND.get(name, "nv"))
                 for T in ts:
                     r = cell(pk, pool, T, topk, args.iters if T < 1024 else max(5, args.iters // 10), not args.only_loop, not args.only_moe, seed=T)
                     r.update(model=name, proj=proj)
