@@ -55,6 +55,14 @@ def main():
     err_f = (fused.double().cpu() - ref).pow(2).mean().sqrt() / ref.pow(2).mean().sqrt()
     print(f"fp4_moe_fused: rms error / rms = {err_f:.2e}")
     assert err_f < 1e-2
+    # from the router's logits: the routing (softmax, top-k, renormalise; the lower index among equal logits) and the align in one launch
+    logits = torch.randn(T, E, generator=g).to(torch.bfloat16).to(dev)
+    rw, rids = petit_kernel.moe_route(logits, topk, scoring="softmax", renormalize=True)
+    routed = petit_kernel.fp4_moe_routed(x.to(dev), logits, w13, p13, gs13.to(dev), w2, p2, gs2.to(dev), topk, "nvfp4", scoring="softmax",
+                                         renormalize=True)
+    same = petit_kernel.fp4_moe_fused(x.to(dev), w13, p13, gs13.to(dev), w2, p2, gs2.to(dev), rw, rids, "nvfp4")
+    assert torch.equal(routed.view(torch.int16), same.view(torch.int16))
+    print(f"fp4_moe_routed: equals fp4_moe_fused on moe_route's ids {tuple(rids.shape)} and weights bit for bit")
 
 
 if __name__ == "__main__":

@@ -8,7 +8,8 @@ gate_up_proj, a bias on gate_up and on down, hidden = intermediate = 2880), then
     out = experts.forward(x, topk_weights, topk_ids, path="fused" | "native")
 
 and the maximum error of both paths against a float64 statement of the block (dequantised weights, clamped SwiGLU, router weights on
-down + bias).  The router itself (top-k, then softmax over the k) is plain torch here, as it is in gpt-oss.
+down + bias).  The router (top-k, then softmax over the k) is plain torch for the reference; `experts.forward_routed(x, logits)` does it on
+the device, in the align's launch.
 
     python examples/gptoss_moe.py [--experts 8] [--tokens 16] [--hidden 2880]
 """
@@ -74,6 +75,8 @@ def main():
         err = (out.double().cpu() - ref).abs()
         print(f"{path:6s}: out {tuple(out.shape)} {out.dtype}, max |err| {err.max().item():.4g} (output rms {ref.pow(2).mean().sqrt().item():.4g}, "
               f"rms err / rms {(err.pow(2).mean().sqrt() / ref.pow(2).mean().sqrt()).item():.3e})")
+        routed = experts.forward_routed(x.cuda(), logits.cuda(), topk=topk, path=path)   # from the logits: route + align in one launch
+        print(f"{path:6s}: forward_routed max |difference to forward| {(routed.float() - out.float()).abs().max().item():.4g}")
 
 
 if __name__ == "__main__":

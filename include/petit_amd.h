@@ -546,6 +546,65 @@ int petit_moe_combine(void *out, const void *slot_out, const float *topk_weights
                       unsigned topk, unsigned n, unsigned num_experts, int dtype, void *stream);
 
 /*
+ * Routing on the device, from the router's logits: petit_moe_route turns router_logits [num_tokens][num_experts] (contiguous; logits_dtype
+ * PETIT_DTYPE_FP32 / _BF16 / _FP16, converted to fp32 exactly) into the top-k ids and weights the calls above read.  One launch, one wave
+ * per token; no host sync, graph-capturable, no result depends on the order of atomics (there are none).
+ *
+ * Definition.  Two scorings (petit_route_desc.scoring):
+ *   PETIT_ROUTE_SOFTMAX (Mixtral, Qwen3-MoE, gpt-oss): the selection key of expert e is its logit.  Weights: with renormalize != 0 the
+ *     softmax over the k selected logits (this IS "softmax over all, top-k, divide by the sum", and is gpt-oss's "top-k, then softmax over
+ *     the k"); with renormalize == 0 the softmax over all E, taken at the selected experts.  Max-subtracted, fp32.
+ *   PETIT_ROUTE_SIGMOID (DeepSeek-V3 / R1 and descendants): s_e = sigmoid(logit_e); key = s_e + bias[e] (one fp32 add; bias float32 [E],
+ *     null = 0).  With n_group > 1: the experts form n_group contiguous groups of E / n_group; a group's score is the fp32 sum of its two
+ *     largest keys (largest first); the topk_group groups with the largest scores are kept and only their experts can be selected.
+ *     Weights: the UNBIASED s_e of the selected experts, divided by (their sum + 1e-20) when renormalize, then times routed_scaling_factor.
+ *   Selection, both scorings, experts and groups alike: larger key first; among equal keys the LOWER index first (-0 equals +0).  The k ids
+ *     of a token are written in selection order (slot 0 = best) and are distinct.  A NaN key ranks below every number (as -inf; among
+ *     themselves by index), so ids are always distinct and inside [0, E); the weights of a row that holds a NaN or a +inf (or only -inf)
+ *     are unspecified, its ids are not.
+ *   Outputs: topk_ids int32 [T][topk], topk_weights float32 [T][topk] (what petit_moe_align / petit_moe_combine read) and, when keys_out is
+ *     not null, keys_out float32 [T][E]: the selection keys the kernel ranked (softmax: the logits, bit for bit).
+ *
+ * Accuracy of the weights, relative to the definition evaluated exactly on the same fp32 logits (u = 2^-24; expf and the fp32 divide are
+ * the device library's: expf within 1 ulp = 2 u, the divide correctly rounded = 1 u; D = the largest |logit - row max| among the terms):
+ *   the kernel's sequence is  d = x - max (1 rounding of d: a factor exp(+-u D / 2) on the term, <= u D / 2),  t = expf(d) (2 u),  the sum
+ *   of positive terms -- the k selected ones in a 6-deep tree over the lanes, or for renormalize == 0 each lane's <= 16 experts in order and
+ *   then that tree, <= 21 additions deep (1 u per level) --,  t / sum (1 u),  times the scaling factor (1 u).
+ *     softmax, renormalize:      (2 + D/2) + (2 + D/2 + 6) + 1 + 1  = (12 + D) u
+ *     softmax, all E:            (2 + D/2) + (2 + D/2 + 21) + 1 + 1 = (27 + D) u
+ *     sigmoid: s = 1 / (1 + expf(-x)): expf 2 u (damped by e / (1 + e) <= 1), the add 1 u, the divide 1 u: 4 u on s.  Without renormalize
+ *       4 + 1 = 5 u; with: 4 + (4 + 6 + 1 for the 1e-20) + 1 + 1 = 17 u.  A key is s + bias: |key error| <= 4 u s + u |key|.
+ *   For logits within 16 of their row's maximum every case is below 48 u < 2^-18, far inside the 2^-16 the 16-bit layers could see.
+ *
+ * petit_moe_route_align: petit_moe_route followed by petit_moe_align on its ids, same outputs bit for bit.  When num_tokens * topk <= 1024
+ * (the align's one-launch case, every decode batch) it is ONE launch: the align's workgroup routes the tokens first.  Above: the route
+ * launch, then the align's three.  workspace: petit_moe_route_align_workspace_bytes() = petit_moe_align_workspace_bytes().
+ *
+ * Errors, all before any launch: PETIT_ERROR_PROBLEM_SHAPE for null pointers, topk == 0, topk > num_experts, topk > PETIT_MOE_MAX_TOPK,
+ * num_experts outside 1..PETIT_MOE_MAX_EXPERTS, num_tokens * topk >= 2^31, num_experts % n_group != 0, groups of fewer than 2 experts,
+ * topk_group outside 1..n_group, topk > topk_group * (E / n_group), groups or a bias with the softmax scoring, several chunks without a
+ * workspace; PETIT_ERROR_BAD_ARGUMENT for a logits_dtype or scoring that does not exist.  num_tokens == 0 is PETIT_OK (petit_moe_route_align
+ * then writes the all-zero expert_offsets, as petit_moe_align does).  desc null = a zero-initialised one.
+ * Not here: an expert map for expert parallelism (map ids to -1 afterwards), the router's own GEMM, auxiliary-loss outputs beyond keys_out.
+ */
+#define PETIT_ROUTE_SOFTMAX 0
+#define PETIT_ROUTE_SIGMOID 1
+#define PETIT_MOE_MAX_TOPK 64
+typedef struct petit_route_desc { /* zero-initialised = softmax, no renormalise, no groups */
+    int scoring;                  /* PETIT_ROUTE_SOFTMAX | PETIT_ROUTE_SIGMOID */
+    int renormalize;
+    unsigned n_group, topk_group; /* 0 or 1: no groups.  Groups need scoring == PETIT_ROUTE_SIGMOID */
+    float routed_scaling_factor;  /* 0 is read as 1 */
+    const float *bias;            /* [num_experts] or null; PETIT_ROUTE_SIGMOID only */
+} petit_route_desc;
+int petit_moe_route(const void *router_logits, int logits_dtype, unsigned num_tokens, unsigned num_experts, unsigned topk,
+                    const petit_route_desc *desc, int32_t *topk_ids, float *topk_weights, float *keys_out, void *stream);
+uint64_t petit_moe_route_align_workspace_bytes(unsigned num_tokens, unsigned topk, unsigned num_experts);
+int petit_moe_route_align(const void *router_logits, int logits_dtype, unsigned num_tokens, unsigned num_experts, unsigned topk,
+                          const petit_route_desc *desc, int32_t *topk_ids, float *topk_weights, float *keys_out, int32_t *expert_offsets,
+                          int32_t *sorted_pos, int32_t *token_index, void *workspace, void *stream);
+
+/*
  * Native-class MoE launch (no counterpart in the reference): the routed-expert launch on the block-scaled MFMA, the accuracy class of
  * petit_gemm_mxfp4_native (activations quantised to MXFP8 / MXFP6 / MXFP4; the per-element bound is the native block's above).  Opt-in
  * like every native call: solution_id is a PETIT_SOLUTION_AUTO_NATIVE_* sentinel or an explicit native id that has a MoE form (the 128 x 256

@@ -7,6 +7,11 @@
 // The first two terms come from per-chunk histograms (LDS counters: a count does not depend on the order of its increments) and a
 // scan over (expert, chunk); the third from the chunk's ids in LDS, each entry counting its equals among the entries before it.
 // One chunk (num_tokens * topk <= kChunk, every decode batch) does all of it in ONE launch; more take three (count, scan, place).
+//
+// Route: petit_moe_route turns router logits into top-k ids and weights, one wave per token: lane l holds the keys of experts l, l + 64, ...
+// in registers (E <= 1024: 16 at most) as order-preserving unsigned ranks, and every selection -- of groups, then of experts -- is a round of
+// a wave-wide arg-max on (rank, lowest index) with the winner masked out.  No LDS, no atomics.  petit_moe_route_align runs the same code in
+// the align's single workgroup when the routing is one chunk: the ids go to the LDS array the align sorts, route + align are ONE launch.
 #include <hip/hip_runtime.h>
 
 #include "../../include/petit_amd.h"
@@ -48,18 +53,22 @@ __device__ __forceinline__ unsigned block_exclusive_scan(unsigned v, unsigned *w
     return before + incl - v;
 }
 
+// the histogram of the chunk's ids (one per thread) into cnt[0 .. num_experts); the caller's barrier publishes it
+__device__ __forceinline__ void chunk_histogram(int id, unsigned *cnt) {
+    cnt[threadIdx.x] = 0; // (num_experts <= kChunk)
+    __syncthreads();
+    if (id >= 0)
+        atomicAdd(&cnt[id], 1u);
+}
+
 // the chunk's ids into LDS (-1: unrouted or past the end); the chunk's histogram into cnt[0 .. num_experts) when cnt is given
 __device__ __forceinline__ int load_chunk(const void *ids, bool i64, unsigned n_entries, unsigned num_experts, unsigned chunk, int *ids_s,
                                           unsigned *cnt) {
     const unsigned p = chunk * kChunk + threadIdx.x;
     const int id = p < n_entries ? routed_id(ids, i64, p, num_experts) : -1;
     ids_s[threadIdx.x] = id;
-    if (cnt) {
-        cnt[threadIdx.x] = 0; // (num_experts <= kChunk)
-        __syncthreads();
-        if (id >= 0)
-            atomicAdd(&cnt[id], 1u);
-    }
+    if (cnt)
+        chunk_histogram(id, cnt);
     __syncthreads();
     return id;
 }
@@ -88,15 +97,9 @@ __device__ __forceinline__ void fill_tail(unsigned routed, unsigned n_entries, i
         sorted_pos[r] = -1, token_index[r] = -1;
 }
 
-// one chunk: everything in one workgroup
-__global__ __launch_bounds__(kChunk) void moe_align_one_kernel(const void *ids, unsigned i64, unsigned n_entries, unsigned topk,
-                                                               unsigned num_experts, int *offsets, int *sorted_pos, int *token_index) {
-    __shared__ __attribute__((aligned(16))) int ids_s[kChunk]; // (read as int4: rank_in_chunk)
-    __shared__ unsigned cnt[kChunk], wave_sums[kChunk / 64];
-    const int id = load_chunk(ids, i64 != 0, n_entries, num_experts, 0, ids_s, cnt);
-    const unsigned c = threadIdx.x < num_experts ? cnt[threadIdx.x] : 0u;
-    unsigned routed;
-    const unsigned base = block_exclusive_scan(c, wave_sums, &routed);
+// one chunk, after the scan of its histogram: the offsets, every entry to its position, the unrouted tail
+__device__ __forceinline__ void align_one_place(int id, const int *ids_s, unsigned *cnt, unsigned base, unsigned routed, unsigned n_entries,
+                                                unsigned topk, unsigned num_experts, int *offsets, int *sorted_pos, int *token_index) {
     if (threadIdx.x < num_experts)
         offsets[threadIdx.x] = (int)base;
     if (threadIdx.x == 0)
@@ -106,6 +109,18 @@ __global__ __launch_bounds__(kChunk) void moe_align_one_kernel(const void *ids, 
     if (id >= 0)
         place(cnt[id] + rank_in_chunk(ids_s, id), topk, sorted_pos, token_index);
     fill_tail(routed, n_entries, sorted_pos, token_index);
+}
+
+// one chunk: everything in one workgroup
+__global__ __launch_bounds__(kChunk) void moe_align_one_kernel(const void *ids, unsigned i64, unsigned n_entries, unsigned topk,
+                                                               unsigned num_experts, int *offsets, int *sorted_pos, int *token_index) {
+    __shared__ __attribute__((aligned(16))) int ids_s[kChunk]; // (read as int4: rank_in_chunk)
+    __shared__ unsigned cnt[kChunk], wave_sums[kChunk / 64];
+    const int id = load_chunk(ids, i64 != 0, n_entries, num_experts, 0, ids_s, cnt);
+    const unsigned c = threadIdx.x < num_experts ? cnt[threadIdx.x] : 0u;
+    unsigned routed;
+    const unsigned base = block_exclusive_scan(c, wave_sums, &routed);
+    align_one_place(id, ids_s, cnt, base, routed, n_entries, topk, num_experts, offsets, sorted_pos, token_index);
 }
 
 // several chunks, 1/3: the per-chunk histograms, ws[chunk][expert]
@@ -201,11 +216,325 @@ __global__ __launch_bounds__(256) void moe_combine_kernel(void *out, const void 
     }
 }
 
+// --- Route: router logits -> top-k ids and weights (the definition: include/petit_amd.h "Routing on the device") ---------------------------
+
+constexpr unsigned kMaxTopk = 64;        // PETIT_MOE_MAX_TOPK: slot r of a token is lane r's
+constexpr unsigned kRouteWaves = 4;      // waves (= tokens) per workgroup of the grid form
+constexpr int kDataTypeFp32 = 100;       // PETIT_DTYPE_FP32
+
+struct RouteArgs {
+    const void *logits; // [num_tokens][num_experts], dtype
+    const float *bias;  // [num_experts] or null (sigmoid scoring)
+    int *ids;           // [num_tokens][topk]
+    float *weights;     // [num_tokens][topk]
+    float *keys;        // [num_tokens][num_experts] or null
+    int dtype;
+    unsigned num_tokens, num_experts, topk;
+    unsigned sigmoid, renorm, n_group, topk_group; // n_group 1: no groups
+    float scale;
+};
+
+__device__ __forceinline__ float route_logit(const void *logits, int dtype, size_t i) {
+    if (dtype == kDataTypeFp32)
+        return ((const float *)logits)[i];
+    const unsigned short h = ((const unsigned short *)logits)[i];
+    return dtype == kDataTypeBf16 ? half_to_f32<true>(h) : half_to_f32<false>(h);
+}
+
+__device__ __forceinline__ float route_sigmoid(float x) {
+#pragma clang fp contract(off)
+    return 1.f / (1.f + expf(-x));
+}
+
+// A key as an unsigned that orders as the selection does: larger key = larger rank, NaN as -inf, -0 as +0.  Every key's rank is > 0: 0 marks
+// an entry that cannot be selected (past E, outside the kept groups, already taken).  rank_key is the inverse on ranks > 0.
+__device__ __forceinline__ unsigned key_rank(float k) {
+    const float c = k != k ? -__builtin_inff() : (k == 0.f ? 0.f : k);
+    const unsigned b = __builtin_bit_cast(unsigned, c);
+    return (b & 0x80000000u) ? ~b : (b | 0x80000000u);
+}
+__device__ __forceinline__ float rank_key(unsigned u) { return __builtin_bit_cast(float, (u & 0x80000000u) ? (u & 0x7fffffffu) : ~u); }
+
+// The value of a lane in the other half of this lane's aligned group of 2 d lanes, for butterfly reductions whose lanes all hold their group's
+// result after every step (so "a lane of the other half" is all a step needs): DPP inside a row of 16, a permute across rows.
+template <int kCtrl> __device__ __forceinline__ unsigned dpp_mov(unsigned v) {
+    return (unsigned)__builtin_amdgcn_update_dpp((int)v, (int)v, kCtrl, 0xf, 0xf, false);
+}
+template <unsigned d> __device__ __forceinline__ unsigned other_half(unsigned v) {
+    if constexpr (d == 1)
+        return dpp_mov<0xB1>(v); // quad_perm [1, 0, 3, 2]
+    else if constexpr (d == 2)
+        return dpp_mov<0x4E>(v); // quad_perm [2, 3, 0, 1]
+    else if constexpr (d == 4)
+        return dpp_mov<0x141>(v); // row_half_mirror
+    else if constexpr (d == 8)
+        return dpp_mov<0x140>(v); // row_mirror
+    else
+        return (unsigned)__shfl_xor((int)v, (int)d);
+}
+template <unsigned d> __device__ __forceinline__ float other_half(float v) {
+    return __builtin_bit_cast(float, other_half<d>(__builtin_bit_cast(unsigned, v)));
+}
+
+template <unsigned d> __device__ __forceinline__ void select_step(unsigned &hi, unsigned &lo) {
+    const unsigned oh = other_half<d>(hi), ol = other_half<d>(lo);
+    const bool take = oh > hi || (oh == hi && ol > lo);
+    hi = take ? oh : hi;
+    lo = take ? ol : lo;
+}
+
+// One selection round over the wave's N * 64 entries (entry j * 64 + lane has rank u[j]): the index of the largest rank, the LOWEST index
+// among equal ranks; every lane gets it.  (The pair (rank, ~index) is maximised: a total order, so the result does not depend on the
+// reduction's shape.)
+template <int N> __device__ __forceinline__ unsigned wave_select(const unsigned (&u)[N], unsigned lane) {
+    unsigned hi = 0, lo = 0;
+#pragma unroll
+    for (int j = N - 1; j >= 0; --j)
+        if (u[j] >= hi)
+            hi = u[j], lo = ~((unsigned)j * 64u + lane);
+    select_step<1>(hi, lo);
+    select_step<2>(hi, lo);
+    select_step<4>(hi, lo);
+    select_step<8>(hi, lo);
+    select_step<16>(hi, lo);
+    select_step<32>(hi, lo);
+    return ~lo;
+}
+
+// the wave's sum, a fixed tree: lanes pairwise, then pairs, ... (6 additions deep); every lane gets it
+__device__ __forceinline__ float wave_sum(float v) {
+#pragma clang fp contract(off)
+    v = v + other_half<1>(v);
+    v = v + other_half<2>(v);
+    v = v + other_half<4>(v);
+    v = v + other_half<8>(v);
+    v = v + other_half<16>(v);
+    v = v + other_half<32>(v);
+    return v;
+}
+
+template <unsigned d> __device__ __forceinline__ void top2_step(float &a1, float &a2) {
+    const float b1 = other_half<d>(a1), b2 = other_half<d>(a2);
+    a2 = fmaxf(fminf(a1, b1), fmaxf(a2, b2));
+    a1 = fmaxf(a1, b1);
+}
+
+// One token by one wave (all 64 lanes, wave-uniform control flow).  NJ = ceil(E / 64) rounded up to a power of two: keys per lane.
+// Lane r < topk returns slot r's id and weight.
+template <int NJ> __device__ __forceinline__ void route_token(const RouteArgs &ra, unsigned t, unsigned lane, int *id_out, float *w_out) {
+#pragma clang fp contract(off)
+    const unsigned E = ra.num_experts;
+    const size_t row = (size_t)t * E;
+    unsigned u[NJ];
+#pragma unroll
+    for (int j = 0; j < NJ; ++j) {
+        const unsigned e = (unsigned)j * 64u + lane;
+        u[j] = 0;
+        if (e < E) {
+            float key = route_logit(ra.logits, ra.dtype, row + e);
+            if (ra.sigmoid) {
+                key = route_sigmoid(key);
+                if (ra.bias)
+                    key = key + ra.bias[e];
+            }
+            if (ra.keys)
+                ra.keys[row + e] = key;
+            u[j] = key_rank(key);
+        }
+    }
+
+    if (ra.n_group > 1) {
+        // group scores: the sum of each group's two largest keys, group g's in lane g % 64, slot g / 64
+        constexpr int NG = NJ > 1 ? NJ / 2 : 1; // (groups hold >= 2 experts: n_group <= 32 NJ)
+        const unsigned G = E / ra.n_group;
+        unsigned gu[NG];
+#pragma unroll
+        for (int s = 0; s < NG; ++s)
+            gu[s] = 0;
+        for (unsigned g = 0; g < ra.n_group; ++g) {
+            const unsigned lo = g * G, hi = lo + G;
+            float a1 = -__builtin_inff(), a2 = -__builtin_inff();
+#pragma unroll
+            for (int j = 0; j < NJ; ++j) {
+                if (hi <= (unsigned)j * 64u || lo >= (unsigned)(j + 1) * 64u)
+                    continue; // (wave-uniform)
+                const unsigned e = (unsigned)j * 64u + lane;
+                const float v = (e >= lo && e < hi) ? rank_key(u[j]) : -__builtin_inff();
+                a2 = fmaxf(a2, fminf(a1, v));
+                a1 = fmaxf(a1, v);
+            }
+            top2_step<1>(a1, a2);
+            top2_step<2>(a1, a2);
+            top2_step<4>(a1, a2);
+            top2_step<8>(a1, a2);
+            top2_step<16>(a1, a2);
+            top2_step<32>(a1, a2);
+            const unsigned r = key_rank(a1 + a2);
+#pragma unroll
+            for (int s = 0; s < NG; ++s)
+                if (g == (unsigned)s * 64u + lane)
+                    gu[s] = r;
+        }
+        // the topk_group best groups; only their experts stay selectable
+        unsigned allow = 0;
+        for (unsigned r = 0; r < ra.topk_group; ++r) {
+            const unsigned g = wave_select<NG>(gu, lane);
+#pragma unroll
+            for (int s = 0; s < NG; ++s)
+                if (g == (unsigned)s * 64u + lane)
+                    gu[s] = 0;
+            const unsigned lo = g * G, hi = lo + G;
+#pragma unroll
+            for (int j = 0; j < NJ; ++j) {
+                const unsigned e = (unsigned)j * 64u + lane;
+                allow |= (e >= lo && e < hi) ? 1u << j : 0u;
+            }
+        }
+#pragma unroll
+        for (int j = 0; j < NJ; ++j)
+            u[j] = (allow >> j & 1u) ? u[j] : 0u;
+    }
+
+    unsigned my_id = 0;
+    for (unsigned r = 0; r < ra.topk; ++r) {
+        unsigned e = wave_select<NJ>(u, lane);
+        e = e < E ? e : E - 1; // (always true: topk selectable entries exist; keeps the loads below inside the row whatever happens)
+#pragma unroll
+        for (int j = 0; j < NJ; ++j)
+            if (e == (unsigned)j * 64u + lane)
+                u[j] = 0;
+        if (lane == r)
+            my_id = e;
+    }
+
+    // weights: lane r < topk holds slot r
+    const bool mine = lane < ra.topk;
+    const float x = mine ? route_logit(ra.logits, ra.dtype, row + my_id) : 0.f;
+    float v, denom = 1.f;
+    bool divide = ra.renorm != 0;
+    if (ra.sigmoid) {
+        v = mine ? route_sigmoid(x) : 0.f;
+        if (divide)
+            denom = wave_sum(v) + 1e-20f;
+    } else {
+        const float mx = __shfl(x, 0); // slot 0 is the row's largest logit
+        v = mine ? expf(x - mx) : 0.f;
+        if (divide) {
+            denom = wave_sum(v);
+        } else { // the softmax over all E: each lane's experts in ascending order, then the wave's tree
+            float part = 0.f;
+            for (unsigned e = lane; e < E; e += 64)
+                part = part + expf(route_logit(ra.logits, ra.dtype, row + e) - mx);
+            denom = wave_sum(part);
+            divide = true;
+        }
+    }
+    float w = v;
+    if (divide)
+        w = w / denom;
+    w = w * ra.scale;
+    *id_out = (int)my_id;
+    *w_out = w;
+}
+
+// the grid form: one wave per token
+template <int NJ> __global__ __launch_bounds__(kRouteWaves * 64) void moe_route_kernel(RouteArgs ra) {
+    const unsigned lane = threadIdx.x & 63u, t = blockIdx.x * kRouteWaves + (threadIdx.x >> 6);
+    if (t >= ra.num_tokens)
+        return; // (a whole wave)
+    int id;
+    float w;
+    route_token<NJ>(ra, t, lane, &id, &w);
+    if (lane < ra.topk) {
+        ra.ids[(size_t)t * ra.topk + lane] = id;
+        ra.weights[(size_t)t * ra.topk + lane] = w;
+    }
+}
+
+// one chunk (num_tokens * topk <= kChunk): the workgroup's 16 waves route the tokens, the ids go to LDS as load_chunk leaves them (and to
+// memory with the weights, for the combine), and the align's one-chunk code follows
+template <int NJ> __global__ __launch_bounds__(kChunk) void moe_route_align_one_kernel(RouteArgs ra, int *offsets, int *sorted_pos, int *token_index) {
+    __shared__ __attribute__((aligned(16))) int ids_s[kChunk]; // (read as int4: rank_in_chunk)
+    __shared__ unsigned cnt[kChunk], wave_sums[kChunk / 64];
+    const unsigned lane = threadIdx.x & 63u, n_entries = ra.num_tokens * ra.topk;
+    if (threadIdx.x >= n_entries)
+        ids_s[threadIdx.x] = -1;
+    for (unsigned t = threadIdx.x >> 6; t < ra.num_tokens; t += kChunk / 64) {
+        int id;
+        float w;
+        route_token<NJ>(ra, t, lane, &id, &w);
+        if (lane < ra.topk) {
+            const unsigned p = t * ra.topk + lane; // (< n_entries <= kChunk)
+            ra.ids[p] = id;
+            ra.weights[p] = w;
+            ids_s[p] = id;
+        }
+    }
+    __syncthreads();
+    const int id = ids_s[threadIdx.x];
+    chunk_histogram(id, cnt);
+    __syncthreads();
+    const unsigned c = threadIdx.x < ra.num_experts ? cnt[threadIdx.x] : 0u;
+    unsigned routed;
+    const unsigned base = block_exclusive_scan(c, wave_sums, &routed);
+    align_one_place(id, ids_s, cnt, base, routed, n_entries, ra.topk, ra.num_experts, offsets, sorted_pos, token_index);
+}
+
 bool route_shape_ok(unsigned num_tokens, unsigned topk, unsigned num_experts) {
     return topk != 0 && num_experts != 0 && num_experts <= kMoeMaxExperts && (uint64_t)num_tokens * topk < (1ull << 31);
 }
 
 unsigned align_chunks(unsigned num_tokens, unsigned topk) { return (unsigned)(((uint64_t)num_tokens * topk + kChunk - 1) / kChunk); }
+
+// every refusal of petit_moe_route / petit_moe_route_align that does not depend on a pointer; fills ra's scalar fields
+int route_check(int logits_dtype, unsigned num_tokens, unsigned num_experts, unsigned topk, const petit_route_desc *desc, RouteArgs *ra) {
+    static const petit_route_desc kDefault = {};
+    const petit_route_desc &d = desc ? *desc : kDefault;
+    if (!route_shape_ok(num_tokens, topk, num_experts) || topk > num_experts || topk > kMaxTopk)
+        return kErrProblemShape;
+    if (logits_dtype != kDataTypeFp32 && logits_dtype != kDataTypeBf16 && logits_dtype != kDataTypeFp16)
+        return kErrBadArgument;
+    if (d.scoring != PETIT_ROUTE_SOFTMAX && d.scoring != PETIT_ROUTE_SIGMOID)
+        return kErrBadArgument;
+    const unsigned n_group = d.n_group ? d.n_group : 1u;
+    if (n_group > 1) {
+        if (d.scoring != PETIT_ROUTE_SIGMOID || num_experts % n_group != 0 || num_experts / n_group < 2 || d.topk_group < 1 ||
+            d.topk_group > n_group || (uint64_t)topk > (uint64_t)d.topk_group * (num_experts / n_group))
+            return kErrProblemShape;
+    } else if (d.topk_group > 1) {
+        return kErrProblemShape; // topk_group outside 1..n_group
+    }
+    if (d.bias && d.scoring != PETIT_ROUTE_SIGMOID)
+        return kErrProblemShape;
+    ra->bias = d.bias;
+    ra->dtype = logits_dtype;
+    ra->num_tokens = num_tokens, ra->num_experts = num_experts, ra->topk = topk;
+    ra->sigmoid = d.scoring == PETIT_ROUTE_SIGMOID, ra->renorm = d.renormalize != 0;
+    ra->n_group = n_group, ra->topk_group = n_group > 1 ? d.topk_group : 1u;
+    ra->scale = d.routed_scaling_factor == 0.f ? 1.f : d.routed_scaling_factor;
+    return kOk;
+}
+
+template <int NJ> void launch_route(const RouteArgs &ra, bool with_align, int32_t *offsets, int32_t *sorted_pos, int32_t *token_index, hipStream_t s) {
+    if (with_align)
+        hipLaunchKernelGGL(moe_route_align_one_kernel<NJ>, dim3(1), dim3(kChunk), 0, s, ra, offsets, sorted_pos, token_index);
+    else
+        hipLaunchKernelGGL(moe_route_kernel<NJ>, dim3((ra.num_tokens + kRouteWaves - 1) / kRouteWaves), dim3(kRouteWaves * 64), 0, s, ra);
+}
+
+void launch_route(const RouteArgs &ra, bool with_align, int32_t *offsets, int32_t *sorted_pos, int32_t *token_index, hipStream_t s) {
+    const unsigned E = ra.num_experts;
+    if (E <= 64)
+        launch_route<1>(ra, with_align, offsets, sorted_pos, token_index, s);
+    else if (E <= 128)
+        launch_route<2>(ra, with_align, offsets, sorted_pos, token_index, s);
+    else if (E <= 256)
+        launch_route<4>(ra, with_align, offsets, sorted_pos, token_index, s);
+    else if (E <= 512)
+        launch_route<8>(ra, with_align, offsets, sorted_pos, token_index, s);
+    else
+        launch_route<16>(ra, with_align, offsets, sorted_pos, token_index, s);
+}
 
 } // namespace
 
@@ -261,6 +590,51 @@ int petit_moe_combine(void *out, const void *slot_out, const float *topk_weights
     else
         hipLaunchKernelGGL(moe_combine_kernel<false>, dim3(blocks), dim3(256), 0, (hipStream_t)stream, out, slot_out, topk_weights, topk_ids, i64,
                            num_tokens, topk, n, num_experts);
+    return hipGetLastError() == hipSuccess ? kOk : kErrLaunch;
+}
+
+int petit_moe_route(const void *router_logits, int logits_dtype, unsigned num_tokens, unsigned num_experts, unsigned topk,
+                    const petit_route_desc *desc, int32_t *topk_ids, float *topk_weights, float *keys_out, void *stream) {
+    RouteArgs ra;
+    const int rc = route_check(logits_dtype, num_tokens, num_experts, topk, desc, &ra);
+    if (rc != kOk)
+        return rc;
+    if (num_tokens == 0)
+        return kOk;
+    if (!router_logits || !topk_ids || !topk_weights)
+        return kErrProblemShape;
+    ra.logits = router_logits, ra.ids = topk_ids, ra.weights = topk_weights, ra.keys = keys_out;
+    launch_route(ra, false, nullptr, nullptr, nullptr, (hipStream_t)stream);
+    return hipGetLastError() == hipSuccess ? kOk : kErrLaunch;
+}
+
+uint64_t petit_moe_route_align_workspace_bytes(unsigned num_tokens, unsigned topk, unsigned num_experts) {
+    return petit_moe_align_workspace_bytes(num_tokens, topk, num_experts);
+}
+
+int petit_moe_route_align(const void *router_logits, int logits_dtype, unsigned num_tokens, unsigned num_experts, unsigned topk,
+                          const petit_route_desc *desc, int32_t *topk_ids, float *topk_weights, float *keys_out, int32_t *expert_offsets,
+                          int32_t *sorted_pos, int32_t *token_index, void *workspace, void *stream) {
+    RouteArgs ra;
+    const int rc = route_check(logits_dtype, num_tokens, num_experts, topk, desc, &ra);
+    if (rc != kOk)
+        return rc;
+    if (!expert_offsets)
+        return kErrProblemShape;
+    if (num_tokens && (!router_logits || !topk_ids || !topk_weights || !sorted_pos || !token_index))
+        return kErrProblemShape;
+    if (align_chunks(num_tokens, topk) > 1 && !workspace)
+        return kErrProblemShape;
+    if (num_tokens == 0 || align_chunks(num_tokens, topk) > 1) { // nothing to route, or several chunks: the route grid, then the align's launches
+        if (num_tokens) {
+            const int rr = petit_moe_route(router_logits, logits_dtype, num_tokens, num_experts, topk, desc, topk_ids, topk_weights, keys_out, stream);
+            if (rr != kOk)
+                return rr;
+        }
+        return petit_moe_align(topk_ids, 0, num_tokens, topk, num_experts, expert_offsets, sorted_pos, token_index, workspace, stream);
+    }
+    ra.logits = router_logits, ra.ids = topk_ids, ra.weights = topk_weights, ra.keys = keys_out;
+    launch_route(ra, true, expert_offsets, sorted_pos, token_index, (hipStream_t)stream);
     return hipGetLastError() == hipSuccess ? kOk : kErrLaunch;
 }
 

@@ -13,6 +13,7 @@
 #include <ATen/hip/impl/HIPStreamMasqueradingAsCUDA.h>
 #include <torch/library.h>
 
+#include <algorithm>
 #include <string>
 
 #include "../../include/petit_amd.h"
@@ -302,6 +303,70 @@ at::Tensor moe_combine(const at::Tensor &slot_out, const at::Tensor &topk_weight
     return out;
 }
 
+// routing from the logits (petit_moe_route / petit_moe_route_align); the same checks and texts as petit_kernel/ops.py _check_route
+#define PETIT_ROUTE_ARGS                                                                                                                     \
+    const at::Tensor &router_logits, int64_t topk, int64_t scoring, bool renormalize, const std::optional<at::Tensor> &bias, int64_t n_group, \
+        int64_t topk_group, double routed_scaling_factor, bool return_keys
+int route_logits_dtype(const at::Tensor &t) {
+    return t.scalar_type() == at::kFloat ? PETIT_DTYPE_FP32 : t.scalar_type() == at::kBFloat16 ? kCxxBf16 : kCxxFp16;
+}
+petit_route_desc check_route(PETIT_ROUTE_ARGS) {
+    TORCH_CHECK(scoring == PETIT_ROUTE_SOFTMAX || scoring == PETIT_ROUTE_SIGMOID, "scoring must be 'softmax' or 'sigmoid'");
+    TORCH_CHECK(router_logits.is_cuda() && router_logits.dim() == 2 && router_logits.is_contiguous() &&
+                    (router_logits.scalar_type() == at::kFloat || router_logits.scalar_type() == at::kBFloat16 ||
+                     router_logits.scalar_type() == at::kHalf),
+                "router_logits must be a contiguous float32 / bfloat16 / float16 [num_tokens, num_experts] GPU tensor");
+    const int64_t E = router_logits.size(1);
+    TORCH_CHECK(E >= 1 && E <= PETIT_MOE_MAX_EXPERTS, "num_experts must be in 1..", PETIT_MOE_MAX_EXPERTS, ", got ", E);
+    TORCH_CHECK(topk >= 1 && topk <= std::min<int64_t>(E, PETIT_MOE_MAX_TOPK), "topk must be in 1..min(num_experts, ", PETIT_MOE_MAX_TOPK, "), got ",
+                topk);
+    TORCH_CHECK(n_group >= 1 && topk_group >= 1, "n_group and topk_group must be >= 1");
+    if (bias) {
+        TORCH_CHECK(scoring == PETIT_ROUTE_SIGMOID, "bias needs scoring='sigmoid'");
+        TORCH_CHECK(bias->is_cuda() && bias->device() == router_logits.device() && bias->scalar_type() == at::kFloat && bias->is_contiguous() &&
+                        bias->dim() == 1 && bias->size(0) == E,
+                    "bias must be a contiguous float32 [num_experts] tensor on router_logits' device");
+    }
+    petit_route_desc d{};
+    d.scoring = (int)scoring, d.renormalize = renormalize, d.n_group = (unsigned)n_group, d.topk_group = (unsigned)topk_group;
+    d.routed_scaling_factor = (float)routed_scaling_factor, d.bias = bias ? (const float *)bias->data_ptr() : nullptr;
+    return d;
+}
+void route_rc(int rc, const char *what, int64_t T, int64_t E, int64_t topk, int64_t n_group, int64_t topk_group) {
+    TORCH_CHECK(rc != PETIT_ERROR_PROBLEM_SHAPE, "Incompatible routing shape (num_tokens=", T, ", num_experts=", E, ", topk=", topk, ", n_group=", n_group,
+                ", topk_group=", topk_group, ")");
+    TORCH_CHECK(rc == PETIT_OK, what, ": ", petit_error_string(rc));
+}
+std::tuple<at::Tensor, at::Tensor, at::Tensor> moe_route(PETIT_ROUTE_ARGS) {
+    const petit_route_desc d = check_route(router_logits, topk, scoring, renormalize, bias, n_group, topk_group, routed_scaling_factor, return_keys);
+    const int64_t T = router_logits.size(0), E = router_logits.size(1);
+    const c10::hip::HIPGuardMasqueradingAsCUDA guard(router_logits.device());
+    at::Tensor ids = at::empty({T, topk}, router_logits.options().dtype(at::kInt)), w = at::empty({T, topk}, router_logits.options().dtype(at::kFloat));
+    at::Tensor keys = return_keys ? at::empty({T, E}, w.options()) : at::empty({0}, w.options());
+    const int rc = petit_moe_route(router_logits.data_ptr(), route_logits_dtype(router_logits), (unsigned)T, (unsigned)E, (unsigned)topk, &d,
+                                   (int32_t *)ids.data_ptr(), (float *)w.data_ptr(), return_keys ? (float *)keys.data_ptr() : nullptr,
+                                   stream_of(router_logits));
+    route_rc(rc, "moe_route", T, E, topk, n_group, topk_group);
+    return {w, ids, keys};
+}
+std::tuple<at::Tensor, at::Tensor, at::Tensor, at::Tensor, at::Tensor, at::Tensor> moe_route_align(PETIT_ROUTE_ARGS) {
+    const petit_route_desc d = check_route(router_logits, topk, scoring, renormalize, bias, n_group, topk_group, routed_scaling_factor, return_keys);
+    const int64_t T = router_logits.size(0), E = router_logits.size(1);
+    const c10::hip::HIPGuardMasqueradingAsCUDA guard(router_logits.device());
+    const auto i32 = router_logits.options().dtype(at::kInt);
+    at::Tensor ids = at::empty({T, topk}, i32), w = at::empty({T, topk}, router_logits.options().dtype(at::kFloat));
+    at::Tensor keys = return_keys ? at::empty({T, E}, w.options()) : at::empty({0}, w.options());
+    at::Tensor sorted_pos = at::empty({T * topk}, i32), token_index = at::empty({T * topk}, i32), offsets = at::empty({E + 1}, i32);
+    const uint64_t ws_bytes = petit_moe_route_align_workspace_bytes((unsigned)T, (unsigned)topk, (unsigned)E);
+    at::Tensor ws = at::empty({(int64_t)ws_bytes}, router_logits.options().dtype(at::kByte));
+    const int rc = petit_moe_route_align(router_logits.data_ptr(), route_logits_dtype(router_logits), (unsigned)T, (unsigned)E, (unsigned)topk, &d,
+                                         (int32_t *)ids.data_ptr(), (float *)w.data_ptr(), return_keys ? (float *)keys.data_ptr() : nullptr,
+                                         (int32_t *)offsets.data_ptr(), (int32_t *)sorted_pos.data_ptr(), (int32_t *)token_index.data_ptr(),
+                                         ws_bytes ? ws.data_ptr() : nullptr, stream_of(router_logits));
+    route_rc(rc, "moe_route_align", T, E, topk, n_group, topk_group);
+    return {w, ids, sorted_pos, offsets, token_index, keys};
+}
+
 // native-class MoE launch (petit_gemm_native_moe); the same checks and texts as petit_kernel/ops.py _mul_native_moe.  A: 16-bit [a_rows,
 // size_k] (a_format 0), or the bytes of the size_m quantised grouped rows (a_format 8 / 6 / 4; a_type names their 16-bit dtype).  Returns
 // 16-bit [c_rows, n_out], or with out_format the bytes of the quantised grouped [size_m, size_n / 2] rows.
@@ -480,6 +545,18 @@ std::tuple<at::Tensor, at::Tensor, at::Tensor> moe_align_device_meta(const at::T
 at::Tensor moe_combine_meta(const at::Tensor &slot_out, const at::Tensor &, const at::Tensor &topk_ids, int64_t) {
     return at::empty({topk_ids.size(0), slot_out.size(1)}, slot_out.options());
 }
+std::tuple<at::Tensor, at::Tensor, at::Tensor> moe_route_meta(PETIT_ROUTE_ARGS) {
+    const int64_t T = router_logits.size(0), E = router_logits.size(1);
+    const auto f32 = router_logits.options().dtype(at::kFloat);
+    return {at::empty({T, topk}, f32), at::empty({T, topk}, router_logits.options().dtype(at::kInt)), (return_keys ? at::empty({T, E}, f32) : at::empty({0}, f32))};
+}
+std::tuple<at::Tensor, at::Tensor, at::Tensor, at::Tensor, at::Tensor, at::Tensor> moe_route_align_meta(PETIT_ROUTE_ARGS) {
+    const int64_t T = router_logits.size(0), E = router_logits.size(1);
+    const auto f32 = router_logits.options().dtype(at::kFloat);
+    const auto i32 = router_logits.options().dtype(at::kInt);
+    return {at::empty({T, topk}, f32), at::empty({T, topk}, i32),     at::empty({T * topk}, i32),
+            at::empty({E + 1}, i32),   at::empty({T * topk}, i32), (return_keys ? at::empty({T, E}, f32) : at::empty({0}, f32))};
+}
 
 } // namespace
 
@@ -515,6 +592,11 @@ TORCH_LIBRARY(petit_kernel, m) {
           "Tensor? bias=None, int activation=0, int a_format=0, int a_type=5, int out_format=0) -> Tensor");
     m.def("moe_align_device(Tensor topk_ids, int num_experts) -> (Tensor, Tensor, Tensor)");
     m.def("moe_combine(Tensor slot_out, Tensor topk_weights, Tensor topk_ids, int num_experts) -> Tensor");
+#define PETIT_ROUTE_SCHEMA                                                                                                            \
+    "Tensor router_logits, int topk, int scoring=0, bool renormalize=True, Tensor? bias=None, int n_group=1, int topk_group=1, " \
+    "float routed_scaling_factor=1.0, bool return_keys=False"
+    m.def("moe_route(" PETIT_ROUTE_SCHEMA ") -> (Tensor, Tensor, Tensor)");
+    m.def("moe_route_align(" PETIT_ROUTE_SCHEMA ") -> (Tensor, Tensor, Tensor, Tensor, Tensor, Tensor)");
     // round 3's op name (scales promised inside fp16's range): an alias of mul_mxfp4_a16 for one more round -- the kernels test the range themselves
     m.def("mul_mxfp4_a16_f16range(Tensor A, Tensor B, Tensor s, Tensor global_scale, int size_m, int size_n, int size_k, int solution_id, "
           "Tensor? bias=None, int activation=0) -> Tensor");
@@ -536,7 +618,9 @@ TORCH_LIBRARY(petit_kernel, m) {
     m.impl("mul_nvfp4_native_moe", &mul_nvfp4_native_moe);      \
     m.impl("mul_nvfp4_native_transient", &mul_nvfp4_native_transient); \
     m.impl("moe_align_device", &moe_align_device);              \
-    m.impl("moe_combine", &moe_combine);
+    m.impl("moe_combine", &moe_combine);                        \
+    m.impl("moe_route", &moe_route);                            \
+    m.impl("moe_route_align", &moe_route_align);
 TORCH_LIBRARY_IMPL(petit_kernel, CUDA, m) { PETIT_IMPL_REAL(m) }
 TORCH_LIBRARY_IMPL(petit_kernel, CPU, m) { PETIT_IMPL_REAL(m) }
 TORCH_LIBRARY_IMPL(petit_kernel, Meta, m) {
@@ -557,4 +641,6 @@ TORCH_LIBRARY_IMPL(petit_kernel, Meta, m) {
     m.impl("mul_nvfp4_native_transient", &mul_nvfp4_native_transient_meta);
     m.impl("moe_align_device", &moe_align_device_meta);
     m.impl("moe_combine", &moe_combine_meta);
+    m.impl("moe_route", &moe_route_meta);
+    m.impl("moe_route_align", &moe_route_align_meta);
 }

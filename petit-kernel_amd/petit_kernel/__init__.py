@@ -14,7 +14,7 @@ import torch
 
 from . import compiled, gptoss, offline, ops, tuning
 from .gptoss import GptOssExperts, prepare_gptoss_experts
-from .moe import fp4_moe, fp4_moe_fused, fp4_moe_native, moe_align
+from .moe import fp4_moe, fp4_moe_fused, fp4_moe_native, fp4_moe_routed, moe_align
 from .ops import QuantizedActivations, mul_fp4_a16_grouped, mul_mxfp4_native, quantize_activations
 from .ops import attach_nvfp4_native, mul_nvfp4_native, nvfp4_native_image, nvfp4_native_images
 from .tuning import tune, tune_tensors
@@ -137,6 +137,22 @@ def moe_combine(slot_out: torch.Tensor, topk_weights: torch.Tensor, topk_ids: to
     return _impl.moe_combine(slot_out, topk_weights, topk_ids, num_experts)
 
 
+def moe_route(router_logits: torch.Tensor, topk: int, *, scoring: str = "softmax", renormalize: bool = True, bias: torch.Tensor = None,
+              n_group: int = 1, topk_group: int = 1, routed_scaling_factor: float = 1.0, return_keys: bool = False):
+    # router logits [T, E] (float32 / bfloat16 / float16) -> (topk_weights float32, topk_ids int32[, keys float32 [T, E]]) in one launch
+    # (include/petit_amd.h "Routing on the device, from the router's logits").  scoring "softmax" (Mixtral, Qwen3-MoE, gpt-oss with renormalize)
+    # or "sigmoid" (DeepSeek-V3: bias = e_score_correction_bias, n_group / topk_group, routed_scaling_factor).  Larger key first, the LOWER index
+    # among equal keys: a routing is a pure function of the logits
+    return _impl.moe_route(router_logits, topk, scoring, renormalize, bias, n_group, topk_group, routed_scaling_factor, return_keys)
+
+
+def moe_route_align(router_logits: torch.Tensor, topk: int, *, scoring: str = "softmax", renormalize: bool = True, bias: torch.Tensor = None,
+                    n_group: int = 1, topk_group: int = 1, routed_scaling_factor: float = 1.0, return_keys: bool = False):
+    # moe_route, then moe_align_device on its ids, bit for bit: (topk_weights, topk_ids, sorted_pos, expert_offsets, token_index[, keys]);
+    # ONE launch when T * topk <= 1024, four above
+    return _impl.moe_route_align(router_logits, topk, scoring, renormalize, bias, n_group, topk_group, routed_scaling_factor, return_keys)
+
+
 def mul_mxfp4_native_moe(a, b: torch.Tensor, s: torch.Tensor, global_scales: torch.Tensor, expert_offsets: torch.Tensor, size_m: int, size_n: int,
                          size_k: int, num_experts: int, a_row_index: torch.Tensor = None, c_row_index: torch.Tensor = None, c_rows: int = None,
                          solution_id: int = SOLUTION_AUTO_NATIVE_MXFP8, bias: torch.Tensor = None, activation: str = None, out_quantized: str = None):
@@ -216,6 +232,9 @@ __all__ = [
     "mul_mxfp4_a16_moe_indexed",
     "moe_align_device",
     "moe_combine",
+    "moe_route",
+    "moe_route_align",
+    "fp4_moe_routed",
     "fp4_moe_native",
     "mul_mxfp4_native_moe",
     "mul_nvfp4_native_moe",

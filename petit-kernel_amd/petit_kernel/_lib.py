@@ -30,7 +30,9 @@ CXX_DTYPE_MXFP4_E2M1 = 7
 CXX_DTYPE_MXFP4_E2M1_F16RANGE = 8   # extension: MXFP4 with every e8m0 scale in 114..140 (include/petit_amd.h)
 MXFP4_F16RANGE_SCALE_MIN, MXFP4_F16RANGE_SCALE_MAX = 114, 140
 PETIT_MOE_MAX_EXPERTS = 1024
-PETIT_DTYPE_FP32 = 100   # petit_dequant_packed_weights only
+PETIT_DTYPE_FP32 = 100   # petit_dequant_packed_weights; float32 router logits (petit_moe_route)
+PETIT_MOE_MAX_TOPK = 64
+PETIT_ROUTE_SOFTMAX, PETIT_ROUTE_SIGMOID = 0, 1
 
 
 class SolutionHints(C.Structure):
@@ -53,6 +55,12 @@ class GroupMember(C.Structure):
 class NativeArgs(C.Structure):
     """petit_native_args (include/petit_amd.h)."""
     _fields_ = [("struct_bytes", C.c_uint32), ("a_format", C.c_int32), ("out_format", C.c_int32), ("reserved", C.c_int32)]
+
+
+class RouteDesc(C.Structure):
+    """petit_route_desc (include/petit_amd.h)."""
+    _fields_ = [("scoring", C.c_int), ("renormalize", C.c_int), ("n_group", C.c_uint), ("topk_group", C.c_uint),
+                ("routed_scaling_factor", C.c_float), ("bias", C.c_void_p)]
 
 
 class TuneParams(C.Structure):
@@ -112,6 +120,9 @@ _SIGNATURES = {
     "petit_moe_align_workspace_bytes": (C.c_uint64, [C.c_uint] * 3),
     "petit_moe_align": (C.c_int, [C.c_void_p, C.c_int] + [C.c_uint] * 3 + [C.c_void_p] * 5),
     "petit_moe_combine": (C.c_int, [C.c_void_p] * 4 + [C.c_int] + [C.c_uint] * 4 + [C.c_int, C.c_void_p]),
+    "petit_moe_route": (C.c_int, [C.c_void_p, C.c_int] + [C.c_uint] * 3 + [C.POINTER(RouteDesc)] + [C.c_void_p] * 4),
+    "petit_moe_route_align_workspace_bytes": (C.c_uint64, [C.c_uint] * 3),
+    "petit_moe_route_align": (C.c_int, [C.c_void_p, C.c_int] + [C.c_uint] * 3 + [C.POINTER(RouteDesc)] + [C.c_void_p] * 8),
     "petit_gemm_mxfp4_native": (C.c_int, [C.c_void_p] * 5 + [C.c_uint] * 3 + [C.POINTER(SolutionHints), C.c_uint64, C.POINTER(Epilogue),
                                           C.POINTER(NativeArgs), C.c_void_p, C.c_uint64, C.c_void_p]),
     "petit_nvfp4_native_image_bytes": (C.c_uint64, [C.c_uint, C.c_uint]),

@@ -126,6 +126,30 @@ def moe_combine(slot_out, topk_weights, topk_ids, num_experts):
     return torch.ops.petit_kernel.moe_combine(slot_out, topk_weights, topk_ids, num_experts)
 
 
+_SCORING = {"softmax": 0, "sigmoid": 1}
+
+
+def _scoring(scoring) -> int:
+    if scoring not in _SCORING:
+        raise RuntimeError("scoring must be 'softmax' or 'sigmoid'")
+    return _SCORING[scoring]
+
+
+def moe_route(router_logits, topk, scoring="softmax", renormalize=True, bias=None, n_group=1, topk_group=1, routed_scaling_factor=1.0,
+              return_keys=False):
+    w, ids, keys = torch.ops.petit_kernel.moe_route(router_logits, int(topk), _scoring(scoring), bool(renormalize), bias, int(n_group),
+                                                    int(topk_group), float(routed_scaling_factor), bool(return_keys))
+    return (w, ids, keys) if return_keys else (w, ids)
+
+
+def moe_route_align(router_logits, topk, scoring="softmax", renormalize=True, bias=None, n_group=1, topk_group=1, routed_scaling_factor=1.0,
+                    return_keys=False):
+    w, ids, sp, off, ti, keys = torch.ops.petit_kernel.moe_route_align(router_logits, int(topk), _scoring(scoring), bool(renormalize), bias,
+                                                                       int(n_group), int(topk_group), float(routed_scaling_factor),
+                                                                       bool(return_keys))
+    return (w, ids, sp, off, ti, keys) if return_keys else (w, ids, sp, off, ti)
+
+
 def _native_sid(solution_id: int) -> int:
     # the native MoE ops read -2 / -3 / -4 as the native sentinels (the caller has opted in by calling them); other negatives: PETIT_SOLUTION_AUTO
     solution_id = int(solution_id)

@@ -9,7 +9,8 @@ only (CPU or GPU tensors):
     quantising gate_up epilogue: both are zero-padded to 3072;
   * the activation is the clamped SwiGLU (activation="swiglu_oai"), and every expert has a bias on gate_up and on down.
 
-The router (top-k, then softmax over the k), attention sinks and the dense bf16 linears of gpt-oss are not this module's business.
+The router's top-k (then softmax over the k) is `moe_route(..., scoring="softmax", renormalize=True)`: `GptOssExperts.forward_routed` starts
+from the logits.  The router's own linear, attention sinks and the dense bf16 linears of gpt-oss are not this module's business.
 """
 from __future__ import annotations
 
@@ -112,6 +113,16 @@ class GptOssExperts:
             return fp4_moe_fused(xp, self.w13, self.s13, self.gs13, self.w2, self.s2, self.gs2, topk_weights, topk_ids, kind="mxfp4", **kw)
         return fp4_moe_native(xp, self.w13, self.s13, self.gs13, self.w2, self.s2, self.gs2, topk_weights, topk_ids, kind="mxfp4",
                               activations=activations, **kw)
+
+    def forward_routed(self, x: torch.Tensor, router_logits: torch.Tensor, topk: int = 4, path: str = "fused",
+                       activations: str = "mxfp8") -> torch.Tensor:
+        """forward from the router's logits [T, E] (float32 / bfloat16 / float16): gpt-oss's routing -- the top-k logits, softmax over the k --
+        by moe_route_align, then forward's launches: bit for bit forward(x, *moe_route(router_logits, topk), path, activations)."""
+        from .moe import fp4_moe_routed
+        _check(path in ("fused", "native"), "path must be 'fused' or 'native'")
+        return fp4_moe_routed(self.pad_hidden(x), router_logits, self.w13, self.s13, self.gs13, self.w2, self.s2, self.gs2, topk, kind="mxfp4",
+                              path=path, activations=activations, bias13=self.bias13, bias2=self.bias2, activation="swiglu_oai",
+                              scoring="softmax", renormalize=True)
 
 
 def prepare_gptoss_experts(gate_up_blocks: torch.Tensor, gate_up_scales: torch.Tensor, gate_up_bias: torch.Tensor, down_blocks: torch.Tensor,

@@ -8,6 +8,9 @@ MoE launch each; the router weighting and the top-k combine are torch plumbing, 
 align runs on the device, gate_up reads the token rows through the sorted index (no gathered copy of the activations), down writes each
 (token, slot) result straight to its slot, and a deterministic top-k reduce finishes the layer.  Ids of -1 (experts that are not local
 under expert parallelism) are skipped.
+
+`fp4_moe_routed` starts one step earlier, from the router's logits: `moe_route_align` (top-k ids and weights with a stated tie rule, fused
+with the align into one launch for every decode batch), then the launches of `fp4_moe_fused` or `fp4_moe_native`.
 """
 from __future__ import annotations
 
@@ -86,20 +89,31 @@ def fp4_moe_fused(hidden: torch.Tensor, w13: torch.Tensor, s13: torch.Tensor, gs
     [0, E) (-1 under expert parallelism) contribute nothing.  topk_weights: float32 or bfloat16 [T, topk] (converted to float32 once).
     bias13 / bias2 / activation: as fp4_moe (the biases ride in the gate_up and down launches: no launch more).
     No host sync: capturable in a graph and replayable with any routing of the same shape."""
-    from . import moe_align_device, moe_combine, mul_mxfp4_a16_moe_indexed, mul_nvfp4_a16_moe_indexed
+    from . import moe_align_device
+    _check_fused(kind, activation)
+    E = gs13.numel()
+    ids = topk_ids if topk_ids.dtype in (torch.int32, torch.int64) and topk_ids.is_contiguous() else topk_ids.contiguous().to(torch.int64)
+    w = topk_weights if topk_weights.dtype == torch.float32 and topk_weights.is_contiguous() else topk_weights.float().contiguous()
+    sorted_pos, offsets, token_index = moe_align_device(ids, E)
+    return _fused_after_align(hidden, w13, s13, gs13, w2, s2, gs2, w, ids, sorted_pos, offsets, token_index, kind, bias13, bias2, activation)
+
+
+def _check_fused(kind, activation) -> None:
     if kind not in ("nvfp4", "mxfp4"):
         raise RuntimeError("kind must be 'nvfp4' or 'mxfp4'")
     _check_activation(activation)
+
+
+def _fused_after_align(hidden, w13, s13, gs13, w2, s2, gs2, w, ids, sorted_pos, offsets, token_index, kind, bias13, bias2, activation):
+    """fp4_moe_fused after its align: gate_up on gathered rows, down scattered into slot order, the combine (w float32, ids int32 / int64)."""
+    from . import moe_combine, mul_mxfp4_a16_moe_indexed, mul_nvfp4_a16_moe_indexed
     mul = mul_nvfp4_a16_moe_indexed if kind == "nvfp4" else mul_mxfp4_a16_moe_indexed
     T, H = hidden.shape
-    topk = topk_ids.shape[1]
+    topk = ids.shape[1]
     E = gs13.numel()
     n13 = w13.numel() * w13.element_size() * 2 // (E * H)   # 2 I
     inter = n13 // 2
     m = T * topk
-    ids = topk_ids if topk_ids.dtype in (torch.int32, torch.int64) and topk_ids.is_contiguous() else topk_ids.contiguous().to(torch.int64)
-    w = topk_weights if topk_weights.dtype == torch.float32 and topk_weights.is_contiguous() else topk_weights.float().contiguous()
-    sorted_pos, offsets, token_index = moe_align_device(ids, E)
     n2 = _down_n(w2, E, inter, H)
     h = mul(hidden, w13, s13, gs13, offsets, m, n13, H, E, a_row_index=token_index, bias=bias13, activation=activation)  # [m, I], grouped order
     y = mul(h, w2, s2, gs2, offsets, m, n2, inter, E, c_row_index=sorted_pos, c_rows=m, bias=bias2)          # [m, n2], (token, slot) order
@@ -118,15 +132,31 @@ def fp4_moe_native(hidden: torch.Tensor, w13: torch.Tensor, s13, gs13: torch.Ten
     when the align needs its three-launch form): the device align, the gathering quantiser, gate_up with SiLU-mul writing the quantised
     grouped rows down reads, down scattered into slot order, the top-k combine.  bias13 / bias2 / activation: as fp4_moe; 'swiglu_oai' is
     quantised for down from its f32 value, as SiLU-mul is.  No host sync: capturable."""
-    from . import moe_align_device, moe_combine, mul_mxfp4_native_moe, mul_nvfp4_native_moe, quantize_activation_rows
+    from . import moe_align_device
+    _check_native(kind, activation, activations)
+    E = gs13.numel()
+    ids = topk_ids if topk_ids.dtype in (torch.int32, torch.int64) and topk_ids.is_contiguous() else topk_ids.contiguous().to(torch.int64)
+    w = topk_weights if topk_weights.dtype == torch.float32 and topk_weights.is_contiguous() else topk_weights.float().contiguous()
+    sorted_pos, offsets, token_index = moe_align_device(ids, E)
+    return _native_after_align(hidden, w13, s13, gs13, w2, s2, gs2, w, ids, sorted_pos, offsets, token_index, kind, activations, bias13, bias2,
+                               activation)
+
+
+def _check_native(kind, activation, activations) -> None:
     if kind not in ("nvfp4", "mxfp4"):
         raise RuntimeError("kind must be 'nvfp4' or 'mxfp4'")
     _check_activation(activation)
     if activations not in _NATIVE_SENTINELS:
         raise RuntimeError("activations must be 'mxfp8', 'mxfp6' or 'mxfp4'")
+
+
+def _native_after_align(hidden, w13, s13, gs13, w2, s2, gs2, w, ids, sorted_pos, offsets, token_index, kind, activations, bias13, bias2,
+                        activation):
+    """fp4_moe_native after its align: the gathering quantiser, gate_up, down scattered into slot order, the combine."""
+    from . import moe_combine, mul_mxfp4_native_moe, mul_nvfp4_native_moe, quantize_activation_rows
     sid = _NATIVE_SENTINELS[activations]
     T, H = hidden.shape
-    topk = topk_ids.shape[1]
+    topk = ids.shape[1]
     E = gs13.numel()
     if kind == "mxfp4":
         n13 = w13.numel() * w13.element_size() * 2 // (E * H)   # 2 I
@@ -139,9 +169,6 @@ def fp4_moe_native(hidden: torch.Tensor, w13: torch.Tensor, s13, gs13: torch.Ten
     inter = n13 // 2
     n2 = _down_n(w2, E, inter, H) if kind == "mxfp4" else H
     m = T * topk
-    ids = topk_ids if topk_ids.dtype in (torch.int32, torch.int64) and topk_ids.is_contiguous() else topk_ids.contiguous().to(torch.int64)
-    w = topk_weights if topk_weights.dtype == torch.float32 and topk_weights.is_contiguous() else topk_weights.float().contiguous()
-    sorted_pos, offsets, token_index = moe_align_device(ids, E)
     qa = quantize_activation_rows(hidden, activations, token_index)                  # grouped rows; unrouted (-1) rows are zeros
     if n13 % 512 == 0:
         h = mul13(qa, bias=bias13, activation=activation, out_quantized=activations)  # down's quantised input, grouped
@@ -149,3 +176,29 @@ def fp4_moe_native(hidden: torch.Tensor, w13: torch.Tensor, s13, gs13: torch.Ten
         h = mul13(qa, bias=bias13, activation=activation)                            # 16-bit; down quantises it (one more launch)
     y = mul2(h, c_row_index=sorted_pos, c_rows=m, bias=bias2)                        # [m, n2], (token, slot) order
     return moe_combine(y, w, ids, E)
+
+
+def fp4_moe_routed(hidden: torch.Tensor, router_logits: torch.Tensor, w13: torch.Tensor, s13, gs13: torch.Tensor, w2: torch.Tensor, s2,
+                   gs2: torch.Tensor, topk: int, kind: str = "nvfp4", *, path: str = "fused", activations: str = "mxfp8",
+                   bias13: torch.Tensor = None, bias2: torch.Tensor = None, activation: str = "silu_mul", **routing) -> torch.Tensor:
+    """The layer from the router's logits: moe_route_align(router_logits, topk, **routing), then exactly the launches fp4_moe_fused (path
+    'fused') or fp4_moe_native (path 'native', with `activations`) issue after their align -- bit for bit
+    fp4_moe_fused(..., *moe_route(router_logits, topk, **routing)).  router_logits [T, E] float32 / bfloat16 / float16; routing: moe_route's
+    keyword arguments (scoring, renormalize, bias, n_group, topk_group, routed_scaling_factor).  Route and align are ONE launch when
+    T * topk <= 1024 (the fused layer: 4 launches; 7 above).  No host sync: capturable, and a routing is a pure function of the logits."""
+    from . import moe_route_align
+    if path not in ("fused", "native"):
+        raise RuntimeError("path must be 'fused' or 'native'")
+    if "return_keys" in routing:
+        raise RuntimeError("fp4_moe_routed returns the layer's output only: call moe_route(..., return_keys=True) for the keys")
+    if path == "fused":
+        _check_fused(kind, activation)
+    else:
+        _check_native(kind, activation, activations)
+    if router_logits.dim() != 2 or router_logits.size(0) != hidden.size(0) or router_logits.size(1) != gs13.numel():
+        raise RuntimeError(f"router_logits must be [{hidden.size(0)}, {gs13.numel()}] (tokens of hidden, experts of the weights)")
+    w, ids, sorted_pos, offsets, token_index = moe_route_align(router_logits, topk, **routing)
+    if path == "fused":
+        return _fused_after_align(hidden, w13, s13, gs13, w2, s2, gs2, w, ids, sorted_pos, offsets, token_index, kind, bias13, bias2, activation)
+    return _native_after_align(hidden, w13, s13, gs13, w2, s2, gs2, w, ids, sorted_pos, offsets, token_index, kind, activations, bias13, bias2,
+                               activation)

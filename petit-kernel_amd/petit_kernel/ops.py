@@ -843,6 +843,81 @@ def moe_combine(slot_out: torch.Tensor, topk_weights: torch.Tensor, topk_ids: to
     return out
 
 
+_SCORINGS = {"softmax": _lib.PETIT_ROUTE_SOFTMAX, "sigmoid": _lib.PETIT_ROUTE_SIGMOID}
+_LOGIT_DTYPES = {torch.float32: _lib.PETIT_DTYPE_FP32, torch.bfloat16: _lib.CXX_DTYPE_BF16, torch.float16: _lib.CXX_DTYPE_FP16}
+
+
+def _check_route(router_logits, topk, scoring, bias, n_group, topk_group):
+    """The argument checks of moe_route / moe_route_align (the same texts as csrc/torch_binding.cpp); returns (T, E)."""
+    _check(scoring in _SCORINGS, "scoring must be 'softmax' or 'sigmoid'")
+    _check(router_logits.is_cuda and router_logits.dim() == 2 and router_logits.is_contiguous() and router_logits.dtype in _LOGIT_DTYPES,
+           "router_logits must be a contiguous float32 / bfloat16 / float16 [num_tokens, num_experts] GPU tensor")
+    T, E = router_logits.shape
+    _check(1 <= E <= _lib.PETIT_MOE_MAX_EXPERTS, f"num_experts must be in 1..{_lib.PETIT_MOE_MAX_EXPERTS}, got {E}")
+    _check(1 <= int(topk) <= min(E, _lib.PETIT_MOE_MAX_TOPK), f"topk must be in 1..min(num_experts, {_lib.PETIT_MOE_MAX_TOPK}), got {topk}")
+    _check(int(n_group) >= 1 and int(topk_group) >= 1, "n_group and topk_group must be >= 1")
+    if bias is not None:
+        _check(scoring == "sigmoid", "bias needs scoring='sigmoid'")
+        _check(bias.is_cuda and bias.device == router_logits.device and bias.dtype == torch.float32 and bias.is_contiguous() and
+               tuple(bias.shape) == (E,), "bias must be a contiguous float32 [num_experts] tensor on router_logits' device")
+    return T, E
+
+
+def _route_desc(scoring, renormalize, bias, n_group, topk_group, routed_scaling_factor):
+    return _lib.RouteDesc(_SCORINGS[scoring], int(bool(renormalize)), int(n_group), int(topk_group), float(routed_scaling_factor),
+                          bias.data_ptr() if bias is not None else None)
+
+
+def _route_shape_error(rc, T, E, topk, n_group, topk_group):
+    if rc == _lib.PETIT_ERROR_PROBLEM_SHAPE:
+        raise RuntimeError(f"Incompatible routing shape (num_tokens={T}, num_experts={E}, topk={topk}, n_group={n_group}, topk_group={topk_group})")
+
+
+def moe_route(router_logits: torch.Tensor, topk: int, scoring: str = "softmax", renormalize: bool = True, bias: torch.Tensor = None,
+              n_group: int = 1, topk_group: int = 1, routed_scaling_factor: float = 1.0, return_keys: bool = False):
+    """Router logits [T, E] (float32 / bfloat16 / float16) -> (topk_weights float32 [T, topk], topk_ids int32 [T, topk][, keys float32 [T, E]])
+    by petit_moe_route (include/petit_amd.h "Routing on the device, from the router's logits": the scorings, the tie rule -- larger key first,
+    the lower index among equal keys --, the accuracy of the weights).  One launch, no host sync, deterministic."""
+    T, E = _check_route(router_logits, topk, scoring, bias, n_group, topk_group)
+    dev = router_logits.device
+    ids = torch.empty((T, int(topk)), dtype=torch.int32, device=dev)
+    w = torch.empty((T, int(topk)), dtype=torch.float32, device=dev)
+    keys = torch.empty((T, E), dtype=torch.float32, device=dev) if return_keys else None
+    desc = _route_desc(scoring, renormalize, bias, n_group, topk_group, routed_scaling_factor)
+    with torch.cuda.device(dev):
+        rc = _lib.lib.petit_moe_route(_ptr(router_logits), _LOGIT_DTYPES[router_logits.dtype], T, E, int(topk), C.byref(desc), _ptr(ids), _ptr(w),
+                                      _ptr(keys) if keys is not None else None, _stream(router_logits))
+    _route_shape_error(rc, T, E, topk, n_group, topk_group)
+    _raise_on(rc, "moe_route")
+    return (w, ids, keys) if return_keys else (w, ids)
+
+
+def moe_route_align(router_logits: torch.Tensor, topk: int, scoring: str = "softmax", renormalize: bool = True, bias: torch.Tensor = None,
+                    n_group: int = 1, topk_group: int = 1, routed_scaling_factor: float = 1.0, return_keys: bool = False):
+    """moe_route followed by moe_align_device on its ids, bit for bit: (topk_weights, topk_ids, sorted_pos, expert_offsets, token_index[, keys]).
+    ONE launch when T * topk <= 1024 (petit_moe_route_align: the align's workgroup routes first), four above."""
+    T, E = _check_route(router_logits, topk, scoring, bias, n_group, topk_group)
+    dev = router_logits.device
+    topk = int(topk)
+    ids = torch.empty((T, topk), dtype=torch.int32, device=dev)
+    w = torch.empty((T, topk), dtype=torch.float32, device=dev)
+    keys = torch.empty((T, E), dtype=torch.float32, device=dev) if return_keys else None
+    sorted_pos = torch.empty(T * topk, dtype=torch.int32, device=dev)
+    token_index = torch.empty(T * topk, dtype=torch.int32, device=dev)
+    offsets = torch.empty(E + 1, dtype=torch.int32, device=dev)
+    ws_bytes = int(_lib.lib.petit_moe_route_align_workspace_bytes(T, topk, E))
+    ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev) if ws_bytes else None
+    desc = _route_desc(scoring, renormalize, bias, n_group, topk_group, routed_scaling_factor)
+    with torch.cuda.device(dev):
+        rc = _lib.lib.petit_moe_route_align(_ptr(router_logits), _LOGIT_DTYPES[router_logits.dtype], T, E, topk, C.byref(desc), _ptr(ids), _ptr(w),
+                                            _ptr(keys) if keys is not None else None, _ptr(offsets), _ptr(sorted_pos), _ptr(token_index),
+                                            _ptr(ws) if ws is not None else None, _stream(router_logits))
+    _route_shape_error(rc, T, E, topk, n_group, topk_group)
+    _raise_on(rc, "moe_route_align")
+    out = (w, ids, sorted_pos, offsets, token_index)
+    return out + (keys,) if return_keys else out
+
+
 def moe_resolve_solution(hints: PetitSolutionHints, num_experts: int, size_m: int, size_n: int, size_k: int, solution_id: int = -1,
                          activation=None) -> int:
     """The kernel id a MoE call with these arguments runs (petit_gemm_moe_resolve_solution, the launcher's own pick); 0 when it would be refused."""

@@ -2,7 +2,7 @@
 """tools/moe_bench.py -- the routed-expert (MoE) launch against a host loop of dense calls, on real expert shapes.
 
     python tools/moe_bench.py [--cells decode|prefill|all] [--models deepseek,qwen3,mixtral] [--iters N] [--out FILE]
-                              [--only-moe | --only-loop] [--single-expert] [--layer [--native mxfp8|mxfp6|mxfp4]] [--gptoss]
+                              [--only-moe | --only-loop] [--single-expert] [--layer [--native mxfp8|mxfp6|mxfp4 | --from-logits]] [--gptoss]
 
 Per cell (model, projection, T tokens): E experts' NVFP4 weights (bf16 activations) stacked back to back, copied until the pool is >= 1 GB so
 that rotating over copies and over routings (drawn from a seed, top-k of random router logits) keeps the 256 MB Infinity Cache from serving
@@ -18,6 +18,10 @@ plain MoE GEMMs on pre-gathered rows against the indexed ones (gate_up gathering
 --layer --native mxfp8|mxfp6|mxfp4: fp4_moe_native against fp4_moe_fused on the same weights (MXFP4 raw; NVFP4 through nvfp4_native_images), graph
 replays, T = 1, 16, 64, 1024, 4096; plus one single-expert cell (M = 4096, every row on one expert, activations pre-quantised: the native MoE launch
 against the dense native call with the same id).
+--layer --from-logits: the layer from the router's logits, graph replays on one stream, two columns: (a) the model's torch routing chain
+(softmax + top-k + renormalise; gpt-oss: top-k, softmax over the k; DeepSeek-V3: the grouped top-k chain written out in torch_routing) followed
+by fp4_moe_fused, and (b) fp4_moe_routed.  Measured a, b, a, b in one process, both pairs reported; per cell also the number of kernels the
+routing chain of (a) launches (torch.profiler's kernel events) and saving / (that count x 1.6 .. 1.9 us).
 --gptoss: the gpt-oss-20b / -120b expert block (bf16 x MXFP4, 2880 -> 3072, biases, activation="swiglu_oai"): see gptoss_cells.  The two
 models are also in the model list of the default cells (--models gpt-oss-20b,gpt-oss-120b: MXFP4 pools).
 Kernel times without launch gaps: run under `rocprofv3 --kernel-trace --stats -- python tools/moe_bench.py ...`.
@@ -237,6 +241,106 @@ def layer_cells(pk, models, ts, iters):
     return cells
 
 
+ROUTING = {  # moe_route's keyword arguments per model
+    "deepseek": dict(scoring="sigmoid", renormalize=True, n_group=8, topk_group=4, routed_scaling_factor=2.5),
+    "qwen3": dict(scoring="softmax", renormalize=True),
+    "mixtral": dict(scoring="softmax", renormalize=True),
+    "gpt-oss-20b": dict(scoring="softmax", renormalize=True),
+    "gpt-oss-120b": dict(scoring="softmax", renormalize=True),
+}
+
+
+def torch_routing(name, logits, topk, bias=None):
+    """The routing chain a caller runs in front of fp4_moe_fused today: (topk_weights float32, topk_ids int32)."""
+    if name.startswith("gpt-oss"):                      # the top-k logits, softmax over the k
+        v, ids = torch.topk(logits, topk, dim=-1)
+        return torch.softmax(v.float(), -1), ids.to(torch.int32)
+    if name != "deepseek":                              # softmax over all, top-k, renormalise
+        w, ids = torch.topk(torch.softmax(logits.float(), -1), topk, dim=-1)
+        return w / w.sum(-1, keepdim=True), ids.to(torch.int32)
+    r = ROUTING[name]                                   # DeepSeek-V3: sigmoid, correction bias, group-limited top-k, renormalise, scale
+    T, E = logits.shape
+    scores = logits.float().sigmoid()
+    biased = scores + bias
+    group_scores = biased.view(T, r["n_group"], -1).topk(2, dim=-1)[0].sum(-1)
+    group_idx = torch.topk(group_scores, r["topk_group"], dim=-1, sorted=False)[1]
+    group_mask = torch.zeros_like(group_scores).scatter_(1, group_idx, 1)
+    score_mask = group_mask.unsqueeze(-1).expand(T, r["n_group"], E // r["n_group"]).reshape(T, E)
+    ids = torch.topk(biased.masked_fill(~score_mask.bool(), float("-inf")), topk, dim=-1, sorted=False)[1]
+    w = scores.gather(1, ids)
+    w = w / (w.sum(-1, keepdim=True) + 1e-20)
+    return w * r["routed_scaling_factor"], ids.to(torch.int32)
+
+
+def kernel_launches(fn):
+    """kernels fn launches (eagerly), from torch.profiler's device-side kernel events; None when the profiler reports none"""
+    from torch.profiler import ProfilerActivity, profile
+    fn()
+    torch.cuda.synchronize()
+    with profile(activities=[ProfilerActivity.CUDA]) as prof:
+        fn()
+        torch.cuda.synchronize()
+    n = sum(1 for e in prof.events() if e.device_type == torch.autograd.DeviceType.CUDA and "emcpy" not in e.name and "emset" not in e.name)
+    return n or None
+
+
+def routed_layer_cells(pk, models, ts, iters):
+    """--layer --from-logits (module docstring): a = torch routing chain + fp4_moe_fused, b = fp4_moe_routed, measured a, b, a, b."""
+    cells = []
+    for name in models:
+        (n13, hid), (n2, inter), E, topk = MODELS[name]
+        kind = "mxfp4" if MODEL_KIND.get(name) == "mx" else "nvfp4"
+        g = torch.Generator(device="cuda").manual_seed(7)
+        ri = lambda *shape: torch.randint(-2 ** 31, 2 ** 31 - 1, shape, dtype=torch.int32, device="cuda", generator=g)  # noqa: E731
+        w13, w2 = ri(E * n13 // 16, 2 * hid), ri(E * n2 // 16, 2 * inter)
+        if kind == "nvfp4":
+            s13 = torch.randint(0x28, 0x40, (E * n13, hid // 16), dtype=torch.uint8, device="cuda", generator=g).view(torch.float8_e4m3fn)
+            s2 = torch.randint(0x28, 0x40, (E * n2, inter // 16), dtype=torch.uint8, device="cuda", generator=g).view(torch.float8_e4m3fn)
+            gs13, gs2 = torch.rand(E, device="cuda") * 0.01 + 0.01, torch.rand(E, device="cuda") * 0.01 + 0.01
+            extra = {}
+        else:
+            s13 = torch.randint(118, 127, (E * n13 // 32, hid), dtype=torch.uint8, device="cuda", generator=g)
+            s2 = torch.randint(118, 127, (E * n2 // 32, inter), dtype=torch.uint8, device="cuda", generator=g)
+            gs13, gs2 = torch.ones(E, device="cuda"), torch.ones(E, device="cuda")
+            extra = dict(bias13=torch.randn(E, n13, device="cuda").bfloat16(), bias2=torch.randn(E, n2, device="cuda").bfloat16(),
+                         activation="swiglu_oai")
+        routing = dict(ROUTING[name])
+        bias = torch.randn(E, device="cuda", generator=g) * 0.1 if name == "deepseek" else None
+        if bias is not None:
+            routing["bias"] = bias
+        for T in ts:
+            it = iters if T < 1024 else max(5, iters // 5)
+            x = torch.randn(T, hid, device="cuda").to(torch.bfloat16)
+            logits = torch.randn(T, E, device="cuda", generator=g).to(torch.bfloat16)
+            wts = (x, w13, s13, gs13, w2, s2, gs2)
+
+            def a():
+                tw, tid = torch_routing(name, logits, topk, bias)
+                return pk.fp4_moe_fused(*wts, tw, tid, kind, **extra)
+
+            def b():
+                return pk.fp4_moe_routed(x, logits, w13, s13, gs13, w2, s2, gs2, topk, kind, **extra, **routing)
+
+            r = {"model": name, "T": T, "E": E, "topk": topk, "hidden": hid, "inter": inter}
+            r["torch_chain_fused_us"], r["routed_us"] = [], []
+            for _ in range(2):
+                r["torch_chain_fused_us"].append(graph_us(a, it))
+                r["routed_us"].append(graph_us(b, it))
+            try:
+                r["chain_launches"] = kernel_launches(lambda: torch_routing(name, logits, topk, bias))
+            except Exception as exc:  # noqa: BLE001 -- a count, not a time: the cell stands without it
+                r["chain_launches"], r["chain_launches_error"] = None, repr(exc)
+            saving = [x_ - y_ for x_, y_ in zip(r["torch_chain_fused_us"], r["routed_us"])]
+            r["saving_us"] = saving
+            if r["chain_launches"]:
+                r["saving_over_expected"] = [[s_ / (r["chain_launches"] * c) for c in (1.9, 1.6)] for s_ in saving]
+            print(json.dumps(r), file=sys.stderr, flush=True)
+            cells.append(r)
+        del w13, s13, w2, s2
+        torch.cuda.empty_cache()
+    return cells
+
+
 def native_layer_cells(pk, models, ts, iters, fmt):
     """--layer --native FMT: fp4_moe_native (activations quantised to FMT) against fp4_moe_fused on the same weights: MXFP4 weights raw, NVFP4
     weights through their native images (nvfp4_native_images) -- graph replays, as layer_cells"""
@@ -391,6 +495,7 @@ def main():
     ap.add_argument("--t", default="", help="--layer: comma-separated token counts (default 1,4,16,64,1024,4096)")
     ap.add_argument("--native", default="", choices=["", "mxfp8", "mxfp6", "mxfp4"],
                     help="--layer: fp4_moe_native with these activations against fp4_moe_fused (MXFP4 raw and NVFP4 images), plus the single-expert cell")
+    ap.add_argument("--from-logits", action="store_true", help="--layer: the torch routing chain + fp4_moe_fused against fp4_moe_routed")
     ap.add_argument("--gptoss", action="store_true", help="the gpt-oss expert block (petit_kernel.gptoss): layer, host loop, native, fused activation")
     ap.add_argument("--out", default="")
     args = ap.parse_args()
@@ -400,6 +505,10 @@ def main():
         ts = tuple(int(t) for t in args.t.split(",")) if args.t else LAYER_T
         models = [m for m in args.models.split(",") if m in MODEL_KIND] or list(MODEL_KIND)
         report["gptoss"] = gptoss_cells(pk, models, ts, args.iters)
+    elif args.layer and args.from_logits:
+        ts = tuple(int(t) for t in args.t.split(",")) if args.t else LAYER_T
+        models = args.models.split(",") if args.models != "deepseek,qwen3,mixtral" else ["deepseek", "qwen3", "mixtral", "gpt-oss-120b"]
+        report["routed_layer"] = routed_layer_cells(pk, models, ts, args.iters)
     elif args.layer and args.native:
         ts = tuple(int(t) for t in args.t.split(",")) if args.t else NATIVE_LAYER_T
         report["native_layer"] = native_layer_cells(pk, args.models.split(","), ts, args.iters, args.native)
