@@ -25,6 +25,87 @@ constexpr int kCxxFp4 = 3, kCxxFp16 = 4, kCxxBf16 = 5, kCxxMxFp4 = 7; // quantiz
 
 void *stream_of(const at::Tensor &t) { return c10::hip::getCurrentHIPStreamMasqueradingAsCUDA(t.device().index()).stream(); }
 
+// --- the rules more than one op states: each once, the same texts as petit_kernel/ops.py ---
+
+void check_a16(const at::Tensor &A) {
+    TORCH_CHECK(A.scalar_type() == at::kBFloat16 || A.scalar_type() == at::kHalf, "A must be bfloat16 or float16.");
+}
+int a_type_of(at::ScalarType t) { return t == at::kBFloat16 ? kCxxBf16 : kCxxFp16; }
+
+// The schema's `int` (a signed int64) -> the C ABI's uint64 id.  -2 / -3 / -4 are the native-class sentinels where the caller has opted into that
+// class (native_ok: a native op, or NVFP4 weights with an image attached).  Ids are 64-bit patterns whose top nibble is the K split: a split
+// of 8..15 sets bit 63, and such an id arrives as its two's-complement value (petit_kernel/compiled.py maps it), far below -4096, and is
+// reinterpreted; a small negative value is "library default", as in the reference (fp4.cc:189-191,240: solution_id < 0).  The native ops
+// take no such ids: there every other negative value is the library default.
+uint64_t c_solution_id(int64_t solution_id, bool native_ok) {
+    if (native_ok && solution_id <= -2 && solution_id >= -4)
+        return solution_id == -2 ? PETIT_SOLUTION_AUTO_NATIVE_MXFP8 : solution_id == -3 ? PETIT_SOLUTION_AUTO_NATIVE_MXFP4 : PETIT_SOLUTION_AUTO_NATIVE_MXFP6;
+    return solution_id < 0 && (native_ok || solution_id >= -4096) ? PETIT_SOLUTION_AUTO : (uint64_t)solution_id;
+}
+
+// a GEMM entry point's refusal as the caller sees it (call it with rc != PETIT_OK: the shape text is built for the message alone)
+void check_gemm_rc(int rc, const char *name, int64_t printed_id, const std::string &shape_text) {
+    TORCH_CHECK(rc != PETIT_ERROR_PROBLEM_SHAPE, "Incompatible problem shape (", shape_text, ")");
+    TORCH_CHECK(rc != PETIT_ERROR_KERNEL_SHAPE, "No kernel implementation for solution_id=", printed_id, ".");
+    TORCH_CHECK(rc == PETIT_OK, name, ": ", petit_error_string(rc));
+}
+
+// activation: 0 none, 1 silu_mul, 2 swiglu_oai (PETIT_ACTIVATION_*); halves_of: the size_n whose gate / up halves a gated form splits
+void check_activation(int64_t activation, std::optional<int64_t> halves_of = std::nullopt) {
+    TORCH_CHECK(activation >= 0 && activation <= 2, "activation must be 0 (none), 1 (silu_mul) or 2 (swiglu_oai)");
+    if (activation && halves_of)
+        TORCH_CHECK(*halves_of % 32 == 0, "silu_mul / swiglu_oai need size_n % 32 == 0 (gate / up halves of whole tiles), got ", *halves_of);
+}
+
+// the epilogue's bias: `numel` contiguous elements of `dtype` on A's device (text: the rule in the caller's words)
+void check_bias(const std::optional<at::Tensor> &bias, const at::Tensor &A, at::ScalarType dtype, int64_t numel, const char *text) {
+    if (bias.has_value())
+        TORCH_CHECK(bias->is_cuda() && bias->device() == A.device() && bias->scalar_type() == dtype && bias->is_contiguous() && bias->numel() == numel,
+                    text);
+}
+
+// what the routed-expert launches share on everything but the activations' shape: the expert count, the stacked weights (packed B / s, or
+// for NVFP4 on the native class the experts' images), one global scale per expert, the E + 1 offsets
+void check_expert_operands(bool mx, bool native, const at::Tensor &A, const at::Tensor &B, const at::Tensor *s, const at::Tensor &global_scales,
+                           const at::Tensor &expert_offsets, int64_t E, int64_t size_n, int64_t size_k) {
+    TORCH_CHECK(E >= 1 && E <= PETIT_MOE_MAX_EXPERTS, "num_experts must be in 1..", PETIT_MOE_MAX_EXPERTS, ", got ", E);
+    // (on the native class s is absent with images, and otherwise answers for itself below)
+    TORCH_CHECK(A.is_cuda() && B.is_cuda() && global_scales.is_cuda() && expert_offsets.is_cuda() &&
+                    (native ? A.is_contiguous() && B.is_contiguous() : s->is_cuda()),
+                "all tensors must be on GPU");
+    if (native && !mx) {
+        const int64_t per = (int64_t)petit_nvfp4_native_image_bytes((unsigned)size_k, (unsigned)size_n);
+        TORCH_CHECK(B.scalar_type() == at::kByte && per > 0 && B.numel() == E * per, "images do not hold num_experts native images (nvfp4_native_images)");
+    } else {
+        const int64_t group = mx ? 32 : 16;
+        TORCH_CHECK(B.is_contiguous() && B.numel() * B.element_size() == E * size_n * size_k / 2,
+                    "B does not hold num_experts * size_n * size_k packed 4-bit weights");
+        TORCH_CHECK(s && s->is_cuda() && s->is_contiguous() && s->numel() * s->element_size() == E * size_n * size_k / group,
+                    "s does not hold num_experts * size_n * size_k / ", group, " scales");
+    }
+    TORCH_CHECK(global_scales.scalar_type() == at::kFloat && global_scales.is_contiguous() && global_scales.numel() == E,
+                "global_scales must be a contiguous float32 [num_experts] tensor");
+    TORCH_CHECK(expert_offsets.scalar_type() == at::kInt && expert_offsets.is_contiguous() && expert_offsets.numel() == E + 1,
+                "expert_offsets must be a contiguous int32 [num_experts + 1] tensor");
+}
+
+void check_row_indices(const std::optional<at::Tensor> &a_row_index, const std::optional<at::Tensor> &c_row_index, const at::Tensor &A,
+                       int64_t size_m) {
+    for (const auto *idx : {&a_row_index, &c_row_index})
+        if (idx->has_value())
+            TORCH_CHECK((*idx)->is_cuda() && (*idx)->device() == A.device() && (*idx)->scalar_type() == at::kInt && (*idx)->is_contiguous() &&
+                            (*idx)->numel() == size_m,
+                        "row indices must be contiguous int32 [size_m] tensors on A's device");
+}
+const int32_t *row_index_ptr(const std::optional<at::Tensor> &idx) { return idx.has_value() ? (const int32_t *)idx->data_ptr() : nullptr; }
+
+// the output of a native op: 16-bit [rows, n_out], or with out_format the bytes of the quantised [size_m, n_out] rows (the real op and its Meta twin)
+at::Tensor native_output(const at::Tensor &A, at::ScalarType dtype, int64_t rows, int64_t size_m, int64_t n_out, int64_t out_format) {
+    if (out_format)
+        return at::empty({(int64_t)petit_quantized_activation_bytes((unsigned)size_m, (unsigned)n_out, (int)out_format)}, A.options().dtype(at::kByte));
+    return at::empty({rows, n_out}, A.options().dtype(dtype));
+}
+
 at::Tensor repack_nvfp4(const at::Tensor &b_q_weight, int64_t size_n, int64_t size_k) {
     TORCH_CHECK(size_k % kLayoutM == 0, "size_k = ", size_k, " is not divisible by tile_k_size = ", kLayoutM);
     TORCH_CHECK(size_n % kLayoutN == 0, "size_n = ", size_n, " is not divisible by tile_n_size = ", kLayoutN);
@@ -72,7 +153,6 @@ at::Tensor process_scales(const at::Tensor &scales, int64_t size_n, int64_t size
 at::Tensor process_nvfp4_scales(const at::Tensor &s, int64_t n, int64_t k) { return process_scales(s, n, k, false); }
 at::Tensor process_mxfp4_scales(const at::Tensor &s, int64_t n, int64_t k) { return process_scales(s, n, k, true); }
 
-// activation: 0 none, 1 silu_mul, 2 swiglu_oai (PETIT_ACTIVATION_*)
 at::Tensor mul_a16(bool mx, const at::Tensor &A, const at::Tensor &B, const at::Tensor &s, const at::Tensor &global_scale, int64_t size_m,
                    int64_t size_n, int64_t size_k, int64_t solution_id, const std::optional<at::Tensor> &bias, int64_t activation) {
     // (check order as in the reference's MulNvFp4A16 / MulMxFp4A16, fp4.cc:163-260: the scale / weight tensor contracts first)
@@ -86,30 +166,20 @@ at::Tensor mul_a16(bool mx, const at::Tensor &A, const at::Tensor &B, const at::
                     ", s.size(1) = ", s.size(-1));
         TORCH_CHECK(s.numel() == size_n * size_k / 16, "s does not hold size_n * size_k / 16 scales");
     }
-    TORCH_CHECK(A.scalar_type() == at::kBFloat16 || A.scalar_type() == at::kHalf, "A must be bfloat16 or float16.");
+    check_a16(A);
     TORCH_CHECK(A.is_cuda() && B.is_cuda() && s.is_cuda() && global_scale.is_cuda(), "all tensors must be on GPU");
     TORCH_CHECK(A.is_contiguous() && A.numel() == size_m * size_k, "A must be a contiguous [size_m, size_k] tensor");
     TORCH_CHECK(B.is_contiguous() && B.numel() * B.element_size() == size_n * size_k / 2, "B does not hold size_n * size_k packed 4-bit weights");
     TORCH_CHECK(global_scale.scalar_type() == at::kFloat && global_scale.numel() >= 1, "global_scale must be float32");
-    TORCH_CHECK(activation >= 0 && activation <= 2, "activation must be 0 (none), 1 (silu_mul) or 2 (swiglu_oai)");
-    if (activation)
-        TORCH_CHECK(size_n % 32 == 0, "silu_mul / swiglu_oai need size_n % 32 == 0 (gate / up halves of whole tiles), got ", size_n);
-    if (bias.has_value())
-        TORCH_CHECK(bias->is_cuda() && bias->device() == A.device() && bias->scalar_type() == A.scalar_type() && bias->is_contiguous() &&
-                        bias->numel() == size_n,
-                    "bias must be a contiguous [size_n] tensor of A's dtype on A's device");
+    check_activation(activation, size_n);
+    check_bias(bias, A, A.scalar_type(), size_n, "bias must be a contiguous [size_n] tensor of A's dtype on A's device");
     const c10::hip::HIPGuardMasqueradingAsCUDA guard(A.device());
     at::Tensor c = at::empty({size_m, activation ? size_n / 2 : size_n}, A.options());
-    const int a_type = A.scalar_type() == at::kBFloat16 ? kCxxBf16 : kCxxFp16;
+    const int a_type = a_type_of(A.scalar_type());
     const petit_solution_hints hints{a_type, mx ? kCxxMxFp4 : kCxxFp4, a_type, 0};
-    // ids are 64-bit patterns whose top nibble is the K split: a split of 8..15 sets bit 63, and the schema's `int` is a
-    // signed int64 -- such an id arrives as its two's-complement value (petit_kernel/compiled.py maps it) and is
-    // reinterpreted here.  A small negative value is "library default", as in the reference (fp4.cc:189-191,240: solution_id < 0) -- including
-    // -2 / -3, which name the native class only on ITS entry point (mul_mxfp4_native): these two ops are the reference's, and exact
-    uint64_t sid = (solution_id < 0 && solution_id >= -4096) ? PETIT_SOLUTION_AUTO : (uint64_t)solution_id;
-    // NVFP4 weights with an MFMA-native image attached (petit_nvfp4_native_attach) have opted into the native class: -2 / -3 / -4 name it then
-    if (!mx && solution_id <= -2 && solution_id >= -4 && petit_nvfp4_native_attached(B.data_ptr()))
-        sid = solution_id == -2 ? PETIT_SOLUTION_AUTO_NATIVE_MXFP8 : solution_id == -3 ? PETIT_SOLUTION_AUTO_NATIVE_MXFP4 : PETIT_SOLUTION_AUTO_NATIVE_MXFP6;
+    // -2 / -3 / -4 name the native class only on ITS entry points: these two ops are the reference's, and exact -- unless the NVFP4 weights have
+    // an MFMA-native image attached (petit_nvfp4_native_attach): they have opted into the native class then
+    const uint64_t sid = c_solution_id(solution_id, !mx && solution_id <= -2 && solution_id >= -4 && petit_nvfp4_native_attached(B.data_ptr()));
     const petit_epilogue epi{bias.has_value() ? bias->data_ptr() : nullptr, (int32_t)activation, 0};
     // per-call scratch from the caching allocator (stream-ordered, capture-safe): K-split slabs / native-FP4 activations
     const uint64_t ws_bytes = petit_gemm_workspace_bytes_ex(&hints, (unsigned)size_m, (unsigned)size_n, (unsigned)size_k, sid,
@@ -121,9 +191,8 @@ at::Tensor mul_a16(bool mx, const at::Tensor &A, const at::Tensor &B, const at::
     const int rc = fn((unsigned *)c.data_ptr(), (const unsigned *)A.data_ptr(), (const unsigned *)B.data_ptr(), (const unsigned *)s.data_ptr(),
                       (const float *)global_scale.data_ptr(), (unsigned)size_m, (unsigned)size_n, (unsigned)size_k, &hints, sid,
                       (bias.has_value() || activation) ? &epi : nullptr, ws_bytes ? ws.data_ptr() : nullptr, ws_bytes, stream_of(A));
-    TORCH_CHECK(rc != PETIT_ERROR_PROBLEM_SHAPE, "Incompatible problem shape (m=", size_m, ", n=", size_n, ", k=", size_k, ")");
-    TORCH_CHECK(rc != PETIT_ERROR_KERNEL_SHAPE, "No kernel implementation for solution_id=", sid == PETIT_SOLUTION_AUTO ? "-1" : std::to_string((int64_t)sid), ".");
-    TORCH_CHECK(rc == PETIT_OK, mx ? "mul_mxfp4_a16: " : "mul_nvfp4_a16: ", petit_error_string(rc));
+    if (rc != PETIT_OK) // (the id as the caller spelled it: PETIT_SOLUTION_AUTO reads -1)
+        check_gemm_rc(rc, mx ? "mul_mxfp4_a16" : "mul_nvfp4_a16", (int64_t)sid, c10::str("m=", size_m, ", n=", size_n, ", k=", size_k));
     return c;
 }
 at::Tensor mul_nvfp4_a16(const at::Tensor &A, const at::Tensor &B, const at::Tensor &s, const at::Tensor &gs, int64_t m, int64_t n, int64_t k,
@@ -139,38 +208,24 @@ at::Tensor mul_mxfp4_a16(const at::Tensor &A, const at::Tensor &B, const at::Ten
 at::Tensor mul_a16_moe(bool mx, const at::Tensor &A, const at::Tensor &B, const at::Tensor &s, const at::Tensor &global_scales,
                        const at::Tensor &expert_offsets, int64_t size_m, int64_t size_n, int64_t size_k, int64_t num_experts, int64_t solution_id,
                        const std::optional<at::Tensor> &bias, int64_t activation) {
-    const int64_t group = mx ? 32 : 16, E = num_experts;
-    TORCH_CHECK(A.scalar_type() == at::kBFloat16 || A.scalar_type() == at::kHalf, "A must be bfloat16 or float16.");
-    TORCH_CHECK(E >= 1 && E <= PETIT_MOE_MAX_EXPERTS, "num_experts must be in 1..", PETIT_MOE_MAX_EXPERTS, ", got ", E);
-    TORCH_CHECK(A.is_cuda() && B.is_cuda() && s.is_cuda() && global_scales.is_cuda() && expert_offsets.is_cuda(), "all tensors must be on GPU");
+    const int64_t E = num_experts;
+    check_a16(A);
+    check_expert_operands(mx, false, A, B, &s, global_scales, expert_offsets, E, size_n, size_k);
     TORCH_CHECK(A.is_contiguous() && A.numel() == size_m * size_k, "A must be a contiguous [size_m, size_k] tensor");
-    TORCH_CHECK(B.is_contiguous() && B.numel() * B.element_size() == E * size_n * size_k / 2,
-                "B does not hold num_experts * size_n * size_k packed 4-bit weights");
-    TORCH_CHECK(s.is_contiguous() && s.numel() * s.element_size() == E * size_n * size_k / group, "s does not hold num_experts * size_n * size_k / ",
-                group, " scales");
-    TORCH_CHECK(global_scales.scalar_type() == at::kFloat && global_scales.is_contiguous() && global_scales.numel() == E,
-                "global_scales must be a contiguous float32 [num_experts] tensor");
-    TORCH_CHECK(expert_offsets.scalar_type() == at::kInt && expert_offsets.is_contiguous() && expert_offsets.numel() == E + 1,
-                "expert_offsets must be a contiguous int32 [num_experts + 1] tensor");
-    TORCH_CHECK(activation >= 0 && activation <= 2, "activation must be 0 (none), 1 (silu_mul) or 2 (swiglu_oai)");
-    if (activation)
-        TORCH_CHECK(size_n % 32 == 0, "silu_mul / swiglu_oai need size_n % 32 == 0 (gate / up halves of whole tiles), got ", size_n);
-    if (bias.has_value())
-        TORCH_CHECK(bias->is_cuda() && bias->device() == A.device() && bias->scalar_type() == A.scalar_type() && bias->is_contiguous() &&
-                        bias->numel() == E * size_n,
-                    "bias must be a contiguous [num_experts, size_n] tensor of A's dtype on A's device");
+    check_activation(activation, size_n);
+    check_bias(bias, A, A.scalar_type(), E * size_n, "bias must be a contiguous [num_experts, size_n] tensor of A's dtype on A's device");
     const c10::hip::HIPGuardMasqueradingAsCUDA guard(A.device());
     at::Tensor c = at::empty({size_m, activation ? size_n / 2 : size_n}, A.options());
-    const int a_type = A.scalar_type() == at::kBFloat16 ? kCxxBf16 : kCxxFp16;
+    const int a_type = a_type_of(A.scalar_type());
     const petit_solution_hints hints{a_type, mx ? kCxxMxFp4 : kCxxFp4, a_type, 0};
-    const uint64_t sid = (solution_id < 0 && solution_id >= -4096) ? PETIT_SOLUTION_AUTO : (uint64_t)solution_id;
+    const uint64_t sid = c_solution_id(solution_id, false);
     const petit_epilogue epi{bias.has_value() ? bias->data_ptr() : nullptr, (int32_t)activation, 0};
     const int rc = petit_gemm_fp4_fp16_moe(c.data_ptr(), A.data_ptr(), B.data_ptr(), s.data_ptr(), (const float *)global_scales.data_ptr(),
                                            (const int32_t *)expert_offsets.data_ptr(), (unsigned)E, (unsigned)size_m, (unsigned)size_n,
                                            (unsigned)size_k, &hints, sid, (bias.has_value() || activation) ? &epi : nullptr, stream_of(A));
-    TORCH_CHECK(rc != PETIT_ERROR_PROBLEM_SHAPE, "Incompatible problem shape (m=", size_m, ", n=", size_n, ", k=", size_k, ", num_experts=", E, ")");
-    TORCH_CHECK(rc != PETIT_ERROR_KERNEL_SHAPE, "No kernel implementation for solution_id=", sid == PETIT_SOLUTION_AUTO ? "-1" : std::to_string((int64_t)sid), ".");
-    TORCH_CHECK(rc == PETIT_OK, mx ? "mul_mxfp4_a16_moe: " : "mul_nvfp4_a16_moe: ", petit_error_string(rc));
+    if (rc != PETIT_OK)
+        check_gemm_rc(rc, mx ? "mul_mxfp4_a16_moe" : "mul_nvfp4_a16_moe", (int64_t)sid,
+                      c10::str("m=", size_m, ", n=", size_n, ", k=", size_k, ", num_experts=", E));
     return c;
 }
 at::Tensor mul_nvfp4_a16_moe(const at::Tensor &A, const at::Tensor &B, const at::Tensor &s, const at::Tensor &gs, const at::Tensor &off, int64_t m,
@@ -188,31 +243,13 @@ at::Tensor mul_a16_moe_indexed_impl(bool mx, const at::Tensor &A, const at::Tens
                                     const at::Tensor &expert_offsets, int64_t size_m, int64_t size_n, int64_t size_k, int64_t num_experts,
                                     const std::optional<at::Tensor> &a_row_index, const std::optional<at::Tensor> &c_row_index, int64_t c_rows,
                                     int64_t solution_id, const std::optional<at::Tensor> &bias, int64_t activation, const at::Tensor *out) {
-    const int64_t group = mx ? 32 : 16, E = num_experts;
-    TORCH_CHECK(A.scalar_type() == at::kBFloat16 || A.scalar_type() == at::kHalf, "A must be bfloat16 or float16.");
-    TORCH_CHECK(E >= 1 && E <= PETIT_MOE_MAX_EXPERTS, "num_experts must be in 1..", PETIT_MOE_MAX_EXPERTS, ", got ", E);
-    TORCH_CHECK(A.is_cuda() && B.is_cuda() && s.is_cuda() && global_scales.is_cuda() && expert_offsets.is_cuda(), "all tensors must be on GPU");
+    const int64_t E = num_experts;
+    check_a16(A);
+    check_expert_operands(mx, false, A, B, &s, global_scales, expert_offsets, E, size_n, size_k);
     TORCH_CHECK(A.is_contiguous() && size_k > 0 && A.numel() % size_k == 0, "A must be a contiguous [a_rows, size_k] tensor");
-    TORCH_CHECK(B.is_contiguous() && B.numel() * B.element_size() == E * size_n * size_k / 2,
-                "B does not hold num_experts * size_n * size_k packed 4-bit weights");
-    TORCH_CHECK(s.is_contiguous() && s.numel() * s.element_size() == E * size_n * size_k / group, "s does not hold num_experts * size_n * size_k / ",
-                group, " scales");
-    TORCH_CHECK(global_scales.scalar_type() == at::kFloat && global_scales.is_contiguous() && global_scales.numel() == E,
-                "global_scales must be a contiguous float32 [num_experts] tensor");
-    TORCH_CHECK(expert_offsets.scalar_type() == at::kInt && expert_offsets.is_contiguous() && expert_offsets.numel() == E + 1,
-                "expert_offsets must be a contiguous int32 [num_experts + 1] tensor");
-    for (const auto *idx : {&a_row_index, &c_row_index})
-        if (idx->has_value())
-            TORCH_CHECK((*idx)->is_cuda() && (*idx)->device() == A.device() && (*idx)->scalar_type() == at::kInt && (*idx)->is_contiguous() &&
-                            (*idx)->numel() == size_m,
-                        "row indices must be contiguous int32 [size_m] tensors on A's device");
-    TORCH_CHECK(activation >= 0 && activation <= 2, "activation must be 0 (none), 1 (silu_mul) or 2 (swiglu_oai)");
-    if (activation)
-        TORCH_CHECK(size_n % 32 == 0, "silu_mul / swiglu_oai need size_n % 32 == 0 (gate / up halves of whole tiles), got ", size_n);
-    if (bias.has_value())
-        TORCH_CHECK(bias->is_cuda() && bias->device() == A.device() && bias->scalar_type() == A.scalar_type() && bias->is_contiguous() &&
-                        bias->numel() == E * size_n,
-                    "bias must be a contiguous [num_experts, size_n] tensor of A's dtype on A's device");
+    check_row_indices(a_row_index, c_row_index, A, size_m);
+    check_activation(activation, size_n);
+    check_bias(bias, A, A.scalar_type(), E * size_n, "bias must be a contiguous [num_experts, size_n] tensor of A's dtype on A's device");
     const int64_t a_rows = A.numel() / size_k, n_out = activation ? size_n / 2 : size_n;
     const c10::hip::HIPGuardMasqueradingAsCUDA guard(A.device());
     at::Tensor c;
@@ -227,19 +264,17 @@ at::Tensor mul_a16_moe_indexed_impl(bool mx, const at::Tensor &A, const at::Tens
         c_rows = c_rows < 0 ? size_m : c_rows;
         c = at::empty({c_rows, n_out}, A.options());
     }
-    const int a_type = A.scalar_type() == at::kBFloat16 ? kCxxBf16 : kCxxFp16;
+    const int a_type = a_type_of(A.scalar_type());
     const petit_solution_hints hints{a_type, mx ? kCxxMxFp4 : kCxxFp4, a_type, 0};
-    const uint64_t sid = (solution_id < 0 && solution_id >= -4096) ? PETIT_SOLUTION_AUTO : (uint64_t)solution_id;
+    const uint64_t sid = c_solution_id(solution_id, false);
     const petit_epilogue epi{bias.has_value() ? bias->data_ptr() : nullptr, (int32_t)activation, 0};
     const int rc = petit_gemm_fp4_fp16_moe_ex(c.data_ptr(), A.data_ptr(), B.data_ptr(), s.data_ptr(), (const float *)global_scales.data_ptr(),
                                               (const int32_t *)expert_offsets.data_ptr(), (unsigned)E, (unsigned)size_m, (unsigned)size_n,
-                                              (unsigned)size_k, a_row_index.has_value() ? (const int32_t *)a_row_index->data_ptr() : nullptr,
-                                              (unsigned)a_rows, c_row_index.has_value() ? (const int32_t *)c_row_index->data_ptr() : nullptr,
+                                              (unsigned)size_k, row_index_ptr(a_row_index), (unsigned)a_rows, row_index_ptr(c_row_index),
                                               (unsigned)c_rows, &hints, sid, (bias.has_value() || activation) ? &epi : nullptr, stream_of(A));
-    TORCH_CHECK(rc != PETIT_ERROR_PROBLEM_SHAPE, "Incompatible problem shape (m=", size_m, ", n=", size_n, ", k=", size_k, ", num_experts=", E,
-                ", a_rows=", a_rows, ", c_rows=", c_rows, ")");
-    TORCH_CHECK(rc != PETIT_ERROR_KERNEL_SHAPE, "No kernel implementation for solution_id=", sid == PETIT_SOLUTION_AUTO ? "-1" : std::to_string((int64_t)sid), ".");
-    TORCH_CHECK(rc == PETIT_OK, mx ? "mul_mxfp4_a16_moe_indexed: " : "mul_nvfp4_a16_moe_indexed: ", petit_error_string(rc));
+    if (rc != PETIT_OK)
+        check_gemm_rc(rc, mx ? "mul_mxfp4_a16_moe_indexed" : "mul_nvfp4_a16_moe_indexed", (int64_t)sid,
+                      c10::str("m=", size_m, ", n=", size_n, ", k=", size_k, ", num_experts=", E, ", a_rows=", a_rows, ", c_rows=", c_rows));
     return c;
 }
 #define PETIT_MOE_INDEXED_ARGS                                                                                                                   \
@@ -297,7 +332,7 @@ at::Tensor moe_combine(const at::Tensor &slot_out, const at::Tensor &topk_weight
     at::Tensor out = at::empty({T, n}, slot_out.options());
     const int rc = petit_moe_combine(out.data_ptr(), slot_out.data_ptr(), (const float *)topk_weights.data_ptr(), topk_ids.data_ptr(),
                                      topk_ids.scalar_type() == at::kLong, (unsigned)T, (unsigned)topk, (unsigned)n, (unsigned)num_experts,
-                                     slot_out.scalar_type() == at::kBFloat16 ? kCxxBf16 : kCxxFp16, stream_of(slot_out));
+                                     a_type_of(slot_out.scalar_type()), stream_of(slot_out));
     TORCH_CHECK(rc != PETIT_ERROR_PROBLEM_SHAPE, "Incompatible routing shape (num_tokens=", T, ", topk=", topk, ", n=", n, ", num_experts=", num_experts, ")");
     TORCH_CHECK(rc == PETIT_OK, "moe_combine: ", petit_error_string(rc));
     return out;
@@ -308,7 +343,7 @@ at::Tensor moe_combine(const at::Tensor &slot_out, const at::Tensor &topk_weight
     const at::Tensor &router_logits, int64_t topk, int64_t scoring, bool renormalize, const std::optional<at::Tensor> &bias, int64_t n_group, \
         int64_t topk_group, double routed_scaling_factor, bool return_keys
 int route_logits_dtype(const at::Tensor &t) {
-    return t.scalar_type() == at::kFloat ? PETIT_DTYPE_FP32 : t.scalar_type() == at::kBFloat16 ? kCxxBf16 : kCxxFp16;
+    return t.scalar_type() == at::kFloat ? PETIT_DTYPE_FP32 : a_type_of(t.scalar_type());
 }
 petit_route_desc check_route(PETIT_ROUTE_ARGS) {
     TORCH_CHECK(scoring == PETIT_ROUTE_SOFTMAX || scoring == PETIT_ROUTE_SIGMOID, "scoring must be 'softmax' or 'sigmoid'");
@@ -377,7 +412,7 @@ std::tuple<at::Tensor, at::Tensor, at::Tensor, at::Tensor, at::Tensor, at::Tenso
         const std::optional<at::Tensor> &bias, int64_t activation, int64_t a_format, int64_t a_type, int64_t out_format
 at::ScalarType native_moe_dtype(const at::Tensor &A, int64_t a_format, int64_t a_type) {
     if (!a_format) {
-        TORCH_CHECK(A.scalar_type() == at::kBFloat16 || A.scalar_type() == at::kHalf, "A must be bfloat16 or float16.");
+        check_a16(A);
         return A.scalar_type();
     }
     TORCH_CHECK(A.scalar_type() == at::kByte && (a_type == kCxxBf16 || a_type == kCxxFp16), "quantised activations are uint8 bytes of a bf16 / fp16 matrix");
@@ -386,52 +421,22 @@ at::ScalarType native_moe_dtype(const at::Tensor &A, int64_t a_format, int64_t a
 at::Tensor mul_native_moe_impl(bool mx, PETIT_NATIVE_MOE_ARGS) {
     const int64_t E = num_experts;
     const at::ScalarType dtype = native_moe_dtype(A, a_format, a_type);
-    TORCH_CHECK(E >= 1 && E <= PETIT_MOE_MAX_EXPERTS, "num_experts must be in 1..", PETIT_MOE_MAX_EXPERTS, ", got ", E);
-    TORCH_CHECK(A.is_cuda() && B.is_cuda() && global_scales.is_cuda() && expert_offsets.is_cuda() && A.is_contiguous() && B.is_contiguous(),
-                "all tensors must be on GPU");
+    check_expert_operands(mx, true, A, B, s.has_value() ? &*s : nullptr, global_scales, expert_offsets, E, size_n, size_k);
     TORCH_CHECK(size_k > 0 && (a_format || A.numel() % size_k == 0), "A must be a contiguous [a_rows, size_k] bfloat16 / float16 GPU tensor");
     if (a_format)
         TORCH_CHECK(A.numel() == (int64_t)petit_quantized_activation_bytes((unsigned)size_m, (unsigned)size_k, (int)a_format) && !a_row_index.has_value(),
                     "quantised activations are grouped rows already: a_row_index must be None");
-    if (mx) {
-        TORCH_CHECK(B.numel() * B.element_size() == E * size_n * size_k / 2, "B does not hold num_experts * size_n * size_k packed 4-bit weights");
-        TORCH_CHECK(s.has_value() && s->is_cuda() && s->is_contiguous() && s->numel() * s->element_size() == E * size_n * size_k / 32,
-                    "s does not hold num_experts * size_n * size_k / 32 scales");
-    } else {
-        const int64_t per = (int64_t)petit_nvfp4_native_image_bytes((unsigned)size_k, (unsigned)size_n);
-        TORCH_CHECK(B.scalar_type() == at::kByte && per > 0 && B.numel() == E * per, "images do not hold num_experts native images (nvfp4_native_images)");
-    }
-    TORCH_CHECK(global_scales.scalar_type() == at::kFloat && global_scales.is_contiguous() && global_scales.numel() == E,
-                "global_scales must be a contiguous float32 [num_experts] tensor");
-    TORCH_CHECK(expert_offsets.scalar_type() == at::kInt && expert_offsets.is_contiguous() && expert_offsets.numel() == E + 1,
-                "expert_offsets must be a contiguous int32 [num_experts + 1] tensor");
-    for (const auto *idx : {&a_row_index, &c_row_index})
-        if (idx->has_value())
-            TORCH_CHECK((*idx)->is_cuda() && (*idx)->device() == A.device() && (*idx)->scalar_type() == at::kInt && (*idx)->is_contiguous() &&
-                            (*idx)->numel() == size_m,
-                        "row indices must be contiguous int32 [size_m] tensors on A's device");
-    TORCH_CHECK(activation >= 0 && activation <= 2, "activation must be 0 (none), 1 (silu_mul) or 2 (swiglu_oai)");
+    check_row_indices(a_row_index, c_row_index, A, size_m);
+    check_activation(activation);
     TORCH_CHECK(!out_format || (activation && !c_row_index.has_value()), "out_quantized needs activation='silu_mul' or 'swiglu_oai' and no c_row_index");
-    if (bias.has_value())
-        TORCH_CHECK(bias->is_cuda() && bias->device() == A.device() && bias->scalar_type() == dtype && bias->is_contiguous() && bias->numel() == E * size_n,
-                    "bias must be a contiguous [num_experts, size_n] tensor of the activation dtype on the same device");
+    check_bias(bias, A, dtype, E * size_n, "bias must be a contiguous [num_experts, size_n] tensor of the activation dtype on the same device");
     const int64_t a_rows = a_format ? size_m : A.numel() / size_k, n_out = activation ? size_n / 2 : size_n;
     const c10::hip::HIPGuardMasqueradingAsCUDA guard(A.device());
-    at::Tensor c;
-    if (out_format) {
-        c_rows = size_m;
-        c = at::empty({(int64_t)petit_quantized_activation_bytes((unsigned)size_m, (unsigned)n_out, (int)out_format)}, A.options().dtype(at::kByte));
-    } else {
-        c_rows = c_rows < 0 ? size_m : c_rows;
-        c = at::empty({c_rows, n_out}, A.options().dtype(dtype));
-    }
-    const int at_code = dtype == at::kBFloat16 ? kCxxBf16 : kCxxFp16;
+    c_rows = out_format || c_rows < 0 ? size_m : c_rows;
+    at::Tensor c = native_output(A, dtype, c_rows, size_m, n_out, out_format);
+    const int at_code = a_type_of(dtype);
     const petit_solution_hints hints{at_code, mx ? kCxxMxFp4 : kCxxFp4, at_code, 0};
-    const uint64_t sid = solution_id == -2   ? PETIT_SOLUTION_AUTO_NATIVE_MXFP8
-                         : solution_id == -3 ? PETIT_SOLUTION_AUTO_NATIVE_MXFP4
-                         : solution_id == -4 ? PETIT_SOLUTION_AUTO_NATIVE_MXFP6
-                         : solution_id < 0   ? PETIT_SOLUTION_AUTO
-                                             : (uint64_t)solution_id;
+    const uint64_t sid = c_solution_id(solution_id, true);
     const petit_epilogue epi{bias.has_value() ? bias->data_ptr() : nullptr, (int32_t)activation, 0};
     const petit_epilogue *epi_p = (bias.has_value() || activation) ? &epi : nullptr;
     const petit_native_args na{sizeof(petit_native_args), (int32_t)a_format, (int32_t)out_format, 0};
@@ -439,13 +444,11 @@ at::Tensor mul_native_moe_impl(bool mx, PETIT_NATIVE_MOE_ARGS) {
     at::Tensor ws = at::empty({(int64_t)ws_bytes}, A.options().dtype(at::kByte));
     const int rc = petit_gemm_native_moe(c.data_ptr(), A.data_ptr(), B.data_ptr(), mx ? s->data_ptr() : nullptr, (const float *)global_scales.data_ptr(),
                                          (const int32_t *)expert_offsets.data_ptr(), (unsigned)E, (unsigned)size_m, (unsigned)size_n, (unsigned)size_k,
-                                         a_row_index.has_value() ? (const int32_t *)a_row_index->data_ptr() : nullptr, (unsigned)a_rows,
-                                         c_row_index.has_value() ? (const int32_t *)c_row_index->data_ptr() : nullptr, (unsigned)c_rows, &hints, sid,
-                                         epi_p, &na, ws_bytes ? ws.data_ptr() : nullptr, ws_bytes, stream_of(A));
-    TORCH_CHECK(rc != PETIT_ERROR_PROBLEM_SHAPE, "Incompatible problem shape (m=", size_m, ", n=", size_n, ", k=", size_k, ", num_experts=", E,
-                ", a_rows=", a_rows, ", c_rows=", c_rows, ")");
-    TORCH_CHECK(rc != PETIT_ERROR_KERNEL_SHAPE, "No kernel implementation for solution_id=", solution_id < 0 ? std::to_string(solution_id) : std::to_string((int64_t)sid), ".");
-    TORCH_CHECK(rc == PETIT_OK, mx ? "mul_mxfp4_native_moe: " : "mul_nvfp4_native_moe: ", petit_error_string(rc));
+                                         row_index_ptr(a_row_index), (unsigned)a_rows, row_index_ptr(c_row_index), (unsigned)c_rows, &hints, sid, epi_p, &na,
+                                         ws_bytes ? ws.data_ptr() : nullptr, ws_bytes, stream_of(A));
+    if (rc != PETIT_OK)
+        check_gemm_rc(rc, mx ? "mul_mxfp4_native_moe" : "mul_nvfp4_native_moe", solution_id,
+                      c10::str("m=", size_m, ", n=", size_n, ", k=", size_k, ", num_experts=", E, ", a_rows=", a_rows, ", c_rows=", c_rows));
     return c;
 }
 at::Tensor mul_mxfp4_native_moe(PETIT_NATIVE_MOE_ARGS) {
@@ -472,22 +475,14 @@ at::Tensor mul_nvfp4_native_transient(PETIT_NV_TRANSIENT_ARGS) {
     TORCH_CHECK(B.is_cuda() && s.is_cuda() && global_scale.is_cuda(), "all tensors must be on GPU");
     TORCH_CHECK(B.is_contiguous() && B.numel() * B.element_size() == size_n * size_k / 2, "B does not hold size_n * size_k packed 4-bit weights");
     TORCH_CHECK(s.is_contiguous() && s.numel() * s.element_size() == size_n * size_k / 16, "s does not hold size_n * size_k / 16 scales");
-    TORCH_CHECK(activation >= 0 && activation <= 2, "activation must be 0 (none), 1 (silu_mul) or 2 (swiglu_oai)");
+    check_activation(activation);
     TORCH_CHECK(!out_format || activation, "out_quantized needs activation='silu_mul' or 'swiglu_oai'");
-    if (bias.has_value())
-        TORCH_CHECK(bias->is_cuda() && bias->device() == A.device() && bias->scalar_type() == dtype && bias->is_contiguous() && bias->numel() == size_n,
-                    "bias must be a contiguous [size_n] tensor of the activation dtype on the same device");
+    check_bias(bias, A, dtype, size_n, "bias must be a contiguous [size_n] tensor of the activation dtype on the same device");
     const c10::hip::HIPGuardMasqueradingAsCUDA guard(A.device());
-    const int64_t n_out = activation ? size_n / 2 : size_n;
-    at::Tensor c = out_format ? at::empty({(int64_t)petit_quantized_activation_bytes((unsigned)size_m, (unsigned)n_out, (int)out_format)}, A.options().dtype(at::kByte))
-                              : at::empty({size_m, n_out}, A.options().dtype(dtype));
-    const int at_code = dtype == at::kBFloat16 ? kCxxBf16 : kCxxFp16;
+    at::Tensor c = native_output(A, dtype, size_m, size_m, activation ? size_n / 2 : size_n, out_format);
+    const int at_code = a_type_of(dtype);
     const petit_solution_hints hints{at_code, kCxxFp4, at_code, 0};
-    const uint64_t sid = solution_id == -2   ? PETIT_SOLUTION_AUTO_NATIVE_MXFP8
-                         : solution_id == -3 ? PETIT_SOLUTION_AUTO_NATIVE_MXFP4
-                         : solution_id == -4 ? PETIT_SOLUTION_AUTO_NATIVE_MXFP6
-                         : solution_id < 0   ? PETIT_SOLUTION_AUTO
-                                             : (uint64_t)solution_id;
+    const uint64_t sid = c_solution_id(solution_id, true);
     const petit_epilogue epi{bias.has_value() ? bias->data_ptr() : nullptr, (int32_t)activation, 0};
     const petit_epilogue *epi_p = (bias.has_value() || activation) ? &epi : nullptr;
     const petit_native_args na{sizeof(petit_native_args), (int32_t)a_format, (int32_t)out_format, 0};
@@ -496,9 +491,8 @@ at::Tensor mul_nvfp4_native_transient(PETIT_NV_TRANSIENT_ARGS) {
     const int rc = petit_gemm_nvfp4_native_transient(c.data_ptr(), A.data_ptr(), (const unsigned *)B.data_ptr(), (const unsigned *)s.data_ptr(),
                                                      (const float *)global_scale.data_ptr(), (unsigned)size_m, (unsigned)size_n, (unsigned)size_k, &hints,
                                                      sid, epi_p, &na, ws_bytes ? ws.data_ptr() : nullptr, ws_bytes, stream_of(A));
-    TORCH_CHECK(rc != PETIT_ERROR_PROBLEM_SHAPE, "Incompatible problem shape (m=", size_m, ", n=", size_n, ", k=", size_k, ")");
-    TORCH_CHECK(rc != PETIT_ERROR_KERNEL_SHAPE, "No kernel implementation for solution_id=", solution_id < 0 ? std::to_string(solution_id) : std::to_string((int64_t)sid), ".");
-    TORCH_CHECK(rc == PETIT_OK, "mul_nvfp4_native_transient: ", petit_error_string(rc));
+    if (rc != PETIT_OK)
+        check_gemm_rc(rc, "mul_nvfp4_native_transient", solution_id, c10::str("m=", size_m, ", n=", size_n, ", k=", size_k));
     return c;
 }
 
@@ -509,33 +503,25 @@ at::Tensor process_nvfp4_scales_meta(const at::Tensor &s, int64_t n, int64_t k) 
 at::Tensor process_mxfp4_scales_meta(const at::Tensor &s, int64_t n, int64_t k) { return at::empty({n / 32, k}, s.options()); }
 at::Tensor mul_a16_meta(const at::Tensor &A, const at::Tensor &, const at::Tensor &, const at::Tensor &, int64_t m, int64_t n, int64_t, int64_t,
                         const std::optional<at::Tensor> &, int64_t activation) {
-    TORCH_CHECK(A.scalar_type() == at::kBFloat16 || A.scalar_type() == at::kHalf, "A must be bfloat16 or float16.");
+    check_a16(A);
     return at::empty({m, activation ? n / 2 : n}, A.options());
 }
 at::Tensor mul_a16_moe_meta(const at::Tensor &A, const at::Tensor &, const at::Tensor &, const at::Tensor &, const at::Tensor &, int64_t m, int64_t n,
                             int64_t, int64_t, int64_t, const std::optional<at::Tensor> &, int64_t activation) {
-    TORCH_CHECK(A.scalar_type() == at::kBFloat16 || A.scalar_type() == at::kHalf, "A must be bfloat16 or float16.");
+    check_a16(A);
     return at::empty({m, activation ? n / 2 : n}, A.options());
 }
 
 at::Tensor mul_a16_moe_indexed_meta(PETIT_MOE_INDEXED_ARGS) {
-    TORCH_CHECK(A.scalar_type() == at::kBFloat16 || A.scalar_type() == at::kHalf, "A must be bfloat16 or float16.");
+    check_a16(A);
     return at::empty({c_rows < 0 ? m : c_rows, activation ? n / 2 : n}, A.options());
 }
 void mul_a16_moe_indexed_out_meta(const at::Tensor &, PETIT_MOE_INDEXED_ARGS) {}
 at::Tensor mul_nvfp4_native_transient_meta(PETIT_NV_TRANSIENT_ARGS) {
-    const at::ScalarType dtype = native_moe_dtype(A, a_format, a_type);
-    const int64_t n_out = activation ? size_n / 2 : size_n;
-    if (out_format)
-        return at::empty({(int64_t)petit_quantized_activation_bytes((unsigned)size_m, (unsigned)n_out, (int)out_format)}, A.options().dtype(at::kByte));
-    return at::empty({size_m, n_out}, A.options().dtype(dtype));
+    return native_output(A, native_moe_dtype(A, a_format, a_type), size_m, size_m, activation ? size_n / 2 : size_n, out_format);
 }
 at::Tensor mul_native_moe_meta(PETIT_NATIVE_MOE_ARGS) {
-    const at::ScalarType dtype = native_moe_dtype(A, a_format, a_type);
-    const int64_t n_out = activation ? size_n / 2 : size_n;
-    if (out_format)
-        return at::empty({(int64_t)petit_quantized_activation_bytes((unsigned)size_m, (unsigned)n_out, (int)out_format)}, A.options().dtype(at::kByte));
-    return at::empty({c_rows < 0 ? size_m : c_rows, n_out}, A.options().dtype(dtype));
+    return native_output(A, native_moe_dtype(A, a_format, a_type), c_rows < 0 ? size_m : c_rows, size_m, activation ? size_n / 2 : size_n, out_format);
 }
 std::tuple<at::Tensor, at::Tensor, at::Tensor> moe_align_device_meta(const at::Tensor &topk_ids, int64_t num_experts) {
     const auto i32 = topk_ids.options().dtype(at::kInt);

@@ -14,6 +14,7 @@ from pathlib import Path
 import torch
 
 from . import _lib  # loads libpetit_amd.so first (the binding links against it)
+from .ops import QuantizedActivations, _a_type, _activation as _act, _activation_operand, _quantized_format
 
 LIB_PATH = Path(_lib.LIB_PATH).parent / "libpetit_torch.so"
 _loaded = False
@@ -42,24 +43,20 @@ def why_unavailable() -> str:
     return _error or ""
 
 
-_ACT = {None: 0, "none": 0, "silu_mul": 1, "swiglu_oai": 2}
-
-
-def _act(activation) -> int:
-    if activation not in _ACT:
-        raise RuntimeError(f"activation must be one of {sorted(k for k in _ACT if k)} or None")
-    return _ACT[activation]
-
-
-def _sid(solution_id: int) -> int:
+def _sid(solution_id: int, native: bool = False) -> int:
     """Python id -> the signed 64-bit value the op schema carries (`int` = int64).  Ids are unsigned 64-bit patterns with
     the K split in bits 60-63, so a split of 8..15 does not fit a signed int64 as such: it crosses as its two's-complement
-    value and the binding reinterprets it.  Any negative id means "library default" (reference: fp4.cc:189-191)."""
+    value and the binding reinterprets it.  Any negative id means "library default" (reference: fp4.cc:189-191).
+    native: for the native ops, which read every negative value but -2 / -3 / -4 as the library default: an id of 2^63 or more goes to them
+    as it is, and the schema's int64 refuses it."""
     solution_id = int(solution_id)
     if solution_id < 0:
-        # -2 / -3 / -4 cross as they are: the binding reads them as the native-class sentinels ONLY for NVFP4 weights that have an MFMA-native image
-        # attached (attach_nvfp4_native: the caller's opt-in), as the library default everywhere else -- the reference's meaning of any negative id
+        # -2 / -3 / -4 cross as they are.  The native ops read them as the native-class sentinels (the caller has opted in by calling them); the
+        # reference's ops do so ONLY for NVFP4 weights that have an MFMA-native image attached (attach_nvfp4_native: the caller's opt-in), and
+        # as the library default everywhere else -- the reference's meaning of any negative id
         return solution_id if solution_id >= -4 else -1
+    if native:
+        return solution_id
     if solution_id >= 1 << 64:
         raise RuntimeError(f"No kernel implementation for solution_id={solution_id}.")
     return solution_id - (1 << 64) if solution_id >= 1 << 63 else solution_id
@@ -150,28 +147,19 @@ def moe_route_align(router_logits, topk, scoring="softmax", renormalize=True, bi
     return (w, ids, sp, off, ti, keys) if return_keys else (w, ids, sp, off, ti)
 
 
-def _native_sid(solution_id: int) -> int:
-    # the native MoE ops read -2 / -3 / -4 as the native sentinels (the caller has opted in by calling them); other negatives: PETIT_SOLUTION_AUTO
-    solution_id = int(solution_id)
-    return solution_id if solution_id >= -4 else -1 if solution_id < 0 else _sid(solution_id)
+def _native_operands(A, size_m, size_k, out_quantized):
+    """What the native ops take in place of A and out_quantized: (activation tensor, a_format, a_type, out_format, 16-bit dtype)."""
+    out_fmt = _quantized_format(out_quantized, "out_quantized must be None, 'mxfp8', 'mxfp6' or 'mxfp4'")
+    a_t, dtype, a_fmt = _activation_operand(A, size_m, size_k)
+    return a_t, a_fmt, _a_type(dtype), out_fmt, dtype
 
 
 def _mul_native_moe(kind, A, B, s, global_scales, expert_offsets, size_m, size_n, size_k, num_experts, a_row_index, c_row_index, c_rows,
                     solution_id, bias, activation, out_quantized):
-    from .ops import _QFORMATS, QuantizedActivations
-    if out_quantized is not None and out_quantized not in _QFORMATS:
-        raise RuntimeError("out_quantized must be None, 'mxfp8', 'mxfp6' or 'mxfp4'")
-    out_fmt = _QFORMATS[out_quantized] if out_quantized else 0
-    if isinstance(A, QuantizedActivations):
-        if A.m != size_m or A.k != size_k:
-            raise RuntimeError(f"quantised activations are [{A.m}, {A.k}], the call says [{size_m}, {size_k}]")
-        a_t, a_fmt, dtype = A.data, _QFORMATS[A.fmt], A.dtype
-    else:
-        a_t, a_fmt, dtype = A, 0, A.dtype
-    a_type = 5 if dtype == torch.bfloat16 else 4
+    a_t, a_fmt, a_type, out_fmt, dtype = _native_operands(A, size_m, size_k, out_quantized)
     c = getattr(torch.ops.petit_kernel, f"mul_{kind}fp4_native_moe")(a_t, B, s, global_scales, expert_offsets, size_m, size_n, size_k, num_experts,
                                                                       a_row_index, c_row_index, -1 if c_rows is None else int(c_rows),
-                                                                      _native_sid(solution_id), bias, _act(activation), a_fmt, a_type, out_fmt)
+                                                                      _sid(solution_id, native=True), bias, _act(activation), a_fmt, a_type, out_fmt)
     return QuantizedActivations(c, size_m, size_n // 2, out_quantized, dtype) if out_fmt else c
 
 
@@ -188,17 +176,7 @@ def mul_nvfp4_native_moe(A, images, global_scales, expert_offsets, size_m, size_
 
 
 def mul_nvfp4_native_transient(A, B, s, global_scale, size_m, size_n, size_k, solution_id=-2, bias=None, activation=None, out_quantized=None):
-    from .ops import _QFORMATS, QuantizedActivations
-    if out_quantized is not None and out_quantized not in _QFORMATS:
-        raise RuntimeError("out_quantized must be None, 'mxfp8', 'mxfp6' or 'mxfp4'")
-    out_fmt = _QFORMATS[out_quantized] if out_quantized else 0
-    if isinstance(A, QuantizedActivations):
-        if A.m != size_m or A.k != size_k:
-            raise RuntimeError(f"quantised activations are [{A.m}, {A.k}], the call says [{size_m}, {size_k}]")
-        a_t, a_fmt, dtype = A.data, _QFORMATS[A.fmt], A.dtype
-    else:
-        a_t, a_fmt, dtype = A, 0, A.dtype
-    a_type = 5 if dtype == torch.bfloat16 else 4
-    c = torch.ops.petit_kernel.mul_nvfp4_native_transient(a_t, B, s, global_scale, size_m, size_n, size_k, _native_sid(solution_id), bias,
-                                                          _act(activation), a_fmt, a_type, out_fmt)
+    a_t, a_fmt, a_type, out_fmt, dtype = _native_operands(A, size_m, size_k, out_quantized)
+    c = torch.ops.petit_kernel.mul_nvfp4_native_transient(a_t, B, s, global_scale, size_m, size_n, size_k, _sid(solution_id, native=True),
+                                                          bias, _act(activation), a_fmt, a_type, out_fmt)
     return QuantizedActivations(c, size_m, size_n // 2, out_quantized, dtype) if out_fmt else c

@@ -89,13 +89,17 @@ def fp4_moe_fused(hidden: torch.Tensor, w13: torch.Tensor, s13: torch.Tensor, gs
     [0, E) (-1 under expert parallelism) contribute nothing.  topk_weights: float32 or bfloat16 [T, topk] (converted to float32 once).
     bias13 / bias2 / activation: as fp4_moe (the biases ride in the gate_up and down launches: no launch more).
     No host sync: capturable in a graph and replayable with any routing of the same shape."""
-    from . import moe_align_device
     _check_fused(kind, activation)
-    E = gs13.numel()
+    w, ids, sorted_pos, offsets, token_index = _align_routing(topk_weights, topk_ids, gs13.numel())
+    return _fused_after_align(hidden, w13, s13, gs13, w2, s2, gs2, w, ids, sorted_pos, offsets, token_index, kind, bias13, bias2, activation)
+
+
+def _align_routing(topk_weights, topk_ids, num_experts):
+    """The routing as the fused and native layers take it: (float32 weights, int32 / int64 ids, both contiguous, then moe_align_device of the ids)."""
+    from . import moe_align_device
     ids = topk_ids if topk_ids.dtype in (torch.int32, torch.int64) and topk_ids.is_contiguous() else topk_ids.contiguous().to(torch.int64)
     w = topk_weights if topk_weights.dtype == torch.float32 and topk_weights.is_contiguous() else topk_weights.float().contiguous()
-    sorted_pos, offsets, token_index = moe_align_device(ids, E)
-    return _fused_after_align(hidden, w13, s13, gs13, w2, s2, gs2, w, ids, sorted_pos, offsets, token_index, kind, bias13, bias2, activation)
+    return (w, ids) + tuple(moe_align_device(ids, num_experts))
 
 
 def _check_fused(kind, activation) -> None:
@@ -132,12 +136,8 @@ def fp4_moe_native(hidden: torch.Tensor, w13: torch.Tensor, s13, gs13: torch.Ten
     when the align needs its three-launch form): the device align, the gathering quantiser, gate_up with SiLU-mul writing the quantised
     grouped rows down reads, down scattered into slot order, the top-k combine.  bias13 / bias2 / activation: as fp4_moe; 'swiglu_oai' is
     quantised for down from its f32 value, as SiLU-mul is.  No host sync: capturable."""
-    from . import moe_align_device
     _check_native(kind, activation, activations)
-    E = gs13.numel()
-    ids = topk_ids if topk_ids.dtype in (torch.int32, torch.int64) and topk_ids.is_contiguous() else topk_ids.contiguous().to(torch.int64)
-    w = topk_weights if topk_weights.dtype == torch.float32 and topk_weights.is_contiguous() else topk_weights.float().contiguous()
-    sorted_pos, offsets, token_index = moe_align_device(ids, E)
+    w, ids, sorted_pos, offsets, token_index = _align_routing(topk_weights, topk_ids, gs13.numel())
     return _native_after_align(hidden, w13, s13, gs13, w2, s2, gs2, w, ids, sorted_pos, offsets, token_index, kind, activations, bias13, bias2,
                                activation)
 
@@ -156,25 +156,23 @@ def _native_after_align(hidden, w13, s13, gs13, w2, s2, gs2, w, ids, sorted_pos,
     from . import moe_combine, mul_mxfp4_native_moe, mul_nvfp4_native_moe, quantize_activation_rows
     sid = _NATIVE_SENTINELS[activations]
     T, H = hidden.shape
-    topk = ids.shape[1]
     E = gs13.numel()
+    m = T * ids.shape[1]
     if kind == "mxfp4":
         n13 = w13.numel() * w13.element_size() * 2 // (E * H)   # 2 I
-        mul13 = lambda a, **kw: mul_mxfp4_native_moe(a, w13, s13, gs13, offsets, m, n13, H, E, solution_id=sid, **kw)  # noqa: E731
-        mul2 = lambda a, **kw: mul_mxfp4_native_moe(a, w2, s2, gs2, offsets, m, n2, inter, E, solution_id=sid, **kw)  # noqa: E731
+        inter = n13 // 2
+        n2 = _down_n(w2, E, inter, H)
+        mul, gate_up, down = mul_mxfp4_native_moe, (w13, s13, gs13), (w2, s2, gs2)
     else:
         n13 = w13.numel() * 32 // (E * H * 25)                  # an image holds 25 / 32 bytes per weight (6.25 bits)
-        mul13 = lambda a, **kw: mul_nvfp4_native_moe(a, w13, gs13, offsets, m, n13, H, E, solution_id=sid, **kw)  # noqa: E731
-        mul2 = lambda a, **kw: mul_nvfp4_native_moe(a, w2, gs2, offsets, m, n2, inter, E, solution_id=sid, **kw)  # noqa: E731
-    inter = n13 // 2
-    n2 = _down_n(w2, E, inter, H) if kind == "mxfp4" else H
-    m = T * topk
+        inter = n13 // 2
+        n2 = H
+        mul, gate_up, down = mul_nvfp4_native_moe, (w13, gs13), (w2, gs2)
     qa = quantize_activation_rows(hidden, activations, token_index)                  # grouped rows; unrouted (-1) rows are zeros
-    if n13 % 512 == 0:
-        h = mul13(qa, bias=bias13, activation=activation, out_quantized=activations)  # down's quantised input, grouped
-    else:
-        h = mul13(qa, bias=bias13, activation=activation)                            # 16-bit; down quantises it (one more launch)
-    y = mul2(h, c_row_index=sorted_pos, c_rows=m, bias=bias2)                        # [m, n2], (token, slot) order
+    # gate_up writes down's quantised input, grouped, where its tiles allow; else 16-bit, and down quantises it (one more launch)
+    h = mul(qa, *gate_up, offsets, m, n13, H, E, solution_id=sid, bias=bias13, activation=activation,
+            out_quantized=activations if n13 % 512 == 0 else None)
+    y = mul(h, *down, offsets, m, n2, inter, E, solution_id=sid, c_row_index=sorted_pos, c_rows=m, bias=bias2)   # [m, n2], (token, slot) order
     return moe_combine(y, w, ids, E)
 
 

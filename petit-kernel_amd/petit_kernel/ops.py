@@ -33,9 +33,31 @@ def _ptr(t: torch.Tensor) -> C.c_void_p:
     return C.c_void_p(t.data_ptr())
 
 
+def _opt_ptr(t):
+    return None if t is None else C.c_void_p(t.data_ptr())
+
+
 def _raise_on(code: int, what: str) -> None:
     if code != _lib.PETIT_OK:
         raise RuntimeError(f"{what}: {_lib.error_string(code)}")
+
+
+def _raise_gemm(err: int, name: str, solution_id, shape_text: str) -> None:
+    """A GEMM entry point's return code as the caller sees it: the two refusals in the reference's words, anything else in the library's."""
+    if err == _lib.PETIT_ERROR_PROBLEM_SHAPE:
+        raise RuntimeError(f"Incompatible problem shape ({shape_text})")
+    if err == _lib.PETIT_ERROR_KERNEL_SHAPE:
+        raise RuntimeError(f"No kernel implementation for solution_id={solution_id}.")
+    _raise_on(err, name)
+
+
+def _a_type(dtype: torch.dtype) -> int:
+    return _lib.CXX_DTYPE_BF16 if dtype == torch.bfloat16 else _lib.CXX_DTYPE_FP16
+
+
+def _scratch(nbytes: int, dev):
+    """Per-call scratch from torch's stream-ordered caching allocator (safe with several streams and under graph capture), or None."""
+    return torch.empty(nbytes, dtype=torch.uint8, device=dev) if nbytes else None
 
 
 class PetitSolutionHints:
@@ -143,6 +165,37 @@ def process_mxfp4_scales(scales: torch.Tensor, size_n: int, size_k: int) -> torc
 
 
 _ACTIVATIONS = {None: 0, "none": 0, "silu_mul": 1, "swiglu_oai": 2}   # PETIT_ACTIVATION_* (include/petit_amd.h)
+_B_TYPES = {"nv": _lib.CXX_DTYPE_FP4_E2M1, "nvfp4": _lib.CXX_DTYPE_FP4_E2M1, "mx": _lib.CXX_DTYPE_MXFP4_E2M1, "mxfp4": _lib.CXX_DTYPE_MXFP4_E2M1}
+_ACTIVATION_RULE = f"activation must be one of {sorted(k for k in _ACTIVATIONS if k)} or None"
+
+
+def _activation(activation, size_n=None) -> int:
+    """The epilogue's activation code; with size_n, also the gated forms' shape rule."""
+    _check(activation in _ACTIVATIONS, _ACTIVATION_RULE)
+    act = _ACTIVATIONS[activation]
+    if act and size_n is not None:
+        _check(size_n % 32 == 0, f"{activation} needs size_n % 32 == 0 (gate / up halves of whole tiles), got {size_n}")
+    return act
+
+
+def _query_epilogue(activation):
+    """The epilogue argument of the queries (of the epilogue only the activation matters to a pick): a reference, or None without one."""
+    act = _ACTIVATIONS[activation]
+    return C.byref(_lib.Epilogue(None, act, 0)) if act else None
+
+
+def _epilogue(bias, act: int, dev, dtype, numel: int, text: str):
+    """The fused epilogue c = round16(act(acc * gs + bias[n])) (include/petit_amd.h, petit_epilogue) as the C call's argument: a reference,
+    or None when the call has neither part.  `text`: the rule a bias breaks when it is not `numel` contiguous elements of `dtype` on `dev`."""
+    if bias is None:
+        return C.byref(_lib.Epilogue(None, act, 0)) if act else None
+    _check(bias.is_cuda and bias.device == dev and bias.dtype == dtype and bias.is_contiguous() and bias.numel() == numel, text)
+    return C.byref(_lib.Epilogue(bias.data_ptr(), act, 0))
+
+
+def _hints(kind: str, dtype: torch.dtype) -> _CHints:
+    a_type = _a_type(dtype)
+    return _CHints(a_type, _B_TYPES[kind], a_type, 0)
 
 # solution_id of the Python surface: any negative value = "library default" as in the reference (fp4.cc:189-191), with two
 # values reserved for the default pick INSIDE the opt-in native-FP4 class (MXFP4 weights only; petit_amd.h)
@@ -192,44 +245,26 @@ def _mul(kind: str, A, B, s, global_scale, size_m, size_n, size_k, solution_id, 
     _check(B.is_contiguous() and B.numel() * B.element_size() == size_n * size_k // 2,
            "B does not hold size_n * size_k packed 4-bit weights")
     _check(global_scale.dtype == torch.float32 and global_scale.numel() >= 1, "global_scale must be float32")
-    _check(activation in _ACTIVATIONS, f"activation must be one of {sorted(k for k in _ACTIVATIONS if k)} or None")
-    act = _ACTIVATIONS[activation]
-    if act:
-        _check(size_n % 32 == 0, f"{activation} needs size_n % 32 == 0 (gate / up halves of whole tiles), got {size_n}")
+    act = _activation(activation, size_n)
     c = torch.empty((size_m, size_n // 2 if act else size_n), dtype=A.dtype, device=A.device)
-    a_type = _lib.CXX_DTYPE_BF16 if A.dtype == torch.bfloat16 else _lib.CXX_DTYPE_FP16
-    b_type = _lib.CXX_DTYPE_FP4_E2M1 if kind == "nv" else _lib.CXX_DTYPE_MXFP4_E2M1
     # require_high_precision: the reference turns it on for arch <= gfx90a when
     # solution_id < 0 (fp4.cc:24-34,189-191); gfx950 -> False.
-    hints = _CHints(a_type, b_type, a_type, 0)
+    hints = _hints(kind, A.dtype)
     # (NVFP4 weights with an MFMA-native image attached -- attach_nvfp4_native -- have opted into the native class: -2 / -3 / -4 then name it)
     sid = _c_solution_id(solution_id, native_ok=(kind == "nv" and int(solution_id) in (-2, -3, -4) and B.data_ptr() in _attached_images))
-    epi = None
-    if bias is not None or act:
-        # fused epilogue (include/petit_amd.h, petit_epilogue): c = round16(act(acc * gs + bias[n]))
-        if bias is not None:
-            _check(bias.is_cuda and bias.device == A.device and bias.dtype == A.dtype and bias.is_contiguous() and
-                   bias.numel() == size_n, "bias must be a contiguous [size_n] tensor of A's dtype on A's device")
-        epi = _lib.Epilogue(bias.data_ptr() if bias is not None else None, act, 0)
-    # Scratch for kernels that need it (cross-workgroup K split, native-FP4 path): ALWAYS per call, from torch's
-    # stream-ordered caching allocator -- safe with several streams and under graph capture, and the same rule as the
+    epi = _epilogue(bias, act, A.device, A.dtype, size_n, "bias must be a contiguous [size_n] tensor of A's dtype on A's device")
+    # Scratch for kernels that need it (cross-workgroup K split, native-FP4 path): ALWAYS per call -- the same rule as the
     # compiled binding (a workspace registered with set_workspace() serves raw C-ABI callers only: it binds to one
     # stream, and a call from a second stream -- e.g. the side stream torch.cuda.graph captures on after an eager
     # warm-up -- would otherwise drop silently to a slower no-scratch kernel).
-    ws = None
-    ws_bytes = _workspace_need(a_type, b_type, size_m, size_n, size_k, sid, act)
-    if ws_bytes:
-        ws = torch.empty(ws_bytes, dtype=torch.uint8, device=A.device)
+    ws_bytes = _workspace_need(hints.a_type, hints.b_type, size_m, size_n, size_k, sid, act)
+    ws = _scratch(ws_bytes, A.device)
     fn = _lib.lib.petit_gemm_fp4_fp16_grid_ws if kind == "nv" else _lib.lib.petit_gemm_mxfp4_fp16_grid_ws
     with torch.cuda.device(A.device):
-        err = fn(_ptr(c), _ptr(A), _ptr(B), _ptr(s), _ptr(global_scale), size_m, size_n, size_k,
-                 C.byref(hints), C.c_uint64(sid), C.byref(epi) if epi is not None else None,
-                 _ptr(ws) if ws is not None else None, C.c_uint64(ws_bytes), _stream(A))
-    if err == _lib.PETIT_ERROR_PROBLEM_SHAPE:
-        raise RuntimeError(f"Incompatible problem shape (m={size_m}, n={size_n}, k={size_k})")
-    if err == _lib.PETIT_ERROR_KERNEL_SHAPE:
-        raise RuntimeError(f"No kernel implementation for solution_id={solution_id}.")
-    _raise_on(err, "mul_%sfp4_a16" % kind)
+        err = fn(_ptr(c), _ptr(A), _ptr(B), _ptr(s), _ptr(global_scale), size_m, size_n, size_k, C.byref(hints), C.c_uint64(sid), epi,
+                 _opt_ptr(ws), C.c_uint64(ws_bytes), _stream(A))
+    if err:
+        _raise_gemm(err, "mul_%sfp4_a16" % kind, solution_id, f"m={size_m}, n={size_n}, k={size_k}")
     return c
 
 
@@ -325,19 +360,16 @@ def resolve_solution(hints: PetitSolutionHints, size_m: int, size_n: int, size_k
     """The concrete kernel id a call with these arguments runs (petit_gemm_resolve_solution): solution_id may be -1, -2 / -3 / -4
     (default pick inside the native class) or an explicit id; 0 when the call would be refused."""
     ch = _c_hints(hints)
-    act = _ACTIVATIONS[activation]
-    epi = _lib.Epilogue(None, act, 0)
     return int(_lib.lib.petit_gemm_resolve_solution(C.byref(ch), size_m, size_n, size_k, C.c_uint64(_c_solution_id(solution_id, native_ok=True)),
-                                                    C.byref(epi) if act else None, C.c_uint64(workspace_bytes)))
+                                                    _query_epilogue(activation), C.c_uint64(workspace_bytes)))
 
 
 def auto_row_split(hints: PetitSolutionHints, size_m: int, size_n: int, size_k: int, activation=None, solution_id: int = -1) -> int:
     """Rows of the first of the TWO launches a default-pick call at this (ragged prefill) M runs as, 0 = one launch (petit_gemm_row_split).  solution_id -2 / -4 / -3:
     the rows a native-class call runs in the class -- the short tail goes through the exact default pick."""
     ch = _c_hints(hints)
-    act = _ACTIVATIONS[activation]
-    epi = _lib.Epilogue(None, act, 0)
-    return int(_lib.lib.petit_gemm_row_split(C.byref(ch), size_m, size_n, size_k, C.c_uint64(_c_solution_id(solution_id, native_ok=True)), C.byref(epi) if act else None))
+    return int(_lib.lib.petit_gemm_row_split(C.byref(ch), size_m, size_n, size_k, C.c_uint64(_c_solution_id(solution_id, native_ok=True)),
+                                             _query_epilogue(activation)))
 
 
 def dequant_packed(B: torch.Tensor, s: torch.Tensor, size_n: int, size_k: int, kind: str = "nvfp4", dtype=torch.float32,
@@ -346,14 +378,13 @@ def dequant_packed(B: torch.Tensor, s: torch.Tensor, size_n: int, size_k: int, k
     counterpart of the reference's test-only DequantPetitFp4 kernels (quantization_utils.cu:542-727)."""
     _check(kind in ("nvfp4", "mxfp4"), "kind must be 'nvfp4' or 'mxfp4'")
     _check(B.is_cuda and s.is_cuda and B.is_contiguous() and s.is_contiguous(), "packed tensors must be contiguous GPU tensors")
-    _check(B.numel() * B.element_size() == size_n * size_k // 2, "B does not hold size_n * size_k packed 4-bit weights")
+    _check_packed(B, None, size_n, size_k, None)
     out_type = {torch.float32: _lib.PETIT_DTYPE_FP32, torch.bfloat16: _lib.CXX_DTYPE_BF16, torch.float16: _lib.CXX_DTYPE_FP16}.get(dtype)
     _check(out_type is not None, "dtype must be float32, bfloat16 or float16")
     out = torch.empty((size_n, size_k), dtype=dtype, device=B.device)
     with torch.cuda.device(B.device):
-        rc = _lib.lib.petit_dequant_packed_weights(_ptr(out), _ptr(B), _ptr(s), float(global_scale), size_n, size_k,
-                                                   _lib.CXX_DTYPE_FP4_E2M1 if kind == "nvfp4" else _lib.CXX_DTYPE_MXFP4_E2M1,
-                                                   out_type, _stream(B))
+        rc = _lib.lib.petit_dequant_packed_weights(_ptr(out), _ptr(B), _ptr(s), float(global_scale), size_n, size_k, _B_TYPES[kind], out_type,
+                                                   _stream(B))
     _raise_on(rc, "dequant_packed")
     return out
 
@@ -404,12 +435,81 @@ def quantize_activations(A: torch.Tensor, fmt: str = "mxfp4") -> QuantizedActiva
     nbytes = int(_lib.lib.petit_quantized_activation_bytes(m, k, _QFORMATS[fmt]))
     qa = torch.empty(nbytes, dtype=torch.uint8, device=A.device)
     with torch.cuda.device(A.device):
-        rc = _lib.lib.petit_quantize_activations(_ptr(qa), _ptr(A), m, k, _lib.CXX_DTYPE_BF16 if A.dtype == torch.bfloat16 else _lib.CXX_DTYPE_FP16,
-                                                 _QFORMATS[fmt], _stream(A))
+        rc = _lib.lib.petit_quantize_activations(_ptr(qa), _ptr(A), m, k, _a_type(A.dtype), _QFORMATS[fmt], _stream(A))
     if rc == _lib.PETIT_ERROR_PROBLEM_SHAPE:
         raise RuntimeError(f"Incompatible problem shape (m={m}, k={k})")
     _raise_on(rc, "quantize_activations")
     return QuantizedActivations(qa, m, k, fmt, A.dtype)
+
+
+def _quantized_format(fmt, text: str) -> int:
+    """'mxfp8' / 'mxfp6' / 'mxfp4' -> the format code of the C ABI, None -> 0; `text` for anything else."""
+    _check(fmt is None or fmt in _QFORMATS, text)
+    return _QFORMATS[fmt] if fmt else 0
+
+
+def _activation_operand(A, size_m: int, size_k: int):
+    """The activation argument of the native class, a 16-bit tensor or QuantizedActivations -> (tensor, 16-bit dtype, a_format).
+    Quantised activations must be the call's [size_m, size_k]; what a 16-bit tensor must be is the caller's rule."""
+    if isinstance(A, QuantizedActivations):
+        _check(A.m == size_m and A.k == size_k, f"quantised activations are [{A.m}, {A.k}], the call says [{size_m}, {size_k}]")
+        return A.data, A.dtype, _QFORMATS[A.fmt]
+    return A, A.dtype, 0
+
+
+def _native_output(rows: int, size_m: int, n_out: int, out_quantized, dtype, dev):
+    """(the tensor the call writes, what the caller returns): 16-bit [rows, n_out], or with out_quantized the bytes of the quantised
+    [size_m, n_out] rows and the QuantizedActivations around them."""
+    if out_quantized:
+        c = torch.empty(int(_lib.lib.petit_quantized_activation_bytes(size_m, n_out, _QFORMATS[out_quantized])), dtype=torch.uint8, device=dev)
+        return c, QuantizedActivations(c, size_m, n_out, out_quantized, dtype)
+    c = torch.empty((rows, n_out), dtype=dtype, device=dev)
+    return c, c
+
+
+def _check_packed(B, s, size_n: int, size_k: int, group, num_experts=None) -> None:
+    """B holds the packed [size_n, size_k] FP4 weights and s one scale per `group` of k (None: s is not looked at) -- with num_experts,
+    of that many matrices back to back."""
+    count, what = (1, "") if num_experts is None else (num_experts, "num_experts * ")
+    _check(B.is_contiguous() and B.numel() * B.element_size() == count * size_n * size_k // 2,
+           f"B does not hold {what}size_n * size_k packed 4-bit weights")
+    if group:
+        _check(s is not None and s.is_cuda and s.is_contiguous() and s.numel() * s.element_size() == count * size_n * size_k // group,
+               f"s does not hold {what}size_n * size_k / {group} scales")
+
+
+def _mul_native(fn, workspace_bytes, name: str, kind: str, A, weights, global_scale, size_m, size_n, size_k, solution_id, bias, activation,
+                out_quantized):
+    """The dense call on the native class behind mul_mxfp4_native / mul_nvfp4_native / mul_nvfp4_native_transient.  weights: (B, s), the
+    packed tensors of `kind` ('mx' / 'nv'), or (image,); fn / workspace_bytes: the C entry point and its scratch query."""
+    a_t, dtype, a_fmt = _activation_operand(A, size_m, size_k)
+    _check(a_fmt or (A.is_cuda and A.is_contiguous() and A.numel() == size_m * size_k and A.dtype in (torch.bfloat16, torch.float16)),
+           "A must be a contiguous [size_m, size_k] bfloat16 / float16 GPU tensor")
+    dev = a_t.device
+    _check(all(t.is_cuda for t in weights) and global_scale.is_cuda, "all tensors must be on GPU")
+    if len(weights) == 2:
+        _check_packed(*weights, size_n, size_k, 32 if kind == "mx" else 16)
+    else:
+        image, = weights
+        _check(image.is_contiguous() and image.dtype == torch.uint8 and
+               image.numel() == int(_lib.lib.petit_nvfp4_native_image_bytes(size_k, size_n)) and image.numel() > 0,
+               "image does not hold the native image of size_n x size_k NVFP4 weights")
+    act = _activation(activation)
+    out_fmt = _quantized_format(out_quantized, "out_quantized must be None, 'mxfp8', 'mxfp6' or 'mxfp4'")
+    _check(not out_fmt or act, "out_quantized needs activation='silu_mul' or 'swiglu_oai'")
+    hints = _hints(kind, dtype)
+    sid = C.c_uint64(_c_solution_id(solution_id, native_ok=True))
+    epi = _epilogue(bias, act, dev, dtype, size_n, "bias must be a contiguous [size_n] tensor of the activation dtype on the same device")
+    na = _lib.NativeArgs(C.sizeof(_lib.NativeArgs), a_fmt, out_fmt, 0)
+    c, result = _native_output(size_m, size_m, size_n // 2 if act else size_n, out_quantized, dtype, dev)
+    ws_bytes = int(workspace_bytes(C.byref(hints), size_m, size_n, size_k, sid, epi, C.byref(na)))
+    ws = _scratch(ws_bytes, dev)
+    with torch.cuda.device(dev):
+        err = fn(_ptr(c), _ptr(a_t), *map(_ptr, weights), _ptr(global_scale), size_m, size_n, size_k, C.byref(hints), sid, epi, C.byref(na),
+                 _opt_ptr(ws), C.c_uint64(ws_bytes), C.c_void_p(torch.cuda.current_stream(dev).cuda_stream))
+    if err:
+        _raise_gemm(err, name, solution_id, f"m={size_m}, n={size_n}, k={size_k}")
+    return result
 
 
 def mul_mxfp4_native(A, B, s, global_scale, size_m, size_n, size_k, solution_id=SOLUTION_AUTO_NATIVE_MXFP4, bias=None, activation=None,
@@ -418,49 +518,8 @@ def mul_mxfp4_native(A, B, s, global_scale, size_m, size_n, size_k, solution_id=
     by the call: two launches) or QuantizedActivations (one launch).  out_quantized 'mxfp8' / 'mxfp6' / 'mxfp4' (with activation='silu_mul'):
     returns QuantizedActivations [size_m, size_n / 2] for the next GEMM instead of a 16-bit tensor.
     solution_id: SOLUTION_AUTO_NATIVE_MXFP8 / _MXFP4 / _MXFP6 (-2 / -3 / -4) or an explicit native kernel id."""
-    pre = isinstance(A, QuantizedActivations)
-    if pre:
-        _check(A.m == size_m and A.k == size_k, f"quantised activations are [{A.m}, {A.k}], the call says [{size_m}, {size_k}]")
-        a_t, dtype, a_fmt, dev = A.data, A.dtype, _QFORMATS[A.fmt], A.data.device
-    else:
-        _check(A.is_cuda and A.is_contiguous() and A.numel() == size_m * size_k and A.dtype in (torch.bfloat16, torch.float16),
-               "A must be a contiguous [size_m, size_k] bfloat16 / float16 GPU tensor")
-        a_t, dtype, a_fmt, dev = A, A.dtype, 0, A.device
-    _check(B.is_cuda and s.is_cuda and global_scale.is_cuda, "all tensors must be on GPU")
-    _check(B.is_contiguous() and B.numel() * B.element_size() == size_n * size_k // 2, "B does not hold size_n * size_k packed 4-bit weights")
-    _check(s.is_contiguous() and s.numel() * s.element_size() == size_n * size_k // 32, "s does not hold size_n * size_k / 32 scales")
-    _check(activation in _ACTIVATIONS, f"activation must be one of {sorted(k for k in _ACTIVATIONS if k)} or None")
-    _check(out_quantized is None or out_quantized in _QFORMATS, "out_quantized must be None, 'mxfp8', 'mxfp6' or 'mxfp4'")
-    act = _ACTIVATIONS[activation]
-    out_fmt = _QFORMATS[out_quantized] if out_quantized else 0
-    _check(not out_fmt or act, "out_quantized needs activation='silu_mul' or 'swiglu_oai'")
-    a_type = _lib.CXX_DTYPE_BF16 if dtype == torch.bfloat16 else _lib.CXX_DTYPE_FP16
-    hints = _CHints(a_type, _lib.CXX_DTYPE_MXFP4_E2M1, a_type, 0)
-    sid = _c_solution_id(solution_id, native_ok=True)
-    epi = None
-    if bias is not None or act:
-        if bias is not None:
-            _check(bias.is_cuda and bias.device == dev and bias.dtype == dtype and bias.is_contiguous() and bias.numel() == size_n,
-                   "bias must be a contiguous [size_n] tensor of the activation dtype on the same device")
-        epi = _lib.Epilogue(bias.data_ptr() if bias is not None else None, act, 0)
-    na = _lib.NativeArgs(C.sizeof(_lib.NativeArgs), a_fmt, out_fmt, 0)
-    epi_p = C.byref(epi) if epi is not None else None
-    if out_fmt:
-        c = torch.empty(int(_lib.lib.petit_quantized_activation_bytes(size_m, size_n // 2, out_fmt)), dtype=torch.uint8, device=dev)
-    else:
-        c = torch.empty((size_m, size_n // 2 if act else size_n), dtype=dtype, device=dev)
-    ws_bytes = int(_lib.lib.petit_gemm_native_workspace_bytes(C.byref(hints), size_m, size_n, size_k, C.c_uint64(sid), epi_p, C.byref(na)))
-    ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev) if ws_bytes else None
-    with torch.cuda.device(dev):
-        err = _lib.lib.petit_gemm_mxfp4_native(_ptr(c), _ptr(a_t), _ptr(B), _ptr(s), _ptr(global_scale), size_m, size_n, size_k, C.byref(hints),
-                                               C.c_uint64(sid), epi_p, C.byref(na), _ptr(ws) if ws is not None else None, C.c_uint64(ws_bytes),
-                                               C.c_void_p(torch.cuda.current_stream(dev).cuda_stream))
-    if err == _lib.PETIT_ERROR_PROBLEM_SHAPE:
-        raise RuntimeError(f"Incompatible problem shape (m={size_m}, n={size_n}, k={size_k})")
-    if err == _lib.PETIT_ERROR_KERNEL_SHAPE:
-        raise RuntimeError(f"No kernel implementation for solution_id={solution_id}.")
-    _raise_on(err, "mul_mxfp4_native")
-    return QuantizedActivations(c, size_m, size_n // 2, out_quantized, dtype) if out_fmt else c
+    return _mul_native(_lib.lib.petit_gemm_mxfp4_native, _lib.lib.petit_gemm_native_workspace_bytes, "mul_mxfp4_native", "mx", A, (B, s),
+                       global_scale, size_m, size_n, size_k, solution_id, bias, activation, out_quantized)
 
 
 # --- NVFP4 weights on the native class (include/petit_amd.h "NVFP4 weights on the native class"; no counterpart in the reference) ----------
@@ -472,8 +531,7 @@ def nvfp4_native_image(B: torch.Tensor, s: torch.Tensor, size_n: int, size_k: in
     """The MFMA-native image ("petit-cdna4-nv6/1": FP6 e2m3 elements + one E8M0 scale per 32 k, 6.25 bits per weight) of NVFP4 weights,
     from the PACKED tensors of repack_nvfp4 / process_nvfp4_scales; one launch, once at load time.  An opaque uint8 tensor."""
     _check(B.is_cuda and s.is_cuda and B.device == s.device, "B and s must be GPU tensors on one device")
-    _check(B.is_contiguous() and B.numel() * B.element_size() == size_n * size_k // 2, "B does not hold size_n * size_k packed 4-bit weights")
-    _check(s.is_contiguous() and s.numel() * s.element_size() == size_n * size_k // 16, "s does not hold size_n * size_k / 16 scales")
+    _check_packed(B, s, size_n, size_k, 16)
     nbytes = int(_lib.lib.petit_nvfp4_native_image_bytes(size_k, size_n))
     if nbytes == 0:
         raise RuntimeError(f"Incompatible problem shape (n={size_n}, k={size_k})")
@@ -504,84 +562,22 @@ def mul_nvfp4_native(A, image: torch.Tensor, global_scale, size_m, size_n, size_
     """NVFP4 weights on the block-scaled MFMA (petit_gemm_nvfp4_native): `image` from nvfp4_native_image; everything else as mul_mxfp4_native
     (A a 16-bit tensor or QuantizedActivations; solution_id -2 / -3 / -4 = MXFP8 / MXFP4 / MXFP6 activations or an explicit native id of the
     NVFP4 family; out_quantized with activation='silu_mul')."""
-    pre = isinstance(A, QuantizedActivations)
-    if pre:
-        _check(A.m == size_m and A.k == size_k, f"quantised activations are [{A.m}, {A.k}], the call says [{size_m}, {size_k}]")
-        a_t, dtype, a_fmt, dev = A.data, A.dtype, _QFORMATS[A.fmt], A.data.device
-    else:
-        _check(A.is_cuda and A.is_contiguous() and A.numel() == size_m * size_k and A.dtype in (torch.bfloat16, torch.float16),
-               "A must be a contiguous [size_m, size_k] bfloat16 / float16 GPU tensor")
-        a_t, dtype, a_fmt, dev = A, A.dtype, 0, A.device
-    _check(image.is_cuda and global_scale.is_cuda, "all tensors must be on GPU")
-    _check(image.is_contiguous() and image.dtype == torch.uint8 and
-           image.numel() == int(_lib.lib.petit_nvfp4_native_image_bytes(size_k, size_n)) and image.numel() > 0,
-           "image does not hold the native image of size_n x size_k NVFP4 weights")
-    _check(activation in _ACTIVATIONS, f"activation must be one of {sorted(k for k in _ACTIVATIONS if k)} or None")
-    _check(out_quantized is None or out_quantized in _QFORMATS, "out_quantized must be None, 'mxfp8', 'mxfp6' or 'mxfp4'")
-    act = _ACTIVATIONS[activation]
-    out_fmt = _QFORMATS[out_quantized] if out_quantized else 0
-    _check(not out_fmt or act, "out_quantized needs activation='silu_mul' or 'swiglu_oai'")
-    a_type = _lib.CXX_DTYPE_BF16 if dtype == torch.bfloat16 else _lib.CXX_DTYPE_FP16
-    hints = _CHints(a_type, _lib.CXX_DTYPE_FP4_E2M1, a_type, 0)
-    sid = _c_solution_id(solution_id, native_ok=True)
-    epi = None
-    if bias is not None or act:
-        if bias is not None:
-            _check(bias.is_cuda and bias.device == dev and bias.dtype == dtype and bias.is_contiguous() and bias.numel() == size_n,
-                   "bias must be a contiguous [size_n] tensor of the activation dtype on the same device")
-        epi = _lib.Epilogue(bias.data_ptr() if bias is not None else None, act, 0)
-    na = _lib.NativeArgs(C.sizeof(_lib.NativeArgs), a_fmt, out_fmt, 0)
-    epi_p = C.byref(epi) if epi is not None else None
-    if out_fmt:
-        c = torch.empty(int(_lib.lib.petit_quantized_activation_bytes(size_m, size_n // 2, out_fmt)), dtype=torch.uint8, device=dev)
-    else:
-        c = torch.empty((size_m, size_n // 2 if act else size_n), dtype=dtype, device=dev)
-    ws_bytes = int(_lib.lib.petit_gemm_native_workspace_bytes(C.byref(hints), size_m, size_n, size_k, C.c_uint64(sid), epi_p, C.byref(na)))
-    ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev) if ws_bytes else None
-    with torch.cuda.device(dev):
-        err = _lib.lib.petit_gemm_nvfp4_native(_ptr(c), _ptr(a_t), _ptr(image), _ptr(global_scale), size_m, size_n, size_k, C.byref(hints),
-                                               C.c_uint64(sid), epi_p, C.byref(na), _ptr(ws) if ws is not None else None, C.c_uint64(ws_bytes),
-                                               C.c_void_p(torch.cuda.current_stream(dev).cuda_stream))
-    if err == _lib.PETIT_ERROR_PROBLEM_SHAPE:
-        raise RuntimeError(f"Incompatible problem shape (m={size_m}, n={size_n}, k={size_k})")
-    if err == _lib.PETIT_ERROR_KERNEL_SHAPE:
-        raise RuntimeError(f"No kernel implementation for solution_id={solution_id}.")
-    _raise_on(err, "mul_nvfp4_native")
-    return QuantizedActivations(c, size_m, size_n // 2, out_quantized, dtype) if out_fmt else c
-
-
-def _nv_transient_args(A, size_m, size_k, activation, out_quantized):
-    """(activation tensor, dtype, a_format, device, act, out_format) of a transient call, with the checks mul_nvfp4_native makes."""
-    if isinstance(A, QuantizedActivations):
-        _check(A.m == size_m and A.k == size_k, f"quantised activations are [{A.m}, {A.k}], the call says [{size_m}, {size_k}]")
-        a_t, dtype, a_fmt, dev = A.data, A.dtype, _QFORMATS[A.fmt], A.data.device
-    else:
-        _check(A.is_cuda and A.is_contiguous() and A.numel() == size_m * size_k and A.dtype in (torch.bfloat16, torch.float16),
-               "A must be a contiguous [size_m, size_k] bfloat16 / float16 GPU tensor")
-        a_t, dtype, a_fmt, dev = A, A.dtype, 0, A.device
-    _check(activation in _ACTIVATIONS, f"activation must be one of {sorted(k for k in _ACTIVATIONS if k)} or None")
-    _check(out_quantized is None or out_quantized in _QFORMATS, "out_quantized must be None, 'mxfp8', 'mxfp6' or 'mxfp4'")
-    act = _ACTIVATIONS[activation]
-    out_fmt = _QFORMATS[out_quantized] if out_quantized else 0
-    _check(not out_fmt or act, "out_quantized needs activation='silu_mul' or 'swiglu_oai'")
-    return a_t, dtype, a_fmt, dev, act, out_fmt
+    return _mul_native(_lib.lib.petit_gemm_nvfp4_native, _lib.lib.petit_gemm_native_workspace_bytes, "mul_nvfp4_native", "nv", A, (image,),
+                       global_scale, size_m, size_n, size_k, solution_id, bias, activation, out_quantized)
 
 
 def nvfp4_native_transient_workspace_bytes(size_m, size_n, size_k, solution_id=SOLUTION_AUTO_NATIVE_MXFP8, dtype=torch.bfloat16, activation=None,
                                            a_format=None, out_quantized=None) -> int:
     """Workspace bytes of mul_nvfp4_native_transient (petit_gemm_nvfp4_native_transient_workspace_bytes): the image rounded up to 256 bytes, then the
     native call's own scratch; 0 when the call would be refused.  a_format: the format of pre-quantised activations (None: 16-bit)."""
-    _check(activation in _ACTIVATIONS, f"activation must be one of {sorted(k for k in _ACTIVATIONS if k)} or None")
-    _check(a_format is None or a_format in _QFORMATS, "a_format must be None, 'mxfp8', 'mxfp6' or 'mxfp4'")
-    _check(out_quantized is None or out_quantized in _QFORMATS, "out_quantized must be None, 'mxfp8', 'mxfp6' or 'mxfp4'")
-    a_type = _lib.CXX_DTYPE_BF16 if dtype == torch.bfloat16 else _lib.CXX_DTYPE_FP16
-    hints = _CHints(a_type, _lib.CXX_DTYPE_FP4_E2M1, a_type, 0)
-    act = _ACTIVATIONS[activation]
-    epi = _lib.Epilogue(None, act, 0)
-    na = _lib.NativeArgs(C.sizeof(_lib.NativeArgs), _QFORMATS[a_format] if a_format else 0, _QFORMATS[out_quantized] if out_quantized else 0, 0)
+    _activation(activation)
+    a_fmt = _quantized_format(a_format, "a_format must be None, 'mxfp8', 'mxfp6' or 'mxfp4'")
+    out_fmt = _quantized_format(out_quantized, "out_quantized must be None, 'mxfp8', 'mxfp6' or 'mxfp4'")
+    hints = _hints("nv", dtype)
+    na = _lib.NativeArgs(C.sizeof(_lib.NativeArgs), a_fmt, out_fmt, 0)
     return int(_lib.lib.petit_gemm_nvfp4_native_transient_workspace_bytes(C.byref(hints), size_m, size_n, size_k,
                                                                           C.c_uint64(_c_solution_id(solution_id, native_ok=True)),
-                                                                          C.byref(epi) if act else None, C.byref(na)))
+                                                                          _query_epilogue(activation), C.byref(na)))
 
 
 def mul_nvfp4_native_transient(A, B, s, global_scale, size_m, size_n, size_k, solution_id=SOLUTION_AUTO_NATIVE_MXFP8, bias=None, activation=None,
@@ -590,38 +586,9 @@ def mul_nvfp4_native_transient(A, B, s, global_scale, size_m, size_n, size_k, so
     mul_nvfp4_a16 takes; the call builds the image into a workspace it takes from torch's caching allocator, then runs the native call on it.
     Bit for bit mul_nvfp4_a16(..., solution_id) with the image attached (16-bit A and result) / mul_nvfp4_native on the image (QuantizedActivations
     A, out_quantized).  Everything else as mul_nvfp4_native."""
-    a_t, dtype, a_fmt, dev, act, out_fmt = _nv_transient_args(A, size_m, size_k, activation, out_quantized)
-    _check(B.is_cuda and s.is_cuda and global_scale.is_cuda, "all tensors must be on GPU")
-    _check(B.is_contiguous() and B.numel() * B.element_size() == size_n * size_k // 2, "B does not hold size_n * size_k packed 4-bit weights")
-    _check(s.is_contiguous() and s.numel() * s.element_size() == size_n * size_k // 16, "s does not hold size_n * size_k / 16 scales")
-    a_type = _lib.CXX_DTYPE_BF16 if dtype == torch.bfloat16 else _lib.CXX_DTYPE_FP16
-    hints = _CHints(a_type, _lib.CXX_DTYPE_FP4_E2M1, a_type, 0)
-    sid = _c_solution_id(solution_id, native_ok=True)
-    epi = None
-    if bias is not None or act:
-        if bias is not None:
-            _check(bias.is_cuda and bias.device == dev and bias.dtype == dtype and bias.is_contiguous() and bias.numel() == size_n,
-                   "bias must be a contiguous [size_n] tensor of the activation dtype on the same device")
-        epi = _lib.Epilogue(bias.data_ptr() if bias is not None else None, act, 0)
-    na = _lib.NativeArgs(C.sizeof(_lib.NativeArgs), a_fmt, out_fmt, 0)
-    epi_p = C.byref(epi) if epi is not None else None
-    if out_fmt:
-        c = torch.empty(int(_lib.lib.petit_quantized_activation_bytes(size_m, size_n // 2, out_fmt)), dtype=torch.uint8, device=dev)
-    else:
-        c = torch.empty((size_m, size_n // 2 if act else size_n), dtype=dtype, device=dev)
-    ws_bytes = int(_lib.lib.petit_gemm_nvfp4_native_transient_workspace_bytes(C.byref(hints), size_m, size_n, size_k, C.c_uint64(sid), epi_p,
-                                                                              C.byref(na)))
-    ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev) if ws_bytes else None
-    with torch.cuda.device(dev):
-        err = _lib.lib.petit_gemm_nvfp4_native_transient(_ptr(c), _ptr(a_t), _ptr(B), _ptr(s), _ptr(global_scale), size_m, size_n, size_k,
-                                                         C.byref(hints), C.c_uint64(sid), epi_p, C.byref(na), _ptr(ws) if ws is not None else None,
-                                                         C.c_uint64(ws_bytes), C.c_void_p(torch.cuda.current_stream(dev).cuda_stream))
-    if err == _lib.PETIT_ERROR_PROBLEM_SHAPE:
-        raise RuntimeError(f"Incompatible problem shape (m={size_m}, n={size_n}, k={size_k})")
-    if err == _lib.PETIT_ERROR_KERNEL_SHAPE:
-        raise RuntimeError(f"No kernel implementation for solution_id={solution_id}.")
-    _raise_on(err, "mul_nvfp4_native_transient")
-    return QuantizedActivations(c, size_m, size_n // 2, out_quantized, dtype) if out_fmt else c
+    return _mul_native(_lib.lib.petit_gemm_nvfp4_native_transient, _lib.lib.petit_gemm_nvfp4_native_transient_workspace_bytes,
+                       "mul_nvfp4_native_transient", "nv", A, (B, s), global_scale, size_m, size_n, size_k, solution_id, bias, activation,
+                       out_quantized)
 
 
 # --- grouped launch (include/petit_amd.h "Grouped launch"; no counterpart in the reference) ---------------------------------
@@ -641,33 +608,49 @@ def mul_fp4_a16_grouped(kind: str, A: torch.Tensor, members, size_m: int, size_k
         B, s, gs, n = mem[:4]
         bias = mem[4] if len(mem) > 4 else None
         _check(B.is_cuda and s.is_cuda and gs.is_cuda and B.device == A.device, "all tensors must be on A's GPU")
-        _check(B.is_contiguous() and B.numel() * B.element_size() == n * size_k // 2, "B does not hold size_n * size_k packed 4-bit weights")
-        _check(s.is_contiguous() and s.numel() * s.element_size() == n * size_k // group, f"s does not hold size_n * size_k / {group} scales")
+        _check_packed(B, s, n, size_k, group)
         _check(gs.dtype == torch.float32 and gs.numel() >= 1, "global_scale must be float32")
         if bias is not None:
             _check(bias.is_cuda and bias.dtype == A.dtype and bias.is_contiguous() and bias.numel() == n, "bias must be a contiguous [size_n] tensor of A's dtype")
         c = torch.empty((size_m, n), dtype=A.dtype, device=A.device)
         outs.append(c)
         arr[i] = _lib.GroupMember(c.data_ptr(), B.data_ptr(), s.data_ptr(), gs.data_ptr(), bias.data_ptr() if bias is not None else None, n, 0)
-    a_type = _lib.CXX_DTYPE_BF16 if A.dtype == torch.bfloat16 else _lib.CXX_DTYPE_FP16
-    b_type = _lib.CXX_DTYPE_FP4_E2M1 if kind == "nvfp4" else _lib.CXX_DTYPE_MXFP4_E2M1
-    hints = _CHints(a_type, b_type, a_type, 0)
+    hints = _hints(kind, A.dtype)
     with torch.cuda.device(A.device):
         err = _lib.lib.petit_gemm_fp4_fp16_grouped(arr, len(members), _ptr(A), size_m, size_k, C.byref(hints), C.c_uint64(_c_solution_id(solution_id)),
                                                    _stream(A))
-    if err == _lib.PETIT_ERROR_PROBLEM_SHAPE:
-        raise RuntimeError(f"Incompatible problem shape (m={size_m}, k={size_k}, n={[mem[3] for mem in members]})")
-    if err == _lib.PETIT_ERROR_KERNEL_SHAPE:
-        raise RuntimeError(f"No kernel implementation for solution_id={solution_id}.")
-    _raise_on(err, "mul_fp4_a16_grouped")
+    if err:
+        _raise_gemm(err, "mul_fp4_a16_grouped", solution_id, f"m={size_m}, k={size_k}, n={[mem[3] for mem in members]}")
     return outs
 
 
 # --- routed-expert (MoE) launch (include/petit_amd.h "Routed-expert (MoE) launch"; no counterpart in the reference) ------------------------
 
-def _moe_hints(kind: str, A: torch.Tensor) -> _CHints:
-    a_type = _lib.CXX_DTYPE_BF16 if A.dtype == torch.bfloat16 else _lib.CXX_DTYPE_FP16
-    return _CHints(a_type, _lib.CXX_DTYPE_FP4_E2M1 if kind == "nv" else _lib.CXX_DTYPE_MXFP4_E2M1, a_type, 0)
+def _check_expert_operands(kind: str, a_t, B, s, global_scales, expert_offsets, size_m, size_n, size_k, num_experts, row_indices=(),
+                           native: bool = False) -> int:
+    """The rules the routed-expert launches share, on everything but the activations' shape: the expert count (returned as an int), the
+    stacked weights -- packed B / s of `kind` ('nv' / 'mx'), or on the native class with kind 'nv' the experts' images --, one global scale
+    per expert, the E + 1 offsets, and int32 [size_m] row indices on the activations' device.  a_t: the activation tensor."""
+    E = int(num_experts)
+    _check(1 <= E <= _lib.PETIT_MOE_MAX_EXPERTS, f"num_experts must be in 1..{_lib.PETIT_MOE_MAX_EXPERTS}, got {E}")
+    if native:   # (s is None with images, and otherwise answers for itself below)
+        _check(a_t.is_cuda and B.is_cuda and global_scales.is_cuda and expert_offsets.is_cuda and B.is_contiguous(), "all tensors must be on GPU")
+    else:
+        _check(a_t.is_cuda and B.is_cuda and s.is_cuda and global_scales.is_cuda and expert_offsets.is_cuda, "all tensors must be on GPU")
+    if native and kind == "nv":
+        per = int(_lib.lib.petit_nvfp4_native_image_bytes(size_k, size_n))
+        _check(B.dtype == torch.uint8 and per > 0 and B.numel() == E * per, "images do not hold num_experts native images (nvfp4_native_images)")
+    else:
+        _check_packed(B, s, size_n, size_k, 32 if kind == "mx" else 16, E)
+    _check(global_scales.dtype == torch.float32 and global_scales.is_contiguous() and global_scales.numel() == E,
+           "global_scales must be a contiguous float32 [num_experts] tensor")
+    _check(expert_offsets.dtype == torch.int32 and expert_offsets.is_contiguous() and expert_offsets.numel() == E + 1,
+           "expert_offsets must be a contiguous int32 [num_experts + 1] tensor")
+    for idx in row_indices:
+        if idx is not None:
+            _check(idx.is_cuda and idx.device == a_t.device and idx.dtype == torch.int32 and idx.is_contiguous() and idx.numel() == size_m,
+                   "row indices must be contiguous int32 [size_m] tensors on A's device")
+    return E
 
 
 def _mul_moe(kind: str, A, B, s, global_scales, expert_offsets, size_m, size_n, size_k, num_experts, solution_id=-1, bias=None,
@@ -677,38 +660,18 @@ def _mul_moe(kind: str, A, B, s, global_scales, expert_offsets, size_m, size_n, 
     global_scales: float32 [E]; expert_offsets: int32 [E + 1] on A's device, never read by the host (no sync: capturable)."""
     if A.dtype != torch.bfloat16 and A.dtype != torch.float16:
         raise RuntimeError("A must be bfloat16 or float16.")
-    group = 16 if kind == "nv" else 32
-    E = int(num_experts)
-    _check(1 <= E <= _lib.PETIT_MOE_MAX_EXPERTS, f"num_experts must be in 1..{_lib.PETIT_MOE_MAX_EXPERTS}, got {E}")
-    _check(A.is_cuda and B.is_cuda and s.is_cuda and global_scales.is_cuda and expert_offsets.is_cuda, "all tensors must be on GPU")
+    E = _check_expert_operands(kind, A, B, s, global_scales, expert_offsets, size_m, size_n, size_k, num_experts)
     _check(A.is_contiguous() and A.numel() == size_m * size_k, "A must be a contiguous [size_m, size_k] tensor")
-    _check(B.is_contiguous() and B.numel() * B.element_size() == E * size_n * size_k // 2,
-           "B does not hold num_experts * size_n * size_k packed 4-bit weights")
-    _check(s.is_contiguous() and s.numel() * s.element_size() == E * size_n * size_k // group,
-           f"s does not hold num_experts * size_n * size_k / {group} scales")
-    _check(global_scales.dtype == torch.float32 and global_scales.is_contiguous() and global_scales.numel() == E,
-           "global_scales must be a contiguous float32 [num_experts] tensor")
-    _check(expert_offsets.dtype == torch.int32 and expert_offsets.is_contiguous() and expert_offsets.numel() == E + 1,
-           "expert_offsets must be a contiguous int32 [num_experts + 1] tensor")
-    _check(activation in _ACTIVATIONS, f"activation must be one of {sorted(k for k in _ACTIVATIONS if k)} or None")
-    act = _ACTIVATIONS[activation]
-    if act:
-        _check(size_n % 32 == 0, f"{activation} needs size_n % 32 == 0 (gate / up halves of whole tiles), got {size_n}")
-    if bias is not None:
-        _check(bias.is_cuda and bias.device == A.device and bias.dtype == A.dtype and bias.is_contiguous() and bias.numel() == E * size_n,
-               "bias must be a contiguous [num_experts, size_n] tensor of A's dtype on A's device")
+    act = _activation(activation, size_n)
+    epi = _epilogue(bias, act, A.device, A.dtype, E * size_n, "bias must be a contiguous [num_experts, size_n] tensor of A's dtype on A's device")
     c = torch.empty((size_m, size_n // 2 if act else size_n), dtype=A.dtype, device=A.device)
-    hints = _moe_hints(kind, A)
-    epi = _lib.Epilogue(bias.data_ptr() if bias is not None else None, act, 0) if (bias is not None or act) else None
+    hints = _hints(kind, A.dtype)
     with torch.cuda.device(A.device):
         err = _lib.lib.petit_gemm_fp4_fp16_moe(_ptr(c), _ptr(A), _ptr(B), _ptr(s), _ptr(global_scales), _ptr(expert_offsets), E, size_m, size_n,
                                                size_k, C.byref(hints), C.c_uint64(_c_solution_id(solution_id)),
-                                               C.byref(epi) if epi is not None else None, _stream(A))
-    if err == _lib.PETIT_ERROR_PROBLEM_SHAPE:
-        raise RuntimeError(f"Incompatible problem shape (m={size_m}, n={size_n}, k={size_k}, num_experts={E})")
-    if err == _lib.PETIT_ERROR_KERNEL_SHAPE:
-        raise RuntimeError(f"No kernel implementation for solution_id={solution_id}.")
-    _raise_on(err, "mul_%sfp4_a16_moe" % kind)
+                                               epi, _stream(A))
+    if err:
+        _raise_gemm(err, "mul_%sfp4_a16_moe" % kind, solution_id, f"m={size_m}, n={size_n}, k={size_k}, num_experts={E}")
     return c
 
 
@@ -729,30 +692,10 @@ def _mul_moe_indexed(kind: str, A, B, s, global_scales, expert_offsets, size_m, 
     matrix reads zeros / stores nothing.  out: write into this tensor (rows no index names stay untouched) instead of a new one."""
     if A.dtype != torch.bfloat16 and A.dtype != torch.float16:
         raise RuntimeError("A must be bfloat16 or float16.")
-    group = 16 if kind == "nv" else 32
-    E = int(num_experts)
-    _check(1 <= E <= _lib.PETIT_MOE_MAX_EXPERTS, f"num_experts must be in 1..{_lib.PETIT_MOE_MAX_EXPERTS}, got {E}")
-    _check(A.is_cuda and B.is_cuda and s.is_cuda and global_scales.is_cuda and expert_offsets.is_cuda, "all tensors must be on GPU")
+    E = _check_expert_operands(kind, A, B, s, global_scales, expert_offsets, size_m, size_n, size_k, num_experts, (a_row_index, c_row_index))
     _check(A.is_contiguous() and size_k > 0 and A.numel() % size_k == 0, "A must be a contiguous [a_rows, size_k] tensor")
-    _check(B.is_contiguous() and B.numel() * B.element_size() == E * size_n * size_k // 2,
-           "B does not hold num_experts * size_n * size_k packed 4-bit weights")
-    _check(s.is_contiguous() and s.numel() * s.element_size() == E * size_n * size_k // group,
-           f"s does not hold num_experts * size_n * size_k / {group} scales")
-    _check(global_scales.dtype == torch.float32 and global_scales.is_contiguous() and global_scales.numel() == E,
-           "global_scales must be a contiguous float32 [num_experts] tensor")
-    _check(expert_offsets.dtype == torch.int32 and expert_offsets.is_contiguous() and expert_offsets.numel() == E + 1,
-           "expert_offsets must be a contiguous int32 [num_experts + 1] tensor")
-    for idx in (a_row_index, c_row_index):
-        if idx is not None:
-            _check(idx.is_cuda and idx.device == A.device and idx.dtype == torch.int32 and idx.is_contiguous() and idx.numel() == size_m,
-                   "row indices must be contiguous int32 [size_m] tensors on A's device")
-    _check(activation in _ACTIVATIONS, f"activation must be one of {sorted(k for k in _ACTIVATIONS if k)} or None")
-    act = _ACTIVATIONS[activation]
-    if act:
-        _check(size_n % 32 == 0, f"{activation} needs size_n % 32 == 0 (gate / up halves of whole tiles), got {size_n}")
-    if bias is not None:
-        _check(bias.is_cuda and bias.device == A.device and bias.dtype == A.dtype and bias.is_contiguous() and bias.numel() == E * size_n,
-               "bias must be a contiguous [num_experts, size_n] tensor of A's dtype on A's device")
+    act = _activation(activation, size_n)
+    epi = _epilogue(bias, act, A.device, A.dtype, E * size_n, "bias must be a contiguous [num_experts, size_n] tensor of A's dtype on A's device")
     a_rows = A.numel() // size_k
     n_out = size_n // 2 if act else size_n
     if out is not None:
@@ -763,18 +706,14 @@ def _mul_moe_indexed(kind: str, A, B, s, global_scales, expert_offsets, size_m, 
     else:
         c_rows = size_m if c_rows is None or c_rows < 0 else int(c_rows)
         out = torch.empty((c_rows, n_out), dtype=A.dtype, device=A.device)
-    hints = _moe_hints(kind, A)
-    epi = _lib.Epilogue(bias.data_ptr() if bias is not None else None, act, 0) if (bias is not None or act) else None
+    hints = _hints(kind, A.dtype)
     with torch.cuda.device(A.device):
         err = _lib.lib.petit_gemm_fp4_fp16_moe_ex(_ptr(out), _ptr(A), _ptr(B), _ptr(s), _ptr(global_scales), _ptr(expert_offsets), E, size_m,
-                                                  size_n, size_k, _ptr(a_row_index) if a_row_index is not None else None, a_rows,
-                                                  _ptr(c_row_index) if c_row_index is not None else None, c_rows, C.byref(hints),
-                                                  C.c_uint64(_c_solution_id(solution_id)), C.byref(epi) if epi is not None else None, _stream(A))
-    if err == _lib.PETIT_ERROR_PROBLEM_SHAPE:
-        raise RuntimeError(f"Incompatible problem shape (m={size_m}, n={size_n}, k={size_k}, num_experts={E}, a_rows={a_rows}, c_rows={c_rows})")
-    if err == _lib.PETIT_ERROR_KERNEL_SHAPE:
-        raise RuntimeError(f"No kernel implementation for solution_id={solution_id}.")
-    _raise_on(err, "mul_%sfp4_a16_moe_indexed" % kind)
+                                                  size_n, size_k, _opt_ptr(a_row_index), a_rows, _opt_ptr(c_row_index), c_rows, C.byref(hints),
+                                                  C.c_uint64(_c_solution_id(solution_id)), epi, _stream(A))
+    if err:
+        _raise_gemm(err, "mul_%sfp4_a16_moe_indexed" % kind, solution_id,
+                    f"m={size_m}, n={size_n}, k={size_k}, num_experts={E}, a_rows={a_rows}, c_rows={c_rows}")
     return out
 
 
@@ -809,10 +748,10 @@ def moe_align_device(topk_ids: torch.Tensor, num_experts: int):
     token_index = torch.empty(T * topk, dtype=torch.int32, device=dev)
     offsets = torch.empty(int(num_experts) + 1, dtype=torch.int32, device=dev)
     ws_bytes = int(_lib.lib.petit_moe_align_workspace_bytes(T, topk, int(num_experts)))
-    ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev) if ws_bytes else None
+    ws = _scratch(ws_bytes, dev)
     with torch.cuda.device(dev):
         rc = _lib.lib.petit_moe_align(_ptr(topk_ids), int(topk_ids.dtype == torch.int64), T, topk, int(num_experts), _ptr(offsets),
-                                      _ptr(sorted_pos), _ptr(token_index), _ptr(ws) if ws is not None else None, _stream(topk_ids))
+                                      _ptr(sorted_pos), _ptr(token_index), _opt_ptr(ws), _stream(topk_ids))
     if rc == _lib.PETIT_ERROR_PROBLEM_SHAPE:
         raise RuntimeError(f"Incompatible routing shape (num_tokens={T}, topk={topk}, num_experts={num_experts})")
     _raise_on(rc, "moe_align_device")
@@ -833,10 +772,9 @@ def moe_combine(slot_out: torch.Tensor, topk_weights: torch.Tensor, topk_ids: to
     n = slot_out.size(1)
     _check(n % 8 == 0, f"n must be a multiple of 8, got {n}")
     out = torch.empty((T, n), dtype=slot_out.dtype, device=slot_out.device)
-    dtype = _lib.CXX_DTYPE_BF16 if slot_out.dtype == torch.bfloat16 else _lib.CXX_DTYPE_FP16
     with torch.cuda.device(slot_out.device):
         rc = _lib.lib.petit_moe_combine(_ptr(out), _ptr(slot_out), _ptr(topk_weights), _ptr(topk_ids), int(topk_ids.dtype == torch.int64), T, topk,
-                                        n, int(num_experts), dtype, _stream(slot_out))
+                                        n, int(num_experts), _a_type(slot_out.dtype), _stream(slot_out))
     if rc == _lib.PETIT_ERROR_PROBLEM_SHAPE:
         raise RuntimeError(f"Incompatible routing shape (num_tokens={T}, topk={topk}, n={n}, num_experts={num_experts})")
     _raise_on(rc, "moe_combine")
@@ -886,7 +824,7 @@ def moe_route(router_logits: torch.Tensor, topk: int, scoring: str = "softmax", 
     desc = _route_desc(scoring, renormalize, bias, n_group, topk_group, routed_scaling_factor)
     with torch.cuda.device(dev):
         rc = _lib.lib.petit_moe_route(_ptr(router_logits), _LOGIT_DTYPES[router_logits.dtype], T, E, int(topk), C.byref(desc), _ptr(ids), _ptr(w),
-                                      _ptr(keys) if keys is not None else None, _stream(router_logits))
+                                      _opt_ptr(keys), _stream(router_logits))
     _route_shape_error(rc, T, E, topk, n_group, topk_group)
     _raise_on(rc, "moe_route")
     return (w, ids, keys) if return_keys else (w, ids)
@@ -906,12 +844,12 @@ def moe_route_align(router_logits: torch.Tensor, topk: int, scoring: str = "soft
     token_index = torch.empty(T * topk, dtype=torch.int32, device=dev)
     offsets = torch.empty(E + 1, dtype=torch.int32, device=dev)
     ws_bytes = int(_lib.lib.petit_moe_route_align_workspace_bytes(T, topk, E))
-    ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev) if ws_bytes else None
+    ws = _scratch(ws_bytes, dev)
     desc = _route_desc(scoring, renormalize, bias, n_group, topk_group, routed_scaling_factor)
     with torch.cuda.device(dev):
         rc = _lib.lib.petit_moe_route_align(_ptr(router_logits), _LOGIT_DTYPES[router_logits.dtype], T, E, topk, C.byref(desc), _ptr(ids), _ptr(w),
-                                            _ptr(keys) if keys is not None else None, _ptr(offsets), _ptr(sorted_pos), _ptr(token_index),
-                                            _ptr(ws) if ws is not None else None, _stream(router_logits))
+                                            _opt_ptr(keys), _ptr(offsets), _ptr(sorted_pos), _ptr(token_index), _opt_ptr(ws),
+                                            _stream(router_logits))
     _route_shape_error(rc, T, E, topk, n_group, topk_group)
     _raise_on(rc, "moe_route_align")
     out = (w, ids, sorted_pos, offsets, token_index)
@@ -922,10 +860,8 @@ def moe_resolve_solution(hints: PetitSolutionHints, num_experts: int, size_m: in
                          activation=None) -> int:
     """The kernel id a MoE call with these arguments runs (petit_gemm_moe_resolve_solution, the launcher's own pick); 0 when it would be refused."""
     ch = _c_hints(hints)
-    act = _ACTIVATIONS[activation]
-    epi = _lib.Epilogue(None, act, 0)
     return int(_lib.lib.petit_gemm_moe_resolve_solution(C.byref(ch), int(num_experts), size_m, size_n, size_k,
-                                                        C.c_uint64(_c_solution_id(solution_id)), C.byref(epi) if act else None))
+                                                        C.c_uint64(_c_solution_id(solution_id)), _query_epilogue(activation)))
 
 
 # --- native-class MoE (include/petit_amd.h "Native-class MoE launch"; no counterpart in the reference) ------------------------------------
@@ -947,8 +883,7 @@ def quantize_activation_rows(A: torch.Tensor, fmt: str = "mxfp8", row_index: tor
     nbytes = int(_lib.lib.petit_quantized_activation_bytes(m, k, _QFORMATS[fmt]))
     qa = torch.empty(nbytes, dtype=torch.uint8, device=A.device)
     with torch.cuda.device(A.device):
-        rc = _lib.lib.petit_quantize_activations_rows(_ptr(qa), _ptr(A), _ptr(row_index) if row_index is not None else None, a_rows, m, k,
-                                                      _lib.CXX_DTYPE_BF16 if A.dtype == torch.bfloat16 else _lib.CXX_DTYPE_FP16, _QFORMATS[fmt],
+        rc = _lib.lib.petit_quantize_activations_rows(_ptr(qa), _ptr(A), _opt_ptr(row_index), a_rows, m, k, _a_type(A.dtype), _QFORMATS[fmt],
                                                       _stream(A))
     if rc == _lib.PETIT_ERROR_PROBLEM_SHAPE:
         raise RuntimeError(f"Incompatible problem shape (m={m}, k={k}, a_rows={a_rows})")
@@ -964,8 +899,7 @@ def nvfp4_native_images(B: torch.Tensor, s: torch.Tensor, num_experts: int, size
     wb = size_n * size_k // 2
     sb = size_n * size_k // 16
     _check(B.is_cuda and s.is_cuda and B.is_contiguous() and s.is_contiguous(), "B and s must be contiguous GPU tensors")
-    _check(B.numel() * B.element_size() == E * wb, "B does not hold num_experts * size_n * size_k packed 4-bit weights")
-    _check(s.numel() * s.element_size() == E * sb, "s does not hold num_experts * size_n * size_k / 16 scales")
+    _check_packed(B, s, size_n, size_k, 16, E)
     per = int(_lib.lib.petit_nvfp4_native_image_bytes(size_k, size_n))
     _check(per > 0, f"no native image for size_n={size_n}, size_k={size_k}")
     out = torch.empty(E * per, dtype=torch.uint8, device=B.device)
@@ -983,69 +917,38 @@ def _mul_native_moe(kind: str, A, B, s, global_scales, expert_offsets, size_m, s
     quantised by the call: two launches) or QuantizedActivations of the size_m grouped rows (one launch).  Output: 16-bit [c_rows, n_out], row
     c_row_index[r] for grouped row r (None: the identity), or with out_quantized (activation='silu_mul') QuantizedActivations of the grouped
     [size_m, size_n / 2] rows for the next launch."""
-    pre = isinstance(A, QuantizedActivations)
-    E = int(num_experts)
-    _check(1 <= E <= _lib.PETIT_MOE_MAX_EXPERTS, f"num_experts must be in 1..{_lib.PETIT_MOE_MAX_EXPERTS}, got {E}")
-    if pre:
-        _check(A.m == size_m and A.k == size_k, f"quantised activations are [{A.m}, {A.k}], the call says [{size_m}, {size_k}]")
+    a_t, dtype, a_fmt = _activation_operand(A, size_m, size_k)
+    if a_fmt:
         _check(a_row_index is None, "quantised activations are grouped rows already: a_row_index must be None")
-        a_t, dtype, a_fmt, dev, a_rows = A.data, A.dtype, _QFORMATS[A.fmt], A.data.device, size_m
+        a_rows = size_m
     else:
         _check(A.is_cuda and A.is_contiguous() and A.dtype in (torch.bfloat16, torch.float16) and size_k > 0 and A.numel() % size_k == 0,
                "A must be a contiguous [a_rows, size_k] bfloat16 / float16 GPU tensor")
-        a_t, dtype, a_fmt, dev, a_rows = A, A.dtype, 0, A.device, A.numel() // size_k
-    _check(B.is_cuda and global_scales.is_cuda and expert_offsets.is_cuda and B.is_contiguous(), "all tensors must be on GPU")
-    if kind == "mx":
-        _check(B.numel() * B.element_size() == E * size_n * size_k // 2, "B does not hold num_experts * size_n * size_k packed 4-bit weights")
-        _check(s is not None and s.is_cuda and s.is_contiguous() and s.numel() * s.element_size() == E * size_n * size_k // 32,
-               "s does not hold num_experts * size_n * size_k / 32 scales")
-    else:
-        per = int(_lib.lib.petit_nvfp4_native_image_bytes(size_k, size_n))
-        _check(B.dtype == torch.uint8 and per > 0 and B.numel() == E * per, "images do not hold num_experts native images (nvfp4_native_images)")
-    _check(global_scales.dtype == torch.float32 and global_scales.is_contiguous() and global_scales.numel() == E,
-           "global_scales must be a contiguous float32 [num_experts] tensor")
-    _check(expert_offsets.dtype == torch.int32 and expert_offsets.is_contiguous() and expert_offsets.numel() == E + 1,
-           "expert_offsets must be a contiguous int32 [num_experts + 1] tensor")
-    for idx in (a_row_index, c_row_index):
-        if idx is not None:
-            _check(idx.is_cuda and idx.device == dev and idx.dtype == torch.int32 and idx.is_contiguous() and idx.numel() == size_m,
-                   "row indices must be contiguous int32 [size_m] tensors on A's device")
-    _check(activation in _ACTIVATIONS, f"activation must be one of {sorted(k for k in _ACTIVATIONS if k)} or None")
-    _check(out_quantized is None or out_quantized in _QFORMATS, "out_quantized must be None, 'mxfp8', 'mxfp6' or 'mxfp4'")
-    act = _ACTIVATIONS[activation]
-    out_fmt = _QFORMATS[out_quantized] if out_quantized else 0
+        a_rows = A.numel() // size_k
+    dev = a_t.device
+    E = _check_expert_operands(kind, a_t, B, s, global_scales, expert_offsets, size_m, size_n, size_k, num_experts, (a_row_index, c_row_index),
+                               native=True)
+    act = _activation(activation)
+    out_fmt = _quantized_format(out_quantized, "out_quantized must be None, 'mxfp8', 'mxfp6' or 'mxfp4'")
     _check(not out_fmt or (act and c_row_index is None), "out_quantized needs activation='silu_mul' or 'swiglu_oai' and no c_row_index")
-    if bias is not None:
-        _check(bias.is_cuda and bias.device == dev and bias.dtype == dtype and bias.is_contiguous() and bias.numel() == E * size_n,
-               "bias must be a contiguous [num_experts, size_n] tensor of the activation dtype on the same device")
-    a_type = _lib.CXX_DTYPE_BF16 if dtype == torch.bfloat16 else _lib.CXX_DTYPE_FP16
-    hints = _CHints(a_type, _lib.CXX_DTYPE_FP4_E2M1 if kind == "nv" else _lib.CXX_DTYPE_MXFP4_E2M1, a_type, 0)
-    sid = _c_solution_id(solution_id, native_ok=True)
-    epi = _lib.Epilogue(bias.data_ptr() if bias is not None else None, act, 0) if (bias is not None or act) else None
-    epi_p = C.byref(epi) if epi is not None else None
+    epi = _epilogue(bias, act, dev, dtype, E * size_n,
+                    "bias must be a contiguous [num_experts, size_n] tensor of the activation dtype on the same device")
+    hints = _hints(kind, dtype)
+    sid = C.c_uint64(_c_solution_id(solution_id, native_ok=True))
     na = _lib.NativeArgs(C.sizeof(_lib.NativeArgs), a_fmt, out_fmt, 0)
-    n_out = size_n // 2 if act else size_n
-    if out_fmt:
-        c_rows = size_m
-        c = torch.empty(int(_lib.lib.petit_quantized_activation_bytes(size_m, n_out, out_fmt)), dtype=torch.uint8, device=dev)
-    else:
-        c_rows = size_m if c_rows is None or c_rows < 0 else int(c_rows)
-        c = torch.empty((c_rows, n_out), dtype=dtype, device=dev)
-    ws_bytes = int(_lib.lib.petit_gemm_native_moe_workspace_bytes(C.byref(hints), E, size_m, size_n, size_k, C.c_uint64(sid), epi_p, C.byref(na)))
-    ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev) if ws_bytes else None
+    c_rows = size_m if out_fmt or c_rows is None or c_rows < 0 else int(c_rows)
+    c, result = _native_output(c_rows, size_m, size_n // 2 if act else size_n, out_quantized, dtype, dev)
+    ws_bytes = int(_lib.lib.petit_gemm_native_moe_workspace_bytes(C.byref(hints), E, size_m, size_n, size_k, sid, epi, C.byref(na)))
+    ws = _scratch(ws_bytes, dev)
     with torch.cuda.device(dev):
-        err = _lib.lib.petit_gemm_native_moe(_ptr(c), _ptr(a_t), _ptr(B), _ptr(s) if s is not None else None, _ptr(global_scales),
-                                             _ptr(expert_offsets), E, size_m, size_n, size_k,
-                                             _ptr(a_row_index) if a_row_index is not None else None, a_rows,
-                                             _ptr(c_row_index) if c_row_index is not None else None, c_rows, C.byref(hints), C.c_uint64(sid),
-                                             epi_p, C.byref(na), _ptr(ws) if ws is not None else None, C.c_uint64(ws_bytes),
+        err = _lib.lib.petit_gemm_native_moe(_ptr(c), _ptr(a_t), _ptr(B), _opt_ptr(s), _ptr(global_scales), _ptr(expert_offsets), E, size_m,
+                                             size_n, size_k, _opt_ptr(a_row_index), a_rows, _opt_ptr(c_row_index), c_rows, C.byref(hints), sid,
+                                             epi, C.byref(na), _opt_ptr(ws), C.c_uint64(ws_bytes),
                                              C.c_void_p(torch.cuda.current_stream(dev).cuda_stream))
-    if err == _lib.PETIT_ERROR_PROBLEM_SHAPE:
-        raise RuntimeError(f"Incompatible problem shape (m={size_m}, n={size_n}, k={size_k}, num_experts={E}, a_rows={a_rows}, c_rows={c_rows})")
-    if err == _lib.PETIT_ERROR_KERNEL_SHAPE:
-        raise RuntimeError(f"No kernel implementation for solution_id={solution_id}.")
-    _raise_on(err, "mul_%sfp4_native_moe" % kind)
-    return QuantizedActivations(c, size_m, n_out, out_quantized, dtype) if out_fmt else c
+    if err:
+        _raise_gemm(err, "mul_%sfp4_native_moe" % kind, solution_id,
+                    f"m={size_m}, n={size_n}, k={size_k}, num_experts={E}, a_rows={a_rows}, c_rows={c_rows}")
+    return result
 
 
 def mul_mxfp4_native_moe(A, B, s, global_scales, expert_offsets, size_m, size_n, size_k, num_experts, a_row_index=None, c_row_index=None,
@@ -1064,9 +967,7 @@ def native_moe_resolve_solution(hints: PetitSolutionHints, num_experts: int, siz
                                 solution_id: int = SOLUTION_AUTO_NATIVE_MXFP8, activation=None, a_format: str = None, out_quantized: str = None) -> int:
     """The kernel id petit_gemm_native_moe runs for these arguments (the launcher's own pick); 0 when the call would be refused."""
     ch = _c_hints(hints)
-    act = _ACTIVATIONS[activation]
-    epi = _lib.Epilogue(None, act, 0)
     na = _lib.NativeArgs(C.sizeof(_lib.NativeArgs), _QFORMATS[a_format] if a_format else 0, _QFORMATS[out_quantized] if out_quantized else 0, 0)
     return int(_lib.lib.petit_gemm_native_moe_resolve_solution(C.byref(ch), int(num_experts), size_m, size_n, size_k,
-                                                               C.c_uint64(_c_solution_id(solution_id, native_ok=True)), C.byref(epi) if act else None,
+                                                               C.c_uint64(_c_solution_id(solution_id, native_ok=True)), _query_epilogue(activation),
                                                                C.byref(na)))
