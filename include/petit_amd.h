@@ -453,6 +453,48 @@ uint64_t petit_gemm_nvfp4_native_transient_workspace_bytes(const petit_solution_
                                                            const petit_epilogue *epilogue, const petit_native_args *native);
 
 /*
+ * Weight quantiser (no counterpart in the reference, whose callers arrive with FP4 checkpoints): 16-bit weights -> the PACKED tensors and the
+ * global scales the GEMMs read, in one pass over the weights (NVFP4 without a supplied scale: two), for a stack that loads a bf16 / fp16
+ * checkpoint or receives fresh 16-bit weights while it serves.  No row-major FP4 intermediate, no repack launch.
+ *
+ *   w           [num_experts][n][k], a_type PETIT_DTYPE_BF16 / _FP16, contiguous, 16-byte aligned; num_experts = 1 is a plain linear.
+ *               n % 16 == 0, k % 256 == 0 (what the scale repack asks).  Every expert is quantised on its own.
+ *   b_type      PETIT_DTYPE_FP4_E2M1 (NVFP4) or PETIT_DTYPE_MXFP4_E2M1
+ *   out_b       what petit_repack_nvfp4_weights makes of the row-major FP4 of the stacked [num_experts n, k] matrix (n k / 2 bytes per expert, expert
+ *               e at e times that); out_scales what petit_repack_nvfp4_scales (n k / 16 bytes per expert) / petit_repack_mxfp4_scales (n k / 32)
+ *               makes of its scales; both 16-byte aligned.  out_gs: float32 [num_experts], the global_scale(s) of the GEMM entry points.
+ *   gs_in       NVFP4 only: null, or float32 [num_experts] positive finite global scales of the caller (calibrated, or shared between tensors);
+ *               then there is no amax pass.  May be out_gs.  Ignored for MXFP4.
+ *   workspace   petit_quantize_weights_workspace_bytes(b_type, num_experts, gs_in != NULL) bytes of device scratch, 4-byte aligned (0: may be
+ *               null): the per-expert maxima, zeroed on the stream by the call.
+ *
+ * The rule.  mid = {0.25, 0.75, 1.25, 1.75, 2.5, 3.5, 5}, the midpoints of the e2m1 magnitudes {0, 0.5, 1, 1.5, 2, 3, 4, 6}.
+ *   NVFP4 (the recipe of the nvidia FP4 checkpoints, every step named):
+ *     global scale  amax_e = max |w_e|;  gs_e = amax_e / 2688.0f, ONE correctly rounded f32 division (2688 = 6 x 448);  gs_e = 1.0f when
+ *                   amax_e == 0.  With gs_in: gs_e = gs_in[e].
+ *     block scale   per 16 consecutive k of a row: byte = e4m3fn_rne( f32( f32(blk_amax / 6.0f) / gs_e ) ), saturating at 448 (0x7e).
+ *     codes         s = the decoded byte; t_i = mid_i * s * gs_e EXACTLY (3 + 4 + 24 significant bits: an f64 product).  The magnitude code is the
+ *                   number of t_i < |w|; at |w| == t_i the even one of i, i + 1; the sign bit is set only with a non-zero magnitude code
+ *                   (there is no -0).  s == 0 gives code 0 for the whole block.
+ *   MXFP4 (OCP MX):
+ *     scale         per 32 consecutive k: e = the smallest integer with 6 * 2^e >= blk_amax, clipped to [-126, 127]; byte = e + 127 (a zero
+ *                   block: 1).  No element clips.
+ *     codes         round to nearest even on the e2m1 grid of w / 2^e (the count above with t_i = mid_i * 2^e), saturating, no -0.
+ *     global scale  gs_e = 1.0f.
+ *   Non-finite weights give unspecified values, never a fault.
+ *
+ * petit_quantize_weights_host is the CPU twin on host memory: same arguments without scratch and stream, the same bytes out (offline conversion).
+ * Errors, all before any launch: PETIT_ERROR_BAD_ARGUMENT for an a_type / b_type outside the above, null or misaligned pointers, a workspace
+ * that is too small; PETIT_ERROR_PROBLEM_SHAPE for n % 16, k % 256 or num_experts * n >= 2^32; PETIT_ERROR_KERNEL_SHAPE for a call that needs
+ * scratch and has none.  num_experts, n or k == 0 returns PETIT_OK.  No host sync, no allocation: capturable; a replay quantises what w holds then.
+ */
+uint64_t petit_quantize_weights_workspace_bytes(int b_type, unsigned num_experts, int gs_supplied);
+int petit_quantize_weights(const void *w, int a_type, int b_type, unsigned num_experts, unsigned n, unsigned k, const float *gs_in, void *out_b,
+                           void *out_scales, float *out_gs, void *workspace, uint64_t workspace_bytes, void *stream);
+int petit_quantize_weights_host(const void *w, int a_type, int b_type, unsigned num_experts, unsigned n, unsigned k, const float *gs_in,
+                                void *out_b, void *out_scales, float *out_gs);
+
+/*
  * Grouped launch (no counterpart in the reference): up to PETIT_GROUP_MAX weight matrices that share the activation rows --
  * q / k / v (or their tensor-parallel shards) kept as separate tensors, gate and up, the experts a token routes to -- in ONE
  * kernel launch: c_i[m][n_i] = a[m][k] . dequant(b_i)[n_i][k]^T * (*global_scale_i) (+ bias_i).  At decode batch sizes a

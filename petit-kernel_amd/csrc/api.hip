@@ -130,6 +130,20 @@ int petit_nvfp4_native_image_dequant_host(float *out, const void *image, unsigne
         return kErrBadArgument;
     return nv6_image_dequant_host(out, image, out_chan, in_chan);
 }
+// the weight quantiser (quantize_weights.hip makes every check: the device form and its host twin refuse the same calls)
+uint64_t petit_quantize_weights_workspace_bytes(int b_type, unsigned num_experts, int gs_supplied) {
+    return quantize_weights_workspace_bytes(canonical_b_type(b_type), num_experts, gs_supplied != 0);
+}
+int petit_quantize_weights(const void *w, int a_type, int b_type, unsigned num_experts, unsigned n, unsigned k, const float *gs_in, void *out_b,
+                           void *out_scales, float *out_gs, void *workspace, uint64_t workspace_bytes, void *stream) {
+    return quantize_weights(w, a_type, canonical_b_type(b_type), num_experts, n, k, gs_in, out_b, out_scales, out_gs, workspace, workspace_bytes,
+                            (hipStream_t)stream);
+}
+int petit_quantize_weights_host(const void *w, int a_type, int b_type, unsigned num_experts, unsigned n, unsigned k, const float *gs_in,
+                                void *out_b, void *out_scales, float *out_gs) {
+    return quantize_weights_host(w, a_type, canonical_b_type(b_type), num_experts, n, k, gs_in, out_b, out_scales, out_gs);
+}
+
 int petit_nvfp4_native_attach(const void *b, const void *image) {
     if (!b || ((uintptr_t)image & 255))
         return kErrBadArgument;

@@ -169,6 +169,13 @@ int convert_reference_mxscales_host(void *out, const void *in, unsigned k, unsig
 int nv6_image(void *image, const void *pw, const void *ps, unsigned n, unsigned k, hipStream_t stream);
 int nv6_image_host(void *image, const void *pw, const void *ps, unsigned n, unsigned k);
 int nv6_image_dequant_host(float *out, const void *image, unsigned n, unsigned k);
+// quantize_weights.hip: 16-bit weights [E][n][k] -> the packed tensors and one global scale per expert (include/petit_amd.h "Weight quantiser");
+// host twin, bit-identical
+uint64_t quantize_weights_workspace_bytes(int b_type, unsigned num_experts, bool gs_supplied);
+int quantize_weights(const void *w, int a_type, int b_type, unsigned num_experts, unsigned n, unsigned k, const float *gs_in, void *out_b,
+                     void *out_scales, float *out_gs, void *workspace, uint64_t workspace_bytes, hipStream_t stream);
+int quantize_weights_host(const void *w, int a_type, int b_type, unsigned num_experts, unsigned n, unsigned k, const float *gs_in, void *out_b,
+                          void *out_scales, float *out_gs);
 // dequant.hip: dense expansion of packed weights (debug aid); out_kind 0 f32, 1 bf16, 2 fp16
 int dequant_packed(void *out, const void *w, const void *s, float gs, unsigned n, unsigned k, int b_type, int out_kind, hipStream_t stream);
 

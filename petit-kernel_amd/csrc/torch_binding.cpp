@@ -153,6 +153,55 @@ at::Tensor process_scales(const at::Tensor &scales, int64_t size_n, int64_t size
 at::Tensor process_nvfp4_scales(const at::Tensor &s, int64_t n, int64_t k) { return process_scales(s, n, k, false); }
 at::Tensor process_mxfp4_scales(const at::Tensor &s, int64_t n, int64_t k) { return process_scales(s, n, k, true); }
 
+// weight quantiser (petit_quantize_weights); the same checks and texts as petit_kernel/ops.py _quantize_operands.  b_type: kCxxFp4 / kCxxMxFp4.
+// quantize_shapes states the rules once, for the real op and its Meta twin, and makes the three outputs.
+struct QuantizeShapes {
+    int64_t E, n, k;
+    at::Tensor b, s, gs;
+};
+QuantizeShapes quantize_shapes(const at::Tensor &w, int64_t b_type, const std::optional<at::Tensor> &global_scale, bool real) {
+    TORCH_CHECK(b_type == kCxxFp4 || b_type == kCxxMxFp4, "b_type must be 3 (NVFP4) or 7 (MXFP4)");
+    const bool mx = b_type == kCxxMxFp4;
+    TORCH_CHECK(w.scalar_type() == at::kBFloat16 || w.scalar_type() == at::kHalf, "w must be bfloat16 or float16.");
+    TORCH_CHECK(w.dim() == 2 || w.dim() == 3, "w must be [size_n, size_k] or [num_experts, size_n, size_k]");
+    if (real) {
+        TORCH_CHECK(w.is_cuda(), "w is not on GPU");
+        TORCH_CHECK(w.is_contiguous(), "w is not contiguous");
+    }
+    const int64_t E = w.dim() == 3 ? w.size(0) : 1, n = w.size(-2), k = w.size(-1);
+    TORCH_CHECK(k % (2 * kLayoutM) == 0, "size_k = ", k, " is not divisible by tile_k_size = ", 2 * kLayoutM);
+    TORCH_CHECK(n % kLayoutN == 0, "size_n = ", n, " is not divisible by tile_n_size = ", kLayoutN);
+    TORCH_CHECK(!mx || E * n % 32 == 0, "num_experts * size_n = ", E * n, " is not divisible by the MX scale tile (32)");
+    if (global_scale.has_value())
+        TORCH_CHECK(global_scale->device() == w.device() && global_scale->scalar_type() == at::kFloat && global_scale->is_contiguous() &&
+                        global_scale->dim() == 1 && global_scale->numel() == E,
+                    "global_scale must be a contiguous float32 [num_experts] tensor on w's device");
+    QuantizeShapes q{E, n, k, {}, {}, {}};
+    q.b = at::empty({E * n / kLayoutN, k * kLayoutN / kPack}, w.options().dtype(at::kInt));
+    q.s = mx ? at::empty({E * n / 32, k}, w.options().dtype(at::kByte)) : at::empty({E * n, k / 16}, w.options().dtype(at::kFloat8_e4m3fn));
+    q.gs = at::empty({E}, w.options().dtype(at::kFloat));
+    return q;
+}
+std::tuple<at::Tensor, at::Tensor, at::Tensor> quantize_weights(const at::Tensor &w, int64_t b_type, const std::optional<at::Tensor> &global_scale) {
+    const QuantizeShapes q = quantize_shapes(w, b_type, global_scale, true);
+    const c10::hip::HIPGuardMasqueradingAsCUDA guard(w.device());
+    const bool supplied = b_type == kCxxFp4 && global_scale.has_value();
+    const uint64_t ws_bytes = petit_quantize_weights_workspace_bytes((int)b_type, (unsigned)q.E, supplied);
+    at::Tensor ws;
+    if (ws_bytes)
+        ws = at::empty({(int64_t)ws_bytes}, w.options().dtype(at::kByte));
+    const int rc = petit_quantize_weights(w.data_ptr(), a_type_of(w.scalar_type()), (int)b_type, (unsigned)q.E, (unsigned)q.n, (unsigned)q.k,
+                                          supplied ? (const float *)global_scale->data_ptr() : nullptr, q.b.data_ptr(), q.s.data_ptr(),
+                                          (float *)q.gs.data_ptr(), ws_bytes ? ws.data_ptr() : nullptr, ws_bytes, stream_of(w));
+    TORCH_CHECK(rc != PETIT_ERROR_PROBLEM_SHAPE, "Incompatible problem shape (num_experts=", q.E, ", n=", q.n, ", k=", q.k, ")");
+    TORCH_CHECK(rc == PETIT_OK, b_type == kCxxMxFp4 ? "quantize_mxfp4: " : "quantize_nvfp4: ", petit_error_string(rc));
+    return {q.b, q.s, q.gs};
+}
+std::tuple<at::Tensor, at::Tensor, at::Tensor> quantize_weights_meta(const at::Tensor &w, int64_t b_type, const std::optional<at::Tensor> &global_scale) {
+    const QuantizeShapes q = quantize_shapes(w, b_type, global_scale, false);
+    return {q.b, q.s, q.gs};
+}
+
 at::Tensor mul_a16(bool mx, const at::Tensor &A, const at::Tensor &B, const at::Tensor &s, const at::Tensor &global_scale, int64_t size_m,
                    int64_t size_n, int64_t size_k, int64_t solution_id, const std::optional<at::Tensor> &bias, int64_t activation) {
     // (check order as in the reference's MulNvFp4A16 / MulMxFp4A16, fp4.cc:163-260: the scale / weight tensor contracts first)
@@ -553,6 +602,7 @@ TORCH_LIBRARY(petit_kernel, m) {
     m.def("repack_nvfp4(Tensor b_q_weight, int size_n, int size_k) -> Tensor");
     m.def("process_nvfp4_scales(Tensor scales, int size_n, int size_k) -> Tensor");
     m.def("process_mxfp4_scales(Tensor scales, int size_n, int size_k) -> Tensor");
+    m.def("quantize_weights(Tensor w, int b_type, Tensor? global_scale=None) -> (Tensor, Tensor, Tensor)");
     m.def("mul_nvfp4_a16(Tensor A, Tensor B, Tensor s, Tensor global_scale, int size_m, int size_n, int size_k, int solution_id, "
           "Tensor? bias=None, int activation=0) -> Tensor");
     m.def("mul_mxfp4_a16(Tensor A, Tensor B, Tensor s, Tensor global_scale, int size_m, int size_n, int size_k, int solution_id, "
@@ -591,6 +641,7 @@ TORCH_LIBRARY(petit_kernel, m) {
     m.impl("repack_nvfp4", &repack_nvfp4);                      \
     m.impl("process_nvfp4_scales", &process_nvfp4_scales);      \
     m.impl("process_mxfp4_scales", &process_mxfp4_scales);      \
+    m.impl("quantize_weights", &quantize_weights);              \
     m.impl("mul_nvfp4_a16", &mul_nvfp4_a16);                    \
     m.impl("mul_mxfp4_a16", &mul_mxfp4_a16);                    \
     m.impl("mul_mxfp4_a16_f16range", &mul_mxfp4_a16);          \
@@ -613,6 +664,7 @@ TORCH_LIBRARY_IMPL(petit_kernel, Meta, m) {
     m.impl("repack_nvfp4", &repack_nvfp4_meta);
     m.impl("process_nvfp4_scales", &process_nvfp4_scales_meta);
     m.impl("process_mxfp4_scales", &process_mxfp4_scales_meta);
+    m.impl("quantize_weights", &quantize_weights_meta);
     m.impl("mul_nvfp4_a16", &mul_a16_meta);
     m.impl("mul_mxfp4_a16", &mul_a16_meta);
     m.impl("mul_mxfp4_a16_f16range", &mul_a16_meta);

@@ -61,6 +61,18 @@ def process_mxfp4_scales(scales: torch.Tensor, size_n: int, size_k: int) -> torc
     return _impl.process_mxfp4_scales(scales, size_n, size_k)
 
 
+def quantize_nvfp4(w: torch.Tensor, global_scale: torch.Tensor = None):
+    # 16-bit weights [N, K] or [E, N, K] -> (b, s, global_scale) on the device (include/petit_amd.h "Weight quantiser"): the packed tensors
+    # repack_nvfp4 / process_nvfp4_scales return for the stacked [E * N, K] tensor and float32 [E] global scales (amax / 2688 per expert, or the
+    # caller's), for mul_nvfp4_a16, the MoE launches, fp4_moe* and nvfp4_native_image(s).  Host twin: offline.quantize_nvfp4_cpu
+    return _impl.quantize_nvfp4(w, global_scale)
+
+
+def quantize_mxfp4(w: torch.Tensor):
+    # the same for MXFP4 (one e8m0 scale per 32 k, global_scale = 1); num_experts * N must be a multiple of 32, as process_mxfp4_scales asks
+    return _impl.quantize_mxfp4(w)
+
+
 def mxfp4_scales_in_fp16_range(raw_scales: torch.Tensor) -> bool:
     """A diagnostic, not an input of any call: True when every e8m0 byte of the RAW (unprocessed) MXFP4 scale tensor lies in 114..140, i.e. when
     fp16 activations run the single-MFMA body in every wave (a wave that meets a byte outside that range finishes its K range in the exact
@@ -212,6 +224,8 @@ __all__ = [
     "repack_mxfp4",
     "process_nvfp4_scales",
     "process_mxfp4_scales",
+    "quantize_nvfp4",
+    "quantize_mxfp4",
     "mul_nvfp4_a16",
     "mul_mxfp4_a16",
     "get_fp4_solutions",

@@ -129,6 +129,9 @@ _SIGNATURES = {
     "petit_nvfp4_native_image": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint, C.c_uint, C.c_void_p]),
     "petit_nvfp4_native_image_host": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint, C.c_uint]),
     "petit_nvfp4_native_image_dequant_host": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint, C.c_uint]),
+    "petit_quantize_weights_workspace_bytes": (C.c_uint64, [C.c_int, C.c_uint, C.c_int]),
+    "petit_quantize_weights": (C.c_int, [C.c_void_p, C.c_int, C.c_int] + [C.c_uint] * 3 + [C.c_void_p] * 5 + [C.c_uint64, C.c_void_p]),
+    "petit_quantize_weights_host": (C.c_int, [C.c_void_p, C.c_int, C.c_int] + [C.c_uint] * 3 + [C.c_void_p] * 4),
     "petit_nvfp4_native_attach": (C.c_int, [C.c_void_p, C.c_void_p]),
     "petit_nvfp4_native_attached": (C.c_void_p, [C.c_void_p]),
     "petit_gemm_nvfp4_native": (C.c_int, [C.c_void_p] * 4 + [C.c_uint] * 3 + [C.POINTER(SolutionHints), C.c_uint64, C.POINTER(Epilogue),

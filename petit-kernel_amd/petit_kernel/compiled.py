@@ -74,6 +74,14 @@ def process_mxfp4_scales(scales, size_n, size_k):
     return torch.ops.petit_kernel.process_mxfp4_scales(scales, size_n, size_k)
 
 
+def quantize_nvfp4(w, global_scale=None):
+    return torch.ops.petit_kernel.quantize_weights(w, _lib.CXX_DTYPE_FP4_E2M1, global_scale)
+
+
+def quantize_mxfp4(w):
+    return torch.ops.petit_kernel.quantize_weights(w, _lib.CXX_DTYPE_MXFP4_E2M1, None)
+
+
 def mul_nvfp4_a16(A, B, s, global_scale, size_m, size_n, size_k, solution_id, bias=None, activation=None):
     return torch.ops.petit_kernel.mul_nvfp4_a16(A, B, s, global_scale, size_m, size_n, size_k, _sid(solution_id), bias, _act(activation))
 

@@ -12,7 +12,7 @@ This is format tooling, not a CPU fallback: only the GPU kernels consume the pac
 import torch
 
 from . import _lib
-from .ops import _LAYOUT_M, _LAYOUT_N, _PACK, _check, _raise_on
+from .ops import _B_TYPES, _LAYOUT_M, _LAYOUT_N, _PACK, _a_type, _check, _quantize_operands, _quantize_outputs, _raise_on, _raise_quantize
 
 
 def _cpu(t: torch.Tensor, name: str) -> None:
@@ -62,6 +62,27 @@ def process_mxfp4_scales_cpu(scales: torch.Tensor, size_n: int, size_k: int) -> 
     _raise_on(_lib.lib.petit_repack_mxfp4_scales_host(out.data_ptr(), scales.data_ptr(), size_k, size_n),
               "process_mxfp4_scales_cpu")
     return out
+
+
+# --- 16-bit weights -> the packed tensors, offline (include/petit_amd.h "Weight quantiser") ------------------------------------------------------
+
+def _quantize_weights_cpu(kind: str, w: torch.Tensor, global_scale=None):
+    E, n, k = _quantize_operands(kind, w, global_scale, on_gpu=False)
+    b, s, gs = _quantize_outputs(kind, E, n, k, w.device)
+    rc = _lib.lib.petit_quantize_weights_host(w.data_ptr(), _a_type(w.dtype), _B_TYPES[kind], E, n, k,
+                                              None if global_scale is None else global_scale.data_ptr(), b.data_ptr(), s.data_ptr(), gs.data_ptr())
+    _raise_quantize(rc, "quantize_%sfp4_cpu" % kind, E, n, k)
+    return b, s, gs
+
+
+def quantize_nvfp4_cpu(w: torch.Tensor, global_scale: torch.Tensor = None):
+    """CPU twin of petit_kernel.quantize_nvfp4: bf16 / fp16 [N, K] or [E, N, K] -> (b, s, global_scale), bit-identical to the device's."""
+    return _quantize_weights_cpu("nv", w, global_scale)
+
+
+def quantize_mxfp4_cpu(w: torch.Tensor):
+    """CPU twin of petit_kernel.quantize_mxfp4."""
+    return _quantize_weights_cpu("mx", w)
 
 
 # --- tensors already packed by the REFERENCE wheel -> this build's layout (include/petit_amd.h, petit_convert_reference_*) -----

@@ -164,6 +164,68 @@ def process_mxfp4_scales(scales: torch.Tensor, size_n: int, size_k: int) -> torc
     return out
 
 
+# --- weight quantiser (include/petit_amd.h "Weight quantiser"; no counterpart in the reference) -----------------------------------------
+
+def _quantize_operands(kind: str, w: torch.Tensor, global_scale, on_gpu: bool = True):
+    """The rules quantize_nvfp4 / quantize_mxfp4 and their CPU twins (offline.py) share -> (num_experts, size_n, size_k).  w: 16-bit
+    [size_n, size_k] or [num_experts, size_n, size_k]; global_scale (NVFP4 only): None or float32 [num_experts] beside w."""
+    _check(w.dtype in (torch.bfloat16, torch.float16), "w must be bfloat16 or float16.")
+    _check(w.dim() in (2, 3), "w must be [size_n, size_k] or [num_experts, size_n, size_k]")
+    _check(w.is_cuda == on_gpu, "w is not on GPU" if on_gpu else "w must be a CPU tensor (use petit_kernel.quantize_* for GPU tensors)")
+    _check(w.is_contiguous(), "w is not contiguous")
+    num_experts, (size_n, size_k) = (w.size(0) if w.dim() == 3 else 1), w.shape[-2:]
+    _check(size_k % (2 * _LAYOUT_M) == 0, f"size_k = {size_k} is not divisible by tile_k_size = {2 * _LAYOUT_M}")
+    _check(size_n % _LAYOUT_N == 0, f"size_n = {size_n} is not divisible by tile_n_size = {_LAYOUT_N}")
+    _check(kind != "mx" or num_experts * size_n % 32 == 0,
+           f"num_experts * size_n = {num_experts * size_n} is not divisible by the MX scale tile (32)")
+    if global_scale is not None:
+        _check(global_scale.device == w.device and global_scale.dtype == torch.float32 and global_scale.is_contiguous() and
+               global_scale.dim() == 1 and global_scale.numel() == num_experts,
+               "global_scale must be a contiguous float32 [num_experts] tensor on w's device")
+    return num_experts, size_n, size_k
+
+
+def _quantize_outputs(kind: str, num_experts: int, size_n: int, size_k: int, dev):
+    """(b, s, global_scale) as repack_* / process_*_scales shape them for the stacked [num_experts * size_n, size_k] tensor."""
+    rows = num_experts * size_n
+    b = torch.empty((rows // _LAYOUT_N, size_k * _LAYOUT_N // _PACK), dtype=torch.int32, device=dev)
+    if kind == "mx":
+        s = torch.empty((rows // 32, size_k), dtype=torch.uint8, device=dev)
+    else:
+        s = torch.empty((rows, size_k // 16), dtype=torch.float8_e4m3fn, device=dev)
+    return b, s, torch.empty(num_experts, dtype=torch.float32, device=dev)
+
+
+def _raise_quantize(rc: int, name: str, num_experts: int, size_n: int, size_k: int) -> None:
+    if rc == _lib.PETIT_ERROR_PROBLEM_SHAPE:
+        raise RuntimeError(f"Incompatible problem shape (num_experts={num_experts}, n={size_n}, k={size_k})")
+    _raise_on(rc, name)
+
+
+def _quantize_weights(kind: str, w: torch.Tensor, global_scale=None):
+    E, n, k = _quantize_operands(kind, w, global_scale)
+    b, s, gs = _quantize_outputs(kind, E, n, k, w.device)
+    ws_bytes = int(_lib.lib.petit_quantize_weights_workspace_bytes(_B_TYPES[kind], E, int(global_scale is not None)))
+    ws = _scratch(ws_bytes, w.device)
+    with torch.cuda.device(w.device):
+        rc = _lib.lib.petit_quantize_weights(_ptr(w), _a_type(w.dtype), _B_TYPES[kind], E, n, k, _opt_ptr(global_scale), _ptr(b), _ptr(s), _ptr(gs),
+                                             _opt_ptr(ws), C.c_uint64(ws_bytes), _stream(w))
+    _raise_quantize(rc, "quantize_%sfp4" % kind, E, n, k)
+    return b, s, gs
+
+
+def quantize_nvfp4(w: torch.Tensor, global_scale: torch.Tensor = None):
+    """16-bit weights [N, K] or [E, N, K] -> (b, s, global_scale): the packed NVFP4 tensors repack_nvfp4 / process_nvfp4_scales return for the
+    stacked [E * N, K] tensor and float32 [E] global scales, straight into mul_nvfp4_a16 / mul_nvfp4_a16_moe* / fp4_moe* / nvfp4_native_image(s).
+    global_scale: None (amax / 2688 per expert) or the caller's float32 [E]."""
+    return _quantize_weights("nv", w, global_scale)
+
+
+def quantize_mxfp4(w: torch.Tensor):
+    """The same for MXFP4 (OCP MX: one e8m0 scale per 32 k, global_scale = 1): (b, s, global_scale) as repack_mxfp4 / process_mxfp4_scales shape them."""
+    return _quantize_weights("mx", w)
+
+
 _ACTIVATIONS = {None: 0, "none": 0, "silu_mul": 1, "swiglu_oai": 2}   # PETIT_ACTIVATION_* (include/petit_amd.h)
 _B_TYPES = {"nv": _lib.CXX_DTYPE_FP4_E2M1, "nvfp4": _lib.CXX_DTYPE_FP4_E2M1, "mx": _lib.CXX_DTYPE_MXFP4_E2M1, "mxfp4": _lib.CXX_DTYPE_MXFP4_E2M1}
 _ACTIVATION_RULE = f"activation must be one of {sorted(k for k in _ACTIVATIONS if k)} or None"
