@@ -176,7 +176,11 @@ uint64_t petit_gemm_default_solution(const petit_solution_hints *hints,
  * scratch as the pick wants" (what the Python layers provide): possibly an id with a K split (bits 60-63 > 1), which a caller
  * WITHOUT scratch cannot run -- such a caller (petit_gemm_fp4_fp16_grid / _ex with no registered workspace) gets the kernel this
  * function names for workspace_bytes = 0.  A call that runs as bulk + tail (petit_gemm_row_split): the kernel of the problem as a
- * whole -- resolve (rows) and (m - rows) for the two launches.  epilogue may be NULL. */
+ * whole -- resolve (rows) and (m - rows) for the two launches.  epilogue may be NULL.
+ * A K too short for the split an id or a table row names runs as ONE slice (no reduce pass); the id keeps its split nibble.  With a gated
+ * activation that is then the kernel's own epilogue's job: an explicit id whose kernel cannot apply it resolves to 0, and a default pick
+ * names the kernel re-picked for it (split nibble 1) -- the one launched.  (Before the plan knew the launch geometry this query named
+ * the table row's kernel there, which was not the one launched.) */
 uint64_t petit_gemm_resolve_solution(const petit_solution_hints *hints, unsigned m, unsigned n, unsigned k, uint64_t solution_id,
                                      const petit_epilogue *epilogue, uint64_t workspace_bytes);
 /* Rows are independent, so a default-pick call (PETIT_SOLUTION_AUTO) at a prefill M whose tile grid ends a little past a whole number
@@ -308,7 +312,8 @@ uint64_t petit_gemm_workspace_bytes(const petit_solution_hints *hints, unsigned 
 /* The same with the epilogue of the call taken into account: PETIT_SOLUTION_AUTO resolves differently under
  * PETIT_ACTIVATION_SILU_MUL (unsplit, only kernels that hold a gate / up tile pair per wave qualify; with a cross-workgroup K
  * split any kernel does -- the slabs hold the plain [m][n] product and the reduce pass applies SiLU-mul); PETIT_ACTIVATION_SWIGLU_OAI
- * resolves exactly as SILU_MUL does. */
+ * resolves exactly as SILU_MUL does.  0 also for an explicit id that petit_gemm_resolve_solution refuses because its K split gives one
+ * slice and its kernel cannot apply the gated activation itself (the launch step made that refusal before; this query named slab bytes). */
 uint64_t petit_gemm_workspace_bytes_ex(const petit_solution_hints *hints, unsigned m, unsigned n, unsigned k,
                                        uint64_t solution_id, const petit_epilogue *epilogue);
 int petit_set_workspace(void *device_ptr, uint64_t bytes);

@@ -81,11 +81,6 @@ uint64_t petit_gemm_workspace_bytes_ex(const petit_solution_hints *hints, unsign
     return p.rc == kOk ? p.need : 0;
 }
 
-static bool native_args_ok(const petit_native_args *na) {
-    return !na || (na->struct_bytes == sizeof(petit_native_args) && na->reserved == 0 &&
-                   (na->a_format == 0 || na->a_format == 8 || na->a_format == 6 || na->a_format == 4) &&
-                   (na->out_format == 0 || na->out_format == 8 || na->out_format == 6 || na->out_format == 4));
-}
 static NativeIo native_io(const petit_native_args *na, const void *image = nullptr) {
     return NativeIo{na ? (unsigned)na->a_format : 0u, na ? (unsigned)na->out_format : 0u, image};
 }

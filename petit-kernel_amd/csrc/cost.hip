@@ -27,9 +27,8 @@ namespace petit_amd {
 unsigned guarded_splitk(const SolutionEntry &e, unsigned splitk, unsigned m, unsigned n, unsigned k, int num_cus) {
     if (splitk <= 1)
         return splitk;
-    unsigned bm, bn;
-    entry_tile(e, &bm, &bn);
-    const uint64_t tiles = (uint64_t)((m + bm - 1) / bm) * ((n + bn - 1) / bn);
+    const WorkgroupTile t = workgroup_tile(e.shape);
+    const uint64_t tiles = (uint64_t)((m + t.bm - 1) / t.bm) * ((n + t.bn - 1) / t.bn);
     if (tiles >= 2ull * (unsigned)num_cus)
         return 1;
     const uint64_t cap = operand_bytes(e, m, n, k);
@@ -48,9 +47,10 @@ unsigned guarded_splitk(const SolutionEntry &e, unsigned splitk, unsigned m, uns
 // tools/check_heuristic.py replays it against every swept case.
 double stream_cost_us(const SolutionEntry &e, unsigned m, unsigned n, unsigned k, int num_cus) {
     const StreamShape &s = e.shape;
+    const LaunchGeometry g = launch_geometry(s, 1, m, n, k);
     const double per_weight = (0.5 + 2.0 * s.mt / s.nt) * 1e-7; // unpack once per block + fragment loads per (m-tile, n-tile) pair
-    const unsigned blocks = (m + 16 * s.mt - 1) / (16 * s.mt);
-    const double wgs = (double)blocks * ((n / kTileN + s.nt * s.wn - 1) / (s.nt * s.wn));
+    const unsigned blocks = (m + g.bm - 1) / g.bm;               // (the staged kernels too: m-tiles, as the model was fitted)
+    const double wgs = (double)blocks * g.grid_x;
     // VALU-bound: a CU that holds two workgroups takes twice as long, one that holds none idles
     const double rounds = (double)(((unsigned)wgs + num_cus - 1) / num_cus);
     return 2.0 + blocks * (double)n * (double)k * per_weight * rounds * num_cus / wgs;
@@ -66,7 +66,7 @@ const StepCost kStepCost[] = {
 };
 const StepCost *step_cost(const SolutionEntry &e) {
     const StreamShape &s = e.shape;
-    const int kind = s.am == kTiledAm ? 8 : 12, kg = (s.am == kWideAm && s.wm == 3) ? 2 : 1, pf = s.am == kWideAm ? s.pa : 1;
+    const int kind = s.am == kTiledAm ? 8 : 12, kg = s.am == kWideAm ? (int)workgroup_tile(s).kparts : 1, pf = s.am == kWideAm ? s.pa : 1;
     for (const StepCost &c : kStepCost)
         if (c.a_type == e.a_type && c.fmt == e.fmt && c.kind == kind && c.tile_m == s.mt && c.nt == s.nt && c.d == s.d && c.pf == pf && c.kg == kg)
             return &c;
@@ -75,11 +75,12 @@ const StepCost *step_cost(const SolutionEntry &e) {
 double tiled_cost_us(const SolutionEntry &e, unsigned m, unsigned n, unsigned k, int num_cus, unsigned splitk) {
     const StreamShape &s = e.shape;
     const bool wide = s.am == kWideAm;
-    const unsigned kg = (wide && s.wm == 3) ? 2u : 1u; // K groups inside the workgroup
-    const unsigned bm = (wide ? 32u : 16u) * s.mt, per_wg = s.nt * s.wn;
-    const double wgs = (double)((m + bm - 1) / bm) * (double)((n / kTileN + per_wg - 1) / per_wg) * splitk;
-    const unsigned ks = span_tiles_for_k(k), nspans = k / (kTileK * ks), parts = splitk * kg;
-    const double steps = (double)((nspans + parts - 1) / parts) * ks; // k-tiles the longest slice walks
+    const LaunchGeometry g = launch_geometry(s, splitk, m, n, k); // (tiled and wide kernels only: kparts = the K groups inside the workgroup)
+    const unsigned kg = g.kparts;
+    // every requested slice counts as a workgroup (the launchers drop empty ones: the model was fitted on this count; it is kept)
+    const double wgs = (double)g.grid_y * (double)g.grid_x * splitk;
+    const unsigned ks = span_tiles_for_k(k);
+    const double steps = (double)g.spans_per_part * ks; // k-tiles the longest slice walks
     const double reduce = splitk > 1 ? 1.5 + (double)splitk * m * n * 8.0 / 5e6 : 0.0;
     if (const StepCost *c = step_cost(e)) {
         // rounds: dispatch is dynamic, so a grid a little over a whole number of rounds pays for part of the next round only when many
@@ -198,7 +199,8 @@ const SolutionEntry *heuristic(const Family &fam, unsigned m, unsigned n, unsign
         const StreamShape &s = e.shape;
         if (s.mt != want_mt || s.am == kTiledAm || is_native_am(s.am) || s.am == kWideAm || s.wm != 1)
             continue; // (the shared-activation-tile kernels, wm = 2, come from the arch table only)
-        const unsigned wgs = (ntiles + s.wn * s.nt - 1) / (s.wn * s.nt);
+        const LaunchGeometry g = launch_geometry(s, 1, m, n, k);
+        const unsigned wgs = g.grid_x;
         const unsigned busy_wk = nspans < (unsigned)s.wk ? nspans : (unsigned)s.wk;
         const double busy = (double)wgs * s.wn * busy_wk;
         double score = 0.0;
@@ -213,7 +215,7 @@ const SolutionEntry *heuristic(const Family &fam, unsigned m, unsigned n, unsign
         // wave count: under-filling costs more than over-filling
         score -= busy < target_waves ? 3.0 * (1.0 - busy / target_waves) : 0.25 * (busy / target_waves - 1.0);
         // spans must divide evenly over the K waves, or some waves idle in the tail
-        const unsigned per = (nspans + s.wk - 1) / s.wk;
+        const unsigned per = g.spans_per_part;
         score -= 2.0 * (1.0 - (double)nspans / ((double)per * s.wk));
         // weight tiles in flight per wave: eight in every swept winner (NT x D = 1 x 8, 2 x 4, 4 x 2); deeper rings measured
         // ~1 us SLOWER at M = 8 / 16, and an unseen shape picked one on the old "deeper on a tie" rule

@@ -1,8 +1,10 @@
 // dispatch.h -- declarations shared by the host-side translation units of libpetit_amd.so (round 6: csrc/api.hip, 1 650 lines, became five):
-//   solutions.hip  the family tables, ids <-> table entries, what an entry can run
+//   solutions.hip  the family tables, ids <-> table entries, what an entry can run (its launch geometry -- tile, grid, K parts and slices -- is
+//                  launch_geometry in solution.h: one function for plan_gemm, the launchers, the cost model, the picks and the tuner's candidates)
 //   cost.hip       the cost model and the formula heuristic behind the arch tables
 //   pick.hip       what PETIT_SOLUTION_AUTO (and the native-class sentinels) resolve to: arch table, neighbours, row split
-//   dispatch.hip   scratch memory, the tuner's candidate list, plan_gemm (what a dense call runs) and gemm_impl (which launches the plan)
+//   dispatch.hip   scratch memory, the tuner's candidate list, plan_gemm (what a dense call runs: kernel, K split and the K slices the launch really
+//                  gets, so also where SiLU-mul is applied when a named split collapses) and gemm_impl (which launches the plan)
 //   api.hip        the C ABI of include/petit_amd.h;  describe.hip: petit_describe_solution / error strings
 // Not installed; the public surface is include/petit_amd.h.
 #pragma once
@@ -42,12 +44,17 @@ enum : int { kClassExact = 0, kClassNativeFp8 = 8, kClassNativeFp6 = 6, kClassNa
 int entry_class(const SolutionEntry &e);
 enum : unsigned { kNeedK32 = 1u, kNeedQuantOut = 2u }; // restrictions of the native pipeline (entry_allows)
 bool entry_allows(const SolutionEntry &e, unsigned restrict_);
-inline bool is_shared(const SolutionEntry &e) { return e.shape.am == kWideAm && e.shape.wm == 5; } // gemm_shared.hpp (plain / bias epilogue only)
-inline bool is_batch(const SolutionEntry &e) { return e.shape.am == 0 && e.shape.wm == 2; }      // gemm_batch.hpp (17 <= M <= 128; reaches the default path through the arch table)
+inline bool is_shared(const SolutionEntry &e) { return shape_is_shared(e.shape); } // gemm_shared.hpp (plain / bias epilogue only)
+inline bool is_batch(const SolutionEntry &e) { return shape_is_batch(e.shape); }   // gemm_batch.hpp (17 <= M <= 128; reaches the default path through the arch table)
 // SiLU-mul epilogue: a wave must hold the gate and the up tile of an output tile -> even n-tiles per wave
 inline bool act_ok(const SolutionEntry &e) { return e.shape.nt % 2 == 0 && !is_shared(e); }
 bool act_runs(const SolutionEntry &e, unsigned splitk, unsigned restrict_ = 0);
-void entry_tile(const SolutionEntry &e, unsigned *bm, unsigned *bn);
+// petit_native_args as the native entry points take it (null: 16-bit in and out)
+inline bool native_args_ok(const petit_native_args *na) {
+    return !na || (na->struct_bytes == sizeof(petit_native_args) && na->reserved == 0 &&
+                   (na->a_format == 0 || na->a_format == 8 || na->a_format == 6 || na->a_format == 4) &&
+                   (na->out_format == 0 || na->out_format == 8 || na->out_format == 6 || na->out_format == 4));
+}
 uint64_t operand_bytes(const SolutionEntry &e, unsigned m, unsigned n, unsigned k);
 
 // --- cost.hip
@@ -120,12 +127,13 @@ struct Scratch { // the scratch a call can use
 struct LaunchPlan {
     int rc = kOk;                         // a refusal, or kOk -- with entry == nullptr: nothing to launch (m, n or k = 0)
     int klass = kClassExact;              // the accuracy class
-    const SolutionEntry *entry = nullptr; // kernel and K split, after the scratch fallbacks
+    const SolutionEntry *entry = nullptr; // kernel and K split, after the scratch fallbacks (the split the id / row / pick names: scratch is sized for it)
     unsigned splitk = 1;
+    LaunchGeometry geo{};                 // grid, spans per K part and K slices of the launch: unsplit where K is too short for the named split
     const void *nv_image = nullptr;       // NVFP4 weights on a native kernel: the MFMA-native image it reads
     uint64_t need = 0;                    // scratch bytes, and the scratch (nullptr for a query)
     void *ws = nullptr;
-    bool act = false, reduce_act = false; // SiLU-mul in the kernel's epilogue / in the reduce pass of a K split
+    bool act = false, reduce_act = false; // SiLU-mul in the kernel's epilogue / in the reduce pass of a K split (geo.slices > 1)
 };
 struct GemmPlan : LaunchPlan {
     unsigned bulk_rows = 0; // 0: one launch.  Else bulk + tail: the row where the tail starts, and the plans of both parts (then entry / splitk name the whole

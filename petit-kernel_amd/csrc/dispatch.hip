@@ -135,8 +135,7 @@ int tune_candidates(int a_type, int b_type, int klass, unsigned m, unsigned n, u
         // kernels none
         // (measured: down 8192 x 28672 at M = 16, staged 16 x 64 tiles with a K split of 2: 29.0 us against 30.5 unsplit -- every CU
         // then pulls half of the activations)
-        const bool splittable = s.am == kTiledAm || s.am == kWideAm || is_native_am(s.am) || (s.am >= 0 && s.am < kDecodeAm && s.wm == 1) || is_batch(e);
-        if (!splittable)
+        if (workgroup_tile(s).one_slice)
             continue;
         for (unsigned sk = 2; sk <= 8 && sk <= nspans; sk *= 2)
             if (guarded_splitk(e, sk, m, n, k, num_cus) == sk) // (a row must never name a split that choose_auto would take away again)
@@ -219,8 +218,9 @@ static GemmPlan plan_transient(const GemmCall &g, const Scratch &s) {
 }
 
 // Every check and decision of a dense call, in the order they are made, and no launch: argument and range checks, the accuracy class, the NVFP4 image, the
-// pick, the bulk + tail row split, the scratch fallbacks.  It keeps no state between calls; the registered workspace is looked up where the launcher needs
-// it, which binds it to the call's stream.
+// pick, the bulk + tail row split, the scratch fallbacks, the launch geometry (how many K slices the named split really gives, and so whether SiLU-mul is
+// the reduce pass's or the kernel's own epilogue's).  It keeps no state between calls; the registered workspace is looked up where the launcher needs it,
+// which binds it to the call's stream.
 GemmPlan plan_gemm(const GemmCall &g, const Scratch &s, bool part) {
     if (g.io && g.io->transient && !part)
         return plan_transient(g, s);
@@ -396,10 +396,33 @@ GemmPlan plan_gemm(const GemmCall &g, const Scratch &s, bool part) {
                 return refuse(kErrKernelShape); // (unreachable: the heuristic never picks a native kernel)
         }
     }
-    p.entry = entry, p.splitk = splitk, p.need = need, p.ws = ws;
     // SiLU-mul: in the kernel's epilogue unsplit; by the reduce pass over plain slabs with a cross-workgroup K split
     p.act = act && splitk == 1;
     p.reduce_act = act && splitk > 1;
+    p.geo = launch_geometry(entry->shape, splitk, m, n, k);
+    if (p.reduce_act && p.geo.slices <= 1 && !p.geo.one_slice) {
+        // K is too short for the split the id (or the table row) names: one slice, no reduce pass -- the launch is unsplit and SiLU-mul its own epilogue's job.
+        // (`need` stays the named split's: what the call was sized for.  The decode / mid kernels take no split at all: their launchers refuse one.)
+        if (!act_ok(*entry)) {
+            if (!is_auto)
+                return refuse(kErrKernelShape);
+            if (klass != kClassExact) { // native class: the class's best kernel whose own epilogue applies SiLU-mul, within the scratch at hand
+                unsigned sk1 = 1;
+                const SolutionEntry *e1 = heuristic_native(fam, klass, m, n, k, true, /*have_slabs=*/false, &sk1, restrict_);
+                if (!e1 || workspace_need(*e1, 1, m, n, k, have_qa) > workspace_need(*entry, splitk, m, n, k, have_qa))
+                    return refuse(kErrKernelShape);
+                entry = e1;
+            } else {
+                entry = heuristic(fam, m, n, k, true);
+                if (!entry || workspace_need(*entry, 1, m, n, k))
+                    return refuse(kErrKernelShape);
+            }
+            splitk = 1;
+        }
+        p.act = true, p.reduce_act = false;
+        p.geo = launch_geometry(entry->shape, 1, m, n, k);
+    }
+    p.entry = entry, p.splitk = splitk, p.need = need, p.ws = ws;
     return p;
 }
 
@@ -418,31 +441,7 @@ static int launch(const GemmCall &g, const LaunchPlan &p) {
     args.workspace = (float *)p.ws;
     const unsigned kind = g.epilogue ? (unsigned)g.epilogue->activation : 0u; // 1 SiLU-mul / 2 SwiGLU-OAI where p.act or p.reduce_act
     args.act = p.act ? kind : 0u, args.reduce_act = p.reduce_act ? kind : 0u;
-    const SolutionEntry *entry = p.entry;
-    int rc = entry->launch(args, p.splitk, (hipStream_t)g.stream);
-    if (rc == kErrSplitCollapsed) {
-        // K is too short for the split the id (or the table row) names: the kernel runs as one part, so SiLU-mul is its own epilogue's job
-        if (!act_ok(*entry)) {
-            if (!is_auto_id(g.solution_id))
-                return kErrKernelShape;
-            Family fam;
-            family_for(g.hints->a_type, g.b_type, &fam);
-            if (p.klass != kClassExact) { // native class: the class's best kernel whose own epilogue applies SiLU-mul, within the scratch at hand
-                unsigned sk1 = 1;
-                const SolutionEntry *e1 = heuristic_native(fam, p.klass, g.m, g.n, g.k, true, /*have_slabs=*/false, &sk1, native_restrictions(g.io));
-                if (!e1 || workspace_need(*e1, 1, g.m, g.n, g.k, a_format != 0) > workspace_need(*entry, p.splitk, g.m, g.n, g.k, a_format != 0))
-                    return kErrKernelShape;
-                entry = e1;
-            } else {
-                entry = heuristic(fam, g.m, g.n, g.k, true);
-                if (!entry || workspace_need(*entry, 1, g.m, g.n, g.k))
-                    return kErrKernelShape;
-            }
-        }
-        args.act = kind, args.reduce_act = 0u;
-        rc = entry->launch(args, 1, (hipStream_t)g.stream);
-    }
-    return rc;
+    return p.entry->launch(args, p.geo, (hipStream_t)g.stream);
 }
 
 int gemm_impl(int b_type, unsigned *c, const unsigned *a, const unsigned *b, const unsigned *scales,

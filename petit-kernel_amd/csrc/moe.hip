@@ -10,8 +10,10 @@ using namespace petit_amd;
 
 namespace {
 
-// rows one workgroup of a MoE form covers (gemm_moe.hpp: the staged / decode kernels' AM / R, the tiled kernel's 16 MT)
-unsigned moe_rows(const SolutionEntry &e) { return e.shape.am == kTiledAm ? 16u * (unsigned)e.shape.mt : (unsigned)am_rows(e.shape.am); }
+// rows one workgroup of a MoE form covers (gemm_moe.hpp: the staged / decode kernels' AM / R, the tiled and native kernels' tile rows)
+unsigned moe_rows(const SolutionEntry &e) { return workgroup_tile(e.shape).moe_rows(); }
+// what the MoE launchers are handed: the kernel's unsplit geometry on the whole problem
+LaunchGeometry moe_geometry(const SolutionEntry &e, unsigned m, unsigned n, unsigned k) { return launch_geometry(e.shape, 1, m, n, k); }
 
 bool moe_runs(const SolutionEntry &e, bool act, unsigned num_experts, unsigned m, unsigned k) {
     return e.launch_moe && e.shape.ks == span_tiles_for_k(k) && (!act || act_ok(e)) && moe_slots(m, moe_rows(e), num_experts) != 0;
@@ -77,9 +79,7 @@ uint64_t qact_bytes(int format, unsigned m, unsigned k) {
 }
 
 bool native_moe_runs(const SolutionEntry &e, bool act, unsigned num_experts, unsigned m, unsigned k) {
-    unsigned bm, bn;
-    entry_tile(e, &bm, &bn);
-    return e.launch_moe_native && e.shape.ks == span_tiles_for_k(k) && (!act || act_ok(e)) && moe_slots(m, bm, num_experts) != 0;
+    return e.launch_moe_native && e.shape.ks == span_tiles_for_k(k) && (!act || act_ok(e)) && moe_slots(m, moe_rows(e), num_experts) != 0;
 }
 
 // A native sentinel: rows per active expert r = ceil(m / min(E, m)); the class's pick for (r, n, k) when it has a MoE form and no K split, else
@@ -113,18 +113,12 @@ const SolutionEntry *native_moe_choose(const Family &fam, int a_type, int b_type
     return nullptr;
 }
 
-bool native_args_valid(const petit_native_args *na) {
-    return !na || (na->struct_bytes == sizeof(petit_native_args) && na->reserved == 0 &&
-                   (na->a_format == 0 || na->a_format == 8 || na->a_format == 6 || na->a_format == 4) &&
-                   (na->out_format == 0 || na->out_format == 8 || na->out_format == 6 || na->out_format == 4));
-}
-
 // the checks every native MoE entry point shares (and the pick): *e, *fam, *act, *a_format, *out_format set on success; m == 0 passes with *e null
 int native_moe_plan(const petit_solution_hints *hints, unsigned num_experts, unsigned m, unsigned n, unsigned k, const int32_t *a_row_index,
                     const int32_t *c_row_index, uint64_t solution_id, const petit_epilogue *epilogue, const petit_native_args *native,
                     const SolutionEntry **e, Family *fam, bool *act, unsigned *a_format, unsigned *out_format) {
     *e = nullptr;
-    if (!native_args_valid(native))
+    if (!native_args_ok(native))
         return kErrBadArgument;
     if (const int rc = moe_check(hints, num_experts, m, n, k, epilogue, fam, act))
         return rc;
@@ -212,7 +206,7 @@ int petit_gemm_native_moe(void *c, const void *a, const void *b, const void *sca
     g.c = c, g.a = qa, g.w = b, g.s = mx ? scales : nullptr, g.gs = global_scales, g.bias = epilogue ? epilogue->bias : nullptr, g.act = act ? (unsigned)epilogue->activation : 0u;
     g.offsets = expert_offsets, g.num_experts = num_experts, g.m = m, g.n = n, g.k = k;
     g.c_idx = c_row_index, g.c_rows = c_row_index ? c_rows : m, g.out_format = out_format;
-    return e->launch_moe_native(g, (hipStream_t)stream);
+    return e->launch_moe_native(g, moe_geometry(*e, m, n, k), (hipStream_t)stream);
 }
 
 int petit_quantize_activations_rows(void *qa, const void *a, const int32_t *a_row_index, unsigned a_rows, unsigned m, unsigned k, int a_type,
@@ -247,7 +241,7 @@ int petit_gemm_fp4_fp16_moe(void *c, const void *a, const void *b, const void *s
     MoeArgs g{};
     g.c = c, g.a = a, g.w = b, g.s = scales, g.gs = global_scales, g.bias = epilogue ? epilogue->bias : nullptr, g.act = act ? (unsigned)epilogue->activation : 0u;
     g.offsets = expert_offsets, g.num_experts = num_experts, g.m = m, g.n = n, g.k = k;
-    return e->launch_moe(g, (hipStream_t)stream);
+    return e->launch_moe(g, moe_geometry(*e, m, n, k), (hipStream_t)stream);
 }
 
 int petit_gemm_fp4_fp16_moe_ex(void *c, const void *a, const void *b, const void *scales, const float *global_scales,
@@ -277,7 +271,7 @@ int petit_gemm_fp4_fp16_moe_ex(void *c, const void *a, const void *b, const void
     g.c = c, g.a = a, g.w = b, g.s = scales, g.gs = global_scales, g.bias = epilogue ? epilogue->bias : nullptr, g.act = act ? (unsigned)epilogue->activation : 0u;
     g.offsets = expert_offsets, g.num_experts = num_experts, g.m = m, g.n = n, g.k = k;
     g.a_idx = a_row_index, g.c_idx = c_row_index, g.a_rows = a_rows, g.c_rows = c_rows;
-    return e->launch_moe_idx(g, (hipStream_t)stream);
+    return e->launch_moe_idx(g, moe_geometry(*e, m, n, k), (hipStream_t)stream);
 }
 
 uint64_t petit_gemm_moe_resolve_solution(const petit_solution_hints *hints, unsigned num_experts, unsigned m, unsigned n, unsigned k,

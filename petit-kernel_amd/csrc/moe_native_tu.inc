@@ -8,20 +8,20 @@
 namespace petit_amd {
 namespace {
 
-template <class Cfg> int launch_native32_moe(const MoeArgs &g, hipStream_t stream) {
+// (geo: the unsplit geometry of the kernel on (m, n, k): solution.h)
+template <class Cfg> int launch_native32_moe(const MoeArgs &g, const LaunchGeometry &geo, hipStream_t stream) {
     // the quantising SiLU-mul epilogue: full 256-column workgroup tiles, identity rows (its output is the next launch's grouped input)
     if (g.out_format && (!g.act || g.n % 512 != 0 || g.c_idx || (g.out_format != 8 && g.out_format != 6 && g.out_format != 4)))
         return kErrKernelShape;
-    const unsigned slots = moe_slots(g.m, Cfg::BM, g.num_experts);
+    const unsigned slots = moe_slots(g.m, geo.moe_rows(), g.num_experts);
     if (!slots)
         return kErrKernelShape;
-    const unsigned ntiles = g.n / kTileN, per_wg = Cfg::WAVES * 2 * Cfg::NP;
     GemmArgs a{};
     a.c = g.c, a.a = g.a, a.w = g.w, a.s = g.s, a.gs = g.gs, a.bias = g.bias, a.act = g.act;
     a.m = g.m, a.n = g.n, a.k = g.k;
-    a.spans_per_wave = g.k / (kTileK * Cfg::KS); // (one K slice: the whole K range)
+    a.spans_per_wave = geo.spans_per_part;       // (one K slice: the whole K range)
     a.qa = g.a, a.qa_format = Cfg::ACT, a.out_format = g.out_format;
-    hipLaunchKernelGGL((gemm_native32_kernel<Cfg, Native32MoeLocator<Cfg>>), dim3((ntiles + per_wg - 1) / per_wg, slots), dim3(Cfg::kThreads), 0,
+    hipLaunchKernelGGL((gemm_native32_kernel<Cfg, Native32MoeLocator<Cfg>>), dim3(geo.grid_x, slots), dim3(Cfg::kThreads), 0,
                        stream, a, (const unsigned char *)g.a, Native32MoeLocator<Cfg>{g.offsets, g.num_experts, g.c_idx, g.c_rows});
     return hipGetLastError() == hipSuccess ? kOk : kErrLaunch;
 }
@@ -31,7 +31,8 @@ template <class Cfg> int launch_native32_moe(const MoeArgs &g, hipStream_t strea
 // family's list (stream_instances.inc) the native arch table picks most; MXFP4 weights have no D = 2 form at KS = 4 with MXFP8 activations.
 // Arguments as PETIT_N32: (KS, MB, NP, WAVES, D, ACT, KT, PF, WM).
 #define PETIT_MOE_N32(KS, MB, NP, WAVES, D, ACT, KT, PF, WM)                                                                         \
-    MoeForm{StreamShape{KS, MB * WM, 2 * NP, WAVES, 4 * KT + PF, D, kNative32Am, ACT == 4 ? 2 : ACT == 6 ? 4 : 1, WM},              \
+    MoeForm{table_shape<StreamShape{KS, MB * WM, 2 * NP, WAVES, 4 * KT + PF, D, kNative32Am, ACT == 4 ? 2 : ACT == 6 ? 4 : 1, WM}, \
+                        32 * MB * WM, 32 * NP * WAVES, 1, true>(),                                                                   \
             &launch_native32_moe<Native32Cfg<PETIT_TU_AT, KS, MB, NP, WAVES, D, ACT, KT, PF, WM, 1, 0, PETIT_TU_WF>>},
 #if PETIT_TU_WF == 6
 #define PETIT_MOE_N32_KS4_FP8 PETIT_MOE_N32(4, 4, 2, 4, 2, 8, 1, 1, 1)

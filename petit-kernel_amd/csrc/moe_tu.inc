@@ -10,7 +10,6 @@
 namespace petit_amd {
 namespace {
 
-// what the decode / tiled launches check besides the grid: SiLU-mul pairs the gate and the up tile inside one wave
 #ifdef PETIT_TU_MOE_INDEXED
 constexpr bool kIndexed = true;
 #else
@@ -18,57 +17,53 @@ constexpr bool kIndexed = false;
 #endif
 RowIndex row_index(const MoeArgs &g) { return RowIndex{g.a_idx, g.c_idx, 0u, g.a_rows, g.c_rows}; }
 
-template <class Cfg> int launch_stream_moe(const MoeArgs &g, hipStream_t stream) {
+// (geo: the unsplit geometry of the kernel on (m, n, k) -- rows per workgroup, workgroups along N, the one K slice's spans per part: solution.h)
+template <class Cfg> int launch_stream_moe(const MoeArgs &g, const LaunchGeometry &geo, hipStream_t stream) {
     if (g.act && Cfg::NT % 2 != 0)
         return kErrKernelShape;
-    const unsigned slots = moe_slots(g.m, Cfg::AM, g.num_experts);
+    const unsigned slots = moe_slots(g.m, geo.moe_rows(), g.num_experts);
     if (!slots)
         return kErrKernelShape;
-    const unsigned ntiles = g.n / kTileN, per_wg = Cfg::WN * Cfg::NT;
-    const unsigned nspans = g.k / (kTileK * Cfg::KS);
     if constexpr (kIndexed)
-        hipLaunchKernelGGL(gemm_stream_moe_idx_kernel<Cfg>, dim3((ntiles + per_wg - 1) / per_wg, slots), dim3(Cfg::kThreads), 0, stream, g.w, g.s, g.a,
-                           g.k, g.n, g.m, (nspans + Cfg::WK - 1) / Cfg::WK, g.act, g.c, g.gs, g.bias, g.offsets, g.num_experts, row_index(g));
+        hipLaunchKernelGGL(gemm_stream_moe_idx_kernel<Cfg>, dim3(geo.grid_x, slots), dim3(Cfg::kThreads), 0, stream, g.w, g.s, g.a,
+                           g.k, g.n, g.m, geo.spans_per_part, g.act, g.c, g.gs, g.bias, g.offsets, g.num_experts, row_index(g));
     else
-        hipLaunchKernelGGL(gemm_stream_moe_kernel<Cfg>, dim3((ntiles + per_wg - 1) / per_wg, slots), dim3(Cfg::kThreads), 0, stream, g.w, g.s, g.a,
-                           g.k, g.n, g.m, (nspans + Cfg::WK - 1) / Cfg::WK, g.act, g.c, g.gs, g.bias, g.offsets, g.num_experts);
+        hipLaunchKernelGGL(gemm_stream_moe_kernel<Cfg>, dim3(geo.grid_x, slots), dim3(Cfg::kThreads), 0, stream, g.w, g.s, g.a,
+                           g.k, g.n, g.m, geo.spans_per_part, g.act, g.c, g.gs, g.bias, g.offsets, g.num_experts);
     return hipGetLastError() == hipSuccess ? kOk : kErrLaunch;
 }
 
-template <class Cfg> int launch_decode_moe(const MoeArgs &g, hipStream_t stream) {
+template <class Cfg> int launch_decode_moe(const MoeArgs &g, const LaunchGeometry &geo, hipStream_t stream) {
     if (g.act && Cfg::NT % 2 != 0)
         return kErrKernelShape;
-    const unsigned slots = moe_slots(g.m, Cfg::R, g.num_experts);
+    const unsigned slots = moe_slots(g.m, geo.moe_rows(), g.num_experts);
     if (!slots)
         return kErrKernelShape;
-    const unsigned ntiles = g.n / kTileN;
-    const unsigned nspans = g.k / (kTileK * Cfg::KS);
     if constexpr (kIndexed)
-        hipLaunchKernelGGL(gemm_decode_moe_idx_kernel<Cfg>, dim3((ntiles + Cfg::NT - 1) / Cfg::NT, slots), dim3(Cfg::kThreads), 0, stream, g.w, g.s,
-                           g.a, g.k, g.n, g.m, (nspans + Cfg::WK - 1) / Cfg::WK, g.act, g.c, g.gs, g.bias, g.offsets, g.num_experts, row_index(g));
+        hipLaunchKernelGGL(gemm_decode_moe_idx_kernel<Cfg>, dim3(geo.grid_x, slots), dim3(Cfg::kThreads), 0, stream, g.w, g.s,
+                           g.a, g.k, g.n, g.m, geo.spans_per_part, g.act, g.c, g.gs, g.bias, g.offsets, g.num_experts, row_index(g));
     else
-        hipLaunchKernelGGL(gemm_decode_moe_kernel<Cfg>, dim3((ntiles + Cfg::NT - 1) / Cfg::NT, slots), dim3(Cfg::kThreads), 0, stream, g.w, g.s,
-                           g.a, g.k, g.n, g.m, (nspans + Cfg::WK - 1) / Cfg::WK, g.act, g.c, g.gs, g.bias, g.offsets, g.num_experts);
+        hipLaunchKernelGGL(gemm_decode_moe_kernel<Cfg>, dim3(geo.grid_x, slots), dim3(Cfg::kThreads), 0, stream, g.w, g.s,
+                           g.a, g.k, g.n, g.m, geo.spans_per_part, g.act, g.c, g.gs, g.bias, g.offsets, g.num_experts);
     return hipGetLastError() == hipSuccess ? kOk : kErrLaunch;
 }
 
-template <class Cfg> int launch_tiled_moe(const MoeArgs &g, hipStream_t stream) {
+template <class Cfg> int launch_tiled_moe(const MoeArgs &g, const LaunchGeometry &geo, hipStream_t stream) {
     if (g.act && Cfg::NTW % 2 != 0)
         return kErrKernelShape;
-    const unsigned slots = moe_slots(g.m, Cfg::BM, g.num_experts);
+    const unsigned slots = moe_slots(g.m, geo.moe_rows(), g.num_experts);
     if (!slots)
         return kErrKernelShape;
-    const unsigned ntiles = g.n / kTileN, per_wg = Cfg::WAVES * Cfg::NTW;
     GemmArgs a{};
     a.c = g.c, a.a = g.a, a.w = g.w, a.s = g.s, a.gs = g.gs, a.bias = g.bias, a.act = g.act;
     a.m = g.m, a.n = g.n, a.k = g.k;
-    a.spans_per_wave = g.k / (kTileK * Cfg::KS); // (one K slice: the whole K range)
+    a.spans_per_wave = geo.spans_per_part;       // (one K slice: the whole K range)
     a.flags = kFlagPrio;                         // (the raster order is the MoE kernel's own: no XCD raster bits)
     if constexpr (kIndexed)
-        hipLaunchKernelGGL(gemm_tiled_moe_idx_kernel<Cfg>, dim3((ntiles + per_wg - 1) / per_wg, slots), dim3(Cfg::kThreads), 0, stream, a, g.offsets,
+        hipLaunchKernelGGL(gemm_tiled_moe_idx_kernel<Cfg>, dim3(geo.grid_x, slots), dim3(Cfg::kThreads), 0, stream, a, g.offsets,
                            g.num_experts, row_index(g));
     else
-        hipLaunchKernelGGL(gemm_tiled_moe_kernel<Cfg>, dim3((ntiles + per_wg - 1) / per_wg, slots), dim3(Cfg::kThreads), 0, stream, a, g.offsets,
+        hipLaunchKernelGGL(gemm_tiled_moe_kernel<Cfg>, dim3(geo.grid_x, slots), dim3(Cfg::kThreads), 0, stream, a, g.offsets,
                            g.num_experts);
     return hipGetLastError() == hipSuccess ? kOk : kErrLaunch;
 }
@@ -84,11 +79,14 @@ template <class Cfg> constexpr LaunchMoeFn stream_moe_fn() {
         return nullptr;
 }
 #define PETIT_MOE_X(KS, MT, NT, WN, WK, D, AM) \
-    MoeForm{StreamShape{KS, MT, NT, WN, WK, D, AM}, stream_moe_fn<StreamCfg<PETIT_TU_AT, PETIT_TU_FMT, KS, MT, NT, WN, WK, D, AM>>()},
+    MoeForm{table_shape<StreamShape{KS, MT, NT, WN, WK, D, AM}, AM ? AM : 16 * MT, 16 * WN * NT, WK, true>(),                                      \
+            stream_moe_fn<StreamCfg<PETIT_TU_AT, PETIT_TU_FMT, KS, MT, NT, WN, WK, D, AM>>()},
 #define PETIT_MOE_G(KS, NT, WK, D, R) \
-    MoeForm{StreamShape{KS, 1, NT, 1, WK, D, kDecodeAm + R, 1, R == 8 ? 2 : 1}, &launch_decode_moe<DecodeCfg<PETIT_TU_AT, KS, NT, WK, D, R>>},
+    MoeForm{table_shape<StreamShape{KS, 1, NT, 1, WK, D, kDecodeAm + R, 1, R == 8 ? 2 : 1}, R, 16 * NT, WK, true>(),                               \
+            &launch_decode_moe<DecodeCfg<PETIT_TU_AT, KS, NT, WK, D, R>>},
 #define PETIT_MOE_T(KS, MT, NTW, WAVES, D) \
-    MoeForm{StreamShape{KS, MT, NTW, WAVES, 1, D, kTiledAm}, &launch_tiled_moe<TiledCfg<PETIT_TU_AT, PETIT_TU_FMT, KS, MT, NTW, WAVES, D>>},
+    MoeForm{table_shape<StreamShape{KS, MT, NTW, WAVES, 1, D, kTiledAm}, TiledCfg<PETIT_TU_AT, PETIT_TU_FMT, KS, MT, NTW, WAVES, D>::BM, 16 * WAVES * NTW, 1, true>(), \
+            &launch_tiled_moe<TiledCfg<PETIT_TU_AT, PETIT_TU_FMT, KS, MT, NTW, WAVES, D>>},
 
 // (a subset of PETIT_WIDE_SHAPES)
 #define PETIT_MOE_WIDE_SHAPES(X) \

@@ -16,9 +16,6 @@ enum : int {
     kErrKernelShape = 2,  // kErrorKernelShape
     kErrLaunch = 3,       // hipGetLastError() != hipSuccess after a launch
     kErrBadArgument = 4,  // null pointer / unknown dtype
-    // internal, never returned to a caller: a launcher asked for SiLU-mul in the reduce pass found that the K range does not split (fewer
-    // spans than parts -> one part, no reduce pass); gemm_impl's launch step then runs the kernel unsplit with SiLU-mul in its own epilogue
-    kErrSplitCollapsed = 100,
 };
 
 // Arithmetic / element types, numbered as the reference's C++ DataType
@@ -61,7 +58,7 @@ struct GemmArgs {
     unsigned reduce_act; // 1 / 2: that activation with a cross-workgroup K split -- the kernels see act = 0 (plain slabs), the reduce pass applies it
     float *workspace;   // fp32 split-K slabs (may be null when splitk == 1)
     unsigned m, n, k;
-    unsigned spans_per_wave; // set by the launcher: ceil(spans / (split_k * WK))
+    unsigned spans_per_wave; // set by the launcher from the planned geometry (LaunchGeometry::spans_per_part, solution.h)
     unsigned flags;          // large-M kernels: kFlagPrio | kFlagXcdRaster | band << kFlagBandShift (launch_flags(), stream_tu.inc)
     // native-FP4 pipeline (gemm_native32.hpp): activations the CALLER already holds quantised (no quantiser launch), and a
     // SiLU-mul epilogue that emits the NEXT GEMM's quantised activations instead of a 16-bit matrix

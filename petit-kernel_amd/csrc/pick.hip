@@ -31,7 +31,7 @@ const SolutionEntry *heuristic_native(const Family &fam, int klass, unsigned m, 
         if (entry_class(e) != klass || !entry_fits(e, m, k) || s.wm == 2 || (need_pairs && !act_ok(e)) || !entry_allows(e, restrict_))
             continue; // (wm = 2: two waves along M, a measured loser kept as a tested instance; wm = 3: two K groups)
         const bool k32 = s.am == kNative32Am;
-        const unsigned bm = (k32 ? 32u : 16u) * s.mt, bn = 16u * s.wn * s.nt;
+        const unsigned bm = workgroup_tile(s).bm, bn = workgroup_tile(s).bn;
         const bool fp4_rate = klass == kClassNativeFp4 || klass == kClassNativeFp6; // (e2m3 activations run at the e2m1 rate)
         const bool two = k32 && fp4_rate && s.mt * s.nt == 16 && s.d == 2; // Native32Cfg::kMinWavesPerSimd
         double tflops; // sustained by this tile shape when the chip is full
@@ -102,19 +102,20 @@ double grid_overhead(const SolutionEntry &e, unsigned splitk, unsigned m, unsign
         // one case worse -- there the activation block starts to weigh and balance alone does not rank: the nearest row is taken as before.)
         if (is_shared(e) || is_native_am(s.am) || s.nt <= 0 || s.wn <= 0)
             return 0.0;
-        const unsigned cols = 16u * (unsigned)s.nt * (unsigned)s.wn;
+        const unsigned cols = workgroup_tile(s).bn;
         const double r = (double)((n + cols - 1) / cols) * std::max(1u, splitk) / num_cus;
         return std::ceil(r - 1e-9) / r;
     }
     if (!tiled && !wide && !batch)
         return 0.0;
-    unsigned bm, bn;
-    entry_tile(e, &bm, &bn);
-    const unsigned kp = batch ? (unsigned)s.wk : (wide && s.wm == 3) ? 2u : 1u; // K parts inside the workgroup
+    const WorkgroupTile t = workgroup_tile(s);
+    const unsigned bm = t.bm, bn = t.bn, kp = t.kparts; // (kp: K parts inside the workgroup)
     const unsigned nspans = k / (kTileK * span_tiles_for_k(k));
     if (nspans == 0 || bm == 0 || bn == 0)
         return 0.0;
-    const unsigned sk = std::max(1u, std::min(splitk, nspans >= kp ? nspans / kp : 1u)); // (the launchers drop empty slices)
+    // (the launchers drop empty slices.  An approximation of launch_geometry's slices -- floor(nspans / kp) where that has ceil(nspans / (spans per part x kp)) --
+    // kept as it is: the neighbour ranking was swept with these values)
+    const unsigned sk = std::max(1u, std::min(splitk, nspans >= kp ? nspans / kp : 1u));
     const unsigned parts = std::min(sk * kp, nspans);
     const StepCost *c = step_cost(e);
     const double resident = c ? (double)c->resident : 1.0;
@@ -160,8 +161,7 @@ AutoChoice choose_auto(const Family &fam, int dev, int a_type, int b_type, bool 
         const int n_alt = tuned_shape_rows(dev, a_type, b_type, n, k, klass, alt, 24);
         const int num_cus = arch_info(dev).num_cus;
         auto waste = [&](const SolutionEntry &e, unsigned mm) {
-            unsigned bm, bn;
-            entry_tile(e, &bm, &bn);
+            const unsigned bm = workgroup_tile(e.shape).bm, bn = workgroup_tile(e.shape).bn;
             const StepCost *sc = step_cost(e);
             const double slots = num_cus * (sc ? (double)sc->resident : 1.0);
             const double tiles = (double)((mm + bm - 1) / bm) * (double)((n + bn - 1) / bn), r = tiles / slots;
@@ -284,8 +284,7 @@ unsigned plan_row_split(const SolutionEntry &e, unsigned splitk, unsigned m, uns
     const StreamShape &s = e.shape;
     if (row_split_disabled() || m <= 512 || splitk != 1 || !(s.am == kTiledAm || s.am == kWideAm))
         return 0;
-    unsigned bm, bn;
-    entry_tile(e, &bm, &bn);
+    const unsigned bm = workgroup_tile(s).bm, bn = workgroup_tile(s).bn;
     const StepCost *sc = step_cost(e);
     const double slots = num_cus * (sc ? (double)sc->resident : 1.0);
     const unsigned nx = (n + bn - 1) / bn, ny = (m + bm - 1) / bm;
@@ -319,8 +318,7 @@ unsigned plan_row_split_native(const SolutionEntry &e, int klass, unsigned split
     const StreamShape &s = e.shape;
     if (row_split_disabled() || m <= 512 || splitk != 1 || s.am != kNative32Am)
         return 0;
-    unsigned bm, bn;
-    entry_tile(e, &bm, &bn);
+    const unsigned bm = workgroup_tile(s).bm, bn = workgroup_tile(s).bn;
     const bool two = s.wm == 1 && s.mt * s.nt == 16 && s.d == 2; // Native32Cfg: the 128 x 256 two-tile-ring forms fit two workgroups per CU
     const double slots = num_cus * (two ? 2.0 : 1.0);
     const unsigned nx = (n + bn - 1) / bn, ny = (m + bm - 1) / bm;

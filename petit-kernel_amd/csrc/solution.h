@@ -46,6 +46,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "layout.h"
 #include "petit_internal.h"
 
 namespace petit_amd {
@@ -103,12 +104,66 @@ constexpr uint64_t make_solution_id(const StreamShape &s, unsigned elem_b, unsig
 constexpr unsigned solution_splitk(uint64_t id) { return (unsigned)(id >> 60) & 0xf; }
 constexpr uint64_t solution_without_splitk(uint64_t id) { return (id & ~((uint64_t)0xf << 60)) | ((uint64_t)1 << 60); }
 
-using LaunchFn = int (*)(const GemmArgs &, unsigned splitk, hipStream_t);
+// --- Launch geometry: the ONE statement of how a kernel's grid and K range lie on a problem, read from the table entry's shape.  plan_gemm (dispatch.hip)
+// decides a call's K split with it, the launchers (stream_tu.inc, moe_tu.inc, moe_native_tu.inc) launch what it says, and the cost model, the picks and the
+// tuner's candidate list read their tiles from it.  The launcher TUs assert at compile time that tile and K parts are their Cfg's own (table_shape).
+constexpr bool shape_is_shared(const StreamShape &s) { return s.am == kWideAm && s.wm == 5; }                 // gemm_shared.hpp
+constexpr bool shape_is_batch(const StreamShape &s) { return s.am == 0 && s.wm == 2; }                        // gemm_batch.hpp
+constexpr bool shape_is_decode(const StreamShape &s) { return s.am >= kDecodeAm; }                            // gemm_decode.hpp
+constexpr bool shape_is_mid(const StreamShape &s) { return s.am > 0 && s.am < kBfpAm && s.wm == 2; }          // gemm_mid.hpp
+constexpr bool shape_is_stream(const StreamShape &s) { return s.am >= 0 && s.am < kDecodeAm && s.wm == 1; }   // gemm_stream.hpp, direct and staged
+struct WorkgroupTile {
+    unsigned bm, bn;     // rows x columns of C per workgroup; the 32x32 MFMA kinds count tile_m in m32-blocks.  (The staged / decode kernels, one m-tile in the
+                         // id, hold stage_rows rows: bm stays the m-tile for the readers that compare tiles across kinds.)
+    unsigned kparts;     // K parts inside a workgroup: the K waves WK of the streaming / decode / mid / batch kinds, the K groups of wide / native32 (wm == 3: 2)
+    unsigned stage_rows; // staged streaming / mid / decode kernels: the activation rows a workgroup holds -- all the M they run; else 0
+    bool one_slice;      // decode / mid: the kinds that take no K split across workgroups
+    bool even_split;     // streaming: grid z is the requested split whatever K (the other kinds drop empty slices)
+    constexpr unsigned moe_rows() const { return stage_rows ? stage_rows : bm; } // rows per workgroup of the kernel's MoE form
+};
+constexpr WorkgroupTile workgroup_tile(const StreamShape &s) {
+    const bool m32 = s.am == kWideAm || s.am == kNative32Am;
+    const bool tile_kind = s.am == kTiledAm || s.am == kNativeAm || m32; // (these read warp_partition_k as something else: solution.h, stream_tu.inc)
+    return WorkgroupTile{(m32 ? 32u : 16u) * (unsigned)s.mt,
+                         16u * (unsigned)s.wn * (unsigned)s.nt,
+                         tile_kind ? (m32 && s.wm == 3 ? 2u : 1u) : (unsigned)s.wk,
+                         s.am > 0 ? (unsigned)am_rows(s.am) : 0u,
+                         shape_is_decode(s) || shape_is_mid(s),
+                         shape_is_stream(s)};
+}
+struct LaunchGeometry : WorkgroupTile {
+    unsigned splitk;         // the split asked for (the launchers of the one-slice kinds refuse > 1)
+    unsigned grid_x, grid_y; // workgroups along N and M (decode / mid: one row of workgroups)
+    unsigned spans_per_part; // K spans one part walks (GemmArgs::spans_per_wave)
+    unsigned slices;         // workgroups along K that own at least one span: grid z; > 1 = fp32 slabs and a reduce pass
+};
+// `splitk` K slices of whole spans over the kparts parts of each workgroup: spans_per_part = ceil(nspans / (splitk kparts)), and as many slices as then
+// own a span (the last may be shorter, and the last workgroup may find its later parts empty) -- what the batch, tiled, wide, shared and native
+// launchers each computed for themselves; the streaming kernels keep every requested slice; decode / mid have one.
+constexpr LaunchGeometry launch_geometry(const StreamShape &s, unsigned splitk, unsigned m, unsigned n, unsigned k) {
+    const WorkgroupTile t = workgroup_tile(s);
+    const unsigned nspans = k / (unsigned)(kTileK * s.ks), split = t.one_slice || splitk == 0 ? 1u : splitk;
+    const unsigned per_wg = t.bn / kTileN, ntiles = n / kTileN;
+    const unsigned spp = (nspans + split * t.kparts - 1) / (split * t.kparts);
+    const unsigned slices = t.even_split ? split : spp ? (nspans + spp * t.kparts - 1) / (spp * t.kparts) : 1u;
+    return LaunchGeometry{t, splitk, (ntiles + per_wg - 1) / per_wg, t.one_slice ? 1u : (m + t.bm - 1) / t.bm, spp, slices};
+}
+// The shape of a table entry (or MoE form), written next to its Cfg from the same macro arguments: states once, at compile time, that the tile and the
+// in-workgroup K parts read from the shape are the Cfg's own.  ROWS: the Cfg's rows per workgroup (kMoe: of its MoE form), COLS: its columns.
+template <StreamShape S, int ROWS, int COLS, int KPARTS, bool kMoe = false> constexpr StreamShape table_shape() {
+    constexpr WorkgroupTile t = workgroup_tile(S);
+    static_assert((kMoe ? t.moe_rows() : t.bm) == (unsigned)ROWS && t.bn == (unsigned)COLS && t.kparts == (unsigned)KPARTS,
+                  "launch geometry (workgroup_tile) disagrees with the kernel's Cfg");
+    return S;
+}
+
+using LaunchFn = int (*)(const GemmArgs &, const LaunchGeometry &, hipStream_t);
 // several GEMMs sharing the activation rows in one launch (GroupTable, petit_internal.h): the launcher fills wg_end
 using LaunchGroupedFn = int (*)(GroupTable, const void *a, unsigned m, unsigned k, hipStream_t);
 
 // all experts of a MoE layer in one launch (MoeArgs, petit_internal.h; gemm_moe.hpp); never a K split across workgroups, no scratch
-using LaunchMoeFn = int (*)(const MoeArgs &, hipStream_t);
+// (the geometry of (shape, split 1, m, n, k): rows per workgroup, grid x, the one slice's spans)
+using LaunchMoeFn = int (*)(const MoeArgs &, const LaunchGeometry &, hipStream_t);
 
 struct SolutionEntry {
     StreamShape shape;

@@ -117,13 +117,6 @@ bool act_runs(const SolutionEntry &e, unsigned splitk, unsigned restrict_) {
     return splitk > 1 ? !(restrict_ & kNeedQuantOut) : act_ok(e);
 }
 
-// The workgroup tile of a kernel (rows x columns of C), whatever its kind (solution.h: the fields read differently per kind).
-void entry_tile(const SolutionEntry &e, unsigned *bm, unsigned *bn) {
-    const StreamShape &s = e.shape;
-    const bool m32 = s.am == kWideAm || s.am == kNative32Am; // 32-row MFMA blocks: tile_m counts m32-blocks
-    *bm = (m32 ? 32u : 16u) * (unsigned)s.mt;
-    *bn = 16u * (unsigned)s.wn * (unsigned)s.nt;
-}
 uint64_t operand_bytes(const SolutionEntry &e, unsigned m, unsigned n, unsigned k) {
     return (uint64_t)n * k / 2 + (uint64_t)n * k / (e.fmt == kFmtNv ? 16 : 32) + 2ull * m * k + 2ull * m * n;
 }

@@ -23,33 +23,26 @@ namespace {
 
 template <class AT> int launch_splitk_reduce(const GemmArgs &args, unsigned parts, hipStream_t stream);
 
-template <class Cfg> int launch_stream(const GemmArgs &args, unsigned splitk, hipStream_t stream) {
+// The launchers launch the geometry they are handed (launch_geometry, solution.h: grid, spans per K part, K slices -- decided in plan_gemm) and keep the
+// refusals only their Cfg can make.
+template <class Cfg> int launch_stream(const GemmArgs &args, const LaunchGeometry &geo, hipStream_t stream) {
     using AT = typename Cfg::AT;
     if (args.act && Cfg::NT % 2 != 0)
         return kErrKernelShape; // SiLU-mul in the kernel's epilogue needs the gate and the up tile in one wave (dispatch.h act_ok); never a silent no-op
-    const unsigned ntiles = args.n / kTileN;
-    const unsigned per_wg = Cfg::WN * Cfg::NT;
-    dim3 grid((ntiles + per_wg - 1) / per_wg, (args.m + 16 * Cfg::MT - 1) / (16 * Cfg::MT), splitk);
-    GemmArgs a = args;
-    const unsigned nspans = args.k / (kTileK * Cfg::KS), kparts = splitk * Cfg::WK;
-    a.spans_per_wave = (nspans + kparts - 1) / kparts;
-    hipLaunchKernelGGL(gemm_stream_kernel<Cfg>, grid, dim3(Cfg::kThreads), 0, stream, a.w, a.s, a.a, a.k, a.n, a.m,
-                       a.spans_per_wave, a.act, a.c, a.gs, a.bias, a.workspace);
+    hipLaunchKernelGGL(gemm_stream_kernel<Cfg>, dim3(geo.grid_x, geo.grid_y, geo.slices), dim3(Cfg::kThreads), 0, stream, args.w, args.s, args.a, args.k,
+                       args.n, args.m, geo.spans_per_part, args.act, args.c, args.gs, args.bias, args.workspace);
     if (hipGetLastError() != hipSuccess)
         return kErrLaunch;
-    return splitk > 1 ? launch_splitk_reduce<AT>(args, splitk, stream) : kOk;
+    return geo.slices > 1 ? launch_splitk_reduce<AT>(args, geo.slices, stream) : kOk;
 }
 
-template <class Cfg> int launch_decode(const GemmArgs &args, unsigned splitk, hipStream_t stream) {
-    if (splitk > 1 || args.m > (unsigned)Cfg::R)
+template <class Cfg> int launch_decode(const GemmArgs &args, const LaunchGeometry &geo, hipStream_t stream) {
+    if (geo.splitk > 1 || args.m > (unsigned)Cfg::R)
         return kErrKernelShape;
     if (args.act && Cfg::NT % 2 != 0)
         return kErrKernelShape;
-    const unsigned ntiles = args.n / kTileN;
-    const unsigned nspans = args.k / (kTileK * Cfg::KS);
-    const unsigned spw = (nspans + Cfg::WK - 1) / Cfg::WK;
-    hipLaunchKernelGGL(gemm_decode_kernel<Cfg>, dim3((ntiles + Cfg::NT - 1) / Cfg::NT), dim3(Cfg::kThreads), 0, stream, args.w,
-                       args.s, args.a, args.k, args.n, args.m, spw, args.act, args.c, args.gs, args.bias);
+    hipLaunchKernelGGL(gemm_decode_kernel<Cfg>, dim3(geo.grid_x), dim3(Cfg::kThreads), 0, stream, args.w,
+                       args.s, args.a, args.k, args.n, args.m, geo.spans_per_part, args.act, args.c, args.gs, args.bias);
     return hipGetLastError() == hipSuccess ? kOk : kErrLaunch;
 }
 
@@ -96,43 +89,30 @@ inline unsigned mid_debug_flags() {
     }();
     return flags;
 }
-template <class Cfg> int launch_mid(const GemmArgs &args, unsigned splitk, hipStream_t stream) {
-    if (splitk > 1 || args.m > (unsigned)Cfg::AM)
+template <class Cfg> int launch_mid(const GemmArgs &args, const LaunchGeometry &geo, hipStream_t stream) {
+    if (geo.splitk > 1 || args.m > (unsigned)Cfg::AM)
         return kErrKernelShape;
     if (args.act && Cfg::NT % 2 != 0)
         return kErrKernelShape;
-    const unsigned ntiles = args.n / kTileN;
-    const unsigned per_wg = Cfg::WN * Cfg::NT;
-    const unsigned nspans = args.k / (kTileK * Cfg::KS);
-    const unsigned spw = (nspans + Cfg::WK - 1) / Cfg::WK;
-    hipLaunchKernelGGL(gemm_mid_kernel<Cfg>, dim3((ntiles + per_wg - 1) / per_wg), dim3(Cfg::kThreads), 0, stream, args.w, args.s,
-                       args.a, args.k, args.n, args.m, spw, args.act, args.c, args.gs, args.bias, mid_debug_flags());
+    hipLaunchKernelGGL(gemm_mid_kernel<Cfg>, dim3(geo.grid_x), dim3(Cfg::kThreads), 0, stream, args.w, args.s,
+                       args.a, args.k, args.n, args.m, geo.spans_per_part, args.act, args.c, args.gs, args.bias, mid_debug_flags());
     return hipGetLastError() == hipSuccess ? kOk : kErrLaunch;
 }
 
 // 17 <= M <= 128 (gemm_batch.hpp): grid (n-blocks, m-blocks, K slices); the K slices of one workgroup's WK parts are whole spans
-template <class Cfg> int launch_batch(const GemmArgs &args, unsigned splitk, hipStream_t stream) {
+template <class Cfg> int launch_batch(const GemmArgs &args, const LaunchGeometry &geo, hipStream_t stream) {
     using AT = typename Cfg::AT;
     if (args.act && Cfg::NT % 2 != 0)
         return kErrKernelShape;
     if (args.out_format || args.qa)
         return kErrKernelShape;
-    const unsigned ntiles = args.n / kTileN;
-    const unsigned per_wg = Cfg::WN * Cfg::NT;
-    const unsigned nspans = args.k / (kTileK * Cfg::KS);
-    const unsigned kparts = (splitk ? splitk : 1u) * Cfg::WK;
-    const unsigned spw = (nspans + kparts - 1) / kparts;                              // spans per part
-    const unsigned slices = (nspans + spw * Cfg::WK - 1) / (spw * Cfg::WK);           // workgroups along K that own at least one span
-    if (slices > 1 && !args.workspace)
+    if (geo.slices > 1 && !args.workspace)
         return kErrKernelShape;
-    if (args.reduce_act && slices <= 1)
-        return kErrSplitCollapsed; // (nothing launched: dispatch.hip runs the kernel unsplit with SiLU-mul in its own epilogue)
-    const dim3 grid((ntiles + per_wg - 1) / per_wg, (args.m + Cfg::BM - 1) / Cfg::BM, slices);
-    hipLaunchKernelGGL(gemm_batch_kernel<Cfg>, grid, dim3(Cfg::kThreads), 0, stream, args.w, args.s, args.a, args.k, args.n, args.m, spw, args.act,
-                       args.c, args.gs, args.bias, args.workspace);
+    hipLaunchKernelGGL(gemm_batch_kernel<Cfg>, dim3(geo.grid_x, geo.grid_y, geo.slices), dim3(Cfg::kThreads), 0, stream, args.w, args.s, args.a, args.k,
+                       args.n, args.m, geo.spans_per_part, args.act, args.c, args.gs, args.bias, args.workspace);
     if (hipGetLastError() != hipSuccess)
         return kErrLaunch;
-    return slices > 1 ? launch_splitk_reduce<AT>(args, slices, stream) : kOk;
+    return geo.slices > 1 ? launch_splitk_reduce<AT>(args, geo.slices, stream) : kOk;
 }
 
 // Second pass of a cross-workgroup K split (fixed summation order: deterministic).
@@ -179,77 +159,40 @@ inline unsigned launch_flags(unsigned bm, unsigned bn, unsigned a_bits = 16) {
     return flags | (ph << kFlagBandShift);
 }
 
-// K slices of whole spans for the tiled / native kernels: `parts` non-empty slices of `chunk` spans (the last may be shorter).
-inline void split_spans(unsigned nspans, unsigned splitk, unsigned *chunk, unsigned *parts) {
-    if (splitk > nspans)
-        splitk = nspans;
-    *chunk = (nspans + splitk - 1) / splitk;
-    *parts = (nspans + *chunk - 1) / *chunk;
+// the large-M kernels (GemmArgs by value): the planned grid, its spans per part and the raster flags of the tile; a_bits as launch_flags.  (The reduce pass
+// of a K split stays with each launcher: called from here, the kernels are emitted in another order.)
+template <class Kernel, class... Extra>
+int launch_large(Kernel kernel, unsigned threads, const GemmArgs &args, const LaunchGeometry &geo, unsigned a_bits, hipStream_t stream, Extra... extra) {
+    if (geo.slices > 1 && !args.workspace)
+        return kErrKernelShape;
+    GemmArgs a = args;
+    a.flags = launch_flags(geo.bm, geo.bn, a_bits);
+    a.spans_per_wave = geo.spans_per_part;
+    hipLaunchKernelGGL(kernel, dim3(geo.grid_x, geo.grid_y, geo.slices), dim3(threads), 0, stream, a, extra...);
+    return hipGetLastError() == hipSuccess ? kOk : kErrLaunch;
 }
 
-template <class Cfg> int launch_tiled(const GemmArgs &args, unsigned splitk, hipStream_t stream) {
-    using AT = typename Cfg::AT;
+template <class Cfg> int launch_tiled(const GemmArgs &args, const LaunchGeometry &geo, hipStream_t stream) {
     if (args.act && Cfg::NTW % 2 != 0)
         return kErrKernelShape; // (the epilogue would store nothing: dispatch.h act_ok keeps such a kernel away from SiLU-mul, this is the backstop)
-    const unsigned ntiles = args.n / kTileN;
-    const unsigned per_wg = Cfg::WAVES * Cfg::NTW;
-    GemmArgs a = args;
-    a.flags = launch_flags(Cfg::BM, per_wg * kTileN);
-    unsigned parts;
-    split_spans(args.k / (kTileK * Cfg::KS), splitk, &a.spans_per_wave, &parts);
-    if (parts > 1 && !args.workspace)
-        return kErrKernelShape;
-    if (args.reduce_act && parts <= 1)
-        return kErrSplitCollapsed; // (nothing launched: dispatch.hip runs the kernel unsplit with SiLU-mul in its own epilogue)
-    dim3 grid((ntiles + per_wg - 1) / per_wg, (args.m + Cfg::BM - 1) / Cfg::BM, parts);
-    hipLaunchKernelGGL(gemm_tiled_kernel<Cfg>, grid, dim3(Cfg::kThreads), 0, stream, a);
-    if (hipGetLastError() != hipSuccess)
-        return kErrLaunch;
-    return parts > 1 ? launch_splitk_reduce<AT>(args, parts, stream) : kOk;
+    const int rc = launch_large(gemm_tiled_kernel<Cfg>, Cfg::kThreads, args, geo, 16, stream);
+    return rc == kOk && geo.slices > 1 ? launch_splitk_reduce<typename Cfg::AT>(args, geo.slices, stream) : rc;
 }
 
-template <class Cfg> int launch_wide(const GemmArgs &args, unsigned splitk, hipStream_t stream) {
-    using AT = typename Cfg::AT;
-    const unsigned ntiles = args.n / kTileN;
-    const unsigned per_wg = Cfg::WAVES * 2 * Cfg::NP;
-    GemmArgs a = args;
-    a.flags = launch_flags(Cfg::BM, per_wg * kTileN);
-    unsigned parts;
-    split_spans(args.k / (kTileK * Cfg::KS), splitk * Cfg::KG, &a.spans_per_wave, &parts);
-    parts = (parts + Cfg::KG - 1) / Cfg::KG; // workgroups along K: each walks KG parts (the last may find its second one empty)
-    if (parts > 1 && !args.workspace)
-        return kErrKernelShape;
-    if (args.reduce_act && parts <= 1)
-        return kErrSplitCollapsed; // (nothing launched: dispatch.hip runs the kernel unsplit with SiLU-mul in its own epilogue)
-    dim3 grid((ntiles + per_wg - 1) / per_wg, (args.m + Cfg::BM - 1) / Cfg::BM, parts);
-    hipLaunchKernelGGL(gemm_wide_kernel<Cfg>, grid, dim3(Cfg::kThreads), 0, stream, a);
-    if (hipGetLastError() != hipSuccess)
-        return kErrLaunch;
-    return parts > 1 ? launch_splitk_reduce<AT>(args, parts, stream) : kOk;
+template <class Cfg> int launch_wide(const GemmArgs &args, const LaunchGeometry &geo, hipStream_t stream) {
+    const int rc = launch_large(gemm_wide_kernel<Cfg>, Cfg::kThreads, args, geo, 16, stream);
+    return rc == kOk && geo.slices > 1 ? launch_splitk_reduce<typename Cfg::AT>(args, geo.slices, stream) : rc;
 }
 
-template <class Cfg> int launch_shared(const GemmArgs &args, unsigned splitk, hipStream_t stream) {
-    using AT = typename Cfg::AT;
+template <class Cfg> int launch_shared(const GemmArgs &args, const LaunchGeometry &geo, hipStream_t stream) {
     if (args.act || args.out_format || args.qa)
         return kErrKernelShape; // (plain / bias epilogue only)
-    const unsigned ntiles = args.n / kTileN;
-    GemmArgs a = args;
-    a.flags = launch_flags(Cfg::BM, 2 * Cfg::NB * kTileN);
-    unsigned parts;
-    split_spans(args.k / (kTileK * Cfg::KS), splitk, &a.spans_per_wave, &parts);
-    if (parts > 1 && !args.workspace)
-        return kErrKernelShape;
-    if (args.reduce_act && parts <= 1)
-        return kErrSplitCollapsed; // (nothing launched: dispatch.hip runs the kernel unsplit with SiLU-mul in its own epilogue)
-    dim3 grid((ntiles + 2 * Cfg::NB - 1) / (2 * Cfg::NB), (args.m + Cfg::BM - 1) / Cfg::BM, parts);
-    hipLaunchKernelGGL(gemm_shared_kernel<Cfg>, grid, dim3(Cfg::kThreads), 0, stream, a);
-    if (hipGetLastError() != hipSuccess)
-        return kErrLaunch;
-    return parts > 1 ? launch_splitk_reduce<AT>(args, parts, stream) : kOk;
+    const int rc = launch_large(gemm_shared_kernel<Cfg>, Cfg::kThreads, args, geo, 16, stream);
+    return rc == kOk && geo.slices > 1 ? launch_splitk_reduce<typename Cfg::AT>(args, geo.slices, stream) : rc;
 }
 
 #if defined(PETIT_TU_NATIVE_AT) && PETIT_TU_PART == 5
-template <class Cfg> int launch_native(const GemmArgs &args, unsigned splitk, hipStream_t stream) {
+template <class Cfg> int launch_native(const GemmArgs &args, const LaunchGeometry &geo, hipStream_t stream) {
     using AT = typename Cfg::AT;
     if (!args.workspace || args.qa || args.out_format)
         return kErrKernelShape; // (pre-quantised input / quantised output are the 32x32x64 kernels' interface)
@@ -264,29 +207,19 @@ template <class Cfg> int launch_native(const GemmArgs &args, unsigned splitk, hi
     hipLaunchKernelGGL(quantize_act_kernel<AT>, dim3((unsigned)blocks), dim3(256), 0, stream, args.a, ws, args.m, args.k);
     if (hipGetLastError() != hipSuccess)
         return kErrLaunch;
-    const unsigned ntiles = args.n / kTileN;
-    const unsigned per_wg = Cfg::WAVES * Cfg::NTW;
     GemmArgs a = args;
-    a.flags = launch_flags(Cfg::BM, per_wg * kTileN, 8);
-    unsigned parts;
-    split_spans(args.k / (kTileK * Cfg::KS), splitk, &a.spans_per_wave, &parts);
     a.workspace = reinterpret_cast<float *>(ws + native_ws_aligned(args.m, args.k));
-    if (args.reduce_act && parts <= 1)
-        return kErrSplitCollapsed; // (only the quantiser has run: the retry repeats it)
-    dim3 grid((ntiles + per_wg - 1) / per_wg, (args.m + Cfg::BM - 1) / Cfg::BM, parts);
-    hipLaunchKernelGGL(gemm_native_kernel<Cfg>, grid, dim3(Cfg::kThreads), 0, stream, a, (const unsigned char *)ws);
-    if (hipGetLastError() != hipSuccess)
-        return kErrLaunch;
-    return parts > 1 ? launch_splitk_reduce<AT>(a, parts, stream) : kOk;
+    const int rc = launch_large(gemm_native_kernel<Cfg>, Cfg::kThreads, a, geo, 8, stream, (const unsigned char *)ws);
+    return rc == kOk && geo.slices > 1 ? launch_splitk_reduce<AT>(a, geo.slices, stream) : rc;
 }
-template <class Cfg> int launch_native32(const GemmArgs &args, unsigned splitk, hipStream_t stream) {
+template <class Cfg> int launch_native32(const GemmArgs &args, const LaunchGeometry &geo, hipStream_t stream) {
     using AT = typename Cfg::AT;
     // activations: quantised here into the call's scratch, or handed over already quantised (args.qa, same layout: the
     // output of petit_quantize_activations or of a producer GEMM's quantising epilogue)
     if (args.qa ? args.qa_format != (unsigned)Cfg::ACT : !args.workspace)
         return kErrKernelShape;
     if (args.out_format) { // quantising SiLU-mul epilogue: 256-column workgroup tiles that are all full, no K split
-        if (!args.act || Cfg::NP != 2 || Cfg::WAVES != 4 || Cfg::WM != 1 || splitk != 1 || args.n % 512 != 0 ||
+        if (!args.act || Cfg::NP != 2 || Cfg::WAVES != 4 || Cfg::WM != 1 || geo.splitk != 1 || args.n % 512 != 0 ||
             (args.out_format != 8 && args.out_format != 6 && args.out_format != 4))
             return kErrKernelShape;
     }
@@ -305,23 +238,11 @@ template <class Cfg> int launch_native32(const GemmArgs &args, unsigned splitk, 
             return kErrLaunch;
         qa = ws;
     }
-    const unsigned ntiles = args.n / kTileN;
-    const unsigned per_wg = Cfg::WAVES * 2 * Cfg::NP;
     GemmArgs a = args;
-    a.flags = launch_flags(Cfg::BM, per_wg * kTileN, Cfg::ACT);
-    unsigned parts;
-    split_spans(args.k / (kTileK * Cfg::KS), splitk * Cfg::KG, &a.spans_per_wave, &parts);
-    parts = (parts + Cfg::KG - 1) / Cfg::KG; // workgroups along K: each walks KG parts (the last may find its second one empty)
     a.workspace = args.qa ? args.workspace : reinterpret_cast<float *>(ws + native_ws_aligned(args.m, args.k));
-    if (parts > 1 && !a.workspace)
-        return kErrKernelShape;
-    if (args.reduce_act && parts <= 1)
-        return kErrSplitCollapsed; // (only the quantiser has run: the retry repeats it)
-    dim3 grid((ntiles + per_wg - 1) / per_wg, (args.m + Cfg::BM - 1) / Cfg::BM, parts);
-    hipLaunchKernelGGL(gemm_native32_kernel<Cfg>, grid, dim3(Cfg::kThreads), 0, stream, a, qa);
-    if (hipGetLastError() != hipSuccess)
-        return kErrLaunch;
-    return parts > 1 ? launch_splitk_reduce<AT>(a, parts, stream) : kOk;
+    void (*const kernel)(GemmArgs, const unsigned char *) = gemm_native32_kernel<Cfg>; // (the dense form: no MoE locator)
+    const int rc = launch_large(kernel, Cfg::kThreads, a, geo, Cfg::ACT, stream, qa);
+    return rc == kOk && geo.slices > 1 ? launch_splitk_reduce<AT>(a, geo.slices, stream) : rc;
 }
 // the stand-alone quantiser of the 32x32x64 kernels' activation layout (petit_quantize_activations)
 template <class AT> int launch_quantize32(const void *a, void *qa, unsigned m, unsigned k, int format, hipStream_t stream) {
@@ -347,20 +268,25 @@ template <class AT> int launch_quantize32(const void *a, void *qa, unsigned m, u
 #define PETIT_TU_NATIVE_FMT kFmtMx
 #define PETIT_TU_NATIVE_WF 4
 #endif
-#define PETIT_N32(KS, MB, NP, WAVES, D, ACT, KT, PF, WM)                                                                      \
-    SolutionEntry{StreamShape{KS, MB * WM, 2 * NP, WAVES, 4 * KT + PF, D, kNative32Am, ACT == 4 ? 2 : ACT == 6 ? 4 : 1, WM}, PETIT_TU_NATIVE_AT::kType, PETIT_TU_NATIVE_FMT, \
-                  &launch_native32<Native32Cfg<PETIT_TU_NATIVE_AT, KS, MB, NP, WAVES, D, ACT, KT, PF, WM, 1, 0, PETIT_TU_NATIVE_WF>>},
+// The table entries, here and below: kernel Cfg, the shape its id spells, and -- stated once, at compile time (table_shape, solution.h) -- that the rows
+// and columns per workgroup and the in-workgroup K parts the host reads from that shape are the Cfg's own; then activation type, format and launchers.
+#define PETIT_N32_CFG(KS_, MB_, NP_, WAVES_, D_, ACT_, KT_, PF_, WM_, KG_, LW_, WM_NIBBLE_)                                                  \
+    ([] { \
+        using Cfg = Native32Cfg<PETIT_TU_NATIVE_AT, KS_, MB_, NP_, WAVES_, D_, ACT_, KT_, PF_, WM_, KG_, LW_, PETIT_TU_NATIVE_WF>; \
+        return SolutionEntry{table_shape<StreamShape{KS_, MB_ * WM_, 2 * NP_, WAVES_, 4 * KT_ + PF_, D_, kNative32Am, ACT_ == 4 ? 2 : ACT_ == 6 ? 4 : 1, WM_NIBBLE_}, Cfg::BM, 32 * Cfg::NP * Cfg::WAVES, Cfg::KG>(), \
+                             PETIT_TU_NATIVE_AT::kType, PETIT_TU_NATIVE_FMT, &launch_native32<Cfg>}; \
+    }()),
+#define PETIT_N32(KS, MB, NP, WAVES, D, ACT, KT, PF, WM) PETIT_N32_CFG(KS, MB, NP, WAVES, D, ACT, KT, PF, WM, 1, 0, WM)
 // two K groups per workgroup (Native32Cfg KG = 2): warp_partition_m nibble 3
-#define PETIT_N32K(KS, MB, NP, WAVES, D, ACT, KT, PF)                                                                          \
-    SolutionEntry{StreamShape{KS, MB, 2 * NP, WAVES, 4 * KT + PF, D, kNative32Am, ACT == 4 ? 2 : ACT == 6 ? 4 : 1, 3}, PETIT_TU_NATIVE_AT::kType, PETIT_TU_NATIVE_FMT, \
-                  &launch_native32<Native32Cfg<PETIT_TU_NATIVE_AT, KS, MB, NP, WAVES, D, ACT, KT, PF, 1, 2, 0, PETIT_TU_NATIVE_WF>>},
+#define PETIT_N32K(KS, MB, NP, WAVES, D, ACT, KT, PF) PETIT_N32_CFG(KS, MB, NP, WAVES, D, ACT, KT, PF, 1, 2, 0, 3)
 // a loader wave stages the activation tiles (Native32Cfg LW = 1): warp_partition_m nibble 4
-#define PETIT_N32L(KS, MB, NP, WAVES, D, ACT, KT, PF)                                                                          \
-    SolutionEntry{StreamShape{KS, MB, 2 * NP, WAVES, 4 * KT + PF, D, kNative32Am, ACT == 4 ? 2 : ACT == 6 ? 4 : 1, 4}, PETIT_TU_NATIVE_AT::kType, PETIT_TU_NATIVE_FMT, \
-                  &launch_native32<Native32Cfg<PETIT_TU_NATIVE_AT, KS, MB, NP, WAVES, D, ACT, KT, PF, 1, 1, 1, PETIT_TU_NATIVE_WF>>},
-#define PETIT_N(KS, MT, NTW, WAVES, D)                                                                  \
-    SolutionEntry{StreamShape{KS, MT, NTW, WAVES, 1, D, kNativeAm}, PETIT_TU_NATIVE_AT::kType, kFmtMx,  \
-                  &launch_native<NativeCfg<PETIT_TU_NATIVE_AT, KS, MT, NTW, WAVES, D>>},
+#define PETIT_N32L(KS, MB, NP, WAVES, D, ACT, KT, PF) PETIT_N32_CFG(KS, MB, NP, WAVES, D, ACT, KT, PF, 1, 1, 1, 4)
+#define PETIT_N(KS_, MT_, NTW_, WAVES_, D_)                                                                                      \
+    ([] { \
+        using Cfg = NativeCfg<PETIT_TU_NATIVE_AT, KS_, MT_, NTW_, WAVES_, D_>; \
+        return SolutionEntry{table_shape<StreamShape{KS_, MT_, NTW_, WAVES_, 1, D_, kNativeAm}, Cfg::BM, 16 * Cfg::WAVES * Cfg::NTW, 1>(), \
+                             PETIT_TU_NATIVE_AT::kType, kFmtMx, &launch_native<Cfg>}; \
+    }()),
 #ifdef PETIT_TU_NV6
 #define PETIT_NATIVE_ENTRIES PETIT_NVNATIVE32_SHAPES(PETIT_N32) PETIT_NVNATIVE32_KG_SHAPES(PETIT_N32K)
 #else
@@ -370,27 +296,35 @@ template <class AT> int launch_quantize32(const void *a, void *qa, unsigned m, u
 #define PETIT_NATIVE_ENTRIES
 #endif
 
-#define PETIT_X(KS, MT, NT, WN, WK, D, AM)                                                   \
-    SolutionEntry{StreamShape{KS, MT, NT, WN, WK, D, AM}, PETIT_TU_AT::kType, PETIT_TU_FMT, \
-                  &launch_stream<StreamCfg<PETIT_TU_AT, PETIT_TU_FMT, KS, MT, NT, WN, WK, D, AM>>, \
-                  stream_grouped_fn<StreamCfg<PETIT_TU_AT, PETIT_TU_FMT, KS, MT, NT, WN, WK, D, AM>>()},
-#define PETIT_P(KS, MT, NT, WN, WK, D, PA)                                                      \
-    SolutionEntry{StreamShape{KS, MT, NT, WN, WK, D, 0, PA}, PETIT_TU_AT::kType, PETIT_TU_FMT, \
-                  &launch_stream<StreamCfg<PETIT_TU_AT, PETIT_TU_FMT, KS, MT, NT, WN, WK, D, 0, 0, PA>>},
-#define PETIT_T(KS, MT, NTW, WAVES, D)                                                              \
-    SolutionEntry{StreamShape{KS, MT, NTW, WAVES, 1, D, kTiledAm}, PETIT_TU_AT::kType, PETIT_TU_FMT,  \
-                  &launch_tiled<TiledCfg<PETIT_TU_AT, PETIT_TU_FMT, KS, MT, NTW, WAVES, D>>},
-#define PETIT_W(KS, MB, NP, WAVES, D, PF)                                                                  \
-    SolutionEntry{StreamShape{KS, MB, 2 * NP, WAVES, 1, D, kWideAm, PF}, PETIT_TU_AT::kType, PETIT_TU_FMT,   \
-                  &launch_wide<WideCfg<PETIT_TU_AT, PETIT_TU_FMT, KS, MB, NP, WAVES, D, PF>>},
+#define PETIT_X(KS_, MT_, NT_, WN_, WK_, D_, AM_)                                                                                          \
+    ([] { \
+        using Cfg = StreamCfg<PETIT_TU_AT, PETIT_TU_FMT, KS_, MT_, NT_, WN_, WK_, D_, AM_>; \
+        return SolutionEntry{table_shape<StreamShape{KS_, MT_, NT_, WN_, WK_, D_, AM_}, 16 * Cfg::MT, 16 * Cfg::WN * Cfg::NT, Cfg::WK>(), \
+                             PETIT_TU_AT::kType, PETIT_TU_FMT, &launch_stream<Cfg>, stream_grouped_fn<Cfg>()}; \
+    }()),
+#define PETIT_P(KS_, MT_, NT_, WN_, WK_, D_, PA_)                                                                                                 \
+    ([] { \
+        using Cfg = StreamCfg<PETIT_TU_AT, PETIT_TU_FMT, KS_, MT_, NT_, WN_, WK_, D_, 0, 0, PA_>; \
+        return SolutionEntry{table_shape<StreamShape{KS_, MT_, NT_, WN_, WK_, D_, 0, PA_}, 16 * Cfg::MT, 16 * Cfg::WN * Cfg::NT, Cfg::WK>(), \
+                             PETIT_TU_AT::kType, PETIT_TU_FMT, &launch_stream<Cfg>}; \
+    }()),
+#define PETIT_T(KS_, MT_, NTW_, WAVES_, D_)                                                                                               \
+    ([] { \
+        using Cfg = TiledCfg<PETIT_TU_AT, PETIT_TU_FMT, KS_, MT_, NTW_, WAVES_, D_>; \
+        return SolutionEntry{table_shape<StreamShape{KS_, MT_, NTW_, WAVES_, 1, D_, kTiledAm}, Cfg::BM, 16 * Cfg::WAVES * Cfg::NTW, 1>(), \
+                             PETIT_TU_AT::kType, PETIT_TU_FMT, &launch_tiled<Cfg>}; \
+    }()),
+#define PETIT_WIDE_CFG(KS_, MB_, NP_, WAVES_, D_, PF_, KG_, GA_, WM_NIBBLE_)                                                                      \
+    ([] { \
+        using Cfg = WideCfg<PETIT_TU_AT, PETIT_TU_FMT, KS_, MB_, NP_, WAVES_, D_, PF_, KG_, GA_>; \
+        return SolutionEntry{table_shape<StreamShape{KS_, MB_, 2 * NP_, WAVES_, 1, D_, kWideAm, PF_, WM_NIBBLE_}, Cfg::BM, Cfg::BN, Cfg::KG>(), \
+                             PETIT_TU_AT::kType, PETIT_TU_FMT, &launch_wide<Cfg>}; \
+    }()),
+#define PETIT_W(KS, MB, NP, WAVES, D, PF) PETIT_WIDE_CFG(KS, MB, NP, WAVES, D, PF, 1, 0, 1)
 // two K groups per workgroup (WideCfg KG = 2): warp_partition_m nibble 3
-#define PETIT_WK2(KS, MB, NP, WAVES, D, PF)                                                                \
-    SolutionEntry{StreamShape{KS, MB, 2 * NP, WAVES, 1, D, kWideAm, PF, 3}, PETIT_TU_AT::kType, PETIT_TU_FMT, \
-                  &launch_wide<WideCfg<PETIT_TU_AT, PETIT_TU_FMT, KS, MB, NP, WAVES, D, PF, 2>>},
+#define PETIT_WK2(KS, MB, NP, WAVES, D, PF) PETIT_WIDE_CFG(KS, MB, NP, WAVES, D, PF, 2, 0, 3)
 // the group-ahead form (WideCfg GA = 1): warp_partition_m nibble 6
-#define PETIT_WGA(KS, MB, NP, WAVES, D)                                                                    \
-    SolutionEntry{StreamShape{KS, MB, 2 * NP, WAVES, 1, D, kWideAm, 1, 6}, PETIT_TU_AT::kType, PETIT_TU_FMT,  \
-                  &launch_wide<WideCfg<PETIT_TU_AT, PETIT_TU_FMT, KS, MB, NP, WAVES, D, 1, 1, 1>>},
+#define PETIT_WGA(KS, MB, NP, WAVES, D) PETIT_WIDE_CFG(KS, MB, NP, WAVES, D, 1, 1, 1, 6)
 // W unpacked once per workgroup into LDS (gemm_shared.hpp): the 32x32x16 family's nibble, warp_partition_m nibble 5; tile_m = 8 m32-blocks
 // (256 rows), 2 NB n-tiles per workgroup, listed as one "wave" along N
 #if !defined(PETIT_TU_NO_GA) && PETIT_TU_PART == 4
@@ -399,40 +333,53 @@ template <class AT> int launch_quantize32(const void *a, void *qa, unsigned m, u
 #define PETIT_WGA_ENTRIES
 #endif
 #if defined(PETIT_TU_SHARED) && PETIT_TU_PART == 4
-#define PETIT_S(KS, NB)                                                                                    \
-    SolutionEntry{StreamShape{KS, 8, 2 * NB, 1, 1, 2, kWideAm, 1, 5}, PETIT_TU_AT::kType, PETIT_TU_FMT,     \
-                  &launch_shared<SharedCfg<PETIT_TU_AT, PETIT_TU_FMT, KS, NB>>},
+#define PETIT_S(KS_, NB_)                                                                                                            \
+    ([] { \
+        using Cfg = SharedCfg<PETIT_TU_AT, PETIT_TU_FMT, KS_, NB_>; \
+        return SolutionEntry{table_shape<StreamShape{KS_, 8, 2 * NB_, 1, 1, 2, kWideAm, 1, 5}, Cfg::BM, Cfg::BN, 1>(), \
+                             PETIT_TU_AT::kType, PETIT_TU_FMT, &launch_shared<Cfg>}; \
+    }()),
 #define PETIT_SHARED_ENTRIES PETIT_SHARED_SHAPES(PETIT_S)
 #else
 #define PETIT_SHARED_ENTRIES
 #endif
 #if defined(PETIT_TU_DECODE) && PETIT_TU_PART == 3
-#define PETIT_G(KS, NT, WK, D, R)                                                                       \
-    SolutionEntry{StreamShape{KS, 1, NT, 1, WK, D, kDecodeAm + R, 1, R == 8 ? 2 : 1}, PETIT_TU_AT::kType, PETIT_TU_FMT,     \
-                  &launch_decode<DecodeCfg<PETIT_TU_AT, KS, NT, WK, D, R>>, &launch_decode_grouped<DecodeCfg<PETIT_TU_AT, KS, NT, WK, D, R>>},
+#define PETIT_G(KS_, NT_, WK_, D_, R_)                                                                                                      \
+    ([] { \
+        using Cfg = DecodeCfg<PETIT_TU_AT, KS_, NT_, WK_, D_, R_>; \
+        return SolutionEntry{table_shape<StreamShape{KS_, 1, NT_, 1, WK_, D_, kDecodeAm + R_, 1, R_ == 8 ? 2 : 1}, 16, 16 * Cfg::NT, Cfg::WK>(), \
+                             PETIT_TU_AT::kType, PETIT_TU_FMT, &launch_decode<Cfg>, &launch_decode_grouped<Cfg>}; \
+    }()),
 #define PETIT_DECODE_ENTRIES PETIT_DECODE_SHAPES(PETIT_G)
 #else
 #define PETIT_DECODE_ENTRIES
 #endif
-#define PETIT_M(KS, NT, WN, WK, D, AM)                                                                  \
-    SolutionEntry{StreamShape{KS, 1, NT, WN, WK, D, AM, 1, 2}, PETIT_TU_AT::kType, PETIT_TU_FMT,         \
-                  &launch_mid<MidCfg<PETIT_TU_AT, PETIT_TU_FMT, KS, NT, WN, WK, D, AM>>},
+#define PETIT_M(KS_, NT_, WN_, WK_, D_, AM_)                                                                                             \
+    ([] { \
+        using Cfg = MidCfg<PETIT_TU_AT, PETIT_TU_FMT, KS_, NT_, WN_, WK_, D_, AM_>; \
+        return SolutionEntry{table_shape<StreamShape{KS_, 1, NT_, WN_, WK_, D_, AM_, 1, 2}, 16, 16 * Cfg::WN * Cfg::NT, Cfg::WK>(), \
+                             PETIT_TU_AT::kType, PETIT_TU_FMT, &launch_mid<Cfg>}; \
+    }()),
 #define PETIT_MID_ENTRIES PETIT_MID_SHAPES(PETIT_M)
-#define PETIT_BT(KS, MT, NT, WN, WK, D)                                                                 \
-    SolutionEntry{StreamShape{KS, MT, NT, WN, WK, D, 0, 1, 2}, PETIT_TU_AT::kType, PETIT_TU_FMT,         \
-                  &launch_batch<BatchCfg<PETIT_TU_AT, PETIT_TU_FMT, KS, MT, NT, WN, WK, D>>},
+#define PETIT_BATCH_CFG(KS_, MT_, NT_, WN_, WK_, D_, DA_, PA_)                                                                                  \
+    ([] { \
+        using Cfg = BatchCfg<PETIT_TU_AT, PETIT_TU_FMT, KS_, MT_, NT_, WN_, WK_, D_, DA_>; \
+        return SolutionEntry{table_shape<StreamShape{KS_, MT_, NT_, WN_, WK_, D_, 0, PA_, 2}, Cfg::BM, 16 * Cfg::WN * Cfg::NT, Cfg::WK>(), \
+                             PETIT_TU_AT::kType, PETIT_TU_FMT, &launch_batch<Cfg>}; \
+    }()),
+#define PETIT_BT(KS, MT, NT, WN, WK, D) PETIT_BATCH_CFG(KS, MT, NT, WN, WK, D, 0, 1)
 // ... with a loader wave per K part: the activation prefetch distance DA rides in the id's prefetch field (pa = 2 / 4 / 8 for DA = 1 / 2 / 4)
-#define PETIT_BTL(KS, MT, NT, WN, WK, D, DA)                                                            \
-    SolutionEntry{StreamShape{KS, MT, NT, WN, WK, D, 0, DA == 1 ? 2 : DA == 2 ? 4 : 8, 2}, PETIT_TU_AT::kType, PETIT_TU_FMT, \
-                  &launch_batch<BatchCfg<PETIT_TU_AT, PETIT_TU_FMT, KS, MT, NT, WN, WK, D, DA>>},
+#define PETIT_BTL(KS, MT, NT, WN, WK, D, DA) PETIT_BATCH_CFG(KS, MT, NT, WN, WK, D, DA, DA == 1 ? 2 : DA == 2 ? 4 : 8)
 #if PETIT_TU_PART == 1
 const SolutionEntry kTable[] = {PETIT_STREAM_SHAPES(PETIT_X) PETIT_PREFETCH_SHAPES(PETIT_P)};
 #elif PETIT_TU_PART == 2
 #ifdef PETIT_TU_BFP_AT
-#define PETIT_B(KS, NT, WN, WK, D, AM)                                                                 \
-    SolutionEntry{StreamShape{KS, 1, NT, WN, WK, D, kBfpAm + AM}, PETIT_TU_AT::kType, PETIT_TU_FMT,   \
-                  &launch_stream<StreamCfg<PETIT_TU_BFP_AT, PETIT_TU_FMT, KS, 1, NT, WN, WK, D, AM>>,   \
-                  stream_grouped_fn<StreamCfg<PETIT_TU_BFP_AT, PETIT_TU_FMT, KS, 1, NT, WN, WK, D, AM>>()},
+#define PETIT_B(KS_, NT_, WN_, WK_, D_, AM_)                                                                                              \
+    ([] { \
+        using Cfg = StreamCfg<PETIT_TU_BFP_AT, PETIT_TU_FMT, KS_, 1, NT_, WN_, WK_, D_, AM_>; \
+        return SolutionEntry{table_shape<StreamShape{KS_, 1, NT_, WN_, WK_, D_, kBfpAm + AM_}, 16 * Cfg::MT, 16 * Cfg::WN * Cfg::NT, Cfg::WK>(), \
+                             PETIT_TU_AT::kType, PETIT_TU_FMT, &launch_stream<Cfg>, stream_grouped_fn<Cfg>()}; \
+    }()),
 const SolutionEntry kTable[] = {PETIT_WIDE_SHAPES(PETIT_X) PETIT_BFP_SHAPES(PETIT_B)};
 #undef PETIT_B
 #else

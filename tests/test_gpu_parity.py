@@ -897,6 +897,67 @@ def test_fused_silu_mul_epilogue(pk, kind, is_bf16, with_bias, m, n, k):
     assert split_served >= 2 or k < 2048
 
 
+@pytest.mark.parametrize("m", [16, 40, 130])
+@pytest.mark.parametrize("n", [64, 256])
+@pytest.mark.parametrize("k", [256, 512, 1024])
+@pytest.mark.parametrize("kind,is_bf16", [("nv", True), ("mx", False)])
+def test_silu_mul_with_a_k_split_that_collapses(pk, kind, is_bf16, m, n, k):
+    """K of one span (256 / 512 / 1024 at span sizes 2 / 4 / 8) with a split nibble of 2: the launch has one K slice and no reduce pass, so SiLU-mul is
+    the kernel's own epilogue's job.  Every enumerated tiled, wide, LDS-shared and batched-decode kernel: bit-identical to its unsplit launch when its
+    epilogue can apply the activation, refused when it cannot (odd n-tiles per wave, the LDS-shared kernel) -- never C unwritten or plain.  The same for
+    one 32x32x64 native kernel per activation format (MXFP4 weights), and the default pick stays within the SiLU-mul bound against the oracle."""
+    dtype = torch.bfloat16 if is_bf16 else torch.float16
+    a, q, s, gs = random_problem(kind, m, n, k, 777 + m + n + k, is_bf16, mx_band=(122, 130))
+    y = oracle_ref(kind, a, is_bf16, q, s, gs).astype(np.float64) * 0.05          # keep silu in its curved range
+    gs *= 0.05
+    bias = (torch.randn(n, generator=torch.Generator().manual_seed(n)) * 0.5).to(dtype)
+    y = y + bias.float().numpy().astype(np.float64)[None, :]
+    gate, up = y[:, : n // 2], y[:, n // 2:]
+    ref = gate / (1.0 + np.exp(-gate)) * up
+    ad, qd, bd = from_bits(a, dtype).to(DEV), torch.from_numpy(q).to(DEV), bias.to(DEV)
+    gsd = torch.tensor([gs], dtype=torch.float32, device=DEV)
+    if kind == "nv":
+        b, sp = pk.repack_nvfp4(qd.view(torch.int32), n, k), pk.process_nvfp4_scales(torch.from_numpy(s).to(DEV).view(torch.float8_e4m3fn), n, k)
+        mul = pk.mul_nvfp4_a16
+    else:
+        b, sp = pk.repack_mxfp4(qd.view(torch.int32), n, k), pk.process_mxfp4_scales(torch.from_numpy(s).to(DEV), n, k)
+        mul = pk.mul_mxfp4_a16
+    h = pk.PetitSolutionHints()
+    h.a_type = h.c_type = dtype
+    h.b_type = pk.DataType.float4_e2m1 if kind == "nv" else pk.DataType.mxfloat4_e2m1
+
+    def split2_is_unsplit_or_refused(sid):
+        sid2 = (sid & ~(0xF << 60)) | (2 << 60)
+        shared = (sid >> 48) & 0xF == 12 and (sid >> 36) & 0xF == 5
+        if ((sid >> 52) & 0xF) % 2 or shared:
+            with pytest.raises(RuntimeError, match="No kernel implementation"):
+                mul(ad, b, sp, gsd, m, n, k, sid2, bias=bd, activation="silu_mul")
+            return False
+        c1 = mul(ad, b, sp, gsd, m, n, k, sid, bias=bd, activation="silu_mul")
+        c2 = mul(ad, b, sp, gsd, m, n, k, sid2, bias=bd, activation="silu_mul")
+        assert c2.shape == (m, n // 2) and torch.equal(c1.view(torch.int16), c2.view(torch.int16)), f"sid {sid2:#x}"
+        return True
+
+    kinds = set()
+    for sid in pk.ops.get_fp4_solutions(h, m, n, k):
+        kind_nib, wm = (sid >> 48) & 0xF, (sid >> 36) & 0xF
+        assert k // (128 * (((sid >> 16) & 0x1F) // 2)) == 1          # one span: nothing to split
+        if kind_nib == 8 or kind_nib == 12 or (kind_nib == 0 and wm == 2):
+            kinds.add((kind_nib, wm == 5, split2_is_unsplit_or_refused(sid)))
+    assert any(served for _, _, served in kinds), kinds
+    if kind == "mx":
+        pk.ops.enable_native_fp4(True)
+        try:
+            native = [sid for sid in pk.ops.get_fp4_solutions(h, m, n, k) if (sid >> 48) & 0xF == 13]
+            for code in (2, 4, 6):                                    # activations quantised to MXFP8 / MXFP6 / MXFP4
+                assert split2_is_unsplit_or_refused(next(sid for sid in native if (sid >> 32) & 7 == code))
+        finally:
+            pk.ops.enable_native_fp4(False)
+    c = mul(ad, b, sp, gsd, m, n, k, -1, bias=bd, activation="silu_mul")
+    err = np.abs(to_f32(bits(c), is_bf16).astype(np.float64) - ref)
+    assert (err <= np.maximum(1e-2, 2e-2 * np.abs(ref))).all(), f"default pick: max err {err.max()}"
+
+
 # --- adversarial activations: the kernels must not depend on the activations' dynamic range ---------------
 
 SPAN = 1024   # k per span at KS = 8: the block-floating-point unit of the Bf16Bfp kernels (csrc/gemm_stream.hpp)

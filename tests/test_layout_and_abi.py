@@ -975,6 +975,40 @@ def test_native_silu_mul_without_slab_scratch_names_a_kernel_that_applies_it():
                         assert split == 1 and ntw % 2 == 0, (hex(sid), _lib.describe_solution(sid))
 
 
+def test_collapsed_k_split_with_silu_mul_is_decided_in_the_plan():
+    """A K of one span cannot be split: a split nibble of 2 gives one slice and no reduce pass, so SiLU-mul -- which rides on the reduce pass of a real
+    split -- is the kernel's own epilogue's job.  The plan knows the launch geometry, so petit_gemm_resolve_solution answers as the launcher will: an
+    explicit id resolves exactly when its kernel can apply the epilogue (an even number of n-tiles per wave, and not the LDS-shared kernel, whose
+    epilogue is plain / bias only), and PETIT_SOLUTION_AUTO names such a kernel.  k = 256 / 512 / 1024 are one span at span sizes 2 / 4 / 8."""
+    from petit_kernel import _lib
+    L = _lib.lib
+    epi = _lib.Epilogue(None, 1, 0)
+    applies = lambda sid: ((sid >> 52) & 0xF) % 2 == 0 and not ((sid >> 48) & 0xF == 12 and (sid >> 36) & 0xF == 5)
+    seen = set()
+    for at in (_lib.CXX_DTYPE_BF16, _lib.CXX_DTYPE_FP16):
+        for bt in (_lib.CXX_DTYPE_FP4_E2M1, _lib.CXX_DTYPE_MXFP4_E2M1):
+            h = _lib.SolutionHints(at, bt, at, 0)
+            for k in (256, 512, 1024):
+                for n in (64, 256):
+                    for m in (40, 300):
+                        cnt = C.c_uint(0)
+                        L.petit_gemm_get_solutions(C.byref(h), m, n, k, None, C.byref(cnt))
+                        buf = (C.c_uint64 * cnt.value)()
+                        L.petit_gemm_get_solutions(C.byref(h), m, n, k, buf, C.byref(cnt))
+                        for sid in buf[:cnt.value]:
+                            kind, wm = (sid >> 48) & 0xF, (sid >> 36) & 0xF
+                            if not (kind == 8 or kind == 12 or (kind == 0 and wm == 2)):
+                                continue
+                            seen.add((kind, wm == 5, applies(sid)))
+                            split2 = (sid & ~(0xF << 60)) | (2 << 60)
+                            got = L.petit_gemm_resolve_solution(C.byref(h), m, n, k, C.c_uint64(split2), C.byref(epi), C.c_uint64(1 << 40))
+                            assert (got != 0) == applies(sid), (m, n, k, hex(sid), hex(got), _lib.describe_solution(sid))
+                        auto = L.petit_gemm_resolve_solution(C.byref(h), m, n, k, C.c_uint64(_lib.PETIT_SOLUTION_AUTO), C.byref(epi), C.c_uint64(1 << 40))
+                        assert auto and applies(auto), (m, n, k, hex(auto), _lib.describe_solution(auto))
+    # every kind met, kernels that apply the epilogue and kernels that do not
+    assert {(8, False, True), (8, False, False), (12, False, True), (12, True, False), (0, False, True), (0, False, False)} <= seen, seen
+
+
 # --- the MFMA-native image of NVFP4 weights (csrc/nvnative.hip): the host twin against its numpy statement ------------------------
 
 def _checkpoint_like_nvfp4(n, k, seed):

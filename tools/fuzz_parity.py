@@ -53,7 +53,7 @@ while time.time() - t0 < float(sys.argv[2]) if len(sys.argv) > 2 else 150:
             sid_k = (sid & ~(0xF << 60)) | (sk << 60)
             try:
                 c = T.run_case(pk, kind, a, is_bf16, q, s, gs, m, n, k, sid_k)
-            except RuntimeError:      # (this kernel kind has no such split / K too short)
+            except RuntimeError:      # (this kernel kind takes no split; a K too short for the split runs as one slice: plan_gemm)
                 c = T.run_case(pk, kind, a, is_bf16, q, s, gs, m, n, k, sid)
                 sid_k = sid
             mode = f"explicit {sid_k:#x}"
