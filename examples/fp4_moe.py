@@ -63,6 +63,32 @@ def main():
     same = petit_kernel.fp4_moe_fused(x.to(dev), w13, p13, gs13.to(dev), w2, p2, gs2.to(dev), rw, rids, "nvfp4")
     assert torch.equal(routed.view(torch.int16), same.view(torch.int16))
     print(f"fp4_moe_routed: equals fp4_moe_fused on moe_route's ids {tuple(rids.shape)} and weights bit for bit")
+    # DeepSeek-style: sigmoid scoring with groups, and one always-on shared expert of the routed experts' size as expert E of the stacks
+    # ("shared-experts fusion"): every token gets slot topk with id E and weight 1, written by the same route + align launch
+    qs13, ss13 = random_nvfp4(2 * I, H, g)
+    qs2, ss2 = random_nvfp4(H, I, g)
+    EA = E + 1
+    w13a = petit_kernel.repack_nvfp4(torch.cat([q13, qs13]).to(dev).view(torch.int32), EA * 2 * I, H)
+    p13a = petit_kernel.process_nvfp4_scales(torch.cat([s13.view(torch.uint8), ss13.view(torch.uint8)]).view(torch.float8_e4m3fn).to(dev), EA * 2 * I, H)
+    w2a = petit_kernel.repack_nvfp4(torch.cat([q2, qs2]).to(dev).view(torch.int32), EA * H, I)
+    p2a = petit_kernel.process_nvfp4_scales(torch.cat([s2.view(torch.uint8), ss2.view(torch.uint8)]).view(torch.float8_e4m3fn).to(dev), EA * H, I)
+    gsa = torch.full((EA,), 0.05, device=dev)
+    deepseek = dict(scoring="sigmoid", renormalize=True, n_group=4, topk_group=2, routed_scaling_factor=2.5,
+                    bias=torch.randn(E, generator=g).to(dev) * 0.1)
+    with_shared = petit_kernel.fp4_moe_routed(x.to(dev), logits, w13a, p13a, gsa, w2a, p2a, gsa, topk, "nvfp4", num_shared=1, **deepseek)
+    sw, sids = petit_kernel.moe_route(logits, topk, num_shared=1, **deepseek)
+    assert sids.shape == (T, topk + 1) and (sids[:, topk] == E).all() and (sw[:, topk] == 1.0).all()
+    # the same thing the long way: the routed layer on the E routed experts, the shared expert as two dense calls, an add
+    routed_only = petit_kernel.fp4_moe_routed(x.to(dev), logits, w13, p13, gs13.to(dev), w2, p2, gs2.to(dev), topk, "nvfp4", **deepseek)
+    ws13 = petit_kernel.repack_nvfp4(qs13.to(dev).view(torch.int32), 2 * I, H)
+    ps13 = petit_kernel.process_nvfp4_scales(ss13.to(dev), 2 * I, H)
+    ws2 = petit_kernel.repack_nvfp4(qs2.to(dev).view(torch.int32), H, I)
+    ps2 = petit_kernel.process_nvfp4_scales(ss2.to(dev), H, I)
+    hs = petit_kernel.mul_nvfp4_a16(x.to(dev), ws13, ps13, gsa[:1], T, 2 * I, H, -1, activation="silu_mul")
+    long_way = routed_only.float() + petit_kernel.mul_nvfp4_a16(hs, ws2, ps2, gsa[:1], T, H, I, -1).float()
+    err_s = (with_shared.float() - long_way).pow(2).mean().sqrt() / long_way.pow(2).mean().sqrt()
+    print(f"fp4_moe_routed(num_shared=1): {topk + 1} slots per token, rms difference to routed layer + dense shared expert = {err_s:.2e}")
+    assert err_s < 1e-2
 
 
 if __name__ == "__main__":

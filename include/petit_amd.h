@@ -632,7 +632,8 @@ int petit_moe_combine(void *out, const void *slot_out, const float *topk_weights
  * topk_group outside 1..n_group, topk > topk_group * (E / n_group), groups or a bias with the softmax scoring, several chunks without a
  * workspace; PETIT_ERROR_BAD_ARGUMENT for a logits_dtype or scoring that does not exist.  num_tokens == 0 is PETIT_OK (petit_moe_route_align
  * then writes the all-zero expert_offsets, as petit_moe_align does).  desc null = a zero-initialised one.
- * Not here: an expert map for expert parallelism (map ids to -1 afterwards), the router's own GEMM, auxiliary-loss outputs beyond keys_out.
+ * An expert map for expert parallelism and shared experts: the _ex entries below.
+ * Not here: the router's own GEMM, auxiliary-loss outputs beyond keys_out.
  */
 #define PETIT_ROUTE_SOFTMAX 0
 #define PETIT_ROUTE_SIGMOID 1
@@ -650,6 +651,50 @@ uint64_t petit_moe_route_align_workspace_bytes(unsigned num_tokens, unsigned top
 int petit_moe_route_align(const void *router_logits, int logits_dtype, unsigned num_tokens, unsigned num_experts, unsigned topk,
                           const petit_route_desc *desc, int32_t *topk_ids, float *topk_weights, float *keys_out, int32_t *expert_offsets,
                           int32_t *sorted_pos, int32_t *token_index, void *workspace, void *stream);
+
+/*
+ * The complete slot list in the route launch: petit_moe_route_ex / petit_moe_route_align_ex take petit_moe_route's arguments and a
+ * petit_route_slots, and write what petit_moe_align and petit_moe_combine read for a layer with an expert map (expert parallelism) and
+ * shared experts (DeepSeek-V3 / R1, Llama-4, Qwen2-MoE: "shared-experts fusion", the shared expert as one more expert that every token
+ * routes to).  slots null or zero-initialised is petit_moe_route / petit_moe_route_align exactly; those ARE the _ex entries with null slots.
+ *
+ * Definition.  L = num_local_experts (0 = num_experts), S = num_shared.  topk_ids int32 [T][topk + S], topk_weights float32 [T][topk + S]:
+ *   Slots 0 .. topk-1, the routed experts: selection, order and weights are petit_moe_route's, bit for bit.  The weights come from the
+ *     GLOBAL selection: a renormalisation runs over all topk selected experts, local or not -- what an all-reduce of the ranks' partial
+ *     layer outputs needs.  The id written is expert_map[e] for the selected global expert e (int32 [num_experts]; null = e itself); a
+ *     mapped value outside [0, L) is written as -1 (not local: petit_moe_align gives it no row, petit_moe_combine skips it).
+ *   Slots topk + s, s < S, the shared experts: id L + s; weight shared_weight (0 is read as 1), or with shared_gate_logits ([T][S],
+ *     logits_dtype; Qwen2-MoE's shared_expert_gate)  shared_weight * sigmoid(gate_logit[t][s]): the route's own fp32 sigmoid and one
+ *     multiply.  Accuracy, as above: 4 u on the sigmoid plus 1 u for the product, 5 u.  routed_scaling_factor does not touch shared slots.
+ *   keys_out stays [T][num_experts]: the keys of the global experts, unchanged.
+ *   The expert stacks of the layer hold the L local routed experts followed by the S shared ones (L + S experts: what the MoE launches,
+ *   petit_moe_align and petit_moe_combine are given as num_experts, with topk + S as topk).
+ * petit_moe_route_align_ex: petit_moe_route_ex followed by petit_moe_align with num_experts = L + S on the T * (topk + S) entries, same
+ *   outputs bit for bit (expert_offsets int32 [L + S + 1]).  ONE launch when T * (topk + S) <= 1024; above: the route launch, then the
+ *   align's three.  workspace: petit_moe_route_align_ex_workspace_bytes() = petit_moe_align_workspace_bytes(T, topk + S, L + S).
+ * Expert parallelism with shared experts.  A REPLICATED shared expert must be added once: give one rank S > 0 and the others S = 0, or
+ *   give every rank shared_weight = 1 / ranks.  A shared expert SHARDED along its intermediate dimension takes weight 1 on every rank: down
+ *   sums over that dimension, so the ranks' partial outputs add up.  A shared expert k times wider than the routed ones is k shared
+ *   experts of the routed width (S = k, column blocks of gate / up and the matching row blocks of down): the gated activation is per
+ *   column and down sums over columns.
+ * Errors, all before any launch: everything petit_moe_route refuses, and PETIT_ERROR_PROBLEM_SHAPE for topk + S > PETIT_MOE_MAX_TOPK,
+ * L + S > PETIT_MOE_MAX_EXPERTS, L > num_experts, L != num_experts without an expert_map, num_tokens * (topk + S) >= 2^31,
+ * shared_gate_logits with S == 0.
+ */
+typedef struct petit_route_slots {      /* null or zero-initialised = petit_moe_route exactly */
+    const int32_t *expert_map;          /* [num_experts] or null: global expert -> local expert */
+    unsigned num_local_experts;         /* 0 = num_experts; must be num_experts (or 0) when expert_map is null */
+    unsigned num_shared;                /* S >= 0 */
+    float shared_weight;                /* 0 is read as 1 */
+    const void *shared_gate_logits;     /* [num_tokens][S], logits_dtype, or null */
+} petit_route_slots;
+int petit_moe_route_ex(const void *router_logits, int logits_dtype, unsigned num_tokens, unsigned num_experts, unsigned topk,
+                       const petit_route_desc *desc, const petit_route_slots *slots, int32_t *topk_ids, float *topk_weights, float *keys_out,
+                       void *stream);
+uint64_t petit_moe_route_align_ex_workspace_bytes(unsigned num_tokens, unsigned topk, unsigned num_experts, const petit_route_slots *slots);
+int petit_moe_route_align_ex(const void *router_logits, int logits_dtype, unsigned num_tokens, unsigned num_experts, unsigned topk,
+                             const petit_route_desc *desc, const petit_route_slots *slots, int32_t *topk_ids, float *topk_weights,
+                             float *keys_out, int32_t *expert_offsets, int32_t *sorted_pos, int32_t *token_index, void *workspace, void *stream);
 
 /*
  * Native-class MoE launch (no counterpart in the reference): the routed-expert launch on the block-scaled MFMA, the accuracy class of

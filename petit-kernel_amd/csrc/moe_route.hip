@@ -12,6 +12,8 @@
 // in registers (E <= 1024: 16 at most) as order-preserving unsigned ranks, and every selection -- of groups, then of experts -- is a round of
 // a wave-wide arg-max on (rank, lowest index) with the winner masked out.  No LDS, no atomics.  petit_moe_route_align runs the same code in
 // the align's single workgroup when the routing is one chunk: the ids go to the LDS array the align sorts, route + align are ONE launch.
+// The _ex entries (petit_route_slots) make the same launch write the complete slot list of a token: the routed ids through an expert map
+// (global -> local, -1 when not local), then S shared-expert slots with ids L .. L + S - 1 -- lanes topk .. topk + S - 1 of the token's wave.
 #include <hip/hip_runtime.h>
 
 #include "../../include/petit_amd.h"
@@ -225,13 +227,18 @@ constexpr int kDataTypeFp32 = 100;       // PETIT_DTYPE_FP32
 struct RouteArgs {
     const void *logits; // [num_tokens][num_experts], dtype
     const float *bias;  // [num_experts] or null (sigmoid scoring)
-    int *ids;           // [num_tokens][topk]
-    float *weights;     // [num_tokens][topk]
+    int *ids;           // [num_tokens][topk + num_shared]
+    float *weights;     // [num_tokens][topk + num_shared]
     float *keys;        // [num_tokens][num_experts] or null
     int dtype;
-    unsigned num_tokens, num_experts, topk;
+    unsigned num_tokens, num_experts, topk; // num_experts: the E global experts the routing ranks
     unsigned sigmoid, renorm, n_group, topk_group; // n_group 1: no groups
     float scale;
+    // the slot list (petit_route_slots); without one: no map, num_local = num_experts, num_shared = 0
+    unsigned num_local, num_shared; // L: ids the map may name; S: shared slots, ids L .. L + S - 1.  The align sorts L + S experts
+    float shared_weight;
+    const int *expert_map;   // [num_experts] or null: global id -> local id
+    const void *shared_gate; // [num_tokens][num_shared], dtype, or null
 };
 
 __device__ __forceinline__ float route_logit(const void *logits, int dtype, size_t i) {
@@ -437,6 +444,28 @@ template <int NJ> __device__ __forceinline__ void route_token(const RouteArgs &r
     *w_out = w;
 }
 
+// route_token's (id, weight) of lane r to slot r of the token's slot list: lanes < topk map their global id (one gathered load; a value
+// outside [0, L) is -1), lanes topk + s, s < S, take shared expert s: id L + s, weight shared_weight (* sigmoid(gate logit), one multiply).
+// Both branches are wave-uniform; without a map and without shared experts nothing changes.
+template <class Args> __device__ __forceinline__ void route_slots(const Args &ra, unsigned t, unsigned lane, int *id, float *w) {
+#pragma clang fp contract(off)
+    if (ra.expert_map) {
+        const unsigned e = (unsigned)*id < ra.num_experts ? (unsigned)*id : ra.num_experts - 1; // (always true: keeps the load inside the map)
+        const int m = ra.expert_map[e];
+        *id = (m >= 0 && (unsigned)m < ra.num_local) ? m : -1;
+    }
+    if (ra.num_shared) {
+        const unsigned s = lane - ra.topk;
+        if (lane >= ra.topk && s < ra.num_shared) {
+            float sw = ra.shared_weight;
+            if (ra.shared_gate)
+                sw = sw * route_sigmoid(route_logit(ra.shared_gate, ra.dtype, (size_t)t * ra.num_shared + s));
+            *id = (int)(ra.num_local + s);
+            *w = sw;
+        }
+    }
+}
+
 // the grid form: one wave per token
 template <int NJ> __global__ __launch_bounds__(kRouteWaves * 64) void moe_route_kernel(RouteArgs ra) {
     const unsigned lane = threadIdx.x & 63u, t = blockIdx.x * kRouteWaves + (threadIdx.x >> 6);
@@ -445,26 +474,39 @@ template <int NJ> __global__ __launch_bounds__(kRouteWaves * 64) void moe_route_
     int id;
     float w;
     route_token<NJ>(ra, t, lane, &id, &w);
-    if (lane < ra.topk) {
-        ra.ids[(size_t)t * ra.topk + lane] = id;
-        ra.weights[(size_t)t * ra.topk + lane] = w;
+    route_slots(ra, t, lane, &id, &w);
+    const unsigned slots = ra.topk + ra.num_shared; // (<= kMaxTopk: one lane each)
+    if (lane < slots) {
+        ra.ids[(size_t)t * slots + lane] = id;
+        ra.weights[(size_t)t * slots + lane] = w;
     }
 }
 
-// one chunk (num_tokens * topk <= kChunk): the workgroup's 16 waves route the tokens, the ids go to LDS as load_chunk leaves them (and to
-// memory with the weights, for the combine), and the align's one-chunk code follows
+// one chunk (num_tokens * (topk + num_shared) <= kChunk): the workgroup's 16 waves route the tokens, the slot ids go to LDS as load_chunk leaves
+// them (and to memory with the weights, for the combine), and the align's one-chunk code follows on the L + S experts the slot ids name
 template <int NJ> __global__ __launch_bounds__(kChunk) void moe_route_align_one_kernel(RouteArgs ra, int *offsets, int *sorted_pos, int *token_index) {
     __shared__ __attribute__((aligned(16))) int ids_s[kChunk]; // (read as int4: rank_in_chunk)
     __shared__ unsigned cnt[kChunk], wave_sums[kChunk / 64];
-    const unsigned lane = threadIdx.x & 63u, n_entries = ra.num_tokens * ra.topk;
+    const unsigned lane = threadIdx.x & 63u, slots = ra.topk + ra.num_shared, n_entries = ra.num_tokens * slots;
+    const unsigned align_experts = ra.num_local + ra.num_shared; // (<= kChunk; the routing above it ranks ra.num_experts)
     if (threadIdx.x >= n_entries)
         ids_s[threadIdx.x] = -1;
     for (unsigned t = threadIdx.x >> 6; t < ra.num_tokens; t += kChunk / 64) {
         int id;
         float w;
         route_token<NJ>(ra, t, lane, &id, &w);
-        if (lane < ra.topk) {
-            const unsigned p = t * ra.topk + lane; // (< n_entries <= kChunk)
+        if constexpr (NJ == 16) {
+            // the 16-key form has no register to spare for the slot list's arguments across route_token: read them from the kernel
+            // argument segment (scalar loads, RouteArgs is the first argument) once per token instead
+            typedef const __attribute__((address_space(4))) RouteArgs *KernArgs;
+            KernArgs ka = (KernArgs)__builtin_amdgcn_kernarg_segment_ptr();
+            asm volatile("" : "+s"(ka));
+            route_slots(*ka, t, lane, &id, &w);
+        } else {
+            route_slots(ra, t, lane, &id, &w);
+        }
+        if (lane < slots) {
+            const unsigned p = t * slots + lane; // (< n_entries <= kChunk)
             ra.ids[p] = id;
             ra.weights[p] = w;
             ids_s[p] = id;
@@ -474,10 +516,10 @@ template <int NJ> __global__ __launch_bounds__(kChunk) void moe_route_align_one_
     const int id = ids_s[threadIdx.x];
     chunk_histogram(id, cnt);
     __syncthreads();
-    const unsigned c = threadIdx.x < ra.num_experts ? cnt[threadIdx.x] : 0u;
+    const unsigned c = threadIdx.x < align_experts ? cnt[threadIdx.x] : 0u;
     unsigned routed;
     const unsigned base = block_exclusive_scan(c, wave_sums, &routed);
-    align_one_place(id, ids_s, cnt, base, routed, n_entries, ra.topk, ra.num_experts, offsets, sorted_pos, token_index);
+    align_one_place(id, ids_s, cnt, base, routed, n_entries, slots, align_experts, offsets, sorted_pos, token_index);
 }
 
 bool route_shape_ok(unsigned num_tokens, unsigned topk, unsigned num_experts) {
@@ -486,10 +528,14 @@ bool route_shape_ok(unsigned num_tokens, unsigned topk, unsigned num_experts) {
 
 unsigned align_chunks(unsigned num_tokens, unsigned topk) { return (unsigned)(((uint64_t)num_tokens * topk + kChunk - 1) / kChunk); }
 
-// every refusal of petit_moe_route / petit_moe_route_align that does not depend on a pointer; fills ra's scalar fields
-int route_check(int logits_dtype, unsigned num_tokens, unsigned num_experts, unsigned topk, const petit_route_desc *desc, RouteArgs *ra) {
+// every refusal of petit_moe_route(_ex) / petit_moe_route_align(_ex) that does not depend on an output pointer; fills ra's scalar fields and
+// the slot list's two input pointers
+int route_check(int logits_dtype, unsigned num_tokens, unsigned num_experts, unsigned topk, const petit_route_desc *desc,
+                const petit_route_slots *slots, RouteArgs *ra) {
     static const petit_route_desc kDefault = {};
+    static const petit_route_slots kNoSlots = {};
     const petit_route_desc &d = desc ? *desc : kDefault;
+    const petit_route_slots &sl = slots ? *slots : kNoSlots;
     if (!route_shape_ok(num_tokens, topk, num_experts) || topk > num_experts || topk > kMaxTopk)
         return kErrProblemShape;
     if (logits_dtype != kDataTypeFp32 && logits_dtype != kDataTypeBf16 && logits_dtype != kDataTypeFp16)
@@ -512,6 +558,14 @@ int route_check(int logits_dtype, unsigned num_tokens, unsigned num_experts, uns
     ra->sigmoid = d.scoring == PETIT_ROUTE_SIGMOID, ra->renorm = d.renormalize != 0;
     ra->n_group = n_group, ra->topk_group = n_group > 1 ? d.topk_group : 1u;
     ra->scale = d.routed_scaling_factor == 0.f ? 1.f : d.routed_scaling_factor;
+    // the slot list: L local experts, S shared slots
+    const unsigned L = sl.num_local_experts ? sl.num_local_experts : num_experts, S = sl.num_shared;
+    if (L > num_experts || (!sl.expert_map && L != num_experts) || (uint64_t)topk + S > kMaxTopk || (uint64_t)L + S > kMoeMaxExperts ||
+        (uint64_t)num_tokens * ((uint64_t)topk + S) >= (1ull << 31) || (sl.shared_gate_logits && S == 0))
+        return kErrProblemShape;
+    ra->num_local = L, ra->num_shared = S;
+    ra->shared_weight = sl.shared_weight == 0.f ? 1.f : sl.shared_weight;
+    ra->expert_map = sl.expert_map, ra->shared_gate = sl.shared_gate_logits;
     return kOk;
 }
 
@@ -593,10 +647,11 @@ int petit_moe_combine(void *out, const void *slot_out, const float *topk_weights
     return hipGetLastError() == hipSuccess ? kOk : kErrLaunch;
 }
 
-int petit_moe_route(const void *router_logits, int logits_dtype, unsigned num_tokens, unsigned num_experts, unsigned topk,
-                    const petit_route_desc *desc, int32_t *topk_ids, float *topk_weights, float *keys_out, void *stream) {
+int petit_moe_route_ex(const void *router_logits, int logits_dtype, unsigned num_tokens, unsigned num_experts, unsigned topk,
+                       const petit_route_desc *desc, const petit_route_slots *slots, int32_t *topk_ids, float *topk_weights, float *keys_out,
+                       void *stream) {
     RouteArgs ra;
-    const int rc = route_check(logits_dtype, num_tokens, num_experts, topk, desc, &ra);
+    const int rc = route_check(logits_dtype, num_tokens, num_experts, topk, desc, slots, &ra);
     if (rc != kOk)
         return rc;
     if (num_tokens == 0)
@@ -608,34 +663,55 @@ int petit_moe_route(const void *router_logits, int logits_dtype, unsigned num_to
     return hipGetLastError() == hipSuccess ? kOk : kErrLaunch;
 }
 
+int petit_moe_route(const void *router_logits, int logits_dtype, unsigned num_tokens, unsigned num_experts, unsigned topk,
+                    const petit_route_desc *desc, int32_t *topk_ids, float *topk_weights, float *keys_out, void *stream) {
+    return petit_moe_route_ex(router_logits, logits_dtype, num_tokens, num_experts, topk, desc, nullptr, topk_ids, topk_weights, keys_out, stream);
+}
+
+uint64_t petit_moe_route_align_ex_workspace_bytes(unsigned num_tokens, unsigned topk, unsigned num_experts, const petit_route_slots *slots) {
+    const unsigned L = slots && slots->num_local_experts ? slots->num_local_experts : num_experts, S = slots ? slots->num_shared : 0u;
+    if ((uint64_t)topk + S > kMaxTopk || (uint64_t)L + S > kMoeMaxExperts)
+        return 0;
+    return petit_moe_align_workspace_bytes(num_tokens, topk + S, L + S);
+}
+
 uint64_t petit_moe_route_align_workspace_bytes(unsigned num_tokens, unsigned topk, unsigned num_experts) {
     return petit_moe_align_workspace_bytes(num_tokens, topk, num_experts);
 }
 
-int petit_moe_route_align(const void *router_logits, int logits_dtype, unsigned num_tokens, unsigned num_experts, unsigned topk,
-                          const petit_route_desc *desc, int32_t *topk_ids, float *topk_weights, float *keys_out, int32_t *expert_offsets,
-                          int32_t *sorted_pos, int32_t *token_index, void *workspace, void *stream) {
+int petit_moe_route_align_ex(const void *router_logits, int logits_dtype, unsigned num_tokens, unsigned num_experts, unsigned topk,
+                             const petit_route_desc *desc, const petit_route_slots *slots, int32_t *topk_ids, float *topk_weights,
+                             float *keys_out, int32_t *expert_offsets, int32_t *sorted_pos, int32_t *token_index, void *workspace, void *stream) {
     RouteArgs ra;
-    const int rc = route_check(logits_dtype, num_tokens, num_experts, topk, desc, &ra);
+    const int rc = route_check(logits_dtype, num_tokens, num_experts, topk, desc, slots, &ra);
     if (rc != kOk)
         return rc;
     if (!expert_offsets)
         return kErrProblemShape;
     if (num_tokens && (!router_logits || !topk_ids || !topk_weights || !sorted_pos || !token_index))
         return kErrProblemShape;
-    if (align_chunks(num_tokens, topk) > 1 && !workspace)
+    const unsigned n_slots = topk + ra.num_shared, align_experts = ra.num_local + ra.num_shared;
+    if (align_chunks(num_tokens, n_slots) > 1 && !workspace)
         return kErrProblemShape;
-    if (num_tokens == 0 || align_chunks(num_tokens, topk) > 1) { // nothing to route, or several chunks: the route grid, then the align's launches
+    if (num_tokens == 0 || align_chunks(num_tokens, n_slots) > 1) { // nothing to route, or several chunks: the route grid, then the align's launches
         if (num_tokens) {
-            const int rr = petit_moe_route(router_logits, logits_dtype, num_tokens, num_experts, topk, desc, topk_ids, topk_weights, keys_out, stream);
+            const int rr = petit_moe_route_ex(router_logits, logits_dtype, num_tokens, num_experts, topk, desc, slots, topk_ids, topk_weights,
+                                              keys_out, stream);
             if (rr != kOk)
                 return rr;
         }
-        return petit_moe_align(topk_ids, 0, num_tokens, topk, num_experts, expert_offsets, sorted_pos, token_index, workspace, stream);
+        return petit_moe_align(topk_ids, 0, num_tokens, n_slots, align_experts, expert_offsets, sorted_pos, token_index, workspace, stream);
     }
     ra.logits = router_logits, ra.ids = topk_ids, ra.weights = topk_weights, ra.keys = keys_out;
     launch_route(ra, true, expert_offsets, sorted_pos, token_index, (hipStream_t)stream);
     return hipGetLastError() == hipSuccess ? kOk : kErrLaunch;
+}
+
+int petit_moe_route_align(const void *router_logits, int logits_dtype, unsigned num_tokens, unsigned num_experts, unsigned topk,
+                          const petit_route_desc *desc, int32_t *topk_ids, float *topk_weights, float *keys_out, int32_t *expert_offsets,
+                          int32_t *sorted_pos, int32_t *token_index, void *workspace, void *stream) {
+    return petit_moe_route_align_ex(router_logits, logits_dtype, num_tokens, num_experts, topk, desc, nullptr, topk_ids, topk_weights, keys_out,
+                                    expert_offsets, sorted_pos, token_index, workspace, stream);
 }
 
 } // extern "C"

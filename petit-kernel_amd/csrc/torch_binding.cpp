@@ -451,6 +451,72 @@ std::tuple<at::Tensor, at::Tensor, at::Tensor, at::Tensor, at::Tensor, at::Tenso
     return {w, ids, sorted_pos, offsets, token_index, keys};
 }
 
+// the complete slot list (petit_moe_route_ex / petit_moe_route_align_ex); the same checks and texts as petit_kernel/ops.py _check_route_slots
+#define PETIT_ROUTE_SLOTS_ARGS                                                                                                          \
+    const std::optional<at::Tensor> &expert_map, int64_t num_local_experts, int64_t num_shared, double shared_weight,                    \
+        const std::optional<at::Tensor> &shared_gate_logits
+struct RouteSlots {
+    petit_route_slots s;
+    int64_t L, S;
+};
+RouteSlots check_route_slots(const at::Tensor &router_logits, int64_t topk, PETIT_ROUTE_SLOTS_ARGS) {
+    const int64_t T = router_logits.size(0), E = router_logits.size(1), S = num_shared;
+    const int64_t L = num_local_experts <= 0 ? E : num_local_experts; // (-1 or 0: num_experts, as the C ABI's 0)
+    TORCH_CHECK(S >= 0 && topk + S <= PETIT_MOE_MAX_TOPK, "topk + num_shared must be in 1..", PETIT_MOE_MAX_TOPK, ", got ", topk + S);
+    TORCH_CHECK(L >= 1 && L <= E && L + S <= PETIT_MOE_MAX_EXPERTS, "num_local_experts must be in 1..num_experts with num_local_experts + num_shared <= ",
+                PETIT_MOE_MAX_EXPERTS, ", got ", L);
+    if (!expert_map) {
+        TORCH_CHECK(L == E, "num_local_experts needs an expert_map");
+    } else {
+        TORCH_CHECK(expert_map->is_cuda() && expert_map->device() == router_logits.device() && expert_map->scalar_type() == at::kInt &&
+                        expert_map->is_contiguous() && expert_map->dim() == 1 && expert_map->size(0) == E,
+                    "expert_map must be a contiguous int32 [num_experts] tensor on router_logits' device");
+    }
+    if (shared_gate_logits) {
+        TORCH_CHECK(S >= 1, "shared_gate_logits needs num_shared >= 1");
+        TORCH_CHECK(shared_gate_logits->is_cuda() && shared_gate_logits->device() == router_logits.device() &&
+                        shared_gate_logits->scalar_type() == router_logits.scalar_type() && shared_gate_logits->is_contiguous() &&
+                        shared_gate_logits->dim() == 2 && shared_gate_logits->size(0) == T && shared_gate_logits->size(1) == S,
+                    "shared_gate_logits must be a contiguous [num_tokens, num_shared] tensor of router_logits' dtype on its device");
+    }
+    petit_route_slots s{};
+    s.expert_map = expert_map ? (const int32_t *)expert_map->data_ptr() : nullptr;
+    s.num_local_experts = (unsigned)L, s.num_shared = (unsigned)S, s.shared_weight = (float)shared_weight;
+    s.shared_gate_logits = shared_gate_logits ? shared_gate_logits->data_ptr() : nullptr;
+    return {s, L, S};
+}
+std::tuple<at::Tensor, at::Tensor, at::Tensor> moe_route_ex(PETIT_ROUTE_ARGS, PETIT_ROUTE_SLOTS_ARGS) {
+    const petit_route_desc d = check_route(router_logits, topk, scoring, renormalize, bias, n_group, topk_group, routed_scaling_factor, return_keys);
+    const RouteSlots sl = check_route_slots(router_logits, topk, expert_map, num_local_experts, num_shared, shared_weight, shared_gate_logits);
+    const int64_t T = router_logits.size(0), E = router_logits.size(1), n_slots = topk + sl.S;
+    const c10::hip::HIPGuardMasqueradingAsCUDA guard(router_logits.device());
+    at::Tensor ids = at::empty({T, n_slots}, router_logits.options().dtype(at::kInt)), w = at::empty({T, n_slots}, router_logits.options().dtype(at::kFloat));
+    at::Tensor keys = return_keys ? at::empty({T, E}, w.options()) : at::empty({0}, w.options());
+    const int rc = petit_moe_route_ex(router_logits.data_ptr(), route_logits_dtype(router_logits), (unsigned)T, (unsigned)E, (unsigned)topk, &d, &sl.s,
+                                      (int32_t *)ids.data_ptr(), (float *)w.data_ptr(), return_keys ? (float *)keys.data_ptr() : nullptr,
+                                      stream_of(router_logits));
+    route_rc(rc, "moe_route_ex", T, E, topk, n_group, topk_group);
+    return {w, ids, keys};
+}
+std::tuple<at::Tensor, at::Tensor, at::Tensor, at::Tensor, at::Tensor, at::Tensor> moe_route_align_ex(PETIT_ROUTE_ARGS, PETIT_ROUTE_SLOTS_ARGS) {
+    const petit_route_desc d = check_route(router_logits, topk, scoring, renormalize, bias, n_group, topk_group, routed_scaling_factor, return_keys);
+    const RouteSlots sl = check_route_slots(router_logits, topk, expert_map, num_local_experts, num_shared, shared_weight, shared_gate_logits);
+    const int64_t T = router_logits.size(0), E = router_logits.size(1), n_slots = topk + sl.S;
+    const c10::hip::HIPGuardMasqueradingAsCUDA guard(router_logits.device());
+    const auto i32 = router_logits.options().dtype(at::kInt);
+    at::Tensor ids = at::empty({T, n_slots}, i32), w = at::empty({T, n_slots}, router_logits.options().dtype(at::kFloat));
+    at::Tensor keys = return_keys ? at::empty({T, E}, w.options()) : at::empty({0}, w.options());
+    at::Tensor sorted_pos = at::empty({T * n_slots}, i32), token_index = at::empty({T * n_slots}, i32), offsets = at::empty({sl.L + sl.S + 1}, i32);
+    const uint64_t ws_bytes = petit_moe_route_align_ex_workspace_bytes((unsigned)T, (unsigned)topk, (unsigned)E, &sl.s);
+    at::Tensor ws = at::empty({(int64_t)ws_bytes}, router_logits.options().dtype(at::kByte));
+    const int rc = petit_moe_route_align_ex(router_logits.data_ptr(), route_logits_dtype(router_logits), (unsigned)T, (unsigned)E, (unsigned)topk, &d, &sl.s,
+                                            (int32_t *)ids.data_ptr(), (float *)w.data_ptr(), return_keys ? (float *)keys.data_ptr() : nullptr,
+                                            (int32_t *)offsets.data_ptr(), (int32_t *)sorted_pos.data_ptr(), (int32_t *)token_index.data_ptr(),
+                                            ws_bytes ? ws.data_ptr() : nullptr, stream_of(router_logits));
+    route_rc(rc, "moe_route_align_ex", T, E, topk, n_group, topk_group);
+    return {w, ids, sorted_pos, offsets, token_index, keys};
+}
+
 // native-class MoE launch (petit_gemm_native_moe); the same checks and texts as petit_kernel/ops.py _mul_native_moe.  A: 16-bit [a_rows,
 // size_k] (a_format 0), or the bytes of the size_m quantised grouped rows (a_format 8 / 6 / 4; a_type names their 16-bit dtype).  Returns
 // 16-bit [c_rows, n_out], or with out_format the bytes of the quantised grouped [size_m, size_n / 2] rows.
@@ -592,6 +658,21 @@ std::tuple<at::Tensor, at::Tensor, at::Tensor, at::Tensor, at::Tensor, at::Tenso
     return {at::empty({T, topk}, f32), at::empty({T, topk}, i32),     at::empty({T * topk}, i32),
             at::empty({E + 1}, i32),   at::empty({T * topk}, i32), (return_keys ? at::empty({T, E}, f32) : at::empty({0}, f32))};
 }
+// (the slot list: topk + num_shared slots, num_local_experts + num_shared experts; num_local_experts <= 0 = num_experts)
+std::tuple<at::Tensor, at::Tensor, at::Tensor> moe_route_ex_meta(PETIT_ROUTE_ARGS, PETIT_ROUTE_SLOTS_ARGS) {
+    const int64_t T = router_logits.size(0), E = router_logits.size(1), n_slots = topk + num_shared;
+    const auto f32 = router_logits.options().dtype(at::kFloat);
+    return {at::empty({T, n_slots}, f32), at::empty({T, n_slots}, router_logits.options().dtype(at::kInt)),
+            (return_keys ? at::empty({T, E}, f32) : at::empty({0}, f32))};
+}
+std::tuple<at::Tensor, at::Tensor, at::Tensor, at::Tensor, at::Tensor, at::Tensor> moe_route_align_ex_meta(PETIT_ROUTE_ARGS, PETIT_ROUTE_SLOTS_ARGS) {
+    const int64_t T = router_logits.size(0), E = router_logits.size(1), n_slots = topk + num_shared;
+    const int64_t L = num_local_experts <= 0 ? E : num_local_experts;
+    const auto f32 = router_logits.options().dtype(at::kFloat);
+    const auto i32 = router_logits.options().dtype(at::kInt);
+    return {at::empty({T, n_slots}, f32),         at::empty({T, n_slots}, i32),     at::empty({T * n_slots}, i32),
+            at::empty({L + num_shared + 1}, i32), at::empty({T * n_slots}, i32), (return_keys ? at::empty({T, E}, f32) : at::empty({0}, f32))};
+}
 
 } // namespace
 
@@ -633,6 +714,10 @@ TORCH_LIBRARY(petit_kernel, m) {
     "float routed_scaling_factor=1.0, bool return_keys=False"
     m.def("moe_route(" PETIT_ROUTE_SCHEMA ") -> (Tensor, Tensor, Tensor)");
     m.def("moe_route_align(" PETIT_ROUTE_SCHEMA ") -> (Tensor, Tensor, Tensor, Tensor, Tensor, Tensor)");
+#define PETIT_ROUTE_SLOTS_SCHEMA \
+    ", Tensor? expert_map=None, int num_local_experts=-1, int num_shared=0, float shared_weight=1.0, Tensor? shared_gate_logits=None"
+    m.def("moe_route_ex(" PETIT_ROUTE_SCHEMA PETIT_ROUTE_SLOTS_SCHEMA ") -> (Tensor, Tensor, Tensor)");
+    m.def("moe_route_align_ex(" PETIT_ROUTE_SCHEMA PETIT_ROUTE_SLOTS_SCHEMA ") -> (Tensor, Tensor, Tensor, Tensor, Tensor, Tensor)");
     // round 3's op name (scales promised inside fp16's range): an alias of mul_mxfp4_a16 for one more round -- the kernels test the range themselves
     m.def("mul_mxfp4_a16_f16range(Tensor A, Tensor B, Tensor s, Tensor global_scale, int size_m, int size_n, int size_k, int solution_id, "
           "Tensor? bias=None, int activation=0) -> Tensor");
@@ -657,7 +742,9 @@ TORCH_LIBRARY(petit_kernel, m) {
     m.impl("moe_align_device", &moe_align_device);              \
     m.impl("moe_combine", &moe_combine);                        \
     m.impl("moe_route", &moe_route);                            \
-    m.impl("moe_route_align", &moe_route_align);
+    m.impl("moe_route_align", &moe_route_align);                \
+    m.impl("moe_route_ex", &moe_route_ex);                      \
+    m.impl("moe_route_align_ex", &moe_route_align_ex);
 TORCH_LIBRARY_IMPL(petit_kernel, CUDA, m) { PETIT_IMPL_REAL(m) }
 TORCH_LIBRARY_IMPL(petit_kernel, CPU, m) { PETIT_IMPL_REAL(m) }
 TORCH_LIBRARY_IMPL(petit_kernel, Meta, m) {
@@ -681,4 +768,6 @@ TORCH_LIBRARY_IMPL(petit_kernel, Meta, m) {
     m.impl("moe_combine", &moe_combine_meta);
     m.impl("moe_route", &moe_route_meta);
     m.impl("moe_route_align", &moe_route_align_meta);
+    m.impl("moe_route_ex", &moe_route_ex_meta);
+    m.impl("moe_route_align_ex", &moe_route_align_ex_meta);
 }

@@ -149,20 +149,41 @@ def moe_combine(slot_out: torch.Tensor, topk_weights: torch.Tensor, topk_ids: to
     return _impl.moe_combine(slot_out, topk_weights, topk_ids, num_experts)
 
 
+def _no_slots(expert_map, num_local_experts, num_shared, shared_weight, shared_gate_logits) -> bool:
+    # every slot-list argument of moe_route / moe_route_align at its default: the call is the plain route
+    return expert_map is None and num_local_experts is None and num_shared == 0 and shared_weight == 1.0 and shared_gate_logits is None
+
+
 def moe_route(router_logits: torch.Tensor, topk: int, *, scoring: str = "softmax", renormalize: bool = True, bias: torch.Tensor = None,
-              n_group: int = 1, topk_group: int = 1, routed_scaling_factor: float = 1.0, return_keys: bool = False):
+              n_group: int = 1, topk_group: int = 1, routed_scaling_factor: float = 1.0, return_keys: bool = False,
+              expert_map: torch.Tensor = None, num_local_experts: int = None, num_shared: int = 0, shared_weight: float = 1.0,
+              shared_gate_logits: torch.Tensor = None):
     # router logits [T, E] (float32 / bfloat16 / float16) -> (topk_weights float32, topk_ids int32[, keys float32 [T, E]]) in one launch
     # (include/petit_amd.h "Routing on the device, from the router's logits").  scoring "softmax" (Mixtral, Qwen3-MoE, gpt-oss with renormalize)
     # or "sigmoid" (DeepSeek-V3: bias = e_score_correction_bias, n_group / topk_group, routed_scaling_factor).  Larger key first, the LOWER index
-    # among equal keys: a routing is a pure function of the logits
-    return _impl.moe_route(router_logits, topk, scoring, renormalize, bias, n_group, topk_group, routed_scaling_factor, return_keys)
+    # among equal keys: a routing is a pure function of the logits.
+    # The complete slot list of a layer with expert parallelism and shared experts, in the same launch (include/petit_amd.h "The complete slot
+    # list in the route launch"): expert_map int32 [E] maps the selected global ids to local ones (a value outside [0, num_local_experts) is
+    # written as -1; the weights stay those of the global selection); num_shared appends slots with ids num_local_experts + s and weight
+    # shared_weight (0 is read as 1), times sigmoid(shared_gate_logits[t, s]) when given ([T, num_shared], router_logits' dtype).  Outputs are
+    # then [T, topk + num_shared]
+    if _no_slots(expert_map, num_local_experts, num_shared, shared_weight, shared_gate_logits):
+        return _impl.moe_route(router_logits, topk, scoring, renormalize, bias, n_group, topk_group, routed_scaling_factor, return_keys)
+    return _impl.moe_route_ex(router_logits, topk, scoring, renormalize, bias, n_group, topk_group, routed_scaling_factor, return_keys,
+                              expert_map, num_local_experts, num_shared, shared_weight, shared_gate_logits)
 
 
 def moe_route_align(router_logits: torch.Tensor, topk: int, *, scoring: str = "softmax", renormalize: bool = True, bias: torch.Tensor = None,
-                    n_group: int = 1, topk_group: int = 1, routed_scaling_factor: float = 1.0, return_keys: bool = False):
+                    n_group: int = 1, topk_group: int = 1, routed_scaling_factor: float = 1.0, return_keys: bool = False,
+                    expert_map: torch.Tensor = None, num_local_experts: int = None, num_shared: int = 0, shared_weight: float = 1.0,
+                    shared_gate_logits: torch.Tensor = None):
     # moe_route, then moe_align_device on its ids, bit for bit: (topk_weights, topk_ids, sorted_pos, expert_offsets, token_index[, keys]);
-    # ONE launch when T * topk <= 1024, four above
-    return _impl.moe_route_align(router_logits, topk, scoring, renormalize, bias, n_group, topk_group, routed_scaling_factor, return_keys)
+    # ONE launch when T * topk <= 1024, four above.  With moe_route's slot-list arguments: the align of the T * (topk + num_shared) slots over
+    # num_local_experts + num_shared experts, ONE launch when T * (topk + num_shared) <= 1024
+    if _no_slots(expert_map, num_local_experts, num_shared, shared_weight, shared_gate_logits):
+        return _impl.moe_route_align(router_logits, topk, scoring, renormalize, bias, n_group, topk_group, routed_scaling_factor, return_keys)
+    return _impl.moe_route_align_ex(router_logits, topk, scoring, renormalize, bias, n_group, topk_group, routed_scaling_factor, return_keys,
+                                    expert_map, num_local_experts, num_shared, shared_weight, shared_gate_logits)
 
 
 def mul_mxfp4_native_moe(a, b: torch.Tensor, s: torch.Tensor, global_scales: torch.Tensor, expert_offsets: torch.Tensor, size_m: int, size_n: int,

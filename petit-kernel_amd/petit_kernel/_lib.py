@@ -63,6 +63,12 @@ class RouteDesc(C.Structure):
                 ("routed_scaling_factor", C.c_float), ("bias", C.c_void_p)]
 
 
+class RouteSlots(C.Structure):
+    """petit_route_slots (include/petit_amd.h)."""
+    _fields_ = [("expert_map", C.c_void_p), ("num_local_experts", C.c_uint), ("num_shared", C.c_uint), ("shared_weight", C.c_float),
+                ("shared_gate_logits", C.c_void_p)]
+
+
 class TuneParams(C.Structure):
     """petit_tune_params (include/petit_amd.h)."""
     _fields_ = [("struct_bytes", C.c_uint32), ("klass", C.c_int32), ("n_copies", C.c_uint32), ("launches", C.c_uint32),
@@ -123,6 +129,10 @@ _SIGNATURES = {
     "petit_moe_route": (C.c_int, [C.c_void_p, C.c_int] + [C.c_uint] * 3 + [C.POINTER(RouteDesc)] + [C.c_void_p] * 4),
     "petit_moe_route_align_workspace_bytes": (C.c_uint64, [C.c_uint] * 3),
     "petit_moe_route_align": (C.c_int, [C.c_void_p, C.c_int] + [C.c_uint] * 3 + [C.POINTER(RouteDesc)] + [C.c_void_p] * 8),
+    "petit_moe_route_ex": (C.c_int, [C.c_void_p, C.c_int] + [C.c_uint] * 3 + [C.POINTER(RouteDesc), C.POINTER(RouteSlots)] + [C.c_void_p] * 4),
+    "petit_moe_route_align_ex_workspace_bytes": (C.c_uint64, [C.c_uint] * 3 + [C.POINTER(RouteSlots)]),
+    "petit_moe_route_align_ex": (C.c_int, [C.c_void_p, C.c_int] + [C.c_uint] * 3 + [C.POINTER(RouteDesc), C.POINTER(RouteSlots)] +
+                                 [C.c_void_p] * 8),
     "petit_gemm_mxfp4_native": (C.c_int, [C.c_void_p] * 5 + [C.c_uint] * 3 + [C.POINTER(SolutionHints), C.c_uint64, C.POINTER(Epilogue),
                                           C.POINTER(NativeArgs), C.c_void_p, C.c_uint64, C.c_void_p]),
     "petit_nvfp4_native_image_bytes": (C.c_uint64, [C.c_uint, C.c_uint]),

@@ -155,6 +155,26 @@ def moe_route_align(router_logits, topk, scoring="softmax", renormalize=True, bi
     return (w, ids, sp, off, ti, keys) if return_keys else (w, ids, sp, off, ti)
 
 
+def _slots_args(expert_map, num_local_experts, num_shared, shared_weight, shared_gate_logits):
+    return (expert_map, -1 if num_local_experts is None else int(num_local_experts), int(num_shared), float(shared_weight), shared_gate_logits)
+
+
+def moe_route_ex(router_logits, topk, scoring="softmax", renormalize=True, bias=None, n_group=1, topk_group=1, routed_scaling_factor=1.0,
+                 return_keys=False, expert_map=None, num_local_experts=None, num_shared=0, shared_weight=1.0, shared_gate_logits=None):
+    w, ids, keys = torch.ops.petit_kernel.moe_route_ex(router_logits, int(topk), _scoring(scoring), bool(renormalize), bias, int(n_group),
+                                                       int(topk_group), float(routed_scaling_factor), bool(return_keys),
+                                                       *_slots_args(expert_map, num_local_experts, num_shared, shared_weight, shared_gate_logits))
+    return (w, ids, keys) if return_keys else (w, ids)
+
+
+def moe_route_align_ex(router_logits, topk, scoring="softmax", renormalize=True, bias=None, n_group=1, topk_group=1, routed_scaling_factor=1.0,
+                       return_keys=False, expert_map=None, num_local_experts=None, num_shared=0, shared_weight=1.0, shared_gate_logits=None):
+    w, ids, sp, off, ti, keys = torch.ops.petit_kernel.moe_route_align_ex(
+        router_logits, int(topk), _scoring(scoring), bool(renormalize), bias, int(n_group), int(topk_group), float(routed_scaling_factor),
+        bool(return_keys), *_slots_args(expert_map, num_local_experts, num_shared, shared_weight, shared_gate_logits))
+    return (w, ids, sp, off, ti, keys) if return_keys else (w, ids, sp, off, ti)
+
+
 def _native_operands(A, size_m, size_k, out_quantized):
     """What the native ops take in place of A and out_quantized: (activation tensor, a_format, a_type, out_format, 16-bit dtype)."""
     out_fmt = _quantized_format(out_quantized, "out_quantized must be None, 'mxfp8', 'mxfp6' or 'mxfp4'")

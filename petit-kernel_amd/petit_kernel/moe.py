@@ -183,7 +183,13 @@ def fp4_moe_routed(hidden: torch.Tensor, router_logits: torch.Tensor, w13: torch
     'fused') or fp4_moe_native (path 'native', with `activations`) issue after their align -- bit for bit
     fp4_moe_fused(..., *moe_route(router_logits, topk, **routing)).  router_logits [T, E] float32 / bfloat16 / float16; routing: moe_route's
     keyword arguments (scoring, renormalize, bias, n_group, topk_group, routed_scaling_factor).  Route and align are ONE launch when
-    T * topk <= 1024 (the fused layer: 4 launches; 7 above).  No host sync: capturable, and a routing is a pure function of the logits."""
+    T * topk <= 1024 (the fused layer: 4 launches; 7 above).  No host sync: capturable, and a routing is a pure function of the logits.
+
+    routing also takes moe_route's slot-list arguments (expert_map, num_local_experts, num_shared, shared_weight, shared_gate_logits): the
+    same launches on topk + num_shared slots per token.  router_logits is always [T, number of GLOBAL experts]; the weight stacks (w13 / s13 /
+    gs13 / w2 / s2 / gs2, bias13 / bias2) hold the LOCAL routed experts followed by the shared ones: router_logits.size(1) + num_shared
+    experts without an expert_map, num_local_experts + num_shared with one.  A shared expert is of the routed experts' size (a k times wider
+    one is k shared experts).  One launch for route + align when T * (topk + num_shared) <= 1024."""
     from . import moe_route_align
     if path not in ("fused", "native"):
         raise RuntimeError("path must be 'fused' or 'native'")
@@ -193,8 +199,17 @@ def fp4_moe_routed(hidden: torch.Tensor, router_logits: torch.Tensor, w13: torch
         _check_fused(kind, activation)
     else:
         _check_native(kind, activation, activations)
-    if router_logits.dim() != 2 or router_logits.size(0) != hidden.size(0) or router_logits.size(1) != gs13.numel():
-        raise RuntimeError(f"router_logits must be [{hidden.size(0)}, {gs13.numel()}] (tokens of hidden, experts of the weights)")
+    if router_logits.dim() != 2 or router_logits.size(0) != hidden.size(0):
+        raise RuntimeError(f"router_logits must be [{hidden.size(0)}, num_experts] (tokens of hidden)")
+    num_shared = int(routing.get("num_shared", 0))
+    if routing.get("expert_map") is None:
+        local = router_logits.size(1)
+    else:
+        given = routing.get("num_local_experts")
+        local = router_logits.size(1) if given is None or int(given) <= 0 else int(given)
+    if gs13.numel() != local + num_shared:
+        raise RuntimeError(f"the weights hold {gs13.numel()} experts, the routing names {local} local + {num_shared} shared "
+                           f"(router_logits must be [{hidden.size(0)}, {gs13.numel() - num_shared}] without an expert_map)")
     w, ids, sorted_pos, offsets, token_index = moe_route_align(router_logits, topk, **routing)
     if path == "fused":
         return _fused_after_align(hidden, w13, s13, gs13, w2, s2, gs2, w, ids, sorted_pos, offsets, token_index, kind, bias13, bias2, activation)

@@ -918,6 +918,87 @@ def moe_route_align(router_logits: torch.Tensor, topk: int, scoring: str = "soft
     return out + (keys,) if return_keys else out
 
 
+def _check_route_slots(router_logits, topk, E, expert_map, num_local_experts, num_shared, shared_gate_logits):
+    """The argument checks of the slot list of moe_route_ex / moe_route_align_ex (the same texts as csrc/torch_binding.cpp); returns (L, S)."""
+    T, S = router_logits.size(0), int(num_shared)
+    L = E if num_local_experts is None or int(num_local_experts) <= 0 else int(num_local_experts)   # (None, -1 or 0: num_experts, as the C ABI's 0)
+    _check(S >= 0 and int(topk) + S <= _lib.PETIT_MOE_MAX_TOPK, f"topk + num_shared must be in 1..{_lib.PETIT_MOE_MAX_TOPK}, got {int(topk) + S}")
+    _check(1 <= L <= E and L + S <= _lib.PETIT_MOE_MAX_EXPERTS,
+           f"num_local_experts must be in 1..num_experts with num_local_experts + num_shared <= {_lib.PETIT_MOE_MAX_EXPERTS}, got {L}")
+    if expert_map is None:
+        _check(L == E, "num_local_experts needs an expert_map")
+    else:
+        _check(expert_map.is_cuda and expert_map.device == router_logits.device and expert_map.dtype == torch.int32 and
+               expert_map.is_contiguous() and tuple(expert_map.shape) == (E,),
+               "expert_map must be a contiguous int32 [num_experts] tensor on router_logits' device")
+    if shared_gate_logits is not None:
+        _check(S >= 1, "shared_gate_logits needs num_shared >= 1")
+        _check(shared_gate_logits.is_cuda and shared_gate_logits.device == router_logits.device and
+               shared_gate_logits.dtype == router_logits.dtype and shared_gate_logits.is_contiguous() and
+               tuple(shared_gate_logits.shape) == (T, S),
+               "shared_gate_logits must be a contiguous [num_tokens, num_shared] tensor of router_logits' dtype on its device")
+    return L, S
+
+
+def _route_slots(expert_map, L, S, shared_weight, shared_gate_logits):
+    return _lib.RouteSlots(expert_map.data_ptr() if expert_map is not None else None, L, S, float(shared_weight),
+                           shared_gate_logits.data_ptr() if shared_gate_logits is not None else None)
+
+
+def moe_route_ex(router_logits: torch.Tensor, topk: int, scoring: str = "softmax", renormalize: bool = True, bias: torch.Tensor = None,
+                 n_group: int = 1, topk_group: int = 1, routed_scaling_factor: float = 1.0, return_keys: bool = False,
+                 expert_map: torch.Tensor = None, num_local_experts: int = None, num_shared: int = 0, shared_weight: float = 1.0,
+                 shared_gate_logits: torch.Tensor = None):
+    """moe_route writing the complete slot list (petit_moe_route_ex, include/petit_amd.h "The complete slot list in the route launch"):
+    topk_weights / topk_ids [T, topk + num_shared]; the routed ids through expert_map (int32 [E], global -> local, -1 when outside
+    [0, num_local_experts)), then the shared slots num_local_experts + s with weight shared_weight (* sigmoid(shared_gate_logits[t, s]))."""
+    T, E = _check_route(router_logits, topk, scoring, bias, n_group, topk_group)
+    L, S = _check_route_slots(router_logits, topk, E, expert_map, num_local_experts, num_shared, shared_gate_logits)
+    dev = router_logits.device
+    ids = torch.empty((T, int(topk) + S), dtype=torch.int32, device=dev)
+    w = torch.empty((T, int(topk) + S), dtype=torch.float32, device=dev)
+    keys = torch.empty((T, E), dtype=torch.float32, device=dev) if return_keys else None
+    desc = _route_desc(scoring, renormalize, bias, n_group, topk_group, routed_scaling_factor)
+    slots = _route_slots(expert_map, L, S, shared_weight, shared_gate_logits)
+    with torch.cuda.device(dev):
+        rc = _lib.lib.petit_moe_route_ex(_ptr(router_logits), _LOGIT_DTYPES[router_logits.dtype], T, E, int(topk), C.byref(desc), C.byref(slots),
+                                         _ptr(ids), _ptr(w), _opt_ptr(keys), _stream(router_logits))
+    _route_shape_error(rc, T, E, topk, n_group, topk_group)
+    _raise_on(rc, "moe_route_ex")
+    return (w, ids, keys) if return_keys else (w, ids)
+
+
+def moe_route_align_ex(router_logits: torch.Tensor, topk: int, scoring: str = "softmax", renormalize: bool = True, bias: torch.Tensor = None,
+                       n_group: int = 1, topk_group: int = 1, routed_scaling_factor: float = 1.0, return_keys: bool = False,
+                       expert_map: torch.Tensor = None, num_local_experts: int = None, num_shared: int = 0, shared_weight: float = 1.0,
+                       shared_gate_logits: torch.Tensor = None):
+    """moe_route_ex followed by moe_align_device(ids, num_local_experts + num_shared), bit for bit (petit_moe_route_align_ex): ONE launch when
+    T * (topk + num_shared) <= 1024, four above.  expert_offsets has num_local_experts + num_shared + 1 entries."""
+    T, E = _check_route(router_logits, topk, scoring, bias, n_group, topk_group)
+    L, S = _check_route_slots(router_logits, topk, E, expert_map, num_local_experts, num_shared, shared_gate_logits)
+    dev = router_logits.device
+    topk = int(topk)
+    n_slots = topk + S
+    ids = torch.empty((T, n_slots), dtype=torch.int32, device=dev)
+    w = torch.empty((T, n_slots), dtype=torch.float32, device=dev)
+    keys = torch.empty((T, E), dtype=torch.float32, device=dev) if return_keys else None
+    sorted_pos = torch.empty(T * n_slots, dtype=torch.int32, device=dev)
+    token_index = torch.empty(T * n_slots, dtype=torch.int32, device=dev)
+    offsets = torch.empty(L + S + 1, dtype=torch.int32, device=dev)
+    desc = _route_desc(scoring, renormalize, bias, n_group, topk_group, routed_scaling_factor)
+    slots = _route_slots(expert_map, L, S, shared_weight, shared_gate_logits)
+    ws_bytes = int(_lib.lib.petit_moe_route_align_ex_workspace_bytes(T, topk, E, C.byref(slots)))
+    ws = _scratch(ws_bytes, dev)
+    with torch.cuda.device(dev):
+        rc = _lib.lib.petit_moe_route_align_ex(_ptr(router_logits), _LOGIT_DTYPES[router_logits.dtype], T, E, topk, C.byref(desc), C.byref(slots),
+                                               _ptr(ids), _ptr(w), _opt_ptr(keys), _ptr(offsets), _ptr(sorted_pos), _ptr(token_index),
+                                               _opt_ptr(ws), _stream(router_logits))
+    _route_shape_error(rc, T, E, topk, n_group, topk_group)
+    _raise_on(rc, "moe_route_align_ex")
+    out = (w, ids, sorted_pos, offsets, token_index)
+    return out + (keys,) if return_keys else out
+
+
 def moe_resolve_solution(hints: PetitSolutionHints, num_experts: int, size_m: int, size_n: int, size_k: int, solution_id: int = -1,
                          activation=None) -> int:
     """The kernel id a MoE call with these arguments runs (petit_gemm_moe_resolve_solution, the launcher's own pick); 0 when it would be refused."""

@@ -2,7 +2,8 @@
 """tools/moe_bench.py -- the routed-expert (MoE) launch against a host loop of dense calls, on real expert shapes.
 
     python tools/moe_bench.py [--cells decode|prefill|all] [--models deepseek,qwen3,mixtral] [--iters N] [--out FILE]
-                              [--only-moe | --only-loop] [--single-expert] [--layer [--native mxfp8|mxfp6|mxfp4 | --from-logits]] [--gptoss]
+                              [--only-moe | --only-loop] [--single-expert] [--layer [--native mxfp8|mxfp6|mxfp4 | --from-logits | --shared]]
+                              [--gptoss]
 
 Per cell (model, projection, T tokens): E experts' NVFP4 weights (bf16 activations) stacked back to back, copied until the pool is >= 1 GB so
 that rotating over copies and over routings (drawn from a seed, top-k of random router logits) keeps the 256 MB Infinity Cache from serving
@@ -22,6 +23,10 @@ against the dense native call with the same id).
 (softmax + top-k + renormalise; gpt-oss: top-k, softmax over the k; DeepSeek-V3: the grouped top-k chain written out in torch_routing) followed
 by fp4_moe_fused, and (b) fp4_moe_routed.  Measured a, b, a, b in one process, both pairs reported; per cell also the number of kernels the
 routing chain of (a) launches (torch.profiler's kernel events) and saving / (that count x 1.6 .. 1.9 us).
+--layer --shared: DeepSeek-V3 with its one shared expert (of the routed experts' size), T = 1, 16, 64, 512, graph replays on one stream, measured
+a, b, a, b: (a) fp4_moe_routed(..., num_shared=1) on the 257-expert stacks -- the shared expert is slot topk of every token, in the layer's own
+launches; (b) what a caller does without it: fp4_moe_routed on the 256 routed experts, the shared expert as two dense mul_nvfp4_a16 calls
+(gate_up with fused SiLU-mul, down) on the same weights, and a torch add.
 --gptoss: the gpt-oss-20b / -120b expert block (bf16 x MXFP4, 2880 -> 3072, biases, activation="swiglu_oai"): see gptoss_cells.  The two
 models are also in the model list of the default cells (--models gpt-oss-20b,gpt-oss-120b: MXFP4 pools).
 Kernel times without launch gaps: run under `rocprofv3 --kernel-trace --stats -- python tools/moe_bench.py ...`.
@@ -341,6 +346,49 @@ def routed_layer_cells(pk, models, ts, iters):
     return cells
 
 
+SHARED_T = (1, 16, 64, 512)
+
+
+def shared_layer_cells(pk, ts, iters):
+    """--layer --shared (module docstring): a = fp4_moe_routed with num_shared=1, b = fp4_moe_routed + two dense calls + add; a, b, a, b."""
+    (n13, hid), (n2, inter), E, topk = MODELS["deepseek"]
+    g = torch.Generator(device="cuda").manual_seed(7)
+    ri = lambda *shape: torch.randint(-2 ** 31, 2 ** 31 - 1, shape, dtype=torch.int32, device="cuda", generator=g)  # noqa: E731
+    EA = E + 1                                                   # the routed experts, then the shared one
+    w13, w2 = ri(EA * n13 // 16, 2 * hid), ri(EA * n2 // 16, 2 * inter)
+    s13 = torch.randint(0x28, 0x40, (EA * n13, hid // 16), dtype=torch.uint8, device="cuda", generator=g).view(torch.float8_e4m3fn)
+    s2 = torch.randint(0x28, 0x40, (EA * n2, inter // 16), dtype=torch.uint8, device="cuda", generator=g).view(torch.float8_e4m3fn)
+    gs13, gs2 = torch.rand(EA, device="cuda") * 0.01 + 0.01, torch.rand(EA, device="cuda") * 0.01 + 0.01
+    routing = dict(ROUTING["deepseek"], bias=torch.randn(E, device="cuda", generator=g) * 0.1)
+    # the routed experts alone (the stacks' first E experts) and the shared expert's dense operands (expert E)
+    r13, rs13 = w13.view(-1)[:E * n13 * hid // 8].view(E * n13 // 16, 2 * hid), s13.view(-1)[:E * n13 * hid // 16].view(E * n13, hid // 16)
+    r2, rs2 = w2.view(-1)[:E * n2 * inter // 8].view(E * n2 // 16, 2 * inter), s2.view(-1)[:E * n2 * inter // 16].view(E * n2, inter // 16)
+    d13, ds13 = w13.view(-1)[E * n13 * hid // 8:].view(n13 // 16, 2 * hid), s13.view(-1)[E * n13 * hid // 16:].view(n13, hid // 16)
+    d2, ds2 = w2.view(-1)[E * n2 * inter // 8:].view(n2 // 16, 2 * inter), s2.view(-1)[E * n2 * inter // 16:].view(n2, inter // 16)
+    cells = []
+    for T in ts:
+        x = torch.randn(T, hid, device="cuda").to(torch.bfloat16)
+        logits = torch.randn(T, E, device="cuda", generator=g).to(torch.bfloat16)
+
+        def a():
+            return pk.fp4_moe_routed(x, logits, w13, s13, gs13, w2, s2, gs2, topk, "nvfp4", num_shared=1, **routing)
+
+        def b():
+            out = pk.fp4_moe_routed(x, logits, r13, rs13, gs13[:E], r2, rs2, gs2[:E], topk, "nvfp4", **routing)
+            h = pk.mul_nvfp4_a16(x, d13, ds13, gs13[E:], T, n13, hid, -1, activation="silu_mul")
+            return out + pk.mul_nvfp4_a16(h, d2, ds2, gs2[E:], T, n2, inter, -1)
+
+        r = {"model": "deepseek", "T": T, "E": E, "topk": topk, "num_shared": 1, "hidden": hid, "inter": inter, "fused_shared_us": [],
+             "separate_shared_us": []}
+        for _ in range(2):
+            r["fused_shared_us"].append(graph_us(a, iters))
+            r["separate_shared_us"].append(graph_us(b, iters))
+        r["saving_us"] = [y_ - x_ for x_, y_ in zip(r["fused_shared_us"], r["separate_shared_us"])]
+        print(json.dumps(r), file=sys.stderr, flush=True)
+        cells.append(r)
+    return cells
+
+
 def native_layer_cells(pk, models, ts, iters, fmt):
     """--layer --native FMT: fp4_moe_native (activations quantised to FMT) against fp4_moe_fused on the same weights: MXFP4 weights raw, NVFP4
     weights through their native images (nvfp4_native_images) -- graph replays, as layer_cells"""
@@ -496,6 +544,7 @@ def main():
     ap.add_argument("--native", default="", choices=["", "mxfp8", "mxfp6", "mxfp4"],
                     help="--layer: fp4_moe_native with these activations against fp4_moe_fused (MXFP4 raw and NVFP4 images), plus the single-expert cell")
     ap.add_argument("--from-logits", action="store_true", help="--layer: the torch routing chain + fp4_moe_fused against fp4_moe_routed")
+    ap.add_argument("--shared", action="store_true", help="--layer: DeepSeek-V3 with its shared expert as slot topk of fp4_moe_routed against separate dense calls")
     ap.add_argument("--gptoss", action="store_true", help="the gpt-oss expert block (petit_kernel.gptoss): layer, host loop, native, fused activation")
     ap.add_argument("--out", default="")
     args = ap.parse_args()
@@ -505,6 +554,9 @@ def main():
         ts = tuple(int(t) for t in args.t.split(",")) if args.t else LAYER_T
         models = [m for m in args.models.split(",") if m in MODEL_KIND] or list(MODEL_KIND)
         report["gptoss"] = gptoss_cells(pk, models, ts, args.iters)
+    elif args.layer and args.shared:
+        ts = tuple(int(t) for t in args.t.split(",")) if args.t else SHARED_T
+        report["shared_layer"] = shared_layer_cells(pk, ts, args.iters)
     elif args.layer and args.from_logits:
         ts = tuple(int(t) for t in args.t.split(",")) if args.t else LAYER_T
         models = args.models.split(",") if args.models != "deepseek,qwen3,mixtral" else ["deepseek", "qwen3", "mixtral", "gpt-oss-120b"]
