@@ -340,6 +340,8 @@ GemmPlan plan_gemm(const GemmCall &g, const Scratch &s, bool part) {
         splitk = solution_splitk(g.solution_id);
         if (splitk == 0)
             return refuse(kErrKernelShape);
+        if (splitk > 1 && workgroup_tile(entry->shape).one_slice)
+            return refuse(kErrKernelShape); // decode / mid take no K split across workgroups: what their launchers refuse, the queries refuse too
         if (act && !act_runs(*entry, splitk, restrict_))
             return refuse(kErrKernelShape); // unsplit: needs an even number of n-tiles per wave; split: a 16-bit output (the reduce pass applies SiLU-mul)
         if (!entry_allows(*entry, restrict_) || (a_format && (unsigned)entry_class(*entry) != a_format))
