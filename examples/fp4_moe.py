@@ -89,6 +89,19 @@ def main():
     err_s = (with_shared.float() - long_way).pow(2).mean().sqrt() / long_way.pow(2).mean().sqrt()
     print(f"fp4_moe_routed(num_shared=1): {topk + 1} slots per token, rms difference to routed layer + dense shared expert = {err_s:.2e}")
     assert err_s < 1e-2
+    # the native class (block-scaled MFMA, activations quantised to MXFP8: another accuracy class, for prefill) on the same packed tensors,
+    # without resident images: each launch builds the images of the experts this routing uses into its scratch.  Bit for bit the layer on
+    # images built once at load time, which would hold 6.25 more bits per weight
+    ids_dev = topk_ids.to(torch.int32).to(dev)
+    transient = petit_kernel.fp4_moe_native(x.to(dev), w13, p13, gs13.to(dev), w2, p2, gs2.to(dev), topk_w.to(dev), ids_dev, kind="nvfp4",
+                                            activations="mxfp8", transient=True)
+    i13 = petit_kernel.nvfp4_native_images(w13, p13, E, 2 * I, H)
+    i2 = petit_kernel.nvfp4_native_images(w2, p2, E, H, I)
+    resident = petit_kernel.fp4_moe_native(x.to(dev), i13, None, gs13.to(dev), i2, None, gs2.to(dev), topk_w.to(dev), ids_dev, kind="nvfp4",
+                                           activations="mxfp8")
+    assert torch.equal(transient.view(torch.int16), resident.view(torch.int16))
+    err_n = (transient.double().cpu() - ref).pow(2).mean().sqrt() / ref.pow(2).mean().sqrt()
+    print(f"fp4_moe_native(transient=True): equals the resident-image layer bit for bit; rms error / rms = {err_n:.2e} (native class)")
 
 
 if __name__ == "__main__":

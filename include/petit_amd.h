@@ -416,6 +416,17 @@ int petit_quantize_activations(void *qa, const void *a, unsigned m, unsigned k, 
  *   petit_nvfp4_native_image_host                                host twin, bit-identical (offline conversion; packed host tensors from
  *                                                                petit_repack_nvfp4_*_host)
  *   petit_nvfp4_native_image_dequant_host(out, image, K, N)      test / debug aid: out[n][k] f32 = element x 2^(scale - 127), no global scale
+ *   petit_nvfp4_native_images(images, b, scales, E, K, N, expert_offsets, m, stream)
+ *                                                                the images of E stacked experts back to back in ONE launch: expert e reads byte
+ *                                                                e N K / 2 of b and e N K / 16 of scales and writes byte
+ *                                                                e * petit_nvfp4_native_image_bytes(K, N) of images -- what petit_gemm_native_moe
+ *                                                                reads.  Shapes and alignment per expert as petit_nvfp4_native_image; E in
+ *                                                                1 .. PETIT_MOE_MAX_EXPERTS.  expert_offsets NULL: every expert.  Otherwise the
+ *                                                                device int32 [E + 1] offsets of a MoE launch over m grouped rows (never read by
+ *                                                                the host): an expert to which that launch gives no rows -- each offset clamped
+ *                                                                into [its predecessor, m], then a count of 0 -- is skipped, its region left
+ *                                                                untouched.  No host sync, no allocation: capturable.
+ *   petit_nvfp4_native_images_host                               host twin, bit-identical, the same skip; expert_offsets in HOST memory
  *
  * Running it -- two ways, same kernels:
  *   petit_gemm_nvfp4_native(c, a, image, ...)   names the image per call; solution_id = PETIT_SOLUTION_AUTO_NATIVE_MXFP8 / _MXFP6 / _MXFP4 (the
@@ -446,6 +457,10 @@ uint64_t petit_nvfp4_native_image_bytes(unsigned in_chan, unsigned out_chan);
 int petit_nvfp4_native_image(void *image, const unsigned *b, const unsigned *scales, unsigned in_chan, unsigned out_chan, void *stream);
 int petit_nvfp4_native_image_host(void *image, const unsigned *b, const unsigned *scales, unsigned in_chan, unsigned out_chan);
 int petit_nvfp4_native_image_dequant_host(float *out, const void *image, unsigned in_chan, unsigned out_chan);
+int petit_nvfp4_native_images(void *images, const void *b, const void *scales, unsigned num_experts, unsigned in_chan, unsigned out_chan,
+                              const int32_t *expert_offsets, unsigned m, void *stream);
+int petit_nvfp4_native_images_host(void *images, const void *b, const void *scales, unsigned num_experts, unsigned in_chan, unsigned out_chan,
+                                   const int32_t *expert_offsets /* host */, unsigned m);
 int petit_nvfp4_native_attach(const void *b, const void *image);
 const void *petit_nvfp4_native_attached(const void *b);
 int petit_gemm_nvfp4_native(void *c, const void *a, const void *image, const float *global_scale, unsigned m, unsigned n, unsigned k,
@@ -721,7 +736,32 @@ int petit_moe_route_align_ex(const void *router_logits, int logits_dtype, unsign
  * capturable.  The queries return 0 for a call that would be refused; the workspace query also 0 with a_format set.
  * petit_quantize_activations_rows: petit_quantize_activations of the gathered rows (layout row r from row a_row_index[r] of a [a_rows][k];
  * null: the identity, a_rows >= m), one launch; any m (no grid-row limit) below 2^32 bytes of output.
+ *
+ * Without resident images -- petit_gemm_native_moe_transient(c, a, b, scales, ...), NVFP4 experts only: b / scales are the stacked PACKED tensors,
+ * exactly what petit_gemm_fp4_fp16_moe reads.  The call builds the images of the experts that have rows into its workspace
+ * (petit_nvfp4_native_images on expert_offsets, one launch), then does what petit_gemm_native_moe does on them, all in stream order on `stream`.
+ * Nothing is registered or cached: two layers' calls may share one workspace one after the other, and a captured call reads b, scales and
+ * expert_offsets anew at every replay.  The experts then cost 4.5 bits per weight plus ONE workspace the size of the largest layer's images,
+ * shared by all layers, where resident images add 6.25 bits per weight to every layer.
+ *   workspace layout: [0, E * I) the images, I = petit_nvfp4_native_image_bytes(k, n) -- a multiple of 256 for every accepted shape (6400 bytes per
+ *       32 rows x 256 k), so expert e's image is at e * I as petit_gemm_native_moe reads it; [E * I, E * I + S) exactly what
+ *       petit_gemm_native_moe_workspace_bytes returns for the same call (0 with pre-quantised a).  The region of an expert without rows is not written.
+ *       petit_gemm_native_moe_transient_workspace_bytes returns E * I + S in 64 bits (0: the call would be refused).
+ *   refusals, all before the first launch (C and the workspace untouched, nothing enters a stream capture): PETIT_SOLUTION_AUTO and exact-class ids
+ *       PETIT_ERROR_KERNEL_SHAPE; hints->b_type MXFP4 PETIT_ERROR_BAD_ARGUMENT (MXFP4 needs no image: petit_gemm_native_moe); scales NULL
+ *       PETIT_ERROR_PROBLEM_SHAPE; b / scales not 16-byte aligned PETIT_ERROR_BAD_ARGUMENT; a workspace that is missing or below the query
+ *       PETIT_ERROR_KERNEL_SHAPE, misaligned PETIT_ERROR_BAD_ARGUMENT; every shape limit of petit_gemm_native_moe and petit_nvfp4_native_image.
+ *       m == 0 returns PETIT_OK and launches nothing.
+ *   results: bit for bit petit_gemm_native_moe with the same id on petit_nvfp4_native_images of the same tensors -- every epilogue, pre-quantised
+ *       a, out_format, the indexed A / C forms.
  */
+uint64_t petit_gemm_native_moe_transient_workspace_bytes(const petit_solution_hints *hints, unsigned num_experts, unsigned m, unsigned n, unsigned k,
+                                                         uint64_t solution_id, const petit_epilogue *epilogue, const petit_native_args *native);
+int petit_gemm_native_moe_transient(void *c, const void *a, const void *b, const void *scales, const float *global_scales,
+                                    const int32_t *expert_offsets, unsigned num_experts, unsigned m, unsigned n, unsigned k,
+                                    const int32_t *a_row_index, unsigned a_rows, const int32_t *c_row_index, unsigned c_rows,
+                                    const petit_solution_hints *hints, uint64_t solution_id, const petit_epilogue *epilogue,
+                                    const petit_native_args *native, void *workspace, uint64_t workspace_bytes, void *stream);
 uint64_t petit_gemm_native_moe_workspace_bytes(const petit_solution_hints *hints, unsigned num_experts, unsigned m, unsigned n, unsigned k,
                                                uint64_t solution_id, const petit_epilogue *epilogue, const petit_native_args *native);
 uint64_t petit_gemm_native_moe_resolve_solution(const petit_solution_hints *hints, unsigned num_experts, unsigned m, unsigned n, unsigned k,

@@ -120,6 +120,18 @@ int petit_nvfp4_native_image_host(void *image, const unsigned *b, const unsigned
         return kErrBadArgument;
     return nv6_image_host(image, b, scales, out_chan, in_chan);
 }
+int petit_nvfp4_native_images(void *images, const void *b, const void *scales, unsigned num_experts, unsigned in_chan, unsigned out_chan,
+                              const int32_t *expert_offsets, unsigned m, void *stream) {
+    if ((!images || !b || !scales || ((uintptr_t)images & 255)) && in_chan && out_chan)
+        return kErrBadArgument;
+    return nv6_images(images, b, scales, num_experts, out_chan, in_chan, expert_offsets, m, (hipStream_t)stream);
+}
+int petit_nvfp4_native_images_host(void *images, const void *b, const void *scales, unsigned num_experts, unsigned in_chan, unsigned out_chan,
+                                   const int32_t *expert_offsets, unsigned m) {
+    if ((!images || !b || !scales) && in_chan && out_chan)
+        return kErrBadArgument;
+    return nv6_images_host(images, b, scales, num_experts, out_chan, in_chan, expert_offsets, m);
+}
 int petit_nvfp4_native_image_dequant_host(float *out, const void *image, unsigned in_chan, unsigned out_chan) {
     if ((!out || !image) && in_chan && out_chan)
         return kErrBadArgument;

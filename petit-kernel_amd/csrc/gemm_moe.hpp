@@ -13,7 +13,9 @@
 // expert's first row, as a dense call's start at row 0).
 //
 // Robustness: every offset is clamped into [offsets[e-1], m] (offsets[-1] := 0) before use -- a running maximum, then
-// min(., m) -- so malformed offsets can only leave rows unwritten, never read or write out of bounds.
+// min(., m) -- so malformed offsets can only leave rows unwritten, never read or write out of bounds.  The same rule decides which experts
+// the NVFP4 image builder skips (moe_expert_rows, petit_internal.h, used by nvnative.hip): moe_locate below and that function are its two
+// statements, and must change together.
 //
 // Indexed forms (petit_gemm_fp4_fp16_moe_ex; the *_idx_kernel templates below, instantiated by the gemm_moe_idx_<family> TUs): grouped
 // row r reads A row a_idx[r] and writes C row c_idx[r] (device_common.hpp RowIndex), so the layer needs no gathered copy of the

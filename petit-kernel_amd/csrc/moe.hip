@@ -143,6 +143,62 @@ int native_moe_plan(const petit_solution_hints *hints, unsigned num_experts, uns
     return kOk;
 }
 
+// The launch behind petit_gemm_native_moe and petit_gemm_native_moe_transient.  transient (NVFP4 only): b / scales are the stacked PACKED tensors;
+// the images of the experts with rows are built into [0, E x nv6_image_bytes) of the workspace first (nv6_images on expert_offsets), the call's own
+// scratch follows them, and the launch reads the workspace as its images.  Every refusal comes before the first launch.
+int native_moe_run(void *c, const void *a, const void *b, const void *scales, const float *global_scales, const int32_t *expert_offsets,
+                   unsigned num_experts, unsigned m, unsigned n, unsigned k, const int32_t *a_row_index, unsigned a_rows, const int32_t *c_row_index,
+                   unsigned c_rows, const petit_solution_hints *hints, uint64_t solution_id, const petit_epilogue *epilogue,
+                   const petit_native_args *native, void *workspace, uint64_t workspace_bytes, void *stream, bool transient) {
+    const SolutionEntry *e;
+    Family fam;
+    bool act = false;
+    unsigned a_format = 0, out_format = 0;
+    const bool mx = hints && is_mx_type(hints->b_type);
+    if (transient && mx)
+        return kErrBadArgument; // MXFP4 experts need no image: petit_gemm_native_moe reads the packed tensors
+    if (!c || !a || !b || ((mx || transient) && !scales) || !global_scales || !expert_offsets)
+        return kErrProblemShape;
+    if (const int rc = native_moe_plan(hints, num_experts, m, n, k, a_row_index, c_row_index, solution_id, epilogue, native, &e, &fam, &act, &a_format,
+                                       &out_format))
+        return rc;
+    // a null index is the identity: the rows it would name must exist
+    if ((!a_format && !a_row_index && a_rows < m) || (!out_format && !c_row_index && c_rows < m))
+        return kErrProblemShape;
+    // 16-byte loads and stores of A / C (and of the packed tensors a transient call converts), 256-byte aligned scratch and NV6 images (as the
+    // dense native entry points)
+    if (((uintptr_t)a & 15) || ((uintptr_t)c & 15) || ((uintptr_t)workspace & 255) || (!workspace && workspace_bytes) ||
+        (!mx && !transient && ((uintptr_t)b & 255)) || (transient && (((uintptr_t)b & 15) || ((uintptr_t)scales & 15))))
+        return kErrBadArgument;
+    if (m == 0)
+        return kOk;
+    const int klass = entry_class(*e);
+    // (the image of every accepted shape is a multiple of 256 bytes -- 6400 per 32 rows x 256 k --, so images and scratch stay aligned)
+    const uint64_t images_bytes = transient ? (uint64_t)num_experts * nv6_image_bytes(n, k) : 0;
+    const uint64_t need = images_bytes + (a_format ? 0 : qact_bytes(klass, m, k));
+    if (need && (!workspace || workspace_bytes < need))
+        return kErrKernelShape; // (as the dense native entry points: scratch below the query)
+    void *const scratch = (char *)workspace + images_bytes;
+    if (transient) {
+        if (const int rc = nv6_images(workspace, b, scales, num_experts, n, k, expert_offsets, m, (hipStream_t)stream))
+            return rc;
+        b = workspace;
+    }
+    const void *qa = a;
+    if (!a_format) {
+        const int rc = hints->a_type == kDataTypeBf16 ? quantize32_rows_bf16(a, a_row_index, a_rows, scratch, m, k, klass, (hipStream_t)stream)
+                                                      : quantize32_rows_f16(a, a_row_index, a_rows, scratch, m, k, klass, (hipStream_t)stream);
+        if (rc)
+            return rc;
+        qa = scratch;
+    }
+    MoeArgs g{};
+    g.c = c, g.a = qa, g.w = b, g.s = mx ? scales : nullptr, g.gs = global_scales, g.bias = epilogue ? epilogue->bias : nullptr, g.act = act ? (unsigned)epilogue->activation : 0u;
+    g.offsets = expert_offsets, g.num_experts = num_experts, g.m = m, g.n = n, g.k = k;
+    g.c_idx = c_row_index, g.c_rows = c_row_index ? c_rows : m, g.out_format = out_format;
+    return e->launch_moe_native(g, moe_geometry(*e, m, n, k), (hipStream_t)stream);
+}
+
 } // namespace
 
 extern "C" {
@@ -173,40 +229,30 @@ int petit_gemm_native_moe(void *c, const void *a, const void *b, const void *sca
                           unsigned num_experts, unsigned m, unsigned n, unsigned k, const int32_t *a_row_index, unsigned a_rows,
                           const int32_t *c_row_index, unsigned c_rows, const petit_solution_hints *hints, uint64_t solution_id,
                           const petit_epilogue *epilogue, const petit_native_args *native, void *workspace, uint64_t workspace_bytes, void *stream) {
+    return native_moe_run(c, a, b, scales, global_scales, expert_offsets, num_experts, m, n, k, a_row_index, a_rows, c_row_index, c_rows, hints,
+                          solution_id, epilogue, native, workspace, workspace_bytes, stream, false);
+}
+
+uint64_t petit_gemm_native_moe_transient_workspace_bytes(const petit_solution_hints *hints, unsigned num_experts, unsigned m, unsigned n, unsigned k,
+                                                         uint64_t solution_id, const petit_epilogue *epilogue, const petit_native_args *native) {
     const SolutionEntry *e;
     Family fam;
     bool act = false;
     unsigned a_format = 0, out_format = 0;
-    const bool mx = hints && is_mx_type(hints->b_type);
-    if (!c || !a || !b || (mx && !scales) || !global_scales || !expert_offsets)
-        return kErrProblemShape;
-    if (const int rc = native_moe_plan(hints, num_experts, m, n, k, a_row_index, c_row_index, solution_id, epilogue, native, &e, &fam, &act, &a_format,
-                                       &out_format))
-        return rc;
-    // a null index is the identity: the rows it would name must exist
-    if ((!a_format && !a_row_index && a_rows < m) || (!out_format && !c_row_index && c_rows < m))
-        return kErrProblemShape;
-    // 16-byte loads and stores of A / C, 256-byte aligned scratch and NV6 images (as the dense native entry points)
-    if (((uintptr_t)a & 15) || ((uintptr_t)c & 15) || ((uintptr_t)workspace & 255) || (!workspace && workspace_bytes) || (!mx && ((uintptr_t)b & 255)))
-        return kErrBadArgument;
-    if (m == 0)
-        return kOk;
-    const int klass = entry_class(*e);
-    const void *qa = a;
-    if (!a_format) {
-        if (!workspace || workspace_bytes < qact_bytes(klass, m, k))
-            return kErrKernelShape; // (as the dense native entry points: scratch below the query)
-        const int rc = hints->a_type == kDataTypeBf16 ? quantize32_rows_bf16(a, a_row_index, a_rows, workspace, m, k, klass, (hipStream_t)stream)
-                                                      : quantize32_rows_f16(a, a_row_index, a_rows, workspace, m, k, klass, (hipStream_t)stream);
-        if (rc)
-            return rc;
-        qa = workspace;
-    }
-    MoeArgs g{};
-    g.c = c, g.a = qa, g.w = b, g.s = mx ? scales : nullptr, g.gs = global_scales, g.bias = epilogue ? epilogue->bias : nullptr, g.act = act ? (unsigned)epilogue->activation : 0u;
-    g.offsets = expert_offsets, g.num_experts = num_experts, g.m = m, g.n = n, g.k = k;
-    g.c_idx = c_row_index, g.c_rows = c_row_index ? c_rows : m, g.out_format = out_format;
-    return e->launch_moe_native(g, moe_geometry(*e, m, n, k), (hipStream_t)stream);
+    if (!hints || is_mx_type(hints->b_type))
+        return 0;
+    if (native_moe_plan(hints, num_experts, m, n, k, nullptr, nullptr, solution_id, epilogue, native, &e, &fam, &act, &a_format, &out_format) != kOk || !e)
+        return 0;
+    return (uint64_t)num_experts * nv6_image_bytes(n, k) + (a_format ? 0 : qact_bytes(entry_class(*e), m, k));
+}
+
+int petit_gemm_native_moe_transient(void *c, const void *a, const void *b, const void *scales, const float *global_scales,
+                                    const int32_t *expert_offsets, unsigned num_experts, unsigned m, unsigned n, unsigned k,
+                                    const int32_t *a_row_index, unsigned a_rows, const int32_t *c_row_index, unsigned c_rows,
+                                    const petit_solution_hints *hints, uint64_t solution_id, const petit_epilogue *epilogue,
+                                    const petit_native_args *native, void *workspace, uint64_t workspace_bytes, void *stream) {
+    return native_moe_run(c, a, b, scales, global_scales, expert_offsets, num_experts, m, n, k, a_row_index, a_rows, c_row_index, c_rows, hints,
+                          solution_id, epilogue, native, workspace, workspace_bytes, stream, true);
 }
 
 int petit_quantize_activations_rows(void *qa, const void *a, const int32_t *a_row_index, unsigned a_rows, unsigned m, unsigned k, int a_type,

@@ -168,7 +168,6 @@ __device__ __forceinline__ unsigned nv6_block(const u32x4 w, unsigned s_lo, unsi
         words[d] = nan ? 0u : (unsigned)qv[d];
     return nan ? 0xffu : sbyte;
 }
-#endif
 
 // The builder, organised around the packed layout (layout.h): one wave = one (32-row block b, span sp of KS k-tiles).  Lane l = 32 h + r owns row
 // 32 b + r and, of every k-tile of the span, the blocks g = h (image plane 0) and g = 2 + h (plane 1) -- exactly its lane of the image tile.  Its
@@ -177,75 +176,147 @@ __device__ __forceinline__ unsigned nv6_block(const u32x4 w, unsigned s_lo, unsi
 // 2 KS-byte store (the image's scale record); the planes leave as three 16-byte stores per k-tile.  Rows >= N (N % 32 == 16: the upper half of
 // the last block) read nothing and produce what the host twin writes (zero elements, scale byte 127).  Vector stores only.
 template <int KS>
-__global__ __launch_bounds__(256) void nv6_image_kernel(unsigned char *__restrict__ img, const u32x4 *__restrict__ pw, const unsigned char *__restrict__ ps,
-                                                        unsigned n, unsigned k, unsigned items) {
-#if defined(__HIP_DEVICE_COMPILE__)
+__device__ __forceinline__ void nv6_item(unsigned char *__restrict__ img, const u32x4 *__restrict__ pw, const unsigned char *__restrict__ ps, unsigned n,
+                                         unsigned k, unsigned item) {
     const unsigned lane = threadIdx.x % 64, h = lane / 32, r = lane % 32;
     const unsigned ktiles = k / kTileK, nspans = ktiles / KS;
     unsigned char *const sc = img + nv6_elem_bytes(n, k);
-    for (unsigned item = blockIdx.x * 4 + threadIdx.x / 64; item < items; item += gridDim.x * 4) {
-        const unsigned b32 = item / nspans, sp = item % nspans;
-        const unsigned row = b32 * 32 + r, nt = row / 16, rr = row % 16;
-        const bool live = row < n;
-        // packed inputs: tile (nt, kt) lane 16 g + rr (weights), record (nt, sp) lane 16 g + rr (scales), for g = h (q = 0) and g = 2 + h (q = 1)
-        unsigned rec[2][KS / 2];
-        u32x4 w[KS][2];
+    const unsigned b32 = item / nspans, sp = item % nspans;
+    const unsigned row = b32 * 32 + r, nt = row / 16, rr = row % 16;
+    const bool live = row < n;
+    // packed inputs: tile (nt, kt) lane 16 g + rr (weights), record (nt, sp) lane 16 g + rr (scales), for g = h (q = 0) and g = 2 + h (q = 1)
+    unsigned rec[2][KS / 2];
+    u32x4 w[KS][2];
+#pragma unroll
+    for (int q = 0; q < 2; ++q) {
+        const unsigned g = 2 * q + h;
+        if (live) {
+            load_rec<KS>(rec[q], ps + (((size_t)nt * nspans + sp) * 64 + g * 16 + rr) * (2 * KS));
+#pragma unroll
+            for (int t = 0; t < KS; ++t)
+                w[t][q] = pw[((size_t)nt * ktiles + sp * KS + t) * 64 + g * 16 + rr];
+        } else {
+#pragma unroll
+            for (int d = 0; d < KS / 2; ++d)
+                rec[q][d] = 0u;
+#pragma unroll
+            for (int t = 0; t < KS; ++t)
+                w[t][q] = u32x4{0u, 0u, 0u, 0u};
+        }
+    }
+    unsigned out_rec[KS / 2];
+#pragma unroll
+    for (int d = 0; d < KS / 2; ++d)
+        out_rec[d] = 0u;
+#pragma unroll
+    for (int t = 0; t < KS; ++t) {
+        unsigned words[2][6];
 #pragma unroll
         for (int q = 0; q < 2; ++q) {
-            const unsigned g = 2 * q + h;
-            if (live) {
-                load_rec<KS>(rec[q], ps + (((size_t)nt * nspans + sp) * 64 + g * 16 + rr) * (2 * KS));
-#pragma unroll
-                for (int t = 0; t < KS; ++t)
-                    w[t][q] = pw[((size_t)nt * ktiles + sp * KS + t) * 64 + g * 16 + rr];
-            } else {
-#pragma unroll
-                for (int d = 0; d < KS / 2; ++d)
-                    rec[q][d] = 0u;
-#pragma unroll
-                for (int t = 0; t < KS; ++t)
-                    w[t][q] = u32x4{0u, 0u, 0u, 0u};
-            }
+            const unsigned sw = rec[q][t / 2] >> (16 * (t % 2)); // bytes [t][0 .. 1] of the record: the block's two group scales
+            const unsigned sbyte = nv6_block(w[t][q], sw & 0xffu, (sw >> 8) & 0xffu, words[q]);
+            out_rec[(q * KS + t) / 4] |= sbyte << (8 * ((q * KS + t) % 4)); // image record byte [q][t]
         }
-        unsigned out_rec[KS / 2];
+        unsigned char *const tile = img + ((size_t)b32 * ktiles + sp * KS + t) * kNv6TileBytes + lane * 16;
+        *reinterpret_cast<u32x4 *>(tile) = u32x4{words[0][0], words[0][1], words[0][2], words[0][3]};
+        *reinterpret_cast<u32x4 *>(tile + 1024) = u32x4{words[1][0], words[1][1], words[1][2], words[1][3]};
+        *reinterpret_cast<u32x4 *>(tile + 2048) = u32x4{words[0][4], words[0][5], words[1][4], words[1][5]};
+    }
+    store_rec<KS>(sc + (((size_t)b32 * nspans + sp) * 64 + lane) * (2 * KS), out_rec);
+}
+#endif
+
+template <int KS>
+__global__ __launch_bounds__(256) void nv6_image_kernel(unsigned char *__restrict__ img, const u32x4 *__restrict__ pw, const unsigned char *__restrict__ ps,
+                                                        unsigned n, unsigned k, unsigned items) {
+#if defined(__HIP_DEVICE_COMPILE__)
+    for (unsigned item = blockIdx.x * 4 + threadIdx.x / 64; item < items; item += gridDim.x * 4)
+        nv6_item<KS>(img, pw, ps, n, k, item);
+#endif
+}
+
+// The images of E stacked experts in ONE launch (petit_nvfp4_native_images; the front of petit_gemm_native_moe_transient's workspace): the same
+// work item, the item index running over E x per_expert -- item / per_expert is the expert, whose packed slice starts n k / 2 (weights) and
+// n k / 16 (scales) bytes after its predecessor's and whose image starts nv6_image_bytes(n, k) after it: the layout gemm_moe_native.hpp reads.
+// With `offsets` (the MoE launch's expert_offsets, a device array the host never reads) an item of an expert WITHOUT ROWS returns before any load
+// or store: its image region stays as it was, and the MoE launch never reads it (its slots map to experts with rows only).  "Without rows" is
+// moe_expert_rows (petit_internal.h) == 0, the predicate of moe_locate (gemm_moe.hpp).  Its lower end is a running maximum over every earlier
+// offset, so two loads per item decide only well-formed offsets; to agree with the MoE launch on malformed ones as well, the wave keeps the
+// running maximum along its (ascending) items: each offset is loaded once per wave, 64 at a time, and reduced across the lanes.  Wave-uniform:
+// the expert of an item is, so every lane takes the same side.
+template <int KS>
+__global__ __launch_bounds__(256) void nv6_images_kernel(unsigned char *__restrict__ img, const unsigned char *__restrict__ pw,
+                                                         const unsigned char *__restrict__ ps, unsigned n, unsigned k, unsigned per_expert, unsigned items,
+                                                         const int *__restrict__ offsets, unsigned m) {
+#if defined(__HIP_DEVICE_COMPILE__)
+    const unsigned lane = threadIdx.x % 64;
+    const size_t image_bytes = nv6_image_bytes(n, k), w_bytes = (size_t)n * k / 2, s_bytes = (size_t)n * k / 16;
+    unsigned seen = 0, lo = 0; // lo = the maximum of the clamped offsets[0 .. seen - 1]
+    for (unsigned item = blockIdx.x * 4 + threadIdx.x / 64; item < items; item += gridDim.x * 4) {
+        const unsigned e = __builtin_amdgcn_readfirstlane(item / per_expert);
+        if (offsets) {
+            for (; seen <= e; seen += 64) { // (the last chunk stops at e: the lanes past it add nothing)
+                unsigned v = seen + lane <= e ? moe_offset_clamped(offsets[seen + lane], m) : 0u;
 #pragma unroll
-        for (int d = 0; d < KS / 2; ++d)
-            out_rec[d] = 0u;
-#pragma unroll
-        for (int t = 0; t < KS; ++t) {
-            unsigned words[2][6];
-#pragma unroll
-            for (int q = 0; q < 2; ++q) {
-                const unsigned sw = rec[q][t / 2] >> (16 * (t % 2)); // bytes [t][0 .. 1] of the record: the block's two group scales
-                const unsigned sbyte = nv6_block(w[t][q], sw & 0xffu, (sw >> 8) & 0xffu, words[q]);
-                out_rec[(q * KS + t) / 4] |= sbyte << (8 * ((q * KS + t) % 4)); // image record byte [q][t]
+                for (unsigned d = 32; d >= 1; d /= 2)
+                    v = max(v, (unsigned)__shfl_xor(v, d));
+                lo = max(lo, (unsigned)__builtin_amdgcn_readfirstlane(v));
             }
-            unsigned char *const tile = img + ((size_t)b32 * ktiles + sp * KS + t) * kNv6TileBytes + lane * 16;
-            *reinterpret_cast<u32x4 *>(tile) = u32x4{words[0][0], words[0][1], words[0][2], words[0][3]};
-            *reinterpret_cast<u32x4 *>(tile + 1024) = u32x4{words[1][0], words[1][1], words[1][2], words[1][3]};
-            *reinterpret_cast<u32x4 *>(tile + 2048) = u32x4{words[0][4], words[0][5], words[1][4], words[1][5]};
+            seen = e + 1;
+            if (moe_expert_rows(lo, offsets[e + 1], m) == 0)
+                continue;
         }
-        store_rec<KS>(sc + (((size_t)b32 * nspans + sp) * 64 + lane) * (2 * KS), out_rec);
+        nv6_item<KS>(img + e * image_bytes, reinterpret_cast<const u32x4 *>(pw + e * w_bytes), ps + e * s_bytes, n, k, item - e * per_expert);
     }
 #endif
 }
 
-int nv6_image(void *image, const void *pw, const void *ps, unsigned n, unsigned k, hipStream_t stream) {
-    if (n == 0 || k == 0)
-        return kOk;
+namespace {
+// the shapes the image takes (0: nothing to do)
+int nv6_shape(unsigned n, unsigned k) {
     if (n % kTileN || k % 256)
         return kErrProblemShape;
     if (nv6_elem_bytes(n, k) >= (1ull << 32))
         return kErrProblemShape; // (the kernels address the element part through one 32-bit buffer descriptor)
-    const int ks = span_tiles_for_k(k);
-    const unsigned items = (n + 31) / 32 * (k / (kTileK * ks)); // (< 2^32 / 3072: the element bytes above)
-    // a grid-stride loop over the waves' items: at most one full occupancy of the device's CUs (4 waves per workgroup, 32 waves per CU)
+    return kOk;
+}
+// a grid-stride loop over the waves' items: at most one full occupancy of the device's CUs (4 waves per workgroup, 32 waves per CU)
+unsigned nv6_blocks(unsigned items) {
     int dev = 0;
     (void)hipGetDevice(&dev);
     const unsigned cap = (unsigned)arch_info(dev).num_cus * 8u;
-    const unsigned blocks = std::min((items + 3) / 4, cap);
+    return std::min((items + 3) / 4, cap);
+}
+} // namespace
+
+int nv6_image(void *image, const void *pw, const void *ps, unsigned n, unsigned k, hipStream_t stream) {
+    if (n == 0 || k == 0)
+        return kOk;
+    if (const int rc = nv6_shape(n, k))
+        return rc;
+    const int ks = span_tiles_for_k(k);
+    const unsigned items = (n + 31) / 32 * (k / (kTileK * ks)); // (< 2^32 / 3072: the element bytes above)
     const auto kern = ks == 8 ? nv6_image_kernel<8> : ks == 4 ? nv6_image_kernel<4> : nv6_image_kernel<2>;
-    hipLaunchKernelGGL(kern, dim3(blocks), dim3(256), 0, stream, (unsigned char *)image, (const u32x4 *)pw, (const unsigned char *)ps, n, k, items);
+    hipLaunchKernelGGL(kern, dim3(nv6_blocks(items)), dim3(256), 0, stream, (unsigned char *)image, (const u32x4 *)pw, (const unsigned char *)ps, n, k,
+                       items);
+    return hipGetLastError() == hipSuccess ? kOk : kErrLaunch;
+}
+
+// E images back to back from the stacked packed tensors, one launch; offsets (device, may be null: every expert) / m: the routing skip above
+int nv6_images(void *images, const void *pw, const void *ps, unsigned num_experts, unsigned n, unsigned k, const int32_t *offsets, unsigned m,
+               hipStream_t stream) {
+    if (num_experts == 0 || num_experts > kMoeMaxExperts)
+        return kErrProblemShape;
+    if (n == 0 || k == 0 || (offsets && m == 0))
+        return kOk;
+    if (const int rc = nv6_shape(n, k))
+        return rc;
+    const int ks = span_tiles_for_k(k);
+    const unsigned per_expert = (n + 31) / 32 * (k / (kTileK * ks));
+    const unsigned items = num_experts * per_expert; // (< 2^10 x 2^32 / 3072)
+    const auto kern = ks == 8 ? nv6_images_kernel<8> : ks == 4 ? nv6_images_kernel<4> : nv6_images_kernel<2>;
+    hipLaunchKernelGGL(kern, dim3(nv6_blocks(items)), dim3(256), 0, stream, (unsigned char *)images, (const unsigned char *)pw,
+                       (const unsigned char *)ps, n, k, per_expert, items, (const int *)offsets, m);
     return hipGetLastError() == hipSuccess ? kOk : kErrLaunch;
 }
 
@@ -253,10 +324,8 @@ int nv6_image(void *image, const void *pw, const void *ps, unsigned n, unsigned 
 int nv6_image_host(void *image, const void *pw_, const void *ps_, unsigned n, unsigned k) {
     if (n == 0 || k == 0)
         return kOk;
-    if (n % kTileN || k % 256)
-        return kErrProblemShape;
-    if (nv6_elem_bytes(n, k) >= (1ull << 32))
-        return kErrProblemShape;
+    if (const int rc = nv6_shape(n, k))
+        return rc;
     unsigned char *const img = (unsigned char *)image;
     const unsigned *const pw = (const unsigned *)pw_;
     const unsigned char *const ps = (const unsigned char *)ps_;
@@ -288,6 +357,29 @@ int nv6_image_host(void *image, const void *pw_, const void *ps_, unsigned n, un
             memcpy(tile_base + 2048 + lane_img * 16 + q * 8, words + 4, 8);
             sc[nv6_scale_offset(k, row, blk)] = (unsigned char)sbyte;
         }
+    return kOk;
+}
+
+// host twin of nv6_images: the same images, the same skip (offsets: HOST memory here) -- the regions of experts without rows are not touched
+int nv6_images_host(void *images, const void *pw, const void *ps, unsigned num_experts, unsigned n, unsigned k, const int32_t *offsets, unsigned m) {
+    if (num_experts == 0 || num_experts > kMoeMaxExperts)
+        return kErrProblemShape;
+    if (n == 0 || k == 0 || (offsets && m == 0))
+        return kOk;
+    if (const int rc = nv6_shape(n, k))
+        return rc;
+    unsigned lo = offsets ? moe_offset_clamped(offsets[0], m) : 0u;
+    for (unsigned e = 0; e < num_experts; ++e) {
+        if (offsets) {
+            const unsigned rows = moe_expert_rows(lo, offsets[e + 1], m);
+            lo += rows; // (the running maximum: the clamped upper end of expert e)
+            if (rows == 0)
+                continue;
+        }
+        if (const int rc = nv6_image_host((unsigned char *)images + e * nv6_image_bytes(n, k), (const unsigned char *)pw + (size_t)e * n * k / 2,
+                                          (const unsigned char *)ps + (size_t)e * n * k / 16, n, k))
+            return rc;
+    }
     return kOk;
 }
 

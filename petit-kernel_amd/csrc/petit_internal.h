@@ -5,6 +5,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "layout.h"
+
 namespace petit_amd {
 
 // Error codes.  0/1/2 are the reference's (quantization/gemm.h:107-108);
@@ -108,6 +110,19 @@ inline unsigned moe_slots(unsigned m, unsigned bm, unsigned num_experts) {
     return slots <= 65535u ? (unsigned)slots : 0u;
 }
 
+// The rows of an expert, as every MoE launch reads malformed offsets: each offset clamped into [its predecessor's clamped value, m] -- into
+// [0, m], then a running maximum.  Stated here for the image builder's routing skip (nvnative.hip nv6_images_kernel, nv6_images_host), which
+// must skip exactly the experts the launch gives no slot; moe_locate (gemm_moe.hpp) states the same rule as a wave-wide scan of its own -- two
+// sites, change them together.  lo: the maximum of the clamped offsets[0 .. e]; raw_hi: offsets[e + 1]; the expert's upper end is lo + the result.
+PETIT_HD unsigned moe_offset_clamped(int raw, unsigned m) {
+    const unsigned v = raw > 0 ? (unsigned)raw : 0u;
+    return v < m ? v : m;
+}
+PETIT_HD unsigned moe_expert_rows(unsigned lo, int raw_hi, unsigned m) {
+    const unsigned hi = moe_offset_clamped(raw_hi, m);
+    return hi > lo ? hi - lo : 0u;
+}
+
 // dispatch.hip: the dispatcher behind every GEMM entry point, which launches what plan_gemm (dispatch.h) decides (solution_id: explicit id or one of the AUTO sentinels)
 } // namespace petit_amd
 struct petit_solution_hints;
@@ -166,6 +181,11 @@ int convert_reference_mxscales_host(void *out, const void *in, unsigned k, unsig
 int nv6_image(void *image, const void *pw, const void *ps, unsigned n, unsigned k, hipStream_t stream);
 int nv6_image_host(void *image, const void *pw, const void *ps, unsigned n, unsigned k);
 int nv6_image_dequant_host(float *out, const void *image, unsigned n, unsigned k);
+// num_experts images back to back from the stacked packed tensors, ONE launch; offsets (int32 [E + 1], may be null) / m: experts without rows
+// (moe_expert_rows == 0) are skipped, their regions untouched.  The host twin reads HOST offsets.
+int nv6_images(void *images, const void *pw, const void *ps, unsigned num_experts, unsigned n, unsigned k, const int32_t *offsets, unsigned m,
+               hipStream_t stream);
+int nv6_images_host(void *images, const void *pw, const void *ps, unsigned num_experts, unsigned n, unsigned k, const int32_t *offsets, unsigned m);
 // quantize_weights.hip: 16-bit weights [E][n][k] -> the packed tensors and one global scale per expert (include/petit_amd.h "Weight quantiser");
 // host twin, bit-identical
 uint64_t quantize_weights_workspace_bytes(int b_type, unsigned num_experts, bool gs_supplied);

@@ -65,15 +65,16 @@ void check_bias(const std::optional<at::Tensor> &bias, const at::Tensor &A, at::
 }
 
 // what the routed-expert launches share on everything but the activations' shape: the expert count, the stacked weights (packed B / s, or
-// for NVFP4 on the native class the experts' images), one global scale per expert, the E + 1 offsets
+// for NVFP4 on the native class the experts' images -- unless the call is transient and brings the packed tensors), one global scale per expert,
+// the E + 1 offsets
 void check_expert_operands(bool mx, bool native, const at::Tensor &A, const at::Tensor &B, const at::Tensor *s, const at::Tensor &global_scales,
-                           const at::Tensor &expert_offsets, int64_t E, int64_t size_n, int64_t size_k) {
+                           const at::Tensor &expert_offsets, int64_t E, int64_t size_n, int64_t size_k, bool transient = false) {
     TORCH_CHECK(E >= 1 && E <= PETIT_MOE_MAX_EXPERTS, "num_experts must be in 1..", PETIT_MOE_MAX_EXPERTS, ", got ", E);
     // (on the native class s is absent with images, and otherwise answers for itself below)
     TORCH_CHECK(A.is_cuda() && B.is_cuda() && global_scales.is_cuda() && expert_offsets.is_cuda() &&
                     (native ? A.is_contiguous() && B.is_contiguous() : s->is_cuda()),
                 "all tensors must be on GPU");
-    if (native && !mx) {
+    if (native && !mx && !transient) {
         const int64_t per = (int64_t)petit_nvfp4_native_image_bytes((unsigned)size_k, (unsigned)size_n);
         TORCH_CHECK(B.scalar_type() == at::kByte && per > 0 && B.numel() == E * per, "images do not hold num_experts native images (nvfp4_native_images)");
     } else {
@@ -533,10 +534,12 @@ at::ScalarType native_moe_dtype(const at::Tensor &A, int64_t a_format, int64_t a
     TORCH_CHECK(A.scalar_type() == at::kByte && (a_type == kCxxBf16 || a_type == kCxxFp16), "quantised activations are uint8 bytes of a bf16 / fp16 matrix");
     return a_type == kCxxBf16 ? at::kBFloat16 : at::kHalf;
 }
-at::Tensor mul_native_moe_impl(bool mx, PETIT_NATIVE_MOE_ARGS) {
+// transient (NVFP4): B / s are the stacked packed tensors, the images are built per call into the call's workspace (petit_gemm_native_moe_transient)
+// workspace (transient only): the caller's scratch instead of one from the allocator
+at::Tensor mul_native_moe_impl(bool mx, bool transient, PETIT_NATIVE_MOE_ARGS, const std::optional<at::Tensor> &workspace = std::nullopt) {
     const int64_t E = num_experts;
     const at::ScalarType dtype = native_moe_dtype(A, a_format, a_type);
-    check_expert_operands(mx, true, A, B, s.has_value() ? &*s : nullptr, global_scales, expert_offsets, E, size_n, size_k);
+    check_expert_operands(mx, true, A, B, s.has_value() ? &*s : nullptr, global_scales, expert_offsets, E, size_n, size_k, transient);
     TORCH_CHECK(size_k > 0 && (a_format || A.numel() % size_k == 0), "A must be a contiguous [a_rows, size_k] bfloat16 / float16 GPU tensor");
     if (a_format)
         TORCH_CHECK(A.numel() == (int64_t)petit_quantized_activation_bytes((unsigned)size_m, (unsigned)size_k, (int)a_format) && !a_row_index.has_value(),
@@ -555,24 +558,34 @@ at::Tensor mul_native_moe_impl(bool mx, PETIT_NATIVE_MOE_ARGS) {
     const petit_epilogue epi{bias.has_value() ? bias->data_ptr() : nullptr, (int32_t)activation, 0};
     const petit_epilogue *epi_p = (bias.has_value() || activation) ? &epi : nullptr;
     const petit_native_args na{sizeof(petit_native_args), (int32_t)a_format, (int32_t)out_format, 0};
-    const uint64_t ws_bytes = petit_gemm_native_moe_workspace_bytes(&hints, (unsigned)E, (unsigned)size_m, (unsigned)size_n, (unsigned)size_k, sid, epi_p, &na);
-    at::Tensor ws = at::empty({(int64_t)ws_bytes}, A.options().dtype(at::kByte));
-    const int rc = petit_gemm_native_moe(c.data_ptr(), A.data_ptr(), B.data_ptr(), mx ? s->data_ptr() : nullptr, (const float *)global_scales.data_ptr(),
-                                         (const int32_t *)expert_offsets.data_ptr(), (unsigned)E, (unsigned)size_m, (unsigned)size_n, (unsigned)size_k,
-                                         row_index_ptr(a_row_index), (unsigned)a_rows, row_index_ptr(c_row_index), (unsigned)c_rows, &hints, sid, epi_p, &na,
-                                         ws_bytes ? ws.data_ptr() : nullptr, ws_bytes, stream_of(A));
+    const auto query = transient ? petit_gemm_native_moe_transient_workspace_bytes : petit_gemm_native_moe_workspace_bytes;
+    const auto launch = transient ? petit_gemm_native_moe_transient : petit_gemm_native_moe;
+    const uint64_t ws_bytes = query(&hints, (unsigned)E, (unsigned)size_m, (unsigned)size_n, (unsigned)size_k, sid, epi_p, &na);
+    if (workspace.has_value())
+        TORCH_CHECK(workspace->is_cuda() && workspace->device() == A.device() && workspace->scalar_type() == at::kByte && workspace->is_contiguous() &&
+                        workspace->numel() >= (int64_t)ws_bytes,
+                    "workspace must be a contiguous uint8 tensor on A's device of at least the queried bytes");
+    at::Tensor ws = workspace.has_value() && ws_bytes ? *workspace : at::empty({(int64_t)ws_bytes}, A.options().dtype(at::kByte));
+    const int rc = launch(c.data_ptr(), A.data_ptr(), B.data_ptr(), mx || transient ? s->data_ptr() : nullptr, (const float *)global_scales.data_ptr(),
+                          (const int32_t *)expert_offsets.data_ptr(), (unsigned)E, (unsigned)size_m, (unsigned)size_n, (unsigned)size_k,
+                          row_index_ptr(a_row_index), (unsigned)a_rows, row_index_ptr(c_row_index), (unsigned)c_rows, &hints, sid, epi_p, &na,
+                          ws_bytes ? ws.data_ptr() : nullptr, ws_bytes, stream_of(A));
     if (rc != PETIT_OK)
-        check_gemm_rc(rc, mx ? "mul_mxfp4_native_moe" : "mul_nvfp4_native_moe", solution_id,
+        check_gemm_rc(rc, mx ? "mul_mxfp4_native_moe" : transient ? "mul_nvfp4_native_moe_transient" : "mul_nvfp4_native_moe", solution_id,
                       c10::str("m=", size_m, ", n=", size_n, ", k=", size_k, ", num_experts=", E, ", a_rows=", a_rows, ", c_rows=", c_rows));
     return c;
 }
 at::Tensor mul_mxfp4_native_moe(PETIT_NATIVE_MOE_ARGS) {
-    return mul_native_moe_impl(true, A, B, s, global_scales, expert_offsets, size_m, size_n, size_k, num_experts, a_row_index, c_row_index, c_rows,
+    return mul_native_moe_impl(true, false, A, B, s, global_scales, expert_offsets, size_m, size_n, size_k, num_experts, a_row_index, c_row_index, c_rows,
                                solution_id, bias, activation, a_format, a_type, out_format);
 }
 at::Tensor mul_nvfp4_native_moe(PETIT_NATIVE_MOE_ARGS) {
-    return mul_native_moe_impl(false, A, B, s, global_scales, expert_offsets, size_m, size_n, size_k, num_experts, a_row_index, c_row_index, c_rows,
+    return mul_native_moe_impl(false, false, A, B, s, global_scales, expert_offsets, size_m, size_n, size_k, num_experts, a_row_index, c_row_index, c_rows,
                                solution_id, bias, activation, a_format, a_type, out_format);
+}
+at::Tensor mul_nvfp4_native_moe_transient(PETIT_NATIVE_MOE_ARGS, const std::optional<at::Tensor> &workspace) {
+    return mul_native_moe_impl(false, true, A, B, s, global_scales, expert_offsets, size_m, size_n, size_k, num_experts, a_row_index, c_row_index, c_rows,
+                               solution_id, bias, activation, a_format, a_type, out_format, workspace);
 }
 
 // NVFP4 weights on the native class without a resident image (petit_gemm_nvfp4_native_transient): the same checks and texts as petit_kernel/ops.py
@@ -636,6 +649,9 @@ at::Tensor mul_nvfp4_native_transient_meta(PETIT_NV_TRANSIENT_ARGS) {
     return native_output(A, native_moe_dtype(A, a_format, a_type), size_m, size_m, activation ? size_n / 2 : size_n, out_format);
 }
 at::Tensor mul_native_moe_meta(PETIT_NATIVE_MOE_ARGS) {
+    return native_output(A, native_moe_dtype(A, a_format, a_type), c_rows < 0 ? size_m : c_rows, size_m, activation ? size_n / 2 : size_n, out_format);
+}
+at::Tensor mul_native_moe_transient_meta(PETIT_NATIVE_MOE_ARGS, const std::optional<at::Tensor> &) {
     return native_output(A, native_moe_dtype(A, a_format, a_type), c_rows < 0 ? size_m : c_rows, size_m, activation ? size_n / 2 : size_n, out_format);
 }
 std::tuple<at::Tensor, at::Tensor, at::Tensor> moe_align_device_meta(const at::Tensor &topk_ids, int64_t num_experts) {
@@ -705,6 +721,7 @@ TORCH_LIBRARY(petit_kernel, m) {
     "int a_format=0, int a_type=5, int out_format=0"
     m.def("mul_mxfp4_native_moe(" PETIT_NATIVE_MOE_SCHEMA ") -> Tensor");
     m.def("mul_nvfp4_native_moe(" PETIT_NATIVE_MOE_SCHEMA ") -> Tensor");
+    m.def("mul_nvfp4_native_moe_transient(" PETIT_NATIVE_MOE_SCHEMA ", Tensor? workspace=None) -> Tensor");
     m.def("mul_nvfp4_native_transient(Tensor A, Tensor B, Tensor s, Tensor global_scale, int size_m, int size_n, int size_k, int solution_id=-2, "
           "Tensor? bias=None, int activation=0, int a_format=0, int a_type=5, int out_format=0) -> Tensor");
     m.def("moe_align_device(Tensor topk_ids, int num_experts) -> (Tensor, Tensor, Tensor)");
@@ -738,6 +755,7 @@ TORCH_LIBRARY(petit_kernel, m) {
     m.impl("mul_mxfp4_a16_moe_indexed_out", &mul_mxfp4_a16_moe_indexed_out); \
     m.impl("mul_mxfp4_native_moe", &mul_mxfp4_native_moe);      \
     m.impl("mul_nvfp4_native_moe", &mul_nvfp4_native_moe);      \
+    m.impl("mul_nvfp4_native_moe_transient", &mul_nvfp4_native_moe_transient); \
     m.impl("mul_nvfp4_native_transient", &mul_nvfp4_native_transient); \
     m.impl("moe_align_device", &moe_align_device);              \
     m.impl("moe_combine", &moe_combine);                        \
@@ -763,6 +781,7 @@ TORCH_LIBRARY_IMPL(petit_kernel, Meta, m) {
     m.impl("mul_mxfp4_a16_moe_indexed_out", &mul_a16_moe_indexed_out_meta);
     m.impl("mul_mxfp4_native_moe", &mul_native_moe_meta);
     m.impl("mul_nvfp4_native_moe", &mul_native_moe_meta);
+    m.impl("mul_nvfp4_native_moe_transient", &mul_native_moe_transient_meta);
     m.impl("mul_nvfp4_native_transient", &mul_nvfp4_native_transient_meta);
     m.impl("moe_align_device", &moe_align_device_meta);
     m.impl("moe_combine", &moe_combine_meta);

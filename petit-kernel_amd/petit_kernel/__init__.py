@@ -204,6 +204,26 @@ def mul_nvfp4_native_moe(a, images: torch.Tensor, global_scales: torch.Tensor, e
                                       solution_id, bias, activation, out_quantized)
 
 
+def mul_nvfp4_native_moe_transient(a, b: torch.Tensor, s: torch.Tensor, global_scales: torch.Tensor, expert_offsets: torch.Tensor, size_m: int,
+                                   size_n: int, size_k: int, num_experts: int, a_row_index: torch.Tensor = None, c_row_index: torch.Tensor = None,
+                                   c_rows: int = None, solution_id: int = SOLUTION_AUTO_NATIVE_MXFP8, bias: torch.Tensor = None,
+                                   activation: str = None, out_quantized: str = None, workspace: torch.Tensor = None):
+    # NVFP4 experts on the native class WITHOUT resident images (include/petit_amd.h "Without resident images"): b / s are the stacked packed
+    # tensors of mul_nvfp4_a16_moe; each call builds the images of the experts that have rows into a per-call workspace (one launch) and runs on
+    # them -- bit for bit mul_nvfp4_native_moe on nvfp4_native_images(b, s, ...).  workspace: the caller's scratch instead (uint8, at least
+    # nvfp4_native_moe_transient_workspace_bytes), which several calls may share one after the other
+    return _impl.mul_nvfp4_native_moe_transient(a, b, s, global_scales, expert_offsets, size_m, size_n, size_k, num_experts, a_row_index,
+                                                c_row_index, c_rows, solution_id, bias, activation, out_quantized, workspace)
+
+
+def nvfp4_native_moe_transient_workspace_bytes(num_experts: int, size_m: int, size_n: int, size_k: int,
+                                               solution_id: int = SOLUTION_AUTO_NATIVE_MXFP8, dtype: torch.dtype = torch.bfloat16,
+                                               activation: str = None, a_format: str = None, out_quantized: str = None) -> int:
+    # the per-call workspace of mul_nvfp4_native_moe_transient: num_experts images, then the native launch's own scratch
+    return ops.nvfp4_native_moe_transient_workspace_bytes(num_experts, size_m, size_n, size_k, solution_id, dtype, activation, a_format,
+                                                          out_quantized)
+
+
 def mul_nvfp4_native_transient(a, b: torch.Tensor, s: torch.Tensor, global_scale: torch.Tensor, size_m: int, size_n: int, size_k: int,
                                solution_id: int = SOLUTION_AUTO_NATIVE_MXFP8, bias: torch.Tensor = None, activation: str = None,
                                out_quantized: str = None):
@@ -281,6 +301,8 @@ __all__ = [
     "attach_nvfp4_native",
     "mul_nvfp4_native",
     "mul_nvfp4_native_transient",
+    "mul_nvfp4_native_moe_transient",
+    "nvfp4_native_moe_transient_workspace_bytes",
     "nvfp4_native_transient_workspace_bytes",
     "QuantizedActivations",
     "SOLUTION_AUTO",

@@ -139,6 +139,8 @@ _SIGNATURES = {
     "petit_nvfp4_native_image": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint, C.c_uint, C.c_void_p]),
     "petit_nvfp4_native_image_host": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint, C.c_uint]),
     "petit_nvfp4_native_image_dequant_host": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint, C.c_uint]),
+    "petit_nvfp4_native_images": (C.c_int, [C.c_void_p] * 3 + [C.c_uint] * 3 + [C.c_void_p, C.c_uint, C.c_void_p]),
+    "petit_nvfp4_native_images_host": (C.c_int, [C.c_void_p] * 3 + [C.c_uint] * 3 + [C.c_void_p, C.c_uint]),
     "petit_quantize_weights_workspace_bytes": (C.c_uint64, [C.c_int, C.c_uint, C.c_int]),
     "petit_quantize_weights": (C.c_int, [C.c_void_p, C.c_int, C.c_int] + [C.c_uint] * 3 + [C.c_void_p] * 5 + [C.c_uint64, C.c_void_p]),
     "petit_quantize_weights_host": (C.c_int, [C.c_void_p, C.c_int, C.c_int] + [C.c_uint] * 3 + [C.c_void_p] * 4),
@@ -161,6 +163,11 @@ _SIGNATURES = {
                                                                                                          C.POINTER(NativeArgs)]),
     "petit_gemm_native_moe": (C.c_int, [C.c_void_p] * 6 + [C.c_uint] * 4 + [C.c_void_p, C.c_uint, C.c_void_p, C.c_uint] +
                               [C.POINTER(SolutionHints), C.c_uint64, C.POINTER(Epilogue), C.POINTER(NativeArgs), C.c_void_p, C.c_uint64, C.c_void_p]),
+    "petit_gemm_native_moe_transient_workspace_bytes": (C.c_uint64, [C.POINTER(SolutionHints)] + [C.c_uint] * 4 +
+                                                        [C.c_uint64, C.POINTER(Epilogue), C.POINTER(NativeArgs)]),
+    "petit_gemm_native_moe_transient": (C.c_int, [C.c_void_p] * 6 + [C.c_uint] * 4 + [C.c_void_p, C.c_uint, C.c_void_p, C.c_uint] +
+                                        [C.POINTER(SolutionHints), C.c_uint64, C.POINTER(Epilogue), C.POINTER(NativeArgs), C.c_void_p, C.c_uint64,
+                                         C.c_void_p]),
     "petit_gemm_tune": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint, C.c_uint, C.c_uint, C.POINTER(SolutionHints),
                                   C.POINTER(TuneParams), C.c_void_p, C.c_uint64, C.c_void_p, C.POINTER(C.c_uint64), C.POINTER(C.c_float)]),
     "petit_tune_reserve": (C.c_int, [C.c_void_p, C.c_uint64]),

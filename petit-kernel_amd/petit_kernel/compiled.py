@@ -183,11 +183,12 @@ def _native_operands(A, size_m, size_k, out_quantized):
 
 
 def _mul_native_moe(kind, A, B, s, global_scales, expert_offsets, size_m, size_n, size_k, num_experts, a_row_index, c_row_index, c_rows,
-                    solution_id, bias, activation, out_quantized):
+                    solution_id, bias, activation, out_quantized, transient=False, workspace=None):
     a_t, a_fmt, a_type, out_fmt, dtype = _native_operands(A, size_m, size_k, out_quantized)
-    c = getattr(torch.ops.petit_kernel, f"mul_{kind}fp4_native_moe")(a_t, B, s, global_scales, expert_offsets, size_m, size_n, size_k, num_experts,
-                                                                      a_row_index, c_row_index, -1 if c_rows is None else int(c_rows),
-                                                                      _sid(solution_id, native=True), bias, _act(activation), a_fmt, a_type, out_fmt)
+    op = getattr(torch.ops.petit_kernel, f"mul_{kind}fp4_native_moe" + ("_transient" if transient else ""))
+    extra = (workspace,) if transient else ()
+    c = op(a_t, B, s, global_scales, expert_offsets, size_m, size_n, size_k, num_experts, a_row_index, c_row_index,
+           -1 if c_rows is None else int(c_rows), _sid(solution_id, native=True), bias, _act(activation), a_fmt, a_type, out_fmt, *extra)
     return QuantizedActivations(c, size_m, size_n // 2, out_quantized, dtype) if out_fmt else c
 
 
@@ -201,6 +202,13 @@ def mul_nvfp4_native_moe(A, images, global_scales, expert_offsets, size_m, size_
                          c_rows=None, solution_id=-2, bias=None, activation=None, out_quantized=None):
     return _mul_native_moe("nv", A, images, None, global_scales, expert_offsets, size_m, size_n, size_k, num_experts, a_row_index, c_row_index,
                            c_rows, solution_id, bias, activation, out_quantized)
+
+
+def mul_nvfp4_native_moe_transient(A, B, s, global_scales, expert_offsets, size_m, size_n, size_k, num_experts, a_row_index=None,
+                                   c_row_index=None, c_rows=None, solution_id=-2, bias=None, activation=None, out_quantized=None,
+                                   workspace=None):
+    return _mul_native_moe("nv", A, B, s, global_scales, expert_offsets, size_m, size_n, size_k, num_experts, a_row_index, c_row_index, c_rows,
+                           solution_id, bias, activation, out_quantized, transient=True, workspace=workspace)
 
 
 def mul_nvfp4_native_transient(A, B, s, global_scale, size_m, size_n, size_k, solution_id=-2, bias=None, activation=None, out_quantized=None):

@@ -129,56 +129,73 @@ _NATIVE_SENTINELS = {"mxfp8": -2, "mxfp4": -3, "mxfp6": -4}   # SOLUTION_AUTO_NA
 
 def fp4_moe_native(hidden: torch.Tensor, w13: torch.Tensor, s13, gs13: torch.Tensor, w2: torch.Tensor, s2, gs2: torch.Tensor,
                    topk_weights: torch.Tensor, topk_ids: torch.Tensor, kind: str = "mxfp4", activations: str = "mxfp8", *,
-                   bias13: torch.Tensor = None, bias2: torch.Tensor = None, activation: str = "silu_mul") -> torch.Tensor:
+                   bias13: torch.Tensor = None, bias2: torch.Tensor = None, activation: str = "silu_mul", transient: bool = False) -> torch.Tensor:
     """fp4_moe_fused's layer on the NATIVE class (the block-scaled MFMA, activations quantised to `activations`: 'mxfp8', 'mxfp6' or 'mxfp4';
     petit_gemm_native_moe -- a different accuracy class than the exact layers).  kind 'mxfp4': w13 / s13 / w2 / s2 as fp4_moe_fused; kind
     'nvfp4': w13 / w2 are the experts' MFMA-native images back to back (nvfp4_native_images) and s13 / s2 are None.  Five launches (seven
     when the align needs its three-launch form): the device align, the gathering quantiser, gate_up with SiLU-mul writing the quantised
     grouped rows down reads, down scattered into slot order, the top-k combine.  bias13 / bias2 / activation: as fp4_moe; 'swiglu_oai' is
-    quantised for down from its f32 value, as SiLU-mul is.  No host sync: capturable."""
-    _check_native(kind, activation, activations)
+    quantised for down from its f32 value, as SiLU-mul is.  No host sync: capturable.
+
+    transient=True (kind 'nvfp4' only): w13 / s13 / w2 / s2 are the PACKED stacked tensors, as fp4_moe_fused takes them, and no image stays
+    resident: each of the two launches is mul_nvfp4_native_moe_transient, which first builds the images of the experts this routing uses
+    into the scratch (one more launch each).  Both launches run one after the other on ONE scratch buffer, which the layer takes from the
+    allocator for the call (the larger of the two launches' workspace queries) and releases on return: the layer holds 4.5 bits per weight
+    and, while it runs, that scratch.  Bit for bit the resident layer on nvfp4_native_images of the same tensors."""
+    _check_native(kind, activation, activations, transient)
     w, ids, sorted_pos, offsets, token_index = _align_routing(topk_weights, topk_ids, gs13.numel())
     return _native_after_align(hidden, w13, s13, gs13, w2, s2, gs2, w, ids, sorted_pos, offsets, token_index, kind, activations, bias13, bias2,
-                               activation)
+                               activation, transient)
 
 
-def _check_native(kind, activation, activations) -> None:
+def _check_native(kind, activation, activations, transient=False) -> None:
     if kind not in ("nvfp4", "mxfp4"):
         raise RuntimeError("kind must be 'nvfp4' or 'mxfp4'")
     _check_activation(activation)
     if activations not in _NATIVE_SENTINELS:
         raise RuntimeError("activations must be 'mxfp8', 'mxfp6' or 'mxfp4'")
+    if transient and kind != "nvfp4":
+        raise RuntimeError("transient=True is for kind 'nvfp4' (MXFP4 experts run on the packed tensors: there is no image to build)")
 
 
 def _native_after_align(hidden, w13, s13, gs13, w2, s2, gs2, w, ids, sorted_pos, offsets, token_index, kind, activations, bias13, bias2,
-                        activation):
+                        activation, transient=False):
     """fp4_moe_native after its align: the gathering quantiser, gate_up, down scattered into slot order, the combine."""
-    from . import moe_combine, mul_mxfp4_native_moe, mul_nvfp4_native_moe, quantize_activation_rows
+    from . import moe_combine, mul_mxfp4_native_moe, mul_nvfp4_native_moe, mul_nvfp4_native_moe_transient, quantize_activation_rows
     sid = _NATIVE_SENTINELS[activations]
     T, H = hidden.shape
     E = gs13.numel()
     m = T * ids.shape[1]
-    if kind == "mxfp4":
+    if kind == "mxfp4" or transient:                            # packed stacked tensors
         n13 = w13.numel() * w13.element_size() * 2 // (E * H)   # 2 I
         inter = n13 // 2
         n2 = _down_n(w2, E, inter, H)
-        mul, gate_up, down = mul_mxfp4_native_moe, (w13, s13, gs13), (w2, s2, gs2)
+        mul, gate_up, down = (mul_nvfp4_native_moe_transient if transient else mul_mxfp4_native_moe), (w13, s13, gs13), (w2, s2, gs2)
     else:
         n13 = w13.numel() * 32 // (E * H * 25)                  # an image holds 25 / 32 bytes per weight (6.25 bits)
         inter = n13 // 2
         n2 = H
         mul, gate_up, down = mul_nvfp4_native_moe, (w13, gs13), (w2, gs2)
     qa = quantize_activation_rows(hidden, activations, token_index)                  # grouped rows; unrouted (-1) rows are zeros
+    ws = {}
+    if transient:   # one scratch for both launches (a_format: both take quantised rows where gate_up hands them over; else down quantises)
+        from . import nvfp4_native_moe_transient_workspace_bytes as query
+        quantised = n13 % 512 == 0
+        need = max(query(E, m, n13, H, sid, hidden.dtype, activation, activations, activations if quantised else None),
+                   query(E, m, n2, inter, sid, hidden.dtype, None, activations if quantised else None, None))
+        if need:    # (0: nothing to do, or a call the launch itself refuses with its own message)
+            ws = {"workspace": torch.empty(need, dtype=torch.uint8, device=hidden.device)}
     # gate_up writes down's quantised input, grouped, where its tiles allow; else 16-bit, and down quantises it (one more launch)
     h = mul(qa, *gate_up, offsets, m, n13, H, E, solution_id=sid, bias=bias13, activation=activation,
-            out_quantized=activations if n13 % 512 == 0 else None)
-    y = mul(h, *down, offsets, m, n2, inter, E, solution_id=sid, c_row_index=sorted_pos, c_rows=m, bias=bias2)   # [m, n2], (token, slot) order
+            out_quantized=activations if n13 % 512 == 0 else None, **ws)
+    y = mul(h, *down, offsets, m, n2, inter, E, solution_id=sid, c_row_index=sorted_pos, c_rows=m, bias=bias2, **ws)   # [m, n2], (token, slot) order
     return moe_combine(y, w, ids, E)
 
 
 def fp4_moe_routed(hidden: torch.Tensor, router_logits: torch.Tensor, w13: torch.Tensor, s13, gs13: torch.Tensor, w2: torch.Tensor, s2,
                    gs2: torch.Tensor, topk: int, kind: str = "nvfp4", *, path: str = "fused", activations: str = "mxfp8",
-                   bias13: torch.Tensor = None, bias2: torch.Tensor = None, activation: str = "silu_mul", **routing) -> torch.Tensor:
+                   bias13: torch.Tensor = None, bias2: torch.Tensor = None, activation: str = "silu_mul", transient: bool = False,
+                   **routing) -> torch.Tensor:
     """The layer from the router's logits: moe_route_align(router_logits, topk, **routing), then exactly the launches fp4_moe_fused (path
     'fused') or fp4_moe_native (path 'native', with `activations`) issue after their align -- bit for bit
     fp4_moe_fused(..., *moe_route(router_logits, topk, **routing)).  router_logits [T, E] float32 / bfloat16 / float16; routing: moe_route's
@@ -189,7 +206,9 @@ def fp4_moe_routed(hidden: torch.Tensor, router_logits: torch.Tensor, w13: torch
     same launches on topk + num_shared slots per token.  router_logits is always [T, number of GLOBAL experts]; the weight stacks (w13 / s13 /
     gs13 / w2 / s2 / gs2, bias13 / bias2) hold the LOCAL routed experts followed by the shared ones: router_logits.size(1) + num_shared
     experts without an expert_map, num_local_experts + num_shared with one.  A shared expert is of the routed experts' size (a k times wider
-    one is k shared experts).  One launch for route + align when T * (topk + num_shared) <= 1024."""
+    one is k shared experts).  One launch for route + align when T * (topk + num_shared) <= 1024.
+
+    transient (path 'native', kind 'nvfp4'): fp4_moe_native's switch -- the packed tensors, no resident images."""
     from . import moe_route_align
     if path not in ("fused", "native"):
         raise RuntimeError("path must be 'fused' or 'native'")
@@ -197,8 +216,10 @@ def fp4_moe_routed(hidden: torch.Tensor, router_logits: torch.Tensor, w13: torch
         raise RuntimeError("fp4_moe_routed returns the layer's output only: call moe_route(..., return_keys=True) for the keys")
     if path == "fused":
         _check_fused(kind, activation)
+        if transient:
+            raise RuntimeError("transient=True is for path 'native'")
     else:
-        _check_native(kind, activation, activations)
+        _check_native(kind, activation, activations, transient)
     if router_logits.dim() != 2 or router_logits.size(0) != hidden.size(0):
         raise RuntimeError(f"router_logits must be [{hidden.size(0)}, num_experts] (tokens of hidden)")
     num_shared = int(routing.get("num_shared", 0))
@@ -214,4 +235,4 @@ def fp4_moe_routed(hidden: torch.Tensor, router_logits: torch.Tensor, w13: torch
     if path == "fused":
         return _fused_after_align(hidden, w13, s13, gs13, w2, s2, gs2, w, ids, sorted_pos, offsets, token_index, kind, bias13, bias2, activation)
     return _native_after_align(hidden, w13, s13, gs13, w2, s2, gs2, w, ids, sorted_pos, offsets, token_index, kind, activations, bias13, bias2,
-                               activation)
+                               activation, transient)

@@ -689,9 +689,10 @@ def mul_fp4_a16_grouped(kind: str, A: torch.Tensor, members, size_m: int, size_k
 # --- routed-expert (MoE) launch (include/petit_amd.h "Routed-expert (MoE) launch"; no counterpart in the reference) ------------------------
 
 def _check_expert_operands(kind: str, a_t, B, s, global_scales, expert_offsets, size_m, size_n, size_k, num_experts, row_indices=(),
-                           native: bool = False) -> int:
+                           native: bool = False, transient: bool = False) -> int:
     """The rules the routed-expert launches share, on everything but the activations' shape: the expert count (returned as an int), the
-    stacked weights -- packed B / s of `kind` ('nv' / 'mx'), or on the native class with kind 'nv' the experts' images --, one global scale
+    stacked weights -- packed B / s of `kind` ('nv' / 'mx'), or on the native class with kind 'nv' the experts' images (unless the call is
+    transient and brings the packed tensors) --, one global scale
     per expert, the E + 1 offsets, and int32 [size_m] row indices on the activations' device.  a_t: the activation tensor."""
     E = int(num_experts)
     _check(1 <= E <= _lib.PETIT_MOE_MAX_EXPERTS, f"num_experts must be in 1..{_lib.PETIT_MOE_MAX_EXPERTS}, got {E}")
@@ -699,7 +700,7 @@ def _check_expert_operands(kind: str, a_t, B, s, global_scales, expert_offsets, 
         _check(a_t.is_cuda and B.is_cuda and global_scales.is_cuda and expert_offsets.is_cuda and B.is_contiguous(), "all tensors must be on GPU")
     else:
         _check(a_t.is_cuda and B.is_cuda and s.is_cuda and global_scales.is_cuda and expert_offsets.is_cuda, "all tensors must be on GPU")
-    if native and kind == "nv":
+    if native and kind == "nv" and not transient:
         per = int(_lib.lib.petit_nvfp4_native_image_bytes(size_k, size_n))
         _check(B.dtype == torch.uint8 and per > 0 and B.numel() == E * per, "images do not hold num_experts native images (nvfp4_native_images)")
     else:
@@ -1039,28 +1040,29 @@ def nvfp4_native_images(B: torch.Tensor, s: torch.Tensor, num_experts: int, size
     nvfp4_native_image of its slice of the stacked packed tensors B / s (repack_nvfp4 / process_nvfp4_scales of [E * size_n, size_k])."""
     E = int(num_experts)
     _check(1 <= E <= _lib.PETIT_MOE_MAX_EXPERTS, f"num_experts must be in 1..{_lib.PETIT_MOE_MAX_EXPERTS}, got {E}")
-    wb = size_n * size_k // 2
-    sb = size_n * size_k // 16
     _check(B.is_cuda and s.is_cuda and B.is_contiguous() and s.is_contiguous(), "B and s must be contiguous GPU tensors")
     _check_packed(B, s, size_n, size_k, 16, E)
     per = int(_lib.lib.petit_nvfp4_native_image_bytes(size_k, size_n))
     _check(per > 0, f"no native image for size_n={size_n}, size_k={size_k}")
     out = torch.empty(E * per, dtype=torch.uint8, device=B.device)
-    bb, ss = B.view(torch.uint8).reshape(-1), s.view(torch.uint8).reshape(-1)
     with torch.cuda.device(B.device):
-        for e in range(E):
-            rc = _lib.lib.petit_nvfp4_native_image(_ptr(out[e * per:]), _ptr(bb[e * wb:]), _ptr(ss[e * sb:]), size_k, size_n, _stream(B))
-            _raise_on(rc, "nvfp4_native_images")
+        rc = _lib.lib.petit_nvfp4_native_images(_ptr(out), _ptr(B), _ptr(s), E, size_k, size_n, None, 0, _stream(B))
+    _raise_on(rc, "nvfp4_native_images")
     return out
 
 
 def _mul_native_moe(kind: str, A, B, s, global_scales, expert_offsets, size_m, size_n, size_k, num_experts, a_row_index=None, c_row_index=None,
-                    c_rows=None, solution_id=SOLUTION_AUTO_NATIVE_MXFP8, bias=None, activation=None, out_quantized=None):
+                    c_rows=None, solution_id=SOLUTION_AUTO_NATIVE_MXFP8, bias=None, activation=None, out_quantized=None, transient=False,
+                    workspace=None):
     """The routed-expert launch on the native class (petit_gemm_native_moe).  A: 16-bit [a_rows, size_k] (gathered through a_row_index and
     quantised by the call: two launches) or QuantizedActivations of the size_m grouped rows (one launch).  Output: 16-bit [c_rows, n_out], row
     c_row_index[r] for grouped row r (None: the identity), or with out_quantized (activation='silu_mul') QuantizedActivations of the grouped
-    [size_m, size_n / 2] rows for the next launch."""
+    [size_m, size_n / 2] rows for the next launch.  transient (kind 'nv'): petit_gemm_native_moe_transient on the packed B / s; workspace: the caller's
+    scratch for it (a 256-byte aligned uint8 tensor of at least the queried bytes) instead of one from the allocator."""
     a_t, dtype, a_fmt = _activation_operand(A, size_m, size_k)
+    fn, workspace_bytes, name = ((_lib.lib.petit_gemm_native_moe_transient, _lib.lib.petit_gemm_native_moe_transient_workspace_bytes,
+                                  "mul_nvfp4_native_moe_transient") if transient else
+                                 (_lib.lib.petit_gemm_native_moe, _lib.lib.petit_gemm_native_moe_workspace_bytes, "mul_%sfp4_native_moe" % kind))
     if a_fmt:
         _check(a_row_index is None, "quantised activations are grouped rows already: a_row_index must be None")
         a_rows = size_m
@@ -1070,7 +1072,7 @@ def _mul_native_moe(kind: str, A, B, s, global_scales, expert_offsets, size_m, s
         a_rows = A.numel() // size_k
     dev = a_t.device
     E = _check_expert_operands(kind, a_t, B, s, global_scales, expert_offsets, size_m, size_n, size_k, num_experts, (a_row_index, c_row_index),
-                               native=True)
+                               native=True, transient=transient)
     act = _activation(activation)
     out_fmt = _quantized_format(out_quantized, "out_quantized must be None, 'mxfp8', 'mxfp6' or 'mxfp4'")
     _check(not out_fmt or (act and c_row_index is None), "out_quantized needs activation='silu_mul' or 'swiglu_oai' and no c_row_index")
@@ -1081,15 +1083,17 @@ def _mul_native_moe(kind: str, A, B, s, global_scales, expert_offsets, size_m, s
     na = _lib.NativeArgs(C.sizeof(_lib.NativeArgs), a_fmt, out_fmt, 0)
     c_rows = size_m if out_fmt or c_rows is None or c_rows < 0 else int(c_rows)
     c, result = _native_output(c_rows, size_m, size_n // 2 if act else size_n, out_quantized, dtype, dev)
-    ws_bytes = int(_lib.lib.petit_gemm_native_moe_workspace_bytes(C.byref(hints), E, size_m, size_n, size_k, sid, epi, C.byref(na)))
-    ws = _scratch(ws_bytes, dev)
+    ws_bytes = int(workspace_bytes(C.byref(hints), E, size_m, size_n, size_k, sid, epi, C.byref(na)))
+    if workspace is not None:
+        _check(transient and workspace.is_cuda and workspace.device == dev and workspace.dtype == torch.uint8 and workspace.is_contiguous() and
+               workspace.numel() >= ws_bytes, "workspace must be a contiguous uint8 tensor on A's device of at least the queried bytes")
+    ws = workspace if workspace is not None and ws_bytes else _scratch(ws_bytes, dev)
     with torch.cuda.device(dev):
-        err = _lib.lib.petit_gemm_native_moe(_ptr(c), _ptr(a_t), _ptr(B), _opt_ptr(s), _ptr(global_scales), _ptr(expert_offsets), E, size_m,
-                                             size_n, size_k, _opt_ptr(a_row_index), a_rows, _opt_ptr(c_row_index), c_rows, C.byref(hints), sid,
-                                             epi, C.byref(na), _opt_ptr(ws), C.c_uint64(ws_bytes),
-                                             C.c_void_p(torch.cuda.current_stream(dev).cuda_stream))
+        err = fn(_ptr(c), _ptr(a_t), _ptr(B), _opt_ptr(s), _ptr(global_scales), _ptr(expert_offsets), E, size_m, size_n, size_k,
+                 _opt_ptr(a_row_index), a_rows, _opt_ptr(c_row_index), c_rows, C.byref(hints), sid, epi, C.byref(na), _opt_ptr(ws),
+                 C.c_uint64(ws_bytes), C.c_void_p(torch.cuda.current_stream(dev).cuda_stream))
     if err:
-        _raise_gemm(err, "mul_%sfp4_native_moe" % kind, solution_id,
+        _raise_gemm(err, name, solution_id,
                     f"m={size_m}, n={size_n}, k={size_k}, num_experts={E}, a_rows={a_rows}, c_rows={c_rows}")
     return result
 
@@ -1104,6 +1108,32 @@ def mul_nvfp4_native_moe(A, images, global_scales, expert_offsets, size_m, size_
                          c_rows=None, solution_id=SOLUTION_AUTO_NATIVE_MXFP8, bias=None, activation=None, out_quantized=None):
     return _mul_native_moe("nv", A, images, None, global_scales, expert_offsets, size_m, size_n, size_k, num_experts, a_row_index, c_row_index,
                            c_rows, solution_id, bias, activation, out_quantized)
+
+
+def mul_nvfp4_native_moe_transient(A, B, s, global_scales, expert_offsets, size_m, size_n, size_k, num_experts, a_row_index=None,
+                                   c_row_index=None, c_rows=None, solution_id=SOLUTION_AUTO_NATIVE_MXFP8, bias=None, activation=None,
+                                   out_quantized=None, workspace=None):
+    """mul_nvfp4_native_moe WITHOUT resident images (petit_gemm_native_moe_transient): B / s are the experts' stacked packed tensors, what
+    mul_nvfp4_a16_moe takes; the call builds the images of the experts that have rows into a workspace it takes from torch's caching allocator
+    (one launch), then runs the native launch on them -- or into `workspace`, a uint8 tensor of at least
+    nvfp4_native_moe_transient_workspace_bytes(...) that several calls may share one after the other.  Bit for bit mul_nvfp4_native_moe on
+    nvfp4_native_images(B, s, ...)."""
+    return _mul_native_moe("nv", A, B, s, global_scales, expert_offsets, size_m, size_n, size_k, num_experts, a_row_index, c_row_index, c_rows,
+                           solution_id, bias, activation, out_quantized, transient=True, workspace=workspace)
+
+
+def nvfp4_native_moe_transient_workspace_bytes(num_experts, size_m, size_n, size_k, solution_id=SOLUTION_AUTO_NATIVE_MXFP8, dtype=torch.bfloat16,
+                                               activation=None, a_format=None, out_quantized=None) -> int:
+    """Workspace bytes of mul_nvfp4_native_moe_transient (petit_gemm_native_moe_transient_workspace_bytes): num_experts images, then the native
+    launch's own scratch; 0 when the call would be refused.  a_format: the format of pre-quantised activations (None: 16-bit)."""
+    _activation(activation)
+    a_fmt = _quantized_format(a_format, "a_format must be None, 'mxfp8', 'mxfp6' or 'mxfp4'")
+    out_fmt = _quantized_format(out_quantized, "out_quantized must be None, 'mxfp8', 'mxfp6' or 'mxfp4'")
+    hints = _hints("nv", dtype)
+    na = _lib.NativeArgs(C.sizeof(_lib.NativeArgs), a_fmt, out_fmt, 0)
+    return int(_lib.lib.petit_gemm_native_moe_transient_workspace_bytes(C.byref(hints), int(num_experts), size_m, size_n, size_k,
+                                                                        C.c_uint64(_c_solution_id(solution_id, native_ok=True)),
+                                                                        _query_epilogue(activation), C.byref(na)))
 
 
 def native_moe_resolve_solution(hints: PetitSolutionHints, num_experts: int, size_m: int, size_n: int, size_k: int,
