@@ -2,7 +2,8 @@
 """examples/mxfp4_mlp_pipeline.py -- the round-3 extensions on one gated-MLP block with MXFP4 weights (needs an MI355X):
 
   1. exact:     bf16 activations end to end, SiLU-mul fused into gate_up's epilogue            (solution_id = -1)
-  2. pipeline:  the opt-in native FP4 class -- quantise x once, gate_up emits the quantised h, down reads it (solution_id = -4 / -2 / -3: MXFP6 / MXFP8 / MXFP4 activations)
+  2. pipeline:  the opt-in native FP4 class -- the block's RMSNorm (with the residual add) writes the quantised input in its own launch
+                (rmsnorm_quantize), gate_up emits the quantised h, down reads it (solution_id = -4 / -2 / -3: MXFP6 / MXFP8 / MXFP4 activations)
   3. grouped:   gate and up kept as two tensors, one launch for both (decode batch)              (mul_fp4_a16_grouped)
   4. tuning:    petit_kernel.tune_tensors on the layer's own tensors; solution_id = -1 uses the winner from then on
 
@@ -31,14 +32,20 @@ def main() -> None:
     b1, s1 = mx_weights(2 * inter, hidden, g, dev)        # gate_up: rows [0, inter) = gate, [inter, 2 inter) = up
     b2, s2 = mx_weights(hidden, inter, g, dev)            # down
     gs = torch.tensor([0.03], device=dev)
-    x = torch.randn((m, hidden), generator=g).bfloat16().to(dev)
+    # the block as a decoder layer has it: attention output + residual stream -> RMSNorm -> gate_up -> SiLU-mul -> down
+    attn_out = torch.randn((m, hidden), generator=g).bfloat16().to(dev)
+    resid = torch.randn((m, hidden), generator=g).bfloat16().to(dev)
+    norm_w = (1.0 + 0.1 * torch.randn(hidden, generator=g)).bfloat16().to(dev)
+    # one launch: the updated residual stream, the 16-bit normed input (only the exact path below wants it) and its quantised form
+    _, resid_new, x = pk.rmsnorm_quantize(attn_out, norm_w, 1e-6, "mxfp6", residual=resid, return_normed=True)
+    assert torch.equal(resid_new, attn_out + resid)
 
     h = pk.mul_mxfp4_a16(x, b1, s1, gs, m, 2 * inter, hidden, -1, activation="silu_mul")
     y_exact = pk.mul_mxfp4_a16(h, b2, s2, gs, m, hidden, inter, -1)
 
     # the native class, three activation formats: MXFP6 (e2m3: e4m3's mantissa at the instruction's FP4 rate) is the one to serve with
     for fmt, sentinel in (("mxfp6", pk.SOLUTION_AUTO_NATIVE_MXFP6), ("mxfp8", pk.SOLUTION_AUTO_NATIVE_MXFP8), ("mxfp4", pk.SOLUTION_AUTO_NATIVE_MXFP4)):
-        xq = pk.quantize_activations(x, fmt)
+        xq, _ = pk.rmsnorm_quantize(attn_out, norm_w, 1e-6, fmt, residual=resid)   # == quantize_activations(x, fmt), without the 16-bit round trip
         hq = pk.mul_mxfp4_native(xq, b1, s1, gs, m, 2 * inter, hidden, sentinel, activation="silu_mul", out_quantized=fmt)
         y_q = pk.mul_mxfp4_native(hq, b2, s2, gs, m, hidden, inter, sentinel)
         rel = ((y_q.float() - y_exact.float()).pow(2).mean().sqrt() / y_exact.float().pow(2).mean().sqrt()).item()

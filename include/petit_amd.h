@@ -393,6 +393,48 @@ uint64_t petit_quantized_activation_bytes(unsigned m, unsigned k, int format);
 int petit_quantize_activations(void *qa, const void *a, unsigned m, unsigned k, int a_type, int format, void *stream);
 
 /*
+ * RMSNorm into quantised activations (no counterpart in the reference).  Two of the three activation matrices a decoder layer quantises
+ * come straight out of an RMSNorm (the inputs of qkv and of gate_up).  ONE launch computes
+ *     h = x (+ residual),   y = RMSNorm(h) * (weight + weight_offset),   qa = petit_quantize_activations(y)
+ * and can also write the updated residual h and the 16-bit y: no [m][k] 16-bit hand-over between the norm and the quantiser.
+ *
+ *   x, residual, y16, residual_out   [m][k] in a_type (PETIT_DTYPE_BF16 / _FP16); residual, y16 and residual_out may be NULL
+ *   weight                           [k] in a_type
+ *   qa                               petit_quantized_activation_bytes(m, k, format) bytes, format 8 / 6 / 4 (MXFP8 / MXFP6 / MXFP4): the layout
+ *                                    petit_quantize_activations writes
+ *
+ * Arithmetic, f32 unless said otherwise; round16 = round to nearest even into a_type:
+ *   1. with a residual h = round16(f32(x) + f32(residual)) -- the unfused h = x + r in the 16-bit type; that ROUNDED h is what residual_out
+ *      receives and what the norm runs on.  Without: h = x, and residual_out must be NULL.
+ *   2. S = the sum of h^2 over the row in ONE order, the same for every format, type and k: the row is cut into 8-element columns c = 0 ..
+ *      k / 8 - 1; a column's partial is the ascending chain p = h0 h0, p = fma(h_i, h_i, p), i = 1 .. 7; thread t of 256 starts from +0 and adds the
+ *      partials of its columns t, t + 256, ... in ascending order (a thread without a column holds +0); within each group of 64 consecutive
+ *      threads s[t] = s[t] + s[t xor d] for d = 1, 2, 4, 8, 16, 32; S = ((s[0] + s[64]) + s[128]) + s[192].  Every product and sum is rounded once;
+ *      nothing fuses but the stated fma.
+ *   3. inv = 1 / sqrt(S * (1 / k) + eps): 1 / k, the product, the sum, the square root and the division each correctly rounded.
+ *   4. y = round16((f32(h) * inv) * (f32(weight) + weight_offset)): three f32 operations, ONE rounding to the 16-bit type.  weight_offset is 0
+ *      for Llama-style norms, 1 for Gemma-style.
+ *   5. qa = exactly what petit_quantize_activations produces from that 16-bit y: the fused launch is bit for bit the two-step chain on y16, and
+ *      the y16 a caller may also ask for is the same matrix (the exact tail of a row-split call or a router needs it).
+ * Every consequence is part of the contract and mirrored by the host twin: a zero row gives inv = 1 / sqrt(eps) and zero blocks with scale
+ * byte 127; a row whose squares overflow f32 (bf16 only) gives S = inf, inv = 0, y = +-0.
+ *
+ * y16 may alias x; residual_out may alias residual or x (a row is read completely before any of it is written).  qa must not overlap an input.
+ *
+ * Errors, all before any launch: PETIT_ERROR_PROBLEM_SHAPE for k % 256 != 0 (and m above 2^20, as everywhere); PETIT_ERROR_KERNEL_SHAPE for
+ * k > 16384 (the row is held in registers) and for an a_type that is not bf16 / fp16; PETIT_ERROR_BAD_ARGUMENT for an eps that is not finite or
+ * is <= 0, a weight_offset that is not finite, a null (qa, x, weight) or misaligned (16 bytes, any of the six) pointer, a residual_out without
+ * a residual, a format other than 8 / 6 / 4.  m == 0 or k == 0 returns PETIT_OK.  No allocation, no host sync, graph-capturable.
+ * petit_rmsnorm_quantize_host is the host twin (host pointers): bit-identical outputs, the same refusals.  petit_rmsnorm_inv_host writes the f32
+ * `inv` of step 3 for each of the m rows, as the twin (and so the kernel) forms it -- a test aid: y carries inv only through a 16-bit rounding.
+ */
+int petit_rmsnorm_quantize(void *qa, void *y16, void *residual_out, const void *x, const void *residual, const void *weight, float eps,
+                           float weight_offset, unsigned m, unsigned k, int a_type, int format, void *stream);
+int petit_rmsnorm_quantize_host(void *qa, void *y16, void *residual_out, const void *x, const void *residual, const void *weight, float eps,
+                                float weight_offset, unsigned m, unsigned k, int a_type, int format);
+int petit_rmsnorm_inv_host(float *inv, const void *x, const void *residual, float eps, unsigned m, unsigned k, int a_type);
+
+/*
  * NVFP4 weights on the native class (no counterpart in the reference; BASELINE north_star: "a native fp4/fp8 MFMA variant").
  *
  * NVFP4's e4m3 group-16 scales do not fit the block-scaled MFMA (one E8M0 scale per 32 k), and multiplying the e4m3 mantissa into the elements

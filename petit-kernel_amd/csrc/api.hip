@@ -257,6 +257,19 @@ int petit_quantize_activations(void *qa, const void *a, unsigned m, unsigned k, 
     return kErrKernelShape;
 }
 
+// RMSNorm into quantised activations (rmsnorm_quant.hip makes every check: the device form and its host twin refuse the same calls)
+int petit_rmsnorm_quantize(void *qa, void *y16, void *residual_out, const void *x, const void *residual, const void *weight, float eps,
+                           float weight_offset, unsigned m, unsigned k, int a_type, int format, void *stream) {
+    return rmsnorm_quantize(qa, y16, residual_out, x, residual, weight, eps, weight_offset, m, k, a_type, format, (hipStream_t)stream);
+}
+int petit_rmsnorm_quantize_host(void *qa, void *y16, void *residual_out, const void *x, const void *residual, const void *weight, float eps,
+                                float weight_offset, unsigned m, unsigned k, int a_type, int format) {
+    return rmsnorm_quantize_host(qa, y16, residual_out, x, residual, weight, eps, weight_offset, m, k, a_type, format);
+}
+int petit_rmsnorm_inv_host(float *inv, const void *x, const void *residual, float eps, unsigned m, unsigned k, int a_type) {
+    return rmsnorm_inv_host(inv, x, residual, eps, m, k, a_type);
+}
+
 uint64_t petit_gemm_workspace_bytes(const petit_solution_hints *hints, unsigned m, unsigned n, unsigned k,
                                     uint64_t solution_id) {
     return petit_gemm_workspace_bytes_ex(hints, m, n, k, solution_id, nullptr);

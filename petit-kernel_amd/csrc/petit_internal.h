@@ -193,6 +193,13 @@ int quantize_weights(const void *w, int a_type, int b_type, unsigned num_experts
                      void *out_scales, float *out_gs, void *workspace, uint64_t workspace_bytes, hipStream_t stream);
 int quantize_weights_host(const void *w, int a_type, int b_type, unsigned num_experts, unsigned n, unsigned k, const float *gs_in, void *out_b,
                           void *out_scales, float *out_gs);
+// rmsnorm_quant.hip: (residual add +) RMSNorm -> "petit-qact/1" bytes in one launch (include/petit_amd.h "RMSNorm into quantised activations");
+// host twin, bit-identical.  Both make every check of the contract.
+int rmsnorm_quantize(void *qa, void *y16, void *residual_out, const void *x, const void *residual, const void *weight, float eps,
+                     float weight_offset, unsigned m, unsigned k, int a_type, int format, hipStream_t stream);
+int rmsnorm_quantize_host(void *qa, void *y16, void *residual_out, const void *x, const void *residual, const void *weight, float eps,
+                          float weight_offset, unsigned m, unsigned k, int a_type, int format);
+int rmsnorm_inv_host(float *inv, const void *x, const void *residual, float eps, unsigned m, unsigned k, int a_type); // (test aid: f32 inv per row)
 // dequant.hip: dense expansion of packed weights (debug aid); out_kind 0 f32, 1 bf16, 2 fp16
 int dequant_packed(void *out, const void *w, const void *s, float gs, unsigned n, unsigned k, int b_type, int out_kind, hipStream_t stream);
 

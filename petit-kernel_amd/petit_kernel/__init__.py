@@ -15,7 +15,7 @@ import torch
 from . import compiled, gptoss, offline, ops, tuning
 from .gptoss import GptOssExperts, prepare_gptoss_experts
 from .moe import fp4_moe, fp4_moe_fused, fp4_moe_native, fp4_moe_routed, moe_align
-from .ops import QuantizedActivations, mul_fp4_a16_grouped, mul_mxfp4_native, quantize_activations
+from .ops import QuantizedActivations, mul_fp4_a16_grouped, mul_mxfp4_native, quantize_activations, rmsnorm_quantize
 from .ops import attach_nvfp4_native, mul_nvfp4_native, nvfp4_native_image, nvfp4_native_images
 from .tuning import tune, tune_tensors
 from .ops import SOLUTION_AUTO, SOLUTION_AUTO_NATIVE_MXFP4, SOLUTION_AUTO_NATIVE_MXFP6, SOLUTION_AUTO_NATIVE_MXFP8, PetitSolutionHints
@@ -276,6 +276,7 @@ __all__ = [
     "tune",
     "tune_tensors",
     "quantize_activations",
+    "rmsnorm_quantize",
     "mul_fp4_a16_grouped",
     "mul_nvfp4_a16_moe",
     "mul_mxfp4_a16_moe",

@@ -12,7 +12,8 @@ This is format tooling, not a CPU fallback: only the GPU kernels consume the pac
 import torch
 
 from . import _lib
-from .ops import _B_TYPES, _LAYOUT_M, _LAYOUT_N, _PACK, _a_type, _check, _quantize_operands, _quantize_outputs, _raise_on, _raise_quantize
+from .ops import _B_TYPES, _LAYOUT_M, _LAYOUT_N, _PACK, _QFORMATS, _a_type, _check, _opt_ptr, _ptr, _quantize_operands, _quantize_outputs, _raise_on
+from .ops import _raise_quantize, _rmsnorm_operands, _rmsnorm_outputs, _rmsnorm_result
 
 
 def _cpu(t: torch.Tensor, name: str) -> None:
@@ -83,6 +84,18 @@ def quantize_nvfp4_cpu(w: torch.Tensor, global_scale: torch.Tensor = None):
 def quantize_mxfp4_cpu(w: torch.Tensor):
     """CPU twin of petit_kernel.quantize_mxfp4."""
     return _quantize_weights_cpu("mx", w)
+
+
+# --- RMSNorm into quantised activations, on the CPU (include/petit_amd.h "RMSNorm into quantised activations") ----------------------------------
+
+def rmsnorm_quantize_cpu(x: torch.Tensor, weight: torch.Tensor, eps: float = 1e-6, fmt: str = "mxfp8", *, residual: torch.Tensor = None,
+                         weight_offset: float = 0.0, return_normed: bool = False, inplace_residual: bool = False):
+    """CPU twin of petit_kernel.rmsnorm_quantize (the C ABI's host twin): the same arguments on CPU tensors, the same results bit for bit."""
+    m, k = _rmsnorm_operands(x, weight, eps, fmt, residual, weight_offset, on_gpu=False)
+    qa, res_out, y16 = _rmsnorm_outputs(x, fmt, residual, return_normed, inplace_residual)
+    rc = _lib.lib.petit_rmsnorm_quantize_host(_ptr(qa), _opt_ptr(y16), _opt_ptr(res_out), _ptr(x), _opt_ptr(residual), _ptr(weight), float(eps),
+                                              float(weight_offset), m, k, _a_type(x.dtype), _QFORMATS[fmt])
+    return _rmsnorm_result(rc, "rmsnorm_quantize_cpu", x, fmt, qa, res_out, y16)
 
 
 # --- tensors already packed by the REFERENCE wheel -> this build's layout (include/petit_amd.h, petit_convert_reference_*) -----

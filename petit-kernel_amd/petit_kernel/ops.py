@@ -9,6 +9,7 @@ device memory and the current stream; the compute is libpetit_amd.so.
 from __future__ import annotations
 
 import ctypes as C
+import math
 
 import torch
 
@@ -502,6 +503,58 @@ def quantize_activations(A: torch.Tensor, fmt: str = "mxfp4") -> QuantizedActiva
         raise RuntimeError(f"Incompatible problem shape (m={m}, k={k})")
     _raise_on(rc, "quantize_activations")
     return QuantizedActivations(qa, m, k, fmt, A.dtype)
+
+
+def _rmsnorm_operands(x, weight, eps, fmt, residual, weight_offset, on_gpu: bool):
+    """The argument checks of rmsnorm_quantize and of its CPU twin, stated once -> (m, k)."""
+    where = "GPU" if on_gpu else "CPU"
+    _check(fmt in _QFORMATS, "fmt must be 'mxfp8', 'mxfp6' or 'mxfp4'")
+    _check(x.is_cuda == on_gpu and x.is_contiguous() and x.dim() == 2 and x.dtype in (torch.bfloat16, torch.float16),
+           f"x must be a contiguous 2-D bfloat16 / float16 {where} tensor")
+    m, k = x.shape
+    _check(weight.device == x.device and weight.is_contiguous() and weight.dtype == x.dtype and tuple(weight.shape) == (k,),
+           f"weight must be a contiguous [k] tensor of x's dtype on x's device (k={k})")
+    _check(residual is None or (residual.device == x.device and residual.is_contiguous() and residual.dtype == x.dtype and
+                                residual.shape == x.shape), "residual must be a contiguous tensor of x's shape and dtype on x's device")
+    _check(math.isfinite(eps) and eps > 0, "eps must be finite and positive")
+    _check(math.isfinite(weight_offset), "weight_offset must be finite")
+    return m, k
+
+
+def _rmsnorm_outputs(x, fmt, residual, return_normed, inplace_residual):
+    m, k = x.shape
+    _check(not inplace_residual or residual is not None, "inplace_residual needs a residual")
+    qa = torch.empty(int(_lib.lib.petit_quantized_activation_bytes(m, k, _QFORMATS[fmt])), dtype=torch.uint8, device=x.device)
+    res_out = None if residual is None else residual if inplace_residual else torch.empty_like(residual)
+    y16 = torch.empty_like(x) if return_normed else None
+    return qa, res_out, y16
+
+
+def _rmsnorm_result(rc, name, x, fmt, qa, res_out, y16):
+    m, k = x.shape
+    if rc == _lib.PETIT_ERROR_PROBLEM_SHAPE:
+        raise RuntimeError(f"Incompatible problem shape (m={m}, k={k})")
+    if rc == _lib.PETIT_ERROR_KERNEL_SHAPE:
+        raise RuntimeError(f"No kernel implementation for k={k} (the fused norm holds a row of at most 16384 elements).")
+    _raise_on(rc, name)
+    q = QuantizedActivations(qa, m, k, fmt, x.dtype)
+    if res_out is None and y16 is None:
+        return q
+    return (q,) + ((res_out,) if res_out is not None else ()) + ((y16,) if y16 is not None else ())
+
+
+def rmsnorm_quantize(x: torch.Tensor, weight: torch.Tensor, eps: float = 1e-6, fmt: str = "mxfp8", *, residual: torch.Tensor = None,
+                     weight_offset: float = 0.0, return_normed: bool = False, inplace_residual: bool = False):
+    """(Residual add +) RMSNorm + quantize_activations in ONE launch (include/petit_amd.h "RMSNorm into quantised activations"):
+    h = x (+ residual), y = RMSNorm(h) * (weight + weight_offset), result = quantize_activations(y, fmt) bit for bit.  Returns the
+    QuantizedActivations alone, or a tuple (q, residual_out[, y16]): the updated residual h when `residual` is given (a new tensor, or `residual`
+    itself written in place with inplace_residual=True), then the 16-bit y with return_normed=True."""
+    m, k = _rmsnorm_operands(x, weight, eps, fmt, residual, weight_offset, on_gpu=True)
+    qa, res_out, y16 = _rmsnorm_outputs(x, fmt, residual, return_normed, inplace_residual)
+    with torch.cuda.device(x.device):
+        rc = _lib.lib.petit_rmsnorm_quantize(_ptr(qa), _opt_ptr(y16), _opt_ptr(res_out), _ptr(x), _opt_ptr(residual), _ptr(weight), float(eps),
+                                             float(weight_offset), m, k, _a_type(x.dtype), _QFORMATS[fmt], _stream(x))
+    return _rmsnorm_result(rc, "rmsnorm_quantize", x, fmt, qa, res_out, y16)
 
 
 def _quantized_format(fmt, text: str) -> int:
