@@ -63,6 +63,16 @@ def main():
     same = petit_kernel.fp4_moe_fused(x.to(dev), w13, p13, gs13.to(dev), w2, p2, gs2.to(dev), rw, rids, "nvfp4")
     assert torch.equal(routed.view(torch.int16), same.view(torch.int16))
     print(f"fp4_moe_routed: equals fp4_moe_fused on moe_route's ids {tuple(rids.shape)} and weights bit for bit")
+    # the fused end: the layer's last launch also adds the residual stream, applies the NEXT block's RMSNorm and quantises its input for a
+    # native-class GEMM -- bit for bit the layer followed by rmsnorm_quantize, one launch and one [T, H] round trip less.  (For a layer whose
+    # combine is complete on this rank: with tensor or expert parallelism the all-reduce comes between the combine and the residual add.)
+    resid = torch.randn(T, H, generator=g).to(torch.bfloat16).to(dev)
+    norm_w = (1.0 + 0.1 * torch.randn(H, generator=g)).to(torch.bfloat16).to(dev)
+    q, h_next = petit_kernel.fp4_moe_routed(x.to(dev), logits, w13, p13, gs13.to(dev), w2, p2, gs2.to(dev), topk, "nvfp4", scoring="softmax",
+                                            renormalize=True, norm_weight=norm_w, norm_eps=1e-6, norm_residual=resid, norm_fmt="mxfp8")
+    q_ref, h_ref = petit_kernel.rmsnorm_quantize(routed, norm_w, 1e-6, "mxfp8", residual=resid)
+    assert torch.equal(q.data, q_ref.data) and torch.equal(h_next.view(torch.int16), h_ref.view(torch.int16))
+    print(f"fp4_moe_routed(norm_weight=...): {q} and the new residual stream, equal to the layer + rmsnorm_quantize bit for bit")
     # DeepSeek-style: sigmoid scoring with groups, and one always-on shared expert of the routed experts' size as expert E of the stacks
     # ("shared-experts fusion"): every token gets slot topk with id E and weight 1, written by the same route + align launch
     qs13, ss13 = random_nvfp4(2 * I, H, g)

@@ -427,6 +427,9 @@ int petit_quantize_activations(void *qa, const void *a, unsigned m, unsigned k, 
  * a residual, a format other than 8 / 6 / 4.  m == 0 or k == 0 returns PETIT_OK.  No allocation, no host sync, graph-capturable.
  * petit_rmsnorm_quantize_host is the host twin (host pointers): bit-identical outputs, the same refusals.  petit_rmsnorm_inv_host writes the f32
  * `inv` of step 3 for each of the m rows, as the twin (and so the kernel) forms it -- a test aid: y carries inv only through a 16-bit rounding.
+ * It refuses what petit_rmsnorm_quantize refuses for the arguments it takes (a_type, m, k > 16384, eps, a null or misaligned x / residual, a null
+ * inv), except that k need only be a multiple of 8 (PETIT_ERROR_PROBLEM_SHAPE otherwise): the sum of step 2 is defined for any k / 8, and the
+ * 16-bit-only form of petit_moe_combine_rmsnorm norms such rows.
  */
 int petit_rmsnorm_quantize(void *qa, void *y16, void *residual_out, const void *x, const void *residual, const void *weight, float eps,
                            float weight_offset, unsigned m, unsigned k, int a_type, int format, void *stream);
@@ -648,6 +651,49 @@ int petit_moe_align(const void *topk_ids, int ids_are_int64, unsigned num_tokens
                     int32_t *sorted_pos, int32_t *token_index, void *workspace, void *stream);
 int petit_moe_combine(void *out, const void *slot_out, const float *topk_weights, const void *topk_ids, int ids_are_int64, unsigned num_tokens,
                       unsigned topk, unsigned n, unsigned num_experts, int dtype, void *stream);
+
+/*
+ * Top-k combine into the norm: petit_moe_combine, the residual add, the RMSNorm and (optionally) the activation quantiser in ONE launch -- the
+ * end of a routed-expert layer and the head of the next block, without the 16-bit [num_tokens][k] matrix and the launch boundary between them.
+ *
+ *   slot_out                     [num_tokens * topk][k] in a_type (PETIT_DTYPE_BF16 / _FP16); topk_weights float32 [num_tokens][topk];
+ *                                topk_ids int32, or int64 when ids_are_int64, [num_tokens][topk]
+ *   residual, residual_out, y16  [num_tokens][k] in a_type; each may be NULL (y16 not with format 0)
+ *   weight                       [k] in a_type
+ *   format                       8 / 6 / 4 as petit_rmsnorm_quantize (qa: petit_quantized_activation_bytes(num_tokens, k, format) bytes), or
+ *                                0 = no quantised output: qa must be NULL and y16 must not be
+ *
+ * Per token t, in this order (f32 unless said otherwise; round16 = round to nearest even into a_type):
+ *   1. c = the row petit_moe_combine writes for t: acc = +0; for j = 0 .. topk-1 in order, skipping ids outside [0, num_experts),
+ *      acc = acc + f32(slot_out[t * topk + j][:]) * topk_weights[t][j], the product and the sum each rounded, nothing fused; c = round16(acc).
+ *      Slot rows of skipped entries are never read.
+ *   2. h = round16(f32(c) + f32(residual)) with a residual, else h = c.  residual_out, when given, receives h IN BOTH CASES: without a
+ *      residual it is the combined layer output itself (wider than petit_rmsnorm_quantize's rule, so a caller can still have that matrix).
+ *   3. steps 2 - 5 of "RMSNorm into quantised activations" above, word for word, on that h: the same summation order (for any k / 8: a thread
+ *      without a column holds +0), the same inv, the same single rounding into y, and qa exactly what petit_quantize_activations makes of y.
+ * Whenever the chain accepts the call (k % 256 == 0, a format, a residual when residual_out is wanted) the outputs are bit for bit those of
+ * petit_moe_combine -> petit_rmsnorm_quantize(residual = ...) on the same inputs.  With format 0 only y16 and residual_out are written, for any
+ * k % 8 == 0 (gpt-oss: 2880).  A token whose slots are all unrouted has c = +0: h = residual, or a zero row with scale bytes 127.
+ *
+ * residual_out may alias residual: a thread reads from the residual row only the columns it then writes (a lane without a column reads the
+ * weight row in its place, never the residual row).  y16, residual_out and qa must not overlap slot_out (other workgroups are still reading
+ * it) or weight; qa must not overlap any input.
+ *
+ * Errors, all before any launch: PETIT_ERROR_PROBLEM_SHAPE for k % 8 != 0, k % 256 != 0 with a format, topk == 0, num_experts outside
+ * 1..PETIT_MOE_MAX_EXPERTS, num_tokens * topk >= 2^31, num_tokens above 2^20; PETIT_ERROR_KERNEL_SHAPE for k > 16384 (the row is held in
+ * registers) and for an a_type that is not bf16 / fp16; PETIT_ERROR_BAD_ARGUMENT for an eps that is not finite or is <= 0, a weight_offset
+ * that is not finite, a null slot_out / topk_weights / topk_ids / weight, a pointer among (qa, y16, residual_out, slot_out, residual, weight)
+ * that is not 16-byte aligned, a format outside {0, 8, 6, 4}, format 0 with a qa or without a y16, a format without a qa.  num_tokens == 0 or
+ * k == 0 returns PETIT_OK.  No allocation, no host sync, graph-capturable.  petit_moe_combine_rmsnorm_host is the host twin (host pointers):
+ * bit-identical outputs on every number (a NaN accumulator gives a NaN, its payload is not pinned), the same refusals.
+ * petit_rmsnorm_inv_host takes any k % 8 == 0, so the norm of a format-0 row can be checked through it.
+ */
+int petit_moe_combine_rmsnorm(void *qa, void *y16, void *residual_out, const void *slot_out, const float *topk_weights, const void *topk_ids,
+                              int ids_are_int64, const void *residual, const void *weight, float eps, float weight_offset, unsigned num_tokens,
+                              unsigned topk, unsigned k, unsigned num_experts, int a_type, int format, void *stream);
+int petit_moe_combine_rmsnorm_host(void *qa, void *y16, void *residual_out, const void *slot_out, const float *topk_weights, const void *topk_ids,
+                                   int ids_are_int64, const void *residual, const void *weight, float eps, float weight_offset,
+                                   unsigned num_tokens, unsigned topk, unsigned k, unsigned num_experts, int a_type, int format);
 
 /*
  * Routing on the device, from the router's logits: petit_moe_route turns router_logits [num_tokens][num_experts] (contiguous; logits_dtype

@@ -270,6 +270,20 @@ int petit_rmsnorm_inv_host(float *inv, const void *x, const void *residual, floa
     return rmsnorm_inv_host(inv, x, residual, eps, m, k, a_type);
 }
 
+// MoE top-k combine + residual add + RMSNorm (+ quantise) in one launch (rmsnorm_quant.hip makes every check, for both forms)
+int petit_moe_combine_rmsnorm(void *qa, void *y16, void *residual_out, const void *slot_out, const float *topk_weights, const void *topk_ids,
+                              int ids_are_int64, const void *residual, const void *weight, float eps, float weight_offset, unsigned num_tokens,
+                              unsigned topk, unsigned k, unsigned num_experts, int a_type, int format, void *stream) {
+    return moe_combine_rmsnorm(qa, y16, residual_out, slot_out, topk_weights, topk_ids, ids_are_int64, residual, weight, eps, weight_offset,
+                               num_tokens, topk, k, num_experts, a_type, format, (hipStream_t)stream);
+}
+int petit_moe_combine_rmsnorm_host(void *qa, void *y16, void *residual_out, const void *slot_out, const float *topk_weights, const void *topk_ids,
+                                   int ids_are_int64, const void *residual, const void *weight, float eps, float weight_offset,
+                                   unsigned num_tokens, unsigned topk, unsigned k, unsigned num_experts, int a_type, int format) {
+    return moe_combine_rmsnorm_host(qa, y16, residual_out, slot_out, topk_weights, topk_ids, ids_are_int64, residual, weight, eps, weight_offset,
+                                    num_tokens, topk, k, num_experts, a_type, format);
+}
+
 uint64_t petit_gemm_workspace_bytes(const petit_solution_hints *hints, unsigned m, unsigned n, unsigned k,
                                     uint64_t solution_id) {
     return petit_gemm_workspace_bytes_ex(hints, m, n, k, solution_id, nullptr);

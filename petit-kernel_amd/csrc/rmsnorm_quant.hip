@@ -9,10 +9,14 @@
 // hardware's 32-element convert: the 16-bit y row goes through LDS once (<= 32 KiB) and is quantised as quantize_act32_fp6_kernel does.
 // The quantise-and-store code is COPIED from those two kernels, not shared with them: they compile to the device code they had.
 //
+// moe_combine_rmsnorm_kernel (include/petit_amd.h "Top-k combine into the norm") is the same row with petit_moe_combine as its front end: h comes
+// from the token's top-k slot rows instead of x.  Both kernels end in ONE device function, norm_quant_tail; its format 0 writes 16-bit outputs only.
+//
 // Host and device evaluate the same scalar helpers below; this file is compiled with floating-point contraction OFF (the pragma), so a product
 // and a sum fuse only where the code says fma, on either side.
 #include <hip/hip_runtime.h>
 
+#include <algorithm>
 #include <cmath>
 #include <cstring>
 #include <vector>
@@ -128,56 +132,28 @@ struct RmsQuantArgs {
     unsigned m, k;
 };
 
-// grid = (M): one workgroup per row.  ILP = columns per thread: K <= 2048 ILP.  Lanes whose column lies past K / 8 hold zeros and add +0 to the sum;
-// K / 8 is a multiple of 32, so the 16 lanes of a k-tile (and the 4 of a block) are masked together and every shuffle below stays among live lanes.
-template <bool BF16, int ACT, int ILP> __global__ __launch_bounds__(256) void rmsnorm_quant_kernel(const RmsQuantArgs p) {
 #if defined(__HIP_DEVICE_COMPILE__)
-    __shared__ float wave_sum[4];
-    __shared__ u32x4 y_row[ACT == 6 ? 256 * ILP : 1]; // MXFP6 only: the 16-bit y row
+// h = round16(h + r), element by element (step 1 of the contract)
+template <bool BF16, int ILP> __device__ __forceinline__ void add_residual(u32x4 (&h)[ILP], const u32x4 (&r)[ILP]) {
+#pragma unroll
+    for (int j = 0; j < ILP; ++j)
+#pragma unroll
+        for (int d = 0; d < 4; ++d) {
+            const unsigned xw = h[j][d], rw = r[j][d];
+            float x0, x1, r0, r1;
+            unpack2<BF16>(xw, x0, x1);
+            unpack2<BF16>(rw, r0, r1);
+            h[j][d] = pack2<BF16>(add_rn(x0, r0), add_rn(x1, r1));
+        }
+}
+
+// Steps 2 - 5 of the contract on a row of h held as thread t's columns t + 256 j, and every store of y16 / qa: the tail of rmsnorm_quant_kernel and
+// of moe_combine_rmsnorm_kernel, which differ only in how they come by h.  wave_sum: 4 floats of LDS; y_row: the MXFP6 row (256 ILP vectors).
+// ACT == 0 writes no quantised bytes and needs no whole k-tiles: any K / 8.
+template <bool BF16, int ACT, int ILP>
+__device__ __forceinline__ void norm_quant_tail(const RmsQuantArgs &p, const u32x4 (&h)[ILP], const u32x4 (&wv)[ILP], float *wave_sum, u32x4 *y_row) {
     const unsigned t = threadIdx.x, row = blockIdx.x, cols = p.k / 8, m = p.m;
     const size_t row_v = (size_t)row * cols;
-    const u32x4 *const x_row = reinterpret_cast<const u32x4 *>(p.x) + row_v;
-    const u32x4 *const w_row = reinterpret_cast<const u32x4 *>(p.w);
-    // every load of the row is requested before the first is used
-    u32x4 h[ILP], wv[ILP];
-#pragma unroll
-    for (int j = 0; j < ILP; ++j) {
-        const unsigned c = t + 256u * j;
-        h[j] = c < cols ? x_row[c] : u32x4{0u, 0u, 0u, 0u};
-    }
-#pragma unroll
-    for (int j = 0; j < ILP; ++j) {
-        const unsigned c = t + 256u * j;
-        wv[j] = c < cols ? w_row[c] : u32x4{0u, 0u, 0u, 0u};
-    }
-    if (p.res) { // (wave-uniform: one branch around all the residual loads, not one per load)
-        const u32x4 *const r_row = reinterpret_cast<const u32x4 *>(p.res) + row_v;
-        u32x4 r[ILP];
-#pragma unroll
-        for (int j = 0; j < ILP; ++j) {
-            const unsigned c = t + 256u * j;
-            r[j] = c < cols ? r_row[c] : u32x4{0u, 0u, 0u, 0u};
-        }
-#pragma unroll
-        for (int j = 0; j < ILP; ++j)
-#pragma unroll
-            for (int d = 0; d < 4; ++d) {
-                const unsigned xw = h[j][d], rw = r[j][d];
-                float x0, x1, r0, r1;
-                unpack2<BF16>(xw, x0, x1);
-                unpack2<BF16>(rw, r0, r1);
-                h[j][d] = pack2<BF16>(add_rn(x0, r0), add_rn(x1, r1));
-            }
-        if (p.res_out) { // a thread writes only the columns it has read: res_out may be residual or x
-            u32x4 *const o_row = reinterpret_cast<u32x4 *>(p.res_out) + row_v;
-#pragma unroll
-            for (int j = 0; j < ILP; ++j) {
-                const unsigned c = t + 256u * j;
-                if (c < cols)
-                    o_row[c] = h[j];
-            }
-        }
-    }
     // the sum of squares in the contract's order: column chains, the thread's columns ascending, butterflies 1 .. 32, the four waves ascending
     float s = 0.f;
 #pragma unroll
@@ -201,7 +177,7 @@ template <bool BF16, int ACT, int ILP> __global__ __launch_bounds__(256) void rm
 
     const unsigned row_bytes = p.k / 8 * ACT;
     unsigned char *const qa = p.qa;
-    unsigned char *const qs = p.qa + (size_t)m * row_bytes;
+    unsigned char *const qs = p.qa + (size_t)m * row_bytes; // (ACT == 0: none of the three is used)
 #pragma unroll
     for (int j = 0; j < ILP; ++j) {
         const unsigned c8 = t + 256u * j; // 8-element column
@@ -219,7 +195,7 @@ template <bool BF16, int ACT, int ILP> __global__ __launch_bounds__(256) void rm
                 (reinterpret_cast<u32x4 *>(p.y16) + row_v)[c8] = yv;
             if constexpr (ACT == 6) {
                 y_row[c8] = yv;
-            } else {
+            } else if constexpr (ACT != 0) {
                 // from here: quantize_act32_kernel's column, on the 16-bit y
                 float v[8];
 #pragma unroll
@@ -304,14 +280,224 @@ template <bool BF16, int ACT, int ILP> __global__ __launch_bounds__(256) void rm
             }
         }
     }
+}
+#endif
+
+// grid = (M): one workgroup per row.  ILP = columns per thread: K <= 2048 ILP.  Lanes whose column lies past K / 8 hold zeros and add +0 to the sum;
+// K / 8 is a multiple of 32, so the 16 lanes of a k-tile (and the 4 of a block) are masked together and every shuffle of the tail stays among live
+// lanes.
+template <bool BF16, int ACT, int ILP> __global__ __launch_bounds__(256) void rmsnorm_quant_kernel(const RmsQuantArgs p) {
+#if defined(__HIP_DEVICE_COMPILE__)
+    __shared__ float wave_sum[4];
+    __shared__ u32x4 y_row[ACT == 6 ? 256 * ILP : 1]; // MXFP6 only: the 16-bit y row
+    const unsigned t = threadIdx.x, row = blockIdx.x, cols = p.k / 8;
+    const size_t row_v = (size_t)row * cols;
+    const u32x4 *const x_row = reinterpret_cast<const u32x4 *>(p.x) + row_v;
+    const u32x4 *const w_row = reinterpret_cast<const u32x4 *>(p.w);
+    // every load of the row is requested before the first is used
+    u32x4 h[ILP], wv[ILP];
+#pragma unroll
+    for (int j = 0; j < ILP; ++j) {
+        const unsigned c = t + 256u * j;
+        h[j] = c < cols ? x_row[c] : u32x4{0u, 0u, 0u, 0u};
+    }
+#pragma unroll
+    for (int j = 0; j < ILP; ++j) {
+        const unsigned c = t + 256u * j;
+        wv[j] = c < cols ? w_row[c] : u32x4{0u, 0u, 0u, 0u};
+    }
+    if (p.res) { // (wave-uniform: one branch around all the residual loads, not one per load)
+        const u32x4 *const r_row = reinterpret_cast<const u32x4 *>(p.res) + row_v;
+        u32x4 r[ILP];
+#pragma unroll
+        for (int j = 0; j < ILP; ++j) {
+            const unsigned c = t + 256u * j;
+            r[j] = c < cols ? r_row[c] : u32x4{0u, 0u, 0u, 0u};
+        }
+        add_residual<BF16, ILP>(h, r);
+        if (p.res_out) { // a thread writes only the columns it has read: res_out may be residual or x
+            u32x4 *const o_row = reinterpret_cast<u32x4 *>(p.res_out) + row_v;
+#pragma unroll
+            for (int j = 0; j < ILP; ++j) {
+                const unsigned c = t + 256u * j;
+                if (c < cols)
+                    o_row[c] = h[j];
+            }
+        }
+    }
+    norm_quant_tail<BF16, ACT, ILP>(p, h, wv, wave_sum, y_row);
+#endif
+}
+
+// --- the MoE top-k combine as the front end of the same row (include/petit_amd.h "Top-k combine into the norm") --------------------------------------
+
+struct CombineNormArgs {
+    RmsQuantArgs n;            // x unused: the row comes from the combine; m = num_tokens
+    const void *slot;          // [num_tokens * topk][k]
+    const float *topk_weights; // [num_tokens][topk]
+    const void *ids;           // [num_tokens][topk], int32 or int64
+    unsigned i64, topk, num_experts;
+};
+
+namespace {
+
+// petit_moe_combine's rule: an id outside [0, num_experts) is not routed
+PETIT_HD bool slot_routed(const void *ids, bool i64, size_t p, unsigned num_experts) {
+    const long long v = i64 ? ((const long long *)ids)[p] : (long long)((const int *)ids)[p];
+    return v >= 0 && v < (long long)num_experts;
+}
+// the combine's one rounding of two accumulators into a dword.  bf16: the convert moe_combine_kernel uses (the integer rule of f32_h16 on every
+// number; a NaN comes out quiet with its upper payload bits, which the host spells out); fp16: f32_h16's
+template <bool BF16> PETIT_HD unsigned combine_round2(float lo, float hi) {
+    if constexpr (BF16) {
+#if defined(__HIP_DEVICE_COMPILE__)
+        return __builtin_bit_cast(unsigned, __builtin_convertvector(f32x2{lo, hi}, bf16x2));
+#else
+        const unsigned u[2] = {f32_bits(lo), f32_bits(hi)};
+        unsigned o[2];
+        for (int i = 0; i < 2; ++i)
+            o[i] = (u[i] & 0x7fffffffu) > 0x7f800000u ? (u[i] >> 16) | 0x40u : f32_h16<true>(bits_f32(u[i])) & 0xffffu;
+        return o[0] | (o[1] << 16);
+#endif
+    }
+    return pack2<false>(lo, hi);
+}
+
+} // namespace
+
+// grid = (num_tokens): one workgroup per token, the thread map of rmsnorm_quant_kernel.  Each column has 8 f32 accumulators.  The token's ids and
+// weights are read ONCE, 64 slots at a time, one per lane; a ballot turns the routed ones into a wave-uniform mask, and the slots are taken off that
+// mask in ascending order, up to kSlotDepth at a time.  A group of N slots is one straight-line piece of code (combine_slots<N>): the N x ILP 16-byte
+// loads, all unconditional, then the N x ILP accumulations in slot order -- so the loads of a group are in flight together and the sums are
+// petit_moe_combine's.  An unrouted slot never enters the mask: its row is not read.  The residual and weight loads are requested before the first
+// slot's.  A lane without a column reads column 0 of the slot rows and of the weight row in its place (no divergent branch around a load; neither
+// is written by this launch) and is set to h = +0 once, after the residual add.
+template <int ILP> constexpr int kSlotDepth = ILP >= 4 ? 2 : 8 / ILP;
+
+#if defined(__HIP_DEVICE_COMPILE__)
+// N routed slots of the token, lanes idx[0 .. N-1] of the chunk starting at `first`: every load, then every accumulation
+template <bool BF16, int ILP, int N>
+__device__ __forceinline__ void combine_slots(float (&acc)[ILP][8], const u32x4 *first, unsigned cols, const unsigned (&col)[ILP], float w_lane,
+                                              const unsigned *idx) {
+    u32x4 v[N][ILP];
+    float w[N];
+#pragma unroll
+    for (int d = 0; d < N; ++d) {
+        w[d] = bits_f32((unsigned)__builtin_amdgcn_readlane((int)f32_bits(w_lane), (int)idx[d]));
+        const u32x4 *const s_row = first + (size_t)idx[d] * cols;
+#pragma unroll
+        for (int j = 0; j < ILP; ++j)
+            v[d][j] = s_row[col[j]];
+    }
+    __builtin_amdgcn_sched_barrier(0); // the scheduler moves nothing across: no accumulation of slot 0 ahead of the loads of slot N - 1
+#pragma unroll
+    for (int d = 0; d < N; ++d)
+#pragma unroll
+        for (int j = 0; j < ILP; ++j)
+#pragma unroll
+            for (int q = 0; q < 4; ++q) {
+                const unsigned xw = v[d][j][q];
+                float x0, x1;
+                unpack2<BF16>(xw, x0, x1);
+                acc[j][2 * q] = add_rn(acc[j][2 * q], mul_rn(x0, w[d])); // product and sum each rounded: petit_moe_combine's
+                acc[j][2 * q + 1] = add_rn(acc[j][2 * q + 1], mul_rn(x1, w[d]));
+            }
+}
+// the group of n slots, 1 <= n <= N (wave-uniform): one branch to its straight-line form
+template <bool BF16, int ILP, int N>
+__device__ __forceinline__ void combine_group(int n, float (&acc)[ILP][8], const u32x4 *first, unsigned cols, const unsigned (&col)[ILP],
+                                              float w_lane, const unsigned *idx) {
+    if (n == N)
+        combine_slots<BF16, ILP, N>(acc, first, cols, col, w_lane, idx);
+    else if constexpr (N > 1)
+        combine_group<BF16, ILP, N - 1>(n, acc, first, cols, col, w_lane, idx);
+}
+#endif
+
+template <bool BF16, int ACT, int ILP> __global__ __launch_bounds__(256) void moe_combine_rmsnorm_kernel(const CombineNormArgs a) {
+#if defined(__HIP_DEVICE_COMPILE__)
+    constexpr int kDepth = kSlotDepth<ILP>;
+    __shared__ float wave_sum[4];
+    __shared__ u32x4 y_row[ACT == 6 ? 256 * ILP : 1]; // MXFP6 only: the 16-bit y row
+    const RmsQuantArgs &p = a.n;
+    const unsigned t = threadIdx.x, row = blockIdx.x, cols = p.k / 8, topk = a.topk;
+    const size_t row_v = (size_t)row * cols, p0 = (size_t)row * topk;
+    const u32x4 zero = u32x4{0u, 0u, 0u, 0u};
+    const u32x4 *const w_row = reinterpret_cast<const u32x4 *>(p.w);
+    const bool has_res = p.res != nullptr; // (wave-uniform)
+    unsigned col[ILP];
+#pragma unroll
+    for (int j = 0; j < ILP; ++j)
+        col[j] = t + 256u * j < cols ? t + 256u * j : 0u;
+    u32x4 wv[ILP], r[ILP];
+#pragma unroll
+    for (int j = 0; j < ILP; ++j)
+        wv[j] = w_row[col[j]];
+    if (has_res) { // a lane without a column reads the weight row here, not the residual row: residual_out may be residual, which another thread writes
+        const u32x4 *const r_row = reinterpret_cast<const u32x4 *>(p.res) + row_v;
+#pragma unroll
+        for (int j = 0; j < ILP; ++j)
+            r[j] = *(t + 256u * j < cols ? r_row + col[j] : w_row);
+    }
+    float acc[ILP][8];
+#pragma unroll
+    for (int j = 0; j < ILP; ++j)
+#pragma unroll
+        for (int i = 0; i < 8; ++i)
+            acc[j][i] = 0.f;
+    const u32x4 *const slot = reinterpret_cast<const u32x4 *>(a.slot);
+    for (unsigned base = 0; base < topk; base += 64) { // (one pass for topk <= 64)
+        const unsigned s = base + (t & 63u);
+        const bool routed = s < topk && slot_routed(a.ids, a.i64 != 0, p0 + s, a.num_experts);
+        const float w_lane = routed ? a.topk_weights[p0 + s] : 0.f;
+        unsigned long long mask = __ballot(routed);
+        const u32x4 *const first = slot + (p0 + base) * cols;
+        while (mask) {
+            unsigned idx[kDepth];
+            int n = 0;
+#pragma unroll
+            for (int d = 0; d < kDepth; ++d) {
+                idx[d] = 0;
+                if (mask) {
+                    idx[d] = (unsigned)__builtin_ctzll(mask);
+                    mask &= mask - 1;
+                    ++n;
+                }
+            }
+            combine_group<BF16, ILP, kDepth>(n, acc, first, cols, col, w_lane, idx);
+        }
+    }
+    u32x4 h[ILP];
+#pragma unroll
+    for (int j = 0; j < ILP; ++j)
+#pragma unroll
+        for (int q = 0; q < 4; ++q)
+            h[j][q] = combine_round2<BF16>(acc[j][2 * q], acc[j][2 * q + 1]);
+    if (has_res)
+        add_residual<BF16, ILP>(h, r);
+#pragma unroll
+    for (int j = 0; j < ILP; ++j)
+        if (!(t + 256u * j < cols))
+            h[j] = zero;
+    if (p.res_out) { // h with or without a residual; a thread writes only columns of the residual row that it alone has read: res_out may be residual
+        u32x4 *const o_row = reinterpret_cast<u32x4 *>(p.res_out) + row_v;
+#pragma unroll
+        for (int j = 0; j < ILP; ++j) {
+            const unsigned c = t + 256u * j;
+            if (c < cols)
+                o_row[c] = h[j];
+        }
+    }
+    norm_quant_tail<BF16, ACT, ILP>(p, h, wv, wave_sum, y_row);
 #endif
 }
 
 namespace {
 
 // what both forms refuse, in one place (include/petit_amd.h lists it); kOk with *run = false: nothing to do
+// k_step: what k must be a multiple of -- 256 where quantised bytes are written (whole k-tiles), 8 for the query that only sums a row
 int rmsq_check(const void *qa, const void *y16, const void *res_out, const void *x, const void *res, const void *w, float eps, float woff, unsigned m,
-               unsigned k, int a_type, int format, bool *run) {
+               unsigned k, int a_type, int format, bool *run, unsigned k_step = 256) {
     *run = false;
     if (m == 0 || k == 0)
         return kOk;
@@ -319,7 +505,7 @@ int rmsq_check(const void *qa, const void *y16, const void *res_out, const void 
         return kErrBadArgument;
     if (a_type != kDataTypeBf16 && a_type != kDataTypeFp16)
         return kErrKernelShape;
-    if (k % 256 != 0 || m > kMaxM)
+    if (k % k_step != 0 || m > kMaxM)
         return kErrProblemShape;
     if (k > 16384)
         return kErrKernelShape; // (the row is held in registers)
@@ -506,7 +692,8 @@ int rmsnorm_quantize_host(void *qa, void *y16, void *res_out, const void *x, con
 int rmsnorm_inv_host(float *inv, const void *x, const void *res, float eps, unsigned m, unsigned k, int a_type) {
     bool run;
     alignas(16) static const uint64_t aligned[2] = {0, 0}; // (stands in for the pointers this query does not take)
-    if (const int rc = rmsq_check(aligned, nullptr, nullptr, x, res, aligned, eps, 0.f, m, k, a_type, 8, &run); rc != kOk || !run)
+    // any k % 8 == 0: the stated order needs no whole k-tiles, and the 16-bit-only form of petit_moe_combine_rmsnorm norms such rows
+    if (const int rc = rmsq_check(aligned, nullptr, nullptr, x, res, aligned, eps, 0.f, m, k, a_type, 8, &run, 8); rc != kOk || !run)
         return rc;
     if (!inv)
         return kErrBadArgument;
@@ -522,6 +709,127 @@ int rmsnorm_inv_host(float *inv, const void *x, const void *res, float eps, unsi
             inv[row] = row_inv_host<false>(h.data(), k, 1.0f / (float)k, eps);
         }
     }
+    return kOk;
+}
+
+// --- petit_moe_combine_rmsnorm ----------------------------------------------------------------------------------------------------------------
+
+namespace {
+
+// what both forms refuse, in one place (include/petit_amd.h lists it); kOk with *run = false: nothing to do
+int mcn_check(const void *qa, const void *y16, const void *res_out, const void *slot, const float *tw, const void *ids, const void *res,
+              const void *w, float eps, float woff, unsigned num_tokens, unsigned topk, unsigned k, unsigned num_experts, int a_type, int format,
+              bool *run) {
+    *run = false;
+    if (num_tokens == 0 || k == 0)
+        return kOk;
+    if (format != 0 && format != 8 && format != 6 && format != 4)
+        return kErrBadArgument;
+    if (a_type != kDataTypeBf16 && a_type != kDataTypeFp16)
+        return kErrKernelShape;
+    if (k % 8 != 0 || (format != 0 && k % 256 != 0))
+        return kErrProblemShape;
+    if (topk == 0 || num_experts == 0 || num_experts > kMoeMaxExperts || (uint64_t)num_tokens * topk >= (1ull << 31) || num_tokens > kMaxM)
+        return kErrProblemShape;
+    if (k > 16384)
+        return kErrKernelShape; // (the row is held in registers)
+    if (!std::isfinite(eps) || !(eps > 0.f) || !std::isfinite(woff))
+        return kErrBadArgument;
+    if (!slot || !tw || !ids || !w)
+        return kErrBadArgument;
+    if (format == 0 ? (qa != nullptr || !y16) : !qa)
+        return kErrBadArgument;
+    if (((uintptr_t)qa | (uintptr_t)y16 | (uintptr_t)res_out | (uintptr_t)slot | (uintptr_t)res | (uintptr_t)w) & 15)
+        return kErrBadArgument;
+    *run = true;
+    return kOk;
+}
+
+template <bool BF16, int ACT> auto mcn_kernel_for(unsigned k) {
+    return k <= 2048   ? moe_combine_rmsnorm_kernel<BF16, ACT, 1>
+           : k <= 4096 ? moe_combine_rmsnorm_kernel<BF16, ACT, 2>
+           : k <= 8192 ? moe_combine_rmsnorm_kernel<BF16, ACT, 4>
+                       : moe_combine_rmsnorm_kernel<BF16, ACT, 8>;
+}
+template <bool BF16> auto mcn_kernel_for(int format, unsigned k) {
+    return format == 8   ? mcn_kernel_for<BF16, 8>(k)
+           : format == 6 ? mcn_kernel_for<BF16, 6>(k)
+           : format == 4 ? mcn_kernel_for<BF16, 4>(k)
+                         : mcn_kernel_for<BF16, 0>(k);
+}
+
+template <bool BF16, int ACT> void mcn_host(const CombineNormArgs &a) {
+    const RmsQuantArgs &p = a.n;
+    const unsigned k = p.k;
+    std::vector<float> acc(k);
+    std::vector<uint16_t> c(k), h(k), y(k);
+    const uint16_t *const w = (const uint16_t *)p.w;
+    for (unsigned row = 0; row < p.m; ++row) {
+        std::fill(acc.begin(), acc.end(), 0.f);
+        for (unsigned s = 0; s < a.topk; ++s) {
+            const size_t e = (size_t)row * a.topk + s;
+            if (!slot_routed(a.ids, a.i64 != 0, e, a.num_experts))
+                continue; // (the row is not read)
+            const float tw = a.topk_weights[e];
+            const uint16_t *const x = (const uint16_t *)a.slot + e * k;
+            for (unsigned i = 0; i < k; ++i)
+                acc[i] = add_rn(acc[i], mul_rn(h16_f32<BF16>(x[i]), tw));
+        }
+        for (unsigned i = 0; i < k; i += 2) {
+            const unsigned d = combine_round2<BF16>(acc[i], acc[i + 1]);
+            c[i] = (uint16_t)d, c[i + 1] = (uint16_t)(d >> 16);
+        }
+        const uint16_t *const r = p.res ? (const uint16_t *)p.res + (size_t)row * k : nullptr;
+        add_row_host<BF16>(h.data(), c.data(), r, k);
+        if (p.res_out)
+            memcpy((uint16_t *)p.res_out + (size_t)row * k, h.data(), 2 * (size_t)k);
+        const float inv = row_inv_host<BF16>(h.data(), k, p.rk, p.eps);
+        for (unsigned i = 0; i < k; ++i)
+            y[i] = (uint16_t)f32_h16<BF16>(normed(h16_f32<BF16>(h[i]), inv, h16_f32<BF16>(w[i]), p.woff));
+        if (p.y16)
+            memcpy((uint16_t *)p.y16 + (size_t)row * k, y.data(), 2 * (size_t)k);
+        if constexpr (ACT != 0)
+            quantize_row_host<BF16, ACT>(p.qa, y.data(), p.m, k, row);
+    }
+}
+
+CombineNormArgs mcn_args(void *qa, void *y16, void *res_out, const void *slot, const float *tw, const void *ids, int i64, const void *res,
+                         const void *w, float eps, float woff, unsigned num_tokens, unsigned topk, unsigned k, unsigned num_experts) {
+    return CombineNormArgs{rmsq_args(qa, y16, res_out, nullptr, res, w, eps, woff, num_tokens, k), slot, tw, ids, i64 ? 1u : 0u, topk, num_experts};
+}
+
+} // namespace
+
+int moe_combine_rmsnorm(void *qa, void *y16, void *res_out, const void *slot, const float *tw, const void *ids, int i64, const void *res,
+                        const void *w, float eps, float woff, unsigned num_tokens, unsigned topk, unsigned k, unsigned num_experts, int a_type,
+                        int format, hipStream_t stream) {
+    bool run;
+    if (const int rc = mcn_check(qa, y16, res_out, slot, tw, ids, res, w, eps, woff, num_tokens, topk, k, num_experts, a_type, format, &run);
+        rc != kOk || !run)
+        return rc;
+    const auto kern = a_type == kDataTypeBf16 ? mcn_kernel_for<true>(format, k) : mcn_kernel_for<false>(format, k);
+    hipLaunchKernelGGL(kern, dim3(num_tokens), dim3(256), 0, stream,
+                       mcn_args(qa, y16, res_out, slot, tw, ids, i64, res, w, eps, woff, num_tokens, topk, k, num_experts));
+    return hipGetLastError() == hipSuccess ? kOk : kErrLaunch;
+}
+
+int moe_combine_rmsnorm_host(void *qa, void *y16, void *res_out, const void *slot, const float *tw, const void *ids, int i64, const void *res,
+                             const void *w, float eps, float woff, unsigned num_tokens, unsigned topk, unsigned k, unsigned num_experts,
+                             int a_type, int format) {
+    bool run;
+    if (const int rc = mcn_check(qa, y16, res_out, slot, tw, ids, res, w, eps, woff, num_tokens, topk, k, num_experts, a_type, format, &run);
+        rc != kOk || !run)
+        return rc;
+    const CombineNormArgs a = mcn_args(qa, y16, res_out, slot, tw, ids, i64, res, w, eps, woff, num_tokens, topk, k, num_experts);
+    const bool bf16 = a_type == kDataTypeBf16;
+    if (format == 8)
+        bf16 ? mcn_host<true, 8>(a) : mcn_host<false, 8>(a);
+    else if (format == 6)
+        bf16 ? mcn_host<true, 6>(a) : mcn_host<false, 6>(a);
+    else if (format == 4)
+        bf16 ? mcn_host<true, 4>(a) : mcn_host<false, 4>(a);
+    else
+        bf16 ? mcn_host<true, 0>(a) : mcn_host<false, 0>(a);
     return kOk;
 }
 

@@ -388,6 +388,53 @@ at::Tensor moe_combine(const at::Tensor &slot_out, const at::Tensor &topk_weight
     return out;
 }
 
+// petit_moe_combine_rmsnorm: (qa, h, y16), an absent output as an empty tensor; format 0 = no quantised output.  The checks that keep every
+// access inside its tensor; petit_kernel/ops.py _combine_norm_operands states the full set, with its texts, for both Python layers
+#define PETIT_COMBINE_NORM_ARGS                                                                                                            \
+    const at::Tensor &slot_out, const at::Tensor &topk_weights, const at::Tensor &topk_ids, int64_t num_experts, const at::Tensor &weight, \
+        double eps, int64_t format, const std::optional<at::Tensor> &residual, double weight_offset, bool return_normed, bool return_hidden, \
+        bool inplace_residual
+std::tuple<at::Tensor, at::Tensor, at::Tensor> moe_combine_rmsnorm(PETIT_COMBINE_NORM_ARGS) {
+    check_topk_ids(topk_ids, num_experts);
+    const int64_t T = topk_ids.size(0), topk = topk_ids.size(1);
+    TORCH_CHECK(slot_out.is_cuda() && slot_out.device() == topk_ids.device() &&
+                    (slot_out.scalar_type() == at::kBFloat16 || slot_out.scalar_type() == at::kHalf) && slot_out.is_contiguous() &&
+                    slot_out.dim() == 2 && slot_out.size(0) == T * topk,
+                "slot_out must be a contiguous bfloat16 / float16 [num_tokens * topk, k] tensor on topk_ids' device");
+    TORCH_CHECK(topk_weights.device() == topk_ids.device() && topk_weights.scalar_type() == at::kFloat && topk_weights.is_contiguous() &&
+                    topk_weights.sizes() == topk_ids.sizes(),
+                "topk_weights must be a contiguous float32 [num_tokens, topk] tensor on topk_ids' device");
+    const int64_t k = slot_out.size(1);
+    TORCH_CHECK(format == 0 || format == 8 || format == 6 || format == 4, "fmt must be None, 'mxfp8', 'mxfp6' or 'mxfp4'");
+    TORCH_CHECK(k % 8 == 0, "k must be a multiple of 8, got ", k);
+    TORCH_CHECK(format == 0 || k % 256 == 0, "k must be a multiple of 256 with a fmt, got ", k);
+    TORCH_CHECK(weight.device() == slot_out.device() && weight.is_contiguous() && weight.scalar_type() == slot_out.scalar_type() &&
+                    weight.dim() == 1 && weight.size(0) == k,
+                "weight must be a contiguous [k] tensor of slot_out's dtype on its device (k=", k, ")");
+    const bool has_res = residual.has_value() && residual->defined();
+    TORCH_CHECK(!has_res || (residual->device() == slot_out.device() && residual->is_contiguous() &&
+                             residual->scalar_type() == slot_out.scalar_type() && residual->dim() == 2 && residual->size(0) == T &&
+                             residual->size(1) == k),
+                "residual must be a contiguous [num_tokens, k] tensor of slot_out's dtype on its device");
+    TORCH_CHECK(format != 0 || return_normed, "fmt=None returns the 16-bit y: return_normed cannot be False");
+    TORCH_CHECK(!inplace_residual || (has_res && return_hidden), "inplace_residual needs a residual and return_hidden");
+    const c10::hip::HIPGuardMasqueradingAsCUDA guard(slot_out.device());
+    const auto bytes = slot_out.options().dtype(at::kByte);
+    at::Tensor qa = at::empty({format ? (int64_t)petit_quantized_activation_bytes((unsigned)T, (unsigned)k, (int)format) : 0}, bytes);
+    at::Tensor h = return_hidden && !inplace_residual ? at::empty({T, k}, slot_out.options()) : at::empty({0}, slot_out.options());
+    at::Tensor y = return_normed ? at::empty({T, k}, slot_out.options()) : at::empty({0}, slot_out.options());
+    void *const h_ptr = !return_hidden ? nullptr : inplace_residual ? residual->data_ptr() : h.data_ptr();
+    const int rc = petit_moe_combine_rmsnorm(format ? qa.data_ptr() : nullptr, return_normed ? y.data_ptr() : nullptr, h_ptr, slot_out.data_ptr(),
+                                             (const float *)topk_weights.data_ptr(), topk_ids.data_ptr(), topk_ids.scalar_type() == at::kLong,
+                                             has_res ? residual->data_ptr() : nullptr, weight.data_ptr(), (float)eps, (float)weight_offset,
+                                             (unsigned)T, (unsigned)topk, (unsigned)k, (unsigned)num_experts, a_type_of(slot_out.scalar_type()),
+                                             (int)format, stream_of(slot_out));
+    TORCH_CHECK(rc != PETIT_ERROR_PROBLEM_SHAPE, "Incompatible problem shape (num_tokens=", T, ", topk=", topk, ", k=", k, ", num_experts=", num_experts, ")");
+    TORCH_CHECK(rc != PETIT_ERROR_KERNEL_SHAPE, "No kernel implementation for k=", k, " (the fused norm holds a row of at most 16384 elements).");
+    TORCH_CHECK(rc == PETIT_OK, "moe_combine_rmsnorm: ", petit_error_string(rc));
+    return {qa, h, y};
+}
+
 // routing from the logits (petit_moe_route / petit_moe_route_align); the same checks and texts as petit_kernel/ops.py _check_route
 #define PETIT_ROUTE_ARGS                                                                                                                     \
     const at::Tensor &router_logits, int64_t topk, int64_t scoring, bool renormalize, const std::optional<at::Tensor> &bias, int64_t n_group, \
@@ -662,6 +709,12 @@ std::tuple<at::Tensor, at::Tensor, at::Tensor> moe_align_device_meta(const at::T
 at::Tensor moe_combine_meta(const at::Tensor &slot_out, const at::Tensor &, const at::Tensor &topk_ids, int64_t) {
     return at::empty({topk_ids.size(0), slot_out.size(1)}, slot_out.options());
 }
+std::tuple<at::Tensor, at::Tensor, at::Tensor> moe_combine_rmsnorm_meta(PETIT_COMBINE_NORM_ARGS) {
+    const int64_t T = topk_ids.size(0), k = slot_out.size(1);
+    const auto none = at::empty({0}, slot_out.options());
+    return {at::empty({format ? (int64_t)petit_quantized_activation_bytes((unsigned)T, (unsigned)k, (int)format) : 0}, slot_out.options().dtype(at::kByte)),
+            return_hidden && !inplace_residual ? at::empty({T, k}, slot_out.options()) : none, return_normed ? at::empty({T, k}, slot_out.options()) : none};
+}
 std::tuple<at::Tensor, at::Tensor, at::Tensor> moe_route_meta(PETIT_ROUTE_ARGS) {
     const int64_t T = router_logits.size(0), E = router_logits.size(1);
     const auto f32 = router_logits.options().dtype(at::kFloat);
@@ -726,6 +779,9 @@ TORCH_LIBRARY(petit_kernel, m) {
           "Tensor? bias=None, int activation=0, int a_format=0, int a_type=5, int out_format=0) -> Tensor");
     m.def("moe_align_device(Tensor topk_ids, int num_experts) -> (Tensor, Tensor, Tensor)");
     m.def("moe_combine(Tensor slot_out, Tensor topk_weights, Tensor topk_ids, int num_experts) -> Tensor");
+    m.def("moe_combine_rmsnorm(Tensor slot_out, Tensor topk_weights, Tensor topk_ids, int num_experts, Tensor weight, float eps=1e-6, "
+          "int format=0, Tensor(a!)? residual=None, float weight_offset=0.0, bool return_normed=True, bool return_hidden=False, "
+          "bool inplace_residual=False) -> (Tensor, Tensor, Tensor)");
 #define PETIT_ROUTE_SCHEMA                                                                                                            \
     "Tensor router_logits, int topk, int scoring=0, bool renormalize=True, Tensor? bias=None, int n_group=1, int topk_group=1, " \
     "float routed_scaling_factor=1.0, bool return_keys=False"
@@ -759,6 +815,7 @@ TORCH_LIBRARY(petit_kernel, m) {
     m.impl("mul_nvfp4_native_transient", &mul_nvfp4_native_transient); \
     m.impl("moe_align_device", &moe_align_device);              \
     m.impl("moe_combine", &moe_combine);                        \
+    m.impl("moe_combine_rmsnorm", &moe_combine_rmsnorm);        \
     m.impl("moe_route", &moe_route);                            \
     m.impl("moe_route_align", &moe_route_align);                \
     m.impl("moe_route_ex", &moe_route_ex);                      \
@@ -785,6 +842,7 @@ TORCH_LIBRARY_IMPL(petit_kernel, Meta, m) {
     m.impl("mul_nvfp4_native_transient", &mul_nvfp4_native_transient_meta);
     m.impl("moe_align_device", &moe_align_device_meta);
     m.impl("moe_combine", &moe_combine_meta);
+    m.impl("moe_combine_rmsnorm", &moe_combine_rmsnorm_meta);
     m.impl("moe_route", &moe_route_meta);
     m.impl("moe_route_align", &moe_route_align_meta);
     m.impl("moe_route_ex", &moe_route_ex_meta);

@@ -149,6 +149,16 @@ def moe_combine(slot_out: torch.Tensor, topk_weights: torch.Tensor, topk_ids: to
     return _impl.moe_combine(slot_out, topk_weights, topk_ids, num_experts)
 
 
+def moe_combine_rmsnorm(slot_out: torch.Tensor, topk_weights: torch.Tensor, topk_ids: torch.Tensor, num_experts: int, weight: torch.Tensor,
+                        eps: float = 1e-6, fmt: str = None, *, residual: torch.Tensor = None, weight_offset: float = 0.0,
+                        return_normed: bool = None, return_hidden: bool = None, inplace_residual: bool = False):
+    # moe_combine, the residual add, the RMSNorm and (with fmt) quantize_activations in ONE launch (include/petit_amd.h "Top-k combine into the
+    # norm"; ops.moe_combine_rmsnorm has the return convention): the end of a routed-expert layer and the head of the next block
+    return _impl.moe_combine_rmsnorm(slot_out, topk_weights, topk_ids, num_experts, weight, eps, fmt, residual=residual,
+                                     weight_offset=weight_offset, return_normed=return_normed, return_hidden=return_hidden,
+                                     inplace_residual=inplace_residual)
+
+
 def _no_slots(expert_map, num_local_experts, num_shared, shared_weight, shared_gate_logits) -> bool:
     # every slot-list argument of moe_route / moe_route_align at its default: the call is the plain route
     return expert_map is None and num_local_experts is None and num_shared == 0 and shared_weight == 1.0 and shared_gate_logits is None
@@ -288,6 +298,7 @@ __all__ = [
     "mul_mxfp4_a16_moe_indexed",
     "moe_align_device",
     "moe_combine",
+    "moe_combine_rmsnorm",
     "moe_route",
     "moe_route_align",
     "fp4_moe_routed",

@@ -159,6 +159,10 @@ _SIGNATURES = {
     "petit_rmsnorm_quantize": (C.c_int, [C.c_void_p] * 6 + [C.c_float, C.c_float, C.c_uint, C.c_uint, C.c_int, C.c_int, C.c_void_p]),
     "petit_rmsnorm_quantize_host": (C.c_int, [C.c_void_p] * 6 + [C.c_float, C.c_float, C.c_uint, C.c_uint, C.c_int, C.c_int]),
     "petit_rmsnorm_inv_host": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_float, C.c_uint, C.c_uint, C.c_int]),
+    "petit_moe_combine_rmsnorm": (C.c_int, [C.c_void_p] * 6 + [C.c_int, C.c_void_p, C.c_void_p, C.c_float, C.c_float] + [C.c_uint] * 4 +
+                                  [C.c_int, C.c_int, C.c_void_p]),
+    "petit_moe_combine_rmsnorm_host": (C.c_int, [C.c_void_p] * 6 + [C.c_int, C.c_void_p, C.c_void_p, C.c_float, C.c_float] + [C.c_uint] * 4 +
+                                       [C.c_int, C.c_int]),
     "petit_quantize_activations_rows": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p] + [C.c_uint] * 3 + [C.c_int, C.c_int, C.c_void_p]),
     "petit_gemm_native_moe_workspace_bytes": (C.c_uint64, [C.POINTER(SolutionHints)] + [C.c_uint] * 4 + [C.c_uint64, C.POINTER(Epilogue),
                                                                                                         C.POINTER(NativeArgs)]),

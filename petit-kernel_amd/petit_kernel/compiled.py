@@ -15,6 +15,7 @@ import torch
 
 from . import _lib  # loads libpetit_amd.so first (the binding links against it)
 from .ops import QuantizedActivations, _a_type, _activation as _act, _activation_operand, _quantized_format
+from .ops import _combine_norm_operands, _combine_norm_returns
 
 LIB_PATH = Path(_lib.LIB_PATH).parent / "libpetit_torch.so"
 _loaded = False
@@ -129,6 +130,19 @@ def moe_align_device(topk_ids, num_experts):
 
 def moe_combine(slot_out, topk_weights, topk_ids, num_experts):
     return torch.ops.petit_kernel.moe_combine(slot_out, topk_weights, topk_ids, num_experts)
+
+
+def moe_combine_rmsnorm(slot_out, topk_weights, topk_ids, num_experts, weight, eps=1e-6, fmt=None, *, residual=None, weight_offset=0.0,
+                        return_normed=None, return_hidden=None, inplace_residual=False):
+    T, _, k = _combine_norm_operands(slot_out, topk_weights, topk_ids, num_experts, weight, eps, fmt, residual, weight_offset, on_gpu=True)
+    want_h, want_y = _combine_norm_returns(fmt, residual, return_normed, return_hidden, inplace_residual)
+    qa, h, y = torch.ops.petit_kernel.moe_combine_rmsnorm(slot_out, topk_weights, topk_ids, int(num_experts), weight, float(eps),
+                                                          _quantized_format(fmt, "fmt must be None, 'mxfp8', 'mxfp6' or 'mxfp4'"), residual,
+                                                          float(weight_offset), want_y, want_h, bool(inplace_residual))
+    out = (QuantizedActivations(qa, T, k, fmt, slot_out.dtype),) if fmt else ()
+    out += ((residual if inplace_residual else h),) if want_h else ()
+    out += (y,) if want_y else ()
+    return out[0] if len(out) == 1 else out
 
 
 _SCORING = {"softmax": 0, "sigmoid": 1}

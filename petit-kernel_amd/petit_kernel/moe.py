@@ -83,15 +83,40 @@ def fp4_moe(hidden: torch.Tensor, w13: torch.Tensor, s13: torch.Tensor, gs13: to
 
 def fp4_moe_fused(hidden: torch.Tensor, w13: torch.Tensor, s13: torch.Tensor, gs13: torch.Tensor, w2: torch.Tensor, s2: torch.Tensor,
                   gs2: torch.Tensor, topk_weights: torch.Tensor, topk_ids: torch.Tensor, kind: str = "nvfp4", *, bias13: torch.Tensor = None,
-                  bias2: torch.Tensor = None, activation: str = "silu_mul") -> torch.Tensor:
+                  bias2: torch.Tensor = None, activation: str = "silu_mul", norm_weight: torch.Tensor = None, norm_eps: float = 1e-6,
+                  norm_residual: torch.Tensor = None, norm_weight_offset: float = 0.0, norm_fmt: str = None):
     """fp4_moe's layer (same arguments, same result up to the combine's rounding order) on the indexed MoE launches: align on the device,
     gate_up on gathered rows, down scattered into slot order, the top-k combine.  topk_ids: int32 or int64 [T, topk]; entries outside
     [0, E) (-1 under expert parallelism) contribute nothing.  topk_weights: float32 or bfloat16 [T, topk] (converted to float32 once).
     bias13 / bias2 / activation: as fp4_moe (the biases ride in the gate_up and down launches: no launch more).
-    No host sync: capturable in a graph and replayable with any routing of the same shape."""
+    No host sync: capturable in a graph and replayable with any routing of the same shape.
+
+    norm_weight (with norm_eps, norm_residual, norm_weight_offset, norm_fmt): the fused end -- the layer ends in moe_combine_rmsnorm instead of
+    moe_combine, one launch for the combine, the residual add (norm_residual), the next block's RMSNorm (norm_weight [H]) and, with norm_fmt
+    ('mxfp8' / 'mxfp6' / 'mxfp4'), its activation quantiser.  Returns (h, y16) with norm_fmt None and (q, h) with one: h = layer output (+
+    norm_residual) in 16 bits, y16 = RMSNorm(h) * (norm_weight + norm_weight_offset), q = quantize_activations(y16, norm_fmt), each bit for bit
+    what the un-fused layer followed by rmsnorm_quantize gives.  The fused end is for a layer whose combine is COMPLETE on this rank: under
+    tensor or expert parallelism an all-reduce belongs between the combine and the residual add, so such a layer ends in moe_combine.
+    Measured (profiles/moe_combine_norm.md) against moe_combine followed by the norm."""
     _check_fused(kind, activation)
+    norm = _norm_end(norm_weight, norm_eps, norm_residual, norm_weight_offset, norm_fmt)
     w, ids, sorted_pos, offsets, token_index = _align_routing(topk_weights, topk_ids, gs13.numel())
-    return _fused_after_align(hidden, w13, s13, gs13, w2, s2, gs2, w, ids, sorted_pos, offsets, token_index, kind, bias13, bias2, activation)
+    return _fused_after_align(hidden, w13, s13, gs13, w2, s2, gs2, w, ids, sorted_pos, offsets, token_index, kind, bias13, bias2, activation, norm)
+
+
+def _norm_end(norm_weight, norm_eps, norm_residual, norm_weight_offset, norm_fmt):
+    """The fused end of a layer as its last step takes it: None (the layer ends in moe_combine) or moe_combine_rmsnorm's arguments."""
+    if norm_weight is None:
+        if norm_residual is not None or norm_fmt is not None:
+            raise RuntimeError("norm_residual / norm_fmt need a norm_weight (the fused end of the layer)")
+        return None
+    return dict(weight=norm_weight, eps=norm_eps, fmt=norm_fmt, residual=norm_residual, weight_offset=norm_weight_offset, return_hidden=True)
+
+
+def _combine(y, w, ids, num_experts, norm):
+    """The last launch of a layer: the top-k combine, or with a fused end the combine into the norm."""
+    from . import moe_combine, moe_combine_rmsnorm
+    return moe_combine(y, w, ids, num_experts) if norm is None else moe_combine_rmsnorm(y, w, ids, num_experts, **norm)
 
 
 def _align_routing(topk_weights, topk_ids, num_experts):
@@ -108,9 +133,9 @@ def _check_fused(kind, activation) -> None:
     _check_activation(activation)
 
 
-def _fused_after_align(hidden, w13, s13, gs13, w2, s2, gs2, w, ids, sorted_pos, offsets, token_index, kind, bias13, bias2, activation):
+def _fused_after_align(hidden, w13, s13, gs13, w2, s2, gs2, w, ids, sorted_pos, offsets, token_index, kind, bias13, bias2, activation, norm=None):
     """fp4_moe_fused after its align: gate_up on gathered rows, down scattered into slot order, the combine (w float32, ids int32 / int64)."""
-    from . import moe_combine, mul_mxfp4_a16_moe_indexed, mul_nvfp4_a16_moe_indexed
+    from . import mul_mxfp4_a16_moe_indexed, mul_nvfp4_a16_moe_indexed
     mul = mul_nvfp4_a16_moe_indexed if kind == "nvfp4" else mul_mxfp4_a16_moe_indexed
     T, H = hidden.shape
     topk = ids.shape[1]
@@ -121,7 +146,7 @@ def _fused_after_align(hidden, w13, s13, gs13, w2, s2, gs2, w, ids, sorted_pos, 
     n2 = _down_n(w2, E, inter, H)
     h = mul(hidden, w13, s13, gs13, offsets, m, n13, H, E, a_row_index=token_index, bias=bias13, activation=activation)  # [m, I], grouped order
     y = mul(h, w2, s2, gs2, offsets, m, n2, inter, E, c_row_index=sorted_pos, c_rows=m, bias=bias2)          # [m, n2], (token, slot) order
-    return moe_combine(y, w, ids, E)
+    return _combine(y, w, ids, E, norm)
 
 
 _NATIVE_SENTINELS = {"mxfp8": -2, "mxfp4": -3, "mxfp6": -4}   # SOLUTION_AUTO_NATIVE_MXFP8 / _MXFP4 / _MXFP6
@@ -129,7 +154,9 @@ _NATIVE_SENTINELS = {"mxfp8": -2, "mxfp4": -3, "mxfp6": -4}   # SOLUTION_AUTO_NA
 
 def fp4_moe_native(hidden: torch.Tensor, w13: torch.Tensor, s13, gs13: torch.Tensor, w2: torch.Tensor, s2, gs2: torch.Tensor,
                    topk_weights: torch.Tensor, topk_ids: torch.Tensor, kind: str = "mxfp4", activations: str = "mxfp8", *,
-                   bias13: torch.Tensor = None, bias2: torch.Tensor = None, activation: str = "silu_mul", transient: bool = False) -> torch.Tensor:
+                   bias13: torch.Tensor = None, bias2: torch.Tensor = None, activation: str = "silu_mul", transient: bool = False,
+                   norm_weight: torch.Tensor = None, norm_eps: float = 1e-6, norm_residual: torch.Tensor = None, norm_weight_offset: float = 0.0,
+                   norm_fmt: str = None):
     """fp4_moe_fused's layer on the NATIVE class (the block-scaled MFMA, activations quantised to `activations`: 'mxfp8', 'mxfp6' or 'mxfp4';
     petit_gemm_native_moe -- a different accuracy class than the exact layers).  kind 'mxfp4': w13 / s13 / w2 / s2 as fp4_moe_fused; kind
     'nvfp4': w13 / w2 are the experts' MFMA-native images back to back (nvfp4_native_images) and s13 / s2 are None.  Five launches (seven
@@ -141,11 +168,15 @@ def fp4_moe_native(hidden: torch.Tensor, w13: torch.Tensor, s13, gs13: torch.Ten
     resident: each of the two launches is mul_nvfp4_native_moe_transient, which first builds the images of the experts this routing uses
     into the scratch (one more launch each).  Both launches run one after the other on ONE scratch buffer, which the layer takes from the
     allocator for the call (the larger of the two launches' workspace queries) and releases on return: the layer holds 4.5 bits per weight
-    and, while it runs, that scratch.  Bit for bit the resident layer on nvfp4_native_images of the same tensors."""
+    and, while it runs, that scratch.  Bit for bit the resident layer on nvfp4_native_images of the same tensors.
+
+    norm_weight / norm_eps / norm_residual / norm_weight_offset / norm_fmt: fp4_moe_fused's fused end (the combine, the residual add, the next
+    RMSNorm and its quantiser in the last launch; returns (h, y16) or (q, h)), for a layer whose combine is complete on this rank."""
     _check_native(kind, activation, activations, transient)
+    norm = _norm_end(norm_weight, norm_eps, norm_residual, norm_weight_offset, norm_fmt)
     w, ids, sorted_pos, offsets, token_index = _align_routing(topk_weights, topk_ids, gs13.numel())
     return _native_after_align(hidden, w13, s13, gs13, w2, s2, gs2, w, ids, sorted_pos, offsets, token_index, kind, activations, bias13, bias2,
-                               activation, transient)
+                               activation, transient, norm)
 
 
 def _check_native(kind, activation, activations, transient=False) -> None:
@@ -159,9 +190,9 @@ def _check_native(kind, activation, activations, transient=False) -> None:
 
 
 def _native_after_align(hidden, w13, s13, gs13, w2, s2, gs2, w, ids, sorted_pos, offsets, token_index, kind, activations, bias13, bias2,
-                        activation, transient=False):
+                        activation, transient=False, norm=None):
     """fp4_moe_native after its align: the gathering quantiser, gate_up, down scattered into slot order, the combine."""
-    from . import moe_combine, mul_mxfp4_native_moe, mul_nvfp4_native_moe, mul_nvfp4_native_moe_transient, quantize_activation_rows
+    from . import mul_mxfp4_native_moe, mul_nvfp4_native_moe, mul_nvfp4_native_moe_transient, quantize_activation_rows
     sid = _NATIVE_SENTINELS[activations]
     T, H = hidden.shape
     E = gs13.numel()
@@ -189,13 +220,14 @@ def _native_after_align(hidden, w13, s13, gs13, w2, s2, gs2, w, ids, sorted_pos,
     h = mul(qa, *gate_up, offsets, m, n13, H, E, solution_id=sid, bias=bias13, activation=activation,
             out_quantized=activations if n13 % 512 == 0 else None, **ws)
     y = mul(h, *down, offsets, m, n2, inter, E, solution_id=sid, c_row_index=sorted_pos, c_rows=m, bias=bias2, **ws)   # [m, n2], (token, slot) order
-    return moe_combine(y, w, ids, E)
+    return _combine(y, w, ids, E, norm)
 
 
 def fp4_moe_routed(hidden: torch.Tensor, router_logits: torch.Tensor, w13: torch.Tensor, s13, gs13: torch.Tensor, w2: torch.Tensor, s2,
                    gs2: torch.Tensor, topk: int, kind: str = "nvfp4", *, path: str = "fused", activations: str = "mxfp8",
                    bias13: torch.Tensor = None, bias2: torch.Tensor = None, activation: str = "silu_mul", transient: bool = False,
-                   **routing) -> torch.Tensor:
+                   norm_weight: torch.Tensor = None, norm_eps: float = 1e-6, norm_residual: torch.Tensor = None, norm_weight_offset: float = 0.0,
+                   norm_fmt: str = None, **routing):
     """The layer from the router's logits: moe_route_align(router_logits, topk, **routing), then exactly the launches fp4_moe_fused (path
     'fused') or fp4_moe_native (path 'native', with `activations`) issue after their align -- bit for bit
     fp4_moe_fused(..., *moe_route(router_logits, topk, **routing)).  router_logits [T, E] float32 / bfloat16 / float16; routing: moe_route's
@@ -208,7 +240,11 @@ def fp4_moe_routed(hidden: torch.Tensor, router_logits: torch.Tensor, w13: torch
     experts without an expert_map, num_local_experts + num_shared with one.  A shared expert is of the routed experts' size (a k times wider
     one is k shared experts).  One launch for route + align when T * (topk + num_shared) <= 1024.
 
-    transient (path 'native', kind 'nvfp4'): fp4_moe_native's switch -- the packed tensors, no resident images."""
+    transient (path 'native', kind 'nvfp4'): fp4_moe_native's switch -- the packed tensors, no resident images.
+
+    norm_weight / norm_eps / norm_residual / norm_weight_offset / norm_fmt: fp4_moe_fused's fused end on either path (returns (h, y16) or
+    (q, h)): with route + align in one launch the whole layer and the next block's norm are four launches.  For a layer whose combine is complete
+    on this rank (no all-reduce between the combine and the residual add)."""
     from . import moe_route_align
     if path not in ("fused", "native"):
         raise RuntimeError("path must be 'fused' or 'native'")
@@ -231,8 +267,10 @@ def fp4_moe_routed(hidden: torch.Tensor, router_logits: torch.Tensor, w13: torch
     if gs13.numel() != local + num_shared:
         raise RuntimeError(f"the weights hold {gs13.numel()} experts, the routing names {local} local + {num_shared} shared "
                            f"(router_logits must be [{hidden.size(0)}, {gs13.numel() - num_shared}] without an expert_map)")
+    norm = _norm_end(norm_weight, norm_eps, norm_residual, norm_weight_offset, norm_fmt)
     w, ids, sorted_pos, offsets, token_index = moe_route_align(router_logits, topk, **routing)
     if path == "fused":
-        return _fused_after_align(hidden, w13, s13, gs13, w2, s2, gs2, w, ids, sorted_pos, offsets, token_index, kind, bias13, bias2, activation)
+        return _fused_after_align(hidden, w13, s13, gs13, w2, s2, gs2, w, ids, sorted_pos, offsets, token_index, kind, bias13, bias2, activation,
+                                  norm)
     return _native_after_align(hidden, w13, s13, gs13, w2, s2, gs2, w, ids, sorted_pos, offsets, token_index, kind, activations, bias13, bias2,
-                               activation, transient)
+                               activation, transient, norm)

@@ -14,6 +14,7 @@ import torch
 from . import _lib
 from .ops import _B_TYPES, _LAYOUT_M, _LAYOUT_N, _PACK, _QFORMATS, _a_type, _check, _opt_ptr, _ptr, _quantize_operands, _quantize_outputs, _raise_on
 from .ops import _raise_quantize, _rmsnorm_operands, _rmsnorm_outputs, _rmsnorm_result
+from .ops import _combine_norm_operands, _combine_norm_outputs, _combine_norm_result, _combine_norm_returns
 
 
 def _cpu(t: torch.Tensor, name: str) -> None:
@@ -96,6 +97,20 @@ def rmsnorm_quantize_cpu(x: torch.Tensor, weight: torch.Tensor, eps: float = 1e-
     rc = _lib.lib.petit_rmsnorm_quantize_host(_ptr(qa), _opt_ptr(y16), _opt_ptr(res_out), _ptr(x), _opt_ptr(residual), _ptr(weight), float(eps),
                                               float(weight_offset), m, k, _a_type(x.dtype), _QFORMATS[fmt])
     return _rmsnorm_result(rc, "rmsnorm_quantize_cpu", x, fmt, qa, res_out, y16)
+
+
+def moe_combine_rmsnorm_cpu(slot_out: torch.Tensor, topk_weights: torch.Tensor, topk_ids: torch.Tensor, num_experts: int, weight: torch.Tensor,
+                            eps: float = 1e-6, fmt: str = None, *, residual: torch.Tensor = None, weight_offset: float = 0.0,
+                            return_normed: bool = None, return_hidden: bool = None, inplace_residual: bool = False):
+    """CPU twin of petit_kernel.moe_combine_rmsnorm (the C ABI's host twin): the same arguments on CPU tensors, the same results bit for bit."""
+    T, topk, k = _combine_norm_operands(slot_out, topk_weights, topk_ids, num_experts, weight, eps, fmt, residual, weight_offset, on_gpu=False)
+    want_h, want_y = _combine_norm_returns(fmt, residual, return_normed, return_hidden, inplace_residual)
+    qa, res_out, y16 = _combine_norm_outputs(slot_out, T, k, fmt, residual, want_h, want_y, inplace_residual)
+    rc = _lib.lib.petit_moe_combine_rmsnorm_host(_opt_ptr(qa), _opt_ptr(y16), _opt_ptr(res_out), _ptr(slot_out), _ptr(topk_weights),
+                                                 _ptr(topk_ids), int(topk_ids.dtype == torch.int64), _opt_ptr(residual), _ptr(weight), float(eps),
+                                                 float(weight_offset), T, topk, k, int(num_experts), _a_type(slot_out.dtype),
+                                                 _QFORMATS[fmt] if fmt else 0)
+    return _combine_norm_result(rc, "moe_combine_rmsnorm_cpu", slot_out.dtype, T, topk, k, num_experts, fmt, qa, res_out, y16)
 
 
 # --- tensors already packed by the REFERENCE wheel -> this build's layout (include/petit_amd.h, petit_convert_reference_*) -----

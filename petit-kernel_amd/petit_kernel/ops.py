@@ -897,6 +897,83 @@ def moe_combine(slot_out: torch.Tensor, topk_weights: torch.Tensor, topk_ids: to
     return out
 
 
+def _combine_norm_operands(slot_out, topk_weights, topk_ids, num_experts, weight, eps, fmt, residual, weight_offset, on_gpu: bool):
+    """The argument checks of moe_combine_rmsnorm and of its CPU twin, stated once -> (T, topk, k)."""
+    where = "GPU" if on_gpu else "CPU"
+    _check(fmt is None or fmt in _QFORMATS, "fmt must be None, 'mxfp8', 'mxfp6' or 'mxfp4'")
+    _check(1 <= int(num_experts) <= _lib.PETIT_MOE_MAX_EXPERTS, f"num_experts must be in 1..{_lib.PETIT_MOE_MAX_EXPERTS}, got {num_experts}")
+    _check(topk_ids.is_cuda == on_gpu and topk_ids.dim() == 2 and topk_ids.is_contiguous() and topk_ids.dtype in (torch.int32, torch.int64),
+           f"topk_ids must be a contiguous int32 / int64 [num_tokens, topk] {where} tensor")
+    T, topk = topk_ids.shape
+    _check(topk >= 1, "topk must be >= 1")
+    _check(slot_out.device == topk_ids.device and slot_out.dtype in (torch.bfloat16, torch.float16) and slot_out.is_contiguous() and
+           slot_out.dim() == 2 and slot_out.size(0) == T * topk,
+           "slot_out must be a contiguous bfloat16 / float16 [num_tokens * topk, k] tensor on topk_ids' device")
+    _check(topk_weights.device == topk_ids.device and topk_weights.dtype == torch.float32 and topk_weights.is_contiguous() and
+           topk_weights.shape == topk_ids.shape, "topk_weights must be a contiguous float32 [num_tokens, topk] tensor on topk_ids' device")
+    k = slot_out.size(1)
+    _check(k % 8 == 0, f"k must be a multiple of 8, got {k}")
+    _check(fmt is None or k % 256 == 0, f"k must be a multiple of 256 with a fmt, got {k}")
+    _check(weight.device == slot_out.device and weight.is_contiguous() and weight.dtype == slot_out.dtype and tuple(weight.shape) == (k,),
+           f"weight must be a contiguous [k] tensor of slot_out's dtype on its device (k={k})")
+    _check(residual is None or (residual.device == slot_out.device and residual.is_contiguous() and residual.dtype == slot_out.dtype and
+                                tuple(residual.shape) == (T, k)),
+           "residual must be a contiguous [num_tokens, k] tensor of slot_out's dtype on its device")
+    _check(math.isfinite(eps) and eps > 0, "eps must be finite and positive")
+    _check(math.isfinite(weight_offset), "weight_offset must be finite")
+    return T, topk, k
+
+
+def _combine_norm_returns(fmt, residual, return_normed, return_hidden, inplace_residual):
+    """What the call returns besides the quantised bytes -> (h wanted, y16 wanted), the defaults resolved."""
+    want_y = fmt is None if return_normed is None else bool(return_normed)
+    want_h = residual is not None if return_hidden is None else bool(return_hidden)
+    _check(fmt is not None or want_y, "fmt=None returns the 16-bit y: return_normed cannot be False")
+    _check(not inplace_residual or residual is not None, "inplace_residual needs a residual")
+    _check(not inplace_residual or want_h, "inplace_residual writes h: return_hidden cannot be False")
+    return want_h, want_y
+
+
+def _combine_norm_outputs(slot_out, T, k, fmt, residual, want_h, want_y, inplace_residual):
+    qa = None
+    if fmt is not None:
+        qa = torch.empty(int(_lib.lib.petit_quantized_activation_bytes(T, k, _QFORMATS[fmt])), dtype=torch.uint8, device=slot_out.device)
+    res_out = None if not want_h else residual if inplace_residual else torch.empty((T, k), dtype=slot_out.dtype, device=slot_out.device)
+    y16 = torch.empty((T, k), dtype=slot_out.dtype, device=slot_out.device) if want_y else None
+    return qa, res_out, y16
+
+
+def _combine_norm_result(rc, name, dtype, T, topk, k, num_experts, fmt, qa, res_out, y16):
+    if rc == _lib.PETIT_ERROR_PROBLEM_SHAPE:
+        raise RuntimeError(f"Incompatible problem shape (num_tokens={T}, topk={topk}, k={k}, num_experts={num_experts})")
+    if rc == _lib.PETIT_ERROR_KERNEL_SHAPE:
+        raise RuntimeError(f"No kernel implementation for k={k} (the fused norm holds a row of at most 16384 elements).")
+    _raise_on(rc, name)
+    out = () if qa is None else (QuantizedActivations(qa, T, k, fmt, dtype),)
+    out += tuple(t for t in (res_out, y16) if t is not None)
+    return out[0] if len(out) == 1 else out
+
+
+def moe_combine_rmsnorm(slot_out: torch.Tensor, topk_weights: torch.Tensor, topk_ids: torch.Tensor, num_experts: int, weight: torch.Tensor,
+                        eps: float = 1e-6, fmt: str = None, *, residual: torch.Tensor = None, weight_offset: float = 0.0,
+                        return_normed: bool = None, return_hidden: bool = None, inplace_residual: bool = False):
+    """moe_combine, the residual add, the RMSNorm and (with fmt) quantize_activations in ONE launch (include/petit_amd.h "Top-k combine into the
+    norm"): c = moe_combine(slot_out, topk_weights, topk_ids, num_experts), h = c (+ residual), y = RMSNorm(h) * (weight + weight_offset) -- bit
+    for bit moe_combine -> rmsnorm_quantize(residual=...) where that chain takes the call.  fmt None: no quantised output, any k % 8 == 0.
+    Returns, in this order and alone when it is one: the QuantizedActivations when fmt is given; h when return_hidden (default: when a residual
+    is given; without a residual h is the combined layer output; `residual` itself, written in place, with inplace_residual=True); the 16-bit y
+    when return_normed (default, and always: when fmt is None)."""
+    T, topk, k = _combine_norm_operands(slot_out, topk_weights, topk_ids, num_experts, weight, eps, fmt, residual, weight_offset, on_gpu=True)
+    want_h, want_y = _combine_norm_returns(fmt, residual, return_normed, return_hidden, inplace_residual)
+    qa, res_out, y16 = _combine_norm_outputs(slot_out, T, k, fmt, residual, want_h, want_y, inplace_residual)
+    with torch.cuda.device(slot_out.device):
+        rc = _lib.lib.petit_moe_combine_rmsnorm(_opt_ptr(qa), _opt_ptr(y16), _opt_ptr(res_out), _ptr(slot_out), _ptr(topk_weights), _ptr(topk_ids),
+                                                int(topk_ids.dtype == torch.int64), _opt_ptr(residual), _ptr(weight), float(eps),
+                                                float(weight_offset), T, topk, k, int(num_experts), _a_type(slot_out.dtype),
+                                                _QFORMATS[fmt] if fmt else 0, _stream(slot_out))
+    return _combine_norm_result(rc, "moe_combine_rmsnorm", slot_out.dtype, T, topk, k, num_experts, fmt, qa, res_out, y16)
+
+
 _SCORINGS = {"softmax": _lib.PETIT_ROUTE_SOFTMAX, "sigmoid": _lib.PETIT_ROUTE_SIGMOID}
 _LOGIT_DTYPES = {torch.float32: _lib.PETIT_DTYPE_FP32, torch.bfloat16: _lib.CXX_DTYPE_BF16, torch.float16: _lib.CXX_DTYPE_FP16}
 
