@@ -34,6 +34,7 @@ KS = (256, 1280, 2048, 2560, 5120)
 MS = (1, 3, 4, 5, 16, 17, 40, 128, 129, 257)
 NS = {"nv": (16, 272), "mx": (32, 288)}
 REGIMES = ("A", "B")
+REGIMES_ALL = ("A", "B", "G")                   # (the position seeds the generator: A and B keep the streams they always had)
 POISON = {True: 0x7FC1, False: 0x7E01}          # a NaN of the output type: no expected value is one
 GUARD = 4096                                    # bytes on either side of C and behind the scratch
 E4M3_BYTE = {0.5: 0x30, 1.0: 0x38, 1.5: 0x3C, 2.0: 0x40, 3.0: 0x44}
@@ -82,10 +83,13 @@ class Problem:
     pass
 
 
-def exact_problem(kind, is_bf16, m, n, k, regime, seed):
+def exact_problem(kind, is_bf16, m, n, k, regime, seed, shift=None):
     """-> Problem with the launch operands (a_bits u16 [m, k], q u8 [n, k/2], s u8 block scale bytes, gs, bias bits u16 [n] or None), the expected
-    output bits `want` u16 [m, n], and the float64 model behind them (a [m, k], w [n, k] = code value x block scale, acc, y, quantum)."""
-    rng = np.random.default_rng([seed, kind == "mx", is_bf16, m, n, k, regime == "B"])
+    output bits `want` u16 [m, n], and the float64 model behind them (a [m, k], w [n, k] = code value x block scale, acc, y, quantum).
+    Regime "G" (the gated epilogues, test_gated_contract.py): B's weights and activations, gs = 3 * 2^-shift, a bias of multiples of 2^-4 drawn for
+    every column, for the gate half from [1, 2], for the up half with magnitude in [1.5, 2] and either sign (the gated module says why); `want` is
+    then the PLAIN epilogue's, the gated module derives its own."""
+    rng = np.random.default_rng([seed, kind == "mx", is_bf16, m, n, k, REGIMES_ALL.index(regime)])
     group = 16 if kind == "nv" else 32
     P = Problem()
     if regime == "A":
@@ -97,7 +101,11 @@ def exact_problem(kind, is_bf16, m, n, k, regime, seed):
         code = rng.integers(0, 16, (n, k), dtype=np.uint8)
         scales = np.array([0.5, 1.0, 1.5, 2.0, 3.0] if kind == "nv" else [0.5, 1.0, 2.0, 4.0])
         a = rng.choice(np.array([-3.0, -2.0, -1.0, 1.0, 2.0, 3.0]), (m, k)) * (rng.random((m, k)) < 0.5)
-        P.gs, bias, P.quantum = 0.75, rng.integers(-32, 33, n) * 0.25, 0.25
+        if regime == "B":
+            P.gs, bias, P.quantum = 0.75, rng.integers(-32, 33, n) * 0.25, 0.25
+        else:
+            gate, up = rng.integers(16, 33, n // 2), rng.integers(24, 33, n // 2) * rng.choice(np.array([-1, 1]), n // 2)
+            P.gs, bias, P.quantum = 3.0 * 2.0 ** -shift, np.concatenate([gate, up]) * 2.0 ** -4, 0.25
     a = a + 0.0                                                                       # (no -0.0 activations)
     P.q = (code[:, 0::2] | (code[:, 1::2] << 4)).astype(np.uint8)
     sidx = rng.integers(0, len(scales), (n, k // group))
@@ -211,12 +219,35 @@ def with_split(sid: int, split: int) -> int:
     return (sid & ~(0xF << 60)) | (split << 60)
 
 
-class Device:
-    """One problem's operands on the device, its guarded C and scratch, and the launch + check of one solution id."""
+def k_slices(sid: int, k: int) -> int:
+    """The K slices (grid z) the launch of an explicit id makes: launch_geometry of csrc/solution.h restated on the id's fields.  nspans spans of
+    ks k-tiles go to `split` slices of kparts in-workgroup parts each, spans_per_part = ceil(nspans / (split kparts)), and the slices that then own no
+    span are dropped -- except by the streaming kinds (gemm_stream.hpp), whose grid z is the split the id names whatever K.  One slice: no slabs, no
+    reduce pass, the kernel's own epilogue writes C (and applies a gated activation)."""
+    split, ks = max(1, (sid >> 60) & 0xF), ((sid >> 16) & 0x1F) // 2
+    code, wm, wk = (sid >> 48) & 0xF, (sid >> 36) & 0xF, (sid >> 44) & 0xF
+    if code in (0, 1, 2, 3, 5, 6, 7, 10, 11) and wm == 1:                             # shape_is_stream: even_split
+        return split
+    if code in (4, 14, 15) or (code in (1, 2, 3, 10, 11) and wm == 2):               # decode / mid: one_slice (they refuse a split)
+        return 1
+    kparts = (2 if code in (12, 13) and wm == 3 else 1) if code in (8, 9, 12, 13) else wk
+    nspans = k // (128 * ks)
+    spp = -(-nspans // (split * kparts))
+    return -(-nspans // (spp * kparts)) if spp else 1
 
-    def __init__(self, pk, kind, is_bf16, m, n, k, P):
+
+ACTIVATION_NAMES = {0: None, 1: "silu_mul", 2: "swiglu_oai"}
+
+
+class Device:
+    """One problem's operands on the device, its guarded C and scratch, and the launch + check of one solution id.  activation 1 / 2 (the gated
+    epilogues): C is the m * n / 2 outputs between its guards, the Epilogue carries the activation and P.want is [m, n / 2].  `compare` judges
+    the outputs of a launch: here by equality with P.want; a subclass may judge otherwise (test_gated_contract.GatedDevice)."""
+
+    def __init__(self, pk, kind, is_bf16, m, n, k, P, activation=0):
         from petit_kernel import _lib
         self.pk, self.L, self.kind, self.is_bf16, self.m, self.n, self.k = pk, _lib, kind, is_bf16, m, n, k
+        self.activation, self.n_out, self.P = activation, n // 2 if activation else n, P
         self.dtype = torch.bfloat16 if is_bf16 else torch.float16
         dev16 = lambda b: torch.from_numpy(b.view(np.int16).copy()).to(DEV)
         self.a = dev16(P.a_bits)
@@ -234,26 +265,44 @@ class Device:
         self.want = dev16(P.want).reshape(-1)
         a_type = _lib.CXX_DTYPE_BF16 if is_bf16 else _lib.CXX_DTYPE_FP16
         self.hints = _lib.SolutionHints(a_type, _lib.CXX_DTYPE_FP4_E2M1 if kind == "nv" else _lib.CXX_DTYPE_MXFP4_E2M1, a_type, 0)
-        self.epilogue = None if self.bias is None else _lib.Epilogue(self.bias.data_ptr(), 0, 0)
-        self.epi = None if self.bias is None else C.byref(self.epilogue)
+        with_epilogue = self.bias is not None or activation
+        self.epilogue = _lib.Epilogue(None if self.bias is None else self.bias.data_ptr(), activation, 0) if with_epilogue else None
+        self.epi = C.byref(self.epilogue) if with_epilogue else None
         self.h = pk.PetitSolutionHints()
         self.h.a_type = self.h.c_type = self.dtype
         self.h.b_type = pk.DataType.float4_e2m1 if kind == "nv" else pk.DataType.mxfloat4_e2m1
         self.poison = POISON[is_bf16]
         g = GUARD // 2
-        self.c_all = torch.empty(g + m * n + g, dtype=torch.int16, device=DEV)       # [guard | m * n outputs | guard]
-        self.c_lo, self.c_out, self.c_hi = self.c_all[:g], self.c_all[g:g + m * n], self.c_all[g + m * n:]
+        mn = m * self.n_out
+        assert self.want.numel() == mn
+        self.c_all = torch.empty(g + mn + g, dtype=torch.int16, device=DEV)          # [guard | m * n_out outputs | guard]
+        self.c_lo, self.c_out, self.c_hi = self.c_all[:g], self.c_all[g:g + mn], self.c_all[g + mn:]
         self.guard = torch.full((g,), self.poison, dtype=torch.int16, device=DEV)
         self.ws_all = self.ws_ref = None
 
     def need(self, sid: int) -> int:
-        return int(self.L.lib.petit_gemm_workspace_bytes_ex(C.byref(self.hints), self.m, self.n, self.k, C.c_uint64(sid & (2 ** 64 - 1)), None))
+        return int(self.L.lib.petit_gemm_workspace_bytes_ex(C.byref(self.hints), self.m, self.n, self.k, C.c_uint64(sid & (2 ** 64 - 1)),
+                                                            self.epi if self.activation else None))
 
     def reserve_scratch(self, most: int) -> None:
         """One allocation that serves every id of the problem: an id is handed its declared bytes, all that follows is guard."""
         total = (most + GUARD + 511) // 512 * 512
         self.ws_all = torch.empty(total // 2, dtype=torch.int16, device=DEV)
         self.ws_ref = torch.full((total // 2,), self.poison, dtype=torch.int16, device=DEV).view(torch.uint8)
+
+    def compare(self) -> list:
+        """What is wrong with the outputs the launch just made left in C: none, or one line of the report."""
+        if torch.equal(self.c_out, self.want):
+            return []
+        got = self.c_out.cpu().numpy().view(np.uint16)
+        return [self.describe(got, np.flatnonzero(got != self.P.want.reshape(-1)))]
+
+    def describe(self, got, bad) -> str:
+        want = self.P.want.reshape(-1)
+        rows, cols = bad // self.n_out, bad % self.n_out
+        return (f"{bad.size} of {got.size} outputs differ, {int((got[bad] == self.poison).sum())} of them unwritten (still poison); first at "
+                f"(row {rows[0]}, col {cols[0]}): got {got[bad[0]]:#06x} want {want[bad[0]]:#06x}; rows {rows.min()}..{rows.max()}, "
+                f"cols {cols.min()}..{cols.max()}")
 
     def run(self, sid: int):
         """Poison, launch, compare on the device -> None, or the report of what is wrong."""
@@ -268,13 +317,8 @@ class Device:
         what = []
         if rc != 0:
             what.append(f"the queries accept the call, the launch returns {rc} ({self.L.error_string(rc)})")
-        elif not torch.equal(self.c_out, self.want):
-            got, want = self.c_out.cpu().numpy().view(np.uint16), self.want.cpu().numpy().view(np.uint16)
-            bad = np.flatnonzero(got != want)
-            rows, cols = bad // self.n, bad % self.n
-            what.append(f"{bad.size} of {got.size} outputs differ, {int((got[bad] == self.poison).sum())} of them unwritten (still poison); first at "
-                        f"(row {rows[0]}, col {cols[0]}): got {got[bad[0]]:#06x} want {want[bad[0]]:#06x}; rows {rows.min()}..{rows.max()}, "
-                        f"cols {cols.min()}..{cols.max()}")
+        else:
+            what += self.compare()
         if not torch.equal(self.c_lo, self.guard):
             what.append("the guard in front of C was written")
         if not torch.equal(self.c_hi, self.guard):
@@ -288,24 +332,28 @@ class Device:
         return f"m={self.m} n={self.n} k={self.k} id {sid:#x} [{self.L.describe_solution(sid)}]: " + "; ".join(what)
 
 
-def run_ids(pk, kind, is_bf16, m, n, k, regime, ids_of, counts):
-    """Every id `ids_of(D)` names for the problem: launched when the library resolves it, counted when it refuses.  -> the reports of what failed."""
-    P = exact_problem(kind, is_bf16, m, n, k, regime, 0)
-    D = Device(pk, kind, is_bf16, m, n, k, P)
+def run_ids(pk, kind, is_bf16, m, n, k, regime, ids_of, counts, activation=0, P=None, device=Device):
+    """Every id `ids_of(D)` names for the problem: launched when the library resolves it, counted when it refuses.  -> the reports of what failed.
+    activation 1 / 2: the gated epilogues on the problem P of the caller (regime "G" with its [m, n / 2] expectation), judged by `device`.
+    counts["collapsed"]: the launched ids that name a K split and run as ONE slice (k_slices)."""
+    P = P or exact_problem(kind, is_bf16, m, n, k, regime, 0)
+    D = device(pk, kind, is_bf16, m, n, k, P, activation)
     enumerated, ids = ids_of(D)
     runnable = []
     for sid in ids:
-        if pk.ops.resolve_solution(D.h, m, n, k, sid) != 0:
+        if pk.ops.resolve_solution(D.h, m, n, k, sid, activation=ACTIVATION_NAMES[activation]) != 0:
             runnable.append(sid)
         else:
             counts["refused"] += 1
-    assert len(runnable) >= len(enumerated) > 0, "every enumerated id runs"
+    # (a gated epilogue is refused by the kernels that cannot pair the halves: odd n-tiles per wave unsplit, the LDS-shared kernel)
+    assert (runnable if activation else len(runnable) >= len(enumerated) > 0), "every enumerated id runs"
     D.reserve_scratch(max(D.need(sid) for sid in runnable))
     failures = []
     for sid in runnable:
         report = D.run(sid)
         counts["launched"] += 1
         counts["split"] += sid >= 0 and (sid >> 60) & 0xF > 1
+        counts["collapsed"] = counts.get("collapsed", 0) + (sid >= 0 and (sid >> 60) & 0xF > 1 and k_slices(sid, k) == 1)
         if report:
             failures.append(f"regime {regime}: {report}")
     return failures
