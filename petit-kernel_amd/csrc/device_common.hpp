@@ -149,7 +149,9 @@ __device__ __forceinline__ f16x8 unpack_mx(Fp16, unsigned w, float s) {
 }
 __device__ __forceinline__ f16x8 unpack_mx(Fp16Mx, unsigned w, float s) { return unpack_mx(Fp16{}, w, s); }
 
-// 8 fp16 values -> (hi, lo) bf16 fragments with hi + lo == the fp16 value exactly.
+// 8 fp16 values -> (hi, lo) bf16 fragments with hi + lo == the fp16 value exactly.  +-inf goes to hi alone: lo = f - hi would be inf - inf = NaN
+// and make every output of the row NaN where the fast body and IEEE arithmetic give +-inf.  A NaN needs no care: hi may lose its payload to the
+// truncation (and read inf), but lo = NaN - hi is a NaN whatever hi is.
 __device__ __forceinline__ void split_f16(const u32x4 &h, u32x4 &hi, u32x4 &lo) {
 #pragma unroll
     for (int d = 0; d < 4; ++d) {
@@ -158,8 +160,8 @@ __device__ __forceinline__ void split_f16(const u32x4 &h, u32x4 &hi, u32x4 &lo) 
         const float f0 = (float)p[0], f1 = (float)p[1];             // exact
         const unsigned u0 = __builtin_bit_cast(unsigned, f0) & 0xffff0000u;
         const unsigned u1 = __builtin_bit_cast(unsigned, f1) & 0xffff0000u;
-        const float l0 = f0 - __builtin_bit_cast(float, u0);       // <= 3 significant bits: exact,
-        const float l1 = f1 - __builtin_bit_cast(float, u1);       // and exactly a bf16
+        const float l0 = __builtin_isinf(f0) ? 0.f : f0 - __builtin_bit_cast(float, u0); // <= 3 significant bits: exact,
+        const float l1 = __builtin_isinf(f1) ? 0.f : f1 - __builtin_bit_cast(float, u1); // and exactly a bf16
         hi[d] = (u0 >> 16) | u1;
         lo[d] = (__builtin_bit_cast(unsigned, l0) >> 16) | (__builtin_bit_cast(unsigned, l1) & 0xffff0000u);
     }

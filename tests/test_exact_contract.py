@@ -83,12 +83,16 @@ class Problem:
     pass
 
 
-def exact_problem(kind, is_bf16, m, n, k, regime, seed, shift=None):
+def exact_problem(kind, is_bf16, m, n, k, regime, seed, shift=None, mx_shift=0, switch=None):
     """-> Problem with the launch operands (a_bits u16 [m, k], q u8 [n, k/2], s u8 block scale bytes, gs, bias bits u16 [n] or None), the expected
     output bits `want` u16 [m, n], and the float64 model behind them (a [m, k], w [n, k] = code value x block scale, acc, y, quantum).
     Regime "G" (the gated epilogues, test_gated_contract.py): B's weights and activations, gs = 3 * 2^-shift, a bias of multiples of 2^-4 drawn for
     every column, for the gate half from [1, 2], for the up half with magnitude in [1.5, 2] and either sign (the gated module says why); `want` is
-    then the PLAIN epilogue's, the gated module derives its own."""
+    then the PLAIN epilogue's, the gated module derives its own.
+    Two options of test_value_contract.py on MXFP4 weights, applied after every draw (the streams of A, B and G stay what they were):
+    mx_shift = d moves every e8m0 byte by d and multiplies the launched gs by 2^-d (P.gs; the model keeps w, acc, y and `want` of the unshifted
+    problem: every weight moved by one power of two); switch = "mid" / "last" zeroes chosen 32-blocks (codes 0 or 8) under a scale byte outside
+    114..140 (switch_blocks), which the model's w, acc, y and `want` follow."""
     rng = np.random.default_rng([seed, kind == "mx", is_bf16, m, n, k, REGIMES_ALL.index(regime)])
     group = 16 if kind == "nv" else 32
     P = Problem()
@@ -112,14 +116,41 @@ def exact_problem(kind, is_bf16, m, n, k, regime, seed, shift=None):
     sval = scales[sidx]
     sbyte = [E4M3_BYTE[v] for v in scales] if kind == "nv" else [127 + int(np.log2(v)) for v in scales]      # e4m3 bytes / e8m0 126..129
     P.s = np.array(sbyte, dtype=np.uint8)[sidx]
-    P.a, P.w = a, FP4[code] * np.repeat(sval, group, axis=1)
+    keep = np.ones((n, k), dtype=bool)
+    if switch is not None:
+        assert kind == "mx"
+        P.switched = switch_blocks(n, k, seed, switch)
+        for row, blk, byte, negative in P.switched:
+            code[row, 32 * blk:32 * blk + 32], P.s[row, blk], keep[row, 32 * blk:32 * blk + 32] = 8 * negative, byte, False
+        P.q = (code[:, 0::2] | (code[:, 1::2] << 4)).astype(np.uint8)
+    if mx_shift:
+        assert kind == "mx" and 1 <= int(P.s.min()) + mx_shift and int(P.s.max()) + mx_shift <= 254
+        P.s = (P.s.astype(np.int64) + mx_shift).astype(np.uint8)
+    P.a, P.w = a, FP4[code] * np.repeat(sval, group, axis=1) * keep
     P.a_bits = to_bits(a, is_bf16)
     P.bias = bias
     P.bias_bits = None if bias is None else to_bits(bias, is_bf16)
     P.acc = a @ P.w.T                                                                 # float64: exact, see the preconditions
     P.y = P.acc * P.gs + (0.0 if bias is None else bias[None, :])                     # (+ 0.0: the kernel's fma adds a +0 bias, -0 becomes +0)
     P.want = rne_bits(P.y, is_bf16)
+    P.mx_shift, P.gs = mx_shift, P.gs * 2.0 ** -mx_shift                              # (the launched gs; y above is the unshifted problem's)
     return P
+
+
+def switch_blocks(n, k, seed, variant):
+    """[(row, 32-block, scale byte, negative zeros)] of regime "S": the placement of test_gpu_parity.mx_f16_scale_profiles' switch profile -- every
+    even 16-row tile gets one block in the second half of K, a few tiles one anywhere, row 5 the very first block -- or, variant "last", every
+    even tile one block in the last 256 k, so that the fp16 x MXFP4 kernels switch bodies right before their accumulators join."""
+    rng = np.random.default_rng([seed, n, k, variant == "last", 0x53])
+    kb, out = k // 32, {}
+    for t in range(0, n // 16, 2):
+        blk = kb - 8 + int(rng.integers(0, 8)) if variant == "last" else kb // 2 + int(rng.integers(0, kb - kb // 2))
+        out[(16 * t + int(rng.integers(0, 16)), blk)] = int(rng.choice([100, 113, 141, 143]))
+    if variant != "last":
+        for t in rng.integers(0, n // 16, max(1, n // 64)):
+            out[(16 * int(t) + int(rng.integers(0, 16)), int(rng.integers(0, kb)))] = int(rng.choice([100, 113, 141, 143]))
+        out[(5 % n, 0)] = 141
+    return [(row, blk, byte, int(rng.integers(0, 2))) for (row, blk), byte in sorted(out.items())]
 
 
 def shares(P, is_bf16):
@@ -335,7 +366,8 @@ class Device:
 def run_ids(pk, kind, is_bf16, m, n, k, regime, ids_of, counts, activation=0, P=None, device=Device):
     """Every id `ids_of(D)` names for the problem: launched when the library resolves it, counted when it refuses.  -> the reports of what failed.
     activation 1 / 2: the gated epilogues on the problem P of the caller (regime "G" with its [m, n / 2] expectation), judged by `device`.
-    counts["collapsed"]: the launched ids that name a K split and run as ONE slice (k_slices)."""
+    counts["collapsed"]: the launched ids that name a K split and run as ONE slice (k_slices); counts["kinds"], where the caller put a set there:
+    the kind nibbles of the launched ids."""
     P = P or exact_problem(kind, is_bf16, m, n, k, regime, 0)
     D = device(pk, kind, is_bf16, m, n, k, P, activation)
     enumerated, ids = ids_of(D)
@@ -354,6 +386,8 @@ def run_ids(pk, kind, is_bf16, m, n, k, regime, ids_of, counts, activation=0, P=
         counts["launched"] += 1
         counts["split"] += sid >= 0 and (sid >> 60) & 0xF > 1
         counts["collapsed"] = counts.get("collapsed", 0) + (sid >= 0 and (sid >> 60) & 0xF > 1 and k_slices(sid, k) == 1)
+        if "kinds" in counts and sid >= 0:
+            counts["kinds"].add((sid >> 48) & 0xF)                                    # (the kind nibbles that ran: test_value_contract.py)
         if report:
             failures.append(f"regime {regime}: {report}")
     return failures

@@ -118,14 +118,15 @@ def expect(P, is_bf16, act):
 
 
 @functools.lru_cache(maxsize=4)
-def inputs(kind, is_bf16, m, n, k, seed):
-    return exact_problem(kind, is_bf16, m, n, k, "G", seed, shift=G_SHIFT[k][kind == "mx"])
+def inputs(kind, is_bf16, m, n, k, seed, mx_shift=0, switch=None):
+    return exact_problem(kind, is_bf16, m, n, k, "G", seed, shift=G_SHIFT[k][kind == "mx"], mx_shift=mx_shift, switch=switch)
 
 
-def gated_problem(kind, is_bf16, m, n, k, act, first_seed=0):
-    """The problem of a GPU case: regime G at the first seed whose undecided share is within the cap (the inputs are shared by both activations)."""
+def gated_problem(kind, is_bf16, m, n, k, act, first_seed=0, mx_shift=0, switch=None):
+    """The problem of a GPU case: regime G at the first seed whose undecided share is within the cap (the inputs are shared by both activations).
+    mx_shift / switch: exact_problem's two options for test_value_contract.py, under the same cap and the same band."""
     for seed in range(first_seed, first_seed + SEEDS_TRIED):
-        base = inputs(kind, is_bf16, m, n, k, seed)
+        base = inputs(kind, is_bf16, m, n, k, seed, mx_shift, switch)
         P = type(base)()
         P.__dict__.update(base.__dict__)
         P.seed = seed
