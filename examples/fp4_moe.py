@@ -63,6 +63,16 @@ def main():
     same = petit_kernel.fp4_moe_fused(x.to(dev), w13, p13, gs13.to(dev), w2, p2, gs2.to(dev), rw, rids, "nvfp4")
     assert torch.equal(routed.view(torch.int16), same.view(torch.int16))
     print(f"fp4_moe_routed: equals fp4_moe_fused on moe_route's ids {tuple(rids.shape)} and weights bit for bit")
+    # one step earlier, from the hidden state: the router's linear as the library's router GEMM (fp32 accumulation in an order the shape
+    # alone fixes, so a token's experts do not depend on its batch), then route + align on its partial sums -- two launches
+    router_w = (torch.randn(E, H, generator=g) / H ** 0.5).to(torch.bfloat16).to(dev)
+    from_hidden = petit_kernel.fp4_moe_routed(x.to(dev), None, w13, p13, gs13.to(dev), w2, p2, gs2.to(dev), topk, "nvfp4", scoring="softmax",
+                                              renormalize=True, router_weight=router_w)
+    own_logits = petit_kernel.moe_router_logits(x.to(dev), router_w)
+    from_logits = petit_kernel.fp4_moe_routed(x.to(dev), own_logits, w13, p13, gs13.to(dev), w2, p2, gs2.to(dev), topk, "nvfp4", scoring="softmax",
+                                              renormalize=True)
+    assert torch.equal(from_hidden.view(torch.int16), from_logits.view(torch.int16))
+    print(f"fp4_moe_routed(router_weight=...): equals the layer on moe_router_logits {tuple(own_logits.shape)} bit for bit")
     # the fused end: the layer's last launch also adds the residual stream, applies the NEXT block's RMSNorm and quantises its input for a
     # native-class GEMM -- bit for bit the layer followed by rmsnorm_quantize, one launch and one [T, H] round trip less.  (For a layer whose
     # combine is complete on this rank: with tensor or expert parallelism the all-reduce comes between the combine and the residual add.)

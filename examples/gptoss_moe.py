@@ -77,6 +77,12 @@ def main():
               f"rms err / rms {(err.pow(2).mean().sqrt() / ref.pow(2).mean().sqrt()).item():.3e})")
         routed = experts.forward_routed(x.cuda(), logits.cuda(), topk=topk, path=path)   # from the logits: route + align in one launch
         print(f"{path:6s}: forward_routed max |difference to forward| {(routed.float() - out.float()).abs().max().item():.4g}")
+        # from the hidden state: the router's linear (weight [E, hidden], float32 bias) as the library's router GEMM on the unpadded x
+        router_w = (torch.randn(experts.num_experts, x.size(1)) / x.size(1) ** 0.5).bfloat16().cuda()
+        router_b = torch.randn(experts.num_experts).cuda()
+        hidden = experts.forward_hidden(x.cuda(), router_w, router_b, topk=topk, path=path)
+        same = experts.forward_routed(x.cuda(), petit_kernel.moe_router_logits(x.cuda(), router_w, router_b), topk=topk, path=path)
+        print(f"{path:6s}: forward_hidden equals forward_routed on moe_router_logits: {torch.equal(hidden.view(torch.int16), same.view(torch.int16))}")
 
 
 if __name__ == "__main__":

@@ -735,8 +735,8 @@ int petit_moe_combine_rmsnorm_host(void *qa, void *y16, void *residual_out, cons
  * topk_group outside 1..n_group, topk > topk_group * (E / n_group), groups or a bias with the softmax scoring, several chunks without a
  * workspace; PETIT_ERROR_BAD_ARGUMENT for a logits_dtype or scoring that does not exist.  num_tokens == 0 is PETIT_OK (petit_moe_route_align
  * then writes the all-zero expert_offsets, as petit_moe_align does).  desc null = a zero-initialised one.
- * An expert map for expert parallelism and shared experts: the _ex entries below.
- * Not here: the router's own GEMM, auxiliary-loss outputs beyond keys_out.
+ * An expert map for expert parallelism and shared experts: the _ex entries below.  From the hidden state: "The router's GEMM" below.
+ * Not here: auxiliary-loss outputs beyond keys_out.
  */
 #define PETIT_ROUTE_SOFTMAX 0
 #define PETIT_ROUTE_SIGMOID 1
@@ -798,6 +798,54 @@ uint64_t petit_moe_route_align_ex_workspace_bytes(unsigned num_tokens, unsigned 
 int petit_moe_route_align_ex(const void *router_logits, int logits_dtype, unsigned num_tokens, unsigned num_experts, unsigned topk,
                              const petit_route_desc *desc, const petit_route_slots *slots, int32_t *topk_ids, float *topk_weights,
                              float *keys_out, int32_t *expert_offsets, int32_t *sorted_pos, int32_t *token_index, void *workspace, void *stream);
+
+/*
+ * The router's GEMM (no counterpart in the reference): router logits from the hidden state, logits [T][E] = hidden [T][K] . weight[E][K]^T
+ * (+ router_bias), and the routing above started from the hidden state in two launches.  hidden [T][K] and weight [E][K] are contiguous
+ * 16-bit tensors of one type (a_type PETIT_DTYPE_BF16 / _FP16; weight in the checkpoint's layout, no repack), both 16-byte aligned;
+ * router_bias is float32 [E] or null; the logits are float32.  Any E in 1..PETIT_MOE_MAX_EXPERTS.  No host sync, graph-capturable.
+ *
+ * Definition, honoured bit for bit whatever T is:
+ *     logit[t][e] = ( ... ((p_0 + p_1) + p_2) ... + p_{S-1} ) + router_bias[e]
+ *   fp32 additions in this order, no contraction; without a bias the last add is not made.  p_s is the accumulation of slice s of K,
+ *   k in [s L, min(K, (s + 1) L)), by one chain of v_mfma_f32_16x16x32_{bf16,f16} from a zero accumulator, k ascending in steps of 32.
+ *   S and L (a multiple of 32) are functions of (E, K, a_type) alone -- petit_moe_router_geometry -- never of T or of a row's position in the
+ *   batch: a token's logits, and with the tie rule above its experts, are a pure function of its hidden state.
+ *   Accuracy: products of two 16-bit values are exact in fp32, so |logit - exact| <= 2 u (K + S + 1) (sum_k |a_k w_k| + |bias|), u = 2^-24.
+ * Two forms produce those bits, chosen by T alone.  Small T (the split form): S x n-blocks x m-tiles workgroups store their partial tiles
+ *   to S slabs [T][E] of the workspace with plain stores -- no tickets, no fences, no atomics -- and the NEXT launch adds the slabs.  Large T
+ *   (the whole form): a workgroup walks all S slices, adding each slice's accumulation to a running total, and stores one slab.
+ *   petit_moe_router_slabs is the slab count of the form T gets: S or 1.
+ * Workspace: petit_moe_router_workspace_bytes = slabs * T * E * 4 rounded up to a multiple of 256 (0 for a shape the calls refuse);
+ *   petit_moe_route_hidden_workspace_bytes = that, plus T * E * 4 (rounded up likewise) when E > 512, plus
+ *   petit_moe_route_align_ex_workspace_bytes(T, topk, E, slots).
+ *
+ * petit_moe_router_logits writes the logits.  Launches: 1 when there is no bias and one slab (the GEMM writes straight into logits), else 2
+ *   (the GEMM, then a finishing launch that makes the definition's additions).
+ * petit_moe_route_hidden is petit_moe_route_align_ex (expert_offsets given) or petit_moe_route_ex (expert_offsets null: route only; sorted_pos
+ *   and token_index are then not read) on those logits as float32, same outputs bit for bit -- keys_out with the softmax scoring IS the
+ *   logit of the definition -- without the logits ever being stored: the route kernels add the slabs themselves.  A shared_gate_logits of the
+ *   slot list is float32 here.  Launches: with the align and T * (topk + S_shared) <= 1024, 2 (the GEMM, then route + align in one launch on
+ *   the slabs); larger T or route only: the GEMM and the route launch, plus the align's three when there is an align.  E > 512: one more, the
+ *   finishing launch in front of the route (the 16-keys-per-lane route kernel has no register left to add slabs), unless one slab without a
+ *   bias already is the logits.
+ * Errors, all before any launch: PETIT_ERROR_PROBLEM_SHAPE for null required pointers or a hidden / weight that is not 16-byte aligned,
+ *   K % 32 != 0 or K outside 32..16384, E outside 1..PETIT_MOE_MAX_EXPERTS, T >= 2^20, a null workspace when the byte query is not zero, and
+ *   everything petit_moe_route_align_ex refuses; PETIT_ERROR_BAD_ARGUMENT for an a_type that is not FP16 or BF16.  T == 0 is PETIT_OK (with
+ *   an align: the all-zero expert_offsets).
+ * Not here: fp32 router weights, a strided hidden, a one-launch form (a last-arriver combine costs what the launch boundary does).
+ */
+void petit_moe_router_geometry(unsigned num_experts, unsigned k, int a_type, unsigned *slices, unsigned *slice_k); /* S, L */
+unsigned petit_moe_router_slabs(unsigned num_tokens, unsigned num_experts, unsigned k, int a_type);
+uint64_t petit_moe_router_workspace_bytes(unsigned num_tokens, unsigned num_experts, unsigned k, int a_type);
+int petit_moe_router_logits(float *logits, const void *hidden, const void *weight, const float *router_bias, int a_type, unsigned num_tokens,
+                            unsigned num_experts, unsigned k, void *workspace, void *stream);
+uint64_t petit_moe_route_hidden_workspace_bytes(unsigned num_tokens, unsigned num_experts, unsigned k, int a_type, unsigned topk,
+                                                const petit_route_slots *slots);
+int petit_moe_route_hidden(const void *hidden, const void *weight, const float *router_bias, int a_type, unsigned num_tokens, unsigned num_experts,
+                           unsigned k, unsigned topk, const petit_route_desc *desc, const petit_route_slots *slots, int32_t *topk_ids,
+                           float *topk_weights, float *keys_out, int32_t *expert_offsets /* null: route only */, int32_t *sorted_pos,
+                           int32_t *token_index, void *workspace, void *stream);
 
 /*
  * Native-class MoE launch (no counterpart in the reference): the routed-expert launch on the block-scaled MFMA, the accuracy class of

@@ -14,7 +14,12 @@
 // the align's single workgroup when the routing is one chunk: the ids go to the LDS array the align sorts, route + align are ONE launch.
 // The _ex entries (petit_route_slots) make the same launch write the complete slot list of a token: the routed ids through an expert map
 // (global -> local, -1 when not local), then S shared-expert slots with ids L .. L + S - 1 -- lanes topk .. topk + S - 1 of the token's wave.
+// From the hidden state (petit_moe_route_hidden, "The router's GEMM"): the router GEMM of moe_router.hip leaves fp32 partial slabs, and the
+// kSlab instantiations of the same route code read a logit as the sum of the slabs in order plus the router bias; everything after the logit
+// is the code above.  Above 512 experts (the 16-key form has no register to spare) a finishing launch sums the slabs in front of the route.
 #include <hip/hip_runtime.h>
+
+#include <type_traits>
 
 #include "../../include/petit_amd.h"
 #include "device_common.hpp"
@@ -241,11 +246,42 @@ struct RouteArgs {
     const void *shared_gate; // [num_tokens][num_shared], dtype, or null
 };
 
+// the slab form's arguments (petit_moe_route_hidden): logits = slab 0 of n_slabs fp32 slabs [num_tokens][num_experts], slab_stride elements apart
+struct RouteSlabArgs : RouteArgs {
+    const float *router_bias; // [num_experts] or null: the router linear's own bias
+    size_t slab_stride;
+    unsigned n_slabs;
+};
+template <bool kSlab> using RouteArgsOf = std::conditional_t<kSlab, RouteSlabArgs, RouteArgs>;
+
 __device__ __forceinline__ float route_logit(const void *logits, int dtype, size_t i) {
     if (dtype == kDataTypeFp32)
         return ((const float *)logits)[i];
     const unsigned short h = ((const unsigned short *)logits)[i];
     return dtype == kDataTypeBf16 ? half_to_f32<true>(h) : half_to_f32<false>(h);
+}
+
+// The logit of expert e of the row, element i = row + e.  kSlab: the router GEMM's definition -- the slabs added in order, then the router bias.
+template <bool kSlab, class Args> __device__ __forceinline__ float route_source(const Args &ra, size_t i, unsigned e) {
+    if constexpr (!kSlab) {
+        return route_logit(ra.logits, ra.dtype, i);
+    } else {
+#pragma clang fp contract(off)
+        // every load first (one memory latency, not one per slab): slab min(s, n_slabs - 1) for s < kRouterMaxSlices -- a repeated
+        // address past the last slab, never an address outside them -- then the additions of the slabs that exist, in order
+        const float *p = (const float *)ra.logits + i;
+        const unsigned last = ra.n_slabs - 1;
+        float q[kRouterMaxSlices];
+#pragma unroll
+        for (unsigned s = 0; s < kRouterMaxSlices; ++s)
+            q[s] = p[(size_t)(s < last ? s : last) * ra.slab_stride];
+        const float b = ra.router_bias ? ra.router_bias[e] : 0.f;
+        float v = q[0];
+#pragma unroll
+        for (unsigned s = 1; s < kRouterMaxSlices; ++s)
+            v = s <= last ? v + q[s] : v;
+        return ra.router_bias ? v + b : v;
+    }
 }
 
 __device__ __forceinline__ float route_sigmoid(float x) {
@@ -327,8 +363,9 @@ template <unsigned d> __device__ __forceinline__ void top2_step(float &a1, float
 }
 
 // One token by one wave (all 64 lanes, wave-uniform control flow).  NJ = ceil(E / 64) rounded up to a power of two: keys per lane.
-// Lane r < topk returns slot r's id and weight.
-template <int NJ> __device__ __forceinline__ void route_token(const RouteArgs &ra, unsigned t, unsigned lane, int *id_out, float *w_out) {
+// Lane r < topk returns slot r's id and weight.  kSlab: the logits come from the router GEMM's slabs (route_source).
+template <int NJ, bool kSlab = false>
+__device__ __forceinline__ void route_token(const RouteArgsOf<kSlab> &ra, unsigned t, unsigned lane, int *id_out, float *w_out) {
 #pragma clang fp contract(off)
     const unsigned E = ra.num_experts;
     const size_t row = (size_t)t * E;
@@ -338,7 +375,7 @@ template <int NJ> __device__ __forceinline__ void route_token(const RouteArgs &r
         const unsigned e = (unsigned)j * 64u + lane;
         u[j] = 0;
         if (e < E) {
-            float key = route_logit(ra.logits, ra.dtype, row + e);
+            float key = route_source<kSlab>(ra, row + e, e);
             if (ra.sigmoid) {
                 key = route_sigmoid(key);
                 if (ra.bias)
@@ -416,7 +453,7 @@ template <int NJ> __device__ __forceinline__ void route_token(const RouteArgs &r
 
     // weights: lane r < topk holds slot r
     const bool mine = lane < ra.topk;
-    const float x = mine ? route_logit(ra.logits, ra.dtype, row + my_id) : 0.f;
+    const float x = mine ? route_source<kSlab>(ra, row + my_id, my_id) : 0.f;
     float v, denom = 1.f;
     bool divide = ra.renorm != 0;
     if (ra.sigmoid) {
@@ -431,7 +468,7 @@ template <int NJ> __device__ __forceinline__ void route_token(const RouteArgs &r
         } else { // the softmax over all E: each lane's experts in ascending order, then the wave's tree
             float part = 0.f;
             for (unsigned e = lane; e < E; e += 64)
-                part = part + expf(route_logit(ra.logits, ra.dtype, row + e) - mx);
+                part = part + expf(route_source<kSlab>(ra, row + e, e) - mx);
             denom = wave_sum(part);
             divide = true;
         }
@@ -467,13 +504,13 @@ template <class Args> __device__ __forceinline__ void route_slots(const Args &ra
 }
 
 // the grid form: one wave per token
-template <int NJ> __global__ __launch_bounds__(kRouteWaves * 64) void moe_route_kernel(RouteArgs ra) {
+template <int NJ, bool kSlab = false> __global__ __launch_bounds__(kRouteWaves * 64) void moe_route_kernel(RouteArgsOf<kSlab> ra) {
     const unsigned lane = threadIdx.x & 63u, t = blockIdx.x * kRouteWaves + (threadIdx.x >> 6);
     if (t >= ra.num_tokens)
         return; // (a whole wave)
     int id;
     float w;
-    route_token<NJ>(ra, t, lane, &id, &w);
+    route_token<NJ, kSlab>(ra, t, lane, &id, &w);
     route_slots(ra, t, lane, &id, &w);
     const unsigned slots = ra.topk + ra.num_shared; // (<= kMaxTopk: one lane each)
     if (lane < slots) {
@@ -484,7 +521,8 @@ template <int NJ> __global__ __launch_bounds__(kRouteWaves * 64) void moe_route_
 
 // one chunk (num_tokens * (topk + num_shared) <= kChunk): the workgroup's 16 waves route the tokens, the slot ids go to LDS as load_chunk leaves
 // them (and to memory with the weights, for the combine), and the align's one-chunk code follows on the L + S experts the slot ids name
-template <int NJ> __global__ __launch_bounds__(kChunk) void moe_route_align_one_kernel(RouteArgs ra, int *offsets, int *sorted_pos, int *token_index) {
+template <int NJ, bool kSlab = false>
+__global__ __launch_bounds__(kChunk) void moe_route_align_one_kernel(RouteArgsOf<kSlab> ra, int *offsets, int *sorted_pos, int *token_index) {
     __shared__ __attribute__((aligned(16))) int ids_s[kChunk]; // (read as int4: rank_in_chunk)
     __shared__ unsigned cnt[kChunk], wave_sums[kChunk / 64];
     const unsigned lane = threadIdx.x & 63u, slots = ra.topk + ra.num_shared, n_entries = ra.num_tokens * slots;
@@ -494,11 +532,11 @@ template <int NJ> __global__ __launch_bounds__(kChunk) void moe_route_align_one_
     for (unsigned t = threadIdx.x >> 6; t < ra.num_tokens; t += kChunk / 64) {
         int id;
         float w;
-        route_token<NJ>(ra, t, lane, &id, &w);
+        route_token<NJ, kSlab>(ra, t, lane, &id, &w);
         if constexpr (NJ == 16) {
             // the 16-key form has no register to spare for the slot list's arguments across route_token: read them from the kernel
             // argument segment (scalar loads, RouteArgs is the first argument) once per token instead
-            typedef const __attribute__((address_space(4))) RouteArgs *KernArgs;
+            typedef const __attribute__((address_space(4))) RouteArgsOf<kSlab> *KernArgs;
             KernArgs ka = (KernArgs)__builtin_amdgcn_kernarg_segment_ptr();
             asm volatile("" : "+s"(ka));
             route_slots(*ka, t, lane, &id, &w);
@@ -569,11 +607,25 @@ int route_check(int logits_dtype, unsigned num_tokens, unsigned num_experts, uns
     return kOk;
 }
 
-template <int NJ> void launch_route(const RouteArgs &ra, bool with_align, int32_t *offsets, int32_t *sorted_pos, int32_t *token_index, hipStream_t s) {
+template <int NJ, bool kSlab = false>
+void launch_route(const RouteArgsOf<kSlab> &ra, bool with_align, int32_t *offsets, int32_t *sorted_pos, int32_t *token_index, hipStream_t s) {
     if (with_align)
-        hipLaunchKernelGGL(moe_route_align_one_kernel<NJ>, dim3(1), dim3(kChunk), 0, s, ra, offsets, sorted_pos, token_index);
+        hipLaunchKernelGGL((moe_route_align_one_kernel<NJ, kSlab>), dim3(1), dim3(kChunk), 0, s, ra, offsets, sorted_pos, token_index);
     else
-        hipLaunchKernelGGL(moe_route_kernel<NJ>, dim3((ra.num_tokens + kRouteWaves - 1) / kRouteWaves), dim3(kRouteWaves * 64), 0, s, ra);
+        hipLaunchKernelGGL((moe_route_kernel<NJ, kSlab>), dim3((ra.num_tokens + kRouteWaves - 1) / kRouteWaves), dim3(kRouteWaves * 64), 0, s, ra);
+}
+
+// the slab form, E <= 512 (above: a finishing launch and the plain form, petit_moe_route_hidden)
+void launch_route_slabs(const RouteSlabArgs &ra, bool with_align, int32_t *offsets, int32_t *sorted_pos, int32_t *token_index, hipStream_t s) {
+    const unsigned E = ra.num_experts;
+    if (E <= 64)
+        launch_route<1, true>(ra, with_align, offsets, sorted_pos, token_index, s);
+    else if (E <= 128)
+        launch_route<2, true>(ra, with_align, offsets, sorted_pos, token_index, s);
+    else if (E <= 256)
+        launch_route<4, true>(ra, with_align, offsets, sorted_pos, token_index, s);
+    else
+        launch_route<8, true>(ra, with_align, offsets, sorted_pos, token_index, s);
 }
 
 void launch_route(const RouteArgs &ra, bool with_align, int32_t *offsets, int32_t *sorted_pos, int32_t *token_index, hipStream_t s) {
@@ -712,6 +764,67 @@ int petit_moe_route_align(const void *router_logits, int logits_dtype, unsigned 
                           int32_t *sorted_pos, int32_t *token_index, void *workspace, void *stream) {
     return petit_moe_route_align_ex(router_logits, logits_dtype, num_tokens, num_experts, topk, desc, nullptr, topk_ids, topk_weights, keys_out,
                                     expert_offsets, sorted_pos, token_index, workspace, stream);
+}
+
+// --- from the hidden state: the router GEMM (moe_router.hip), then the route on its slabs ("The router's GEMM") --------------------------------
+// workspace: [the GEMM's slabs][E > 512: the finished logits][the align's workspace], each rounded up to 256 bytes
+
+static uint64_t route_hidden_logit_bytes(unsigned num_tokens, unsigned num_experts) {
+    return num_experts > 512 ? ((uint64_t)num_tokens * num_experts * 4 + 255) / 256 * 256 : 0;
+}
+
+uint64_t petit_moe_route_hidden_workspace_bytes(unsigned num_tokens, unsigned num_experts, unsigned k, int a_type, unsigned topk,
+                                                const petit_route_slots *slots) {
+    if (router_shape_rc(num_tokens, num_experts, k, a_type) != kOk)
+        return 0;
+    return router_slab_bytes(num_tokens, num_experts, k, a_type) + route_hidden_logit_bytes(num_tokens, num_experts) +
+           petit_moe_route_align_ex_workspace_bytes(num_tokens, topk, num_experts, slots);
+}
+
+int petit_moe_route_hidden(const void *hidden, const void *weight, const float *router_bias, int a_type, unsigned num_tokens, unsigned num_experts,
+                           unsigned k, unsigned topk, const petit_route_desc *desc, const petit_route_slots *slots, int32_t *topk_ids,
+                           float *topk_weights, float *keys_out, int32_t *expert_offsets, int32_t *sorted_pos, int32_t *token_index, void *workspace,
+                           void *stream) {
+    int rc = router_shape_rc(num_tokens, num_experts, k, a_type);
+    if (rc != kOk)
+        return rc;
+    RouteSlabArgs ra;
+    rc = route_check(kDataTypeFp32, num_tokens, num_experts, topk, desc, slots, &ra); // (the logits, and a shared gate's, are fp32 here)
+    if (rc != kOk)
+        return rc;
+    const bool with_align = expert_offsets != nullptr;
+    const unsigned n_slots = topk + ra.num_shared, align_experts = ra.num_local + ra.num_shared;
+    if (num_tokens == 0)
+        return with_align ? petit_moe_align(topk_ids, 0, 0, n_slots, align_experts, expert_offsets, sorted_pos, token_index, nullptr, stream) : kOk;
+    if (!hidden || !weight || !topk_ids || !topk_weights || !workspace || (with_align && (!sorted_pos || !token_index)) ||
+        ((uintptr_t)hidden | (uintptr_t)weight) % 16 != 0)
+        return kErrProblemShape;
+    const hipStream_t s = (hipStream_t)stream;
+    float *slabs = (float *)workspace;
+    const uint64_t slab_bytes = router_slab_bytes(num_tokens, num_experts, k, a_type);
+    float *finished = (float *)((char *)workspace + slab_bytes);
+    void *align_ws = (char *)workspace + slab_bytes + route_hidden_logit_bytes(num_tokens, num_experts);
+    const unsigned n_slabs = router_slabs(num_tokens, num_experts, k, a_type);
+    const bool one_launch = with_align && align_chunks(num_tokens, n_slots) <= 1;
+
+    router_gemm_launch(slabs, hidden, weight, a_type, num_tokens, num_experts, k, s);
+    ra.ids = topk_ids, ra.weights = topk_weights, ra.keys = keys_out;
+    if (n_slabs == 1 && !router_bias) { // the one slab IS the logits: the plain route reads it
+        ra.logits = slabs;
+        launch_route(ra, one_launch, expert_offsets, sorted_pos, token_index, s);
+    } else if (num_experts > 512) {
+        router_finish_launch(finished, slabs, n_slabs, router_bias, num_tokens, num_experts, s);
+        ra.logits = finished;
+        launch_route(ra, one_launch, expert_offsets, sorted_pos, token_index, s);
+    } else {
+        ra.logits = slabs, ra.router_bias = router_bias, ra.slab_stride = (size_t)num_tokens * num_experts, ra.n_slabs = n_slabs;
+        launch_route_slabs(ra, one_launch, expert_offsets, sorted_pos, token_index, s);
+    }
+    if (hipGetLastError() != hipSuccess)
+        return kErrLaunch;
+    if (with_align && !one_launch)
+        return petit_moe_align(topk_ids, 0, num_tokens, n_slots, align_experts, expert_offsets, sorted_pos, token_index, align_ws, stream);
+    return kOk;
 }
 
 } // extern "C"

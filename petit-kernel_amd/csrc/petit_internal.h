@@ -207,6 +207,18 @@ int moe_combine_rmsnorm(void *qa, void *y16, void *residual_out, const void *slo
 int moe_combine_rmsnorm_host(void *qa, void *y16, void *residual_out, const void *slot_out, const float *topk_weights, const void *topk_ids,
                              int ids_are_int64, const void *residual, const void *weight, float eps, float weight_offset, unsigned num_tokens,
                              unsigned topk, unsigned k, unsigned num_experts, int a_type, int format);
+// moe_router.hip: the router's GEMM (include/petit_amd.h "The router's GEMM"), as the route entries of moe_route.hip use it.  router_shape_rc:
+// the shape / dtype refusals (kOk when the call can run).  router_slab_bytes: the fp32 slabs of the form T gets, rounded up to 256 bytes.
+// router_gemm_launch writes router_slabs(T, ...) slabs [T][E] back to back; router_finish_launch sums n_slabs of them in order and adds the
+// bias (null: none) into logits [T][E] -- the definition's additions, one thread per logit.
+constexpr unsigned kRouterMaxSlices = 16; // S <= 16: what a route wave loads and adds per logit
+int router_shape_rc(unsigned num_tokens, unsigned num_experts, unsigned k, int a_type);
+unsigned router_slabs(unsigned num_tokens, unsigned num_experts, unsigned k, int a_type);
+uint64_t router_slab_bytes(unsigned num_tokens, unsigned num_experts, unsigned k, int a_type);
+void router_gemm_launch(float *slabs, const void *hidden, const void *weight, int a_type, unsigned num_tokens, unsigned num_experts, unsigned k,
+                        hipStream_t stream);
+void router_finish_launch(float *logits, const float *slabs, unsigned n_slabs, const float *router_bias, unsigned num_tokens,
+                          unsigned num_experts, hipStream_t stream);
 // dequant.hip: dense expansion of packed weights (debug aid); out_kind 0 f32, 1 bf16, 2 fp16
 int dequant_packed(void *out, const void *w, const void *s, float gs, unsigned n, unsigned k, int b_type, int out_kind, hipStream_t stream);
 

@@ -565,6 +565,82 @@ std::tuple<at::Tensor, at::Tensor, at::Tensor, at::Tensor, at::Tensor, at::Tenso
     return {w, ids, sorted_pos, offsets, token_index, keys};
 }
 
+// the router's GEMM (petit_moe_router_logits / petit_moe_route_hidden).  The argument checks and their texts are stated once, in
+// petit_kernel/ops.py (_check_router, _check_route_hidden), which petit_kernel/compiled.py runs in front of these ops; what is checked here is
+// what keeps a direct torch.ops call inside its tensors.
+#define PETIT_ROUTER_ARGS const at::Tensor &hidden, const at::Tensor &router_weight, const std::optional<at::Tensor> &router_bias
+void check_router(PETIT_ROUTER_ARGS) {
+    TORCH_CHECK(hidden.is_cuda() && hidden.dim() == 2 && hidden.is_contiguous() &&
+                    (hidden.scalar_type() == at::kBFloat16 || hidden.scalar_type() == at::kHalf) && router_weight.is_cuda() &&
+                    router_weight.device() == hidden.device() && router_weight.dim() == 2 && router_weight.is_contiguous() &&
+                    router_weight.scalar_type() == hidden.scalar_type() && router_weight.size(1) == hidden.size(1) &&
+                    (!router_bias || (router_bias->is_cuda() && router_bias->device() == hidden.device() && router_bias->is_contiguous() &&
+                                      router_bias->scalar_type() == at::kFloat && router_bias->dim() == 1 &&
+                                      router_bias->size(0) == router_weight.size(0))),
+                "hidden [num_tokens, k] and router_weight [num_experts, k] must be contiguous bfloat16 / float16 GPU tensors of one dtype, "
+                "router_bias a contiguous float32 [num_experts] tensor on their device");
+}
+at::Tensor moe_router_logits(PETIT_ROUTER_ARGS) {
+    check_router(hidden, router_weight, router_bias);
+    const int64_t T = hidden.size(0), K = hidden.size(1), E = router_weight.size(0);
+    const c10::hip::HIPGuardMasqueradingAsCUDA guard(hidden.device());
+    const int a_type = a_type_of(hidden.scalar_type());
+    at::Tensor logits = at::empty({T, E}, hidden.options().dtype(at::kFloat));
+    const uint64_t ws_bytes = petit_moe_router_workspace_bytes((unsigned)T, (unsigned)E, (unsigned)K, a_type);
+    at::Tensor ws = at::empty({(int64_t)ws_bytes}, hidden.options().dtype(at::kByte));
+    const int rc = petit_moe_router_logits((float *)logits.data_ptr(), hidden.data_ptr(), router_weight.data_ptr(),
+                                           router_bias ? (const float *)router_bias->data_ptr() : nullptr, a_type, (unsigned)T, (unsigned)E,
+                                           (unsigned)K, ws_bytes ? ws.data_ptr() : nullptr, stream_of(hidden));
+    TORCH_CHECK(rc != PETIT_ERROR_PROBLEM_SHAPE, "Incompatible router shape (num_tokens=", T, ", num_experts=", E, ", k=", K, ")");
+    TORCH_CHECK(rc == PETIT_OK, "moe_router_logits: ", petit_error_string(rc));
+    return logits;
+}
+// (the routing's arguments are PETIT_ROUTE_ARGS without the logits)
+#define PETIT_ROUTE_HIDDEN_ARGS                                                                                                             \
+    PETIT_ROUTER_ARGS, int64_t topk, bool align, int64_t scoring, bool renormalize, const std::optional<at::Tensor> &bias, int64_t n_group, \
+        int64_t topk_group, double routed_scaling_factor, bool return_keys, PETIT_ROUTE_SLOTS_ARGS
+std::tuple<at::Tensor, at::Tensor, at::Tensor, at::Tensor, at::Tensor, at::Tensor> moe_route_hidden(PETIT_ROUTE_HIDDEN_ARGS) {
+    check_router(hidden, router_weight, router_bias);
+    const int64_t T = hidden.size(0), K = hidden.size(1), E = router_weight.size(0);
+    const auto f32 = hidden.options().dtype(at::kFloat);
+    const auto i32 = hidden.options().dtype(at::kInt);
+    TORCH_CHECK(scoring == PETIT_ROUTE_SOFTMAX || scoring == PETIT_ROUTE_SIGMOID, "scoring must be 'softmax' or 'sigmoid'");
+    TORCH_CHECK(E >= 1 && E <= PETIT_MOE_MAX_EXPERTS && topk >= 1 && topk <= std::min<int64_t>(E, PETIT_MOE_MAX_TOPK) && n_group >= 1 &&
+                    topk_group >= 1 && num_shared >= 0 && topk + num_shared <= PETIT_MOE_MAX_TOPK,
+                "moe_route_hidden: num_experts, topk, n_group, topk_group or num_shared out of range");
+    const int64_t S = num_shared, L = num_local_experts <= 0 ? E : num_local_experts, n_slots = topk + S;
+    TORCH_CHECK(L <= E && L + S <= PETIT_MOE_MAX_EXPERTS && (expert_map || L == E), "moe_route_hidden: num_local_experts out of range");
+    auto on_dev = [&](const at::Tensor &t, at::ScalarType st, int64_t n) {
+        return t.is_cuda() && t.device() == hidden.device() && t.scalar_type() == st && t.is_contiguous() && t.numel() == n;
+    };
+    TORCH_CHECK((!bias || (scoring == PETIT_ROUTE_SIGMOID && on_dev(*bias, at::kFloat, E))) && (!expert_map || on_dev(*expert_map, at::kInt, E)) &&
+                    (!shared_gate_logits || (S >= 1 && on_dev(*shared_gate_logits, at::kFloat, T * S))),
+                "moe_route_hidden: bias float32 [num_experts] (sigmoid scoring), expert_map int32 [num_experts] and shared_gate_logits float32 "
+                "[num_tokens, num_shared] must be contiguous tensors on hidden's device");
+    petit_route_desc d{};
+    d.scoring = (int)scoring, d.renormalize = renormalize, d.n_group = (unsigned)n_group, d.topk_group = (unsigned)topk_group;
+    d.routed_scaling_factor = (float)routed_scaling_factor, d.bias = bias ? (const float *)bias->data_ptr() : nullptr;
+    petit_route_slots sl{};
+    sl.expert_map = expert_map ? (const int32_t *)expert_map->data_ptr() : nullptr;
+    sl.num_local_experts = (unsigned)L, sl.num_shared = (unsigned)S, sl.shared_weight = (float)shared_weight;
+    sl.shared_gate_logits = shared_gate_logits ? shared_gate_logits->data_ptr() : nullptr;
+    const c10::hip::HIPGuardMasqueradingAsCUDA guard(hidden.device());
+    const int a_type = a_type_of(hidden.scalar_type());
+    at::Tensor ids = at::empty({T, n_slots}, i32), w = at::empty({T, n_slots}, f32);
+    at::Tensor keys = return_keys ? at::empty({T, E}, f32) : at::empty({0}, f32);
+    const int64_t entries = align ? T * n_slots : 0;
+    at::Tensor sorted_pos = at::empty({entries}, i32), token_index = at::empty({entries}, i32), offsets = at::empty({align ? L + S + 1 : 0}, i32);
+    const uint64_t ws_bytes = petit_moe_route_hidden_workspace_bytes((unsigned)T, (unsigned)E, (unsigned)K, a_type, (unsigned)topk, &sl);
+    at::Tensor ws = at::empty({(int64_t)ws_bytes}, hidden.options().dtype(at::kByte));
+    const int rc = petit_moe_route_hidden(hidden.data_ptr(), router_weight.data_ptr(), router_bias ? (const float *)router_bias->data_ptr() : nullptr,
+                                          a_type, (unsigned)T, (unsigned)E, (unsigned)K, (unsigned)topk, &d, &sl, (int32_t *)ids.data_ptr(),
+                                          (float *)w.data_ptr(), return_keys ? (float *)keys.data_ptr() : nullptr,
+                                          align ? (int32_t *)offsets.data_ptr() : nullptr, align ? (int32_t *)sorted_pos.data_ptr() : nullptr,
+                                          align ? (int32_t *)token_index.data_ptr() : nullptr, ws_bytes ? ws.data_ptr() : nullptr, stream_of(hidden));
+    route_rc(rc, "moe_route_hidden", T, E, topk, n_group, topk_group);
+    return {w, ids, sorted_pos, offsets, token_index, keys};
+}
+
 // native-class MoE launch (petit_gemm_native_moe); the same checks and texts as petit_kernel/ops.py _mul_native_moe.  A: 16-bit [a_rows,
 // size_k] (a_format 0), or the bytes of the size_m quantised grouped rows (a_format 8 / 6 / 4; a_type names their 16-bit dtype).  Returns
 // 16-bit [c_rows, n_out], or with out_format the bytes of the quantised grouped [size_m, size_n / 2] rows.
@@ -742,6 +818,17 @@ std::tuple<at::Tensor, at::Tensor, at::Tensor, at::Tensor, at::Tensor, at::Tenso
     return {at::empty({T, n_slots}, f32),         at::empty({T, n_slots}, i32),     at::empty({T * n_slots}, i32),
             at::empty({L + num_shared + 1}, i32), at::empty({T * n_slots}, i32), (return_keys ? at::empty({T, E}, f32) : at::empty({0}, f32))};
 }
+at::Tensor moe_router_logits_meta(PETIT_ROUTER_ARGS) {
+    return at::empty({hidden.size(0), router_weight.size(0)}, hidden.options().dtype(at::kFloat));
+}
+std::tuple<at::Tensor, at::Tensor, at::Tensor, at::Tensor, at::Tensor, at::Tensor> moe_route_hidden_meta(PETIT_ROUTE_HIDDEN_ARGS) {
+    const int64_t T = hidden.size(0), E = router_weight.size(0), n_slots = topk + num_shared;
+    const int64_t L = num_local_experts <= 0 ? E : num_local_experts, entries = align ? T * n_slots : 0;
+    const auto f32 = hidden.options().dtype(at::kFloat);
+    const auto i32 = hidden.options().dtype(at::kInt);
+    return {at::empty({T, n_slots}, f32),        at::empty({T, n_slots}, i32), at::empty({entries}, i32), at::empty({align ? L + num_shared + 1 : 0}, i32),
+            at::empty({entries}, i32), (return_keys ? at::empty({T, E}, f32) : at::empty({0}, f32))};
+}
 
 } // namespace
 
@@ -791,6 +878,10 @@ TORCH_LIBRARY(petit_kernel, m) {
     ", Tensor? expert_map=None, int num_local_experts=-1, int num_shared=0, float shared_weight=1.0, Tensor? shared_gate_logits=None"
     m.def("moe_route_ex(" PETIT_ROUTE_SCHEMA PETIT_ROUTE_SLOTS_SCHEMA ") -> (Tensor, Tensor, Tensor)");
     m.def("moe_route_align_ex(" PETIT_ROUTE_SCHEMA PETIT_ROUTE_SLOTS_SCHEMA ") -> (Tensor, Tensor, Tensor, Tensor, Tensor, Tensor)");
+    m.def("moe_router_logits(Tensor hidden, Tensor router_weight, Tensor? router_bias=None) -> Tensor");
+    m.def("moe_route_hidden(Tensor hidden, Tensor router_weight, Tensor? router_bias, int topk, bool align=True, int scoring=0, "
+          "bool renormalize=True, Tensor? bias=None, int n_group=1, int topk_group=1, float routed_scaling_factor=1.0, bool return_keys=False"
+          PETIT_ROUTE_SLOTS_SCHEMA ") -> (Tensor, Tensor, Tensor, Tensor, Tensor, Tensor)");
     // round 3's op name (scales promised inside fp16's range): an alias of mul_mxfp4_a16 for one more round -- the kernels test the range themselves
     m.def("mul_mxfp4_a16_f16range(Tensor A, Tensor B, Tensor s, Tensor global_scale, int size_m, int size_n, int size_k, int solution_id, "
           "Tensor? bias=None, int activation=0) -> Tensor");
@@ -819,7 +910,9 @@ TORCH_LIBRARY(petit_kernel, m) {
     m.impl("moe_route", &moe_route);                            \
     m.impl("moe_route_align", &moe_route_align);                \
     m.impl("moe_route_ex", &moe_route_ex);                      \
-    m.impl("moe_route_align_ex", &moe_route_align_ex);
+    m.impl("moe_route_align_ex", &moe_route_align_ex);          \
+    m.impl("moe_router_logits", &moe_router_logits);            \
+    m.impl("moe_route_hidden", &moe_route_hidden);
 TORCH_LIBRARY_IMPL(petit_kernel, CUDA, m) { PETIT_IMPL_REAL(m) }
 TORCH_LIBRARY_IMPL(petit_kernel, CPU, m) { PETIT_IMPL_REAL(m) }
 TORCH_LIBRARY_IMPL(petit_kernel, Meta, m) {
@@ -847,4 +940,6 @@ TORCH_LIBRARY_IMPL(petit_kernel, Meta, m) {
     m.impl("moe_route_align", &moe_route_align_meta);
     m.impl("moe_route_ex", &moe_route_ex_meta);
     m.impl("moe_route_align_ex", &moe_route_align_ex_meta);
+    m.impl("moe_router_logits", &moe_router_logits_meta);
+    m.impl("moe_route_hidden", &moe_route_hidden_meta);
 }

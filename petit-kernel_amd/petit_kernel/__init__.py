@@ -196,6 +196,26 @@ def moe_route_align(router_logits: torch.Tensor, topk: int, *, scoring: str = "s
                                     expert_map, num_local_experts, num_shared, shared_weight, shared_gate_logits)
 
 
+def moe_router_logits(hidden: torch.Tensor, router_weight: torch.Tensor, router_bias: torch.Tensor = None) -> torch.Tensor:
+    # the router's linear: hidden [T, K] . router_weight [E, K]^T (+ router_bias float32 [E]) -> float32 [T, E] (include/petit_amd.h "The
+    # router's GEMM").  bfloat16 or float16, both alike, contiguous, the weight as the checkpoint stores it.  fp32 accumulation in an order that
+    # (E, K) alone fix: a token's logits -- and so its experts -- do not depend on the batch it sits in
+    return _impl.moe_router_logits(hidden, router_weight, router_bias)
+
+
+def moe_route_hidden(hidden: torch.Tensor, router_weight: torch.Tensor, topk: int, *, router_bias: torch.Tensor = None, align: bool = True,
+                     scoring: str = "softmax", renormalize: bool = True, bias: torch.Tensor = None, n_group: int = 1, topk_group: int = 1,
+                     routed_scaling_factor: float = 1.0, return_keys: bool = False, expert_map: torch.Tensor = None,
+                     num_local_experts: int = None, num_shared: int = 0, shared_weight: float = 1.0, shared_gate_logits: torch.Tensor = None):
+    # the routing from the hidden state: what moe_route_align (align=True) or moe_route (align=False) return on
+    # moe_router_logits(hidden, router_weight, router_bias), bit for bit, without the logits being stored: TWO launches for a decode batch
+    # (the router GEMM, then route + align on its partial sums).  `bias` is the sigmoid scoring's correction bias, `router_bias` the linear's own;
+    # shared_gate_logits is float32 [T, num_shared] here
+    return _impl.moe_route_hidden(hidden, router_weight, topk, router_bias, align, scoring, renormalize, bias, n_group, topk_group,
+                                  routed_scaling_factor, return_keys, expert_map, num_local_experts, num_shared, shared_weight,
+                                  shared_gate_logits)
+
+
 def mul_mxfp4_native_moe(a, b: torch.Tensor, s: torch.Tensor, global_scales: torch.Tensor, expert_offsets: torch.Tensor, size_m: int, size_n: int,
                          size_k: int, num_experts: int, a_row_index: torch.Tensor = None, c_row_index: torch.Tensor = None, c_rows: int = None,
                          solution_id: int = SOLUTION_AUTO_NATIVE_MXFP8, bias: torch.Tensor = None, activation: str = None, out_quantized: str = None):
@@ -301,6 +321,8 @@ __all__ = [
     "moe_combine_rmsnorm",
     "moe_route",
     "moe_route_align",
+    "moe_router_logits",
+    "moe_route_hidden",
     "fp4_moe_routed",
     "fp4_moe_native",
     "mul_mxfp4_native_moe",

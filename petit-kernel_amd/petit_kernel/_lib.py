@@ -133,6 +133,13 @@ _SIGNATURES = {
     "petit_moe_route_align_ex_workspace_bytes": (C.c_uint64, [C.c_uint] * 3 + [C.POINTER(RouteSlots)]),
     "petit_moe_route_align_ex": (C.c_int, [C.c_void_p, C.c_int] + [C.c_uint] * 3 + [C.POINTER(RouteDesc), C.POINTER(RouteSlots)] +
                                  [C.c_void_p] * 8),
+    "petit_moe_router_geometry": (None, [C.c_uint, C.c_uint, C.c_int, C.POINTER(C.c_uint), C.POINTER(C.c_uint)]),
+    "petit_moe_router_slabs": (C.c_uint, [C.c_uint, C.c_uint, C.c_uint, C.c_int]),
+    "petit_moe_router_workspace_bytes": (C.c_uint64, [C.c_uint, C.c_uint, C.c_uint, C.c_int]),
+    "petit_moe_router_logits": (C.c_int, [C.c_void_p] * 4 + [C.c_int] + [C.c_uint] * 3 + [C.c_void_p] * 2),
+    "petit_moe_route_hidden_workspace_bytes": (C.c_uint64, [C.c_uint, C.c_uint, C.c_uint, C.c_int, C.c_uint, C.POINTER(RouteSlots)]),
+    "petit_moe_route_hidden": (C.c_int, [C.c_void_p] * 3 + [C.c_int] + [C.c_uint] * 4 + [C.POINTER(RouteDesc), C.POINTER(RouteSlots)] +
+                               [C.c_void_p] * 8),
     "petit_gemm_mxfp4_native": (C.c_int, [C.c_void_p] * 5 + [C.c_uint] * 3 + [C.POINTER(SolutionHints), C.c_uint64, C.POINTER(Epilogue),
                                           C.POINTER(NativeArgs), C.c_void_p, C.c_uint64, C.c_void_p]),
     "petit_nvfp4_native_image_bytes": (C.c_uint64, [C.c_uint, C.c_uint]),

@@ -15,7 +15,7 @@ import torch
 
 from . import _lib  # loads libpetit_amd.so first (the binding links against it)
 from .ops import QuantizedActivations, _a_type, _activation as _act, _activation_operand, _quantized_format
-from .ops import _combine_norm_operands, _combine_norm_returns
+from .ops import _check_route_hidden, _check_router, _combine_norm_operands, _combine_norm_returns
 
 LIB_PATH = Path(_lib.LIB_PATH).parent / "libpetit_torch.so"
 _loaded = False
@@ -187,6 +187,23 @@ def moe_route_align_ex(router_logits, topk, scoring="softmax", renormalize=True,
         router_logits, int(topk), _scoring(scoring), bool(renormalize), bias, int(n_group), int(topk_group), float(routed_scaling_factor),
         bool(return_keys), *_slots_args(expert_map, num_local_experts, num_shared, shared_weight, shared_gate_logits))
     return (w, ids, sp, off, ti, keys) if return_keys else (w, ids, sp, off, ti)
+
+
+def moe_router_logits(hidden, router_weight, router_bias=None):
+    _check_router(hidden, router_weight, router_bias)
+    return torch.ops.petit_kernel.moe_router_logits(hidden, router_weight, router_bias)
+
+
+def moe_route_hidden(hidden, router_weight, topk, router_bias=None, align=True, scoring="softmax", renormalize=True, bias=None, n_group=1,
+                     topk_group=1, routed_scaling_factor=1.0, return_keys=False, expert_map=None, num_local_experts=None, num_shared=0,
+                     shared_weight=1.0, shared_gate_logits=None):
+    _check_route_hidden(hidden, router_weight, topk, router_bias, scoring, bias, n_group, topk_group, expert_map, num_local_experts, num_shared,
+                        shared_gate_logits)
+    w, ids, sp, off, ti, keys = torch.ops.petit_kernel.moe_route_hidden(
+        hidden, router_weight, router_bias, int(topk), bool(align), _scoring(scoring), bool(renormalize), bias, int(n_group), int(topk_group),
+        float(routed_scaling_factor), bool(return_keys), *_slots_args(expert_map, num_local_experts, num_shared, shared_weight, shared_gate_logits))
+    out = (w, ids, sp, off, ti) if align else (w, ids)
+    return out + (keys,) if return_keys else out
 
 
 def _native_operands(A, size_m, size_k, out_quantized):

@@ -10,7 +10,8 @@ only (CPU or GPU tensors):
   * the activation is the clamped SwiGLU (activation="swiglu_oai"), and every expert has a bias on gate_up and on down.
 
 The router's top-k (then softmax over the k) is `moe_route(..., scoring="softmax", renormalize=True)`: `GptOssExperts.forward_routed` starts
-from the logits.  The router's own linear, attention sinks and the dense bf16 linears of gpt-oss are not this module's business.
+from the logits, `GptOssExperts.forward_hidden` one step earlier, from the hidden state and the router's weight and bias (the router's linear
+runs as the library's router GEMM).  Attention sinks and the dense bf16 linears of gpt-oss are not this module's business.
 """
 from __future__ import annotations
 
@@ -123,6 +124,17 @@ class GptOssExperts:
         return fp4_moe_routed(self.pad_hidden(x), router_logits, self.w13, self.s13, self.gs13, self.w2, self.s2, self.gs2, topk, kind="mxfp4",
                               path=path, activations=activations, bias13=self.bias13, bias2=self.bias2, activation="swiglu_oai",
                               scoring="softmax", renormalize=True)
+
+    def forward_hidden(self, x: torch.Tensor, router_weight: torch.Tensor, router_bias: torch.Tensor = None, topk: int = 4, path: str = "fused",
+                       activations: str = "mxfp8") -> torch.Tensor:
+        """forward from the hidden state: the router's linear x . router_weight [E, hidden]^T + router_bias (float32 [E]) as the library's
+        router GEMM on the UNPADDED x (K = 2880), the routing on its partial sums, then forward's launches on pad_hidden(x): bit for bit
+        forward_routed(x, moe_router_logits(x, router_weight, router_bias), topk, path, activations)."""
+        from .moe import fp4_moe_routed
+        _check(path in ("fused", "native"), "path must be 'fused' or 'native'")
+        return fp4_moe_routed(self.pad_hidden(x), None, self.w13, self.s13, self.gs13, self.w2, self.s2, self.gs2, topk, kind="mxfp4",
+                              path=path, activations=activations, bias13=self.bias13, bias2=self.bias2, activation="swiglu_oai",
+                              router_weight=router_weight, router_bias=router_bias, router_input=x, scoring="softmax", renormalize=True)
 
 
 def prepare_gptoss_experts(gate_up_blocks: torch.Tensor, gate_up_scales: torch.Tensor, gate_up_bias: torch.Tensor, down_blocks: torch.Tensor,

@@ -227,7 +227,8 @@ def fp4_moe_routed(hidden: torch.Tensor, router_logits: torch.Tensor, w13: torch
                    gs2: torch.Tensor, topk: int, kind: str = "nvfp4", *, path: str = "fused", activations: str = "mxfp8",
                    bias13: torch.Tensor = None, bias2: torch.Tensor = None, activation: str = "silu_mul", transient: bool = False,
                    norm_weight: torch.Tensor = None, norm_eps: float = 1e-6, norm_residual: torch.Tensor = None, norm_weight_offset: float = 0.0,
-                   norm_fmt: str = None, **routing):
+                   norm_fmt: str = None, router_weight: torch.Tensor = None, router_bias: torch.Tensor = None,
+                   router_input: torch.Tensor = None, **routing):
     """The layer from the router's logits: moe_route_align(router_logits, topk, **routing), then exactly the launches fp4_moe_fused (path
     'fused') or fp4_moe_native (path 'native', with `activations`) issue after their align -- bit for bit
     fp4_moe_fused(..., *moe_route(router_logits, topk, **routing)).  router_logits [T, E] float32 / bfloat16 / float16; routing: moe_route's
@@ -242,10 +243,16 @@ def fp4_moe_routed(hidden: torch.Tensor, router_logits: torch.Tensor, w13: torch
 
     transient (path 'native', kind 'nvfp4'): fp4_moe_native's switch -- the packed tensors, no resident images.
 
+    router_weight (with router_logits None; router_bias float32 [E] optional): the layer from the hidden state.  The router's linear
+    hidden . router_weight[E, K]^T (+ router_bias) runs as the library's router GEMM and moe_route_hidden takes moe_route_align's place: one
+    launch more than from the logits (5 for the fused layer at T * topk <= 1024), bit for bit
+    fp4_moe_routed(hidden, moe_router_logits(hidden, router_weight, router_bias), ...).  The router reads `hidden`, or router_input [T, k] when the
+    experts' `hidden` is a padded copy of it (gpt-oss: 2880 columns against 3072).
+
     norm_weight / norm_eps / norm_residual / norm_weight_offset / norm_fmt: fp4_moe_fused's fused end on either path (returns (h, y16) or
     (q, h)): with route + align in one launch the whole layer and the next block's norm are four launches.  For a layer whose combine is complete
     on this rank (no all-reduce between the combine and the residual add)."""
-    from . import moe_route_align
+    from . import moe_route_align, moe_route_hidden
     if path not in ("fused", "native"):
         raise RuntimeError("path must be 'fused' or 'native'")
     if "return_keys" in routing:
@@ -256,19 +263,33 @@ def fp4_moe_routed(hidden: torch.Tensor, router_logits: torch.Tensor, w13: torch
             raise RuntimeError("transient=True is for path 'native'")
     else:
         _check_native(kind, activation, activations, transient)
-    if router_logits.dim() != 2 or router_logits.size(0) != hidden.size(0):
-        raise RuntimeError(f"router_logits must be [{hidden.size(0)}, num_experts] (tokens of hidden)")
+    if router_weight is not None:
+        if router_logits is not None:
+            raise RuntimeError("router_logits must be None when router_weight is given: the layer then starts at the hidden state")
+        if router_weight.dim() != 2:
+            raise RuntimeError("router_weight must be [num_experts, k]")
+        global_experts = router_weight.size(0)
+    else:
+        if router_bias is not None or router_input is not None:
+            raise RuntimeError("router_bias and router_input need router_weight")
+        if router_logits is None or router_logits.dim() != 2 or router_logits.size(0) != hidden.size(0):
+            raise RuntimeError(f"router_logits must be [{hidden.size(0)}, num_experts] (tokens of hidden)")
+        global_experts = router_logits.size(1)
     num_shared = int(routing.get("num_shared", 0))
     if routing.get("expert_map") is None:
-        local = router_logits.size(1)
+        local = global_experts
     else:
         given = routing.get("num_local_experts")
-        local = router_logits.size(1) if given is None or int(given) <= 0 else int(given)
+        local = global_experts if given is None or int(given) <= 0 else int(given)
     if gs13.numel() != local + num_shared:
         raise RuntimeError(f"the weights hold {gs13.numel()} experts, the routing names {local} local + {num_shared} shared "
                            f"(router_logits must be [{hidden.size(0)}, {gs13.numel() - num_shared}] without an expert_map)")
     norm = _norm_end(norm_weight, norm_eps, norm_residual, norm_weight_offset, norm_fmt)
-    w, ids, sorted_pos, offsets, token_index = moe_route_align(router_logits, topk, **routing)
+    if router_weight is not None:
+        w, ids, sorted_pos, offsets, token_index = moe_route_hidden(router_input if router_input is not None else hidden, router_weight, topk,
+                                                                    router_bias=router_bias, **routing)
+    else:
+        w, ids, sorted_pos, offsets, token_index = moe_route_align(router_logits, topk, **routing)
     if path == "fused":
         return _fused_after_align(hidden, w13, s13, gs13, w2, s2, gs2, w, ids, sorted_pos, offsets, token_index, kind, bias13, bias2, activation,
                                   norm)

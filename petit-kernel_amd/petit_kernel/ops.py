@@ -980,18 +980,27 @@ _LOGIT_DTYPES = {torch.float32: _lib.PETIT_DTYPE_FP32, torch.bfloat16: _lib.CXX_
 
 def _check_route(router_logits, topk, scoring, bias, n_group, topk_group):
     """The argument checks of moe_route / moe_route_align (the same texts as csrc/torch_binding.cpp); returns (T, E)."""
-    _check(scoring in _SCORINGS, "scoring must be 'softmax' or 'sigmoid'")
+    _check_scoring(scoring)
     _check(router_logits.is_cuda and router_logits.dim() == 2 and router_logits.is_contiguous() and router_logits.dtype in _LOGIT_DTYPES,
            "router_logits must be a contiguous float32 / bfloat16 / float16 [num_tokens, num_experts] GPU tensor")
     T, E = router_logits.shape
+    _check_route_args(E, router_logits.device, topk, scoring, bias, n_group, topk_group)
+    return T, E
+
+
+def _check_scoring(scoring):
+    _check(scoring in _SCORINGS, "scoring must be 'softmax' or 'sigmoid'")
+
+
+def _check_route_args(E, dev, topk, scoring, bias, n_group, topk_group):
+    """What a routing asks of everything but its logits (E experts, on device dev); moe_route_hidden has no logits tensor to show."""
     _check(1 <= E <= _lib.PETIT_MOE_MAX_EXPERTS, f"num_experts must be in 1..{_lib.PETIT_MOE_MAX_EXPERTS}, got {E}")
     _check(1 <= int(topk) <= min(E, _lib.PETIT_MOE_MAX_TOPK), f"topk must be in 1..min(num_experts, {_lib.PETIT_MOE_MAX_TOPK}), got {topk}")
     _check(int(n_group) >= 1 and int(topk_group) >= 1, "n_group and topk_group must be >= 1")
     if bias is not None:
         _check(scoring == "sigmoid", "bias needs scoring='sigmoid'")
-        _check(bias.is_cuda and bias.device == router_logits.device and bias.dtype == torch.float32 and bias.is_contiguous() and
+        _check(bias.is_cuda and bias.device == dev and bias.dtype == torch.float32 and bias.is_contiguous() and
                tuple(bias.shape) == (E,), "bias must be a contiguous float32 [num_experts] tensor on router_logits' device")
-    return T, E
 
 
 def _route_desc(scoring, renormalize, bias, n_group, topk_group, routed_scaling_factor):
@@ -1051,7 +1060,13 @@ def moe_route_align(router_logits: torch.Tensor, topk: int, scoring: str = "soft
 
 def _check_route_slots(router_logits, topk, E, expert_map, num_local_experts, num_shared, shared_gate_logits):
     """The argument checks of the slot list of moe_route_ex / moe_route_align_ex (the same texts as csrc/torch_binding.cpp); returns (L, S)."""
-    T, S = router_logits.size(0), int(num_shared)
+    return _check_route_slot_args(router_logits.size(0), E, router_logits.device, router_logits.dtype, topk, expert_map, num_local_experts,
+                                  num_shared, shared_gate_logits)
+
+
+def _check_route_slot_args(T, E, dev, logits_dtype, topk, expert_map, num_local_experts, num_shared, shared_gate_logits):
+    """The slot list's checks for T tokens and E experts on device dev, the logits (and a shared gate's) being logits_dtype."""
+    S = int(num_shared)
     L = E if num_local_experts is None or int(num_local_experts) <= 0 else int(num_local_experts)   # (None, -1 or 0: num_experts, as the C ABI's 0)
     _check(S >= 0 and int(topk) + S <= _lib.PETIT_MOE_MAX_TOPK, f"topk + num_shared must be in 1..{_lib.PETIT_MOE_MAX_TOPK}, got {int(topk) + S}")
     _check(1 <= L <= E and L + S <= _lib.PETIT_MOE_MAX_EXPERTS,
@@ -1059,13 +1074,13 @@ def _check_route_slots(router_logits, topk, E, expert_map, num_local_experts, nu
     if expert_map is None:
         _check(L == E, "num_local_experts needs an expert_map")
     else:
-        _check(expert_map.is_cuda and expert_map.device == router_logits.device and expert_map.dtype == torch.int32 and
+        _check(expert_map.is_cuda and expert_map.device == dev and expert_map.dtype == torch.int32 and
                expert_map.is_contiguous() and tuple(expert_map.shape) == (E,),
                "expert_map must be a contiguous int32 [num_experts] tensor on router_logits' device")
     if shared_gate_logits is not None:
         _check(S >= 1, "shared_gate_logits needs num_shared >= 1")
-        _check(shared_gate_logits.is_cuda and shared_gate_logits.device == router_logits.device and
-               shared_gate_logits.dtype == router_logits.dtype and shared_gate_logits.is_contiguous() and
+        _check(shared_gate_logits.is_cuda and shared_gate_logits.device == dev and
+               shared_gate_logits.dtype == logits_dtype and shared_gate_logits.is_contiguous() and
                tuple(shared_gate_logits.shape) == (T, S),
                "shared_gate_logits must be a contiguous [num_tokens, num_shared] tensor of router_logits' dtype on its device")
     return L, S
@@ -1127,6 +1142,101 @@ def moe_route_align_ex(router_logits: torch.Tensor, topk: int, scoring: str = "s
     _route_shape_error(rc, T, E, topk, n_group, topk_group)
     _raise_on(rc, "moe_route_align_ex")
     out = (w, ids, sorted_pos, offsets, token_index)
+    return out + (keys,) if return_keys else out
+
+
+# --- the router's GEMM (include/petit_amd.h "The router's GEMM"; no counterpart in the reference) -----------------------------------------
+
+def _check_router(hidden, router_weight, router_bias):
+    """The argument checks of moe_router_logits / moe_route_hidden, stated here for both operator layers; returns (T, E, K)."""
+    _check(hidden.is_cuda and hidden.dim() == 2 and hidden.dtype in (torch.bfloat16, torch.float16),
+           "hidden must be a bfloat16 / float16 [num_tokens, k] GPU tensor")
+    _check(hidden.is_contiguous(), "hidden must be contiguous")
+    _check(router_weight.is_cuda and router_weight.device == hidden.device and router_weight.dim() == 2,
+           "router_weight must be a [num_experts, k] tensor on hidden's device")
+    _check(router_weight.dtype == hidden.dtype, f"router_weight must have hidden's dtype ({hidden.dtype}), got {router_weight.dtype}")
+    _check(router_weight.is_contiguous(), "router_weight must be contiguous")
+    (T, K), E = hidden.shape, router_weight.size(0)
+    _check(router_weight.size(1) == K, f"router_weight must be [num_experts, {K}] (hidden's k), got {tuple(router_weight.shape)}")
+    _check(K % 32 == 0 and 32 <= K <= 16384, f"k must be a multiple of 32 in 32..16384, got {K}")
+    _check(1 <= E <= _lib.PETIT_MOE_MAX_EXPERTS, f"num_experts must be in 1..{_lib.PETIT_MOE_MAX_EXPERTS}, got {E}")
+    _check(T < 1 << 20, f"num_tokens must be below 2^20, got {T}")
+    _check(hidden.data_ptr() % 16 == 0 and router_weight.data_ptr() % 16 == 0, "hidden and router_weight must be 16-byte aligned")
+    if router_bias is not None:
+        _check(router_bias.is_cuda and router_bias.device == hidden.device and tuple(router_bias.shape) == (E,),
+               "router_bias must be a [num_experts] tensor on hidden's device")
+        _check(router_bias.dtype == torch.float32, f"router_bias must be float32, got {router_bias.dtype}")
+        _check(router_bias.is_contiguous(), "router_bias must be contiguous")
+    return T, E, K
+
+
+def _check_route_hidden(hidden, router_weight, topk, router_bias, scoring, bias, n_group, topk_group, expert_map, num_local_experts, num_shared,
+                        shared_gate_logits):
+    """moe_route_hidden's checks: the router's, then the routing's on float32 logits that are never stored; returns (T, E, K, L, S)."""
+    _check_scoring(scoring)
+    T, E, K = _check_router(hidden, router_weight, router_bias)
+    _check_route_args(E, hidden.device, topk, scoring, bias, n_group, topk_group)
+    L, S = _check_route_slot_args(T, E, hidden.device, torch.float32, topk, expert_map, num_local_experts, num_shared, shared_gate_logits)
+    return T, E, K, L, S
+
+
+def router_geometry(num_experts: int, k: int, dtype: torch.dtype = torch.bfloat16):
+    """(S, L) of the router GEMM for (E, K): S slices of L along K (petit_moe_router_geometry) -- functions of the shape alone, never of T."""
+    S, L = C.c_uint(0), C.c_uint(0)
+    _lib.lib.petit_moe_router_geometry(int(num_experts), int(k), _a_type(dtype), C.byref(S), C.byref(L))
+    return S.value, L.value
+
+
+def router_slabs(num_tokens: int, num_experts: int, k: int, dtype: torch.dtype = torch.bfloat16) -> int:
+    """The slab count of the form T tokens get (petit_moe_router_slabs): S in the split form (small T), 1 in the whole form."""
+    return int(_lib.lib.petit_moe_router_slabs(int(num_tokens), int(num_experts), int(k), _a_type(dtype)))
+
+
+def moe_router_logits(hidden: torch.Tensor, router_weight: torch.Tensor, router_bias: torch.Tensor = None) -> torch.Tensor:
+    """hidden [T, K] . router_weight [E, K]^T (+ router_bias float32 [E]) -> float32 [T, E] by petit_moe_router_logits (include/petit_amd.h
+    "The router's GEMM": fp32 accumulation in an order fixed by (E, K) alone, so a row's logits do not depend on its batch).  bfloat16 or
+    float16, both tensors alike and contiguous.  One launch without a bias in the whole form, else two."""
+    T, E, K = _check_router(hidden, router_weight, router_bias)
+    dev = hidden.device
+    logits = torch.empty((T, E), dtype=torch.float32, device=dev)
+    a_type = _a_type(hidden.dtype)
+    ws = _scratch(int(_lib.lib.petit_moe_router_workspace_bytes(T, E, K, a_type)), dev)
+    with torch.cuda.device(dev):
+        rc = _lib.lib.petit_moe_router_logits(_ptr(logits), _ptr(hidden), _ptr(router_weight), _opt_ptr(router_bias), a_type, T, E, K,
+                                              _opt_ptr(ws), _stream(hidden))
+    _raise_on(rc, "moe_router_logits")
+    return logits
+
+
+def moe_route_hidden(hidden: torch.Tensor, router_weight: torch.Tensor, topk: int, router_bias: torch.Tensor = None, align: bool = True,
+                     scoring: str = "softmax", renormalize: bool = True, bias: torch.Tensor = None, n_group: int = 1, topk_group: int = 1,
+                     routed_scaling_factor: float = 1.0, return_keys: bool = False, expert_map: torch.Tensor = None,
+                     num_local_experts: int = None, num_shared: int = 0, shared_weight: float = 1.0, shared_gate_logits: torch.Tensor = None):
+    """The routing from the hidden state (petit_moe_route_hidden): what moe_route_align_ex (align=True) or moe_route_ex (align=False) return
+    on moe_router_logits(hidden, router_weight, router_bias), bit for bit, in two launches for a decode batch -- the router GEMM, then
+    route (+ align) on its partial sums; the logits are never stored.  shared_gate_logits is float32 here."""
+    T, E, K, L, S = _check_route_hidden(hidden, router_weight, topk, router_bias, scoring, bias, n_group, topk_group, expert_map,
+                                        num_local_experts, num_shared, shared_gate_logits)
+    dev = hidden.device
+    topk = int(topk)
+    n_slots = topk + S
+    ids = torch.empty((T, n_slots), dtype=torch.int32, device=dev)
+    w = torch.empty((T, n_slots), dtype=torch.float32, device=dev)
+    keys = torch.empty((T, E), dtype=torch.float32, device=dev) if return_keys else None
+    sorted_pos = torch.empty(T * n_slots, dtype=torch.int32, device=dev) if align else None
+    token_index = torch.empty(T * n_slots, dtype=torch.int32, device=dev) if align else None
+    offsets = torch.empty(L + S + 1, dtype=torch.int32, device=dev) if align else None
+    desc = _route_desc(scoring, renormalize, bias, n_group, topk_group, routed_scaling_factor)
+    slots = _route_slots(expert_map, L, S, shared_weight, shared_gate_logits)
+    a_type = _a_type(hidden.dtype)
+    ws = _scratch(int(_lib.lib.petit_moe_route_hidden_workspace_bytes(T, E, K, a_type, topk, C.byref(slots))), dev)
+    with torch.cuda.device(dev):
+        rc = _lib.lib.petit_moe_route_hidden(_ptr(hidden), _ptr(router_weight), _opt_ptr(router_bias), a_type, T, E, K, topk, C.byref(desc),
+                                             C.byref(slots), _ptr(ids), _ptr(w), _opt_ptr(keys), _opt_ptr(offsets), _opt_ptr(sorted_pos),
+                                             _opt_ptr(token_index), _opt_ptr(ws), _stream(hidden))
+    _route_shape_error(rc, T, E, topk, n_group, topk_group)
+    _raise_on(rc, "moe_route_hidden")
+    out = (w, ids, sorted_pos, offsets, token_index) if align else (w, ids)
     return out + (keys,) if return_keys else out
 
 

@@ -27,6 +27,8 @@ routing chain of (a) launches (torch.profiler's kernel events) and saving / (tha
 a, b, a, b: (a) fp4_moe_routed(..., num_shared=1) on the 257-expert stacks -- the shared expert is slot topk of every token, in the layer's own
 launches; (b) what a caller does without it: fp4_moe_routed on the 256 routed experts, the shared expert as two dense mul_nvfp4_a16 calls
 (gate_up with fused SiLU-mul, down) on the same weights, and a torch add.
+--layer --from-hidden: the layer from the hidden state (see hidden_layer_cells): the caller's linear + .float() + fp4_moe_routed against
+fp4_moe_routed(router_weight=...), each model with its real router (E, K), measured a, b, a, b.
 --gptoss: the gpt-oss-20b / -120b expert block (bf16 x MXFP4, 2880 -> 3072, biases, activation="swiglu_oai"): see gptoss_cells.  The two
 models are also in the model list of the default cells (--models gpt-oss-20b,gpt-oss-120b: MXFP4 pools).
 Kernel times without launch gaps: run under `rocprofv3 --kernel-trace --stats -- python tools/moe_bench.py ...`.
@@ -346,6 +348,75 @@ def routed_layer_cells(pk, models, ts, iters):
     return cells
 
 
+ROUTER_K = {"gpt-oss-20b": 2880, "gpt-oss-120b": 2880}   # the router's K where the experts' hidden size is a padded one
+
+
+def hidden_layer_cells(pk, models, ts, iters):
+    """--layer --from-hidden: the layer from the hidden state, each model with its real router (E, K), graph replays on one stream.
+    a = the caller's path today: torch.nn.functional.linear(x, W, b) in the model's dtype, .float(), fp4_moe_routed(x, logits, ...);
+    b = fp4_moe_routed(x, None, ..., router_weight=W, router_bias=b).  Measured a, b, a, b in one process: the two a's are the spread.
+    Per cell also the two routers alone (linear + .float() against moe_router_logits) and the slab count of the form T gets."""
+    from petit_kernel import ops
+    cells = []
+    for name in models:
+        (n13, hid), (n2, inter), E, topk = MODELS[name]
+        kind = "mxfp4" if MODEL_KIND.get(name) == "mx" else "nvfp4"
+        g = torch.Generator(device="cuda").manual_seed(7)
+        ri = lambda *shape: torch.randint(-2 ** 31, 2 ** 31 - 1, shape, dtype=torch.int32, device="cuda", generator=g)  # noqa: E731
+        w13, w2 = ri(E * n13 // 16, 2 * hid), ri(E * n2 // 16, 2 * inter)
+        if kind == "nvfp4":
+            s13 = torch.randint(0x28, 0x40, (E * n13, hid // 16), dtype=torch.uint8, device="cuda", generator=g).view(torch.float8_e4m3fn)
+            s2 = torch.randint(0x28, 0x40, (E * n2, inter // 16), dtype=torch.uint8, device="cuda", generator=g).view(torch.float8_e4m3fn)
+            gs13, gs2 = torch.rand(E, device="cuda") * 0.01 + 0.01, torch.rand(E, device="cuda") * 0.01 + 0.01
+            extra = {}
+        else:
+            s13 = torch.randint(118, 127, (E * n13 // 32, hid), dtype=torch.uint8, device="cuda", generator=g)
+            s2 = torch.randint(118, 127, (E * n2 // 32, inter), dtype=torch.uint8, device="cuda", generator=g)
+            gs13, gs2 = torch.ones(E, device="cuda"), torch.ones(E, device="cuda")
+            extra = dict(bias13=torch.randn(E, n13, device="cuda").bfloat16(), bias2=torch.randn(E, n2, device="cuda").bfloat16(),
+                         activation="swiglu_oai")
+        routing = dict(ROUTING[name])
+        if name == "deepseek":
+            routing["bias"] = torch.randn(E, device="cuda", generator=g) * 0.1
+        K = ROUTER_K.get(name, hid)
+        W = (torch.randn(E, K, device="cuda", generator=g) / K ** 0.5).to(torch.bfloat16)
+        rb = torch.randn(E, device="cuda", generator=g) if name.startswith("gpt-oss") else None   # gpt-oss's router has a bias
+        rb16 = None if rb is None else rb.to(torch.bfloat16)                                       # (the model's own parameter dtype)
+        S, L = ops.router_geometry(E, K)
+        for T in ts:
+            it = iters if T < 1024 else max(5, iters // 5)
+            x = torch.randn(T, hid, device="cuda").to(torch.bfloat16)
+            xr = x if K == hid else x[:, :K].contiguous()                                          # what the router reads
+            rin = {} if K == hid else {"router_input": xr}
+
+            def linear():
+                return torch.nn.functional.linear(xr, W, rb16).float()
+
+            def a():
+                return pk.fp4_moe_routed(x, linear(), w13, s13, gs13, w2, s2, gs2, topk, kind, **extra, **routing)
+
+            def b():
+                return pk.fp4_moe_routed(x, None, w13, s13, gs13, w2, s2, gs2, topk, kind, router_weight=W, router_bias=rb, **rin, **extra,
+                                         **routing)
+
+            r = {"model": name, "T": T, "E": E, "K": K, "topk": topk, "hidden": hid, "inter": inter, "slices": S, "slice_k": L,
+                 "slabs": ops.router_slabs(T, E, K)}
+            r["linear_routed_us"], r["from_hidden_us"] = [], []
+            for _ in range(2):
+                r["linear_routed_us"].append(graph_us(a, it))
+                r["from_hidden_us"].append(graph_us(b, it))
+            r["linear_alone_us"] = graph_us(linear, it)
+            r["router_logits_alone_us"] = graph_us(lambda: pk.moe_router_logits(xr, W, rb), it)
+            r["saving_us"] = [x_ - y_ for x_, y_ in zip(r["linear_routed_us"], r["from_hidden_us"])]
+            r["spread_a_us"] = abs(r["linear_routed_us"][0] - r["linear_routed_us"][1])
+            r["meets"] = all(s_ > 0 for s_ in r["saving_us"]) if T <= 64 else all(-s_ <= r["spread_a_us"] for s_ in r["saving_us"])
+            print(json.dumps(r), file=sys.stderr, flush=True)
+            cells.append(r)
+        del w13, s13, w2, s2
+        torch.cuda.empty_cache()
+    return cells
+
+
 SHARED_T = (1, 16, 64, 512)
 
 
@@ -544,6 +615,8 @@ def main():
     ap.add_argument("--native", default="", choices=["", "mxfp8", "mxfp6", "mxfp4"],
                     help="--layer: fp4_moe_native with these activations against fp4_moe_fused (MXFP4 raw and NVFP4 images), plus the single-expert cell")
     ap.add_argument("--from-logits", action="store_true", help="--layer: the torch routing chain + fp4_moe_fused against fp4_moe_routed")
+    ap.add_argument("--from-hidden", action="store_true",
+                    help="--layer: linear + .float() + fp4_moe_routed against fp4_moe_routed(router_weight=...), each model's real router (E, K)")
     ap.add_argument("--shared", action="store_true", help="--layer: DeepSeek-V3 with its shared expert as slot topk of fp4_moe_routed against separate dense calls")
     ap.add_argument("--gptoss", action="store_true", help="the gpt-oss expert block (petit_kernel.gptoss): layer, host loop, native, fused activation")
     ap.add_argument("--out", default="")
@@ -557,6 +630,10 @@ def main():
     elif args.layer and args.shared:
         ts = tuple(int(t) for t in args.t.split(",")) if args.t else SHARED_T
         report["shared_layer"] = shared_layer_cells(pk, ts, args.iters)
+    elif args.layer and args.from_hidden:
+        ts = tuple(int(t) for t in args.t.split(",")) if args.t else LAYER_T
+        models = args.models.split(",") if args.models != "deepseek,qwen3,mixtral" else ["deepseek", "qwen3", "mixtral", "gpt-oss-120b"]
+        report["hidden_layer"] = hidden_layer_cells(pk, models, ts, args.iters)
     elif args.layer and args.from_logits:
         ts = tuple(int(t) for t in args.t.split(",")) if args.t else LAYER_T
         models = args.models.split(",") if args.models != "deepseek,qwen3,mixtral" else ["deepseek", "qwen3", "mixtral", "gpt-oss-120b"]
