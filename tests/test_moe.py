@@ -272,7 +272,8 @@ def test_moe_vs_oracle_per_expert(pk, kind, is_bf16, case):
 @pytest.mark.parametrize("kind,is_bf16", [("nv", True), ("nv", False), ("mx", True), ("mx", False)])
 def test_moe_bit_identical_to_dense_per_expert(pk, kind, is_bf16, k):
     """For every id the MoE call accepts: each expert's rows equal a dense call on those rows with the same id, bit for bit (where the
-    dense call takes that many rows); AUTO runs the id moe_resolve_solution names."""
+    dense call takes that many rows: every expert whose row count the dense resolver accepts for the id is compared, and the count is printed);
+    AUTO runs the id moe_resolve_solution names."""
     dtype = torch.bfloat16 if is_bf16 else torch.float16
     counts = np.array([1, 0, 3, 16, 40, 130, 0])
     E, m = len(counts), int(counts.sum())
@@ -290,6 +291,8 @@ def test_moe_bit_identical_to_dense_per_expert(pk, kind, is_bf16, k):
     for sid in accepted:
         c = _bits(ex.mul(pk, ad, offd, m, sid))
         compared = 0
+        # the experts whose row count the id's dense form takes, by the dense resolver: each of them must be compared, none may slip past below
+        takes = [e for e in range(E) if counts[e] and pk.ops.resolve_solution(h, int(counts[e]), n, k, sid) != 0]
         for e in range(E):
             lo, hi = offs[e], offs[e + 1]
             if hi == lo:
@@ -297,10 +300,14 @@ def test_moe_bit_identical_to_dense_per_expert(pk, kind, is_bf16, k):
             try:
                 d = ex.dense(pk, ad[lo:hi].contiguous(), e, sid)
             except RuntimeError:
+                assert e not in takes, f"{pk.ops._lib.describe_solution(sid)}: the dense resolver takes expert {e}'s {hi - lo} rows, the dense call refuses"
                 continue   # (a staged kernel holds fewer rows than this expert has: the dense call refuses it)
             assert np.array_equal(c[lo:hi], _bits(d)), f"{pk.ops._lib.describe_solution(sid)}: expert {e} differs from the dense call"
             compared += 1
+        print(f"moe vs dense {kind} bf16={is_bf16} k={k} [{pk.ops._lib.describe_solution(sid)}]: compared {compared} of {int((counts > 0).sum())} "
+              f"experts with rows, the dense form takes {len(takes)}")
         assert compared >= 1, pk.ops._lib.describe_solution(sid)
+        assert compared >= len(takes), pk.ops._lib.describe_solution(sid)
     auto = pk.moe_resolve_solution(h, E, m, n, k, -1)
     assert auto and pk.ops._lib.describe_solution(auto)
     assert np.array_equal(_bits(ex.mul(pk, ad, offd, m, -1)), _bits(ex.mul(pk, ad, offd, m, auto)))
