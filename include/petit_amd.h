@@ -848,6 +848,63 @@ int petit_moe_route_hidden(const void *hidden, const void *weight, const float *
                            int32_t *token_index, void *workspace, void *stream);
 
 /*
+ * Batch-invariant GEMM (no counterpart in the reference): an opt-in dense FP4 GEMM whose every output element is a pure function of its
+ * activation row, the weights, the scales and the bias -- not of m, not of the row's position in the batch, not of the launch form.  The
+ * default calls above are pinned bit for bit within one call only: across calls the pick (MFMA shape, where the group scale is applied, how K
+ * is split, bulk + tail) moves with m, so a token's bits differ alone and inside a batch.  This entry pays speed for the opposite
+ * (profiles/gemm_invariant.md has the price).  Arguments as the _ex calls without solution_id, plus `workspace`; a, b, scales, c as there
+ * (hints->a_type BF16 or FP16, c_type equal to it, hints->b_type the entry's format; the packed layout the other GEMMs read); global_scale
+ * may be NULL.  No host sync, no allocation, graph-capturable.  Nothing here goes through the picks, the arch tables or the tuner.
+ *
+ * Definition, honoured bit for bit whatever m is:
+ *     y[m][n] = ( ... ((p_0 + p_1) + p_2) ... + p_{S-1} ) * (*global_scale) + bias[n]
+ *     c[m][n] = round16(y[m][n])                                  (round to nearest even, the one rounding of the exact-class contract)
+ *   fp32 additions and one fp32 multiply, each rounded, in this order, no contraction; without a bias the last add is not made, without a
+ *   global scale the multiply is not made.  p_s is the accumulation of slice s of K, k in [s L, min(K, (s + 1) L)), by ONE chain of
+ *   v_mfma_f32_16x16x32_{bf16,f16} from a zero accumulator: the k-tiles of 128 ascending, inside a tile the four steps of the packed layout in
+ *   their own order (step j covers k = 128 kt + 32 g + 8 j + i, g < 4, i < 8; petit-kernel_amd/csrc/layout.h).  The weight operand is the
+ *   exactly dequantised value fp4 x group scale in the activation type (what petit_dequant_packed_weights returns with global_scale 1); the
+ *   group scale is applied before the MFMA in every form.
+ *   S and L (a multiple of 256: the packed scale layout exists for k % 256 == 0) are functions of (n, k, a_type, b_type) alone --
+ *   petit_gemm_invariant_geometry; S * L >= k > (S - 1) * L, S <= 16.
+ *   Accuracy: products of an activation and a dequantised weight are exact in fp32, so with u = 2^-24
+ *     |y - exact| <= 2 u (K + S + 2) (|gs| sum_k |a_k w_k| + |bias|)      (K accumulation steps, S - 1 slab adds, one multiply, one add).
+ *   This y, and the bound, are the PLAIN call's.  A gated call's y (next paragraph) is the fused multiply-add of the same fold: one rounding
+ *   fewer, so the same bound holds for it, but with both a global scale and a bias it is not the same fp32 number as the plain call's y.
+ *   Gated epilogues (epilogue->activation = PETIT_ACTIVATION_SILU_MUL / _SWIGLU_OAI; c is [m][n/2], n % 32 == 0, as in the _ex calls) are
+ *   element-wise on y through the epilogue function every gated kernel of the library calls (silu_mul4, device_common.hpp), which forms
+ *   y = fma(fold, gs, bias) -- ONE rounding where the plain call has two; without a bias or without a global scale the two agree.
+ * Two forms produce those bits, chosen by m alone for a given shape.  Small m (the split form): S x n-blocks x m-tiles workgroups store their
+ *   partial fp32 tiles to S slabs [m][n] of the workspace with plain vector stores -- no tickets, no fences, no atomics -- and a second launch
+ *   adds the slabs in ascending order and applies scale, bias and activation.  Large m (the whole form): a workgroup walks all S slices,
+ *   accumulates each from zero and adds it to a running total, applies the epilogue itself; one launch, no workspace (the activation tile of a workgroup goes through LDS).
+ *   The switch is a constant of the library (m <= 32: split), not a setting.
+ *   petit_gemm_invariant_slabs is the slab count of the form m gets: S or 1.
+ * Workspace: petit_gemm_invariant_workspace_bytes = slabs * m * n * 4 rounded up to a multiple of 256; 0 for the whole form and for a shape
+ *   or type pair the calls refuse.  Caller-owned device memory, 256-byte aligned, untouched until the call's work on `stream` has finished.
+ * Errors, all before any launch: PETIT_ERROR_BAD_ARGUMENT for null hints, an a_type that is not BF16 / FP16, a c_type that differs, a b_type
+ *   that is not the entry's format, an activation value that does not exist, a non-zero `reserved`; PETIT_ERROR_PROBLEM_SHAPE for n % 16 != 0
+ *   (MXFP4: n % 32 != 0, as in the routed-expert launches: its processed scale tensor comes in rows of 32), k % 256 != 0, n or k zero, m >= 2^20, a gated activation with n % 32 != 0, null required pointers (c, a, b, scales), c / a / b / scales
+ *   not 16-byte aligned, a bias not 8-byte aligned, a null or misaligned workspace when the byte query is not zero;
+ *   PETIT_ERROR_KERNEL_SHAPE for fp16 activations with MXFP4 weights (below).  m == 0 returns PETIT_OK.
+ * petit_gemm_fp4_invariant_host is the CPU twin for HOST pointers (activation none; bias may be NULL): it evaluates the definition with a
+ *   sequential fp32 sum per slice in place of the MFMA chain -- the same bits whenever the partial sums are exact, a few ulp of y apart
+ *   otherwise.  It documents the format and serves the tests that run without a GPU; it is not a fallback.
+ * Not here: routed-expert (MoE) and grouped launches; the native class; fp16 x MXFP4 (out-of-range scale bytes need the hi / lo fallback body,
+ *   a second chain and a definition of its own); a one-launch split form (a last-arriver combine was probed and closed);
+ *   any change to what PETIT_SOLUTION_AUTO runs.
+ */
+void petit_gemm_invariant_geometry(unsigned n, unsigned k, int a_type, int b_type, unsigned *slices, unsigned *slice_k); /* S, L */
+unsigned petit_gemm_invariant_slabs(unsigned m, unsigned n, unsigned k, int a_type, int b_type);
+uint64_t petit_gemm_invariant_workspace_bytes(unsigned m, unsigned n, unsigned k, int a_type, int b_type);
+int petit_gemm_fp4_fp16_invariant(void *c, const void *a, const void *b, const void *scales, const float *global_scale, unsigned m, unsigned n,
+                                  unsigned k, const petit_solution_hints *hints, const petit_epilogue *epilogue, void *workspace, void *stream);
+int petit_gemm_mxfp4_fp16_invariant(void *c, const void *a, const void *b, const void *scales, const float *global_scale, unsigned m, unsigned n,
+                                    unsigned k, const petit_solution_hints *hints, const petit_epilogue *epilogue, void *workspace, void *stream);
+int petit_gemm_fp4_invariant_host(void *c, const void *a, const void *b, const void *scales, const float *global_scale, const void *bias,
+                                  unsigned m, unsigned n, unsigned k, int a_type, int b_type);
+
+/*
  * Native-class MoE launch (no counterpart in the reference): the routed-expert launch on the block-scaled MFMA, the accuracy class of
  * petit_gemm_mxfp4_native (activations quantised to MXFP8 / MXFP6 / MXFP4; the per-element bound is the native block's above).  Opt-in
  * like every native call: solution_id is a PETIT_SOLUTION_AUTO_NATIVE_* sentinel or an explicit native id that has a MoE form (the 128 x 256

@@ -1,0 +1,184 @@
+// gemm_invariant_host.h -- the host side of the batch-invariant GEMM (include/petit_amd.h "Batch-invariant GEMM") that needs no GPU: the
+// geometry, the form switch, the workspace arithmetic, the argument checks and the CPU twin.  Plain C++ (no HIP), so that the same lines build
+// into libpetit_amd.so (gemm_invariant.hip) and into a stand-alone program for sanitizer runs (tools/gemm_invariant_hostcheck.cc).
+#pragma once
+
+#include <stddef.h>
+#include <stdint.h>
+#include <string.h>
+
+#include <vector>
+
+#include "layout.h"
+
+namespace petit_amd {
+namespace invariant {
+
+// (values of include/petit_amd.h, restated so that this header stands alone; gemm_invariant.hip static_asserts them against petit_internal.h)
+enum : int { kRcOk = 0, kRcProblemShape = 1, kRcKernelShape = 2, kRcBadArgument = 4 };
+enum : int { kTypeNv = 3, kTypeFp16 = 4, kTypeBf16 = 5, kTypeMx = 7, kTypeMxF16Range = 8 };
+constexpr unsigned kMaxRows = 1u << 20;     // kMaxM of petit_internal.h
+constexpr unsigned kMaxSlices = 16;         // S <= 16
+constexpr unsigned kSliceStep = 256;        // L is a multiple of it: the packed scale layout exists for k % 256 == 0 only (layout.h)
+constexpr unsigned kTargetWaves = 2048;     // the split form's waves at M <= 16: 8 per CU of a 256-CU chip (n-tiles x S of them)
+constexpr unsigned kSplitMaxM = 32;         // the largest M of the split form
+
+inline bool is_mx(int b_type) { return b_type == kTypeMx || b_type == kTypeMxF16Range; }
+
+// S and L from (n, k): enough slices that the n-tiles x S waves of a decode call reach kTargetWaves, no more than kMaxSlices, none shorter
+// than kSliceStep.  The types do not enter today; they are arguments so that they may.
+inline void geometry(unsigned n, unsigned k, int /*a_type*/, int /*b_type*/, unsigned *slices, unsigned *slice_k) {
+    const unsigned ntiles = n / 16 ? n / 16 : 1;
+    unsigned want = (kTargetWaves + ntiles - 1) / ntiles;
+    want = want > kMaxSlices ? kMaxSlices : want;
+    const unsigned per = (k + want - 1) / want;
+    unsigned L = (per + kSliceStep - 1) / kSliceStep * kSliceStep;
+    L = L ? L : kSliceStep;
+    *slice_k = L;
+    *slices = k ? (k + L - 1) / L : 1u;
+}
+
+// every refusal that depends on shape and types alone (kRcOk: the call can run)
+inline int shape_rc(unsigned m, unsigned n, unsigned k, int a_type, int b_type, int activation) {
+    if ((a_type != kTypeBf16 && a_type != kTypeFp16) || (b_type != kTypeNv && !is_mx(b_type)) || activation < 0 || activation > 2)
+        return kRcBadArgument;
+    // (MXFP4: n % 32 == 0, as the routed-expert launches ask -- its processed scale tensor comes in rows of 32 weight rows)
+    if (n == 0 || k == 0 || n % 16 != 0 || (is_mx(b_type) && n % 32 != 0) || k % 256 != 0 || m >= kMaxRows || (activation && n % 32 != 0) ||
+        (uint64_t)k * 128 >= (1ull << 31))
+        return kRcProblemShape;
+    if (a_type == kTypeFp16 && is_mx(b_type))
+        return kRcKernelShape; // out-of-range scale bytes need the hi / lo fallback body: a second chain, a definition of its own
+    return kRcOk;
+}
+
+inline unsigned slabs(unsigned m, unsigned n, unsigned k, int a_type, int b_type, unsigned split_max_m = kSplitMaxM) {
+    unsigned S, L;
+    geometry(n, k, a_type, b_type, &S, &L);
+    return m <= split_max_m ? S : 1u;
+}
+
+inline uint64_t workspace_bytes(unsigned m, unsigned n, unsigned k, int a_type, int b_type, unsigned split_max_m = kSplitMaxM) {
+    if (shape_rc(m, n, k, a_type, b_type, 0) != kRcOk || m == 0 || m > split_max_m)
+        return 0;
+    return ((uint64_t)slabs(m, n, k, a_type, b_type, split_max_m) * m * n * 4 + 255) / 256 * 256;
+}
+
+// the pointer checks of a call that passed shape_rc and has m > 0
+inline int pointers_rc(const void *c, const void *a, const void *b, const void *scales, const void *bias, const void *workspace,
+                       uint64_t workspace_need) {
+    if (!c || !a || !b || !scales || (workspace_need && !workspace))
+        return kRcProblemShape;
+    if ((((uintptr_t)c | (uintptr_t)a | (uintptr_t)b | (uintptr_t)scales) & 15u) || ((uintptr_t)bias & 7u) ||
+        (workspace_need && ((uintptr_t)workspace & 255u)))
+        return kRcProblemShape;
+    return kRcOk;
+}
+
+// ---- the CPU twin --------------------------------------------------------------------------------------------------------------------------
+
+inline float bits_f32(uint32_t u) {
+    float f;
+    memcpy(&f, &u, 4);
+    return f;
+}
+inline uint32_t f32_bits(float f) {
+    uint32_t u;
+    memcpy(&u, &f, 4);
+    return u;
+}
+inline float h16_f32(bool bf16, uint32_t h) {
+    if (bf16)
+        return bits_f32(h << 16);
+    const uint32_t sign = (h & 0x8000u) << 16, e = (h >> 10) & 31u, m = h & 0x3ffu;
+    if (e == 0)
+        return bits_f32(sign | f32_bits((float)m * (1.0f / 16777216.0f)));
+    return bits_f32(sign | (e == 31 ? 0x7f800000u : (e + 112u) << 23) | (m << 13));
+}
+inline uint32_t f32_h16(bool bf16, float x) { // round to nearest even
+    const uint32_t u = f32_bits(x);
+    if (bf16) {
+        if ((u & 0x7fffffffu) > 0x7f800000u)
+            return (u >> 16) | 0x40u;
+        return (u + 0x7fffu + ((u >> 16) & 1u)) >> 16;
+    }
+    const uint32_t sign = (u >> 16) & 0x8000u, a = u & 0x7fffffffu;
+    if (a > 0x7f800000u)
+        return sign | 0x7e00u;
+    if (a >= 0x477ff000u)
+        return sign | 0x7c00u;
+    if (a < 0x38800000u)
+        return sign | (f32_bits(bits_f32(a) * 16777216.0f + 8388608.0f) & 0x7fffffu);
+    const uint32_t r = a - 0x38000000u;
+    return sign | ((r + 0xfffu + ((r >> 13) & 1u)) >> 13);
+}
+inline float e2m1_f32(unsigned code) {
+    static const float mag[8] = {0.f, 0.5f, 1.f, 1.5f, 2.f, 3.f, 4.f, 6.f};
+    return (code & 8u) ? -mag[code & 7u] : mag[code & 7u];
+}
+inline float e4m3_f32(unsigned b) { // OCP e4m3 (fn): no infinities, 0x7f / 0xff are NaN
+    const unsigned e = (b >> 3) & 15u, m = b & 7u;
+    float v;
+    if (e == 0)
+        v = (float)m * (1.0f / 512.0f);
+    else if (e == 15 && m == 7)
+        v = bits_f32(0x7fc00000u);
+    else
+        v = bits_f32(((e + 120u) << 23) | (m << 20));
+    return (b & 0x80u) ? -v : v;
+}
+inline float e8m0_f32(unsigned b) { return bits_f32((b & 0xffu) << 23); } // 2^(b - 127), as the kernels decode it
+
+// the weight operand of the definition: fp4 x group scale, exact in the activation type for every (type, format) pair the entry accepts
+inline float weight_value(const uint32_t *pw, const uint8_t *ps, bool mx, unsigned k_total, unsigned n, unsigned kk) {
+    const uint32_t word = pw[packed_weight_word_index(k_total, n, kk / 8)];
+    const float q = e2m1_f32((word >> (4 * (kk % 8))) & 15u);
+    const float sc = mx ? e8m0_f32(ps[packed_mxscale_byte_index(k_total, n, kk / kMxGroup)])
+                        : e4m3_f32(ps[packed_nvscale_byte_index(k_total, n, kk / kNvGroup)]);
+    return q * sc;
+}
+
+// c = round16(((p_0 + p_1) + ... + p_{S-1}) * gs + bias), p_s a sequential fp32 sum over the slice's k ascending (the device's p_s is an MFMA
+// chain: the same value whenever the partial sums are exact, a few ulp apart otherwise).  Host pointers; global_scale and bias may be null.
+inline int gemm_host(void *c, const void *a, const void *b, const void *scales, const float *global_scale, const void *bias, unsigned m, unsigned n,
+                     unsigned k, int a_type, int b_type) {
+    const int rc = shape_rc(m, n, k, a_type, b_type, 0);
+    if (rc != kRcOk)
+        return rc;
+    if (m == 0)
+        return kRcOk;
+    if (!c || !a || !b || !scales)
+        return kRcProblemShape;
+    const bool bf16 = a_type == kTypeBf16, mx = is_mx(b_type);
+    unsigned S, L;
+    geometry(n, k, a_type, b_type, &S, &L);
+    const uint16_t *a16 = (const uint16_t *)a, *b16 = (const uint16_t *)bias;
+    uint16_t *c16 = (uint16_t *)c;
+    std::vector<float> wrow(k), arow(k);
+    for (unsigned col = 0; col < n; ++col) {
+        for (unsigned kk = 0; kk < k; ++kk)
+            wrow[kk] = weight_value((const uint32_t *)b, (const uint8_t *)scales, mx, k, col, kk);
+        for (unsigned row = 0; row < m; ++row) {
+            float y = 0.f;
+            for (unsigned s = 0; s < S; ++s) {
+                const unsigned k_end = (s + 1) * L < k ? (s + 1) * L : k;
+                volatile float p = 0.f; // (volatile: one rounding per step, whatever the compiler's contraction setting)
+                for (unsigned kk = s * L; kk < k_end; ++kk) {
+                    volatile float t = h16_f32(bf16, a16[(size_t)row * k + kk]) * wrow[kk];
+                    p = p + t;
+                }
+                y = s ? y + p : p;
+            }
+            if (global_scale) {
+                volatile float t = y * *global_scale;
+                y = t;
+            }
+            if (bias)
+                y = y + h16_f32(bf16, b16[col]);
+            c16[(size_t)row * n + col] = (uint16_t)f32_h16(bf16, y);
+        }
+    }
+    return kRcOk;
+}
+
+} // namespace invariant
+} // namespace petit_amd

@@ -254,6 +254,44 @@ at::Tensor mul_mxfp4_a16(const at::Tensor &A, const at::Tensor &B, const at::Ten
     return mul_a16(true, A, B, s, gs, m, n, k, solution_id, bias, activation);
 }
 
+// the batch-invariant GEMM (petit_gemm_fp4_fp16_invariant / petit_gemm_mxfp4_fp16_invariant).  The argument checks and their texts are stated
+// once, in petit_kernel/ops.py (_check_invariant), which petit_kernel/compiled.py runs in front of these ops; what is checked here is what keeps
+// a direct torch.ops call inside its tensors.
+#define PETIT_INVARIANT_ARGS                                                                                                                   \
+    const at::Tensor &A, const at::Tensor &B, const at::Tensor &s, const std::optional<at::Tensor> &global_scale, int64_t size_m, int64_t size_n, \
+        int64_t size_k, const std::optional<at::Tensor> &bias, int64_t activation
+at::Tensor mul_a16_invariant(bool mx, PETIT_INVARIANT_ARGS) {
+    check_a16(A);
+    TORCH_CHECK(size_m >= 0 && size_n > 0 && size_k > 0 && A.is_cuda() && B.is_cuda() && s.is_cuda() && A.is_contiguous() && B.is_contiguous() &&
+                    s.is_contiguous() && B.device() == A.device() && s.device() == A.device() && A.numel() == size_m * size_k &&
+                    B.numel() * B.element_size() == size_n * size_k / 2 && s.numel() * s.element_size() == size_n * size_k / (mx ? 32 : 16) &&
+                    (!global_scale || (global_scale->is_cuda() && global_scale->device() == A.device() &&
+                                       global_scale->scalar_type() == at::kFloat && global_scale->numel() >= 1)),
+                "A [size_m, size_k], packed B and s of [size_n, size_k] weights must be contiguous GPU tensors on one device, global_scale a float32 "
+                "tensor on it");
+    check_activation(activation, size_n);
+    check_bias(bias, A, A.scalar_type(), size_n, "bias must be a contiguous [size_n] tensor of A's dtype on A's device");
+    const c10::hip::HIPGuardMasqueradingAsCUDA guard(A.device());
+    at::Tensor c = at::empty({size_m, activation ? size_n / 2 : size_n}, A.options());
+    const int a_type = a_type_of(A.scalar_type()), b_type = mx ? kCxxMxFp4 : kCxxFp4;
+    const petit_solution_hints hints{a_type, b_type, a_type, 0};
+    const petit_epilogue epi{bias.has_value() ? bias->data_ptr() : nullptr, (int32_t)activation, 0};
+    const uint64_t ws_bytes = petit_gemm_invariant_workspace_bytes((unsigned)size_m, (unsigned)size_n, (unsigned)size_k, a_type, b_type);
+    at::Tensor ws;
+    if (ws_bytes)
+        ws = at::empty({(int64_t)ws_bytes}, A.options().dtype(at::kByte));
+    auto fn = mx ? petit_gemm_mxfp4_fp16_invariant : petit_gemm_fp4_fp16_invariant;
+    const int rc = fn(c.data_ptr(), A.data_ptr(), B.data_ptr(), s.data_ptr(), global_scale ? (const float *)global_scale->data_ptr() : nullptr,
+                      (unsigned)size_m, (unsigned)size_n, (unsigned)size_k, &hints, (bias.has_value() || activation) ? &epi : nullptr,
+                      ws_bytes ? ws.data_ptr() : nullptr, stream_of(A));
+    TORCH_CHECK(rc != PETIT_ERROR_PROBLEM_SHAPE, "Incompatible problem shape (m=", size_m, ", n=", size_n, ", k=", size_k, ")");
+    TORCH_CHECK(rc != PETIT_ERROR_KERNEL_SHAPE, "No batch-invariant kernel for these types.");
+    TORCH_CHECK(rc == PETIT_OK, mx ? "mul_mxfp4_a16_invariant" : "mul_nvfp4_a16_invariant", ": ", petit_error_string(rc));
+    return c;
+}
+at::Tensor mul_nvfp4_a16_invariant(PETIT_INVARIANT_ARGS) { return mul_a16_invariant(false, A, B, s, global_scale, size_m, size_n, size_k, bias, activation); }
+at::Tensor mul_mxfp4_a16_invariant(PETIT_INVARIANT_ARGS) { return mul_a16_invariant(true, A, B, s, global_scale, size_m, size_n, size_k, bias, activation); }
+
 // routed-expert (MoE) launch: all experts in one call (include/petit_amd.h); the same checks and texts as petit_kernel/ops.py _mul_moe
 at::Tensor mul_a16_moe(bool mx, const at::Tensor &A, const at::Tensor &B, const at::Tensor &s, const at::Tensor &global_scales,
                        const at::Tensor &expert_offsets, int64_t size_m, int64_t size_n, int64_t size_k, int64_t num_experts, int64_t solution_id,
@@ -757,6 +795,10 @@ at::Tensor mul_a16_meta(const at::Tensor &A, const at::Tensor &, const at::Tenso
     check_a16(A);
     return at::empty({m, activation ? n / 2 : n}, A.options());
 }
+at::Tensor mul_a16_invariant_meta(PETIT_INVARIANT_ARGS) {
+    check_a16(A);
+    return at::empty({size_m, activation ? size_n / 2 : size_n}, A.options());
+}
 at::Tensor mul_a16_moe_meta(const at::Tensor &A, const at::Tensor &, const at::Tensor &, const at::Tensor &, const at::Tensor &, int64_t m, int64_t n,
                             int64_t, int64_t, int64_t, const std::optional<at::Tensor> &, int64_t activation) {
     check_a16(A);
@@ -882,6 +924,10 @@ TORCH_LIBRARY(petit_kernel, m) {
     m.def("moe_route_hidden(Tensor hidden, Tensor router_weight, Tensor? router_bias, int topk, bool align=True, int scoring=0, "
           "bool renormalize=True, Tensor? bias=None, int n_group=1, int topk_group=1, float routed_scaling_factor=1.0, bool return_keys=False"
           PETIT_ROUTE_SLOTS_SCHEMA ") -> (Tensor, Tensor, Tensor, Tensor, Tensor, Tensor)");
+    m.def("mul_nvfp4_a16_invariant(Tensor A, Tensor B, Tensor s, Tensor? global_scale, int size_m, int size_n, int size_k, Tensor? bias=None, "
+          "int activation=0) -> Tensor");
+    m.def("mul_mxfp4_a16_invariant(Tensor A, Tensor B, Tensor s, Tensor? global_scale, int size_m, int size_n, int size_k, Tensor? bias=None, "
+          "int activation=0) -> Tensor");
     // round 3's op name (scales promised inside fp16's range): an alias of mul_mxfp4_a16 for one more round -- the kernels test the range themselves
     m.def("mul_mxfp4_a16_f16range(Tensor A, Tensor B, Tensor s, Tensor global_scale, int size_m, int size_n, int size_k, int solution_id, "
           "Tensor? bias=None, int activation=0) -> Tensor");
@@ -894,6 +940,8 @@ TORCH_LIBRARY(petit_kernel, m) {
     m.impl("mul_nvfp4_a16", &mul_nvfp4_a16);                    \
     m.impl("mul_mxfp4_a16", &mul_mxfp4_a16);                    \
     m.impl("mul_mxfp4_a16_f16range", &mul_mxfp4_a16);          \
+    m.impl("mul_nvfp4_a16_invariant", &mul_nvfp4_a16_invariant); \
+    m.impl("mul_mxfp4_a16_invariant", &mul_mxfp4_a16_invariant); \
     m.impl("mul_nvfp4_a16_moe", &mul_nvfp4_a16_moe);            \
     m.impl("mul_mxfp4_a16_moe", &mul_mxfp4_a16_moe);            \
     m.impl("mul_nvfp4_a16_moe_indexed", &mul_nvfp4_a16_moe_indexed); \
@@ -923,6 +971,8 @@ TORCH_LIBRARY_IMPL(petit_kernel, Meta, m) {
     m.impl("mul_nvfp4_a16", &mul_a16_meta);
     m.impl("mul_mxfp4_a16", &mul_a16_meta);
     m.impl("mul_mxfp4_a16_f16range", &mul_a16_meta);
+    m.impl("mul_nvfp4_a16_invariant", &mul_a16_invariant_meta);
+    m.impl("mul_mxfp4_a16_invariant", &mul_a16_invariant_meta);
     m.impl("mul_nvfp4_a16_moe", &mul_a16_moe_meta);
     m.impl("mul_mxfp4_a16_moe", &mul_a16_moe_meta);
     m.impl("mul_nvfp4_a16_moe_indexed", &mul_a16_moe_indexed_meta);

@@ -105,6 +105,35 @@ def mul_mxfp4_a16(a: torch.Tensor, b: torch.Tensor, s: torch.Tensor, global_scal
     return _impl.mul_mxfp4_a16(a, b, s, global_scale, size_m, size_n, size_k, solution_id, bias, activation)
 
 
+def mul_nvfp4_a16_invariant(a: torch.Tensor, b: torch.Tensor, s: torch.Tensor, global_scale: torch.Tensor, size_m: int, size_n: int, size_k: int,
+                            bias: torch.Tensor = None, activation: str = None) -> torch.Tensor:
+    # mul_nvfp4_a16 by the batch-invariant entry (include/petit_amd.h "Batch-invariant GEMM"): every output row is a pure function of its
+    # activation row, the weights, the scales and the bias -- the same bits alone (size_m = 1), inside any batch and at any position of it.
+    # Opt-in: slower than the default pick (profiles/gemm_invariant.md), no solution_id (nothing is picked).  global_scale may be None.
+    return _impl.mul_nvfp4_a16_invariant(a, b, s, global_scale, size_m, size_n, size_k, bias, activation)
+
+
+def mul_mxfp4_a16_invariant(a: torch.Tensor, b: torch.Tensor, s: torch.Tensor, global_scale: torch.Tensor, size_m: int, size_n: int, size_k: int,
+                            bias: torch.Tensor = None, activation: str = None) -> torch.Tensor:
+    # the same for MXFP4 weights; bfloat16 activations only (float16 x MXFP4 has no batch-invariant kernel)
+    return _impl.mul_mxfp4_a16_invariant(a, b, s, global_scale, size_m, size_n, size_k, bias, activation)
+
+
+def invariant_geometry(size_n: int, size_k: int, dtype: torch.dtype = torch.bfloat16, kind: str = "nvfp4"):
+    # (S, L): the slices of K whose partial sums the batch-invariant GEMM adds in order -- functions of (n, k, types) alone
+    return ops.invariant_geometry(size_n, size_k, dtype, kind)
+
+
+def invariant_slabs(size_m: int, size_n: int, size_k: int, dtype: torch.dtype = torch.bfloat16, kind: str = "nvfp4") -> int:
+    # S when size_m rows run in the split form (two launches, slabs in scratch), 1 in the whole form
+    return ops.invariant_slabs(size_m, size_n, size_k, dtype, kind)
+
+
+def invariant_workspace_bytes(size_m: int, size_n: int, size_k: int, dtype: torch.dtype = torch.bfloat16, kind: str = "nvfp4") -> int:
+    # bytes of scratch the batch-invariant call allocates per call (the Python layers do it themselves); 0 in the whole form
+    return ops.invariant_workspace_bytes(size_m, size_n, size_k, dtype, kind)
+
+
 def mul_nvfp4_a16_moe(a: torch.Tensor, b: torch.Tensor, s: torch.Tensor, global_scales: torch.Tensor, expert_offsets: torch.Tensor,
                       size_m: int, size_n: int, size_k: int, num_experts: int, solution_id: int = -1, bias: torch.Tensor = None,
                       activation: str = None) -> torch.Tensor:
@@ -299,6 +328,11 @@ __all__ = [
     "quantize_mxfp4",
     "mul_nvfp4_a16",
     "mul_mxfp4_a16",
+    "mul_nvfp4_a16_invariant",
+    "mul_mxfp4_a16_invariant",
+    "invariant_geometry",
+    "invariant_slabs",
+    "invariant_workspace_bytes",
     "get_fp4_solutions",
     "mxfp4_scales_in_fp16_range",
     "DataType",

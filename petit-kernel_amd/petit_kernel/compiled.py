@@ -15,7 +15,8 @@ import torch
 
 from . import _lib  # loads libpetit_amd.so first (the binding links against it)
 from .ops import QuantizedActivations, _a_type, _activation as _act, _activation_operand, _quantized_format
-from .ops import _check_route_hidden, _check_router, _combine_norm_operands, _combine_norm_returns
+from .ops import _check_invariant, _check_route_hidden, _check_router, _combine_norm_operands, _combine_norm_returns
+from .ops import invariant_geometry, invariant_slabs, invariant_workspace_bytes  # (queries: plain C calls, no op behind them)
 
 LIB_PATH = Path(_lib.LIB_PATH).parent / "libpetit_torch.so"
 _loaded = False
@@ -89,6 +90,16 @@ def mul_nvfp4_a16(A, B, s, global_scale, size_m, size_n, size_k, solution_id, bi
 
 def mul_mxfp4_a16(A, B, s, global_scale, size_m, size_n, size_k, solution_id, bias=None, activation=None):
     return torch.ops.petit_kernel.mul_mxfp4_a16(A, B, s, global_scale, size_m, size_n, size_k, _sid(solution_id), bias, _act(activation))
+
+
+def mul_nvfp4_a16_invariant(A, B, s, global_scale, size_m, size_n, size_k, bias=None, activation=None):
+    act = _check_invariant("nv", A, B, s, global_scale, size_m, size_n, size_k, bias, activation)
+    return torch.ops.petit_kernel.mul_nvfp4_a16_invariant(A, B, s, global_scale, int(size_m), int(size_n), int(size_k), bias, act)
+
+
+def mul_mxfp4_a16_invariant(A, B, s, global_scale, size_m, size_n, size_k, bias=None, activation=None):
+    act = _check_invariant("mx", A, B, s, global_scale, size_m, size_n, size_k, bias, activation)
+    return torch.ops.petit_kernel.mul_mxfp4_a16_invariant(A, B, s, global_scale, int(size_m), int(size_n), int(size_k), bias, act)
 
 
 def mul_nvfp4_a16_moe(A, B, s, global_scales, expert_offsets, size_m, size_n, size_k, num_experts, solution_id=-1, bias=None, activation=None):

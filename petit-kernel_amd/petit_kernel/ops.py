@@ -354,6 +354,80 @@ def mul_mxfp4_a16(A, B, s, global_scale, size_m, size_n, size_k, solution_id, bi
     return _mul("mx", A, B, s, global_scale, size_m, size_n, size_k, solution_id, bias, activation)
 
 
+# --- the batch-invariant GEMM (include/petit_amd.h "Batch-invariant GEMM"; no counterpart in the reference) ---------------------------------
+
+def _check_invariant(kind: str, A, B, s, global_scale, size_m, size_n, size_k, bias, activation) -> int:
+    """The argument checks of mul_nvfp4_a16_invariant / mul_mxfp4_a16_invariant, stated here for both operator layers; returns the
+    activation code.  Value checks come first and device checks last, so that the texts can be read without a GPU."""
+    name = "mul_%sfp4_a16_invariant" % kind
+    _check(A.dtype in (torch.bfloat16, torch.float16), "A must be bfloat16 or float16.")
+    size_m, size_n, size_k = int(size_m), int(size_n), int(size_k)
+    _check(size_n > 0 and size_n % 16 == 0 and size_k > 0 and size_k % 256 == 0 and 0 <= size_m < 1 << 20,
+           f"Incompatible problem shape (m={size_m}, n={size_n}, k={size_k}): {name} needs n % 16 == 0, k % 256 == 0, m < 2^20")
+    _check(not (kind == "mx" and A.dtype == torch.float16),
+           f"{name}: float16 activations with MXFP4 weights have no batch-invariant kernel (use bfloat16)")
+    act = _activation(activation, size_n)
+    _check(A.is_contiguous() and A.numel() == size_m * size_k, "A must be a contiguous [size_m, size_k] tensor")
+    _check(B.is_contiguous() and B.numel() * B.element_size() == size_n * size_k // 2, "B does not hold size_n * size_k packed 4-bit weights")
+    group = 16 if kind == "nv" else 32
+    _check(s.is_contiguous() and s.numel() * s.element_size() == size_n * size_k // group,
+           f"s does not hold size_n * size_k / {group} scales")
+    if global_scale is not None:
+        _check(global_scale.dtype == torch.float32 and global_scale.numel() >= 1, "global_scale must be float32")
+    if bias is not None:
+        _check(bias.dtype == A.dtype and bias.is_contiguous() and bias.numel() == size_n and bias.device == A.device,
+               "bias must be a contiguous [size_n] tensor of A's dtype on A's device")
+    _check(A.is_cuda and B.is_cuda and s.is_cuda and (global_scale is None or global_scale.is_cuda), "all tensors must be on GPU")
+    _check(B.device == A.device and s.device == A.device and (global_scale is None or global_scale.device == A.device),
+           "all tensors must be on A's device")
+    return act
+
+
+def invariant_geometry(size_n: int, size_k: int, dtype: torch.dtype = torch.bfloat16, kind: str = "nvfp4"):
+    """(S, L) of the batch-invariant GEMM for (n, k): S slices of L along K (petit_gemm_invariant_geometry) -- functions of the shape and the
+    types alone, never of m."""
+    S, L = C.c_uint(0), C.c_uint(0)
+    _lib.lib.petit_gemm_invariant_geometry(int(size_n), int(size_k), _a_type(dtype), _B_TYPES[kind], C.byref(S), C.byref(L))
+    return S.value, L.value
+
+
+def invariant_slabs(size_m: int, size_n: int, size_k: int, dtype: torch.dtype = torch.bfloat16, kind: str = "nvfp4") -> int:
+    """The slab count of the form m rows get (petit_gemm_invariant_slabs): S in the split form (small m), 1 in the whole form."""
+    return int(_lib.lib.petit_gemm_invariant_slabs(int(size_m), int(size_n), int(size_k), _a_type(dtype), _B_TYPES[kind]))
+
+
+def invariant_workspace_bytes(size_m: int, size_n: int, size_k: int, dtype: torch.dtype = torch.bfloat16, kind: str = "nvfp4") -> int:
+    """Bytes of scratch the batch-invariant call uses (petit_gemm_invariant_workspace_bytes): the split form's slabs; 0 for the whole form
+    and for a call that would be refused."""
+    return int(_lib.lib.petit_gemm_invariant_workspace_bytes(int(size_m), int(size_n), int(size_k), _a_type(dtype), _B_TYPES[kind]))
+
+
+def _mul_invariant(kind: str, A, B, s, global_scale, size_m, size_n, size_k, bias, activation) -> torch.Tensor:
+    act = _check_invariant(kind, A, B, s, global_scale, size_m, size_n, size_k, bias, activation)
+    size_m, size_n, size_k = int(size_m), int(size_n), int(size_k)
+    c = torch.empty((size_m, size_n // 2 if act else size_n), dtype=A.dtype, device=A.device)
+    hints = _hints(kind, A.dtype)
+    epi = _epilogue(bias, act, A.device, A.dtype, size_n, "bias must be a contiguous [size_n] tensor of A's dtype on A's device")
+    ws = _scratch(int(_lib.lib.petit_gemm_invariant_workspace_bytes(size_m, size_n, size_k, hints.a_type, hints.b_type)), A.device)
+    fn = _lib.lib.petit_gemm_fp4_fp16_invariant if kind == "nv" else _lib.lib.petit_gemm_mxfp4_fp16_invariant
+    with torch.cuda.device(A.device):
+        err = fn(_ptr(c), _ptr(A), _ptr(B), _ptr(s), _opt_ptr(global_scale), size_m, size_n, size_k, C.byref(hints), epi, _opt_ptr(ws), _stream(A))
+    if err:
+        _raise_gemm(err, "mul_%sfp4_a16_invariant" % kind, "invariant", f"m={size_m}, n={size_n}, k={size_k}")
+    return c
+
+
+def mul_nvfp4_a16_invariant(A, B, s, global_scale, size_m, size_n, size_k, bias=None, activation=None) -> torch.Tensor:
+    """mul_nvfp4_a16 by the batch-invariant entry (petit_gemm_fp4_fp16_invariant, include/petit_amd.h "Batch-invariant GEMM"): a row's result
+    does not depend on size_m, on the row's position or on the launch form.  Opt-in and slower than the default pick; no solution_id."""
+    return _mul_invariant("nv", A, B, s, global_scale, size_m, size_n, size_k, bias, activation)
+
+
+def mul_mxfp4_a16_invariant(A, B, s, global_scale, size_m, size_n, size_k, bias=None, activation=None) -> torch.Tensor:
+    """mul_mxfp4_a16 by the batch-invariant entry (petit_gemm_mxfp4_fp16_invariant); bfloat16 activations only."""
+    return _mul_invariant("mx", A, B, s, global_scale, size_m, size_n, size_k, bias, activation)
+
+
 def get_fp4_solutions(*args) -> list:
     """fp4.cc:262-283 (GetNvFp4Solutions), bound twice (pybind.cc:14-17).
 
