@@ -73,6 +73,22 @@ def main():
                                               renormalize=True)
     assert torch.equal(from_hidden.view(torch.int16), from_logits.view(torch.int16))
     print(f"fp4_moe_routed(router_weight=...): equals the layer on moe_router_logits {tuple(own_logits.shape)} bit for bit")
+    # batch-invariant: with invariant=True gate_up and down run as the batch-invariant MoE launches, so from the hidden state a token's output
+    # row is a pure function of its hidden row and the weights -- the same bits alone and inside the batch (opt-in: slower than the default
+    # pick, profiles/moe_invariant.md).  The default layer makes no such promise: its kernels are picked by the batch's size.
+    inv = dict(scoring="softmax", renormalize=True, router_weight=router_w)
+    args = (w13, p13, gs13.to(dev), w2, p2, gs2.to(dev), topk, "nvfp4")
+    batch_inv = petit_kernel.fp4_moe_routed(x.to(dev), None, *args, invariant=True, **inv)
+    batch_def = petit_kernel.fp4_moe_routed(x.to(dev), None, *args, **inv)
+    equal_inv = equal_def = True
+    for t in (0, T // 2, T - 1):
+        one = x[t:t + 1].to(dev)
+        alone_inv = petit_kernel.fp4_moe_routed(one, None, *args, invariant=True, **inv)
+        alone_def = petit_kernel.fp4_moe_routed(one, None, *args, **inv)
+        equal_inv &= torch.equal(alone_inv[0].view(torch.int16), batch_inv[t].view(torch.int16))
+        equal_def &= torch.equal(alone_def[0].view(torch.int16), batch_def[t].view(torch.int16))
+    print(f"fp4_moe_routed(invariant=True): a token's row alone equals its row in the batch of {T}: {equal_inv} (default layer: {equal_def})")
+    assert equal_inv
     # the fused end: the layer's last launch also adds the residual stream, applies the NEXT block's RMSNorm and quantises its input for a
     # native-class GEMM -- bit for bit the layer followed by rmsnorm_quantize, one launch and one [T, H] round trip less.  (For a layer whose
     # combine is complete on this rank: with tensor or expert parallelism the all-reduce comes between the combine and the residual add.)

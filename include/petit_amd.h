@@ -890,7 +890,7 @@ int petit_moe_route_hidden(const void *hidden, const void *weight, const float *
  * petit_gemm_fp4_invariant_host is the CPU twin for HOST pointers (activation none; bias may be NULL): it evaluates the definition with a
  *   sequential fp32 sum per slice in place of the MFMA chain -- the same bits whenever the partial sums are exact, a few ulp of y apart
  *   otherwise.  It documents the format and serves the tests that run without a GPU; it is not a fallback.
- * Not here: routed-expert (MoE) and grouped launches; the native class; fp16 x MXFP4 (out-of-range scale bytes need the hi / lo fallback body,
+ * Not here: grouped launches (the routed-expert launch: "Batch-invariant MoE launch" below); the native class; fp16 x MXFP4 (out-of-range scale bytes need the hi / lo fallback body,
  *   a second chain and a definition of its own); a one-launch split form (a last-arriver combine was probed and closed);
  *   any change to what PETIT_SOLUTION_AUTO runs.
  */
@@ -903,6 +903,53 @@ int petit_gemm_mxfp4_fp16_invariant(void *c, const void *a, const void *b, const
                                     unsigned k, const petit_solution_hints *hints, const petit_epilogue *epilogue, void *workspace, void *stream);
 int petit_gemm_fp4_invariant_host(void *c, const void *a, const void *b, const void *scales, const float *global_scale, const void *bias,
                                   unsigned m, unsigned n, unsigned k, int a_type, int b_type);
+
+/*
+ * Batch-invariant MoE launch (no counterpart in the reference): the routed-expert launch of the batch-invariant GEMM above.  Arguments as
+ * petit_gemm_fp4_fp16_moe_ex without solution_id, plus `workspace`: grouped row r belongs to expert e under the clamp rule of the routed-expert
+ * launch (every offset clamped into [its predecessor, m], a running maximum; rows of no expert are left untouched), reads row a_row_index[r]
+ * of a [a_rows][k] and writes row c_row_index[r] of c [c_rows][n_out] (a NULL index is the identity).
+ * Definition: the written row equals, bit for bit, row 0 of
+ *     petit_gemm_{fp4,mxfp4}_fp16_invariant(m = 1, a = that A row, b / scales = expert e's packed tensors, global_scale = &global_scales[e],
+ *                                           bias = bias + e * n, the same activation)
+ *   so S and L are petit_gemm_invariant_geometry(n, k, a_type, b_type) -- never functions of m, num_experts or the routing --, the arithmetic
+ *   is the dense entry's (one MFMA chain per slice from zero, slices added in ascending order, * gs, + bias, no contraction, one rounding),
+ *   and the gated epilogues pair gate tile t with up tile t + ntiles / 2 of the same expert.  With a token's slot rows combined by
+ *   petit_moe_combine (slot order, fp32, one rounding), a token's layer output is a pure function of its hidden row and the weights.
+ *   An A index outside [0, a_rows) reads a zero row; a C index outside [0, c_rows) stores nothing; malformed offsets can only leave rows
+ *   unwritten.  An expert without rows is never read.  The host never reads the offsets: no sync, no allocation, no atomics, tickets or
+ *   fences; graph-capturable, and a replay follows new offsets.
+ * Two forms produce those bits; petit_gemm_moe_invariant_form(m, num_experts) names the one a call gets (1: split, 0: whole), a function of
+ *   these two host-known arguments alone: split iff ceil(m / min(E, m)) <= 8 and m <= 8 (constants of the library, not settings; measured, profiles/moe_invariant.md:
+ *   the split form pays for a decode step's few rows only).
+ *   split: ceil(m / 16) + min(E, m) slots x S x n-blocks workgroups store fp32 tiles to S slabs [m][n], indexed by grouped row, with plain
+ *     vector stores; a second launch over the same slot map adds the slabs in ascending order, applies gs[e], bias[e] and the activation and
+ *     scatters C.  Nothing in the workspace needs clearing.
+ *   whole: ceil(m / 64) + min(E, m) slots x n-blocks workgroups stage the gathered activation tile through LDS, walk all S slices and
+ *     apply the epilogue themselves; no workspace.
+ * Workspace: petit_gemm_moe_invariant_workspace_bytes = S * m * n * 4 rounded up to a multiple of 256 in the split form; 0 in the whole form
+ *   and for a call that would be refused.  Caller-owned device memory, 256-byte aligned.
+ * Errors, all before any launch: the dense entry's codes (above), and PETIT_ERROR_PROBLEM_SHAPE for num_experts outside 1..1024, a NULL index
+ *   with fewer than m rows behind it, a_rows * k * 2 > 2^31 (one buffer descriptor bounds every A load), a launch of 2^31 workgroups or
+ *   more, a NULL global_scales or expert_offsets, an index or offset pointer that is not 4-byte aligned.  m == 0 returns PETIT_OK.
+ * petit_gemm_fp4_moe_invariant_host is the CPU twin on HOST pointers (offsets and indices included; activation none; bias [E][n] or NULL):
+ *   petit_gemm_fp4_invariant_host per expert under the clamp rule.
+ * Not here: the native class; fp16 x MXFP4; the grouped q / k / v launch; a one-launch split form; a persistent-slot form for dead slots.
+ */
+int petit_gemm_moe_invariant_form(unsigned m, unsigned num_experts);
+uint64_t petit_gemm_moe_invariant_workspace_bytes(unsigned num_experts, unsigned m, unsigned n, unsigned k, int a_type, int b_type);
+int petit_gemm_fp4_fp16_moe_invariant(void *c, const void *a, const void *b, const void *scales, const float *global_scales,
+                                      const int32_t *expert_offsets, unsigned num_experts, unsigned m, unsigned n, unsigned k,
+                                      const int32_t *a_row_index, unsigned a_rows, const int32_t *c_row_index, unsigned c_rows,
+                                      const petit_solution_hints *hints, const petit_epilogue *epilogue, void *workspace, void *stream);
+int petit_gemm_mxfp4_fp16_moe_invariant(void *c, const void *a, const void *b, const void *scales, const float *global_scales,
+                                        const int32_t *expert_offsets, unsigned num_experts, unsigned m, unsigned n, unsigned k,
+                                        const int32_t *a_row_index, unsigned a_rows, const int32_t *c_row_index, unsigned c_rows,
+                                        const petit_solution_hints *hints, const petit_epilogue *epilogue, void *workspace, void *stream);
+int petit_gemm_fp4_moe_invariant_host(void *c, const void *a, const void *b, const void *scales, const float *global_scales, const void *bias,
+                                      const int32_t *expert_offsets, unsigned num_experts, unsigned m, unsigned n, unsigned k,
+                                      const int32_t *a_row_index, unsigned a_rows, const int32_t *c_row_index, unsigned c_rows, int a_type,
+                                      int b_type);
 
 /*
  * Native-class MoE launch (no counterpart in the reference): the routed-expert launch on the block-scaled MFMA, the accuracy class of

@@ -1,6 +1,7 @@
 // gemm_invariant_host.h -- the host side of the batch-invariant GEMM (include/petit_amd.h "Batch-invariant GEMM") that needs no GPU: the
 // geometry, the form switch, the workspace arithmetic, the argument checks and the CPU twin.  Plain C++ (no HIP), so that the same lines build
-// into libpetit_amd.so (gemm_invariant.hip) and into a stand-alone program for sanitizer runs (tools/gemm_invariant_hostcheck.cc).
+// into libpetit_amd.so (gemm_invariant.hip, gemm_invariant_moe.hip) and into stand-alone programs for sanitizer runs
+// (tools/gemm_invariant_hostcheck.cc, tools/moe_invariant_hostcheck.cc).  The routed-expert (MoE) launch's part is at the end.
 #pragma once
 
 #include <stddef.h>
@@ -176,6 +177,112 @@ inline int gemm_host(void *c, const void *a, const void *b, const void *scales, 
                 y = y + h16_f32(bf16, b16[col]);
             c16[(size_t)row * n + col] = (uint16_t)f32_h16(bf16, y);
         }
+    }
+    return kRcOk;
+}
+
+// ---- the routed-expert (MoE) launch (include/petit_amd.h "Batch-invariant MoE launch") -----------------------------------------------------
+
+constexpr unsigned kMoeMaxExperts = 1024;      // kMoeMaxExperts of petit_internal.h
+// The form switch's two constants, measured (profiles/moe_invariant.md): the whole form wins wherever the routing gives it workgroups enough to
+// fill the chip -- from about 8 to 13 grouped rows on -- and by 2x and more from 64 rows; the split form wins at a decode step's 4 to 8 rows.
+constexpr unsigned kMoeSplitMaxRowsPer = 8;    // split form: ceil(m / min(E, m)) <= this (the rows-per-active-expert estimate of the MoE pick) ...
+constexpr unsigned kMoeSplitMaxM = 8;          // ... and m <= this (also the cap of the slab workspace S * m * n * 4); at 8 the first is implied
+
+// the form switch: a function of (m, num_experts) alone.  Either form gives the same bits, so it is a speed choice only.
+inline bool moe_split(unsigned m, unsigned num_experts) {
+    const unsigned active = num_experts < m ? num_experts : m;
+    if (active == 0)
+        return true;
+    return (m + active - 1) / active <= kMoeSplitMaxRowsPer && m <= kMoeSplitMaxM;
+}
+
+// workgroups of the larger launch of a call (one linear index in grid x)
+inline uint64_t moe_grid(unsigned m, unsigned n, unsigned num_experts, unsigned slices, bool split, int activation) {
+    const uint64_t active = num_experts < m ? num_experts : m, ntiles = n / 16;
+    if (split)
+        return ((m + 15ull) / 16 + active) * slices * ((ntiles + 3) / 4);
+    const uint64_t pairs = activation ? ntiles / 2 : (ntiles + 1) / 2;
+    return ((m + 63ull) / 64 + active) * ((pairs + 3) / 4);
+}
+
+// every refusal that depends on shape, types and counts alone
+inline int moe_shape_rc(unsigned num_experts, unsigned m, unsigned n, unsigned k, const int32_t *a_row_index, unsigned a_rows,
+                        const int32_t *c_row_index, unsigned c_rows, int a_type, int b_type, int activation) {
+    const int rc = shape_rc(m, n, k, a_type, b_type, activation);
+    if (rc != kRcOk)
+        return rc;
+    if (num_experts == 0 || num_experts > kMoeMaxExperts)
+        return kRcProblemShape;
+    // a null index is the identity: the rows it would name must exist
+    if ((!a_row_index && a_rows < m) || (!c_row_index && c_rows < m))
+        return kRcProblemShape;
+    // one descriptor bounds every A load, and the kernels' out-of-range voffset (2^31) must lie past its end
+    if ((uint64_t)a_rows * k * 2 > (1ull << 31))
+        return kRcProblemShape;
+    unsigned S, L;
+    geometry(n, k, a_type, b_type, &S, &L);
+    if (moe_grid(m, n, num_experts, S, moe_split(m, num_experts), activation) >= (1ull << 31))
+        return kRcProblemShape;
+    return kRcOk;
+}
+
+inline uint64_t moe_workspace_bytes(unsigned num_experts, unsigned m, unsigned n, unsigned k, int a_type, int b_type) {
+    if (shape_rc(m, n, k, a_type, b_type, 0) != kRcOk || num_experts == 0 || num_experts > kMoeMaxExperts || m == 0 || !moe_split(m, num_experts))
+        return 0;
+    unsigned S, L;
+    geometry(n, k, a_type, b_type, &S, &L);
+    return ((uint64_t)S * m * n * 4 + 255) / 256 * 256;
+}
+
+// the pointer checks of a MoE call that passed moe_shape_rc and has m > 0
+inline int moe_pointers_rc(const void *c, const void *a, const void *b, const void *scales, const void *global_scales, const void *expert_offsets,
+                           const void *a_row_index, const void *c_row_index, const void *bias, const void *workspace, uint64_t workspace_need) {
+    if (!global_scales || !expert_offsets || (((uintptr_t)global_scales | (uintptr_t)expert_offsets | (uintptr_t)a_row_index | (uintptr_t)c_row_index) & 3u))
+        return kRcProblemShape;
+    return pointers_rc(c, a, b, scales, bias, workspace, workspace_need);
+}
+
+// The CPU twin: gemm_host per expert under the clamp rule (each offset clamped into [its predecessor, m], a running maximum), with HOST offsets
+// and indices.  Plain epilogue.  An A index outside [0, a_rows) reads a zero row, a C index outside [0, c_rows) stores nothing, rows of no
+// expert are left untouched.  bias: [num_experts][n] or null.
+inline int moe_gemm_host(void *c, const void *a, const void *b, const void *scales, const float *global_scales, const void *bias,
+                         const int32_t *expert_offsets, unsigned num_experts, unsigned m, unsigned n, unsigned k, const int32_t *a_row_index,
+                         unsigned a_rows, const int32_t *c_row_index, unsigned c_rows, int a_type, int b_type) {
+    const int rc = moe_shape_rc(num_experts, m, n, k, a_row_index, a_rows, c_row_index, c_rows, a_type, b_type, 0);
+    if (rc != kRcOk)
+        return rc;
+    if (m == 0)
+        return kRcOk;
+    if (!c || !a || !b || !scales || !global_scales || !expert_offsets)
+        return kRcProblemShape;
+    const size_t w_bytes = (size_t)n * k / 2, s_bytes = (size_t)n * k / (is_mx(b_type) ? 32 : 16);
+    auto clamp = [&](int32_t v, unsigned lo) {
+        const unsigned u = v < 0 ? 0u : (unsigned)v;
+        return u < lo ? lo : (u > m ? m : u);
+    };
+    unsigned lo = clamp(expert_offsets[0], 0);
+    std::vector<uint16_t> rows_a, rows_c;
+    for (unsigned e = 0; e < num_experts; ++e) {
+        const unsigned hi = clamp(expert_offsets[e + 1], lo), rows = hi - lo;
+        if (rows) {
+            rows_a.assign((size_t)rows * k, 0), rows_c.assign((size_t)rows * n, 0);
+            for (unsigned r = 0; r < rows; ++r) {
+                const unsigned src = a_row_index ? (unsigned)a_row_index[lo + r] : lo + r;
+                if (src < a_rows)
+                    memcpy(&rows_a[(size_t)r * k], (const uint16_t *)a + (size_t)src * k, (size_t)k * 2);
+            }
+            const int grc = gemm_host(rows_c.data(), rows_a.data(), (const char *)b + e * w_bytes, (const char *)scales + e * s_bytes,
+                                      global_scales + e, bias ? (const uint16_t *)bias + (size_t)e * n : nullptr, rows, n, k, a_type, b_type);
+            if (grc != kRcOk)
+                return grc;
+            for (unsigned r = 0; r < rows; ++r) {
+                const unsigned dst = c_row_index ? (unsigned)c_row_index[lo + r] : lo + r;
+                if (dst < c_rows)
+                    memcpy((uint16_t *)c + (size_t)dst * n, &rows_c[(size_t)r * n], (size_t)n * 2);
+            }
+        }
+        lo = hi;
     }
     return kRcOk;
 }

@@ -382,6 +382,57 @@ void mul_mxfp4_a16_moe_indexed_out(const at::Tensor &out, PETIT_MOE_INDEXED_ARGS
     mul_a16_moe_indexed_impl(true, A, B, s, gs, off, m, n, k, e, a_idx, c_idx, c_rows, solution_id, bias, activation, &out);
 }
 
+// the batch-invariant MoE launch (petit_gemm_{fp4,mxfp4}_fp16_moe_invariant): the indexed launch's arguments without a solution id.  The
+// argument checks and their texts are stated once, in petit_kernel/ops.py (_check_moe_invariant), which petit_kernel/compiled.py runs in front
+// of these ops; what is checked here is what keeps a direct torch.ops call inside its tensors.
+#define PETIT_MOE_INVARIANT_ARGS                                                                                                                 \
+    const at::Tensor &A, const at::Tensor &B, const at::Tensor &s, const at::Tensor &gs, const at::Tensor &off, int64_t m, int64_t n, int64_t k, \
+        int64_t e, const std::optional<at::Tensor> &a_idx, const std::optional<at::Tensor> &c_idx, int64_t c_rows,                               \
+        const std::optional<at::Tensor> &bias, int64_t activation
+at::Tensor mul_a16_moe_invariant_impl(bool mx, PETIT_MOE_INVARIANT_ARGS, const at::Tensor *out) {
+    check_a16(A);
+    check_expert_operands(mx, false, A, B, &s, gs, off, e, n, k);
+    TORCH_CHECK(m >= 0 && A.is_contiguous() && k > 0 && A.numel() % k == 0, "A must be a contiguous [a_rows, size_k] tensor");
+    check_row_indices(a_idx, c_idx, A, m);
+    check_activation(activation, n);
+    check_bias(bias, A, A.scalar_type(), e * n, "bias must be a contiguous [num_experts, size_n] tensor of A's dtype on A's device");
+    const int64_t a_rows = A.numel() / k, n_out = activation ? n / 2 : n;
+    const c10::hip::HIPGuardMasqueradingAsCUDA guard(A.device());
+    at::Tensor c;
+    if (out) {
+        TORCH_CHECK(out->is_cuda() && out->device() == A.device() && out->scalar_type() == A.scalar_type() && out->is_contiguous() && out->dim() == 2 &&
+                        out->size(1) == n_out,
+                    "out must be a contiguous [c_rows, n_out] tensor of A's dtype on A's device");
+        TORCH_CHECK(c_rows < 0 || c_rows == out->size(0), "c_rows does not match out.size(0)");
+        c = *out;
+        c_rows = out->size(0);
+    } else {
+        c_rows = c_rows < 0 ? m : c_rows;
+        c = at::empty({c_rows, n_out}, A.options());
+    }
+    const int a_type = a_type_of(A.scalar_type()), b_type = mx ? kCxxMxFp4 : kCxxFp4;
+    const petit_solution_hints hints{a_type, b_type, a_type, 0};
+    const petit_epilogue epi{bias.has_value() ? bias->data_ptr() : nullptr, (int32_t)activation, 0};
+    const uint64_t ws_bytes = petit_gemm_moe_invariant_workspace_bytes((unsigned)e, (unsigned)m, (unsigned)n, (unsigned)k, a_type, b_type);
+    at::Tensor ws;
+    if (ws_bytes)
+        ws = at::empty({(int64_t)ws_bytes}, A.options().dtype(at::kByte));
+    auto fn = mx ? petit_gemm_mxfp4_fp16_moe_invariant : petit_gemm_fp4_fp16_moe_invariant;
+    const int rc = fn(c.data_ptr(), A.data_ptr(), B.data_ptr(), s.data_ptr(), (const float *)gs.data_ptr(), (const int32_t *)off.data_ptr(),
+                      (unsigned)e, (unsigned)m, (unsigned)n, (unsigned)k, row_index_ptr(a_idx), (unsigned)a_rows, row_index_ptr(c_idx),
+                      (unsigned)c_rows, &hints, (bias.has_value() || activation) ? &epi : nullptr, ws_bytes ? ws.data_ptr() : nullptr, stream_of(A));
+    TORCH_CHECK(rc != PETIT_ERROR_PROBLEM_SHAPE, "Incompatible problem shape (m=", m, ", n=", n, ", k=", k, ", num_experts=", e, ", a_rows=", a_rows,
+                ", c_rows=", c_rows, ")");
+    TORCH_CHECK(rc != PETIT_ERROR_KERNEL_SHAPE, "No batch-invariant kernel for these types.");
+    TORCH_CHECK(rc == PETIT_OK, mx ? "mul_mxfp4_a16_moe_invariant" : "mul_nvfp4_a16_moe_invariant", ": ", petit_error_string(rc));
+    return c;
+}
+#define PETIT_MOE_INVARIANT_PASS A, B, s, gs, off, m, n, k, e, a_idx, c_idx, c_rows, bias, activation
+at::Tensor mul_nvfp4_a16_moe_invariant(PETIT_MOE_INVARIANT_ARGS) { return mul_a16_moe_invariant_impl(false, PETIT_MOE_INVARIANT_PASS, nullptr); }
+at::Tensor mul_mxfp4_a16_moe_invariant(PETIT_MOE_INVARIANT_ARGS) { return mul_a16_moe_invariant_impl(true, PETIT_MOE_INVARIANT_PASS, nullptr); }
+void mul_nvfp4_a16_moe_invariant_out(const at::Tensor &out, PETIT_MOE_INVARIANT_ARGS) { mul_a16_moe_invariant_impl(false, PETIT_MOE_INVARIANT_PASS, &out); }
+void mul_mxfp4_a16_moe_invariant_out(const at::Tensor &out, PETIT_MOE_INVARIANT_ARGS) { mul_a16_moe_invariant_impl(true, PETIT_MOE_INVARIANT_PASS, &out); }
+
 // device routing (petit_moe_align / petit_moe_combine); the same checks and texts as petit_kernel/ops.py
 void check_topk_ids(const at::Tensor &ids, int64_t num_experts) {
     TORCH_CHECK(num_experts >= 1 && num_experts <= PETIT_MOE_MAX_EXPERTS, "num_experts must be in 1..", PETIT_MOE_MAX_EXPERTS, ", got ", num_experts);
@@ -810,6 +861,11 @@ at::Tensor mul_a16_moe_indexed_meta(PETIT_MOE_INDEXED_ARGS) {
     return at::empty({c_rows < 0 ? m : c_rows, activation ? n / 2 : n}, A.options());
 }
 void mul_a16_moe_indexed_out_meta(const at::Tensor &, PETIT_MOE_INDEXED_ARGS) {}
+at::Tensor mul_a16_moe_invariant_meta(PETIT_MOE_INVARIANT_ARGS) {
+    check_a16(A);
+    return at::empty({c_rows < 0 ? m : c_rows, activation ? n / 2 : n}, A.options());
+}
+void mul_a16_moe_invariant_out_meta(const at::Tensor &, PETIT_MOE_INVARIANT_ARGS) {}
 at::Tensor mul_nvfp4_native_transient_meta(PETIT_NV_TRANSIENT_ARGS) {
     return native_output(A, native_moe_dtype(A, a_format, a_type), size_m, size_m, activation ? size_n / 2 : size_n, out_format);
 }
@@ -928,6 +984,13 @@ TORCH_LIBRARY(petit_kernel, m) {
           "int activation=0) -> Tensor");
     m.def("mul_mxfp4_a16_invariant(Tensor A, Tensor B, Tensor s, Tensor? global_scale, int size_m, int size_n, int size_k, Tensor? bias=None, "
           "int activation=0) -> Tensor");
+#define PETIT_MOE_INVARIANT_SCHEMA                                                                                                        \
+    "Tensor A, Tensor B, Tensor s, Tensor global_scales, Tensor expert_offsets, int size_m, int size_n, int size_k, int num_experts, " \
+    "Tensor? a_row_index=None, Tensor? c_row_index=None, int c_rows=-1, Tensor? bias=None, int activation=0"
+    m.def("mul_nvfp4_a16_moe_invariant(" PETIT_MOE_INVARIANT_SCHEMA ") -> Tensor");
+    m.def("mul_mxfp4_a16_moe_invariant(" PETIT_MOE_INVARIANT_SCHEMA ") -> Tensor");
+    m.def("mul_nvfp4_a16_moe_invariant_out(Tensor(a!) out, " PETIT_MOE_INVARIANT_SCHEMA ") -> ()");
+    m.def("mul_mxfp4_a16_moe_invariant_out(Tensor(a!) out, " PETIT_MOE_INVARIANT_SCHEMA ") -> ()");
     // round 3's op name (scales promised inside fp16's range): an alias of mul_mxfp4_a16 for one more round -- the kernels test the range themselves
     m.def("mul_mxfp4_a16_f16range(Tensor A, Tensor B, Tensor s, Tensor global_scale, int size_m, int size_n, int size_k, int solution_id, "
           "Tensor? bias=None, int activation=0) -> Tensor");
@@ -948,6 +1011,10 @@ TORCH_LIBRARY(petit_kernel, m) {
     m.impl("mul_mxfp4_a16_moe_indexed", &mul_mxfp4_a16_moe_indexed); \
     m.impl("mul_nvfp4_a16_moe_indexed_out", &mul_nvfp4_a16_moe_indexed_out); \
     m.impl("mul_mxfp4_a16_moe_indexed_out", &mul_mxfp4_a16_moe_indexed_out); \
+    m.impl("mul_nvfp4_a16_moe_invariant", &mul_nvfp4_a16_moe_invariant); \
+    m.impl("mul_mxfp4_a16_moe_invariant", &mul_mxfp4_a16_moe_invariant); \
+    m.impl("mul_nvfp4_a16_moe_invariant_out", &mul_nvfp4_a16_moe_invariant_out); \
+    m.impl("mul_mxfp4_a16_moe_invariant_out", &mul_mxfp4_a16_moe_invariant_out); \
     m.impl("mul_mxfp4_native_moe", &mul_mxfp4_native_moe);      \
     m.impl("mul_nvfp4_native_moe", &mul_nvfp4_native_moe);      \
     m.impl("mul_nvfp4_native_moe_transient", &mul_nvfp4_native_moe_transient); \
@@ -979,6 +1046,10 @@ TORCH_LIBRARY_IMPL(petit_kernel, Meta, m) {
     m.impl("mul_mxfp4_a16_moe_indexed", &mul_a16_moe_indexed_meta);
     m.impl("mul_nvfp4_a16_moe_indexed_out", &mul_a16_moe_indexed_out_meta);
     m.impl("mul_mxfp4_a16_moe_indexed_out", &mul_a16_moe_indexed_out_meta);
+    m.impl("mul_nvfp4_a16_moe_invariant", &mul_a16_moe_invariant_meta);
+    m.impl("mul_mxfp4_a16_moe_invariant", &mul_a16_moe_invariant_meta);
+    m.impl("mul_nvfp4_a16_moe_invariant_out", &mul_a16_moe_invariant_out_meta);
+    m.impl("mul_mxfp4_a16_moe_invariant_out", &mul_a16_moe_invariant_out_meta);
     m.impl("mul_mxfp4_native_moe", &mul_native_moe_meta);
     m.impl("mul_nvfp4_native_moe", &mul_native_moe_meta);
     m.impl("mul_nvfp4_native_moe_transient", &mul_native_moe_transient_meta);

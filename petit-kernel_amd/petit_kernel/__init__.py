@@ -134,6 +134,37 @@ def invariant_workspace_bytes(size_m: int, size_n: int, size_k: int, dtype: torc
     return ops.invariant_workspace_bytes(size_m, size_n, size_k, dtype, kind)
 
 
+def mul_nvfp4_a16_moe_invariant(a: torch.Tensor, b: torch.Tensor, s: torch.Tensor, global_scales: torch.Tensor, expert_offsets: torch.Tensor,
+                                size_m: int, size_n: int, size_k: int, num_experts: int, a_row_index: torch.Tensor = None,
+                                c_row_index: torch.Tensor = None, c_rows: int = None, bias: torch.Tensor = None, activation: str = None,
+                                out: torch.Tensor = None) -> torch.Tensor:
+    # mul_nvfp4_a16_moe_indexed by the batch-invariant entry (include/petit_amd.h "Batch-invariant MoE launch"): every written row equals,
+    # bit for bit, mul_nvfp4_a16_invariant(size_m=1) on its A row with its expert's tensors, global scale and bias -- whatever the batch,
+    # the routing and the row's position.  Opt-in: slower than the default pick (profiles/moe_invariant.md), no solution_id.
+    return _impl.mul_nvfp4_a16_moe_invariant(a, b, s, global_scales, expert_offsets, size_m, size_n, size_k, num_experts, a_row_index, c_row_index,
+                                             c_rows, bias, activation, out)
+
+
+def mul_mxfp4_a16_moe_invariant(a: torch.Tensor, b: torch.Tensor, s: torch.Tensor, global_scales: torch.Tensor, expert_offsets: torch.Tensor,
+                                size_m: int, size_n: int, size_k: int, num_experts: int, a_row_index: torch.Tensor = None,
+                                c_row_index: torch.Tensor = None, c_rows: int = None, bias: torch.Tensor = None, activation: str = None,
+                                out: torch.Tensor = None) -> torch.Tensor:
+    # the same for MXFP4 experts; bfloat16 activations only
+    return _impl.mul_mxfp4_a16_moe_invariant(a, b, s, global_scales, expert_offsets, size_m, size_n, size_k, num_experts, a_row_index, c_row_index,
+                                             c_rows, bias, activation, out)
+
+
+def moe_invariant_form(size_m: int, num_experts: int) -> int:
+    # the form a batch-invariant MoE call gets: 1 split (slabs in scratch, two launches), 0 whole -- a function of these two arguments alone
+    return ops.moe_invariant_form(size_m, num_experts)
+
+
+def moe_invariant_workspace_bytes(num_experts: int, size_m: int, size_n: int, size_k: int, dtype: torch.dtype = torch.bfloat16,
+                                  kind: str = "nvfp4") -> int:
+    # bytes of scratch the batch-invariant MoE call allocates per call (the Python layers do it themselves); 0 in the whole form
+    return ops.moe_invariant_workspace_bytes(num_experts, size_m, size_n, size_k, dtype, kind)
+
+
 def mul_nvfp4_a16_moe(a: torch.Tensor, b: torch.Tensor, s: torch.Tensor, global_scales: torch.Tensor, expert_offsets: torch.Tensor,
                       size_m: int, size_n: int, size_k: int, num_experts: int, solution_id: int = -1, bias: torch.Tensor = None,
                       activation: str = None) -> torch.Tensor:
@@ -333,6 +364,10 @@ __all__ = [
     "invariant_geometry",
     "invariant_slabs",
     "invariant_workspace_bytes",
+    "mul_nvfp4_a16_moe_invariant",
+    "mul_mxfp4_a16_moe_invariant",
+    "moe_invariant_form",
+    "moe_invariant_workspace_bytes",
     "get_fp4_solutions",
     "mxfp4_scales_in_fp16_range",
     "DataType",

@@ -16,7 +16,9 @@ import torch
 from . import _lib  # loads libpetit_amd.so first (the binding links against it)
 from .ops import QuantizedActivations, _a_type, _activation as _act, _activation_operand, _quantized_format
 from .ops import _check_invariant, _check_route_hidden, _check_router, _combine_norm_operands, _combine_norm_returns
+from .ops import _check_moe_invariant
 from .ops import invariant_geometry, invariant_slabs, invariant_workspace_bytes  # (queries: plain C calls, no op behind them)
+from .ops import moe_invariant_form, moe_invariant_workspace_bytes
 
 LIB_PATH = Path(_lib.LIB_PATH).parent / "libpetit_torch.so"
 _loaded = False
@@ -133,6 +135,29 @@ def mul_mxfp4_a16_moe_indexed(A, B, s, global_scales, expert_offsets, size_m, si
                               c_rows=None, solution_id=-1, bias=None, activation=None, out=None):
     return _mul_moe_indexed("mx", A, B, s, global_scales, expert_offsets, size_m, size_n, size_k, num_experts, a_row_index, c_row_index, c_rows,
                             solution_id, bias, activation, out)
+
+
+def _mul_moe_invariant(kind, A, B, s, global_scales, expert_offsets, size_m, size_n, size_k, num_experts, a_row_index, c_row_index, c_rows, bias,
+                       activation, out):
+    E, act, _, c_rows = _check_moe_invariant(kind, A, B, s, global_scales, expert_offsets, size_m, size_n, size_k, num_experts, a_row_index,
+                                             c_row_index, c_rows, bias, activation, out)
+    args = (A, B, s, global_scales, expert_offsets, int(size_m), int(size_n), int(size_k), E, a_row_index, c_row_index, int(c_rows), bias, act)
+    if out is None:
+        return getattr(torch.ops.petit_kernel, f"mul_{kind}fp4_a16_moe_invariant")(*args)
+    getattr(torch.ops.petit_kernel, f"mul_{kind}fp4_a16_moe_invariant_out")(out, *args)
+    return out
+
+
+def mul_nvfp4_a16_moe_invariant(A, B, s, global_scales, expert_offsets, size_m, size_n, size_k, num_experts, a_row_index=None,
+                                c_row_index=None, c_rows=None, bias=None, activation=None, out=None):
+    return _mul_moe_invariant("nv", A, B, s, global_scales, expert_offsets, size_m, size_n, size_k, num_experts, a_row_index, c_row_index,
+                              c_rows, bias, activation, out)
+
+
+def mul_mxfp4_a16_moe_invariant(A, B, s, global_scales, expert_offsets, size_m, size_n, size_k, num_experts, a_row_index=None,
+                                c_row_index=None, c_rows=None, bias=None, activation=None, out=None):
+    return _mul_moe_invariant("mx", A, B, s, global_scales, expert_offsets, size_m, size_n, size_k, num_experts, a_row_index, c_row_index,
+                              c_rows, bias, activation, out)
 
 
 def moe_align_device(topk_ids, num_experts):

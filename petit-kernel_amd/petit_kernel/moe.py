@@ -84,7 +84,7 @@ def fp4_moe(hidden: torch.Tensor, w13: torch.Tensor, s13: torch.Tensor, gs13: to
 def fp4_moe_fused(hidden: torch.Tensor, w13: torch.Tensor, s13: torch.Tensor, gs13: torch.Tensor, w2: torch.Tensor, s2: torch.Tensor,
                   gs2: torch.Tensor, topk_weights: torch.Tensor, topk_ids: torch.Tensor, kind: str = "nvfp4", *, bias13: torch.Tensor = None,
                   bias2: torch.Tensor = None, activation: str = "silu_mul", norm_weight: torch.Tensor = None, norm_eps: float = 1e-6,
-                  norm_residual: torch.Tensor = None, norm_weight_offset: float = 0.0, norm_fmt: str = None):
+                  norm_residual: torch.Tensor = None, norm_weight_offset: float = 0.0, norm_fmt: str = None, invariant: bool = False):
     """fp4_moe's layer (same arguments, same result up to the combine's rounding order) on the indexed MoE launches: align on the device,
     gate_up on gathered rows, down scattered into slot order, the top-k combine.  topk_ids: int32 or int64 [T, topk]; entries outside
     [0, E) (-1 under expert parallelism) contribute nothing.  topk_weights: float32 or bfloat16 [T, topk] (converted to float32 once).
@@ -97,11 +97,20 @@ def fp4_moe_fused(hidden: torch.Tensor, w13: torch.Tensor, s13: torch.Tensor, gs
     norm_residual) in 16 bits, y16 = RMSNorm(h) * (norm_weight + norm_weight_offset), q = quantize_activations(y16, norm_fmt), each bit for bit
     what the un-fused layer followed by rmsnorm_quantize gives.  The fused end is for a layer whose combine is COMPLETE on this rank: under
     tensor or expert parallelism an all-reduce belongs between the combine and the residual add, so such a layer ends in moe_combine.
-    Measured (profiles/moe_combine_norm.md) against moe_combine followed by the norm."""
+    Measured (profiles/moe_combine_norm.md) against moe_combine followed by the norm.
+
+    invariant=True: gate_up and down run as the batch-invariant MoE launches (mul_*_a16_moe_invariant) in place of the indexed ones;
+    everything else is unchanged.  Every slot row is then a pure function of its token's hidden row and its expert's weights, and the
+    combine adds a token's slots in slot order, in fp32, with one rounding: given the same topk_weights / topk_ids row, a token's output row
+    has the same bits alone and inside any batch, at any position.  This holds with the fused norm end too (both returned tensors: the norm
+    works per row).  Under expert or tensor parallelism it holds only up to the all-reduce, which is outside this library.  Opt-in and slower
+    (profiles/moe_invariant.md); float16 hidden states with kind 'mxfp4' have no batch-invariant kernel."""
     _check_fused(kind, activation)
+    _check_invariant_layer(invariant, "fused", kind, hidden)
     norm = _norm_end(norm_weight, norm_eps, norm_residual, norm_weight_offset, norm_fmt)
     w, ids, sorted_pos, offsets, token_index = _align_routing(topk_weights, topk_ids, gs13.numel())
-    return _fused_after_align(hidden, w13, s13, gs13, w2, s2, gs2, w, ids, sorted_pos, offsets, token_index, kind, bias13, bias2, activation, norm)
+    return _fused_after_align(hidden, w13, s13, gs13, w2, s2, gs2, w, ids, sorted_pos, offsets, token_index, kind, bias13, bias2, activation, norm,
+                              invariant)
 
 
 def _norm_end(norm_weight, norm_eps, norm_residual, norm_weight_offset, norm_fmt):
@@ -133,10 +142,26 @@ def _check_fused(kind, activation) -> None:
     _check_activation(activation)
 
 
-def _fused_after_align(hidden, w13, s13, gs13, w2, s2, gs2, w, ids, sorted_pos, offsets, token_index, kind, bias13, bias2, activation, norm=None):
-    """fp4_moe_fused after its align: gate_up on gathered rows, down scattered into slot order, the combine (w float32, ids int32 / int64)."""
-    from . import mul_mxfp4_a16_moe_indexed, mul_nvfp4_a16_moe_indexed
-    mul = mul_nvfp4_a16_moe_indexed if kind == "nvfp4" else mul_mxfp4_a16_moe_indexed
+def _check_invariant_layer(invariant, path, kind, hidden) -> None:
+    if not invariant:
+        return
+    if path == "native":
+        raise RuntimeError("invariant=True is for path 'fused': the native class quantises activations per call and has no batch-invariant "
+                           "kernel")
+    if kind == "mxfp4" and hidden.dtype == torch.float16:
+        raise RuntimeError("invariant=True with kind 'mxfp4' needs bfloat16 hidden states: float16 activations with MXFP4 weights have no "
+                           "batch-invariant kernel")
+
+
+def _fused_after_align(hidden, w13, s13, gs13, w2, s2, gs2, w, ids, sorted_pos, offsets, token_index, kind, bias13, bias2, activation, norm=None,
+                       invariant=False):
+    """fp4_moe_fused after its align: gate_up on gathered rows, down scattered into slot order, the combine (w float32, ids int32 / int64).
+    invariant: the two launches are the batch-invariant ones."""
+    from . import mul_mxfp4_a16_moe_indexed, mul_mxfp4_a16_moe_invariant, mul_nvfp4_a16_moe_indexed, mul_nvfp4_a16_moe_invariant
+    if invariant:
+        mul = mul_nvfp4_a16_moe_invariant if kind == "nvfp4" else mul_mxfp4_a16_moe_invariant
+    else:
+        mul = mul_nvfp4_a16_moe_indexed if kind == "nvfp4" else mul_mxfp4_a16_moe_indexed
     T, H = hidden.shape
     topk = ids.shape[1]
     E = gs13.numel()
@@ -228,7 +253,7 @@ def fp4_moe_routed(hidden: torch.Tensor, router_logits: torch.Tensor, w13: torch
                    bias13: torch.Tensor = None, bias2: torch.Tensor = None, activation: str = "silu_mul", transient: bool = False,
                    norm_weight: torch.Tensor = None, norm_eps: float = 1e-6, norm_residual: torch.Tensor = None, norm_weight_offset: float = 0.0,
                    norm_fmt: str = None, router_weight: torch.Tensor = None, router_bias: torch.Tensor = None,
-                   router_input: torch.Tensor = None, **routing):
+                   router_input: torch.Tensor = None, invariant: bool = False, **routing):
     """The layer from the router's logits: moe_route_align(router_logits, topk, **routing), then exactly the launches fp4_moe_fused (path
     'fused') or fp4_moe_native (path 'native', with `activations`) issue after their align -- bit for bit
     fp4_moe_fused(..., *moe_route(router_logits, topk, **routing)).  router_logits [T, E] float32 / bfloat16 / float16; routing: moe_route's
@@ -251,7 +276,14 @@ def fp4_moe_routed(hidden: torch.Tensor, router_logits: torch.Tensor, w13: torch
 
     norm_weight / norm_eps / norm_residual / norm_weight_offset / norm_fmt: fp4_moe_fused's fused end on either path (returns (h, y16) or
     (q, h)): with route + align in one launch the whole layer and the next block's norm are four launches.  For a layer whose combine is complete
-    on this rank (no all-reduce between the combine and the residual add)."""
+    on this rank (no all-reduce between the combine and the residual add).
+
+    invariant=True (path 'fused'): fp4_moe_fused's switch -- gate_up and down run as the batch-invariant MoE launches.  From
+    router_weight=... (or from router_logits that are themselves batch-invariant) the whole layer is then batch-invariant: the router's
+    logits, with the tie rule the chosen experts and their weights, every slot row and the combine are pure functions of the token's hidden
+    row and the weights, so a token's output row has the same bits alone and inside any batch.  This holds with the fused norm end too (both
+    returned tensors).  Under expert or tensor parallelism it holds only up to the all-reduce, which is outside this library.  path 'native'
+    and kind 'mxfp4' on float16 hidden states have no batch-invariant kernel and raise."""
     from . import moe_route_align, moe_route_hidden
     if path not in ("fused", "native"):
         raise RuntimeError("path must be 'fused' or 'native'")
@@ -263,6 +295,7 @@ def fp4_moe_routed(hidden: torch.Tensor, router_logits: torch.Tensor, w13: torch
             raise RuntimeError("transient=True is for path 'native'")
     else:
         _check_native(kind, activation, activations, transient)
+    _check_invariant_layer(invariant, path, kind, hidden)
     if router_weight is not None:
         if router_logits is not None:
             raise RuntimeError("router_logits must be None when router_weight is given: the layer then starts at the hidden state")
@@ -292,6 +325,6 @@ def fp4_moe_routed(hidden: torch.Tensor, router_logits: torch.Tensor, w13: torch
         w, ids, sorted_pos, offsets, token_index = moe_route_align(router_logits, topk, **routing)
     if path == "fused":
         return _fused_after_align(hidden, w13, s13, gs13, w2, s2, gs2, w, ids, sorted_pos, offsets, token_index, kind, bias13, bias2, activation,
-                                  norm)
+                                  norm, invariant)
     return _native_after_align(hidden, w13, s13, gs13, w2, s2, gs2, w, ids, sorted_pos, offsets, token_index, kind, activations, bias13, bias2,
                                activation, transient, norm)

@@ -919,6 +919,107 @@ def mul_mxfp4_a16_moe_indexed(A, B, s, global_scales, expert_offsets, size_m, si
                             solution_id, bias, activation, out)
 
 
+# --- the batch-invariant MoE launch (include/petit_amd.h "Batch-invariant MoE launch"; no counterpart in the reference) ---------------------
+
+def _check_moe_invariant(kind: str, A, B, s, global_scales, expert_offsets, size_m, size_n, size_k, num_experts, a_row_index, c_row_index,
+                         c_rows, bias, activation, out):
+    """The argument checks of mul_nvfp4_a16_moe_invariant / mul_mxfp4_a16_moe_invariant, stated here for both operator layers; returns
+    (E, activation code, a_rows, c_rows).  Value checks come first and device checks last, so that the texts can be read without a GPU."""
+    name = "mul_%sfp4_a16_moe_invariant" % kind
+    _check(A.dtype in (torch.bfloat16, torch.float16), "A must be bfloat16 or float16.")
+    size_m, size_n, size_k, E = int(size_m), int(size_n), int(size_k), int(num_experts)
+    _check(1 <= E <= _lib.PETIT_MOE_MAX_EXPERTS, f"num_experts must be in 1..{_lib.PETIT_MOE_MAX_EXPERTS}, got {E}")
+    _check(size_n > 0 and size_n % (32 if kind == "mx" else 16) == 0 and size_k > 0 and size_k % 256 == 0 and 0 <= size_m < 1 << 20,
+           f"Incompatible problem shape (m={size_m}, n={size_n}, k={size_k}): {name} needs n % {32 if kind == 'mx' else 16} == 0, "
+           "k % 256 == 0, m < 2^20")
+    _check(not (kind == "mx" and A.dtype == torch.float16),
+           f"{name}: float16 activations with MXFP4 weights have no batch-invariant kernel (use bfloat16)")
+    act = _activation(activation, size_n)
+    _check(A.is_contiguous() and A.numel() % size_k == 0, "A must be a contiguous [a_rows, size_k] tensor")
+    a_rows = A.numel() // size_k
+    _check(a_rows * size_k * 2 <= 1 << 31, f"{name}: A holds more than 2^31 bytes (a_rows={a_rows}, k={size_k})")
+    group = 32 if kind == "mx" else 16
+    _check(B.is_contiguous() and B.numel() * B.element_size() == E * size_n * size_k // 2,
+           "B does not hold num_experts * size_n * size_k packed 4-bit weights")
+    _check(s.is_contiguous() and s.numel() * s.element_size() == E * size_n * size_k // group,
+           f"s does not hold num_experts * size_n * size_k / {group} scales")
+    _check(global_scales.dtype == torch.float32 and global_scales.is_contiguous() and global_scales.numel() == E,
+           "global_scales must be a contiguous float32 [num_experts] tensor")
+    _check(expert_offsets.dtype == torch.int32 and expert_offsets.is_contiguous() and expert_offsets.numel() == E + 1,
+           "expert_offsets must be a contiguous int32 [num_experts + 1] tensor")
+    for idx in (a_row_index, c_row_index):
+        if idx is not None:
+            _check(idx.dtype == torch.int32 and idx.is_contiguous() and idx.numel() == size_m and idx.device == A.device,
+                   "row indices must be contiguous int32 [size_m] tensors on A's device")
+    n_out = size_n // 2 if act else size_n
+    if out is not None:
+        _check(out.device == A.device and out.dtype == A.dtype and out.is_contiguous() and out.dim() == 2 and out.size(1) == n_out,
+               "out must be a contiguous [c_rows, n_out] tensor of A's dtype on A's device")
+        _check(c_rows is None or c_rows < 0 or c_rows == out.size(0), "c_rows does not match out.size(0)")
+        c_rows = out.size(0)
+    else:
+        c_rows = size_m if c_rows is None or c_rows < 0 else int(c_rows)
+    _check((a_row_index is not None or a_rows >= size_m) and (c_row_index is not None or c_rows >= size_m),
+           f"{name}: without a row index the matrix must hold size_m rows (a_rows={a_rows}, c_rows={c_rows}, m={size_m})")
+    if bias is not None:
+        _check(bias.dtype == A.dtype and bias.is_contiguous() and bias.numel() == E * size_n and bias.device == A.device,
+               "bias must be a contiguous [num_experts, size_n] tensor of A's dtype on A's device")
+    _check(A.is_cuda and B.is_cuda and s.is_cuda and global_scales.is_cuda and expert_offsets.is_cuda, "all tensors must be on GPU")
+    _check(B.device == A.device and s.device == A.device and global_scales.device == A.device and expert_offsets.device == A.device,
+           "all tensors must be on A's device")
+    return E, act, a_rows, c_rows
+
+
+def moe_invariant_form(size_m: int, num_experts: int) -> int:
+    """The form a batch-invariant MoE call of size_m grouped rows over num_experts gets (petit_gemm_moe_invariant_form): 1 split, 0 whole.
+    Both forms give the same bits; the switch is a speed choice."""
+    return int(_lib.lib.petit_gemm_moe_invariant_form(int(size_m), int(num_experts)))
+
+
+def moe_invariant_workspace_bytes(num_experts: int, size_m: int, size_n: int, size_k: int, dtype: torch.dtype = torch.bfloat16,
+                                  kind: str = "nvfp4") -> int:
+    """Bytes of scratch the batch-invariant MoE call uses (petit_gemm_moe_invariant_workspace_bytes): the split form's slabs; 0 for the
+    whole form and for a call that would be refused."""
+    return int(_lib.lib.petit_gemm_moe_invariant_workspace_bytes(int(num_experts), int(size_m), int(size_n), int(size_k), _a_type(dtype),
+                                                                 _B_TYPES[kind]))
+
+
+def _mul_moe_invariant(kind: str, A, B, s, global_scales, expert_offsets, size_m, size_n, size_k, num_experts, a_row_index=None,
+                       c_row_index=None, c_rows=None, bias=None, activation=None, out=None) -> torch.Tensor:
+    E, act, a_rows, c_rows = _check_moe_invariant(kind, A, B, s, global_scales, expert_offsets, size_m, size_n, size_k, num_experts,
+                                                  a_row_index, c_row_index, c_rows, bias, activation, out)
+    size_m, size_n, size_k = int(size_m), int(size_n), int(size_k)
+    if out is None:
+        out = torch.empty((c_rows, size_n // 2 if act else size_n), dtype=A.dtype, device=A.device)
+    hints = _hints(kind, A.dtype)
+    epi = _epilogue(bias, act, A.device, A.dtype, E * size_n, "bias must be a contiguous [num_experts, size_n] tensor of A's dtype on A's device")
+    ws = _scratch(int(_lib.lib.petit_gemm_moe_invariant_workspace_bytes(E, size_m, size_n, size_k, hints.a_type, hints.b_type)), A.device)
+    fn = _lib.lib.petit_gemm_fp4_fp16_moe_invariant if kind == "nv" else _lib.lib.petit_gemm_mxfp4_fp16_moe_invariant
+    with torch.cuda.device(A.device):
+        err = fn(_ptr(out), _ptr(A), _ptr(B), _ptr(s), _ptr(global_scales), _ptr(expert_offsets), E, size_m, size_n, size_k,
+                 _opt_ptr(a_row_index), a_rows, _opt_ptr(c_row_index), c_rows, C.byref(hints), epi, _opt_ptr(ws), _stream(A))
+    if err:
+        _raise_gemm(err, "mul_%sfp4_a16_moe_invariant" % kind, "invariant",
+                    f"m={size_m}, n={size_n}, k={size_k}, num_experts={E}, a_rows={a_rows}, c_rows={c_rows}")
+    return out
+
+
+def mul_nvfp4_a16_moe_invariant(A, B, s, global_scales, expert_offsets, size_m, size_n, size_k, num_experts, a_row_index=None,
+                                c_row_index=None, c_rows=None, bias=None, activation=None, out=None) -> torch.Tensor:
+    """mul_nvfp4_a16_moe_indexed by the batch-invariant entry (petit_gemm_fp4_fp16_moe_invariant): every written row equals, bit for bit,
+    mul_nvfp4_a16_invariant(size_m=1) on its A row and its expert's tensors -- whatever else is in the batch and wherever the row sits.
+    Opt-in and slower than the default pick (profiles/moe_invariant.md); no solution_id."""
+    return _mul_moe_invariant("nv", A, B, s, global_scales, expert_offsets, size_m, size_n, size_k, num_experts, a_row_index, c_row_index,
+                              c_rows, bias, activation, out)
+
+
+def mul_mxfp4_a16_moe_invariant(A, B, s, global_scales, expert_offsets, size_m, size_n, size_k, num_experts, a_row_index=None,
+                                c_row_index=None, c_rows=None, bias=None, activation=None, out=None) -> torch.Tensor:
+    """The same for MXFP4 experts (petit_gemm_mxfp4_fp16_moe_invariant); bfloat16 activations only."""
+    return _mul_moe_invariant("mx", A, B, s, global_scales, expert_offsets, size_m, size_n, size_k, num_experts, a_row_index, c_row_index,
+                              c_rows, bias, activation, out)
+
+
 def _check_topk_ids(topk_ids: torch.Tensor, num_experts: int) -> None:
     _check(1 <= int(num_experts) <= _lib.PETIT_MOE_MAX_EXPERTS, f"num_experts must be in 1..{_lib.PETIT_MOE_MAX_EXPERTS}, got {num_experts}")
     _check(topk_ids.is_cuda and topk_ids.dim() == 2 and topk_ids.is_contiguous() and topk_ids.dtype in (torch.int32, torch.int64),
