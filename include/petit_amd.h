@@ -863,7 +863,9 @@ int petit_moe_route_hidden(const void *hidden, const void *weight, const float *
  *   global scale the multiply is not made.  p_s is the accumulation of slice s of K, k in [s L, min(K, (s + 1) L)), by ONE chain of
  *   v_mfma_f32_16x16x32_{bf16,f16} from a zero accumulator: the k-tiles of 128 ascending, inside a tile the four steps of the packed layout in
  *   their own order (step j covers k = 128 kt + 32 g + 8 j + i, g < 4, i < 8; petit-kernel_amd/csrc/layout.h).  The weight operand is the
- *   exactly dequantised value fp4 x group scale in the activation type (what petit_dequant_packed_weights returns with global_scale 1); the
+ *   exactly dequantised value fp4 x group scale in the activation type (what petit_dequant_packed_weights returns with global_scale 1, with
+ *   ONE exception: e8m0 scale byte 0 is 2^-127 here, the hardware convert's reading that every exact-class kernel has, where
+ *   petit_dequant_packed_weights restates the reference's 0.0; byte 255 is no finite scale in either); the
  *   group scale is applied before the MFMA in every form.
  *   S and L (a multiple of 256: the packed scale layout exists for k % 256 == 0) are functions of (n, k, a_type, b_type) alone --
  *   petit_gemm_invariant_geometry; S * L >= k > (S - 1) * L, S <= 16.
@@ -889,7 +891,8 @@ int petit_moe_route_hidden(const void *hidden, const void *weight, const float *
  *   PETIT_ERROR_KERNEL_SHAPE for fp16 activations with MXFP4 weights (below).  m == 0 returns PETIT_OK.
  * petit_gemm_fp4_invariant_host is the CPU twin for HOST pointers (activation none; bias may be NULL): it evaluates the definition with a
  *   sequential fp32 sum per slice in place of the MFMA chain -- the same bits whenever the partial sums are exact, a few ulp of y apart
- *   otherwise.  It documents the format and serves the tests that run without a GPU; it is not a fallback.
+ *   otherwise.  It reads e8m0 byte 0 as the kernels do (2^-127, an fp32 subnormal: its products with a code are exact).  It documents the
+ *   format and serves the tests that run without a GPU; it is not a fallback.
  * Not here: grouped launches (the routed-expert launch: "Batch-invariant MoE launch" below); the native class; fp16 x MXFP4 (out-of-range scale bytes need the hi / lo fallback body,
  *   a second chain and a definition of its own); a one-launch split form (a last-arriver combine was probed and closed);
  *   any change to what PETIT_SOLUTION_AUTO runs.

@@ -127,7 +127,9 @@ inline float e4m3_f32(unsigned b) { // OCP e4m3 (fn): no infinities, 0x7f / 0xff
         v = bits_f32(((e + 120u) << 23) | (m << 20));
     return (b & 0x80u) ? -v : v;
 }
-inline float e8m0_f32(unsigned b) { return bits_f32((b & 0xffu) << 23); } // 2^(b - 127), as the kernels decode it
+// 2^(b - 127), as the kernels decode it (the hardware convert): byte 0 is 2^-127, an fp32 subnormal -- not the 0.0 of `b << 23`, which is what
+// dequant.hip and the oracle restate from the reference --, byte 255 is `b << 23` = inf, whose product with any code or activation ends as NaN
+inline float e8m0_f32(unsigned b) { return bits_f32((b & 0xffu) ? (b & 0xffu) << 23 : 0x00400000u); }
 
 // the weight operand of the definition: fp4 x group scale, exact in the activation type for every (type, format) pair the entry accepts
 inline float weight_value(const uint32_t *pw, const uint8_t *ps, bool mx, unsigned k_total, unsigned n, unsigned kk) {

@@ -187,6 +187,28 @@ def test_host_twin_gives_a_row_the_same_bits_alone_and_in_a_batch(a_type, b_type
     assert torch.equal(_host(a_type, b_type, b, s, moved, bias, 0.0123, n, k).view(torch.int16), torch.roll(full, 2, 0).view(torch.int16))
 
 
+def test_host_twin_reads_e8m0_byte_0_as_the_kernels_do():
+    """e8m0 scale byte 0 is 2^-127 (the hardware convert the kernels dequantise with; `byte << 23` would make it 0.0 and every output 0):
+    every weight +6 under byte 0, one activation of +-2^120 per row -> +-6 * 2^-127 * 2^120 = +-1.5 * 2^-5 in every column; with gs = 2 and
+    a bias of 1: 1 +- 3 * 2^-5.  Byte 255 in one block of one column: that column is NaN in every row, the others keep their bits."""
+    n, k, m = 32, 512, 2
+    q = torch.full((n, k // 2), 0x77, dtype=torch.uint8).view(torch.int32)
+    b = offline.repack_nvfp4_cpu(q, n, k).contiguous()
+    sbyte = np.zeros((n, k // 32), dtype=np.uint8)
+    s = offline.process_mxfp4_scales_cpu(torch.from_numpy(sbyte), n, k).contiguous()
+    a = np.zeros((m, k))
+    a[0, 5], a[1, 300] = 2.0 ** 120, -2.0 ** 120
+    sign = np.array([[1.0], [-1.0]])
+    got = _host(BF16, MX, b, s, a, None, None, n, k)
+    assert np.array_equal(got.double().numpy(), np.broadcast_to(sign * 1.5 * 2.0 ** -5, (m, n)))
+    got = _host(BF16, MX, b, s, a, np.ones(n), 2.0, n, k)
+    assert np.array_equal(got.double().numpy(), np.broadcast_to(1.0 + sign * 3.0 * 2.0 ** -5, (m, n)))
+    sbyte[7, 3] = 255
+    s = offline.process_mxfp4_scales_cpu(torch.from_numpy(sbyte), n, k).contiguous()
+    v = _host(BF16, MX, b, s, a, np.ones(n), 2.0, n, k).double().numpy()
+    assert np.isnan(v[:, 7]).all() and np.array_equal(np.delete(v, 7, axis=1), np.broadcast_to(1.0 + sign * 3.0 * 2.0 ** -5, (m, n - 1)))
+
+
 # --- the operator layers -----------------------------------------------------------------------------------------------------------------
 
 NAMES = ("mul_nvfp4_a16_invariant", "mul_mxfp4_a16_invariant", "invariant_geometry", "invariant_slabs", "invariant_workspace_bytes")

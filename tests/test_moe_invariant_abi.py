@@ -202,6 +202,30 @@ def test_host_twin_equals_the_dense_twin_per_owned_row(a_type, b_type, name):
     assert np.array_equal((out2 == 0x7FC1).all(axis=1), owner < 0) and not (out2[owner >= 0] == 0x7FC1).all(axis=1).any()
 
 
+def test_host_twin_reads_e8m0_byte_0_as_the_kernels_do():
+    """The MoE twin inherits the dense twin's decode: expert 1 of 2 has every weight +6 under e8m0 byte 0 (2^-127, not 0.0), expert 0 -6 under
+    byte 127; the one A row holds 2^120 once.  Expert 0's row is -6 * 2^120, expert 1's rows 6 * 2^-127 * 2^120 * gs[1] = 1.5 * 2^-4, and the
+    grouped row whose A index is out of range is 0."""
+    E, m, n, k = 2, 3, 32, 256
+    q = torch.full((E * n, k // 2), 0xFF, dtype=torch.uint8)
+    q[n:] = 0x77
+    sbyte = np.full((E * n, k // 32), 127, dtype=np.uint8)
+    sbyte[n:] = 0
+    b = offline.repack_nvfp4_cpu(q.view(torch.int32), E * n, k).contiguous()
+    s = offline.process_mxfp4_scales_cpu(torch.from_numpy(sbyte), E * n, k).contiguous()
+    a = torch.zeros(1, k, dtype=torch.bfloat16)
+    a[0, 77] = 2.0 ** 120
+    a_bits = a.view(torch.int16).numpy()
+    gs = torch.tensor([1.0, 2.0])
+    offsets, a_idx = np.array([0, 1, 3], dtype=np.int32), np.array([0, 0, 5], dtype=np.int32)
+    out = np.full((m, n), 0x7FC1, dtype=np.int16)
+    rc = L.petit_gemm_fp4_moe_invariant_host(out.ctypes.data, a_bits.ctypes.data, b.data_ptr(), s.data_ptr(), gs.data_ptr(), None, offsets.ctypes.data,
+                                             E, m, n, k, a_idx.ctypes.data, 1, None, m, BF16, MX)
+    assert rc == OK
+    got = torch.from_numpy(out).view(torch.bfloat16).double().numpy()
+    assert np.array_equal(got, np.repeat(np.array([[-6.0 * 2.0 ** 120], [1.5 * 2.0 ** -4], [0.0]]), n, axis=1))
+
+
 # --- the operator layers -----------------------------------------------------------------------------------------------------------------
 
 NAMES = ("mul_nvfp4_a16_moe_invariant", "mul_mxfp4_a16_moe_invariant", "moe_invariant_form", "moe_invariant_workspace_bytes")

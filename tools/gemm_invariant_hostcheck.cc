@@ -76,8 +76,34 @@ static void run_pair(int a_type, int b_type, unsigned m, unsigned n, unsigned k,
         }
 }
 
+// e8m0 scale byte 0 is 2^-127 (the hardware convert's reading, the kernels'), not 0.0: every weight +6 under byte 0, one activation of
+// 2^120 per row -> 6 * 2^-127 * 2^120 = 1.5 * 2^-5 in every column, times gs 2, plus bias 1; byte 255 is not a number.
+static void run_e8m0_ends() {
+    const unsigned m = 2, n = 32, k = 512; // (two slices of 256)
+    std::vector<uint32_t> pw((size_t)n * k / 8, 0x77777777u);
+    std::vector<uint8_t> ps((size_t)n * k / kMxGroup, 0u);
+    std::vector<uint16_t> a((size_t)m * k, 0u), bias(n, 0x3f80u), c((size_t)m * n, 0x7fc1u);
+    a[5] = 0x7b80u, a[k + 300] = 0xfb80u; // +2^120 at k = 5 of row 0, -2^120 at k = 300 of row 1
+    EXPECT(e8m0_f32(0) == 0x1p-127f && e8m0_f32(1) == 0x1p-126f && e8m0_f32(127) == 1.0f && e8m0_f32(254) == 0x1p127f && std::isinf(e8m0_f32(255)));
+    EXPECT(gemm_host(c.data(), a.data(), pw.data(), ps.data(), nullptr, nullptr, m, n, k, kTypeBf16, kTypeMx) == kRcOk);
+    for (unsigned col = 0; col < n; ++col)
+        EXPECT(c[col] == 0x3d40u && c[n + col] == 0xbd40u); // +-1.5 * 2^-5
+    const float gs = 2.0f;
+    EXPECT(gemm_host(c.data(), a.data(), pw.data(), ps.data(), &gs, bias.data(), m, n, k, kTypeBf16, kTypeMx) == kRcOk);
+    for (unsigned col = 0; col < n; ++col)
+        EXPECT(c[col] == 0x3f8cu && c[n + col] == 0x3f68u); // 1 + 3 * 2^-5 = 1.09375, 1 - 3 * 2^-5 = 0.90625 = 1.8125 / 2
+    ps.at(packed_mxscale_byte_index(k, 7, 3)) = 255u; // column 7 alone: NaN in every row
+    EXPECT(gemm_host(c.data(), a.data(), pw.data(), ps.data(), &gs, bias.data(), m, n, k, kTypeBf16, kTypeMx) == kRcOk);
+    for (unsigned col = 0; col < n; ++col)
+        for (unsigned row = 0; row < m; ++row) {
+            const uint16_t got = c[(size_t)row * n + col];
+            EXPECT(col == 7 ? (got & 0x7fffu) > 0x7f80u : got == (row ? 0x3f68u : 0x3f8cu));
+        }
+}
+
 int main() {
     const int pairs[3][2] = {{kTypeBf16, kTypeNv}, {kTypeBf16, kTypeMx}, {kTypeFp16, kTypeNv}};
+    run_e8m0_ends();
     for (const auto &p : pairs) {
         run_pair(p[0], p[1], 3, 32, 256, 1);
         run_pair(p[0], p[1], 2, 48 - (is_mx(p[1]) ? 16 : 0), 768, 2); // three slices

@@ -8,6 +8,7 @@
 // Every buffer has exactly the bytes the call declares (an index outside them is a heap overflow the sanitizer sees).  The twin runs under
 // well-formed and malformed offsets, with gathers and scatters that go out of range, on poisoned outputs, and is compared row by row with the
 // dense twin on the row's owner (the clamp rule, restated here); then the form switch, the workspace query and every refusal.
+#include <algorithm>
 #include <cstdio>
 #include <cstdlib>
 #include <random>
@@ -85,8 +86,28 @@ static void run_pair(int a_type, int b_type, unsigned E, unsigned m, unsigned n,
                 EXPECT(c[(size_t)r * n + col] == 0x7fc1u); // rows of no expert, and rows nothing names: untouched
 }
 
+// e8m0 scale byte 0 is 2^-127, as in the dense twin: expert 1 of 2 has every weight +6 under byte 0 (expert 0: -6 under byte 127), the one
+// A row holds 2^120 once -> expert 1's rows hold 6 * 2^-127 * 2^120 * gs[1] = 1.5 * 2^-4, expert 0's -6 * 2^120.
+static void run_e8m0_byte0() {
+    const unsigned E = 2, m = 3, n = 32, k = 256;
+    const size_t w_words = (size_t)n * k / 8, s_bytes = (size_t)n * k / kMxGroup;
+    std::vector<uint32_t> pw(E * w_words, 0xffffffffu);
+    std::vector<uint8_t> ps(E * s_bytes, 127u);
+    std::fill(pw.begin() + w_words, pw.end(), 0x77777777u);
+    std::fill(ps.begin() + s_bytes, ps.end(), (uint8_t)0u);
+    std::vector<uint16_t> a(k, 0u), c((size_t)m * n, 0x7fc1u);
+    a[77] = 0x7b80u; // 2^120
+    const std::vector<float> gs = {1.0f, 2.0f};
+    const std::vector<int32_t> off = {0, 1, 3}, a_idx = {0, 0, 5}; // (grouped row 2 reads no row: zeros)
+    EXPECT(moe_gemm_host(c.data(), a.data(), pw.data(), ps.data(), gs.data(), nullptr, off.data(), E, m, n, k, a_idx.data(), 1, nullptr, m,
+                         kTypeBf16, kTypeMx) == kRcOk);
+    for (unsigned col = 0; col < n; ++col)
+        EXPECT(c[col] == 0xfcc0u && c[n + col] == 0x3dc0u && c[2 * n + col] == 0u); // -1.5 * 2^122, 1.5 * 2^-4, 0
+}
+
 int main() {
     const int pairs[3][2] = {{kTypeBf16, kTypeNv}, {kTypeBf16, kTypeMx}, {kTypeFp16, kTypeNv}};
+    run_e8m0_byte0();
     for (const auto &p : pairs) {
         run_pair(p[0], p[1], 3, 9, 32, 256, {0, 4, 4, 9}, 1);          // well formed, an empty expert
         run_pair(p[0], p[1], 4, 11, 32, 768, {2, 7, 3, -5, 40}, 2);    // rows before offsets[0] unowned; descending, negative, beyond m
