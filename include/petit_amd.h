@@ -893,7 +893,7 @@ int petit_moe_route_hidden(const void *hidden, const void *weight, const float *
  *   sequential fp32 sum per slice in place of the MFMA chain -- the same bits whenever the partial sums are exact, a few ulp of y apart
  *   otherwise.  It reads e8m0 byte 0 as the kernels do (2^-127, an fp32 subnormal: its products with a code are exact).  It documents the
  *   format and serves the tests that run without a GPU; it is not a fallback.
- * Not here: grouped launches (the routed-expert launch: "Batch-invariant MoE launch" below); the native class; fp16 x MXFP4 (out-of-range scale bytes need the hi / lo fallback body,
+ * Not here: grouped launches (the routed-expert launch: "Batch-invariant MoE launch" below); the native class in this entry (its dense form has one of its own: "Batch-invariant GEMM on the native class" below); fp16 x MXFP4 (out-of-range scale bytes need the hi / lo fallback body,
  *   a second chain and a definition of its own); a one-launch split form (a last-arriver combine was probed and closed);
  *   any change to what PETIT_SOLUTION_AUTO runs.
  */
@@ -937,7 +937,7 @@ int petit_gemm_fp4_invariant_host(void *c, const void *a, const void *b, const v
  *   more, a NULL global_scales or expert_offsets, an index or offset pointer that is not 4-byte aligned.  m == 0 returns PETIT_OK.
  * petit_gemm_fp4_moe_invariant_host is the CPU twin on HOST pointers (offsets and indices included; activation none; bias [E][n] or NULL):
  *   petit_gemm_fp4_invariant_host per expert under the clamp rule.
- * Not here: the native class; fp16 x MXFP4; the grouped q / k / v launch; a one-launch split form; a persistent-slot form for dead slots.
+ * Not here: the native class (dense calls have "Batch-invariant GEMM on the native class" below; its routed-expert launch does not exist); fp16 x MXFP4; the grouped q / k / v launch; a one-launch split form; a persistent-slot form for dead slots.
  */
 int petit_gemm_moe_invariant_form(unsigned m, unsigned num_experts);
 uint64_t petit_gemm_moe_invariant_workspace_bytes(unsigned num_experts, unsigned m, unsigned n, unsigned k, int a_type, int b_type);
@@ -953,6 +953,65 @@ int petit_gemm_fp4_moe_invariant_host(void *c, const void *a, const void *b, con
                                       const int32_t *expert_offsets, unsigned num_experts, unsigned m, unsigned n, unsigned k,
                                       const int32_t *a_row_index, unsigned a_rows, const int32_t *c_row_index, unsigned c_rows, int a_type,
                                       int b_type);
+
+/*
+ * Batch-invariant GEMM on the native class (no counterpart in the reference): the dense batch-invariant entry for MXFP4 weights on the
+ * block-scaled MFMA -- the accuracy class of petit_gemm_mxfp4_native (activations quantised to MXFP8 / MXFP6 / MXFP4), with the guarantee of
+ * "Batch-invariant GEMM" above: every output element is a pure function of its activation row, the weights, the scales and the bias -- not of m,
+ * not of the row's position in the batch, not of the launch form.  The native default is not: its pick (kernel, wave-level K split, bulk rows in
+ * the class plus a tail in the exact class) moves with m.  Opt-in by calling it; nothing here goes through the picks, the arch tables or the tuner.
+ *   a               a_is_quantized == 0: the 16-bit [m][k] matrix (hints->a_type BF16 or FP16); the call first runs the library's own quantiser
+ *                   (petit_quantize_activations) into the workspace.  Otherwise "petit-qact/1" bytes of act_format for (m, k), as
+ *                   petit_quantize_activations / petit_rmsnorm_quantize write them.  Both paths give the same bits: the quantised bytes of a row
+ *                   are a function of that row alone (per row and per 32-k block; only their ADDRESS in the k-tile-major image depends on m).
+ *   act_format      8 (MXFP8), 6 (MXFP6 e2m3) or 4 (MXFP4).
+ *   b, scales       the packed MXFP4 tensors the other GEMMs read; hints->b_type an MXFP4 type, hints->c_type == hints->a_type (FP16 IS accepted:
+ *                   the instruction takes any E8M0 byte, so the exact entry's reason for refusing fp16 x MXFP4 does not apply).
+ *   global_scale, epilogue (bias, activation), c as in the exact invariant entry; gated calls (c is [m][n/2]) need n % 64 == 0.
+ * Definition, honoured bit for bit whatever m is:
+ *     y[m][n] = ( ... ((p_0 + p_1) + p_2) ... + p_{S-1} ) * (*global_scale) + bias[n]
+ *     c[m][n] = round16(y[m][n])
+ *   S and L are petit_gemm_invariant_geometry(n, k, a_type, PETIT_DTYPE_MXFP4): never functions of m or of the activation format.  p_s is the
+ *   accumulation of slice s of K by ONE chain of v_mfma_scale_f32_32x32x64_f8f6f4 from a zero accumulator: the k-tiles of 128 ascending, two
+ *   instructions per k-tile -- k 0..63 of the tile (P1), then k 64..127 (P2).  The weight operand is the pair of neighbouring n-tiles (32 rows)
+ *   as stored -- raw E2M1 nibbles, 32 consecutive k per lane -- with the E8M0 byte of the lane's block as its scale; the activation operand is the
+ *   row's "petit-qact/1" bytes of that k-tile and their four E8M0 bytes.  (The 16x16x128 shape aligns and truncates a different number of block
+ *   sums per instruction and does not give the same bits: both forms use 32x32x64.)  Fold and epilogue are the exact invariant entry's: fp32
+ *   additions in ascending order, no contraction; the plain call then multiplies and adds with a rounding each, the gated call
+ *   (PETIT_ACTIVATION_SILU_MUL / _SWIGLU_OAI) forms fma(fold, gs, bias) -- one rounding -- in the epilogue function every gated kernel calls.
+ *   Pinned for weight scale bytes 1..254; bytes 0 and 255 are whatever the instruction does, as for the rest of the class.
+ *   Accuracy, given the quantised activations: the bound of "Native-FP4 kernels" above.  It holds for any K split, and its 16 * T term is sixteen
+ *   fp32 additions of at most 2^-24 * T each: the S - 1 <= 15 slab additions here are covered by it as they stand, and the global-scale multiply
+ *   is the sixteenth; a bias adds one more rounding, 2^-24 * (gs * T + |bias|).  Nothing is fitted.
+ * Two forms produce those bits, chosen by m alone.  m <= 64 (the split form): pairs of n-tiles x S x m-tiles of 32 waves store their fp32 tiles to
+ *   S slabs [m][n] with plain vector stores -- no atomics, tickets or fences --, and a second launch adds the slabs in ascending order and applies
+ *   scale, bias and activation.  Above (the whole form): a workgroup stages its activation tile of every k-tile through LDS, a wave walks all S
+ *   slices, accumulates each from zero and adds it to a running total, and applies the epilogue itself; no slab workspace.  The switch is a
+ *   constant of the library, not a setting (profiles/native_invariant.md).  petit_gemm_native_invariant_slabs: S or 1, the form m gets.
+ * Workspace: petit_gemm_native_invariant_workspace_bytes = the quantised bytes (petit_quantized_activation_bytes; 16-bit input only) + the slabs
+ *   (slabs * m * n * 4; split form only), each part rounded up to a multiple of 256, in this order; 0 for a call that would be refused and for
+ *   m == 0.  Caller-owned device memory, 256-byte aligned.  No host sync, no allocation, graph-capturable.
+ * Errors, all before any launch: PETIT_ERROR_BAD_ARGUMENT for null hints, an a_type that is not BF16 / FP16, a c_type that differs, a b_type that
+ *   is not MXFP4, an act_format outside {8, 6, 4}, an activation value that does not exist, a non-zero `reserved`; PETIT_ERROR_PROBLEM_SHAPE for
+ *   n % 32 != 0, k % 256 != 0, n or k zero, m >= 2^20, a gated activation with n % 64 != 0, null required pointers, c / a / b / scales not
+ *   16-byte aligned, a bias not 8-byte aligned, a null or misaligned workspace when the byte query is not zero; PETIT_ERROR_KERNEL_SHAPE for a
+ *   16-bit input of more than 65535 rows (the quantiser's limit: pass quantised bytes).  m == 0 returns PETIT_OK.
+ * petit_quantize_activations_host is petit_quantize_activations on HOST pointers, bit for bit (the quantiser of petit_rmsnorm_quantize_host).
+ * petit_gemm_native_invariant_host is the CPU twin on HOST "petit-qact/1" bytes (activation none; global_scale and bias may be NULL): per slice a
+ *   sequential fp32 sum of a_q * w, k ascending, then the stated fold and epilogue -- the device's bits whenever every partial sum is exact.  The
+ *   activation bytes are decoded with the formats' own tables, E8M0 as the exact twin reads it.  It documents the format and serves the tests
+ *   that run without a GPU; it is not a fallback.
+ * Not here: NVFP4 images on this entry; the routed-expert launch; a quantising (out_format) epilogue; the layer switches
+ *   (fp4_moe_native(..., invariant=...)); any change to what the sentinels run.
+ */
+unsigned petit_gemm_native_invariant_slabs(unsigned m, unsigned n, unsigned k, int a_type);
+uint64_t petit_gemm_native_invariant_workspace_bytes(unsigned m, unsigned n, unsigned k, int a_type, int act_format, int a_is_quantized);
+int petit_gemm_mxfp4_native_invariant(void *c, const void *a, const void *b, const void *scales, const float *global_scale, unsigned m, unsigned n,
+                                      unsigned k, const petit_solution_hints *hints, int act_format /* 8 | 6 | 4 */, int a_is_quantized,
+                                      const petit_epilogue *epilogue, void *workspace, void *stream);
+int petit_quantize_activations_host(void *qa, const void *a, unsigned m, unsigned k, int a_type, int format);
+int petit_gemm_native_invariant_host(void *c, const void *qa, const void *b, const void *scales, const float *global_scale, const void *bias,
+                                     unsigned m, unsigned n, unsigned k, int a_type, int act_format);
 
 /*
  * Native-class MoE launch (no counterpart in the reference): the routed-expert launch on the block-scaled MFMA, the accuracy class of

@@ -1,0 +1,6 @@
+// gemm_native_invariant_f16.hip -- the native-class batch-invariant GEMM's kernels (gemm_native_invariant.hpp) for fp16 outputs and biases.
+#include "gemm_native_invariant.hpp"
+
+namespace petit_amd {
+template void native_invariant_launch<Fp16>(const NativeInvariantArgs &, int, bool, hipStream_t);
+} // namespace petit_amd

@@ -712,6 +712,31 @@ int rmsnorm_inv_host(float *inv, const void *x, const void *res, float eps, unsi
     return kOk;
 }
 
+// petit_quantize_activations on HOST pointers: quantize_row_host on every row of a 16-bit [m][k] matrix (what the twins above write after the norm).
+// It refuses what petit_quantize_activations refuses, and an unknown format.
+int quantize_activations_host(void *qa, const void *a, unsigned m, unsigned k, int a_type, int format) {
+    if (m == 0 || k == 0)
+        return kOk;
+    if (!qa || !a || (((uintptr_t)qa | (uintptr_t)a) & 15) || (format != 8 && format != 6 && format != 4))
+        return kErrBadArgument;
+    if (k % 256 != 0)
+        return kErrProblemShape;
+    if (a_type != kDataTypeBf16 && a_type != kDataTypeFp16)
+        return kErrKernelShape;
+    const bool bf16 = a_type == kDataTypeBf16;
+    for (unsigned row = 0; row < m; ++row) {
+        const uint16_t *const y = (const uint16_t *)a + (size_t)row * k;
+        unsigned char *const ws = (unsigned char *)qa;
+        if (format == 8)
+            bf16 ? quantize_row_host<true, 8>(ws, y, m, k, row) : quantize_row_host<false, 8>(ws, y, m, k, row);
+        else if (format == 6)
+            bf16 ? quantize_row_host<true, 6>(ws, y, m, k, row) : quantize_row_host<false, 6>(ws, y, m, k, row);
+        else
+            bf16 ? quantize_row_host<true, 4>(ws, y, m, k, row) : quantize_row_host<false, 4>(ws, y, m, k, row);
+    }
+    return kOk;
+}
+
 // --- petit_moe_combine_rmsnorm ----------------------------------------------------------------------------------------------------------------
 
 namespace {

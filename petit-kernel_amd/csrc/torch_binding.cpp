@@ -292,6 +292,48 @@ at::Tensor mul_a16_invariant(bool mx, PETIT_INVARIANT_ARGS) {
 at::Tensor mul_nvfp4_a16_invariant(PETIT_INVARIANT_ARGS) { return mul_a16_invariant(false, A, B, s, global_scale, size_m, size_n, size_k, bias, activation); }
 at::Tensor mul_mxfp4_a16_invariant(PETIT_INVARIANT_ARGS) { return mul_a16_invariant(true, A, B, s, global_scale, size_m, size_n, size_k, bias, activation); }
 
+// the batch-invariant GEMM on the native class (petit_gemm_mxfp4_native_invariant).  A is the 16-bit matrix, or (quantized) the "petit-qact/1"
+// bytes of act_format -- then bf16 names the 16-bit type of c and the bias.  The argument checks and their texts are stated once, in
+// petit_kernel/ops.py (_check_native_invariant), which petit_kernel/compiled.py runs in front of this op; what is checked here is what keeps a
+// direct torch.ops call inside its tensors.
+#define PETIT_NATIVE_INVARIANT_ARGS                                                                                                            \
+    const at::Tensor &A, const at::Tensor &B, const at::Tensor &s, const std::optional<at::Tensor> &global_scale, int64_t size_m, int64_t size_n, \
+        int64_t size_k, int64_t act_format, bool quantized, bool bf16, const std::optional<at::Tensor> &bias, int64_t activation
+at::Tensor mul_mxfp4_native_invariant(PETIT_NATIVE_INVARIANT_ARGS) {
+    const at::ScalarType st = bf16 ? at::kBFloat16 : at::kHalf;
+    TORCH_CHECK(act_format == 8 || act_format == 6 || act_format == 4, "act_format must be 8, 6 or 4");
+    TORCH_CHECK(size_m >= 0 && size_n > 0 && size_k > 0 && size_k % 256 == 0 && A.is_cuda() && B.is_cuda() && s.is_cuda() && A.is_contiguous() &&
+                    B.is_contiguous() && s.is_contiguous() && B.device() == A.device() && s.device() == A.device() &&
+                    (quantized ? A.scalar_type() == at::kByte && A.numel() == size_m * (size_k / 8 * act_format) + size_m * (size_k / 32)
+                               : A.scalar_type() == st && A.numel() == size_m * size_k) &&
+                    B.numel() * B.element_size() == size_n * size_k / 2 && s.numel() * s.element_size() == size_n * size_k / 32 &&
+                    (!global_scale || (global_scale->is_cuda() && global_scale->device() == A.device() &&
+                                       global_scale->scalar_type() == at::kFloat && global_scale->numel() >= 1)),
+                "A [size_m, size_k] (or its quantised bytes), packed B and s of [size_n, size_k] weights must be contiguous GPU tensors on one "
+                "device, global_scale a float32 tensor on it");
+    TORCH_CHECK(activation >= 0 && activation <= 2 && (!activation || size_n % 64 == 0), "activation must be 0, 1 or 2; gated forms need size_n % 64 == 0");
+    check_bias(bias, A, st, size_n, "bias must be a contiguous [size_n] tensor of A's dtype on A's device");
+    const c10::hip::HIPGuardMasqueradingAsCUDA guard(A.device());
+    at::Tensor c = at::empty({size_m, activation ? size_n / 2 : size_n}, A.options().dtype(st));
+    const int a_type = a_type_of(st);
+    const petit_solution_hints hints{a_type, kCxxMxFp4, a_type, 0};
+    const petit_epilogue epi{bias.has_value() ? bias->data_ptr() : nullptr, (int32_t)activation, 0};
+    const uint64_t ws_bytes = petit_gemm_native_invariant_workspace_bytes((unsigned)size_m, (unsigned)size_n, (unsigned)size_k, a_type,
+                                                                          (int)act_format, quantized ? 1 : 0);
+    at::Tensor ws;
+    if (ws_bytes)
+        ws = at::empty({(int64_t)ws_bytes}, A.options().dtype(at::kByte));
+    const int rc = petit_gemm_mxfp4_native_invariant(c.data_ptr(), A.data_ptr(), B.data_ptr(), s.data_ptr(),
+                                                     global_scale ? (const float *)global_scale->data_ptr() : nullptr, (unsigned)size_m,
+                                                     (unsigned)size_n, (unsigned)size_k, &hints, (int)act_format, quantized ? 1 : 0,
+                                                     (bias.has_value() || activation) ? &epi : nullptr, ws_bytes ? ws.data_ptr() : nullptr,
+                                                     stream_of(A));
+    TORCH_CHECK(rc != PETIT_ERROR_PROBLEM_SHAPE, "Incompatible problem shape (m=", size_m, ", n=", size_n, ", k=", size_k, ")");
+    TORCH_CHECK(rc != PETIT_ERROR_KERNEL_SHAPE, "No kernel implementation for solution_id=native-invariant.");
+    TORCH_CHECK(rc == PETIT_OK, "mul_mxfp4_native_invariant: ", petit_error_string(rc));
+    return c;
+}
+
 // routed-expert (MoE) launch: all experts in one call (include/petit_amd.h); the same checks and texts as petit_kernel/ops.py _mul_moe
 at::Tensor mul_a16_moe(bool mx, const at::Tensor &A, const at::Tensor &B, const at::Tensor &s, const at::Tensor &global_scales,
                        const at::Tensor &expert_offsets, int64_t size_m, int64_t size_n, int64_t size_k, int64_t num_experts, int64_t solution_id,
@@ -850,6 +892,9 @@ at::Tensor mul_a16_invariant_meta(PETIT_INVARIANT_ARGS) {
     check_a16(A);
     return at::empty({size_m, activation ? size_n / 2 : size_n}, A.options());
 }
+at::Tensor mul_mxfp4_native_invariant_meta(PETIT_NATIVE_INVARIANT_ARGS) {
+    return at::empty({size_m, activation ? size_n / 2 : size_n}, A.options().dtype(bf16 ? at::kBFloat16 : at::kHalf));
+}
 at::Tensor mul_a16_moe_meta(const at::Tensor &A, const at::Tensor &, const at::Tensor &, const at::Tensor &, const at::Tensor &, int64_t m, int64_t n,
                             int64_t, int64_t, int64_t, const std::optional<at::Tensor> &, int64_t activation) {
     check_a16(A);
@@ -987,6 +1032,8 @@ TORCH_LIBRARY(petit_kernel, m) {
 #define PETIT_MOE_INVARIANT_SCHEMA                                                                                                        \
     "Tensor A, Tensor B, Tensor s, Tensor global_scales, Tensor expert_offsets, int size_m, int size_n, int size_k, int num_experts, " \
     "Tensor? a_row_index=None, Tensor? c_row_index=None, int c_rows=-1, Tensor? bias=None, int activation=0"
+    m.def("mul_mxfp4_native_invariant(Tensor A, Tensor B, Tensor s, Tensor? global_scale, int size_m, int size_n, int size_k, int act_format, "
+          "bool quantized, bool bf16, Tensor? bias=None, int activation=0) -> Tensor");
     m.def("mul_nvfp4_a16_moe_invariant(" PETIT_MOE_INVARIANT_SCHEMA ") -> Tensor");
     m.def("mul_mxfp4_a16_moe_invariant(" PETIT_MOE_INVARIANT_SCHEMA ") -> Tensor");
     m.def("mul_nvfp4_a16_moe_invariant_out(Tensor(a!) out, " PETIT_MOE_INVARIANT_SCHEMA ") -> ()");
@@ -1005,6 +1052,7 @@ TORCH_LIBRARY(petit_kernel, m) {
     m.impl("mul_mxfp4_a16_f16range", &mul_mxfp4_a16);          \
     m.impl("mul_nvfp4_a16_invariant", &mul_nvfp4_a16_invariant); \
     m.impl("mul_mxfp4_a16_invariant", &mul_mxfp4_a16_invariant); \
+    m.impl("mul_mxfp4_native_invariant", &mul_mxfp4_native_invariant); \
     m.impl("mul_nvfp4_a16_moe", &mul_nvfp4_a16_moe);            \
     m.impl("mul_mxfp4_a16_moe", &mul_mxfp4_a16_moe);            \
     m.impl("mul_nvfp4_a16_moe_indexed", &mul_nvfp4_a16_moe_indexed); \
@@ -1040,6 +1088,7 @@ TORCH_LIBRARY_IMPL(petit_kernel, Meta, m) {
     m.impl("mul_mxfp4_a16_f16range", &mul_a16_meta);
     m.impl("mul_nvfp4_a16_invariant", &mul_a16_invariant_meta);
     m.impl("mul_mxfp4_a16_invariant", &mul_a16_invariant_meta);
+    m.impl("mul_mxfp4_native_invariant", &mul_mxfp4_native_invariant_meta);
     m.impl("mul_nvfp4_a16_moe", &mul_a16_moe_meta);
     m.impl("mul_mxfp4_a16_moe", &mul_a16_moe_meta);
     m.impl("mul_nvfp4_a16_moe_indexed", &mul_a16_moe_indexed_meta);

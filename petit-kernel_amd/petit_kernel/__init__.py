@@ -134,6 +134,25 @@ def invariant_workspace_bytes(size_m: int, size_n: int, size_k: int, dtype: torc
     return ops.invariant_workspace_bytes(size_m, size_n, size_k, dtype, kind)
 
 
+def mul_mxfp4_native_invariant(a, b: torch.Tensor, s: torch.Tensor, global_scale: torch.Tensor, size_m: int, size_n: int, size_k: int,
+                               fmt: str = "mxfp8", bias: torch.Tensor = None, activation: str = None) -> torch.Tensor:
+    # the native class (MXFP4 weights on the block-scaled MFMA, activations quantised to fmt) by its batch-invariant entry (include/petit_amd.h
+    # "Batch-invariant GEMM on the native class"): the same bits for a row alone, in any batch and at any position.  a: a 16-bit tensor
+    # (quantised by the call) or QuantizedActivations of the same fmt (quantize_activations / rmsnorm_quantize) -- the same bits either way.
+    return _impl.mul_mxfp4_native_invariant(a, b, s, global_scale, size_m, size_n, size_k, fmt, bias, activation)
+
+
+def native_invariant_slabs(size_m: int, size_n: int, size_k: int, dtype: torch.dtype = torch.bfloat16) -> int:
+    # S when size_m rows run in the split form (two launches, slabs in scratch), 1 in the whole form
+    return ops.native_invariant_slabs(size_m, size_n, size_k, dtype)
+
+
+def native_invariant_workspace_bytes(size_m: int, size_n: int, size_k: int, dtype: torch.dtype = torch.bfloat16, fmt: str = "mxfp8",
+                                     quantized: bool = False) -> int:
+    # bytes of scratch the call allocates per call: the quantised bytes of a 16-bit input plus the split form's slabs
+    return ops.native_invariant_workspace_bytes(size_m, size_n, size_k, dtype, fmt, quantized)
+
+
 def mul_nvfp4_a16_moe_invariant(a: torch.Tensor, b: torch.Tensor, s: torch.Tensor, global_scales: torch.Tensor, expert_offsets: torch.Tensor,
                                 size_m: int, size_n: int, size_k: int, num_experts: int, a_row_index: torch.Tensor = None,
                                 c_row_index: torch.Tensor = None, c_rows: int = None, bias: torch.Tensor = None, activation: str = None,
@@ -364,6 +383,9 @@ __all__ = [
     "invariant_geometry",
     "invariant_slabs",
     "invariant_workspace_bytes",
+    "mul_mxfp4_native_invariant",
+    "native_invariant_slabs",
+    "native_invariant_workspace_bytes",
     "mul_nvfp4_a16_moe_invariant",
     "mul_mxfp4_a16_moe_invariant",
     "moe_invariant_form",

@@ -19,6 +19,7 @@ from .ops import _check_invariant, _check_route_hidden, _check_router, _combine_
 from .ops import _check_moe_invariant
 from .ops import invariant_geometry, invariant_slabs, invariant_workspace_bytes  # (queries: plain C calls, no op behind them)
 from .ops import moe_invariant_form, moe_invariant_workspace_bytes
+from .ops import _QFORMATS, _check_native_invariant, native_invariant_slabs, native_invariant_workspace_bytes
 
 LIB_PATH = Path(_lib.LIB_PATH).parent / "libpetit_torch.so"
 _loaded = False
@@ -102,6 +103,12 @@ def mul_nvfp4_a16_invariant(A, B, s, global_scale, size_m, size_n, size_k, bias=
 def mul_mxfp4_a16_invariant(A, B, s, global_scale, size_m, size_n, size_k, bias=None, activation=None):
     act = _check_invariant("mx", A, B, s, global_scale, size_m, size_n, size_k, bias, activation)
     return torch.ops.petit_kernel.mul_mxfp4_a16_invariant(A, B, s, global_scale, int(size_m), int(size_n), int(size_k), bias, act)
+
+
+def mul_mxfp4_native_invariant(A, B, s, global_scale, size_m, size_n, size_k, fmt="mxfp8", bias=None, activation=None):
+    a, dtype, quantized, act = _check_native_invariant(A, B, s, global_scale, size_m, size_n, size_k, fmt, bias, activation)
+    return torch.ops.petit_kernel.mul_mxfp4_native_invariant(a, B, s, global_scale, int(size_m), int(size_n), int(size_k), _QFORMATS[fmt],
+                                                             bool(quantized), dtype == torch.bfloat16, bias, act)
 
 
 def mul_nvfp4_a16_moe(A, B, s, global_scales, expert_offsets, size_m, size_n, size_k, num_experts, solution_id=-1, bias=None, activation=None):

@@ -646,6 +646,79 @@ def _activation_operand(A, size_m: int, size_k: int):
     return A, A.dtype, 0
 
 
+# --- the batch-invariant GEMM on the native class (include/petit_amd.h "Batch-invariant GEMM on the native class") -------------------------
+
+def _check_native_invariant(A, B, s, global_scale, size_m, size_n, size_k, fmt, bias, activation):
+    """The argument checks of mul_mxfp4_native_invariant, stated here for both operator layers -> (activation tensor, 16-bit dtype,
+    a_is_quantized, activation code).  Value checks come first and device checks last, so that the texts can be read without a GPU."""
+    name = "mul_mxfp4_native_invariant"
+    _check(fmt in _QFORMATS, "fmt must be 'mxfp8', 'mxfp6' or 'mxfp4'")
+    quantized = isinstance(A, QuantizedActivations)
+    dtype = A.dtype
+    _check(dtype in (torch.bfloat16, torch.float16), "A must be bfloat16 or float16 (or QuantizedActivations of such a tensor).")
+    size_m, size_n, size_k = int(size_m), int(size_n), int(size_k)
+    _check(size_n > 0 and size_n % 32 == 0 and size_k > 0 and size_k % 256 == 0 and 0 <= size_m < 1 << 20,
+           f"Incompatible problem shape (m={size_m}, n={size_n}, k={size_k}): {name} needs n % 32 == 0, k % 256 == 0, m < 2^20")
+    _check(activation in _ACTIVATIONS, _ACTIVATION_RULE)
+    act = _ACTIVATIONS[activation]
+    _check(not act or size_n % 64 == 0, f"{activation} needs size_n % 64 == 0 here (gate / up halves of whole tile pairs), got {size_n}")
+    if quantized:
+        _check(A.fmt == fmt, f"quantised activations are {A.fmt}, the call says fmt={fmt!r}")
+        _check(A.m == size_m and A.k == size_k, f"quantised activations are [{A.m}, {A.k}], the call says [{size_m}, {size_k}]")
+        a = A.data
+        _check(a.dtype == torch.uint8 and a.is_contiguous() and a.numel() == size_m * (size_k // 8 * _QFORMATS[fmt]) + size_m * (size_k // 32),
+               "quantised activations do not hold the bytes of their [m, k] and format")
+    else:
+        a = A
+        _check(size_m <= 65535, f"{name}: a 16-bit A of more than 65535 rows must be quantised first (quantize_activations in pieces)")
+        _check(a.is_contiguous() and a.numel() == size_m * size_k, "A must be a contiguous [size_m, size_k] tensor")
+    _check(B.is_contiguous() and B.numel() * B.element_size() == size_n * size_k // 2, "B does not hold size_n * size_k packed 4-bit weights")
+    _check(s.is_contiguous() and s.numel() * s.element_size() == size_n * size_k // 32, "s does not hold size_n * size_k / 32 scales")
+    if global_scale is not None:
+        _check(global_scale.dtype == torch.float32 and global_scale.numel() >= 1, "global_scale must be float32")
+    if bias is not None:
+        _check(bias.dtype == dtype and bias.is_contiguous() and bias.numel() == size_n and bias.device == a.device,
+               "bias must be a contiguous [size_n] tensor of A's dtype on A's device")
+    _check(a.is_cuda and B.is_cuda and s.is_cuda and (global_scale is None or global_scale.is_cuda), "all tensors must be on GPU")
+    _check(B.device == a.device and s.device == a.device and (global_scale is None or global_scale.device == a.device),
+           "all tensors must be on A's device")
+    return a, dtype, int(quantized), act
+
+
+def native_invariant_slabs(size_m: int, size_n: int, size_k: int, dtype: torch.dtype = torch.bfloat16) -> int:
+    """The slab count of the form m rows get (petit_gemm_native_invariant_slabs): S in the split form (m <= 64), 1 in the whole form."""
+    return int(_lib.lib.petit_gemm_native_invariant_slabs(int(size_m), int(size_n), int(size_k), _a_type(dtype)))
+
+
+def native_invariant_workspace_bytes(size_m: int, size_n: int, size_k: int, dtype: torch.dtype = torch.bfloat16, fmt: str = "mxfp8",
+                                     quantized: bool = False) -> int:
+    """Bytes of scratch mul_mxfp4_native_invariant uses (petit_gemm_native_invariant_workspace_bytes): the quantised bytes of a 16-bit A plus
+    the split form's slabs, each rounded up to 256; 0 for a call that would be refused."""
+    _check(fmt in _QFORMATS, "fmt must be 'mxfp8', 'mxfp6' or 'mxfp4'")
+    return int(_lib.lib.petit_gemm_native_invariant_workspace_bytes(int(size_m), int(size_n), int(size_k), _a_type(dtype), _QFORMATS[fmt],
+                                                                    int(bool(quantized))))
+
+
+def mul_mxfp4_native_invariant(A, B, s, global_scale, size_m, size_n, size_k, fmt="mxfp8", bias=None, activation=None) -> torch.Tensor:
+    """The native class's GEMM by the batch-invariant entry (petit_gemm_mxfp4_native_invariant, include/petit_amd.h "Batch-invariant GEMM on
+    the native class"): MXFP4 weights against activations quantised to `fmt`, a row's result independent of size_m, of the row's position and
+    of the launch form.  A: a 16-bit [size_m, size_k] tensor (quantised by the call) or QuantizedActivations of the same fmt -- the same bits
+    either way.  Opt-in; no solution_id."""
+    a, dtype, quantized, act = _check_native_invariant(A, B, s, global_scale, size_m, size_n, size_k, fmt, bias, activation)
+    size_m, size_n, size_k = int(size_m), int(size_n), int(size_k)
+    c = torch.empty((size_m, size_n // 2 if act else size_n), dtype=dtype, device=a.device)
+    hints = _hints("mx", dtype)
+    epi = _epilogue(bias, act, a.device, dtype, size_n, "bias must be a contiguous [size_n] tensor of A's dtype on A's device")
+    ws = _scratch(int(_lib.lib.petit_gemm_native_invariant_workspace_bytes(size_m, size_n, size_k, hints.a_type, _QFORMATS[fmt], quantized)),
+                  a.device)
+    with torch.cuda.device(a.device):
+        err = _lib.lib.petit_gemm_mxfp4_native_invariant(_ptr(c), _ptr(a), _ptr(B), _ptr(s), _opt_ptr(global_scale), size_m, size_n, size_k,
+                                                         C.byref(hints), _QFORMATS[fmt], quantized, epi, _opt_ptr(ws), _stream(a))
+    if err:
+        _raise_gemm(err, "mul_mxfp4_native_invariant", "native-invariant", f"m={size_m}, n={size_n}, k={size_k}")
+    return c
+
+
 def _native_output(rows: int, size_m: int, n_out: int, out_quantized, dtype, dev):
     """(the tensor the call writes, what the caller returns): 16-bit [rows, n_out], or with out_quantized the bytes of the quantised
     [size_m, n_out] rows and the QuantizedActivations around them."""
