@@ -6,6 +6,7 @@ gate_up_proj, a bias on gate_up and on down, hidden = intermediate = 2880), then
 
     experts = petit_kernel.prepare_gptoss_experts(...)      # load time: de-interleave, pad 2880 -> 3072, repack
     out = experts.forward(x, topk_weights, topk_ids, path="fused" | "native")
+    out = experts.forward(x, topk_weights, topk_ids, path="native", invariant=True)   # batch-invariant: the same bits for a token in any batch
 
 and the maximum error of both paths against a float64 statement of the block (dequantised weights, clamped SwiGLU, router weights on
 down + bias).  The router (top-k, then softmax over the k) is plain torch for the reference; `experts.forward_routed(x, logits)` does it on
@@ -83,6 +84,13 @@ def main():
         hidden = experts.forward_hidden(x.cuda(), router_w, router_b, topk=topk, path=path)
         same = experts.forward_routed(x.cuda(), petit_kernel.moe_router_logits(x.cuda(), router_w, router_b), topk=topk, path=path)
         print(f"{path:6s}: forward_hidden equals forward_routed on moe_router_logits: {torch.equal(hidden.view(torch.int16), same.view(torch.int16))}")
+
+        # batch-invariant: a token's output row has the same bits alone and inside the batch (fp4_moe_native / fp4_moe_fused, invariant=True)
+        inv = experts.forward(x.cuda(), tw.cuda(), ids.int().cuda(), path=path, invariant=True)
+        one = experts.forward(x[3:4].cuda(), tw[3:4].cuda(), ids[3:4].int().cuda(), path=path, invariant=True)
+        err = (inv.double().cpu() - ref).abs()
+        print(f"{path:6s}: forward(..., path={path!r}, invariant=True): token 3 alone == token 3 in the batch: "
+              f"{torch.equal(one[0].view(torch.int16), inv[3].view(torch.int16))}, max |err| {err.max().item():.4g}")
 
 
 if __name__ == "__main__":

@@ -893,7 +893,7 @@ int petit_moe_route_hidden(const void *hidden, const void *weight, const float *
  *   sequential fp32 sum per slice in place of the MFMA chain -- the same bits whenever the partial sums are exact, a few ulp of y apart
  *   otherwise.  It reads e8m0 byte 0 as the kernels do (2^-127, an fp32 subnormal: its products with a code are exact).  It documents the
  *   format and serves the tests that run without a GPU; it is not a fallback.
- * Not here: grouped launches (the routed-expert launch: "Batch-invariant MoE launch" below); the native class in this entry (its dense form has one of its own: "Batch-invariant GEMM on the native class" below); fp16 x MXFP4 (out-of-range scale bytes need the hi / lo fallback body,
+ * Not here: grouped launches (the routed-expert launch: "Batch-invariant MoE launch" below); the native class in this entry (it has entries of its own: "Batch-invariant GEMM on the native class" and "Batch-invariant MoE launch on the native class" below); fp16 x MXFP4 (out-of-range scale bytes need the hi / lo fallback body,
  *   a second chain and a definition of its own); a one-launch split form (a last-arriver combine was probed and closed);
  *   any change to what PETIT_SOLUTION_AUTO runs.
  */
@@ -937,7 +937,7 @@ int petit_gemm_fp4_invariant_host(void *c, const void *a, const void *b, const v
  *   more, a NULL global_scales or expert_offsets, an index or offset pointer that is not 4-byte aligned.  m == 0 returns PETIT_OK.
  * petit_gemm_fp4_moe_invariant_host is the CPU twin on HOST pointers (offsets and indices included; activation none; bias [E][n] or NULL):
  *   petit_gemm_fp4_invariant_host per expert under the clamp rule.
- * Not here: the native class (dense calls have "Batch-invariant GEMM on the native class" below; its routed-expert launch does not exist); fp16 x MXFP4; the grouped q / k / v launch; a one-launch split form; a persistent-slot form for dead slots.
+ * Not here: the native class (it has entries of its own below: "Batch-invariant GEMM on the native class" and its routed-expert launch, "Batch-invariant MoE launch on the native class", which also takes fp16 x MXFP4); fp16 x MXFP4; the grouped q / k / v launch; a one-launch split form; a persistent-slot form for dead slots.
  */
 int petit_gemm_moe_invariant_form(unsigned m, unsigned num_experts);
 uint64_t petit_gemm_moe_invariant_workspace_bytes(unsigned num_experts, unsigned m, unsigned n, unsigned k, int a_type, int b_type);
@@ -1001,8 +1001,8 @@ int petit_gemm_fp4_moe_invariant_host(void *c, const void *a, const void *b, con
  *   sequential fp32 sum of a_q * w, k ascending, then the stated fold and epilogue -- the device's bits whenever every partial sum is exact.  The
  *   activation bytes are decoded with the formats' own tables, E8M0 as the exact twin reads it.  It documents the format and serves the tests
  *   that run without a GPU; it is not a fallback.
- * Not here: NVFP4 images on this entry; the routed-expert launch; a quantising (out_format) epilogue; the layer switches
- *   (fp4_moe_native(..., invariant=...)); any change to what the sentinels run.
+ * Not here: NVFP4 images on this entry; grouped launches (the routed-expert launch: "Batch-invariant MoE launch on the native class" below,
+ *   which fp4_moe_native(..., invariant=True) runs); a quantising (out_format) epilogue; any change to what the sentinels run.
  */
 unsigned petit_gemm_native_invariant_slabs(unsigned m, unsigned n, unsigned k, int a_type);
 uint64_t petit_gemm_native_invariant_workspace_bytes(unsigned m, unsigned n, unsigned k, int a_type, int act_format, int a_is_quantized);
@@ -1012,6 +1012,63 @@ int petit_gemm_mxfp4_native_invariant(void *c, const void *a, const void *b, con
 int petit_quantize_activations_host(void *qa, const void *a, unsigned m, unsigned k, int a_type, int format);
 int petit_gemm_native_invariant_host(void *c, const void *qa, const void *b, const void *scales, const float *global_scale, const void *bias,
                                      unsigned m, unsigned n, unsigned k, int a_type, int act_format);
+
+/*
+ * Batch-invariant MoE launch on the native class (no counterpart in the reference): the routed-expert launch of "Batch-invariant GEMM on the
+ * native class" above -- MXFP4 experts on the block-scaled MFMA, activations quantised to MXFP8 / MXFP6 / MXFP4.  Arguments as
+ * petit_gemm_mxfp4_fp16_moe_invariant plus act_format and a_is_quantized: grouped row r belongs to expert e under the clamp rule of the
+ * routed-expert launch (every offset clamped into [its predecessor, m], a running maximum; rows of no expert are left untouched) and is written
+ * to row c_row_index[r] of c [c_rows][n_out] (a NULL index is the identity).
+ *   a               a_is_quantized == 0: the 16-bit [a_rows][k] matrix (hints->a_type BF16 or FP16); grouped row r is its row a_row_index[r] (NULL:
+ *                   r).  The call first runs the gathering quantiser (petit_quantize_activations_rows' launch) into the workspace; an index
+ *                   outside [0, a_rows) quantises a zero row.  Otherwise "petit-qact/1" bytes of (m, k, act_format) for the m GROUPED rows, as
+ *                   petit_quantize_activations_rows writes them; a_row_index must be NULL and a_rows is not read.  Both give the same bits.
+ *   b, scales       the experts' packed MXFP4 tensors back to back, as the other MoE launches read them; hints->b_type an MXFP4 type,
+ *                   hints->c_type == hints->a_type; FP16 and BF16 are both accepted.
+ *   global_scales [E], epilogue (bias [E][n], activation), c as in the exact MoE invariant entry; gated calls (c is [c_rows][n/2]) need n % 64 == 0.
+ * Definition: the row written for grouped row r of expert e equals, bit for bit, row 0 of
+ *     petit_gemm_mxfp4_native_invariant(m = 1, a = that row, b / scales = expert e's packed tensors, global_scale = &global_scales[e],
+ *                                       bias = bias + e * n, the same activation, the same act_format)
+ *   so S and L are petit_gemm_invariant_geometry(n, k, a_type, PETIT_DTYPE_MXFP4) -- never functions of m, num_experts or the routing --, the
+ *   arithmetic is the dense native entry's (one chain of v_mfma_scale_f32_32x32x64_f8f6f4 per slice from zero, k-tiles of 128 ascending, P1 then
+ *   P2, slices added ascending in fp32, no contraction, the same epilogue functions), and the gated epilogues pair gate pair t with up pair
+ *   t + ntiles / 4 of the same expert.  With a token's slot rows combined by petit_moe_combine (slot order, fp32, one rounding), a token's
+ *   layer output is a pure function of its hidden row and the weights.  A C index outside [0, c_rows) stores nothing; malformed offsets can only
+ *   leave rows unwritten.  An expert without rows is never read.  The host never reads the offsets: no sync, no allocation, no atomics, tickets
+ *   or fences; graph-capturable, and a replay follows new offsets.
+ * Two forms produce those bits; petit_gemm_native_moe_invariant_form(m, num_experts) names the one a call gets (1: split, 0: whole), a function
+ *   of these two host-known arguments alone: split iff ceil(m / min(E, m)) <= 8 and m <= 8 (constants of the library, not settings;
+ *   profiles/native_moe_invariant.md).  The quantised activations are the k-tile-major image of the m grouped rows, so a tile's rows are one
+ *   contiguous run; its descriptor ends with the tile's last valid row of its expert, and rows of the next expert or past m read zeros.
+ *   split: ceil(m / 32) + min(E, m) slots x S x blocks of 4 pairs of n-tiles; a wave stores its 32 x 32 fp32 tile of one slice to slab s of
+ *     [S][m][n], indexed by grouped row, with plain vector stores; the second launch is the exact MoE entry's fold over its own 16-row slot map
+ *     of the same offsets (gs[e], bias[e], the activation, the scatter into C).  Nothing in the workspace needs clearing.
+ *   whole: ceil(m / 64) + min(E, m) slots x blocks of 4 x 2 pairs of n-tiles; the workgroup stages its expert's 64-row activation tile of every
+ *     k-tile through LDS, a wave walks all S slices with one join per slice, applies the epilogue itself and scatters C; no slab workspace.
+ * Workspace: petit_gemm_native_moe_invariant_workspace_bytes = the quantised bytes (petit_quantized_activation_bytes(m, k, act_format); 16-bit
+ *   input only) + the slabs (S * m * n * 4; split form only), each part rounded up to a multiple of 256, in this order; 0 for a call that would
+ *   be refused and for m == 0.  Caller-owned device memory, 256-byte aligned.
+ * Errors, all before any launch: the dense native-invariant entry's codes (above) without its 65535-row limit on 16-bit input -- the gathering
+ *   quantiser takes any row count; m < 2^20 stays --; the MoE invariant entry's codes (PETIT_ERROR_PROBLEM_SHAPE for num_experts outside
+ *   1..1024, a NULL global_scales or expert_offsets, an index or offset pointer that is not 4-byte aligned, a NULL index with fewer than m rows
+ *   behind it, a launch of 2^31 workgroups or more); PETIT_ERROR_BAD_ARGUMENT for a_is_quantized with an a_row_index;
+ *   PETIT_ERROR_PROBLEM_SHAPE when the quantised rows reach 2^32 bytes.  m == 0 returns PETIT_OK.
+ * petit_gemm_native_moe_invariant_host is the CPU twin on HOST pointers: the grouped "petit-qact/1" bytes of (m, k, act_format), offsets and a C
+ *   index (activation none; bias [E][n] or NULL).  Per expert under the clamp rule it computes each row as petit_gemm_native_invariant_host
+ *   computes it, decoded from the m-row image (the image's addresses depend on m, the values do not).
+ * Not here: NVFP4 images; a quantising (out_format) epilogue; a pipelined whole form; a one-launch split form.
+ */
+int petit_gemm_native_moe_invariant_form(unsigned m, unsigned num_experts); /* 1: split, 0: whole */
+uint64_t petit_gemm_native_moe_invariant_workspace_bytes(unsigned num_experts, unsigned m, unsigned n, unsigned k, int a_type, int act_format,
+                                                         int a_is_quantized);
+int petit_gemm_mxfp4_native_moe_invariant(void *c, const void *a, const void *b, const void *scales, const float *global_scales,
+                                          const int32_t *expert_offsets, unsigned num_experts, unsigned m, unsigned n, unsigned k,
+                                          const int32_t *a_row_index, unsigned a_rows, const int32_t *c_row_index, unsigned c_rows,
+                                          const petit_solution_hints *hints, int act_format /* 8 | 6 | 4 */, int a_is_quantized,
+                                          const petit_epilogue *epilogue, void *workspace, void *stream);
+int petit_gemm_native_moe_invariant_host(void *c, const void *qa, const void *b, const void *scales, const float *global_scales, const void *bias,
+                                         const int32_t *expert_offsets, unsigned num_experts, unsigned m, unsigned n, unsigned k,
+                                         const int32_t *c_row_index, unsigned c_rows, int a_type, int act_format);
 
 /*
  * Native-class MoE launch (no counterpart in the reference): the routed-expert launch on the block-scaled MFMA, the accuracy class of

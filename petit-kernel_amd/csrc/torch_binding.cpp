@@ -475,6 +475,48 @@ at::Tensor mul_mxfp4_a16_moe_invariant(PETIT_MOE_INVARIANT_ARGS) { return mul_a1
 void mul_nvfp4_a16_moe_invariant_out(const at::Tensor &out, PETIT_MOE_INVARIANT_ARGS) { mul_a16_moe_invariant_impl(false, PETIT_MOE_INVARIANT_PASS, &out); }
 void mul_mxfp4_a16_moe_invariant_out(const at::Tensor &out, PETIT_MOE_INVARIANT_ARGS) { mul_a16_moe_invariant_impl(true, PETIT_MOE_INVARIANT_PASS, &out); }
 
+// the batch-invariant MoE launch on the native class (petit_gemm_mxfp4_native_moe_invariant).  A is the 16-bit [a_rows, k] matrix, or
+// (quantized) the "petit-qact/1" bytes of the m grouped rows -- then bf16 names the 16-bit type of c and the bias.  The argument checks and
+// their texts are stated once, in petit_kernel/ops.py (_check_native_moe_invariant), which petit_kernel/compiled.py runs in front of this op;
+// what is checked here is what keeps a direct torch.ops call inside its tensors.
+#define PETIT_NATIVE_MOE_INVARIANT_ARGS                                                                                                          \
+    const at::Tensor &A, const at::Tensor &B, const at::Tensor &s, const at::Tensor &gs, const at::Tensor &off, int64_t m, int64_t n, int64_t k, \
+        int64_t e, const std::optional<at::Tensor> &a_idx, const std::optional<at::Tensor> &c_idx, int64_t c_rows, int64_t act_format,           \
+        bool quantized, bool bf16, const std::optional<at::Tensor> &bias, int64_t activation
+at::Tensor mul_mxfp4_native_moe_invariant(PETIT_NATIVE_MOE_INVARIANT_ARGS) {
+    const at::ScalarType st = bf16 ? at::kBFloat16 : at::kHalf;
+    TORCH_CHECK(act_format == 8 || act_format == 6 || act_format == 4, "act_format must be 8, 6 or 4");
+    check_expert_operands(true, false, A, B, &s, gs, off, e, n, k);
+    TORCH_CHECK(m >= 0 && n > 0 && k > 0 && k % 256 == 0 && A.is_contiguous() &&
+                    (quantized ? A.scalar_type() == at::kByte && A.numel() == m * (k / 8 * act_format) + m * (k / 32) && !a_idx.has_value()
+                               : A.scalar_type() == st && A.numel() % k == 0),
+                "A must be a contiguous [a_rows, size_k] tensor, or the quantised bytes of the size_m grouped rows without an a_row_index");
+    check_row_indices(a_idx, c_idx, A, m);
+    TORCH_CHECK(activation >= 0 && activation <= 2 && (!activation || n % 64 == 0), "activation must be 0, 1 or 2; gated forms need size_n % 64 == 0");
+    check_bias(bias, A, st, e * n, "bias must be a contiguous [num_experts, size_n] tensor of A's dtype on A's device");
+    const int64_t a_rows = quantized ? m : A.numel() / k, n_out = activation ? n / 2 : n;
+    const c10::hip::HIPGuardMasqueradingAsCUDA guard(A.device());
+    c_rows = c_rows < 0 ? m : c_rows;
+    at::Tensor c = at::empty({c_rows, n_out}, A.options().dtype(st));
+    const int a_type = a_type_of(st);
+    const petit_solution_hints hints{a_type, kCxxMxFp4, a_type, 0};
+    const petit_epilogue epi{bias.has_value() ? bias->data_ptr() : nullptr, (int32_t)activation, 0};
+    const uint64_t ws_bytes = petit_gemm_native_moe_invariant_workspace_bytes((unsigned)e, (unsigned)m, (unsigned)n, (unsigned)k, a_type,
+                                                                              (int)act_format, quantized ? 1 : 0);
+    at::Tensor ws;
+    if (ws_bytes)
+        ws = at::empty({(int64_t)ws_bytes}, A.options().dtype(at::kByte));
+    const int rc = petit_gemm_mxfp4_native_moe_invariant(
+        c.data_ptr(), A.data_ptr(), B.data_ptr(), s.data_ptr(), (const float *)gs.data_ptr(), (const int32_t *)off.data_ptr(), (unsigned)e, (unsigned)m,
+        (unsigned)n, (unsigned)k, row_index_ptr(a_idx), (unsigned)a_rows, row_index_ptr(c_idx), (unsigned)c_rows, &hints, (int)act_format,
+        quantized ? 1 : 0, (bias.has_value() || activation) ? &epi : nullptr, ws_bytes ? ws.data_ptr() : nullptr, stream_of(A));
+    TORCH_CHECK(rc != PETIT_ERROR_PROBLEM_SHAPE, "Incompatible problem shape (m=", m, ", n=", n, ", k=", k, ", num_experts=", e, ", a_rows=", a_rows,
+                ", c_rows=", c_rows, ")");
+    TORCH_CHECK(rc != PETIT_ERROR_KERNEL_SHAPE, "No kernel implementation for solution_id=native-invariant.");
+    TORCH_CHECK(rc == PETIT_OK, "mul_mxfp4_native_moe_invariant: ", petit_error_string(rc));
+    return c;
+}
+
 // device routing (petit_moe_align / petit_moe_combine); the same checks and texts as petit_kernel/ops.py
 void check_topk_ids(const at::Tensor &ids, int64_t num_experts) {
     TORCH_CHECK(num_experts >= 1 && num_experts <= PETIT_MOE_MAX_EXPERTS, "num_experts must be in 1..", PETIT_MOE_MAX_EXPERTS, ", got ", num_experts);
@@ -911,6 +953,9 @@ at::Tensor mul_a16_moe_invariant_meta(PETIT_MOE_INVARIANT_ARGS) {
     return at::empty({c_rows < 0 ? m : c_rows, activation ? n / 2 : n}, A.options());
 }
 void mul_a16_moe_invariant_out_meta(const at::Tensor &, PETIT_MOE_INVARIANT_ARGS) {}
+at::Tensor mul_mxfp4_native_moe_invariant_meta(PETIT_NATIVE_MOE_INVARIANT_ARGS) {
+    return at::empty({c_rows < 0 ? m : c_rows, activation ? n / 2 : n}, A.options().dtype(bf16 ? at::kBFloat16 : at::kHalf));
+}
 at::Tensor mul_nvfp4_native_transient_meta(PETIT_NV_TRANSIENT_ARGS) {
     return native_output(A, native_moe_dtype(A, a_format, a_type), size_m, size_m, activation ? size_n / 2 : size_n, out_format);
 }
@@ -1034,6 +1079,9 @@ TORCH_LIBRARY(petit_kernel, m) {
     "Tensor? a_row_index=None, Tensor? c_row_index=None, int c_rows=-1, Tensor? bias=None, int activation=0"
     m.def("mul_mxfp4_native_invariant(Tensor A, Tensor B, Tensor s, Tensor? global_scale, int size_m, int size_n, int size_k, int act_format, "
           "bool quantized, bool bf16, Tensor? bias=None, int activation=0) -> Tensor");
+    m.def("mul_mxfp4_native_moe_invariant(Tensor A, Tensor B, Tensor s, Tensor global_scales, Tensor expert_offsets, int size_m, int size_n, "
+          "int size_k, int num_experts, Tensor? a_row_index, Tensor? c_row_index, int c_rows, int act_format, bool quantized, bool bf16, "
+          "Tensor? bias=None, int activation=0) -> Tensor");
     m.def("mul_nvfp4_a16_moe_invariant(" PETIT_MOE_INVARIANT_SCHEMA ") -> Tensor");
     m.def("mul_mxfp4_a16_moe_invariant(" PETIT_MOE_INVARIANT_SCHEMA ") -> Tensor");
     m.def("mul_nvfp4_a16_moe_invariant_out(Tensor(a!) out, " PETIT_MOE_INVARIANT_SCHEMA ") -> ()");
@@ -1059,6 +1107,7 @@ TORCH_LIBRARY(petit_kernel, m) {
     m.impl("mul_mxfp4_a16_moe_indexed", &mul_mxfp4_a16_moe_indexed); \
     m.impl("mul_nvfp4_a16_moe_indexed_out", &mul_nvfp4_a16_moe_indexed_out); \
     m.impl("mul_mxfp4_a16_moe_indexed_out", &mul_mxfp4_a16_moe_indexed_out); \
+    m.impl("mul_mxfp4_native_moe_invariant", &mul_mxfp4_native_moe_invariant); \
     m.impl("mul_nvfp4_a16_moe_invariant", &mul_nvfp4_a16_moe_invariant); \
     m.impl("mul_mxfp4_a16_moe_invariant", &mul_mxfp4_a16_moe_invariant); \
     m.impl("mul_nvfp4_a16_moe_invariant_out", &mul_nvfp4_a16_moe_invariant_out); \
@@ -1095,6 +1144,7 @@ TORCH_LIBRARY_IMPL(petit_kernel, Meta, m) {
     m.impl("mul_mxfp4_a16_moe_indexed", &mul_a16_moe_indexed_meta);
     m.impl("mul_nvfp4_a16_moe_indexed_out", &mul_a16_moe_indexed_out_meta);
     m.impl("mul_mxfp4_a16_moe_indexed_out", &mul_a16_moe_indexed_out_meta);
+    m.impl("mul_mxfp4_native_moe_invariant", &mul_mxfp4_native_moe_invariant_meta);
     m.impl("mul_nvfp4_a16_moe_invariant", &mul_a16_moe_invariant_meta);
     m.impl("mul_mxfp4_a16_moe_invariant", &mul_a16_moe_invariant_meta);
     m.impl("mul_nvfp4_a16_moe_invariant_out", &mul_a16_moe_invariant_out_meta);

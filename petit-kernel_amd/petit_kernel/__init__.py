@@ -173,6 +173,29 @@ def mul_mxfp4_a16_moe_invariant(a: torch.Tensor, b: torch.Tensor, s: torch.Tenso
                                              c_rows, bias, activation, out)
 
 
+def mul_mxfp4_native_moe_invariant(a, b: torch.Tensor, s: torch.Tensor, global_scales: torch.Tensor, expert_offsets: torch.Tensor, size_m: int,
+                                   size_n: int, size_k: int, num_experts: int, a_row_index: torch.Tensor = None,
+                                   c_row_index: torch.Tensor = None, c_rows: int = None, fmt: str = "mxfp8", bias: torch.Tensor = None,
+                                   activation: str = None) -> torch.Tensor:
+    # the native class's routed-expert launch by its batch-invariant entry (include/petit_amd.h "Batch-invariant MoE launch on the native
+    # class"): every written row equals, bit for bit, mul_mxfp4_native_invariant(size_m=1) on its row with its expert's tensors, global scale
+    # and bias.  a: a 16-bit [a_rows, size_k] tensor (gathered and quantised by the call) or QuantizedActivations of the size_m grouped rows
+    # (quantize_activation_rows) -- the same bits either way.  Opt-in (profiles/native_moe_invariant.md), no solution_id.
+    return _impl.mul_mxfp4_native_moe_invariant(a, b, s, global_scales, expert_offsets, size_m, size_n, size_k, num_experts, a_row_index,
+                                                c_row_index, c_rows, fmt, bias, activation)
+
+
+def native_moe_invariant_form(size_m: int, num_experts: int) -> int:
+    # the form a native-class batch-invariant MoE call gets: 1 split, 0 whole -- a function of these two arguments alone
+    return ops.native_moe_invariant_form(size_m, num_experts)
+
+
+def native_moe_invariant_workspace_bytes(num_experts: int, size_m: int, size_n: int, size_k: int, dtype: torch.dtype = torch.bfloat16,
+                                         fmt: str = "mxfp8", quantized: bool = False) -> int:
+    # bytes of scratch the call allocates per call: the quantised bytes of a 16-bit input plus the split form's slabs
+    return ops.native_moe_invariant_workspace_bytes(num_experts, size_m, size_n, size_k, dtype, fmt, quantized)
+
+
 def moe_invariant_form(size_m: int, num_experts: int) -> int:
     # the form a batch-invariant MoE call gets: 1 split (slabs in scratch, two launches), 0 whole -- a function of these two arguments alone
     return ops.moe_invariant_form(size_m, num_experts)
@@ -390,6 +413,9 @@ __all__ = [
     "mul_mxfp4_a16_moe_invariant",
     "moe_invariant_form",
     "moe_invariant_workspace_bytes",
+    "mul_mxfp4_native_moe_invariant",
+    "native_moe_invariant_form",
+    "native_moe_invariant_workspace_bytes",
     "get_fp4_solutions",
     "mxfp4_scales_in_fp16_range",
     "DataType",

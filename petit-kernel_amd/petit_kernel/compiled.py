@@ -20,6 +20,7 @@ from .ops import _check_moe_invariant
 from .ops import invariant_geometry, invariant_slabs, invariant_workspace_bytes  # (queries: plain C calls, no op behind them)
 from .ops import moe_invariant_form, moe_invariant_workspace_bytes
 from .ops import _QFORMATS, _check_native_invariant, native_invariant_slabs, native_invariant_workspace_bytes
+from .ops import _check_native_moe_invariant, native_moe_invariant_form, native_moe_invariant_workspace_bytes
 
 LIB_PATH = Path(_lib.LIB_PATH).parent / "libpetit_torch.so"
 _loaded = False
@@ -165,6 +166,15 @@ def mul_mxfp4_a16_moe_invariant(A, B, s, global_scales, expert_offsets, size_m, 
                                 c_row_index=None, c_rows=None, bias=None, activation=None, out=None):
     return _mul_moe_invariant("mx", A, B, s, global_scales, expert_offsets, size_m, size_n, size_k, num_experts, a_row_index, c_row_index,
                               c_rows, bias, activation, out)
+
+
+def mul_mxfp4_native_moe_invariant(A, B, s, global_scales, expert_offsets, size_m, size_n, size_k, num_experts, a_row_index=None,
+                                   c_row_index=None, c_rows=None, fmt="mxfp8", bias=None, activation=None):
+    a, dtype, quantized, E, act, _, c_rows = _check_native_moe_invariant(A, B, s, global_scales, expert_offsets, size_m, size_n, size_k,
+                                                                         num_experts, a_row_index, c_row_index, c_rows, fmt, bias, activation)
+    return torch.ops.petit_kernel.mul_mxfp4_native_moe_invariant(a, B, s, global_scales, expert_offsets, int(size_m), int(size_n), int(size_k), E,
+                                                                 a_row_index, c_row_index, int(c_rows), _QFORMATS[fmt], bool(quantized),
+                                                                 dtype == torch.bfloat16, bias, act)
 
 
 def moe_align_device(topk_ids, num_experts):

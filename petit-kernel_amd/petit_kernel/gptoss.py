@@ -99,21 +99,24 @@ class GptOssExperts:
         return x if self.hidden_padded == self.hidden else torch.nn.functional.pad(x, (0, self.hidden_padded - self.hidden))
 
     def forward(self, x: torch.Tensor, topk_weights: torch.Tensor, topk_ids: torch.Tensor, path: str = "fused",
-                activations: str = "mxfp8") -> torch.Tensor:
+                activations: str = "mxfp8", invariant: bool = False) -> torch.Tensor:
         """The expert block of gpt-oss: out[t] = sum_j topk_weights[t, j] * (down_e(swiglu_oai(gate_up_e(x_t) + b13_e)) + b2_e), e = topk_ids[t, j].
 
         x [T, hidden] bf16 / fp16 (the biases' dtype); returns [T, hidden] -- down's N is the unpadded hidden size, so nothing is sliced off.
         path 'fused': fp4_moe_fused (exact class); 'native': fp4_moe_native with `activations` ('mxfp8' / 'mxfp6' / 'mxfp4').
         Cost of the padding: x is zero-padded to hidden_padded with one torch op, i.e. one T x hidden_padded 16-bit copy per call (18 KiB per
-        token at 2880 -> 3072: the kernels read A in whole 256-column spans and have no column mask).  No host sync: capturable."""
+        token at 2880 -> 3072: the kernels read A in whole 256-column spans and have no column mask).  No host sync: capturable.
+        invariant=True: the layer's batch-invariant switch on either path (fp4_moe_fused / fp4_moe_native, invariant=True): a token's output
+        row has the same bits alone and inside any batch.  Path 'native' takes bf16 and fp16; path 'fused' bf16 only."""
         from .moe import fp4_moe_fused, fp4_moe_native
         _check(path in ("fused", "native"), "path must be 'fused' or 'native'")
         xp = self.pad_hidden(x)
         kw = dict(bias13=self.bias13, bias2=self.bias2, activation="swiglu_oai")
         if path == "fused":
-            return fp4_moe_fused(xp, self.w13, self.s13, self.gs13, self.w2, self.s2, self.gs2, topk_weights, topk_ids, kind="mxfp4", **kw)
+            return fp4_moe_fused(xp, self.w13, self.s13, self.gs13, self.w2, self.s2, self.gs2, topk_weights, topk_ids, kind="mxfp4",
+                                 invariant=invariant, **kw)
         return fp4_moe_native(xp, self.w13, self.s13, self.gs13, self.w2, self.s2, self.gs2, topk_weights, topk_ids, kind="mxfp4",
-                              activations=activations, **kw)
+                              activations=activations, invariant=invariant, **kw)
 
     def forward_routed(self, x: torch.Tensor, router_logits: torch.Tensor, topk: int = 4, path: str = "fused",
                        activations: str = "mxfp8") -> torch.Tensor:

@@ -181,7 +181,7 @@ def fp4_moe_native(hidden: torch.Tensor, w13: torch.Tensor, s13, gs13: torch.Ten
                    topk_weights: torch.Tensor, topk_ids: torch.Tensor, kind: str = "mxfp4", activations: str = "mxfp8", *,
                    bias13: torch.Tensor = None, bias2: torch.Tensor = None, activation: str = "silu_mul", transient: bool = False,
                    norm_weight: torch.Tensor = None, norm_eps: float = 1e-6, norm_residual: torch.Tensor = None, norm_weight_offset: float = 0.0,
-                   norm_fmt: str = None):
+                   norm_fmt: str = None, invariant: bool = False):
     """fp4_moe_fused's layer on the NATIVE class (the block-scaled MFMA, activations quantised to `activations`: 'mxfp8', 'mxfp6' or 'mxfp4';
     petit_gemm_native_moe -- a different accuracy class than the exact layers).  kind 'mxfp4': w13 / s13 / w2 / s2 as fp4_moe_fused; kind
     'nvfp4': w13 / w2 are the experts' MFMA-native images back to back (nvfp4_native_images) and s13 / s2 are None.  Five launches (seven
@@ -196,10 +196,27 @@ def fp4_moe_native(hidden: torch.Tensor, w13: torch.Tensor, s13, gs13: torch.Ten
     and, while it runs, that scratch.  Bit for bit the resident layer on nvfp4_native_images of the same tensors.
 
     norm_weight / norm_eps / norm_residual / norm_weight_offset / norm_fmt: fp4_moe_fused's fused end (the combine, the residual add, the next
-    RMSNorm and its quantiser in the last launch; returns (h, y16) or (q, h)), for a layer whose combine is complete on this rank."""
+    RMSNorm and its quantiser in the last launch; returns (h, y16) or (q, h)), for a layer whose combine is complete on this rank.
+
+    invariant=True (kind 'mxfp4', resident tensors): gate_up and down run as the native class's batch-invariant MoE launches
+    (mul_mxfp4_native_moe_invariant): the device align, the gathering quantiser, gate_up on the quantised grouped rows with the gated
+    activation writing 16-bit [m, I] grouped rows, down on that matrix -- which quantises it itself -- scattered into slot order, the combine.
+    Every slot row is then a pure function of its token's hidden row and its expert's weights, and the combine adds a token's slots in slot
+    order, in fp32, with one rounding: given the same topk_weights / topk_ids row, a token's output row has the same bits alone and inside
+    any batch, at any position -- with the fused norm end too.  bfloat16 and float16 hidden states.  Opt-in and slower
+    (profiles/native_moe_invariant.md).  kind 'nvfp4' and transient=True raise: images are not on the invariant native entries."""
     _check_native(kind, activation, activations, transient)
+    if invariant:
+        if transient:
+            raise RuntimeError("invariant=True on the native class does not take transient=True: images have no batch-invariant native kernel")
+        if kind == "nvfp4":
+            raise RuntimeError("invariant=True on the native class is for kind 'mxfp4': NVFP4 images have no batch-invariant native kernel "
+                               "(fp4_moe_fused(..., invariant=True) runs NVFP4 experts in the exact class)")
     norm = _norm_end(norm_weight, norm_eps, norm_residual, norm_weight_offset, norm_fmt)
     w, ids, sorted_pos, offsets, token_index = _align_routing(topk_weights, topk_ids, gs13.numel())
+    if invariant:
+        return _native_invariant_after_align(hidden, w13, s13, gs13, w2, s2, gs2, w, ids, sorted_pos, offsets, token_index, activations, bias13,
+                                             bias2, activation, norm)
     return _native_after_align(hidden, w13, s13, gs13, w2, s2, gs2, w, ids, sorted_pos, offsets, token_index, kind, activations, bias13, bias2,
                                activation, transient, norm)
 
@@ -212,6 +229,23 @@ def _check_native(kind, activation, activations, transient=False) -> None:
         raise RuntimeError("activations must be 'mxfp8', 'mxfp6' or 'mxfp4'")
     if transient and kind != "nvfp4":
         raise RuntimeError("transient=True is for kind 'nvfp4' (MXFP4 experts run on the packed tensors: there is no image to build)")
+
+
+def _native_invariant_after_align(hidden, w13, s13, gs13, w2, s2, gs2, w, ids, sorted_pos, offsets, token_index, activations, bias13, bias2,
+                                  activation, norm=None):
+    """fp4_moe_native(invariant=True) after its align: the gathering quantiser, the two batch-invariant launches, the combine."""
+    from . import mul_mxfp4_native_moe_invariant, quantize_activation_rows
+    T, H = hidden.shape
+    E = gs13.numel()
+    m = T * ids.shape[1]
+    n13 = w13.numel() * w13.element_size() * 2 // (E * H)   # 2 I
+    inter = n13 // 2
+    n2 = _down_n(w2, E, inter, H)
+    qa = quantize_activation_rows(hidden, activations, token_index)                  # grouped rows; unrouted (-1) rows are zeros
+    h = mul_mxfp4_native_moe_invariant(qa, w13, s13, gs13, offsets, m, n13, H, E, fmt=activations, bias=bias13, activation=activation)  # [m, I]
+    y = mul_mxfp4_native_moe_invariant(h, w2, s2, gs2, offsets, m, n2, inter, E, c_row_index=sorted_pos, c_rows=m, fmt=activations,
+                                       bias=bias2)                                   # [m, n2], (token, slot) order
+    return _combine(y, w, ids, E, norm)
 
 
 def _native_after_align(hidden, w13, s13, gs13, w2, s2, gs2, w, ids, sorted_pos, offsets, token_index, kind, activations, bias13, bias2,
@@ -283,7 +317,8 @@ def fp4_moe_routed(hidden: torch.Tensor, router_logits: torch.Tensor, w13: torch
     logits, with the tie rule the chosen experts and their weights, every slot row and the combine are pure functions of the token's hidden
     row and the weights, so a token's output row has the same bits alone and inside any batch.  This holds with the fused norm end too (both
     returned tensors).  Under expert or tensor parallelism it holds only up to the all-reduce, which is outside this library.  path 'native'
-    and kind 'mxfp4' on float16 hidden states have no batch-invariant kernel and raise."""
+    and kind 'mxfp4' on float16 hidden states raise here: the native class's batch-invariant layer is fp4_moe_native(..., invariant=True), from
+    a routing computed by the caller (moe_route_hidden)."""
     from . import moe_route_align, moe_route_hidden
     if path not in ("fused", "native"):
         raise RuntimeError("path must be 'fused' or 'native'")

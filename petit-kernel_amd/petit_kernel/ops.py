@@ -1093,6 +1093,101 @@ def mul_mxfp4_a16_moe_invariant(A, B, s, global_scales, expert_offsets, size_m, 
                               c_rows, bias, activation, out)
 
 
+# --- the batch-invariant MoE launch on the native class (include/petit_amd.h "Batch-invariant MoE launch on the native class") --------------
+
+def _check_native_moe_invariant(A, B, s, global_scales, expert_offsets, size_m, size_n, size_k, num_experts, a_row_index, c_row_index, c_rows,
+                                fmt, bias, activation):
+    """The argument checks of mul_mxfp4_native_moe_invariant, stated here for both operator layers -> (activation tensor, 16-bit dtype,
+    a_is_quantized, E, activation code, a_rows, c_rows).  Value checks come first and device checks last, so that the texts can be read
+    without a GPU."""
+    name = "mul_mxfp4_native_moe_invariant"
+    _check(fmt in _QFORMATS, "fmt must be 'mxfp8', 'mxfp6' or 'mxfp4'")
+    quantized = isinstance(A, QuantizedActivations)
+    dtype = A.dtype
+    _check(dtype in (torch.bfloat16, torch.float16), "A must be bfloat16 or float16 (or QuantizedActivations of such a tensor).")
+    size_m, size_n, size_k, E = int(size_m), int(size_n), int(size_k), int(num_experts)
+    _check(1 <= E <= _lib.PETIT_MOE_MAX_EXPERTS, f"num_experts must be in 1..{_lib.PETIT_MOE_MAX_EXPERTS}, got {E}")
+    _check(size_n > 0 and size_n % 32 == 0 and size_k > 0 and size_k % 256 == 0 and 0 <= size_m < 1 << 20,
+           f"Incompatible problem shape (m={size_m}, n={size_n}, k={size_k}): {name} needs n % 32 == 0, k % 256 == 0, m < 2^20")
+    _check(activation in _ACTIVATIONS, _ACTIVATION_RULE)
+    act = _ACTIVATIONS[activation]
+    _check(not act or size_n % 64 == 0, f"{activation} needs size_n % 64 == 0 here (gate / up halves of whole tile pairs), got {size_n}")
+    if quantized:
+        _check(A.fmt == fmt, f"quantised activations are {A.fmt}, the call says fmt={fmt!r}")
+        _check(A.m == size_m and A.k == size_k, f"quantised activations are [{A.m}, {A.k}], the call says [{size_m}, {size_k}]")
+        _check(a_row_index is None, f"{name}: quantised activations are the grouped rows already; a_row_index must be None")
+        a = A.data
+        _check(a.dtype == torch.uint8 and a.is_contiguous() and a.numel() == size_m * (size_k // 8 * _QFORMATS[fmt]) + size_m * (size_k // 32),
+               "quantised activations do not hold the bytes of their [m, k] and format")
+        a_rows = size_m
+    else:
+        a = A
+        _check(a.is_contiguous() and a.numel() % size_k == 0, "A must be a contiguous [a_rows, size_k] tensor")
+        a_rows = a.numel() // size_k
+    _check(B.is_contiguous() and B.numel() * B.element_size() == E * size_n * size_k // 2,
+           "B does not hold num_experts * size_n * size_k packed 4-bit weights")
+    _check(s.is_contiguous() and s.numel() * s.element_size() == E * size_n * size_k // 32, "s does not hold num_experts * size_n * size_k / 32 scales")
+    _check(global_scales.dtype == torch.float32 and global_scales.is_contiguous() and global_scales.numel() == E,
+           "global_scales must be a contiguous float32 [num_experts] tensor")
+    _check(expert_offsets.dtype == torch.int32 and expert_offsets.is_contiguous() and expert_offsets.numel() == E + 1,
+           "expert_offsets must be a contiguous int32 [num_experts + 1] tensor")
+    for idx in (a_row_index, c_row_index):
+        if idx is not None:
+            _check(idx.dtype == torch.int32 and idx.is_contiguous() and idx.numel() == size_m and idx.device == a.device,
+                   "row indices must be contiguous int32 [size_m] tensors on A's device")
+    c_rows = size_m if c_rows is None or c_rows < 0 else int(c_rows)
+    _check((a_row_index is not None or a_rows >= size_m) and (c_row_index is not None or c_rows >= size_m),
+           f"{name}: without a row index the matrix must hold size_m rows (a_rows={a_rows}, c_rows={c_rows}, m={size_m})")
+    if bias is not None:
+        _check(bias.dtype == dtype and bias.is_contiguous() and bias.numel() == E * size_n and bias.device == a.device,
+               "bias must be a contiguous [num_experts, size_n] tensor of A's dtype on A's device")
+    _check(a.is_cuda and B.is_cuda and s.is_cuda and global_scales.is_cuda and expert_offsets.is_cuda, "all tensors must be on GPU")
+    _check(B.device == a.device and s.device == a.device and global_scales.device == a.device and expert_offsets.device == a.device,
+           "all tensors must be on A's device")
+    return a, dtype, int(quantized), E, act, a_rows, c_rows
+
+
+def native_moe_invariant_form(size_m: int, num_experts: int) -> int:
+    """The form a native-class batch-invariant MoE call of size_m grouped rows over num_experts gets
+    (petit_gemm_native_moe_invariant_form): 1 split, 0 whole.  Both forms give the same bits; the switch is a speed choice."""
+    return int(_lib.lib.petit_gemm_native_moe_invariant_form(int(size_m), int(num_experts)))
+
+
+def native_moe_invariant_workspace_bytes(num_experts: int, size_m: int, size_n: int, size_k: int, dtype: torch.dtype = torch.bfloat16,
+                                         fmt: str = "mxfp8", quantized: bool = False) -> int:
+    """Bytes of scratch mul_mxfp4_native_moe_invariant uses (petit_gemm_native_moe_invariant_workspace_bytes): the quantised bytes of a 16-bit
+    A plus the split form's slabs, each rounded up to 256; 0 for a call that would be refused."""
+    _check(fmt in _QFORMATS, "fmt must be 'mxfp8', 'mxfp6' or 'mxfp4'")
+    return int(_lib.lib.petit_gemm_native_moe_invariant_workspace_bytes(int(num_experts), int(size_m), int(size_n), int(size_k), _a_type(dtype),
+                                                                        _QFORMATS[fmt], int(bool(quantized))))
+
+
+def mul_mxfp4_native_moe_invariant(A, B, s, global_scales, expert_offsets, size_m, size_n, size_k, num_experts, a_row_index=None,
+                                   c_row_index=None, c_rows=None, fmt="mxfp8", bias=None, activation=None) -> torch.Tensor:
+    """The native class's MoE GEMM by the batch-invariant entry (petit_gemm_mxfp4_native_moe_invariant, include/petit_amd.h "Batch-invariant
+    MoE launch on the native class"): every written row equals, bit for bit, mul_mxfp4_native_invariant(size_m=1) on its row and its expert's
+    tensors -- whatever else is in the batch and wherever the row sits.  A: a 16-bit [a_rows, size_k] tensor (gathered through a_row_index and
+    quantised by the call) or QuantizedActivations of the size_m grouped rows (quantize_activation_rows) -- the same bits either way.
+    Opt-in; no solution_id (profiles/native_moe_invariant.md has the price)."""
+    a, dtype, quantized, E, act, a_rows, c_rows = _check_native_moe_invariant(A, B, s, global_scales, expert_offsets, size_m, size_n, size_k,
+                                                                              num_experts, a_row_index, c_row_index, c_rows, fmt, bias,
+                                                                              activation)
+    size_m, size_n, size_k = int(size_m), int(size_n), int(size_k)
+    c = torch.empty((c_rows, size_n // 2 if act else size_n), dtype=dtype, device=a.device)
+    hints = _hints("mx", dtype)
+    epi = _epilogue(bias, act, a.device, dtype, E * size_n, "bias must be a contiguous [num_experts, size_n] tensor of A's dtype on A's device")
+    ws = _scratch(int(_lib.lib.petit_gemm_native_moe_invariant_workspace_bytes(E, size_m, size_n, size_k, hints.a_type, _QFORMATS[fmt],
+                                                                               quantized)), a.device)
+    with torch.cuda.device(a.device):
+        err = _lib.lib.petit_gemm_mxfp4_native_moe_invariant(_ptr(c), _ptr(a), _ptr(B), _ptr(s), _ptr(global_scales), _ptr(expert_offsets), E,
+                                                             size_m, size_n, size_k, _opt_ptr(a_row_index), a_rows, _opt_ptr(c_row_index),
+                                                             c_rows, C.byref(hints), _QFORMATS[fmt], quantized, epi, _opt_ptr(ws), _stream(a))
+    if err:
+        _raise_gemm(err, "mul_mxfp4_native_moe_invariant", "native-invariant",
+                    f"m={size_m}, n={size_n}, k={size_k}, num_experts={E}, a_rows={a_rows}, c_rows={c_rows}")
+    return c
+
+
 def _check_topk_ids(topk_ids: torch.Tensor, num_experts: int) -> None:
     _check(1 <= int(num_experts) <= _lib.PETIT_MOE_MAX_EXPERTS, f"num_experts must be in 1..{_lib.PETIT_MOE_MAX_EXPERTS}, got {num_experts}")
     _check(topk_ids.is_cuda and topk_ids.dim() == 2 and topk_ids.is_contiguous() and topk_ids.dtype in (torch.int32, torch.int64),
