@@ -1,7 +1,7 @@
 // gemm_invariant.hpp -- the batch-invariant dense GEMM (include/petit_amd.h "Batch-invariant GEMM"): every output element is a pure function of
 // its activation row, the weights, the scales and the bias -- never of M, of the row's position, or of the launch form.
 //
-// K is cut into S slices of L (invariant_geometry, gemm_invariant_host.h: a function of (n, k, a_type, b_type) alone).  The partial sum p_s of a
+// K is cut into S slices of L (geometry, gemm_invariant_host.h: a function of (n, k, a_type, b_type) alone).  The partial sum p_s of a
 // slice is ONE chain of v_mfma_f32_16x16x32_{bf16,f16} from a zero accumulator: k-tiles of 128 ascending, the four words of a packed tile in
 // their own order (layout.h), the weight operand dequantised exactly to the activation type with its group scale applied BEFORE the MFMA.  The
 // result is ((p_0 + p_1) + ... + p_{S-1}) * gs + bias in fp32, rounded once.  Two forms produce those bits:
@@ -24,6 +24,7 @@
 #include <hip/hip_runtime.h>
 
 #include "device_common.hpp"
+#include "gemm_invariant_host.h"
 
 namespace petit_amd {
 
@@ -141,20 +142,16 @@ template <class AT> __global__ __launch_bounds__(256) void invariant_fold_kernel
 
 constexpr int kInvariantSplitDepth = 4;
 
+// the grid of one launch of the plan (gemm_invariant_host.h), which is where every grid of the family is computed
+inline dim3 invariant_grid(const invariant::Launch &l) { return dim3((unsigned)l.grid_x, l.grid_y, l.grid_z); }
+
 // one (format, type) pair's launches; instantiated by gemm_invariant_*.hip
-template <class AT, int FMT> void invariant_launch(const InvariantArgs &p, bool whole, hipStream_t stream) {
-    const unsigned ntiles = p.n / kTileN;
-    if (!whole) {
-        const dim3 grid((ntiles + 3) / 4, p.slices, (p.m + 15) / 16);
-        hipLaunchKernelGGL((gemm_invariant_split_kernel<AT, FMT, kInvariantSplitDepth>), grid, dim3(256), 0, stream, p);
-        const unsigned n_out = p.act ? p.n / 2 : p.n;
-        const size_t count = (size_t)p.m * (n_out / 4);
-        const unsigned blocks = (unsigned)((count + 255) / 256 < 4096 ? (count + 255) / 256 : 4096);
-        hipLaunchKernelGGL((invariant_fold_kernel<AT>), dim3(blocks), dim3(256), 0, stream, p);
+template <class AT, int FMT> void invariant_launch(const InvariantArgs &p, const invariant::Plan &plan, hipStream_t stream) {
+    if (plan.split) {
+        hipLaunchKernelGGL((gemm_invariant_split_kernel<AT, FMT, kInvariantSplitDepth>), invariant_grid(plan.gemm), dim3(256), 0, stream, p);
+        hipLaunchKernelGGL((invariant_fold_kernel<AT>), invariant_grid(plan.fold), dim3(256), 0, stream, p);
     } else {
-        const unsigned slots = p.act ? ntiles / 2 : (ntiles + 1) / 2; // tile pairs
-        const dim3 grid((slots + 3) / 4, (p.m + 63) / 64);
-        hipLaunchKernelGGL((gemm_invariant_whole_kernel<AT, FMT>), grid, dim3(256), 0, stream, p);
+        hipLaunchKernelGGL((gemm_invariant_whole_kernel<AT, FMT>), invariant_grid(plan.gemm), dim3(256), 0, stream, p);
     }
 }
 

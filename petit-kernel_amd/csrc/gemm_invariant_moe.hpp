@@ -128,21 +128,16 @@ template <class AT, int FMT> __global__ __launch_bounds__(256) void gemm_invaria
 #include "gemm_invariant_whole.inc"
 }
 
-// one (format, type) pair's launches; instantiated by gemm_invariant_moe_*.hip.  The grids were bounded by the host (moe_grid, gemm_invariant_host.h).
-template <class AT, int FMT> void invariant_moe_launch(InvariantMoeArgs p, bool split, hipStream_t stream) {
-    const unsigned ntiles = p.n / kTileN, active = p.experts < p.m ? p.experts : p.m;
-    if (split) {
-        const unsigned slots = (p.m + 15) / 16 + active;
-        p.nblocks = (ntiles + 3) / 4;
-        hipLaunchKernelGGL((gemm_invariant_moe_split_kernel<AT, FMT, kInvariantSplitDepth>), dim3(slots * p.slices * p.nblocks), dim3(256), 0, stream, p);
-        const unsigned n_out = p.act ? p.n / 2 : p.n;
-        p.nblocks = (16u * (n_out / 4) + 1023) / 1024; // a thread folds at most 4 units of its m-tile
-        hipLaunchKernelGGL((invariant_moe_fold_kernel<AT>), dim3(slots * p.nblocks), dim3(256), 0, stream, p);
+// one (format, type) pair's launches; instantiated by gemm_invariant_moe_*.hip.  The grids are the plan's (gemm_invariant_host.h), which refused
+// the call had one of them reached 2^31.
+template <class AT, int FMT> void invariant_moe_launch(InvariantMoeArgs p, const invariant::Plan &plan, hipStream_t stream) {
+    p.nblocks = plan.gemm.nblocks;
+    if (plan.split) {
+        hipLaunchKernelGGL((gemm_invariant_moe_split_kernel<AT, FMT, kInvariantSplitDepth>), invariant_grid(plan.gemm), dim3(256), 0, stream, p);
+        p.nblocks = plan.fold.nblocks;
+        hipLaunchKernelGGL((invariant_moe_fold_kernel<AT>), invariant_grid(plan.fold), dim3(256), 0, stream, p);
     } else {
-        const unsigned slots = (p.m + 63) / 64 + active;
-        const unsigned pairs = p.act ? ntiles / 2 : (ntiles + 1) / 2;
-        p.nblocks = (pairs + 3) / 4;
-        hipLaunchKernelGGL((gemm_invariant_moe_whole_kernel<AT, FMT>), dim3(slots * p.nblocks), dim3(256), 0, stream, p);
+        hipLaunchKernelGGL((gemm_invariant_moe_whole_kernel<AT, FMT>), invariant_grid(plan.gemm), dim3(256), 0, stream, p);
     }
 }
 

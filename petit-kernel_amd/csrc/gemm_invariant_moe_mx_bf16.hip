@@ -2,5 +2,5 @@
 #include "gemm_invariant_moe.hpp"
 
 namespace petit_amd {
-template void invariant_moe_launch<Bf16, kFmtMx>(InvariantMoeArgs, bool, hipStream_t);
+template void invariant_moe_launch<Bf16, kFmtMx>(InvariantMoeArgs, const invariant::Plan &, hipStream_t);
 } // namespace petit_amd

@@ -2,5 +2,5 @@
 #include "gemm_invariant.hpp"
 
 namespace petit_amd {
-template void invariant_launch<Fp16, kFmtNv>(const InvariantArgs &, bool, hipStream_t);
+template void invariant_launch<Fp16, kFmtNv>(const InvariantArgs &, const invariant::Plan &, hipStream_t);
 } // namespace petit_amd

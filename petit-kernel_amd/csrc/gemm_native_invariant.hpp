@@ -2,7 +2,7 @@
 // raw MXFP4 weights against MXFP8 / MXFP6 / MXFP4 activations ("petit-qact/1" bytes) on v_mfma_scale_f32_32x32x64_f8f6f4, every output element a
 // pure function of its quantised activation row, the weights, the scales and the bias -- never of M, of the row's position, or of the launch form.
 //
-// K is cut into S slices of L (invariant_geometry, gemm_invariant_host.h: a function of (n, k) alone).  The partial sum p_s of a slice is ONE
+// K is cut into S slices of L (geometry, gemm_invariant_host.h: a function of (n, k) alone).  The partial sum p_s of a slice is ONE
 // chain of the 32x32x64 instruction from a zero accumulator: k-tiles of 128 ascending, two instructions per k-tile -- P1 (k 0..63 of the tile),
 // then P2 (k 64..127).  The weight operand is the pair of neighbouring n-tiles merged in registers (merge_tiles, gemm_wide.hpp: the lane's four
 // registers ARE the FP4 operand) with the merged span-record byte as its E8M0 scale; the activation operand is the row's quantised bytes of that
@@ -130,31 +130,24 @@ template <class AT, int ACT> __global__ __launch_bounds__(256) void native_invar
 constexpr int kNativeInvariantSplitDepth = 3;
 
 // one activation type's launches; instantiated by gemm_native_invariant_{bf16,f16}.hip
-template <class AT, int ACT> void native_invariant_launch_fmt(const NativeInvariantArgs &p, bool whole, hipStream_t stream) {
-    const unsigned pairs = p.n / (2 * kTileN);
-    if (!whole) {
-        const dim3 grid((pairs + 3) / 4, p.slices, (p.m + 31) / 32);
-        hipLaunchKernelGGL((native_invariant_split_kernel<AT, ACT, kNativeInvariantSplitDepth>), grid, dim3(256), 0, stream, p);
-        InvariantArgs f{};
+template <class AT, int ACT> void native_invariant_launch_fmt(const NativeInvariantArgs &p, const invariant::Plan &plan, hipStream_t stream) {
+    if (plan.split) {
+        hipLaunchKernelGGL((native_invariant_split_kernel<AT, ACT, kNativeInvariantSplitDepth>), invariant_grid(plan.gemm), dim3(256), 0, stream, p);
+        InvariantArgs f{}; // the fold of the exact class
         f.c = p.c, f.gs = p.gs, f.bias = p.bias, f.slabs = p.slabs, f.m = p.m, f.n = p.n, f.k = p.k, f.slice_k = p.slice_k, f.slices = p.slices,
         f.act = p.act;
-        const unsigned n_out = p.act ? p.n / 2 : p.n;
-        const size_t count = (size_t)p.m * (n_out / 4);
-        const unsigned blocks = (unsigned)((count + 255) / 256 < 4096 ? (count + 255) / 256 : 4096);
-        hipLaunchKernelGGL((invariant_fold_kernel<AT>), dim3(blocks), dim3(256), 0, stream, f);
+        hipLaunchKernelGGL((invariant_fold_kernel<AT>), invariant_grid(plan.fold), dim3(256), 0, stream, f);
     } else {
-        const unsigned slots = p.act ? pairs / 2 : (pairs + 1) / 2;
-        const dim3 grid((slots + 3) / 4, (p.m + 63) / 64);
-        hipLaunchKernelGGL((native_invariant_whole_kernel<AT, ACT>), grid, dim3(256), 0, stream, p);
+        hipLaunchKernelGGL((native_invariant_whole_kernel<AT, ACT>), invariant_grid(plan.gemm), dim3(256), 0, stream, p);
     }
 }
-template <class AT> void native_invariant_launch(const NativeInvariantArgs &p, int act_format, bool whole, hipStream_t stream) {
+template <class AT> void native_invariant_launch(const NativeInvariantArgs &p, int act_format, const invariant::Plan &plan, hipStream_t stream) {
     if (act_format == 8)
-        native_invariant_launch_fmt<AT, 8>(p, whole, stream);
+        native_invariant_launch_fmt<AT, 8>(p, plan, stream);
     else if (act_format == 6)
-        native_invariant_launch_fmt<AT, 6>(p, whole, stream);
+        native_invariant_launch_fmt<AT, 6>(p, plan, stream);
     else
-        native_invariant_launch_fmt<AT, 4>(p, whole, stream);
+        native_invariant_launch_fmt<AT, 4>(p, plan, stream);
 }
 
 } // namespace petit_amd

@@ -2,5 +2,5 @@
 #include "gemm_native_invariant.hpp"
 
 namespace petit_amd {
-template void native_invariant_launch<Fp16>(const NativeInvariantArgs &, int, bool, hipStream_t);
+template void native_invariant_launch<Fp16>(const NativeInvariantArgs &, int, const invariant::Plan &, hipStream_t);
 } // namespace petit_amd

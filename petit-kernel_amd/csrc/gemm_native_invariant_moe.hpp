@@ -86,36 +86,29 @@ template <class AT, int ACT> __global__ __launch_bounds__(256) void native_invar
 #include "gemm_native_invariant_whole.inc"
 }
 
-// one activation type's launches; instantiated by gemm_native_invariant_moe_{bf16,f16}.hip.  The grids were bounded by the host (moe_grid,
-// gemm_native_invariant_moe_host.h).
-template <class AT, int ACT> void native_invariant_moe_launch_fmt(NativeInvariantMoeArgs p, bool split, hipStream_t stream) {
-    const unsigned pairs = p.n / (2 * kTileN), active = p.experts < p.m ? p.experts : p.m;
-    if (split) {
-        const unsigned slots = (p.m + 31) / 32 + active;
-        p.nblocks = (pairs + 3) / 4;
-        hipLaunchKernelGGL((native_invariant_moe_split_kernel<AT, ACT, kNativeInvariantSplitDepth>), dim3(slots * p.slices * p.nblocks), dim3(256), 0,
-                           stream, p);
+// one activation type's launches; instantiated by gemm_native_invariant_moe_{bf16,f16}.hip.  The grids are the plan's (gemm_invariant_host.h),
+// which refused the call had one of them reached 2^31.
+template <class AT, int ACT> void native_invariant_moe_launch_fmt(NativeInvariantMoeArgs p, const invariant::Plan &plan, hipStream_t stream) {
+    p.nblocks = plan.gemm.nblocks;
+    if (plan.split) {
+        hipLaunchKernelGGL((native_invariant_moe_split_kernel<AT, ACT, kNativeInvariantSplitDepth>), invariant_grid(plan.gemm), dim3(256), 0, stream, p);
         // the fold of the exact MoE launch, over its own 16-row slot map of the same offsets
         InvariantMoeArgs f{};
         f.c = p.c, f.gs = p.gs, f.bias = p.bias, f.slabs = p.slabs, f.offsets = p.offsets, f.c_idx = p.c_idx;
         f.m = p.m, f.n = p.n, f.k = p.k, f.slice_k = p.slice_k, f.slices = p.slices, f.act = p.act, f.experts = p.experts, f.c_rows = p.c_rows;
-        const unsigned n_out = p.act ? p.n / 2 : p.n, fold_slots = (p.m + 15) / 16 + active;
-        f.nblocks = (16u * (n_out / 4) + 1023) / 1024; // a thread folds at most 4 units of its m-tile
-        hipLaunchKernelGGL((invariant_moe_fold_kernel<AT>), dim3(fold_slots * f.nblocks), dim3(256), 0, stream, f);
+        f.nblocks = plan.fold.nblocks;
+        hipLaunchKernelGGL((invariant_moe_fold_kernel<AT>), invariant_grid(plan.fold), dim3(256), 0, stream, f);
     } else {
-        const unsigned slots = (p.m + 63) / 64 + active;
-        const unsigned nslots = p.act ? pairs / 2 : (pairs + 1) / 2;
-        p.nblocks = (nslots + 3) / 4;
-        hipLaunchKernelGGL((native_invariant_moe_whole_kernel<AT, ACT>), dim3(slots * p.nblocks), dim3(256), 0, stream, p);
+        hipLaunchKernelGGL((native_invariant_moe_whole_kernel<AT, ACT>), invariant_grid(plan.gemm), dim3(256), 0, stream, p);
     }
 }
-template <class AT> void native_invariant_moe_launch(const NativeInvariantMoeArgs &p, int act_format, bool split, hipStream_t stream) {
+template <class AT> void native_invariant_moe_launch(const NativeInvariantMoeArgs &p, int act_format, const invariant::Plan &plan, hipStream_t stream) {
     if (act_format == 8)
-        native_invariant_moe_launch_fmt<AT, 8>(p, split, stream);
+        native_invariant_moe_launch_fmt<AT, 8>(p, plan, stream);
     else if (act_format == 6)
-        native_invariant_moe_launch_fmt<AT, 6>(p, split, stream);
+        native_invariant_moe_launch_fmt<AT, 6>(p, plan, stream);
     else
-        native_invariant_moe_launch_fmt<AT, 4>(p, split, stream);
+        native_invariant_moe_launch_fmt<AT, 4>(p, plan, stream);
 }
 
 } // namespace petit_amd

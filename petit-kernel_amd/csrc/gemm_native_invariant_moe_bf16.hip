@@ -2,5 +2,5 @@
 #include "gemm_native_invariant_moe.hpp"
 
 namespace petit_amd {
-template void native_invariant_moe_launch<Bf16>(const NativeInvariantMoeArgs &, int, bool, hipStream_t);
+template void native_invariant_moe_launch<Bf16>(const NativeInvariantMoeArgs &, int, const invariant::Plan &, hipStream_t);
 } // namespace petit_amd

@@ -254,9 +254,74 @@ at::Tensor mul_mxfp4_a16(const at::Tensor &A, const at::Tensor &B, const at::Ten
     return mul_a16(true, A, B, s, gs, m, n, k, solution_id, bias, activation);
 }
 
-// the batch-invariant GEMM (petit_gemm_fp4_fp16_invariant / petit_gemm_mxfp4_fp16_invariant).  The argument checks and their texts are stated
-// once, in petit_kernel/ops.py (_check_invariant), which petit_kernel/compiled.py runs in front of these ops; what is checked here is what keeps
-// a direct torch.ops call inside its tensors.
+// The batch-invariant GEMM family (include/petit_amd.h "Batch-invariant GEMM", "Batch-invariant MoE launch" and their two "... on the native
+// class" sections).  The argument checks and their texts are stated once, in petit_kernel/ops.py (_check_invariant), which
+// petit_kernel/compiled.py runs in front of these ops; what each op checks itself is what keeps a direct torch.ops call inside its tensors.
+// Behind the ops is ONE routine: the output (allocated, or `out` checked), hints, epilogue, workspace tensor, the C call of the entry and the
+// three checks on its return code.
+struct InvariantRouting { // the MoE entries' part of a call
+    const at::Tensor &off;
+    int64_t e;
+    const std::optional<at::Tensor> &a_idx, &c_idx;
+    int64_t a_rows, c_rows;
+    const at::Tensor *out;
+};
+// act_format: 8 / 6 / 4 on the native class (then `quantized` says what A is, and st names the 16-bit type of c and the bias), 0 on the exact
+at::Tensor invariant_call(const char *name, bool mx, int64_t act_format, bool quantized, at::ScalarType st, const at::Tensor &A, const at::Tensor &B,
+                          const at::Tensor &s, const float *gs, int64_t m, int64_t n, int64_t k, const std::optional<at::Tensor> &bias,
+                          int64_t activation, const InvariantRouting *r) {
+    const bool native = act_format != 0;
+    const int64_t n_out = activation ? n / 2 : n;
+    const c10::hip::HIPGuardMasqueradingAsCUDA guard(A.device());
+    at::Tensor c;
+    int64_t c_rows = m;
+    if (r && r->out) {
+        const at::Tensor *out = r->out;
+        TORCH_CHECK(out->is_cuda() && out->device() == A.device() && out->scalar_type() == st && out->is_contiguous() && out->dim() == 2 &&
+                        out->size(1) == n_out,
+                    "out must be a contiguous [c_rows, n_out] tensor of A's dtype on A's device");
+        TORCH_CHECK(r->c_rows < 0 || r->c_rows == out->size(0), "c_rows does not match out.size(0)");
+        c = *out;
+        c_rows = out->size(0);
+    } else {
+        c_rows = r && r->c_rows >= 0 ? r->c_rows : m;
+        c = at::empty({c_rows, n_out}, A.options().dtype(st));
+    }
+    const int a_type = a_type_of(st), b_type = mx ? kCxxMxFp4 : kCxxFp4, fmt = (int)act_format, q = quantized ? 1 : 0;
+    const unsigned um = (unsigned)m, un = (unsigned)n, uk = (unsigned)k, ue = r ? (unsigned)r->e : 0u;
+    const petit_solution_hints hints{a_type, b_type, a_type, 0};
+    const petit_epilogue epi{bias.has_value() ? bias->data_ptr() : nullptr, (int32_t)activation, 0};
+    const petit_epilogue *const pe = (bias.has_value() || activation) ? &epi : nullptr;
+    const uint64_t ws_bytes = native ? (r ? petit_gemm_native_moe_invariant_workspace_bytes(ue, um, un, uk, a_type, fmt, q)
+                                          : petit_gemm_native_invariant_workspace_bytes(um, un, uk, a_type, fmt, q))
+                                     : (r ? petit_gemm_moe_invariant_workspace_bytes(ue, um, un, uk, a_type, b_type)
+                                          : petit_gemm_invariant_workspace_bytes(um, un, uk, a_type, b_type));
+    at::Tensor ws;
+    if (ws_bytes)
+        ws = at::empty({(int64_t)ws_bytes}, A.options().dtype(at::kByte));
+    void *const w = ws_bytes ? ws.data_ptr() : nullptr, *const stream = stream_of(A);
+    int rc;
+    if (!r && !native)
+        rc = (mx ? petit_gemm_mxfp4_fp16_invariant : petit_gemm_fp4_fp16_invariant)(c.data_ptr(), A.data_ptr(), B.data_ptr(), s.data_ptr(), gs, um, un,
+                                                                                   uk, &hints, pe, w, stream);
+    else if (!r)
+        rc = petit_gemm_mxfp4_native_invariant(c.data_ptr(), A.data_ptr(), B.data_ptr(), s.data_ptr(), gs, um, un, uk, &hints, fmt, q, pe, w, stream);
+    else if (!native)
+        rc = (mx ? petit_gemm_mxfp4_fp16_moe_invariant : petit_gemm_fp4_fp16_moe_invariant)(
+            c.data_ptr(), A.data_ptr(), B.data_ptr(), s.data_ptr(), gs, (const int32_t *)r->off.data_ptr(), ue, um, un, uk, row_index_ptr(r->a_idx),
+            (unsigned)r->a_rows, row_index_ptr(r->c_idx), (unsigned)c_rows, &hints, pe, w, stream);
+    else
+        rc = petit_gemm_mxfp4_native_moe_invariant(c.data_ptr(), A.data_ptr(), B.data_ptr(), s.data_ptr(), gs, (const int32_t *)r->off.data_ptr(), ue, um,
+                                                   un, uk, row_index_ptr(r->a_idx), (unsigned)r->a_rows, row_index_ptr(r->c_idx), (unsigned)c_rows,
+                                                   &hints, fmt, q, pe, w, stream);
+    TORCH_CHECK(rc != PETIT_ERROR_PROBLEM_SHAPE, "Incompatible problem shape (m=", m, ", n=", n, ", k=", k,
+                r ? c10::str(", num_experts=", r->e, ", a_rows=", r->a_rows, ", c_rows=", c_rows) : std::string(), ")");
+    TORCH_CHECK(rc != PETIT_ERROR_KERNEL_SHAPE,
+                native ? "No kernel implementation for solution_id=native-invariant." : "No batch-invariant kernel for these types.");
+    TORCH_CHECK(rc == PETIT_OK, name, ": ", petit_error_string(rc));
+    return c;
+}
+
 #define PETIT_INVARIANT_ARGS                                                                                                                   \
     const at::Tensor &A, const at::Tensor &B, const at::Tensor &s, const std::optional<at::Tensor> &global_scale, int64_t size_m, int64_t size_n, \
         int64_t size_k, const std::optional<at::Tensor> &bias, int64_t activation
@@ -271,31 +336,14 @@ at::Tensor mul_a16_invariant(bool mx, PETIT_INVARIANT_ARGS) {
                 "tensor on it");
     check_activation(activation, size_n);
     check_bias(bias, A, A.scalar_type(), size_n, "bias must be a contiguous [size_n] tensor of A's dtype on A's device");
-    const c10::hip::HIPGuardMasqueradingAsCUDA guard(A.device());
-    at::Tensor c = at::empty({size_m, activation ? size_n / 2 : size_n}, A.options());
-    const int a_type = a_type_of(A.scalar_type()), b_type = mx ? kCxxMxFp4 : kCxxFp4;
-    const petit_solution_hints hints{a_type, b_type, a_type, 0};
-    const petit_epilogue epi{bias.has_value() ? bias->data_ptr() : nullptr, (int32_t)activation, 0};
-    const uint64_t ws_bytes = petit_gemm_invariant_workspace_bytes((unsigned)size_m, (unsigned)size_n, (unsigned)size_k, a_type, b_type);
-    at::Tensor ws;
-    if (ws_bytes)
-        ws = at::empty({(int64_t)ws_bytes}, A.options().dtype(at::kByte));
-    auto fn = mx ? petit_gemm_mxfp4_fp16_invariant : petit_gemm_fp4_fp16_invariant;
-    const int rc = fn(c.data_ptr(), A.data_ptr(), B.data_ptr(), s.data_ptr(), global_scale ? (const float *)global_scale->data_ptr() : nullptr,
-                      (unsigned)size_m, (unsigned)size_n, (unsigned)size_k, &hints, (bias.has_value() || activation) ? &epi : nullptr,
-                      ws_bytes ? ws.data_ptr() : nullptr, stream_of(A));
-    TORCH_CHECK(rc != PETIT_ERROR_PROBLEM_SHAPE, "Incompatible problem shape (m=", size_m, ", n=", size_n, ", k=", size_k, ")");
-    TORCH_CHECK(rc != PETIT_ERROR_KERNEL_SHAPE, "No batch-invariant kernel for these types.");
-    TORCH_CHECK(rc == PETIT_OK, mx ? "mul_mxfp4_a16_invariant" : "mul_nvfp4_a16_invariant", ": ", petit_error_string(rc));
-    return c;
+    return invariant_call(mx ? "mul_mxfp4_a16_invariant" : "mul_nvfp4_a16_invariant", mx, 0, false, A.scalar_type(), A, B, s,
+                          global_scale ? (const float *)global_scale->data_ptr() : nullptr, size_m, size_n, size_k, bias, activation, nullptr);
 }
 at::Tensor mul_nvfp4_a16_invariant(PETIT_INVARIANT_ARGS) { return mul_a16_invariant(false, A, B, s, global_scale, size_m, size_n, size_k, bias, activation); }
 at::Tensor mul_mxfp4_a16_invariant(PETIT_INVARIANT_ARGS) { return mul_a16_invariant(true, A, B, s, global_scale, size_m, size_n, size_k, bias, activation); }
 
-// the batch-invariant GEMM on the native class (petit_gemm_mxfp4_native_invariant).  A is the 16-bit matrix, or (quantized) the "petit-qact/1"
-// bytes of act_format -- then bf16 names the 16-bit type of c and the bias.  The argument checks and their texts are stated once, in
-// petit_kernel/ops.py (_check_native_invariant), which petit_kernel/compiled.py runs in front of this op; what is checked here is what keeps a
-// direct torch.ops call inside its tensors.
+// on the native class A is the 16-bit matrix, or (quantized) the "petit-qact/1" bytes of act_format -- then bf16 names the 16-bit type of c
+// and the bias
 #define PETIT_NATIVE_INVARIANT_ARGS                                                                                                            \
     const at::Tensor &A, const at::Tensor &B, const at::Tensor &s, const std::optional<at::Tensor> &global_scale, int64_t size_m, int64_t size_n, \
         int64_t size_k, int64_t act_format, bool quantized, bool bf16, const std::optional<at::Tensor> &bias, int64_t activation
@@ -313,25 +361,8 @@ at::Tensor mul_mxfp4_native_invariant(PETIT_NATIVE_INVARIANT_ARGS) {
                 "device, global_scale a float32 tensor on it");
     TORCH_CHECK(activation >= 0 && activation <= 2 && (!activation || size_n % 64 == 0), "activation must be 0, 1 or 2; gated forms need size_n % 64 == 0");
     check_bias(bias, A, st, size_n, "bias must be a contiguous [size_n] tensor of A's dtype on A's device");
-    const c10::hip::HIPGuardMasqueradingAsCUDA guard(A.device());
-    at::Tensor c = at::empty({size_m, activation ? size_n / 2 : size_n}, A.options().dtype(st));
-    const int a_type = a_type_of(st);
-    const petit_solution_hints hints{a_type, kCxxMxFp4, a_type, 0};
-    const petit_epilogue epi{bias.has_value() ? bias->data_ptr() : nullptr, (int32_t)activation, 0};
-    const uint64_t ws_bytes = petit_gemm_native_invariant_workspace_bytes((unsigned)size_m, (unsigned)size_n, (unsigned)size_k, a_type,
-                                                                          (int)act_format, quantized ? 1 : 0);
-    at::Tensor ws;
-    if (ws_bytes)
-        ws = at::empty({(int64_t)ws_bytes}, A.options().dtype(at::kByte));
-    const int rc = petit_gemm_mxfp4_native_invariant(c.data_ptr(), A.data_ptr(), B.data_ptr(), s.data_ptr(),
-                                                     global_scale ? (const float *)global_scale->data_ptr() : nullptr, (unsigned)size_m,
-                                                     (unsigned)size_n, (unsigned)size_k, &hints, (int)act_format, quantized ? 1 : 0,
-                                                     (bias.has_value() || activation) ? &epi : nullptr, ws_bytes ? ws.data_ptr() : nullptr,
-                                                     stream_of(A));
-    TORCH_CHECK(rc != PETIT_ERROR_PROBLEM_SHAPE, "Incompatible problem shape (m=", size_m, ", n=", size_n, ", k=", size_k, ")");
-    TORCH_CHECK(rc != PETIT_ERROR_KERNEL_SHAPE, "No kernel implementation for solution_id=native-invariant.");
-    TORCH_CHECK(rc == PETIT_OK, "mul_mxfp4_native_invariant: ", petit_error_string(rc));
-    return c;
+    return invariant_call("mul_mxfp4_native_invariant", true, act_format, quantized, st, A, B, s,
+                          global_scale ? (const float *)global_scale->data_ptr() : nullptr, size_m, size_n, size_k, bias, activation, nullptr);
 }
 
 // routed-expert (MoE) launch: all experts in one call (include/petit_amd.h); the same checks and texts as petit_kernel/ops.py _mul_moe
@@ -424,9 +455,7 @@ void mul_mxfp4_a16_moe_indexed_out(const at::Tensor &out, PETIT_MOE_INDEXED_ARGS
     mul_a16_moe_indexed_impl(true, A, B, s, gs, off, m, n, k, e, a_idx, c_idx, c_rows, solution_id, bias, activation, &out);
 }
 
-// the batch-invariant MoE launch (petit_gemm_{fp4,mxfp4}_fp16_moe_invariant): the indexed launch's arguments without a solution id.  The
-// argument checks and their texts are stated once, in petit_kernel/ops.py (_check_moe_invariant), which petit_kernel/compiled.py runs in front
-// of these ops; what is checked here is what keeps a direct torch.ops call inside its tensors.
+// the batch-invariant MoE launch (petit_gemm_{fp4,mxfp4}_fp16_moe_invariant): the indexed launch's arguments without a solution id
 #define PETIT_MOE_INVARIANT_ARGS                                                                                                                 \
     const at::Tensor &A, const at::Tensor &B, const at::Tensor &s, const at::Tensor &gs, const at::Tensor &off, int64_t m, int64_t n, int64_t k, \
         int64_t e, const std::optional<at::Tensor> &a_idx, const std::optional<at::Tensor> &c_idx, int64_t c_rows,                               \
@@ -438,36 +467,9 @@ at::Tensor mul_a16_moe_invariant_impl(bool mx, PETIT_MOE_INVARIANT_ARGS, const a
     check_row_indices(a_idx, c_idx, A, m);
     check_activation(activation, n);
     check_bias(bias, A, A.scalar_type(), e * n, "bias must be a contiguous [num_experts, size_n] tensor of A's dtype on A's device");
-    const int64_t a_rows = A.numel() / k, n_out = activation ? n / 2 : n;
-    const c10::hip::HIPGuardMasqueradingAsCUDA guard(A.device());
-    at::Tensor c;
-    if (out) {
-        TORCH_CHECK(out->is_cuda() && out->device() == A.device() && out->scalar_type() == A.scalar_type() && out->is_contiguous() && out->dim() == 2 &&
-                        out->size(1) == n_out,
-                    "out must be a contiguous [c_rows, n_out] tensor of A's dtype on A's device");
-        TORCH_CHECK(c_rows < 0 || c_rows == out->size(0), "c_rows does not match out.size(0)");
-        c = *out;
-        c_rows = out->size(0);
-    } else {
-        c_rows = c_rows < 0 ? m : c_rows;
-        c = at::empty({c_rows, n_out}, A.options());
-    }
-    const int a_type = a_type_of(A.scalar_type()), b_type = mx ? kCxxMxFp4 : kCxxFp4;
-    const petit_solution_hints hints{a_type, b_type, a_type, 0};
-    const petit_epilogue epi{bias.has_value() ? bias->data_ptr() : nullptr, (int32_t)activation, 0};
-    const uint64_t ws_bytes = petit_gemm_moe_invariant_workspace_bytes((unsigned)e, (unsigned)m, (unsigned)n, (unsigned)k, a_type, b_type);
-    at::Tensor ws;
-    if (ws_bytes)
-        ws = at::empty({(int64_t)ws_bytes}, A.options().dtype(at::kByte));
-    auto fn = mx ? petit_gemm_mxfp4_fp16_moe_invariant : petit_gemm_fp4_fp16_moe_invariant;
-    const int rc = fn(c.data_ptr(), A.data_ptr(), B.data_ptr(), s.data_ptr(), (const float *)gs.data_ptr(), (const int32_t *)off.data_ptr(),
-                      (unsigned)e, (unsigned)m, (unsigned)n, (unsigned)k, row_index_ptr(a_idx), (unsigned)a_rows, row_index_ptr(c_idx),
-                      (unsigned)c_rows, &hints, (bias.has_value() || activation) ? &epi : nullptr, ws_bytes ? ws.data_ptr() : nullptr, stream_of(A));
-    TORCH_CHECK(rc != PETIT_ERROR_PROBLEM_SHAPE, "Incompatible problem shape (m=", m, ", n=", n, ", k=", k, ", num_experts=", e, ", a_rows=", a_rows,
-                ", c_rows=", c_rows, ")");
-    TORCH_CHECK(rc != PETIT_ERROR_KERNEL_SHAPE, "No batch-invariant kernel for these types.");
-    TORCH_CHECK(rc == PETIT_OK, mx ? "mul_mxfp4_a16_moe_invariant" : "mul_nvfp4_a16_moe_invariant", ": ", petit_error_string(rc));
-    return c;
+    const InvariantRouting r{off, e, a_idx, c_idx, A.numel() / k, c_rows, out};
+    return invariant_call(mx ? "mul_mxfp4_a16_moe_invariant" : "mul_nvfp4_a16_moe_invariant", mx, 0, false, A.scalar_type(), A, B, s,
+                          (const float *)gs.data_ptr(), m, n, k, bias, activation, &r);
 }
 #define PETIT_MOE_INVARIANT_PASS A, B, s, gs, off, m, n, k, e, a_idx, c_idx, c_rows, bias, activation
 at::Tensor mul_nvfp4_a16_moe_invariant(PETIT_MOE_INVARIANT_ARGS) { return mul_a16_moe_invariant_impl(false, PETIT_MOE_INVARIANT_PASS, nullptr); }
@@ -476,9 +478,7 @@ void mul_nvfp4_a16_moe_invariant_out(const at::Tensor &out, PETIT_MOE_INVARIANT_
 void mul_mxfp4_a16_moe_invariant_out(const at::Tensor &out, PETIT_MOE_INVARIANT_ARGS) { mul_a16_moe_invariant_impl(true, PETIT_MOE_INVARIANT_PASS, &out); }
 
 // the batch-invariant MoE launch on the native class (petit_gemm_mxfp4_native_moe_invariant).  A is the 16-bit [a_rows, k] matrix, or
-// (quantized) the "petit-qact/1" bytes of the m grouped rows -- then bf16 names the 16-bit type of c and the bias.  The argument checks and
-// their texts are stated once, in petit_kernel/ops.py (_check_native_moe_invariant), which petit_kernel/compiled.py runs in front of this op;
-// what is checked here is what keeps a direct torch.ops call inside its tensors.
+// (quantized) the "petit-qact/1" bytes of the m grouped rows -- then bf16 names the 16-bit type of c and the bias
 #define PETIT_NATIVE_MOE_INVARIANT_ARGS                                                                                                          \
     const at::Tensor &A, const at::Tensor &B, const at::Tensor &s, const at::Tensor &gs, const at::Tensor &off, int64_t m, int64_t n, int64_t k, \
         int64_t e, const std::optional<at::Tensor> &a_idx, const std::optional<at::Tensor> &c_idx, int64_t c_rows, int64_t act_format,           \
@@ -494,27 +494,9 @@ at::Tensor mul_mxfp4_native_moe_invariant(PETIT_NATIVE_MOE_INVARIANT_ARGS) {
     check_row_indices(a_idx, c_idx, A, m);
     TORCH_CHECK(activation >= 0 && activation <= 2 && (!activation || n % 64 == 0), "activation must be 0, 1 or 2; gated forms need size_n % 64 == 0");
     check_bias(bias, A, st, e * n, "bias must be a contiguous [num_experts, size_n] tensor of A's dtype on A's device");
-    const int64_t a_rows = quantized ? m : A.numel() / k, n_out = activation ? n / 2 : n;
-    const c10::hip::HIPGuardMasqueradingAsCUDA guard(A.device());
-    c_rows = c_rows < 0 ? m : c_rows;
-    at::Tensor c = at::empty({c_rows, n_out}, A.options().dtype(st));
-    const int a_type = a_type_of(st);
-    const petit_solution_hints hints{a_type, kCxxMxFp4, a_type, 0};
-    const petit_epilogue epi{bias.has_value() ? bias->data_ptr() : nullptr, (int32_t)activation, 0};
-    const uint64_t ws_bytes = petit_gemm_native_moe_invariant_workspace_bytes((unsigned)e, (unsigned)m, (unsigned)n, (unsigned)k, a_type,
-                                                                              (int)act_format, quantized ? 1 : 0);
-    at::Tensor ws;
-    if (ws_bytes)
-        ws = at::empty({(int64_t)ws_bytes}, A.options().dtype(at::kByte));
-    const int rc = petit_gemm_mxfp4_native_moe_invariant(
-        c.data_ptr(), A.data_ptr(), B.data_ptr(), s.data_ptr(), (const float *)gs.data_ptr(), (const int32_t *)off.data_ptr(), (unsigned)e, (unsigned)m,
-        (unsigned)n, (unsigned)k, row_index_ptr(a_idx), (unsigned)a_rows, row_index_ptr(c_idx), (unsigned)c_rows, &hints, (int)act_format,
-        quantized ? 1 : 0, (bias.has_value() || activation) ? &epi : nullptr, ws_bytes ? ws.data_ptr() : nullptr, stream_of(A));
-    TORCH_CHECK(rc != PETIT_ERROR_PROBLEM_SHAPE, "Incompatible problem shape (m=", m, ", n=", n, ", k=", k, ", num_experts=", e, ", a_rows=", a_rows,
-                ", c_rows=", c_rows, ")");
-    TORCH_CHECK(rc != PETIT_ERROR_KERNEL_SHAPE, "No kernel implementation for solution_id=native-invariant.");
-    TORCH_CHECK(rc == PETIT_OK, "mul_mxfp4_native_moe_invariant: ", petit_error_string(rc));
-    return c;
+    const InvariantRouting r{off, e, a_idx, c_idx, quantized ? m : A.numel() / k, c_rows, nullptr};
+    return invariant_call("mul_mxfp4_native_moe_invariant", true, act_format, quantized, st, A, B, s, (const float *)gs.data_ptr(), m, n, k, bias,
+                          activation, &r);
 }
 
 // device routing (petit_moe_align / petit_moe_combine); the same checks and texts as petit_kernel/ops.py

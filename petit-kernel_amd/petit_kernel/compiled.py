@@ -16,11 +16,10 @@ import torch
 from . import _lib  # loads libpetit_amd.so first (the binding links against it)
 from .ops import QuantizedActivations, _a_type, _activation as _act, _activation_operand, _quantized_format
 from .ops import _check_invariant, _check_route_hidden, _check_router, _combine_norm_operands, _combine_norm_returns
-from .ops import _check_moe_invariant
 from .ops import invariant_geometry, invariant_slabs, invariant_workspace_bytes  # (queries: plain C calls, no op behind them)
 from .ops import moe_invariant_form, moe_invariant_workspace_bytes
-from .ops import _QFORMATS, _check_native_invariant, native_invariant_slabs, native_invariant_workspace_bytes
-from .ops import _check_native_moe_invariant, native_moe_invariant_form, native_moe_invariant_workspace_bytes
+from .ops import _QFORMATS, native_invariant_slabs, native_invariant_workspace_bytes
+from .ops import native_moe_invariant_form, native_moe_invariant_workspace_bytes
 
 LIB_PATH = Path(_lib.LIB_PATH).parent / "libpetit_torch.so"
 _loaded = False
@@ -97,17 +96,17 @@ def mul_mxfp4_a16(A, B, s, global_scale, size_m, size_n, size_k, solution_id, bi
 
 
 def mul_nvfp4_a16_invariant(A, B, s, global_scale, size_m, size_n, size_k, bias=None, activation=None):
-    act = _check_invariant("nv", A, B, s, global_scale, size_m, size_n, size_k, bias, activation)
+    act = _check_invariant(A, B, s, global_scale, size_m, size_n, size_k, bias, activation, "nv")[3]
     return torch.ops.petit_kernel.mul_nvfp4_a16_invariant(A, B, s, global_scale, int(size_m), int(size_n), int(size_k), bias, act)
 
 
 def mul_mxfp4_a16_invariant(A, B, s, global_scale, size_m, size_n, size_k, bias=None, activation=None):
-    act = _check_invariant("mx", A, B, s, global_scale, size_m, size_n, size_k, bias, activation)
+    act = _check_invariant(A, B, s, global_scale, size_m, size_n, size_k, bias, activation, "mx")[3]
     return torch.ops.petit_kernel.mul_mxfp4_a16_invariant(A, B, s, global_scale, int(size_m), int(size_n), int(size_k), bias, act)
 
 
 def mul_mxfp4_native_invariant(A, B, s, global_scale, size_m, size_n, size_k, fmt="mxfp8", bias=None, activation=None):
-    a, dtype, quantized, act = _check_native_invariant(A, B, s, global_scale, size_m, size_n, size_k, fmt, bias, activation)
+    a, dtype, quantized, act = _check_invariant(A, B, s, global_scale, size_m, size_n, size_k, bias, activation, "mx", fmt)[:4]
     return torch.ops.petit_kernel.mul_mxfp4_native_invariant(a, B, s, global_scale, int(size_m), int(size_n), int(size_k), _QFORMATS[fmt],
                                                              bool(quantized), dtype == torch.bfloat16, bias, act)
 
@@ -147,8 +146,8 @@ def mul_mxfp4_a16_moe_indexed(A, B, s, global_scales, expert_offsets, size_m, si
 
 def _mul_moe_invariant(kind, A, B, s, global_scales, expert_offsets, size_m, size_n, size_k, num_experts, a_row_index, c_row_index, c_rows, bias,
                        activation, out):
-    E, act, _, c_rows = _check_moe_invariant(kind, A, B, s, global_scales, expert_offsets, size_m, size_n, size_k, num_experts, a_row_index,
-                                             c_row_index, c_rows, bias, activation, out)
+    _, _, _, act, E, _, c_rows = _check_invariant(A, B, s, global_scales, size_m, size_n, size_k, bias, activation, kind,
+                                                  experts=(expert_offsets, num_experts, a_row_index, c_row_index, c_rows, out))
     args = (A, B, s, global_scales, expert_offsets, int(size_m), int(size_n), int(size_k), E, a_row_index, c_row_index, int(c_rows), bias, act)
     if out is None:
         return getattr(torch.ops.petit_kernel, f"mul_{kind}fp4_a16_moe_invariant")(*args)
@@ -170,8 +169,8 @@ def mul_mxfp4_a16_moe_invariant(A, B, s, global_scales, expert_offsets, size_m, 
 
 def mul_mxfp4_native_moe_invariant(A, B, s, global_scales, expert_offsets, size_m, size_n, size_k, num_experts, a_row_index=None,
                                    c_row_index=None, c_rows=None, fmt="mxfp8", bias=None, activation=None):
-    a, dtype, quantized, E, act, _, c_rows = _check_native_moe_invariant(A, B, s, global_scales, expert_offsets, size_m, size_n, size_k,
-                                                                         num_experts, a_row_index, c_row_index, c_rows, fmt, bias, activation)
+    a, dtype, quantized, act, E, _, c_rows = _check_invariant(A, B, s, global_scales, size_m, size_n, size_k, bias, activation, "mx", fmt,
+                                                              (expert_offsets, num_experts, a_row_index, c_row_index, c_rows, None))
     return torch.ops.petit_kernel.mul_mxfp4_native_moe_invariant(a, B, s, global_scales, expert_offsets, int(size_m), int(size_n), int(size_k), E,
                                                                  a_row_index, c_row_index, int(c_rows), _QFORMATS[fmt], bool(quantized),
                                                                  dtype == torch.bfloat16, bias, act)

@@ -354,33 +354,140 @@ def mul_mxfp4_a16(A, B, s, global_scale, size_m, size_n, size_k, solution_id, bi
     return _mul("mx", A, B, s, global_scale, size_m, size_n, size_k, solution_id, bias, activation)
 
 
-# --- the batch-invariant GEMM (include/petit_amd.h "Batch-invariant GEMM"; no counterpart in the reference) ---------------------------------
+# --- the batch-invariant GEMM family (include/petit_amd.h "Batch-invariant GEMM", "Batch-invariant MoE launch" and their two "... on the native
+# class" sections; no counterpart in the reference): one check and one driver for the four entries ------------------------------------------
 
-def _check_invariant(kind: str, A, B, s, global_scale, size_m, size_n, size_k, bias, activation) -> int:
-    """The argument checks of mul_nvfp4_a16_invariant / mul_mxfp4_a16_invariant, stated here for both operator layers; returns the
-    activation code.  Value checks come first and device checks last, so that the texts can be read without a GPU."""
-    name = "mul_%sfp4_a16_invariant" % kind
-    _check(A.dtype in (torch.bfloat16, torch.float16), "A must be bfloat16 or float16.")
+def _invariant_name(kind: str, native: bool, moe: bool) -> str:
+    if native:
+        return "mul_mxfp4_native_moe_invariant" if moe else "mul_mxfp4_native_invariant"
+    return ("mul_%sfp4_a16_moe_invariant" if moe else "mul_%sfp4_a16_invariant") % kind
+
+
+_INVARIANT_BIAS_TEXT = {False: "bias must be a contiguous [size_n] tensor of A's dtype on A's device",
+                        True: "bias must be a contiguous [num_experts, size_n] tensor of A's dtype on A's device"}  # by `moe`
+
+
+def _check_invariant(A, B, s, global_scale, size_m, size_n, size_k, bias, activation, kind="mx", fmt=None, experts=None):
+    """The argument checks of the four batch-invariant entries, stated here for both operator layers.  kind: the weight format, 'nv' / 'mx';
+    fmt: the native class's activation format (None: the exact class); experts: (expert_offsets, num_experts, a_row_index, c_row_index,
+    c_rows, out) of a MoE call, whose global_scale is the [num_experts] tensor (None: a dense call).
+    -> (activation tensor, 16-bit dtype, a_is_quantized, activation code, E, a_rows, c_rows), the last three None for a dense call.
+    Value checks come first and device checks last, so that the texts can be read without a GPU.  The order within an entry decides which
+    text an ill-formed call gets, and is each entry's own."""
+    native, moe = fmt is not None, experts is not None
+    name = _invariant_name(kind, native, moe)
+    if native:
+        _check(fmt in _QFORMATS, "fmt must be 'mxfp8', 'mxfp6' or 'mxfp4'")
+    quantized = native and isinstance(A, QuantizedActivations)
+    dtype = A.dtype
+    _check(dtype in (torch.bfloat16, torch.float16),
+           "A must be bfloat16 or float16 (or QuantizedActivations of such a tensor)." if native else "A must be bfloat16 or float16.")
     size_m, size_n, size_k = int(size_m), int(size_n), int(size_k)
-    _check(size_n > 0 and size_n % 16 == 0 and size_k > 0 and size_k % 256 == 0 and 0 <= size_m < 1 << 20,
-           f"Incompatible problem shape (m={size_m}, n={size_n}, k={size_k}): {name} needs n % 16 == 0, k % 256 == 0, m < 2^20")
-    _check(not (kind == "mx" and A.dtype == torch.float16),
-           f"{name}: float16 activations with MXFP4 weights have no batch-invariant kernel (use bfloat16)")
-    act = _activation(activation, size_n)
-    _check(A.is_contiguous() and A.numel() == size_m * size_k, "A must be a contiguous [size_m, size_k] tensor")
-    _check(B.is_contiguous() and B.numel() * B.element_size() == size_n * size_k // 2, "B does not hold size_n * size_k packed 4-bit weights")
+    E = a_rows = c_rows = None
+    if moe:
+        expert_offsets, num_experts, a_row_index, c_row_index, c_rows, out = experts
+        E = int(num_experts)
+        if not 1 <= E <= _lib.PETIT_MOE_MAX_EXPERTS:  # (this is the per-call path of a decode step: the longer texts are built when raised)
+            _check(False, f"num_experts must be in 1..{_lib.PETIT_MOE_MAX_EXPERTS}, got {E}")
+    # (the exact dense entry accepts n % 16 for both kinds: MXFP4's n % 32 is its C return code's)
+    n_mult = 32 if native or (moe and kind == "mx") else 16
+    if not (size_n > 0 and size_n % n_mult == 0 and size_k > 0 and size_k % 256 == 0 and 0 <= size_m < 1 << 20):
+        _check(False, f"Incompatible problem shape (m={size_m}, n={size_n}, k={size_k}): {name} needs n % {n_mult} == 0, k % 256 == 0, m < 2^20")
+    if native:
+        _check(activation in _ACTIVATIONS, _ACTIVATION_RULE)
+        act = _ACTIVATIONS[activation]
+        _check(not act or size_n % 64 == 0, f"{activation} needs size_n % 64 == 0 here (gate / up halves of whole tile pairs), got {size_n}")
+    else:
+        _check(not (kind == "mx" and dtype == torch.float16),
+               f"{name}: float16 activations with MXFP4 weights have no batch-invariant kernel (use bfloat16)")
+        act = _activation(activation, size_n)
+    # the activation operand: quantised bytes of the [size_m, size_k] rows, a 16-bit [a_rows, size_k] matrix (MoE), or [size_m, size_k]
+    if quantized:
+        _check(A.fmt == fmt, f"quantised activations are {A.fmt}, the call says fmt={fmt!r}")
+        _check(A.m == size_m and A.k == size_k, f"quantised activations are [{A.m}, {A.k}], the call says [{size_m}, {size_k}]")
+        if moe:
+            _check(a_row_index is None, f"{name}: quantised activations are the grouped rows already; a_row_index must be None")
+        a, a_rows = A.data, size_m
+        _check(a.dtype == torch.uint8 and a.is_contiguous() and a.numel() == size_m * (size_k // 8 * _QFORMATS[fmt]) + size_m * (size_k // 32),
+               "quantised activations do not hold the bytes of their [m, k] and format")
+    elif moe:
+        a = A
+        _check(a.is_contiguous() and a.numel() % size_k == 0, "A must be a contiguous [a_rows, size_k] tensor")
+        a_rows = a.numel() // size_k
+        if not native:
+            _check(a_rows * size_k * 2 <= 1 << 31, f"{name}: A holds more than 2^31 bytes (a_rows={a_rows}, k={size_k})")
+    else:
+        a = A
+        if native:
+            _check(size_m <= 65535, f"{name}: a 16-bit A of more than 65535 rows must be quantised first (quantize_activations in pieces)")
+        _check(a.is_contiguous() and a.numel() == size_m * size_k, "A must be a contiguous [size_m, size_k] tensor")
+    # weights and scales, of num_experts matrices back to back in a MoE call
+    count, what = (E, "num_experts * ") if moe else (1, "")
     group = 16 if kind == "nv" else 32
-    _check(s.is_contiguous() and s.numel() * s.element_size() == size_n * size_k // group,
-           f"s does not hold size_n * size_k / {group} scales")
-    if global_scale is not None:
+    _check(B.is_contiguous() and B.numel() * B.element_size() == count * size_n * size_k // 2,
+           f"B does not hold {what}size_n * size_k packed 4-bit weights")
+    _check(s.is_contiguous() and s.numel() * s.element_size() == count * size_n * size_k // group,
+           f"s does not hold {what}size_n * size_k / {group} scales")
+    if moe:
+        _check(global_scale.dtype == torch.float32 and global_scale.is_contiguous() and global_scale.numel() == E,
+               "global_scales must be a contiguous float32 [num_experts] tensor")
+        _check(expert_offsets.dtype == torch.int32 and expert_offsets.is_contiguous() and expert_offsets.numel() == E + 1,
+               "expert_offsets must be a contiguous int32 [num_experts + 1] tensor")
+        for idx in (a_row_index, c_row_index):
+            if idx is not None:
+                _check(idx.dtype == torch.int32 and idx.is_contiguous() and idx.numel() == size_m and idx.device == a.device,
+                       "row indices must be contiguous int32 [size_m] tensors on A's device")
+        if out is not None:
+            _check(out.device == a.device and out.dtype == dtype and out.is_contiguous() and out.dim() == 2 and
+                   out.size(1) == (size_n // 2 if act else size_n), "out must be a contiguous [c_rows, n_out] tensor of A's dtype on A's device")
+            _check(c_rows is None or c_rows < 0 or c_rows == out.size(0), "c_rows does not match out.size(0)")
+            c_rows = out.size(0)
+        else:
+            c_rows = size_m if c_rows is None or c_rows < 0 else int(c_rows)
+        if not ((a_row_index is not None or a_rows >= size_m) and (c_row_index is not None or c_rows >= size_m)):
+            _check(False, f"{name}: without a row index the matrix must hold size_m rows (a_rows={a_rows}, c_rows={c_rows}, m={size_m})")
+    elif global_scale is not None:
         _check(global_scale.dtype == torch.float32 and global_scale.numel() >= 1, "global_scale must be float32")
     if bias is not None:
-        _check(bias.dtype == A.dtype and bias.is_contiguous() and bias.numel() == size_n and bias.device == A.device,
-               "bias must be a contiguous [size_n] tensor of A's dtype on A's device")
-    _check(A.is_cuda and B.is_cuda and s.is_cuda and (global_scale is None or global_scale.is_cuda), "all tensors must be on GPU")
-    _check(B.device == A.device and s.device == A.device and (global_scale is None or global_scale.device == A.device),
-           "all tensors must be on A's device")
-    return act
+        _check(bias.dtype == dtype and bias.is_contiguous() and bias.numel() == count * size_n and bias.device == a.device, _INVARIANT_BIAS_TEXT[moe])
+    dev = a.device
+    _check(a.is_cuda and B.is_cuda and s.is_cuda and (global_scale is None or global_scale.is_cuda) and (not moe or expert_offsets.is_cuda),
+           "all tensors must be on GPU")
+    _check(B.device == dev and s.device == dev and (global_scale is None or global_scale.device == dev) and
+           (not moe or expert_offsets.device == dev), "all tensors must be on A's device")
+    return a, dtype, int(quantized), act, E, a_rows, c_rows
+
+
+def _mul_invariant(A, B, s, global_scale, size_m, size_n, size_k, bias, activation, kind="mx", fmt=None, experts=None) -> torch.Tensor:
+    """One call of any of the four entries (the arguments of _check_invariant): output, hints, epilogue, workspace, the C call, the raise."""
+    a, dtype, quantized, act, E, a_rows, c_rows = _check_invariant(A, B, s, global_scale, size_m, size_n, size_k, bias, activation, kind, fmt,
+                                                                   experts)
+    native, moe, shape = fmt is not None, experts is not None, (int(size_m), int(size_n), int(size_k))
+    lib = _lib.lib  # (plain attribute reads: this is the per-call path of a decode step)
+    if native:
+        fn, ws_fn = ((lib.petit_gemm_mxfp4_native_moe_invariant, lib.petit_gemm_native_moe_invariant_workspace_bytes) if moe else
+                     (lib.petit_gemm_mxfp4_native_invariant, lib.petit_gemm_native_invariant_workspace_bytes))
+    elif moe:
+        fn = lib.petit_gemm_fp4_fp16_moe_invariant if kind == "nv" else lib.petit_gemm_mxfp4_fp16_moe_invariant
+        ws_fn = lib.petit_gemm_moe_invariant_workspace_bytes
+    else:
+        fn = lib.petit_gemm_fp4_fp16_invariant if kind == "nv" else lib.petit_gemm_mxfp4_fp16_invariant
+        ws_fn = lib.petit_gemm_invariant_workspace_bytes
+    out = experts[5] if moe else None
+    if out is None:
+        out = torch.empty((c_rows if moe else shape[0], shape[1] // 2 if act else shape[1]), dtype=dtype, device=a.device)
+    hints = _hints(kind, dtype)
+    epi = _epilogue(bias, act, a.device, dtype, (E if moe else 1) * shape[1], _INVARIANT_BIAS_TEXT[moe])
+    form = (_QFORMATS[fmt], quantized) if native else ()
+    ws = _scratch(int(ws_fn(*((E,) if moe else ()), *shape, hints.a_type, *(form or (hints.b_type,)))), a.device)
+    routing = ((_ptr(experts[0]), E), (_opt_ptr(experts[2]), a_rows, _opt_ptr(experts[3]), c_rows)) if moe else ((), ())
+    with torch.cuda.device(a.device):
+        err = fn(_ptr(out), _ptr(a), _ptr(B), _ptr(s), _opt_ptr(global_scale), *routing[0], *shape, *routing[1], C.byref(hints), *form, epi,
+                 _opt_ptr(ws), _stream(a))
+    if err:
+        where = "m=%d, n=%d, k=%d" % shape + (f", num_experts={E}, a_rows={a_rows}, c_rows={c_rows}" if moe else "")
+        _raise_gemm(err, _invariant_name(kind, native, moe), "native-invariant" if native else "invariant", where)
+    return out
 
 
 def invariant_geometry(size_n: int, size_k: int, dtype: torch.dtype = torch.bfloat16, kind: str = "nvfp4"):
@@ -402,30 +509,15 @@ def invariant_workspace_bytes(size_m: int, size_n: int, size_k: int, dtype: torc
     return int(_lib.lib.petit_gemm_invariant_workspace_bytes(int(size_m), int(size_n), int(size_k), _a_type(dtype), _B_TYPES[kind]))
 
 
-def _mul_invariant(kind: str, A, B, s, global_scale, size_m, size_n, size_k, bias, activation) -> torch.Tensor:
-    act = _check_invariant(kind, A, B, s, global_scale, size_m, size_n, size_k, bias, activation)
-    size_m, size_n, size_k = int(size_m), int(size_n), int(size_k)
-    c = torch.empty((size_m, size_n // 2 if act else size_n), dtype=A.dtype, device=A.device)
-    hints = _hints(kind, A.dtype)
-    epi = _epilogue(bias, act, A.device, A.dtype, size_n, "bias must be a contiguous [size_n] tensor of A's dtype on A's device")
-    ws = _scratch(int(_lib.lib.petit_gemm_invariant_workspace_bytes(size_m, size_n, size_k, hints.a_type, hints.b_type)), A.device)
-    fn = _lib.lib.petit_gemm_fp4_fp16_invariant if kind == "nv" else _lib.lib.petit_gemm_mxfp4_fp16_invariant
-    with torch.cuda.device(A.device):
-        err = fn(_ptr(c), _ptr(A), _ptr(B), _ptr(s), _opt_ptr(global_scale), size_m, size_n, size_k, C.byref(hints), epi, _opt_ptr(ws), _stream(A))
-    if err:
-        _raise_gemm(err, "mul_%sfp4_a16_invariant" % kind, "invariant", f"m={size_m}, n={size_n}, k={size_k}")
-    return c
-
-
 def mul_nvfp4_a16_invariant(A, B, s, global_scale, size_m, size_n, size_k, bias=None, activation=None) -> torch.Tensor:
     """mul_nvfp4_a16 by the batch-invariant entry (petit_gemm_fp4_fp16_invariant, include/petit_amd.h "Batch-invariant GEMM"): a row's result
     does not depend on size_m, on the row's position or on the launch form.  Opt-in and slower than the default pick; no solution_id."""
-    return _mul_invariant("nv", A, B, s, global_scale, size_m, size_n, size_k, bias, activation)
+    return _mul_invariant(A, B, s, global_scale, size_m, size_n, size_k, bias, activation, "nv")
 
 
 def mul_mxfp4_a16_invariant(A, B, s, global_scale, size_m, size_n, size_k, bias=None, activation=None) -> torch.Tensor:
     """mul_mxfp4_a16 by the batch-invariant entry (petit_gemm_mxfp4_fp16_invariant); bfloat16 activations only."""
-    return _mul_invariant("mx", A, B, s, global_scale, size_m, size_n, size_k, bias, activation)
+    return _mul_invariant(A, B, s, global_scale, size_m, size_n, size_k, bias, activation, "mx")
 
 
 def get_fp4_solutions(*args) -> list:
@@ -648,43 +740,6 @@ def _activation_operand(A, size_m: int, size_k: int):
 
 # --- the batch-invariant GEMM on the native class (include/petit_amd.h "Batch-invariant GEMM on the native class") -------------------------
 
-def _check_native_invariant(A, B, s, global_scale, size_m, size_n, size_k, fmt, bias, activation):
-    """The argument checks of mul_mxfp4_native_invariant, stated here for both operator layers -> (activation tensor, 16-bit dtype,
-    a_is_quantized, activation code).  Value checks come first and device checks last, so that the texts can be read without a GPU."""
-    name = "mul_mxfp4_native_invariant"
-    _check(fmt in _QFORMATS, "fmt must be 'mxfp8', 'mxfp6' or 'mxfp4'")
-    quantized = isinstance(A, QuantizedActivations)
-    dtype = A.dtype
-    _check(dtype in (torch.bfloat16, torch.float16), "A must be bfloat16 or float16 (or QuantizedActivations of such a tensor).")
-    size_m, size_n, size_k = int(size_m), int(size_n), int(size_k)
-    _check(size_n > 0 and size_n % 32 == 0 and size_k > 0 and size_k % 256 == 0 and 0 <= size_m < 1 << 20,
-           f"Incompatible problem shape (m={size_m}, n={size_n}, k={size_k}): {name} needs n % 32 == 0, k % 256 == 0, m < 2^20")
-    _check(activation in _ACTIVATIONS, _ACTIVATION_RULE)
-    act = _ACTIVATIONS[activation]
-    _check(not act or size_n % 64 == 0, f"{activation} needs size_n % 64 == 0 here (gate / up halves of whole tile pairs), got {size_n}")
-    if quantized:
-        _check(A.fmt == fmt, f"quantised activations are {A.fmt}, the call says fmt={fmt!r}")
-        _check(A.m == size_m and A.k == size_k, f"quantised activations are [{A.m}, {A.k}], the call says [{size_m}, {size_k}]")
-        a = A.data
-        _check(a.dtype == torch.uint8 and a.is_contiguous() and a.numel() == size_m * (size_k // 8 * _QFORMATS[fmt]) + size_m * (size_k // 32),
-               "quantised activations do not hold the bytes of their [m, k] and format")
-    else:
-        a = A
-        _check(size_m <= 65535, f"{name}: a 16-bit A of more than 65535 rows must be quantised first (quantize_activations in pieces)")
-        _check(a.is_contiguous() and a.numel() == size_m * size_k, "A must be a contiguous [size_m, size_k] tensor")
-    _check(B.is_contiguous() and B.numel() * B.element_size() == size_n * size_k // 2, "B does not hold size_n * size_k packed 4-bit weights")
-    _check(s.is_contiguous() and s.numel() * s.element_size() == size_n * size_k // 32, "s does not hold size_n * size_k / 32 scales")
-    if global_scale is not None:
-        _check(global_scale.dtype == torch.float32 and global_scale.numel() >= 1, "global_scale must be float32")
-    if bias is not None:
-        _check(bias.dtype == dtype and bias.is_contiguous() and bias.numel() == size_n and bias.device == a.device,
-               "bias must be a contiguous [size_n] tensor of A's dtype on A's device")
-    _check(a.is_cuda and B.is_cuda and s.is_cuda and (global_scale is None or global_scale.is_cuda), "all tensors must be on GPU")
-    _check(B.device == a.device and s.device == a.device and (global_scale is None or global_scale.device == a.device),
-           "all tensors must be on A's device")
-    return a, dtype, int(quantized), act
-
-
 def native_invariant_slabs(size_m: int, size_n: int, size_k: int, dtype: torch.dtype = torch.bfloat16) -> int:
     """The slab count of the form m rows get (petit_gemm_native_invariant_slabs): S in the split form (m <= 64), 1 in the whole form."""
     return int(_lib.lib.petit_gemm_native_invariant_slabs(int(size_m), int(size_n), int(size_k), _a_type(dtype)))
@@ -704,19 +759,7 @@ def mul_mxfp4_native_invariant(A, B, s, global_scale, size_m, size_n, size_k, fm
     the native class"): MXFP4 weights against activations quantised to `fmt`, a row's result independent of size_m, of the row's position and
     of the launch form.  A: a 16-bit [size_m, size_k] tensor (quantised by the call) or QuantizedActivations of the same fmt -- the same bits
     either way.  Opt-in; no solution_id."""
-    a, dtype, quantized, act = _check_native_invariant(A, B, s, global_scale, size_m, size_n, size_k, fmt, bias, activation)
-    size_m, size_n, size_k = int(size_m), int(size_n), int(size_k)
-    c = torch.empty((size_m, size_n // 2 if act else size_n), dtype=dtype, device=a.device)
-    hints = _hints("mx", dtype)
-    epi = _epilogue(bias, act, a.device, dtype, size_n, "bias must be a contiguous [size_n] tensor of A's dtype on A's device")
-    ws = _scratch(int(_lib.lib.petit_gemm_native_invariant_workspace_bytes(size_m, size_n, size_k, hints.a_type, _QFORMATS[fmt], quantized)),
-                  a.device)
-    with torch.cuda.device(a.device):
-        err = _lib.lib.petit_gemm_mxfp4_native_invariant(_ptr(c), _ptr(a), _ptr(B), _ptr(s), _opt_ptr(global_scale), size_m, size_n, size_k,
-                                                         C.byref(hints), _QFORMATS[fmt], quantized, epi, _opt_ptr(ws), _stream(a))
-    if err:
-        _raise_gemm(err, "mul_mxfp4_native_invariant", "native-invariant", f"m={size_m}, n={size_n}, k={size_k}")
-    return c
+    return _mul_invariant(A, B, s, global_scale, size_m, size_n, size_k, bias, activation, "mx", fmt)
 
 
 def _native_output(rows: int, size_m: int, n_out: int, out_quantized, dtype, dev):
@@ -994,55 +1037,6 @@ def mul_mxfp4_a16_moe_indexed(A, B, s, global_scales, expert_offsets, size_m, si
 
 # --- the batch-invariant MoE launch (include/petit_amd.h "Batch-invariant MoE launch"; no counterpart in the reference) ---------------------
 
-def _check_moe_invariant(kind: str, A, B, s, global_scales, expert_offsets, size_m, size_n, size_k, num_experts, a_row_index, c_row_index,
-                         c_rows, bias, activation, out):
-    """The argument checks of mul_nvfp4_a16_moe_invariant / mul_mxfp4_a16_moe_invariant, stated here for both operator layers; returns
-    (E, activation code, a_rows, c_rows).  Value checks come first and device checks last, so that the texts can be read without a GPU."""
-    name = "mul_%sfp4_a16_moe_invariant" % kind
-    _check(A.dtype in (torch.bfloat16, torch.float16), "A must be bfloat16 or float16.")
-    size_m, size_n, size_k, E = int(size_m), int(size_n), int(size_k), int(num_experts)
-    _check(1 <= E <= _lib.PETIT_MOE_MAX_EXPERTS, f"num_experts must be in 1..{_lib.PETIT_MOE_MAX_EXPERTS}, got {E}")
-    _check(size_n > 0 and size_n % (32 if kind == "mx" else 16) == 0 and size_k > 0 and size_k % 256 == 0 and 0 <= size_m < 1 << 20,
-           f"Incompatible problem shape (m={size_m}, n={size_n}, k={size_k}): {name} needs n % {32 if kind == 'mx' else 16} == 0, "
-           "k % 256 == 0, m < 2^20")
-    _check(not (kind == "mx" and A.dtype == torch.float16),
-           f"{name}: float16 activations with MXFP4 weights have no batch-invariant kernel (use bfloat16)")
-    act = _activation(activation, size_n)
-    _check(A.is_contiguous() and A.numel() % size_k == 0, "A must be a contiguous [a_rows, size_k] tensor")
-    a_rows = A.numel() // size_k
-    _check(a_rows * size_k * 2 <= 1 << 31, f"{name}: A holds more than 2^31 bytes (a_rows={a_rows}, k={size_k})")
-    group = 32 if kind == "mx" else 16
-    _check(B.is_contiguous() and B.numel() * B.element_size() == E * size_n * size_k // 2,
-           "B does not hold num_experts * size_n * size_k packed 4-bit weights")
-    _check(s.is_contiguous() and s.numel() * s.element_size() == E * size_n * size_k // group,
-           f"s does not hold num_experts * size_n * size_k / {group} scales")
-    _check(global_scales.dtype == torch.float32 and global_scales.is_contiguous() and global_scales.numel() == E,
-           "global_scales must be a contiguous float32 [num_experts] tensor")
-    _check(expert_offsets.dtype == torch.int32 and expert_offsets.is_contiguous() and expert_offsets.numel() == E + 1,
-           "expert_offsets must be a contiguous int32 [num_experts + 1] tensor")
-    for idx in (a_row_index, c_row_index):
-        if idx is not None:
-            _check(idx.dtype == torch.int32 and idx.is_contiguous() and idx.numel() == size_m and idx.device == A.device,
-                   "row indices must be contiguous int32 [size_m] tensors on A's device")
-    n_out = size_n // 2 if act else size_n
-    if out is not None:
-        _check(out.device == A.device and out.dtype == A.dtype and out.is_contiguous() and out.dim() == 2 and out.size(1) == n_out,
-               "out must be a contiguous [c_rows, n_out] tensor of A's dtype on A's device")
-        _check(c_rows is None or c_rows < 0 or c_rows == out.size(0), "c_rows does not match out.size(0)")
-        c_rows = out.size(0)
-    else:
-        c_rows = size_m if c_rows is None or c_rows < 0 else int(c_rows)
-    _check((a_row_index is not None or a_rows >= size_m) and (c_row_index is not None or c_rows >= size_m),
-           f"{name}: without a row index the matrix must hold size_m rows (a_rows={a_rows}, c_rows={c_rows}, m={size_m})")
-    if bias is not None:
-        _check(bias.dtype == A.dtype and bias.is_contiguous() and bias.numel() == E * size_n and bias.device == A.device,
-               "bias must be a contiguous [num_experts, size_n] tensor of A's dtype on A's device")
-    _check(A.is_cuda and B.is_cuda and s.is_cuda and global_scales.is_cuda and expert_offsets.is_cuda, "all tensors must be on GPU")
-    _check(B.device == A.device and s.device == A.device and global_scales.device == A.device and expert_offsets.device == A.device,
-           "all tensors must be on A's device")
-    return E, act, a_rows, c_rows
-
-
 def moe_invariant_form(size_m: int, num_experts: int) -> int:
     """The form a batch-invariant MoE call of size_m grouped rows over num_experts gets (petit_gemm_moe_invariant_form): 1 split, 0 whole.
     Both forms give the same bits; the switch is a speed choice."""
@@ -1057,95 +1051,23 @@ def moe_invariant_workspace_bytes(num_experts: int, size_m: int, size_n: int, si
                                                                  _B_TYPES[kind]))
 
 
-def _mul_moe_invariant(kind: str, A, B, s, global_scales, expert_offsets, size_m, size_n, size_k, num_experts, a_row_index=None,
-                       c_row_index=None, c_rows=None, bias=None, activation=None, out=None) -> torch.Tensor:
-    E, act, a_rows, c_rows = _check_moe_invariant(kind, A, B, s, global_scales, expert_offsets, size_m, size_n, size_k, num_experts,
-                                                  a_row_index, c_row_index, c_rows, bias, activation, out)
-    size_m, size_n, size_k = int(size_m), int(size_n), int(size_k)
-    if out is None:
-        out = torch.empty((c_rows, size_n // 2 if act else size_n), dtype=A.dtype, device=A.device)
-    hints = _hints(kind, A.dtype)
-    epi = _epilogue(bias, act, A.device, A.dtype, E * size_n, "bias must be a contiguous [num_experts, size_n] tensor of A's dtype on A's device")
-    ws = _scratch(int(_lib.lib.petit_gemm_moe_invariant_workspace_bytes(E, size_m, size_n, size_k, hints.a_type, hints.b_type)), A.device)
-    fn = _lib.lib.petit_gemm_fp4_fp16_moe_invariant if kind == "nv" else _lib.lib.petit_gemm_mxfp4_fp16_moe_invariant
-    with torch.cuda.device(A.device):
-        err = fn(_ptr(out), _ptr(A), _ptr(B), _ptr(s), _ptr(global_scales), _ptr(expert_offsets), E, size_m, size_n, size_k,
-                 _opt_ptr(a_row_index), a_rows, _opt_ptr(c_row_index), c_rows, C.byref(hints), epi, _opt_ptr(ws), _stream(A))
-    if err:
-        _raise_gemm(err, "mul_%sfp4_a16_moe_invariant" % kind, "invariant",
-                    f"m={size_m}, n={size_n}, k={size_k}, num_experts={E}, a_rows={a_rows}, c_rows={c_rows}")
-    return out
-
-
 def mul_nvfp4_a16_moe_invariant(A, B, s, global_scales, expert_offsets, size_m, size_n, size_k, num_experts, a_row_index=None,
                                 c_row_index=None, c_rows=None, bias=None, activation=None, out=None) -> torch.Tensor:
     """mul_nvfp4_a16_moe_indexed by the batch-invariant entry (petit_gemm_fp4_fp16_moe_invariant): every written row equals, bit for bit,
     mul_nvfp4_a16_invariant(size_m=1) on its A row and its expert's tensors -- whatever else is in the batch and wherever the row sits.
     Opt-in and slower than the default pick (profiles/moe_invariant.md); no solution_id."""
-    return _mul_moe_invariant("nv", A, B, s, global_scales, expert_offsets, size_m, size_n, size_k, num_experts, a_row_index, c_row_index,
-                              c_rows, bias, activation, out)
+    return _mul_invariant(A, B, s, global_scales, size_m, size_n, size_k, bias, activation, "nv",
+                          experts=(expert_offsets, num_experts, a_row_index, c_row_index, c_rows, out))
 
 
 def mul_mxfp4_a16_moe_invariant(A, B, s, global_scales, expert_offsets, size_m, size_n, size_k, num_experts, a_row_index=None,
                                 c_row_index=None, c_rows=None, bias=None, activation=None, out=None) -> torch.Tensor:
     """The same for MXFP4 experts (petit_gemm_mxfp4_fp16_moe_invariant); bfloat16 activations only."""
-    return _mul_moe_invariant("mx", A, B, s, global_scales, expert_offsets, size_m, size_n, size_k, num_experts, a_row_index, c_row_index,
-                              c_rows, bias, activation, out)
+    return _mul_invariant(A, B, s, global_scales, size_m, size_n, size_k, bias, activation, "mx",
+                          experts=(expert_offsets, num_experts, a_row_index, c_row_index, c_rows, out))
 
 
 # --- the batch-invariant MoE launch on the native class (include/petit_amd.h "Batch-invariant MoE launch on the native class") --------------
-
-def _check_native_moe_invariant(A, B, s, global_scales, expert_offsets, size_m, size_n, size_k, num_experts, a_row_index, c_row_index, c_rows,
-                                fmt, bias, activation):
-    """The argument checks of mul_mxfp4_native_moe_invariant, stated here for both operator layers -> (activation tensor, 16-bit dtype,
-    a_is_quantized, E, activation code, a_rows, c_rows).  Value checks come first and device checks last, so that the texts can be read
-    without a GPU."""
-    name = "mul_mxfp4_native_moe_invariant"
-    _check(fmt in _QFORMATS, "fmt must be 'mxfp8', 'mxfp6' or 'mxfp4'")
-    quantized = isinstance(A, QuantizedActivations)
-    dtype = A.dtype
-    _check(dtype in (torch.bfloat16, torch.float16), "A must be bfloat16 or float16 (or QuantizedActivations of such a tensor).")
-    size_m, size_n, size_k, E = int(size_m), int(size_n), int(size_k), int(num_experts)
-    _check(1 <= E <= _lib.PETIT_MOE_MAX_EXPERTS, f"num_experts must be in 1..{_lib.PETIT_MOE_MAX_EXPERTS}, got {E}")
-    _check(size_n > 0 and size_n % 32 == 0 and size_k > 0 and size_k % 256 == 0 and 0 <= size_m < 1 << 20,
-           f"Incompatible problem shape (m={size_m}, n={size_n}, k={size_k}): {name} needs n % 32 == 0, k % 256 == 0, m < 2^20")
-    _check(activation in _ACTIVATIONS, _ACTIVATION_RULE)
-    act = _ACTIVATIONS[activation]
-    _check(not act or size_n % 64 == 0, f"{activation} needs size_n % 64 == 0 here (gate / up halves of whole tile pairs), got {size_n}")
-    if quantized:
-        _check(A.fmt == fmt, f"quantised activations are {A.fmt}, the call says fmt={fmt!r}")
-        _check(A.m == size_m and A.k == size_k, f"quantised activations are [{A.m}, {A.k}], the call says [{size_m}, {size_k}]")
-        _check(a_row_index is None, f"{name}: quantised activations are the grouped rows already; a_row_index must be None")
-        a = A.data
-        _check(a.dtype == torch.uint8 and a.is_contiguous() and a.numel() == size_m * (size_k // 8 * _QFORMATS[fmt]) + size_m * (size_k // 32),
-               "quantised activations do not hold the bytes of their [m, k] and format")
-        a_rows = size_m
-    else:
-        a = A
-        _check(a.is_contiguous() and a.numel() % size_k == 0, "A must be a contiguous [a_rows, size_k] tensor")
-        a_rows = a.numel() // size_k
-    _check(B.is_contiguous() and B.numel() * B.element_size() == E * size_n * size_k // 2,
-           "B does not hold num_experts * size_n * size_k packed 4-bit weights")
-    _check(s.is_contiguous() and s.numel() * s.element_size() == E * size_n * size_k // 32, "s does not hold num_experts * size_n * size_k / 32 scales")
-    _check(global_scales.dtype == torch.float32 and global_scales.is_contiguous() and global_scales.numel() == E,
-           "global_scales must be a contiguous float32 [num_experts] tensor")
-    _check(expert_offsets.dtype == torch.int32 and expert_offsets.is_contiguous() and expert_offsets.numel() == E + 1,
-           "expert_offsets must be a contiguous int32 [num_experts + 1] tensor")
-    for idx in (a_row_index, c_row_index):
-        if idx is not None:
-            _check(idx.dtype == torch.int32 and idx.is_contiguous() and idx.numel() == size_m and idx.device == a.device,
-                   "row indices must be contiguous int32 [size_m] tensors on A's device")
-    c_rows = size_m if c_rows is None or c_rows < 0 else int(c_rows)
-    _check((a_row_index is not None or a_rows >= size_m) and (c_row_index is not None or c_rows >= size_m),
-           f"{name}: without a row index the matrix must hold size_m rows (a_rows={a_rows}, c_rows={c_rows}, m={size_m})")
-    if bias is not None:
-        _check(bias.dtype == dtype and bias.is_contiguous() and bias.numel() == E * size_n and bias.device == a.device,
-               "bias must be a contiguous [num_experts, size_n] tensor of A's dtype on A's device")
-    _check(a.is_cuda and B.is_cuda and s.is_cuda and global_scales.is_cuda and expert_offsets.is_cuda, "all tensors must be on GPU")
-    _check(B.device == a.device and s.device == a.device and global_scales.device == a.device and expert_offsets.device == a.device,
-           "all tensors must be on A's device")
-    return a, dtype, int(quantized), E, act, a_rows, c_rows
-
 
 def native_moe_invariant_form(size_m: int, num_experts: int) -> int:
     """The form a native-class batch-invariant MoE call of size_m grouped rows over num_experts gets
@@ -1169,23 +1091,8 @@ def mul_mxfp4_native_moe_invariant(A, B, s, global_scales, expert_offsets, size_
     tensors -- whatever else is in the batch and wherever the row sits.  A: a 16-bit [a_rows, size_k] tensor (gathered through a_row_index and
     quantised by the call) or QuantizedActivations of the size_m grouped rows (quantize_activation_rows) -- the same bits either way.
     Opt-in; no solution_id (profiles/native_moe_invariant.md has the price)."""
-    a, dtype, quantized, E, act, a_rows, c_rows = _check_native_moe_invariant(A, B, s, global_scales, expert_offsets, size_m, size_n, size_k,
-                                                                              num_experts, a_row_index, c_row_index, c_rows, fmt, bias,
-                                                                              activation)
-    size_m, size_n, size_k = int(size_m), int(size_n), int(size_k)
-    c = torch.empty((c_rows, size_n // 2 if act else size_n), dtype=dtype, device=a.device)
-    hints = _hints("mx", dtype)
-    epi = _epilogue(bias, act, a.device, dtype, E * size_n, "bias must be a contiguous [num_experts, size_n] tensor of A's dtype on A's device")
-    ws = _scratch(int(_lib.lib.petit_gemm_native_moe_invariant_workspace_bytes(E, size_m, size_n, size_k, hints.a_type, _QFORMATS[fmt],
-                                                                               quantized)), a.device)
-    with torch.cuda.device(a.device):
-        err = _lib.lib.petit_gemm_mxfp4_native_moe_invariant(_ptr(c), _ptr(a), _ptr(B), _ptr(s), _ptr(global_scales), _ptr(expert_offsets), E,
-                                                             size_m, size_n, size_k, _opt_ptr(a_row_index), a_rows, _opt_ptr(c_row_index),
-                                                             c_rows, C.byref(hints), _QFORMATS[fmt], quantized, epi, _opt_ptr(ws), _stream(a))
-    if err:
-        _raise_gemm(err, "mul_mxfp4_native_moe_invariant", "native-invariant",
-                    f"m={size_m}, n={size_n}, k={size_k}, num_experts={E}, a_rows={a_rows}, c_rows={c_rows}")
-    return c
+    return _mul_invariant(A, B, s, global_scales, size_m, size_n, size_k, bias, activation, "mx", fmt,
+                          (expert_offsets, num_experts, a_row_index, c_row_index, c_rows, None))
 
 
 def _check_topk_ids(topk_ids: torch.Tensor, num_experts: int) -> None:

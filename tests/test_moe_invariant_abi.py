@@ -289,7 +289,7 @@ BROKEN = [
 @pytest.mark.parametrize("kind", ["nv", "mx"])
 @pytest.mark.parametrize("case", BROKEN, ids=[b[0] for b in BROKEN])
 def test_both_layers_raise_the_same_texts(kind, case):
-    """The argument checks are stated once (ops._check_moe_invariant) and run by both layers in front of anything that needs a device."""
+    """The argument checks are stated once (ops._check_invariant) and run by both layers in front of anything that needs a device."""
     from petit_kernel import compiled, ops
     _, breakage, text = case
     messages = []

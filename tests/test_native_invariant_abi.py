@@ -365,7 +365,7 @@ BROKEN_Q = [
 @pytest.mark.parametrize("dtype", [torch.bfloat16, torch.float16])
 @pytest.mark.parametrize("case", BROKEN + BROKEN_Q, ids=[b[0] for b in BROKEN] + ["q " + b[0] for b in BROKEN_Q])
 def test_both_layers_raise_the_same_texts(case, dtype):
-    """The argument checks are stated once (ops._check_native_invariant) and run by both layers in front of anything that needs a device."""
+    """The argument checks are stated once (ops._check_invariant) and run by both layers in front of anything that needs a device."""
     from petit_kernel import compiled, ops
     _, breakage, text = case
     messages = []

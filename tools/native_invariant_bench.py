@@ -13,7 +13,7 @@ Every side goes through the C ABI with a per-problem workspace and is captured i
 (together beyond the 256 MB Infinity Cache; tools/benchlib.py Weights), replayed `reps` times, all sides in turn, then all once more; reported
 per launch: the median over a side's replays, its minimum and maximum.
 
---forms-lib: the form switch.  A measurement-only build of the library (csrc/gemm_native_invariant.hip compiled with
+--forms-lib: the form switch.  A measurement-only build of the library (csrc/gemm_invariant_api.hip compiled with
 -DPETIT_NATIVE_INV_MEASURE_FORMS=1 and linked with the other objects, -Wl,-Bsymbolic) reads the switch from $PETIT_NATIVE_INV_SPLIT_MAX_M per call; the run
 times the split and the whole form of the new entry at M = 16 / 32 / 64 on the four shapes, interleaved."""
 from __future__ import annotations

@@ -13,7 +13,7 @@ graph touch different experts and the weights do not sit in the Infinity Cache),
 (14 replays a side with the default --reps 7); reported per layer call: the median over all replays of a side, its minimum and maximum.
 
 --forms, the form switch.  No call can be forced into a form, so the two forms are timed through a measurement-only build of the library
-(csrc/gemm_native_invariant_moe.hip compiled with -DPETIT_NATIVE_MOE_INV_MEASURE_FORMS=1 and linked with the other objects), which reads the
+(csrc/gemm_invariant_api.hip compiled with -DPETIT_NATIVE_MOE_INV_MEASURE_FORMS=1 and linked with the other objects), which reads the
 switch's two constants from $PETIT_NATIVE_MOE_INV_SPLIT_ROWS_PER / $PETIT_NATIVE_MOE_INV_SPLIT_MAX_M per call.  Three settings stand for the
 three builds of profiles/moe_invariant.md: the starting constants (8, 8), always-whole (0, 0) and a candidate (--rows-per, --max-m); the layer
 is timed under each at T in {1, 2, 4, 8, 16, 32, 64, 128} -- the range in which the answer can change.  The same bits under every setting,
