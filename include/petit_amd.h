@@ -1001,8 +1001,9 @@ int petit_gemm_fp4_moe_invariant_host(void *c, const void *a, const void *b, con
  *   sequential fp32 sum of a_q * w, k ascending, then the stated fold and epilogue -- the device's bits whenever every partial sum is exact.  The
  *   activation bytes are decoded with the formats' own tables, E8M0 as the exact twin reads it.  It documents the format and serves the tests
  *   that run without a GPU; it is not a fallback.
- * Not here: NVFP4 images on this entry; grouped launches (the routed-expert launch: "Batch-invariant MoE launch on the native class" below,
- *   which fp4_moe_native(..., invariant=True) runs); a quantising (out_format) epilogue; any change to what the sentinels run.
+ * Not here: NVFP4 images on this entry (they have entries of their own: "Batch-invariant native-class GEMM and MoE launch on NVFP4 images"
+ *   below); grouped launches (the routed-expert launch: "Batch-invariant MoE launch on the native class" below, which
+ *   fp4_moe_native(..., invariant=True) runs); a quantising (out_format) epilogue; any change to what the sentinels run.
  */
 unsigned petit_gemm_native_invariant_slabs(unsigned m, unsigned n, unsigned k, int a_type);
 uint64_t petit_gemm_native_invariant_workspace_bytes(unsigned m, unsigned n, unsigned k, int a_type, int act_format, int a_is_quantized);
@@ -1056,7 +1057,8 @@ int petit_gemm_native_invariant_host(void *c, const void *qa, const void *b, con
  * petit_gemm_native_moe_invariant_host is the CPU twin on HOST pointers: the grouped "petit-qact/1" bytes of (m, k, act_format), offsets and a C
  *   index (activation none; bias [E][n] or NULL).  Per expert under the clamp rule it computes each row as petit_gemm_native_invariant_host
  *   computes it, decoded from the m-row image (the image's addresses depend on m, the values do not).
- * Not here: NVFP4 images; a quantising (out_format) epilogue; a pipelined whole form; a one-launch split form.
+ * Not here: NVFP4 images on this entry (petit_gemm_nvfp4_native_moe_invariant below takes them); a quantising (out_format) epilogue; a
+ *   pipelined whole form; a one-launch split form.
  */
 int petit_gemm_native_moe_invariant_form(unsigned m, unsigned num_experts); /* 1: split, 0: whole */
 uint64_t petit_gemm_native_moe_invariant_workspace_bytes(unsigned num_experts, unsigned m, unsigned n, unsigned k, int a_type, int act_format,
@@ -1069,6 +1071,64 @@ int petit_gemm_mxfp4_native_moe_invariant(void *c, const void *a, const void *b,
 int petit_gemm_native_moe_invariant_host(void *c, const void *qa, const void *b, const void *scales, const float *global_scales, const void *bias,
                                          const int32_t *expert_offsets, unsigned num_experts, unsigned m, unsigned n, unsigned k,
                                          const int32_t *c_row_index, unsigned c_rows, int a_type, int act_format);
+
+/*
+ * Batch-invariant native-class GEMM and MoE launch on NVFP4 images (no counterpart in the reference): the two entries above for NVFP4 weights,
+ * read from their MFMA-native image ("petit-cdna4-nv6/1": petit_nvfp4_native_image / _images above) -- the accuracy class of
+ * petit_gemm_nvfp4_native on an image, with the guarantee of "Batch-invariant GEMM on the native class".  Arguments as
+ * petit_gemm_mxfp4_native_invariant / petit_gemm_mxfp4_native_moe_invariant with `image` / `images` in the place of (b, scales):
+ *   image           petit_nvfp4_native_image of the packed (n, k) tensors: petit_nvfp4_native_image_bytes(k, n) bytes of device memory, 256-byte
+ *                   aligned.  hints->b_type PETIT_DTYPE_FP4_E2M1, hints->c_type == hints->a_type (BF16 or FP16).
+ *   images          the MoE entry: E images back to back, expert e's at byte e * petit_nvfp4_native_image_bytes(k, n) with its scale region
+ *                   after its own elements -- the layout petit_gemm_native_moe reads and petit_nvfp4_native_images writes.
+ *   global_scale(s) NVFP4's real global scale (one float; the MoE entry: [E]); a, act_format, a_is_quantized, epilogue, c, the row indices and the
+ *                   offsets as in the MXFP4 entries.
+ * Definition: that of "Batch-invariant GEMM on the native class" with one substitution -- the weight operand is the image's bytes of the block
+ *   of 32 weight rows: FP6 e2m3 elements, 32 consecutive k per lane, with the image's E8M0 byte of the lane's block as its scale.  S and L are
+ *   petit_gemm_invariant_geometry(n, k, a_type, PETIT_DTYPE_FP4_E2M1); per slice ONE chain of v_mfma_scale_f32_32x32x64_f8f6f4 from a zero
+ *   accumulator, k-tiles of 128 ascending, P1 then P2; slices added ascending in fp32 with no contraction; the plain epilogue rounds twice
+ *   (multiply, add), the gated ones form fma(fold, gs, bias) once and pair gate block t with up block t + n / 64.  The MoE row of grouped row r
+ *   of expert e equals, bit for bit, row 0 of petit_gemm_nvfp4_native_invariant(m = 1, a = that row, image = expert e's image,
+ *   global_scale = &global_scales[e], bias = bias + e * n, the same activation and act_format).
+ *   Accuracy: given the quantised activations and the image's weights (petit_nvfp4_native_image_dequant_host), the bound of "Native-FP4 kernels"
+ *   exactly as the MXFP4 entry states it; against the true NVFP4 weights add the re-encoding bound stated with petit_nvfp4_native_image above.
+ *   Nothing is fitted.
+ * Forms, queries, workspace: the MXFP4 native entries' as they stand -- the form constants are shared (dense: split iff m <= 64; MoE: split iff
+ *   ceil(m / min(E, m)) <= 8 and m <= 8), so petit_gemm_native_invariant_slabs, petit_gemm_native_moe_invariant_form and the two
+ *   ..._workspace_bytes queries answer for these entries too (quantised bytes, then slabs, each rounded up to 256).  A wave's unit of columns is
+ *   one block of 32 weight rows, where the MXFP4 kernels merge a pair of n-tiles; everything after the instruction is shared with them.
+ * Errors, all before any launch and in this order: PETIT_ERROR_BAD_ARGUMENT for null hints, a c_type that differs from a_type, a b_type that is
+ *   not PETIT_DTYPE_FP4_E2M1, a non-zero `reserved`, an a_type that is not BF16 / FP16, an act_format outside {8, 6, 4}, an activation value
+ *   that does not exist; PETIT_ERROR_PROBLEM_SHAPE for n % 32 != 0 (the image's zero-padded last block never arises), k % 256 != 0, n or k
+ *   zero, m >= 2^20, a gated activation with n % 64 != 0, an image of 2^32 element bytes or more (n * k * 3 / 4); PETIT_ERROR_PROBLEM_SHAPE for
+ *   an image address that is no multiple of 256; PETIT_ERROR_KERNEL_SHAPE for a dense 16-bit input of more than 65535 rows; then the MXFP4
+ *   entries' routing, pointer and workspace codes.  m == 0 returns PETIT_OK.  The MXFP4 entries keep refusing an NVFP4 b_type.
+ * petit_gemm_nvfp4_native_invariant_host / petit_gemm_nvfp4_native_moe_invariant_host are the CPU twins on HOST "petit-qact/1" bytes and HOST
+ *   images (activation none): every product is formed exactly from (decoded activation element x its E8M0) x (e2m3 element x 2^(byte - 127))
+ *   and rounded once to fp32; per slice a sequential fp32 sum, k ascending, then the stated fold and epilogue -- the device's bits whenever every
+ *   partial sum is exact.  The image is decoded at the offsets petit_nvfp4_native_image_dequant_host uses.  Not fallbacks.
+ * Measured (profiles/nvfp4_native_invariant.md, bf16, the four Llama-3-70B linears, quantiser launch included): against
+ *   petit_gemm_fp4_fp16_invariant, the only invariant NVFP4 path before, 1.2-1.7x faster in every cell at m = 512 and 4096, 1.5-4.0x faster
+ *   at m = 64 except on 57344 columns (1.6-2.1x slower), and 11-39 % slower at m = 1 on the narrower layers; 1.8-4.2x the time of
+ *   petit_gemm_nvfp4_native on the same image from m = 512 on; 1.0-1.4x the time of petit_gemm_mxfp4_native_invariant with MXFP8
+ *   activations (up to 2.0x with MXFP6 / MXFP4: the FP6 weight operand).  Both form switches were measured on images and kept.
+ * Not here: the transient (image-per-call) form; a quantising epilogue; a pipelined whole form; a one-launch split form; any change to the
+ *   sentinels and default picks; fp4_moe_native(kind="nvfp4", invariant=True), which keeps raising (compose the layer from these launches:
+ *   examples/nvfp4_native_invariant.py).
+ */
+int petit_gemm_nvfp4_native_invariant(void *c, const void *a, const void *image, const float *global_scale, unsigned m, unsigned n, unsigned k,
+                                      const petit_solution_hints *hints, int act_format /* 8 | 6 | 4 */, int a_is_quantized,
+                                      const petit_epilogue *epilogue, void *workspace, void *stream);
+int petit_gemm_nvfp4_native_moe_invariant(void *c, const void *a, const void *images, const float *global_scales, const int32_t *expert_offsets,
+                                          unsigned num_experts, unsigned m, unsigned n, unsigned k, const int32_t *a_row_index, unsigned a_rows,
+                                          const int32_t *c_row_index, unsigned c_rows, const petit_solution_hints *hints,
+                                          int act_format /* 8 | 6 | 4 */, int a_is_quantized, const petit_epilogue *epilogue, void *workspace,
+                                          void *stream);
+int petit_gemm_nvfp4_native_invariant_host(void *c, const void *qa, const void *image, const float *global_scale, const void *bias, unsigned m,
+                                           unsigned n, unsigned k, int a_type, int act_format);
+int petit_gemm_nvfp4_native_moe_invariant_host(void *c, const void *qa, const void *images, const float *global_scales, const void *bias,
+                                               const int32_t *expert_offsets, unsigned num_experts, unsigned m, unsigned n, unsigned k,
+                                               const int32_t *c_row_index, unsigned c_rows, int a_type, int act_format);
 
 /*
  * Native-class MoE launch (no counterpart in the reference): the routed-expert launch on the block-scaled MFMA, the accuracy class of

@@ -1,5 +1,5 @@
 // gemm_invariant_api.hip -- the C ABI of the batch-invariant GEMM family (include/petit_amd.h "Batch-invariant GEMM", "Batch-invariant MoE
-// launch" and their two "... on the native class" sections): ONE entry routine behind the six launch entries, and the queries and CPU twins as
+// launch" and their two "... on the native class" sections): ONE entry routine behind the eight launch entries, and the queries and CPU twins as
 // reads of gemm_invariant_host.h, where everything that needs no GPU is (the call description, the plan, the checks, the twins).  The kernels
 // are in gemm_invariant.hpp, gemm_invariant_moe.hpp, gemm_native_invariant.hpp and gemm_native_invariant_moe.hpp, instantiated by the
 // gemm_invariant_*.hip / gemm_native_invariant_*.hip next to this file.  Nothing here goes through dispatch.hip, pick.hip, moe_choose, the arch
@@ -32,6 +32,10 @@ extern template void native_invariant_launch<Bf16>(const NativeInvariantArgs &, 
 extern template void native_invariant_launch<Fp16>(const NativeInvariantArgs &, int, const inv::Plan &, hipStream_t);
 extern template void native_invariant_moe_launch<Bf16>(const NativeInvariantMoeArgs &, int, const inv::Plan &, hipStream_t);
 extern template void native_invariant_moe_launch<Fp16>(const NativeInvariantMoeArgs &, int, const inv::Plan &, hipStream_t);
+extern template void native_invariant_launch<Bf16, 6>(const NativeInvariantArgs &, int, const inv::Plan &, hipStream_t);
+extern template void native_invariant_launch<Fp16, 6>(const NativeInvariantArgs &, int, const inv::Plan &, hipStream_t);
+extern template void native_invariant_moe_launch<Bf16, 6>(const NativeInvariantMoeArgs &, int, const inv::Plan &, hipStream_t);
+extern template void native_invariant_moe_launch<Fp16, 6>(const NativeInvariantMoeArgs &, int, const inv::Plan &, hipStream_t);
 
 namespace {
 
@@ -98,12 +102,19 @@ int run(inv::Call call, const Operands &o) {
             return qrc;
         a = o.workspace;
     }
+    const bool image = call.native && call.b_type == kDataTypeFp4e2m1; // the NVFP4 image(s): o.b, the scale region of the first at o.scales
     if (call.native && call.moe) {
         const auto p = make_args<NativeInvariantMoeArgs>(call, plan, o, a, bias);
-        bf16 ? native_invariant_moe_launch<Bf16>(p, call.act_format, plan, s) : native_invariant_moe_launch<Fp16>(p, call.act_format, plan, s);
+        if (image)
+            bf16 ? native_invariant_moe_launch<Bf16, 6>(p, call.act_format, plan, s) : native_invariant_moe_launch<Fp16, 6>(p, call.act_format, plan, s);
+        else
+            bf16 ? native_invariant_moe_launch<Bf16>(p, call.act_format, plan, s) : native_invariant_moe_launch<Fp16>(p, call.act_format, plan, s);
     } else if (call.native) {
         const auto p = make_args<NativeInvariantArgs>(call, plan, o, a, bias);
-        bf16 ? native_invariant_launch<Bf16>(p, call.act_format, plan, s) : native_invariant_launch<Fp16>(p, call.act_format, plan, s);
+        if (image)
+            bf16 ? native_invariant_launch<Bf16, 6>(p, call.act_format, plan, s) : native_invariant_launch<Fp16, 6>(p, call.act_format, plan, s);
+        else
+            bf16 ? native_invariant_launch<Bf16>(p, call.act_format, plan, s) : native_invariant_launch<Fp16>(p, call.act_format, plan, s);
     } else if (call.moe) {
         const auto p = make_args<InvariantMoeArgs>(call, plan, o, a, bias);
         if (bf16 && is_mx_type(call.b_type))
@@ -228,6 +239,25 @@ int petit_gemm_mxfp4_native_moe_invariant(void *c, const void *a, const void *b,
                {c, a, b, scales, global_scales, expert_offsets, a_row_index, c_row_index, hints, epilogue, workspace, stream});
 }
 
+// the image entries: `image` takes the place of (b, scales) -- the scale region follows the (first) image's elements
+int petit_gemm_nvfp4_native_invariant(void *c, const void *a, const void *image, const float *global_scale, unsigned m, unsigned n, unsigned k,
+                                      const petit_solution_hints *hints, int act_format, int a_is_quantized, const petit_epilogue *epilogue,
+                                      void *workspace, void *stream) {
+    const void *const scales = image ? (const char *)image + nv6_elem_bytes(n, k) : nullptr;
+    return run(inv::native_call(m, n, k, 0, act_format, a_is_quantized, 0, kDataTypeFp4e2m1, image),
+               {c, a, image, scales, global_scale, nullptr, nullptr, nullptr, hints, epilogue, workspace, stream});
+}
+
+int petit_gemm_nvfp4_native_moe_invariant(void *c, const void *a, const void *images, const float *global_scales, const int32_t *expert_offsets,
+                                          unsigned num_experts, unsigned m, unsigned n, unsigned k, const int32_t *a_row_index, unsigned a_rows,
+                                          const int32_t *c_row_index, unsigned c_rows, const petit_solution_hints *hints, int act_format,
+                                          int a_is_quantized, const petit_epilogue *epilogue, void *workspace, void *stream) {
+    const void *const scales = images ? (const char *)images + nv6_elem_bytes(n, k) : nullptr;
+    return run(inv::moe_call(inv::native_call(m, n, k, 0, act_format, a_is_quantized, 0, kDataTypeFp4e2m1, images), num_experts,
+                             a_row_index != nullptr, a_rows, c_row_index != nullptr, c_rows),
+               {c, a, images, scales, global_scales, expert_offsets, a_row_index, c_row_index, hints, epilogue, workspace, stream});
+}
+
 // ---- the CPU twins -------------------------------------------------------------------------------------------------------------------------
 
 int petit_gemm_fp4_invariant_host(void *c, const void *a, const void *b, const void *scales, const float *global_scale, const void *bias,
@@ -253,6 +283,18 @@ int petit_gemm_native_moe_invariant_host(void *c, const void *qa, const void *b,
                                          const int32_t *c_row_index, unsigned c_rows, int a_type, int act_format) {
     return inv::native_moe_gemm_host(c, qa, b, scales, global_scales, bias, expert_offsets, num_experts, m, n, k, c_row_index, c_rows, a_type,
                                      act_format);
+}
+
+int petit_gemm_nvfp4_native_invariant_host(void *c, const void *qa, const void *image, const float *global_scale, const void *bias, unsigned m,
+                                           unsigned n, unsigned k, int a_type, int act_format) {
+    return inv::nv_native_gemm_host(c, qa, image, global_scale, bias, m, n, k, a_type, act_format);
+}
+
+int petit_gemm_nvfp4_native_moe_invariant_host(void *c, const void *qa, const void *images, const float *global_scales, const void *bias,
+                                               const int32_t *expert_offsets, unsigned num_experts, unsigned m, unsigned n, unsigned k,
+                                               const int32_t *c_row_index, unsigned c_rows, int a_type, int act_format) {
+    return inv::nv_native_moe_gemm_host(c, qa, images, global_scales, bias, expert_offsets, num_experts, m, n, k, c_row_index, c_rows, a_type,
+                                        act_format);
 }
 
 int petit_quantize_activations_host(void *qa, const void *a, unsigned m, unsigned k, int a_type, int format) {

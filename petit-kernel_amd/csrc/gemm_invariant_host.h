@@ -1,5 +1,5 @@
 // gemm_invariant_host.h -- the host side of the batch-invariant GEMM family (include/petit_amd.h "Batch-invariant GEMM", "Batch-invariant MoE
-// launch" and their two "... on the native class" sections) that needs no GPU: ONE description of a call of any of the four entries (Call), ONE
+// launch" and their two "... on the native class" sections) that needs no GPU: ONE description of a call of any entry (Call), ONE
 // function from it to a plan (return code, S and L, the form, the workspace parts, every launch's grid), the pointer checks, the decode of
 // "petit-qact/1" bytes and the CPU twins.  Plain C++ (no HIP), so that the same lines build into libpetit_amd.so (gemm_invariant_api.hip, and
 // the launch functions of gemm_invariant*.hpp / gemm_native_invariant*.hpp, which take their grids from the plan) and into a stand-alone
@@ -41,20 +41,24 @@ inline uint64_t round256(uint64_t x) { return (x + 255) / 256 * 256; }
 // bytes of the "petit-qact/1" image of (m, k, format): elements, then one E8M0 byte per 32 k (native32_ws_bytes, gemm_native32.hpp)
 inline uint64_t qact_bytes(unsigned m, unsigned k, int act_format) { return (uint64_t)m * (k / 8 * (unsigned)act_format) + (uint64_t)m * (k / 32); }
 
-// One call of any of the four entries.  The exact class reads b_type (act_format and a_is_quantized are 0); the native class has MXFP4 weights
-// (b_type = kTypeMx) and reads act_format and a_is_quantized.  The last five fields are the MoE entries'.
+// One call of any entry.  The exact class reads b_type (act_format and a_is_quantized are 0); the native class reads act_format and
+// a_is_quantized, and its b_type names the weight operand: kTypeMx, raw MXFP4 tensors, or kTypeNv, the "petit-cdna4-nv6/1" image(s) of NVFP4
+// weights (layout.h) -- whose address enters the refusals (image_misaligned: it is no multiple of 256).  The five fields before it are the MoE
+// entries'.
 struct Call {
     bool native, moe;
     int a_type, b_type, act_format, a_is_quantized, activation;
     unsigned m, n, k;
     unsigned num_experts, a_rows, c_rows;
     bool has_a_index, has_c_index;
+    bool image_misaligned;
 };
 inline Call dense_call(unsigned m, unsigned n, unsigned k, int a_type, int b_type, int activation) {
-    return Call{false, false, a_type, b_type, 0, 0, activation, m, n, k, 0, 0, 0, false, false};
+    return Call{false, false, a_type, b_type, 0, 0, activation, m, n, k, 0, 0, 0, false, false, false};
 }
-inline Call native_call(unsigned m, unsigned n, unsigned k, int a_type, int act_format, int a_is_quantized, int activation) {
-    return Call{true, false, a_type, kTypeMx, act_format, a_is_quantized, activation, m, n, k, 0, 0, 0, false, false};
+inline Call native_call(unsigned m, unsigned n, unsigned k, int a_type, int act_format, int a_is_quantized, int activation, int b_type = kTypeMx,
+                        const void *image = nullptr) {
+    return Call{true, false, a_type, b_type, act_format, a_is_quantized, activation, m, n, k, 0, 0, 0, false, false, ((uintptr_t)image & 255u) != 0};
 }
 inline Call moe_call(Call c, unsigned num_experts, bool has_a_index, unsigned a_rows, bool has_c_index, unsigned c_rows) {
     c.moe = true, c.num_experts = num_experts, c.has_a_index = has_a_index, c.a_rows = a_rows, c.has_c_index = has_c_index, c.c_rows = c_rows;
@@ -118,13 +122,17 @@ inline bool is_split(const Call &c) {
 // Every refusal that depends on shape, types, formats and counts alone, but the grid bound (plan).  The ORDER of the tests decides which code
 // an ill-formed call returns and is each entry's own.
 inline int shape_rc(const Call &c) {
-    const bool mx = is_mx(c.b_type);
-    if ((c.a_type != kTypeBf16 && c.a_type != kTypeFp16) || (c.native ? !format_ok(c.act_format) : c.b_type != kTypeNv && !mx) || c.activation < 0 ||
-        c.activation > 2)
+    const bool mx = is_mx(c.b_type), image = c.native && c.b_type == kTypeNv;
+    if ((c.a_type != kTypeBf16 && c.a_type != kTypeFp16) || (c.b_type != kTypeNv && !mx) || (c.native && !format_ok(c.act_format)) ||
+        c.activation < 0 || c.activation > 2)
         return kRcBadArgument;
-    // (MXFP4: n % 32 == 0 -- its processed scale tensor comes in rows of 32 weight rows.  Gated: the halves are whole tiles / tile pairs.)
-    if (c.n == 0 || c.k == 0 || c.n % 16 != 0 || (mx && c.n % 32 != 0) || c.k % 256 != 0 || c.m >= kMaxRows ||
-        (c.activation && c.n % (c.native ? 64u : 32u) != 0) || (uint64_t)c.k * 128 >= (1ull << 31))
+    // (MXFP4: n % 32 == 0 -- its processed scale tensor comes in rows of 32 weight rows; the image: whole blocks of 32 weight rows, so that its
+    // zero-padded last block never arises.  Gated: the halves are whole tiles / tile pairs / blocks.  The image's elements: 32-bit offsets.)
+    if (c.n == 0 || c.k == 0 || c.n % 16 != 0 || ((mx || image) && c.n % 32 != 0) || c.k % 256 != 0 || c.m >= kMaxRows ||
+        (c.activation && c.n % (c.native ? 64u : 32u) != 0) || (uint64_t)c.k * 128 >= (1ull << 31) ||
+        (image && (uint64_t)nv6_elem_bytes(c.n, c.k) >= (1ull << 32)))
+        return kRcProblemShape;
+    if (image && c.image_misaligned)
         return kRcProblemShape;
     if (!c.native && c.a_type == kTypeFp16 && mx)
         return kRcKernelShape; // out-of-range scale bytes need the hi / lo fallback body: a second chain, a definition of its own
@@ -407,6 +415,46 @@ inline int native_gemm_host(void *c, const void *qa, const void *b, const void *
     return kRcOk;
 }
 
+// the native class on an NVFP4 image: element (col, kk) of the HOST "petit-cdna4-nv6/1" image -- the e2m3 code at bits [6 e, 6 e + 6) of the
+// lane's 192 (planes 0 / 1: registers 0-3 of P1 / P2, plane 2: registers 4-5 of both; nv6_unit_offset) -- times 2^(byte - 127) of its block's
+// E8M0 byte (nv6_scale_offset): what petit_nvfp4_native_image_dequant_host expands, as an exact double
+inline double nv6_weight_f64(const uint8_t *image, unsigned n, unsigned k, unsigned col, unsigned kk) {
+    const unsigned blk = kk / 32, e = kk % 32, kt = blk / 4, q = (blk % 4) >> 1, h = blk & 1u;
+    uint32_t words[6];
+    memcpy(words, image + nv6_unit_offset(k, col, kt, q, h), 16);
+    memcpy(words + 4, image + nv6_unit_offset(k, col, kt, 2, h) + q * 8, 8);
+    const unsigned bit = 6 * e;
+    uint64_t wv = words[bit / 32];
+    if (bit / 32 + 1 < 6)
+        wv |= (uint64_t)words[bit / 32 + 1] << 32;
+    const unsigned sb = image[nv6_elem_bytes(n, k) + nv6_scale_offset(k, col, blk)];
+    return (double)e2m3_f32((unsigned)(wv >> (bit % 32)) & 63u) * e8m0_f64(sb);
+}
+
+// the twin of the entries on images, on HOST "petit-qact/1" bytes and a HOST image: native_gemm_host with the image's weights.  Activation none.
+inline int nv_native_gemm_host(void *c, const void *qa, const void *image, const float *global_scale, const void *bias, unsigned m, unsigned n,
+                               unsigned k, int a_type, int act_format) {
+    const Plan p = plan(native_call(m, n, k, a_type, act_format, 1, 0, kTypeNv));
+    if (p.rc != kRcOk || m == 0)
+        return p.rc;
+    if (!(c && qa && image))
+        return kRcProblemShape;
+    const uint8_t *const q8 = (const uint8_t *)qa;
+    std::vector<double> wrow(k), arow((size_t)m * k);
+    for (unsigned row = 0; row < m; ++row)
+        for (unsigned kk = 0; kk < k; ++kk)
+            arow[(size_t)row * k + kk] =
+                (double)qact_element(q8, m, k, act_format, row, kk) * e8m0_f64(qact_scale_byte(q8, m, k, act_format, row, kk / 32));
+    sliced_sum_finish(
+        c, global_scale, bias, m, n, k, p, a_type == kTypeBf16,
+        [&](unsigned col) {
+            for (unsigned kk = 0; kk < k; ++kk)
+                wrow[kk] = nv6_weight_f64((const uint8_t *)image, n, k, col, kk);
+        },
+        [&](unsigned row, unsigned kk) -> float { return (float)(arow[(size_t)row * k + kk] * wrow[kk]); });
+    return kRcOk;
+}
+
 // The MoE twins' driver: a dense twin per expert under the clamp rule (each offset clamped into [its predecessor, m], a running maximum), with
 // HOST offsets and a HOST C index.  run_expert(e, lo, rows, rows_c) computes grouped rows [lo, lo + rows) of expert e into rows_c and returns
 // the dense twin's code.  A C index outside [0, c_rows) stores nothing, rows of no expert are left untouched.
@@ -475,6 +523,24 @@ inline int native_moe_gemm_host(void *c, const void *qa, const void *b, const vo
         qact_extract_rows(rows_q, (const uint8_t *)qa, m, k, act_format, lo, rows);
         return native_gemm_host(rows_c, rows_q.data(), (const char *)b + e * w_bytes, (const char *)scales + e * s_bytes, global_scales + e,
                                 bias ? (const uint16_t *)bias + (size_t)e * n : nullptr, rows, n, k, a_type, act_format);
+    });
+}
+
+// the native class on the experts' images: expert e's image starts e * nv6_image_bytes(n, k) into `images`
+inline int nv_native_moe_gemm_host(void *c, const void *qa, const void *images, const float *global_scales, const void *bias,
+                                   const int32_t *expert_offsets, unsigned num_experts, unsigned m, unsigned n, unsigned k,
+                                   const int32_t *c_row_index, unsigned c_rows, int a_type, int act_format) {
+    const Plan p =
+        plan(moe_call(native_call(m, n, k, a_type, act_format, 1, 0, kTypeNv), num_experts, false, m, c_row_index != nullptr, c_rows));
+    if (p.rc != kRcOk || m == 0)
+        return p.rc;
+    if (!(c && qa && images && global_scales && expert_offsets))
+        return kRcProblemShape;
+    std::vector<uint8_t> rows_q;
+    return moe_twin(c, expert_offsets, num_experts, m, n, c_row_index, c_rows, [&](unsigned e, unsigned lo, unsigned rows, uint16_t *rows_c) {
+        qact_extract_rows(rows_q, (const uint8_t *)qa, m, k, act_format, lo, rows);
+        return nv_native_gemm_host(rows_c, rows_q.data(), (const char *)images + e * nv6_image_bytes(n, k), global_scales + e,
+                                   bias ? (const uint16_t *)bias + (size_t)e * n : nullptr, rows, n, k, a_type, act_format);
     });
 }
 

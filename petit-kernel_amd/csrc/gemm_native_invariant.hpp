@@ -19,6 +19,12 @@
 // The instruction computes every output element from its own row and column alone, and rows past M read zeros through the descriptor (the
 // descriptor of a k-tile ends with the workgroup's last valid row), so what sits next to a row in its tile cannot reach it.
 //
+// WF names the weight operand, as in gemm_native32.hpp: 4 = raw MXFP4 (everything above); 6 = the "petit-cdna4-nv6/1" image of NVFP4 weights
+// (layout.h): block `pair` of 32 weight rows is stored as the instruction's own FP6 e2m3 operand -- lane 32 h + r holds row r, three 16-byte
+// units per lane and k-tile (registers 0-3 of P1, registers 0-3 of P2, and {P1 r4, P1 r5, P2 r4, P2 r5}), the E8M0 byte of instruction q at
+// [q][t] of the lane's span record -- so a wave loads its operand as it stands (no merge_tiles) and everything after the MFMA is shared: row c
+// of the 32 at lane c, the lane's block 2 q + h, the same output columns.  The entries take n % 32 == 0, so the image has no padded block.
+//
 // Each form's body is stated once, in gemm_native_invariant_split.inc and gemm_native_invariant_whole.inc.  The dense kernels below and the
 // routed-expert kernels (gemm_native_invariant_moe.hpp) are a prologue each -- the weight and scale bases, the tile's first row m0 and its
 // rows_valid, the row of C an output row goes to -- and the include.
@@ -63,13 +69,17 @@ template <int ACT> __device__ __forceinline__ i32x8 native_inv_aop(const u32x4 (
     }
 }
 
-// one k-tile of one accumulator's chain: P1, then P2.  w0 / w1: the packed words of the pair's two n-tiles, s0 / s1 their span-record bytes.
-template <int ACT>
+// 16-byte units of one k-tile a lane holds of its 32 weight rows: the pair's two n-tiles (raw MXFP4) / the image block's three planes
+template <int WF> constexpr int native_inv_w_units() { return WF == 6 ? 3 : 2; }
+
+// one k-tile of one accumulator's chain: P1, then P2.  wop / wsc: the weight operands and E8M0 bytes of the two instructions.
+template <int ACT, int WF = 4>
 __device__ __forceinline__ f32x16 native_inv_ktile(f32x16 acc, const i32x8 (&wop)[2], const unsigned (&wsc)[2],
                                                    const u32x4 (&a)[native_inv_frag_units<ACT>()], const unsigned a_sc1, const unsigned a_sc2) {
     constexpr int kBlgp = ACT == 8 ? 0 : ACT == 6 ? 2 : 4; // the activation operand's format: e4m3 / e2m3 / e2m1
-    acc = __builtin_amdgcn_mfma_scale_f32_32x32x64_f8f6f4(wop[0], native_inv_aop<ACT>(a, 0), acc, 4 /* A = FP4 */, kBlgp, 0, (int)wsc[0], 0, (int)a_sc1);
-    acc = __builtin_amdgcn_mfma_scale_f32_32x32x64_f8f6f4(wop[1], native_inv_aop<ACT>(a, 1), acc, 4, kBlgp, 0, (int)wsc[1], 0, (int)a_sc2);
+    constexpr int kCbsz = WF == 6 ? 2 : 4;                 // the weight operand's: e2m3 (the image) / e2m1 (raw MXFP4)
+    acc = __builtin_amdgcn_mfma_scale_f32_32x32x64_f8f6f4(wop[0], native_inv_aop<ACT>(a, 0), acc, kCbsz, kBlgp, 0, (int)wsc[0], 0, (int)a_sc1);
+    acc = __builtin_amdgcn_mfma_scale_f32_32x32x64_f8f6f4(wop[1], native_inv_aop<ACT>(a, 1), acc, kCbsz, kBlgp, 0, (int)wsc[1], 0, (int)a_sc2);
     return acc;
 }
 
@@ -86,6 +96,16 @@ __device__ __forceinline__ void native_inv_merge(const u32x4 w0, const u32x4 w1,
         wop[q] = i32x8{(int)pw[q][0], (int)pw[q][1], (int)pw[q][2], (int)pw[q][3], 0, 0, 0, 0};
 }
 
+// WF = 6: the block's operands from its three planes -- P1 is plane 0 followed by plane 2's words 0 and 1, P2 plane 1 followed by words 2 and 3
+// (the assembly native_inv_aop<6> does for MXFP6 activations) -- and the two bytes [q][t] of the lane's span record
+__device__ __forceinline__ void native_inv_image_ops(const u32x4 (&w)[3], const unsigned (&sc)[2], i32x8 (&wop)[2], unsigned (&wsc)[2]) {
+#pragma unroll
+    for (int q = 0; q < 2; ++q) {
+        wop[q] = i32x8{(int)w[q][0], (int)w[q][1], (int)w[q][2], (int)w[q][3], (int)w[2][2 * q], (int)w[2][2 * q + 1], 0, 0};
+        wsc[q] = sc[q];
+    }
+}
+
 // The split form.  ACT: 8 / 6 / 4.  kDepth: k-tiles in flight per wave.  (AT does not enter the arithmetic: the slabs are fp32.)
 template <class AT, int ACT, int kDepth> __global__ __launch_bounds__(256) void native_invariant_split_kernel(const NativeInvariantArgs p) {
     const unsigned lane = threadIdx.x & 63u, m_l = lane & 31u, h = lane >> 5;
@@ -98,6 +118,23 @@ template <class AT, int ACT, int kDepth> __global__ __launch_bounds__(256) void 
     const unsigned m0 = blockIdx.z * 32u, s = blockIdx.y;
     const unsigned rows_left = p.m - m0, rows_valid = rows_left < 32u ? rows_left : 32u; // (the grid keeps m0 < m)
     const char *const w_base = (const char *)p.w, *const s_base = (const char *)p.s;
+    constexpr int WF = 4;
+#include "gemm_native_invariant_split.inc"
+}
+
+// The split form on the image (WF = 6): p.w is the image's elements, p.s its scale region; a wave's `pair` is its block of 32 weight rows.
+template <class AT, int ACT, int kDepth> __global__ __launch_bounds__(256) void native_invariant_nv_split_kernel(const NativeInvariantArgs p) {
+    const unsigned lane = threadIdx.x & 63u, m_l = lane & 31u, h = lane >> 5;
+    const unsigned wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const unsigned pairs = p.n / 32u, ktiles = p.k / kTileK;
+    const unsigned ks = (unsigned)span_tiles_for_k(p.k);
+    const unsigned pair = blockIdx.x * 4u + wave;
+    if (pair >= pairs)
+        return; // (wave-uniform; the loop has no barrier)
+    const unsigned m0 = blockIdx.z * 32u, s = blockIdx.y;
+    const unsigned rows_left = p.m - m0, rows_valid = rows_left < 32u ? rows_left : 32u; // (the grid keeps m0 < m)
+    const char *const w_base = (const char *)p.w, *const s_base = (const char *)p.s;
+    constexpr int WF = 6;
 #include "gemm_native_invariant_split.inc"
 }
 
@@ -124,30 +161,55 @@ template <class AT, int ACT> __global__ __launch_bounds__(256) void native_invar
     const float *const gs = p.gs;
     const void *const bias = p.bias;
     auto c_row = [](unsigned row) { return row; };
+    constexpr int WF = 4;
+#include "gemm_native_invariant_whole.inc"
+}
+
+// The whole form on the image (WF = 6): a slot is two blocks of 32 weight rows -- 2 t and 2 t + 1, or (gated) gate block t and up block t + n / 64.
+template <class AT, int ACT> __global__ __launch_bounds__(256) void native_invariant_nv_whole_kernel(const NativeInvariantArgs p) {
+#pragma clang fp contract(off)
+    const unsigned tid = threadIdx.x, lane = tid & 63u;
+    const unsigned wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const unsigned slot = blockIdx.x * 4u + wave;
+    const unsigned m0 = blockIdx.y * 64u;
+    const unsigned rows_left = p.m - m0, rows_valid = rows_left < 64u ? rows_left : 64u; // (the grid keeps m0 < m)
+    const char *const w_base = (const char *)p.w, *const s_base = (const char *)p.s;
+    const float *const gs = p.gs;
+    const void *const bias = p.bias;
+    auto c_row = [](unsigned row) { return row; };
+    constexpr int WF = 6;
 #include "gemm_native_invariant_whole.inc"
 }
 
 constexpr int kNativeInvariantSplitDepth = 3;
 
-// one activation type's launches; instantiated by gemm_native_invariant_{bf16,f16}.hip
-template <class AT, int ACT> void native_invariant_launch_fmt(const NativeInvariantArgs &p, const invariant::Plan &plan, hipStream_t stream) {
+// one activation type's launches of one weight operand; instantiated by gemm_native_invariant_{bf16,f16}.hip (WF = 4) and
+// gemm_native_invariant_nv_{bf16,f16}.hip (WF = 6)
+template <class AT, int ACT, int WF> void native_invariant_launch_fmt(const NativeInvariantArgs &p, const invariant::Plan &plan, hipStream_t stream) {
     if (plan.split) {
-        hipLaunchKernelGGL((native_invariant_split_kernel<AT, ACT, kNativeInvariantSplitDepth>), invariant_grid(plan.gemm), dim3(256), 0, stream, p);
+        if constexpr (WF == 6)
+            hipLaunchKernelGGL((native_invariant_nv_split_kernel<AT, ACT, kNativeInvariantSplitDepth>), invariant_grid(plan.gemm), dim3(256), 0, stream, p);
+        else
+            hipLaunchKernelGGL((native_invariant_split_kernel<AT, ACT, kNativeInvariantSplitDepth>), invariant_grid(plan.gemm), dim3(256), 0, stream, p);
         InvariantArgs f{}; // the fold of the exact class
         f.c = p.c, f.gs = p.gs, f.bias = p.bias, f.slabs = p.slabs, f.m = p.m, f.n = p.n, f.k = p.k, f.slice_k = p.slice_k, f.slices = p.slices,
         f.act = p.act;
         hipLaunchKernelGGL((invariant_fold_kernel<AT>), invariant_grid(plan.fold), dim3(256), 0, stream, f);
     } else {
-        hipLaunchKernelGGL((native_invariant_whole_kernel<AT, ACT>), invariant_grid(plan.gemm), dim3(256), 0, stream, p);
+        if constexpr (WF == 6)
+            hipLaunchKernelGGL((native_invariant_nv_whole_kernel<AT, ACT>), invariant_grid(plan.gemm), dim3(256), 0, stream, p);
+        else
+            hipLaunchKernelGGL((native_invariant_whole_kernel<AT, ACT>), invariant_grid(plan.gemm), dim3(256), 0, stream, p);
     }
 }
-template <class AT> void native_invariant_launch(const NativeInvariantArgs &p, int act_format, const invariant::Plan &plan, hipStream_t stream) {
+template <class AT, int WF = 4>
+void native_invariant_launch(const NativeInvariantArgs &p, int act_format, const invariant::Plan &plan, hipStream_t stream) {
     if (act_format == 8)
-        native_invariant_launch_fmt<AT, 8>(p, plan, stream);
+        native_invariant_launch_fmt<AT, 8, WF>(p, plan, stream);
     else if (act_format == 6)
-        native_invariant_launch_fmt<AT, 6>(p, plan, stream);
+        native_invariant_launch_fmt<AT, 6, WF>(p, plan, stream);
     else
-        native_invariant_launch_fmt<AT, 4>(p, plan, stream);
+        native_invariant_launch_fmt<AT, 4, WF>(p, plan, stream);
 }
 
 } // namespace petit_amd

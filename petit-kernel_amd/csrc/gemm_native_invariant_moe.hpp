@@ -64,6 +64,29 @@ template <class AT, int ACT, int kDepth> __global__ __launch_bounds__(256) void 
     const unsigned m0 = t.row0 + (slot - t.first) * 32u, rows_valid = min(t.row0 + t.rows - m0, 32u);
     const char *const w_base = (const char *)p.w + t.expert * moe_w_bytes<kFmtMx>(p.n, p.k);
     const char *const s_base = (const char *)p.s + t.expert * moe_s_bytes<kFmtMx>(p.n, p.k);
+    constexpr int WF = 4;
+#include "gemm_native_invariant_split.inc"
+}
+
+// The split form on the experts' images (WF = 6): expert e's image starts e * nv6_image_bytes(n, k) into p.w and its scale region follows its own
+// elements -- the layout gemm_moe_native.hpp reads; p.s is not read.
+template <class AT, int ACT, int kDepth> __global__ __launch_bounds__(256) void native_invariant_moe_nv_split_kernel(const NativeInvariantMoeArgs p) {
+    const unsigned lane = threadIdx.x & 63u, m_l = lane & 31u, h = lane >> 5;
+    const unsigned wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const unsigned pairs = p.n / 32u, ktiles = p.k / kTileK;
+    const unsigned ks = (unsigned)span_tiles_for_k(p.k);
+    const unsigned nb = blockIdx.x % p.nblocks, rest = blockIdx.x / p.nblocks;
+    const unsigned s = rest % p.slices, slot = rest / p.slices;
+    MoeTile t;
+    if (!moe_locate(p.offsets, p.experts, p.m, 32u, slot, t))
+        return; // a slot past the last tile: before any operand load
+    const unsigned pair = nb * 4u + wave; // a wave's block of 32 weight rows
+    if (pair >= pairs)
+        return; // (wave-uniform; the loop has no barrier) a ragged last workgroup
+    const unsigned m0 = t.row0 + (slot - t.first) * 32u, rows_valid = min(t.row0 + t.rows - m0, 32u);
+    const char *const w_base = (const char *)p.w + t.expert * nv6_image_bytes(p.n, p.k);
+    const char *const s_base = w_base + nv6_elem_bytes(p.n, p.k);
+    constexpr int WF = 6;
 #include "gemm_native_invariant_split.inc"
 }
 
@@ -83,15 +106,40 @@ template <class AT, int ACT> __global__ __launch_bounds__(256) void native_invar
     const float *const gs = p.gs + t.expert;
     const void *const bias = p.bias ? (const char *)p.bias + (size_t)t.expert * p.n * 2 : nullptr;
     auto c_row = [&](unsigned row) { return native_moe_c_row(p, row); };
+    constexpr int WF = 4;
 #include "gemm_native_invariant_whole.inc"
 }
 
-// one activation type's launches; instantiated by gemm_native_invariant_moe_{bf16,f16}.hip.  The grids are the plan's (gemm_invariant_host.h),
-// which refused the call had one of them reached 2^31.
-template <class AT, int ACT> void native_invariant_moe_launch_fmt(NativeInvariantMoeArgs p, const invariant::Plan &plan, hipStream_t stream) {
+// The whole form on the experts' images (WF = 6).
+template <class AT, int ACT> __global__ __launch_bounds__(256) void native_invariant_moe_nv_whole_kernel(const NativeInvariantMoeArgs p) {
+#pragma clang fp contract(off)
+    const unsigned tid = threadIdx.x, lane = tid & 63u;
+    const unsigned wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const unsigned nb = blockIdx.x % p.nblocks, mslot = blockIdx.x / p.nblocks;
+    MoeTile t;
+    if (!moe_locate(p.offsets, p.experts, p.m, 64u, mslot, t))
+        return; // (workgroup-uniform: before any barrier and any operand load)
+    const unsigned slot = nb * 4u + wave;
+    const unsigned m0 = t.row0 + (mslot - t.first) * 64u, rows_valid = min(t.row0 + t.rows - m0, 64u);
+    const char *const w_base = (const char *)p.w + t.expert * nv6_image_bytes(p.n, p.k);
+    const char *const s_base = w_base + nv6_elem_bytes(p.n, p.k);
+    const float *const gs = p.gs + t.expert;
+    const void *const bias = p.bias ? (const char *)p.bias + (size_t)t.expert * p.n * 2 : nullptr;
+    auto c_row = [&](unsigned row) { return native_moe_c_row(p, row); };
+    constexpr int WF = 6;
+#include "gemm_native_invariant_whole.inc"
+}
+
+// one activation type's launches of one weight operand; instantiated by gemm_native_invariant_moe_{bf16,f16}.hip (WF = 4) and
+// gemm_native_invariant_moe_nv_{bf16,f16}.hip (WF = 6).  The grids are the plan's (gemm_invariant_host.h), which refused the call had one of
+// them reached 2^31.
+template <class AT, int ACT, int WF> void native_invariant_moe_launch_fmt(NativeInvariantMoeArgs p, const invariant::Plan &plan, hipStream_t stream) {
     p.nblocks = plan.gemm.nblocks;
     if (plan.split) {
-        hipLaunchKernelGGL((native_invariant_moe_split_kernel<AT, ACT, kNativeInvariantSplitDepth>), invariant_grid(plan.gemm), dim3(256), 0, stream, p);
+        if constexpr (WF == 6)
+            hipLaunchKernelGGL((native_invariant_moe_nv_split_kernel<AT, ACT, kNativeInvariantSplitDepth>), invariant_grid(plan.gemm), dim3(256), 0, stream, p);
+        else
+            hipLaunchKernelGGL((native_invariant_moe_split_kernel<AT, ACT, kNativeInvariantSplitDepth>), invariant_grid(plan.gemm), dim3(256), 0, stream, p);
         // the fold of the exact MoE launch, over its own 16-row slot map of the same offsets
         InvariantMoeArgs f{};
         f.c = p.c, f.gs = p.gs, f.bias = p.bias, f.slabs = p.slabs, f.offsets = p.offsets, f.c_idx = p.c_idx;
@@ -99,16 +147,20 @@ template <class AT, int ACT> void native_invariant_moe_launch_fmt(NativeInvarian
         f.nblocks = plan.fold.nblocks;
         hipLaunchKernelGGL((invariant_moe_fold_kernel<AT>), invariant_grid(plan.fold), dim3(256), 0, stream, f);
     } else {
-        hipLaunchKernelGGL((native_invariant_moe_whole_kernel<AT, ACT>), invariant_grid(plan.gemm), dim3(256), 0, stream, p);
+        if constexpr (WF == 6)
+            hipLaunchKernelGGL((native_invariant_moe_nv_whole_kernel<AT, ACT>), invariant_grid(plan.gemm), dim3(256), 0, stream, p);
+        else
+            hipLaunchKernelGGL((native_invariant_moe_whole_kernel<AT, ACT>), invariant_grid(plan.gemm), dim3(256), 0, stream, p);
     }
 }
-template <class AT> void native_invariant_moe_launch(const NativeInvariantMoeArgs &p, int act_format, const invariant::Plan &plan, hipStream_t stream) {
+template <class AT, int WF = 4>
+void native_invariant_moe_launch(const NativeInvariantMoeArgs &p, int act_format, const invariant::Plan &plan, hipStream_t stream) {
     if (act_format == 8)
-        native_invariant_moe_launch_fmt<AT, 8>(p, plan, stream);
+        native_invariant_moe_launch_fmt<AT, 8, WF>(p, plan, stream);
     else if (act_format == 6)
-        native_invariant_moe_launch_fmt<AT, 6>(p, plan, stream);
+        native_invariant_moe_launch_fmt<AT, 6, WF>(p, plan, stream);
     else
-        native_invariant_moe_launch_fmt<AT, 4>(p, plan, stream);
+        native_invariant_moe_launch_fmt<AT, 4, WF>(p, plan, stream);
 }
 
 } // namespace petit_amd

@@ -2,14 +2,16 @@
 // native_invariant_whole_kernel (gemm_native_invariant.hpp) and native_invariant_moe_whole_kernel (gemm_native_invariant_moe.hpp) after their
 // prologues.  A text fragment and not a function: behind a call, inlined or not, the compiler rotates the weight ring elsewhere in the k-loop
 // (profiles/invariant_shared_bodies.md).  It reads AT, ACT and the kernel's `p` (c, qa, m, n, k, slice_k, act) and expects the prologue's
+//   WF                the weight operand (gemm_native_invariant.hpp): 4 raw MXFP4, 6 the NVFP4 image
 //   tid, lane, wave   thread, lane and (uniform) wave index
-//   slot              the wave's slot: two pairs of n-tiles of the tensors at w_base / s_base (const char *)
+//   slot              the wave's slot: two pairs of n-tiles (WF = 6: two blocks of 32 weight rows, `pair` below) of the tensors at w_base /
+//                     s_base (const char *; WF = 6: the image's elements and its scale region)
 //   m0, rows_valid    the tile's first row of the m quantised rows and how many of its 64 are there
 //   gs, bias          const float * (null: no multiply) and const void * (null: no add) of the epilogue
 //   c_row(row)        the row of C that row `row` is written to, or ~0u: not written
 using L = NativeWholeLds<ACT>;
 constexpr unsigned kRowB = L::kRowB, U = L::U;
-constexpr int NA = native_inv_frag_units<ACT>(), MB = 2, NP = 2;
+constexpr int NA = native_inv_frag_units<ACT>(), MB = 2, NP = 2, NW = native_inv_w_units<WF>(), NR = WF == 6 ? 1 : 2;
 __shared__ __attribute__((aligned(16))) char lds[2 * L::kBuf];
 const unsigned m_l = lane & 31u, h = lane >> 5;
 const unsigned ntiles = p.n / kTileN, pairs = ntiles / 2, ktiles = p.k / kTileK;
@@ -19,14 +21,20 @@ unsigned pair[NP];
 bool live[NP]; // (wave-uniform) pairs past N: empty descriptors, nothing stored.  Dead waves still walk the loop: they share the barriers.
 pair[0] = gated ? slot : 2u * slot, pair[1] = gated ? slot + pairs / 2 : 2u * slot + 1;
 live[0] = gated ? slot < pairs / 2 : pair[0] < pairs, live[1] = gated ? live[0] : pair[1] < pairs;
-__amdgpu_buffer_rsrc_t w_rsrc[NP][2], s_rsrc[NP][2];
+__amdgpu_buffer_rsrc_t w_rsrc[NP][NR], s_rsrc[NP][NR];
 #pragma unroll
 for (int np = 0; np < NP; ++np)
+    if constexpr (WF == 6) { // the block's stream along K: 3 KiB of elements and 128 scale bytes per k-tile
+        const unsigned b = live[np] ? pair[np] : 0u;
+        w_rsrc[np][0] = make_rsrc(w_base + (size_t)b * ktiles * kNv6TileBytes, live[np] ? ktiles * kNv6TileBytes : 0u);
+        s_rsrc[np][0] = make_rsrc(s_base + (size_t)b * ktiles * 128, live[np] ? ktiles * 128 : 0u);
+    } else {
 #pragma unroll
-    for (int j = 0; j < 2; ++j) {
-        const unsigned t = live[np] ? 2u * pair[np] + j : 0u;
-        w_rsrc[np][j] = make_rsrc(w_base + (size_t)t * ktiles * kTileBytes, live[np] ? ktiles * kTileBytes : 0u);
-        s_rsrc[np][j] = make_rsrc(s_base + (size_t)t * ktiles * 64, live[np] ? ktiles * 64 : 0u);
+        for (int j = 0; j < 2; ++j) {
+            const unsigned t = live[np] ? 2u * pair[np] + j : 0u;
+            w_rsrc[np][j] = make_rsrc(w_base + (size_t)t * ktiles * kTileBytes, live[np] ? ktiles * kTileBytes : 0u);
+            s_rsrc[np][j] = make_rsrc(s_base + (size_t)t * ktiles * 64, live[np] ? ktiles * 64 : 0u);
+        }
     }
 const unsigned char *const qa_hi = p.qa + (size_t)p.m * (p.k / 2); // (MXFP6)
 const unsigned char *const qs = p.qa + (size_t)p.m * (p.k / 8 * ACT);
@@ -72,19 +80,32 @@ auto put_a = [&](const AStage &r, unsigned buf) {
         *reinterpret_cast<unsigned *>(base + L::kData + L::kHi + tid * 4u) = r.sc;
 };
 struct WStage {
-    u32x4 w[NP][2];
+    u32x4 w[NP][NW];
     unsigned sc[NP][2];
 };
 auto load_w = [&](WStage &st, unsigned kt) {
     const unsigned sp = kt / ks, t = kt - sp * ks;
-    const unsigned s_voff = (sp * 64u + lane) * ks + t;
+    if constexpr (WF == 6) { // the lane's unit of planes 0, 1, 2 (nv6_unit_offset) and its bytes [q][t] (nv6_scale_offset), q = 0, 1
+        const unsigned s_voff = (sp * 64u + lane) * (2u * ks) + t;
 #pragma unroll
-    for (int np = 0; np < NP; ++np)
+        for (int np = 0; np < NP; ++np) {
 #pragma unroll
-        for (int j = 0; j < 2; ++j) {
-            st.w[np][j] = buf_load16(w_rsrc[np][j], kt * kTileBytes + lane * 16u, 0, kAuxDefault);
-            st.sc[np][j] = (unsigned)__builtin_amdgcn_raw_buffer_load_b8(s_rsrc[np][j], s_voff, 0, kAuxDefault);
+            for (int i = 0; i < 3; ++i)
+                st.w[np][i] = buf_load16(w_rsrc[np][0], kt * kNv6TileBytes + i * 1024u + lane * 16u, 0, kAuxDefault);
+#pragma unroll
+            for (int q = 0; q < 2; ++q)
+                st.sc[np][q] = (unsigned)__builtin_amdgcn_raw_buffer_load_b8(s_rsrc[np][0], s_voff + q * ks, 0, kAuxDefault);
         }
+    } else {
+        const unsigned s_voff = (sp * 64u + lane) * ks + t;
+#pragma unroll
+        for (int np = 0; np < NP; ++np)
+#pragma unroll
+            for (int j = 0; j < 2; ++j) {
+                st.w[np][j] = buf_load16(w_rsrc[np][j], kt * kTileBytes + lane * 16u, 0, kAuxDefault);
+                st.sc[np][j] = (unsigned)__builtin_amdgcn_raw_buffer_load_b8(s_rsrc[np][j], s_voff, 0, kAuxDefault);
+            }
+    }
 };
 
 f32x16 total[MB][NP], acc[MB][NP];
@@ -144,7 +165,10 @@ for (unsigned kt = 0; kt < ktiles; ++kt) {
     unsigned wsc[NP][2];
 #pragma unroll
     for (int np = 0; np < NP; ++np)
-        native_inv_merge(cur.w[np][0], cur.w[np][1], cur.sc[np][0], cur.sc[np][1], wop[np], wsc[np]);
+        if constexpr (WF == 6)
+            native_inv_image_ops(cur.w[np], cur.sc[np], wop[np], wsc[np]);
+        else
+            native_inv_merge(cur.w[np][0], cur.w[np][1], cur.sc[np][0], cur.sc[np][1], wop[np], wsc[np]);
     const char *const img = lds + (kt & 1u) * L::kBuf;
 #pragma unroll
     for (int mb = 0; mb < MB; ++mb) {
@@ -164,7 +188,7 @@ for (unsigned kt = 0; kt < ktiles; ++kt) {
         const unsigned a_sc1 = sc[h], a_sc2 = sc[2u + h];
 #pragma unroll
         for (int np = 0; np < NP; ++np)
-            acc[mb][np] = native_inv_ktile<ACT>(acc[mb][np], wop[np], wsc[np], a, a_sc1, a_sc2);
+            acc[mb][np] = native_inv_ktile<ACT, WF>(acc[mb][np], wop[np], wsc[np], a, a_sc1, a_sc2);
     }
     put_a(nxt, (kt + 1u) & 1u); // the other half: everybody left it at the barrier that ended the previous step
     __syncthreads();

@@ -266,7 +266,8 @@ struct InvariantRouting { // the MoE entries' part of a call
     int64_t a_rows, c_rows;
     const at::Tensor *out;
 };
-// act_format: 8 / 6 / 4 on the native class (then `quantized` says what A is, and st names the 16-bit type of c and the bias), 0 on the exact
+// act_format: 8 / 6 / 4 on the native class (then `quantized` says what A is, and st names the 16-bit type of c and the bias), 0 on the exact.
+// The native class with !mx: B is the NVFP4 native image (a MoE call: the experts' images) and s is not read (callers pass B).
 at::Tensor invariant_call(const char *name, bool mx, int64_t act_format, bool quantized, at::ScalarType st, const at::Tensor &A, const at::Tensor &B,
                           const at::Tensor &s, const float *gs, int64_t m, int64_t n, int64_t k, const std::optional<at::Tensor> &bias,
                           int64_t activation, const InvariantRouting *r) {
@@ -304,12 +305,18 @@ at::Tensor invariant_call(const char *name, bool mx, int64_t act_format, bool qu
     if (!r && !native)
         rc = (mx ? petit_gemm_mxfp4_fp16_invariant : petit_gemm_fp4_fp16_invariant)(c.data_ptr(), A.data_ptr(), B.data_ptr(), s.data_ptr(), gs, um, un,
                                                                                    uk, &hints, pe, w, stream);
+    else if (!r && !mx)
+        rc = petit_gemm_nvfp4_native_invariant(c.data_ptr(), A.data_ptr(), B.data_ptr(), gs, um, un, uk, &hints, fmt, q, pe, w, stream);
     else if (!r)
         rc = petit_gemm_mxfp4_native_invariant(c.data_ptr(), A.data_ptr(), B.data_ptr(), s.data_ptr(), gs, um, un, uk, &hints, fmt, q, pe, w, stream);
     else if (!native)
         rc = (mx ? petit_gemm_mxfp4_fp16_moe_invariant : petit_gemm_fp4_fp16_moe_invariant)(
             c.data_ptr(), A.data_ptr(), B.data_ptr(), s.data_ptr(), gs, (const int32_t *)r->off.data_ptr(), ue, um, un, uk, row_index_ptr(r->a_idx),
             (unsigned)r->a_rows, row_index_ptr(r->c_idx), (unsigned)c_rows, &hints, pe, w, stream);
+    else if (!mx)
+        rc = petit_gemm_nvfp4_native_moe_invariant(c.data_ptr(), A.data_ptr(), B.data_ptr(), gs, (const int32_t *)r->off.data_ptr(), ue, um, un, uk,
+                                                   row_index_ptr(r->a_idx), (unsigned)r->a_rows, row_index_ptr(r->c_idx), (unsigned)c_rows, &hints,
+                                                   fmt, q, pe, w, stream);
     else
         rc = petit_gemm_mxfp4_native_moe_invariant(c.data_ptr(), A.data_ptr(), B.data_ptr(), s.data_ptr(), gs, (const int32_t *)r->off.data_ptr(), ue, um,
                                                    un, uk, row_index_ptr(r->a_idx), (unsigned)r->a_rows, row_index_ptr(r->c_idx), (unsigned)c_rows,
@@ -362,6 +369,29 @@ at::Tensor mul_mxfp4_native_invariant(PETIT_NATIVE_INVARIANT_ARGS) {
     TORCH_CHECK(activation >= 0 && activation <= 2 && (!activation || size_n % 64 == 0), "activation must be 0, 1 or 2; gated forms need size_n % 64 == 0");
     check_bias(bias, A, st, size_n, "bias must be a contiguous [size_n] tensor of A's dtype on A's device");
     return invariant_call("mul_mxfp4_native_invariant", true, act_format, quantized, st, A, B, s,
+                          global_scale ? (const float *)global_scale->data_ptr() : nullptr, size_m, size_n, size_k, bias, activation, nullptr);
+}
+
+// the same on the NVFP4 native image (petit_gemm_nvfp4_native_invariant)
+#define PETIT_NV_NATIVE_INVARIANT_ARGS                                                                                                         \
+    const at::Tensor &A, const at::Tensor &image, const std::optional<at::Tensor> &global_scale, int64_t size_m, int64_t size_n, int64_t size_k, \
+        int64_t act_format, bool quantized, bool bf16, const std::optional<at::Tensor> &bias, int64_t activation
+at::Tensor mul_nvfp4_native_invariant(PETIT_NV_NATIVE_INVARIANT_ARGS) {
+    const at::ScalarType st = bf16 ? at::kBFloat16 : at::kHalf;
+    TORCH_CHECK(act_format == 8 || act_format == 6 || act_format == 4, "act_format must be 8, 6 or 4");
+    TORCH_CHECK(size_m >= 0 && size_n > 0 && size_k > 0 && size_k % 256 == 0 && A.is_cuda() && image.is_cuda() && A.is_contiguous() &&
+                    image.is_contiguous() && image.device() == A.device() &&
+                    (quantized ? A.scalar_type() == at::kByte && A.numel() == size_m * (size_k / 8 * act_format) + size_m * (size_k / 32)
+                               : A.scalar_type() == st && A.numel() == size_m * size_k) &&
+                    image.scalar_type() == at::kByte && image.numel() > 0 &&
+                    image.numel() == (int64_t)petit_nvfp4_native_image_bytes((unsigned)size_k, (unsigned)size_n) &&
+                    (!global_scale || (global_scale->is_cuda() && global_scale->device() == A.device() &&
+                                       global_scale->scalar_type() == at::kFloat && global_scale->numel() >= 1)),
+                "A [size_m, size_k] (or its quantised bytes) and the native image of [size_n, size_k] NVFP4 weights must be contiguous GPU tensors "
+                "on one device, global_scale a float32 tensor on it");
+    TORCH_CHECK(activation >= 0 && activation <= 2 && (!activation || size_n % 64 == 0), "activation must be 0, 1 or 2; gated forms need size_n % 64 == 0");
+    check_bias(bias, A, st, size_n, "bias must be a contiguous [size_n] tensor of A's dtype on A's device");
+    return invariant_call("mul_nvfp4_native_invariant", false, act_format, quantized, st, A, image, image,
                           global_scale ? (const float *)global_scale->data_ptr() : nullptr, size_m, size_n, size_k, bias, activation, nullptr);
 }
 
@@ -497,6 +527,27 @@ at::Tensor mul_mxfp4_native_moe_invariant(PETIT_NATIVE_MOE_INVARIANT_ARGS) {
     const InvariantRouting r{off, e, a_idx, c_idx, quantized ? m : A.numel() / k, c_rows, nullptr};
     return invariant_call("mul_mxfp4_native_moe_invariant", true, act_format, quantized, st, A, B, s, (const float *)gs.data_ptr(), m, n, k, bias,
                           activation, &r);
+}
+
+// the same on the experts' NVFP4 native images (petit_gemm_nvfp4_native_moe_invariant)
+#define PETIT_NV_NATIVE_MOE_INVARIANT_ARGS                                                                                                      \
+    const at::Tensor &A, const at::Tensor &images, const at::Tensor &gs, const at::Tensor &off, int64_t m, int64_t n, int64_t k, int64_t e,      \
+        const std::optional<at::Tensor> &a_idx, const std::optional<at::Tensor> &c_idx, int64_t c_rows, int64_t act_format, bool quantized,     \
+        bool bf16, const std::optional<at::Tensor> &bias, int64_t activation
+at::Tensor mul_nvfp4_native_moe_invariant(PETIT_NV_NATIVE_MOE_INVARIANT_ARGS) {
+    const at::ScalarType st = bf16 ? at::kBFloat16 : at::kHalf;
+    TORCH_CHECK(act_format == 8 || act_format == 6 || act_format == 4, "act_format must be 8, 6 or 4");
+    TORCH_CHECK(n > 0 && k > 0 && k % 256 == 0, "size_n and size_k must be positive, size_k % 256 == 0");
+    check_expert_operands(false, true, A, images, nullptr, gs, off, e, n, k);
+    TORCH_CHECK(m >= 0 && (quantized ? A.scalar_type() == at::kByte && A.numel() == m * (k / 8 * act_format) + m * (k / 32) && !a_idx.has_value()
+                                     : A.scalar_type() == st && A.numel() % k == 0),
+                "A must be a contiguous [a_rows, size_k] tensor, or the quantised bytes of the size_m grouped rows without an a_row_index");
+    check_row_indices(a_idx, c_idx, A, m);
+    TORCH_CHECK(activation >= 0 && activation <= 2 && (!activation || n % 64 == 0), "activation must be 0, 1 or 2; gated forms need size_n % 64 == 0");
+    check_bias(bias, A, st, e * n, "bias must be a contiguous [num_experts, size_n] tensor of A's dtype on A's device");
+    const InvariantRouting r{off, e, a_idx, c_idx, quantized ? m : A.numel() / k, c_rows, nullptr};
+    return invariant_call("mul_nvfp4_native_moe_invariant", false, act_format, quantized, st, A, images, images, (const float *)gs.data_ptr(), m, n, k,
+                          bias, activation, &r);
 }
 
 // device routing (petit_moe_align / petit_moe_combine); the same checks and texts as petit_kernel/ops.py
@@ -938,6 +989,12 @@ void mul_a16_moe_invariant_out_meta(const at::Tensor &, PETIT_MOE_INVARIANT_ARGS
 at::Tensor mul_mxfp4_native_moe_invariant_meta(PETIT_NATIVE_MOE_INVARIANT_ARGS) {
     return at::empty({c_rows < 0 ? m : c_rows, activation ? n / 2 : n}, A.options().dtype(bf16 ? at::kBFloat16 : at::kHalf));
 }
+at::Tensor mul_nvfp4_native_invariant_meta(PETIT_NV_NATIVE_INVARIANT_ARGS) {
+    return at::empty({size_m, activation ? size_n / 2 : size_n}, A.options().dtype(bf16 ? at::kBFloat16 : at::kHalf));
+}
+at::Tensor mul_nvfp4_native_moe_invariant_meta(PETIT_NV_NATIVE_MOE_INVARIANT_ARGS) {
+    return at::empty({c_rows < 0 ? m : c_rows, activation ? n / 2 : n}, A.options().dtype(bf16 ? at::kBFloat16 : at::kHalf));
+}
 at::Tensor mul_nvfp4_native_transient_meta(PETIT_NV_TRANSIENT_ARGS) {
     return native_output(A, native_moe_dtype(A, a_format, a_type), size_m, size_m, activation ? size_n / 2 : size_n, out_format);
 }
@@ -1064,6 +1121,11 @@ TORCH_LIBRARY(petit_kernel, m) {
     m.def("mul_mxfp4_native_moe_invariant(Tensor A, Tensor B, Tensor s, Tensor global_scales, Tensor expert_offsets, int size_m, int size_n, "
           "int size_k, int num_experts, Tensor? a_row_index, Tensor? c_row_index, int c_rows, int act_format, bool quantized, bool bf16, "
           "Tensor? bias=None, int activation=0) -> Tensor");
+    m.def("mul_nvfp4_native_invariant(Tensor A, Tensor image, Tensor? global_scale, int size_m, int size_n, int size_k, int act_format, "
+          "bool quantized, bool bf16, Tensor? bias=None, int activation=0) -> Tensor");
+    m.def("mul_nvfp4_native_moe_invariant(Tensor A, Tensor images, Tensor global_scales, Tensor expert_offsets, int size_m, int size_n, "
+          "int size_k, int num_experts, Tensor? a_row_index, Tensor? c_row_index, int c_rows, int act_format, bool quantized, bool bf16, "
+          "Tensor? bias=None, int activation=0) -> Tensor");
     m.def("mul_nvfp4_a16_moe_invariant(" PETIT_MOE_INVARIANT_SCHEMA ") -> Tensor");
     m.def("mul_mxfp4_a16_moe_invariant(" PETIT_MOE_INVARIANT_SCHEMA ") -> Tensor");
     m.def("mul_nvfp4_a16_moe_invariant_out(Tensor(a!) out, " PETIT_MOE_INVARIANT_SCHEMA ") -> ()");
@@ -1090,6 +1152,8 @@ TORCH_LIBRARY(petit_kernel, m) {
     m.impl("mul_nvfp4_a16_moe_indexed_out", &mul_nvfp4_a16_moe_indexed_out); \
     m.impl("mul_mxfp4_a16_moe_indexed_out", &mul_mxfp4_a16_moe_indexed_out); \
     m.impl("mul_mxfp4_native_moe_invariant", &mul_mxfp4_native_moe_invariant); \
+    m.impl("mul_nvfp4_native_invariant", &mul_nvfp4_native_invariant); \
+    m.impl("mul_nvfp4_native_moe_invariant", &mul_nvfp4_native_moe_invariant); \
     m.impl("mul_nvfp4_a16_moe_invariant", &mul_nvfp4_a16_moe_invariant); \
     m.impl("mul_mxfp4_a16_moe_invariant", &mul_mxfp4_a16_moe_invariant); \
     m.impl("mul_nvfp4_a16_moe_invariant_out", &mul_nvfp4_a16_moe_invariant_out); \
@@ -1127,6 +1191,8 @@ TORCH_LIBRARY_IMPL(petit_kernel, Meta, m) {
     m.impl("mul_nvfp4_a16_moe_indexed_out", &mul_a16_moe_indexed_out_meta);
     m.impl("mul_mxfp4_a16_moe_indexed_out", &mul_a16_moe_indexed_out_meta);
     m.impl("mul_mxfp4_native_moe_invariant", &mul_mxfp4_native_moe_invariant_meta);
+    m.impl("mul_nvfp4_native_invariant", &mul_nvfp4_native_invariant_meta);
+    m.impl("mul_nvfp4_native_moe_invariant", &mul_nvfp4_native_moe_invariant_meta);
     m.impl("mul_nvfp4_a16_moe_invariant", &mul_a16_moe_invariant_meta);
     m.impl("mul_mxfp4_a16_moe_invariant", &mul_a16_moe_invariant_meta);
     m.impl("mul_nvfp4_a16_moe_invariant_out", &mul_a16_moe_invariant_out_meta);

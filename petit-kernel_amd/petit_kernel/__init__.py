@@ -196,6 +196,23 @@ def native_moe_invariant_workspace_bytes(num_experts: int, size_m: int, size_n: 
     return ops.native_moe_invariant_workspace_bytes(num_experts, size_m, size_n, size_k, dtype, fmt, quantized)
 
 
+def mul_nvfp4_native_invariant(a, image: torch.Tensor, global_scale: torch.Tensor, size_m: int, size_n: int, size_k: int, fmt: str = "mxfp8",
+                               bias: torch.Tensor = None, activation: str = None) -> torch.Tensor:
+    # mul_mxfp4_native_invariant for NVFP4 weights on their native image (nvfp4_native_image; include/petit_amd.h "Batch-invariant native-class
+    # GEMM and MoE launch on NVFP4 images"): the same bits for a row alone, in any batch and at any position.  native_invariant_slabs and
+    # native_invariant_workspace_bytes answer for it too.  Opt-in (profiles/nvfp4_native_invariant.md), no solution_id.
+    return _impl.mul_nvfp4_native_invariant(a, image, global_scale, size_m, size_n, size_k, fmt, bias, activation)
+
+
+def mul_nvfp4_native_moe_invariant(a, images: torch.Tensor, global_scales: torch.Tensor, expert_offsets: torch.Tensor, size_m: int, size_n: int,
+                                   size_k: int, num_experts: int, a_row_index: torch.Tensor = None, c_row_index: torch.Tensor = None,
+                                   c_rows: int = None, fmt: str = "mxfp8", bias: torch.Tensor = None, activation: str = None) -> torch.Tensor:
+    # the routed-expert launch of the same on the experts' images (nvfp4_native_images): every written row equals, bit for bit,
+    # mul_nvfp4_native_invariant(size_m=1) on its row with its expert's image, global scale and bias
+    return _impl.mul_nvfp4_native_moe_invariant(a, images, global_scales, expert_offsets, size_m, size_n, size_k, num_experts, a_row_index,
+                                                c_row_index, c_rows, fmt, bias, activation)
+
+
 def moe_invariant_form(size_m: int, num_experts: int) -> int:
     # the form a batch-invariant MoE call gets: 1 split (slabs in scratch, two launches), 0 whole -- a function of these two arguments alone
     return ops.moe_invariant_form(size_m, num_experts)
@@ -414,6 +431,8 @@ __all__ = [
     "moe_invariant_form",
     "moe_invariant_workspace_bytes",
     "mul_mxfp4_native_moe_invariant",
+    "mul_nvfp4_native_invariant",
+    "mul_nvfp4_native_moe_invariant",
     "native_moe_invariant_form",
     "native_moe_invariant_workspace_bytes",
     "get_fp4_solutions",

@@ -167,6 +167,12 @@ _SIGNATURES = {
     "petit_gemm_mxfp4_native_moe_invariant": (C.c_int, [C.c_void_p] * 6 + [C.c_uint] * 4 + [C.c_void_p, C.c_uint, C.c_void_p, C.c_uint] +
                                               [C.POINTER(SolutionHints), C.c_int, C.c_int, C.POINTER(Epilogue), C.c_void_p, C.c_void_p]),
     "petit_gemm_native_moe_invariant_host": (C.c_int, [C.c_void_p] * 7 + [C.c_uint] * 4 + [C.c_void_p, C.c_uint, C.c_int, C.c_int]),
+    "petit_gemm_nvfp4_native_invariant": (C.c_int, [C.c_void_p] * 4 + [C.c_uint] * 3 + [C.POINTER(SolutionHints), C.c_int, C.c_int,
+                                                    C.POINTER(Epilogue), C.c_void_p, C.c_void_p]),
+    "petit_gemm_nvfp4_native_moe_invariant": (C.c_int, [C.c_void_p] * 5 + [C.c_uint] * 4 + [C.c_void_p, C.c_uint, C.c_void_p, C.c_uint] +
+                                              [C.POINTER(SolutionHints), C.c_int, C.c_int, C.POINTER(Epilogue), C.c_void_p, C.c_void_p]),
+    "petit_gemm_nvfp4_native_invariant_host": (C.c_int, [C.c_void_p] * 5 + [C.c_uint] * 3 + [C.c_int, C.c_int]),
+    "petit_gemm_nvfp4_native_moe_invariant_host": (C.c_int, [C.c_void_p] * 6 + [C.c_uint] * 4 + [C.c_void_p, C.c_uint, C.c_int, C.c_int]),
     "petit_gemm_mxfp4_native": (C.c_int, [C.c_void_p] * 5 + [C.c_uint] * 3 + [C.POINTER(SolutionHints), C.c_uint64, C.POINTER(Epilogue),
                                           C.POINTER(NativeArgs), C.c_void_p, C.c_uint64, C.c_void_p]),
     "petit_nvfp4_native_image_bytes": (C.c_uint64, [C.c_uint, C.c_uint]),

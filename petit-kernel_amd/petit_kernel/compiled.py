@@ -167,6 +167,21 @@ def mul_mxfp4_a16_moe_invariant(A, B, s, global_scales, expert_offsets, size_m, 
                               c_rows, bias, activation, out)
 
 
+def mul_nvfp4_native_invariant(A, image, global_scale, size_m, size_n, size_k, fmt="mxfp8", bias=None, activation=None):
+    a, dtype, quantized, act = _check_invariant(A, image, None, global_scale, size_m, size_n, size_k, bias, activation, "nv", fmt)[:4]
+    return torch.ops.petit_kernel.mul_nvfp4_native_invariant(a, image, global_scale, int(size_m), int(size_n), int(size_k), _QFORMATS[fmt],
+                                                             bool(quantized), dtype == torch.bfloat16, bias, act)
+
+
+def mul_nvfp4_native_moe_invariant(A, images, global_scales, expert_offsets, size_m, size_n, size_k, num_experts, a_row_index=None,
+                                   c_row_index=None, c_rows=None, fmt="mxfp8", bias=None, activation=None):
+    a, dtype, quantized, act, E, _, c_rows = _check_invariant(A, images, None, global_scales, size_m, size_n, size_k, bias, activation, "nv", fmt,
+                                                              (expert_offsets, num_experts, a_row_index, c_row_index, c_rows, None))
+    return torch.ops.petit_kernel.mul_nvfp4_native_moe_invariant(a, images, global_scales, expert_offsets, int(size_m), int(size_n), int(size_k), E,
+                                                                 a_row_index, c_row_index, int(c_rows), _QFORMATS[fmt], bool(quantized),
+                                                                 dtype == torch.bfloat16, bias, act)
+
+
 def mul_mxfp4_native_moe_invariant(A, B, s, global_scales, expert_offsets, size_m, size_n, size_k, num_experts, a_row_index=None,
                                    c_row_index=None, c_rows=None, fmt="mxfp8", bias=None, activation=None):
     a, dtype, quantized, act, E, _, c_rows = _check_invariant(A, B, s, global_scales, size_m, size_n, size_k, bias, activation, "mx", fmt,

@@ -355,11 +355,11 @@ def mul_mxfp4_a16(A, B, s, global_scale, size_m, size_n, size_k, solution_id, bi
 
 
 # --- the batch-invariant GEMM family (include/petit_amd.h "Batch-invariant GEMM", "Batch-invariant MoE launch" and their two "... on the native
-# class" sections; no counterpart in the reference): one check and one driver for the four entries ------------------------------------------
+# class" sections, and "... on NVFP4 images"; no counterpart in the reference): one check and one driver for all the entries ---------------
 
 def _invariant_name(kind: str, native: bool, moe: bool) -> str:
     if native:
-        return "mul_mxfp4_native_moe_invariant" if moe else "mul_mxfp4_native_invariant"
+        return ("mul_%sfp4_native_moe_invariant" if moe else "mul_%sfp4_native_invariant") % kind
     return ("mul_%sfp4_a16_moe_invariant" if moe else "mul_%sfp4_a16_invariant") % kind
 
 
@@ -368,8 +368,9 @@ _INVARIANT_BIAS_TEXT = {False: "bias must be a contiguous [size_n] tensor of A's
 
 
 def _check_invariant(A, B, s, global_scale, size_m, size_n, size_k, bias, activation, kind="mx", fmt=None, experts=None):
-    """The argument checks of the four batch-invariant entries, stated here for both operator layers.  kind: the weight format, 'nv' / 'mx';
-    fmt: the native class's activation format (None: the exact class); experts: (expert_offsets, num_experts, a_row_index, c_row_index,
+    """The argument checks of the batch-invariant entries, stated here for both operator layers.  kind: the weight format, 'nv' / 'mx';
+    fmt: the native class's activation format (None: the exact class), where kind 'nv' means B is the native image (nvfp4_native_image; a MoE
+    call: num_experts images back to back) and s is None; experts: (expert_offsets, num_experts, a_row_index, c_row_index,
     c_rows, out) of a MoE call, whose global_scale is the [num_experts] tensor (None: a dense call).
     -> (activation tensor, 16-bit dtype, a_is_quantized, activation code, E, a_rows, c_rows), the last three None for a dense call.
     Value checks come first and device checks last, so that the texts can be read without a GPU.  The order within an entry decides which
@@ -424,10 +425,16 @@ def _check_invariant(A, B, s, global_scale, size_m, size_n, size_k, bias, activa
     # weights and scales, of num_experts matrices back to back in a MoE call
     count, what = (E, "num_experts * ") if moe else (1, "")
     group = 16 if kind == "nv" else 32
-    _check(B.is_contiguous() and B.numel() * B.element_size() == count * size_n * size_k // 2,
-           f"B does not hold {what}size_n * size_k packed 4-bit weights")
-    _check(s.is_contiguous() and s.numel() * s.element_size() == count * size_n * size_k // group,
-           f"s does not hold {what}size_n * size_k / {group} scales")
+    if native and kind == "nv":
+        image_bytes = int(_lib.lib.petit_nvfp4_native_image_bytes(size_k, size_n))
+        _check(B.is_contiguous() and B.dtype == torch.uint8 and B.numel() == count * image_bytes and image_bytes > 0,
+               "images do not hold num_experts native images of size_n x size_k NVFP4 weights" if moe else
+               "image does not hold the native image of size_n x size_k NVFP4 weights")
+    else:
+        _check(B.is_contiguous() and B.numel() * B.element_size() == count * size_n * size_k // 2,
+               f"B does not hold {what}size_n * size_k packed 4-bit weights")
+        _check(s.is_contiguous() and s.numel() * s.element_size() == count * size_n * size_k // group,
+               f"s does not hold {what}size_n * size_k / {group} scales")
     if moe:
         _check(global_scale.dtype == torch.float32 and global_scale.is_contiguous() and global_scale.numel() == E,
                "global_scales must be a contiguous float32 [num_experts] tensor")
@@ -451,22 +458,25 @@ def _check_invariant(A, B, s, global_scale, size_m, size_n, size_k, bias, activa
     if bias is not None:
         _check(bias.dtype == dtype and bias.is_contiguous() and bias.numel() == count * size_n and bias.device == a.device, _INVARIANT_BIAS_TEXT[moe])
     dev = a.device
-    _check(a.is_cuda and B.is_cuda and s.is_cuda and (global_scale is None or global_scale.is_cuda) and (not moe or expert_offsets.is_cuda),
+    _check(a.is_cuda and B.is_cuda and (s is None or s.is_cuda) and (global_scale is None or global_scale.is_cuda) and (not moe or expert_offsets.is_cuda),
            "all tensors must be on GPU")
-    _check(B.device == dev and s.device == dev and (global_scale is None or global_scale.device == dev) and
+    _check(B.device == dev and (s is None or s.device == dev) and (global_scale is None or global_scale.device == dev) and
            (not moe or expert_offsets.device == dev), "all tensors must be on A's device")
     return a, dtype, int(quantized), act, E, a_rows, c_rows
 
 
 def _mul_invariant(A, B, s, global_scale, size_m, size_n, size_k, bias, activation, kind="mx", fmt=None, experts=None) -> torch.Tensor:
-    """One call of any of the four entries (the arguments of _check_invariant): output, hints, epilogue, workspace, the C call, the raise."""
+    """One call of any entry (the arguments of _check_invariant): output, hints, epilogue, workspace, the C call, the raise."""
     a, dtype, quantized, act, E, a_rows, c_rows = _check_invariant(A, B, s, global_scale, size_m, size_n, size_k, bias, activation, kind, fmt,
                                                                    experts)
     native, moe, shape = fmt is not None, experts is not None, (int(size_m), int(size_n), int(size_k))
     lib = _lib.lib  # (plain attribute reads: this is the per-call path of a decode step)
-    if native:
-        fn, ws_fn = ((lib.petit_gemm_mxfp4_native_moe_invariant, lib.petit_gemm_native_moe_invariant_workspace_bytes) if moe else
-                     (lib.petit_gemm_mxfp4_native_invariant, lib.petit_gemm_native_invariant_workspace_bytes))
+    if native:  # (the form constants are shared by the two weight formats: one pair of queries)
+        ws_fn = lib.petit_gemm_native_moe_invariant_workspace_bytes if moe else lib.petit_gemm_native_invariant_workspace_bytes
+        if kind == "nv":
+            fn = lib.petit_gemm_nvfp4_native_moe_invariant if moe else lib.petit_gemm_nvfp4_native_invariant
+        else:
+            fn = lib.petit_gemm_mxfp4_native_moe_invariant if moe else lib.petit_gemm_mxfp4_native_invariant
     elif moe:
         fn = lib.petit_gemm_fp4_fp16_moe_invariant if kind == "nv" else lib.petit_gemm_mxfp4_fp16_moe_invariant
         ws_fn = lib.petit_gemm_moe_invariant_workspace_bytes
@@ -481,8 +491,9 @@ def _mul_invariant(A, B, s, global_scale, size_m, size_n, size_k, bias, activati
     form = (_QFORMATS[fmt], quantized) if native else ()
     ws = _scratch(int(ws_fn(*((E,) if moe else ()), *shape, hints.a_type, *(form or (hints.b_type,)))), a.device)
     routing = ((_ptr(experts[0]), E), (_opt_ptr(experts[2]), a_rows, _opt_ptr(experts[3]), c_rows)) if moe else ((), ())
+    weights = (_ptr(B),) if s is None else (_ptr(B), _ptr(s))
     with torch.cuda.device(a.device):
-        err = fn(_ptr(out), _ptr(a), _ptr(B), _ptr(s), _opt_ptr(global_scale), *routing[0], *shape, *routing[1], C.byref(hints), *form, epi,
+        err = fn(_ptr(out), _ptr(a), *weights, _opt_ptr(global_scale), *routing[0], *shape, *routing[1], C.byref(hints), *form, epi,
                  _opt_ptr(ws), _stream(a))
     if err:
         where = "m=%d, n=%d, k=%d" % shape + (f", num_experts={E}, a_rows={a_rows}, c_rows={c_rows}" if moe else "")
@@ -894,6 +905,25 @@ def mul_nvfp4_native_transient(A, B, s, global_scale, size_m, size_n, size_k, so
     return _mul_native(_lib.lib.petit_gemm_nvfp4_native_transient, _lib.lib.petit_gemm_nvfp4_native_transient_workspace_bytes,
                        "mul_nvfp4_native_transient", "nv", A, (B, s), global_scale, size_m, size_n, size_k, solution_id, bias, activation,
                        out_quantized)
+
+
+# --- the batch-invariant native class on NVFP4 images (include/petit_amd.h "Batch-invariant native-class GEMM and MoE launch on NVFP4 images") ---
+
+def mul_nvfp4_native_invariant(A, image, global_scale, size_m, size_n, size_k, fmt="mxfp8", bias=None, activation=None) -> torch.Tensor:
+    """mul_mxfp4_native_invariant for NVFP4 weights (petit_gemm_nvfp4_native_invariant): `image` from nvfp4_native_image, global_scale NVFP4's
+    real one.  A row's result is a pure function of that row, the image, the scale and the bias -- never of size_m, of the row's position or
+    of the launch form; the accuracy class of mul_nvfp4_native.  The queries native_invariant_slabs / native_invariant_workspace_bytes
+    answer for this entry too.  Opt-in; no solution_id (profiles/nvfp4_native_invariant.md has the price)."""
+    return _mul_invariant(A, image, None, global_scale, size_m, size_n, size_k, bias, activation, "nv", fmt)
+
+
+def mul_nvfp4_native_moe_invariant(A, images, global_scales, expert_offsets, size_m, size_n, size_k, num_experts, a_row_index=None,
+                                   c_row_index=None, c_rows=None, fmt="mxfp8", bias=None, activation=None) -> torch.Tensor:
+    """mul_mxfp4_native_moe_invariant for NVFP4 experts (petit_gemm_nvfp4_native_moe_invariant): `images` from nvfp4_native_images (expert e's
+    image at byte e * nvfp4_native_image_bytes).  Every written row equals, bit for bit, mul_nvfp4_native_invariant(size_m=1) on its row and
+    its expert's image, global scale and bias."""
+    return _mul_invariant(A, images, None, global_scales, size_m, size_n, size_k, bias, activation, "nv", fmt,
+                          (expert_offsets, num_experts, a_row_index, c_row_index, c_rows, None))
 
 
 # --- grouped launch (include/petit_amd.h "Grouped launch"; no counterpart in the reference) ---------------------------------

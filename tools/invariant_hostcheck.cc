@@ -1,6 +1,6 @@
 // tools/invariant_hostcheck.cc -- a stand-alone program around the host side of the batch-invariant GEMM family
 // (petit-kernel_amd/csrc/gemm_invariant_host.h: the call description and its plan -- return codes, geometry, form rules, workspace and grid
-// arithmetic --, the pointer checks, the decode of "petit-qact/1" bytes and the four CPU twins), for sanitizer runs on the CPU:
+// arithmetic --, the pointer checks, the decode of "petit-qact/1" bytes and the CPU twins), for sanitizer runs on the CPU:
 //
 //     g++ -std=c++17 -O1 -g -fsanitize=address,undefined -fno-sanitize-recover=all -Ipetit-kernel_amd/csrc \
 //         tools/invariant_hostcheck.cc -o invariant_hostcheck && ./invariant_hostcheck
@@ -12,6 +12,7 @@
 //   MoE, both classes: random experts under well-formed and malformed offsets, gathers and scatters that go out of range, poisoned outputs;
 //     every row against the dense twin on that row alone and its owner (the clamp rule, restated here; the native row's image copied out here
 //     by the layout notes, not by the header's own helper).
+//   the native entries on NVFP4 images: the same, on "petit-cdna4-nv6/1" images written element by element from the layout notes of layout.h.
 //   then every refusal, the form rules, the workspace arithmetic written out by hand, and the plan's grids against literals.
 // Exit status 0 and "ok" when everything holds.
 #include <algorithm>
@@ -293,14 +294,12 @@ static void put_element(std::vector<uint8_t> &qa, unsigned m, unsigned k, int fm
     }
 }
 
-static void run_native_pair(int a_type, int fmt, unsigned m, unsigned n, unsigned k, unsigned seed) {
-    std::mt19937 rng(seed);
-    std::vector<uint32_t> pw;
-    std::vector<uint8_t> ps;
-    std::vector<double> w, a64((size_t)m * k);
-    fill_exact_weights(rng, n, k, true, 126, pw, ps, w);
+// exact quantised activations: the m-row image, its values, and every row as an image of its own
+static void fill_exact_qact(std::mt19937 &rng, unsigned m, unsigned k, int fmt, std::vector<uint8_t> &qa, std::vector<double> &a64,
+                            std::vector<std::vector<uint8_t>> &alone) {
+    a64.assign((size_t)m * k, 0.0);
     static const int vals[11] = {0, 1, -1, 2, -2, 3, -3, 4, -4, 6, -6};
-    std::vector<uint8_t> qa((size_t)qact_bytes(m, k, fmt), 0u);
+    qa.assign((size_t)qact_bytes(m, k, fmt), 0u);
     for (unsigned row = 0; row < m; ++row)
         for (unsigned blk = 0; blk < k / 32; ++blk) {
             const unsigned sbyte = 125 + rng() % 5;
@@ -318,7 +317,7 @@ static void run_native_pair(int a_type, int fmt, unsigned m, unsigned n, unsigne
             EXPECT((double)qact_element(qa.data(), m, k, fmt, row, kk) * e8m0_f64(qact_scale_byte(qa.data(), m, k, fmt, row, kk / 32)) ==
                    a64[(size_t)row * k + kk]);
     // a row alone is an image of its own (m = 1): the same elements at other addresses
-    std::vector<std::vector<uint8_t>> alone(m, std::vector<uint8_t>((size_t)qact_bytes(1, k, fmt), 0u));
+    alone.assign(m, std::vector<uint8_t>((size_t)qact_bytes(1, k, fmt), 0u));
     for (unsigned row = 0; row < m; ++row)
         for (unsigned blk = 0; blk < k / 32; ++blk) {
             alone[row].at((size_t)(k / 8 * (unsigned)fmt) + (size_t)(blk / 4) * 4 + blk % 4) = (uint8_t)qact_scale_byte(qa.data(), m, k, fmt, row, blk);
@@ -328,6 +327,16 @@ static void run_native_pair(int a_type, int fmt, unsigned m, unsigned n, unsigne
                 put_element(alone[row], 1, k, fmt, 0, kk, code_of(fmt, (int)std::lround(a64[(size_t)row * k + kk] / scale)));
             }
         }
+}
+
+static void run_native_pair(int a_type, int fmt, unsigned m, unsigned n, unsigned k, unsigned seed) {
+    std::mt19937 rng(seed);
+    std::vector<uint32_t> pw;
+    std::vector<uint8_t> ps, qa;
+    std::vector<double> w, a64;
+    std::vector<std::vector<uint8_t>> alone;
+    fill_exact_weights(rng, n, k, true, 126, pw, ps, w);
+    fill_exact_qact(rng, m, k, fmt, qa, a64, alone);
     check_exact_problem(rng, m, n, k, a_type == kTypeBf16, a64, w, [&](uint16_t *c, int row, const float *gs, const uint16_t *bias) {
         return row < 0 ? native_gemm_host(c, qa.data(), pw.data(), ps.data(), gs, bias, m, n, k, a_type, fmt)
                        : native_gemm_host(c, alone[row].data(), pw.data(), ps.data(), gs, bias, 1, n, k, a_type, fmt);
@@ -401,6 +410,94 @@ static void run_native_moe_pair(int a_type, int fmt, unsigned E, unsigned m, uns
                 }
                 EXPECT(c == want); // rows of an expert: the dense twin's bits; every other row: the poison
             }
+}
+
+// ---- the native entries on NVFP4 images ------------------------------------------------------------------------------------------------------
+
+// writes weight (row, kk) of a "petit-cdna4-nv6/1" image and the E8M0 byte of its block, stated from the layout notes of layout.h: lane
+// 32 h + r of block (row / 32, kt) holds row r; its 24 bytes of instruction q are 16 in plane q and 8 at [q] of its unit of plane 2, element e at
+// bits [6 e, 6 e + 6); the scale bytes follow all the elements, [N / 32][K / (128 KS)][64 lanes][2][KS]
+static void put_nv6(std::vector<uint8_t> &img, unsigned n, unsigned k, unsigned row, unsigned kk, unsigned code, unsigned sbyte) {
+    const unsigned blk = kk / 32, e = kk % 32, kt = blk / 4, q = (blk % 4) >> 1, h = blk & 1u, lane = h * 32 + row % 32;
+    const size_t tile = ((size_t)(row / 32) * (k / 128) + kt) * 3072;
+    auto at = [&](unsigned j) -> uint8_t & { return j < 16 ? img.at(tile + q * 1024 + lane * 16 + j) : img.at(tile + 2048 + lane * 16 + q * 8 + j - 16); };
+    const unsigned bit = 6 * e;
+    at(bit / 8) |= (uint8_t)(code << (bit % 8));
+    if (bit % 8 > 2)
+        at(bit / 8 + 1) |= (uint8_t)(code >> (8 - bit % 8));
+    const unsigned ks = k % 1024 == 0 ? 8 : k % 512 == 0 ? 4 : 2, sp = kt / ks, t = kt % ks;
+    img.at((size_t)(n / 32) * (k / 128) * 3072 + (((size_t)(row / 32) * (k / (128 * ks)) + sp) * 64 + lane) * (2 * ks) + q * ks + t) = (uint8_t)sbyte;
+}
+
+static void run_nv_native_pair(int a_type, int fmt, unsigned m, unsigned n, unsigned k, unsigned seed) {
+    std::mt19937 rng(seed);
+    std::vector<uint8_t> image(nv6_image_bytes(n, k), 0u), qa;
+    std::vector<double> w((size_t)n * k), a64;
+    std::vector<std::vector<uint8_t>> alone;
+    static const int vals[11] = {0, 1, -1, 2, -2, 3, -3, 4, -4, 6, -6};
+    for (unsigned row = 0; row < n; ++row)
+        for (unsigned blk = 0; blk < k / 32; ++blk) {
+            const unsigned sbyte = 126 + rng() % 3;
+            for (unsigned i = 0; i < 32; ++i) {
+                const int v = vals[rng() % 11];
+                put_nv6(image, n, k, row, 32 * blk + i, code_of(6, v), sbyte);
+                w[(size_t)row * k + 32 * blk + i] = v * std::ldexp(1.0, (int)sbyte - 127);
+            }
+        }
+    for (unsigned row = 0; row < n; ++row) // every weight reads back through the header's decode
+        for (unsigned kk = 0; kk < k; ++kk)
+            EXPECT(nv6_weight_f64(image.data(), n, k, row, kk) == w[(size_t)row * k + kk]);
+    fill_exact_qact(rng, m, k, fmt, qa, a64, alone);
+    check_exact_problem(rng, m, n, k, a_type == kTypeBf16, a64, w, [&](uint16_t *c, int row, const float *gs, const uint16_t *bias) {
+        return row < 0 ? nv_native_gemm_host(c, qa.data(), image.data(), gs, bias, m, n, k, a_type, fmt)
+                       : nv_native_gemm_host(c, alone[row].data(), image.data(), gs, bias, 1, n, k, a_type, fmt);
+    });
+}
+
+static void run_nv_native_moe_pair(int a_type, int fmt, unsigned E, unsigned m, unsigned n, unsigned k, unsigned seed) {
+    const bool bf16 = a_type == kTypeBf16;
+    std::mt19937 rng(seed);
+    const size_t per = nv6_image_bytes(n, k), elems = nv6_elem_bytes(n, k);
+    std::vector<uint8_t> images(E * per);
+    for (size_t i = 0; i < images.size(); ++i) // any element bits; scale bytes around 2^0
+        images[i] = i % per < elems ? (uint8_t)rng() : (uint8_t)(124 + rng() % 7);
+    std::vector<uint8_t> qa((size_t)qact_bytes(m, k, fmt));
+    const size_t scale_at = (size_t)m * (k / 8 * (unsigned)fmt);
+    for (size_t i = 0; i < qa.size(); ++i)
+        qa[i] = i < scale_at ? (uint8_t)((rng() & 0xffu) % 0x7fu | (rng() & 0x80u)) : (uint8_t)(122 + rng() % 9);
+    std::vector<float> gs(E);
+    std::vector<uint16_t> bias((size_t)E * n);
+    for (auto &g : gs)
+        g = 0.5f + (float)(rng() % 64) / 128.f;
+    for (auto &b : bias)
+        b = (uint16_t)f32_h16(bf16, (float)((int)(rng() % 33) - 16) * 0.25f);
+    const unsigned c_rows = m + 2;
+    std::vector<int32_t> c_idx(m);
+    for (unsigned r = 0; r < m; ++r)
+        c_idx[r] = (int32_t)((r * 7 + 3) % c_rows);
+    if (m > 3)
+        c_idx[1] = (int32_t)c_rows, c_idx[3] = -2; // outside [0, c_rows): stores nothing
+    for (const auto &off : routings(E, m))
+        for (int with_idx = 0; with_idx < 2; ++with_idx) {
+            const unsigned rows_out = with_idx ? c_rows : m;
+            std::vector<uint16_t> c((size_t)rows_out * n, 0x7fc1u), want((size_t)rows_out * n, 0x7fc1u), c1(n);
+            EXPECT(nv_native_moe_gemm_host(c.data(), qa.data(), images.data(), gs.data(), bias.data(), off.data(), E, m, n, k,
+                                           with_idx ? c_idx.data() : nullptr, rows_out, a_type, fmt) == kRcOk);
+            const std::vector<int> own = owners(off, m);
+            for (unsigned r = 0; r < m; ++r) {
+                if (own[r] < 0)
+                    continue;
+                const unsigned e = (unsigned)own[r];
+                const std::vector<uint8_t> img = row_image(qa, m, k, fmt, r);
+                EXPECT(nv_native_gemm_host(c1.data(), img.data(), images.data() + e * per, &gs[e], bias.data() + (size_t)e * n, 1, n, k, a_type,
+                                           fmt) == kRcOk);
+                const unsigned dst = with_idx ? (unsigned)c_idx[r] : r;
+                if (dst < rows_out)
+                    for (unsigned col = 0; col < n; ++col)
+                        want[(size_t)dst * n + col] = c1[col];
+            }
+            EXPECT(c == want);
+        }
 }
 
 // ---- the cases -------------------------------------------------------------------------------------------------------------------------------
@@ -654,11 +751,78 @@ static void check_native_moe() {
     EXPECT(native_moe_gemm_host(nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, 3, 0, 32, 256, nullptr, 0, kTypeBf16, 8) == kRcOk);
 }
 
+static void check_nv_native() {
+    alignas(256) static char buf[512];
+    const void *ok = buf, *odd = buf + 16;
+    auto nv_plan = [&](unsigned m, unsigned n, unsigned k, int a_type, int fmt, int quantized, int act = 0, const void *image = nullptr) {
+        return plan(native_call(m, n, k, a_type, fmt, quantized, act, kTypeNv, image));
+    };
+    auto nv_moe_plan = [&](unsigned E, unsigned m, unsigned n, unsigned k, int a_type, int fmt, int quantized, int act = 0,
+                           const void *images = nullptr) {
+        return plan(moe_call(native_call(m, n, k, a_type, fmt, quantized, act, kTypeNv, images), E, false, m, false, m));
+    };
+    for (int a_type : {kTypeBf16, kTypeFp16})
+        for (int fmt : {8, 6, 4}) {
+            run_nv_native_pair(a_type, fmt, 2, 64, 1024, 1); // spans of 8 k-tiles
+            run_nv_native_pair(a_type, fmt, 2, 96, 768, 2);  // spans of 2, three blocks of 32 rows, three slices
+        }
+    run_nv_native_pair(kTypeBf16, 8, 1, 32, 4352, 3); // L = 512, a last slice half as long
+    for (int fmt : {8, 6, 4}) {
+        run_nv_native_moe_pair(kTypeBf16, fmt, 4, 10, 64, 1024, 4);
+        run_nv_native_moe_pair(kTypeFp16, fmt, 3, 7, 96, 768, 5);
+    }
+    // the plans are the MXFP4 native entries': the same geometry, forms, workspace and grids (a block of 32 weight rows for a pair of n-tiles)
+    for (unsigned m : {1u, 33u, kNativeSplitMaxM, kNativeSplitMaxM + 1, 200u})
+        for (int fmt : {8, 6, 4})
+            for (int q : {0, 1}) {
+                const Plan a = nv_plan(m, 4096, 2304, kTypeBf16, fmt, q), b = native_plan(m, 4096, 2304, kTypeBf16, fmt, q);
+                EXPECT(a.rc == kRcOk && a.split == b.split && a.slices == b.slices && a.slice_k == b.slice_k && a.workspace_bytes == b.workspace_bytes &&
+                       a.quant_bytes == b.quant_bytes && a.gemm.grid_x == b.gemm.grid_x && a.gemm.grid_y == b.gemm.grid_y &&
+                       a.gemm.grid_z == b.gemm.grid_z && a.fold.grid_x == b.fold.grid_x);
+            }
+    for (unsigned m : {1u, 8u, 9u, 70u})
+        for (unsigned E : {1u, 4u, 16u}) {
+            const Plan a = nv_moe_plan(E, m, 128, 1536, kTypeFp16, 6, 0), b = native_moe_plan(E, m, 128, 1536, kTypeFp16, 6, 0);
+            EXPECT(a.rc == kRcOk && a.split == b.split && a.slices == b.slices && a.workspace_bytes == b.workspace_bytes &&
+                   a.gemm.grid_x == b.gemm.grid_x && a.fold.grid_x == b.fold.grid_x && a.gemm.nblocks == b.gemm.nblocks);
+        }
+    {
+        const Plan s = nv_plan(33, 4096, 2304, kTypeBf16, 8, 0), w = nv_plan(200, 4096, 2304, kTypeBf16, 8, 0), g = nv_plan(200, 192, 768, kTypeBf16, 6, 1, 2);
+        EXPECT(s.split && s.slices == 5 && s.gemm.grid_x == 32 && s.gemm.grid_y == 5 && s.gemm.grid_z == 2 && s.fold.grid_x == 132);
+        EXPECT(!w.split && w.gemm.grid_x == 16 && w.gemm.grid_y == 4 && w.gemm.grid_z == 1);
+        EXPECT(!g.split && g.gemm.grid_x == 1 && g.gemm.grid_y == 4);
+        EXPECT(s.workspace_bytes == s.quant_bytes + s.slab_bytes && s.slab_bytes == (5ull * 33 * 4096 * 4 + 255) / 256 * 256);
+        EXPECT(s.quant_bytes == (33ull * 2304 + 33ull * 72 + 255) / 256 * 256);
+    }
+    // refusals, in their order: the formats, the shape, the image's address, the quantiser's row limit
+    EXPECT(nv_plan(4, 32, 256, kTypeBf16, 8, 0).rc == kRcOk && nv_plan(0, 64, 256, kTypeFp16, 4, 1, 2).rc == kRcOk);
+    EXPECT(nv_plan(4, 32, 256, 3, 8, 0).rc == kRcBadArgument && nv_plan(4, 32, 256, kTypeBf16, 5, 0).rc == kRcBadArgument);
+    EXPECT(nv_plan(4, 48, 256, kTypeBf16, 5, 0, 0, odd).rc == kRcBadArgument && nv_plan(4, 32, 256, kTypeBf16, 8, 0, 3).rc == kRcBadArgument);
+    EXPECT(nv_plan(4, 48, 256, kTypeBf16, 8, 0).rc == kRcProblemShape && nv_plan(4, 16, 256, kTypeBf16, 8, 0).rc == kRcProblemShape);
+    EXPECT(nv_plan(4, 32, 128, kTypeBf16, 8, 0).rc == kRcProblemShape && nv_plan(4, 96, 256, kTypeBf16, 8, 0, 1).rc == kRcProblemShape);
+    EXPECT(nv_plan(4, 0, 256, kTypeBf16, 8, 0).rc == kRcProblemShape && nv_plan(kMaxRows, 32, 256, kTypeBf16, 8, 1).rc == kRcProblemShape);
+    EXPECT(nv_plan(4, 1u << 17, 1u << 15, kTypeBf16, 8, 1).rc == kRcOk);              // 3 * 2^30 element bytes
+    EXPECT(nv_plan(4, 1u << 18, 21760, kTypeBf16, 8, 1).rc == kRcOk);                 // the last k below the limit
+    EXPECT(nv_plan(4, 1u << 18, 22016, kTypeBf16, 8, 1).rc == kRcProblemShape);       // n * k * 3 / 4 >= 2^32
+    EXPECT(native_plan(4, 1u << 18, 22016, kTypeBf16, 8, 1).rc == kRcOk);             // (the raw MXFP4 entry has no such limit)
+    EXPECT(nv_plan(4, 32, 256, kTypeBf16, 8, 0, 0, ok).rc == kRcOk && nv_plan(4, 32, 256, kTypeBf16, 8, 0, 0, odd).rc == kRcProblemShape);
+    EXPECT(nv_plan(70000, 32, 256, kTypeBf16, 8, 0, 0, odd).rc == kRcProblemShape && nv_plan(70000, 48, 256, kTypeBf16, 8, 0).rc == kRcProblemShape);
+    EXPECT(nv_plan(70000, 32, 256, kTypeBf16, 8, 0, 0, ok).rc == kRcKernelShape && nv_plan(70000, 32, 256, kTypeBf16, 8, 1).rc == kRcOk);
+    EXPECT(native_plan(4, 32, 256, kTypeBf16, 8, 0).rc == kRcOk); // (an MXFP4 call never reads the address)
+    EXPECT(nv_moe_plan(3, 70000, 32, 256, kTypeFp16, 6, 0).rc == kRcOk && nv_moe_plan(3, 4, 32, 256, kTypeBf16, 8, 0, 0, odd).rc == kRcProblemShape);
+    EXPECT(nv_moe_plan(0, 4, 32, 256, kTypeBf16, 8, 0).rc == kRcProblemShape && nv_moe_plan(3, 4, 96, 256, kTypeBf16, 8, 0, 1).rc == kRcProblemShape);
+    EXPECT(nv_plan(4, 48, 256, kTypeBf16, 8, 0).workspace_bytes == 0 && nv_plan(0, 32, 256, kTypeBf16, 8, 0).workspace_bytes == 0);
+    EXPECT(nv_native_gemm_host(nullptr, ok, ok, nullptr, nullptr, 1, 32, 256, kTypeBf16, 8) == kRcProblemShape);
+    EXPECT(nv_native_gemm_host(nullptr, nullptr, nullptr, nullptr, nullptr, 0, 32, 256, kTypeBf16, 8) == kRcOk);
+    EXPECT(nv_native_moe_gemm_host(nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, 3, 0, 32, 256, nullptr, 0, kTypeBf16, 8) == kRcOk);
+}
+
 int main() {
     check_dense();
     check_moe();
     check_native();
     check_native_moe();
+    check_nv_native();
     std::printf(failures ? "%d check(s) failed\n" : "ok\n", failures);
     return failures ? 1 : 0;
 }
