@@ -387,7 +387,7 @@ int petit_gemm_mxfp4_native(void *c, const void *a, const unsigned *b, const uns
                             const petit_native_args *native, void *workspace, uint64_t workspace_bytes, void *stream);
 uint64_t petit_gemm_native_workspace_bytes(const petit_solution_hints *hints, unsigned m, unsigned n, unsigned k, uint64_t solution_id,
                                            const petit_epilogue *epilogue, const petit_native_args *native);
-/* 16-bit activations [m][k] (a_type PETIT_DTYPE_BF16 / _FP16) -> "petit-qact/1" bytes of `format` (8 / 4) in qa; k % 256 == 0,
+/* 16-bit activations [m][k] (a_type PETIT_DTYPE_BF16 / _FP16) -> "petit-qact/1" bytes of `format` (8 / 6 / 4) in qa; k % 256 == 0,
  * both pointers 16-byte aligned. */
 uint64_t petit_quantized_activation_bytes(unsigned m, unsigned k, int format);
 int petit_quantize_activations(void *qa, const void *a, unsigned m, unsigned k, int a_type, int format, void *stream);

@@ -240,7 +240,7 @@ int petit_gemm_fp4_fp16_grouped(const petit_group_member *members, unsigned coun
 }
 
 uint64_t petit_quantized_activation_bytes(unsigned m, unsigned k, int format) {
-    return format == 8 ? native32_ws_bytes<8>(m, k) : format == 6 ? native32_ws_bytes<6>(m, k) : format == 4 ? native32_ws_bytes<4>(m, k) : 0;
+    return format == 8 || format == 6 || format == 4 ? qact_bytes(m, k, format) : 0; // ("petit-qact/1": layout.h)
 }
 
 int petit_quantize_activations(void *qa, const void *a, unsigned m, unsigned k, int a_type, int format, void *stream) {

@@ -14,6 +14,7 @@
 #include <vector>
 
 #include "layout.h"
+#include "numfmt.h"
 
 namespace petit_amd {
 namespace invariant {
@@ -38,8 +39,7 @@ constexpr unsigned kMoeSplitMaxM = 8;       // ... and m <= this (also the cap o
 inline bool is_mx(int b_type) { return b_type == kTypeMx || b_type == kTypeMxF16Range; }
 inline bool format_ok(int act_format) { return act_format == 8 || act_format == 6 || act_format == 4; }
 inline uint64_t round256(uint64_t x) { return (x + 255) / 256 * 256; }
-// bytes of the "petit-qact/1" image of (m, k, format): elements, then one E8M0 byte per 32 k (native32_ws_bytes, gemm_native32.hpp)
-inline uint64_t qact_bytes(unsigned m, unsigned k, int act_format) { return (uint64_t)m * (k / 8 * (unsigned)act_format) + (uint64_t)m * (k / 32); }
+// (bytes of the "petit-qact/1" image of (m, k, format): qact_bytes, layout.h)
 
 // One call of any entry.  The exact class reads b_type (act_format and a_is_quantized are 0); the native class reads act_format and
 // a_is_quantized, and its b_type names the weight operand: kTypeMx, raw MXFP4 tensors, or kTypeNv, the "petit-cdna4-nv6/1" image(s) of NVFP4
@@ -214,68 +214,8 @@ inline int moe_pointers_rc(const void *c, const void *a, const void *b, const vo
     return pointers_rc(c, a, b, scales, bias, workspace, workspace_need);
 }
 
-// ---- number formats ------------------------------------------------------------------------------------------------------------------------
-
-inline float bits_f32(uint32_t u) {
-    float f;
-    memcpy(&f, &u, 4);
-    return f;
-}
-inline uint32_t f32_bits(float f) {
-    uint32_t u;
-    memcpy(&u, &f, 4);
-    return u;
-}
-inline float h16_f32(bool bf16, uint32_t h) {
-    if (bf16)
-        return bits_f32(h << 16);
-    const uint32_t sign = (h & 0x8000u) << 16, e = (h >> 10) & 31u, m = h & 0x3ffu;
-    if (e == 0)
-        return bits_f32(sign | f32_bits((float)m * (1.0f / 16777216.0f)));
-    return bits_f32(sign | (e == 31 ? 0x7f800000u : (e + 112u) << 23) | (m << 13));
-}
-inline uint32_t f32_h16(bool bf16, float x) { // round to nearest even
-    const uint32_t u = f32_bits(x);
-    if (bf16) {
-        if ((u & 0x7fffffffu) > 0x7f800000u)
-            return (u >> 16) | 0x40u;
-        return (u + 0x7fffu + ((u >> 16) & 1u)) >> 16;
-    }
-    const uint32_t sign = (u >> 16) & 0x8000u, a = u & 0x7fffffffu;
-    if (a > 0x7f800000u)
-        return sign | 0x7e00u;
-    if (a >= 0x477ff000u)
-        return sign | 0x7c00u;
-    if (a < 0x38800000u)
-        return sign | (f32_bits(bits_f32(a) * 16777216.0f + 8388608.0f) & 0x7fffffu);
-    const uint32_t r = a - 0x38000000u;
-    return sign | ((r + 0xfffu + ((r >> 13) & 1u)) >> 13);
-}
-inline float e2m1_f32(unsigned code) {
-    static const float mag[8] = {0.f, 0.5f, 1.f, 1.5f, 2.f, 3.f, 4.f, 6.f};
-    return (code & 8u) ? -mag[code & 7u] : mag[code & 7u];
-}
-inline float e4m3_f32(unsigned b) { // OCP e4m3 (fn): no infinities, 0x7f / 0xff are NaN
-    const unsigned e = (b >> 3) & 15u, m = b & 7u;
-    float v;
-    if (e == 0)
-        v = (float)m * (1.0f / 512.0f);
-    else if (e == 15 && m == 7)
-        v = bits_f32(0x7fc00000u);
-    else
-        v = bits_f32(((e + 120u) << 23) | (m << 20));
-    return (b & 0x80u) ? -v : v;
-}
-inline float e2m3_f32(unsigned c) { // sign, 2 exponent bits (bias 1), 3 mantissa bits; subnormal step 1/8
-    const unsigned e = (c >> 3) & 3u, m = c & 7u;
-    const float v = e == 0 ? (float)m * 0.125f : (1.0f + (float)m * 0.125f) * (float)(1u << (e - 1));
-    return (c & 32u) ? -v : v;
-}
-// 2^(b - 127), as the kernels decode it (the hardware convert): byte 0 is 2^-127, an fp32 subnormal -- not the 0.0 of `b << 23`, which is what
-// dequant.hip and the oracle restate from the reference --, byte 255 is `b << 23` = inf, whose product with any code or activation ends as NaN
-inline float e8m0_f32(unsigned b) { return bits_f32((b & 0xffu) ? (b & 0xffu) << 23 : 0x00400000u); }
-// the same as a double (exact for every byte)
-inline double e8m0_f64(unsigned b) { return (double)e8m0_f32(b); }
+// (number formats: numfmt.h.  The 16-bit results of this family round as the kernels' epilogues do, f32_h16_quiet_nan; e8m0_f32 reads byte 0 as
+// 2^-127, as the kernels do.)
 
 // the weight operand of the definition: fp4 x group scale, exact in the activation type for every (type, format) pair the entries accept
 inline float weight_value(const uint32_t *pw, const uint8_t *ps, bool mx, unsigned k_total, unsigned n, unsigned kk) {
@@ -286,24 +226,23 @@ inline float weight_value(const uint32_t *pw, const uint8_t *ps, bool mx, unsign
     return q * sc;
 }
 
-// ---- "petit-qact/1" (layouts: gemm_native32.hpp) -------------------------------------------------------------------------------------------
+// ---- "petit-qact/1" (layout.h) -----------------------------------------------------------------------------------------------------------------
 
 // element (row, kk) of the image, WITHOUT its block scale, and the block's E8M0 byte
 inline float qact_element(const uint8_t *qa, unsigned m, unsigned k, int act_format, unsigned row, unsigned kk) {
     const unsigned kt = kk / 128, b = (kk % 128) / 32, i = kk % 32;
-    const size_t tile_row = (size_t)kt * m + row;
+    const size_t tile_row = qact_tile_row(m, kt, row), row_b = qact_row_bytes(act_format);
     if (act_format == 8) {
         const unsigned col16 = (kk % 128) / 8, u16 = col16 >> 1, half = col16 & 1u;
-        const unsigned pos = (u16 & 4u) | ((u16 & 1u) << 1) | ((u16 >> 1) & 1u);
-        return e4m3_f32(qa[tile_row * 128 + pos * 16 + half * 8 + kk % 8]);
+        return e4m3_f32(qa[tile_row * row_b + qact_fp8_unit_pos(u16) * 16 + half * 8 + kk % 8]);
     }
     if (act_format == 4) {
-        const unsigned byte = qa[tile_row * 64 + 16 * b + i / 2];
+        const unsigned byte = qa[tile_row * row_b + 16 * b + i / 2];
         return e2m1_f32((byte >> (4 * (i & 1u))) & 15u);
     }
-    // MXFP6: the block's 24 bytes = 16 in the first image, 8 in the second (blocks 0, 2, 1, 3); element i at bits [6 i, 6 i + 6)
-    const uint8_t *const lo = qa + tile_row * 64 + 16 * b;
-    const uint8_t *const hi = qa + (size_t)m * (k / 2) + tile_row * 32 + 8 * ((b & 1u) * 2 + (b >> 1));
+    // MXFP6: the block's 24 bytes = 16 in the first image, 8 in the second; element i at bits [6 i, 6 i + 6)
+    const uint8_t *const lo = qa + tile_row * row_b + 16 * b;
+    const uint8_t *const hi = qa + qact_hi_offset(m, k) + tile_row * kQactHiRowBytes + 8 * qact_fp6_hi_slot(b);
     const unsigned bit = 6 * i;
     auto byte_at = [&](unsigned j) -> unsigned { return j < 16 ? lo[j] : hi[j - 16]; };
     unsigned v = byte_at(bit / 8) >> (bit % 8);
@@ -312,21 +251,21 @@ inline float qact_element(const uint8_t *qa, unsigned m, unsigned k, int act_for
     return e2m3_f32(v & 63u);
 }
 inline unsigned qact_scale_byte(const uint8_t *qa, unsigned m, unsigned k, int act_format, unsigned row, unsigned blk) {
-    return qa[(size_t)m * (k / 8 * (unsigned)act_format) + ((size_t)(blk / 4) * m + row) * 4 + blk % 4];
+    return qa[qact_elem_bytes(m, k, act_format) + qact_scale_dword(m, blk / 4, row) * kQactScaleRowBytes + blk % 4];
 }
 // rows [row0, row0 + rows) of the m-row image as an image of their own (k-tile-major: the addresses depend on the row count, the bytes of a
 // row do not)
 inline void qact_extract_rows(std::vector<uint8_t> &out, const uint8_t *qa, unsigned m, unsigned k, int act_format, unsigned row0, unsigned rows) {
-    const unsigned row_b = act_format == 8 ? 128u : 64u, ktiles = k / 128;
-    out.assign((size_t)qact_bytes(rows, k, act_format), 0);
-    const size_t src_scale = (size_t)m * (k / 8 * (unsigned)act_format), dst_scale = (size_t)rows * (k / 8 * (unsigned)act_format);
-    const size_t src_hi = (size_t)m * (k / 2), dst_hi = (size_t)rows * (k / 2);
+    const unsigned row_b = qact_row_bytes(act_format), ktiles = k / 128;
+    out.assign(qact_bytes(rows, k, act_format), 0);
+    const size_t src_scale = qact_elem_bytes(m, k, act_format), dst_scale = qact_elem_bytes(rows, k, act_format);
+    const size_t src_hi = qact_hi_offset(m, k), dst_hi = qact_hi_offset(rows, k);
     for (unsigned kt = 0; kt < ktiles; ++kt) {
-        const size_t src = (size_t)kt * m + row0, dst = (size_t)kt * rows;
+        const size_t src = qact_tile_row(m, kt, row0), dst = qact_tile_row(rows, kt, 0);
         memcpy(&out[dst * row_b], qa + src * row_b, (size_t)rows * row_b);
         if (act_format == 6)
-            memcpy(&out[dst_hi + dst * 32], qa + src_hi + src * 32, (size_t)rows * 32);
-        memcpy(&out[dst_scale + dst * 4], qa + src_scale + src * 4, (size_t)rows * 4);
+            memcpy(&out[dst_hi + dst * kQactHiRowBytes], qa + src_hi + src * kQactHiRowBytes, (size_t)rows * kQactHiRowBytes);
+        memcpy(&out[dst_scale + dst * kQactScaleRowBytes], qa + src_scale + src * kQactScaleRowBytes, (size_t)rows * kQactScaleRowBytes);
     }
 }
 
@@ -361,7 +300,7 @@ inline void sliced_sum_finish(void *c, const float *global_scale, const void *bi
             }
             if (bias)
                 y = y + h16_f32(bf16, b16[col]);
-            c16[(size_t)row * n + col] = (uint16_t)f32_h16(bf16, y);
+            c16[(size_t)row * n + col] = (uint16_t)f32_h16_quiet_nan(bf16, y);
         }
     }
 }

@@ -24,6 +24,7 @@
 #pragma once
 
 #include "gemm_tiled.hpp"
+#include "numfmt.h"
 
 namespace petit_amd {
 
@@ -81,9 +82,7 @@ __global__ __launch_bounds__(256) void quantize_act_kernel(const void *a, unsign
         amax = fmaxf(amax, __shfl_xor(amax, 1));
         amax = fmaxf(amax, __shfl_xor(amax, 2));
         // E8M0 scale 2^(E-7): the block maximum lands in [128, 256) <= 448 (e4m3 max)
-        const unsigned ebits = (__builtin_bit_cast(unsigned, amax) >> 23) & 0xffu;
-        unsigned sbyte = amax == 0.f ? 127u : (ebits > 7u ? ebits - 7u : 1u);
-        sbyte = sbyte > 254u ? 254u : sbyte;
+        const unsigned sbyte = act_scale_byte<8>(amax);
         const float inv = __builtin_bit_cast(float, (254u - sbyte) << 23); // 2^-(sbyte-127)
         int q0 = 0, q1 = 0;
         q0 = __builtin_amdgcn_cvt_pk_fp8_f32(v[0] * inv, v[1] * inv, q0, false);

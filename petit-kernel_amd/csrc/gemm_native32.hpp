@@ -27,6 +27,7 @@
 
 #include "gemm_native.hpp"
 #include "gemm_wide.hpp"
+#include "numfmt.h"
 
 // measurement-only builds (tools/ablate_native32.sh): 1 = no activation DMA, 2 = no W refills, 4 = fragments read once,
 // 8 = no MFMAs (operands kept alive), 16 = no output stores.  0 in every shipped library.
@@ -36,23 +37,8 @@
 
 namespace petit_amd {
 
-// Workspace layout, K-TILE MAJOR: qa[K/128][M][16 ACT] bytes, then qs[K/128][M][4] E8M0 bytes -- the activation tile of a
-// workgroup and k-tile (BM rows x 128 k) is ONE contiguous run, so every 1 KiB wave-load of the GEMM's direct-to-LDS staging
-// reads eight whole cache lines (with the row-major form qa[M][K ACT / 8] a wave-load touched 16 half lines 4 KiB apart, and
-// the activation DMA cost more than the weight stream: 8.9 vs 4.8 us of a 30.6 us launch at 8192^2, M = 512 --
-// tools/ablate_native32.sh).  Rows >= M of the last m-block read the next tile's rows (or zeros past the end): such rows
-// only feed output columns that are never stored.
-//   ACT = 8: per 128-k tile 128 bytes in the order [0-15][32-47][16-31][48-63][64-79][96-111][80-95][112-127] (16-k units),
-//            so that lane (m, h) finds its P1 operand at byte 32h and its P2 operand at byte 64 + 32h.
-//   ACT = 4: per 128-k tile 64 bytes, natural nibble order: P1 operand at byte 16h, P2 at 32 + 16h.
-//   ACT = 6 (MXFP6, e2m3 elements: the instruction still runs at the FP4 rate, the elements carry e4m3's three mantissa bits): a 32-k block
-//            is 24 bytes = the 6 operand registers of one lane (element i at bits [6 i, 6 i + 6), tools/probes/mfma32_fp6_probe.hip).  Stored as
-//            TWO images so that every access stays a 16-byte one: qa_lo[K/128][M][64] holds registers 0-3 of block b at byte 16 b (the FP4
-//            geometry), qa_hi[K/128][M][32] registers 4-5 of blocks 0, 2, 1, 3 in that order (lane (m, h) reads ONE 16-byte unit h and finds
-//            the tail of its P1 block in the first 8 bytes, of its P2 block in the last 8); then the scales as above.
-template <int ACT> __host__ __device__ inline size_t native32_ws_bytes(unsigned m, unsigned k) {
-    return (size_t)m * (k / 8 * ACT) + (size_t)m * (k / 32);
-}
+// The quantised activations ("petit-qact/1": elements k-tile major, MXFP6 as two images, then one E8M0 byte per 32 k) are laid out by
+// layout.h, which states every address and size below; the block-scale rule is act_scale_byte of numfmt.h.
 
 // The gathering form of the quantisers (the routed-expert layer, gemm_moe_native.hpp): layout row r from row idx[r] of a [a_rows][k] (a null
 // index: row r); an index outside [0, a_rows) quantises a zero row (scale byte 127, zero elements).  Its grid is xb * M workgroups along x (xb per
@@ -75,9 +61,8 @@ template <class AT, int ACT, class... Gather>
 __global__ __launch_bounds__(256) void quantize_act32_kernel(const void *a, unsigned char *ws, unsigned m, unsigned k, const Gather... gather) {
     // grid = (ceil(K / 8 / (4 * 256)), M): blockIdx.y is the row -- no division in the address arithmetic -- and a thread owns
     // four 8-element columns 256 apart, all four loads requested before the first is used
-    const unsigned row_bytes = k / 8 * ACT;
     unsigned char *qa = ws;
-    unsigned char *qs = ws + (size_t)m * row_bytes;
+    unsigned char *qs = ws + qact_elem_bytes(m, k, ACT);
     constexpr int kIlp = 4;
     const unsigned row = q_row(gather...), cols = k / 8, bx = q_bx(gather...);
     const unsigned src = q_src(row, gather...);
@@ -109,46 +94,7 @@ __global__ __launch_bounds__(256) void quantize_act32_kernel(const void *a, unsi
                 v[2 * d + 1] = (float)p[1];
             }
         }
-        float amax = 0.f;
-#pragma unroll
-        for (int i = 0; i < 8; ++i)
-            amax = fmaxf(amax, fabsf(v[i]));
-        amax = fmaxf(amax, __shfl_xor(amax, 1));
-        amax = fmaxf(amax, __shfl_xor(amax, 2));
-        // E8M0 scale 2^(E - emax_elem) with E the exponent of the block maximum (OCP MX): emax_elem = 7 for e4m3 as
-        // gemm_native.hpp uses it (maximum lands in [128, 256) <= 448), 2 for e2m1 (maximum in [4, 8), above 6 saturates)
-        constexpr unsigned kEmax = ACT == 8 ? 7u : 2u;
-        const unsigned ebits = (__builtin_bit_cast(unsigned, amax) >> 23) & 0xffu;
-        unsigned sbyte = amax == 0.f ? 127u : (ebits > kEmax ? ebits - kEmax : 1u);
-        sbyte = sbyte > 254u ? 254u : sbyte;
-        const unsigned kt = c8 / 16, col16 = c8 % 16;
-        if constexpr (ACT == 8) {
-            const float inv = __builtin_bit_cast(float, (254u - sbyte) << 23); // 2^-(sbyte-127)
-            int q0 = 0, q1 = 0;
-            q0 = __builtin_amdgcn_cvt_pk_fp8_f32(v[0] * inv, v[1] * inv, q0, false);
-            q0 = __builtin_amdgcn_cvt_pk_fp8_f32(v[2] * inv, v[3] * inv, q0, true);
-            q1 = __builtin_amdgcn_cvt_pk_fp8_f32(v[4] * inv, v[5] * inv, q1, false);
-            q1 = __builtin_amdgcn_cvt_pk_fp8_f32(v[6] * inv, v[7] * inv, q1, true);
-            const unsigned u16 = col16 >> 1, half = col16 & 1u;
-            const unsigned pos = (u16 & 4u) | ((u16 & 1u) << 1) | ((u16 >> 1) & 1u);
-            uint2 o;
-            o.x = (unsigned)q0, o.y = (unsigned)q1;
-            *reinterpret_cast<uint2 *>(qa + ((size_t)kt * m + row) * 128 + pos * 16 + half * 8) = o;
-        } else {
-            // hardware RNE conversion to e2m1 with saturation: dst nibbles = cvt(src / scale)
-            const float scale = __builtin_bit_cast(float, sbyte << 23); // 2^(sbyte-127)
-            unsigned q = 0;
-            q = __builtin_amdgcn_cvt_scalef32_pk_fp4_f32(q, v[0], v[1], scale, 0);
-            q = __builtin_amdgcn_cvt_scalef32_pk_fp4_f32(q, v[2], v[3], scale, 1);
-            q = __builtin_amdgcn_cvt_scalef32_pk_fp4_f32(q, v[4], v[5], scale, 2);
-            q = __builtin_amdgcn_cvt_scalef32_pk_fp4_f32(q, v[6], v[7], scale, 3);
-            *reinterpret_cast<unsigned *>(qa + ((size_t)kt * m + row) * 64 + col16 * 4) = q;
-        }
-        // the four scale bytes of a row's k-tile leave as ONE dword (byte stores are the slow path of the memory pipeline):
-        // the 16 lanes of a k-tile are consecutive, the first lane of each quad holds the quad's byte
-        const unsigned s1 = __shfl_down(sbyte, 4, 16), s2 = __shfl_down(sbyte, 8, 16), s3 = __shfl_down(sbyte, 12, 16);
-        if (col16 == 0)
-            *reinterpret_cast<unsigned *>(qs + ((size_t)kt * m + row) * 4) = sbyte | (s1 << 8) | (s2 << 16) | (s3 << 24);
+#include "qact_column.inc"
     }
 }
 
@@ -159,7 +105,8 @@ __global__ __launch_bounds__(256) void quantize_act32_fp6_kernel(const void *a, 
     const unsigned row = q_row(gather...), blocks = k / 32, blk = q_bx(gather...) * 256 + threadIdx.x;
     if (blk >= blocks) // (K / 32 is a multiple of 4: the lanes of a k-tile leave together)
         return;
-    unsigned char *const qa_lo = ws, *const qa_hi = ws + (size_t)m * (k / 2), *const qs = ws + (size_t)m * (k / 8 * 6);
+    constexpr bool BF16 = AT::kType == kDataTypeBf16;
+    unsigned char *const qa = ws, *const qa_hi = ws + qact_hi_offset(m, k), *const qs = ws + qact_elem_bytes(m, k, 6);
     const unsigned src_row = q_src(row, gather...);
     const bool valid = q_valid(src_row, gather...);
     const u32x4 *const src = reinterpret_cast<const u32x4 *>(a) + ((size_t)src_row * blocks + blk) * 4;
@@ -167,42 +114,7 @@ __global__ __launch_bounds__(256) void quantize_act32_fp6_kernel(const void *a, 
 #pragma unroll
     for (int j = 0; j < 4; ++j)
         raw[j] = valid ? src[j] : u32x4{0u, 0u, 0u, 0u};
-    // block maximum on the 16-bit patterns (sign cleared: bf16 and fp16 magnitudes order like their bit patterns), exponent from its f32 value
-    unsigned mx = 0;
-#pragma unroll
-    for (int j = 0; j < 4; ++j)
-#pragma unroll
-        for (int d = 0; d < 4; ++d) {
-            const unsigned w = raw[j][d] & 0x7fff7fffu;
-            const unsigned lo = w & 0xffffu, hi = w >> 16;
-            mx = mx > lo ? mx : lo;
-            mx = mx > hi ? mx : hi;
-        }
-    float amax;
-    if constexpr (AT::kType == kDataTypeBf16) {
-        amax = __builtin_bit_cast(float, mx << 16);
-    } else {
-        const unsigned short hb = (unsigned short)mx;
-        amax = (float)__builtin_bit_cast(_Float16, hb);
-    }
-    // OCP MX scale 2^(E - emax_elem), emax_elem = 2 for e2m3 (largest normal 7.5 = 1.875 x 2^2): the maximum lands in [4, 8), above 7.5 saturates
-    const unsigned ebits = (__builtin_bit_cast(unsigned, amax) >> 23) & 0xffu;
-    unsigned sbyte = amax == 0.f ? 127u : (ebits > 2u ? ebits - 2u : 1u);
-    sbyte = sbyte > 254u ? 254u : sbyte;
-    const float scale = __builtin_bit_cast(float, sbyte << 23);
-    const u32x16 packed = u32x16{raw[0][0], raw[0][1], raw[0][2], raw[0][3], raw[1][0], raw[1][1], raw[1][2], raw[1][3],
-                                 raw[2][0], raw[2][1], raw[2][2], raw[2][3], raw[3][0], raw[3][1], raw[3][2], raw[3][3]};
-    const u32x6 q = cvt_pk32_fp6_16bit<AT::kType == kDataTypeBf16>(packed, scale); // (early-clobber form: device_common.hpp)
-    const unsigned kt = blk / 4, b = blk % 4;
-    const size_t tile_row = (size_t)kt * m + row;
-    *reinterpret_cast<u32x4 *>(qa_lo + tile_row * 64 + 16 * b) = u32x4{q[0], q[1], q[2], q[3]};
-    uint2 tail;
-    tail.x = q[4], tail.y = q[5];
-    *reinterpret_cast<uint2 *>(qa_hi + tile_row * 32 + 8 * ((b & 1u) * 2 + (b >> 1))) = tail;
-    // the four scale bytes of a row's k-tile leave as one dword (the first lane of the four collects them)
-    const unsigned s1 = __shfl_down(sbyte, 1, 4), s2 = __shfl_down(sbyte, 2, 4), s3 = __shfl_down(sbyte, 3, 4);
-    if (b == 0)
-        *reinterpret_cast<unsigned *>(qs + tile_row * 4) = sbyte | (s1 << 8) | (s2 << 16) | (s3 << 24);
+#include "qact_block6.inc"
 }
 
 // The gated epilogue (SiLU-mul, or SwiGLU-OAI: `act`) as a PRODUCER of quantised activations (out_format 8 / 4; 128 x 256 workgroup tiles only: NP = 2, four waves).
@@ -224,9 +136,9 @@ __device__ __forceinline__ void n32_silu_quant_epilogue(const f32x16 (&acc)[MB][
                                                         const unsigned col0, const unsigned kt, const unsigned wn, const unsigned m_l,
                                                         const unsigned h, unsigned char *lds_scales, const unsigned m0, const unsigned tid,
                                                         const unsigned m_lim, const unsigned act) {
-    constexpr unsigned kRowB = OUTF == 6 ? 64 : 16 * OUTF; // bytes per row and k-tile: 128 (FP8) / 64 (FP4; FP6: of the image of registers 0-3)
-    unsigned char *const qs = out + (size_t)m_total * (n_half / 8 * OUTF);
-    unsigned char *const out_hi = out + (size_t)m_total * (n_half / 2); // FP6: the image of registers 4-5 (native32_ws_bytes)
+    constexpr unsigned kRowB = qact_row_bytes(OUTF); // bytes per row and k-tile: 128 (FP8) / 64 (FP4; FP6: of the image of registers 0-3)
+    unsigned char *const qs = out + qact_elem_bytes(m_total, n_half, OUTF);
+    unsigned char *const out_hi = out + qact_hi_offset(m_total, n_half); // FP6: the image of registers 4-5
 #pragma unroll
     for (int mb = 0; mb < MB; ++mb) {
         const unsigned m = m_first + mb * 32;
@@ -250,11 +162,7 @@ __device__ __forceinline__ void n32_silu_quant_epilogue(const f32x16 (&acc)[MB][
             const unsigned s0 = sw[0], s1 = sw[1];
             amax = fmaxf(__builtin_bit_cast(float, s0), __builtin_bit_cast(float, s1));
         }
-        // the quantiser's rule (quantize_act32_kernel): E8M0 scale 2^(E - emax_elem), E = exponent of the block maximum
-        constexpr unsigned kEmax = OUTF == 8 ? 7u : 2u;
-        const unsigned ebits = (__builtin_bit_cast(unsigned, amax) >> 23) & 0xffu;
-        unsigned sbyte = amax == 0.f ? 127u : (ebits > kEmax ? ebits - kEmax : 1u);
-        sbyte = sbyte > 254u ? 254u : sbyte;
+        const unsigned sbyte = act_scale_byte<OUTF>(amax); // the quantiser's rule
         if (h == 0)
             lds_scales[(mb * 32 + m_l) * 4 + wn] = (unsigned char)sbyte;
         if constexpr (OUTF == 6) {
@@ -288,11 +196,11 @@ __device__ __forceinline__ void n32_silu_quant_epilogue(const f32x16 (&acc)[MB][
             }
             if (m < m_lim) {
                 if (h == 0) {
-                    *reinterpret_cast<u32x4 *>(out + ((size_t)kt * m_total + m) * 64 + 16 * wn) = u32x4{full[0], full[1], full[2], full[3]};
+                    *reinterpret_cast<u32x4 *>(out + qact_tile_row(m_total, kt, m) * kRowB + 16 * wn) = u32x4{full[0], full[1], full[2], full[3]};
                 } else {
                     uint2 tail;
                     tail.x = full[4], tail.y = full[5];
-                    *reinterpret_cast<uint2 *>(out_hi + ((size_t)kt * m_total + m) * 32 + 8 * ((wn & 1u) * 2 + (wn >> 1))) = tail;
+                    *reinterpret_cast<uint2 *>(out_hi + qact_tile_row(m_total, kt, m) * kQactHiRowBytes + 8 * qact_fp6_hi_slot(wn)) = tail;
                 }
             }
         } else if constexpr (OUTF == 4) {
@@ -314,7 +222,7 @@ __device__ __forceinline__ void n32_silu_quant_epilogue(const f32x16 (&acc)[MB][
             o.x = __builtin_amdgcn_perm(r1, r0, 0x05040100u); // columns 0-7
             o.y = __builtin_amdgcn_perm(r1, r0, 0x07060302u); // columns 8-15
             if (m < m_lim)
-                *reinterpret_cast<uint2 *>(out + ((size_t)kt * m_total + m) * kRowB + 16 * wn + 8 * h) = o;
+                *reinterpret_cast<uint2 *>(out + qact_tile_row(m_total, kt, m) * kRowB + 16 * wn + 8 * h) = o;
         } else {
             const float inv = __builtin_bit_cast(float, (254u - sbyte) << 23); // 2^-(sbyte - 127)
             unsigned d[2][2];
@@ -331,14 +239,14 @@ __device__ __forceinline__ void n32_silu_quant_epilogue(const f32x16 (&acc)[MB][
             const auto s1 = __builtin_amdgcn_permlane32_swap(d[0][1], d[1][1], false, false); // columns 8-11 | 12-15
             const unsigned a0 = s0[0], a1 = s0[1], b0 = s1[0], b1 = s1[1];
             // the 16-column unit u16 = 2 wn + h sits at position pos of the tile's 128 bytes (the operand order of the layout note)
-            const unsigned u16 = 2 * wn + h, pos = (u16 & 4u) | ((u16 & 1u) << 1) | ((u16 >> 1) & 1u);
+            const unsigned u16 = 2 * wn + h, pos = qact_fp8_unit_pos(u16);
             if (m < m_lim)
-                *reinterpret_cast<u32x4 *>(out + ((size_t)kt * m_total + m) * kRowB + pos * 16) = u32x4{a0, a1, b0, b1};
+                *reinterpret_cast<u32x4 *>(out + qact_tile_row(m_total, kt, m) * kRowB + pos * 16) = u32x4{a0, a1, b0, b1};
         }
     }
     __syncthreads();
     if (tid < (unsigned)(32 * MB) && m0 + tid < m_lim)
-        *reinterpret_cast<unsigned *>(qs + ((size_t)kt * m_total + m0 + tid) * 4) = reinterpret_cast<const unsigned *>(lds_scales)[tid];
+        *reinterpret_cast<unsigned *>(qs + (qact_scale_dword(m_total, kt, m0) + tid) * kQactScaleRowBytes) = reinterpret_cast<const unsigned *>(lds_scales)[tid];
 }
 
 //   MB, NP, WAVES, D as in WideCfg; ACT = 8 (MXFP8 activations), 6 (MXFP6, e2m3) or 4 (MXFP4 activations).
@@ -556,15 +464,15 @@ __global__ __launch_bounds__(Cfg::kThreads, Cfg::kMinWavesPerSimd) void gemm_nat
         else
             return buf_load16(w_rsrc, w_voff[i], kt * kTileBytes, kAuxDefault);
     };
-    // quantised activations and their scales, k-tile major (see the layout note above): tile kt of this m-block starts at
+    // quantised activations and their scales, k-tile major ("petit-qact/1", layout.h): tile kt of this m-block starts at
     // (kt M + m0) rows of 16 ACT (data) / 4 (scales) bytes; the descriptors end with the data / scale region
-    constexpr unsigned kRowB = 16 * Cfg::kRowU4;
-    const size_t qa_bytes = (size_t)p.m * (p.k / 8 * ACT), qs_bytes = (size_t)p.m * (p.k / 32);
-    const size_t lo_bytes = (size_t)p.m * (p.k / 8 * Cfg::kRowU4); // (FP6: the first image; else all of the data)
+    constexpr unsigned kRowB = qact_row_bytes(ACT), kHiB = kQactHiRowBytes, kScB = kQactScaleRowBytes; // (kRowB = 16 Cfg::kRowU4)
+    const size_t qa_bytes = qact_elem_bytes(p.m, p.k, ACT), qs_bytes = qact_scale_bytes(p.m, p.k);
+    const size_t lo_bytes = qact_lo_bytes(p.m, p.k, ACT); // (FP6: the first image; else all of the data)
     const __amdgpu_buffer_rsrc_t qa_rsrc = make_rsrc(ws + (size_t)m0 * kRowB, (unsigned)(lo_bytes - (size_t)m0 * kRowB));
-    const __amdgpu_buffer_rsrc_t qh_rsrc = make_rsrc(ws + lo_bytes + (size_t)m0 * 32, ACT == 6 ? (unsigned)(qa_bytes - lo_bytes - (size_t)m0 * 32) : 0u);
-    const __amdgpu_buffer_rsrc_t qs_rsrc = make_rsrc(ws + qa_bytes + (size_t)m0 * 4, (unsigned)(qs_bytes - (size_t)m0 * 4));
-    const unsigned qa_tile = p.m * kRowB, qs_tile = p.m * 4; // bytes from one k-tile to the next
+    const __amdgpu_buffer_rsrc_t qh_rsrc = make_rsrc(ws + lo_bytes + (size_t)m0 * kHiB, ACT == 6 ? (unsigned)(qa_bytes - lo_bytes - (size_t)m0 * kHiB) : 0u);
+    const __amdgpu_buffer_rsrc_t qs_rsrc = make_rsrc(ws + qa_bytes + (size_t)m0 * kScB, (unsigned)(qs_bytes - (size_t)m0 * kScB));
+    const unsigned qa_tile = p.m * kRowB, qs_tile = p.m * kScB; // bytes from one k-tile to the next
 
     // direct-to-LDS staging.  Data: wave-load i of this wave covers rows RPL*(i*WAVES + wave) .. +RPL-1 (RPL = 8 / 16 rows of
     // 128 / 64 bytes); lane l -> row + l / U, position l % U, which receives unit (l % U) ^ swz(row), U = 8 / 4 units per row,
@@ -595,7 +503,7 @@ __global__ __launch_bounds__(Cfg::kThreads, Cfg::kMinWavesPerSimd) void gemm_nat
 #pragma unroll
                 for (int i = 0; i < Cfg::kHiLoads; ++i)
                     __builtin_amdgcn_raw_ptr_buffer_load_lds(qh_rsrc, (__attribute__((address_space(3))) void *)(dma_wave ? data + Cfg::kLoU4 + (i * kDmaWaves + wave) * 64 : dump), 16,
-                                                             hi_voff, i * (32 * kDmaWaves) * 32 + (kt + t) * (p.m * 32), 0, 0);
+                                                             hi_voff, i * (32 * kDmaWaves) * kHiB + (kt + t) * (p.m * kHiB), 0, 0);
             }
             u32x4 *const sc = smem_g + buf * Cfg::kStageU4 + KT * Cfg::kDataU4 + t * Cfg::kScaleU4;
             __builtin_amdgcn_raw_ptr_buffer_load_lds(qs_rsrc, (__attribute__((address_space(3))) void *)(sc + wave * 16), 4, qs_voff, (kt + t) * qs_tile, 0, 0);

@@ -51,7 +51,7 @@ struct NativeInvariantArgs {
 };
 
 // bytes of one row and k-tile in the (first) data image: 128 (MXFP8) / 64 (MXFP4; MXFP6: registers 0-3 of every block)
-template <int ACT> constexpr unsigned native_inv_row_bytes() { return ACT == 8 ? 128u : 64u; }
+template <int ACT> constexpr unsigned native_inv_row_bytes() { return qact_row_bytes(ACT); }
 // 16-byte units of one k-tile a lane holds: P1 + P2 (MXFP6: the two register 0-3 units and the unit with registers 4-5 of both)
 template <int ACT> constexpr int native_inv_frag_units() { return ACT == 8 ? 4 : ACT == 6 ? 3 : 2; }
 
@@ -147,7 +147,7 @@ template <class AT, int ACT, int kDepth> __global__ __launch_bounds__(256) void 
 constexpr int kNativeWholeRing = 2;
 template <int ACT> struct NativeWholeLds {
     static constexpr unsigned kRowB = native_inv_row_bytes<ACT>(), U = kRowB / 16;
-    static constexpr unsigned kData = 64 * kRowB, kHi = ACT == 6 ? 64 * 32 : 0, kScale = 64 * 4;
+    static constexpr unsigned kData = 64 * kRowB, kHi = ACT == 6 ? 64 * kQactHiRowBytes : 0, kScale = 64 * kQactScaleRowBytes;
     static constexpr unsigned kBuf = kData + kHi + kScale;
 };
 template <class AT, int ACT> __global__ __launch_bounds__(256) void native_invariant_whole_kernel(const NativeInvariantArgs p) {

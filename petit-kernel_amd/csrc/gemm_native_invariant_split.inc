@@ -22,8 +22,8 @@ if constexpr (WF == 6) { // the block's stream along K: 3 KiB of elements and 12
         s_rsrc[j] = make_rsrc(s_base + (size_t)tile * ktiles * 64, ktiles * 64);
     }
 }
-const unsigned char *const qa_hi = p.qa + (size_t)p.m * (p.k / 2);        // (MXFP6)
-const unsigned char *const qs = p.qa + (size_t)p.m * (p.k / 8 * ACT);
+const unsigned char *const qa_hi = p.qa + qact_hi_offset(p.m, p.k); // (MXFP6; "petit-qact/1": layout.h)
+const unsigned char *const qs = p.qa + qact_elem_bytes(p.m, p.k, ACT);
 const unsigned a_voff = m_l * kRowB + h * (ACT == 8 ? 32u : 16u);
 
 struct Stage {
@@ -51,16 +51,16 @@ auto load_stage = [&](Stage &st, unsigned kt) {
         }
     }
     // the k-tile's rows m0 .. m0 + rows_valid - 1 of every image: rows past the tile's last valid row are out of range -> zeros
-    const size_t tile_row = (size_t)kt * p.m + m0;
+    const size_t tile_row = qact_tile_row(p.m, kt, m0);
     const __amdgpu_buffer_rsrc_t a_rsrc = make_rsrc(p.qa + tile_row * kRowB, rows_valid * kRowB);
-    const __amdgpu_buffer_rsrc_t q_rsrc = make_rsrc(qs + tile_row * 4, rows_valid * 4u);
+    const __amdgpu_buffer_rsrc_t q_rsrc = make_rsrc(qs + tile_row * kQactScaleRowBytes, rows_valid * kQactScaleRowBytes);
     if constexpr (ACT == 8) {
         st.a[0] = buf_load16(a_rsrc, a_voff, 0, kAuxDefault), st.a[1] = buf_load16(a_rsrc, a_voff + 16u, 0, kAuxDefault);
         st.a[2] = buf_load16(a_rsrc, a_voff + 64u, 0, kAuxDefault), st.a[3] = buf_load16(a_rsrc, a_voff + 80u, 0, kAuxDefault);
     } else {
         st.a[0] = buf_load16(a_rsrc, a_voff, 0, kAuxDefault), st.a[1] = buf_load16(a_rsrc, a_voff + 32u, 0, kAuxDefault);
         if constexpr (ACT == 6) {
-            const __amdgpu_buffer_rsrc_t h_rsrc = make_rsrc(qa_hi + tile_row * 32, rows_valid * 32u);
+            const __amdgpu_buffer_rsrc_t h_rsrc = make_rsrc(qa_hi + tile_row * kQactHiRowBytes, rows_valid * kQactHiRowBytes);
             st.a[2] = buf_load16(h_rsrc, m_l * 32u + h * 16u, 0, kAuxDefault);
         }
     }

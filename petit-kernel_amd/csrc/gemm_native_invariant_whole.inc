@@ -36,8 +36,8 @@ for (int np = 0; np < NP; ++np)
             s_rsrc[np][j] = make_rsrc(s_base + (size_t)t * ktiles * 64, live[np] ? ktiles * 64 : 0u);
         }
     }
-const unsigned char *const qa_hi = p.qa + (size_t)p.m * (p.k / 2); // (MXFP6)
-const unsigned char *const qs = p.qa + (size_t)p.m * (p.k / 8 * ACT);
+const unsigned char *const qa_hi = p.qa + qact_hi_offset(p.m, p.k); // (MXFP6; "petit-qact/1": layout.h)
+const unsigned char *const qs = p.qa + qact_elem_bytes(p.m, p.k, ACT);
 
 // staging: 16-byte unit u = tid + 256 i of the tile's run is row u / U, position u % U, which lands at position (u % U) ^ swz(row);
 // MXFP6's second image (32 bytes per row): unit tid < 128 is row tid / 2; the scale dwords: one per row, tid < 64
@@ -49,17 +49,17 @@ struct AStage {
     unsigned sc;
 };
 auto fetch_a = [&](AStage &r, unsigned kt) {
-    const size_t tile_row = (size_t)kt * p.m + m0;
+    const size_t tile_row = qact_tile_row(p.m, kt, m0);
     const __amdgpu_buffer_rsrc_t a_rsrc = make_rsrc(p.qa + tile_row * kRowB, rows_valid * kRowB);
 #pragma unroll
     for (int i = 0; i < kDataLoads; ++i)
         r.d[i] = buf_load16(a_rsrc, (tid + 256u * i) * 16u, 0, kAuxDefault);
     if constexpr (ACT == 6) {
-        const __amdgpu_buffer_rsrc_t h_rsrc = make_rsrc(qa_hi + tile_row * 32, rows_valid * 32u);
+        const __amdgpu_buffer_rsrc_t h_rsrc = make_rsrc(qa_hi + tile_row * kQactHiRowBytes, rows_valid * kQactHiRowBytes);
         if (wave < 2u)
             r.hi = buf_load16(h_rsrc, tid * 16u, 0, kAuxDefault);
     }
-    const __amdgpu_buffer_rsrc_t q_rsrc = make_rsrc(qs + tile_row * 4, rows_valid * 4u);
+    const __amdgpu_buffer_rsrc_t q_rsrc = make_rsrc(qs + tile_row * kQactScaleRowBytes, rows_valid * kQactScaleRowBytes);
     if (wave == 0u)
         r.sc = __builtin_amdgcn_raw_buffer_load_b32(q_rsrc, tid * 4u, 0, kAuxDefault);
 };

@@ -122,4 +122,45 @@ PETIT_HD size_t nv6_scale_offset(unsigned k_total, unsigned n, unsigned blk) {
     return (((size_t)(n / 32) * (k_total / (kTileK * ks)) + sp) * 64 + (h * 32 + n % 32)) * (2 * ks) + q * ks + t;
 }
 
+// ---------------------------------------------------------------------------------------------------------------------------------
+// "petit-qact/1": the quantised activations of the native class -- [m][k] in MXFP8 (act = 8, e4m3 elements), MXFP6 (6, e2m3) or MXFP4
+// (4, e2m1), one E8M0 scale byte per 32 k (the rule: act_scale_byte, numfmt.h).  Written by the quantisers and the gated epilogue of
+// gemm_native32.hpp, by rmsnorm_quant.hip and its host twin; read by the native GEMMs and by the twins of gemm_invariant_host.h.  K % 128 == 0.
+// K-TILE MAJOR: every region is [K/128][m][bytes of one row and k-tile], so the activation tile of a workgroup and k-tile (BM rows x 128 k) is
+// ONE contiguous run and every 1 KiB wave-load of the GEMM's direct-to-LDS staging reads eight whole cache lines (with the row-major form
+// qa[M][K ACT / 8] a wave-load touched 16 half lines 4 KiB apart, and the activation DMA cost more than the weight stream: 8.9 vs 4.8 us of
+// a 30.6 us launch at 8192^2, M = 512 -- tools/ablate_native32.sh).  Rows >= M of the last m-block read the next tile's rows (or zeros past
+// the end): such rows only feed output columns that are never stored.  The regions, in order:
+//   elements : u8 qa[K/128][m][16 act']   act' = 4 for MXFP6 (see below), else act: 128 / 64 / 64 bytes per row and k-tile
+//     act = 8: the eight 16-k units of the tile in the order [0-15][32-47][16-31][48-63][64-79][96-111][80-95][112-127] (unit u at position
+//              qact_fp8_unit_pos(u)), so that lane (m, h) of the 32x32x64 MFMA finds its P1 operand at byte 32 h and its P2 operand at 64 + 32 h.
+//     act = 4: natural nibble order (element i of the tile in nibble i & 1 of byte i / 2): P1 operand at byte 16 h, P2 at 32 + 16 h.
+//     act = 6: a 32-k block is 24 bytes = the 6 operand registers of one lane (element i at bits [6 i, 6 i + 6), tools/probes/mfma32_fp6_probe.hip),
+//              stored as TWO images so that every access stays a 16-byte one: this first one holds registers 0-3 of block b at byte 16 b (the FP4
+//              geometry);
+//   MXFP6 only: u8 qa_hi[K/128][m][32]    registers 4-5 of blocks 0, 2, 1, 3 in that order (block b in slot qact_fp6_hi_slot(b)): lane (m, h)
+//              reads ONE 16-byte unit h and finds the tail of its P1 block in the first 8 bytes, of its P2 block in the last 8;
+//   scales   : u8 qs[K/128][m][4]         the E8M0 bytes of the tile's four blocks, one dword per row.
+constexpr unsigned kQactHiRowBytes = 32;    // MXFP6's second image: bytes per row and k-tile
+constexpr unsigned kQactScaleRowBytes = 4;  // the scale region: bytes per row and k-tile
+// bytes per row and k-tile of the (first) element image
+PETIT_HD constexpr unsigned qact_row_bytes(int act) { return act == 8 ? 128u : 64u; }
+// bytes of all the elements = the offset of the scale region; of the scales; of the whole image
+PETIT_HD size_t qact_elem_bytes(unsigned m, unsigned k, int act) { return (size_t)m * (k / 8 * (unsigned)act); }
+PETIT_HD size_t qact_scale_bytes(unsigned m, unsigned k) { return (size_t)m * (k / 32); }
+PETIT_HD size_t qact_bytes(unsigned m, unsigned k, int act) { return qact_elem_bytes(m, k, act) + qact_scale_bytes(m, k); }
+// bytes of the first element image: all the elements but for MXFP6, where the second image starts there.  qact_hi_offset is that start
+// in the arithmetic the quantisers and the invariant kernels compile from (equal for every K % 8 == 0; tools/invariant_hostcheck.cc holds
+// the two against each other): one spelling would change the scalar code of the kernels that use the other.
+PETIT_HD size_t qact_lo_bytes(unsigned m, unsigned k, int act) { return (size_t)m * (k / 8 * (act == 6 ? 4u : (unsigned)act)); }
+PETIT_HD size_t qact_hi_offset(unsigned m, unsigned k) { return (size_t)m * (k / 2); }
+// index of row `row` of k-tile kt in any of the three regions: times the region's bytes per row and k-tile
+PETIT_HD size_t qact_tile_row(unsigned m, unsigned kt, unsigned row) { return (size_t)kt * m + row; }
+// MXFP8: position (of 8, 16 bytes each) of the 16-k unit u of a k-tile
+PETIT_HD unsigned qact_fp8_unit_pos(unsigned u) { return (u & 4u) | ((u & 1u) << 1) | ((u >> 1) & 1u); }
+// MXFP6: slot (of 4, 8 bytes each) of block b's registers 4-5 in the second image
+PETIT_HD unsigned qact_fp6_hi_slot(unsigned b) { return (b & 1u) * 2 + (b >> 1); }
+// dword index, in the scale region, of the four scale bytes of (k-tile, row); block b's byte is byte b of it
+PETIT_HD size_t qact_scale_dword(unsigned m, unsigned kt, unsigned row) { return qact_tile_row(m, kt, row); }
+
 } // namespace petit_amd

@@ -73,11 +73,6 @@ int moe_check(const petit_solution_hints *hints, unsigned num_experts, unsigned 
 
 // --- the native class (petit_gemm_native_moe): the routed-expert forms of the 32x32x64 native kernels (gemm_moe_native.hpp) ---------------
 
-// bytes of m quantised rows of k in format 8 / 6 / 4 (the k-tile-major layout, gemm_native32.hpp)
-uint64_t qact_bytes(int format, unsigned m, unsigned k) {
-    return format == 8 ? native32_ws_bytes<8>(m, k) : format == 6 ? native32_ws_bytes<6>(m, k) : format == 4 ? native32_ws_bytes<4>(m, k) : 0;
-}
-
 bool native_moe_runs(const SolutionEntry &e, bool act, unsigned num_experts, unsigned m, unsigned k) {
     return e.launch_moe_native && e.shape.ks == span_tiles_for_k(k) && (!act || act_ok(e)) && moe_slots(m, moe_rows(e), num_experts) != 0;
 }
@@ -137,7 +132,7 @@ int native_moe_plan(const petit_solution_hints *hints, unsigned num_experts, uns
     if (!*e)
         return kErrKernelShape;
     // the kernels read the quantised rows (and the quantising epilogue writes its output) through 32-bit buffer offsets; one descriptor per NV6 image
-    if (qact_bytes(entry_class(**e), m, k) >= (1ull << 32) || (*out_format && qact_bytes((int)*out_format, m, n / 2) >= (1ull << 32)) ||
+    if (petit_quantized_activation_bytes(m, k, entry_class(**e)) >= (1ull << 32) || (*out_format && petit_quantized_activation_bytes(m, n / 2, (int)*out_format) >= (1ull << 32)) ||
         (!is_mx_type(hints->b_type) && nv6_elem_bytes(n, k) >= (1ull << 32)))
         return kErrProblemShape;
     return kOk;
@@ -175,7 +170,7 @@ int native_moe_run(void *c, const void *a, const void *b, const void *scales, co
     const int klass = entry_class(*e);
     // (the image of every accepted shape is a multiple of 256 bytes -- 6400 per 32 rows x 256 k --, so images and scratch stay aligned)
     const uint64_t images_bytes = transient ? (uint64_t)num_experts * nv6_image_bytes(n, k) : 0;
-    const uint64_t need = images_bytes + (a_format ? 0 : qact_bytes(klass, m, k));
+    const uint64_t need = images_bytes + (a_format ? 0 : petit_quantized_activation_bytes(m, k, klass));
     if (need && (!workspace || workspace_bytes < need))
         return kErrKernelShape; // (as the dense native entry points: scratch below the query)
     void *const scratch = (char *)workspace + images_bytes;
@@ -211,7 +206,7 @@ uint64_t petit_gemm_native_moe_workspace_bytes(const petit_solution_hints *hints
     unsigned a_format = 0, out_format = 0;
     if (native_moe_plan(hints, num_experts, m, n, k, nullptr, nullptr, solution_id, epilogue, native, &e, &fam, &act, &a_format, &out_format) != kOk || !e)
         return 0;
-    return a_format ? 0 : qact_bytes(entry_class(*e), m, k);
+    return a_format ? 0 : petit_quantized_activation_bytes(m, k, entry_class(*e));
 }
 
 uint64_t petit_gemm_native_moe_resolve_solution(const petit_solution_hints *hints, unsigned num_experts, unsigned m, unsigned n, unsigned k,
@@ -243,7 +238,7 @@ uint64_t petit_gemm_native_moe_transient_workspace_bytes(const petit_solution_hi
         return 0;
     if (native_moe_plan(hints, num_experts, m, n, k, nullptr, nullptr, solution_id, epilogue, native, &e, &fam, &act, &a_format, &out_format) != kOk || !e)
         return 0;
-    return (uint64_t)num_experts * nv6_image_bytes(n, k) + (a_format ? 0 : qact_bytes(entry_class(*e), m, k));
+    return (uint64_t)num_experts * nv6_image_bytes(n, k) + (a_format ? 0 : petit_quantized_activation_bytes(m, k, entry_class(*e)));
 }
 
 int petit_gemm_native_moe_transient(void *c, const void *a, const void *b, const void *scales, const float *global_scales,
@@ -261,7 +256,7 @@ int petit_quantize_activations_rows(void *qa, const void *a, const int32_t *a_ro
         return kOk;
     if (!qa || !a || ((uintptr_t)qa & 15) || ((uintptr_t)a & 15))
         return kErrBadArgument;
-    if (k % 256 != 0 || (!a_row_index && a_rows < m) || qact_bytes(format, m, k) >= (1ull << 32))
+    if (k % 256 != 0 || (!a_row_index && a_rows < m) || petit_quantized_activation_bytes(m, k, format) >= (1ull << 32))
         return kErrProblemShape;
     if (a_type == kDataTypeBf16)
         return quantize32_rows_bf16(a, a_row_index, a_rows, qa, m, k, format, (hipStream_t)stream);

@@ -23,6 +23,7 @@
 
 #include "../../include/petit_amd.h"
 #include "device_common.hpp"
+#include "numfmt.h"
 #include "petit_internal.h"
 
 using namespace petit_amd;
@@ -174,15 +175,6 @@ __global__ __launch_bounds__(kChunk) void moe_align_place_kernel(const void *ids
 }
 
 // Combine: one thread per 8 consecutive columns of one token (16-byte loads of each slot row, coalesced along n), grid-stride.
-template <bool kBf16> __device__ __forceinline__ float half_to_f32(unsigned short h) {
-    if constexpr (kBf16) {
-        return __builtin_bit_cast(float, (unsigned)h << 16);
-    } else {
-        const _Float16 f = __builtin_bit_cast(_Float16, h);
-        return (float)f;
-    }
-}
-
 template <bool kBf16>
 __global__ __launch_bounds__(256) void moe_combine_kernel(void *out, const void *slot_out, const float *weights, const void *ids, unsigned i64,
                                                           unsigned num_tokens, unsigned topk, unsigned n, unsigned num_experts) {
@@ -201,7 +193,7 @@ __global__ __launch_bounds__(256) void moe_combine_kernel(void *out, const void 
             const unsigned words[4] = {v.x, v.y, v.z, v.w};
 #pragma unroll
             for (int q = 0; q < 8; ++q) {
-                const float x = half_to_f32<kBf16>((unsigned short)(words[q / 2] >> (16 * (q % 2))));
+                const float x = h16_f32<kBf16>((unsigned short)(words[q / 2] >> (16 * (q % 2))));
                 const float prod = x * w;
                 acc[q] = acc[q] + prod;
             }
@@ -258,7 +250,7 @@ __device__ __forceinline__ float route_logit(const void *logits, int dtype, size
     if (dtype == kDataTypeFp32)
         return ((const float *)logits)[i];
     const unsigned short h = ((const unsigned short *)logits)[i];
-    return dtype == kDataTypeBf16 ? half_to_f32<true>(h) : half_to_f32<false>(h);
+    return dtype == kDataTypeBf16 ? h16_f32<true>(h) : h16_f32<false>(h);
 }
 
 // The logit of expert e of the row, element i = row + e.  kSlab: the router GEMM's definition -- the slabs added in order, then the router bias.

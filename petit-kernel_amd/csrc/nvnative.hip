@@ -29,61 +29,23 @@
 #include "device_common.hpp"
 #include "hal.h"
 #include "layout.h"
+#include "numfmt.h"
 #include "petit_internal.h"
 
 namespace petit_amd {
 
 namespace {
 
-PETIT_HD float fp4_value(unsigned code) {
-    const unsigned mag = code & 7u;
-    const float v = mag == 0 ? 0.f : mag == 1 ? 0.5f : mag == 2 ? 1.f : mag == 3 ? 1.5f : mag == 4 ? 2.f : mag == 5 ? 3.f : mag == 6 ? 4.f : 6.f;
-    return (code & 8u) ? -v : v;
-}
-// e4m3fn byte -> f32 (0x7f / 0xff are NaN; subnormals 2^-9 .. 7 x 2^-9)
-PETIT_HD float e4m3_value(unsigned b, bool *nan) {
-    const unsigned e = (b >> 3) & 15u, m = b & 7u;
-    *nan = (b & 0x7fu) == 0x7fu;
-    float v;
-    if (e == 0) {
-        v = (float)m * (1.0f / 512.0f);
-    } else {
-        const unsigned bits = ((e + 120u) << 23) | (m << 20);
-#if defined(__HIP_DEVICE_COMPILE__)
-        v = __builtin_bit_cast(float, bits);
-#else
-        memcpy(&v, &bits, 4);
-#endif
-    }
-    return (b & 0x80u) ? -v : v;
-}
-PETIT_HD unsigned f32_bits(float x) {
-#if defined(__HIP_DEVICE_COMPILE__)
-    return __builtin_bit_cast(unsigned, x);
-#else
-    unsigned u;
-    memcpy(&u, &x, 4);
-    return u;
-#endif
-}
-PETIT_HD float bits_f32(unsigned u) {
-#if defined(__HIP_DEVICE_COMPILE__)
-    return __builtin_bit_cast(float, u);
-#else
-    float x;
-    memcpy(&x, &u, 4);
-    return x;
-#endif
-}
-
 // the block's values and its E8M0 byte from the lane's 16 bytes of nibbles (word j nibble i = element 8 j + i) and its two group scales
 PETIT_HD unsigned block_values(const unsigned w[4], unsigned s_lo, unsigned s_hi, float v[32]) {
-    bool nan_lo, nan_hi;
-    const float sl = e4m3_value(s_lo, &nan_lo), sh = e4m3_value(s_hi, &nan_hi);
+    const bool nan_lo = e4m3_is_nan(s_lo);
+    const float sl = e4m3_finite_f32(s_lo);
+    const bool nan_hi = e4m3_is_nan(s_hi);
+    const float sh = e4m3_finite_f32(s_hi);
     float amax = 0.f;
     for (int j = 0; j < 4; ++j)
         for (int i = 0; i < 8; ++i) {
-            const float x = fp4_value((w[j] >> (4 * i)) & 15u) * (j < 2 ? sl : sh);
+            const float x = e2m1_f32((w[j] >> (4 * i)) & 15u) * (j < 2 ? sl : sh);
             v[8 * j + i] = x;
             const float ax = x < 0.f ? -x : x;
             amax = ax > amax ? ax : amax;
@@ -93,28 +55,7 @@ PETIT_HD unsigned block_values(const unsigned w[4], unsigned s_lo, unsigned s_hi
             v[e] = 0.f;
         return 0xffu;
     }
-    if (amax == 0.f)
-        return 127u;
-    const unsigned ebits = (f32_bits(amax) >> 23) & 0xffu; // (amax >= 2^-10: never an f32 subnormal)
-    return ebits - 2u;                                     // in 115 .. 136 for every e4m3 scale
-}
-
-// host twin of the hardware convert: RNE onto the e2m3 grid (subnormal step 1/8, normals 1 .. 7.5), saturating; the sign of zero is kept
-inline unsigned e2m3_rne_host(float x) {
-    const unsigned sign = std::signbit(x) ? 32u : 0u;
-    const float ax = std::fabs(x);
-    if (ax >= 7.5f)
-        return sign | 31u;
-    if (ax < 1.0f)
-        return sign | (unsigned)std::nearbyint(ax * 8.0f); // (8 = code of 1.0)
-    int e;
-    (void)std::frexp(ax, &e); // ax = f 2^e, f in [0.5, 1)
-    e -= 1;                   // floor(log2 ax): 0 .. 2
-    const float step = std::ldexp(1.0f, e) / 8.0f;
-    unsigned r = (unsigned)std::nearbyint(ax / step); // 8 .. 16
-    if (r == 16)
-        r = 8, e += 1;
-    return sign | ((unsigned)(e + 1) << 3) | (r - 8u);
+    return act_scale_byte_nv6(amax); // (amax >= 2^-10: never an f32 subnormal; the byte is in 115 .. 136 for every e4m3 scale)
 }
 
 } // namespace
@@ -148,8 +89,10 @@ template <int KS> __device__ __forceinline__ void store_rec(unsigned char *p, co
 // hardware convert, bit for bit.  The nibbles go through the hardware E2M1 convert (exact, sign of zero kept) and the exact products are the
 // values block_values forms; their maximum is taken with abs-modifier max3 (products are canonical floats: no canonicalising moves).
 __device__ __forceinline__ unsigned nv6_block(const u32x4 w, unsigned s_lo, unsigned s_hi, unsigned (&words)[6]) {
-    bool nan_lo, nan_hi;
-    const float sl = e4m3_value(s_lo, &nan_lo), sh = e4m3_value(s_hi, &nan_hi);
+    const bool nan_lo = e4m3_is_nan(s_lo);
+    const float sl = e4m3_finite_f32(s_lo);
+    const bool nan_hi = e4m3_is_nan(s_hi);
+    const float sh = e4m3_finite_f32(s_hi);
     f32x16v ea, eb; // element 2 t = ea[t], 2 t + 1 = eb[t] (tools/probes/mfma32_fp6_probe.hip); word j, byte sel = elements 8 j + 2 sel, + 1
     float amax = 0.f;
     static_for<0, 16>([&](auto T) {
@@ -160,7 +103,7 @@ __device__ __forceinline__ unsigned nv6_block(const u32x4 w, unsigned s_lo, unsi
         ea[t] = x, eb[t] = y;
         amax = fmaxf(amax, fmaxf(fabsf(x), fabsf(y)));
     });
-    const unsigned sbyte = amax == 0.f ? 127u : ((f32_bits(amax) >> 23) & 0xffu) - 2u;
+    const unsigned sbyte = act_scale_byte_nv6(amax);
     const u32x6 qv = cvt_2xpk16_fp6_f32(ea, eb, bits_f32(sbyte << 23)); // (early-clobber form: device_common.hpp)
     const bool nan = nan_lo || nan_hi; // (block_values: NaN-scaled zeros, scale byte 0xff)
 #pragma unroll
@@ -343,7 +286,7 @@ int nv6_image_host(void *image, const void *pw_, const void *ps_, unsigned n, un
                 sbyte = block_values(w, ps[si], ps[si + 1], v);
                 const float inv = std::ldexp(1.0f, 127 - (int)(sbyte == 0xffu ? 127u : sbyte));
                 for (int e = 0; e < 32; ++e) {
-                    const unsigned code = e2m3_rne_host(v[e] * inv);
+                    const unsigned code = e2m3_rne(v[e] * inv); // (the hardware convert's rounding: numfmt.h)
                     const unsigned bit = 6u * (unsigned)e;
                     const uint64_t bits = (uint64_t)code << (bit % 32);
                     words[bit / 32] |= (unsigned)bits;
@@ -404,9 +347,7 @@ int nv6_image_dequant_host(float *out, const void *image, unsigned n, unsigned k
                 uint64_t wv = words[bit / 32];
                 if (bit / 32 + 1 < 6)
                     wv |= (uint64_t)words[bit / 32 + 1] << 32;
-                const unsigned c = (unsigned)(wv >> (bit % 32)) & 63u, ee = (c >> 3) & 3u, mm = c & 7u;
-                const float mag = ee ? std::ldexp(1.0f + mm / 8.0f, (int)ee - 1) : mm / 8.0f;
-                out[(size_t)row * k + 32 * blk + e] = ((c & 32u) ? -mag : mag) * scale;
+                out[(size_t)row * k + 32 * blk + e] = e2m3_f32((unsigned)(wv >> (bit % 32)) & 63u) * scale;
             }
         }
     return kOk;

@@ -23,58 +23,14 @@
 #include "device_common.hpp"
 #include "hal.h"
 #include "layout.h"
+#include "numfmt.h"
 #include "petit_internal.h"
 
 namespace petit_amd {
 
 namespace {
 
-PETIT_HD unsigned f32_bits(float x) {
-#if defined(__HIP_DEVICE_COMPILE__)
-    return __builtin_bit_cast(unsigned, x);
-#else
-    unsigned u;
-    memcpy(&u, &x, 4);
-    return u;
-#endif
-}
-PETIT_HD float bits_f32(unsigned u) {
-#if defined(__HIP_DEVICE_COMPILE__)
-    return __builtin_bit_cast(float, u);
-#else
-    float x;
-    memcpy(&x, &u, 4);
-    return x;
-#endif
-}
-
-// |x| of a 16-bit element from its 15 magnitude bits (bf16: the upper half of the f32; fp16: subnormals are m x 2^-24)
-template <bool BF16> PETIT_HD float abs16_f32(unsigned mag) {
-    if constexpr (BF16)
-        return bits_f32(mag << 16);
-#if defined(__HIP_DEVICE_COMPILE__)
-    return (float)__builtin_bit_cast(_Float16, (unsigned short)mag); // (exact, subnormals included; the host spells the same conversion out)
-#endif
-    const unsigned e = mag >> 10, m = mag & 0x3ffu;
-    if (e == 0)
-        return (float)m * (1.0f / 16777216.0f);
-    return bits_f32((e == 31 ? 0x7f800000u : (e + 112u) << 23) | (m << 13));
-}
-
-// f32 >= 0 -> e4m3fn byte, round to nearest even, saturating at 448 (0x7e; a NaN saturates too)
-PETIT_HD unsigned e4m3_rne_sat(float x) {
-    if (!(x < 448.0f))
-        return 0x7eu;
-    if (x < 0.015625f) // below 2^-6: multiples of 2^-9; x * 512 is exact, the add rounds it to an integer (8 = the byte of 2^-6)
-        return f32_bits(x * 512.0f + 8388608.0f) & 15u;
-    const unsigned u = f32_bits(x);
-    return ((u + 0x7ffffu + ((u >> 20) & 1u)) >> 20) - (120u << 3);
-}
-PETIT_HD float e4m3_value(unsigned b) { // (bytes 0 .. 0x7e: what e4m3_rne_sat returns)
-    const unsigned e = b >> 3, m = b & 7u;
-    return e == 0 ? (float)m * (1.0f / 512.0f) : bits_f32(((e + 120u) << 23) | (m << 20));
-}
-
+// (|x| of a 16-bit element from its 15 magnitude bits is h16_f32 of numfmt.h on the pattern without its sign)
 PETIT_HD float nv_global_scale(float amax) { return amax == 0.f ? 1.0f : amax / 2688.0f; }
 PETIT_HD unsigned nv_scale_byte(float blk_amax, float gs) { return e4m3_rne_sat((blk_amax / 6.0f) / gs); }
 // the e8m0 byte e + 127 of the smallest e with 6 x 2^e >= amax, e clipped to [-126, 127]: amax = f x 2^q, f in [1, 2), has e = q - 2 when
@@ -84,8 +40,6 @@ PETIT_HD unsigned mx_scale_byte(float blk_amax) {
     const int b = (int)(u >> 23) - 2 + ((u & 0x7fffffu) > 0x400000u ? 1 : 0);
     return (unsigned)(b < 1 ? 1 : b > 254 ? 254 : b);
 }
-
-constexpr float kMid[7] = {0.25f, 0.75f, 1.25f, 1.75f, 2.5f, 3.5f, 5.0f};
 
 // x >= 0 -> the largest f32 <= x / the smallest f32 >= x (the conversion rounds to nearest; a step of one bit pattern undoes a wrong direction)
 PETIT_HD float f32_at_or_below(double x) {
@@ -99,10 +53,10 @@ PETIT_HD float f32_at_or_above(double x) {
 // the seven thresholds of a block.  NVFP4: mid x s x gs exactly, then rounded down where the comparison is <, up where it is <=; a zero scale
 // byte gives code 0 for the whole block (+inf thresholds).
 PETIT_HD void nv_thresholds(unsigned sbyte, float gs, float (&t)[7]) {
-    const double d = (double)e4m3_value(sbyte) * (double)gs;
+    const double d = (double)e4m3_mag_f32(sbyte) * (double)gs; // (sbyte <= 0x7e: what e4m3_rne_sat returns)
 #pragma unroll
     for (int i = 0; i < 7; ++i) {
-        const double x = sbyte ? (double)kMid[i] * d : (double)INFINITY;
+        const double x = sbyte ? (double)kE2m1Mid[i] * d : (double)INFINITY;
         t[i] = (i & 1) ? f32_at_or_above(x) : f32_at_or_below(x);
     }
 }
@@ -110,9 +64,9 @@ PETIT_HD void mx_thresholds(unsigned sbyte, float (&t)[7]) {
 #pragma unroll
     for (int i = 0; i < 7; ++i)
 #if defined(__HIP_DEVICE_COMPILE__)
-        t[i] = __builtin_ldexpf(kMid[i], (int)sbyte - 127);
+        t[i] = __builtin_ldexpf(kE2m1Mid[i], (int)sbyte - 127);
 #else
-        t[i] = std::ldexp(kMid[i], (int)sbyte - 127);
+        t[i] = std::ldexp(kE2m1Mid[i], (int)sbyte - 127);
 #endif
 }
 // the e2m1 code of a 16-bit element: the number of thresholds below |w| (ties to the even code), the sign only on a non-zero magnitude
@@ -136,27 +90,27 @@ template <bool MX, bool BF16> PETIT_HD unsigned quantize_lane(const unsigned (&d
     for (int j = 0; j < 4; ++j)
         words[j] = 0u;
     if constexpr (MX) {
-        scales = mx_scale_byte(abs16_f32<BF16>(mag_max[0] > mag_max[1] ? mag_max[0] : mag_max[1]));
+        scales = mx_scale_byte(h16_f32<BF16>(mag_max[0] > mag_max[1] ? mag_max[0] : mag_max[1]));
         float t[7];
         mx_thresholds(scales, t);
 #pragma unroll
         for (int j = 0; j < 16; ++j) {
-            const unsigned c0 = fp4_code(abs16_f32<BF16>(d[j] & 0x7fffu), t, (d[j] >> 15) & 1u);
-            const unsigned c1 = fp4_code(abs16_f32<BF16>((d[j] >> 16) & 0x7fffu), t, d[j] >> 31);
+            const unsigned c0 = fp4_code(h16_f32<BF16>(d[j] & 0x7fffu), t, (d[j] >> 15) & 1u);
+            const unsigned c1 = fp4_code(h16_f32<BF16>((d[j] >> 16) & 0x7fffu), t, d[j] >> 31);
             words[j / 4] |= (c0 | (c1 << 4)) << (8 * (j % 4));
         }
     } else {
         scales = 0u;
 #pragma unroll
         for (int h = 0; h < 2; ++h) {
-            const unsigned sbyte = nv_scale_byte(abs16_f32<BF16>(mag_max[h]), gs);
+            const unsigned sbyte = nv_scale_byte(h16_f32<BF16>(mag_max[h]), gs);
             scales |= sbyte << (8 * h);
             float t[7];
             nv_thresholds(sbyte, gs, t);
 #pragma unroll
             for (int j = 8 * h; j < 8 * h + 8; ++j) {
-                const unsigned c0 = fp4_code(abs16_f32<BF16>(d[j] & 0x7fffu), t, (d[j] >> 15) & 1u);
-                const unsigned c1 = fp4_code(abs16_f32<BF16>((d[j] >> 16) & 0x7fffu), t, d[j] >> 31);
+                const unsigned c0 = fp4_code(h16_f32<BF16>(d[j] & 0x7fffu), t, (d[j] >> 15) & 1u);
+                const unsigned c1 = fp4_code(h16_f32<BF16>((d[j] >> 16) & 0x7fffu), t, d[j] >> 31);
                 words[j / 4] |= (c0 | (c1 << 4)) << (8 * (j % 4));
             }
         }
@@ -219,7 +173,7 @@ __global__ __launch_bounds__(256) void weight_amax_kernel(unsigned *__restrict__
         for (int off = 32; off; off >>= 1)
             m = max(m, (unsigned)__shfl_xor((int)m, off));
         if (lane == 0)
-            atomicMax(amax + e, f32_bits(abs16_f32<BF16>(m)));
+            atomicMax(amax + e, f32_bits(h16_f32<BF16>(m)));
     }
 #endif
 }
@@ -376,7 +330,7 @@ int quantize_weights_host(const void *w_, int a_type, int b_type, unsigned num_e
             unsigned m = 0;
             for (size_t i = (size_t)e * n * k; i < (size_t)(e + 1) * n * k; ++i)
                 m = std::max(m, w[i] & 0x7fffu);
-            gs = nv_global_scale(bf16 ? abs16_f32<true>(m) : abs16_f32<false>(m));
+            gs = nv_global_scale(bf16 ? h16_f32<true>(m) : h16_f32<false>(m));
         }
         out_gs[e] = gs;
     }

@@ -7,7 +7,7 @@
 // (the thread map of quantize_act32_kernel, gemm_native32.hpp), so the row is read from memory ONCE, stays in registers through the reduction, and
 // MXFP8 / MXFP4 quantise in the map the loads already have (a quad of lanes = one 32-k block).  MXFP6 needs 32 consecutive values per lane for the
 // hardware's 32-element convert: the 16-bit y row goes through LDS once (<= 32 KiB) and is quantised as quantize_act32_fp6_kernel does.
-// The quantise-and-store code is COPIED from those two kernels, not shared with them: they compile to the device code they had.
+// The quantise-and-store code is those two kernels' own: qact_column.inc and qact_block6.inc.
 //
 // moe_combine_rmsnorm_kernel (include/petit_amd.h "Top-k combine into the norm") is the same row with petit_moe_combine as its front end: h comes
 // from the token's top-k slot rows instead of x.  Both kernels end in ONE device function, norm_quant_tail; its format 0 writes 16-bit outputs only.
@@ -22,6 +22,7 @@
 #include <vector>
 
 #include "device_common.hpp"
+#include "numfmt.h"
 #include "petit_internal.h"
 
 #pragma clang fp contract(off)
@@ -30,62 +31,13 @@ namespace petit_amd {
 
 namespace {
 
-PETIT_HD unsigned f32_bits(float x) {
-#if defined(__HIP_DEVICE_COMPILE__)
-    return __builtin_bit_cast(unsigned, x);
-#else
-    unsigned u;
-    memcpy(&u, &x, 4);
-    return u;
-#endif
-}
-PETIT_HD float bits_f32(unsigned u) {
-#if defined(__HIP_DEVICE_COMPILE__)
-    return __builtin_bit_cast(float, u);
-#else
-    float x;
-    memcpy(&x, &u, 4);
-    return x;
-#endif
-}
-
 // one rounding each, never fused with a neighbour (contraction is off in this file)
 PETIT_HD float mul_rn(float a, float b) { return a * b; }
 PETIT_HD float add_rn(float a, float b) { return a + b; }
 PETIT_HD float fma_rn(float a, float b, float c) { return __builtin_fmaf(a, b, c); }
 
-// a 16-bit element -> f32 (exact)
-template <bool BF16> PETIT_HD float h16_f32(unsigned h) {
-    if constexpr (BF16)
-        return bits_f32(h << 16);
-#if defined(__HIP_DEVICE_COMPILE__)
-    return (float)__builtin_bit_cast(_Float16, (unsigned short)h);
-#endif
-    const unsigned sign = (h & 0x8000u) << 16, e = (h >> 10) & 31u, m = h & 0x3ffu;
-    if (e == 0)
-        return bits_f32(sign | f32_bits((float)m * (1.0f / 16777216.0f))); // subnormals: m x 2^-24
-    return bits_f32(sign | (e == 31 ? 0x7f800000u : (e + 112u) << 23) | (m << 13));
-}
-// f32 -> the 16-bit element, round to nearest even (bf16 by the integer rule on both sides; fp16 by the hardware convert on the device and the
-// same rule spelled out on the host: overflow to infinity from 65520 up, subnormals as multiples of 2^-24)
-template <bool BF16> PETIT_HD unsigned f32_h16(float x) {
-    const unsigned u = f32_bits(x);
-    if constexpr (BF16)
-        return (u + 0x7fffu + ((u >> 16) & 1u)) >> 16;
-#if defined(__HIP_DEVICE_COMPILE__)
-    return (unsigned)__builtin_bit_cast(unsigned short, (_Float16)x);
-#endif
-    const unsigned sign = (u >> 16) & 0x8000u, a = u & 0x7fffffffu;
-    if (a > 0x7f800000u)
-        return sign | 0x7e00u;
-    if (a >= 0x477ff000u) // 65520 and above, infinity included
-        return sign | 0x7c00u;
-    if (a < 0x38800000u) // below 2^-14: a x 2^24 is exact and below 1024; the add rounds it to an integer (1024 = the pattern of 2^-14)
-        return sign | (f32_bits(bits_f32(a) * 16777216.0f + 8388608.0f) & 0x7fffffu);
-    const unsigned r = a - 0x38000000u;
-    return sign | ((r + 0xfffu + ((r >> 13) & 1u)) >> 13);
-}
-// the two elements of a dword
+// the two elements of a dword (h16_f32 / f32_h16 of numfmt.h: bf16 by the integer rule on both sides; fp16 by the hardware convert on the device
+// and the same rule spelled out on the host)
 template <bool BF16> PETIT_HD void unpack2(unsigned w, float &lo, float &hi) {
     if constexpr (BF16) {
         lo = bits_f32(w << 16), hi = bits_f32(w & 0xffff0000u);
@@ -94,15 +46,6 @@ template <bool BF16> PETIT_HD void unpack2(unsigned w, float &lo, float &hi) {
     }
 }
 template <bool BF16> PETIT_HD unsigned pack2(float lo, float hi) { return (f32_h16<BF16>(lo) & 0xffffu) | (f32_h16<BF16>(hi) << 16); }
-
-// the quantiser's scale rule (quantize_act32_kernel, gemm_native32.hpp): E8M0 byte of 2^(E - emax_elem), E the exponent of the block maximum,
-// emax_elem = 7 for e4m3 as the native kernels use it, 2 for e2m3 and e2m1; a zero block: byte 127
-template <int ACT> PETIT_HD unsigned act_scale_byte(float amax) {
-    constexpr unsigned kEmax = ACT == 8 ? 7u : 2u;
-    const unsigned ebits = (f32_bits(amax) >> 23) & 0xffu;
-    const unsigned sbyte = amax == 0.f ? 127u : (ebits > kEmax ? ebits - kEmax : 1u);
-    return sbyte > 254u ? 254u : sbyte;
-}
 
 // the sum of squares of one 8-element column: an ascending chain
 PETIT_HD float column_sumsq(const float (&v)[8]) {
@@ -175,9 +118,8 @@ __device__ __forceinline__ void norm_quant_tail(const RmsQuantArgs &p, const u32
     const float sumsq = add_rn(add_rn(add_rn(wave_sum[0], wave_sum[1]), wave_sum[2]), wave_sum[3]);
     const float inv = inv_rms(sumsq, p.rk, p.eps), woff = p.woff;
 
-    const unsigned row_bytes = p.k / 8 * ACT;
     unsigned char *const qa = p.qa;
-    unsigned char *const qs = p.qa + (size_t)m * row_bytes; // (ACT == 0: none of the three is used)
+    unsigned char *const qs = p.qa + qact_elem_bytes(m, p.k, ACT); // (ACT == 0: neither is used)
 #pragma unroll
     for (int j = 0; j < ILP; ++j) {
         const unsigned c8 = t + 256u * j; // 8-element column
@@ -196,55 +138,23 @@ __device__ __forceinline__ void norm_quant_tail(const RmsQuantArgs &p, const u32
             if constexpr (ACT == 6) {
                 y_row[c8] = yv;
             } else if constexpr (ACT != 0) {
-                // from here: quantize_act32_kernel's column, on the 16-bit y
+                // quantize_act32_kernel's column, on the 16-bit y
                 float v[8];
 #pragma unroll
                 for (int d = 0; d < 4; ++d) {
                     const unsigned yw = yv[d];
                     unpack2<BF16>(yw, v[2 * d], v[2 * d + 1]);
                 }
-                float amax = 0.f;
-#pragma unroll
-                for (int i = 0; i < 8; ++i)
-                    amax = fmaxf(amax, fabsf(v[i]));
-                amax = fmaxf(amax, __shfl_xor(amax, 1));
-                amax = fmaxf(amax, __shfl_xor(amax, 2));
-                const unsigned sbyte = act_scale_byte<ACT>(amax);
-                const unsigned kt = c8 / 16, col16 = c8 % 16;
-                if constexpr (ACT == 8) {
-                    const float sc = bits_f32((254u - sbyte) << 23); // 2^-(sbyte-127)
-                    int q0 = 0, q1 = 0;
-                    q0 = __builtin_amdgcn_cvt_pk_fp8_f32(v[0] * sc, v[1] * sc, q0, false);
-                    q0 = __builtin_amdgcn_cvt_pk_fp8_f32(v[2] * sc, v[3] * sc, q0, true);
-                    q1 = __builtin_amdgcn_cvt_pk_fp8_f32(v[4] * sc, v[5] * sc, q1, false);
-                    q1 = __builtin_amdgcn_cvt_pk_fp8_f32(v[6] * sc, v[7] * sc, q1, true);
-                    const unsigned u16 = col16 >> 1, half = col16 & 1u;
-                    const unsigned pos = (u16 & 4u) | ((u16 & 1u) << 1) | ((u16 >> 1) & 1u);
-                    uint2 o;
-                    o.x = (unsigned)q0, o.y = (unsigned)q1;
-                    *reinterpret_cast<uint2 *>(qa + ((size_t)kt * m + row) * 128 + pos * 16 + half * 8) = o;
-                } else {
-                    const float scale = bits_f32(sbyte << 23); // 2^(sbyte-127)
-                    unsigned q = 0;
-                    q = __builtin_amdgcn_cvt_scalef32_pk_fp4_f32(q, v[0], v[1], scale, 0);
-                    q = __builtin_amdgcn_cvt_scalef32_pk_fp4_f32(q, v[2], v[3], scale, 1);
-                    q = __builtin_amdgcn_cvt_scalef32_pk_fp4_f32(q, v[4], v[5], scale, 2);
-                    q = __builtin_amdgcn_cvt_scalef32_pk_fp4_f32(q, v[6], v[7], scale, 3);
-                    *reinterpret_cast<unsigned *>(qa + ((size_t)kt * m + row) * 64 + col16 * 4) = q;
-                }
-                // the four scale bytes of a row's k-tile leave as one dword: the first lane of each quad holds the quad's byte
-                const unsigned s1 = __shfl_down(sbyte, 4, 16), s2 = __shfl_down(sbyte, 8, 16), s3 = __shfl_down(sbyte, 12, 16);
-                if (col16 == 0)
-                    *reinterpret_cast<unsigned *>(qs + ((size_t)kt * m + row) * 4) = sbyte | (s1 << 8) | (s2 << 16) | (s3 << 24);
+#include "qact_column.inc"
             }
         }
     }
     if constexpr (ACT == 6) {
-        // from here: quantize_act32_fp6_kernel's block, read from the LDS row -- one thread = one 32-k block, the four blocks of a k-tile on four
+        // quantize_act32_fp6_kernel's block, read from the LDS row -- one thread = one 32-k block, the four blocks of a k-tile on four
         // consecutive lanes
         __syncthreads();
         const unsigned blocks = p.k / 32;
-        unsigned char *const qa_hi = p.qa + (size_t)m * (p.k / 2);
+        unsigned char *const qa_hi = p.qa + qact_hi_offset(m, p.k);
 #pragma unroll
         for (int i = 0; i < (ILP + 3) / 4; ++i) {
             const unsigned blk = t + 256u * i;
@@ -253,30 +163,7 @@ __device__ __forceinline__ void norm_quant_tail(const RmsQuantArgs &p, const u32
 #pragma unroll
                 for (int q = 0; q < 4; ++q)
                     raw[q] = y_row[blk * 4 + q];
-                unsigned mx = 0; // the block maximum on the 16-bit patterns, sign cleared
-#pragma unroll
-                for (int q = 0; q < 4; ++q)
-#pragma unroll
-                    for (int d = 0; d < 4; ++d) {
-                        const unsigned w = raw[q][d] & 0x7fff7fffu;
-                        const unsigned lo = w & 0xffffu, hi = w >> 16;
-                        mx = mx > lo ? mx : lo;
-                        mx = mx > hi ? mx : hi;
-                    }
-                const unsigned sbyte = act_scale_byte<6>(h16_f32<BF16>(mx));
-                const float scale = bits_f32(sbyte << 23);
-                const u32x16 packed = u32x16{raw[0][0], raw[0][1], raw[0][2], raw[0][3], raw[1][0], raw[1][1], raw[1][2], raw[1][3],
-                                             raw[2][0], raw[2][1], raw[2][2], raw[2][3], raw[3][0], raw[3][1], raw[3][2], raw[3][3]};
-                const u32x6 q = cvt_pk32_fp6_16bit<BF16>(packed, scale); // (early-clobber form: device_common.hpp)
-                const unsigned kt = blk / 4, b = blk % 4;
-                const size_t tile_row = (size_t)kt * m + row;
-                *reinterpret_cast<u32x4 *>(qa + tile_row * 64 + 16 * b) = u32x4{q[0], q[1], q[2], q[3]};
-                uint2 tail;
-                tail.x = q[4], tail.y = q[5];
-                *reinterpret_cast<uint2 *>(qa_hi + tile_row * 32 + 8 * ((b & 1u) * 2 + (b >> 1))) = tail;
-                const unsigned s1 = __shfl_down(sbyte, 1, 4), s2 = __shfl_down(sbyte, 2, 4), s3 = __shfl_down(sbyte, 3, 4);
-                if (b == 0)
-                    *reinterpret_cast<unsigned *>(qs + tile_row * 4) = sbyte | (s1 << 8) | (s2 << 16) | (s3 << 24);
+#include "qact_block6.inc"
             }
         }
     }
@@ -353,11 +240,7 @@ template <bool BF16> PETIT_HD unsigned combine_round2(float lo, float hi) {
 #if defined(__HIP_DEVICE_COMPILE__)
         return __builtin_bit_cast(unsigned, __builtin_convertvector(f32x2{lo, hi}, bf16x2));
 #else
-        const unsigned u[2] = {f32_bits(lo), f32_bits(hi)};
-        unsigned o[2];
-        for (int i = 0; i < 2; ++i)
-            o[i] = (u[i] & 0x7fffffffu) > 0x7f800000u ? (u[i] >> 16) | 0x40u : f32_h16<true>(bits_f32(u[i])) & 0xffffu;
-        return o[0] | (o[1] << 16);
+        return (f32_h16_quiet_nan<true>(lo) & 0xffffu) | ((f32_h16_quiet_nan<true>(hi) & 0xffffu) << 16);
 #endif
     }
     return pack2<false>(lo, hi);
@@ -529,46 +412,13 @@ template <bool BF16> auto rmsq_kernel_for(int format, unsigned k) {
     return format == 8 ? rmsq_kernel_for<BF16, 8>(k) : format == 6 ? rmsq_kernel_for<BF16, 6>(k) : rmsq_kernel_for<BF16, 4>(k);
 }
 
-// --- the host twin's element converts: round to nearest even of x (any sign; the sign is kept, on a zero too), as the hardware converts do ---
-// e4m3fn byte; |x| <= 256 here (the block maximum lands in [128, 256))
-unsigned e4m3_rne_host(float x) {
-    const unsigned sign = (f32_bits(x) >> 24) & 0x80u;
-    const float ax = std::fabs(x);
-    if (!(ax < 448.0f))
-        return sign | 0x7eu;
-    if (ax < 0.015625f) // below 2^-6: multiples of 2^-9; ax x 512 is exact, the add rounds it to an integer (8 = the byte of 2^-6)
-        return sign | (f32_bits(ax * 512.0f + 8388608.0f) & 15u);
-    const unsigned u = f32_bits(ax);
-    return sign | (((u + 0x7ffffu + ((u >> 20) & 1u)) >> 20) - (120u << 3));
-}
-// e2m1 code of x = v / scale (exact in f64): the number of midpoints below |x|, a tie to the even code; saturates at 6
-unsigned e2m1_rne_host(double x) {
-    const unsigned sign = std::signbit(x) ? 8u : 0u;
-    const double a = std::fabs(x);
-    return sign | ((unsigned)(0.25 < a) + (unsigned)(0.75 <= a) + (unsigned)(1.25 < a) + (unsigned)(1.75 <= a) + (unsigned)(2.5 < a) +
-                   (unsigned)(3.5 <= a) + (unsigned)(5.0 < a));
-}
-// e2m3 code: subnormal step 1/8, normals 1 .. 7.5, saturating (nvnative.hip e2m3_rne_host, on an exact f64 quotient)
-unsigned e2m3_rne_host(double x) {
-    const unsigned sign = std::signbit(x) ? 32u : 0u;
-    const double ax = std::fabs(x);
-    if (ax >= 7.5)
-        return sign | 31u;
-    if (ax < 1.0)
-        return sign | (unsigned)std::nearbyint(ax * 8.0); // (8 = the code of 1.0)
-    int e;
-    (void)std::frexp(ax, &e);
-    e -= 1; // floor(log2 ax): 0 .. 2
-    unsigned r = (unsigned)std::nearbyint(std::ldexp(ax, 3 - e)); // 8 .. 16
-    if (r == 16)
-        r = 8, e += 1;
-    return sign | ((unsigned)(e + 1) << 3) | (r - 8u);
-}
+// (the host twin's element converts -- round to nearest even, the sign kept on a zero too, as the hardware converts do -- are e4m3_rne,
+// e2m1_rne and e2m3_rne of numfmt.h, the last two on a quotient v / scale that is exact in f64)
 
 // one row of the quantiser on the 16-bit y, written where the kernels write it
 template <bool BF16, int ACT> void quantize_row_host(unsigned char *ws, const uint16_t *y, unsigned m, unsigned k, unsigned row) {
-    unsigned char *const qs = ws + (size_t)m * (k / 8 * ACT);
-    unsigned char *const qa_hi = ws + (size_t)m * (k / 2); // (MXFP6)
+    unsigned char *const qs = ws + qact_elem_bytes(m, k, ACT);
+    unsigned char *const qa_hi = ws + qact_hi_offset(m, k); // (MXFP6)
     for (unsigned blk = 0; blk < k / 32; ++blk) {
         float v[32], amax = 0.f;
         for (int i = 0; i < 32; ++i) {
@@ -577,33 +427,32 @@ template <bool BF16, int ACT> void quantize_row_host(unsigned char *ws, const ui
         }
         const unsigned sbyte = act_scale_byte<ACT>(amax);
         const unsigned kt = blk / 4, b = blk % 4;
-        const size_t tile_row = (size_t)kt * m + row;
-        qs[tile_row * 4 + b] = (unsigned char)sbyte;
+        const size_t tile_row = qact_tile_row(m, kt, row);
+        qs[qact_scale_dword(m, kt, row) * kQactScaleRowBytes + b] = (unsigned char)sbyte;
         if constexpr (ACT == 8) {
             const float sc = bits_f32((254u - sbyte) << 23);
             for (unsigned c = 0; c < 4; ++c) { // the block's four 8-element columns
                 const unsigned col16 = 4 * b + c, u16 = col16 >> 1, half = col16 & 1u;
-                const unsigned pos = (u16 & 4u) | ((u16 & 1u) << 1) | ((u16 >> 1) & 1u);
-                unsigned char *const o = ws + tile_row * 128 + pos * 16 + half * 8;
+                unsigned char *const o = ws + tile_row * qact_row_bytes(8) + qact_fp8_unit_pos(u16) * 16 + half * 8;
                 for (int i = 0; i < 8; ++i)
-                    o[i] = (unsigned char)e4m3_rne_host(v[8 * c + i] * sc);
+                    o[i] = (unsigned char)e4m3_rne(v[8 * c + i] * sc);
             }
         } else if constexpr (ACT == 4) {
-            unsigned char *const o = ws + tile_row * 64 + 16 * b;
+            unsigned char *const o = ws + tile_row * qact_row_bytes(4) + 16 * b;
             for (int i = 0; i < 16; ++i)
-                o[i] = (unsigned char)(e2m1_rne_host(std::ldexp((double)v[2 * i], 127 - (int)sbyte)) |
-                                       (e2m1_rne_host(std::ldexp((double)v[2 * i + 1], 127 - (int)sbyte)) << 4));
+                o[i] = (unsigned char)(e2m1_rne(std::ldexp((double)v[2 * i], 127 - (int)sbyte)) |
+                                       (e2m1_rne(std::ldexp((double)v[2 * i + 1], 127 - (int)sbyte)) << 4));
         } else {
             unsigned char bytes[24] = {};
             for (int i = 0; i < 32; ++i) { // element i at bits [6 i, 6 i + 6)
-                const unsigned code = e2m3_rne_host(std::ldexp((double)v[i], 127 - (int)sbyte));
+                const unsigned code = e2m3_rne(std::ldexp((double)v[i], 127 - (int)sbyte));
                 const unsigned bit = 6 * i;
                 bytes[bit / 8] |= (unsigned char)(code << (bit % 8));
                 if (bit % 8 > 2)
                     bytes[bit / 8 + 1] |= (unsigned char)(code >> (8 - bit % 8));
             }
-            memcpy(ws + tile_row * 64 + 16 * b, bytes, 16);
-            memcpy(qa_hi + tile_row * 32 + 8 * ((b & 1u) * 2 + (b >> 1)), bytes + 16, 8);
+            memcpy(ws + tile_row * qact_row_bytes(6) + 16 * b, bytes, 16);
+            memcpy(qa_hi + tile_row * kQactHiRowBytes + 8 * qact_fp6_hi_slot(b), bytes + 16, 8);
         }
     }
 }

@@ -359,7 +359,7 @@ at::Tensor mul_mxfp4_native_invariant(PETIT_NATIVE_INVARIANT_ARGS) {
     TORCH_CHECK(act_format == 8 || act_format == 6 || act_format == 4, "act_format must be 8, 6 or 4");
     TORCH_CHECK(size_m >= 0 && size_n > 0 && size_k > 0 && size_k % 256 == 0 && A.is_cuda() && B.is_cuda() && s.is_cuda() && A.is_contiguous() &&
                     B.is_contiguous() && s.is_contiguous() && B.device() == A.device() && s.device() == A.device() &&
-                    (quantized ? A.scalar_type() == at::kByte && A.numel() == size_m * (size_k / 8 * act_format) + size_m * (size_k / 32)
+                    (quantized ? A.scalar_type() == at::kByte && A.numel() == (int64_t)petit_quantized_activation_bytes((unsigned)size_m, (unsigned)size_k, (int)act_format)
                                : A.scalar_type() == st && A.numel() == size_m * size_k) &&
                     B.numel() * B.element_size() == size_n * size_k / 2 && s.numel() * s.element_size() == size_n * size_k / 32 &&
                     (!global_scale || (global_scale->is_cuda() && global_scale->device() == A.device() &&
@@ -381,7 +381,7 @@ at::Tensor mul_nvfp4_native_invariant(PETIT_NV_NATIVE_INVARIANT_ARGS) {
     TORCH_CHECK(act_format == 8 || act_format == 6 || act_format == 4, "act_format must be 8, 6 or 4");
     TORCH_CHECK(size_m >= 0 && size_n > 0 && size_k > 0 && size_k % 256 == 0 && A.is_cuda() && image.is_cuda() && A.is_contiguous() &&
                     image.is_contiguous() && image.device() == A.device() &&
-                    (quantized ? A.scalar_type() == at::kByte && A.numel() == size_m * (size_k / 8 * act_format) + size_m * (size_k / 32)
+                    (quantized ? A.scalar_type() == at::kByte && A.numel() == (int64_t)petit_quantized_activation_bytes((unsigned)size_m, (unsigned)size_k, (int)act_format)
                                : A.scalar_type() == st && A.numel() == size_m * size_k) &&
                     image.scalar_type() == at::kByte && image.numel() > 0 &&
                     image.numel() == (int64_t)petit_nvfp4_native_image_bytes((unsigned)size_k, (unsigned)size_n) &&
@@ -518,7 +518,7 @@ at::Tensor mul_mxfp4_native_moe_invariant(PETIT_NATIVE_MOE_INVARIANT_ARGS) {
     TORCH_CHECK(act_format == 8 || act_format == 6 || act_format == 4, "act_format must be 8, 6 or 4");
     check_expert_operands(true, false, A, B, &s, gs, off, e, n, k);
     TORCH_CHECK(m >= 0 && n > 0 && k > 0 && k % 256 == 0 && A.is_contiguous() &&
-                    (quantized ? A.scalar_type() == at::kByte && A.numel() == m * (k / 8 * act_format) + m * (k / 32) && !a_idx.has_value()
+                    (quantized ? A.scalar_type() == at::kByte && A.numel() == (int64_t)petit_quantized_activation_bytes((unsigned)m, (unsigned)k, (int)act_format) && !a_idx.has_value()
                                : A.scalar_type() == st && A.numel() % k == 0),
                 "A must be a contiguous [a_rows, size_k] tensor, or the quantised bytes of the size_m grouped rows without an a_row_index");
     check_row_indices(a_idx, c_idx, A, m);
@@ -539,7 +539,7 @@ at::Tensor mul_nvfp4_native_moe_invariant(PETIT_NV_NATIVE_MOE_INVARIANT_ARGS) {
     TORCH_CHECK(act_format == 8 || act_format == 6 || act_format == 4, "act_format must be 8, 6 or 4");
     TORCH_CHECK(n > 0 && k > 0 && k % 256 == 0, "size_n and size_k must be positive, size_k % 256 == 0");
     check_expert_operands(false, true, A, images, nullptr, gs, off, e, n, k);
-    TORCH_CHECK(m >= 0 && (quantized ? A.scalar_type() == at::kByte && A.numel() == m * (k / 8 * act_format) + m * (k / 32) && !a_idx.has_value()
+    TORCH_CHECK(m >= 0 && (quantized ? A.scalar_type() == at::kByte && A.numel() == (int64_t)petit_quantized_activation_bytes((unsigned)m, (unsigned)k, (int)act_format) && !a_idx.has_value()
                                      : A.scalar_type() == st && A.numel() % k == 0),
                 "A must be a contiguous [a_rows, size_k] tensor, or the quantised bytes of the size_m grouped rows without an a_row_index");
     check_row_indices(a_idx, c_idx, A, m);

@@ -409,7 +409,7 @@ def _check_invariant(A, B, s, global_scale, size_m, size_n, size_k, bias, activa
         if moe:
             _check(a_row_index is None, f"{name}: quantised activations are the grouped rows already; a_row_index must be None")
         a, a_rows = A.data, size_m
-        _check(a.dtype == torch.uint8 and a.is_contiguous() and a.numel() == size_m * (size_k // 8 * _QFORMATS[fmt]) + size_m * (size_k // 32),
+        _check(a.dtype == torch.uint8 and a.is_contiguous() and a.numel() == int(_lib.lib.petit_quantized_activation_bytes(size_m, size_k, _QFORMATS[fmt])),
                "quantised activations do not hold the bytes of their [m, k] and format")
     elif moe:
         a = A

@@ -14,6 +14,8 @@
 //     by the layout notes, not by the header's own helper).
 //   the native entries on NVFP4 images: the same, on "petit-cdna4-nv6/1" images written element by element from the layout notes of layout.h.
 //   then every refusal, the form rules, the workspace arithmetic written out by hand, and the plan's grids against literals.
+//   first of all: the encoders and decoders of numfmt.h and the "petit-qact/1" functions of layout.h on their edge values (zero, subnormals,
+//     ties, the saturation points, infinity, NaN, scale bytes 0 / 254 / 255, the last row and k-tile of an image).
 // Exit status 0 and "ok" when everything holds.
 #include <algorithm>
 #include <cmath>
@@ -129,7 +131,7 @@ static void check_exact_problem(std::mt19937 &rng, unsigned m, unsigned n, unsig
     std::vector<double> b64(n);
     for (unsigned i = 0; i < n; ++i) {
         const int v = (int)(rng() % 17) - 8;
-        bias[i] = (uint16_t)f32_h16(bf16, (float)v), b64[i] = v;
+        bias[i] = (uint16_t)f32_h16_quiet_nan(bf16, (float)v), b64[i] = v;
     }
     for (int with_gs = 0; with_gs < 2; ++with_gs)
         for (int with_bias = 0; with_bias < 2; ++with_bias) {
@@ -142,7 +144,7 @@ static void check_exact_problem(std::mt19937 &rng, unsigned m, unsigned n, unsig
                     for (unsigned kk = 0; kk < k; ++kk)
                         y += a64[(size_t)row * k + kk] * w[(size_t)col * k + kk];
                     y = y * (with_gs ? 0.25 : 1.0) + (with_bias ? b64[col] : 0.0);
-                    EXPECT(c[(size_t)row * n + col] == (uint16_t)f32_h16(bf16, (float)y)); // exact inputs: one rounding is left
+                    EXPECT(c[(size_t)row * n + col] == (uint16_t)f32_h16_quiet_nan(bf16, (float)y)); // exact inputs: one rounding is left
                     EXPECT(c1[col] == c[(size_t)row * n + col]);                           // the row alone: the same bits
                 }
             }
@@ -161,7 +163,7 @@ static void run_pair(int a_type, int b_type, unsigned m, unsigned n, unsigned k,
     std::vector<uint16_t> a((size_t)m * k);
     for (size_t i = 0; i < a.size(); ++i) {
         const int v = (rng() & 1u) ? (int)(rng() % 7) - 3 : 0;
-        a[i] = (uint16_t)f32_h16(bf16, (float)v), a64[i] = v;
+        a[i] = (uint16_t)f32_h16_quiet_nan(bf16, (float)v), a64[i] = v;
     }
     check_exact_problem(rng, m, n, k, bf16, a64, w, [&](uint16_t *c, int row, const float *gs, const uint16_t *bias) {
         return row < 0 ? gemm_host(c, a.data(), pw.data(), ps.data(), gs, bias, m, n, k, a_type, b_type)
@@ -209,9 +211,9 @@ static void run_moe_pair(int a_type, int b_type, unsigned E, unsigned m, unsigne
         s = mx ? (uint8_t)(126 + rng() % 3) : (uint8_t)(0x30 + rng() % 0x18);
     std::vector<uint16_t> a((size_t)a_rows * k), bias((size_t)E * n), c((size_t)c_rows * n, 0x7fc1u), ref(n), zero(k, 0);
     for (auto &v : a)
-        v = (uint16_t)f32_h16(bf16, (float)((int)(rng() % 9) - 4) * 0.25f);
+        v = (uint16_t)f32_h16_quiet_nan(bf16, (float)((int)(rng() % 9) - 4) * 0.25f);
     for (auto &v : bias)
-        v = (uint16_t)f32_h16(bf16, (float)((int)(rng() % 17) - 8));
+        v = (uint16_t)f32_h16_quiet_nan(bf16, (float)((int)(rng() % 17) - 8));
     std::vector<float> gs(E);
     for (auto &g : gs)
         g = 0.125f * (float)(1 + rng() % 5);
@@ -380,7 +382,7 @@ static void run_native_moe_pair(int a_type, int fmt, unsigned E, unsigned m, uns
     for (auto &g : gs)
         g = 0.5f + (float)(rng() % 64) / 128.f;
     for (auto &b : bias)
-        b = (uint16_t)f32_h16(bf16, (float)((int)(rng() % 33) - 16) * 0.25f);
+        b = (uint16_t)f32_h16_quiet_nan(bf16, (float)((int)(rng() % 33) - 16) * 0.25f);
 
     const unsigned c_rows = m + 2;
     std::vector<int32_t> c_idx(m);
@@ -470,7 +472,7 @@ static void run_nv_native_moe_pair(int a_type, int fmt, unsigned E, unsigned m, 
     for (auto &g : gs)
         g = 0.5f + (float)(rng() % 64) / 128.f;
     for (auto &b : bias)
-        b = (uint16_t)f32_h16(bf16, (float)((int)(rng() % 33) - 16) * 0.25f);
+        b = (uint16_t)f32_h16_quiet_nan(bf16, (float)((int)(rng() % 33) - 16) * 0.25f);
     const unsigned c_rows = m + 2;
     std::vector<int32_t> c_idx(m);
     for (unsigned r = 0; r < m; ++r)
@@ -817,7 +819,130 @@ static void check_nv_native() {
     EXPECT(nv_native_moe_gemm_host(nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, 3, 0, 32, 256, nullptr, 0, kTypeBf16, 8) == kRcOk);
 }
 
+// ---- numfmt.h and the "petit-qact/1" functions of layout.h on their edge values ----------------------------------------------------------------
+
+template <bool BF16> static void check_h16() {
+    for (unsigned h = 0; h < 0x10000u; ++h) { // every pattern survives the round trip (fp16: a NaN comes back as the quiet 0x7e00 with its sign)
+        const bool nan = BF16 ? (h & 0x7fffu) > 0x7f80u : (h & 0x7fffu) > 0x7c00u;
+        const float x = h16_f32<BF16>(h);
+        EXPECT(std::isnan(x) == nan && (nan || h16_f32(BF16, h) == x));
+        EXPECT(f32_h16<BF16>(x) == ((nan && !BF16) ? (h & 0x8000u) | 0x7e00u : h));
+        EXPECT(f32_h16_quiet_nan<BF16>(x) == ((nan && BF16) ? h | 0x40u : f32_h16<BF16>(x)));
+        EXPECT(f32_h16_quiet_nan(BF16, x) == f32_h16_quiet_nan<BF16>(x));
+    }
+}
+
+static void check_numfmt() {
+    const float inf = INFINITY, nan = NAN;
+    EXPECT(f32_bits(1.0f) == 0x3f800000u && f32_bits(-0.0f) == 0x80000000u && bits_f32(0x7f800000u) == inf && f32_bits(bits_f32(0x7fc12345u)) == 0x7fc12345u);
+    // the 16-bit types: decode, ties to even, the ends of the range, NaN under both rules
+    check_h16<true>();
+    check_h16<false>();
+    EXPECT(h16_f32<true>(0x3f80u) == 1.0f && h16_f32<false>(0x3c00u) == 1.0f && h16_f32<false>(1u) == 0x1p-24f && h16_f32<false>(0x03ffu) == 1023 * 0x1p-24f);
+    EXPECT(h16_f32<false>(0x7bffu) == 65504.0f && h16_f32<false>(0xfc00u) == -inf && std::signbit(h16_f32<false>(0x8000u)) && h16_f32<false>(0x8000u) == 0.0f);
+    EXPECT(f32_h16<true>(bits_f32(0x3f808000u)) == 0x3f80u && f32_h16<true>(bits_f32(0x3f818000u)) == 0x3f82u && f32_h16<true>(bits_f32(0x3f808001u)) == 0x3f81u);
+    EXPECT(f32_h16<true>(bits_f32(0x7f7fffffu)) == 0x7f80u && f32_h16<true>(inf) == 0x7f80u && f32_h16<true>(-0.0f) == 0x8000u);
+    EXPECT(f32_h16<true>(bits_f32(0x7f800001u)) == 0x7f80u && f32_h16<true>(bits_f32(0x7fffffffu)) == 0x8000u); // the integer rule on a NaN
+    EXPECT(f32_h16_quiet_nan<true>(bits_f32(0x7f800001u)) == 0x7fc0u && f32_h16_quiet_nan<true>(bits_f32(0xffffffffu)) == 0xffffu);
+    EXPECT(f32_h16<false>(65519.0f) == 0x7bffu && f32_h16<false>(65520.0f) == 0x7c00u && f32_h16<false>(inf) == 0x7c00u && f32_h16<false>(-1e30f) == 0xfc00u);
+    EXPECT(f32_h16<false>(0x1p-25f) == 0u && f32_h16<false>(0x1.000002p-25f) == 1u && f32_h16<false>(0x1.8p-24f) == 2u && f32_h16<false>(0x1p-14f) == 0x0400u);
+    EXPECT(f32_h16<false>(bits_f32(1u)) == 0u && f32_h16<false>(-bits_f32(1u)) == 0x8000u && f32_h16<false>(nan) == (0x7e00u | (f32_bits(nan) >> 16 & 0x8000u)));
+    EXPECT(f32_h16<false>(1.0f + 0x1p-11f) == 0x3c00u && f32_h16<false>(1.0f + 0x1.8p-10f) == 0x3c02u);
+    // e2m1: the table, every midpoint to the even code, saturation, the sign of zero
+    static const float mag4[8] = {0.f, 0.5f, 1.f, 1.5f, 2.f, 3.f, 4.f, 6.f};
+    for (unsigned c = 0; c < 16; ++c) {
+        EXPECT(e2m1_f32(c) == ((c & 8u) ? -mag4[c & 7u] : mag4[c & 7u]) && std::signbit(e2m1_f32(c)) == ((c & 8u) != 0));
+        EXPECT(e2m1_rne((double)e2m1_f32(c)) == c);
+    }
+    for (unsigned i = 0; i < 7; ++i) {
+        const double mid = (mag4[i] + mag4[i + 1]) / 2;
+        EXPECT((double)kE2m1Mid[i] == mid && e2m1_rne(mid) == (i % 2 ? i + 1 : i) && e2m1_rne(-mid) == (8u | (i % 2 ? i + 1 : i)));
+        EXPECT(e2m1_rne(std::nextafter(mid, 0.0)) == i && e2m1_rne(std::nextafter(mid, 9.0)) == i + 1);
+    }
+    EXPECT(e2m1_rne(6.0) == 7u && e2m1_rne(1e300) == 7u && e2m1_rne((double)inf) == 7u && e2m1_rne(-(double)inf) == 15u && (e2m1_rne((double)nan) & 7u) == 0u);
+    EXPECT(e2m1_rne(0x1p-1074) == 0u && e2m1_rne(-0x1p-1074) == 8u);
+    // e4m3: every byte decodes and encodes back; subnormals, ties, saturation, NaN; the unsigned and the finite variants
+    for (unsigned b = 0; b < 256; ++b) {
+        const float x = e4m3_f32(b);
+        EXPECT(std::isnan(x) == e4m3_is_nan(b) && std::signbit(x) == (b >= 128));
+        if (e4m3_is_nan(b)) {
+            EXPECT(e4m3_finite_f32(b) == (b & 0x80u ? -480.0f : 480.0f));
+            continue;
+        }
+        EXPECT(e4m3_rne(x) == b && e4m3_finite_f32(b) == x && e4m3_mag_f32(b & 0x7fu) == std::fabs(x) && e4m3_rne_sat(std::fabs(x)) == (b & 0x7fu));
+    }
+    EXPECT(e4m3_f32(1) == 0x1p-9f && e4m3_f32(7) == 7 * 0x1p-9f && e4m3_f32(8) == 0x1p-6f && e4m3_f32(0x7e) == 448.0f && e4m3_f32(0xfe) == -448.0f);
+    EXPECT(e4m3_rne(0x1p-10f) == 0u && e4m3_rne(0x1.8p-9f) == 2u && e4m3_rne(0x1.000002p-10f) == 1u && e4m3_rne(bits_f32(1u)) == 0u && e4m3_rne(-bits_f32(1u)) == 0x80u);
+    EXPECT(e4m3_rne(1.0625f) == 0x38u && e4m3_rne(1.1875f) == 0x3au && e4m3_rne(0x1.fp-7f) == 0x08u && e4m3_rne(-0.0f) == 0x80u);
+    EXPECT(e4m3_rne(448.0f) == 0x7eu && e4m3_rne(464.0f) == 0x7eu && e4m3_rne(1e30f) == 0x7eu && e4m3_rne(-inf) == 0xfeu && (e4m3_rne(nan) & 0x7fu) == 0x7eu);
+    EXPECT(e4m3_rne_sat(nan) == 0x7eu && e4m3_rne_sat(inf) == 0x7eu && e4m3_rne_sat(447.9f) == 0x7eu && e4m3_rne_sat(431.9f) == 0x7du);
+    // e2m3: every code decodes and encodes back; ties, saturation, the sign of zero
+    for (unsigned c = 0; c < 64; ++c)
+        EXPECT(e2m3_rne((double)e2m3_f32(c)) == c && std::signbit(e2m3_f32(c)) == (c >= 32));
+    EXPECT(e2m3_f32(1) == 0.125f && e2m3_f32(7) == 0.875f && e2m3_f32(8) == 1.0f && e2m3_f32(31) == 7.5f && e2m3_f32(63) == -7.5f);
+    EXPECT(e2m3_rne(0.0625) == 0u && e2m3_rne(0.1875) == 2u && e2m3_rne(0.9375) == 8u && e2m3_rne(1.0625) == 8u && e2m3_rne(1.9375) == 16u);
+    EXPECT(e2m3_rne(7.25) == 30u && e2m3_rne(std::nextafter(7.25, 8.0)) == 31u && e2m3_rne(7.5) == 31u && e2m3_rne(7.75) == 31u && e2m3_rne(1e300) == 31u);
+    EXPECT(e2m3_rne((double)inf) == 31u && e2m3_rne(-(double)inf) == 63u && e2m3_rne(0x1p-1074) == 0u && e2m3_rne(-0.0) == 32u && e2m3_rne((double)bits_f32(1u)) == 0u);
+    // e8m0 as the kernels read it
+    EXPECT(e8m0_f32(0) == 0x1p-127f && e8m0_f32(1) == 0x1p-126f && e8m0_f32(127) == 1.0f && e8m0_f32(254) == 0x1p127f && std::isinf(e8m0_f32(255)));
+    EXPECT(e8m0_f64(0) == 0x1p-127 && e8m0_f64(254) == 0x1p127 && std::isinf(e8m0_f64(255)) && e8m0_f32(256 + 127) == 1.0f);
+    // the activation block-scale rule: a zero block, subnormal and tiny maxima (byte 1), the largest, infinity and NaN (never 0 or 255)
+    EXPECT(act_scale_byte<8>(0.f) == 127u && act_scale_byte<6>(0.f) == 127u && act_scale_byte<4>(-0.0f) == 127u);
+    EXPECT(act_scale_byte<8>(1.0f) == 120u && act_scale_byte<8>(200.0f) == 127u && act_scale_byte<8>(255.9f) == 127u && act_scale_byte<8>(256.0f) == 128u);
+    EXPECT(act_scale_byte<6>(1.0f) == 125u && act_scale_byte<6>(7.5f) == 127u && act_scale_byte<4>(6.0f) == 127u && act_scale_byte<4>(8.0f) == 128u);
+    EXPECT(act_scale_byte<8>(bits_f32(1u)) == 1u && act_scale_byte<8>(0x1p-119f) == 1u && act_scale_byte<8>(0x1p-118f) == 2u && act_scale_byte<4>(0x1p-124f) == 1u);
+    EXPECT(act_scale_byte<4>(0x1p-123f) == 2u && act_scale_byte<8>(bits_f32(0x7f7fffffu)) == 247u && act_scale_byte<4>(bits_f32(0x7f7fffffu)) == 252u);
+    EXPECT(act_scale_byte<8>(inf) == 248u && act_scale_byte<6>(inf) == 253u && act_scale_byte<4>(nan) == 253u);
+    for (int e = -10; e <= 9; ++e) // the image builder's variant on its whole domain
+        for (float f : {1.0f, 1.5f, 1.9999999f})
+            EXPECT(act_scale_byte_nv6(std::ldexp(f, e)) == act_scale_byte<6>(std::ldexp(f, e)) && act_scale_byte_nv6(std::ldexp(f, e)) == (unsigned)(e + 125));
+    EXPECT(act_scale_byte_nv6(0.f) == 127u);
+}
+
+// every bit of the element regions and every byte of the scale region is named by exactly one (row, k), the last row and k-tile included; the
+// sizes against the formula written out
+static void check_qact_layout() {
+    static const unsigned pos8[8] = {0, 2, 1, 3, 4, 6, 5, 7}, slot6[4] = {0, 2, 1, 3};
+    for (unsigned u = 0; u < 8; ++u) // the order [0-15][32-47][16-31][48-63][64-79][96-111][80-95][112-127]
+        EXPECT(qact_fp8_unit_pos(u) == pos8[u]);
+    for (unsigned b = 0; b < 4; ++b) // blocks 0, 2, 1, 3
+        EXPECT(qact_fp6_hi_slot(b) == slot6[b]);
+    EXPECT(qact_row_bytes(8) == 128u && qact_row_bytes(6) == 64u && qact_row_bytes(4) == 64u && kQactHiRowBytes == 32u && kQactScaleRowBytes == 4u);
+    const unsigned shapes[][2] = {{1, 128}, {1, 256}, {5, 768}, {33, 256}, {130, 384}};
+    for (const auto &s : shapes)
+        for (int act : {8, 6, 4}) {
+            const unsigned m = s[0], k = s[1];
+            const size_t elems = qact_elem_bytes(m, k, act), total = qact_bytes(m, k, act);
+            EXPECT(elems == (size_t)m * k * act / 8 && qact_scale_bytes(m, k) == (size_t)m * k / 32 && total == elems + (size_t)m * k / 32);
+            EXPECT(qact_lo_bytes(m, k, act) == (act == 6 ? (size_t)m * k / 2 : elems) && qact_hi_offset(m, k) == qact_lo_bytes(m, k, 6));
+            std::vector<uint8_t> bits(elems * 8, 0), scale(total - elems, 0);
+            for (unsigned row = 0; row < m; ++row)
+                for (unsigned kk = 0; kk < k; ++kk) {
+                    const unsigned kt = kk / 128, b = kk % 128 / 32, i = kk % 32, col16 = kk % 128 / 8;
+                    const size_t tile_row = qact_tile_row(m, kt, row), lo = tile_row * qact_row_bytes(act);
+                    if (act == 8) {
+                        for (unsigned j = 0; j < 8; ++j)
+                            ++bits.at((lo + qact_fp8_unit_pos(col16 >> 1) * 16 + (col16 & 1u) * 8 + kk % 8) * 8 + j);
+                    } else if (act == 4) {
+                        for (unsigned j = 0; j < 4; ++j)
+                            ++bits.at((lo + 16 * b + i / 2) * 8 + 4 * (i & 1u) + j);
+                    } else {
+                        const size_t hi = qact_hi_offset(m, k) + tile_row * kQactHiRowBytes + 8 * qact_fp6_hi_slot(b);
+                        for (unsigned j = 6 * i; j < 6 * i + 6; ++j)
+                            ++bits.at((j < 128 ? lo + 16 * b : hi - 16) * 8 + j);
+                    }
+                    if (i == 0)
+                        ++scale.at(qact_scale_dword(m, kt, row) * kQactScaleRowBytes + b);
+                }
+            EXPECT(std::count(bits.begin(), bits.end(), 1) == (long)bits.size() && std::count(scale.begin(), scale.end(), 1) == (long)scale.size());
+        }
+    // the largest image the entries accept stays below their 32-bit limit by the same count
+    EXPECT(qact_bytes(1u << 20, 4096, 8) == (1ull << 32) + (1ull << 27) && qact_bytes(0, 4096, 8) == 0 && qact_hi_offset(1u << 20, 8192) == 1ull << 32);
+}
+
 int main() {
+    check_numfmt();
+    check_qact_layout();
     check_dense();
     check_moe();
     check_native();
