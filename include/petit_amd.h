@@ -1193,6 +1193,55 @@ int petit_quantize_activations_rows(void *qa, const void *a, const int32_t *a_ro
                                     int format, void *stream);
 
 /*
+ * Block-Hadamard rotation ("petit-had/1") in the native class's activation quantisers (no counterpart in the reference).  MXFP4 activations
+ * cost the native class most of its accuracy; the standard cure (QuaRot, MR-GPTQ, QuTLASS) multiplies activations and weights along K by
+ * the same +-1 Hadamard block, which leaves the product unchanged and spreads a block's outliers over all of its coefficients before the
+ * 4-bit rounding.  The rotation runs INSIDE the quantiser launches: no extra launch and no [m][k] 16-bit round trip per GEMM input.
+ *
+ * Definition.  B (`block`) is 32 or 128; k % 256 == 0, so a row is a whole number of blocks.  For a row x of 16-bit elements widened exactly
+ * to f32 and each block of B consecutive k, z[0 .. B-1] is the block; for s = 0 .. log2(B) - 1 IN THIS ORDER, d = 2^s, and every i with
+ * (i & d) == 0:
+ *         (z[i], z[i + d])  <-  (z[i] + z[i + d],  z[i] - z[i + d])
+ * Each sum and each difference is ONE f32 operation, round to nearest even; nothing is fused.  This is z . H_B with the Sylvester Hadamard
+ * matrix in natural order, unnormalised: H_B is symmetric and H_B . H_B = B . I.  The stage order is part of the contract (sums of 128
+ * bf16 values round in f32: another order gives other bits).  Two consumers of z:
+ *   1. rotation to 16 bit (load time, weights): out = round16(z * 2^log2_scale) -- one f32 multiply by a power of two (exact short of
+ *      over- or underflow), ONE round to nearest even into the 16-bit type, subnormals included.   petit_hadamard_rows
+ *   2. rotation into the quantiser (per call, activations): z takes the place of the widened row in petit_quantize_activations and nothing
+ *      else changes -- the block maximum over each 32-k block of z (with B = 128 a rotation block still carries four scales), the same
+ *      scale rule, converts, stores and layout; no intermediate 16-bit rounding.   petit_quantize_activations_rot and its kin
+ * The identity a caller relies on:  (x . H_B) . (W . H_B . 2^-log2(B))^T = x . W^T.  Activations rotate with scale 1; weights rotate with
+ * log2_scale = -log2(B), which is exact.  A checkpoint whose weights were rotated with the orthonormal H / sqrt(B) runs on the same
+ * activation entries: the caller folds 1 / sqrt(B) into global_scale.  The GEMMs read "petit-qact/1" bytes and cannot tell that they were
+ * rotated; a rotated row is still a pure function of its row, so the batch-invariant entries keep their property unchanged.
+ * A block that contains a non-finite element gives unspecified elements and scales for its own 32-k blocks only.  A zero block stays zero
+ * with scale byte 127; a gathered row whose index is out of range stays a zero row.
+ *
+ * block == 0 is the unrotated entry, bit for bit (the call is handed on); a block other than 0 / 32 / 128 is PETIT_ERROR_BAD_ARGUMENT.
+ * format is 8 or 4; format == 6 with a rotation is PETIT_ERROR_KERNEL_SHAPE (the MXFP6 quantiser converts 32 elements straight from their
+ * 16-bit patterns; an f32 form of it is out of scope).  Every other refusal is that of the unrotated entry.  petit_hadamard_rows refuses
+ * k % 256 != 0 (PETIT_ERROR_PROBLEM_SHAPE), an a_type other than bf16 / fp16 (PETIT_ERROR_KERNEL_SHAPE), and a block other than 32 / 128,
+ * |log2_scale| > 126, null pointers or pointers not aligned to 16 bytes (PETIT_ERROR_BAD_ARGUMENT); out may be in (a block is read
+ * completely before it is written).  All refusals come before any launch; no allocation, no host sync, graph-capturable.  The _host
+ * forms are the host twins (host pointers): bit-identical outputs, the same refusals.
+ * In the fused norm steps 1 - 4 of "RMSNorm into quantised activations" are untouched: y is rounded to 16 bit and the rotation runs on
+ * f32(y16), so qa is bit for bit petit_quantize_activations_rot on the y16 the same call can return; y16 and residual_out stay unrotated.
+ * Out of scope: MXFP6 activations; the quantising gated epilogue (out_format of the gate_up kernels cannot rotate -- a rotated `down`
+ * takes the 16-bit hand-over plus petit_quantize_activations_rot); petit_moe_combine_rmsnorm; random sign diagonals; every GEMM and MoE
+ * kernel, which consume the bytes as they are.
+ */
+int petit_hadamard_rows(void *out, const void *in, unsigned rows, unsigned k, int a_type, unsigned block, int log2_scale, void *stream);
+int petit_hadamard_rows_host(void *out, const void *in, unsigned rows, unsigned k, int a_type, unsigned block, int log2_scale);
+int petit_quantize_activations_rot(void *qa, const void *a, unsigned m, unsigned k, int a_type, int format, unsigned block, void *stream);
+int petit_quantize_activations_rot_host(void *qa, const void *a, unsigned m, unsigned k, int a_type, int format, unsigned block);
+int petit_quantize_activations_rows_rot(void *qa, const void *a, const int32_t *a_row_index, unsigned a_rows, unsigned m, unsigned k, int a_type,
+                                        int format, unsigned block, void *stream);
+int petit_rmsnorm_quantize_rot(void *qa, void *y16, void *residual_out, const void *x, const void *residual, const void *weight, float eps,
+                               float weight_offset, unsigned m, unsigned k, int a_type, int format, unsigned block, void *stream);
+int petit_rmsnorm_quantize_rot_host(void *qa, void *y16, void *residual_out, const void *x, const void *residual, const void *weight, float eps,
+                                    float weight_offset, unsigned m, unsigned k, int a_type, int format, unsigned block);
+
+/*
  * Tune-and-persist (replaces the reference's `bench_matmul -algo tune`, tools/benchmarks/matmul/main.cc:269-325, which
  * enumerates and times every solution on the user's device but leaves the winning id for the user to carry around).
  *

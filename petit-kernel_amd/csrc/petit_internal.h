@@ -201,6 +201,12 @@ int rmsnorm_quantize_host(void *qa, void *y16, void *residual_out, const void *x
                           float weight_offset, unsigned m, unsigned k, int a_type, int format);
 int rmsnorm_inv_host(float *inv, const void *x, const void *residual, float eps, unsigned m, unsigned k, int a_type); // (test aid: f32 inv per row)
 int quantize_activations_host(void *qa, const void *a, unsigned m, unsigned k, int a_type, int format); // the twins' quantiser on a 16-bit [m][k]
+// the same three with the block-Hadamard rotation in front of the quantiser (include/petit_amd.h "Block-Hadamard rotation"); block 0: the above
+int rmsnorm_quantize_rot(void *qa, void *y16, void *residual_out, const void *x, const void *residual, const void *weight, float eps,
+                         float weight_offset, unsigned m, unsigned k, int a_type, int format, unsigned block, hipStream_t stream);
+int rmsnorm_quantize_rot_host(void *qa, void *y16, void *residual_out, const void *x, const void *residual, const void *weight, float eps,
+                              float weight_offset, unsigned m, unsigned k, int a_type, int format, unsigned block);
+int quantize_activations_rot_host(void *qa, const void *a, unsigned m, unsigned k, int a_type, int format, unsigned block);
 // the MoE top-k combine as the front end of the same row (include/petit_amd.h "Top-k combine into the norm"); format 0: 16-bit outputs only
 int moe_combine_rmsnorm(void *qa, void *y16, void *residual_out, const void *slot_out, const float *topk_weights, const void *topk_ids,
                         int ids_are_int64, const void *residual, const void *weight, float eps, float weight_offset, unsigned num_tokens,

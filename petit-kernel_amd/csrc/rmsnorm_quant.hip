@@ -22,6 +22,7 @@
 #include <vector>
 
 #include "device_common.hpp"
+#include "hadamard.h"
 #include "numfmt.h"
 #include "petit_internal.h"
 
@@ -92,8 +93,9 @@ template <bool BF16, int ILP> __device__ __forceinline__ void add_residual(u32x4
 
 // Steps 2 - 5 of the contract on a row of h held as thread t's columns t + 256 j, and every store of y16 / qa: the tail of rmsnorm_quant_kernel and
 // of moe_combine_rmsnorm_kernel, which differ only in how they come by h.  wave_sum: 4 floats of LDS; y_row: the MXFP6 row (256 ILP vectors).
-// ACT == 0 writes no quantised bytes and needs no whole k-tiles: any K / 8.
-template <bool BF16, int ACT, int ILP>
+// ACT == 0 writes no quantised bytes and needs no whole k-tiles: any K / 8.  HAD = 32 / 128 (ACT 8 / 4 only): the quantiser runs on the rotated
+// f32(y16) ("petit-had/1", qact_hadamard.inc); y16 itself leaves unrotated.
+template <bool BF16, int ACT, int ILP, int HAD = 0>
 __device__ __forceinline__ void norm_quant_tail(const RmsQuantArgs &p, const u32x4 (&h)[ILP], const u32x4 (&wv)[ILP], float *wave_sum, u32x4 *y_row) {
     const unsigned t = threadIdx.x, row = blockIdx.x, cols = p.k / 8, m = p.m;
     const size_t row_v = (size_t)row * cols;
@@ -145,6 +147,7 @@ __device__ __forceinline__ void norm_quant_tail(const RmsQuantArgs &p, const u32
                     const unsigned yw = yv[d];
                     unpack2<BF16>(yw, v[2 * d], v[2 * d + 1]);
                 }
+#include "qact_hadamard.inc"
 #include "qact_column.inc"
             }
         }
@@ -173,7 +176,7 @@ __device__ __forceinline__ void norm_quant_tail(const RmsQuantArgs &p, const u32
 // grid = (M): one workgroup per row.  ILP = columns per thread: K <= 2048 ILP.  Lanes whose column lies past K / 8 hold zeros and add +0 to the sum;
 // K / 8 is a multiple of 32, so the 16 lanes of a k-tile (and the 4 of a block) are masked together and every shuffle of the tail stays among live
 // lanes.
-template <bool BF16, int ACT, int ILP> __global__ __launch_bounds__(256) void rmsnorm_quant_kernel(const RmsQuantArgs p) {
+template <bool BF16, int ACT, int ILP, int HAD = 0> __global__ __launch_bounds__(256) void rmsnorm_quant_kernel(const RmsQuantArgs p) {
 #if defined(__HIP_DEVICE_COMPILE__)
     __shared__ float wave_sum[4];
     __shared__ u32x4 y_row[ACT == 6 ? 256 * ILP : 1]; // MXFP6 only: the 16-bit y row
@@ -212,7 +215,7 @@ template <bool BF16, int ACT, int ILP> __global__ __launch_bounds__(256) void rm
             }
         }
     }
-    norm_quant_tail<BF16, ACT, ILP>(p, h, wv, wave_sum, y_row);
+    norm_quant_tail<BF16, ACT, ILP, HAD>(p, h, wv, wave_sum, y_row);
 #endif
 }
 
@@ -402,11 +405,15 @@ int rmsq_check(const void *qa, const void *y16, const void *res_out, const void 
     return kOk;
 }
 
-template <bool BF16, int ACT> auto rmsq_kernel_for(unsigned k) {
-    return k <= 2048   ? rmsnorm_quant_kernel<BF16, ACT, 1>
-           : k <= 4096 ? rmsnorm_quant_kernel<BF16, ACT, 2>
-           : k <= 8192 ? rmsnorm_quant_kernel<BF16, ACT, 4>
-                       : rmsnorm_quant_kernel<BF16, ACT, 8>;
+template <bool BF16, int ACT, int HAD = 0> auto rmsq_kernel_for(unsigned k) {
+    return k <= 2048   ? rmsnorm_quant_kernel<BF16, ACT, 1, HAD>
+           : k <= 4096 ? rmsnorm_quant_kernel<BF16, ACT, 2, HAD>
+           : k <= 8192 ? rmsnorm_quant_kernel<BF16, ACT, 4, HAD>
+                       : rmsnorm_quant_kernel<BF16, ACT, 8, HAD>;
+}
+// the rotating forms: MXFP8 / MXFP4 only
+template <bool BF16, int HAD> auto rmsq_rot_kernel_for(int format, unsigned k) {
+    return format == 8 ? rmsq_kernel_for<BF16, 8, HAD>(k) : rmsq_kernel_for<BF16, 4, HAD>(k);
 }
 template <bool BF16> auto rmsq_kernel_for(int format, unsigned k) {
     return format == 8 ? rmsq_kernel_for<BF16, 8>(k) : format == 6 ? rmsq_kernel_for<BF16, 6>(k) : rmsq_kernel_for<BF16, 4>(k);
@@ -415,16 +422,15 @@ template <bool BF16> auto rmsq_kernel_for(int format, unsigned k) {
 // (the host twin's element converts -- round to nearest even, the sign kept on a zero too, as the hardware converts do -- are e4m3_rne,
 // e2m1_rne and e2m3_rne of numfmt.h, the last two on a quotient v / scale that is exact in f64)
 
-// one row of the quantiser on the 16-bit y, written where the kernels write it
-template <bool BF16, int ACT> void quantize_row_host(unsigned char *ws, const uint16_t *y, unsigned m, unsigned k, unsigned row) {
+// one row of the quantiser on f32 values z (the 16-bit y widened, or its rotation), written where the kernels write it
+template <int ACT> void quantize_row_f32_host(unsigned char *ws, const float *z, unsigned m, unsigned k, unsigned row) {
     unsigned char *const qs = ws + qact_elem_bytes(m, k, ACT);
     unsigned char *const qa_hi = ws + qact_hi_offset(m, k); // (MXFP6)
     for (unsigned blk = 0; blk < k / 32; ++blk) {
-        float v[32], amax = 0.f;
-        for (int i = 0; i < 32; ++i) {
-            v[i] = h16_f32<BF16>(y[32 * blk + i]);
+        const float *const v = z + 32 * blk;
+        float amax = 0.f;
+        for (int i = 0; i < 32; ++i)
             amax = std::fmax(amax, std::fabs(v[i])); // (a NaN does not count, as fmaxf on the device)
-        }
         const unsigned sbyte = act_scale_byte<ACT>(amax);
         const unsigned kt = blk / 4, b = blk % 4;
         const size_t tile_row = qact_tile_row(m, kt, row);
@@ -456,6 +462,15 @@ template <bool BF16, int ACT> void quantize_row_host(unsigned char *ws, const ui
         }
     }
 }
+// one row of the quantiser on the 16-bit y; had = 32 / 128: on the rotation of f32(y) ("petit-had/1": no 16-bit rounding in between)
+template <bool BF16, int ACT> void quantize_row_host(unsigned char *ws, const uint16_t *y, unsigned m, unsigned k, unsigned row, unsigned had = 0) {
+    std::vector<float> z(k);
+    for (unsigned i = 0; i < k; ++i)
+        z[i] = h16_f32<BF16>(y[i]);
+    if (had)
+        hadamard_row_host(z.data(), k, had);
+    quantize_row_f32_host<ACT>(ws, z.data(), m, k, row);
+}
 
 // steps 2 and 3 on one row of h -- the kernel's reduction, walked literally: 256 thread sums, six butterflies inside each wave of 64, the four
 // waves in ascending order
@@ -484,7 +499,7 @@ template <bool BF16> void add_row_host(uint16_t *h, const uint16_t *x, const uin
         h[i] = r ? (uint16_t)f32_h16<BF16>(add_rn(h16_f32<BF16>(x[i]), h16_f32<BF16>(r[i]))) : x[i];
 }
 
-template <bool BF16, int ACT> void rmsq_host(const RmsQuantArgs &p) {
+template <bool BF16, int ACT> void rmsq_host(const RmsQuantArgs &p, unsigned had = 0) {
     const unsigned k = p.k;
     std::vector<uint16_t> h(k), y(k);
     const uint16_t *const w = (const uint16_t *)p.w;
@@ -499,7 +514,7 @@ template <bool BF16, int ACT> void rmsq_host(const RmsQuantArgs &p) {
             y[i] = (uint16_t)f32_h16<BF16>(normed(h16_f32<BF16>(h[i]), inv, h16_f32<BF16>(w[i]), p.woff));
         if (p.y16)
             memcpy((uint16_t *)p.y16 + (size_t)row * k, y.data(), 2 * (size_t)k);
-        quantize_row_host<BF16, ACT>(p.qa, y.data(), p.m, k, row);
+        quantize_row_host<BF16, ACT>(p.qa, y.data(), p.m, k, row, had);
     }
 }
 
@@ -533,6 +548,60 @@ int rmsnorm_quantize_host(void *qa, void *y16, void *res_out, const void *x, con
         bf16 ? rmsq_host<true, 6>(p) : rmsq_host<false, 6>(p);
     else
         bf16 ? rmsq_host<true, 4>(p) : rmsq_host<false, 4>(p);
+    return kOk;
+}
+
+// The rotating forms (include/petit_amd.h "Block-Hadamard rotation"): block 0 is the entry above; what it refuses is refused here, then MXFP6.
+// *run = false with kOk: nothing to do, or (block == 0) the caller delegates
+namespace {
+int rmsq_rot_check(const void *qa, const void *y16, const void *res_out, const void *x, const void *res, const void *w, float eps, float woff,
+                   unsigned m, unsigned k, int a_type, int format, unsigned block, bool *run) {
+    *run = false;
+    if (!hadamard_block_ok(block))
+        return kErrBadArgument;
+    if (block == 0)
+        return kOk;
+    if (const int rc = rmsq_check(qa, y16, res_out, x, res, w, eps, woff, m, k, a_type, format, run); rc != kOk || !*run)
+        return rc;
+    if (format == 6) {
+        *run = false;
+        return kErrKernelShape; // (its converts read 16-bit patterns: no f32 form)
+    }
+    return kOk;
+}
+} // namespace
+
+int rmsnorm_quantize_rot(void *qa, void *y16, void *res_out, const void *x, const void *res, const void *w, float eps, float woff, unsigned m,
+                         unsigned k, int a_type, int format, unsigned block, hipStream_t stream) {
+    bool run;
+    if (const int rc = rmsq_rot_check(qa, y16, res_out, x, res, w, eps, woff, m, k, a_type, format, block, &run); rc != kOk)
+        return rc;
+    if (block == 0)
+        return rmsnorm_quantize(qa, y16, res_out, x, res, w, eps, woff, m, k, a_type, format, stream);
+    if (!run)
+        return kOk;
+    const bool bf16 = a_type == kDataTypeBf16;
+    const auto kern = block == 32 ? (bf16 ? rmsq_rot_kernel_for<true, 32>(format, k) : rmsq_rot_kernel_for<false, 32>(format, k))
+                                  : (bf16 ? rmsq_rot_kernel_for<true, 128>(format, k) : rmsq_rot_kernel_for<false, 128>(format, k));
+    hipLaunchKernelGGL(kern, dim3(m), dim3(256), 0, stream, rmsq_args(qa, y16, res_out, x, res, w, eps, woff, m, k));
+    return hipGetLastError() == hipSuccess ? kOk : kErrLaunch;
+}
+
+int rmsnorm_quantize_rot_host(void *qa, void *y16, void *res_out, const void *x, const void *res, const void *w, float eps, float woff, unsigned m,
+                              unsigned k, int a_type, int format, unsigned block) {
+    bool run;
+    if (const int rc = rmsq_rot_check(qa, y16, res_out, x, res, w, eps, woff, m, k, a_type, format, block, &run); rc != kOk)
+        return rc;
+    if (block == 0)
+        return rmsnorm_quantize_host(qa, y16, res_out, x, res, w, eps, woff, m, k, a_type, format);
+    if (!run)
+        return kOk;
+    const RmsQuantArgs p = rmsq_args(qa, y16, res_out, x, res, w, eps, woff, m, k);
+    const bool bf16 = a_type == kDataTypeBf16;
+    if (format == 8)
+        bf16 ? rmsq_host<true, 8>(p, block) : rmsq_host<false, 8>(p, block);
+    else
+        bf16 ? rmsq_host<true, 4>(p, block) : rmsq_host<false, 4>(p, block);
     return kOk;
 }
 
@@ -582,6 +651,32 @@ int quantize_activations_host(void *qa, const void *a, unsigned m, unsigned k, i
             bf16 ? quantize_row_host<true, 6>(ws, y, m, k, row) : quantize_row_host<false, 6>(ws, y, m, k, row);
         else
             bf16 ? quantize_row_host<true, 4>(ws, y, m, k, row) : quantize_row_host<false, 4>(ws, y, m, k, row);
+    }
+    return kOk;
+}
+
+// petit_quantize_activations_rot on HOST pointers: the same rows, each rotated in f32 before the quantiser
+int quantize_activations_rot_host(void *qa, const void *a, unsigned m, unsigned k, int a_type, int format, unsigned block) {
+    if (!hadamard_block_ok(block))
+        return kErrBadArgument;
+    if (block == 0)
+        return quantize_activations_host(qa, a, m, k, a_type, format);
+    if (m == 0 || k == 0)
+        return kOk;
+    if (!qa || !a || (((uintptr_t)qa | (uintptr_t)a) & 15) || (format != 8 && format != 6 && format != 4))
+        return kErrBadArgument;
+    if (k % 256 != 0)
+        return kErrProblemShape;
+    if ((a_type != kDataTypeBf16 && a_type != kDataTypeFp16) || format == 6)
+        return kErrKernelShape;
+    const bool bf16 = a_type == kDataTypeBf16;
+    for (unsigned row = 0; row < m; ++row) {
+        const uint16_t *const y = (const uint16_t *)a + (size_t)row * k;
+        unsigned char *const ws = (unsigned char *)qa;
+        if (format == 8)
+            bf16 ? quantize_row_host<true, 8>(ws, y, m, k, row, block) : quantize_row_host<false, 8>(ws, y, m, k, row, block);
+        else
+            bf16 ? quantize_row_host<true, 4>(ws, y, m, k, row, block) : quantize_row_host<false, 4>(ws, y, m, k, row, block);
     }
     return kOk;
 }

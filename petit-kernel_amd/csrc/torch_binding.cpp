@@ -203,6 +203,29 @@ std::tuple<at::Tensor, at::Tensor, at::Tensor> quantize_weights_meta(const at::T
     return {q.b, q.s, q.gs};
 }
 
+// block-Hadamard rotation to 16 bit (petit_hadamard_rows); the same checks and texts as petit_kernel/ops.py _hadamard_operands
+void hadamard_rotate_out(const at::Tensor &x, int64_t block, int64_t log2_scale, at::Tensor out) {
+    TORCH_CHECK(block == 32 || block == 128, "block must be 32 or 128");
+    TORCH_CHECK(log2_scale >= -126 && log2_scale <= 126, "log2_scale must be an integer in -126 .. 126");
+    TORCH_CHECK(x.is_cuda() && x.is_contiguous() && x.dim() >= 1 && (x.scalar_type() == at::kBFloat16 || x.scalar_type() == at::kHalf),
+                "x must be a contiguous bfloat16 / float16 GPU tensor");
+    const int64_t k = x.size(-1);
+    TORCH_CHECK(k % 256 == 0, "Incompatible problem shape (k=", k, "): the rotated dimension must be a multiple of 256");
+    TORCH_CHECK(out.device() == x.device() && out.scalar_type() == x.scalar_type() && out.sizes() == x.sizes() && out.is_contiguous(),
+                "out must be a contiguous tensor of x's shape and dtype on x's device");
+    const c10::hip::HIPGuardMasqueradingAsCUDA guard(x.device());
+    const int rc = petit_hadamard_rows(out.data_ptr(), x.data_ptr(), (unsigned)(k ? x.numel() / k : 0), (unsigned)k, a_type_of(x.scalar_type()),
+                                       (unsigned)block, (int)log2_scale, stream_of(x));
+    TORCH_CHECK(rc == PETIT_OK, "hadamard_rotate: ", petit_error_string(rc));
+}
+at::Tensor hadamard_rotate(const at::Tensor &x, int64_t block, int64_t log2_scale) {
+    at::Tensor out = at::empty_like(x);
+    hadamard_rotate_out(x, block, log2_scale, out);
+    return out;
+}
+at::Tensor hadamard_rotate_meta(const at::Tensor &x, int64_t block, int64_t log2_scale) { return at::empty_like(x); }
+void hadamard_rotate_out_meta(const at::Tensor &x, int64_t block, int64_t log2_scale, at::Tensor out) {}
+
 at::Tensor mul_a16(bool mx, const at::Tensor &A, const at::Tensor &B, const at::Tensor &s, const at::Tensor &global_scale, int64_t size_m,
                    int64_t size_n, int64_t size_k, int64_t solution_id, const std::optional<at::Tensor> &bias, int64_t activation) {
     // (check order as in the reference's MulNvFp4A16 / MulMxFp4A16, fp4.cc:163-260: the scale / weight tensor contracts first)
@@ -1067,6 +1090,8 @@ TORCH_LIBRARY(petit_kernel, m) {
     m.def("process_nvfp4_scales(Tensor scales, int size_n, int size_k) -> Tensor");
     m.def("process_mxfp4_scales(Tensor scales, int size_n, int size_k) -> Tensor");
     m.def("quantize_weights(Tensor w, int b_type, Tensor? global_scale=None) -> (Tensor, Tensor, Tensor)");
+    m.def("hadamard_rotate(Tensor x, int block, int log2_scale=0) -> Tensor");
+    m.def("hadamard_rotate_out(Tensor x, int block, int log2_scale, Tensor(a!) out) -> ()");
     m.def("mul_nvfp4_a16(Tensor A, Tensor B, Tensor s, Tensor global_scale, int size_m, int size_n, int size_k, int solution_id, "
           "Tensor? bias=None, int activation=0) -> Tensor");
     m.def("mul_mxfp4_a16(Tensor A, Tensor B, Tensor s, Tensor global_scale, int size_m, int size_n, int size_k, int solution_id, "
@@ -1139,6 +1164,8 @@ TORCH_LIBRARY(petit_kernel, m) {
     m.impl("process_nvfp4_scales", &process_nvfp4_scales);      \
     m.impl("process_mxfp4_scales", &process_mxfp4_scales);      \
     m.impl("quantize_weights", &quantize_weights);              \
+    m.impl("hadamard_rotate", &hadamard_rotate);                \
+    m.impl("hadamard_rotate_out", &hadamard_rotate_out);        \
     m.impl("mul_nvfp4_a16", &mul_nvfp4_a16);                    \
     m.impl("mul_mxfp4_a16", &mul_mxfp4_a16);                    \
     m.impl("mul_mxfp4_a16_f16range", &mul_mxfp4_a16);          \
@@ -1178,6 +1205,8 @@ TORCH_LIBRARY_IMPL(petit_kernel, Meta, m) {
     m.impl("process_nvfp4_scales", &process_nvfp4_scales_meta);
     m.impl("process_mxfp4_scales", &process_mxfp4_scales_meta);
     m.impl("quantize_weights", &quantize_weights_meta);
+    m.impl("hadamard_rotate", &hadamard_rotate_meta);
+    m.impl("hadamard_rotate_out", &hadamard_rotate_out_meta);
     m.impl("mul_nvfp4_a16", &mul_a16_meta);
     m.impl("mul_mxfp4_a16", &mul_a16_meta);
     m.impl("mul_mxfp4_a16_f16range", &mul_a16_meta);

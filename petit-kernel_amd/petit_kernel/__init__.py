@@ -61,16 +61,23 @@ def process_mxfp4_scales(scales: torch.Tensor, size_n: int, size_k: int) -> torc
     return _impl.process_mxfp4_scales(scales, size_n, size_k)
 
 
-def quantize_nvfp4(w: torch.Tensor, global_scale: torch.Tensor = None):
+def hadamard_rotate(x: torch.Tensor, block: int, log2_scale: int = 0, out: torch.Tensor = None) -> torch.Tensor:
+    # every row of x [..., k] times the unnormalised Hadamard block H_block (32 / 128) along k, times 2^log2_scale, rounded once to x's type
+    # (include/petit_amd.h "Block-Hadamard rotation"); out may be x.  Host twin: offline.hadamard_rotate_cpu
+    return _impl.hadamard_rotate(x, block, log2_scale, out)
+
+
+def quantize_nvfp4(w: torch.Tensor, global_scale: torch.Tensor = None, hadamard: int = 0):
     # 16-bit weights [N, K] or [E, N, K] -> (b, s, global_scale) on the device (include/petit_amd.h "Weight quantiser"): the packed tensors
     # repack_nvfp4 / process_nvfp4_scales return for the stacked [E * N, K] tensor and float32 [E] global scales (amax / 2688 per expert, or the
     # caller's), for mul_nvfp4_a16, the MoE launches, fp4_moe* and nvfp4_native_image(s).  Host twin: offline.quantize_nvfp4_cpu
-    return _impl.quantize_nvfp4(w, global_scale)
+    # hadamard = 32 / 128: exactly quantize_nvfp4(hadamard_rotate(w, B, -log2 B)) -- the weights for activations quantised with the same hadamard
+    return _impl.quantize_nvfp4(w, global_scale, hadamard)
 
 
-def quantize_mxfp4(w: torch.Tensor):
+def quantize_mxfp4(w: torch.Tensor, hadamard: int = 0):
     # the same for MXFP4 (one e8m0 scale per 32 k, global_scale = 1); num_experts * N must be a multiple of 32, as process_mxfp4_scales asks
-    return _impl.quantize_mxfp4(w)
+    return _impl.quantize_mxfp4(w, hadamard)
 
 
 def mxfp4_scales_in_fp16_range(raw_scales: torch.Tensor) -> bool:
@@ -389,9 +396,10 @@ def nvfp4_native_transient_workspace_bytes(size_m: int, size_n: int, size_k: int
     return ops.nvfp4_native_transient_workspace_bytes(size_m, size_n, size_k, solution_id, dtype, activation, a_format, out_quantized)
 
 
-def quantize_activation_rows(a: torch.Tensor, fmt: str = "mxfp8", row_index: torch.Tensor = None, rows: int = None) -> QuantizedActivations:
+def quantize_activation_rows(a: torch.Tensor, fmt: str = "mxfp8", row_index: torch.Tensor = None, rows: int = None,
+                             hadamard: int = 0) -> QuantizedActivations:
     # quantize_activations of the rows row_index names (None: all rows); an index outside the matrix gives a zero row
-    return ops.quantize_activation_rows(a, fmt, row_index, rows)
+    return ops.quantize_activation_rows(a, fmt, row_index, rows, hadamard)
 
 
 def native_moe_resolve_solution(hints: PetitSolutionHints, num_experts: int, size_m: int, size_n: int, size_k: int,
@@ -416,6 +424,7 @@ __all__ = [
     "process_mxfp4_scales",
     "quantize_nvfp4",
     "quantize_mxfp4",
+    "hadamard_rotate",
     "mul_nvfp4_a16",
     "mul_mxfp4_a16",
     "mul_nvfp4_a16_invariant",

@@ -204,6 +204,14 @@ _SIGNATURES = {
     "petit_moe_combine_rmsnorm_host": (C.c_int, [C.c_void_p] * 6 + [C.c_int, C.c_void_p, C.c_void_p, C.c_float, C.c_float] + [C.c_uint] * 4 +
                                        [C.c_int, C.c_int]),
     "petit_quantize_activations_rows": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p] + [C.c_uint] * 3 + [C.c_int, C.c_int, C.c_void_p]),
+    # the block-Hadamard rotation ("petit-had/1") and the rotating forms of the quantisers: `block` follows `format`
+    "petit_hadamard_rows": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint, C.c_uint, C.c_int, C.c_uint, C.c_int, C.c_void_p]),
+    "petit_hadamard_rows_host": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint, C.c_uint, C.c_int, C.c_uint, C.c_int]),
+    "petit_quantize_activations_rot": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint, C.c_uint, C.c_int, C.c_int, C.c_uint, C.c_void_p]),
+    "petit_quantize_activations_rot_host": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint, C.c_uint, C.c_int, C.c_int, C.c_uint]),
+    "petit_quantize_activations_rows_rot": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p] + [C.c_uint] * 3 + [C.c_int, C.c_int, C.c_uint, C.c_void_p]),
+    "petit_rmsnorm_quantize_rot": (C.c_int, [C.c_void_p] * 6 + [C.c_float, C.c_float, C.c_uint, C.c_uint, C.c_int, C.c_int, C.c_uint, C.c_void_p]),
+    "petit_rmsnorm_quantize_rot_host": (C.c_int, [C.c_void_p] * 6 + [C.c_float, C.c_float, C.c_uint, C.c_uint, C.c_int, C.c_int, C.c_uint]),
     "petit_gemm_native_moe_workspace_bytes": (C.c_uint64, [C.POINTER(SolutionHints)] + [C.c_uint] * 4 + [C.c_uint64, C.POINTER(Epilogue),
                                                                                                         C.POINTER(NativeArgs)]),
     "petit_gemm_native_moe_resolve_solution": (C.c_uint64, [C.POINTER(SolutionHints)] + [C.c_uint] * 4 + [C.c_uint64, C.POINTER(Epilogue),

@@ -14,6 +14,7 @@ from pathlib import Path
 import torch
 
 from . import _lib  # loads libpetit_amd.so first (the binding links against it)
+from .ops import _rotated_weights
 from .ops import QuantizedActivations, _a_type, _activation as _act, _activation_operand, _quantized_format
 from .ops import _check_invariant, _check_route_hidden, _check_router, _combine_norm_operands, _combine_norm_returns
 from .ops import invariant_geometry, invariant_slabs, invariant_workspace_bytes  # (queries: plain C calls, no op behind them)
@@ -79,12 +80,19 @@ def process_mxfp4_scales(scales, size_n, size_k):
     return torch.ops.petit_kernel.process_mxfp4_scales(scales, size_n, size_k)
 
 
-def quantize_nvfp4(w, global_scale=None):
-    return torch.ops.petit_kernel.quantize_weights(w, _lib.CXX_DTYPE_FP4_E2M1, global_scale)
+def hadamard_rotate(x, block, log2_scale=0, out=None):
+    if out is None:
+        return torch.ops.petit_kernel.hadamard_rotate(x, block, log2_scale)
+    torch.ops.petit_kernel.hadamard_rotate_out(x, block, log2_scale, out)
+    return out
 
 
-def quantize_mxfp4(w):
-    return torch.ops.petit_kernel.quantize_weights(w, _lib.CXX_DTYPE_MXFP4_E2M1, None)
+def quantize_nvfp4(w, global_scale=None, hadamard=0):
+    return torch.ops.petit_kernel.quantize_weights(_rotated_weights(w, hadamard, hadamard_rotate), _lib.CXX_DTYPE_FP4_E2M1, global_scale)
+
+
+def quantize_mxfp4(w, hadamard=0):
+    return torch.ops.petit_kernel.quantize_weights(_rotated_weights(w, hadamard, hadamard_rotate), _lib.CXX_DTYPE_MXFP4_E2M1, None)
 
 
 def mul_nvfp4_a16(A, B, s, global_scale, size_m, size_n, size_k, solution_id, bias=None, activation=None):

@@ -14,6 +14,7 @@ import torch
 from . import _lib
 from .ops import _B_TYPES, _LAYOUT_M, _LAYOUT_N, _PACK, _QFORMATS, _a_type, _check, _opt_ptr, _ptr, _quantize_operands, _quantize_outputs, _raise_on
 from .ops import _raise_quantize, _rmsnorm_operands, _rmsnorm_outputs, _rmsnorm_result
+from .ops import QuantizedActivations, _HADAMARD_FP6, _hadamard_block, _hadamard_operands, _rotated_weights
 from .ops import _combine_norm_operands, _combine_norm_outputs, _combine_norm_result, _combine_norm_returns
 
 
@@ -77,26 +78,50 @@ def _quantize_weights_cpu(kind: str, w: torch.Tensor, global_scale=None):
     return b, s, gs
 
 
-def quantize_nvfp4_cpu(w: torch.Tensor, global_scale: torch.Tensor = None):
+def hadamard_rotate_cpu(x: torch.Tensor, block: int, log2_scale: int = 0, out: torch.Tensor = None) -> torch.Tensor:
+    """CPU twin of petit_kernel.hadamard_rotate (petit_hadamard_rows_host): the same arguments on CPU tensors, the same bits."""
+    rows, k, out = _hadamard_operands(x, block, log2_scale, out, on_gpu=False)
+    _raise_on(_lib.lib.petit_hadamard_rows_host(_ptr(out), _ptr(x), rows, k, _a_type(x.dtype), int(block), int(log2_scale)), "hadamard_rotate_cpu")
+    return out
+
+
+def quantize_nvfp4_cpu(w: torch.Tensor, global_scale: torch.Tensor = None, hadamard: int = 0):
     """CPU twin of petit_kernel.quantize_nvfp4: bf16 / fp16 [N, K] or [E, N, K] -> (b, s, global_scale), bit-identical to the device's."""
-    return _quantize_weights_cpu("nv", w, global_scale)
+    return _quantize_weights_cpu("nv", _rotated_weights(w, hadamard, hadamard_rotate_cpu), global_scale)
 
 
-def quantize_mxfp4_cpu(w: torch.Tensor):
+def quantize_mxfp4_cpu(w: torch.Tensor, hadamard: int = 0):
     """CPU twin of petit_kernel.quantize_mxfp4."""
-    return _quantize_weights_cpu("mx", w)
+    return _quantize_weights_cpu("mx", _rotated_weights(w, hadamard, hadamard_rotate_cpu))
+
+
+# --- the activation quantiser, on the CPU (petit_quantize_activations_host / _rot_host) -------------------------------------------------------------
+
+def quantize_activations_cpu(a: torch.Tensor, fmt: str = "mxfp4", hadamard: int = 0) -> QuantizedActivations:
+    """CPU twin of petit_kernel.quantize_activations: the same arguments on a CPU tensor, the same bytes."""
+    _check(fmt in _QFORMATS, "fmt must be 'mxfp8', 'mxfp6' or 'mxfp4'")
+    _check(_hadamard_block(hadamard) == 0 or fmt != "mxfp6", _HADAMARD_FP6)
+    _check(not a.is_cuda and a.is_contiguous() and a.dim() == 2 and a.dtype in (torch.bfloat16, torch.float16),
+           "a must be a contiguous 2-D bfloat16 / float16 CPU tensor")
+    m, k = a.shape
+    qa = torch.empty(int(_lib.lib.petit_quantized_activation_bytes(m, k, _QFORMATS[fmt])), dtype=torch.uint8)
+    rc = _lib.lib.petit_quantize_activations_rot_host(_ptr(qa), _ptr(a), m, k, _a_type(a.dtype), _QFORMATS[fmt], hadamard)
+    if rc == _lib.PETIT_ERROR_PROBLEM_SHAPE:
+        raise RuntimeError(f"Incompatible problem shape (m={m}, k={k})")
+    _raise_on(rc, "quantize_activations_cpu")
+    return QuantizedActivations(qa, m, k, fmt, a.dtype, hadamard)
 
 
 # --- RMSNorm into quantised activations, on the CPU (include/petit_amd.h "RMSNorm into quantised activations") ----------------------------------
 
 def rmsnorm_quantize_cpu(x: torch.Tensor, weight: torch.Tensor, eps: float = 1e-6, fmt: str = "mxfp8", *, residual: torch.Tensor = None,
-                         weight_offset: float = 0.0, return_normed: bool = False, inplace_residual: bool = False):
+                         weight_offset: float = 0.0, return_normed: bool = False, inplace_residual: bool = False, hadamard: int = 0):
     """CPU twin of petit_kernel.rmsnorm_quantize (the C ABI's host twin): the same arguments on CPU tensors, the same results bit for bit."""
-    m, k = _rmsnorm_operands(x, weight, eps, fmt, residual, weight_offset, on_gpu=False)
+    m, k = _rmsnorm_operands(x, weight, eps, fmt, residual, weight_offset, on_gpu=False, hadamard=hadamard)
     qa, res_out, y16 = _rmsnorm_outputs(x, fmt, residual, return_normed, inplace_residual)
-    rc = _lib.lib.petit_rmsnorm_quantize_host(_ptr(qa), _opt_ptr(y16), _opt_ptr(res_out), _ptr(x), _opt_ptr(residual), _ptr(weight), float(eps),
-                                              float(weight_offset), m, k, _a_type(x.dtype), _QFORMATS[fmt])
-    return _rmsnorm_result(rc, "rmsnorm_quantize_cpu", x, fmt, qa, res_out, y16)
+    rc = _lib.lib.petit_rmsnorm_quantize_rot_host(_ptr(qa), _opt_ptr(y16), _opt_ptr(res_out), _ptr(x), _opt_ptr(residual), _ptr(weight),
+                                                  float(eps), float(weight_offset), m, k, _a_type(x.dtype), _QFORMATS[fmt], hadamard)
+    return _rmsnorm_result(rc, "rmsnorm_quantize_cpu", x, fmt, qa, res_out, y16, hadamard)
 
 
 def moe_combine_rmsnorm_cpu(slot_out: torch.Tensor, topk_weights: torch.Tensor, topk_ids: torch.Tensor, num_experts: int, weight: torch.Tensor,

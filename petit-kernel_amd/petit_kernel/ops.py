@@ -215,16 +215,66 @@ def _quantize_weights(kind: str, w: torch.Tensor, global_scale=None):
     return b, s, gs
 
 
-def quantize_nvfp4(w: torch.Tensor, global_scale: torch.Tensor = None):
+# --- block-Hadamard rotation (include/petit_amd.h "Block-Hadamard rotation"; no counterpart in the reference) ---------------------------
+
+_HADAMARD_RULE = "hadamard must be 0 (no rotation), 32 or 128"
+
+
+def _hadamard_block(hadamard, allow_zero: bool = True) -> int:
+    """The rotation block of a `hadamard=` / `block` argument: 0 (where allowed), 32 or 128."""
+    _check(isinstance(hadamard, int) and not isinstance(hadamard, bool) and hadamard in ((0, 32, 128) if allow_zero else (32, 128)),
+           _HADAMARD_RULE if allow_zero else "block must be 32 or 128")
+    return int(hadamard)
+
+
+def _hadamard_operands(x: torch.Tensor, block, log2_scale, out, on_gpu: bool):
+    """The argument checks of hadamard_rotate and of its CPU twin, stated once -> (rows, k, out)."""
+    where = "GPU" if on_gpu else "CPU"
+    _hadamard_block(block, allow_zero=False)
+    _check(isinstance(log2_scale, int) and abs(log2_scale) <= 126, "log2_scale must be an integer in -126 .. 126")
+    _check(x.is_cuda == on_gpu and x.is_contiguous() and x.dim() >= 1 and x.dtype in (torch.bfloat16, torch.float16),
+           f"x must be a contiguous bfloat16 / float16 {where} tensor")
+    k = x.shape[-1]
+    _check(k % 256 == 0, f"Incompatible problem shape (k={k}): the rotated dimension must be a multiple of 256")
+    if out is None:
+        out = torch.empty_like(x)
+    else:
+        _check(out.device == x.device and out.dtype == x.dtype and out.shape == x.shape and out.is_contiguous(),
+               "out must be a contiguous tensor of x's shape and dtype on x's device")
+    return (x.numel() // k if k else 0), k, out
+
+
+def hadamard_rotate(x: torch.Tensor, block: int, log2_scale: int = 0, out: torch.Tensor = None) -> torch.Tensor:
+    """Every row of x [..., k] times the unnormalised Sylvester Hadamard block H_block (32 or 128) along k, times 2^log2_scale, rounded once
+    to x's 16-bit type ("petit-had/1", petit_hadamard_rows).  Weights for rotated activations: hadamard_rotate(w, B, -log2(B)).  out may be x."""
+    rows, k, out = _hadamard_operands(x, block, log2_scale, out, on_gpu=True)
+    with torch.cuda.device(x.device):
+        rc = _lib.lib.petit_hadamard_rows(_ptr(out), _ptr(x), rows, k, _a_type(x.dtype), int(block), int(log2_scale), _stream(x))
+    _raise_on(rc, "hadamard_rotate")
+    return out
+
+
+def _rotated_weights(w: torch.Tensor, hadamard, rotate):
+    """w for quantize_*(w, hadamard=B): w itself, or rotate(w, B, -log2 B) on its [E * N, K] view (checked by the quantiser afterwards)."""
+    block = _hadamard_block(hadamard)
+    if block == 0:
+        return w
+    _check(w.dtype in (torch.bfloat16, torch.float16), "w must be bfloat16 or float16.")
+    _check(w.is_contiguous(), "w is not contiguous")
+    return rotate(w, block, -(block.bit_length() - 1))
+
+
+def quantize_nvfp4(w: torch.Tensor, global_scale: torch.Tensor = None, hadamard: int = 0):
     """16-bit weights [N, K] or [E, N, K] -> (b, s, global_scale): the packed NVFP4 tensors repack_nvfp4 / process_nvfp4_scales return for the
     stacked [E * N, K] tensor and float32 [E] global scales, straight into mul_nvfp4_a16 / mul_nvfp4_a16_moe* / fp4_moe* / nvfp4_native_image(s).
-    global_scale: None (amax / 2688 per expert) or the caller's float32 [E]."""
-    return _quantize_weights("nv", w, global_scale)
+    global_scale: None (amax / 2688 per expert) or the caller's float32 [E].  hadamard = 32 / 128: exactly
+    quantize_nvfp4(hadamard_rotate(w, B, -log2 B)), the weights for activations quantised with the same hadamard."""
+    return _quantize_weights("nv", _rotated_weights(w, hadamard, hadamard_rotate), global_scale)
 
 
-def quantize_mxfp4(w: torch.Tensor):
+def quantize_mxfp4(w: torch.Tensor, hadamard: int = 0):
     """The same for MXFP4 (OCP MX: one e8m0 scale per 32 k, global_scale = 1): (b, s, global_scale) as repack_mxfp4 / process_mxfp4_scales shape them."""
-    return _quantize_weights("mx", w)
+    return _quantize_weights("mx", _rotated_weights(w, hadamard, hadamard_rotate))
 
 
 _ACTIVATIONS = {None: 0, "none": 0, "silu_mul": 1, "swiglu_oai": 2}   # PETIT_ACTIVATION_* (include/petit_amd.h)
@@ -659,33 +709,44 @@ class QuantizedActivations:
     bytes, k-tile major).  Produced by quantize_activations() or by mul_mxfp4_a16(..., activation="silu_mul",
     out_quantized=...); consumed by mul_mxfp4_a16(a=<this>, ...)."""
 
-    def __init__(self, data: torch.Tensor, m: int, k: int, fmt: str, dtype: torch.dtype):
+    def __init__(self, data: torch.Tensor, m: int, k: int, fmt: str, dtype: torch.dtype, hadamard: int = 0):
         self.data, self.m, self.k, self.fmt, self.dtype = data, m, k, fmt, dtype
+        self.hadamard = hadamard   # the rotation block the rows were rotated with (bookkeeping: a GEMM cannot know how its weights were made)
 
     def __repr__(self) -> str:
-        return f"QuantizedActivations(m={self.m}, k={self.k}, fmt={self.fmt!r}, dtype={self.dtype}, {self.data.numel()} bytes)"
+        return (f"QuantizedActivations(m={self.m}, k={self.k}, fmt={self.fmt!r}, dtype={self.dtype}, hadamard={self.hadamard}, "
+                f"{self.data.numel()} bytes)")
 
 
-def quantize_activations(A: torch.Tensor, fmt: str = "mxfp4") -> QuantizedActivations:
-    """16-bit activations [m, k] -> QuantizedActivations (one launch; share the result among GEMMs with the same input)."""
+_HADAMARD_FP6 = "hadamard needs fmt 'mxfp8' or 'mxfp4': the MXFP6 quantiser has no rotating form"
+
+
+def quantize_activations(A: torch.Tensor, fmt: str = "mxfp4", hadamard: int = 0) -> QuantizedActivations:
+    """16-bit activations [m, k] -> QuantizedActivations (one launch; share the result among GEMMs with the same input).  hadamard = 32 / 128:
+    the rows are rotated by that Hadamard block in f32 inside the launch ("petit-had/1"), for weights made with the same hadamard."""
     _check(fmt in _QFORMATS, "fmt must be 'mxfp8', 'mxfp6' or 'mxfp4'")
+    _check(_hadamard_block(hadamard) == 0 or fmt != "mxfp6", _HADAMARD_FP6)
     _check(A.is_cuda and A.is_contiguous() and A.dim() == 2 and A.dtype in (torch.bfloat16, torch.float16),
            "A must be a contiguous 2-D bfloat16 / float16 GPU tensor")
     m, k = A.shape
     nbytes = int(_lib.lib.petit_quantized_activation_bytes(m, k, _QFORMATS[fmt]))
     qa = torch.empty(nbytes, dtype=torch.uint8, device=A.device)
     with torch.cuda.device(A.device):
-        rc = _lib.lib.petit_quantize_activations(_ptr(qa), _ptr(A), m, k, _a_type(A.dtype), _QFORMATS[fmt], _stream(A))
+        if hadamard:
+            rc = _lib.lib.petit_quantize_activations_rot(_ptr(qa), _ptr(A), m, k, _a_type(A.dtype), _QFORMATS[fmt], hadamard, _stream(A))
+        else:
+            rc = _lib.lib.petit_quantize_activations(_ptr(qa), _ptr(A), m, k, _a_type(A.dtype), _QFORMATS[fmt], _stream(A))
     if rc == _lib.PETIT_ERROR_PROBLEM_SHAPE:
         raise RuntimeError(f"Incompatible problem shape (m={m}, k={k})")
     _raise_on(rc, "quantize_activations")
-    return QuantizedActivations(qa, m, k, fmt, A.dtype)
+    return QuantizedActivations(qa, m, k, fmt, A.dtype, hadamard)
 
 
-def _rmsnorm_operands(x, weight, eps, fmt, residual, weight_offset, on_gpu: bool):
+def _rmsnorm_operands(x, weight, eps, fmt, residual, weight_offset, on_gpu: bool, hadamard: int = 0):
     """The argument checks of rmsnorm_quantize and of its CPU twin, stated once -> (m, k)."""
     where = "GPU" if on_gpu else "CPU"
     _check(fmt in _QFORMATS, "fmt must be 'mxfp8', 'mxfp6' or 'mxfp4'")
+    _check(_hadamard_block(hadamard) == 0 or fmt != "mxfp6", _HADAMARD_FP6)
     _check(x.is_cuda == on_gpu and x.is_contiguous() and x.dim() == 2 and x.dtype in (torch.bfloat16, torch.float16),
            f"x must be a contiguous 2-D bfloat16 / float16 {where} tensor")
     m, k = x.shape
@@ -707,31 +768,35 @@ def _rmsnorm_outputs(x, fmt, residual, return_normed, inplace_residual):
     return qa, res_out, y16
 
 
-def _rmsnorm_result(rc, name, x, fmt, qa, res_out, y16):
+def _rmsnorm_result(rc, name, x, fmt, qa, res_out, y16, hadamard: int = 0):
     m, k = x.shape
     if rc == _lib.PETIT_ERROR_PROBLEM_SHAPE:
         raise RuntimeError(f"Incompatible problem shape (m={m}, k={k})")
     if rc == _lib.PETIT_ERROR_KERNEL_SHAPE:
         raise RuntimeError(f"No kernel implementation for k={k} (the fused norm holds a row of at most 16384 elements).")
     _raise_on(rc, name)
-    q = QuantizedActivations(qa, m, k, fmt, x.dtype)
+    q = QuantizedActivations(qa, m, k, fmt, x.dtype, hadamard)
     if res_out is None and y16 is None:
         return q
     return (q,) + ((res_out,) if res_out is not None else ()) + ((y16,) if y16 is not None else ())
 
 
 def rmsnorm_quantize(x: torch.Tensor, weight: torch.Tensor, eps: float = 1e-6, fmt: str = "mxfp8", *, residual: torch.Tensor = None,
-                     weight_offset: float = 0.0, return_normed: bool = False, inplace_residual: bool = False):
+                     weight_offset: float = 0.0, return_normed: bool = False, inplace_residual: bool = False, hadamard: int = 0):
     """(Residual add +) RMSNorm + quantize_activations in ONE launch (include/petit_amd.h "RMSNorm into quantised activations"):
-    h = x (+ residual), y = RMSNorm(h) * (weight + weight_offset), result = quantize_activations(y, fmt) bit for bit.  Returns the
+    h = x (+ residual), y = RMSNorm(h) * (weight + weight_offset), result = quantize_activations(y, fmt, hadamard) bit for bit.  Returns the
     QuantizedActivations alone, or a tuple (q, residual_out[, y16]): the updated residual h when `residual` is given (a new tensor, or `residual`
-    itself written in place with inplace_residual=True), then the 16-bit y with return_normed=True."""
-    m, k = _rmsnorm_operands(x, weight, eps, fmt, residual, weight_offset, on_gpu=True)
+    itself written in place with inplace_residual=True), then the 16-bit y with return_normed=True (never rotated)."""
+    m, k = _rmsnorm_operands(x, weight, eps, fmt, residual, weight_offset, on_gpu=True, hadamard=hadamard)
     qa, res_out, y16 = _rmsnorm_outputs(x, fmt, residual, return_normed, inplace_residual)
+    args = (_ptr(qa), _opt_ptr(y16), _opt_ptr(res_out), _ptr(x), _opt_ptr(residual), _ptr(weight), float(eps), float(weight_offset), m, k,
+            _a_type(x.dtype), _QFORMATS[fmt])
     with torch.cuda.device(x.device):
-        rc = _lib.lib.petit_rmsnorm_quantize(_ptr(qa), _opt_ptr(y16), _opt_ptr(res_out), _ptr(x), _opt_ptr(residual), _ptr(weight), float(eps),
-                                             float(weight_offset), m, k, _a_type(x.dtype), _QFORMATS[fmt], _stream(x))
-    return _rmsnorm_result(rc, "rmsnorm_quantize", x, fmt, qa, res_out, y16)
+        if hadamard:
+            rc = _lib.lib.petit_rmsnorm_quantize_rot(*args, hadamard, _stream(x))
+        else:
+            rc = _lib.lib.petit_rmsnorm_quantize(*args, _stream(x))
+    return _rmsnorm_result(rc, "rmsnorm_quantize", x, fmt, qa, res_out, y16, hadamard)
 
 
 def _quantized_format(fmt, text: str) -> int:
@@ -1530,10 +1595,13 @@ def moe_resolve_solution(hints: PetitSolutionHints, num_experts: int, size_m: in
 
 # --- native-class MoE (include/petit_amd.h "Native-class MoE launch"; no counterpart in the reference) ------------------------------------
 
-def quantize_activation_rows(A: torch.Tensor, fmt: str = "mxfp8", row_index: torch.Tensor = None, rows: int = None) -> QuantizedActivations:
+def quantize_activation_rows(A: torch.Tensor, fmt: str = "mxfp8", row_index: torch.Tensor = None, rows: int = None,
+                             hadamard: int = 0) -> QuantizedActivations:
     """quantize_activations of gathered rows (petit_quantize_activations_rows): row r of the result is row row_index[r] of A [a_rows, k]
-    (None: row r; rows = row_index.numel(), or A's row count).  An index outside [0, a_rows) gives a zero row.  One launch, any row count."""
+    (None: row r; rows = row_index.numel(), or A's row count).  An index outside [0, a_rows) gives a zero row.  One launch, any row count.
+    hadamard: as quantize_activations."""
     _check(fmt in _QFORMATS, "fmt must be 'mxfp8', 'mxfp6' or 'mxfp4'")
+    _check(_hadamard_block(hadamard) == 0 or fmt != "mxfp6", _HADAMARD_FP6)
     _check(A.is_cuda and A.is_contiguous() and A.dim() == 2 and A.dtype in (torch.bfloat16, torch.float16),
            "A must be a contiguous 2-D bfloat16 / float16 GPU tensor")
     a_rows, k = A.shape
@@ -1547,12 +1615,16 @@ def quantize_activation_rows(A: torch.Tensor, fmt: str = "mxfp8", row_index: tor
     nbytes = int(_lib.lib.petit_quantized_activation_bytes(m, k, _QFORMATS[fmt]))
     qa = torch.empty(nbytes, dtype=torch.uint8, device=A.device)
     with torch.cuda.device(A.device):
-        rc = _lib.lib.petit_quantize_activations_rows(_ptr(qa), _ptr(A), _opt_ptr(row_index), a_rows, m, k, _a_type(A.dtype), _QFORMATS[fmt],
-                                                      _stream(A))
+        if hadamard:
+            rc = _lib.lib.petit_quantize_activations_rows_rot(_ptr(qa), _ptr(A), _opt_ptr(row_index), a_rows, m, k, _a_type(A.dtype),
+                                                              _QFORMATS[fmt], hadamard, _stream(A))
+        else:
+            rc = _lib.lib.petit_quantize_activations_rows(_ptr(qa), _ptr(A), _opt_ptr(row_index), a_rows, m, k, _a_type(A.dtype), _QFORMATS[fmt],
+                                                          _stream(A))
     if rc == _lib.PETIT_ERROR_PROBLEM_SHAPE:
         raise RuntimeError(f"Incompatible problem shape (m={m}, k={k}, a_rows={a_rows})")
     _raise_on(rc, "quantize_activation_rows")
-    return QuantizedActivations(qa, m, k, fmt, A.dtype)
+    return QuantizedActivations(qa, m, k, fmt, A.dtype, hadamard)
 
 
 def nvfp4_native_images(B: torch.Tensor, s: torch.Tensor, num_experts: int, size_n: int, size_k: int) -> torch.Tensor:
