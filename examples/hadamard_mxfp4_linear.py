@@ -50,6 +50,25 @@ class HadamardFp4Linear(torch.nn.Module):
         return y.reshape(*x.shape[:-1], self.size_n)
 
 
+class HadamardFp4GatedMlp(torch.nn.Module):
+    """down(silu(gate(x)) * up(x)) on MXFP4 weights and MXFP4 activations in TWO GEMM launches behind the quantiser of x: gate_up's epilogue
+    rotates and quantises what down reads (out_quantized="mxfp4", out_hadamard=B), and w2 is rotated with the same block at load time."""
+
+    def __init__(self, w13: torch.Tensor, w2: torch.Tensor, hadamard: int = 128):
+        super().__init__()
+        self.hadamard, (self.n13, self.hidden), self.inter = hadamard, w13.shape, w2.shape[1]
+        for name, w in (("13", w13), ("2", w2)):
+            for part, t in zip("bsg", petit_kernel.quantize_mxfp4(w, hadamard=hadamard)):
+                self.register_buffer(part + name, t)
+
+    def forward(self, x: torch.Tensor) -> torch.Tensor:
+        sid = petit_kernel.SOLUTION_AUTO_NATIVE_MXFP4
+        q = petit_kernel.quantize_activations(x, "mxfp4", hadamard=self.hadamard)
+        h = petit_kernel.mul_mxfp4_native(q, self.b13, self.s13, self.g13, q.m, self.n13, self.hidden, sid, activation="silu_mul",
+                                          out_quantized="mxfp4", out_hadamard=self.hadamard)
+        return petit_kernel.mul_mxfp4_native(h, self.b2, self.s2, self.g2, q.m, self.hidden, self.inter, sid)
+
+
 def main() -> None:
     dev = torch.device("cuda")
     g = torch.Generator().manual_seed(0)
@@ -67,6 +86,14 @@ def main() -> None:
             err = (layer(x).float() - ref).pow(2).mean().sqrt() / rms
             name = "MXFP4 weights" if kind == "mx" else "NVFP4 image "
             print(f"{name}, MXFP4 activations, {'no rotation' if not hadamard else f'B = {hadamard:3d}   '}: rms error {100 * float(err):5.1f} % of the bf16 layer's output rms")
+    inter = 2048
+    w13 = (torch.randn(2 * inter, k, generator=g) * 0.02).bfloat16().to(dev)
+    w2 = (torch.randn(k, inter, generator=g) * 0.02).bfloat16().to(dev)
+    y1 = x.float() @ w13.float().T
+    ref = (torch.nn.functional.silu(y1[:, :inter]) * y1[:, inter:]) @ w2.float().T
+    for hadamard in (0, 32, 128):
+        err = (HadamardFp4GatedMlp(w13, w2, hadamard)(x).float() - ref).pow(2).mean().sqrt() / ref.pow(2).mean().sqrt()
+        print(f"gated MLP, two GEMM launches, {'no rotation' if not hadamard else f'B = {hadamard:3d}   '}: rms error {100 * float(err):5.1f} % of the bf16 block's output rms")
 
 
 if __name__ == "__main__":

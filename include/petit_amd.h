@@ -370,6 +370,21 @@ int petit_get_mxfp4_default_class(void);
  *              16-bit [m][n/2] matrix: gate_up -> SiLU-mul -> down of a gated MLP in two launches.  Needs n % 512 == 0 and a
  *              kernel with 128 x 256 workgroup tiles (the sentinels pick one).  Quantised from the f32 result with the
  *              quantiser's own rule (E8M0 scale from the block maximum of 32 columns).
+ *   out_block  0 / 32 / 128, with out_format 8 / 4: the block-Hadamard rotation ("petit-had/1", below) INSIDE that epilogue.  v[m][j] is the f32
+ *              gated value the epilogue quantises (SiLU-mul or SwiGLU-OAI of the fma'd gate / up, bias and global scale exactly as without
+ *              it).  With out_block = B every block of B consecutive output columns j is replaced by z, the transform of that block: the
+ *              stages d = 1, 2, 4 .. B / 2 IN THIS ORDER, (z[i], z[i + d]) <- (z[i] + z[i + d], z[i] - z[i + d]) for (i & d) == 0, each ONE
+ *              f32 operation, nothing fused -- not with the product that makes v either.  z is then quantised by the quantiser's own rule,
+ *              unchanged: E8M0 from the maximum of each 32-column block, the same converts, the same "petit-qact/1" stores.  No 16-bit
+ *              rounding in between: the one rounding of the unrotated epilogue, kept.  The consumer is a `down` whose weights were rotated
+ *              with the same B (petit_hadamard_rows, log2_scale = -log2 B): a rotated gated MLP is two GEMM launches.  0 is the call
+ *              without the field (the struct's former `reserved`), bit for bit.  A block other than 0 / 32 / 128, or out_block without
+ *              out_format: PETIT_ERROR_BAD_ARGUMENT; out_format == 6 with a rotation: PETIT_ERROR_KERNEL_SHAPE, as in the quantisers, and so
+ *              is a rotation in the MXFP6 activation class (a_format 6, its sentinel, its kernel ids: those kernels carry no rotating
+ *              epilogue); all before any launch.  The workspace and resolve queries answer exactly as for out_block = 0 (no scratch, no other
+ *              pick; 0 for a call that would be refused).  Every entry that takes petit_native_args and runs this epilogue honours
+ *              it: petit_gemm_mxfp4_native, petit_gemm_nvfp4_native, its _transient form, petit_gemm_native_moe and its _transient form (the
+ *              rotation runs along columns: the row limit of a routed-expert launch is untouched).
  * solution_id: PETIT_SOLUTION_AUTO_NATIVE_MXFP8 / _MXFP6 / _MXFP4 (must match a_format when given) or an explicit native kernel id;
  * with a_format or out_format set only the 32x32x64 kernels qualify (PETIT_ERROR_KERNEL_SHAPE otherwise).  hints->a_type
  * names the 16-bit type of the matrix input / output and of the bias.  workspace: what petit_gemm_native_workspace_bytes()
@@ -380,7 +395,7 @@ typedef struct petit_native_args {
     uint32_t struct_bytes; /* sizeof(petit_native_args) */
     int32_t a_format;      /* 0, 8 (MXFP8), 6 (MXFP6 e2m3) or 4 (MXFP4) */
     int32_t out_format;    /* 0, 8, 6 or 4 */
-    int32_t reserved;      /* 0 */
+    int32_t out_block;     /* 0 (the old `reserved`, and its meaning: no rotation), 32 or 128: see "out_block" above */
 } petit_native_args;
 int petit_gemm_mxfp4_native(void *c, const void *a, const unsigned *b, const unsigned *scales, const float *global_scale, unsigned m,
                             unsigned n, unsigned k, const petit_solution_hints *hints, uint64_t solution_id, const petit_epilogue *epilogue,
@@ -1226,9 +1241,11 @@ int petit_quantize_activations_rows(void *qa, const void *a, const int32_t *a_ro
  * forms are the host twins (host pointers): bit-identical outputs, the same refusals.
  * In the fused norm steps 1 - 4 of "RMSNorm into quantised activations" are untouched: y is rounded to 16 bit and the rotation runs on
  * f32(y16), so qa is bit for bit petit_quantize_activations_rot on the y16 the same call can return; y16 and residual_out stay unrotated.
- * Out of scope: MXFP6 activations; the quantising gated epilogue (out_format of the gate_up kernels cannot rotate -- a rotated `down`
- * takes the 16-bit hand-over plus petit_quantize_activations_rot); petit_moe_combine_rmsnorm; random sign diagonals; every GEMM and MoE
- * kernel, which consume the bytes as they are.
+ * The other two producers of quantised activations rotate too: the quantising gated epilogue (petit_native_args.out_block, defined there)
+ * and petit_moe_combine_rmsnorm_rot, which is bit for bit petit_moe_combine followed by petit_rmsnorm_quantize_rot(.., residual, .., block)
+ * (format 8 / 4; format 0 -- no quantised bytes, nothing to rotate -- with a block is PETIT_ERROR_BAD_ARGUMENT; block 0 hands on to
+ * petit_moe_combine_rmsnorm).
+ * Out of scope: MXFP6 activations; random sign diagonals.  The GEMM and MoE kernels consume the bytes as they are.
  */
 int petit_hadamard_rows(void *out, const void *in, unsigned rows, unsigned k, int a_type, unsigned block, int log2_scale, void *stream);
 int petit_hadamard_rows_host(void *out, const void *in, unsigned rows, unsigned k, int a_type, unsigned block, int log2_scale);
@@ -1240,6 +1257,14 @@ int petit_rmsnorm_quantize_rot(void *qa, void *y16, void *residual_out, const vo
                                float weight_offset, unsigned m, unsigned k, int a_type, int format, unsigned block, void *stream);
 int petit_rmsnorm_quantize_rot_host(void *qa, void *y16, void *residual_out, const void *x, const void *residual, const void *weight, float eps,
                                     float weight_offset, unsigned m, unsigned k, int a_type, int format, unsigned block);
+int petit_moe_combine_rmsnorm_rot(void *qa, void *y16, void *residual_out, const void *slot_out, const float *topk_weights, const void *topk_ids,
+                                  int ids_are_int64, const void *residual, const void *weight, float eps, float weight_offset,
+                                  unsigned num_tokens, unsigned topk, unsigned k, unsigned num_experts, int a_type, int format, unsigned block,
+                                  void *stream);
+int petit_moe_combine_rmsnorm_rot_host(void *qa, void *y16, void *residual_out, const void *slot_out, const float *topk_weights,
+                                       const void *topk_ids, int ids_are_int64, const void *residual, const void *weight, float eps,
+                                       float weight_offset, unsigned num_tokens, unsigned topk, unsigned k, unsigned num_experts, int a_type,
+                                       int format, unsigned block);
 
 /*
  * Tune-and-persist (replaces the reference's `bench_matmul -algo tune`, tools/benchmarks/matmul/main.cc:269-325, which

@@ -82,7 +82,9 @@ uint64_t petit_gemm_workspace_bytes_ex(const petit_solution_hints *hints, unsign
 }
 
 static NativeIo native_io(const petit_native_args *na, const void *image = nullptr) {
-    return NativeIo{na ? (unsigned)na->a_format : 0u, na ? (unsigned)na->out_format : 0u, image};
+    NativeIo io{na ? (unsigned)na->a_format : 0u, na ? (unsigned)na->out_format : 0u, image};
+    io.out_block = na ? (unsigned)na->out_block : 0u;
+    return io;
 }
 
 int petit_gemm_mxfp4_native(void *c, const void *a, const unsigned *b, const unsigned *scales, const float *global_scale, unsigned m,
@@ -282,6 +284,20 @@ int petit_moe_combine_rmsnorm_host(void *qa, void *y16, void *residual_out, cons
                                    unsigned num_tokens, unsigned topk, unsigned k, unsigned num_experts, int a_type, int format) {
     return moe_combine_rmsnorm_host(qa, y16, residual_out, slot_out, topk_weights, topk_ids, ids_are_int64, residual, weight, eps, weight_offset,
                                     num_tokens, topk, k, num_experts, a_type, format);
+}
+int petit_moe_combine_rmsnorm_rot(void *qa, void *y16, void *residual_out, const void *slot_out, const float *topk_weights, const void *topk_ids,
+                                  int ids_are_int64, const void *residual, const void *weight, float eps, float weight_offset,
+                                  unsigned num_tokens, unsigned topk, unsigned k, unsigned num_experts, int a_type, int format, unsigned block,
+                                  void *stream) {
+    return moe_combine_rmsnorm_rot(qa, y16, residual_out, slot_out, topk_weights, topk_ids, ids_are_int64, residual, weight, eps, weight_offset,
+                                   num_tokens, topk, k, num_experts, a_type, format, block, (hipStream_t)stream);
+}
+int petit_moe_combine_rmsnorm_rot_host(void *qa, void *y16, void *residual_out, const void *slot_out, const float *topk_weights,
+                                       const void *topk_ids, int ids_are_int64, const void *residual, const void *weight, float eps,
+                                       float weight_offset, unsigned num_tokens, unsigned topk, unsigned k, unsigned num_experts, int a_type,
+                                       int format, unsigned block) {
+    return moe_combine_rmsnorm_rot_host(qa, y16, residual_out, slot_out, topk_weights, topk_ids, ids_are_int64, residual, weight, eps,
+                                        weight_offset, num_tokens, topk, k, num_experts, a_type, format, block);
 }
 
 uint64_t petit_gemm_workspace_bytes(const petit_solution_hints *hints, unsigned m, unsigned n, unsigned k,

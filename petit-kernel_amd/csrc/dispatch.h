@@ -51,7 +51,7 @@ inline bool act_ok(const SolutionEntry &e) { return e.shape.nt % 2 == 0 && !is_s
 bool act_runs(const SolutionEntry &e, unsigned splitk, unsigned restrict_ = 0);
 // petit_native_args as the native entry points take it (null: 16-bit in and out)
 inline bool native_args_ok(const petit_native_args *na) {
-    return !na || (na->struct_bytes == sizeof(petit_native_args) && na->reserved == 0 &&
+    return !na || (na->struct_bytes == sizeof(petit_native_args) && (na->out_block == 0 || na->out_block == 32 || na->out_block == 128) &&
                    (na->a_format == 0 || na->a_format == 8 || na->a_format == 6 || na->a_format == 4) &&
                    (na->out_format == 0 || na->out_format == 8 || na->out_format == 6 || na->out_format == 4));
 }

@@ -209,7 +209,7 @@ static GemmPlan plan_transient(const GemmCall &g, const Scratch &s) {
     NativeIo io = *g.io;
     io.transient = false;
     GemmCall gi = g;
-    gi.io = (io.a_format || io.out_format) ? &io : nullptr; // (16-bit in and out: planned exactly as the attached-image call, io == nullptr)
+    gi.io = (io.a_format || io.out_format || io.out_block) ? &io : nullptr; // (16-bit in and out: planned exactly as the attached-image call, io == nullptr)
     gi.image = image;
     p = plan_gemm(gi, rest);
     if (p.rc == kOk && p.entry)
@@ -236,6 +236,12 @@ GemmPlan plan_gemm(const GemmCall &g, const Scratch &s, bool part) {
     const unsigned a_format = io ? io->a_format : 0u, out_format = io ? io->out_format : 0u;
     if ((a_format != 0 && a_format != 8 && a_format != 6 && a_format != 4) || (out_format != 0 && out_format != 8 && out_format != 6 && out_format != 4))
         return refuse(kErrBadArgument);
+    // the epilogue's rotation (petit_native_args.out_block): refused here, before any pick; it changes no pick, scratch or geometry below
+    const unsigned out_block = io ? io->out_block : 0u;
+    if ((out_block != 0 && out_block != 32 && out_block != 128) || (out_block && !out_format))
+        return refuse(kErrBadArgument);
+    if (out_block && (out_format == 6 || a_format == 6 || auto_class(g.solution_id) == kClassNativeFp6))
+        return refuse(kErrKernelShape); // (as the quantisers: the MXFP6 converts have no f32 form; the MXFP6 class's kernels carry no rotating epilogue)
     if (m == 0 || n == 0 || k == 0)
         return p; // gemm_fp4_fp16_grid.cc:42-44
     if (!hints)
@@ -346,6 +352,8 @@ GemmPlan plan_gemm(const GemmCall &g, const Scratch &s, bool part) {
             return refuse(kErrKernelShape); // unsplit: needs an even number of n-tiles per wave; split: a 16-bit output (the reduce pass applies SiLU-mul)
         if (!entry_allows(*entry, restrict_) || (a_format && (unsigned)entry_class(*entry) != a_format))
             return refuse(kErrKernelShape);
+        if (out_block && entry_class(*entry) == kClassNativeFp6)
+            return refuse(kErrKernelShape); // (an explicit id of the MXFP6 class: no rotating epilogue)
         if (g.b_type == kDataTypeFp4e2m1 && ((io && io->image) || g.image) && entry_class(*entry) == kClassExact)
             return refuse(kErrKernelShape); // an image names the native class: an exact kernel would read image bytes as packed weights
     }
@@ -440,6 +448,7 @@ static int launch(const GemmCall &g, const LaunchPlan &p) {
     args.m = g.m, args.n = g.n, args.k = g.k;
     args.bias = g.epilogue ? g.epilogue->bias : nullptr;
     args.qa = a_format ? (const void *)g.a : nullptr, args.qa_format = a_format, args.out_format = g.io ? g.io->out_format : 0u;
+    args.out_block = g.io ? g.io->out_block : 0u;
     args.workspace = (float *)p.ws;
     const unsigned kind = g.epilogue ? (unsigned)g.epilogue->activation : 0u; // 1 SiLU-mul / 2 SwiGLU-OAI where p.act or p.reduce_act
     args.act = p.act ? kind : 0u, args.reduce_act = p.reduce_act ? kind : 0u;

@@ -130,12 +130,118 @@ __global__ __launch_bounds__(256) void quantize_act32_fp6_kernel(const void *a, 
 //   32-column block is the wave's two tiles of one row, i.e. this lane's 16 values and its partner's (lane ^ 32) 16.  The block
 //   maximum needs one cross-half swap; a second swap (of the packed codes) leaves lane h with ALL 16 columns of tile np = h, so each
 //   lane stores 8 (FP4) / 16 (FP8) contiguous bytes.
-template <class AT, int OUTF, int MB>
+//
+// HAD = 1 (out_block 32, or 128 with had128; OUTF 8 / 4): the f32 gated values are rotated first, "petit-had/1" along the output columns -- stages d = 1, 2, 4, ..
+// HAD / 2 IN THIS ORDER, (z[c], z[c + d]) <- (z[c] + z[c + d], z[c] - z[c + d]) for (c & d) == 0, every sum and difference one f32 operation --
+// and the quantiser runs on z: still one rounding.  Column c = 32 wn + 16 np + 8 u + 4 h + i of a 128-column k-tile (i: element of the f32x4):
+//   d = 1, 2    inside the lane's f32x4
+//   d = 4       with lane ^ 32 (one permlane32_swap per register: both halves see (h = 0's value, h = 1's value) and add or subtract)
+//   d = 8, 16   between the lane's own registers (u, then np)
+//   d = 32, 64  (HAD = 128) between the workgroup's four waves, through LDS: a 256-column workgroup tile is one 128-column rotation block per row.
+//               Every wave parks its 32 x 32 values of the m-block (16 KiB for the four: x[wn][np][u][lane], 16-byte units, conflict-free), one barrier,
+//               then reads all four waves' values at its own lane position and does both stages itself: with b0 = wn & 1, b1 = wn >> 1
+//                   y[j] = x[2 j] +- x[2 j + 1]   (j = 0, 1; - when b0)         z = y[0] +- y[1]   (- when b1)
+//               which is exactly the value the stage order gives column 32 wn + c.  The buffer alternates between two halves from m-block to
+//               m-block (MB >= 2), so one barrier per m-block orders the reads of m-block mb before the writes of mb + 2.
+// The element that subtracts does so by adding the other operand with its sign flipped (lo - hi == lo + (-hi) bit for bit), so every step is one
+// basic block for all lanes and waves.  lds_x: the exchange buffer, behind the scale bytes in the dead stages (HAD = 128 only).
+constexpr bool n32_out_block_ok(unsigned out_format, unsigned out_block) {
+    return out_block == 0 || ((out_block == 32 || out_block == 128) && (out_format == 8 || out_format == 4));
+}
+// the kernels that carry the rotating epilogue: those of the MXFP8 and MXFP4 activation classes.  The MXFP6 class has no rotated input (its
+// quantiser does not rotate), and its kernels have no register headroom for the extra forms (profiles/hadamard_epilogue.md)
+constexpr bool n32_rotates(int act) { return act == 8 || act == 4; }
+constexpr unsigned kN32HadXBytes = 4 * 4 * 64 * 16; // the exchange buffer of one m-block: four waves x four f32x4 per lane
+constexpr unsigned n32_had_lds_bytes(int mb) { return mb * 128 + (mb >= 2 ? 2 : 1) * kN32HadXBytes; } // scale bytes + exchange halves
+__device__ __forceinline__ float n32_flip(float v, unsigned sign) { return __builtin_bit_cast(float, __builtin_bit_cast(unsigned, v) ^ sign); }
+// (contraction is off inside these bodies only: a gated value is a product, and its first sum must not fuse with it; the rest of the kernel keeps
+// the translation unit's setting)
+__device__ __forceinline__ void n32_pair(float &a, float &b) {
+#pragma clang fp contract(off)
+    const float s = a + b, d = a - b;
+    a = s, b = d;
+}
+// One m-block's 16 values per lane, by value in and out.  NOT inlined: the kernels that carry it sit at their register budget with 128
+// accumulator registers live, and the inlined forms moved the allocation of their main loops (profiles/hadamard_epilogue.md); as a call the
+// body has registers of its own (the callee's clobbers are known to the caller) and one copy serves every kernel and output format of a
+// translation unit.  had128 and x (the exchange buffer's half for this m-block, an LDS address) are workgroup-uniform.
+struct N32Rot {
+    f32x4 v[2][2];
+};
+__device__ __attribute__((noinline)) N32Rot n32_hadamard_block(N32Rot io, const unsigned wn, const unsigned h, const unsigned lane,
+                                                               unsigned char *lds_x, const bool had128) {
+#pragma clang fp contract(off)
+    f32x4(&v)[2][2] = io.v;
+    const unsigned sign_h = h << 31;
+    float z[2][2][4]; // [np][u][i]: column 16 np + 8 u + 4 h + i of the wave's 32-column block
+#pragma unroll
+    for (int np = 0; np < 2; ++np)
+#pragma unroll
+        for (int u = 0; u < 2; ++u) {
+            float(&c)[4] = z[np][u];
+#pragma unroll
+            for (int i = 0; i < 4; ++i)
+                c[i] = v[np][u][i];
+            n32_pair(c[0], c[1]), n32_pair(c[2], c[3]); // d = 1
+            n32_pair(c[0], c[2]), n32_pair(c[1], c[3]); // d = 2
+#pragma unroll
+            for (int i = 0; i < 4; ++i) { // d = 4: lo = the h = 0 lane's value, hi = the h = 1 lane's, in both lanes
+                const unsigned x = __builtin_bit_cast(unsigned, c[i]);
+                const auto sw = __builtin_amdgcn_permlane32_swap(x, x, false, false);
+                const unsigned lo = sw[0], hi = sw[1];
+                c[i] = __builtin_bit_cast(float, lo) + n32_flip(__builtin_bit_cast(float, hi), sign_h);
+            }
+        }
+#pragma unroll
+    for (int np = 0; np < 2; ++np) // d = 8
+#pragma unroll
+        for (int i = 0; i < 4; ++i)
+            n32_pair(z[np][0][i], z[np][1][i]);
+#pragma unroll
+    for (int u = 0; u < 2; ++u) // d = 16
+#pragma unroll
+        for (int i = 0; i < 4; ++i)
+            n32_pair(z[0][u][i], z[1][u][i]);
+#pragma unroll
+    for (int np = 0; np < 2; ++np)
+#pragma unroll
+        for (int u = 0; u < 2; ++u)
+            v[np][u] = f32x4{z[np][u][0], z[np][u][1], z[np][u][2], z[np][u][3]};
+    if (had128) {
+        __attribute__((address_space(3))) f32x4 *const x = (__attribute__((address_space(3))) f32x4 *)lds_x;
+#pragma unroll
+        for (int np = 0; np < 2; ++np)
+#pragma unroll
+            for (int u = 0; u < 2; ++u)
+                x[(wn * 4 + np * 2 + u) * 64 + lane] = v[np][u];
+        __syncthreads();
+        const unsigned sign0 = (wn & 1u) << 31, sign1 = (wn >> 1) << 31;
+#pragma unroll
+        for (int np = 0; np < 2; ++np)
+#pragma unroll
+            for (int u = 0; u < 2; ++u) {
+                const int r = np * 2 + u;
+                const f32x4 x0 = x[(0 * 4 + r) * 64 + lane], x1 = x[(1 * 4 + r) * 64 + lane];
+                const f32x4 x2 = x[(2 * 4 + r) * 64 + lane], x3 = x[(3 * 4 + r) * 64 + lane];
+                f32x4 o;
+#pragma unroll
+                for (int i = 0; i < 4; ++i) {
+                    const float y0 = x0[i] + n32_flip(x1[i], sign0), y1 = x2[i] + n32_flip(x3[i], sign0); // d = 32
+                    o[i] = y0 + n32_flip(y1, sign1);                                                     // d = 64
+                }
+                v[np][u] = o;
+            }
+    }
+    return io;
+}
+template <class AT, int OUTF, int MB, int HAD = 0>
 __device__ __forceinline__ void n32_silu_quant_epilogue(const f32x16 (&acc)[MB][2], const float gs, const void *bias, unsigned char *out,
                                                         const unsigned m_total, const unsigned n_half, const unsigned m_first,
                                                         const unsigned col0, const unsigned kt, const unsigned wn, const unsigned m_l,
                                                         const unsigned h, unsigned char *lds_scales, const unsigned m0, const unsigned tid,
-                                                        const unsigned m_lim, const unsigned act) {
+                                                        const unsigned m_lim, const unsigned act, unsigned char *lds_x = nullptr,
+                                                        const bool had128 = false) {
+    static_assert(HAD == 0 || OUTF == 8 || OUTF == 4, "the rotation: MXFP8 / MXFP4 output only"); // HAD = 1: rotates, by 128 (had128) or 32
     constexpr unsigned kRowB = qact_row_bytes(OUTF); // bytes per row and k-tile: 128 (FP8) / 64 (FP4; FP6: of the image of registers 0-3)
     unsigned char *const qs = out + qact_elem_bytes(m_total, n_half, OUTF);
     unsigned char *const out_hi = out + qact_hi_offset(m_total, n_half); // FP6: the image of registers 4-5
@@ -156,6 +262,28 @@ __device__ __forceinline__ void n32_silu_quant_epilogue(const f32x16 (&acc)[MB][
                 for (int i = 0; i < 4; ++i)
                     amax = fmaxf(amax, fabsf(v[np][u][i]));
             }
+        if constexpr (HAD != 0) { // the quantiser's rule on the rotated values: the block maximum is taken again
+            N32Rot io;
+#pragma unroll
+            for (int np = 0; np < 2; ++np)
+#pragma unroll
+                for (int u = 0; u < 2; ++u)
+                    io.v[np][u] = v[np][u];
+            io = n32_hadamard_block(io, wn, h, h * 32 + m_l, lds_x + (MB >= 2 ? (unsigned)(mb & 1) * kN32HadXBytes : 0u), had128);
+#pragma unroll
+            for (int np = 0; np < 2; ++np)
+#pragma unroll
+                for (int u = 0; u < 2; ++u)
+                    v[np][u] = io.v[np][u];
+            amax = 0.f;
+#pragma unroll
+            for (int np = 0; np < 2; ++np)
+#pragma unroll
+                for (int u = 0; u < 2; ++u)
+#pragma unroll
+                    for (int i = 0; i < 4; ++i)
+                        amax = fmaxf(amax, fabsf(v[np][u][i]));
+        }
         {
             const unsigned au = __builtin_bit_cast(unsigned, amax);
             const auto sw = __builtin_amdgcn_permlane32_swap(au, au, false, false);
@@ -940,6 +1068,19 @@ __global__ __launch_bounds__(Cfg::kThreads, Cfg::kMinWavesPerSimd) void gemm_nat
                 __syncthreads(); // the stages are dead: their LDS holds the scale bytes of the tile
                 unsigned char *const lds_sc = reinterpret_cast<unsigned char *>(smem);
                 const unsigned col0 = (nt0 >> 1) * 16;
+                // (workgroup-uniform, as out_format) the rotating forms: output 8 / 4, in the kernels of the MXFP8 / MXFP4 classes (a rotated
+                // pipeline's own: n32_rotates); a cold branch; the exchange buffer lies behind the scale bytes
+                if constexpr (n32_rotates(ACT)) if (__builtin_expect(p.out_block != 0, 0)) {
+                    static_assert(n32_had_lds_bytes(MB) <= (unsigned)Cfg::kSmemU4 * 16, "the rotation's exchange buffer fits the dead stages");
+                    unsigned char *const lds_x = lds_sc + MB * 128;
+                    if (p.out_format == 4)
+                        n32_silu_quant_epilogue<AT, 4, MB, 1>(acc, gs, bias_e, (unsigned char *)p.c, p.m, n_half, m_base, col0, bn, wn, m_l, h, lds_sc, m0,
+                                                              tid, m_lim, p.act, lds_x, p.out_block == 128);
+                    else
+                        n32_silu_quant_epilogue<AT, 8, MB, 1>(acc, gs, bias_e, (unsigned char *)p.c, p.m, n_half, m_base, col0, bn, wn, m_l, h, lds_sc, m0,
+                                                              tid, m_lim, p.act, lds_x, p.out_block == 128);
+                    return;
+                }
                 if (p.out_format == 4)
                     n32_silu_quant_epilogue<AT, 4, MB>(acc, gs, bias_e, (unsigned char *)p.c, p.m, n_half, m_base, col0, bn, wn, m_l, h, lds_sc, m0, tid,
                                                               m_lim, p.act);

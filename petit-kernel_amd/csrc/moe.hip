@@ -122,6 +122,11 @@ int native_moe_plan(const petit_solution_hints *hints, unsigned num_experts, uns
         return kErrBadArgument; // quantised activations are grouped rows already: nothing to gather
     if (*out_format && (!*act || c_row_index))
         return kErrBadArgument; // the quantised output is the SiLU-mul epilogue's, in the grouped order the next launch reads
+    // the epilogue's rotation (native->out_block, 0 / 32 / 128 by native_args_ok): MXFP8 / MXFP4 output only; no pick or scratch depends on it
+    if (native && native->out_block && !*out_format)
+        return kErrBadArgument;
+    if (native && native->out_block && (*out_format == 6 || *a_format == 6 || auto_class(solution_id) == kClassNativeFp6))
+        return kErrKernelShape; // (the MXFP6 class's kernels carry no rotating epilogue)
     if (*out_format && n % 512 != 0)
         return kErrProblemShape; // the consumer's K = n / 2 must be a whole number of 256-column producer tiles
     if (solution_id == PETIT_SOLUTION_AUTO)
@@ -129,7 +134,7 @@ int native_moe_plan(const petit_solution_hints *hints, unsigned num_experts, uns
     if (m == 0)
         return kOk;
     *e = native_moe_choose(*fam, hints->a_type, canonical_b_type(hints->b_type), *act, num_experts, m, n, k, solution_id, *a_format, *out_format);
-    if (!*e)
+    if (!*e || (native && native->out_block && entry_class(**e) == kClassNativeFp6)) // (an explicit id of the MXFP6 class: no rotating epilogue)
         return kErrKernelShape;
     // the kernels read the quantised rows (and the quantising epilogue writes its output) through 32-bit buffer offsets; one descriptor per NV6 image
     if (petit_quantized_activation_bytes(m, k, entry_class(**e)) >= (1ull << 32) || (*out_format && petit_quantized_activation_bytes(m, n / 2, (int)*out_format) >= (1ull << 32)) ||
@@ -190,7 +195,7 @@ int native_moe_run(void *c, const void *a, const void *b, const void *scales, co
     MoeArgs g{};
     g.c = c, g.a = qa, g.w = b, g.s = mx ? scales : nullptr, g.gs = global_scales, g.bias = epilogue ? epilogue->bias : nullptr, g.act = act ? (unsigned)epilogue->activation : 0u;
     g.offsets = expert_offsets, g.num_experts = num_experts, g.m = m, g.n = n, g.k = k;
-    g.c_idx = c_row_index, g.c_rows = c_row_index ? c_rows : m, g.out_format = out_format;
+    g.c_idx = c_row_index, g.c_rows = c_row_index ? c_rows : m, g.out_format = out_format, g.out_block = native ? (unsigned)native->out_block : 0u;
     return e->launch_moe_native(g, moe_geometry(*e, m, n, k), (hipStream_t)stream);
 }
 

@@ -13,6 +13,8 @@ template <class Cfg> int launch_native32_moe(const MoeArgs &g, const LaunchGeome
     // the quantising SiLU-mul epilogue: full 256-column workgroup tiles, identity rows (its output is the next launch's grouped input)
     if (g.out_format && (!g.act || g.n % 512 != 0 || g.c_idx || (g.out_format != 8 && g.out_format != 6 && g.out_format != 4)))
         return kErrKernelShape;
+    if (g.out_block && !(n32_rotates(Cfg::ACT) && n32_out_block_ok(g.out_format, g.out_block)))
+        return kErrKernelShape;
     const unsigned slots = moe_slots(g.m, geo.moe_rows(), g.num_experts);
     if (!slots)
         return kErrKernelShape;
@@ -20,7 +22,7 @@ template <class Cfg> int launch_native32_moe(const MoeArgs &g, const LaunchGeome
     a.c = g.c, a.a = g.a, a.w = g.w, a.s = g.s, a.gs = g.gs, a.bias = g.bias, a.act = g.act;
     a.m = g.m, a.n = g.n, a.k = g.k;
     a.spans_per_wave = geo.spans_per_part;       // (one K slice: the whole K range)
-    a.qa = g.a, a.qa_format = Cfg::ACT, a.out_format = g.out_format;
+    a.qa = g.a, a.qa_format = Cfg::ACT, a.out_format = g.out_format, a.out_block = g.out_block;
     hipLaunchKernelGGL((gemm_native32_kernel<Cfg, Native32MoeLocator<Cfg>>), dim3(geo.grid_x, slots), dim3(Cfg::kThreads), 0,
                        stream, a, (const unsigned char *)g.a, Native32MoeLocator<Cfg>{g.offsets, g.num_experts, g.c_idx, g.c_rows});
     return hipGetLastError() == hipSuccess ? kOk : kErrLaunch;

@@ -67,6 +67,7 @@ struct GemmArgs {
     const void *qa;          // pre-quantised activations in the k-tile-major scratch layout of format qa_format, or null
     unsigned qa_format;      // 8 (MXFP8) / 4 (MXFP4) when qa is set
     unsigned out_format;     // 0: c is a 16-bit matrix; 8 / 4: c receives [m][n/2] activations quantised to MXFP8 / MXFP4 (act = 1 / 2 only)
+    unsigned out_block;      // out_format 8 / 4: 32 / 128 = the gated values are rotated ("petit-had/1") in blocks of that many columns first; 0: not
 };
 enum : unsigned { kFlagPrio = 1u, kFlagXcdRaster = 2u, kFlagBandShift = 8 }; // bits 8..15: m-tiles per raster band (0 = whole columns)
 
@@ -103,6 +104,7 @@ struct MoeArgs {
     // the native forms only (petit_gemm_native_moe, gemm_moe_native.hpp): a holds the QUANTISED grouped rows (the kernel's own format), and
     // out_format 8 / 6 / 4 makes the SiLU-mul epilogue write c as the next launch's quantised grouped rows
     unsigned out_format = 0;
+    unsigned out_block = 0; // 32 / 128 (out_format 8 / 4): that epilogue rotates its f32 values in blocks of that many columns first ("petit-had/1")
 };
 // the grid rows a MoE launch needs for any routing (gemm_moe.hpp), 0 when that exceeds the grid's y limit
 inline unsigned moe_slots(unsigned m, unsigned bm, unsigned num_experts) {
@@ -134,6 +136,7 @@ struct NativeIo {
     unsigned a_format, out_format;
     const void *image = nullptr; // NVFP4 weights: their MFMA-native image (nvnative.hip), when the caller hands it over per call
     bool transient = false;      // NVFP4 weights: the image is built per call at the front of the call's scratch (petit_gemm_nvfp4_native_transient)
+    unsigned out_block = 0;      // out_format 8 / 4: the epilogue's rotation block, 32 / 128 (petit_native_args.out_block); changes no pick and no scratch
 };
 int gemm_impl(int b_type, unsigned *c, const unsigned *a, const unsigned *b, const unsigned *scales, const float *global_scale, unsigned m,
               unsigned n, unsigned k, const petit_solution_hints *hints, uint64_t solution_id, const petit_epilogue *epilogue, void *call_ws,
@@ -214,6 +217,13 @@ int moe_combine_rmsnorm(void *qa, void *y16, void *residual_out, const void *slo
 int moe_combine_rmsnorm_host(void *qa, void *y16, void *residual_out, const void *slot_out, const float *topk_weights, const void *topk_ids,
                              int ids_are_int64, const void *residual, const void *weight, float eps, float weight_offset, unsigned num_tokens,
                              unsigned topk, unsigned k, unsigned num_experts, int a_type, int format);
+// ... with the rotation in front of its quantiser (format 8 / 4); block 0: the above
+int moe_combine_rmsnorm_rot(void *qa, void *y16, void *residual_out, const void *slot_out, const float *topk_weights, const void *topk_ids,
+                            int ids_are_int64, const void *residual, const void *weight, float eps, float weight_offset, unsigned num_tokens,
+                            unsigned topk, unsigned k, unsigned num_experts, int a_type, int format, unsigned block, hipStream_t stream);
+int moe_combine_rmsnorm_rot_host(void *qa, void *y16, void *residual_out, const void *slot_out, const float *topk_weights, const void *topk_ids,
+                                 int ids_are_int64, const void *residual, const void *weight, float eps, float weight_offset, unsigned num_tokens,
+                                 unsigned topk, unsigned k, unsigned num_experts, int a_type, int format, unsigned block);
 // moe_router.hip: the router's GEMM (include/petit_amd.h "The router's GEMM"), as the route entries of moe_route.hip use it.  router_shape_rc:
 // the shape / dtype refusals (kOk when the call can run).  router_slab_bytes: the fp32 slabs of the form T gets, rounded up to 256 bytes.
 // router_gemm_launch writes router_slabs(T, ...) slabs [T][E] back to back; router_finish_launch sums n_slabs of them in order and adds the

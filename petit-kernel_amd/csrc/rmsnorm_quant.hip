@@ -300,7 +300,7 @@ __device__ __forceinline__ void combine_group(int n, float (&acc)[ILP][8], const
 }
 #endif
 
-template <bool BF16, int ACT, int ILP> __global__ __launch_bounds__(256) void moe_combine_rmsnorm_kernel(const CombineNormArgs a) {
+template <bool BF16, int ACT, int ILP, int HAD = 0> __global__ __launch_bounds__(256) void moe_combine_rmsnorm_kernel(const CombineNormArgs a) {
 #if defined(__HIP_DEVICE_COMPILE__)
     constexpr int kDepth = kSlotDepth<ILP>;
     __shared__ float wave_sum[4];
@@ -374,7 +374,7 @@ template <bool BF16, int ACT, int ILP> __global__ __launch_bounds__(256) void mo
                 o_row[c] = h[j];
         }
     }
-    norm_quant_tail<BF16, ACT, ILP>(p, h, wv, wave_sum, y_row);
+    norm_quant_tail<BF16, ACT, ILP, HAD>(p, h, wv, wave_sum, y_row); // (HAD: the quantiser runs on the rotated f32(y16), as in rmsnorm_quant_kernel)
 #endif
 }
 
@@ -714,11 +714,15 @@ int mcn_check(const void *qa, const void *y16, const void *res_out, const void *
     return kOk;
 }
 
-template <bool BF16, int ACT> auto mcn_kernel_for(unsigned k) {
-    return k <= 2048   ? moe_combine_rmsnorm_kernel<BF16, ACT, 1>
-           : k <= 4096 ? moe_combine_rmsnorm_kernel<BF16, ACT, 2>
-           : k <= 8192 ? moe_combine_rmsnorm_kernel<BF16, ACT, 4>
-                       : moe_combine_rmsnorm_kernel<BF16, ACT, 8>;
+template <bool BF16, int ACT, int HAD = 0> auto mcn_kernel_for(unsigned k) {
+    return k <= 2048   ? moe_combine_rmsnorm_kernel<BF16, ACT, 1, HAD>
+           : k <= 4096 ? moe_combine_rmsnorm_kernel<BF16, ACT, 2, HAD>
+           : k <= 8192 ? moe_combine_rmsnorm_kernel<BF16, ACT, 4, HAD>
+                       : moe_combine_rmsnorm_kernel<BF16, ACT, 8, HAD>;
+}
+// the rotating forms: MXFP8 / MXFP4 only
+template <bool BF16, int HAD> auto mcn_rot_kernel_for(int format, unsigned k) {
+    return format == 8 ? mcn_kernel_for<BF16, 8, HAD>(k) : mcn_kernel_for<BF16, 4, HAD>(k);
 }
 template <bool BF16> auto mcn_kernel_for(int format, unsigned k) {
     return format == 8   ? mcn_kernel_for<BF16, 8>(k)
@@ -727,7 +731,7 @@ template <bool BF16> auto mcn_kernel_for(int format, unsigned k) {
                          : mcn_kernel_for<BF16, 0>(k);
 }
 
-template <bool BF16, int ACT> void mcn_host(const CombineNormArgs &a) {
+template <bool BF16, int ACT> void mcn_host(const CombineNormArgs &a, unsigned had = 0) {
     const RmsQuantArgs &p = a.n;
     const unsigned k = p.k;
     std::vector<float> acc(k);
@@ -758,7 +762,7 @@ template <bool BF16, int ACT> void mcn_host(const CombineNormArgs &a) {
         if (p.y16)
             memcpy((uint16_t *)p.y16 + (size_t)row * k, y.data(), 2 * (size_t)k);
         if constexpr (ACT != 0)
-            quantize_row_host<BF16, ACT>(p.qa, y.data(), p.m, k, row);
+            quantize_row_host<BF16, ACT>(p.qa, y.data(), p.m, k, row, had);
     }
 }
 
@@ -799,6 +803,69 @@ int moe_combine_rmsnorm_host(void *qa, void *y16, void *res_out, const void *slo
         bf16 ? mcn_host<true, 4>(a) : mcn_host<false, 4>(a);
     else
         bf16 ? mcn_host<true, 0>(a) : mcn_host<false, 0>(a);
+    return kOk;
+}
+
+// The rotating forms (include/petit_amd.h "Block-Hadamard rotation"): block 0 is the entry above; what it refuses is refused here, then a call
+// without quantised bytes (nothing to rotate) and MXFP6.  *run = false with kOk: nothing to do, or (block == 0) the caller delegates
+namespace {
+int mcn_rot_check(const void *qa, const void *y16, const void *res_out, const void *slot, const float *tw, const void *ids, const void *res,
+                  const void *w, float eps, float woff, unsigned num_tokens, unsigned topk, unsigned k, unsigned num_experts, int a_type, int format,
+                  unsigned block, bool *run) {
+    *run = false;
+    if (!hadamard_block_ok(block))
+        return kErrBadArgument;
+    if (block == 0)
+        return kOk;
+    if (const int rc = mcn_check(qa, y16, res_out, slot, tw, ids, res, w, eps, woff, num_tokens, topk, k, num_experts, a_type, format, run);
+        rc != kOk || !*run)
+        return rc;
+    if (format == 0 || format == 6) {
+        *run = false;
+        return format == 0 ? kErrBadArgument : kErrKernelShape;
+    }
+    return kOk;
+}
+} // namespace
+
+int moe_combine_rmsnorm_rot(void *qa, void *y16, void *res_out, const void *slot, const float *tw, const void *ids, int i64, const void *res,
+                            const void *w, float eps, float woff, unsigned num_tokens, unsigned topk, unsigned k, unsigned num_experts, int a_type,
+                            int format, unsigned block, hipStream_t stream) {
+    bool run;
+    if (const int rc =
+            mcn_rot_check(qa, y16, res_out, slot, tw, ids, res, w, eps, woff, num_tokens, topk, k, num_experts, a_type, format, block, &run);
+        rc != kOk)
+        return rc;
+    if (block == 0)
+        return moe_combine_rmsnorm(qa, y16, res_out, slot, tw, ids, i64, res, w, eps, woff, num_tokens, topk, k, num_experts, a_type, format, stream);
+    if (!run)
+        return kOk;
+    const bool bf16 = a_type == kDataTypeBf16;
+    const auto kern = block == 32 ? (bf16 ? mcn_rot_kernel_for<true, 32>(format, k) : mcn_rot_kernel_for<false, 32>(format, k))
+                                  : (bf16 ? mcn_rot_kernel_for<true, 128>(format, k) : mcn_rot_kernel_for<false, 128>(format, k));
+    hipLaunchKernelGGL(kern, dim3(num_tokens), dim3(256), 0, stream,
+                       mcn_args(qa, y16, res_out, slot, tw, ids, i64, res, w, eps, woff, num_tokens, topk, k, num_experts));
+    return hipGetLastError() == hipSuccess ? kOk : kErrLaunch;
+}
+
+int moe_combine_rmsnorm_rot_host(void *qa, void *y16, void *res_out, const void *slot, const float *tw, const void *ids, int i64, const void *res,
+                                 const void *w, float eps, float woff, unsigned num_tokens, unsigned topk, unsigned k, unsigned num_experts,
+                                 int a_type, int format, unsigned block) {
+    bool run;
+    if (const int rc =
+            mcn_rot_check(qa, y16, res_out, slot, tw, ids, res, w, eps, woff, num_tokens, topk, k, num_experts, a_type, format, block, &run);
+        rc != kOk)
+        return rc;
+    if (block == 0)
+        return moe_combine_rmsnorm_host(qa, y16, res_out, slot, tw, ids, i64, res, w, eps, woff, num_tokens, topk, k, num_experts, a_type, format);
+    if (!run)
+        return kOk;
+    const CombineNormArgs a = mcn_args(qa, y16, res_out, slot, tw, ids, i64, res, w, eps, woff, num_tokens, topk, k, num_experts);
+    const bool bf16 = a_type == kDataTypeBf16;
+    if (format == 8)
+        bf16 ? mcn_host<true, 8>(a, block) : mcn_host<false, 8>(a, block);
+    else
+        bf16 ? mcn_host<true, 4>(a, block) : mcn_host<false, 4>(a, block);
     return kOk;
 }
 

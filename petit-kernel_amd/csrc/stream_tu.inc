@@ -223,6 +223,8 @@ template <class Cfg> int launch_native32(const GemmArgs &args, const LaunchGeome
             (args.out_format != 8 && args.out_format != 6 && args.out_format != 4))
             return kErrKernelShape;
     }
+    if (args.out_block && !(n32_rotates(Cfg::ACT) && n32_out_block_ok(args.out_format, args.out_block)))
+        return kErrKernelShape; // (backstop: the plan refuses it first)
     // workspace: [quantised activations + their scales | fp32 slabs of a K split]  (sized for the FP8 form: dispatch.hip workspace_need)
     unsigned char *ws = reinterpret_cast<unsigned char *>(args.workspace);
     const unsigned char *qa = reinterpret_cast<const unsigned char *>(args.qa);

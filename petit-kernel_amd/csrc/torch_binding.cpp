@@ -622,7 +622,7 @@ at::Tensor moe_combine(const at::Tensor &slot_out, const at::Tensor &topk_weight
 #define PETIT_COMBINE_NORM_ARGS                                                                                                            \
     const at::Tensor &slot_out, const at::Tensor &topk_weights, const at::Tensor &topk_ids, int64_t num_experts, const at::Tensor &weight, \
         double eps, int64_t format, const std::optional<at::Tensor> &residual, double weight_offset, bool return_normed, bool return_hidden, \
-        bool inplace_residual
+        bool inplace_residual, int64_t hadamard
 std::tuple<at::Tensor, at::Tensor, at::Tensor> moe_combine_rmsnorm(PETIT_COMBINE_NORM_ARGS) {
     check_topk_ids(topk_ids, num_experts);
     const int64_t T = topk_ids.size(0), topk = topk_ids.size(1);
@@ -635,6 +635,9 @@ std::tuple<at::Tensor, at::Tensor, at::Tensor> moe_combine_rmsnorm(PETIT_COMBINE
                 "topk_weights must be a contiguous float32 [num_tokens, topk] tensor on topk_ids' device");
     const int64_t k = slot_out.size(1);
     TORCH_CHECK(format == 0 || format == 8 || format == 6 || format == 4, "fmt must be None, 'mxfp8', 'mxfp6' or 'mxfp4'");
+    TORCH_CHECK(hadamard == 0 || hadamard == 32 || hadamard == 128, "hadamard must be 0 (no rotation), 32 or 128");
+    TORCH_CHECK(!hadamard || format, "hadamard needs a fmt: it rotates the quantised output only");
+    TORCH_CHECK(!hadamard || format != 6, "hadamard needs fmt 'mxfp8' or 'mxfp4': the MXFP6 quantiser has no rotating form");
     TORCH_CHECK(k % 8 == 0, "k must be a multiple of 8, got ", k);
     TORCH_CHECK(format == 0 || k % 256 == 0, "k must be a multiple of 256 with a fmt, got ", k);
     TORCH_CHECK(weight.device() == slot_out.device() && weight.is_contiguous() && weight.scalar_type() == slot_out.scalar_type() &&
@@ -653,11 +656,11 @@ std::tuple<at::Tensor, at::Tensor, at::Tensor> moe_combine_rmsnorm(PETIT_COMBINE
     at::Tensor h = return_hidden && !inplace_residual ? at::empty({T, k}, slot_out.options()) : at::empty({0}, slot_out.options());
     at::Tensor y = return_normed ? at::empty({T, k}, slot_out.options()) : at::empty({0}, slot_out.options());
     void *const h_ptr = !return_hidden ? nullptr : inplace_residual ? residual->data_ptr() : h.data_ptr();
-    const int rc = petit_moe_combine_rmsnorm(format ? qa.data_ptr() : nullptr, return_normed ? y.data_ptr() : nullptr, h_ptr, slot_out.data_ptr(),
+    const int rc = petit_moe_combine_rmsnorm_rot(format ? qa.data_ptr() : nullptr, return_normed ? y.data_ptr() : nullptr, h_ptr, slot_out.data_ptr(),
                                              (const float *)topk_weights.data_ptr(), topk_ids.data_ptr(), topk_ids.scalar_type() == at::kLong,
                                              has_res ? residual->data_ptr() : nullptr, weight.data_ptr(), (float)eps, (float)weight_offset,
                                              (unsigned)T, (unsigned)topk, (unsigned)k, (unsigned)num_experts, a_type_of(slot_out.scalar_type()),
-                                             (int)format, stream_of(slot_out));
+                                             (int)format, (unsigned)hadamard, stream_of(slot_out)); // (block 0: the unrotated entry)
     TORCH_CHECK(rc != PETIT_ERROR_PROBLEM_SHAPE, "Incompatible problem shape (num_tokens=", T, ", topk=", topk, ", k=", k, ", num_experts=", num_experts, ")");
     TORCH_CHECK(rc != PETIT_ERROR_KERNEL_SHAPE, "No kernel implementation for k=", k, " (the fused norm holds a row of at most 16384 elements).");
     TORCH_CHECK(rc == PETIT_OK, "moe_combine_rmsnorm: ", petit_error_string(rc));
@@ -878,6 +881,13 @@ std::tuple<at::Tensor, at::Tensor, at::Tensor, at::Tensor, at::Tensor, at::Tenso
         const at::Tensor &expert_offsets, int64_t size_m, int64_t size_n, int64_t size_k, int64_t num_experts,                                    \
         const std::optional<at::Tensor> &a_row_index, const std::optional<at::Tensor> &c_row_index, int64_t c_rows, int64_t solution_id,         \
         const std::optional<at::Tensor> &bias, int64_t activation, int64_t a_format, int64_t a_type, int64_t out_format
+// out_hadamard of the native ops (petit_native_args.out_block): the same checks and texts as petit_kernel/ops.py _out_hadamard
+int32_t check_out_hadamard(int64_t out_hadamard, int64_t out_format) {
+    TORCH_CHECK(out_hadamard == 0 || out_hadamard == 32 || out_hadamard == 128, "hadamard must be 0 (no rotation), 32 or 128");
+    TORCH_CHECK(!out_hadamard || out_format, "out_hadamard needs out_quantized 'mxfp8' or 'mxfp4'");
+    TORCH_CHECK(!out_hadamard || out_format != 6, "hadamard needs fmt 'mxfp8' or 'mxfp4': the MXFP6 quantiser has no rotating form");
+    return (int32_t)out_hadamard;
+}
 at::ScalarType native_moe_dtype(const at::Tensor &A, int64_t a_format, int64_t a_type) {
     if (!a_format) {
         check_a16(A);
@@ -888,7 +898,8 @@ at::ScalarType native_moe_dtype(const at::Tensor &A, int64_t a_format, int64_t a
 }
 // transient (NVFP4): B / s are the stacked packed tensors, the images are built per call into the call's workspace (petit_gemm_native_moe_transient)
 // workspace (transient only): the caller's scratch instead of one from the allocator
-at::Tensor mul_native_moe_impl(bool mx, bool transient, PETIT_NATIVE_MOE_ARGS, const std::optional<at::Tensor> &workspace = std::nullopt) {
+at::Tensor mul_native_moe_impl(bool mx, bool transient, PETIT_NATIVE_MOE_ARGS, const std::optional<at::Tensor> &workspace = std::nullopt,
+                               int64_t out_hadamard = 0) {
     const int64_t E = num_experts;
     const at::ScalarType dtype = native_moe_dtype(A, a_format, a_type);
     check_expert_operands(mx, true, A, B, s.has_value() ? &*s : nullptr, global_scales, expert_offsets, E, size_n, size_k, transient);
@@ -909,7 +920,7 @@ at::Tensor mul_native_moe_impl(bool mx, bool transient, PETIT_NATIVE_MOE_ARGS, c
     const uint64_t sid = c_solution_id(solution_id, true);
     const petit_epilogue epi{bias.has_value() ? bias->data_ptr() : nullptr, (int32_t)activation, 0};
     const petit_epilogue *epi_p = (bias.has_value() || activation) ? &epi : nullptr;
-    const petit_native_args na{sizeof(petit_native_args), (int32_t)a_format, (int32_t)out_format, 0};
+    const petit_native_args na{sizeof(petit_native_args), (int32_t)a_format, (int32_t)out_format, check_out_hadamard(out_hadamard, out_format)};
     const auto query = transient ? petit_gemm_native_moe_transient_workspace_bytes : petit_gemm_native_moe_workspace_bytes;
     const auto launch = transient ? petit_gemm_native_moe_transient : petit_gemm_native_moe;
     const uint64_t ws_bytes = query(&hints, (unsigned)E, (unsigned)size_m, (unsigned)size_n, (unsigned)size_k, sid, epi_p, &na);
@@ -927,17 +938,17 @@ at::Tensor mul_native_moe_impl(bool mx, bool transient, PETIT_NATIVE_MOE_ARGS, c
                       c10::str("m=", size_m, ", n=", size_n, ", k=", size_k, ", num_experts=", E, ", a_rows=", a_rows, ", c_rows=", c_rows));
     return c;
 }
-at::Tensor mul_mxfp4_native_moe(PETIT_NATIVE_MOE_ARGS) {
+at::Tensor mul_mxfp4_native_moe(PETIT_NATIVE_MOE_ARGS, int64_t out_hadamard) {
     return mul_native_moe_impl(true, false, A, B, s, global_scales, expert_offsets, size_m, size_n, size_k, num_experts, a_row_index, c_row_index, c_rows,
-                               solution_id, bias, activation, a_format, a_type, out_format);
+                               solution_id, bias, activation, a_format, a_type, out_format, std::nullopt, out_hadamard);
 }
-at::Tensor mul_nvfp4_native_moe(PETIT_NATIVE_MOE_ARGS) {
+at::Tensor mul_nvfp4_native_moe(PETIT_NATIVE_MOE_ARGS, int64_t out_hadamard) {
     return mul_native_moe_impl(false, false, A, B, s, global_scales, expert_offsets, size_m, size_n, size_k, num_experts, a_row_index, c_row_index, c_rows,
-                               solution_id, bias, activation, a_format, a_type, out_format);
+                               solution_id, bias, activation, a_format, a_type, out_format, std::nullopt, out_hadamard);
 }
-at::Tensor mul_nvfp4_native_moe_transient(PETIT_NATIVE_MOE_ARGS, const std::optional<at::Tensor> &workspace) {
+at::Tensor mul_nvfp4_native_moe_transient(PETIT_NATIVE_MOE_ARGS, const std::optional<at::Tensor> &workspace, int64_t out_hadamard) {
     return mul_native_moe_impl(false, true, A, B, s, global_scales, expert_offsets, size_m, size_n, size_k, num_experts, a_row_index, c_row_index, c_rows,
-                               solution_id, bias, activation, a_format, a_type, out_format, workspace);
+                               solution_id, bias, activation, a_format, a_type, out_format, workspace, out_hadamard);
 }
 
 // NVFP4 weights on the native class without a resident image (petit_gemm_nvfp4_native_transient): the same checks and texts as petit_kernel/ops.py
@@ -947,7 +958,7 @@ at::Tensor mul_nvfp4_native_moe_transient(PETIT_NATIVE_MOE_ARGS, const std::opti
     const at::Tensor &A, const at::Tensor &B, const at::Tensor &s, const at::Tensor &global_scale, int64_t size_m, int64_t size_n,         \
         int64_t size_k, int64_t solution_id, const std::optional<at::Tensor> &bias, int64_t activation, int64_t a_format, int64_t a_type,    \
         int64_t out_format
-at::Tensor mul_nvfp4_native_transient(PETIT_NV_TRANSIENT_ARGS) {
+at::Tensor mul_nvfp4_native_transient(PETIT_NV_TRANSIENT_ARGS, int64_t out_hadamard) {
     const at::ScalarType dtype = native_moe_dtype(A, a_format, a_type);
     TORCH_CHECK(A.is_cuda() && A.is_contiguous() && (a_format ? A.numel() == (int64_t)petit_quantized_activation_bytes((unsigned)size_m, (unsigned)size_k, (int)a_format)
                                                                : A.numel() == size_m * size_k),
@@ -965,7 +976,7 @@ at::Tensor mul_nvfp4_native_transient(PETIT_NV_TRANSIENT_ARGS) {
     const uint64_t sid = c_solution_id(solution_id, true);
     const petit_epilogue epi{bias.has_value() ? bias->data_ptr() : nullptr, (int32_t)activation, 0};
     const petit_epilogue *epi_p = (bias.has_value() || activation) ? &epi : nullptr;
-    const petit_native_args na{sizeof(petit_native_args), (int32_t)a_format, (int32_t)out_format, 0};
+    const petit_native_args na{sizeof(petit_native_args), (int32_t)a_format, (int32_t)out_format, check_out_hadamard(out_hadamard, out_format)};
     const uint64_t ws_bytes = petit_gemm_nvfp4_native_transient_workspace_bytes(&hints, (unsigned)size_m, (unsigned)size_n, (unsigned)size_k, sid, epi_p, &na);
     at::Tensor ws = at::empty({(int64_t)ws_bytes}, A.options().dtype(at::kByte));
     const int rc = petit_gemm_nvfp4_native_transient(c.data_ptr(), A.data_ptr(), (const unsigned *)B.data_ptr(), (const unsigned *)s.data_ptr(),
@@ -1018,13 +1029,16 @@ at::Tensor mul_nvfp4_native_invariant_meta(PETIT_NV_NATIVE_INVARIANT_ARGS) {
 at::Tensor mul_nvfp4_native_moe_invariant_meta(PETIT_NV_NATIVE_MOE_INVARIANT_ARGS) {
     return at::empty({c_rows < 0 ? m : c_rows, activation ? n / 2 : n}, A.options().dtype(bf16 ? at::kBFloat16 : at::kHalf));
 }
-at::Tensor mul_nvfp4_native_transient_meta(PETIT_NV_TRANSIENT_ARGS) {
+at::Tensor mul_nvfp4_native_transient_meta(PETIT_NV_TRANSIENT_ARGS, int64_t out_hadamard) {
+    check_out_hadamard(out_hadamard, out_format);
     return native_output(A, native_moe_dtype(A, a_format, a_type), size_m, size_m, activation ? size_n / 2 : size_n, out_format);
 }
-at::Tensor mul_native_moe_meta(PETIT_NATIVE_MOE_ARGS) {
+at::Tensor mul_native_moe_meta(PETIT_NATIVE_MOE_ARGS, int64_t out_hadamard) {
+    check_out_hadamard(out_hadamard, out_format);
     return native_output(A, native_moe_dtype(A, a_format, a_type), c_rows < 0 ? size_m : c_rows, size_m, activation ? size_n / 2 : size_n, out_format);
 }
-at::Tensor mul_native_moe_transient_meta(PETIT_NATIVE_MOE_ARGS, const std::optional<at::Tensor> &) {
+at::Tensor mul_native_moe_transient_meta(PETIT_NATIVE_MOE_ARGS, const std::optional<at::Tensor> &, int64_t out_hadamard) {
+    check_out_hadamard(out_hadamard, out_format);
     return native_output(A, native_moe_dtype(A, a_format, a_type), c_rows < 0 ? size_m : c_rows, size_m, activation ? size_n / 2 : size_n, out_format);
 }
 std::tuple<at::Tensor, at::Tensor, at::Tensor> moe_align_device_meta(const at::Tensor &topk_ids, int64_t num_experts) {
@@ -1111,16 +1125,16 @@ TORCH_LIBRARY(petit_kernel, m) {
     "Tensor A, Tensor B, Tensor? s, Tensor global_scales, Tensor expert_offsets, int size_m, int size_n, int size_k, int num_experts, "    \
     "Tensor? a_row_index=None, Tensor? c_row_index=None, int c_rows=-1, int solution_id=-2, Tensor? bias=None, int activation=0, "        \
     "int a_format=0, int a_type=5, int out_format=0"
-    m.def("mul_mxfp4_native_moe(" PETIT_NATIVE_MOE_SCHEMA ") -> Tensor");
-    m.def("mul_nvfp4_native_moe(" PETIT_NATIVE_MOE_SCHEMA ") -> Tensor");
-    m.def("mul_nvfp4_native_moe_transient(" PETIT_NATIVE_MOE_SCHEMA ", Tensor? workspace=None) -> Tensor");
+    m.def("mul_mxfp4_native_moe(" PETIT_NATIVE_MOE_SCHEMA ", int out_hadamard=0) -> Tensor");
+    m.def("mul_nvfp4_native_moe(" PETIT_NATIVE_MOE_SCHEMA ", int out_hadamard=0) -> Tensor");
+    m.def("mul_nvfp4_native_moe_transient(" PETIT_NATIVE_MOE_SCHEMA ", Tensor? workspace=None, int out_hadamard=0) -> Tensor");
     m.def("mul_nvfp4_native_transient(Tensor A, Tensor B, Tensor s, Tensor global_scale, int size_m, int size_n, int size_k, int solution_id=-2, "
-          "Tensor? bias=None, int activation=0, int a_format=0, int a_type=5, int out_format=0) -> Tensor");
+          "Tensor? bias=None, int activation=0, int a_format=0, int a_type=5, int out_format=0, int out_hadamard=0) -> Tensor");
     m.def("moe_align_device(Tensor topk_ids, int num_experts) -> (Tensor, Tensor, Tensor)");
     m.def("moe_combine(Tensor slot_out, Tensor topk_weights, Tensor topk_ids, int num_experts) -> Tensor");
     m.def("moe_combine_rmsnorm(Tensor slot_out, Tensor topk_weights, Tensor topk_ids, int num_experts, Tensor weight, float eps=1e-6, "
           "int format=0, Tensor(a!)? residual=None, float weight_offset=0.0, bool return_normed=True, bool return_hidden=False, "
-          "bool inplace_residual=False) -> (Tensor, Tensor, Tensor)");
+          "bool inplace_residual=False, int hadamard=0) -> (Tensor, Tensor, Tensor)");
 #define PETIT_ROUTE_SCHEMA                                                                                                            \
     "Tensor router_logits, int topk, int scoring=0, bool renormalize=True, Tensor? bias=None, int n_group=1, int topk_group=1, " \
     "float routed_scaling_factor=1.0, bool return_keys=False"

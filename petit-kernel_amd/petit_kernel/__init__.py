@@ -277,12 +277,12 @@ def moe_combine(slot_out: torch.Tensor, topk_weights: torch.Tensor, topk_ids: to
 
 def moe_combine_rmsnorm(slot_out: torch.Tensor, topk_weights: torch.Tensor, topk_ids: torch.Tensor, num_experts: int, weight: torch.Tensor,
                         eps: float = 1e-6, fmt: str = None, *, residual: torch.Tensor = None, weight_offset: float = 0.0,
-                        return_normed: bool = None, return_hidden: bool = None, inplace_residual: bool = False):
+                        return_normed: bool = None, return_hidden: bool = None, inplace_residual: bool = False, hadamard: int = 0):
     # moe_combine, the residual add, the RMSNorm and (with fmt) quantize_activations in ONE launch (include/petit_amd.h "Top-k combine into the
     # norm"; ops.moe_combine_rmsnorm has the return convention): the end of a routed-expert layer and the head of the next block
     return _impl.moe_combine_rmsnorm(slot_out, topk_weights, topk_ids, num_experts, weight, eps, fmt, residual=residual,
                                      weight_offset=weight_offset, return_normed=return_normed, return_hidden=return_hidden,
-                                     inplace_residual=inplace_residual)
+                                     inplace_residual=inplace_residual, hadamard=hadamard)
 
 
 def _no_slots(expert_map, num_local_experts, num_shared, shared_weight, shared_gate_logits) -> bool:
@@ -344,32 +344,35 @@ def moe_route_hidden(hidden: torch.Tensor, router_weight: torch.Tensor, topk: in
 
 def mul_mxfp4_native_moe(a, b: torch.Tensor, s: torch.Tensor, global_scales: torch.Tensor, expert_offsets: torch.Tensor, size_m: int, size_n: int,
                          size_k: int, num_experts: int, a_row_index: torch.Tensor = None, c_row_index: torch.Tensor = None, c_rows: int = None,
-                         solution_id: int = SOLUTION_AUTO_NATIVE_MXFP8, bias: torch.Tensor = None, activation: str = None, out_quantized: str = None):
+                         solution_id: int = SOLUTION_AUTO_NATIVE_MXFP8, bias: torch.Tensor = None, activation: str = None, out_quantized: str = None,
+                         out_hadamard: int = 0):
     # the MoE launch on the native class (include/petit_amd.h "Native-class MoE launch"): `a` 16-bit [a_rows, size_k] (gathered through
     # a_row_index, quantised by the call) or QuantizedActivations of the size_m grouped rows; solution_id a native sentinel or a native id with
-    # a MoE form; out_quantized (activation "silu_mul") returns the grouped rows quantised for the next launch
+    # a MoE form; out_quantized (activation "silu_mul") returns the grouped rows quantised for the next launch, rotated inside the epilogue by
+    # the Hadamard block out_hadamard (32 / 128; 'mxfp8' / 'mxfp4') for a next launch on quantize_*(w, hadamard=) weights
     return _impl.mul_mxfp4_native_moe(a, b, s, global_scales, expert_offsets, size_m, size_n, size_k, num_experts, a_row_index, c_row_index, c_rows,
-                                      solution_id, bias, activation, out_quantized)
+                                      solution_id, bias, activation, out_quantized, out_hadamard)
 
 
 def mul_nvfp4_native_moe(a, images: torch.Tensor, global_scales: torch.Tensor, expert_offsets: torch.Tensor, size_m: int, size_n: int, size_k: int,
                          num_experts: int, a_row_index: torch.Tensor = None, c_row_index: torch.Tensor = None, c_rows: int = None,
-                         solution_id: int = SOLUTION_AUTO_NATIVE_MXFP8, bias: torch.Tensor = None, activation: str = None, out_quantized: str = None):
+                         solution_id: int = SOLUTION_AUTO_NATIVE_MXFP8, bias: torch.Tensor = None, activation: str = None, out_quantized: str = None,
+                         out_hadamard: int = 0):
     # NVFP4 experts on the native class: `images` = nvfp4_native_images of the stacked packed tensors (E images back to back)
     return _impl.mul_nvfp4_native_moe(a, images, global_scales, expert_offsets, size_m, size_n, size_k, num_experts, a_row_index, c_row_index, c_rows,
-                                      solution_id, bias, activation, out_quantized)
+                                      solution_id, bias, activation, out_quantized, out_hadamard)
 
 
 def mul_nvfp4_native_moe_transient(a, b: torch.Tensor, s: torch.Tensor, global_scales: torch.Tensor, expert_offsets: torch.Tensor, size_m: int,
                                    size_n: int, size_k: int, num_experts: int, a_row_index: torch.Tensor = None, c_row_index: torch.Tensor = None,
                                    c_rows: int = None, solution_id: int = SOLUTION_AUTO_NATIVE_MXFP8, bias: torch.Tensor = None,
-                                   activation: str = None, out_quantized: str = None, workspace: torch.Tensor = None):
+                                   activation: str = None, out_quantized: str = None, workspace: torch.Tensor = None, out_hadamard: int = 0):
     # NVFP4 experts on the native class WITHOUT resident images (include/petit_amd.h "Without resident images"): b / s are the stacked packed
     # tensors of mul_nvfp4_a16_moe; each call builds the images of the experts that have rows into a per-call workspace (one launch) and runs on
     # them -- bit for bit mul_nvfp4_native_moe on nvfp4_native_images(b, s, ...).  workspace: the caller's scratch instead (uint8, at least
     # nvfp4_native_moe_transient_workspace_bytes), which several calls may share one after the other
     return _impl.mul_nvfp4_native_moe_transient(a, b, s, global_scales, expert_offsets, size_m, size_n, size_k, num_experts, a_row_index,
-                                                c_row_index, c_rows, solution_id, bias, activation, out_quantized, workspace)
+                                                c_row_index, c_rows, solution_id, bias, activation, out_quantized, workspace, out_hadamard)
 
 
 def nvfp4_native_moe_transient_workspace_bytes(num_experts: int, size_m: int, size_n: int, size_k: int,
@@ -382,11 +385,12 @@ def nvfp4_native_moe_transient_workspace_bytes(num_experts: int, size_m: int, si
 
 def mul_nvfp4_native_transient(a, b: torch.Tensor, s: torch.Tensor, global_scale: torch.Tensor, size_m: int, size_n: int, size_k: int,
                                solution_id: int = SOLUTION_AUTO_NATIVE_MXFP8, bias: torch.Tensor = None, activation: str = None,
-                               out_quantized: str = None):
+                               out_quantized: str = None, out_hadamard: int = 0):
     # NVFP4 weights on the native class WITHOUT a resident image (include/petit_amd.h "Without a resident image"): b / s are the packed tensors of
     # mul_nvfp4_a16; each call builds the image into a per-call workspace and runs on it -- bit for bit mul_nvfp4_a16(..., -2 / -3 / -4) with the image
     # attached, or mul_nvfp4_native on the image; `a` a 16-bit tensor or QuantizedActivations
-    return _impl.mul_nvfp4_native_transient(a, b, s, global_scale, size_m, size_n, size_k, solution_id, bias, activation, out_quantized)
+    return _impl.mul_nvfp4_native_transient(a, b, s, global_scale, size_m, size_n, size_k, solution_id, bias, activation, out_quantized,
+                                            out_hadamard)
 
 
 def nvfp4_native_transient_workspace_bytes(size_m: int, size_n: int, size_k: int, solution_id: int = SOLUTION_AUTO_NATIVE_MXFP8,

@@ -54,7 +54,7 @@ class GroupMember(C.Structure):
 
 class NativeArgs(C.Structure):
     """petit_native_args (include/petit_amd.h)."""
-    _fields_ = [("struct_bytes", C.c_uint32), ("a_format", C.c_int32), ("out_format", C.c_int32), ("reserved", C.c_int32)]
+    _fields_ = [("struct_bytes", C.c_uint32), ("a_format", C.c_int32), ("out_format", C.c_int32), ("out_block", C.c_int32)]
 
 
 class RouteDesc(C.Structure):
@@ -203,6 +203,10 @@ _SIGNATURES = {
                                   [C.c_int, C.c_int, C.c_void_p]),
     "petit_moe_combine_rmsnorm_host": (C.c_int, [C.c_void_p] * 6 + [C.c_int, C.c_void_p, C.c_void_p, C.c_float, C.c_float] + [C.c_uint] * 4 +
                                        [C.c_int, C.c_int]),
+    "petit_moe_combine_rmsnorm_rot": (C.c_int, [C.c_void_p] * 6 + [C.c_int, C.c_void_p, C.c_void_p, C.c_float, C.c_float] + [C.c_uint] * 4 +
+                                      [C.c_int, C.c_int, C.c_uint, C.c_void_p]),
+    "petit_moe_combine_rmsnorm_rot_host": (C.c_int, [C.c_void_p] * 6 + [C.c_int, C.c_void_p, C.c_void_p, C.c_float, C.c_float] + [C.c_uint] * 4 +
+                                           [C.c_int, C.c_int, C.c_uint]),
     "petit_quantize_activations_rows": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p] + [C.c_uint] * 3 + [C.c_int, C.c_int, C.c_void_p]),
     # the block-Hadamard rotation ("petit-had/1") and the rotating forms of the quantisers: `block` follows `format`
     "petit_hadamard_rows": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint, C.c_uint, C.c_int, C.c_uint, C.c_int, C.c_void_p]),

@@ -19,7 +19,7 @@ from .ops import QuantizedActivations, _a_type, _activation as _act, _activation
 from .ops import _check_invariant, _check_route_hidden, _check_router, _combine_norm_operands, _combine_norm_returns
 from .ops import invariant_geometry, invariant_slabs, invariant_workspace_bytes  # (queries: plain C calls, no op behind them)
 from .ops import moe_invariant_form, moe_invariant_workspace_bytes
-from .ops import _QFORMATS, native_invariant_slabs, native_invariant_workspace_bytes
+from .ops import _QFORMATS, _out_hadamard, native_invariant_slabs, native_invariant_workspace_bytes
 from .ops import native_moe_invariant_form, native_moe_invariant_workspace_bytes
 
 LIB_PATH = Path(_lib.LIB_PATH).parent / "libpetit_torch.so"
@@ -208,13 +208,14 @@ def moe_combine(slot_out, topk_weights, topk_ids, num_experts):
 
 
 def moe_combine_rmsnorm(slot_out, topk_weights, topk_ids, num_experts, weight, eps=1e-6, fmt=None, *, residual=None, weight_offset=0.0,
-                        return_normed=None, return_hidden=None, inplace_residual=False):
-    T, _, k = _combine_norm_operands(slot_out, topk_weights, topk_ids, num_experts, weight, eps, fmt, residual, weight_offset, on_gpu=True)
+                        return_normed=None, return_hidden=None, inplace_residual=False, hadamard=0):
+    T, _, k = _combine_norm_operands(slot_out, topk_weights, topk_ids, num_experts, weight, eps, fmt, residual, weight_offset, on_gpu=True,
+                                     hadamard=hadamard)
     want_h, want_y = _combine_norm_returns(fmt, residual, return_normed, return_hidden, inplace_residual)
     qa, h, y = torch.ops.petit_kernel.moe_combine_rmsnorm(slot_out, topk_weights, topk_ids, int(num_experts), weight, float(eps),
                                                           _quantized_format(fmt, "fmt must be None, 'mxfp8', 'mxfp6' or 'mxfp4'"), residual,
-                                                          float(weight_offset), want_y, want_h, bool(inplace_residual))
-    out = (QuantizedActivations(qa, T, k, fmt, slot_out.dtype),) if fmt else ()
+                                                          float(weight_offset), want_y, want_h, bool(inplace_residual), hadamard)
+    out = (QuantizedActivations(qa, T, k, fmt, slot_out.dtype, hadamard),) if fmt else ()
     out += ((residual if inplace_residual else h),) if want_h else ()
     out += (y,) if want_y else ()
     return out[0] if len(out) == 1 else out
@@ -289,36 +290,40 @@ def _native_operands(A, size_m, size_k, out_quantized):
 
 
 def _mul_native_moe(kind, A, B, s, global_scales, expert_offsets, size_m, size_n, size_k, num_experts, a_row_index, c_row_index, c_rows,
-                    solution_id, bias, activation, out_quantized, transient=False, workspace=None):
+                    solution_id, bias, activation, out_quantized, transient=False, workspace=None, out_hadamard=0):
     a_t, a_fmt, a_type, out_fmt, dtype = _native_operands(A, size_m, size_k, out_quantized)
+    out_block = _out_hadamard(out_hadamard, out_quantized)
     op = getattr(torch.ops.petit_kernel, f"mul_{kind}fp4_native_moe" + ("_transient" if transient else ""))
     extra = (workspace,) if transient else ()
     c = op(a_t, B, s, global_scales, expert_offsets, size_m, size_n, size_k, num_experts, a_row_index, c_row_index,
-           -1 if c_rows is None else int(c_rows), _sid(solution_id, native=True), bias, _act(activation), a_fmt, a_type, out_fmt, *extra)
-    return QuantizedActivations(c, size_m, size_n // 2, out_quantized, dtype) if out_fmt else c
+           -1 if c_rows is None else int(c_rows), _sid(solution_id, native=True), bias, _act(activation), a_fmt, a_type, out_fmt, *extra,
+           out_hadamard=out_block)
+    return QuantizedActivations(c, size_m, size_n // 2, out_quantized, dtype, out_block) if out_fmt else c
 
 
 def mul_mxfp4_native_moe(A, B, s, global_scales, expert_offsets, size_m, size_n, size_k, num_experts, a_row_index=None, c_row_index=None,
-                         c_rows=None, solution_id=-2, bias=None, activation=None, out_quantized=None):
+                         c_rows=None, solution_id=-2, bias=None, activation=None, out_quantized=None, out_hadamard=0):
     return _mul_native_moe("mx", A, B, s, global_scales, expert_offsets, size_m, size_n, size_k, num_experts, a_row_index, c_row_index, c_rows,
-                           solution_id, bias, activation, out_quantized)
+                           solution_id, bias, activation, out_quantized, out_hadamard=out_hadamard)
 
 
 def mul_nvfp4_native_moe(A, images, global_scales, expert_offsets, size_m, size_n, size_k, num_experts, a_row_index=None, c_row_index=None,
-                         c_rows=None, solution_id=-2, bias=None, activation=None, out_quantized=None):
+                         c_rows=None, solution_id=-2, bias=None, activation=None, out_quantized=None, out_hadamard=0):
     return _mul_native_moe("nv", A, images, None, global_scales, expert_offsets, size_m, size_n, size_k, num_experts, a_row_index, c_row_index,
-                           c_rows, solution_id, bias, activation, out_quantized)
+                           c_rows, solution_id, bias, activation, out_quantized, out_hadamard=out_hadamard)
 
 
 def mul_nvfp4_native_moe_transient(A, B, s, global_scales, expert_offsets, size_m, size_n, size_k, num_experts, a_row_index=None,
                                    c_row_index=None, c_rows=None, solution_id=-2, bias=None, activation=None, out_quantized=None,
-                                   workspace=None):
+                                   workspace=None, out_hadamard=0):
     return _mul_native_moe("nv", A, B, s, global_scales, expert_offsets, size_m, size_n, size_k, num_experts, a_row_index, c_row_index, c_rows,
-                           solution_id, bias, activation, out_quantized, transient=True, workspace=workspace)
+                           solution_id, bias, activation, out_quantized, transient=True, workspace=workspace, out_hadamard=out_hadamard)
 
 
-def mul_nvfp4_native_transient(A, B, s, global_scale, size_m, size_n, size_k, solution_id=-2, bias=None, activation=None, out_quantized=None):
+def mul_nvfp4_native_transient(A, B, s, global_scale, size_m, size_n, size_k, solution_id=-2, bias=None, activation=None, out_quantized=None,
+                               out_hadamard=0):
     a_t, a_fmt, a_type, out_fmt, dtype = _native_operands(A, size_m, size_k, out_quantized)
+    out_block = _out_hadamard(out_hadamard, out_quantized)
     c = torch.ops.petit_kernel.mul_nvfp4_native_transient(a_t, B, s, global_scale, size_m, size_n, size_k, _sid(solution_id, native=True),
-                                                          bias, _act(activation), a_fmt, a_type, out_fmt)
-    return QuantizedActivations(c, size_m, size_n // 2, out_quantized, dtype) if out_fmt else c
+                                                          bias, _act(activation), a_fmt, a_type, out_fmt, out_block)
+    return QuantizedActivations(c, size_m, size_n // 2, out_quantized, dtype, out_block) if out_fmt else c

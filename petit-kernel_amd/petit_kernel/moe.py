@@ -84,7 +84,8 @@ def fp4_moe(hidden: torch.Tensor, w13: torch.Tensor, s13: torch.Tensor, gs13: to
 def fp4_moe_fused(hidden: torch.Tensor, w13: torch.Tensor, s13: torch.Tensor, gs13: torch.Tensor, w2: torch.Tensor, s2: torch.Tensor,
                   gs2: torch.Tensor, topk_weights: torch.Tensor, topk_ids: torch.Tensor, kind: str = "nvfp4", *, bias13: torch.Tensor = None,
                   bias2: torch.Tensor = None, activation: str = "silu_mul", norm_weight: torch.Tensor = None, norm_eps: float = 1e-6,
-                  norm_residual: torch.Tensor = None, norm_weight_offset: float = 0.0, norm_fmt: str = None, invariant: bool = False):
+                  norm_residual: torch.Tensor = None, norm_weight_offset: float = 0.0, norm_fmt: str = None, invariant: bool = False,
+                  norm_hadamard: int = 0):
     """fp4_moe's layer (same arguments, same result up to the combine's rounding order) on the indexed MoE launches: align on the device,
     gate_up on gathered rows, down scattered into slot order, the top-k combine.  topk_ids: int32 or int64 [T, topk]; entries outside
     [0, E) (-1 under expert parallelism) contribute nothing.  topk_weights: float32 or bfloat16 [T, topk] (converted to float32 once).
@@ -97,7 +98,8 @@ def fp4_moe_fused(hidden: torch.Tensor, w13: torch.Tensor, s13: torch.Tensor, gs
     norm_residual) in 16 bits, y16 = RMSNorm(h) * (norm_weight + norm_weight_offset), q = quantize_activations(y16, norm_fmt), each bit for bit
     what the un-fused layer followed by rmsnorm_quantize gives.  The fused end is for a layer whose combine is COMPLETE on this rank: under
     tensor or expert parallelism an all-reduce belongs between the combine and the residual add, so such a layer ends in moe_combine.
-    Measured (profiles/moe_combine_norm.md) against moe_combine followed by the norm.
+    Measured (profiles/moe_combine_norm.md) against moe_combine followed by the norm.  norm_hadamard = 32 / 128 (norm_fmt 'mxfp8' / 'mxfp4'):
+    q is rotated by that Hadamard block, as quantize_activations(y16, norm_fmt, hadamard=) does, for a next block on rotated weights.
 
     invariant=True: gate_up and down run as the batch-invariant MoE launches (mul_*_a16_moe_invariant) in place of the indexed ones;
     everything else is unchanged.  Every slot row is then a pure function of its token's hidden row and its expert's weights, and the
@@ -107,19 +109,20 @@ def fp4_moe_fused(hidden: torch.Tensor, w13: torch.Tensor, s13: torch.Tensor, gs
     (profiles/moe_invariant.md); float16 hidden states with kind 'mxfp4' have no batch-invariant kernel."""
     _check_fused(kind, activation)
     _check_invariant_layer(invariant, "fused", kind, hidden)
-    norm = _norm_end(norm_weight, norm_eps, norm_residual, norm_weight_offset, norm_fmt)
+    norm = _norm_end(norm_weight, norm_eps, norm_residual, norm_weight_offset, norm_fmt, norm_hadamard)
     w, ids, sorted_pos, offsets, token_index = _align_routing(topk_weights, topk_ids, gs13.numel())
     return _fused_after_align(hidden, w13, s13, gs13, w2, s2, gs2, w, ids, sorted_pos, offsets, token_index, kind, bias13, bias2, activation, norm,
                               invariant)
 
 
-def _norm_end(norm_weight, norm_eps, norm_residual, norm_weight_offset, norm_fmt):
+def _norm_end(norm_weight, norm_eps, norm_residual, norm_weight_offset, norm_fmt, norm_hadamard=0):
     """The fused end of a layer as its last step takes it: None (the layer ends in moe_combine) or moe_combine_rmsnorm's arguments."""
     if norm_weight is None:
-        if norm_residual is not None or norm_fmt is not None:
-            raise RuntimeError("norm_residual / norm_fmt need a norm_weight (the fused end of the layer)")
+        if norm_residual is not None or norm_fmt is not None or norm_hadamard:
+            raise RuntimeError("norm_residual / norm_fmt / norm_hadamard need a norm_weight (the fused end of the layer)")
         return None
-    return dict(weight=norm_weight, eps=norm_eps, fmt=norm_fmt, residual=norm_residual, weight_offset=norm_weight_offset, return_hidden=True)
+    return dict(weight=norm_weight, eps=norm_eps, fmt=norm_fmt, residual=norm_residual, weight_offset=norm_weight_offset, return_hidden=True,
+                hadamard=norm_hadamard)
 
 
 def _combine(y, w, ids, num_experts, norm):
@@ -181,7 +184,7 @@ def fp4_moe_native(hidden: torch.Tensor, w13: torch.Tensor, s13, gs13: torch.Ten
                    topk_weights: torch.Tensor, topk_ids: torch.Tensor, kind: str = "mxfp4", activations: str = "mxfp8", *,
                    bias13: torch.Tensor = None, bias2: torch.Tensor = None, activation: str = "silu_mul", transient: bool = False,
                    norm_weight: torch.Tensor = None, norm_eps: float = 1e-6, norm_residual: torch.Tensor = None, norm_weight_offset: float = 0.0,
-                   norm_fmt: str = None, invariant: bool = False):
+                   norm_fmt: str = None, invariant: bool = False, hadamard: int = 0, norm_hadamard: int = 0):
     """fp4_moe_fused's layer on the NATIVE class (the block-scaled MFMA, activations quantised to `activations`: 'mxfp8', 'mxfp6' or 'mxfp4';
     petit_gemm_native_moe -- a different accuracy class than the exact layers).  kind 'mxfp4': w13 / s13 / w2 / s2 as fp4_moe_fused; kind
     'nvfp4': w13 / w2 are the experts' MFMA-native images back to back (nvfp4_native_images) and s13 / s2 are None.  Five launches (seven
@@ -196,7 +199,12 @@ def fp4_moe_native(hidden: torch.Tensor, w13: torch.Tensor, s13, gs13: torch.Ten
     and, while it runs, that scratch.  Bit for bit the resident layer on nvfp4_native_images of the same tensors.
 
     norm_weight / norm_eps / norm_residual / norm_weight_offset / norm_fmt: fp4_moe_fused's fused end (the combine, the residual add, the next
-    RMSNorm and its quantiser in the last launch; returns (h, y16) or (q, h)), for a layer whose combine is complete on this rank.
+    RMSNorm and its quantiser in the last launch; returns (h, y16) or (q, h)), for a layer whose combine is complete on this rank;
+    norm_hadamard rotates q, as in fp4_moe_fused.
+
+    hadamard = 32 / 128 (activations 'mxfp8' / 'mxfp4'; w13 / w2 from quantize_*(w, hadamard=B)): the rotated layer in the same launches --
+    the gathering quantiser rotates the hidden rows and gate_up's epilogue rotates the quantised rows it hands to down (out_hadamard).
+    Not with invariant=True, whose entries have no quantising epilogue.
 
     invariant=True (kind 'mxfp4', resident tensors): gate_up and down run as the native class's batch-invariant MoE launches
     (mul_mxfp4_native_moe_invariant): the device align, the gathering quantiser, gate_up on the quantised grouped rows with the gated
@@ -206,19 +214,21 @@ def fp4_moe_native(hidden: torch.Tensor, w13: torch.Tensor, s13, gs13: torch.Ten
     any batch, at any position -- with the fused norm end too.  bfloat16 and float16 hidden states.  Opt-in and slower
     (profiles/native_moe_invariant.md).  kind 'nvfp4' and transient=True raise: images are not on the invariant native entries."""
     _check_native(kind, activation, activations, transient)
+    if hadamard and invariant:
+        raise RuntimeError("hadamard is not for invariant=True: the batch-invariant native entries have no quantising epilogue to rotate in")
     if invariant:
         if transient:
             raise RuntimeError("invariant=True on the native class does not take transient=True: images have no batch-invariant native kernel")
         if kind == "nvfp4":
             raise RuntimeError("invariant=True on the native class is for kind 'mxfp4': NVFP4 images have no batch-invariant native kernel "
                                "(fp4_moe_fused(..., invariant=True) runs NVFP4 experts in the exact class)")
-    norm = _norm_end(norm_weight, norm_eps, norm_residual, norm_weight_offset, norm_fmt)
+    norm = _norm_end(norm_weight, norm_eps, norm_residual, norm_weight_offset, norm_fmt, norm_hadamard)
     w, ids, sorted_pos, offsets, token_index = _align_routing(topk_weights, topk_ids, gs13.numel())
     if invariant:
         return _native_invariant_after_align(hidden, w13, s13, gs13, w2, s2, gs2, w, ids, sorted_pos, offsets, token_index, activations, bias13,
                                              bias2, activation, norm)
     return _native_after_align(hidden, w13, s13, gs13, w2, s2, gs2, w, ids, sorted_pos, offsets, token_index, kind, activations, bias13, bias2,
-                               activation, transient, norm)
+                               activation, transient, norm, hadamard)
 
 
 def _check_native(kind, activation, activations, transient=False) -> None:
@@ -249,8 +259,9 @@ def _native_invariant_after_align(hidden, w13, s13, gs13, w2, s2, gs2, w, ids, s
 
 
 def _native_after_align(hidden, w13, s13, gs13, w2, s2, gs2, w, ids, sorted_pos, offsets, token_index, kind, activations, bias13, bias2,
-                        activation, transient=False, norm=None):
-    """fp4_moe_native after its align: the gathering quantiser, gate_up, down scattered into slot order, the combine."""
+                        activation, transient=False, norm=None, hadamard=0):
+    """fp4_moe_native after its align: the gathering quantiser, gate_up, down scattered into slot order, the combine.  hadamard: both
+    quantised inputs (the gathered rows, gate_up's hand-over) are rotated by that block."""
     from . import mul_mxfp4_native_moe, mul_nvfp4_native_moe, mul_nvfp4_native_moe_transient, quantize_activation_rows
     sid = _NATIVE_SENTINELS[activations]
     T, H = hidden.shape
@@ -266,7 +277,7 @@ def _native_after_align(hidden, w13, s13, gs13, w2, s2, gs2, w, ids, sorted_pos,
         inter = n13 // 2
         n2 = H
         mul, gate_up, down = mul_nvfp4_native_moe, (w13, gs13), (w2, gs2)
-    qa = quantize_activation_rows(hidden, activations, token_index)                  # grouped rows; unrouted (-1) rows are zeros
+    qa = quantize_activation_rows(hidden, activations, token_index, hadamard=hadamard)   # grouped rows; unrouted (-1) rows are zeros
     ws = {}
     if transient:   # one scratch for both launches (a_format: both take quantised rows where gate_up hands them over; else down quantises)
         from . import nvfp4_native_moe_transient_workspace_bytes as query
@@ -277,7 +288,7 @@ def _native_after_align(hidden, w13, s13, gs13, w2, s2, gs2, w, ids, sorted_pos,
             ws = {"workspace": torch.empty(need, dtype=torch.uint8, device=hidden.device)}
     # gate_up writes down's quantised input, grouped, where its tiles allow; else 16-bit, and down quantises it (one more launch)
     h = mul(qa, *gate_up, offsets, m, n13, H, E, solution_id=sid, bias=bias13, activation=activation,
-            out_quantized=activations if n13 % 512 == 0 else None, **ws)
+            out_quantized=activations if n13 % 512 == 0 else None, out_hadamard=hadamard, **ws)
     y = mul(h, *down, offsets, m, n2, inter, E, solution_id=sid, c_row_index=sorted_pos, c_rows=m, bias=bias2, **ws)   # [m, n2], (token, slot) order
     return _combine(y, w, ids, E, norm)
 
@@ -287,7 +298,7 @@ def fp4_moe_routed(hidden: torch.Tensor, router_logits: torch.Tensor, w13: torch
                    bias13: torch.Tensor = None, bias2: torch.Tensor = None, activation: str = "silu_mul", transient: bool = False,
                    norm_weight: torch.Tensor = None, norm_eps: float = 1e-6, norm_residual: torch.Tensor = None, norm_weight_offset: float = 0.0,
                    norm_fmt: str = None, router_weight: torch.Tensor = None, router_bias: torch.Tensor = None,
-                   router_input: torch.Tensor = None, invariant: bool = False, **routing):
+                   router_input: torch.Tensor = None, invariant: bool = False, norm_hadamard: int = 0, **routing):
     """The layer from the router's logits: moe_route_align(router_logits, topk, **routing), then exactly the launches fp4_moe_fused (path
     'fused') or fp4_moe_native (path 'native', with `activations`) issue after their align -- bit for bit
     fp4_moe_fused(..., *moe_route(router_logits, topk, **routing)).  router_logits [T, E] float32 / bfloat16 / float16; routing: moe_route's
@@ -309,7 +320,7 @@ def fp4_moe_routed(hidden: torch.Tensor, router_logits: torch.Tensor, w13: torch
     experts' `hidden` is a padded copy of it (gpt-oss: 2880 columns against 3072).
 
     norm_weight / norm_eps / norm_residual / norm_weight_offset / norm_fmt: fp4_moe_fused's fused end on either path (returns (h, y16) or
-    (q, h)): with route + align in one launch the whole layer and the next block's norm are four launches.  For a layer whose combine is complete
+    (q, h); norm_hadamard rotates q): with route + align in one launch the whole layer and the next block's norm are four launches.  For a layer whose combine is complete
     on this rank (no all-reduce between the combine and the residual add).
 
     invariant=True (path 'fused'): fp4_moe_fused's switch -- gate_up and down run as the batch-invariant MoE launches.  From
@@ -352,7 +363,7 @@ def fp4_moe_routed(hidden: torch.Tensor, router_logits: torch.Tensor, w13: torch
     if gs13.numel() != local + num_shared:
         raise RuntimeError(f"the weights hold {gs13.numel()} experts, the routing names {local} local + {num_shared} shared "
                            f"(router_logits must be [{hidden.size(0)}, {gs13.numel() - num_shared}] without an expert_map)")
-    norm = _norm_end(norm_weight, norm_eps, norm_residual, norm_weight_offset, norm_fmt)
+    norm = _norm_end(norm_weight, norm_eps, norm_residual, norm_weight_offset, norm_fmt, norm_hadamard)
     if router_weight is not None:
         w, ids, sorted_pos, offsets, token_index = moe_route_hidden(router_input if router_input is not None else hidden, router_weight, topk,
                                                                     router_bias=router_bias, **routing)

@@ -838,12 +838,23 @@ def mul_mxfp4_native_invariant(A, B, s, global_scale, size_m, size_n, size_k, fm
     return _mul_invariant(A, B, s, global_scale, size_m, size_n, size_k, bias, activation, "mx", fmt)
 
 
-def _native_output(rows: int, size_m: int, n_out: int, out_quantized, dtype, dev):
+_OUT_HADAMARD_NEEDS = "out_hadamard needs out_quantized 'mxfp8' or 'mxfp4'"
+
+
+def _out_hadamard(out_hadamard, out_quantized) -> int:
+    """The rotation block of a quantising gated epilogue (petit_native_args.out_block): 0, or 32 / 128 with an MXFP8 / MXFP4 out_quantized."""
+    block = _hadamard_block(out_hadamard)
+    _check(block == 0 or out_quantized is not None, _OUT_HADAMARD_NEEDS)
+    _check(block == 0 or out_quantized != "mxfp6", _HADAMARD_FP6)
+    return block
+
+
+def _native_output(rows: int, size_m: int, n_out: int, out_quantized, dtype, dev, out_hadamard: int = 0):
     """(the tensor the call writes, what the caller returns): 16-bit [rows, n_out], or with out_quantized the bytes of the quantised
     [size_m, n_out] rows and the QuantizedActivations around them."""
     if out_quantized:
         c = torch.empty(int(_lib.lib.petit_quantized_activation_bytes(size_m, n_out, _QFORMATS[out_quantized])), dtype=torch.uint8, device=dev)
-        return c, QuantizedActivations(c, size_m, n_out, out_quantized, dtype)
+        return c, QuantizedActivations(c, size_m, n_out, out_quantized, dtype, out_hadamard)
     c = torch.empty((rows, n_out), dtype=dtype, device=dev)
     return c, c
 
@@ -860,7 +871,7 @@ def _check_packed(B, s, size_n: int, size_k: int, group, num_experts=None) -> No
 
 
 def _mul_native(fn, workspace_bytes, name: str, kind: str, A, weights, global_scale, size_m, size_n, size_k, solution_id, bias, activation,
-                out_quantized):
+                out_quantized, out_hadamard=0):
     """The dense call on the native class behind mul_mxfp4_native / mul_nvfp4_native / mul_nvfp4_native_transient.  weights: (B, s), the
     packed tensors of `kind` ('mx' / 'nv'), or (image,); fn / workspace_bytes: the C entry point and its scratch query."""
     a_t, dtype, a_fmt = _activation_operand(A, size_m, size_k)
@@ -878,11 +889,12 @@ def _mul_native(fn, workspace_bytes, name: str, kind: str, A, weights, global_sc
     act = _activation(activation)
     out_fmt = _quantized_format(out_quantized, "out_quantized must be None, 'mxfp8', 'mxfp6' or 'mxfp4'")
     _check(not out_fmt or act, "out_quantized needs activation='silu_mul' or 'swiglu_oai'")
+    out_block = _out_hadamard(out_hadamard, out_quantized)
     hints = _hints(kind, dtype)
     sid = C.c_uint64(_c_solution_id(solution_id, native_ok=True))
     epi = _epilogue(bias, act, dev, dtype, size_n, "bias must be a contiguous [size_n] tensor of the activation dtype on the same device")
-    na = _lib.NativeArgs(C.sizeof(_lib.NativeArgs), a_fmt, out_fmt, 0)
-    c, result = _native_output(size_m, size_m, size_n // 2 if act else size_n, out_quantized, dtype, dev)
+    na = _lib.NativeArgs(C.sizeof(_lib.NativeArgs), a_fmt, out_fmt, out_block)
+    c, result = _native_output(size_m, size_m, size_n // 2 if act else size_n, out_quantized, dtype, dev, out_block)
     ws_bytes = int(workspace_bytes(C.byref(hints), size_m, size_n, size_k, sid, epi, C.byref(na)))
     ws = _scratch(ws_bytes, dev)
     with torch.cuda.device(dev):
@@ -894,13 +906,15 @@ def _mul_native(fn, workspace_bytes, name: str, kind: str, A, weights, global_sc
 
 
 def mul_mxfp4_native(A, B, s, global_scale, size_m, size_n, size_k, solution_id=SOLUTION_AUTO_NATIVE_MXFP4, bias=None, activation=None,
-                     out_quantized=None):
+                     out_quantized=None, out_hadamard=0):
     """The native-FP4 class with its hand-over points (petit_gemm_mxfp4_native).  A: a 16-bit [size_m, size_k] tensor (quantised
     by the call: two launches) or QuantizedActivations (one launch).  out_quantized 'mxfp8' / 'mxfp6' / 'mxfp4' (with activation='silu_mul'):
-    returns QuantizedActivations [size_m, size_n / 2] for the next GEMM instead of a 16-bit tensor.
+    returns QuantizedActivations [size_m, size_n / 2] for the next GEMM instead of a 16-bit tensor.  out_hadamard = 32 / 128 (out_quantized
+    'mxfp8' / 'mxfp4'): the epilogue rotates its f32 values by that Hadamard block before it quantises them ("petit-had/1", as
+    quantize_activations(.., hadamard=)), for a next GEMM whose weights come from quantize_*(w, hadamard=B).
     solution_id: SOLUTION_AUTO_NATIVE_MXFP8 / _MXFP4 / _MXFP6 (-2 / -3 / -4) or an explicit native kernel id."""
     return _mul_native(_lib.lib.petit_gemm_mxfp4_native, _lib.lib.petit_gemm_native_workspace_bytes, "mul_mxfp4_native", "mx", A, (B, s),
-                       global_scale, size_m, size_n, size_k, solution_id, bias, activation, out_quantized)
+                       global_scale, size_m, size_n, size_k, solution_id, bias, activation, out_quantized, out_hadamard)
 
 
 # --- NVFP4 weights on the native class (include/petit_amd.h "NVFP4 weights on the native class"; no counterpart in the reference) ----------
@@ -939,12 +953,12 @@ def attach_nvfp4_native(B: torch.Tensor, image) -> None:
 
 
 def mul_nvfp4_native(A, image: torch.Tensor, global_scale, size_m, size_n, size_k, solution_id=SOLUTION_AUTO_NATIVE_MXFP8, bias=None,
-                     activation=None, out_quantized=None):
+                     activation=None, out_quantized=None, out_hadamard=0):
     """NVFP4 weights on the block-scaled MFMA (petit_gemm_nvfp4_native): `image` from nvfp4_native_image; everything else as mul_mxfp4_native
     (A a 16-bit tensor or QuantizedActivations; solution_id -2 / -3 / -4 = MXFP8 / MXFP4 / MXFP6 activations or an explicit native id of the
-    NVFP4 family; out_quantized with activation='silu_mul')."""
+    NVFP4 family; out_quantized with activation='silu_mul', out_hadamard with out_quantized)."""
     return _mul_native(_lib.lib.petit_gemm_nvfp4_native, _lib.lib.petit_gemm_native_workspace_bytes, "mul_nvfp4_native", "nv", A, (image,),
-                       global_scale, size_m, size_n, size_k, solution_id, bias, activation, out_quantized)
+                       global_scale, size_m, size_n, size_k, solution_id, bias, activation, out_quantized, out_hadamard)
 
 
 def nvfp4_native_transient_workspace_bytes(size_m, size_n, size_k, solution_id=SOLUTION_AUTO_NATIVE_MXFP8, dtype=torch.bfloat16, activation=None,
@@ -962,14 +976,14 @@ def nvfp4_native_transient_workspace_bytes(size_m, size_n, size_k, solution_id=S
 
 
 def mul_nvfp4_native_transient(A, B, s, global_scale, size_m, size_n, size_k, solution_id=SOLUTION_AUTO_NATIVE_MXFP8, bias=None, activation=None,
-                               out_quantized=None):
+                               out_quantized=None, out_hadamard=0):
     """NVFP4 weights on the block-scaled MFMA WITHOUT a resident image (petit_gemm_nvfp4_native_transient): B / s are the packed tensors
     mul_nvfp4_a16 takes; the call builds the image into a workspace it takes from torch's caching allocator, then runs the native call on it.
     Bit for bit mul_nvfp4_a16(..., solution_id) with the image attached (16-bit A and result) / mul_nvfp4_native on the image (QuantizedActivations
     A, out_quantized).  Everything else as mul_nvfp4_native."""
     return _mul_native(_lib.lib.petit_gemm_nvfp4_native_transient, _lib.lib.petit_gemm_nvfp4_native_transient_workspace_bytes,
                        "mul_nvfp4_native_transient", "nv", A, (B, s), global_scale, size_m, size_n, size_k, solution_id, bias, activation,
-                       out_quantized)
+                       out_quantized, out_hadamard)
 
 
 # --- the batch-invariant native class on NVFP4 images (include/petit_amd.h "Batch-invariant native-class GEMM and MoE launch on NVFP4 images") ---
@@ -1242,10 +1256,13 @@ def moe_combine(slot_out: torch.Tensor, topk_weights: torch.Tensor, topk_ids: to
     return out
 
 
-def _combine_norm_operands(slot_out, topk_weights, topk_ids, num_experts, weight, eps, fmt, residual, weight_offset, on_gpu: bool):
+def _combine_norm_operands(slot_out, topk_weights, topk_ids, num_experts, weight, eps, fmt, residual, weight_offset, on_gpu: bool,
+                           hadamard: int = 0):
     """The argument checks of moe_combine_rmsnorm and of its CPU twin, stated once -> (T, topk, k)."""
     where = "GPU" if on_gpu else "CPU"
     _check(fmt is None or fmt in _QFORMATS, "fmt must be None, 'mxfp8', 'mxfp6' or 'mxfp4'")
+    _check(_hadamard_block(hadamard) == 0 or fmt is not None, "hadamard needs a fmt: it rotates the quantised output only")
+    _check(hadamard == 0 or fmt != "mxfp6", _HADAMARD_FP6)
     _check(1 <= int(num_experts) <= _lib.PETIT_MOE_MAX_EXPERTS, f"num_experts must be in 1..{_lib.PETIT_MOE_MAX_EXPERTS}, got {num_experts}")
     _check(topk_ids.is_cuda == on_gpu and topk_ids.dim() == 2 and topk_ids.is_contiguous() and topk_ids.dtype in (torch.int32, torch.int64),
            f"topk_ids must be a contiguous int32 / int64 [num_tokens, topk] {where} tensor")
@@ -1288,35 +1305,37 @@ def _combine_norm_outputs(slot_out, T, k, fmt, residual, want_h, want_y, inplace
     return qa, res_out, y16
 
 
-def _combine_norm_result(rc, name, dtype, T, topk, k, num_experts, fmt, qa, res_out, y16):
+def _combine_norm_result(rc, name, dtype, T, topk, k, num_experts, fmt, qa, res_out, y16, hadamard: int = 0):
     if rc == _lib.PETIT_ERROR_PROBLEM_SHAPE:
         raise RuntimeError(f"Incompatible problem shape (num_tokens={T}, topk={topk}, k={k}, num_experts={num_experts})")
     if rc == _lib.PETIT_ERROR_KERNEL_SHAPE:
         raise RuntimeError(f"No kernel implementation for k={k} (the fused norm holds a row of at most 16384 elements).")
     _raise_on(rc, name)
-    out = () if qa is None else (QuantizedActivations(qa, T, k, fmt, dtype),)
+    out = () if qa is None else (QuantizedActivations(qa, T, k, fmt, dtype, hadamard),)
     out += tuple(t for t in (res_out, y16) if t is not None)
     return out[0] if len(out) == 1 else out
 
 
 def moe_combine_rmsnorm(slot_out: torch.Tensor, topk_weights: torch.Tensor, topk_ids: torch.Tensor, num_experts: int, weight: torch.Tensor,
                         eps: float = 1e-6, fmt: str = None, *, residual: torch.Tensor = None, weight_offset: float = 0.0,
-                        return_normed: bool = None, return_hidden: bool = None, inplace_residual: bool = False):
+                        return_normed: bool = None, return_hidden: bool = None, inplace_residual: bool = False, hadamard: int = 0):
     """moe_combine, the residual add, the RMSNorm and (with fmt) quantize_activations in ONE launch (include/petit_amd.h "Top-k combine into the
     norm"): c = moe_combine(slot_out, topk_weights, topk_ids, num_experts), h = c (+ residual), y = RMSNorm(h) * (weight + weight_offset) -- bit
-    for bit moe_combine -> rmsnorm_quantize(residual=...) where that chain takes the call.  fmt None: no quantised output, any k % 8 == 0.
-    Returns, in this order and alone when it is one: the QuantizedActivations when fmt is given; h when return_hidden (default: when a residual
+    for bit moe_combine -> rmsnorm_quantize(residual=..., hadamard=hadamard) where that chain takes the call.  fmt None: no quantised output, any
+    k % 8 == 0.  hadamard = 32 / 128 (fmt 'mxfp8' / 'mxfp4'): the quantised rows are rotated as quantize_activations(y, fmt, hadamard) does; h and
+    y stay unrotated.  Returns, in this order and alone when it is one: the QuantizedActivations when fmt is given; h when return_hidden (default: when a residual
     is given; without a residual h is the combined layer output; `residual` itself, written in place, with inplace_residual=True); the 16-bit y
     when return_normed (default, and always: when fmt is None)."""
-    T, topk, k = _combine_norm_operands(slot_out, topk_weights, topk_ids, num_experts, weight, eps, fmt, residual, weight_offset, on_gpu=True)
+    T, topk, k = _combine_norm_operands(slot_out, topk_weights, topk_ids, num_experts, weight, eps, fmt, residual, weight_offset, on_gpu=True,
+                                        hadamard=hadamard)
     want_h, want_y = _combine_norm_returns(fmt, residual, return_normed, return_hidden, inplace_residual)
     qa, res_out, y16 = _combine_norm_outputs(slot_out, T, k, fmt, residual, want_h, want_y, inplace_residual)
     with torch.cuda.device(slot_out.device):
-        rc = _lib.lib.petit_moe_combine_rmsnorm(_opt_ptr(qa), _opt_ptr(y16), _opt_ptr(res_out), _ptr(slot_out), _ptr(topk_weights), _ptr(topk_ids),
-                                                int(topk_ids.dtype == torch.int64), _opt_ptr(residual), _ptr(weight), float(eps),
-                                                float(weight_offset), T, topk, k, int(num_experts), _a_type(slot_out.dtype),
-                                                _QFORMATS[fmt] if fmt else 0, _stream(slot_out))
-    return _combine_norm_result(rc, "moe_combine_rmsnorm", slot_out.dtype, T, topk, k, num_experts, fmt, qa, res_out, y16)
+        rc = _lib.lib.petit_moe_combine_rmsnorm_rot(_opt_ptr(qa), _opt_ptr(y16), _opt_ptr(res_out), _ptr(slot_out), _ptr(topk_weights),
+                                                    _ptr(topk_ids), int(topk_ids.dtype == torch.int64), _opt_ptr(residual), _ptr(weight),
+                                                    float(eps), float(weight_offset), T, topk, k, int(num_experts), _a_type(slot_out.dtype),
+                                                    _QFORMATS[fmt] if fmt else 0, hadamard, _stream(slot_out))  # (block 0: the unrotated entry)
+    return _combine_norm_result(rc, "moe_combine_rmsnorm", slot_out.dtype, T, topk, k, num_experts, fmt, qa, res_out, y16, hadamard)
 
 
 _SCORINGS = {"softmax": _lib.PETIT_ROUTE_SOFTMAX, "sigmoid": _lib.PETIT_ROUTE_SIGMOID}
@@ -1645,11 +1664,12 @@ def nvfp4_native_images(B: torch.Tensor, s: torch.Tensor, num_experts: int, size
 
 def _mul_native_moe(kind: str, A, B, s, global_scales, expert_offsets, size_m, size_n, size_k, num_experts, a_row_index=None, c_row_index=None,
                     c_rows=None, solution_id=SOLUTION_AUTO_NATIVE_MXFP8, bias=None, activation=None, out_quantized=None, transient=False,
-                    workspace=None):
+                    workspace=None, out_hadamard=0):
     """The routed-expert launch on the native class (petit_gemm_native_moe).  A: 16-bit [a_rows, size_k] (gathered through a_row_index and
     quantised by the call: two launches) or QuantizedActivations of the size_m grouped rows (one launch).  Output: 16-bit [c_rows, n_out], row
     c_row_index[r] for grouped row r (None: the identity), or with out_quantized (activation='silu_mul') QuantizedActivations of the grouped
-    [size_m, size_n / 2] rows for the next launch.  transient (kind 'nv'): petit_gemm_native_moe_transient on the packed B / s; workspace: the caller's
+    [size_m, size_n / 2] rows for the next launch, rotated by the Hadamard block out_hadamard (32 / 128, as mul_mxfp4_native) when that is
+    set.  transient (kind 'nv'): petit_gemm_native_moe_transient on the packed B / s; workspace: the caller's
     scratch for it (a 256-byte aligned uint8 tensor of at least the queried bytes) instead of one from the allocator."""
     a_t, dtype, a_fmt = _activation_operand(A, size_m, size_k)
     fn, workspace_bytes, name = ((_lib.lib.petit_gemm_native_moe_transient, _lib.lib.petit_gemm_native_moe_transient_workspace_bytes,
@@ -1668,13 +1688,14 @@ def _mul_native_moe(kind: str, A, B, s, global_scales, expert_offsets, size_m, s
     act = _activation(activation)
     out_fmt = _quantized_format(out_quantized, "out_quantized must be None, 'mxfp8', 'mxfp6' or 'mxfp4'")
     _check(not out_fmt or (act and c_row_index is None), "out_quantized needs activation='silu_mul' or 'swiglu_oai' and no c_row_index")
+    out_block = _out_hadamard(out_hadamard, out_quantized)
     epi = _epilogue(bias, act, dev, dtype, E * size_n,
                     "bias must be a contiguous [num_experts, size_n] tensor of the activation dtype on the same device")
     hints = _hints(kind, dtype)
     sid = C.c_uint64(_c_solution_id(solution_id, native_ok=True))
-    na = _lib.NativeArgs(C.sizeof(_lib.NativeArgs), a_fmt, out_fmt, 0)
+    na = _lib.NativeArgs(C.sizeof(_lib.NativeArgs), a_fmt, out_fmt, out_block)
     c_rows = size_m if out_fmt or c_rows is None or c_rows < 0 else int(c_rows)
-    c, result = _native_output(c_rows, size_m, size_n // 2 if act else size_n, out_quantized, dtype, dev)
+    c, result = _native_output(c_rows, size_m, size_n // 2 if act else size_n, out_quantized, dtype, dev, out_block)
     ws_bytes = int(workspace_bytes(C.byref(hints), E, size_m, size_n, size_k, sid, epi, C.byref(na)))
     if workspace is not None:
         _check(transient and workspace.is_cuda and workspace.device == dev and workspace.dtype == torch.uint8 and workspace.is_contiguous() and
@@ -1691,27 +1712,27 @@ def _mul_native_moe(kind: str, A, B, s, global_scales, expert_offsets, size_m, s
 
 
 def mul_mxfp4_native_moe(A, B, s, global_scales, expert_offsets, size_m, size_n, size_k, num_experts, a_row_index=None, c_row_index=None,
-                         c_rows=None, solution_id=SOLUTION_AUTO_NATIVE_MXFP8, bias=None, activation=None, out_quantized=None):
+                         c_rows=None, solution_id=SOLUTION_AUTO_NATIVE_MXFP8, bias=None, activation=None, out_quantized=None, out_hadamard=0):
     return _mul_native_moe("mx", A, B, s, global_scales, expert_offsets, size_m, size_n, size_k, num_experts, a_row_index, c_row_index, c_rows,
-                           solution_id, bias, activation, out_quantized)
+                           solution_id, bias, activation, out_quantized, out_hadamard=out_hadamard)
 
 
 def mul_nvfp4_native_moe(A, images, global_scales, expert_offsets, size_m, size_n, size_k, num_experts, a_row_index=None, c_row_index=None,
-                         c_rows=None, solution_id=SOLUTION_AUTO_NATIVE_MXFP8, bias=None, activation=None, out_quantized=None):
+                         c_rows=None, solution_id=SOLUTION_AUTO_NATIVE_MXFP8, bias=None, activation=None, out_quantized=None, out_hadamard=0):
     return _mul_native_moe("nv", A, images, None, global_scales, expert_offsets, size_m, size_n, size_k, num_experts, a_row_index, c_row_index,
-                           c_rows, solution_id, bias, activation, out_quantized)
+                           c_rows, solution_id, bias, activation, out_quantized, out_hadamard=out_hadamard)
 
 
 def mul_nvfp4_native_moe_transient(A, B, s, global_scales, expert_offsets, size_m, size_n, size_k, num_experts, a_row_index=None,
                                    c_row_index=None, c_rows=None, solution_id=SOLUTION_AUTO_NATIVE_MXFP8, bias=None, activation=None,
-                                   out_quantized=None, workspace=None):
+                                   out_quantized=None, workspace=None, out_hadamard=0):
     """mul_nvfp4_native_moe WITHOUT resident images (petit_gemm_native_moe_transient): B / s are the experts' stacked packed tensors, what
     mul_nvfp4_a16_moe takes; the call builds the images of the experts that have rows into a workspace it takes from torch's caching allocator
     (one launch), then runs the native launch on them -- or into `workspace`, a uint8 tensor of at least
     nvfp4_native_moe_transient_workspace_bytes(...) that several calls may share one after the other.  Bit for bit mul_nvfp4_native_moe on
     nvfp4_native_images(B, s, ...)."""
     return _mul_native_moe("nv", A, B, s, global_scales, expert_offsets, size_m, size_n, size_k, num_experts, a_row_index, c_row_index, c_rows,
-                           solution_id, bias, activation, out_quantized, transient=True, workspace=workspace)
+                           solution_id, bias, activation, out_quantized, transient=True, workspace=workspace, out_hadamard=out_hadamard)
 
 
 def nvfp4_native_moe_transient_workspace_bytes(num_experts, size_m, size_n, size_k, solution_id=SOLUTION_AUTO_NATIVE_MXFP8, dtype=torch.bfloat16,
