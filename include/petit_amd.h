@@ -575,6 +575,45 @@ int petit_quantize_weights_host(const void *w, int a_type, int b_type, unsigned 
                                 void *out_b, void *out_scales, float *out_gs);
 
 /*
+ * MXFP6 weights on the native class (no counterpart in the reference).
+ *
+ * The MFMA-native image of "NVFP4 weights on the native class" ("petit-cdna4-nv6/1", csrc/layout.h) holds FP6 e2m3 elements and one E8M0 scale
+ * per 32 k: byte for byte the content of an OCP MXFP6 (e2m3) weight tensor.  These entries write that image WITHOUT a 4-bit rounding in
+ * between -- from 16-bit weights, or from an MXFP6 checkpoint -- at 6.25 bits per weight.  There are no GEMM entries of their own: the images go
+ * to petit_gemm_nvfp4_native, petit_gemm_nvfp4_native_invariant, petit_gemm_native_moe (b_type NVFP4) and
+ * petit_gemm_nvfp4_native_moe_invariant with global_scale(s) = 1.0f, and run the same kernels at the same rate as an NVFP4-derived image.
+ *
+ * Which M: an image named per call (the four entries above) runs every M the native class takes (m <= 65535, m * k < 2^32) as ONE launch in
+ * the class -- the bulk + tail row split of a ragged prefill M belongs to the attached-image path (petit_nvfp4_native_attach), whose tail runs
+ * the exact class on the PACKED tensors; an MXFP6 image has no packed tensors to attach to, so that path and petit_gemm_nvfp4_native_transient
+ * are not for it.
+ *
+ * The rule, per 32 consecutive k of a weight row (it is the MXFP6 activation quantiser's, "petit-qact/1": one MXFP6 rule in the library):
+ *     scale     amax = max |w| of the block;  E = floor(log2 amax) - 2;  byte = E + 127 clamped into [1, 254].  An all-zero block: byte 127.
+ *     element   round to nearest even of w / 2^(byte - 127) on the e2m3 grid {0, 1/8 .. 7/8, 1 .. 7.5}, saturating at +-7.5 (only a maximum
+ *               above 7.5 x 2^E, which rounds up across the power of two, and its like saturate); the sign is kept, on a zero too.
+ *   Non-finite weights are the caller's error: unspecified values, never a fault.
+ *
+ *   petit_quantize_weights_mxfp6(w, a_type, num_experts, n, k, images, stream)
+ *       w       [num_experts][n][k], PETIT_DTYPE_BF16 / _FP16, contiguous, 16-byte aligned device memory; n % 16 == 0, k % 256 == 0
+ *       images  num_experts images back to back, expert e's at byte e * petit_nvfp4_native_image_bytes(k, n) (what petit_nvfp4_native_images
+ *               lays out and the MoE entries read; num_experts = 1: the image of the dense entries); 256-byte aligned.  Every byte is written:
+ *               rows >= n of the last 32-row block are zero elements with scale byte 127.
+ *   petit_mxfp6_native_images(images, elems, scales, num_experts, n, k, stream)
+ *       elems   [num_experts][n][3 k / 4] bytes: element e of a row at bits [6 e, 6 e + 6) of the row's little-endian bit stream (OCP MXFP6 e2m3,
+ *               32 elements = 24 bytes); 16-byte aligned.  scales [num_experts][n][k / 32] E8M0 bytes.  Copied, never rounded: the image
+ *               dequantises (petit_nvfp4_native_image_dequant_host) to exactly the tensor's values.
+ *   ..._host    the CPU twins on host memory, bit-identical (offline conversion).
+ * Errors, all before any launch and in this order: PETIT_ERROR_BAD_ARGUMENT for an a_type outside the above; PETIT_ERROR_PROBLEM_SHAPE for
+ * num_experts outside 1 .. PETIT_MOE_MAX_EXPERTS, n % 16, k % 256 or an element part of 2^32 bytes or more; n or k == 0 returns PETIT_OK;
+ * PETIT_ERROR_BAD_ARGUMENT for misaligned or null pointers.  One launch, no scratch, no host sync: capturable; a replay converts what w holds then.
+ */
+int petit_quantize_weights_mxfp6(const void *w, int a_type, unsigned num_experts, unsigned n, unsigned k, void *images, void *stream);
+int petit_quantize_weights_mxfp6_host(const void *w, int a_type, unsigned num_experts, unsigned n, unsigned k, void *images);
+int petit_mxfp6_native_images(void *images, const void *elems, const void *scales, unsigned num_experts, unsigned n, unsigned k, void *stream);
+int petit_mxfp6_native_images_host(void *images, const void *elems, const void *scales, unsigned num_experts, unsigned n, unsigned k);
+
+/*
  * Grouped launch (no counterpart in the reference): up to PETIT_GROUP_MAX weight matrices that share the activation rows --
  * q / k / v (or their tensor-parallel shards) kept as separate tensors, gate and up, the experts a token routes to -- in ONE
  * kernel launch: c_i[m][n_i] = a[m][k] . dequant(b_i)[n_i][k]^T * (*global_scale_i) (+ bias_i).  At decode batch sizes a

@@ -27,6 +27,9 @@ FLAGS = ["-O3", "-std=c++20", "-fPIC", f"--offload-arch={ARCH}", "-Wall", "-Wno-
 if not os.environ.get("PETIT_AMD_NO_KERNARG_PRELOAD"):
     FLAGS += ["-mllvm", "-amdgpu-kernarg-preload-count=16"]
 
+# per translation unit: new code is compiled without the packed-f32 VALU forms (v_pk_{add,mul,fma}_f32)
+EXTRA_FLAGS = {"mxfp6_weights.hip": ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"]}
+
 
 def sources():
     # the slowest translation units first (by the size of their previous object file), so that the tail of a parallel build is short
@@ -46,7 +49,7 @@ def compile_one(src: Path, force: bool, hdr_mtime: float) -> Path:
     obj = OBJ / (src.stem + ".o")
     if not force and obj.exists() and obj.stat().st_mtime > max(src.stat().st_mtime, hdr_mtime):
         return obj
-    cmd = ["hipcc", *FLAGS, "-c", str(src), "-o", str(obj)]
+    cmd = ["hipcc", *FLAGS, *EXTRA_FLAGS.get(src.name, []), "-c", str(src), "-o", str(obj)]
     r = subprocess.run(cmd, capture_output=True, text=True)
     if r.returncode != 0:
         sys.stderr.write(r.stdout + r.stderr)

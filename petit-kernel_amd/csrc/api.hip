@@ -152,6 +152,19 @@ int petit_quantize_weights_host(const void *w, int a_type, int b_type, unsigned 
                                 void *out_b, void *out_scales, float *out_gs) {
     return quantize_weights_host(w, a_type, canonical_b_type(b_type), num_experts, n, k, gs_in, out_b, out_scales, out_gs);
 }
+// MXFP6 weights into the native image (mxfp6_weights.hip makes every check: the device forms and their host twins refuse the same calls)
+int petit_quantize_weights_mxfp6(const void *w, int a_type, unsigned num_experts, unsigned n, unsigned k, void *images, void *stream) {
+    return mxfp6_quantize_weights(w, a_type, num_experts, n, k, images, (hipStream_t)stream);
+}
+int petit_quantize_weights_mxfp6_host(const void *w, int a_type, unsigned num_experts, unsigned n, unsigned k, void *images) {
+    return mxfp6_quantize_weights_host(w, a_type, num_experts, n, k, images);
+}
+int petit_mxfp6_native_images(void *images, const void *elems, const void *scales, unsigned num_experts, unsigned n, unsigned k, void *stream) {
+    return mxfp6_native_images(images, elems, scales, num_experts, n, k, (hipStream_t)stream);
+}
+int petit_mxfp6_native_images_host(void *images, const void *elems, const void *scales, unsigned num_experts, unsigned n, unsigned k) {
+    return mxfp6_native_images_host(images, elems, scales, num_experts, n, k);
+}
 
 int petit_nvfp4_native_attach(const void *b, const void *image) {
     if (!b || ((uintptr_t)image & 255))

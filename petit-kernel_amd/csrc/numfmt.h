@@ -162,7 +162,8 @@ PETIT_HD double e8m0_f64(unsigned b) { return (double)e8m0_f32(b); }
 
 // The block-scale rule of the quantised activations: the E8M0 byte of 2^(E - emax_elem), E the exponent of the block maximum (OCP MX),
 // emax_elem = 7 for e4m3 as the native kernels use it (the maximum lands in [128, 256) <= 448), 2 for e2m3 (in [4, 8), above 7.5 saturates)
-// and e2m1 (above 6 saturates); a zero block: byte 127; never byte 0 or 255.
+// and e2m1 (above 6 saturates); a zero block: byte 127; never byte 0 or 255.  ACT = 6 is also the rule of the MXFP6 WEIGHT quantiser
+// (mxfp6_weights.hip): the library has one MXFP6 rule.
 template <int ACT> PETIT_HD unsigned act_scale_byte(float amax) {
     constexpr unsigned kEmax = ACT == 8 ? 7u : 2u;
     const unsigned ebits = (f32_bits(amax) >> 23) & 0xffu;

@@ -196,6 +196,12 @@ int quantize_weights(const void *w, int a_type, int b_type, unsigned num_experts
                      void *out_scales, float *out_gs, void *workspace, uint64_t workspace_bytes, hipStream_t stream);
 int quantize_weights_host(const void *w, int a_type, int b_type, unsigned num_experts, unsigned n, unsigned k, const float *gs_in, void *out_b,
                           void *out_scales, float *out_gs);
+// mxfp6_weights.hip: num_experts images ("petit-cdna4-nv6/1") back to back from 16-bit weights [E][n][k] (quantised: include/petit_amd.h "MXFP6
+// weights on the native class") or from an OCP MXFP6 tensor (elems [E][n][3 k / 4], scales [E][n][k / 32]; no rounding); host twins, bit-identical
+int mxfp6_quantize_weights(const void *w, int a_type, unsigned num_experts, unsigned n, unsigned k, void *images, hipStream_t stream);
+int mxfp6_quantize_weights_host(const void *w, int a_type, unsigned num_experts, unsigned n, unsigned k, void *images);
+int mxfp6_native_images(void *images, const void *elems, const void *scales, unsigned num_experts, unsigned n, unsigned k, hipStream_t stream);
+int mxfp6_native_images_host(void *images, const void *elems, const void *scales, unsigned num_experts, unsigned n, unsigned k);
 // rmsnorm_quant.hip: (residual add +) RMSNorm -> "petit-qact/1" bytes in one launch (include/petit_amd.h "RMSNorm into quantised activations");
 // host twin, bit-identical.  Both make every check of the contract.
 int rmsnorm_quantize(void *qa, void *y16, void *residual_out, const void *x, const void *residual, const void *weight, float eps,

@@ -203,6 +203,63 @@ std::tuple<at::Tensor, at::Tensor, at::Tensor> quantize_weights_meta(const at::T
     return {q.b, q.s, q.gs};
 }
 
+// MXFP6 weights into the native image (petit_quantize_weights_mxfp6 / petit_mxfp6_native_images); the same checks and texts as
+// petit_kernel/ops.py _mxfp6_quantize_operands / _mxfp6_ingest_operands.  mxfp6_images makes the output for the real ops and their Meta twins.
+at::Tensor mxfp6_images(const at::Tensor &like, int64_t E, int64_t n, int64_t k) {
+    TORCH_CHECK(E >= 1 && E <= PETIT_MOE_MAX_EXPERTS, "num_experts must be in 1..", PETIT_MOE_MAX_EXPERTS, ", got ", E);
+    TORCH_CHECK(k % (2 * kLayoutM) == 0, "size_k = ", k, " is not divisible by tile_k_size = ", 2 * kLayoutM);
+    TORCH_CHECK(n % kLayoutN == 0, "size_n = ", n, " is not divisible by tile_n_size = ", kLayoutN);
+    const int64_t per = (int64_t)petit_nvfp4_native_image_bytes((unsigned)k, (unsigned)n);
+    TORCH_CHECK(per > 0, "no native image for size_n=", n, ", size_k=", k);
+    return at::empty({E * per}, like.options().dtype(at::kByte));
+}
+at::Tensor quantize_mxfp6_impl(const at::Tensor &w, bool real) {
+    TORCH_CHECK(w.scalar_type() == at::kBFloat16 || w.scalar_type() == at::kHalf, "w must be bfloat16 or float16.");
+    TORCH_CHECK(w.dim() == 2 || w.dim() == 3, "w must be [size_n, size_k] or [num_experts, size_n, size_k]");
+    if (real) {
+        TORCH_CHECK(w.is_cuda(), "w is not on GPU");
+        TORCH_CHECK(w.is_contiguous(), "w is not contiguous");
+    }
+    const int64_t E = w.dim() == 3 ? w.size(0) : 1, n = w.size(-2), k = w.size(-1);
+    at::Tensor images = mxfp6_images(w, E, n, k);
+    if (!real)
+        return images;
+    const c10::hip::HIPGuardMasqueradingAsCUDA guard(w.device());
+    const int rc = petit_quantize_weights_mxfp6(w.data_ptr(), a_type_of(w.scalar_type()), (unsigned)E, (unsigned)n, (unsigned)k, images.data_ptr(),
+                                                stream_of(w));
+    TORCH_CHECK(rc != PETIT_ERROR_PROBLEM_SHAPE, "Incompatible problem shape (num_experts=", E, ", n=", n, ", k=", k, ")");
+    TORCH_CHECK(rc == PETIT_OK, "quantize_mxfp6: ", petit_error_string(rc));
+    return images;
+}
+at::Tensor quantize_mxfp6(const at::Tensor &w) { return quantize_mxfp6_impl(w, true); }
+at::Tensor quantize_mxfp6_meta(const at::Tensor &w) { return quantize_mxfp6_impl(w, false); }
+at::Tensor mxfp6_native_image_impl(const at::Tensor &elems, const at::Tensor &scales, int64_t n, int64_t k, bool real) {
+    TORCH_CHECK(elems.scalar_type() == at::kByte && scales.scalar_type() == at::kByte && scales.device() == elems.device() &&
+                    (!real || (elems.is_cuda() && elems.is_contiguous() && scales.is_contiguous())),
+                "elems and scales must be contiguous uint8 GPU tensors on one device");
+    TORCH_CHECK((elems.dim() == 2 || elems.dim() == 3) && scales.dim() == elems.dim(),
+                "elems must be [size_n, 3 * size_k / 4] or [num_experts, size_n, 3 * size_k / 4]");
+    const int64_t E = elems.dim() == 3 ? elems.size(0) : 1;
+    at::Tensor images = mxfp6_images(elems, E, n, k);
+    TORCH_CHECK(elems.size(-2) == n && elems.size(-1) == k / 4 * 3 && scales.size(-2) == n && scales.size(-1) == k / 32 &&
+                    (elems.dim() == 2 || scales.size(0) == E),
+                "elems / scales do not hold [size_n, size_k] MXFP6 weights (24 bytes and one scale per 32 k)");
+    if (!real)
+        return images;
+    const c10::hip::HIPGuardMasqueradingAsCUDA guard(elems.device());
+    const int rc = petit_mxfp6_native_images(images.data_ptr(), elems.data_ptr(), scales.data_ptr(), (unsigned)E, (unsigned)n, (unsigned)k,
+                                             stream_of(elems));
+    TORCH_CHECK(rc != PETIT_ERROR_PROBLEM_SHAPE, "Incompatible problem shape (num_experts=", E, ", n=", n, ", k=", k, ")");
+    TORCH_CHECK(rc == PETIT_OK, "mxfp6_native_image: ", petit_error_string(rc));
+    return images;
+}
+at::Tensor mxfp6_native_image(const at::Tensor &elems, const at::Tensor &scales, int64_t n, int64_t k) {
+    return mxfp6_native_image_impl(elems, scales, n, k, true);
+}
+at::Tensor mxfp6_native_image_meta(const at::Tensor &elems, const at::Tensor &scales, int64_t n, int64_t k) {
+    return mxfp6_native_image_impl(elems, scales, n, k, false);
+}
+
 // block-Hadamard rotation to 16 bit (petit_hadamard_rows); the same checks and texts as petit_kernel/ops.py _hadamard_operands
 void hadamard_rotate_out(const at::Tensor &x, int64_t block, int64_t log2_scale, at::Tensor out) {
     TORCH_CHECK(block == 32 || block == 128, "block must be 32 or 128");
@@ -1104,6 +1161,8 @@ TORCH_LIBRARY(petit_kernel, m) {
     m.def("process_nvfp4_scales(Tensor scales, int size_n, int size_k) -> Tensor");
     m.def("process_mxfp4_scales(Tensor scales, int size_n, int size_k) -> Tensor");
     m.def("quantize_weights(Tensor w, int b_type, Tensor? global_scale=None) -> (Tensor, Tensor, Tensor)");
+    m.def("quantize_mxfp6(Tensor w) -> Tensor");
+    m.def("mxfp6_native_image(Tensor elems, Tensor scales, int size_n, int size_k) -> Tensor");
     m.def("hadamard_rotate(Tensor x, int block, int log2_scale=0) -> Tensor");
     m.def("hadamard_rotate_out(Tensor x, int block, int log2_scale, Tensor(a!) out) -> ()");
     m.def("mul_nvfp4_a16(Tensor A, Tensor B, Tensor s, Tensor global_scale, int size_m, int size_n, int size_k, int solution_id, "
@@ -1178,6 +1237,8 @@ TORCH_LIBRARY(petit_kernel, m) {
     m.impl("process_nvfp4_scales", &process_nvfp4_scales);      \
     m.impl("process_mxfp4_scales", &process_mxfp4_scales);      \
     m.impl("quantize_weights", &quantize_weights);              \
+    m.impl("quantize_mxfp6", &quantize_mxfp6);                  \
+    m.impl("mxfp6_native_image", &mxfp6_native_image);          \
     m.impl("hadamard_rotate", &hadamard_rotate);                \
     m.impl("hadamard_rotate_out", &hadamard_rotate_out);        \
     m.impl("mul_nvfp4_a16", &mul_nvfp4_a16);                    \
@@ -1219,6 +1280,8 @@ TORCH_LIBRARY_IMPL(petit_kernel, Meta, m) {
     m.impl("process_nvfp4_scales", &process_nvfp4_scales_meta);
     m.impl("process_mxfp4_scales", &process_mxfp4_scales_meta);
     m.impl("quantize_weights", &quantize_weights_meta);
+    m.impl("quantize_mxfp6", &quantize_mxfp6_meta);
+    m.impl("mxfp6_native_image", &mxfp6_native_image_meta);
     m.impl("hadamard_rotate", &hadamard_rotate_meta);
     m.impl("hadamard_rotate_out", &hadamard_rotate_out_meta);
     m.impl("mul_nvfp4_a16", &mul_a16_meta);

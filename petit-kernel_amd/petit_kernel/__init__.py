@@ -80,6 +80,18 @@ def quantize_mxfp4(w: torch.Tensor, hadamard: int = 0):
     return _impl.quantize_mxfp4(w, hadamard)
 
 
+def quantize_mxfp6(w: torch.Tensor, hadamard: int = 0) -> torch.Tensor:
+    # 16-bit weights [N, K] or [E, N, K] -> their MFMA-native image(s) in MXFP6 (e2m3, one e8m0 scale per 32 k; include/petit_amd.h "MXFP6
+    # weights on the native class"): uint8, E images back to back, for mul_nvfp4_native / _invariant / _moe / _moe_invariant with global
+    # scale(s) 1.0 -- 4 significant bits per weight where the FP4 formats keep 2.  Host twin: offline.quantize_mxfp6_cpu
+    return _impl.quantize_mxfp6(w, hadamard)
+
+
+def mxfp6_native_image(elems: torch.Tensor, scales: torch.Tensor, size_n: int, size_k: int) -> torch.Tensor:
+    # an OCP MXFP6 (e2m3) checkpoint tensor (uint8 [N, 3 K / 4] or [E, N, 3 K / 4] and e8m0 [.., N, K / 32]) -> the same image(s), no rounding
+    return _impl.mxfp6_native_image(elems, scales, size_n, size_k)
+
+
 def mxfp4_scales_in_fp16_range(raw_scales: torch.Tensor) -> bool:
     """A diagnostic, not an input of any call: True when every e8m0 byte of the RAW (unprocessed) MXFP4 scale tensor lies in 114..140, i.e. when
     fp16 activations run the single-MFMA body in every wave (a wave that meets a byte outside that range finishes its K range in the exact
@@ -428,6 +440,8 @@ __all__ = [
     "process_mxfp4_scales",
     "quantize_nvfp4",
     "quantize_mxfp4",
+    "quantize_mxfp6",
+    "mxfp6_native_image",
     "hadamard_rotate",
     "mul_nvfp4_a16",
     "mul_mxfp4_a16",

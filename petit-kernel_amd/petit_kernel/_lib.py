@@ -184,6 +184,10 @@ _SIGNATURES = {
     "petit_quantize_weights_workspace_bytes": (C.c_uint64, [C.c_int, C.c_uint, C.c_int]),
     "petit_quantize_weights": (C.c_int, [C.c_void_p, C.c_int, C.c_int] + [C.c_uint] * 3 + [C.c_void_p] * 5 + [C.c_uint64, C.c_void_p]),
     "petit_quantize_weights_host": (C.c_int, [C.c_void_p, C.c_int, C.c_int] + [C.c_uint] * 3 + [C.c_void_p] * 4),
+    "petit_quantize_weights_mxfp6": (C.c_int, [C.c_void_p, C.c_int] + [C.c_uint] * 3 + [C.c_void_p] * 2),
+    "petit_quantize_weights_mxfp6_host": (C.c_int, [C.c_void_p, C.c_int] + [C.c_uint] * 3 + [C.c_void_p]),
+    "petit_mxfp6_native_images": (C.c_int, [C.c_void_p] * 3 + [C.c_uint] * 3 + [C.c_void_p]),
+    "petit_mxfp6_native_images_host": (C.c_int, [C.c_void_p] * 3 + [C.c_uint] * 3),
     "petit_nvfp4_native_attach": (C.c_int, [C.c_void_p, C.c_void_p]),
     "petit_nvfp4_native_attached": (C.c_void_p, [C.c_void_p]),
     "petit_gemm_nvfp4_native": (C.c_int, [C.c_void_p] * 4 + [C.c_uint] * 3 + [C.POINTER(SolutionHints), C.c_uint64, C.POINTER(Epilogue),

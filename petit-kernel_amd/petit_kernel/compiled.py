@@ -95,6 +95,14 @@ def quantize_mxfp4(w, hadamard=0):
     return torch.ops.petit_kernel.quantize_weights(_rotated_weights(w, hadamard, hadamard_rotate), _lib.CXX_DTYPE_MXFP4_E2M1, None)
 
 
+def quantize_mxfp6(w, hadamard=0):
+    return torch.ops.petit_kernel.quantize_mxfp6(_rotated_weights(w, hadamard, hadamard_rotate))
+
+
+def mxfp6_native_image(elems, scales, size_n, size_k):
+    return torch.ops.petit_kernel.mxfp6_native_image(elems, scales, int(size_n), int(size_k))
+
+
 def mul_nvfp4_a16(A, B, s, global_scale, size_m, size_n, size_k, solution_id, bias=None, activation=None):
     return torch.ops.petit_kernel.mul_nvfp4_a16(A, B, s, global_scale, size_m, size_n, size_k, _sid(solution_id), bias, _act(activation))
 

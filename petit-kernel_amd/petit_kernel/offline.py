@@ -15,6 +15,7 @@ from . import _lib
 from .ops import _B_TYPES, _LAYOUT_M, _LAYOUT_N, _PACK, _QFORMATS, _a_type, _check, _opt_ptr, _ptr, _quantize_operands, _quantize_outputs, _raise_on
 from .ops import _raise_quantize, _rmsnorm_operands, _rmsnorm_outputs, _rmsnorm_result
 from .ops import QuantizedActivations, _HADAMARD_FP6, _hadamard_block, _hadamard_operands, _rotated_weights
+from .ops import _mxfp6_ingest_operands, _mxfp6_quantize_operands
 from .ops import _combine_norm_operands, _combine_norm_outputs, _combine_norm_result, _combine_norm_returns
 
 
@@ -93,6 +94,22 @@ def quantize_nvfp4_cpu(w: torch.Tensor, global_scale: torch.Tensor = None, hadam
 def quantize_mxfp4_cpu(w: torch.Tensor, hadamard: int = 0):
     """CPU twin of petit_kernel.quantize_mxfp4."""
     return _quantize_weights_cpu("mx", _rotated_weights(w, hadamard, hadamard_rotate_cpu))
+
+
+def quantize_mxfp6_cpu(w: torch.Tensor, hadamard: int = 0) -> torch.Tensor:
+    """CPU twin of petit_kernel.quantize_mxfp6: bf16 / fp16 [N, K] or [E, N, K] -> the MXFP6 native image(s), bit-identical to the device's."""
+    w = _rotated_weights(w, hadamard, hadamard_rotate_cpu)
+    E, n, k, images = _mxfp6_quantize_operands(w, on_gpu=False)
+    _raise_quantize(_lib.lib.petit_quantize_weights_mxfp6_host(w.data_ptr(), _a_type(w.dtype), E, n, k, images.data_ptr()), "quantize_mxfp6_cpu", E, n, k)
+    return images
+
+
+def mxfp6_native_image_cpu(elems: torch.Tensor, scales: torch.Tensor, size_n: int, size_k: int) -> torch.Tensor:
+    """CPU twin of petit_kernel.mxfp6_native_image: an OCP MXFP6 (e2m3) tensor -> the native image(s), no rounding."""
+    E, images = _mxfp6_ingest_operands(elems, scales, size_n, size_k, on_gpu=False)
+    _raise_quantize(_lib.lib.petit_mxfp6_native_images_host(images.data_ptr(), elems.data_ptr(), scales.data_ptr(), E, size_n, size_k),
+                    "mxfp6_native_image_cpu", E, size_n, size_k)
+    return images
 
 
 # --- the activation quantiser, on the CPU (petit_quantize_activations_host / _rot_host) -------------------------------------------------------------

@@ -277,6 +277,63 @@ def quantize_mxfp4(w: torch.Tensor, hadamard: int = 0):
     return _quantize_weights("mx", _rotated_weights(w, hadamard, hadamard_rotate))
 
 
+# --- MXFP6 weights into the native image (include/petit_amd.h "MXFP6 weights on the native class"; no counterpart in the reference) ---------
+
+def _mxfp6_image_bytes(num_experts: int, size_n: int, size_k: int) -> int:
+    """Bytes of one image of the shape, checked by the rules quantize_mxfp6 / mxfp6_native_image and their CPU twins share."""
+    _check(1 <= num_experts <= _lib.PETIT_MOE_MAX_EXPERTS, f"num_experts must be in 1..{_lib.PETIT_MOE_MAX_EXPERTS}, got {num_experts}")
+    _check(size_k % (2 * _LAYOUT_M) == 0, f"size_k = {size_k} is not divisible by tile_k_size = {2 * _LAYOUT_M}")
+    _check(size_n % _LAYOUT_N == 0, f"size_n = {size_n} is not divisible by tile_n_size = {_LAYOUT_N}")
+    per = int(_lib.lib.petit_nvfp4_native_image_bytes(size_k, size_n))
+    _check(per > 0, f"no native image for size_n={size_n}, size_k={size_k}")
+    return per
+
+
+def _mxfp6_quantize_operands(w: torch.Tensor, on_gpu: bool = True):
+    """w: 16-bit [size_n, size_k] or [num_experts, size_n, size_k] -> (num_experts, size_n, size_k, the images: uint8 [num_experts * bytes])."""
+    _check(w.dtype in (torch.bfloat16, torch.float16), "w must be bfloat16 or float16.")
+    _check(w.dim() in (2, 3), "w must be [size_n, size_k] or [num_experts, size_n, size_k]")
+    _check(w.is_cuda == on_gpu, "w is not on GPU" if on_gpu else "w must be a CPU tensor (use petit_kernel.quantize_mxfp6 for GPU tensors)")
+    _check(w.is_contiguous(), "w is not contiguous")
+    E, (n, k) = (w.size(0) if w.dim() == 3 else 1), w.shape[-2:]
+    return E, n, k, torch.empty(E * _mxfp6_image_bytes(E, n, k), dtype=torch.uint8, device=w.device)
+
+
+def _mxfp6_ingest_operands(elems: torch.Tensor, scales: torch.Tensor, size_n: int, size_k: int, on_gpu: bool = True):
+    """elems: uint8 [size_n, 3 size_k / 4] or [num_experts, ...] (OCP MXFP6 e2m3 bit stream), scales: uint8 [..., size_n, size_k / 32]."""
+    where = "GPU" if on_gpu else "CPU"
+    _check(elems.dtype == torch.uint8 and scales.dtype == torch.uint8 and elems.is_cuda == on_gpu and scales.device == elems.device and
+           elems.is_contiguous() and scales.is_contiguous(), f"elems and scales must be contiguous uint8 {where} tensors on one device")
+    _check(elems.dim() in (2, 3) and scales.dim() == elems.dim(), "elems must be [size_n, 3 * size_k / 4] or [num_experts, size_n, 3 * size_k / 4]")
+    E = elems.size(0) if elems.dim() == 3 else 1
+    per = _mxfp6_image_bytes(E, size_n, size_k)
+    _check(tuple(elems.shape[-2:]) == (size_n, size_k // 4 * 3) and tuple(scales.shape[-2:]) == (size_n, size_k // 32) and
+           (elems.dim() == 2 or scales.size(0) == E), "elems / scales do not hold [size_n, size_k] MXFP6 weights (24 bytes and one scale per 32 k)")
+    return E, torch.empty(E * per, dtype=torch.uint8, device=elems.device)
+
+
+def quantize_mxfp6(w: torch.Tensor, hadamard: int = 0) -> torch.Tensor:
+    """16-bit weights [N, K] or [E, N, K] -> their MFMA-native image(s) in MXFP6 (e2m3 elements, one e8m0 scale per 32 k; uint8, E images back
+    to back as nvfp4_native_images lays them out): the operand of mul_nvfp4_native / mul_nvfp4_native_invariant / mul_nvfp4_native_moe /
+    mul_nvfp4_native_moe_invariant with global scale(s) 1.0.  hadamard = 32 / 128: exactly quantize_mxfp6(hadamard_rotate(w, B, -log2 B))."""
+    w = _rotated_weights(w, hadamard, hadamard_rotate)
+    E, n, k, images = _mxfp6_quantize_operands(w)
+    with torch.cuda.device(w.device):
+        rc = _lib.lib.petit_quantize_weights_mxfp6(_ptr(w), _a_type(w.dtype), E, n, k, _ptr(images), _stream(w))
+    _raise_quantize(rc, "quantize_mxfp6", E, n, k)
+    return images
+
+
+def mxfp6_native_image(elems: torch.Tensor, scales: torch.Tensor, size_n: int, size_k: int) -> torch.Tensor:
+    """An OCP MXFP6 (e2m3) weight tensor -> the same image(s), without rounding.  elems: uint8 [N, 3 K / 4] or [E, N, 3 K / 4], element e of a
+    row at bits [6 e, 6 e + 6) of the row's little-endian bit stream; scales: uint8 e8m0 [N, K / 32] or [E, N, K / 32]."""
+    E, images = _mxfp6_ingest_operands(elems, scales, size_n, size_k)
+    with torch.cuda.device(elems.device):
+        rc = _lib.lib.petit_mxfp6_native_images(_ptr(images), _ptr(elems), _ptr(scales), E, size_n, size_k, _stream(elems))
+    _raise_quantize(rc, "mxfp6_native_image", E, size_n, size_k)
+    return images
+
+
 _ACTIVATIONS = {None: 0, "none": 0, "silu_mul": 1, "swiglu_oai": 2}   # PETIT_ACTIVATION_* (include/petit_amd.h)
 _B_TYPES = {"nv": _lib.CXX_DTYPE_FP4_E2M1, "nvfp4": _lib.CXX_DTYPE_FP4_E2M1, "mx": _lib.CXX_DTYPE_MXFP4_E2M1, "mxfp4": _lib.CXX_DTYPE_MXFP4_E2M1}
 _ACTIVATION_RULE = f"activation must be one of {sorted(k for k in _ACTIVATIONS if k)} or None"
