@@ -2,11 +2,12 @@
 """examples/quantize_linear.py -- loading a bf16 checkpoint: quantise the 16-bit weights to packed NVFP4 / MXFP4 on the device and run them.
 Needs an MI355X.
 
-    python examples/quantize_linear.py
+    python examples/quantize_linear.py [--search]
 
 quantize_nvfp4 / quantize_mxfp4 return (b, s, global_scale) in the layout mul_*_a16 and the MoE layers read: there is no row-major FP4
 tensor and no repack call in between.  A stack that receives fresh bf16 weights while it serves (an RL rollout engine) calls the same
-function again: it makes no host sync and can be captured in a graph.
+function again: it makes no host sync and can be captured in a graph.  --search quantises with method="search" (per block the better of two
+scale bytes by squared error: the same tensors for the same kernels, a smaller weight error, a quantise call about twice as long).
 """
 import sys
 from pathlib import Path
@@ -20,12 +21,12 @@ import petit_kernel  # noqa: E402
 class QuantizedLinear(torch.nn.Module):
     """y = x @ W^T with W quantised at load time from its 16-bit form (fmt 'nvfp4' or 'mxfp4')."""
 
-    def __init__(self, weight: torch.Tensor, fmt: str = "nvfp4"):
+    def __init__(self, weight: torch.Tensor, fmt: str = "nvfp4", method: str = "absmax"):
         super().__init__()
         self.size_n, self.size_k = weight.shape
         quantize = petit_kernel.quantize_nvfp4 if fmt == "nvfp4" else petit_kernel.quantize_mxfp4
         self.mul = petit_kernel.mul_nvfp4_a16 if fmt == "nvfp4" else petit_kernel.mul_mxfp4_a16
-        b, s, gs = quantize(weight.contiguous())
+        b, s, gs = quantize(weight.contiguous(), method=method)
         self.register_buffer("b", b)
         self.register_buffer("s", s)
         self.register_buffer("global_scale", gs)
@@ -37,6 +38,7 @@ class QuantizedLinear(torch.nn.Module):
 
 def main() -> None:
     dev = torch.device("cuda")
+    method = "search" if "--search" in sys.argv[1:] else "absmax"
     g = torch.Generator().manual_seed(0)
     # a bf16 linear layer
     n, k = 4096, 4096
@@ -44,9 +46,9 @@ def main() -> None:
     x = torch.randn((7, k), generator=g).bfloat16().to(dev)
     ref = x.float() @ weight.float().T
     for fmt in ("nvfp4", "mxfp4"):
-        y = QuantizedLinear(weight, fmt)(x).float()
+        y = QuantizedLinear(weight, fmt, method)(x).float()
         err = ((y - ref).norm() / ref.norm()).item()
-        print(f"{fmt} linear {n} x {k}: output error {err:.3f} of the bf16 layer's output rms (FP4 weights: about 0.1)")
+        print(f"{fmt} ({method}) linear {n} x {k}: output error {err:.3f} of the bf16 layer's output rms (FP4 weights: about 0.1)")
         assert err < 0.2
 
     # a stacked-expert layer: [E, 2 I, H] gate_up and [E, H, I] down, every expert quantised on its own (one global scale each)

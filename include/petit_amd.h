@@ -563,8 +563,26 @@ uint64_t petit_gemm_nvfp4_native_transient_workspace_bytes(const petit_solution_
  *     global scale  gs_e = 1.0f.
  *   Non-finite weights give unspecified values, never a fault.
  *
+ * The search (petit_quantize_weights_ex with method PETIT_QUANT_SEARCH; PETIT_QUANT_ABSMAX is the rule above, and what the entries without
+ * a method use).  The rule above fixes a block's scale from its maximum alone, which lands the maximum near the top code 6 of a grid that is
+ * coarse there (.., 3, 4, 6).  SEARCH gives each block exactly TWO candidate scale bytes and keeps the one with the smaller squared error:
+ *     NVFP4   b0 = e4m3fn_rne( f32( f32(blk_amax / 6.0f) / gs_e ) ) (the byte above) and b1 = e4m3fn_rne( f32( f32(blk_amax / 4.0f) / gs_e ) ),
+ *             both saturating; gs_e exactly as above (amax_e / 2688, or gs_in): the global scale is not searched.
+ *     MXFP4   b0 = the byte above and b1 = max(b0 - 1, 1): half the step, the maximum clips to 6 x 2^(e - 1).
+ *   A candidate's codes are what the rule above gives with that byte (the same thresholds, ties to the even code, no -0).  Its error is
+ *     err = 0.0f;  for the block's elements in ascending k:  d = fmaf(-q, G, |w|);  err = fmaf(d, d, err)
+ *   in f32, where |w| is the element's magnitude (exact), q = e2m1(code) x s with s the decoded byte (2 + 4 significant bits: exact) and
+ *   G = gs_e for NVFP4, q = e2m1(code) and G = 2^(byte - 127) for MXFP4: q x G is the weight the GEMMs multiply by -- they apply gs_e after
+ *   the sum, so it is never rounded on its own -- and each element costs two fused operations with one rounding each.  The sequence holds no
+ *   separate multiply-then-add, so neither a compiler's contraction nor its absence changes a bit: the device and the host twin agree.
+ *   b1 wins only if b1 != b0 and err(b1) < err(b0).  A tie, a zero block (b1 == b0) and an error that is not a number keep b0.  One pass
+ *   over the weights as before, no further scratch, the same three tensors in the same layout: only scale bytes and codes differ.  An MXFP4
+ *   byte can be one lower than ABSMAX's (petit's fp16 scale-range diagnostics apply to the result as to any tensor).  Not searched: the NVFP4
+ *   global scale, a third candidate, MXFP6 weights, activations.
+ *
  * petit_quantize_weights_host is the CPU twin on host memory: same arguments without scratch and stream, the same bytes out (offline conversion).
- * Errors, all before any launch: PETIT_ERROR_BAD_ARGUMENT for an a_type / b_type outside the above, null or misaligned pointers, a workspace
+ * petit_quantize_weights_ex / _ex_host are the two entries with the method named; the entries without it forward PETIT_QUANT_ABSMAX.
+ * Errors, all before any launch: PETIT_ERROR_BAD_ARGUMENT for a method, a_type or b_type outside the above, null or misaligned pointers, a workspace
  * that is too small; PETIT_ERROR_PROBLEM_SHAPE for n % 16, k % 256 or num_experts * n >= 2^32; PETIT_ERROR_KERNEL_SHAPE for a call that needs
  * scratch and has none.  num_experts, n or k == 0 returns PETIT_OK.  No host sync, no allocation: capturable; a replay quantises what w holds then.
  */
@@ -573,6 +591,11 @@ int petit_quantize_weights(const void *w, int a_type, int b_type, unsigned num_e
                            void *out_scales, float *out_gs, void *workspace, uint64_t workspace_bytes, void *stream);
 int petit_quantize_weights_host(const void *w, int a_type, int b_type, unsigned num_experts, unsigned n, unsigned k, const float *gs_in,
                                 void *out_b, void *out_scales, float *out_gs);
+enum { PETIT_QUANT_ABSMAX = 0, PETIT_QUANT_SEARCH = 1 };
+int petit_quantize_weights_ex(const void *w, int a_type, int b_type, int method, unsigned num_experts, unsigned n, unsigned k, const float *gs_in,
+                              void *out_b, void *out_scales, float *out_gs, void *workspace, uint64_t workspace_bytes, void *stream);
+int petit_quantize_weights_ex_host(const void *w, int a_type, int b_type, int method, unsigned num_experts, unsigned n, unsigned k,
+                                   const float *gs_in, void *out_b, void *out_scales, float *out_gs);
 
 /*
  * MXFP6 weights on the native class (no counterpart in the reference).

@@ -145,12 +145,21 @@ uint64_t petit_quantize_weights_workspace_bytes(int b_type, unsigned num_experts
 }
 int petit_quantize_weights(const void *w, int a_type, int b_type, unsigned num_experts, unsigned n, unsigned k, const float *gs_in, void *out_b,
                            void *out_scales, float *out_gs, void *workspace, uint64_t workspace_bytes, void *stream) {
-    return quantize_weights(w, a_type, canonical_b_type(b_type), num_experts, n, k, gs_in, out_b, out_scales, out_gs, workspace, workspace_bytes,
-                            (hipStream_t)stream);
+    return petit_quantize_weights_ex(w, a_type, b_type, PETIT_QUANT_ABSMAX, num_experts, n, k, gs_in, out_b, out_scales, out_gs, workspace,
+                                     workspace_bytes, stream);
 }
 int petit_quantize_weights_host(const void *w, int a_type, int b_type, unsigned num_experts, unsigned n, unsigned k, const float *gs_in,
                                 void *out_b, void *out_scales, float *out_gs) {
-    return quantize_weights_host(w, a_type, canonical_b_type(b_type), num_experts, n, k, gs_in, out_b, out_scales, out_gs);
+    return petit_quantize_weights_ex_host(w, a_type, b_type, PETIT_QUANT_ABSMAX, num_experts, n, k, gs_in, out_b, out_scales, out_gs);
+}
+int petit_quantize_weights_ex(const void *w, int a_type, int b_type, int method, unsigned num_experts, unsigned n, unsigned k, const float *gs_in,
+                              void *out_b, void *out_scales, float *out_gs, void *workspace, uint64_t workspace_bytes, void *stream) {
+    return quantize_weights(w, a_type, canonical_b_type(b_type), method, num_experts, n, k, gs_in, out_b, out_scales, out_gs, workspace,
+                            workspace_bytes, (hipStream_t)stream);
+}
+int petit_quantize_weights_ex_host(const void *w, int a_type, int b_type, int method, unsigned num_experts, unsigned n, unsigned k,
+                                   const float *gs_in, void *out_b, void *out_scales, float *out_gs) {
+    return quantize_weights_host(w, a_type, canonical_b_type(b_type), method, num_experts, n, k, gs_in, out_b, out_scales, out_gs);
 }
 // MXFP6 weights into the native image (mxfp6_weights.hip makes every check: the device forms and their host twins refuse the same calls)
 int petit_quantize_weights_mxfp6(const void *w, int a_type, unsigned num_experts, unsigned n, unsigned k, void *images, void *stream) {

@@ -192,10 +192,12 @@ int nv6_images_host(void *images, const void *pw, const void *ps, unsigned num_e
 // quantize_weights.hip: 16-bit weights [E][n][k] -> the packed tensors and one global scale per expert (include/petit_amd.h "Weight quantiser");
 // host twin, bit-identical
 uint64_t quantize_weights_workspace_bytes(int b_type, unsigned num_experts, bool gs_supplied);
-int quantize_weights(const void *w, int a_type, int b_type, unsigned num_experts, unsigned n, unsigned k, const float *gs_in, void *out_b,
-                     void *out_scales, float *out_gs, void *workspace, uint64_t workspace_bytes, hipStream_t stream);
-int quantize_weights_host(const void *w, int a_type, int b_type, unsigned num_experts, unsigned n, unsigned k, const float *gs_in, void *out_b,
-                          void *out_scales, float *out_gs);
+// (method: PETIT_QUANT_ABSMAX / PETIT_QUANT_SEARCH)
+enum : int { kQuantAbsmax = 0, kQuantSearch = 1 };
+int quantize_weights(const void *w, int a_type, int b_type, int method, unsigned num_experts, unsigned n, unsigned k, const float *gs_in,
+                     void *out_b, void *out_scales, float *out_gs, void *workspace, uint64_t workspace_bytes, hipStream_t stream);
+int quantize_weights_host(const void *w, int a_type, int b_type, int method, unsigned num_experts, unsigned n, unsigned k, const float *gs_in,
+                          void *out_b, void *out_scales, float *out_gs);
 // mxfp6_weights.hip: num_experts images ("petit-cdna4-nv6/1") back to back from 16-bit weights [E][n][k] (quantised: include/petit_amd.h "MXFP6
 // weights on the native class") or from an OCP MXFP6 tensor (elems [E][n][3 k / 4], scales [E][n][k / 32]; no rounding); host twins, bit-identical
 int mxfp6_quantize_weights(const void *w, int a_type, unsigned num_experts, unsigned n, unsigned k, void *images, hipStream_t stream);

@@ -19,6 +19,7 @@
 #include <algorithm>
 #include <cmath>
 #include <cstring>
+#include <type_traits>
 
 #include "device_common.hpp"
 #include "hal.h"
@@ -116,6 +117,85 @@ template <bool MX, bool BF16> PETIT_HD unsigned quantize_lane(const unsigned (&d
         }
     }
     return scales;
+}
+
+// ---- PETIT_QUANT_SEARCH: the better of two scale bytes per block, by squared error (include/petit_amd.h "Weight quantiser", "The search") ----
+
+// the e2m1 magnitude of a code 0 .. 7 without a table (a table indexed per element would live in memory): the codes 2 .. 7 = 1, 1.5, 2, 3, 4, 6
+// are the f32 patterns (c + 252) << 22 -- the code's low bit is the top mantissa bit --, the codes 0 and 1 are 0 and 0.5
+PETIT_HD float e2m1_mag_f32(unsigned c) { return bits_f32(c > 1u ? (c + 252u) << 22 : c ? 0x3f000000u : 0u); }
+
+// One candidate of one block: the codes of the dwords [J0, J0 + NJ) of the lane under the scale byte -- exactly what quantize_lane gives with
+// that byte -- into words[(j - J0) / 4], and the candidate's error in the header's operation order:
+//     err = 0;  per element in ascending k:  d = fmaf(-q, G, |w|);  err = fmaf(d, d, err)
+// with q = e2m1(code) x s, G = gs (NVFP4: q has 2 + 4 significant bits, exact) and q = e2m1(code), G = 2^e (MXFP4).  Two explicit fused
+// operations per element and nothing a contraction could join: the host twin and the kernel round alike whatever the compiler's mode.
+template <bool MX, bool BF16, int J0, int NJ>
+PETIT_HD float search_candidate(const unsigned (&d)[16], unsigned sbyte, float gs, unsigned (&words)[NJ / 4]) {
+    float t[7];
+    if constexpr (MX)
+        mx_thresholds(sbyte, t);
+    else
+        nv_thresholds(sbyte, gs, t);
+    const float s = MX ? 1.0f : e4m3_mag_f32(sbyte), G = MX ? e8m0_f32(sbyte) : gs;
+    float err = 0.f;
+#pragma unroll
+    for (int j = 0; j < NJ / 4; ++j)
+        words[j] = 0u;
+#pragma unroll
+    for (int j = 0; j < NJ; ++j) {
+        const unsigned w = d[J0 + j];
+        const float a0 = h16_f32<BF16>(w & 0x7fffu), a1 = h16_f32<BF16>((w >> 16) & 0x7fffu);
+        const unsigned c0 = fp4_code(a0, t, (w >> 15) & 1u), c1 = fp4_code(a1, t, w >> 31);
+        words[j / 4] |= (c0 | (c1 << 4)) << (8 * (j % 4));
+        const float d0 = fmaf(-(e2m1_mag_f32(c0 & 7u) * s), G, a0);
+        err = fmaf(d0, d0, err);
+        const float d1 = fmaf(-(e2m1_mag_f32(c1 & 7u) * s), G, a1);
+        err = fmaf(d1, d1, err);
+    }
+    return err;
+}
+
+// One block under the search: today's byte b0 is evaluated and kept unless the second candidate b1 is another byte AND its error is strictly
+// smaller (a tie, a zero block, a NaN error keep b0).  The candidates are evaluated one after the other and only the winner's words stay.
+template <bool MX, bool BF16, int J0, int NJ>
+PETIT_HD unsigned search_block(const unsigned (&d)[16], unsigned b0, unsigned b1, float gs, unsigned *words) {
+    unsigned w0[NJ / 4];
+    const float e0 = search_candidate<MX, BF16, J0, NJ>(d, b0, gs, w0);
+    unsigned sel = b0;
+    if (b1 != b0) {
+        unsigned w1[NJ / 4];
+        const float e1 = search_candidate<MX, BF16, J0, NJ>(d, b1, gs, w1);
+        if (e1 < e0) {
+            sel = b1;
+#pragma unroll
+            for (int j = 0; j < NJ / 4; ++j)
+                w0[j] = w1[j];
+        }
+    }
+#pragma unroll
+    for (int j = 0; j < NJ / 4; ++j)
+        words[J0 / 4 + j] = w0[j];
+    return sel;
+}
+
+// quantize_lane under PETIT_QUANT_SEARCH: the same unit of work, the same outputs; a block lives in one lane, so there is no cross-lane traffic
+template <bool MX, bool BF16> PETIT_HD unsigned quantize_lane_search(const unsigned (&d)[16], float gs, unsigned (&words)[4]) {
+    unsigned mag_max[2] = {0u, 0u};
+#pragma unroll
+    for (int j = 0; j < 16; ++j) {
+        const unsigned lo = d[j] & 0x7fffu, hi = (d[j] >> 16) & 0x7fffu, m = lo > hi ? lo : hi;
+        mag_max[j / 8] = m > mag_max[j / 8] ? m : mag_max[j / 8];
+    }
+    if constexpr (MX) {
+        const unsigned b0 = mx_scale_byte(h16_f32<BF16>(mag_max[0] > mag_max[1] ? mag_max[0] : mag_max[1]));
+        return search_block<true, BF16, 0, 16>(d, b0, b0 > 1u ? b0 - 1u : 1u, gs, words);
+    } else {
+        const float a0 = h16_f32<BF16>(mag_max[0]), a1 = h16_f32<BF16>(mag_max[1]);
+        const unsigned s0 = search_block<false, BF16, 0, 8>(d, nv_scale_byte(a0, gs), e4m3_rne_sat((a0 / 4.0f) / gs), gs, words);
+        const unsigned s1 = search_block<false, BF16, 8, 8>(d, nv_scale_byte(a1, gs), e4m3_rne_sat((a1 / 4.0f) / gs), gs, words);
+        return s0 | (s1 << 8);
+    }
 }
 
 } // namespace
@@ -230,11 +310,67 @@ __global__ __launch_bounds__(256) void quantize_pack_kernel(u32x4 *__restrict__ 
 #endif
 }
 
+// The same launch under PETIT_QUANT_SEARCH, a kernel of its own name so that quantize_pack_kernel above is compiled from untouched text: the
+// same work split (one wave = one n-tile x one span of KS k-tiles, lane 16 g + r = 32 consecutive k of row r, the next k-tile's 64 bytes in
+// flight while the current one is quantised, no LDS, no barrier, vector stores, one scale record per span), the same arguments, the same
+// addresses.  Only the lane's unit of work differs: quantize_lane_search evaluates both candidate bytes of each block in the lane's own
+// registers.  The work per byte roughly triples (two code passes and two error sums where there was one code pass), so this kernel is bound by
+// the VALU, not by HBM (profiles/weight_quant_search.md); what keeps it fed is the same prefetch and full occupancy.
+template <int KS, bool MX, bool BF16>
+__global__ __launch_bounds__(256) void quantize_pack_search_kernel(u32x4 *__restrict__ pw, unsigned char *__restrict__ ps, float *out_gs,
+                                                                   const u32x4 *__restrict__ w, const float *gs_src, int gs_mode, unsigned n,
+                                                                   unsigned k, unsigned items) { // (out_gs may be gs_src, as above)
+#if defined(__HIP_DEVICE_COMPILE__)
+    constexpr int kRecBytes = MX ? KS : 2 * KS;
+    const unsigned lane = threadIdx.x % 64, g = lane / 16, r = lane % 16;
+    const unsigned ktiles = k / kTileK, nspans = ktiles / KS, tiles_per_expert = n / kTileN, row_u4 = k / 8;
+    for (unsigned item = blockIdx.x * 4 + threadIdx.x / 64; item < items; item += gridDim.x * 4) {
+        const unsigned nt = item / nspans, sp = item % nspans, e = nt / tiles_per_expert;
+        float gs = 1.0f;
+        if (gs_mode == kGsFromAmax)
+            gs = nv_global_scale(gs_src[e]);
+        else if (gs_mode == kGsSupplied)
+            gs = gs_src[e];
+        if (lane == 0 && sp == 0 && nt % tiles_per_expert == 0)
+            out_gs[e] = gs;
+        const u32x4 *const row = w + (size_t)(nt * kTileN + r) * row_u4 + (size_t)sp * KS * 16 + g * 4;
+        unsigned rec[(kRecBytes + 3) / 4];
+#pragma unroll
+        for (int i = 0; i < (kRecBytes + 3) / 4; ++i)
+            rec[i] = 0u;
+        u32x4 nxt[4] = {row[0], row[1], row[2], row[3]};
+        // (not unrolled over the span: the body is some thousand instructions, and the record's word is chosen by a uniform index instead)
+#pragma unroll 1
+        for (int t = 0; t < KS; ++t) {
+            unsigned d[16];
+#pragma unroll
+            for (int i = 0; i < 16; ++i)
+                d[i] = nxt[i / 4][i % 4];
+            if (t + 1 < KS) {
+#pragma unroll
+                for (int i = 0; i < 4; ++i)
+                    nxt[i] = row[(t + 1) * 16 + i];
+            }
+            unsigned words[4];
+            const unsigned scales = quantize_lane_search<MX, BF16>(d, gs, words);
+            pw[((size_t)nt * ktiles + sp * KS + t) * 64 + lane] = u32x4{words[0], words[1], words[2], words[3]};
+            const int wi = MX ? t / 4 : t / 2;
+            const unsigned piece = MX ? scales << (8 * (t % 4)) : scales << (16 * (t % 2));
+#pragma unroll
+            for (int i = 0; i < (kRecBytes + 3) / 4; ++i)
+                rec[i] |= i == wi ? piece : 0u;
+        }
+        store_record<kRecBytes>(ps + (((size_t)nt * nspans + sp) * 64 + lane) * kRecBytes, rec);
+    }
+#endif
+}
+
 namespace {
 
-// what both forms refuse, in one place: the element types, then the shape (every 32-bit quantity the kernels form stays in range)
-int quantize_check(int a_type, int b_type, unsigned num_experts, unsigned n, unsigned k) {
-    if ((a_type != kDataTypeBf16 && a_type != kDataTypeFp16) || (b_type != kDataTypeFp4e2m1 && !is_mx_type(b_type)))
+// what both forms refuse, in one place: the method and the element types, then the shape (every 32-bit quantity the kernels form stays in range)
+int quantize_check(int method, int a_type, int b_type, unsigned num_experts, unsigned n, unsigned k) {
+    if ((method != kQuantAbsmax && method != kQuantSearch) || (a_type != kDataTypeBf16 && a_type != kDataTypeFp16) ||
+        (b_type != kDataTypeFp4e2m1 && !is_mx_type(b_type)))
         return kErrBadArgument;
     if (n % kTileN || k % 256)
         return kErrProblemShape;
@@ -250,14 +386,22 @@ template <int KS, bool MX> auto quantize_kernel_for(bool bf16) {
 template <bool MX> auto quantize_kernel_for(int ks, bool bf16) {
     return ks == 8 ? quantize_kernel_for<8, MX>(bf16) : ks == 4 ? quantize_kernel_for<4, MX>(bf16) : quantize_kernel_for<2, MX>(bf16);
 }
+template <int KS, bool MX> auto quantize_search_kernel_for(bool bf16) {
+    return bf16 ? quantize_pack_search_kernel<KS, MX, true> : quantize_pack_search_kernel<KS, MX, false>;
+}
+template <bool MX> auto quantize_search_kernel_for(int ks, bool bf16) {
+    return ks == 8   ? quantize_search_kernel_for<8, MX>(bf16)
+           : ks == 4 ? quantize_search_kernel_for<4, MX>(bf16)
+                     : quantize_search_kernel_for<2, MX>(bf16);
+}
 
-template <bool MX, bool BF16>
+template <bool MX, bool BF16, bool SEARCH>
 void quantize_host(const uint16_t *w, unsigned rows, unsigned n, unsigned k, const float *gs, unsigned *pw, unsigned char *ps) {
     for (unsigned row = 0; row < rows; ++row)
         for (unsigned blk = 0; blk < k / 32; ++blk) {
             unsigned d[16], words[4];
             memcpy(d, w + (size_t)row * k + 32 * blk, 64);
-            const unsigned scales = quantize_lane<MX, BF16>(d, gs[row / n], words);
+            const unsigned scales = SEARCH ? quantize_lane_search<MX, BF16>(d, gs[row / n], words) : quantize_lane<MX, BF16>(d, gs[row / n], words);
             memcpy(pw + packed_weight_word_index(k, row, 4 * blk), words, 16);
             if constexpr (MX) {
                 ps[packed_mxscale_byte_index(k, row, blk)] = (unsigned char)scales;
@@ -274,9 +418,9 @@ uint64_t quantize_weights_workspace_bytes(int b_type, unsigned num_experts, bool
     return b_type == kDataTypeFp4e2m1 && !gs_supplied ? (uint64_t)num_experts * sizeof(float) : 0;
 }
 
-int quantize_weights(const void *w, int a_type, int b_type, unsigned num_experts, unsigned n, unsigned k, const float *gs_in, void *out_b,
-                     void *out_scales, float *out_gs, void *workspace, uint64_t workspace_bytes, hipStream_t stream) {
-    if (const int rc = quantize_check(a_type, b_type, num_experts, n, k))
+int quantize_weights(const void *w, int a_type, int b_type, int method, unsigned num_experts, unsigned n, unsigned k, const float *gs_in,
+                     void *out_b, void *out_scales, float *out_gs, void *workspace, uint64_t workspace_bytes, hipStream_t stream) {
+    if (const int rc = quantize_check(method, a_type, b_type, num_experts, n, k))
         return rc;
     if (num_experts == 0 || n == 0 || k == 0)
         return kOk;
@@ -304,7 +448,8 @@ int quantize_weights(const void *w, int a_type, int b_type, unsigned num_experts
     }
     const int ks = span_tiles_for_k(k);
     const unsigned items = rows / kTileN * (k / (kTileK * ks));
-    const auto kern = mx ? quantize_kernel_for<true>(ks, bf16) : quantize_kernel_for<false>(ks, bf16);
+    const auto kern = method == kQuantSearch ? (mx ? quantize_search_kernel_for<true>(ks, bf16) : quantize_search_kernel_for<false>(ks, bf16))
+                                             : (mx ? quantize_kernel_for<true>(ks, bf16) : quantize_kernel_for<false>(ks, bf16));
     const float *const gs_src = mx ? nullptr : gs_in ? gs_in : (const float *)workspace;
     hipLaunchKernelGGL(kern, dim3(std::min((items + 3) / 4, cap)), dim3(256), 0, stream, (u32x4 *)out_b, (unsigned char *)out_scales, out_gs,
                        (const u32x4 *)w, gs_src, mx ? kGsOne : gs_in ? kGsSupplied : kGsFromAmax, n, k, items);
@@ -312,9 +457,9 @@ int quantize_weights(const void *w, int a_type, int b_type, unsigned num_experts
 }
 
 // host twin (offline conversion; bit-identical to the device kernels: tests/test_quantize_weights.py)
-int quantize_weights_host(const void *w_, int a_type, int b_type, unsigned num_experts, unsigned n, unsigned k, const float *gs_in, void *out_b,
-                          void *out_scales, float *out_gs) {
-    if (const int rc = quantize_check(a_type, b_type, num_experts, n, k))
+int quantize_weights_host(const void *w_, int a_type, int b_type, int method, unsigned num_experts, unsigned n, unsigned k, const float *gs_in,
+                          void *out_b, void *out_scales, float *out_gs) {
+    if (const int rc = quantize_check(method, a_type, b_type, num_experts, n, k))
         return rc;
     if (num_experts == 0 || n == 0 || k == 0)
         return kOk;
@@ -334,7 +479,12 @@ int quantize_weights_host(const void *w_, int a_type, int b_type, unsigned num_e
         }
         out_gs[e] = gs;
     }
-    const auto fn = mx ? (bf16 ? quantize_host<true, true> : quantize_host<true, false>) : (bf16 ? quantize_host<false, true> : quantize_host<false, false>);
+    const auto pick = [&](auto search) {
+        constexpr bool S = decltype(search)::value;
+        return mx ? (bf16 ? quantize_host<true, true, S> : quantize_host<true, false, S>)
+                  : (bf16 ? quantize_host<false, true, S> : quantize_host<false, false, S>);
+    };
+    const auto fn = method == kQuantSearch ? pick(std::true_type{}) : pick(std::false_type{});
     fn(w, num_experts * n, n, k, out_gs, (unsigned *)out_b, (unsigned char *)out_scales);
     return kOk;
 }

@@ -160,8 +160,9 @@ struct QuantizeShapes {
     int64_t E, n, k;
     at::Tensor b, s, gs;
 };
-QuantizeShapes quantize_shapes(const at::Tensor &w, int64_t b_type, const std::optional<at::Tensor> &global_scale, bool real) {
+QuantizeShapes quantize_shapes(const at::Tensor &w, int64_t b_type, const std::optional<at::Tensor> &global_scale, int64_t method, bool real) {
     TORCH_CHECK(b_type == kCxxFp4 || b_type == kCxxMxFp4, "b_type must be 3 (NVFP4) or 7 (MXFP4)");
+    TORCH_CHECK(method == PETIT_QUANT_ABSMAX || method == PETIT_QUANT_SEARCH, "method must be 'absmax' (0) or 'search' (1)");
     const bool mx = b_type == kCxxMxFp4;
     TORCH_CHECK(w.scalar_type() == at::kBFloat16 || w.scalar_type() == at::kHalf, "w must be bfloat16 or float16.");
     TORCH_CHECK(w.dim() == 2 || w.dim() == 3, "w must be [size_n, size_k] or [num_experts, size_n, size_k]");
@@ -183,23 +184,25 @@ QuantizeShapes quantize_shapes(const at::Tensor &w, int64_t b_type, const std::o
     q.gs = at::empty({E}, w.options().dtype(at::kFloat));
     return q;
 }
-std::tuple<at::Tensor, at::Tensor, at::Tensor> quantize_weights(const at::Tensor &w, int64_t b_type, const std::optional<at::Tensor> &global_scale) {
-    const QuantizeShapes q = quantize_shapes(w, b_type, global_scale, true);
+std::tuple<at::Tensor, at::Tensor, at::Tensor> quantize_weights(const at::Tensor &w, int64_t b_type, const std::optional<at::Tensor> &global_scale,
+                                                                int64_t method) {
+    const QuantizeShapes q = quantize_shapes(w, b_type, global_scale, method, true);
     const c10::hip::HIPGuardMasqueradingAsCUDA guard(w.device());
     const bool supplied = b_type == kCxxFp4 && global_scale.has_value();
     const uint64_t ws_bytes = petit_quantize_weights_workspace_bytes((int)b_type, (unsigned)q.E, supplied);
     at::Tensor ws;
     if (ws_bytes)
         ws = at::empty({(int64_t)ws_bytes}, w.options().dtype(at::kByte));
-    const int rc = petit_quantize_weights(w.data_ptr(), a_type_of(w.scalar_type()), (int)b_type, (unsigned)q.E, (unsigned)q.n, (unsigned)q.k,
-                                          supplied ? (const float *)global_scale->data_ptr() : nullptr, q.b.data_ptr(), q.s.data_ptr(),
-                                          (float *)q.gs.data_ptr(), ws_bytes ? ws.data_ptr() : nullptr, ws_bytes, stream_of(w));
+    const int rc = petit_quantize_weights_ex(w.data_ptr(), a_type_of(w.scalar_type()), (int)b_type, (int)method, (unsigned)q.E, (unsigned)q.n,
+                                             (unsigned)q.k, supplied ? (const float *)global_scale->data_ptr() : nullptr, q.b.data_ptr(),
+                                             q.s.data_ptr(), (float *)q.gs.data_ptr(), ws_bytes ? ws.data_ptr() : nullptr, ws_bytes, stream_of(w));
     TORCH_CHECK(rc != PETIT_ERROR_PROBLEM_SHAPE, "Incompatible problem shape (num_experts=", q.E, ", n=", q.n, ", k=", q.k, ")");
     TORCH_CHECK(rc == PETIT_OK, b_type == kCxxMxFp4 ? "quantize_mxfp4: " : "quantize_nvfp4: ", petit_error_string(rc));
     return {q.b, q.s, q.gs};
 }
-std::tuple<at::Tensor, at::Tensor, at::Tensor> quantize_weights_meta(const at::Tensor &w, int64_t b_type, const std::optional<at::Tensor> &global_scale) {
-    const QuantizeShapes q = quantize_shapes(w, b_type, global_scale, false);
+std::tuple<at::Tensor, at::Tensor, at::Tensor> quantize_weights_meta(const at::Tensor &w, int64_t b_type, const std::optional<at::Tensor> &global_scale,
+                                                                     int64_t method) {
+    const QuantizeShapes q = quantize_shapes(w, b_type, global_scale, method, false);
     return {q.b, q.s, q.gs};
 }
 
@@ -1160,7 +1163,7 @@ TORCH_LIBRARY(petit_kernel, m) {
     m.def("repack_nvfp4(Tensor b_q_weight, int size_n, int size_k) -> Tensor");
     m.def("process_nvfp4_scales(Tensor scales, int size_n, int size_k) -> Tensor");
     m.def("process_mxfp4_scales(Tensor scales, int size_n, int size_k) -> Tensor");
-    m.def("quantize_weights(Tensor w, int b_type, Tensor? global_scale=None) -> (Tensor, Tensor, Tensor)");
+    m.def("quantize_weights(Tensor w, int b_type, Tensor? global_scale=None, int method=0) -> (Tensor, Tensor, Tensor)");
     m.def("quantize_mxfp6(Tensor w) -> Tensor");
     m.def("mxfp6_native_image(Tensor elems, Tensor scales, int size_n, int size_k) -> Tensor");
     m.def("hadamard_rotate(Tensor x, int block, int log2_scale=0) -> Tensor");

@@ -67,17 +67,19 @@ def hadamard_rotate(x: torch.Tensor, block: int, log2_scale: int = 0, out: torch
     return _impl.hadamard_rotate(x, block, log2_scale, out)
 
 
-def quantize_nvfp4(w: torch.Tensor, global_scale: torch.Tensor = None, hadamard: int = 0):
+def quantize_nvfp4(w: torch.Tensor, global_scale: torch.Tensor = None, hadamard: int = 0, method: str = "absmax"):
     # 16-bit weights [N, K] or [E, N, K] -> (b, s, global_scale) on the device (include/petit_amd.h "Weight quantiser"): the packed tensors
     # repack_nvfp4 / process_nvfp4_scales return for the stacked [E * N, K] tensor and float32 [E] global scales (amax / 2688 per expert, or the
     # caller's), for mul_nvfp4_a16, the MoE launches, fp4_moe* and nvfp4_native_image(s).  Host twin: offline.quantize_nvfp4_cpu
     # hadamard = 32 / 128: exactly quantize_nvfp4(hadamard_rotate(w, B, -log2 B)) -- the weights for activations quantised with the same hadamard
-    return _impl.quantize_nvfp4(w, global_scale, hadamard)
+    # method = "search": per block the better, by squared error, of the amax rule's scale byte and one second candidate (the maximum mapped to
+    # 4 instead of 6; MXFP4: one byte lower) -- the same tensors for the same kernels, less weight error (include/petit_amd.h "The search")
+    return _impl.quantize_nvfp4(w, global_scale, hadamard, method)
 
 
-def quantize_mxfp4(w: torch.Tensor, hadamard: int = 0):
+def quantize_mxfp4(w: torch.Tensor, hadamard: int = 0, method: str = "absmax"):
     # the same for MXFP4 (one e8m0 scale per 32 k, global_scale = 1); num_experts * N must be a multiple of 32, as process_mxfp4_scales asks
-    return _impl.quantize_mxfp4(w, hadamard)
+    return _impl.quantize_mxfp4(w, hadamard, method)
 
 
 def quantize_mxfp6(w: torch.Tensor, hadamard: int = 0) -> torch.Tensor:

@@ -30,6 +30,8 @@ CXX_DTYPE_MXFP4_E2M1 = 7
 CXX_DTYPE_MXFP4_E2M1_F16RANGE = 8   # extension: MXFP4 with every e8m0 scale in 114..140 (include/petit_amd.h)
 MXFP4_F16RANGE_SCALE_MIN, MXFP4_F16RANGE_SCALE_MAX = 114, 140
 PETIT_MOE_MAX_EXPERTS = 1024
+PETIT_QUANT_ABSMAX, PETIT_QUANT_SEARCH = 0, 1   # the weight quantiser's block-scale rule (include/petit_amd.h "The search")
+QUANT_METHODS = {"absmax": PETIT_QUANT_ABSMAX, "search": PETIT_QUANT_SEARCH}
 PETIT_DTYPE_FP32 = 100   # petit_dequant_packed_weights; float32 router logits (petit_moe_route)
 PETIT_MOE_MAX_TOPK = 64
 PETIT_ROUTE_SOFTMAX, PETIT_ROUTE_SIGMOID = 0, 1
@@ -184,6 +186,8 @@ _SIGNATURES = {
     "petit_quantize_weights_workspace_bytes": (C.c_uint64, [C.c_int, C.c_uint, C.c_int]),
     "petit_quantize_weights": (C.c_int, [C.c_void_p, C.c_int, C.c_int] + [C.c_uint] * 3 + [C.c_void_p] * 5 + [C.c_uint64, C.c_void_p]),
     "petit_quantize_weights_host": (C.c_int, [C.c_void_p, C.c_int, C.c_int] + [C.c_uint] * 3 + [C.c_void_p] * 4),
+    "petit_quantize_weights_ex": (C.c_int, [C.c_void_p] + [C.c_int] * 3 + [C.c_uint] * 3 + [C.c_void_p] * 5 + [C.c_uint64, C.c_void_p]),
+    "petit_quantize_weights_ex_host": (C.c_int, [C.c_void_p] + [C.c_int] * 3 + [C.c_uint] * 3 + [C.c_void_p] * 4),
     "petit_quantize_weights_mxfp6": (C.c_int, [C.c_void_p, C.c_int] + [C.c_uint] * 3 + [C.c_void_p] * 2),
     "petit_quantize_weights_mxfp6_host": (C.c_int, [C.c_void_p, C.c_int] + [C.c_uint] * 3 + [C.c_void_p]),
     "petit_mxfp6_native_images": (C.c_int, [C.c_void_p] * 3 + [C.c_uint] * 3 + [C.c_void_p]),

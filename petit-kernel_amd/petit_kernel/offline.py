@@ -13,7 +13,7 @@ import torch
 
 from . import _lib
 from .ops import _B_TYPES, _LAYOUT_M, _LAYOUT_N, _PACK, _QFORMATS, _a_type, _check, _opt_ptr, _ptr, _quantize_operands, _quantize_outputs, _raise_on
-from .ops import _raise_quantize, _rmsnorm_operands, _rmsnorm_outputs, _rmsnorm_result
+from .ops import _quantize_method, _raise_quantize, _rmsnorm_operands, _rmsnorm_outputs, _rmsnorm_result
 from .ops import QuantizedActivations, _HADAMARD_FP6, _hadamard_block, _hadamard_operands, _rotated_weights
 from .ops import _mxfp6_ingest_operands, _mxfp6_quantize_operands
 from .ops import _combine_norm_operands, _combine_norm_outputs, _combine_norm_result, _combine_norm_returns
@@ -70,10 +70,11 @@ def process_mxfp4_scales_cpu(scales: torch.Tensor, size_n: int, size_k: int) -> 
 
 # --- 16-bit weights -> the packed tensors, offline (include/petit_amd.h "Weight quantiser") ------------------------------------------------------
 
-def _quantize_weights_cpu(kind: str, w: torch.Tensor, global_scale=None):
+def _quantize_weights_cpu(kind: str, w: torch.Tensor, global_scale=None, method="absmax"):
+    method = _quantize_method(method)
     E, n, k = _quantize_operands(kind, w, global_scale, on_gpu=False)
     b, s, gs = _quantize_outputs(kind, E, n, k, w.device)
-    rc = _lib.lib.petit_quantize_weights_host(w.data_ptr(), _a_type(w.dtype), _B_TYPES[kind], E, n, k,
+    rc = _lib.lib.petit_quantize_weights_ex_host(w.data_ptr(), _a_type(w.dtype), _B_TYPES[kind], method, E, n, k,
                                               None if global_scale is None else global_scale.data_ptr(), b.data_ptr(), s.data_ptr(), gs.data_ptr())
     _raise_quantize(rc, "quantize_%sfp4_cpu" % kind, E, n, k)
     return b, s, gs
@@ -86,14 +87,16 @@ def hadamard_rotate_cpu(x: torch.Tensor, block: int, log2_scale: int = 0, out: t
     return out
 
 
-def quantize_nvfp4_cpu(w: torch.Tensor, global_scale: torch.Tensor = None, hadamard: int = 0):
+def quantize_nvfp4_cpu(w: torch.Tensor, global_scale: torch.Tensor = None, hadamard: int = 0, method: str = "absmax"):
     """CPU twin of petit_kernel.quantize_nvfp4: bf16 / fp16 [N, K] or [E, N, K] -> (b, s, global_scale), bit-identical to the device's."""
-    return _quantize_weights_cpu("nv", _rotated_weights(w, hadamard, hadamard_rotate_cpu), global_scale)
+    _quantize_method(method)
+    return _quantize_weights_cpu("nv", _rotated_weights(w, hadamard, hadamard_rotate_cpu), global_scale, method)
 
 
-def quantize_mxfp4_cpu(w: torch.Tensor, hadamard: int = 0):
+def quantize_mxfp4_cpu(w: torch.Tensor, hadamard: int = 0, method: str = "absmax"):
     """CPU twin of petit_kernel.quantize_mxfp4."""
-    return _quantize_weights_cpu("mx", _rotated_weights(w, hadamard, hadamard_rotate_cpu))
+    _quantize_method(method)
+    return _quantize_weights_cpu("mx", _rotated_weights(w, hadamard, hadamard_rotate_cpu), None, method)
 
 
 def quantize_mxfp6_cpu(w: torch.Tensor, hadamard: int = 0) -> torch.Tensor:

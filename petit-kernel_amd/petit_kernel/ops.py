@@ -203,14 +203,21 @@ def _raise_quantize(rc: int, name: str, num_experts: int, size_n: int, size_k: i
     _raise_on(rc, name)
 
 
-def _quantize_weights(kind: str, w: torch.Tensor, global_scale=None):
+def _quantize_method(method) -> int:
+    """The `method=` of quantize_nvfp4 / quantize_mxfp4 and their CPU twins -> PETIT_QUANT_ABSMAX / PETIT_QUANT_SEARCH."""
+    _check(isinstance(method, str) and method in _lib.QUANT_METHODS, "method must be 'absmax' or 'search'")
+    return _lib.QUANT_METHODS[method]
+
+
+def _quantize_weights(kind: str, w: torch.Tensor, global_scale=None, method="absmax"):
+    method = _quantize_method(method)
     E, n, k = _quantize_operands(kind, w, global_scale)
     b, s, gs = _quantize_outputs(kind, E, n, k, w.device)
     ws_bytes = int(_lib.lib.petit_quantize_weights_workspace_bytes(_B_TYPES[kind], E, int(global_scale is not None)))
     ws = _scratch(ws_bytes, w.device)
     with torch.cuda.device(w.device):
-        rc = _lib.lib.petit_quantize_weights(_ptr(w), _a_type(w.dtype), _B_TYPES[kind], E, n, k, _opt_ptr(global_scale), _ptr(b), _ptr(s), _ptr(gs),
-                                             _opt_ptr(ws), C.c_uint64(ws_bytes), _stream(w))
+        rc = _lib.lib.petit_quantize_weights_ex(_ptr(w), _a_type(w.dtype), _B_TYPES[kind], method, E, n, k, _opt_ptr(global_scale), _ptr(b), _ptr(s),
+                                                _ptr(gs), _opt_ptr(ws), C.c_uint64(ws_bytes), _stream(w))
     _raise_quantize(rc, "quantize_%sfp4" % kind, E, n, k)
     return b, s, gs
 
@@ -264,17 +271,21 @@ def _rotated_weights(w: torch.Tensor, hadamard, rotate):
     return rotate(w, block, -(block.bit_length() - 1))
 
 
-def quantize_nvfp4(w: torch.Tensor, global_scale: torch.Tensor = None, hadamard: int = 0):
+def quantize_nvfp4(w: torch.Tensor, global_scale: torch.Tensor = None, hadamard: int = 0, method: str = "absmax"):
     """16-bit weights [N, K] or [E, N, K] -> (b, s, global_scale): the packed NVFP4 tensors repack_nvfp4 / process_nvfp4_scales return for the
     stacked [E * N, K] tensor and float32 [E] global scales, straight into mul_nvfp4_a16 / mul_nvfp4_a16_moe* / fp4_moe* / nvfp4_native_image(s).
     global_scale: None (amax / 2688 per expert) or the caller's float32 [E].  hadamard = 32 / 128: exactly
-    quantize_nvfp4(hadamard_rotate(w, B, -log2 B)), the weights for activations quantised with the same hadamard."""
-    return _quantize_weights("nv", _rotated_weights(w, hadamard, hadamard_rotate), global_scale)
+    quantize_nvfp4(hadamard_rotate(w, B, -log2 B)), the weights for activations quantised with the same hadamard.  method = "search": each
+    block takes the better, by squared error, of today's scale byte and the one that maps its maximum to 4 instead of 6 (MXFP4: one byte
+    lower) -- same tensors, same kernels downstream, less weight error (include/petit_amd.h "The search")."""
+    _quantize_method(method)
+    return _quantize_weights("nv", _rotated_weights(w, hadamard, hadamard_rotate), global_scale, method)
 
 
-def quantize_mxfp4(w: torch.Tensor, hadamard: int = 0):
+def quantize_mxfp4(w: torch.Tensor, hadamard: int = 0, method: str = "absmax"):
     """The same for MXFP4 (OCP MX: one e8m0 scale per 32 k, global_scale = 1): (b, s, global_scale) as repack_mxfp4 / process_mxfp4_scales shape them."""
-    return _quantize_weights("mx", _rotated_weights(w, hadamard, hadamard_rotate))
+    _quantize_method(method)
+    return _quantize_weights("mx", _rotated_weights(w, hadamard, hadamard_rotate), None, method)
 
 
 # --- MXFP6 weights into the native image (include/petit_amd.h "MXFP6 weights on the native class"; no counterpart in the reference) ---------

@@ -2,13 +2,15 @@
 """tools/quantize_weights_bench.py -- time the device weight quantiser (petit_kernel.quantize_nvfp4 / quantize_mxfp4) against a chain of torch ops
 that does the same recipe on the device and then calls repack_* / process_*_scales (what a caller had to write before the quantiser existed).
 
-    python tools/quantize_weights_bench.py [--reps 10] [--quick] [--out profiles/weight_quant.json]
+    python tools/quantize_weights_bench.py --accuracy [--out FILE]          # CPU twins, both methods, no GPU
+    python tools/quantize_weights_bench.py [--reps 10] [--quick] [--method absmax|search] [--shapes default|llama70b] [--no-chain] [--out FILE]
 
 Shapes: a Llama-70B gate_up [57344, 8192] and a stacked expert tensor [128, 1536, 2048], bf16.  The quantiser is timed as graph replays over
 rotating inputs (each copy is 0.8-0.9 GB, beyond the 256 MB Infinity Cache), the chain eagerly with device events (it allocates GBs of f32
 intermediates: part of what it costs).  GB/s counts 2 N K bytes in and 0.5625 N K out (NVFP4; MXFP4 writes 0.53125 N K, counted as such), shown
 next to the copy ceiling DESIGN.md quotes (6.29 TB/s).  The chain's arithmetic is f32 torch, not the contract's exact thresholds: it is a
-comparator for time, not for bits."""
+comparator for time, not for bits.  --method search times the opt-in block-scale search (the same bytes moved, about three times the
+arithmetic); --shapes llama70b takes the four Llama-3-70B linears (qkv, o, gate_up, down)."""
 from __future__ import annotations
 
 import argparse
@@ -22,11 +24,15 @@ ROOT = Path(__file__).resolve().parent.parent
 sys.path.insert(0, str(ROOT / "petit-kernel_amd"))
 sys.path.insert(0, str(ROOT / "tools"))
 
+sys.path.insert(0, str(ROOT / "tests"))
+sys.path.insert(0, str(ROOT))
+
 import benchlib  # noqa: E402
 import petit_kernel as pk  # noqa: E402
 
 COPY_CEILING_TBS = 6.29
 SHAPES = {"llama70b_gate_up": (1, 57344, 8192), "stacked_experts_128": (128, 1536, 2048)}
+LLAMA70B = {"qkv": (1, 10240, 8192), "o": (1, 8192, 8192), "gate_up": (1, 57344, 8192), "down": (1, 8192, 28672)}
 QUICK = {"small_linear": (1, 4096, 4096), "small_experts": (8, 512, 1024)}
 
 
@@ -77,29 +83,90 @@ def time_eager(fn, reps: int) -> list:
     return out
 
 
+def accuracy() -> list:
+    """CPU twins, no GPU: both methods on checkpoint-like weights (tools/quantize_weights.py) through the MLP block of profiles/mxfp6_weights.md
+    (hidden 2048, intermediate 4096, 96 tokens, six input columns x 60) -> weight error over the weight's rms (gate_up) and the block's error
+    over the rms of the bf16-weight block's output, with 16-bit and with MXFP8 activations (NVFP4: on its native image)."""
+    import numpy as np
+    import quantize_weights as QW
+    from petit_kernel import offline
+    from test_gpu_parity import decode_qact
+    from test_quantize_weights_search import unpacked
+    hid, inter, m = 2048, 4096, 96
+    rng = np.random.default_rng(2027)
+    x = rng.standard_normal((m, hid), dtype=np.float32)
+    x[:, rng.choice(hid, 6, replace=False)] *= 60.0
+    xt = torch.from_numpy(x).bfloat16()
+    w1, w2 = QW.synthetic_weights(2 * inter, hid, 31), QW.synthetic_weights(hid, inter, 32)
+
+    def silu_mul(y1):
+        return y1[:, :inter] / (1.0 + np.exp(-y1[:, :inter])) * y1[:, inter:]
+
+    def mxfp8(a16: torch.Tensor):
+        q = offline.quantize_activations_cpu(a16.contiguous(), "mxfp8")
+        return decode_qact(q.data.numpy(), q.m, q.k, "mxfp8").astype(np.float64)
+
+    def weights_q(w, fmt: str, method: str):
+        """-> (the packed tensors' values, the values the native class multiplies by: the NVFP4 tensor re-encoded into its image), float64"""
+        wt = torch.from_numpy(w).bfloat16()
+        n, k = wt.shape
+        b, sp, gs = (offline.quantize_nvfp4_cpu if fmt == "nvfp4" else offline.quantize_mxfp4_cpu)(wt, method=method)
+        dq = unpacked((b.numpy().view(np.uint32).reshape(-1), sp.view(torch.uint8).numpy().reshape(-1), gs.numpy()), n, k, fmt)[0].astype(np.float64)
+        if fmt == "mxfp4":
+            return dq, dq
+        return dq, offline.nvfp4_native_image_dequant_cpu(offline.nvfp4_native_image_cpu(b, sp, n, k), n, k).double().numpy() * float(gs)
+
+    ref = silu_mul(xt.double().numpy() @ w1.astype(np.float64).T) @ w2.astype(np.float64).T
+    rms = float(np.sqrt(np.mean(ref ** 2)))
+    rows = []
+    for fmt in ("nvfp4", "mxfp4"):
+        for method in ("absmax", "search"):
+            (dq1, im1), (dq2, im2) = weights_q(w1, fmt, method), weights_q(w2, fmt, method)
+            werr = lambda dq: float(np.sqrt(np.mean((dq - w1) ** 2) / np.mean(w1.astype(np.float64) ** 2)))  # noqa: E731
+            y16 = silu_mul(xt.double().numpy() @ dq1.T) @ dq2.T
+            h16 = torch.from_numpy(silu_mul(mxfp8(xt) @ im1.T)).bfloat16()      # the 16-bit hand-over between the two GEMMs
+            y8 = mxfp8(h16) @ im2.T
+            row = {"weights": fmt, "method": method, "weight_error_of_weight_rms": werr(dq1), "image_weight_error_of_weight_rms": werr(im1),
+                   "block_error_16bit_activations": float(np.sqrt(np.mean((y16 - ref) ** 2)) / rms),
+                   "block_error_mxfp8_activations_native": float(np.sqrt(np.mean((y8 - ref) ** 2)) / rms)}
+            print(json.dumps(row), flush=True)
+            rows.append(row)
+    return rows
+
+
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument("--accuracy", action="store_true", help="the accuracy part (CPU twins, both methods) instead of the timing part")
     ap.add_argument("--reps", type=int, default=10)
     ap.add_argument("--copies", type=int, default=2)
     ap.add_argument("--quick", action="store_true", help="small shapes: a rehearsal of the script, not a measurement")
+    ap.add_argument("--method", choices=["absmax", "search"], default="absmax", help="the quantiser's block-scale rule")
+    ap.add_argument("--shapes", choices=["default", "llama70b"], default="default")
+    ap.add_argument("--no-chain", action="store_true", help="skip the torch-op comparator")
     ap.add_argument("--out", default="")
     args = ap.parse_args()
+    if args.accuracy:
+        rows = accuracy()
+        if args.out:
+            Path(args.out).write_text(json.dumps(rows, indent=1) + "\n")
+        return
     assert torch.cuda.is_available(), "this benchmark measures the GPU; there is nothing to report without one"
     stream = torch.cuda.Stream()
     rows = []
-    for name, (E, n, k) in (QUICK if args.quick else SHAPES).items():
+    method = args.method
+    for name, (E, n, k) in (QUICK if args.quick else LLAMA70B if args.shapes == "llama70b" else SHAPES).items():
         gen = torch.Generator(device="cuda").manual_seed(0)
         ws = [(torch.randn((E, n, k), device="cuda", generator=gen) / k ** 0.5).bfloat16() for _ in range(args.copies)]
         gs_in = torch.full((E,), 2.0 ** -12, device="cuda")
-        forms = {"nvfp4": (lambda w: pk.quantize_nvfp4(w), chain_nvfp4, 2.5625),
-                 "nvfp4_gs_supplied": (lambda w: pk.quantize_nvfp4(w, gs_in), None, 2.5625),
-                 "mxfp4": (lambda w: pk.quantize_mxfp4(w), chain_mxfp4, 2.53125)}
+        forms = {"nvfp4": (lambda w: pk.quantize_nvfp4(w, method=method), chain_nvfp4, 2.5625),
+                 "nvfp4_gs_supplied": (lambda w: pk.quantize_nvfp4(w, gs_in, method=method), None, 2.5625),
+                 "mxfp4": (lambda w: pk.quantize_mxfp4(w, method=method), chain_mxfp4, 2.53125)}
         for form, (quant, chain, bytes_per_weight) in forms.items():
             nbytes = bytes_per_weight * E * n * k
             us = benchlib.median(benchlib.time_graph(lambda i: quant(ws[i % len(ws)]), len(ws), args.reps, stream))
-            row = {"shape": name, "E": E, "n": n, "k": k, "form": form, "us": round(us, 1), "GBps": round(nbytes / us / 1e3, 1),
+            row = {"shape": name, "E": E, "n": n, "k": k, "form": form, "method": method, "us": round(us, 1), "GBps": round(nbytes / us / 1e3, 1),
                    "of_copy_ceiling": round(nbytes / us / 1e6 / COPY_CEILING_TBS, 3)}
-            if chain is not None:
+            if chain is not None and not args.no_chain:
                 chain_us = benchlib.median(time_eager(lambda: chain(ws[0]), max(3, args.reps // 3)))
                 row.update(torch_chain_us=round(chain_us, 1), speedup_over_chain=round(chain_us / us, 2))
             print(json.dumps(row), flush=True)
