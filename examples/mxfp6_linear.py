@@ -8,7 +8,8 @@ stacked experts through the batch-invariant MoE launch.  Needs an MI355X.
 quantize_mxfp6 writes the MFMA-native image the NVFP4 path already runs on (FP6 e2m3 elements, one E8M0 scale per 32 k) straight from the
 16-bit weights: 6.25 bits per weight, 4 significant bits per element where the FP4 formats keep 2, and the same GEMM kernels at the same rate.
 The image goes to mul_nvfp4_native / mul_nvfp4_native_invariant / mul_nvfp4_native_moe / mul_nvfp4_native_moe_invariant with a global scale
-of 1.0.  An MXFP6 checkpoint (OCP e2m3 bit stream + e8m0 scales) takes mxfp6_native_image instead: a copy into the same image, no rounding.
+of 1.0.  An MXFP6 checkpoint (OCP e2m3 bit stream + e8m0 scales) takes mxfp6_native_image instead: a copy into the same image, no rounding;
+mxfp6_export is the way back (image -> OCP tensor, to save what quantize_mxfp6 produced) and dequant_native_image expands an image to 16 bit.
 """
 import sys
 from pathlib import Path
@@ -52,7 +53,15 @@ def main() -> None:
 
     w = (torch.randn(n, k, generator=g) * 0.02).bfloat16().to(dev)
     ref = xn @ w.float().T
-    print(f"MXFP6 weights, MXFP8 activations: rms error {err(Mxfp6Linear(w, norm_w)(x), ref):4.1f} % of the bf16 layer's output rms")
+    layer = Mxfp6Linear(w, norm_w)
+    print(f"MXFP6 weights, MXFP8 activations: rms error {err(layer(x), ref):4.1f} % of the bf16 layer's output rms")
+    # save / reload: the image is instruction-shaped; mxfp6_export turns it into the OCP MXFP6 tensor any loader reads, and back without rounding
+    elems, scales = petit_kernel.mxfp6_export(layer.image, n, k)
+    state = {"weight.elems": elems.cpu(), "weight.scales": scales.cpu()}              # what a checkpoint would hold: 6.25 bits per weight
+    reloaded = petit_kernel.mxfp6_native_image(state["weight.elems"].to(dev), state["weight.scales"].to(dev), n, k)
+    w6 = petit_kernel.dequant_native_image(reloaded, n, k)                            # the weights the image holds, in bf16 (exact)
+    print(f"export -> checkpoint -> image: same bytes: {torch.equal(reloaded, layer.image)}; "
+          f"weight error {err(w6, w.float()):4.1f} % of the weight's rms")
     b, s, gs = petit_kernel.quantize_nvfp4(w)
     q = petit_kernel.rmsnorm_quantize(x, norm_w, 1e-6, "mxfp8")
     y4 = petit_kernel.mul_nvfp4_native_invariant(q, petit_kernel.nvfp4_native_image(b, s, n, k), gs, m, n, k, "mxfp8")

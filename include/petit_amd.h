@@ -637,6 +637,40 @@ int petit_mxfp6_native_images(void *images, const void *elems, const void *scale
 int petit_mxfp6_native_images_host(void *images, const void *elems, const void *scales, unsigned num_experts, unsigned n, unsigned k);
 
 /*
+ * Reading an image back (no counterpart in the reference).
+ *
+ * The native image ("petit-cdna4-nv6/1") is laid out for the block-scaled MFMA and for nothing else.  These entries read it on the device: into
+ * row-major 16-bit or f32 weights (a 16-bit GEMM through another library, a LoRA merge, a numerical cross-check), or into the OCP MXFP6 (e2m3)
+ * tensor that petit_mxfp6_native_images takes (a portable checkpoint of what petit_quantize_weights_mxfp6 produced).  They work on any image,
+ * whatever wrote it.
+ *
+ *   petit_native_images_dequant(out, out_type, images, global_scales, num_experts, n, k, stream)
+ *       images          num_experts images back to back at petit_nvfp4_native_image_bytes(k, n) each; 256-byte aligned
+ *       out             row-major [num_experts][n][k] in out_type: PETIT_DTYPE_FP32, PETIT_DTYPE_BF16 or PETIT_DTYPE_FP16; 16-byte aligned.
+ *                       Only rows < n are written: the padding rows of the last 32-row block of an image are never read out.
+ *       global_scales   NULL (1.0: an MXFP6 image) or float32 [num_experts] (an NVFP4-derived image)
+ *     The rule, per element:  v = e2m3(code) x 2^(byte - 127), an exact f32 number for every code and byte (2^128 and above: +-inf; byte 0 is
+ *     2^-127);  p = v when global_scales is NULL, else v x global_scales[e] as ONE f32 multiply;  out = p, or p rounded to nearest even to the
+ *     16-bit type.  bf16 without a global scale is exact; fp16 overflows to +-inf and rounds into its subnormals as the standard conversion
+ *     does; the sign of a zero is kept.  A block whose scale byte is 255 (E8M0's NaN) reads as quiet NaNs (0x7fc00000 and its 16-bit forms).
+ *   petit_mxfp6_export_images(elems, scales, images, num_experts, n, k, stream)
+ *       the exact inverse of petit_mxfp6_native_images: elems [num_experts][n][3 k / 4] bytes (element e of a row at bits [6 e, 6 e + 6) of the
+ *       row's little-endian bit stream; 16-byte aligned), scales [num_experts][n][k / 32] E8M0 bytes.  Copied, never rounded: a lane's 192 bits
+ *       in the image ARE the block's 24 OCP bytes.  The export of an NVFP4-derived image is a valid MXFP6 tensor of the re-encoded weights
+ *       (to be used with that image's global scale).
+ *   ..._host    the CPU twins on host memory, bit-identical.
+ * Errors, all before any launch and in this order: PETIT_ERROR_BAD_ARGUMENT for an out_type outside the three; PETIT_ERROR_PROBLEM_SHAPE for
+ * num_experts outside 1 .. PETIT_MOE_MAX_EXPERTS, n % 16, k % 256 or an element part of 2^32 bytes or more; n or k == 0 returns PETIT_OK;
+ * PETIT_ERROR_BAD_ARGUMENT for misaligned or null pointers.  One launch each, no scratch, no host sync, no allocation: capturable.
+ */
+int petit_native_images_dequant(void *out, int out_type, const void *images, const float *global_scales, unsigned num_experts, unsigned n,
+                                unsigned k, void *stream);
+int petit_native_images_dequant_host(void *out, int out_type, const void *images, const float *global_scales, unsigned num_experts, unsigned n,
+                                     unsigned k);
+int petit_mxfp6_export_images(void *elems, void *scales, const void *images, unsigned num_experts, unsigned n, unsigned k, void *stream);
+int petit_mxfp6_export_images_host(void *elems, void *scales, const void *images, unsigned num_experts, unsigned n, unsigned k);
+
+/*
  * Grouped launch (no counterpart in the reference): up to PETIT_GROUP_MAX weight matrices that share the activation rows --
  * q / k / v (or their tensor-parallel shards) kept as separate tensors, gate and up, the experts a token routes to -- in ONE
  * kernel launch: c_i[m][n_i] = a[m][k] . dequant(b_i)[n_i][k]^T * (*global_scale_i) (+ bias_i).  At decode batch sizes a

@@ -174,6 +174,21 @@ int petit_mxfp6_native_images(void *images, const void *elems, const void *scale
 int petit_mxfp6_native_images_host(void *images, const void *elems, const void *scales, unsigned num_experts, unsigned n, unsigned k) {
     return mxfp6_native_images_host(images, elems, scales, num_experts, n, k);
 }
+// an image read back (native_image_readback.hip makes every check: the device forms and their host twins refuse the same calls)
+int petit_native_images_dequant(void *out, int out_type, const void *images, const float *global_scales, unsigned num_experts, unsigned n,
+                                unsigned k, void *stream) {
+    return native_images_dequant(out, out_type, images, global_scales, num_experts, n, k, (hipStream_t)stream);
+}
+int petit_native_images_dequant_host(void *out, int out_type, const void *images, const float *global_scales, unsigned num_experts, unsigned n,
+                                     unsigned k) {
+    return native_images_dequant_host(out, out_type, images, global_scales, num_experts, n, k);
+}
+int petit_mxfp6_export_images(void *elems, void *scales, const void *images, unsigned num_experts, unsigned n, unsigned k, void *stream) {
+    return mxfp6_export_images(elems, scales, images, num_experts, n, k, (hipStream_t)stream);
+}
+int petit_mxfp6_export_images_host(void *elems, void *scales, const void *images, unsigned num_experts, unsigned n, unsigned k) {
+    return mxfp6_export_images_host(elems, scales, images, num_experts, n, k);
+}
 
 int petit_nvfp4_native_attach(const void *b, const void *image) {
     if (!b || ((uintptr_t)image & 255))

@@ -204,6 +204,15 @@ int mxfp6_quantize_weights(const void *w, int a_type, unsigned num_experts, unsi
 int mxfp6_quantize_weights_host(const void *w, int a_type, unsigned num_experts, unsigned n, unsigned k, void *images);
 int mxfp6_native_images(void *images, const void *elems, const void *scales, unsigned num_experts, unsigned n, unsigned k, hipStream_t stream);
 int mxfp6_native_images_host(void *images, const void *elems, const void *scales, unsigned num_experts, unsigned n, unsigned k);
+// native_image_readback.hip: num_experts images back to back -> row-major [E][n][k] in out_type (PETIT_DTYPE_FP32 / kDataTypeBf16 / kDataTypeFp16;
+// global_scales: null or f32 [E]), or -> the OCP MXFP6 tensor mxfp6_native_images reads (no rounding); include/petit_amd.h "Reading an image
+// back"; host twins, bit-identical
+int native_images_dequant(void *out, int out_type, const void *images, const float *global_scales, unsigned num_experts, unsigned n, unsigned k,
+                          hipStream_t stream);
+int native_images_dequant_host(void *out, int out_type, const void *images, const float *global_scales, unsigned num_experts, unsigned n,
+                               unsigned k);
+int mxfp6_export_images(void *elems, void *scales, const void *images, unsigned num_experts, unsigned n, unsigned k, hipStream_t stream);
+int mxfp6_export_images_host(void *elems, void *scales, const void *images, unsigned num_experts, unsigned n, unsigned k);
 // rmsnorm_quant.hip: (residual add +) RMSNorm -> "petit-qact/1" bytes in one launch (include/petit_amd.h "RMSNorm into quantised activations");
 // host twin, bit-identical.  Both make every check of the contract.
 int rmsnorm_quantize(void *qa, void *y16, void *residual_out, const void *x, const void *residual, const void *weight, float eps,

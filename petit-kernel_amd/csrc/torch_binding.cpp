@@ -263,6 +263,63 @@ at::Tensor mxfp6_native_image_meta(const at::Tensor &elems, const at::Tensor &sc
     return mxfp6_native_image_impl(elems, scales, n, k, false);
 }
 
+// an image read back (petit_native_images_dequant / petit_mxfp6_export_images); the same checks and texts as petit_kernel/ops.py
+// _readback_experts / _dequant_image_operands / _export_image_operands.  readback_experts counts the images for the real ops and their Meta twins.
+int64_t readback_experts(const at::Tensor &images, int64_t n, int64_t k, bool real) {
+    TORCH_CHECK(images.scalar_type() == at::kByte && (!real || (images.is_cuda() && images.is_contiguous())),
+                "images must be a contiguous uint8 GPU tensor");
+    TORCH_CHECK(k % (2 * kLayoutM) == 0, "size_k = ", k, " is not divisible by tile_k_size = ", 2 * kLayoutM);
+    TORCH_CHECK(n % kLayoutN == 0, "size_n = ", n, " is not divisible by tile_n_size = ", kLayoutN);
+    const int64_t per = (int64_t)petit_nvfp4_native_image_bytes((unsigned)k, (unsigned)n);
+    TORCH_CHECK(per > 0, "no native image for size_n=", n, ", size_k=", k);
+    TORCH_CHECK(images.numel() > 0 && images.numel() % per == 0, "images does not hold whole native images of size_n=", n, ", size_k=", k, " (", per,
+                " bytes each)");
+    const int64_t E = images.numel() / per;
+    TORCH_CHECK(E <= PETIT_MOE_MAX_EXPERTS, "num_experts must be in 1..", PETIT_MOE_MAX_EXPERTS, ", got ", E);
+    return E;
+}
+at::Tensor dequant_native_image_impl(const at::Tensor &images, int64_t n, int64_t k, at::ScalarType dtype,
+                                     const std::optional<at::Tensor> &global_scale, bool real) {
+    TORCH_CHECK(dtype == at::kFloat || dtype == at::kBFloat16 || dtype == at::kHalf, "dtype must be torch.float32, torch.bfloat16 or torch.float16");
+    const int64_t E = readback_experts(images, n, k, real);
+    if (global_scale.has_value())
+        TORCH_CHECK(global_scale->device() == images.device() && global_scale->scalar_type() == at::kFloat && global_scale->is_contiguous() &&
+                        global_scale->numel() == E,
+                    "global_scale must be a contiguous float32 tensor of one element per image on images' device");
+    at::Tensor out = E > 1 ? at::empty({E, n, k}, images.options().dtype(dtype)) : at::empty({n, k}, images.options().dtype(dtype));
+    if (!real)
+        return out;
+    const c10::hip::HIPGuardMasqueradingAsCUDA guard(images.device());
+    const int rc = petit_native_images_dequant(out.data_ptr(), dtype == at::kFloat ? PETIT_DTYPE_FP32 : a_type_of(dtype), images.data_ptr(),
+                                               global_scale.has_value() ? (const float *)global_scale->data_ptr() : nullptr, (unsigned)E,
+                                               (unsigned)n, (unsigned)k, stream_of(images));
+    TORCH_CHECK(rc != PETIT_ERROR_PROBLEM_SHAPE, "Incompatible problem shape (num_experts=", E, ", n=", n, ", k=", k, ")");
+    TORCH_CHECK(rc == PETIT_OK, "dequant_native_image: ", petit_error_string(rc));
+    return out;
+}
+at::Tensor dequant_native_image(const at::Tensor &images, int64_t n, int64_t k, at::ScalarType dtype, const std::optional<at::Tensor> &global_scale) {
+    return dequant_native_image_impl(images, n, k, dtype, global_scale, true);
+}
+at::Tensor dequant_native_image_meta(const at::Tensor &images, int64_t n, int64_t k, at::ScalarType dtype,
+                                     const std::optional<at::Tensor> &global_scale) {
+    return dequant_native_image_impl(images, n, k, dtype, global_scale, false);
+}
+std::tuple<at::Tensor, at::Tensor> mxfp6_export_impl(const at::Tensor &images, int64_t n, int64_t k, bool real) {
+    const int64_t E = readback_experts(images, n, k, real);
+    at::Tensor elems = E > 1 ? at::empty({E, n, k / 4 * 3}, images.options()) : at::empty({n, k / 4 * 3}, images.options());
+    at::Tensor scales = E > 1 ? at::empty({E, n, k / 32}, images.options()) : at::empty({n, k / 32}, images.options());
+    if (!real)
+        return {elems, scales};
+    const c10::hip::HIPGuardMasqueradingAsCUDA guard(images.device());
+    const int rc = petit_mxfp6_export_images(elems.data_ptr(), scales.data_ptr(), images.data_ptr(), (unsigned)E, (unsigned)n, (unsigned)k,
+                                             stream_of(images));
+    TORCH_CHECK(rc != PETIT_ERROR_PROBLEM_SHAPE, "Incompatible problem shape (num_experts=", E, ", n=", n, ", k=", k, ")");
+    TORCH_CHECK(rc == PETIT_OK, "mxfp6_export: ", petit_error_string(rc));
+    return {elems, scales};
+}
+std::tuple<at::Tensor, at::Tensor> mxfp6_export(const at::Tensor &images, int64_t n, int64_t k) { return mxfp6_export_impl(images, n, k, true); }
+std::tuple<at::Tensor, at::Tensor> mxfp6_export_meta(const at::Tensor &images, int64_t n, int64_t k) { return mxfp6_export_impl(images, n, k, false); }
+
 // block-Hadamard rotation to 16 bit (petit_hadamard_rows); the same checks and texts as petit_kernel/ops.py _hadamard_operands
 void hadamard_rotate_out(const at::Tensor &x, int64_t block, int64_t log2_scale, at::Tensor out) {
     TORCH_CHECK(block == 32 || block == 128, "block must be 32 or 128");
@@ -1166,6 +1223,8 @@ TORCH_LIBRARY(petit_kernel, m) {
     m.def("quantize_weights(Tensor w, int b_type, Tensor? global_scale=None, int method=0) -> (Tensor, Tensor, Tensor)");
     m.def("quantize_mxfp6(Tensor w) -> Tensor");
     m.def("mxfp6_native_image(Tensor elems, Tensor scales, int size_n, int size_k) -> Tensor");
+    m.def("dequant_native_image(Tensor images, int size_n, int size_k, ScalarType dtype, Tensor? global_scale=None) -> Tensor");
+    m.def("mxfp6_export(Tensor images, int size_n, int size_k) -> (Tensor, Tensor)");
     m.def("hadamard_rotate(Tensor x, int block, int log2_scale=0) -> Tensor");
     m.def("hadamard_rotate_out(Tensor x, int block, int log2_scale, Tensor(a!) out) -> ()");
     m.def("mul_nvfp4_a16(Tensor A, Tensor B, Tensor s, Tensor global_scale, int size_m, int size_n, int size_k, int solution_id, "
@@ -1242,6 +1301,8 @@ TORCH_LIBRARY(petit_kernel, m) {
     m.impl("quantize_weights", &quantize_weights);              \
     m.impl("quantize_mxfp6", &quantize_mxfp6);                  \
     m.impl("mxfp6_native_image", &mxfp6_native_image);          \
+    m.impl("dequant_native_image", &dequant_native_image);      \
+    m.impl("mxfp6_export", &mxfp6_export);                      \
     m.impl("hadamard_rotate", &hadamard_rotate);                \
     m.impl("hadamard_rotate_out", &hadamard_rotate_out);        \
     m.impl("mul_nvfp4_a16", &mul_nvfp4_a16);                    \
@@ -1285,6 +1346,8 @@ TORCH_LIBRARY_IMPL(petit_kernel, Meta, m) {
     m.impl("quantize_weights", &quantize_weights_meta);
     m.impl("quantize_mxfp6", &quantize_mxfp6_meta);
     m.impl("mxfp6_native_image", &mxfp6_native_image_meta);
+    m.impl("dequant_native_image", &dequant_native_image_meta);
+    m.impl("mxfp6_export", &mxfp6_export_meta);
     m.impl("hadamard_rotate", &hadamard_rotate_meta);
     m.impl("hadamard_rotate_out", &hadamard_rotate_out_meta);
     m.impl("mul_nvfp4_a16", &mul_a16_meta);

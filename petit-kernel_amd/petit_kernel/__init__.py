@@ -94,6 +94,20 @@ def mxfp6_native_image(elems: torch.Tensor, scales: torch.Tensor, size_n: int, s
     return _impl.mxfp6_native_image(elems, scales, size_n, size_k)
 
 
+def dequant_native_image(images: torch.Tensor, size_n: int, size_k: int, dtype: torch.dtype = torch.bfloat16,
+                         global_scale: torch.Tensor = None) -> torch.Tensor:
+    # native image(s), whatever wrote them -> the weights they hold, row-major [N, K] (or [E, N, K] for E > 1 images back to back) in float32 /
+    # bfloat16 / float16 (include/petit_amd.h "Reading an image back"): element x 2^(scale - 127), times global_scale[e] (float32 [E], for an
+    # NVFP4-derived image) as one f32 multiply, one rounding.  Host twin: offline.dequant_native_image_cpu
+    return _impl.dequant_native_image(images, size_n, size_k, dtype, global_scale)
+
+
+def mxfp6_export(images: torch.Tensor, size_n: int, size_k: int):
+    # native image(s) -> (elems, scales), the OCP MXFP6 (e2m3) tensor mxfp6_native_image takes: the exact inverse, nothing is rounded -- a
+    # portable checkpoint of what quantize_mxfp6 produced.  Host twin: offline.mxfp6_export_cpu
+    return _impl.mxfp6_export(images, size_n, size_k)
+
+
 def mxfp4_scales_in_fp16_range(raw_scales: torch.Tensor) -> bool:
     """A diagnostic, not an input of any call: True when every e8m0 byte of the RAW (unprocessed) MXFP4 scale tensor lies in 114..140, i.e. when
     fp16 activations run the single-MFMA body in every wave (a wave that meets a byte outside that range finishes its K range in the exact
@@ -444,6 +458,8 @@ __all__ = [
     "quantize_mxfp4",
     "quantize_mxfp6",
     "mxfp6_native_image",
+    "dequant_native_image",
+    "mxfp6_export",
     "hadamard_rotate",
     "mul_nvfp4_a16",
     "mul_mxfp4_a16",

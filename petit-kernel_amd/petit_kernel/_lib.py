@@ -192,6 +192,10 @@ _SIGNATURES = {
     "petit_quantize_weights_mxfp6_host": (C.c_int, [C.c_void_p, C.c_int] + [C.c_uint] * 3 + [C.c_void_p]),
     "petit_mxfp6_native_images": (C.c_int, [C.c_void_p] * 3 + [C.c_uint] * 3 + [C.c_void_p]),
     "petit_mxfp6_native_images_host": (C.c_int, [C.c_void_p] * 3 + [C.c_uint] * 3),
+    "petit_native_images_dequant": (C.c_int, [C.c_void_p, C.c_int] + [C.c_void_p] * 2 + [C.c_uint] * 3 + [C.c_void_p]),
+    "petit_native_images_dequant_host": (C.c_int, [C.c_void_p, C.c_int] + [C.c_void_p] * 2 + [C.c_uint] * 3),
+    "petit_mxfp6_export_images": (C.c_int, [C.c_void_p] * 3 + [C.c_uint] * 3 + [C.c_void_p]),
+    "petit_mxfp6_export_images_host": (C.c_int, [C.c_void_p] * 3 + [C.c_uint] * 3),
     "petit_nvfp4_native_attach": (C.c_int, [C.c_void_p, C.c_void_p]),
     "petit_nvfp4_native_attached": (C.c_void_p, [C.c_void_p]),
     "petit_gemm_nvfp4_native": (C.c_int, [C.c_void_p] * 4 + [C.c_uint] * 3 + [C.POINTER(SolutionHints), C.c_uint64, C.POINTER(Epilogue),

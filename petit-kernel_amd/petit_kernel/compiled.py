@@ -105,6 +105,14 @@ def mxfp6_native_image(elems, scales, size_n, size_k):
     return torch.ops.petit_kernel.mxfp6_native_image(elems, scales, int(size_n), int(size_k))
 
 
+def dequant_native_image(images, size_n, size_k, dtype=torch.bfloat16, global_scale=None):
+    return torch.ops.petit_kernel.dequant_native_image(images, int(size_n), int(size_k), dtype, global_scale)
+
+
+def mxfp6_export(images, size_n, size_k):
+    return torch.ops.petit_kernel.mxfp6_export(images, int(size_n), int(size_k))
+
+
 def mul_nvfp4_a16(A, B, s, global_scale, size_m, size_n, size_k, solution_id, bias=None, activation=None):
     return torch.ops.petit_kernel.mul_nvfp4_a16(A, B, s, global_scale, size_m, size_n, size_k, _sid(solution_id), bias, _act(activation))
 

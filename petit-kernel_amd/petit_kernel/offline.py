@@ -16,6 +16,7 @@ from .ops import _B_TYPES, _LAYOUT_M, _LAYOUT_N, _PACK, _QFORMATS, _a_type, _che
 from .ops import _quantize_method, _raise_quantize, _rmsnorm_operands, _rmsnorm_outputs, _rmsnorm_result
 from .ops import QuantizedActivations, _HADAMARD_FP6, _hadamard_block, _hadamard_operands, _rotated_weights
 from .ops import _mxfp6_ingest_operands, _mxfp6_quantize_operands
+from .ops import _READBACK_DTYPES, _dequant_image_operands, _export_image_operands
 from .ops import _combine_norm_operands, _combine_norm_outputs, _combine_norm_result, _combine_norm_returns
 
 
@@ -113,6 +114,23 @@ def mxfp6_native_image_cpu(elems: torch.Tensor, scales: torch.Tensor, size_n: in
     _raise_quantize(_lib.lib.petit_mxfp6_native_images_host(images.data_ptr(), elems.data_ptr(), scales.data_ptr(), E, size_n, size_k),
                     "mxfp6_native_image_cpu", E, size_n, size_k)
     return images
+
+
+def dequant_native_image_cpu(images: torch.Tensor, size_n: int, size_k: int, dtype: torch.dtype = torch.bfloat16,
+                             global_scale: torch.Tensor = None) -> torch.Tensor:
+    """CPU twin of petit_kernel.dequant_native_image: the same arguments on CPU tensors, the same bits."""
+    E, out = _dequant_image_operands(images, size_n, size_k, dtype, global_scale, on_gpu=False)
+    rc = _lib.lib.petit_native_images_dequant_host(out.data_ptr(), _READBACK_DTYPES[dtype], images.data_ptr(), _opt_ptr(global_scale), E, size_n, size_k)
+    _raise_quantize(rc, "dequant_native_image_cpu", E, size_n, size_k)
+    return out
+
+
+def mxfp6_export_cpu(images: torch.Tensor, size_n: int, size_k: int):
+    """CPU twin of petit_kernel.mxfp6_export: native image(s) -> (elems, scales), the inverse of mxfp6_native_image_cpu."""
+    E, elems, scales = _export_image_operands(images, size_n, size_k, on_gpu=False)
+    _raise_quantize(_lib.lib.petit_mxfp6_export_images_host(elems.data_ptr(), scales.data_ptr(), images.data_ptr(), E, size_n, size_k),
+                    "mxfp6_export_cpu", E, size_n, size_k)
+    return elems, scales
 
 
 # --- the activation quantiser, on the CPU (petit_quantize_activations_host / _rot_host) -------------------------------------------------------------

@@ -345,6 +345,65 @@ def mxfp6_native_image(elems: torch.Tensor, scales: torch.Tensor, size_n: int, s
     return images
 
 
+# --- an image read back (include/petit_amd.h "Reading an image back"; no counterpart in the reference) ------------------------------------
+
+_READBACK_DTYPES = {torch.float32: _lib.PETIT_DTYPE_FP32, torch.bfloat16: _lib.CXX_DTYPE_BF16, torch.float16: _lib.CXX_DTYPE_FP16}
+
+
+def _readback_experts(images: torch.Tensor, size_n: int, size_k: int, on_gpu: bool = True) -> int:
+    """images: uint8, whole native images of [size_n, size_k] weights back to back -> how many (the rules dequant_native_image / mxfp6_export
+    and their CPU twins share)."""
+    _check(images.dtype == torch.uint8 and images.is_cuda == on_gpu and images.is_contiguous(),
+           f"images must be a contiguous uint8 {'GPU' if on_gpu else 'CPU'} tensor")
+    per = _mxfp6_image_bytes(1, size_n, size_k)
+    _check(images.numel() > 0 and images.numel() % per == 0,
+           f"images does not hold whole native images of size_n={size_n}, size_k={size_k} ({per} bytes each)")
+    E = images.numel() // per
+    _check(E <= _lib.PETIT_MOE_MAX_EXPERTS, f"num_experts must be in 1..{_lib.PETIT_MOE_MAX_EXPERTS}, got {E}")
+    return E
+
+
+def _dequant_image_operands(images: torch.Tensor, size_n: int, size_k: int, dtype, global_scale, on_gpu: bool = True):
+    """-> (num_experts, out): out [size_n, size_k], or [num_experts, size_n, size_k] for more than one image."""
+    _check(dtype in _READBACK_DTYPES, "dtype must be torch.float32, torch.bfloat16 or torch.float16")
+    E = _readback_experts(images, size_n, size_k, on_gpu)
+    if global_scale is not None:
+        _check(global_scale.device == images.device and global_scale.dtype == torch.float32 and global_scale.is_contiguous() and
+               global_scale.numel() == E, "global_scale must be a contiguous float32 tensor of one element per image on images' device")
+    return E, torch.empty((E, size_n, size_k) if E > 1 else (size_n, size_k), dtype=dtype, device=images.device)
+
+
+def _export_image_operands(images: torch.Tensor, size_n: int, size_k: int, on_gpu: bool = True):
+    """-> (num_experts, elems, scales) as mxfp6_native_image takes them"""
+    E = _readback_experts(images, size_n, size_k, on_gpu)
+    lead = (E,) if E > 1 else ()
+    return (E, torch.empty(lead + (size_n, size_k // 4 * 3), dtype=torch.uint8, device=images.device),
+            torch.empty(lead + (size_n, size_k // 32), dtype=torch.uint8, device=images.device))
+
+
+def dequant_native_image(images: torch.Tensor, size_n: int, size_k: int, dtype: torch.dtype = torch.bfloat16,
+                         global_scale: torch.Tensor = None) -> torch.Tensor:
+    """Native image(s) (quantize_mxfp6, mxfp6_native_image, nvfp4_native_image(s)) -> the weights they hold, row-major [N, K], or [E, N, K] for
+    E > 1 images back to back (E = images.numel() / bytes of one image): e2m3 element x 2^(scale byte - 127), times global_scale[e] (float32 [E];
+    None = 1.0) as one f32 multiply, rounded once to dtype (float32: no rounding; bfloat16 without a global scale: exact)."""
+    E, out = _dequant_image_operands(images, size_n, size_k, dtype, global_scale)
+    with torch.cuda.device(images.device):
+        rc = _lib.lib.petit_native_images_dequant(_ptr(out), _READBACK_DTYPES[dtype], _ptr(images), _opt_ptr(global_scale), E, size_n, size_k,
+                                                  _stream(images))
+    _raise_quantize(rc, "dequant_native_image", E, size_n, size_k)
+    return out
+
+
+def mxfp6_export(images: torch.Tensor, size_n: int, size_k: int):
+    """Native image(s) -> (elems, scales): the OCP MXFP6 (e2m3) tensor mxfp6_native_image turns into the same image bytes -- uint8
+    [N, 3 K / 4] and uint8 e8m0 [N, K / 32], or [E, ...] for E > 1 images.  Copied, never rounded."""
+    E, elems, scales = _export_image_operands(images, size_n, size_k)
+    with torch.cuda.device(images.device):
+        rc = _lib.lib.petit_mxfp6_export_images(_ptr(elems), _ptr(scales), _ptr(images), E, size_n, size_k, _stream(images))
+    _raise_quantize(rc, "mxfp6_export", E, size_n, size_k)
+    return elems, scales
+
+
 _ACTIVATIONS = {None: 0, "none": 0, "silu_mul": 1, "swiglu_oai": 2}   # PETIT_ACTIVATION_* (include/petit_amd.h)
 _B_TYPES = {"nv": _lib.CXX_DTYPE_FP4_E2M1, "nvfp4": _lib.CXX_DTYPE_FP4_E2M1, "mx": _lib.CXX_DTYPE_MXFP4_E2M1, "mxfp4": _lib.CXX_DTYPE_MXFP4_E2M1}
 _ACTIVATION_RULE = f"activation must be one of {sorted(k for k in _ACTIVATIONS if k)} or None"

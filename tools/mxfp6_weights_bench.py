@@ -61,7 +61,9 @@ def accuracy() -> dict:
         return decode_qact(q.data.numpy(), q.m, q.k, fmt).astype(np.float64)
 
     def image_values(image: torch.Tensor, n: int, k: int) -> np.ndarray:
-        return offline.nvfp4_native_image_dequant_cpu(image, n, k).double().numpy()
+        if torch.cuda.is_available():   # the device dequantiser (f32: exact); its CPU twin, the same bits, without a GPU
+            return pk.dequant_native_image(image.cuda(), n, k, torch.float32).cpu().double().numpy()
+        return offline.dequant_native_image_cpu(image, n, k, torch.float32).double().numpy()
 
     def weights_q(w: np.ndarray, wfmt: str, block: int) -> np.ndarray:
         wt = torch.from_numpy(w).bfloat16()

@@ -114,7 +114,10 @@ def accuracy() -> list:
         dq = unpacked((b.numpy().view(np.uint32).reshape(-1), sp.view(torch.uint8).numpy().reshape(-1), gs.numpy()), n, k, fmt)[0].astype(np.float64)
         if fmt == "mxfp4":
             return dq, dq
-        return dq, offline.nvfp4_native_image_dequant_cpu(offline.nvfp4_native_image_cpu(b, sp, n, k), n, k).double().numpy() * float(gs)
+        image = offline.nvfp4_native_image_cpu(b, sp, n, k)
+        if torch.cuda.is_available():   # the device dequantiser (f32: exact); its CPU twin, the same bits, without a GPU
+            return dq, pk.dequant_native_image(image.cuda(), n, k, torch.float32).cpu().double().numpy() * float(gs)
+        return dq, offline.dequant_native_image_cpu(image, n, k, torch.float32).double().numpy() * float(gs)
 
     ref = silu_mul(xt.double().numpy() @ w1.astype(np.float64).T) @ w2.astype(np.float64).T
     rms = float(np.sqrt(np.mean(ref ** 2)))
