@@ -1,6 +1,7 @@
 #!/usr/bin/env python3
 """examples/mxfp6_linear.py -- MXFP6 weights on the native class (include/petit_amd.h "MXFP6 weights on the native class"): a bf16 linear
-quantised on the device by quantize_mxfp6, run as RMSNorm -> MXFP8 activations -> the batch-invariant native-class GEMM, and a layer of
+quantised on the device by quantize_mxfp6, run as RMSNorm -> MXFP8 activations -> the batch-invariant native-class GEMM (up to 32 rows: the
+decode GEMM on the image, mul_nvfp4_native_decode), and a layer of
 stacked experts through the batch-invariant MoE launch.  Needs an MI355X.
 
     python examples/mxfp6_linear.py
@@ -34,6 +35,8 @@ class Mxfp6Linear(torch.nn.Module):
 
     def forward(self, x: torch.Tensor, expert_offsets: torch.Tensor = None) -> torch.Tensor:
         q = petit_kernel.rmsnorm_quantize(x, self.norm_weight, self.eps, self.fmt)    # norm + quantiser: one launch
+        if not self.experts and q.m <= 32:   # a decode step: the image as a weight stream (no global scale; its accumulation order moves with the shape)
+            return petit_kernel.mul_nvfp4_native_decode(q, self.image, None, q.m, self.size_n, self.size_k, self.fmt)
         if not self.experts:
             return petit_kernel.mul_nvfp4_native_invariant(q, self.image, self.ones, q.m, self.size_n, self.size_k, self.fmt)
         return petit_kernel.mul_nvfp4_native_moe_invariant(q, self.image, self.ones, expert_offsets, q.m, self.size_n, self.size_k, self.experts,
@@ -55,6 +58,7 @@ def main() -> None:
     ref = xn @ w.float().T
     layer = Mxfp6Linear(w, norm_w)
     print(f"MXFP6 weights, MXFP8 activations: rms error {err(layer(x), ref):4.1f} % of the bf16 layer's output rms")
+    print(f"the same layer on 4 rows (mul_nvfp4_native_decode): rms error {err(layer(x[:4]), ref[:4]):4.1f} %")
     # save / reload: the image is instruction-shaped; mxfp6_export turns it into the OCP MXFP6 tensor any loader reads, and back without rounding
     elems, scales = petit_kernel.mxfp6_export(layer.image, n, k)
     state = {"weight.elems": elems.cpu(), "weight.scales": scales.cpu()}              # what a checkpoint would hold: 6.25 bits per weight

@@ -1242,6 +1242,49 @@ int petit_gemm_nvfp4_native_moe_invariant_host(void *c, const void *qa, const vo
                                                const int32_t *c_row_index, unsigned c_rows, int a_type, int act_format);
 
 /*
+ * Decode on the native image (no counterpart in the reference): 1 <= m <= 32 rows against a "petit-cdna4-nv6/1" image as a pure weight stream.
+ * The image -- from petit_nvfp4_native_image (NVFP4; global_scale is NVFP4's), petit_quantize_weights_mxfp6 or petit_mxfp6_native_images (MXFP6;
+ * global_scale NULL) -- is the FP6 operand of v_mfma_scale_f32_32x32x64_f8f6f4 as it stands, and the m <= 32 activation rows are the
+ * instruction's other operand: nothing is unpacked, and the weight stream and the MFMA count do not move with m.  The prefill kernels (petit_gemm_nvfp4_native) serve any
+ * m on 64-256 row tiles; this entry is the path for decode steps, in the same accuracy class, for models that exist only as an image.
+ *   a               16-bit [m][k] (a_is_quantized = 0: each lane quantises its own 32-k blocks in registers, bit for bit what
+ *                   petit_quantize_activations writes -- no quantiser launch, no scratch for it) or "petit-qact/1" bytes of (m, k, act_format)
+ *                   (a_is_quantized = 1; rows rotated by the quantiser work as they are: the kernel only reads them)
+ *   hints           a_type == c_type (BF16 / FP16: the type of a, c and the bias), b_type PETIT_DTYPE_FP4_E2M1
+ *   epilogue        NULL, or bias / activation as everywhere: the class's plain epilogue (one f32 multiply by the global scale when given,
+ *                   one f32 add of the bias when given, one rounding to a_type) or SiLU-mul / SwiGLU-OAI, where gate block b of 32 weight rows
+ *                   pairs with up block b + n / 64 and c is [m][n / 2]
+ *   k_parts         0: the library's P for (n, k) on this device -- petit_gemm_nvfp4_native_decode_parts(n, k): 1 when the ceil(n / 32) blocks
+ *                   fill the CUs, else the cut along K that fills them, at most 4 and never below 16 k-tiles per part.  >= 1: that many parts
+ *                   (tests, measurements).  A workgroup owns one block and one part; its W = min(4, (k / 128) / P, 16 / P) waves split the
+ *                   part's k-tiles and add their tiles in LDS in ascending order; P > 1 writes f32 slabs [P][m][n] that a second launch adds
+ *                   in ascending order before the epilogue.  W P <= 16, so the bound of "Native-FP4 kernels" ("<= 16 cross-wave /
+ *                   cross-slice f32 additions") holds unchanged.
+ *   workspace       petit_gemm_nvfp4_native_decode_workspace_bytes(m, n, k, k_parts) bytes, 256-byte aligned: P m n 4 for P > 1, 0 for P = 1
+ *                   (and for a call that would be refused)
+ * Numerics: the native class's -- given the quantised activations and the image's weights, the per-output bound of "Native-FP4 kernels".  The
+ *   accumulation order (W, P) is a function of (n, k, k_parts, the device) and is NOT promised: batch-invariant callers keep
+ *   petit_gemm_nvfp4_native_invariant.  Only rows < m and columns < n are written.
+ * Errors, all before any launch: PETIT_ERROR_BAD_ARGUMENT for null hints, c_type != a_type, a b_type that is not PETIT_DTYPE_FP4_E2M1, an a_type
+ *   that is not BF16 / FP16, an act_format outside {8, 6, 4}, an a_is_quantized outside {0, 1}, a non-zero `reserved`, an unknown activation;
+ *   PETIT_ERROR_PROBLEM_SHAPE for m == 0 or m > 32, for an (n, k) no image exists for (n % 16, k % 256, zero, 2^32 element bytes or more) and for
+ *   a gated activation with (n / 2) % 32 != 0; PETIT_ERROR_BAD_ARGUMENT for an explicit k_parts above 16 or above k / 128 (a part without a
+ *   k-tile), for a null c / a / image, an image or workspace that is not 256-byte aligned, c or a not 16-byte aligned; PETIT_ERROR_KERNEL_SHAPE
+ *   for a workspace below the query.  No allocation, no host sync, graph-capturable.
+ * Measured (profiles/native_decode.md, bf16, MXFP8, the four Llama-3-70B linears): with quantised input 0.81-1.00x the time of
+ *   petit_gemm_nvfp4_native's default pick on the same image at m = 1 and 0.92-1.37x at m = 32; with 16-bit input 1.2-2.0x SLOWER than it (every
+ *   workgroup re-reads and re-quantises the m rows of its K range), so hand over quantised activations where a producer can write them; 1.3-4.0x
+ *   the stream floor.
+ * Not here: a routed-expert form; a quantising or rotating epilogue; raw MXFP4 packed weights (they have
+ *   exact decode kernels); any sentinel or solution id that picks these kernels.
+ */
+int petit_gemm_nvfp4_native_decode(void *c, const void *a, const void *image, const float *global_scale, unsigned m, unsigned n, unsigned k,
+                                   const petit_solution_hints *hints, int act_format /* 8 | 6 | 4 */, int a_is_quantized,
+                                   const petit_epilogue *epilogue, unsigned k_parts, void *workspace, uint64_t workspace_bytes, void *stream);
+unsigned petit_gemm_nvfp4_native_decode_parts(unsigned n, unsigned k);
+uint64_t petit_gemm_nvfp4_native_decode_workspace_bytes(unsigned m, unsigned n, unsigned k, unsigned k_parts);
+
+/*
  * Native-class MoE launch (no counterpart in the reference): the routed-expert launch on the block-scaled MFMA, the accuracy class of
  * petit_gemm_mxfp4_native (activations quantised to MXFP8 / MXFP6 / MXFP4; the per-element bound is the native block's above).  Opt-in
  * like every native call: solution_id is a PETIT_SOLUTION_AUTO_NATIVE_* sentinel or an explicit native id that has a MoE form (the 128 x 256

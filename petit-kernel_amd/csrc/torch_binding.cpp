@@ -535,6 +535,44 @@ at::Tensor mul_nvfp4_native_invariant(PETIT_NV_NATIVE_INVARIANT_ARGS) {
                           global_scale ? (const float *)global_scale->data_ptr() : nullptr, size_m, size_n, size_k, bias, activation, nullptr);
 }
 
+// the decode GEMM on the native image (petit_gemm_nvfp4_native_decode): 1 <= size_m <= 32.  The argument checks and their texts are stated in
+// petit_kernel/ops.py (_check_native_decode), which petit_kernel/compiled.py runs in front of this op; what it checks itself is what keeps a
+// direct torch.ops call inside its tensors.
+#define PETIT_NV_NATIVE_DECODE_ARGS PETIT_NV_NATIVE_INVARIANT_ARGS, int64_t k_parts
+at::Tensor mul_nvfp4_native_decode(PETIT_NV_NATIVE_DECODE_ARGS) {
+    const at::ScalarType st = bf16 ? at::kBFloat16 : at::kHalf;
+    TORCH_CHECK(act_format == 8 || act_format == 6 || act_format == 4, "act_format must be 8, 6 or 4");
+    TORCH_CHECK(size_m >= 0 && size_n > 0 && size_k > 0 && size_k % 256 == 0 && k_parts >= 0 && A.is_cuda() && image.is_cuda() && A.is_contiguous() &&
+                    image.is_contiguous() && image.device() == A.device() &&
+                    (quantized ? A.scalar_type() == at::kByte && A.numel() == (int64_t)petit_quantized_activation_bytes((unsigned)size_m, (unsigned)size_k, (int)act_format)
+                               : A.scalar_type() == st && A.numel() == size_m * size_k) &&
+                    image.scalar_type() == at::kByte && image.numel() > 0 &&
+                    image.numel() == (int64_t)petit_nvfp4_native_image_bytes((unsigned)size_k, (unsigned)size_n) &&
+                    (!global_scale || (global_scale->is_cuda() && global_scale->device() == A.device() &&
+                                       global_scale->scalar_type() == at::kFloat && global_scale->numel() >= 1)),
+                "A [size_m, size_k] (or its quantised bytes) and the native image of [size_n, size_k] weights must be contiguous GPU tensors "
+                "on one device, global_scale a float32 tensor on it");
+    TORCH_CHECK(activation >= 0 && activation <= 2 && (!activation || size_n % 64 == 0), "activation must be 0, 1 or 2; gated forms need size_n % 64 == 0");
+    check_bias(bias, A, st, size_n, "bias must be a contiguous [size_n] tensor of A's dtype on A's device");
+    const c10::hip::HIPGuardMasqueradingAsCUDA guard(A.device());
+    at::Tensor c = at::empty({size_m, activation ? size_n / 2 : size_n}, A.options().dtype(st));
+    const int a_type = a_type_of(st);
+    const unsigned um = (unsigned)size_m, un = (unsigned)size_n, uk = (unsigned)size_k, parts = (unsigned)k_parts;
+    const petit_solution_hints hints{a_type, kCxxFp4, a_type, 0};
+    const petit_epilogue epi{bias.has_value() ? bias->data_ptr() : nullptr, (int32_t)activation, 0};
+    const uint64_t ws_bytes = petit_gemm_nvfp4_native_decode_workspace_bytes(um, un, uk, parts);
+    at::Tensor ws;
+    if (ws_bytes)
+        ws = at::empty({(int64_t)ws_bytes}, A.options().dtype(at::kByte));
+    const int rc = petit_gemm_nvfp4_native_decode(c.data_ptr(), A.data_ptr(), image.data_ptr(), global_scale ? (const float *)global_scale->data_ptr() : nullptr,
+                                                  um, un, uk, &hints, (int)act_format, quantized ? 1 : 0, (bias.has_value() || activation) ? &epi : nullptr,
+                                                  parts, ws_bytes ? ws.data_ptr() : nullptr, ws_bytes, stream_of(A));
+    TORCH_CHECK(rc != PETIT_ERROR_PROBLEM_SHAPE, "Incompatible problem shape (m=", size_m, ", n=", size_n, ", k=", size_k, ")");
+    TORCH_CHECK(rc != PETIT_ERROR_KERNEL_SHAPE, "No kernel implementation for solution_id=native-decode.");
+    TORCH_CHECK(rc == PETIT_OK, "mul_nvfp4_native_decode: ", petit_error_string(rc));
+    return c;
+}
+
 // routed-expert (MoE) launch: all experts in one call (include/petit_amd.h); the same checks and texts as petit_kernel/ops.py _mul_moe
 at::Tensor mul_a16_moe(bool mx, const at::Tensor &A, const at::Tensor &B, const at::Tensor &s, const at::Tensor &global_scales,
                        const at::Tensor &expert_offsets, int64_t size_m, int64_t size_n, int64_t size_k, int64_t num_experts, int64_t solution_id,
@@ -1143,6 +1181,9 @@ at::Tensor mul_mxfp4_native_moe_invariant_meta(PETIT_NATIVE_MOE_INVARIANT_ARGS) 
 at::Tensor mul_nvfp4_native_invariant_meta(PETIT_NV_NATIVE_INVARIANT_ARGS) {
     return at::empty({size_m, activation ? size_n / 2 : size_n}, A.options().dtype(bf16 ? at::kBFloat16 : at::kHalf));
 }
+at::Tensor mul_nvfp4_native_decode_meta(PETIT_NV_NATIVE_DECODE_ARGS) {
+    return at::empty({size_m, activation ? size_n / 2 : size_n}, A.options().dtype(bf16 ? at::kBFloat16 : at::kHalf));
+}
 at::Tensor mul_nvfp4_native_moe_invariant_meta(PETIT_NV_NATIVE_MOE_INVARIANT_ARGS) {
     return at::empty({c_rows < 0 ? m : c_rows, activation ? n / 2 : n}, A.options().dtype(bf16 ? at::kBFloat16 : at::kHalf));
 }
@@ -1283,6 +1324,8 @@ TORCH_LIBRARY(petit_kernel, m) {
           "Tensor? bias=None, int activation=0) -> Tensor");
     m.def("mul_nvfp4_native_invariant(Tensor A, Tensor image, Tensor? global_scale, int size_m, int size_n, int size_k, int act_format, "
           "bool quantized, bool bf16, Tensor? bias=None, int activation=0) -> Tensor");
+    m.def("mul_nvfp4_native_decode(Tensor A, Tensor image, Tensor? global_scale, int size_m, int size_n, int size_k, int act_format, "
+          "bool quantized, bool bf16, Tensor? bias=None, int activation=0, int k_parts=0) -> Tensor");
     m.def("mul_nvfp4_native_moe_invariant(Tensor A, Tensor images, Tensor global_scales, Tensor expert_offsets, int size_m, int size_n, "
           "int size_k, int num_experts, Tensor? a_row_index, Tensor? c_row_index, int c_rows, int act_format, bool quantized, bool bf16, "
           "Tensor? bias=None, int activation=0) -> Tensor");
@@ -1319,6 +1362,7 @@ TORCH_LIBRARY(petit_kernel, m) {
     m.impl("mul_mxfp4_a16_moe_indexed_out", &mul_mxfp4_a16_moe_indexed_out); \
     m.impl("mul_mxfp4_native_moe_invariant", &mul_mxfp4_native_moe_invariant); \
     m.impl("mul_nvfp4_native_invariant", &mul_nvfp4_native_invariant); \
+    m.impl("mul_nvfp4_native_decode", &mul_nvfp4_native_decode); \
     m.impl("mul_nvfp4_native_moe_invariant", &mul_nvfp4_native_moe_invariant); \
     m.impl("mul_nvfp4_a16_moe_invariant", &mul_nvfp4_a16_moe_invariant); \
     m.impl("mul_mxfp4_a16_moe_invariant", &mul_mxfp4_a16_moe_invariant); \
@@ -1364,6 +1408,7 @@ TORCH_LIBRARY_IMPL(petit_kernel, Meta, m) {
     m.impl("mul_mxfp4_a16_moe_indexed_out", &mul_a16_moe_indexed_out_meta);
     m.impl("mul_mxfp4_native_moe_invariant", &mul_mxfp4_native_moe_invariant_meta);
     m.impl("mul_nvfp4_native_invariant", &mul_nvfp4_native_invariant_meta);
+    m.impl("mul_nvfp4_native_decode", &mul_nvfp4_native_decode_meta);
     m.impl("mul_nvfp4_native_moe_invariant", &mul_nvfp4_native_moe_invariant_meta);
     m.impl("mul_nvfp4_a16_moe_invariant", &mul_a16_moe_invariant_meta);
     m.impl("mul_mxfp4_a16_moe_invariant", &mul_a16_moe_invariant_meta);

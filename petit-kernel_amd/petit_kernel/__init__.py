@@ -239,6 +239,25 @@ def mul_nvfp4_native_invariant(a, image: torch.Tensor, global_scale: torch.Tenso
     return _impl.mul_nvfp4_native_invariant(a, image, global_scale, size_m, size_n, size_k, fmt, bias, activation)
 
 
+def mul_nvfp4_native_decode(a, image: torch.Tensor, global_scale: torch.Tensor, size_m: int, size_n: int, size_k: int, fmt: str = "mxfp8",
+                            bias: torch.Tensor = None, activation: str = None, k_parts: int = 0) -> torch.Tensor:
+    # the decode GEMM on a native image (include/petit_amd.h "Decode on the native image"): 1 <= size_m <= 32 rows against the image of
+    # nvfp4_native_image (global_scale NVFP4's), quantize_mxfp6 or mxfp6_native_image (global_scale None) as a pure weight stream.  a: a 16-bit
+    # tensor (quantised in the kernel's registers) or QuantizedActivations of the same fmt.  Native-class numerics, accumulation order not
+    # promised (batch-invariant callers keep mul_nvfp4_native_invariant).  Opt-in (profiles/native_decode.md), no solution_id.
+    return _impl.mul_nvfp4_native_decode(a, image, global_scale, size_m, size_n, size_k, fmt, bias, activation, k_parts)
+
+
+def nvfp4_native_decode_parts(size_n: int, size_k: int) -> int:
+    # P, the parts along K of mul_nvfp4_native_decode(k_parts=0) on the current device: a function of (size_n, size_k, the CU count) alone
+    return ops.nvfp4_native_decode_parts(size_n, size_k)
+
+
+def nvfp4_native_decode_workspace_bytes(size_m: int, size_n: int, size_k: int, k_parts: int = 0) -> int:
+    # bytes of scratch the call allocates per call: P * m * n * 4 for P > 1 parts, 0 for P = 1
+    return ops.nvfp4_native_decode_workspace_bytes(size_m, size_n, size_k, k_parts)
+
+
 def mul_nvfp4_native_moe_invariant(a, images: torch.Tensor, global_scales: torch.Tensor, expert_offsets: torch.Tensor, size_m: int, size_n: int,
                                    size_k: int, num_experts: int, a_row_index: torch.Tensor = None, c_row_index: torch.Tensor = None,
                                    c_rows: int = None, fmt: str = "mxfp8", bias: torch.Tensor = None, activation: str = None) -> torch.Tensor:
@@ -477,6 +496,9 @@ __all__ = [
     "moe_invariant_workspace_bytes",
     "mul_mxfp4_native_moe_invariant",
     "mul_nvfp4_native_invariant",
+    "mul_nvfp4_native_decode",
+    "nvfp4_native_decode_parts",
+    "nvfp4_native_decode_workspace_bytes",
     "mul_nvfp4_native_moe_invariant",
     "native_moe_invariant_form",
     "native_moe_invariant_workspace_bytes",

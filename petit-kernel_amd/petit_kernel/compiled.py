@@ -21,6 +21,7 @@ from .ops import invariant_geometry, invariant_slabs, invariant_workspace_bytes 
 from .ops import moe_invariant_form, moe_invariant_workspace_bytes
 from .ops import _QFORMATS, _out_hadamard, native_invariant_slabs, native_invariant_workspace_bytes
 from .ops import native_moe_invariant_form, native_moe_invariant_workspace_bytes
+from .ops import _check_native_decode, nvfp4_native_decode_parts, nvfp4_native_decode_workspace_bytes
 
 LIB_PATH = Path(_lib.LIB_PATH).parent / "libpetit_torch.so"
 _loaded = False
@@ -197,6 +198,12 @@ def mul_nvfp4_native_invariant(A, image, global_scale, size_m, size_n, size_k, f
     a, dtype, quantized, act = _check_invariant(A, image, None, global_scale, size_m, size_n, size_k, bias, activation, "nv", fmt)[:4]
     return torch.ops.petit_kernel.mul_nvfp4_native_invariant(a, image, global_scale, int(size_m), int(size_n), int(size_k), _QFORMATS[fmt],
                                                              bool(quantized), dtype == torch.bfloat16, bias, act)
+
+
+def mul_nvfp4_native_decode(A, image, global_scale, size_m, size_n, size_k, fmt="mxfp8", bias=None, activation=None, k_parts=0):
+    a, dtype, quantized, act, k_parts = _check_native_decode(A, image, global_scale, size_m, size_n, size_k, fmt, bias, activation, k_parts)
+    return torch.ops.petit_kernel.mul_nvfp4_native_decode(a, image, global_scale, int(size_m), int(size_n), int(size_k), _QFORMATS[fmt],
+                                                          bool(quantized), dtype == torch.bfloat16, bias, act, k_parts)
 
 
 def mul_nvfp4_native_moe_invariant(A, images, global_scales, expert_offsets, size_m, size_n, size_k, num_experts, a_row_index=None,

@@ -1123,6 +1123,78 @@ def mul_nvfp4_native_invariant(A, image, global_scale, size_m, size_n, size_k, f
     return _mul_invariant(A, image, None, global_scale, size_m, size_n, size_k, bias, activation, "nv", fmt)
 
 
+# --- the decode GEMM on the native image (include/petit_amd.h "Decode on the native image") -------------------------------------------------
+
+def nvfp4_native_decode_parts(size_n: int, size_k: int) -> int:
+    """P, the number of parts along K that mul_nvfp4_native_decode(k_parts=0) cuts (size_n, size_k) into on the current device
+    (petit_gemm_nvfp4_native_decode_parts); 0 for a shape no native image exists for."""
+    return int(_lib.lib.petit_gemm_nvfp4_native_decode_parts(int(size_n), int(size_k)))
+
+
+def nvfp4_native_decode_workspace_bytes(size_m: int, size_n: int, size_k: int, k_parts: int = 0) -> int:
+    """Bytes of scratch mul_nvfp4_native_decode uses (petit_gemm_nvfp4_native_decode_workspace_bytes): P * m * n * 4 for P > 1 parts, 0 for
+    P = 1 and for a call that would be refused."""
+    return int(_lib.lib.petit_gemm_nvfp4_native_decode_workspace_bytes(int(size_m), int(size_n), int(size_k), int(k_parts)))
+
+
+def _check_native_decode(A, image, global_scale, size_m, size_n, size_k, fmt, bias, activation, k_parts):
+    """The argument checks of mul_nvfp4_native_decode, stated here for both operator layers (the texts of _check_invariant where the rule is
+    the same) -> (activation tensor, 16-bit dtype, a_is_quantized, activation code, k_parts)."""
+    _check(fmt in _QFORMATS, "fmt must be 'mxfp8', 'mxfp6' or 'mxfp4'")
+    quantized = isinstance(A, QuantizedActivations)
+    dtype = A.dtype
+    _check(dtype in (torch.bfloat16, torch.float16), "A must be bfloat16 or float16 (or QuantizedActivations of such a tensor).")
+    size_m, size_n, size_k, k_parts = int(size_m), int(size_n), int(size_k), int(k_parts)
+    if not (size_n > 0 and size_n % 16 == 0 and size_k > 0 and size_k % 256 == 0 and 1 <= size_m <= 32):
+        _check(False, f"Incompatible problem shape (m={size_m}, n={size_n}, k={size_k}): mul_nvfp4_native_decode needs n % 16 == 0, "
+                      "k % 256 == 0, 1 <= m <= 32")
+    _check(activation in _ACTIVATIONS, _ACTIVATION_RULE)
+    act = _ACTIVATIONS[activation]
+    _check(not act or size_n % 64 == 0, f"{activation} needs size_n % 64 == 0 here (gate / up halves of whole tile pairs), got {size_n}")
+    _check(0 <= k_parts <= 16 and k_parts <= size_k // 128, f"k_parts must be 0 (the library's choice) or 1 .. min(16, size_k / 128), got {k_parts}")
+    if quantized:
+        _check(A.fmt == fmt, f"quantised activations are {A.fmt}, the call says fmt={fmt!r}")
+        _check(A.m == size_m and A.k == size_k, f"quantised activations are [{A.m}, {A.k}], the call says [{size_m}, {size_k}]")
+        a = A.data
+        _check(a.dtype == torch.uint8 and a.is_contiguous() and a.numel() == int(_lib.lib.petit_quantized_activation_bytes(size_m, size_k, _QFORMATS[fmt])),
+               "quantised activations do not hold the bytes of their [m, k] and format")
+    else:
+        a = A
+        _check(a.is_contiguous() and a.numel() == size_m * size_k, "A must be a contiguous [size_m, size_k] tensor")
+    image_bytes = int(_lib.lib.petit_nvfp4_native_image_bytes(size_k, size_n))
+    _check(image.is_contiguous() and image.dtype == torch.uint8 and image.numel() == image_bytes and image_bytes > 0,
+           "image does not hold the native image of size_n x size_k NVFP4 weights")
+    if global_scale is not None:
+        _check(global_scale.dtype == torch.float32 and global_scale.numel() >= 1, "global_scale must be float32")
+    if bias is not None:
+        _check(bias.dtype == dtype and bias.is_contiguous() and bias.numel() == size_n and bias.device == a.device, _INVARIANT_BIAS_TEXT[False])
+    _check(a.is_cuda and image.is_cuda and (global_scale is None or global_scale.is_cuda), "all tensors must be on GPU")
+    _check(image.device == a.device and (global_scale is None or global_scale.device == a.device), "all tensors must be on A's device")
+    return a, dtype, int(quantized), act, k_parts
+
+
+def mul_nvfp4_native_decode(A, image, global_scale, size_m, size_n, size_k, fmt="mxfp8", bias=None, activation=None, k_parts=0) -> torch.Tensor:
+    """The decode GEMM on the native image (petit_gemm_nvfp4_native_decode, include/petit_amd.h "Decode on the native image"): 1 <= size_m <= 32
+    rows against `image` -- from nvfp4_native_image (global_scale NVFP4's), quantize_mxfp6 or mxfp6_native_image (global_scale None) -- as a
+    pure weight stream on the block-scaled MFMA, activations quantised to `fmt`.  A: a 16-bit [size_m, size_k] tensor (quantised in the
+    kernel's registers, no quantiser launch) or QuantizedActivations of the same fmt -- the same bits either way.  k_parts: 0 = the library's
+    cut along K (nvfp4_native_decode_parts), or an explicit count.  Native-class numerics, accumulation order not promised: batch-invariant
+    callers keep mul_nvfp4_native_invariant.  Opt-in; no solution_id."""
+    a, dtype, quantized, act, k_parts = _check_native_decode(A, image, global_scale, size_m, size_n, size_k, fmt, bias, activation, k_parts)
+    shape = (int(size_m), int(size_n), int(size_k))
+    out = torch.empty((shape[0], shape[1] // 2 if act else shape[1]), dtype=dtype, device=a.device)
+    hints = _hints("nv", dtype)
+    epi = _epilogue(bias, act, a.device, dtype, shape[1], _INVARIANT_BIAS_TEXT[False])
+    ws_bytes = int(_lib.lib.petit_gemm_nvfp4_native_decode_workspace_bytes(*shape, k_parts))
+    ws = _scratch(ws_bytes, a.device)
+    with torch.cuda.device(a.device):
+        err = _lib.lib.petit_gemm_nvfp4_native_decode(_ptr(out), _ptr(a), _ptr(image), _opt_ptr(global_scale), *shape, C.byref(hints),
+                                                      _QFORMATS[fmt], quantized, epi, k_parts, _opt_ptr(ws), ws_bytes, _stream(a))
+    if err:
+        _raise_gemm(err, "mul_nvfp4_native_decode", "native-decode", "m=%d, n=%d, k=%d" % shape)
+    return out
+
+
 def mul_nvfp4_native_moe_invariant(A, images, global_scales, expert_offsets, size_m, size_n, size_k, num_experts, a_row_index=None,
                                    c_row_index=None, c_rows=None, fmt="mxfp8", bias=None, activation=None) -> torch.Tensor:
     """mul_mxfp4_native_moe_invariant for NVFP4 experts (petit_gemm_nvfp4_native_moe_invariant): `images` from nvfp4_native_images (expert e's
