@@ -138,6 +138,12 @@ def main():
     assert torch.equal(transient.view(torch.int16), resident.view(torch.int16))
     err_n = (transient.double().cpu() - ref).pow(2).mean().sqrt() / ref.pow(2).mean().sqrt()
     print(f"fp4_moe_native(transient=True): equals the resident-image layer bit for bit; rms error / rms = {err_n:.2e} (native class)")
+    # a decode step on the resident images: decode=True runs gate_up and down as the routed-expert decode launches -- four launches, no
+    # quantiser and no scratch, only the experts this step routes to are streamed (the same accuracy class; profiles/native_moe_decode.md)
+    step = petit_kernel.fp4_moe_native(x[:4].to(dev), i13, None, gs13.to(dev), i2, None, gs2.to(dev), topk_w[:4].to(dev), ids_dev[:4], kind="nvfp4",
+                                       activations="mxfp8", decode=True)
+    err_d = (step.double().cpu() - ref[:4]).pow(2).mean().sqrt() / ref[:4].pow(2).mean().sqrt()
+    print(f"fp4_moe_native(decode=True): 4 tokens, rms error / rms = {err_d:.2e} (native class)")
 
 
 if __name__ == "__main__":

@@ -1275,14 +1275,54 @@ int petit_gemm_nvfp4_native_moe_invariant_host(void *c, const void *qa, const vo
  *   petit_gemm_nvfp4_native's default pick on the same image at m = 1 and 0.92-1.37x at m = 32; with 16-bit input 1.2-2.0x SLOWER than it (every
  *   workgroup re-reads and re-quantises the m rows of its K range), so hand over quantised activations where a producer can write them; 1.3-4.0x
  *   the stream floor.
- * Not here: a routed-expert form; a quantising or rotating epilogue; raw MXFP4 packed weights (they have
- *   exact decode kernels); any sentinel or solution id that picks these kernels.
+ * Not here: a quantising or rotating epilogue; raw MXFP4 packed weights (they have exact decode kernels); any sentinel or solution id that
+ *   picks these kernels.  The routed-expert form is "MoE decode on the native image" below.
  */
 int petit_gemm_nvfp4_native_decode(void *c, const void *a, const void *image, const float *global_scale, unsigned m, unsigned n, unsigned k,
                                    const petit_solution_hints *hints, int act_format /* 8 | 6 | 4 */, int a_is_quantized,
                                    const petit_epilogue *epilogue, unsigned k_parts, void *workspace, uint64_t workspace_bytes, void *stream);
 unsigned petit_gemm_nvfp4_native_decode_parts(unsigned n, unsigned k);
 uint64_t petit_gemm_nvfp4_native_decode_workspace_bytes(unsigned m, unsigned n, unsigned k, unsigned k_parts);
+
+/*
+ * MoE decode on the native image (no counterpart in the reference): the routed-expert form of "Decode on the native image".  A decode step
+ * puts 0-4 rows on each expert and none on most; this launch streams only the images of the experts that have rows, spreads a block's K over
+ * the waves of one workgroup, and runs nothing before itself: no quantiser launch, no scratch, no second launch.  With it a native MoE decode
+ * layer is align, gate_up, down and combine.
+ *   images          E images back to back, expert e's at byte e * petit_nvfp4_native_image_bytes(k, n), 256-byte aligned: what
+ *                   petit_gemm_native_moe and petit_gemm_nvfp4_native_moe_invariant read (petit_nvfp4_native_images, petit_mxfp6_native_images)
+ *   global_scales   [E] floats, or NULL: no multiply (MXFP6 images)
+ *   a               a_is_quantized = 0: 16-bit [a_rows][k]; grouped row r reads row a_row_index[r] (NULL: r), an index outside [0, a_rows) is a
+ *                   zero row, and each lane quantises its row's 32-k blocks in registers, bit for bit petit_quantize_activations.
+ *                   a_is_quantized = 1: the "petit-qact/1" bytes of the m GROUPED rows (petit_quantize_activations_rows); a_row_index must be
+ *                   NULL and a_rows is not read.
+ *   c               16-bit [c_rows][n] ([c_rows][n / 2] with a gated activation, gate block b of 32 weight rows paired with up block
+ *                   b + n / 64); grouped row r goes to row c_row_index[r] (NULL: r), an index outside [0, c_rows) stores nothing.  Only rows
+ *                   of an expert (below expert_offsets[E], after the clamp rule of petit_gemm_fp4_fp16_moe) and columns < n are written.
+ *   epilogue        bias is [E][n]; expert e uses global_scales[e] and bias + e n
+ * Geometry: grid = (n / 32, or n / 64 gated) x (ceil(m / 32) + min(E, m)) slots, sized from (m, E, n) alone; a slot maps to (expert, m-tile
+ *   of 32 grouped rows) on the device and a slot without a tile returns before any load.  A workgroup owns one block of one expert and one
+ *   m-tile; its W = min(4, k / 128) waves take contiguous runs of the k-tiles and add their tiles in LDS in ascending order.  No K split
+ *   across workgroups.  An expert with more than 32 rows streams its weights once per m-tile.
+ * Contract: every written row equals, bit for bit, row 0 of petit_gemm_nvfp4_native_decode(m = 1, k_parts = 1) on that row's 16-bit or
+ *   quantised input with its expert's image, global scale and bias: W is a function of k alone, and a row's result does not depend on its
+ *   position in the instruction's operand.
+ * Errors, all before any launch: PETIT_ERROR_BAD_ARGUMENT for null hints, c_type != a_type, a b_type that is not PETIT_DTYPE_FP4_E2M1, an a_type
+ *   that is not BF16 / FP16, an act_format outside {8, 6, 4}, an a_is_quantized outside {0, 1}, a non-zero `reserved`, an unknown activation,
+ *   a_is_quantized with an a_row_index; PETIT_ERROR_PROBLEM_SHAPE for num_experts == 0 or above PETIT_MOE_MAX_EXPERTS, n % 32 != 0, k % 256 != 0,
+ *   zero n or k, an image of 2^32 element bytes or more, m of 2^20 or more, a 16-bit a of more than 2^31 bytes, quantised bytes of 2^32 or more,
+ *   more than 65535 slots, a null index over a matrix of fewer than m rows, and a gated activation with (n / 2) % 32 != 0; m == 0 then returns
+ *   PETIT_OK and launches nothing; PETIT_ERROR_BAD_ARGUMENT for a null c / a / images / expert_offsets, images not 256-byte aligned, c or a
+ *   not 16-byte aligned, a bias not 8-byte aligned, global_scales / expert_offsets / indices not 4-byte aligned.  No allocation, no host sync,
+ *   graph-capturable.  No sentinel, solution id, pick or table reaches these kernels.
+ * Measured: profiles/native_moe_decode.md.
+ * Not here: a quantising or rotating gated epilogue; a K split across workgroups; a workgroup that keeps its quantised rows across several
+ *   n-blocks; packed MXFP4 experts and the transient form; any batch-invariance promise beyond the per-row identity above.
+ */
+int petit_gemm_nvfp4_native_moe_decode(void *c, const void *a, const void *images, const float *global_scales, const int32_t *expert_offsets,
+                                       unsigned num_experts, unsigned m, unsigned n, unsigned k, const int32_t *a_row_index, unsigned a_rows,
+                                       const int32_t *c_row_index, unsigned c_rows, const petit_solution_hints *hints,
+                                       int act_format /* 8 | 6 | 4 */, int a_is_quantized, const petit_epilogue *epilogue, void *stream);
 
 /*
  * Native-class MoE launch (no counterpart in the reference): the routed-expert launch on the block-scaled MFMA, the accuracy class of

@@ -30,7 +30,8 @@ if not os.environ.get("PETIT_AMD_NO_KERNARG_PRELOAD"):
 # per translation unit: new code is compiled without the packed-f32 VALU forms (v_pk_{add,mul,fma}_f32)
 _NO_PACKED_F32 = ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"]
 EXTRA_FLAGS = {"mxfp6_weights.hip": _NO_PACKED_F32, "native_image_readback.hip": _NO_PACKED_F32,
-               "gemm_native_decode_bf16.hip": _NO_PACKED_F32, "gemm_native_decode_f16.hip": _NO_PACKED_F32}
+               "gemm_native_decode_bf16.hip": _NO_PACKED_F32, "gemm_native_decode_f16.hip": _NO_PACKED_F32,
+               "gemm_native_moe_decode_bf16.hip": _NO_PACKED_F32, "gemm_native_moe_decode_f16.hip": _NO_PACKED_F32}
 
 
 def sources():

@@ -156,6 +156,22 @@ __device__ __forceinline__ void decode_quantize(const DecodeRawA &raw, const uns
     }
 }
 
+// The waves' tiles in red[wave][nb][register][lane] (gemm_native_decode_kloop.inc) added in ascending wave order: thread (u, lane) takes the
+// lane's registers 4 u .. 4 u + 3 of each block.
+template <int NB> __device__ __forceinline__ void decode_sum4(const float *red, const unsigned waves, const unsigned u, const unsigned lane, f32x4 (&sum)[NB]) {
+#pragma clang fp contract(off)
+#pragma unroll
+    for (int nb = 0; nb < NB; ++nb) {
+#pragma unroll
+        for (int i = 0; i < 4; ++i)
+            sum[nb][i] = red[(nb * 16u + 4u * u + i) * 64u + lane];
+        for (unsigned w = 1; w < waves; ++w) // ascending wave order
+#pragma unroll
+            for (int i = 0; i < 4; ++i)
+                sum[nb][i] = sum[nb][i] + red[((w * NB + nb) * 16u + 4u * u + i) * 64u + lane];
+    }
+}
+
 // AT: Bf16 / Fp16.  ACT: 8 / 6 / 4.  QIN: A is "petit-qact/1" bytes (else 16-bit).  GATED: two blocks per workgroup and a gated epilogue.
 // blockDim.x = 64 W (decode_waves), grid = (blocks, P).
 template <class AT, int ACT, bool QIN, bool GATED> __global__ __launch_bounds__(256) void native_decode_kernel(const NativeDecodeArgs p) {
@@ -188,133 +204,15 @@ template <class AT, int ACT, bool QIN, bool GATED> __global__ __launch_bounds__(
     const __amdgpu_buffer_rsrc_t a16_rsrc = make_rsrc(p.a, QIN ? 0u : p.m * p.k * 2u); // rows >= m: out of range -> zeros
     const unsigned a16_voff = r * p.k * 2u + h * (ACT == 8 ? 32u : 64u);
 
-    struct WStage {
-        u32x4 w[NB][3];
-        unsigned sc[NB][2];
-    };
-    struct AStage {
-        DecodeRawA raw;  // 16-bit input
-        u32x4 a[NA];     // quantised input
-        unsigned asc;
-    };
-    // (kt may run past the wave's last k-tile in both loads: such a stage is never used)
-    auto load_w = [&](WStage &st, unsigned kt) {
-        const unsigned rel = kt - kt0, sp = kt / ks, t = kt - sp * ks;
-        const unsigned s_voff = (sp * 64u + lane) * (2u * ks) + t;
-#pragma unroll
-        for (int nb = 0; nb < NB; ++nb) {
-#pragma unroll
-            for (int i = 0; i < 3; ++i)
-                st.w[nb][i] = buf_load16(w_rsrc[nb], rel * kNv6TileBytes + i * 1024u + lane * 16u, 0, kAuxNt);
-#pragma unroll
-            for (int q = 0; q < 2; ++q)
-                st.sc[nb][q] = (unsigned)__builtin_amdgcn_raw_buffer_load_b8(s_rsrc[nb], s_voff + q * ks, 0, kAuxDefault);
-        }
-    };
-    auto load_a = [&](AStage &st, unsigned kt) {
-        if constexpr (QIN) { // the k-tile's rows 0 .. m - 1 of every region; rows >= m are out of range -> zeros
-            const size_t tile_row = qact_tile_row(p.m, kt < ktiles ? kt : ktiles - 1u, 0);
-            const __amdgpu_buffer_rsrc_t a_rsrc = make_rsrc(qa + tile_row * kRowB, p.m * kRowB);
-            const __amdgpu_buffer_rsrc_t q_rsrc = make_rsrc(qs + tile_row * kQactScaleRowBytes, p.m * kQactScaleRowBytes);
-            const unsigned a_voff = r * kRowB + h * (ACT == 8 ? 32u : 16u);
-            if constexpr (ACT == 8) {
-                st.a[0] = buf_load16(a_rsrc, a_voff, 0, kAuxDefault), st.a[1] = buf_load16(a_rsrc, a_voff + 16u, 0, kAuxDefault);
-                st.a[2] = buf_load16(a_rsrc, a_voff + 64u, 0, kAuxDefault), st.a[3] = buf_load16(a_rsrc, a_voff + 80u, 0, kAuxDefault);
-            } else {
-                st.a[0] = buf_load16(a_rsrc, a_voff, 0, kAuxDefault), st.a[1] = buf_load16(a_rsrc, a_voff + 32u, 0, kAuxDefault);
-                if constexpr (ACT == 6) {
-                    const __amdgpu_buffer_rsrc_t h_rsrc = make_rsrc(qa_hi + tile_row * kQactHiRowBytes, p.m * kQactHiRowBytes);
-                    st.a[2] = buf_load16(h_rsrc, r * 32u + h * 16u, 0, kAuxDefault);
-                }
-            }
-            st.asc = __builtin_amdgcn_raw_buffer_load_b32(q_rsrc, r * 4u, 0, kAuxDefault);
-        } else {
-            const unsigned voff = a16_voff + kt * (kTileK * 2u);
-#pragma unroll
-            for (int q = 0; q < 2; ++q)
-#pragma unroll
-                for (int j = 0; j < 4; ++j) // MXFP8: units 2, 3 are the lane's 16 elements of the instruction's second block, 32 k further
-                    st.raw.u[q][j] = buf_load16(a16_rsrc, voff + q * 128u + (ACT == 8 ? (j >> 1) * 64u + (j & 1) * 16u : j * 16u), 0, kAuxDefault);
-        }
-    };
-
-    f32x16 acc[NB];
-#pragma unroll
-    for (int nb = 0; nb < NB; ++nb)
-#pragma unroll
-        for (int v = 0; v < 16; ++v)
-            acc[nb][v] = 0.f;
-    // two rings: the weights DW k-tiles deep (the same bytes in flight for one block or two), the activations DA (raw 16-bit rows are 32
-    // registers per k-tile and come from the L2)
-    constexpr int DW = kDecodeRing / NB, DA = QIN ? DW : 2;
-    WStage wring[DW];
-    AStage aring[DA];
-#pragma unroll
-    for (int d = 0; d < DW; ++d)
-        load_w(wring[d], kt0 + d);
-#pragma unroll
-    for (int d = 0; d < DA; ++d)
-        load_a(aring[d], kt0 + d);
-    for (unsigned kt = kt0; kt < kt1; ++kt) {
-        const WStage cur = wring[0];
-        const AStage cur_a = aring[0];
-#pragma unroll
-        for (int d = 0; d + 1 < DW; ++d)
-            wring[d] = wring[d + 1];
-#pragma unroll
-        for (int d = 0; d + 1 < DA; ++d)
-            aring[d] = aring[d + 1];
-        load_w(wring[DW - 1], kt + DW);
-        load_a(aring[DA - 1], kt + DA);
-        u32x4 a[NA];
-        unsigned a_sc[2];
-        if constexpr (QIN) {
-#pragma unroll
-            for (int i = 0; i < NA; ++i)
-                a[i] = cur_a.a[i];
-            a_sc[0] = (cur_a.asc >> (8u * h)) & 0xffu, a_sc[1] = (cur_a.asc >> (16u + 8u * h)) & 0xffu; // this lane's block is 2 q + h
-        } else {
-            decode_quantize<AT, ACT>(cur_a.raw, h, a, a_sc);
-        }
-#pragma unroll
-        for (int nb = 0; nb < NB; ++nb) {
-            i32x8 wop[2];
-            unsigned wsc[2];
-            native_inv_image_ops(cur.w[nb], cur.sc[nb], wop, wsc);
-            acc[nb] = native_inv_ktile<ACT, 6>(acc[nb], wop, wsc, a, a_sc[0], a_sc[1]);
-        }
-    }
-    // the accumulators leave the loop's basic block (mfma_join_pin, device_common.hpp)
-#pragma unroll
-    for (int nb = 0; nb < NB; ++nb)
-        mfma_join_pin(acc[nb]);
-    mfma_join_settle();
-#pragma unroll
-    for (int nb = 0; nb < NB; ++nb)
-        mfma_join_pin(acc[nb]);
-
-    // the waves' tiles meet in LDS: red[wave][nb][register][lane]
-#pragma unroll
-    for (int nb = 0; nb < NB; ++nb)
-#pragma unroll
-        for (int v = 0; v < 16; ++v)
-            red[((wave * NB + nb) * 16u + v) * 64u + lane] = acc[nb][v];
-    __syncthreads();
+    const unsigned qa_m = p.m, qa_m0 = 0u, qa_rows = p.m; // the m-tile is the whole image: rows >= m are out of range -> zeros
+    // the K loop: rings, MFMA, the waves' tiles into red (shared with the routed-expert form, gemm_native_moe_decode.hpp)
+#include "gemm_native_decode_kloop.inc"
     // lane (r, h) holds row r; register 4 u + i is column 16 (u >> 1) + 8 (u & 1) + 4 h + i of the block's 32
     if (r >= p.m)
         return;
     for (unsigned u = wave; u < 4u; u += waves) {
         f32x4 sum[NB];
-#pragma unroll
-        for (int nb = 0; nb < NB; ++nb) {
-#pragma unroll
-            for (int i = 0; i < 4; ++i)
-                sum[nb][i] = red[(nb * 16u + 4u * u + i) * 64u + lane];
-            for (unsigned w = 1; w < waves; ++w) // ascending wave order
-#pragma unroll
-                for (int i = 0; i < 4; ++i)
-                    sum[nb][i] = sum[nb][i] + red[((w * NB + nb) * 16u + 4u * u + i) * 64u + lane];
-        }
+        decode_sum4<NB>(red, waves, u, lane, sum);
         const unsigned nl = (u >> 1) * 16u + (u & 1u) * 8u + 4u * h;
         if (p.parts > 1u) {
 #pragma unroll

@@ -39,8 +39,8 @@ struct NativeInvariantMoeArgs {
     unsigned nblocks;         // workgroups along n per (slot[, slice])
 };
 
-// C row of grouped row `row`, or ~0u: the store is skipped
-__device__ __forceinline__ unsigned native_moe_c_row(const NativeInvariantMoeArgs &p, unsigned row) {
+// C row of grouped row `row`, or ~0u: the store is skipped (Args: a native MoE launch's, with c_idx and c_rows)
+template <class Args> __device__ __forceinline__ unsigned native_moe_c_row(const Args &p, unsigned row) {
     const unsigned c = p.c_idx ? (unsigned)p.c_idx[row] : row;
     return c < p.c_rows ? c : ~0u;
 }

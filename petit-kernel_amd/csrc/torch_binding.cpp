@@ -728,6 +728,49 @@ at::Tensor mul_nvfp4_native_moe_invariant(PETIT_NV_NATIVE_MOE_INVARIANT_ARGS) {
                           bias, activation, &r);
 }
 
+// the routed-expert decode GEMM on the experts' images (petit_gemm_nvfp4_native_moe_decode): the operands of mul_nvfp4_native_moe_invariant with
+// optional global scales; one launch, no workspace.  The texts are stated in petit_kernel/ops.py (_check_invariant), which
+// petit_kernel/compiled.py runs in front of this op; what it checks itself is what keeps a direct torch.ops call inside its tensors.
+#define PETIT_NV_NATIVE_MOE_DECODE_ARGS                                                                                                         \
+    const at::Tensor &A, const at::Tensor &images, const std::optional<at::Tensor> &gs, const at::Tensor &off, int64_t m, int64_t n, int64_t k, \
+        int64_t e, const std::optional<at::Tensor> &a_idx, const std::optional<at::Tensor> &c_idx, int64_t c_rows, int64_t act_format,          \
+        bool quantized, bool bf16, const std::optional<at::Tensor> &bias, int64_t activation
+at::Tensor mul_nvfp4_native_moe_decode(PETIT_NV_NATIVE_MOE_DECODE_ARGS) {
+    const at::ScalarType st = bf16 ? at::kBFloat16 : at::kHalf;
+    TORCH_CHECK(act_format == 8 || act_format == 6 || act_format == 4, "act_format must be 8, 6 or 4");
+    TORCH_CHECK(n > 0 && k > 0 && k % 256 == 0, "size_n and size_k must be positive, size_k % 256 == 0");
+    TORCH_CHECK(e >= 1 && e <= PETIT_MOE_MAX_EXPERTS, "num_experts must be in 1..", PETIT_MOE_MAX_EXPERTS, ", got ", e);
+    const int64_t per = (int64_t)petit_nvfp4_native_image_bytes((unsigned)k, (unsigned)n);
+    TORCH_CHECK(A.is_cuda() && images.is_cuda() && off.is_cuda() && A.is_contiguous() && images.is_contiguous() && images.device() == A.device() &&
+                    off.device() == A.device(),
+                "all tensors must be on GPU, on A's device");
+    TORCH_CHECK(images.scalar_type() == at::kByte && per > 0 && images.numel() == e * per, "images do not hold num_experts native images");
+    TORCH_CHECK(!gs || (gs->is_cuda() && gs->device() == A.device() && gs->scalar_type() == at::kFloat && gs->is_contiguous() && gs->numel() == e),
+                "global_scales must be a contiguous float32 [num_experts] tensor");
+    TORCH_CHECK(off.scalar_type() == at::kInt && off.is_contiguous() && off.numel() == e + 1,
+                "expert_offsets must be a contiguous int32 [num_experts + 1] tensor");
+    TORCH_CHECK(m >= 0 && (quantized ? A.scalar_type() == at::kByte && A.numel() == (int64_t)petit_quantized_activation_bytes((unsigned)m, (unsigned)k, (int)act_format) && !a_idx.has_value()
+                                     : A.scalar_type() == st && A.numel() % k == 0),
+                "A must be a contiguous [a_rows, size_k] tensor, or the quantised bytes of the size_m grouped rows without an a_row_index");
+    check_row_indices(a_idx, c_idx, A, m);
+    TORCH_CHECK(activation >= 0 && activation <= 2 && (!activation || n % 64 == 0), "activation must be 0, 1 or 2; gated forms need size_n % 64 == 0");
+    check_bias(bias, A, st, e * n, "bias must be a contiguous [num_experts, size_n] tensor of A's dtype on A's device");
+    const c10::hip::HIPGuardMasqueradingAsCUDA guard(A.device());
+    const int64_t rows = c_rows >= 0 ? c_rows : m, a_rows = quantized ? m : A.numel() / k;
+    at::Tensor c = at::empty({rows, activation ? n / 2 : n}, A.options().dtype(st));
+    const int a_type = a_type_of(st);
+    const petit_solution_hints hints{a_type, kCxxFp4, a_type, 0};
+    const petit_epilogue epi{bias.has_value() ? bias->data_ptr() : nullptr, (int32_t)activation, 0};
+    const int rc = petit_gemm_nvfp4_native_moe_decode(c.data_ptr(), A.data_ptr(), images.data_ptr(), gs ? (const float *)gs->data_ptr() : nullptr,
+                                                      (const int32_t *)off.data_ptr(), (unsigned)e, (unsigned)m, (unsigned)n, (unsigned)k,
+                                                      row_index_ptr(a_idx), (unsigned)a_rows, row_index_ptr(c_idx), (unsigned)rows, &hints,
+                                                      (int)act_format, quantized ? 1 : 0, (bias.has_value() || activation) ? &epi : nullptr, stream_of(A));
+    TORCH_CHECK(rc != PETIT_ERROR_PROBLEM_SHAPE, "Incompatible problem shape (m=", m, ", n=", n, ", k=", k, ", num_experts=", e, ", a_rows=", a_rows,
+                ", c_rows=", rows, ")");
+    TORCH_CHECK(rc == PETIT_OK, "mul_nvfp4_native_moe_decode: ", petit_error_string(rc));
+    return c;
+}
+
 // device routing (petit_moe_align / petit_moe_combine); the same checks and texts as petit_kernel/ops.py
 void check_topk_ids(const at::Tensor &ids, int64_t num_experts) {
     TORCH_CHECK(num_experts >= 1 && num_experts <= PETIT_MOE_MAX_EXPERTS, "num_experts must be in 1..", PETIT_MOE_MAX_EXPERTS, ", got ", num_experts);
@@ -1187,6 +1230,9 @@ at::Tensor mul_nvfp4_native_decode_meta(PETIT_NV_NATIVE_DECODE_ARGS) {
 at::Tensor mul_nvfp4_native_moe_invariant_meta(PETIT_NV_NATIVE_MOE_INVARIANT_ARGS) {
     return at::empty({c_rows < 0 ? m : c_rows, activation ? n / 2 : n}, A.options().dtype(bf16 ? at::kBFloat16 : at::kHalf));
 }
+at::Tensor mul_nvfp4_native_moe_decode_meta(PETIT_NV_NATIVE_MOE_DECODE_ARGS) {
+    return at::empty({c_rows < 0 ? m : c_rows, activation ? n / 2 : n}, A.options().dtype(bf16 ? at::kBFloat16 : at::kHalf));
+}
 at::Tensor mul_nvfp4_native_transient_meta(PETIT_NV_TRANSIENT_ARGS, int64_t out_hadamard) {
     check_out_hadamard(out_hadamard, out_format);
     return native_output(A, native_moe_dtype(A, a_format, a_type), size_m, size_m, activation ? size_n / 2 : size_n, out_format);
@@ -1329,6 +1375,9 @@ TORCH_LIBRARY(petit_kernel, m) {
     m.def("mul_nvfp4_native_moe_invariant(Tensor A, Tensor images, Tensor global_scales, Tensor expert_offsets, int size_m, int size_n, "
           "int size_k, int num_experts, Tensor? a_row_index, Tensor? c_row_index, int c_rows, int act_format, bool quantized, bool bf16, "
           "Tensor? bias=None, int activation=0) -> Tensor");
+    m.def("mul_nvfp4_native_moe_decode(Tensor A, Tensor images, Tensor? global_scales, Tensor expert_offsets, int size_m, int size_n, "
+          "int size_k, int num_experts, Tensor? a_row_index, Tensor? c_row_index, int c_rows, int act_format, bool quantized, bool bf16, "
+          "Tensor? bias=None, int activation=0) -> Tensor");
     m.def("mul_nvfp4_a16_moe_invariant(" PETIT_MOE_INVARIANT_SCHEMA ") -> Tensor");
     m.def("mul_mxfp4_a16_moe_invariant(" PETIT_MOE_INVARIANT_SCHEMA ") -> Tensor");
     m.def("mul_nvfp4_a16_moe_invariant_out(Tensor(a!) out, " PETIT_MOE_INVARIANT_SCHEMA ") -> ()");
@@ -1364,6 +1413,7 @@ TORCH_LIBRARY(petit_kernel, m) {
     m.impl("mul_nvfp4_native_invariant", &mul_nvfp4_native_invariant); \
     m.impl("mul_nvfp4_native_decode", &mul_nvfp4_native_decode); \
     m.impl("mul_nvfp4_native_moe_invariant", &mul_nvfp4_native_moe_invariant); \
+    m.impl("mul_nvfp4_native_moe_decode", &mul_nvfp4_native_moe_decode); \
     m.impl("mul_nvfp4_a16_moe_invariant", &mul_nvfp4_a16_moe_invariant); \
     m.impl("mul_mxfp4_a16_moe_invariant", &mul_mxfp4_a16_moe_invariant); \
     m.impl("mul_nvfp4_a16_moe_invariant_out", &mul_nvfp4_a16_moe_invariant_out); \
@@ -1410,6 +1460,7 @@ TORCH_LIBRARY_IMPL(petit_kernel, Meta, m) {
     m.impl("mul_nvfp4_native_invariant", &mul_nvfp4_native_invariant_meta);
     m.impl("mul_nvfp4_native_decode", &mul_nvfp4_native_decode_meta);
     m.impl("mul_nvfp4_native_moe_invariant", &mul_nvfp4_native_moe_invariant_meta);
+    m.impl("mul_nvfp4_native_moe_decode", &mul_nvfp4_native_moe_decode_meta);
     m.impl("mul_nvfp4_a16_moe_invariant", &mul_a16_moe_invariant_meta);
     m.impl("mul_mxfp4_a16_moe_invariant", &mul_a16_moe_invariant_meta);
     m.impl("mul_nvfp4_a16_moe_invariant_out", &mul_a16_moe_invariant_out_meta);

@@ -258,6 +258,18 @@ def nvfp4_native_decode_workspace_bytes(size_m: int, size_n: int, size_k: int, k
     return ops.nvfp4_native_decode_workspace_bytes(size_m, size_n, size_k, k_parts)
 
 
+def mul_nvfp4_native_moe_decode(a, images: torch.Tensor, global_scales: torch.Tensor, expert_offsets: torch.Tensor, size_m: int, size_n: int,
+                                size_k: int, num_experts: int, a_row_index: torch.Tensor = None, c_row_index: torch.Tensor = None,
+                                c_rows: int = None, fmt: str = "mxfp8", bias: torch.Tensor = None, activation: str = None) -> torch.Tensor:
+    # the routed-expert decode GEMM on the experts' images (include/petit_amd.h "MoE decode on the native image"): one launch, no quantiser,
+    # no scratch; only the experts that have rows are streamed.  a: a 16-bit [a_rows, size_k] tensor gathered through a_row_index, or
+    # QuantizedActivations of the size_m grouped rows.  global_scales: [num_experts] or None (MXFP6 images).  Every written row equals, bit for
+    # bit, mul_nvfp4_native_decode(size_m=1, k_parts=1) on its row with its expert's image, global scale and bias.
+    # Opt-in (profiles/native_moe_decode.md), no solution_id.
+    return _impl.mul_nvfp4_native_moe_decode(a, images, global_scales, expert_offsets, size_m, size_n, size_k, num_experts, a_row_index,
+                                             c_row_index, c_rows, fmt, bias, activation)
+
+
 def mul_nvfp4_native_moe_invariant(a, images: torch.Tensor, global_scales: torch.Tensor, expert_offsets: torch.Tensor, size_m: int, size_n: int,
                                    size_k: int, num_experts: int, a_row_index: torch.Tensor = None, c_row_index: torch.Tensor = None,
                                    c_rows: int = None, fmt: str = "mxfp8", bias: torch.Tensor = None, activation: str = None) -> torch.Tensor:
@@ -499,6 +511,7 @@ __all__ = [
     "mul_nvfp4_native_decode",
     "nvfp4_native_decode_parts",
     "nvfp4_native_decode_workspace_bytes",
+    "mul_nvfp4_native_moe_decode",
     "mul_nvfp4_native_moe_invariant",
     "native_moe_invariant_form",
     "native_moe_invariant_workspace_bytes",

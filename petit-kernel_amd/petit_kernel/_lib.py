@@ -179,6 +179,8 @@ _SIGNATURES = {
                                                  C.c_uint, C.c_void_p, C.c_uint64, C.c_void_p]),
     "petit_gemm_nvfp4_native_decode_parts": (C.c_uint, [C.c_uint, C.c_uint]),
     "petit_gemm_nvfp4_native_decode_workspace_bytes": (C.c_uint64, [C.c_uint] * 4),
+    "petit_gemm_nvfp4_native_moe_decode": (C.c_int, [C.c_void_p] * 5 + [C.c_uint] * 4 + [C.c_void_p, C.c_uint, C.c_void_p, C.c_uint] +
+                                           [C.POINTER(SolutionHints), C.c_int, C.c_int, C.POINTER(Epilogue), C.c_void_p]),
     "petit_gemm_mxfp4_native": (C.c_int, [C.c_void_p] * 5 + [C.c_uint] * 3 + [C.POINTER(SolutionHints), C.c_uint64, C.POINTER(Epilogue),
                                           C.POINTER(NativeArgs), C.c_void_p, C.c_uint64, C.c_void_p]),
     "petit_nvfp4_native_image_bytes": (C.c_uint64, [C.c_uint, C.c_uint]),

@@ -184,7 +184,7 @@ def fp4_moe_native(hidden: torch.Tensor, w13: torch.Tensor, s13, gs13: torch.Ten
                    topk_weights: torch.Tensor, topk_ids: torch.Tensor, kind: str = "mxfp4", activations: str = "mxfp8", *,
                    bias13: torch.Tensor = None, bias2: torch.Tensor = None, activation: str = "silu_mul", transient: bool = False,
                    norm_weight: torch.Tensor = None, norm_eps: float = 1e-6, norm_residual: torch.Tensor = None, norm_weight_offset: float = 0.0,
-                   norm_fmt: str = None, invariant: bool = False, hadamard: int = 0, norm_hadamard: int = 0):
+                   norm_fmt: str = None, invariant: bool = False, hadamard: int = 0, norm_hadamard: int = 0, decode: bool = False):
     """fp4_moe_fused's layer on the NATIVE class (the block-scaled MFMA, activations quantised to `activations`: 'mxfp8', 'mxfp6' or 'mxfp4';
     petit_gemm_native_moe -- a different accuracy class than the exact layers).  kind 'mxfp4': w13 / s13 / w2 / s2 as fp4_moe_fused; kind
     'nvfp4': w13 / w2 are the experts' MFMA-native images back to back (nvfp4_native_images) and s13 / s2 are None.  Five launches (seven
@@ -212,8 +212,23 @@ def fp4_moe_native(hidden: torch.Tensor, w13: torch.Tensor, s13, gs13: torch.Ten
     Every slot row is then a pure function of its token's hidden row and its expert's weights, and the combine adds a token's slots in slot
     order, in fp32, with one rounding: given the same topk_weights / topk_ids row, a token's output row has the same bits alone and inside
     any batch, at any position -- with the fused norm end too.  bfloat16 and float16 hidden states.  Opt-in and slower
-    (profiles/native_moe_invariant.md).  kind 'nvfp4' and transient=True raise: images are not on the invariant native entries."""
+    (profiles/native_moe_invariant.md).  kind 'nvfp4' and transient=True raise: images are not on the invariant native entries.
+
+    decode=True (kind 'nvfp4', resident images): the layer of a decode step, FOUR launches with no quantiser and no scratch -- the device
+    align, gate_up (mul_nvfp4_native_moe_decode) gathered through token_index with the gated activation writing 16-bit [m, I] grouped rows,
+    down reading those rows and scattering through sorted_pos, the combine or the fused norm end.  Both GEMMs quantise their rows in
+    registers and stream only the experts that have rows (profiles/native_moe_decode.md).  kind 'mxfp4', transient=True and invariant=True
+    raise (no image, or an entry of their own), and so does hadamard: this path has no rotating quantiser."""
     _check_native(kind, activation, activations, transient)
+    if decode:
+        if kind != "nvfp4":
+            raise RuntimeError("decode=True is for kind 'nvfp4': the decode launch reads the experts' native images, which MXFP4 experts do not have")
+        if transient:
+            raise RuntimeError("decode=True does not take transient=True: the decode launch reads resident images and builds none")
+        if invariant:
+            raise RuntimeError("decode=True does not take invariant=True: the batch-invariant layer has entries of its own")
+        if hadamard:
+            raise RuntimeError("decode=True does not take hadamard: the decode launch quantises in registers and has no rotating quantiser")
     if hadamard and invariant:
         raise RuntimeError("hadamard is not for invariant=True: the batch-invariant native entries have no quantising epilogue to rotate in")
     if invariant:
@@ -227,6 +242,9 @@ def fp4_moe_native(hidden: torch.Tensor, w13: torch.Tensor, s13, gs13: torch.Ten
     if invariant:
         return _native_invariant_after_align(hidden, w13, s13, gs13, w2, s2, gs2, w, ids, sorted_pos, offsets, token_index, activations, bias13,
                                              bias2, activation, norm)
+    if decode:
+        return _native_decode_after_align(hidden, w13, gs13, w2, gs2, w, ids, sorted_pos, offsets, token_index, activations, bias13, bias2,
+                                          activation, norm)
     return _native_after_align(hidden, w13, s13, gs13, w2, s2, gs2, w, ids, sorted_pos, offsets, token_index, kind, activations, bias13, bias2,
                                activation, transient, norm, hadamard)
 
@@ -256,6 +274,21 @@ def _native_invariant_after_align(hidden, w13, s13, gs13, w2, s2, gs2, w, ids, s
     y = mul_mxfp4_native_moe_invariant(h, w2, s2, gs2, offsets, m, n2, inter, E, c_row_index=sorted_pos, c_rows=m, fmt=activations,
                                        bias=bias2)                                   # [m, n2], (token, slot) order
     return _combine(y, w, ids, E, norm)
+
+
+def _native_decode_after_align(hidden, w13, gs13, w2, gs2, w, ids, sorted_pos, offsets, token_index, activations, bias13, bias2, activation,
+                               norm=None):
+    """fp4_moe_native(decode=True) after its align: the two decode launches on the experts' images, the combine."""
+    from . import mul_nvfp4_native_moe_decode
+    T, H = hidden.shape
+    E = gs13.numel()
+    m = T * ids.shape[1]
+    n13 = w13.numel() * 32 // (E * H * 25)                  # an image holds 25 / 32 bytes per weight (6.25 bits)
+    inter = n13 // 2
+    h = mul_nvfp4_native_moe_decode(hidden, w13, gs13, offsets, m, n13, H, E, a_row_index=token_index, fmt=activations, bias=bias13,
+                                    activation=activation)                           # [m, I], grouped order; unrouted (-1) rows are not written
+    y = mul_nvfp4_native_moe_decode(h, w2, gs2, offsets, m, H, inter, E, c_row_index=sorted_pos, c_rows=m, fmt=activations, bias=bias2)
+    return _combine(y, w, ids, E, norm)                                               # y: [m, H], (token, slot) order
 
 
 def _native_after_align(hidden, w13, s13, gs13, w2, s2, gs2, w, ids, sorted_pos, offsets, token_index, kind, activations, bias13, bias2,

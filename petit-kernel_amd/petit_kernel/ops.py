@@ -544,16 +544,17 @@ _INVARIANT_BIAS_TEXT = {False: "bias must be a contiguous [size_n] tensor of A's
                         True: "bias must be a contiguous [num_experts, size_n] tensor of A's dtype on A's device"}  # by `moe`
 
 
-def _check_invariant(A, B, s, global_scale, size_m, size_n, size_k, bias, activation, kind="mx", fmt=None, experts=None):
+def _check_invariant(A, B, s, global_scale, size_m, size_n, size_k, bias, activation, kind="mx", fmt=None, experts=None, decode=False):
     """The argument checks of the batch-invariant entries, stated here for both operator layers.  kind: the weight format, 'nv' / 'mx';
     fmt: the native class's activation format (None: the exact class), where kind 'nv' means B is the native image (nvfp4_native_image; a MoE
     call: num_experts images back to back) and s is None; experts: (expert_offsets, num_experts, a_row_index, c_row_index,
     c_rows, out) of a MoE call, whose global_scale is the [num_experts] tensor (None: a dense call).
     -> (activation tensor, 16-bit dtype, a_is_quantized, activation code, E, a_rows, c_rows), the last three None for a dense call.
     Value checks come first and device checks last, so that the texts can be read without a GPU.  The order within an entry decides which
-    text an ill-formed call gets, and is each entry's own."""
+    text an ill-formed call gets, and is each entry's own.  decode: the call is mul_nvfp4_native_moe_decode, whose operands are those of
+    mul_nvfp4_native_moe_invariant but for global_scales, which may be None (MXFP6 images), and a 16-bit A, which holds at most 2^31 bytes."""
     native, moe = fmt is not None, experts is not None
-    name = _invariant_name(kind, native, moe)
+    name = "mul_nvfp4_native_moe_decode" if decode else _invariant_name(kind, native, moe)
     if native:
         _check(fmt in _QFORMATS, "fmt must be 'mxfp8', 'mxfp6' or 'mxfp4'")
     quantized = native and isinstance(A, QuantizedActivations)
@@ -592,7 +593,7 @@ def _check_invariant(A, B, s, global_scale, size_m, size_n, size_k, bias, activa
         a = A
         _check(a.is_contiguous() and a.numel() % size_k == 0, "A must be a contiguous [a_rows, size_k] tensor")
         a_rows = a.numel() // size_k
-        if not native:
+        if not native or decode:
             _check(a_rows * size_k * 2 <= 1 << 31, f"{name}: A holds more than 2^31 bytes (a_rows={a_rows}, k={size_k})")
     else:
         a = A
@@ -613,7 +614,8 @@ def _check_invariant(A, B, s, global_scale, size_m, size_n, size_k, bias, activa
         _check(s.is_contiguous() and s.numel() * s.element_size() == count * size_n * size_k // group,
                f"s does not hold {what}size_n * size_k / {group} scales")
     if moe:
-        _check(global_scale.dtype == torch.float32 and global_scale.is_contiguous() and global_scale.numel() == E,
+        _check((decode and global_scale is None) or
+               (global_scale.dtype == torch.float32 and global_scale.is_contiguous() and global_scale.numel() == E),
                "global_scales must be a contiguous float32 [num_experts] tensor")
         _check(expert_offsets.dtype == torch.int32 and expert_offsets.is_contiguous() and expert_offsets.numel() == E + 1,
                "expert_offsets must be a contiguous int32 [num_experts + 1] tensor")
@@ -1202,6 +1204,29 @@ def mul_nvfp4_native_moe_invariant(A, images, global_scales, expert_offsets, siz
     its expert's image, global scale and bias."""
     return _mul_invariant(A, images, None, global_scales, size_m, size_n, size_k, bias, activation, "nv", fmt,
                           (expert_offsets, num_experts, a_row_index, c_row_index, c_rows, None))
+
+
+def mul_nvfp4_native_moe_decode(A, images, global_scales, expert_offsets, size_m, size_n, size_k, num_experts, a_row_index=None,
+                                c_row_index=None, c_rows=None, fmt="mxfp8", bias=None, activation=None) -> torch.Tensor:
+    """The routed-expert decode GEMM on the experts' native images (petit_gemm_nvfp4_native_moe_decode, include/petit_amd.h "MoE decode on
+    the native image"): the operands of mul_nvfp4_native_moe_invariant, global_scales None for MXFP6 images.  ONE launch -- a 16-bit A is
+    gathered through a_row_index and quantised in the kernel's registers, QuantizedActivations are the grouped rows -- that streams only the
+    experts with rows.  Every written row equals, bit for bit, mul_nvfp4_native_decode(size_m=1, k_parts=1) on its row and its expert's image,
+    global scale and bias.  Opt-in; no solution_id."""
+    a, dtype, quantized, act, E, a_rows, c_rows = _check_invariant(A, images, None, global_scales, size_m, size_n, size_k, bias, activation, "nv",
+                                                                   fmt, (expert_offsets, num_experts, a_row_index, c_row_index, c_rows, None), True)
+    shape = (int(size_m), int(size_n), int(size_k))
+    out = torch.empty((c_rows, shape[1] // 2 if act else shape[1]), dtype=dtype, device=a.device)
+    hints = _hints("nv", dtype)
+    epi = _epilogue(bias, act, a.device, dtype, E * shape[1], _INVARIANT_BIAS_TEXT[True])
+    with torch.cuda.device(a.device):
+        err = _lib.lib.petit_gemm_nvfp4_native_moe_decode(_ptr(out), _ptr(a), _ptr(images), _opt_ptr(global_scales), _ptr(expert_offsets), E,
+                                                          *shape, _opt_ptr(a_row_index), a_rows, _opt_ptr(c_row_index), c_rows, C.byref(hints),
+                                                          _QFORMATS[fmt], quantized, epi, _stream(a))
+    if err:
+        _raise_gemm(err, "mul_nvfp4_native_moe_decode", "native-moe-decode",
+                    "m=%d, n=%d, k=%d" % shape + f", num_experts={E}, a_rows={a_rows}, c_rows={c_rows}")
+    return out
 
 
 # --- grouped launch (include/petit_amd.h "Grouped launch"; no counterpart in the reference) ---------------------------------
